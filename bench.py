@@ -2,6 +2,7 @@
 """bench.py -- grasp hypotheses/sec of the MI355X-native HandSearch::findHands path (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4] [--normals det|rand50] [--shard samples|clouds] [--dist]
+                    [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no launcher around it starts its own N ranks (one process per GPU: python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...); under a launcher WORLD_SIZE must equal N.  `--dist` runs the
@@ -87,6 +88,31 @@ def cpu_baseline(sc, n_sub: int, normals_mode: int, classify: bool, svm):
             "host_cores": cores}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, recs: np.ndarray, keep) -> None:
+    """--dump-outputs: the hypothesis list of the last timed step -- what a caller of the path receives -- as one float64
+    array per record field (DIR/hyp_<field>.npy), and the SVM's verdicts for C3 (DIR/keep.npy).  The record's `epoch` is left
+    out: it stamps the call, not the result, and how many calls precede the timed steps depends on the clock spin.  A list
+    beyond DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its rows, their positions in DIR/hyp_row.npy."""
+    from agile_grasp_amd import binding
+
+    fields = [f for f in binding.HYP_DTYPE.names if f != "epoch"]
+    cols = {"hyp_" + f: recs[f].astype(np.float64) for f in fields}
+    if keep is not None:
+        cols["keep"] = keep.astype(np.float64)
+    row_bytes = 8 * (sum(int(np.prod(binding.HYP_DTYPE[f].shape)) for f in fields) + (keep is not None))
+    n_rows = (DUMP_LIMIT_BYTES - 128 * (len(cols) + 1)) // (row_bytes + 8)  # (a .npy header is 128 B)
+    if len(recs) > n_rows:
+        rows = np.sort(np.random.default_rng(0).choice(len(recs), n_rows, replace=False))
+        cols = {k: v[rows] for k, v in cols.items()}
+        cols["hyp_row"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in cols.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def free_port() -> int:
     import socket
 
@@ -160,7 +186,11 @@ def main():
                          "path as N > 1")
     ap.add_argument("--launch-only", action="store_true",
                     help="start the N ranks, let them meet (gloo, no GPU needed) and report who came; measures nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     launched = "WORLD_SIZE" in os.environ
     if args.gpus < 1:
@@ -341,6 +371,11 @@ def main():
             break
         seg[0] = 8 * S
     ctx.synchronize()  # raises if any neighbourhood overflowed the kernels' capacity
+    # --dump-outputs: the buffers as the last timed step left them (the untimed passes below write them again)
+    last = None
+    if args.dump_outputs:
+        last = {"out": out_t.clone(), "nout": nout_t.clone(), "keep": keep_t.clone(),
+                "gather": fb_gather.clone() if fb_gather is not None else None}
     # the spread of the figure above: five more intervals of the same K steps (the contract's `value` stays the ONE interval above)
     spread = timed_intervals(step, fence, args.steps, 5) if not distributed else None
     # HIP events on the launch stream bracket k_hand_sweep inside the timed region -- on every fourth step (profile level 3):
@@ -546,6 +581,17 @@ def main():
             res["cpu_baseline"] = cpu_baseline(sc, min(args.cpu_samples, S), normals_mode, classify, svm)
         elif not args.no_cpu_baseline:
             res["cpu_baseline"] = None
+        if last is not None:
+            if last["gather"] is None:  # one GPU, or the library's all-gather: the merged list is in out_t
+                n = int(last["nout"].item())
+                recs = np.frombuffer(last["out"][:n * 160].cpu().numpy().tobytes(), binding.HYP_DTYPE)
+                keep = last["keep"][:n].cpu().numpy() if classify else None
+            else:  # the torch fall-back exchange: the gathered segments, merged as k_shard_merge merges them
+                nb = sharding.segment_bytes(seg[0])
+                recs = sharding.merge_segments(last["gather"][:world * nb].cpu().numpy(), world, S * world if by_cloud else S,
+                                               seg[0], binding.HYP_DTYPE)
+                keep = None  # (each rank classified its own records only)
+            dump_outputs(args.dump_outputs, recs, keep)
         print(json.dumps(res))
     if hung:  # a rank is stuck in the extra measurement's collective: the line is out, leave without the tidy shutdown
         sys.stdout.flush()
