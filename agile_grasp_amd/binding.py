@@ -87,7 +87,8 @@ EXPORTS = [
     "agh_load_svm_model", "agh_get_learning_points", "agh_get_epoch", "agh_get_packed_images", "agh_classify_images", "agh_comm_rccl_origin",
     "agh_save_svm_file_ex", "agh_comm_unique_id", "agh_comm_init", "agh_comm_init_local", "agh_comm_destroy", "agh_comm_rank", "agh_comm_last_count", "agh_comm_last_exchange", "agh_comm_set_segment_records", "agh_comm_inject_fault",
     "agh_shard_slice", "agh_find_hands_sharded_device", "agh_find_hands_sharded", "agh_classify_sharded_device",
-    "agh_classify_sharded",
+    "agh_classify_sharded", "agh_default_plane_params", "agh_remove_plane", "agh_get_plane_inliers",
+    "agh_get_plane_candidates", "agh_plane_replay",
 ]
 
 
@@ -180,6 +181,27 @@ def draw_samples(n_points: int, n_samples: int, seed: int) -> np.ndarray:
     return out
 
 
+class AghPlaneParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("optimize", C.c_int32), ("distance_threshold", C.c_double),
+                ("probability", C.c_double), ("seed", C.c_uint32), ("cam_ids_by_position", C.c_int32)]
+
+
+class AghPlaneResult(C.Structure):
+    _fields_ = [("coefficients", C.c_float * 4), ("n_inliers", C.c_int64), ("n_remaining", C.c_int64),
+                ("iterations", C.c_int32), ("found", C.c_int32)]
+
+
+def plane_replay(counts, n_points: int, max_iterations: int = 100, probability: float = 0.99):
+    """RandomSampleConsensus::computeModel's termination over candidate inlier counts (agh_plane_replay, host only):
+    returns (chosen candidate or -1, iterations)."""
+    lib = load_library()
+    cnt = np.ascontiguousarray(counts, np.int64)
+    best, it = C.c_int32(0), C.c_int32(0)
+    lib.agh_plane_replay(_p(cnt, C.c_int64), C.c_int64(cnt.size), C.c_int64(n_points), C.c_int32(max_iterations),
+                         C.c_double(probability), C.byref(best), C.byref(it))
+    return best.value, it.value
+
+
 AGH_ERR_INVALID_ARGUMENT, AGH_ERR_HIP, AGH_ERR_CAPACITY, AGH_ERR_NO_CLOUD, AGH_ERR_NO_SVM, AGH_ERR_STATE = -1, -3, -4, -5, -6, -8
 AGH_ERR_RETRY = -9  # the context adapted its configuration to the input (include/agh.h): repeat the call
 
@@ -215,6 +237,8 @@ def load_library():
         lib.agh_destroy.restype = None
         lib.agh_default_params.restype = None
         lib.agh_shard_slice.restype = None
+        lib.agh_plane_replay.restype = None
+        lib.agh_default_plane_params.restype = None
         _LIB = lib
     return _LIB
 
@@ -417,6 +441,34 @@ class Context:
         return {"handles": handles[:res.n_handles].copy(), "inlier_idx": idx[:res.n_inlier_idx].copy(),
                 "hands": hands[:res.n_hands].copy(), "samples": sout[:S].copy(), "n_voxels": int(res.n_voxels),
                 "n_hypotheses": int(res.n_hypotheses)}
+
+    def remove_plane(self, max_iterations: int = 100, distance_threshold: float = 0.01, probability: float = 0.99,
+                     seed: int = 12345, optimize: bool = True, cam_ids_by_position: bool = True) -> dict:
+        """localizeHands' table-plane removal (agh_remove_plane): RANSAC plane on the current cloud, whose non-inliers
+        then become the context's cloud.  Returns the agh_plane_result fields as a dict."""
+        pp = AghPlaneParams(max_iterations, int(optimize), distance_threshold, probability, seed, int(cam_ids_by_position))
+        res = AghPlaneResult()
+        self._check(self.lib.agh_remove_plane(self._h, C.byref(pp), C.byref(res)))
+        self.n = res.n_remaining
+        return {"coefficients": np.array(res.coefficients[:], np.float32), "n_inliers": int(res.n_inliers),
+                "n_remaining": int(res.n_remaining), "iterations": int(res.iterations), "found": bool(res.found)}
+
+    def plane_inliers(self) -> np.ndarray:
+        """PCL's inliers->indices of the last remove_plane."""
+        k = self._check(self.lib.agh_get_plane_inliers(self._h, None, C.c_int64(0)))
+        idx = np.zeros(max(k, 1), np.int32)
+        k = self._check(self.lib.agh_get_plane_inliers(self._h, _p(idx, C.c_int32), C.c_int64(idx.size)))
+        return idx[:k]
+
+    def plane_candidates(self) -> dict:
+        """The candidate planes the last remove_plane drew, their samples and inlier counts (drawing order)."""
+        k = self._check(self.lib.agh_get_plane_candidates(self._h, None, None, None, C.c_int64(0)))
+        planes = np.zeros((max(k, 1), 4), np.float32)
+        samples = np.zeros((max(k, 1), 3), np.int32)
+        counts = np.zeros(max(k, 1), np.int64)
+        self._check(self.lib.agh_get_plane_candidates(self._h, _p(planes, C.c_float), _p(samples, C.c_int32),
+                                                      _p(counts, C.c_int64), C.c_int64(k)))
+        return {"planes": planes[:k], "samples": samples[:k], "counts": counts[:k]}
 
     def cloud(self):
         xyz = np.zeros((max(self.n, 1), 3), np.float32)

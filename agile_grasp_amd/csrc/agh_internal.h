@@ -150,6 +150,8 @@ struct LocalizeState
   int64_t staged_stride = 0, staged_n = 0;
 };
 
+struct PlaneState;
+
 struct Ctx
 {
   agh_params p;
@@ -206,6 +208,7 @@ struct Ctx
   hipEvent_t stage_done = nullptr;
   LocalizeState loc;
   int64_t raw_cap = 0;             // floats
+  PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
 
   // handle search (K5)
   agh_hypothesis* d_h_hands = nullptr;
@@ -464,6 +467,7 @@ int ensure_clouds(Ctx* c, int C);
 int ensure_draws(Ctx* c, int64_t count, hipStream_t st);
 int normals_pass(Ctx* c, int64_t p0, int64_t p1, hipStream_t st);
 void comm_release(Ctx* c);
+void plane_release(Ctx* c);
 
 // ---- device helpers ----
 #if defined(__HIPCC__)

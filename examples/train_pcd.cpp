@@ -1,12 +1,12 @@
 // train_pcd.cpp -- DEMO of the kept API, not part of the hot-path scope (the reference's CLI nodes are out
 // of scope; this file only shows that a caller written against Localization / Learning compiles and runs unchanged).
 // What src/nodes/train.cpp does, without ROS/boost: collect hands with antipodal labels from a set of two-view PCD captures,
-// train the SVM on their grasp images, write the OpenCV model file.  With the reference's default `uses_clustering = true`
-// the search returns nothing (the RANSAC table-plane removal is not built: INTEGRATION.md); this demo passes false.
+// train the SVM on their grasp images, write the OpenCV model file.  The reference passes uses_clustering = true (the RANSAC
+// table-plane removal before the search); this demo does so when its optional last argument [uses_clustering] is 1.
 //
 //   g++ -std=c++11 -O2 -Iinclude examples/train_pcd.cpp -o train_pcd -Lagile_grasp_amd/lib -lagile_grasp_hip
 //       -Wl,-rpath,$PWD/agile_grasp_amd/lib -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
-//   ./train_pcd <num_files> <pcd_dir/> <svm file out> [plots_hands] [num_samples] [num_threads]
+//   ./train_pcd <num_files> <pcd_dir/> <svm file out> [plots_hands] [num_samples] [num_threads] [uses_clustering]
 //
 // As in the node: num_files == 0 reads the capture names from <pcd_dir>files.txt, otherwise the captures are named
 // 0, 1, ...; capture X consists of <pcd_dir>X + "l_reg.pcd" and "r_reg.pcd"; <pcd_dir>workspace.txt (six numbers per line)
@@ -31,7 +31,8 @@ int main(int argc, char** argv)
   if (argc <= 3)
   {
     std::cout << "No PCD filenames given!\n";  // train.cpp:135
-    std::cout << "usage: " << argv[0] << " <num_files> <pcd_dir/> <svm file out> [plots_hands] [num_samples] [num_threads]\n";
+    std::cout << "usage: " << argv[0]
+              << " <num_files> <pcd_dir/> <svm file out> [plots_hands] [num_samples] [num_threads] [uses_clustering]\n";
     return -1;
   }
   const int num_files = std::atoi(argv[1]);
@@ -71,6 +72,7 @@ int main(int argc, char** argv)
   }
   const int num_samples = argc > 5 ? std::atoi(argv[5]) : 1000;
   const int num_threads = argc > 6 ? std::atoi(argv[6]) : 4;
+  const bool uses_clustering = argc > 7 && std::atoi(argv[7]) != 0;  // train.cpp:115 passes true
   // camera poses of the two-camera Baxter setup (train.cpp:80-93): base_tf * sqrt_tf^-1 and base_tf * sqrt_tf; only
   // the translations enter the search
   Matrix4d cam_left, cam_right;
@@ -103,10 +105,10 @@ int main(int argc, char** argv)
     for (int k = 0; k < 6; k++)
       ws((std::size_t) k) = workspace_mat[i][(std::size_t) k];
     loc.setWorkspace(ws);
-    // src/nodes/train.cpp:115 passes uses_clustering = true (RANSAC table-plane removal, pcl::SACSegmentation).  That step
-    // is not part of this build -- asking for it returns an empty list with an error -- so this example expects clouds
-    // whose table plane has been removed already (or workspaces that exclude it) and passes false.
-    std::vector<GraspHypothesis> hands = loc.localizeHands(files[i] + "l_reg.pcd", files[i] + "r_reg.pcd", true, false);
+    // src/nodes/train.cpp:115 passes uses_clustering = true: the table plane is removed (RANSAC, as pcl::SACSegmentation)
+    // and the hands come from the objects only.  Without the [uses_clustering] argument this demo keeps the table (false).
+    std::vector<GraspHypothesis> hands =
+      loc.localizeHands(files[i] + "l_reg.pcd", files[i] + "r_reg.pcd", true, uses_clustering);
     hand_list.insert(hand_list.end(), hands.begin(), hands.end());
     hand_list_sizes[i] = (int) hand_list.size();
     std::cout << i << ") # hands: " << hands.size() << std::endl;

@@ -255,6 +255,46 @@ int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, 
 /* The context's current cloud: packed xyz (3 floats per point) and camera ids; returns the number of points. */
 int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap);
 
+/* Table-plane removal of Localization::localizeHands(..., uses_clustering = true) (localization.cpp:51-98):
+ * pcl::SACSegmentation with SACMODEL_PLANE / SAC_RANSAC, then pcl::ExtractIndices with setNegative(true).
+ * agh_remove_plane works on the context's current single cloud (agh_set_cloud* or agh_preprocess*) and replaces it with
+ * the points that are not inliers of the plane, in their order (the grid build stays queued, as after agh_set_cloud).
+ * The restated algorithm (candidate draws, scoring, termination, refit) is in DESIGN.md, "Table-plane removal".
+ * AGH_ERR_STATE without a cloud, with a batch of several clouds bound, or between agh_localize_begin and _end.
+ * Fewer than 3 points or no sample that passes: found = 0 and the cloud is left as it was (not an error). */
+typedef struct agh_plane_params
+{
+  int32_t max_iterations;       /* 100 (setMaxIterations); 0 .. 1023 */
+  int32_t optimize;             /* 1 (setOptimizeCoefficients): least-squares refit of the plane, then reselection */
+  double distance_threshold;    /* 0.01 (setDistanceThreshold) */
+  double probability;           /* 0.99 (PCL's default) */
+  uint32_t seed;                /* 12345 (PCL's fixed seed of boost::mt19937) */
+  int32_t cam_ids_by_position;  /* 1: the kept point i keeps the camera id of point i of the unsegmented cloud -- the
+                                   reference's behaviour (it builds cluster_cam_source but searches with pts_cam_source);
+                                   0: every kept point keeps its own camera id */
+} agh_plane_params;
+typedef struct agh_plane_result
+{
+  float coefficients[4];  /* a, b, c, d of a x + b y + c z + d = 0 (refined if optimize and >= 4 inliers) */
+  int64_t n_inliers;      /* points removed (PCL's inliers->indices.size()) */
+  int64_t n_remaining;    /* points kept: the new cloud's size */
+  int32_t iterations;     /* RANSAC iterations (candidates scored) */
+  int32_t found;          /* 1 if a model was chosen */
+} agh_plane_result;
+void agh_default_plane_params(agh_plane_params* p);
+int agh_remove_plane(agh_ctx* ctx, const agh_plane_params* pp, agh_plane_result* result);
+/* The inliers of the last agh_remove_plane (PCL's inliers->indices, ascending positions in the cloud it ran on); returns
+ * their number (AGH_ERR_CAPACITY if it exceeds cap; idx may be NULL to ask for the number). */
+int agh_get_plane_inliers(agh_ctx* ctx, int32_t* idx, int64_t cap);
+/* Introspection for parity tests: the candidate planes the last agh_remove_plane drew (planes: 4 floats each, samples: 3
+ * indices each, counts: points within the threshold), in drawing order; returns their number.  Candidates beyond the
+ * ones the termination rule let RANSAC score are drawn and scored all the same (they cannot change the earlier ones). */
+int agh_get_plane_candidates(agh_ctx* ctx, float* planes, int32_t* samples, int64_t* counts, int64_t cap);
+/* RandomSampleConsensus::computeModel's termination rule replayed over the inlier counts of candidates 0 .. n - 1 of N
+ * points: *best = the candidate chosen (-1 if none), *iterations = candidates scored.  Host-only, needs no device. */
+void agh_plane_replay(const int64_t* counts, int64_t n, int64_t n_points, int32_t max_iterations, double probability,
+  int32_t* best, int32_t* iterations);
+
 /* HandSearch::findHands for explicit sample indices.  out receives <= 8*n_samples records, sample-major and
  * orientation-ascending (the reference's concatenation order, hand_search.cpp:194-200).  The host variant stages the sample
  * list in pinned memory of the context, the concatenation kernel writes count, flags and records into pinned memory as well,

@@ -275,6 +275,45 @@ public:
     return true;
   }
 
+  /** The table-plane removal of localization.cpp:51-98 (pcl::SACSegmentation, RANSAC plane, then ExtractIndices with
+   *  setNegative(true)) on the cloud the context holds (after preprocess): agh_remove_plane with the reference's settings.
+   *  The non-planar points become the searched cloud; a host copy is returned.  As in the reference, the search then gives
+   *  kept point i the camera id of point i of the UNSEGMENTED cloud (localization.cpp:88-94 builds cluster_cam_source but
+   *  never uses it).  @return false (after printing) on error; result.found == 0 when no model was found */
+  bool removePlane(agh_plane_result& result, PointCloud::Ptr& cloud_out, VectorXi& pts_cam_source_out)
+  {
+    if (!ensureContext())
+      return false;
+    agh_plane_params pp;
+    agh_default_plane_params(&pp);  // setMaxIterations(100), setDistanceThreshold(0.01), PCL's seed / probability
+    pp.cam_ids_by_position = 1;
+    if (agh_remove_plane(ctx_, &pp, &result) != AGH_OK)
+    {
+      fail("agh_remove_plane");
+      return false;
+    }
+    const std::int64_t m = result.n_remaining;
+    std::vector<float> xyz(3 * (std::size_t) m + 3);
+    std::vector<std::int32_t> cam((std::size_t) m + 1);
+    if (agh_get_cloud(ctx_, xyz.data(), cam.data(), m) < 0)
+    {
+      fail("agh_get_cloud");
+      return false;
+    }
+    cloud_out.reset(new PointCloud);
+    cloud_out->points.resize((std::size_t) m);
+    pts_cam_source_out = VectorXi((std::size_t) m);
+    for (std::int64_t i = 0; i < m; i++)
+    {
+      cloud_out->points[(std::size_t) i].x = xyz[3 * (std::size_t) i];
+      cloud_out->points[(std::size_t) i].y = xyz[3 * (std::size_t) i + 1];
+      cloud_out->points[(std::size_t) i].z = xyz[3 * (std::size_t) i + 2];
+      pts_cam_source_out((std::size_t) i) = cam[(std::size_t) i];
+    }
+    searched_n_ = m;
+    return true;
+  }
+
   /** The online chain of grasp_localizer.cpp:95-103 -- preprocessing, search, Learning::classify, HandleSearch -- as ONE device
    *  call with one synchronisation (agh_localize): the raw capture goes in, the hands the classifier kept, the handles and
    *  their inlier lists come out as records.  indices empty: num_samples indices are drawn ON THE DEVICE (one per stratum of

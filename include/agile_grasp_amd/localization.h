@@ -5,9 +5,9 @@
 // svm_filename), findHandles(hand_list, min_inliers, min_length), filterHands.  The preprocessing that precedes the hot
 // path (NaN removal, workspace box, per-camera 3 mm voxelisation: localization.cpp:25-45, 216-355; its output ORDER
 // defines the point indices the search works on) runs on the GPU as well (agh_preprocess).
-// Not carried over: the RANSAC table-plane removal behind uses_clustering (localization.cpp:51-98,
-// pcl::SACSegmentation; training path only) -- localizeHands(..., uses_clustering = true) prints an error and returns an
-// empty list -- and the Plot members.
+// uses_clustering = true removes the table plane before the search as localization.cpp:51-98 does (pcl::SACSegmentation's
+// RANSAC restated on the GPU: agh_remove_plane); explicit indices together with it are refused (see localizeHands).
+// Not carried over: the Plot members.
 #ifndef AGILE_GRASP_AMD_LOCALIZATION_H
 #define AGILE_GRASP_AMD_LOCALIZATION_H
 
@@ -117,13 +117,13 @@ public:
     // localization.cpp:17-45 on the GPU (agh_preprocess): camera id = (position >= size_left), removal of non-finite
     // points WITHOUT re-indexing the camera ids (the reference's behaviour), workspace box, per-camera 3 mm voxels in
     // lexicographic order.
-    if (uses_clustering)
+    if (uses_clustering && !indices.empty())
     {
-      // localization.cpp:51-98 removes the table plane with pcl::SACSegmentation (RANSAC) before the search; that step
-      // is not part of this build.  Searching the unsegmented cloud instead would label hands on the table and build a
-      // different training set while returning normally, so the request fails like the reference's other errors do.
-      std::cout << " Error: uses_clustering (table-plane removal, pcl::SACSegmentation) is not available in this build; "
-                   "remove the plane before localizeHands or pass uses_clustering = false\n";
+      // Explicit indices would address the cloud left after the table-plane removal, which the caller never sees (the
+      // reference reads out of range once an index passes its size), so the combination fails like the reference's
+      // other errors do.
+      std::cout << " Error: uses_clustering with explicit indices is not supported: they would index the cloud left after "
+                   "the table-plane removal; pass empty indices (samples drawn over that cloud) or uses_clustering = false\n";
       return hand_list;
     }
     std::cout << "Generating camera sources for " << cloud_in->size() << " points ...\n";
@@ -135,6 +135,33 @@ public:
       return hand_list;
     std::cout << " Created " << voxels->points.size() << " voxels\n";
     remove_nan_in_place(*cloud_in);  // localization.cpp:27 filters the caller's cloud in place
+    if (uses_clustering)
+    {
+      // localization.cpp:51-98: the largest plane (the table) goes, the search runs on the rest
+      std::cout << "Finding point cloud clusters ... \n";
+      agh_plane_result plane;
+      PointCloud::Ptr cluster;
+      VectorXi cluster_cam;
+      if (!search_->removePlane(plane, cluster, cluster_cam))
+        return hand_list;
+      if (!plane.found || plane.n_inliers == 0)
+      {
+        std::cout << " Could not estimate a planar model for the given dataset." << std::endl;
+        return hand_list;
+      }
+      std::cout << " PointCloud representing the planar component: " << plane.n_inliers << " data points." << std::endl;
+      std::cout << " PointCloud representing the non-planar component: " << plane.n_remaining << " data points." << std::endl;
+      last_cloud_ = cluster;  // (cloud_plot, localization.cpp:95)
+      last_cam_ = cluster_cam;
+      if (plane.n_remaining == 0)
+      {
+        // the reference would go on searching an empty cloud
+        std::cout << " No points left after removing the plane\n";
+        return hand_list;
+      }
+      voxels = cluster;
+      pts_cam_source = cluster_cam;
+    }
     hand_list = search_->findHandsInSearchedCloud(indices, calculates_antipodal);
     if (filters_boundaries_)
     {
