@@ -13,6 +13,8 @@ namespace agh
 {
 
 constexpr int kBboxBlocks = 128;   // work-groups of k_bbox per cloud (one slot of six extrema each)
+constexpr int kCountBlocks = 2048; // most work-groups of k_cell_count per cloud (one slot of six extrema each)
+constexpr int kGridMargin = 2;     // cells of padding on every face of a kept grid descriptor (grid.hip, desc_next)
 constexpr int kCellCap = 1 << 21;  // cells in the uniform grid table (8 MiB of int32)
 constexpr int kCellStride = kCellCap + 4;  // entries of one cloud's cell table (kCellCap + 1 used; 16-byte aligned tables)
 constexpr int kMaxRows = 128;      // (y,z) cell rows one ball query may touch
@@ -32,7 +34,7 @@ struct GridDesc
   double inv_cell;
   int dim[3];
   int ncell;
-  unsigned done;     // (unused since k_cell_count reduces k_bbox's slots itself)
+  unsigned open;     // faces whose border layer holds points outside the box: bit 2a = low face of axis a, 2a + 1 = high face
   unsigned ticket;   // tile tickets of k_cell_scan (reset by the holder of the last one)
 };
 
@@ -233,8 +235,15 @@ struct Ctx
                             // the voxelised cloud's; the true count is d_cloud_off[1], written by the voxeliser
   int* d_cloud_off = nullptr;       // kMaxClouds + 1
   int32_t* d_scloud = nullptr;      // s_cap: cloud of every sample of the last call (written by k_taubin_moments)
-  GridDesc* d_desc = nullptr;       // clouds_cap
+  GridDesc* d_desc = nullptr;       // clouds_cap: the descriptors of the last build (what the searches read)
+  GridDesc* d_desc_next = nullptr;  // clouds_cap: the descriptors the next build keeps (decided on the device by k_cell_scan)
   float* d_bbox_part = nullptr;     // clouds_cap x kBboxBlocks x 6 partial extrema of k_bbox
+  float* d_count_part = nullptr;    // clouds_cap x kCountBlocks x 6 partial extrema of k_cell_count
+  unsigned* d_grid_miss = nullptr;  // builds of a cloud that had points outside its kept descriptor
+  bool grid_miss_zeroed = false;
+  bool grid_force_cold = false;     // AGH_GRID_COLD=1: every build takes the k_bbox path (A/B measurement)
+  int grid_key_clouds = 0;          // clouds of the last build: another number of them means a cold build
+  int64_t grid_builds = 0, grid_cold_builds = 0;
   int* d_cell_start = nullptr;      // clouds_cap x kCellStride
   int* d_cell_count = nullptr;      // clouds_cap x kCellCap
   int* d_block_sums = nullptr;
@@ -632,10 +641,24 @@ __device__ __forceinline__ void build_rows(const GridView& gv, float qx, float q
       // (t / ny for ny <= 9, t < 128, without the ~40-instruction integer division: exact in float)
       const int tq = (int) (((float) t + 0.5f) * (1.0f / (float) ny));
       const int cy = ly + (t - tq * ny), cz = lz + tq;
-      // distance from q to the row's (y,z) slab; rows that cannot touch the ball are skipped
+      // distance from q to the row's (y,z) slab; rows that cannot touch the ball are skipped.  A border row or layer whose
+      // face is open (points outside the descriptor's box, clamped into it: a kept descriptor that missed the cloud) reaches
+      // to infinity on its outer side.
       const double y0 = g.mn[1] + cy * g.cell, z0 = g.mn[2] + cz * g.cell;
-      const double dy = fmax(fmax(y0 - (double) qy, (double) qy - (y0 + g.cell)), 0.0);
-      const double dz = fmax(fmax(z0 - (double) qz, (double) qz - (z0 + g.cell)), 0.0);
+      double ylo = y0, yhi = y0 + g.cell, zlo = z0, zhi = z0 + g.cell;
+      bool open_row = false;
+      if (g.open)  // (uniform: only after a build that missed)
+      {
+        const bool oy0 = cy == 0 && (g.open & 4u), oy1 = cy == g.dim[1] - 1 && (g.open & 8u);
+        const bool oz0 = cz == 0 && (g.open & 16u), oz1 = cz == g.dim[2] - 1 && (g.open & 32u);
+        ylo = oy0 ? -INFINITY : ylo;
+        yhi = oy1 ? INFINITY : yhi;
+        zlo = oz0 ? -INFINITY : zlo;
+        zhi = oz1 ? INFINITY : zhi;
+        open_row = oy0 | oy1 | oz0 | oz1;
+      }
+      const double dy = fmax(fmax(ylo - (double) qy, (double) qy - yhi), 0.0);
+      const double dz = fmax(fmax(zlo - (double) qz, (double) qz - zhi), 0.0);
       int b = 0, len = 0;
       const double rem = rpad * rpad - (dy * dy + dz * dz);
       if (rem >= 0.0)
@@ -646,7 +669,7 @@ __device__ __forceinline__ void build_rows(const GridView& gv, float qx, float q
         const double xr = sqrt(rem);
         double xlo = (double) qx - xr, xhi = (double) qx + xr;
         bool keep = true;
-        if (SLAB)
+        if (SLAB && !open_row)  // (an open row is not clipped to the slab: its (y, z) extent is unbounded)
         {
           // a_y (y - qy) + a_z (z - qz) over the row's cell lies in [L, U]; a point passes only if a_x (x - qx) + that is
           // inside (-hh, hh), i.e. a_x (x - qx) in (-hh - U, hh - L)

@@ -272,7 +272,10 @@ int ensure_clouds(Ctx* c, int C)
   int rc;
   if ((rc = dev_alloc(c, &c->d_desc, (size_t) C)) || (rc = dev_alloc(c, &c->d_cell_start, (size_t) C * (size_t) kCellStride)) ||
       (rc = dev_alloc(c, &c->d_cell_count, (size_t) C * kCellCap)) || (rc = dev_alloc(c, &c->d_bbox_part, (size_t) C * kBboxBlocks * 6)) ||
-      (rc = dev_alloc(c, &c->d_tile_state, (size_t) C * (kCellCap / 1024))))
+      (rc = dev_alloc(c, &c->d_tile_state, (size_t) C * (kCellCap / 1024))) || (rc = dev_alloc(c, &c->d_desc_next, (size_t) C)) ||
+      (rc = dev_alloc(c, &c->d_count_part, (size_t) C * kCountBlocks * 6)))
+    return rc;
+  if (!c->d_grid_miss && (rc = dev_alloc(c, &c->d_grid_miss, 1)))  // (one counter for the context's life)
     return rc;
   c->clouds_cap = C;
   c->grid_clean = false;  // fresh tables: the next build resets them
@@ -451,6 +454,8 @@ int agh_create(const agh_params* p, agh_ctx** out)
   Ctx* c = &ctx->c;
   c->p = *p;
   c->device = p->device;
+  if (const char* e = std::getenv("AGH_GRID_COLD"))  // every grid build takes the bounding-box path (A/B measurement)
+    c->grid_force_cold = std::atoi(e) != 0;
 #ifdef AGH_DEBUG_HOOKS  // phase-timing aids of scripts/phase_timing.py; not compiled into the product build
   if (const char* e = std::getenv("AGH_DEBUG_STOP_SWEEP"))
     c->debug_stop_sweep = std::atoi(e);
@@ -516,7 +521,8 @@ void agh_destroy(agh_ctx* ctx)
     c->d_images, c->d_slot_index, c->d_scan_tmp, c->d_out_own, c->d_nout, c->d_out_images, c->d_draw_ofs, c->d_draws,
     c->d_flags, c->d_normals, c->d_svm_w, c->d_hog, c->d_geom, c->d_desc_out, c->d_svm_sums, c->d_keep, c->d_vox_desc,
     c->d_weight, c->d_order, c->d_order_sweep, c->d_vmask, c->d_cloud_off, c->d_scloud, c->d_idx_own, c->d_tile_state, c->d_h_hands, c->d_h_bits, c->d_h_rowcnt, c->d_h_first,
-    c->d_h_n, c->d_h_idx, c->d_h_counts, c->d_h_handles, c->d_h_tmp, c->d_images_cam, c->d_xbuf, c->d_nbuf, c->d_xcnt, c->d_cls_images, c->d_cls_keep, c->d_cls_sums, c->d_dbg, c->d_svm_svT, c->d_svm_alpha, c->d_cls_desc, c->d_cls_kbuf, c->d_vox_code, c->d_vox_blk, c->d_vox_blk2, c->d_vox_total, c->d_vox_bitmap, c->d_vox_xyz, c->d_vox_cam, c->d_raw_xyz, c->d_huge_stage, c->d_huge_key, c->d_huge_count, c->d_huge_sorted, c->d_huge_normals, c->d_huge_base, c->d_stage_xyz, c->d_ovf };
+    c->d_h_n, c->d_h_idx, c->d_h_counts, c->d_h_handles, c->d_h_tmp, c->d_images_cam, c->d_xbuf, c->d_nbuf, c->d_xcnt, c->d_cls_images, c->d_cls_keep, c->d_cls_sums, c->d_dbg, c->d_svm_svT, c->d_svm_alpha, c->d_cls_desc, c->d_cls_kbuf, c->d_vox_code, c->d_vox_blk, c->d_vox_blk2, c->d_vox_total, c->d_vox_bitmap, c->d_vox_xyz, c->d_vox_cam, c->d_raw_xyz, c->d_huge_stage, c->d_huge_key, c->d_huge_count, c->d_huge_sorted, c->d_huge_normals, c->d_huge_base, c->d_stage_xyz, c->d_ovf,
+    c->d_desc_next, c->d_count_part, c->d_grid_miss };
   for (void* p : ptrs)
     if (p)
       (void) hipFree(p);
@@ -1543,6 +1549,25 @@ int agh_get_timing_counts(agh_ctx* ctx, int32_t* counts, int32_t cap)
   for (int i = 0; i < cap && i < AGH_TIMING_SLOTS; i++)
     counts[i] = ctx->c.timing_counts[i];
   return AGH_OK;
+}
+
+int agh_get_grid_stats(agh_ctx* ctx, int64_t* stats, int32_t cap)
+{
+  if (!ctx || (!stats && cap > 0) || cap < 0)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  unsigned miss = 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->d_grid_miss && c->grid_miss_zeroed)
+  {
+    HIPCHK(c, hipDeviceSynchronize());  // (the context's device: its builds may have run on any of the caller's streams)
+    HIPCHK(c, hipMemcpy(&miss, c->d_grid_miss, sizeof(unsigned), hipMemcpyDeviceToHost));
+  }
+  const int64_t v[3] = { c->grid_builds, c->grid_cold_builds, (int64_t) miss };
+  int k = 0;
+  for (; k < cap && k < 3; k++)
+    stats[k] = v[k];
+  return k;
 }
 
 int64_t agh_selftest_math(agh_ctx* ctx, int64_t n, uint64_t seed)

@@ -1,10 +1,18 @@
-// grid.hip -- K0: uniform-grid build (bounding box, cell histogram, scan, cell-major scatter).
+// grid.hip -- K0: uniform-grid build (cell histogram, scan, cell-major scatter; a bounding box on cold builds).
 //
 // Stands in for pcl::KdTreeFLANN::setInputCloud (reference src/agile_grasp/hand_search.cpp:10-11): the search
 // structure behind the three radius searches of the hot path.  The cloud is re-laid out cell-major as
 // float4 {x, y, z, bits((index << 1) | cam)} so that a ball query is a handful of contiguous runs read with
 // coalesced 16-byte loads.  Everything runs on the device without a host round trip: the grid descriptor
 // (origin, cell size, dimensions) lives in device memory and later kernels read it from there.
+//
+// Which descriptor a build uses does not change a single result: the searches only see neighbour SETS, and a point outside
+// the descriptor's box is clamped into a border cell whose face is then marked open (GridDesc::open, build_rows), so every ball
+// that reaches the point still reaches its cell.  Only the cell size matters (it bounds the rows of a ball query), and it
+// follows the rule of desc_finish.  So a build does not wait for its own cloud's bounding box: it bins the points into the
+// descriptor the previous build decided (Ctx::d_desc_next), and k_cell_scan decides the next one from the extrema that
+// k_cell_count leaves behind -- the same one again while it covers the cloud and is not much larger than needed.  A cold
+// build (a context's first, one after a failed build, a batch of another size) takes the bounding box first (k_bbox), as before.
 #include "agh_internal.h"
 
 #include <algorithm>
@@ -17,7 +25,7 @@ namespace agh
 __global__ void k_desc_reset(GridDesc* d)
 {
   d += blockIdx.x;
-  d->done = 0u;
+  d->open = 0u;
   d->ticket = 0u;
 }
 
@@ -115,24 +123,52 @@ __global__ __launch_bounds__(kBboxThreads) void k_bbox(const float* __restrict__
   }
 }
 
-// The reduction of k_bbox's slots and the grid descriptor, by one work-group for itself (256 threads; `g` in LDS).
-__device__ __forceinline__ void desc_from_parts(const float* __restrict__ part, int nparts, double base_cell, int64_t n, GridDesc* g)
+static_assert(kCountBlocks % 256 == 0, "reduce_parts: whole rounds of 256 slots");
+
+// Minima and maxima of three coordinates over the wave, on every lane (DPP / permlane moves: no LDS round trips).
+__device__ __forceinline__ void wave_minmax3(float lo[3], float hi[3])
+{
+  for (int a = 0; a < 3; a++)
+  {
+    lo[a] = fminf(lo[a], __int_as_float(xor_partner_i32<32>(__float_as_int(lo[a]))));
+    hi[a] = fmaxf(hi[a], __int_as_float(xor_partner_i32<32>(__float_as_int(hi[a]))));
+    lo[a] = fminf(lo[a], __int_as_float(xor_partner_i32<16>(__float_as_int(lo[a]))));
+    hi[a] = fmaxf(hi[a], __int_as_float(xor_partner_i32<16>(__float_as_int(hi[a]))));
+    lo[a] = fminf(lo[a], __int_as_float(xor_partner_i32<8>(__float_as_int(lo[a]))));
+    hi[a] = fmaxf(hi[a], __int_as_float(xor_partner_i32<8>(__float_as_int(hi[a]))));
+    lo[a] = fminf(lo[a], __int_as_float(xor_partner_i32<4>(__float_as_int(lo[a]))));
+    hi[a] = fmaxf(hi[a], __int_as_float(xor_partner_i32<4>(__float_as_int(hi[a]))));
+    lo[a] = fminf(lo[a], __int_as_float(xor_partner_i32<2>(__float_as_int(lo[a]))));
+    hi[a] = fmaxf(hi[a], __int_as_float(xor_partner_i32<2>(__float_as_int(hi[a]))));
+    lo[a] = fminf(lo[a], __int_as_float(xor_partner_i32<1>(__float_as_int(lo[a]))));
+    hi[a] = fmaxf(hi[a], __int_as_float(xor_partner_i32<1>(__float_as_int(hi[a]))));
+  }
+}
+
+// The reduction of `nparts` slots of six extrema by one work-group (256 threads): thread 0 ends with the cloud's box.
+__device__ __forceinline__ void reduce_parts(const float* __restrict__ part, int nparts, float lo[3], float hi[3])
 {
   __shared__ float red[4][6];
   const int tid = threadIdx.x, lane = tid & 63;
-  float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-  for (int b = tid; b < nparts; b += blockDim.x)
-    for (int a = 0; a < 3; a++)
-    {
-      lo[a] = fminf(lo[a], part[b * 6 + a]);
-      hi[a] = fmaxf(hi[a], part[b * 6 + 3 + a]);
-    }
   for (int a = 0; a < 3; a++)
-    for (int o = 32; o > 0; o >>= 1)
-    {
-      lo[a] = fminf(lo[a], __shfl_xor(lo[a], o));
-      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o));
-    }
+  {
+    lo[a] = INFINITY;
+    hi[a] = -INFINITY;
+  }
+  // (nparts <= kCountBlocks = 8 x 256: unrolled, so that all of a thread's slot loads are in flight at once -- the slots were
+  // written by other XCDs, one round trip each)
+#pragma unroll
+  for (int k = 0; k < kCountBlocks / 256; k++)
+  {
+    const int b = tid + 256 * k;
+    if (b < nparts)
+      for (int a = 0; a < 3; a++)
+      {
+        lo[a] = fminf(lo[a], part[b * 6 + a]);
+        hi[a] = fmaxf(hi[a], part[b * 6 + 3 + a]);
+      }
+  }
+  wave_minmax3(lo, hi);
   if (lane == 0 && tid < 256)
     for (int a = 0; a < 3; a++)
     {
@@ -141,35 +177,50 @@ __device__ __forceinline__ void desc_from_parts(const float* __restrict__ part, 
     }
   __syncthreads();
   if (tid == 0)
-  {
     for (int a = 0; a < 3; a++)
       for (int w = 1; w < 4; w++)
       {
         lo[a] = fminf(lo[a], red[w][a]);
         hi[a] = fmaxf(hi[a], red[w][3 + a]);
       }
+}
+
+// The reduction of k_bbox's slots and the grid descriptor, by one work-group for itself (256 threads; `g` in LDS).
+__device__ __forceinline__ void desc_from_parts(const float* __restrict__ part, int nparts, double base_cell, int64_t n, GridDesc* g)
+{
+  float lo[3], hi[3];
+  reduce_parts(part, nparts, lo, hi);
+  if (threadIdx.x == 0)
     desc_finish(g, base_cell, n, lo, hi);
-  }
   __syncthreads();
 }
 
 // Cell histogram.  Clouds arrive in voxel order (localization.cpp:282-351), so consecutive points mostly share a cell:
 // each run of equal cells inside a wave issues ONE atomic (with return), and every point remembers its rank inside its
 // cell, which makes the scatter below atomic-free.
+// COLD: the descriptor from k_bbox's slots, every work-group for itself (a cold build).  Otherwise the kept descriptor of the
+// cloud, one scalar load.  Either way the first work-group of a cloud publishes the descriptor it bins into for the kernels
+// after this one, and every work-group leaves the extrema of its finite points in its slot of `part_out` for k_cell_scan.
+template <bool COLD>
 __global__ __launch_bounds__(256) void k_cell_count(const float* __restrict__ xyz, int64_t stride,
-  const int* __restrict__ cloud_off, GridDesc* __restrict__ d, int* __restrict__ cell_of, int* __restrict__ rank_of,
-  int* __restrict__ count, const float* __restrict__ part, int nparts, double base_cell)
+  const int* __restrict__ cloud_off, GridDesc* __restrict__ d, const GridDesc* __restrict__ kept, int* __restrict__ cell_of,
+  int* __restrict__ rank_of, int* __restrict__ count, const float* __restrict__ part, int nparts, double base_cell,
+  float* __restrict__ part_out)
 {
   const int64_t p0 = cloud_off[blockIdx.y], n = cloud_off[blockIdx.y + 1] - p0;
   xyz += p0 * stride;
   cell_of += p0;
   rank_of += p0;
   count += (int64_t) blockIdx.y * kCellCap;
-  // the grid descriptor from k_bbox's slots: every work-group for itself; the first one of a cloud publishes it for the
-  // kernels after this one
-  __shared__ GridDesc gs;
-  desc_from_parts(part + (int64_t) blockIdx.y * kBboxBlocks * 6, nparts, base_cell, n, &gs);
-  const GridDesc g = gs;
+  GridDesc g;
+  if (COLD)
+  {
+    __shared__ GridDesc gs;
+    desc_from_parts(part + (int64_t) blockIdx.y * kBboxBlocks * 6, nparts, base_cell, n, &gs);
+    g = gs;
+  }
+  else
+    g = kept[blockIdx.y];
   if (blockIdx.x == 0 && threadIdx.x == 0)
   {
     GridDesc* o = d + blockIdx.y;  // (field by field: `ticket` belongs to k_cell_scan)
@@ -181,7 +232,9 @@ __global__ __launch_bounds__(256) void k_cell_count(const float* __restrict__ xy
     o->cell = g.cell;
     o->inv_cell = g.inv_cell;
     o->ncell = g.ncell;
+    o->open = 0u;  // (k_cell_scan opens the faces the cloud crosses)
   }
+  float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
   const int lane = threadIdx.x & 63;
   const int64_t step = (int64_t) gridDim.x * blockDim.x;
   const int64_t n_up = (n + 63) & ~(int64_t) 63;  // whole waves iterate together (the shuffles below need all lanes)
@@ -191,14 +244,24 @@ __global__ __launch_bounds__(256) void k_cell_count(const float* __restrict__ xy
     if (i < n)
     {
       const float* p = xyz + i * stride;
-      const int cx = cell_coord(g, (double) p[0], 0), cy = cell_coord(g, (double) p[1], 1),
-                cz = cell_coord(g, (double) p[2], 2);
+      const float px = p[0], py = p[1], pz = p[2];
+      const int cx = cell_coord(g, (double) px, 0), cy = cell_coord(g, (double) py, 1), cz = cell_coord(g, (double) pz, 2);
       c = (cz * g.dim[1] + cy) * g.dim[0] + cx;
       // A non-finite point keeps its place in the index space (the callers' indices do not move) and its own coordinates in the
       // sorted array, where every query's float32 distance test rejects it (NaN and Inf compare false with `< r^2`); which cell
-      // it lies in is therefore free -- spread over the cells by index, so that no cell collects a sensor's drop-outs.
-      if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])))
+      // it lies in is therefore free -- spread over the cells by index, so that no cell collects a sensor's drop-outs.  It does
+      // not stretch the box either (pcl::KdTreeFLANN::setInputCloud drops it: it can be nobody's neighbour).
+      if (!(isfinite(px) && isfinite(py) && isfinite(pz)))
         c = (int) (i % (int64_t) g.ncell);
+      else
+      {
+        mn[0] = fminf(mn[0], px);
+        mn[1] = fminf(mn[1], py);
+        mn[2] = fminf(mn[2], pz);
+        mx[0] = fmaxf(mx[0], px);
+        mx[1] = fmaxf(mx[1], py);
+        mx[2] = fmaxf(mx[2], pz);
+      }
     }
     const int prev = __shfl_up(c, 1);
     const bool head = (lane == 0) || (c != prev);
@@ -216,13 +279,81 @@ __global__ __launch_bounds__(256) void k_cell_count(const float* __restrict__ xy
       rank_of[i] = base + (lane - hl);
     }
   }
+  // the work-group's extrema into its slot (after the point loop: its atomics are in flight meanwhile)
+  __shared__ float smn[4][3], smx[4][3];
+  wave_minmax3(mn, mx);
+  if (lane == 0)
+    for (int a = 0; a < 3; a++)
+    {
+      smn[threadIdx.x >> 6][a] = mn[a];
+      smx[threadIdx.x >> 6][a] = mx[a];
+    }
+  __syncthreads();
+  if (threadIdx.x < 3)
+  {
+    const int a = threadIdx.x;
+    const float lo = fminf(fminf(smn[0][a], smn[1][a]), fminf(smn[2][a], smn[3][a]));
+    const float hi = fmaxf(fmaxf(smx[0][a], smx[1][a]), fmaxf(smx[2][a], smx[3][a]));
+    float* slot = part_out + ((int64_t) blockIdx.y * kCountBlocks + blockIdx.x) * 6;
+    slot[a] = lo;
+    slot[3 + a] = hi;
+  }
+}
+
+// The descriptor the next build of a cloud keeps, from the descriptor `u` this build used and the cloud's true box (thread 0 of
+// one work-group of k_cell_scan).  Faces of `u` the cloud crosses are opened in the used descriptor (the searches then treat
+// their border layers as unbounded) and the build counts as a miss.  `u` is kept while it covers the cloud, has the cell size
+// the cloud's own box would give, and exceeds that box by at most 4 kGridMargin cells along every axis; otherwise the next
+// build takes the cloud's box padded by kGridMargin cells on every face (none if the padded grid would pass kCellCap).  The
+// descriptor of a cold build is the unpadded box: never kept.
+__device__ void desc_next(const GridDesc u, GridDesc* used, GridDesc* next, unsigned* miss, double base_cell, int64_t n,
+  const float lo[3], const float hi[3], bool cold)
+{
+  GridDesc t;
+  desc_finish(&t, base_cell, n, lo, hi);
+  const bool any = n > 0 && lo[0] <= hi[0];  // (a finite point sets all six extrema)
+  unsigned open = 0u;
+  bool fits = !cold && any && u.cell == t.cell;
+  if (any)
+    for (int a = 0; a < 3; a++)
+    {
+      // exactly the arithmetic of cell_coord, before its clamp
+      if (floor(((double) lo[a] - u.mn[a]) * u.inv_cell) < 0.0)
+        open |= 1u << (2 * a);
+      if (floor(((double) hi[a] - u.mn[a]) * u.inv_cell) > (double) (u.dim[a] - 1))
+        open |= 2u << (2 * a);
+      fits = fits && u.dim[a] - t.dim[a] <= 4 * kGridMargin;
+    }
+  if (open)
+  {
+    used->open = open;
+    atomicAdd(miss, 1u);
+  }
+  GridDesc o = u;
+  if (!fits || open)
+  {
+    int m = kGridMargin;
+    if ((double) (t.dim[0] + 2 * m) * (double) (t.dim[1] + 2 * m) * (double) (t.dim[2] + 2 * m) > (double) kCellCap)
+      m = 0;
+    o = t;
+    for (int a = 0; a < 3; a++)
+    {
+      o.mn[a] = t.mn[a] - m * t.cell;
+      o.dim[a] = t.dim[a] + 2 * m;
+    }
+    o.ncell = o.dim[0] * o.dim[1] * o.dim[2];
+  }
+  o.open = 0u;
+  o.ticket = 0u;
+  *next = o;
 }
 
 // Exclusive scan of the cell histogram in ONE launch (decoupled look-back): tiles of 1024 cells are walked round-robin
 // by 256 resident work-groups, so a tile's predecessors are always running or done and the look-back cannot deadlock.  A tile
 // publishes (build number, flag, value) in one 64-bit word: flag 1 = the tile's own total, 2 = its inclusive prefix;
 // the build number makes stale words from earlier builds invisible, so the descriptors never need clearing.  The kernel
-// also zeroes the histogram it has read: the next build starts from a clean one without a memset.
+// also zeroes the histogram it has read: the next build starts from a clean one without a memset.  And its last work-group, which
+// has no tile unless the grid is huge, reduces k_cell_count's extrema slots and decides the next build's descriptor (desc_next).
 constexpr int kScanBlock = 4096;  // cells per tile: 16 per thread, four 16-byte accesses each way
 
 __device__ __forceinline__ int block_scan_excl(int v, int* total)
@@ -243,7 +374,8 @@ __device__ __forceinline__ int block_scan_excl(int v, int* total)
 }
 
 __global__ __launch_bounds__(256) void k_cell_scan(int* __restrict__ count, GridDesc* __restrict__ d,
-  unsigned long long* __restrict__ tile_state, unsigned gen, int* __restrict__ cell_start, const int* __restrict__ cloud_off)
+  unsigned long long* __restrict__ tile_state, unsigned gen, int* __restrict__ cell_start, const int* __restrict__ cloud_off,
+  const float* __restrict__ part, int nparts, GridDesc* __restrict__ next, unsigned* __restrict__ miss, double base_cell, int cold)
 {
   __shared__ int s_prefix;
   // blockIdx.y = cloud: its own histogram, tile descriptors and cell table; the table holds positions in the common
@@ -330,6 +462,13 @@ __global__ __launch_bounds__(256) void k_cell_scan(int* __restrict__ count, Grid
     cell_start[ncell] = p0 + n;
   __syncthreads();  // s_prefix is reused by the next tile of this group
   }
+  if (blockIdx.x == gridDim.x - 1)
+  {
+    float lo[3], hi[3];
+    reduce_parts(part + (int64_t) blockIdx.y * kCountBlocks * 6, nparts, lo, hi);
+    if (threadIdx.x == 0)
+      desc_next(*d, d, next + blockIdx.y, miss, base_cell, n, lo, hi, cold != 0);
+  }
 }
 
 __global__ __launch_bounds__(256) void k_scatter(const float* __restrict__ xyz, int64_t stride,
@@ -354,7 +493,16 @@ int grid_build(Ctx* c, hipStream_t st)
   int64_t nmax = 0;
   for (int k = 0; k < C; k++)
     nmax = std::max<int64_t>(nmax, c->cloud_off[(size_t) k + 1] - c->cloud_off[(size_t) k]);
-  const int nblk = (int) std::max<int64_t>(1, std::min<int64_t>((nmax + 255) / 256, 2048));
+  const int nblk = (int) std::max<int64_t>(1, std::min<int64_t>((nmax + 255) / 256, kCountBlocks));
+  // the kept descriptors belong to the cloud slots of the last build: a batch of another size (or a failed build) starts cold.
+  // A cloud of another point count in the same slot does not: the descriptor is only geometry, and a cloud it does not fit
+  // is a miss or a shrink (desc_next).
+  const bool cold = !c->grid_clean || c->grid_force_cold || c->grid_key_clouds != C;
+  if (!c->grid_miss_zeroed)
+  {
+    hipMemsetAsync(c->d_grid_miss, 0, sizeof(unsigned), st);
+    c->grid_miss_zeroed = true;
+  }
   if (!c->grid_clean)  // first build of the context, or the previous one failed half-way
   {
     hipMemsetAsync(c->d_cell_count, 0, sizeof(int) * (size_t) kCellCap * c->clouds_cap, st);
@@ -398,14 +546,25 @@ int grid_build(Ctx* c, hipStream_t st)
   }
   // cell >= r_hands/4 keeps a ball query within 9 x 9 rows
   const double base_cell = std::max(0.02, c->p.nn_radius_hands / 4.0);
-  const int nparts = std::max(1, std::min(nblk, kBboxBlocks));
-  hipLaunchKernelGGL(k_bbox, dim3(nparts, C), dim3(kBboxThreads), 0, st, c->d_xyz, c->stride_floats,
-    (const int*) c->d_cloud_off, c->d_bbox_part);
   // (also for an empty cloud: one work-group writes the descriptor of an empty grid)
-  hipLaunchKernelGGL(k_cell_count, dim3(nblk, C), dim3(256), 0, st, c->d_xyz, c->stride_floats, (const int*) c->d_cloud_off,
-    c->d_desc, c->d_cell_of, c->d_rank_of, c->d_cell_count, (const float*) c->d_bbox_part, nparts, base_cell);
+  if (cold)
+  {
+    const int nparts = std::max(1, std::min(nblk, kBboxBlocks));
+    hipLaunchKernelGGL(k_bbox, dim3(nparts, C), dim3(kBboxThreads), 0, st, c->d_xyz, c->stride_floats,
+      (const int*) c->d_cloud_off, c->d_bbox_part);
+    hipLaunchKernelGGL(k_cell_count<true>, dim3(nblk, C), dim3(256), 0, st, c->d_xyz, c->stride_floats, (const int*) c->d_cloud_off,
+      c->d_desc, (const GridDesc*) c->d_desc_next, c->d_cell_of, c->d_rank_of, c->d_cell_count, (const float*) c->d_bbox_part,
+      nparts, base_cell, c->d_count_part);
+  }
+  else
+    hipLaunchKernelGGL(k_cell_count<false>, dim3(nblk, C), dim3(256), 0, st, c->d_xyz, c->stride_floats, (const int*) c->d_cloud_off,
+      c->d_desc, (const GridDesc*) c->d_desc_next, c->d_cell_of, c->d_rank_of, c->d_cell_count, (const float*) nullptr, 0,
+      base_cell, c->d_count_part);
   hipLaunchKernelGGL(k_cell_scan, dim3(C == 1 ? 256 : 64, C), dim3(256), 0, st, c->d_cell_count, c->d_desc, c->d_tile_state,
-    c->build_gen, c->d_cell_start, (const int*) c->d_cloud_off);
+    c->build_gen, c->d_cell_start, (const int*) c->d_cloud_off, (const float*) c->d_count_part, nblk, c->d_desc_next,
+    c->d_grid_miss, base_cell, cold ? 1 : 0);
+  c->grid_builds++;
+  c->grid_cold_builds += cold ? 1 : 0;
   if (c->pending_cam_host)
   {
     // host-buffer agh_set_cloud: the camera ids (a blocking pageable copy, ~1.2 MB for 300k points) go up while the three
@@ -433,6 +592,7 @@ int grid_build(Ctx* c, hipStream_t st)
   if (hipGetLastError() != hipSuccess)
     return AGH_ERR_HIP;
   c->grid_clean = true;
+  c->grid_key_clouds = C;
   return AGH_OK;
 }
 

@@ -452,6 +452,11 @@ int agh_get_timing(agh_ctx* ctx, agh_timing* out);
 /* Timed launches behind ms[i] of the LAST agh_get_timing call of this context (profile 3 times a sample of the calls):
  * counts[0 .. min(cap, AGH_TIMING_SLOTS) - 1]. */
 int agh_get_timing_counts(agh_ctx* ctx, int32_t* counts, int32_t cap);
+/* Grid-build counters of the context: stats[0] = builds, [1] = cold builds (bounding box first: the context's first build, one
+ * after a failed build or a change of the number of clouds, or every build under AGH_GRID_COLD=1), [2] = builds of a cloud with points
+ * outside the grid descriptor the build kept from the previous one (a miss: still exact, only slower).  Writes min(cap, 3)
+ * values and returns how many; synchronises the context's device. */
+int agh_get_grid_stats(agh_ctx* ctx, int64_t* stats, int32_t cap);
 /* Change agh_params::profile of a live context (0 .. 3); pending timings are dropped. */
 int agh_set_profile(agh_ctx* ctx, int32_t level);
 int agh_synchronize(agh_ctx* ctx);
