@@ -349,7 +349,7 @@ struct Ctx
   int64_t xbuf_bytes = 0;
   double* d_nbuf = nullptr;       // n_ranks segments of per-sample normals (antipodal mode), all-gathered in place
   int64_t nbuf_doubles = 0;
-  int64_t* d_xcnt = nullptr;      // n_ranks RAND50 draw counts + scratch
+  int64_t* d_xcnt = nullptr;      // n_ranks RAND50 draw counts + scratch (kXcntWords; shard.hip)
   bool shard_symmetric_error = false;  // the last sharded device call failed on something every rank saw alike, after the ranks
                                        // had met in a collective: nobody is left waiting, the communicator stays usable
   int64_t shard_seg_override = 0;    // agh_comm_set_segment_records
@@ -360,6 +360,9 @@ struct Ctx
   int64_t shard_cap = 0;
   int64_t* shard_nout = nullptr;
   int64_t shard_last_n = -1;            // length of the merged list, once a host entry point has read it
+  bool shard_host_list = false;         // the last sharded search was agh_find_hands_sharded (the list is d_out_own)
+  int shard_hdr_search = 0;             // kHdrRank* bits the last sharded search left in this rank's own segment header
+  int shard_hdr_bits = 0;               // ... and the kHdrRank* bits that header carries now (a failed classification adds one)
 
   long long* d_dbg = nullptr;  // AGH_DEBUG_CLOCKS: per-sample phase timestamps of k_hand_sweep (dumped to a file)
   int debug_stop_sweep = 0;    // AGH_DEBUG_STOP_SWEEP: phase-timing aid, see k_hand_sweep
@@ -377,6 +380,17 @@ struct Ctx
 };
 
 inline int class_level(const Ctx* c) { return c->huge_classes ? 2 : (c->big_classes ? 1 : 0); }
+
+// include/agh.h: between agh_localize_begin and agh_localize_end only agh_localize_stage and the calls listed there may run on a
+// context.  The others refuse here, before they touch a buffer: the chain in flight owns the per-call buffers (d_out_own, d_flags,
+// d_idx_own, the pinned mirrors) and the cloud, whose size may still be only a bound (n_is_bound).
+inline bool refuse_mid_chain(Ctx* c, const char* fn)
+{
+  if (!c->loc.active)
+    return false;
+  c->err = std::string(fn) + ": a localize chain is in flight on this context (agh_localize_end first)";
+  return true;
+}
 
 // a search about to run on `st`: if the host-buffer agh_set_cloud left its grid build running on the context's stream and `st`
 // is another stream, wait for the build first (streams the caller brings may be non-blocking ones)

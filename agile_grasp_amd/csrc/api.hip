@@ -572,6 +572,8 @@ int agh_set_cloud_batch_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_set_cloud"))
+    return AGH_ERR_STATE;
   if (!offsets || n_clouds < 1 || n_clouds > kMaxClouds || offsets[0] != 0)
   {
     c->err = "agh_set_cloud_batch: need 1 <= n_clouds <= 64 and offsets[0] == 0";
@@ -685,6 +687,8 @@ int agh_set_cloud_batch(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, co
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_set_cloud"))
+    return AGH_ERR_STATE;
   if (!offsets || n_clouds < 1 || n_clouds > kMaxClouds)
   {
     c->err = "agh_set_cloud_batch: need 1 <= n_clouds <= 64 and offsets";
@@ -766,6 +770,8 @@ int agh_set_cloud_batch(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, co
 int agh_preprocess_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, int64_t size_left,
   int dense, const double workspace[6], double cell_size, int64_t* n_voxels_out, void* hip_stream)
 {
+  if (ctx && refuse_mid_chain(&ctx->c, "agh_preprocess"))
+    return AGH_ERR_STATE;
   return preprocess_device_impl(ctx, d_xyz, stride_bytes, n, size_left, dense, workspace, cell_size, n_voxels_out, hip_stream, false,
     nullptr);
 }
@@ -891,6 +897,8 @@ int agh_preprocess(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_preprocess"))
+    return AGH_ERR_STATE;
   if (n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz))
   {
     c->err = "agh_preprocess: need 0 <= n < 2^30, stride_bytes >= 12 and a multiple of 4";
@@ -1014,6 +1022,8 @@ int agh_find_handles(agh_ctx* ctx, const agh_hypothesis* hands, int64_t n_hands,
   if (!ctx || !n_handles_out || n_hands < 0 || (n_hands > 0 && !hands) || handle_cap < 0 || idx_cap < 0 || min_inliers < 1)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_find_handles"))
+    return AGH_ERR_STATE;
   *n_handles_out = 0;
   if (n_hands > 8192)
   {
@@ -1085,6 +1095,8 @@ int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap)
   if (!ctx || cap < 0)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_cloud"))
+    return AGH_ERR_STATE;
   if (!c->has_cloud)
   {
     c->err = "agh_get_cloud: no cloud set";
@@ -1111,6 +1123,8 @@ int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_s
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_find_hands"))
+    return AGH_ERR_STATE;
   if (!c->has_cloud)
   {
     c->err = "agh_find_hands: no cloud set";
@@ -1221,6 +1235,18 @@ extern "C++" int flags_to_status(Ctx* c, const int32_t* flags_in)
   if (flags[0] & kFlagSharded)
   {
     flags[0] &= ~1;
+    // a rank that failed first: every rank returns with this call and none switches a capacity class on it (shard.hip,
+    // shard_flags)
+    if (flags[0] & kFlagShardPeerNoCloud)
+    {
+      c->err = "a rank of the communicator holds no cloud (agh_set_cloud* on every rank first); no list";
+      return AGH_ERR_NO_CLOUD;
+    }
+    if (flags[0] & kFlagShardPeerFailed)
+    {
+      c->err = "a rank of the communicator could not do its share of the call (its own agh_last_error says why); no list";
+      return AGH_ERR_STATE;
+    }
     if (flags[0] & kFlagShardHard)
     {
       c->err = "the Taubin neighbourhoods (r = nn_radius_taubin) of more than 4096 points of one launch hold more than 2^21 points in "
@@ -1260,16 +1286,6 @@ extern "C++" int flags_to_status(Ctx* c, const int32_t* flags_in)
              "all (the pool of the classes beyond the LDS-resident ones); voxelise the cloud (localization.cpp:43) or reduce the radii";
     return AGH_ERR_CAPACITY;
   }
-  if (flags[0] & kFlagShardPeerNoCloud)
-  {
-    c->err = "a rank of the communicator holds no cloud (agh_set_cloud* on every rank first); no list";
-    return AGH_ERR_NO_CLOUD;
-  }
-  if (flags[0] & kFlagShardPeerFailed)
-  {
-    c->err = "a rank of the communicator could not do its share of the call (its own agh_last_error says why); no list";
-    return AGH_ERR_STATE;
-  }
   if ((flags[0] & 2) && !(flags[0] & 16))
   {
     c->err = "output buffer too small for the hypotheses found";
@@ -1297,6 +1313,8 @@ int agh_find_hands(agh_ctx* ctx, const int32_t* sample_idx, int64_t n_samples, i
   if (!ctx || !n_out)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_find_hands"))
+    return AGH_ERR_STATE;
   *n_out = 0;
   if (!c->has_cloud)
   {
@@ -1400,6 +1418,8 @@ int agh_synchronize(agh_ctx* ctx)
   Ctx* c = &ctx->c;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
+  if (c->loc.active)  // (allowed mid-chain: it waits; the chain's flags and counts are agh_localize_end's to read)
+    return AGH_OK;
 #ifdef AGH_DEBUG_HOOKS
   if (c->d_dbg && c->last_s > 0 && std::getenv("AGH_DEBUG_CLOCKS"))  // development aid: dump the phase timestamps
   {
@@ -1428,6 +1448,8 @@ int agh_get_epoch(agh_ctx* ctx, int32_t* epoch, int64_t* n_hyp)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
+  if (refuse_mid_chain(&ctx->c, "agh_get_epoch"))
+    return AGH_ERR_STATE;
   if (epoch)
     *epoch = ctx->c.epoch;
   if (n_hyp)
@@ -1440,6 +1462,8 @@ int agh_get_frames(agh_ctx* ctx, agh_frame* out, int64_t cap)
   if (!ctx || !out)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_frames"))
+    return AGH_ERR_STATE;
   const int64_t n = std::min<int64_t>(cap, c->last_s);
   HIPCHK(c, hipDeviceSynchronize());
   if (n > 0)
@@ -1452,6 +1476,8 @@ int agh_get_neighbor_counts(agh_ctx* ctx, int32_t* n_taubin, int32_t* n_hands, i
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_neighbor_counts"))
+    return AGH_ERR_STATE;
   const int64_t n = std::min<int64_t>(cap, c->last_s);
   HIPCHK(c, hipDeviceSynchronize());
   if (n > 0 && n_taubin)
@@ -1475,6 +1501,8 @@ int agh_get_normals(agh_ctx* ctx, double* normals, int64_t cap_points)
   if (!ctx || !normals)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_normals"))
+    return AGH_ERR_STATE;
   if (!c->has_normals)
   {
     c->err = "no normals: the last agh_find_hands call did not use calculates_antipodal";
@@ -1492,6 +1520,8 @@ int agh_set_profile(agh_ctx* ctx, int32_t level)
   if (!ctx || level < 0 || level > 3)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_set_profile"))
+    return AGH_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
   c->p.profile = level;
@@ -1574,6 +1604,8 @@ int64_t agh_selftest_math(agh_ctx* ctx, int64_t n, uint64_t seed)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
+  if (refuse_mid_chain(&ctx->c, "agh_selftest_math"))
+    return AGH_ERR_STATE;
   return selftest_math(&ctx->c, n, seed);
 }
 

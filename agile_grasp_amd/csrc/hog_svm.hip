@@ -548,6 +548,8 @@ int agh_load_svm(agh_ctx* ctx, const float* weights, int32_t n_weights, double r
   if (!ctx || !weights)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_load_svm"))
+    return AGH_ERR_STATE;
   if (n_weights != 3528)
   {
     c->err = "agh_load_svm: the HOG descriptor has 3528 entries (2 windows x 49 blocks x 36)";
@@ -571,6 +573,8 @@ int agh_load_svm_file(agh_ctx* ctx, const char* path)
   if (!ctx || !path)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_load_svm_file"))
+    return AGH_ERR_STATE;
   FILE* f = std::fopen(path, "rb");
   if (!f)
   {
@@ -678,6 +682,8 @@ int agh_classify_device(agh_ctx* ctx, uint8_t* d_keep, void* hip_stream)
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_classify"))
+    return AGH_ERR_STATE;
   if (!c->has_svm)
   {
     c->err = "agh_classify: no SVM loaded";
@@ -698,6 +704,8 @@ int agh_classify(agh_ctx* ctx, uint8_t* keep, int64_t cap, int64_t* n_kept)
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_classify"))
+    return AGH_ERR_STATE;
   if (n_kept)
     *n_kept = 0;
   if (c->last_nout < 0)
@@ -755,6 +763,8 @@ int agh_get_packed_images(agh_ctx* ctx, uint32_t* images, int64_t cap_hyp)
   if (!ctx || (cap_hyp > 0 && !images) || cap_hyp < 0)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_packed_images"))
+    return AGH_ERR_STATE;
   if (c->last_nout < 0)
   {
     c->err = "agh_get_packed_images: needs a completed agh_find_hands call";
@@ -780,6 +790,8 @@ int agh_classify_images(agh_ctx* ctx, const uint32_t* images, int64_t n, uint8_t
   if (!ctx || n < 0 || (n > 0 && (!images || !keep)))
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_classify_images"))
+    return AGH_ERR_STATE;
   if (!c->has_svm)
   {
     c->err = "agh_classify_images: no SVM loaded";
@@ -850,6 +862,8 @@ int agh_get_images(agh_ctx* ctx, uint8_t* images, int64_t cap_hyp)
   if (!ctx || !images)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_images"))
+    return AGH_ERR_STATE;
   if (c->last_nout < 0)
   {
     c->err = "agh_get_images: needs a completed agh_find_hands call";
@@ -879,6 +893,8 @@ int agh_get_hog(agh_ctx* ctx, float* desc, double* sums, int64_t cap_hyp)
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_hog"))
+    return AGH_ERR_STATE;
   if (c->last_nout < 0 || !c->has_svm)
   {
     c->err = "agh_get_hog: needs an SVM and a completed agh_find_hands call";

@@ -345,7 +345,11 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     }
     else
     {
-      L.staged = false;  // (a staged capture that is not this one is dropped)
+      // (a staged capture that is not this one is dropped -- its copy may still be reading the caller's source: the chain waits
+      // for it too, so that agh_localize_end's synchronisation covers it, as include/agh.h promises)
+      if (L.staged)
+        HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
+      L.staged = false;
       const int64_t need = n * (dev_stride / 4);
       if (need > c->raw_cap || !c->d_raw_xyz)
       {

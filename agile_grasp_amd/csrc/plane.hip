@@ -790,6 +790,8 @@ int agh_get_plane_inliers(agh_ctx* ctx, int32_t* idx, int64_t cap)
   if (!ctx || cap < 0)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_plane_inliers"))
+    return AGH_ERR_STATE;
   if (!c->plane || !c->plane->has_result)
   {
     c->err = "agh_get_plane_inliers: no agh_remove_plane result";
@@ -815,6 +817,8 @@ int agh_get_plane_candidates(agh_ctx* ctx, float* planes, int32_t* samples, int6
   if (!ctx || cap < 0)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_plane_candidates"))
+    return AGH_ERR_STATE;
   if (!c->plane || !c->plane->has_result)
   {
     c->err = "agh_get_plane_candidates: no agh_remove_plane result";

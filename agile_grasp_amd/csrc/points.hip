@@ -136,6 +136,8 @@ extern "C" int agh_get_learning_points(agh_ctx* ctx, int64_t hyp, double* points
   if (!ctx || !n_out)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_learning_points"))
+    return AGH_ERR_STATE;
   *n_out = 0;
   if (c->last_nout < 0 || !c->d_out_last || !c->has_cloud)
   {

@@ -271,10 +271,11 @@ __global__ void k_shard_empty_header(int64_t* __restrict__ hdr, const int32_t* _
   hdr[0] = 0;
   hdr[1] = shard_header_word(flags[0], big) | extra;
 }
-// a rank whose classification failed on its own: its records travel as they are, its header says so
-__global__ void k_shard_flag_header(int64_t* __restrict__ hdr, int extra)
+// the kHdrRank* bits of this rank's own header: a classification that fails on this rank sets kHdrRankFailed (its records
+// travel as they are, its header says so), the next one that does not clears it again
+__global__ void k_shard_flag_header(int64_t* __restrict__ hdr, int bits)
 {
-  hdr[1] |= extra;
+  hdr[1] = (hdr[1] & ~(int64_t) (kHdrRankFailed | kHdrRankNoCloud)) | bits;
 }
 
 // RAND50: draws my slice consumes (50 per neighbourhood of more than 50 points, quadric.cpp:177-193)
@@ -414,7 +415,22 @@ int grow(Ctx* c, T** p, int64_t* have, int64_t want)
   return AGH_OK;
 }
 
-int exchange_and_merge(Ctx* c, uint8_t* d_keep, hipStream_t st)
+// d_xcnt: [0, 64) the RAND50 draw counts, [64, 128) shard_agree's words, then the bystander's scratch (below)
+constexpr int64_t kXcntWords = 128 + 8;
+
+// A rank with a localize chain in flight takes part in a sharded call without searching (include/agh.h).  Its flags word, its
+// count and the list pointer nobody writes (capacity 0) are here, not in d_flags / d_nout / d_out_own, which the chain owns.
+int32_t* bystander_flags(Ctx* c)
+{
+  return reinterpret_cast<int32_t*>(c->d_xcnt + 128);  // (8 words: as d_flags)
+}
+int64_t* bystander_nout(Ctx* c)
+{
+  return c->d_xcnt + 132;
+}
+
+// the merge writes at most `cap` records to `out`, the total to *n_out and ORs what the ranks found into flags[0]
+int exchange_and_merge(Ctx* c, uint8_t* d_keep, agh_hypothesis* out, int64_t cap, int64_t* n_out, int32_t* flags, hipStream_t st)
 {
   Comm* cm = c->comm;
   int rc = all_gather(c, c->d_xbuf, (size_t) c->shard_seg_bytes, st);
@@ -422,7 +438,7 @@ int exchange_and_merge(Ctx* c, uint8_t* d_keep, hipStream_t st)
     return rc;
   timing_mark(c, "shard_allgather", st);
   hipLaunchKernelGGL(k_shard_merge, dim3(256), dim3(256), 0, st, (const uint8_t*) c->d_xbuf, c->shard_seg_bytes, c->shard_seg_records,
-    cm->n_ranks, c->shard_S, c->shard_out, c->shard_cap, c->shard_nout, d_keep, c->d_flags, c->epoch);
+    cm->n_ranks, c->shard_S, out, cap, n_out, d_keep, flags, c->epoch);
   return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
 }
 
@@ -583,7 +599,7 @@ int agh_comm_init(agh_ctx* ctx, int32_t rank, int32_t n_ranks, const uint8_t id[
     if (!c->d_xcnt)
     {
       int64_t have = 0;
-      rc = grow(c, &c->d_xcnt, &have, 128);
+      rc = grow(c, &c->d_xcnt, &have, kXcntWords);
     }
     uint64_t mine = params_fingerprint(c->p), all[64];
     if (rc == AGH_OK && hipMemcpyAsync(c->d_xcnt + 64 + rank, &mine, sizeof(mine), hipMemcpyHostToDevice, c->stream) != hipSuccess)
@@ -630,7 +646,7 @@ int agh_comm_init_local(agh_ctx* const* ctxs, int32_t n_ranks)
     if (!ctxs[q]->c.d_xcnt)
     {
       int64_t have = 0;
-      if (hipSetDevice(ctxs[q]->c.device) != hipSuccess || grow(&ctxs[q]->c, &ctxs[q]->c.d_xcnt, &have, 128) != AGH_OK)
+      if (hipSetDevice(ctxs[q]->c.device) != hipSuccess || grow(&ctxs[q]->c, &ctxs[q]->c.d_xcnt, &have, kXcntWords) != AGH_OK)
         return AGH_ERR_HIP;
     }
   std::shared_ptr<LocalGroup> g(new LocalGroup());
@@ -735,6 +751,8 @@ int agh_find_hands_sharded_device(agh_ctx* ctx, const int32_t* d_sample_idx, int
   agh_hypothesis* d_out, int64_t cap, int64_t* d_n_out, void* hip_stream)
 {
   bool entered = false;
+  if (ctx)
+    ctx->c.shard_host_list = false;
   const int rc = find_hands_sharded_device_impl(ctx, d_sample_idx, n_samples, calculates_antipodal, d_out, cap, d_n_out, hip_stream,
     &entered, AGH_OK, nullptr);
   shard_release_peers(ctx, rc, entered);
@@ -791,6 +809,12 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
       hdr_extra = extra;
     }
   };
+  // A localize chain in flight on this rank (include/agh.h): a bystander.  It takes part like a degraded rank, but its flags word
+  // and count go to scratch of its own (bystander_*), and it keeps the chain's per-call state (last_*, epoch, d_out_last).
+  const bool mid_chain = c->loc.active;
+  if (mid_chain)
+    degrade(AGH_ERR_STATE, "agh_find_hands_sharded: a localize chain is in flight on this context (agh_localize_end first)",
+      kHdrRankFailed);
   if (!c->has_cloud)  // a caller's bug on this rank: it takes part like a rank with an empty cloud, and every rank hears of it
     degrade(AGH_ERR_NO_CLOUD, "agh_find_hands_sharded: no cloud set", kHdrRankNoCloud);
   HIPCHK(c, hipSetDevice(c->device));
@@ -798,7 +822,8 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
   HIPCHK(c, order_after_cloud(c, st));
   const int G = c->comm->n_ranks, r = c->comm->rank;
   const int64_t S = n_samples;
-  const int64_t n_cloud = c->has_cloud ? c->n : 0;
+  const int64_t n_cloud = c->has_cloud && !mid_chain ? c->n : 0;  // (mid-chain, c->n may be a bound of the chain's cloud)
+  int32_t* const d_flags = mid_chain ? bystander_flags(c) : c->d_flags;
   // (a rank whose cloud is EMPTY -- possible when every rank searches a cloud of its own -- takes part with an empty slice: it
   // must still join every collective of the call, or the others wait for it for ever)
   const int64_t lo = shard_lo(S, r, G), hi = shard_lo(S, r + 1, G);
@@ -897,11 +922,14 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
     HIPCHK(c, hipMalloc((void**) &c->d_normals, sizeof(double) * 3 * (size_t) std::max<int64_t>(pcnt, 1)));
     c->normals_cap = pcnt;
   }
-  timing_begin(c, st);
-  c->zero_flags_pending = true;
-  c->epoch = next_epoch();
-  c->last_s = local_rc == AGH_OK ? Sr : 0;
-  c->last_nout = -1;
+  if (!mid_chain)
+  {
+    timing_begin(c, st);
+    c->zero_flags_pending = true;
+    c->epoch = next_epoch();
+    c->last_s = local_rc == AGH_OK ? Sr : 0;
+    c->last_nout = -1;
+  }
   c->shard_seg_records = seg_records;
   c->shard_seg_bytes = seg_bytes;
   c->shard_S = S;
@@ -909,20 +937,27 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
   c->shard_cap = cap;
   c->shard_nout = d_n_out;
   c->shard_last_n = -1;
+  c->shard_hdr_search = c->shard_hdr_bits = 0;
   uint8_t* my_seg = c->d_xbuf + (int64_t) r * seg_bytes;
   agh_hypothesis* my_out = reinterpret_cast<agh_hypothesis*>(my_seg + kHeaderBytes);
   int64_t* my_count = reinterpret_cast<int64_t*>(my_seg);
   // what agh_classify* / the introspection getters see afterwards is this rank's own part
-  c->last_cap = seg_records;
-  c->d_out_last = my_out;
-  c->d_nout_last = my_count;
+  if (!mid_chain)
+  {
+    c->last_cap = seg_records;
+    c->d_out_last = my_out;
+    c->d_nout_last = my_count;
+  }
   if (S == 0)  // (the same on every rank: nobody starts a collective)
   {
-    HIPCHK(c, hipMemsetAsync(c->d_flags, 0, 8 * sizeof(int32_t), st));
-    c->zero_flags_pending = false;
+    HIPCHK(c, hipMemsetAsync(d_flags, 0, 8 * sizeof(int32_t), st));
     HIPCHK(c, hipMemsetAsync(d_n_out, 0, sizeof(int64_t), st));
     HIPCHK(c, hipMemsetAsync(c->d_xbuf, 0, (size_t) G * seg_bytes, st));
-    c->last_s = 0;
+    if (!mid_chain)
+    {
+      c->zero_flags_pending = false;
+      c->last_s = 0;
+    }
     if (local_rc != AGH_OK)
     {
       c->err = local_err;
@@ -941,24 +976,26 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
       degrade(rc, "normals pass launch failed", kHdrRankFailed);
     if ((rc = all_gather(c, c->d_normals, sizeof(double) * 3 * (size_t) pcnt, st)) != AGH_OK)
       return rc;
-    c->has_normals = true;
+    if (!mid_chain)
+      c->has_normals = true;
   }
   if (ok() && Sr > 0)
   {
     if ((rc = injected(c, 2) ? AGH_ERR_HIP : taubin_moments_eigen(c, my_idx, Sr, c->p.nn_radius_taubin, c->d_nt, st)) != AGH_OK)
       degrade(rc, "taubin launch failed", kHdrRankFailed);
   }
-  if (c->zero_flags_pending)  // (no Taubin launch cleared them: an empty or a degraded slice)
+  if (mid_chain || c->zero_flags_pending)  // (no Taubin launch cleared them: an empty or a degraded slice)
   {
-    HIPCHK(c, hipMemsetAsync(c->d_flags, 0, 8 * sizeof(int32_t), st));
-    c->zero_flags_pending = false;
+    HIPCHK(c, hipMemsetAsync(d_flags, 0, 8 * sizeof(int32_t), st));
+    if (!mid_chain)
+      c->zero_flags_pending = false;
   }
   if (rand_mode && G > 1)
   {
     hipLaunchKernelGGL(k_shard_draw_count, dim3(1), dim3(64), 0, st, (const int32_t*) c->d_nt, ok() ? (int) Sr : 0, c->d_xcnt + r);
     if ((rc = all_gather(c, c->d_xcnt, sizeof(int64_t), st)) != AGH_OK)
       return rc;
-    hipLaunchKernelGGL(k_shard_draw_base, dim3(1), dim3(1), 0, st, (const int64_t*) c->d_xcnt, r, c->d_flags + 2);
+    hipLaunchKernelGGL(k_shard_draw_base, dim3(1), dim3(1), 0, st, (const int64_t*) c->d_xcnt, r, d_flags + 2);
   }
   if (ok() && Sr > 0 && (rc = taubin_frame_stage(c, my_idx, Sr, c->p.nn_radius_taubin, c->d_frames, c->d_nt, calculates_antipodal != 0, st)) != AGH_OK)
     degrade(rc, "taubin launch failed", kHdrRankFailed);
@@ -988,19 +1025,23 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
     // an empty slice: count 0 -- and still the flag its share of the all-points pass may have raised (the other ranks must learn
     // of a capacity-class retry from EVERY rank, or this one would repeat the collective alone); a degraded rank: count 0 and
     // the word that makes the call fail on every rank
-    hipLaunchKernelGGL(k_shard_empty_header, dim3(1), dim3(1), 0, st, my_count, (const int32_t*) c->d_flags, class_level(c), hdr_extra);
+    hipLaunchKernelGGL(k_shard_empty_header, dim3(1), dim3(1), 0, st, my_count, (const int32_t*) d_flags, class_level(c), hdr_extra);
     HIPCHK(c, hipGetLastError());
   }
   if (!ok())
+  {
     c->shard_cap = 0;  // (the merged list is not this rank's to keep: its output buffer may not exist)
-  if ((rc = exchange_and_merge(c, nullptr, st)) != AGH_OK)
+    c->shard_hdr_search = c->shard_hdr_bits = hdr_extra;
+  }
+  if ((rc = exchange_and_merge(c, nullptr, c->shard_out, c->shard_cap, c->shard_nout, d_flags, st)) != AGH_OK)
     return rc;
   timing_mark(c, "shard_merge", st);
   if (!ok())
   {
     // this rank's own failure, reported at once; its peers read it from the merged flags -- every collective has been issued
     c->err = local_err;
-    c->last_s = 0;
+    if (!mid_chain)
+      c->last_s = 0;
     *entered = false;
     c->shard_symmetric_error = true;
     return local_rc;
@@ -1031,8 +1072,20 @@ static int classify_sharded_device_impl(agh_ctx* ctx, uint8_t* d_keep, void* hip
     return AGH_ERR_STATE;
   }
   *entered = true;
+  // (mid-chain: a bystander, as in the search -- no HOG / SVM, its merge writes only scratch of its own)
+  const bool mid_chain = c->loc.active;
   int local_rc = pre_rc;
   std::string local_err = pre_err ? pre_err : "";
+  if (local_rc == AGH_OK && mid_chain)
+  {
+    local_rc = AGH_ERR_STATE;
+    local_err = "agh_classify_sharded: a localize chain is in flight on this context (agh_localize_end first)";
+  }
+  if (local_rc == AGH_OK && c->shard_hdr_search)
+  {
+    local_rc = AGH_ERR_STATE;  // (its header still says so: every rank fails this classification too)
+    local_err = "agh_classify_sharded: the preceding agh_find_hands_sharded failed on this rank; no list to classify";
+  }
   if (local_rc == AGH_OK && !c->has_svm)
   {
     local_rc = AGH_ERR_NO_SVM;
@@ -1047,12 +1100,23 @@ static int classify_sharded_device_impl(agh_ctx* ctx, uint8_t* d_keep, void* hip
     local_rc = rc;
     local_err = "HOG / SVM launch failed";
   }
-  if (local_rc != AGH_OK)
+  // My header's kHdrRank* bits: the search's, or kHdrRankFailed if this rank cannot classify now.  The in-place all-gather never
+  // rewrites a rank's own segment, so a bit that an earlier failed classification set is cleared here (the search's list is
+  // still valid); a bit the search set stays.
+  const int hdr_bits = c->shard_hdr_search ? c->shard_hdr_search : (local_rc != AGH_OK ? kHdrRankFailed : 0);
+  if (hdr_bits != c->shard_hdr_bits)
   {
-    hipLaunchKernelGGL(k_shard_flag_header, dim3(1), dim3(1), 0, st, c->d_nout_last, kHdrRankFailed);
+    int64_t* my_hdr = reinterpret_cast<int64_t*>(c->d_xbuf + (int64_t) c->comm->rank * c->shard_seg_bytes);
+    hipLaunchKernelGGL(k_shard_flag_header, dim3(1), dim3(1), 0, st, my_hdr, hdr_bits);
     HIPCHK(c, hipGetLastError());
+    c->shard_hdr_bits = hdr_bits;
   }
-  if ((rc = exchange_and_merge(c, local_rc == AGH_OK ? d_keep : nullptr, st)) != AGH_OK)
+  // (the merge derives the call's flags word from the headers afresh: a failed classification's peer bit must not outlive it either)
+  HIPCHK(c, hipMemsetAsync(mid_chain ? bystander_flags(c) : c->d_flags, 0, mid_chain ? 8 * sizeof(int32_t) : sizeof(int32_t), st));
+  rc = mid_chain ? exchange_and_merge(c, nullptr, reinterpret_cast<agh_hypothesis*>(bystander_flags(c)), 0, bystander_nout(c),
+                     bystander_flags(c), st)
+                 : exchange_and_merge(c, local_rc == AGH_OK ? d_keep : nullptr, c->shard_out, c->shard_cap, c->shard_nout, c->d_flags, st);
+  if (rc != AGH_OK)
     return rc;
   timing_mark(c, "shard_merge", st);
   if (local_rc != AGH_OK)
@@ -1072,6 +1136,19 @@ static int shard_flags(Ctx* c, hipStream_t st, int64_t* n)
   if (n)
     HIPCHK(c, hipMemcpyAsync(n, c->shard_nout, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
+  // A rank that failed (it returned its own error after the exchange) comes first: every rank returns with this call, and none
+  // switches a capacity class or the segment size on it -- the failed rank could not, and the next call's segment sizes and
+  // launches must agree.  A retry this call would have asked for is asked for again by the next one, on every rank.
+  if (flags[0] & kFlagShardPeerNoCloud)
+  {
+    c->err = "a rank of the communicator holds no cloud (agh_set_cloud* on every rank first); no list";
+    return AGH_ERR_NO_CLOUD;
+  }
+  if (flags[0] & kFlagShardPeerFailed)
+  {
+    c->err = "a rank of the communicator could not do its share of the call (its own agh_last_error says why); no list";
+    return AGH_ERR_STATE;
+  }
   if (flags[0] & 16)
     return 16;
   // (every rank reads the same segment headers, so every rank takes the same branch here -- whatever its own big_classes was:
@@ -1090,16 +1167,6 @@ static int shard_flags(Ctx* c, hipStream_t st, int64_t* n)
     c->err = "a Taubin neighbourhood exceeds the capacity classes launched so far; the contexts of the communicator now launch the "
              "larger classes as well: repeat the call";
     return AGH_ERR_RETRY;
-  }
-  if (flags[0] & kFlagShardPeerNoCloud)
-  {
-    c->err = "a rank of the communicator holds no cloud (agh_set_cloud* on every rank first); no list";
-    return AGH_ERR_NO_CLOUD;
-  }
-  if (flags[0] & kFlagShardPeerFailed)
-  {
-    c->err = "a rank of the communicator could not do its share of the call (its own agh_last_error says why); no list";
-    return AGH_ERR_STATE;
   }
   if (flags[0] & 2)
   {
@@ -1167,8 +1234,14 @@ static int find_hands_sharded_host_impl(agh_ctx* ctx, const int32_t* sample_idx,
   // (kStatusBadIndex), the finding travels in the rank's segment header, and every rank returns AGH_ERR_INVALID_ARGUMENT
   // together after the exchange.)
   HIPCHK(c, hipSetDevice(c->device));
+  // (a localize chain in flight owns d_out_own, d_idx_own and the per-call buffers: this rank touches none of them and takes part
+  // as a bystander, include/agh.h)
+  if (c->loc.active)
+    pre_fail(AGH_ERR_STATE, "agh_find_hands_sharded: a localize chain is in flight on this context (agh_localize_end first)");
   const int64_t n_cloud = c->has_cloud ? c->n : 0;
-  int rc = injected(c, 16) ? AGH_ERR_HIP : ensure_call_buffers(c, std::max<int64_t>(n_samples, calculates_antipodal ? std::min<int64_t>(n_cloud, kNormalsChunk) : 0));
+  int rc = AGH_OK;
+  if (pre_rc == AGH_OK)
+    rc = injected(c, 16) ? AGH_ERR_HIP : ensure_call_buffers(c, std::max<int64_t>(n_samples, calculates_antipodal ? std::min<int64_t>(n_cloud, kNormalsChunk) : 0));
   if (rc != AGH_OK)
     pre_fail(rc, c->err.empty() ? "out of device memory for the per-call buffers" : c->err);
   if (pre_rc == AGH_OK && (n_samples > c->idx_cap || !c->d_idx_own))
@@ -1193,12 +1266,13 @@ static int find_hands_sharded_host_impl(agh_ctx* ctx, const int32_t* sample_idx,
         (rc = ensure_call_buffers(c, std::max<int64_t>(n_samples, calculates_antipodal ? std::min<int64_t>(n_cloud, kNormalsChunk) : 0))) != AGH_OK)
       pre_fail(rc, c->err);
     // (s_cap >= n_samples, so d_out_own holds the complete list: 8 slots per sample.  A rank that failed above hands over
-    // pointers nobody reads: a degraded rank launches nothing on the sample list and keeps no list)
+    // pointers nobody reads: a degraded rank launches nothing on the sample list and keeps no list; its count goes to scratch)
     const bool usable = pre_rc == AGH_OK;
     bool in_coll = false;
-    rc = find_hands_sharded_device_impl(ctx, usable ? c->d_idx_own : reinterpret_cast<const int32_t*>(c->d_flags), n_samples,
-      calculates_antipodal, usable ? c->d_out_own : reinterpret_cast<agh_hypothesis*>(c->d_flags), usable ? c->s_cap * 8 : 0,
-      c->d_nout, c->stream, &in_coll, pre_rc, pre_err.c_str());
+    c->shard_host_list = true;
+    rc = find_hands_sharded_device_impl(ctx, usable ? c->d_idx_own : reinterpret_cast<const int32_t*>(bystander_flags(c)), n_samples,
+      calculates_antipodal, usable ? c->d_out_own : reinterpret_cast<agh_hypothesis*>(bystander_flags(c)), usable ? c->s_cap * 8 : 0,
+      usable ? c->d_nout : bystander_nout(c), c->stream, &in_coll, pre_rc, pre_err.c_str());
     if (rc != AGH_OK)
     {
       (void) hipStreamSynchronize(c->stream);
@@ -1259,7 +1333,8 @@ static int classify_sharded_host_impl(agh_ctx* ctx, agh_hypothesis* out, uint8_t
   Ctx* c = &ctx->c;
   if (n_kept)
     *n_kept = 0;
-  if (!c->comm || !c->shard_out || c->shard_out != c->d_out_own)
+  // (the same on every rank: a rank whose search failed, or that has a localize chain in flight, takes part -- it fails there)
+  if (!c->comm || !c->shard_out || !c->d_xbuf || !c->shard_host_list || (!c->shard_hdr_search && c->shard_out != c->d_out_own))
   {
     c->err = "agh_classify_sharded: needs a preceding agh_find_hands_sharded (host variant)";
     return AGH_ERR_STATE;
@@ -1269,7 +1344,7 @@ static int classify_sharded_host_impl(agh_ctx* ctx, agh_hypothesis* out, uint8_t
   int pre_rc = AGH_OK;
   const char* pre_err = nullptr;
   const int64_t room = c->s_cap * 8;
-  if (room > c->keep_cap)
+  if (room > c->keep_cap && !c->loc.active)  // (mid-chain the chain's classification writes d_keep)
   {
     if (c->d_keep)
       (void) hipFree(c->d_keep);

@@ -806,6 +806,8 @@ int agh_set_training_images(agh_ctx* ctx, int on)
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_set_training_images"))
+    return AGH_ERR_STATE;
   c->training_images = on != 0;
   if (!on)
     return AGH_OK;
@@ -832,6 +834,8 @@ int agh_get_training_images(agh_ctx* ctx, uint32_t* images, int64_t cap_hyp)
   if (!ctx || !images)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_training_images"))
+    return AGH_ERR_STATE;
   if (c->last_nout < 0 || !c->last_has_cam_images)
   {
     c->err = "agh_get_training_images: needs agh_set_training_images(1) and a completed "
@@ -866,6 +870,8 @@ int agh_hog_images(agh_ctx* ctx, const uint32_t* images, int64_t n, float* desc)
   if (!ctx || n < 0 || (n > 0 && (!images || !desc)))
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_hog_images"))
+    return AGH_ERR_STATE;
   if (n == 0)
     return AGH_OK;
   if (hipSetDevice(c->device) != hipSuccess)
@@ -904,6 +910,8 @@ int agh_train_svm(agh_ctx* ctx, const uint32_t* images, const int8_t* labels, in
                    "sv_cap >= 1 and the outputs";
     return AGH_ERR_INVALID_ARGUMENT;
   }
+  if (refuse_mid_chain(&ctx->c, "agh_train_svm"))
+    return AGH_ERR_STATE;
   Ctx* c = &ctx->c;
   // cvSortSamplesByClasses: class 0 (label -1, y = +1) first, original order inside a class
   std::vector<int32_t> order;
@@ -949,6 +957,8 @@ int agh_load_svm_model(agh_ctx* ctx, int32_t kernel_type, const float* sv, int32
       ctx->c.err = "agh_load_svm_model: need support vectors, alphas and a supported kernel (LINEAR, POLY degree 2)";
     return AGH_ERR_INVALID_ARGUMENT;
   }
+  if (refuse_mid_chain(&ctx->c, "agh_load_svm_model"))
+    return AGH_ERR_STATE;
   Ctx* c = &ctx->c;
   if (n_weights != kDesc)
   {

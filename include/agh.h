@@ -242,11 +242,21 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  *   agh_localize_end(ctx, outputs)        the one synchronisation; cloud k's results, exactly agh_localize's
  *   agh_localize_begin(ctx, cloud k + 1)  recognises the staged capture (same pointer, stride and count): no upload
  * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a
- * begin); between begin and end only agh_localize_stage may be called on the context.  The capture handed to begin must stay valid
+ * begin).  Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_end,
+ * agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error, agh_destroy, the host-side
+ * counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats) and the communicator's bookkeeping (agh_comm_rank,
+ * agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault, agh_comm_set_segment_records, agh_comm_last_*) may be called on
+ * the context.  Every other call on it returns AGH_ERR_STATE without touching anything: agh_set_cloud*, agh_preprocess*,
+ * agh_find_hands*, agh_classify*, agh_find_handles, agh_localize*, agh_remove_plane, agh_get_cloud and every getter of device
+ * results (frames, normals, neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*,
+ * the training calls (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and
+ * agh_selftest_math.  The sharded calls are collective and do not return early: on such a context they take part without
+ * searching, and every rank of the call returns an error (this one AGH_ERR_STATE); the chain is not disturbed.
+ * The capture handed to begin must stay valid
  * and unchanged until the agh_localize_end of its chain has returned, the one handed to stage until the agh_localize_end of the
  * chain that adopts it has (a pageable source has been read when agh_localize_stage returns; a pinned one is read asynchronously);
  * sample_idx is copied by begin.  A staged capture that the next begin does not name is dropped (its copy may still be running:
- * keep the source until the next agh_localize_end or agh_synchronize). */
+ * keep the source until that begin's agh_localize_end, which waits for the copy too, or an agh_synchronize). */
 int agh_localize_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp);
 int agh_localize_stage(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n);
 int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,

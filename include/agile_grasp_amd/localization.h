@@ -256,12 +256,17 @@ public:
    *      loc.stageNextCloud(cloud_k1);                                                     // its upload runs under cloud k's kernels
    *      handles = loc.localizeHandlesEnd(&antipodal_hands);                               // the one synchronisation
    *      loc.localizeHandlesBegin(cloud_k1, ...);                                          // finds cloud k + 1 on the device
-   *  Same results as localizeHandles.  The clouds must stay alive and unchanged until the localizeHandlesEnd of their chain
+   *  Same results as localizeHandles.  A Begin while a chain is pending returns false and leaves that chain as it was.  The
+   *  clouds must stay alive and unchanged until the localizeHandlesEnd of their chain
    *  has returned (which then filters NaNs out of the searched cloud in place, as localization.cpp:27 does). */
   bool localizeHandlesBegin(const PointCloud::Ptr& cloud_in, int size_left, const std::vector<int>& indices,
     const std::string& svm_filename, int min_inliers, double min_length)
   {
-    pending_cloud_ = PointCloud::Ptr();
+    if (pending_cloud_)  // (one chain at a time: the one in flight stays pending, for its localizeHandlesEnd)
+    {
+      std::cout << " Error: localizeHandlesBegin while a chain is pending (localizeHandlesEnd first)\n";
+      return false;
+    }
     pending_three_calls_ = false;
     if (filters_boundaries_)  // (a host-side filter between the search and the classifier: the three calls, at End)
     {

@@ -1,8 +1,10 @@
 // localization_test.cpp -- drives the Localization facade (include/agile_grasp_amd/localization.h) on a RAW cloud
 // (NaNs, points outside the workspace, no voxelisation), like src/tests/test_local_axes.cpp drives the reference's.
-//   localization_test <raw.bin> <svm file> <mode: voxels|hands|antipodal>   (antipodal: src/tests/antipodal_test.cpp)
+//   localization_test <raw.bin> <svm file> <mode: voxels|hands|antipodal|chain|stream|rebegin>
+//   (antipodal: src/tests/antipodal_test.cpp)
 // raw.bin: int64 n, int64 size_left, int64 n_idx, double ws[6], double cam_left[3], double cam_right[3], n*3 float xyz,
 // n_idx int32 indices (into the voxelised cloud).
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -10,6 +12,20 @@
 #include "agile_grasp_amd/localization.h"
 
 using namespace agile_grasp_amd;
+
+// the same kept hands and the same handles (inlier lists included)
+static bool same_chain(const std::vector<GraspHypothesis>& kept, const std::vector<Handle>& handles,
+  const std::vector<GraspHypothesis>& kept1, const std::vector<Handle>& handles1)
+{
+  bool same = kept.size() == kept1.size() && handles.size() == handles1.size();
+  for (size_t i = 0; same && i < kept.size(); i++)
+    same = kept[i].getGraspSurface()(0) == kept1[i].getGraspSurface()(0) && kept[i].getGraspBottom()(1) == kept1[i].getGraspBottom()(1) &&
+           kept[i].getApproach()(2) == kept1[i].getApproach()(2) && kept[i].getGraspWidth() == kept1[i].getGraspWidth();
+  for (size_t i = 0; same && i < handles.size(); i++)
+    same = handles[i].getInliers() == handles1[i].getInliers() && handles[i].getAxis()(0) == handles1[i].getAxis()(0) &&
+           handles[i].getCenter()(1) == handles1[i].getCenter()(1) && handles[i].getWidth() == handles1[i].getWidth();
+  return same;
+}
 
 int main(int argc, char** argv)
 {
@@ -114,15 +130,43 @@ int main(int argc, char** argv)
       std::vector<Handle> handles = loc.localizeHandlesEnd(&kept);
       if (k + 1 < 3 && !loc.localizeHandlesBegin(clouds[k + 1], (int) size_left, idx, argv[2], 2, 0.005))
         return 5;
-      bool same = kept.size() == kept1.size() && handles.size() == handles1.size();
-      for (size_t i = 0; same && i < kept.size(); i++)
-        same = kept[i].getGraspSurface()(0) == kept1[i].getGraspSurface()(0) && kept[i].getGraspBottom()(1) == kept1[i].getGraspBottom()(1) &&
-               kept[i].getGraspWidth() == kept1[i].getGraspWidth();
-      for (size_t i = 0; same && i < handles.size(); i++)
-        same = handles[i].getInliers() == handles1[i].getInliers() && handles[i].getAxis()(0) == handles1[i].getAxis()(0) &&
-               handles[i].getCenter()(1) == handles1[i].getCenter()(1) && handles[i].getWidth() == handles1[i].getWidth();
-      std::printf("STREAM %d %zu %zu %d\n", k, kept.size(), handles.size(), same ? 1 : 0);
+      std::printf("STREAM %d %zu %zu %d\n", k, kept.size(), handles.size(), same_chain(kept, handles, kept1, handles1) ? 1 : 0);
     }
+    return 0;
+  }
+  if (std::strcmp(argv[3], "rebegin") == 0)
+  {
+    // localizeHandlesBegin while a chain is pending: refused, and the chain in flight stays pending.  Capture A is the cloud,
+    // capture B the same points in reverse order (another cloud with as many voxels, so the indices stay valid).
+    PointCloud::Ptr a(new PointCloud(*cloud)), a_again(new PointCloud(*cloud)), a_ref(new PointCloud(*cloud));
+    PointCloud::Ptr b(new PointCloud(*cloud));
+    std::reverse(b->points.begin(), b->points.end());
+    std::vector<GraspHypothesis> kept_a, kept_b_ref;
+    std::vector<Handle> handles_a = loc.localizeHandles(a_ref, (int) size_left, idx, argv[2], 2, 0.005, &kept_a);
+    Localization loc_b(1, false, 0);  // (B's results on an object of its own)
+    loc_b.setCameraTransforms(tl, tr);
+    loc_b.setWorkspace(w);
+    loc_b.setDeterministicNormalEstimation(true);
+    PointCloud::Ptr b_ref(new PointCloud(*b));
+    std::vector<Handle> handles_b_ref = loc_b.localizeHandles(b_ref, (int) size_left, idx, argv[2], 2, 0.005, &kept_b_ref);
+    std::printf("CHAIN1 %zu %zu\n", kept_a.size(), handles_a.size());
+    if (!loc.localizeHandlesBegin(a, (int) size_left, idx, argv[2], 2, 0.005))
+      return 3;
+    const bool b_refused = !loc.localizeHandlesBegin(b, (int) size_left, idx, argv[2], 2, 0.005);
+    const bool no_svm_refused = !loc.localizeHandlesBegin(a_again, (int) size_left, idx, "no_such_svm_file", 2, 0.005);
+    std::vector<GraspHypothesis> kept;
+    std::vector<Handle> handles = loc.localizeHandlesEnd(&kept);
+    std::printf("REBEGIN %d %d %zu %zu %d\n", b_refused ? 1 : 0, no_svm_refused ? 1 : 0, kept.size(), handles.size(),
+      same_chain(kept, handles, kept_a, handles_a) ? 1 : 0);
+    // the object is usable afterwards: B in one call, then a fresh Begin / End of A
+    std::vector<GraspHypothesis> kept_b;
+    std::vector<Handle> handles_b = loc.localizeHandles(b, (int) size_left, idx, argv[2], 2, 0.005, &kept_b);
+    PointCloud::Ptr a_fresh(new PointCloud(*cloud));
+    const bool begun = loc.localizeHandlesBegin(a_fresh, (int) size_left, idx, argv[2], 2, 0.005);
+    std::vector<GraspHypothesis> kept2;
+    std::vector<Handle> handles2 = loc.localizeHandlesEnd(&kept2);
+    std::printf("AFTER %zu %zu %d %d %d\n", kept_b.size(), handles_b.size(), same_chain(kept_b, handles_b, kept_b_ref, handles_b_ref) ? 1 : 0,
+      begun ? 1 : 0, same_chain(kept2, handles2, kept_a, handles_a) ? 1 : 0);
     return 0;
   }
   const bool antipodal = std::strcmp(argv[3], "antipodal") == 0;  // calculates_antipodal (antipodal_test.cpp:61)

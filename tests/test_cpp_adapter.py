@@ -267,6 +267,29 @@ def test_localization_stream_with_staged_uploads_equals_the_one_call(tmp_path):
 
 
 @pytest.mark.gpu
+def test_localization_second_begin_keeps_the_pending_chain(tmp_path):
+    """localizeHandlesBegin while a chain is pending returns false -- for another capture, and for a call that fails on its own
+    (a missing SVM file) -- and leaves the pending chain alone: its localizeHandlesEnd returns what localizeHandles returns, and
+    the object takes new chains afterwards."""
+    exe = _build_loc(tmp_path)
+    xyz, size_left, ws, cams = _raw_cloud()
+    vox, vcam = _preprocess_numpy(xyz, size_left, ws)
+    idx = np.sort(np.random.default_rng(1).permutation(len(vox))[:300]).astype(np.int32)
+    path = str(tmp_path / "raw.bin")
+    _dump_raw(path, xyz, size_left, idx, ws, cams)
+    out = subprocess.run([exe, path, os.path.join(GOLD, "svm_032015_linear_20_20_same"), "rebegin"], capture_output=True,
+                         text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = out.stdout.splitlines()
+    c1 = [l.split()[1:] for l in lines if l.startswith("CHAIN1")][0]
+    assert int(c1[0]) > 0
+    rb = [l.split()[1:] for l in lines if l.startswith("REBEGIN")][0]
+    assert rb == ["1", "1", c1[0], c1[1], "1"], (rb, c1)
+    after = [l.split()[1:] for l in lines if l.startswith("AFTER")][0]
+    assert after[2:] == ["1", "1", "1"], after  # B in one call as on an object of its own; then a fresh Begin / End of A
+
+
+@pytest.mark.gpu
 def test_localization_facade_antipodal_labels(tmp_path):
     """src/tests/antipodal_test.cpp: localizeHands with calculates_antipodal = true (all-points normals pass + 20 degree
     antipodal test); the half / full labels must be the ones the C ABI gives for the same voxelised cloud."""

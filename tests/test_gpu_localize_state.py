@@ -1,0 +1,139 @@
+"""The begin / stage / end localize chain (csrc/localize.hip, include/agh.h): between agh_localize_begin and agh_localize_end only
+agh_localize_stage and the calls agh.h lists may run on the context.  Every other entry point refuses with AGH_ERR_STATE before it
+touches a buffer, and the chain's results are then exactly those of an uninterrupted agh_localize."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+N_SAMPLES = 400
+SEED = 7
+
+
+@pytest.fixture(scope="module")
+def raw():
+    from agile_grasp_amd import synthetic
+
+    return synthetic.make_raw_cloud(40_000, seed=5)
+
+
+@pytest.fixture(scope="module")
+def uninterrupted(tiny_scene, svm_model, raw):
+    """agh_localize of the capture in one call, on a context of its own"""
+    from agile_grasp_amd import binding
+
+    ctx = binding.Context(tiny_scene.cam_origins)
+    ctx.load_svm(*svm_model)
+    ref = ctx.localize(raw.xyz, raw.size_left, raw.workspace, n_samples=N_SAMPLES, sample_seed=SEED, classify=True, min_inliers=2)
+    assert len(ref["hands"]) > 0
+    return ref
+
+
+def _same_chain(res, ref):
+    for k in ("handles", "inlier_idx", "samples"):
+        assert np.array_equal(res[k], ref[k]), k
+    hands, want = res["hands"], ref["hands"]
+    assert len(hands) == len(want)
+    for f in hands.dtype.names:
+        if f != "epoch":  # (the call's stamp)
+            assert np.array_equal(hands[f], want[f]), f
+    assert res["n_voxels"] == ref["n_voxels"] and res["n_hypotheses"] == ref["n_hypotheses"]
+
+
+def _prepared(tiny_scene, svm_model):
+    """A context that has searched, classified and trained before: every getter would have something to return."""
+    from agile_grasp_amd import binding
+
+    sc = tiny_scene
+    ctx = binding.Context(sc.cam_origins)
+    ctx.load_svm(*svm_model)
+    ctx.set_cloud(sc.xyz, sc.cam)
+    ctx.find_hands(sc.samples[:40], calculates_antipodal=True)
+    ctx.classify()
+    return ctx
+
+
+# every entry point that launches work on the context, or reads or changes its cloud, its device results or its model
+REFUSED = {
+    "set_cloud": lambda c, sc, m, ref: c.set_cloud(sc.xyz, sc.cam),
+    "set_cloud_batch": lambda c, sc, m, ref: c.set_cloud_batch([sc.xyz[:5000], sc.xyz[5000:]], [sc.cam[:5000], sc.cam[5000:]]),
+    "preprocess": lambda c, sc, m, ref: c.preprocess(sc.xyz, sc.xyz.shape[0] // 2, [-9, 9, -9, 9, -9, 9]),
+    "find_hands": lambda c, sc, m, ref: c.find_hands(sc.samples[:40]),
+    "classify": lambda c, sc, m, ref: c.classify(),
+    "find_handles": lambda c, sc, m, ref: c.find_handles(ref["hands"], 2),
+    "localize": lambda c, sc, m, ref: c.localize(sc.xyz, sc.xyz.shape[0] // 2, [-9, 9, -9, 9, -9, 9], n_samples=10),
+    "cloud": lambda c, sc, m, ref: c.cloud(),
+    "frames": lambda c, sc, m, ref: c.frames(),
+    "neighbor_counts": lambda c, sc, m, ref: c.neighbor_counts(),
+    "normals": lambda c, sc, m, ref: c.normals(),
+    "images": lambda c, sc, m, ref: c.images(),
+    "packed_images": lambda c, sc, m, ref: c.packed_images(),
+    "hog": lambda c, sc, m, ref: c.hog(),
+    "learning_points": lambda c, sc, m, ref: c.learning_points(0),
+    "epoch": lambda c, sc, m, ref: c.epoch(),
+    "load_svm": lambda c, sc, m, ref: c.load_svm(-m[0], -m[1]),  # (another model: the chain's labels would change)
+    "classify_images": lambda c, sc, m, ref: c.classify_images(np.zeros((4, 250), "<u4")),
+    "hog_images": lambda c, sc, m, ref: c.hog_images(np.zeros((4, 250), "<u4")),
+    "set_training_images": lambda c, sc, m, ref: c.set_training_images(True),
+    "plane_inliers": lambda c, sc, m, ref: c.plane_inliers(),
+    "set_profile": lambda c, sc, m, ref: c.set_profile(1),
+}
+
+
+@pytest.mark.parametrize("name", sorted(REFUSED))
+def test_a_call_between_begin_and_end_is_refused_and_changes_nothing(tiny_scene, svm_model, raw, uninterrupted, name):
+    from agile_grasp_amd import binding
+
+    ctx = _prepared(tiny_scene, svm_model)
+    ctx.localize_begin(raw.xyz, raw.size_left, raw.workspace, n_samples=N_SAMPLES, sample_seed=SEED, classify=True, min_inliers=2)
+    with pytest.raises(binding.AghError) as e:
+        REFUSED[name](ctx, tiny_scene, svm_model, uninterrupted)
+    assert e.value.code == binding.AGH_ERR_STATE
+    assert "in flight" in str(e.value), str(e.value)  # (refused for the chain, not for a precondition of its own)
+    _same_chain(ctx.localize_end(), uninterrupted)
+    # the context works as before once the chain is collected
+    _same_chain(ctx.localize(raw.xyz, raw.size_left, raw.workspace, n_samples=N_SAMPLES, sample_seed=SEED, classify=True,
+                             min_inliers=2), uninterrupted)
+
+
+def test_the_calls_allowed_between_begin_and_end(tiny_scene, svm_model, raw, uninterrupted):
+    """agh_synchronize, the host-side counters and agh_comm_rank stay allowed mid-chain and leave the chain alone."""
+    from agile_grasp_amd import binding
+
+    ctx = _prepared(tiny_scene, svm_model)
+    ctx.localize_begin(raw.xyz, raw.size_left, raw.workspace, n_samples=N_SAMPLES, sample_seed=SEED, classify=True, min_inliers=2)
+    ctx.synchronize()
+    ctx.timing(counts=True)
+    ctx.grid_stats()
+    assert ctx.comm_rank() == (0, 1)
+    assert ctx.selftest_math(1 << 10) == binding.AGH_ERR_STATE  # (it launches work on the context: refused)
+    _same_chain(ctx.localize_end(), uninterrupted)
+
+
+def test_a_dropped_staged_capture_and_a_restaged_buffer(tiny_scene, svm_model):
+    """agh_localize_stage(X), then a begin of another capture Y drops X (the chain waits for X's copy, so that agh_localize_end
+    covers it).  The same buffer, refilled with new content and staged again, is adopted by the next begin: the results are
+    those of a one-call localize of the new content."""
+    from agile_grasp_amd import binding, synthetic
+
+    x = synthetic.make_raw_cloud(40_000, seed=5)
+    y = synthetic.make_raw_cloud(40_000, seed=6)
+    z = synthetic.make_raw_cloud(40_000, seed=9)
+    m = min(x.xyz.shape[0], z.xyz.shape[0])
+    kw = dict(n_samples=N_SAMPLES, sample_seed=SEED, classify=True, min_inliers=2)
+    one = binding.Context(tiny_scene.cam_origins)
+    one.load_svm(*svm_model)
+    ref_y = one.localize(y.xyz, y.size_left, y.workspace, **kw)
+    ref_z = one.localize(z.xyz[:m], z.size_left, z.workspace, **kw)
+    assert len(ref_z["hands"]) > 0
+
+    ctx = binding.Context(tiny_scene.cam_origins)
+    ctx.load_svm(*svm_model)
+    buf = np.ascontiguousarray(x.xyz[:m], np.float32)
+    ctx.localize_stage(buf)
+    ctx.localize_begin(y.xyz, y.size_left, y.workspace, **kw)  # not the staged capture: X is dropped
+    _same_chain(ctx.localize_end(), ref_y)
+    buf[:] = z.xyz[:m]  # the same buffer (pointer, stride, count), new content
+    assert ctx.localize_stage(buf) is buf
+    ctx.localize_begin(buf, z.size_left, z.workspace, **kw)  # adopted
+    _same_chain(ctx.localize_end(), ref_z)

@@ -655,3 +655,169 @@ def test_a_rank_that_cannot_classify_fails_the_call_on_every_rank(tiny_scene, sv
     _run_ranks(ctxs, lambda r, c: c.find_hands_sharded(sc.samples))
     keeps = [k for _, k in _run_ranks(ctxs, lambda r, c: c.classify_sharded())]
     assert all(np.array_equal(k, keeps[0]) for k in keeps) and keeps[0].size > 0
+
+
+# ---- a peer failure in a call that would repeat: every rank returns with that call ----
+# Run in a child process: were a rank to go on into the next attempt's all-gathers alone, its peers would wait in the in-process
+# barrier, whose timeout is read once per process (AGH_LOCAL_BARRIER_TIMEOUT_S).  The child reports what every rank returned.
+_PEER_FAILURE_CHILD = r"""
+import json, os, sys, time
+sys.path.insert(0, os.getcwd())
+import numpy as np
+from agile_grasp_amd import binding, synthetic
+from tests.test_gpu_sharding import FIELDS, _group, _run_ranks, _run_ranks_codes
+
+case, site = sys.argv[1], int(sys.argv[2])
+sc = synthetic.config("small")  # over-dense: its neighbourhoods need the 4096 class, so its first sharded call repeats
+one = binding.Context(sc.cam_origins)
+one.set_cloud(sc.xyz, sc.cam)
+ref = one.find_hands(sc.samples)
+same = lambda h: len(h) == len(ref) and all(np.array_equal(h[f], ref[f]) for f in FIELDS)
+ctxs = _group(sc, 3)
+out = {}
+if case == "overflow":  # the classes are on everywhere; then segments far too small: the call would repeat with full segments
+    out["warm"] = all(same(h) for h in _run_ranks(ctxs, lambda r, c: c.find_hands_sharded(sc.samples)))
+    for c in ctxs:
+        c.comm_set_segment_records(8)
+ctxs[1].comm_inject_fault(site)
+t0 = time.time()
+if case == "device":
+    import torch
+
+    S = sc.samples.size
+    s_t = torch.from_numpy(sc.samples).cuda()
+    bufs = [(torch.zeros(8 * S * 160, dtype=torch.uint8, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda"))
+            for _ in ctxs]
+
+    def dev(r, c):
+        c.find_hands_sharded_torch(s_t, bufs[r][0], bufs[r][1])
+        c.synchronize()  # (device variants report the merged flags here)
+
+    res = _run_ranks_codes(ctxs, dev)
+else:
+    res = _run_ranks_codes(ctxs, lambda r, c: c.find_hands_sharded(sc.samples))
+out["seconds"] = time.time() - t0
+out["codes"] = [code for _, code in res]
+if case == "classify":  # after that failed search: classify_sharded fails on every rank too, and returns no list
+    for c in ctxs:
+        c.load_svm(np.ones(3528, np.float32), 0.0)
+        c.shard_n = 0  # (no list came back)
+    t0 = time.time()
+    res = _run_ranks_codes(ctxs, lambda r, c: c.classify_sharded())
+    out["classify_seconds"] = time.time() - t0
+    out["classify_codes"] = [code for _, code in res]
+    out["classify_lists"] = [v is not None for v, _ in res]
+follow = _run_ranks_codes(ctxs, lambda r, c: c.find_hands_sharded(sc.samples))
+out["follow_codes"] = [code for _, code in follow]
+out["follow_same"] = [bool(code == 0 and same(h)) for h, code in follow]
+out["segment_bytes"] = [c.comm_last_exchange()[0] for c in ctxs]
+print(json.dumps(out))
+"""
+
+
+@pytest.mark.parametrize("case, site", [("host", 1), ("host", 2), ("host", 16), ("device", 2), ("overflow", 2),
+                                        ("classify", 16)])
+def test_a_peer_failure_in_a_call_that_would_repeat_returns_on_every_rank(case, site):
+    """ADVICE r6 item 1.  Rank 1 fails on its own in the same call where the others' slices ask for a larger capacity class
+    (small_scene's first sharded call) or for full segments ("overflow").  The peer failure is checked before the repeat: every
+    rank returns with this call -- rank 1 its own AGH_ERR_HIP, the others AGH_ERR_STATE -- none switches big_classes or
+    shard_full_exchange on it, and the next call agrees on everything and returns the single-context list on every rank.
+    ("classify": after such a failed search, agh_classify_sharded fails on every rank too, with rank 1 taking part.)"""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from agile_grasp_amd import binding
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, AGH_LOCAL_BARRIER_TIMEOUT_S="60")
+    p = subprocess.run([sys.executable, "-c", _PEER_FAILURE_CHILD, case, str(site)], cwd=root, env=env, capture_output=True,
+                       text=True, timeout=400)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    assert out.get("warm", True)
+    assert out["codes"][1] == binding.AGH_ERR_HIP and out["codes"][0] == out["codes"][2] == binding.AGH_ERR_STATE, out
+    assert out["seconds"] < 30, out  # (returned together, not released by the 60 s barrier timeout)
+    if case == "classify":
+        assert all(code != 0 for code in out["classify_codes"]) and not any(out["classify_lists"]), out
+        assert out["classify_seconds"] < 30, out
+    assert out["follow_codes"] == [0, 0, 0] and all(out["follow_same"]), out
+    assert len(set(out["segment_bytes"])) == 1, out
+
+
+# ---- agh_classify_sharded after a classification that failed on one rank (ADVICE r6 item 2) ----
+def _classify_ref(sc, svm_model):
+    from agile_grasp_amd import binding
+
+    one = binding.Context(sc.cam_origins)
+    one.set_cloud(sc.xyz, sc.cam)
+    one.load_svm(*svm_model)
+    ref = one.find_hands(sc.samples)
+    return ref, one.classify()
+
+
+@pytest.mark.parametrize("how", ["no_svm", "site8"])
+def test_a_failed_classification_leaves_no_stale_failure_behind(tiny_scene, svm_model, how):
+    """A classification that failed on one rank marks that rank's segment header; the in-place all-gather never rewrites a
+    rank's own segment, so the mark used to outlive the call and fail every later classification of the same search.  A
+    corrected repeat -- with no search in between -- returns the single-context labels on every rank."""
+    from agile_grasp_amd import binding
+
+    sc = tiny_scene
+    ref, keep_ref = _classify_ref(sc, svm_model)
+    assert keep_ref.any() and not keep_ref.all()
+    ctxs = _group(sc, 3)
+    for r in (0, 2):
+        ctxs[r].load_svm(*svm_model)
+    if how == "site8":
+        ctxs[1].load_svm(*svm_model)
+        ctxs[1].comm_inject_fault(8)
+    for hyps in _run_ranks(ctxs, lambda r, c: c.find_hands_sharded(sc.samples)):
+        _same(hyps, ref)
+    res = _run_ranks_codes(ctxs, lambda r, c: c.classify_sharded())
+    codes = [code for _, code in res]
+    want = binding.AGH_ERR_NO_SVM if how == "no_svm" else binding.AGH_ERR_HIP
+    assert codes[1] == want and codes[0] == codes[2] == binding.AGH_ERR_STATE, codes
+    if how == "no_svm":
+        ctxs[1].load_svm(*svm_model)
+    for recs, keep in _run_ranks(ctxs, lambda r, c: c.classify_sharded()):  # no search in between
+        _same(recs, ref)
+        assert np.array_equal(keep, keep_ref)
+
+
+# ---- a localize chain in flight on one rank (include/agh.h: only agh_localize_stage between begin and end) ----
+def test_a_rank_with_a_localize_chain_in_flight_takes_part_without_touching_it(tiny_scene, svm_model):
+    """Rank 1 has a localize chain in flight.  The sharded search and classification may not return on it before their
+    collectives: it takes part without searching (its flags and count in scratch of its own), every rank returns an error,
+    the chain's results are those of an uninterrupted agh_localize, and the communicator works afterwards."""
+    from agile_grasp_amd import binding, synthetic
+
+    sc = tiny_scene
+    raw = synthetic.make_raw_cloud(40_000, seed=5)
+    kw = dict(n_samples=60, sample_seed=7, classify=True, min_inliers=2)
+    solo = binding.Context(sc.cam_origins)
+    solo.load_svm(*svm_model)
+    chain_ref = solo.localize(raw.xyz, raw.size_left, raw.workspace, **kw)
+    ref, keep_ref = _classify_ref(sc, svm_model)
+
+    ctxs = _group(sc, 3)
+    for c in ctxs:
+        c.load_svm(*svm_model)
+    for recs, keep in _run_ranks(ctxs, lambda r, c: (c.find_hands_sharded(sc.samples), c.classify_sharded())[1]):
+        _same(recs, ref)
+    ctxs[1].localize_begin(raw.xyz, raw.size_left, raw.workspace, **kw)
+    res = _run_ranks_codes(ctxs, lambda r, c: c.classify_sharded())  # (of the search before the chain)
+    assert all(v is None for v, _ in res) and [code for _, code in res] == [binding.AGH_ERR_STATE] * 3, res
+    res = _run_ranks_codes(ctxs, lambda r, c: c.find_hands_sharded(sc.samples))
+    assert all(v is None for v, _ in res) and [code for _, code in res] == [binding.AGH_ERR_STATE] * 3, res
+    got = ctxs[1].localize_end()
+    for k in ("handles", "inlier_idx", "samples"):
+        assert np.array_equal(got[k], chain_ref[k]), k
+    _same(got["hands"], chain_ref["hands"])  # (every field but the call's stamp)
+    assert len(got["hands"]) > 0
+    assert got["n_hypotheses"] == chain_ref["n_hypotheses"]
+    ctxs[1].set_cloud(sc.xyz, sc.cam)  # (the chain searched its own cloud)
+    for recs, keep in _run_ranks(ctxs, lambda r, c: (c.find_hands_sharded(sc.samples), c.classify_sharded())[1]):
+        _same(recs, ref)
+        assert np.array_equal(keep, keep_ref)
