@@ -313,7 +313,9 @@ int agh_find_hands(agh_ctx* ctx, const int32_t* sample_idx, int64_t n_samples, i
   agh_hypothesis* out, int64_t cap, int64_t* n_out);
 /* Same, everything device-resident and asynchronous on hip_stream (NULL = the context's stream):
  * d_out has room for cap records, *d_n_out (device int64) receives the count.  Device-side errors (capacity, a sample
- * index outside the cloud, AGH_ERR_RETRY) are reported by the next agh_synchronize. */
+ * index outside the cloud, AGH_ERR_RETRY) are reported by the next agh_synchronize.  A list longer than cap is
+ * AGH_ERR_CAPACITY there; *d_n_out then holds its full length and d_out its first cap records.  The host variant
+ * returns AGH_ERR_CAPACITY at once, with *n_out = the full length (cap = 0 and out = NULL ask for it). */
 int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_samples, int calculates_antipodal,
   agh_hypothesis* d_out, int64_t cap, int64_t* d_n_out, void* hip_stream);
 

@@ -330,7 +330,8 @@ def test_capacity_overflow_is_loud():
 
 
 def test_large_neighbourhood_classes(tiny_scene):
-    """Neighbourhoods between 1024 and 2048 points go through the second LDS capacity class."""
+    """Neighbourhoods beyond 1152 points (and at most 4096) go through the 4096 class of K1a and K1c, the first sample
+    beyond 1152 switching the larger classes on (AGH_ERR_RETRY inside the host entry point)."""
     from oracle import oracle_py as O
 
     rng = np.random.default_rng(3)
@@ -348,7 +349,7 @@ def test_large_neighbourhood_classes(tiny_scene):
     samples = np.sort(np.argsort(d)[:6]).astype(np.int32)
     hyps = ctx.find_hands(samples)
     ref = O.find_hands(O.default_params(cams), xyz, cam, samples)
-    assert ref["frames"]["n_nb"].max() > 1024
+    assert 1152 < ref["frames"]["n_nb"].max() <= 4096
     assert_frames_equal(ctx.frames(), ref["frames"])
     assert_hyps_equal(hyps, ref["hyps"])
 
@@ -432,8 +433,8 @@ def test_full_size_c2_against_oracle(svm_model):
 @pytest.mark.parametrize("name", ["C1", "C4", "C5_0", "C2u"])
 def test_full_size_other_configs_against_oracle(svm_model, name):
     """The BASELINE configs besides C2/C3, whole result list (frames, hypotheses, SVM labels) bit-identical to the oracle:
-    C1 (single view, 50k points, 500 samples: every point from camera 0), C4 (1M points, 8000 samples: multi-tile sweeps
-    with the parked-points path, the 4096-point moments class, the large scheduling sort), C5_0 (first cloud of the
+    C1 (single view, 50k points, 500 samples: every point from camera 0), C4 (1M points, 8000 samples: sweeps that stream
+    several LDS tiles, the 4096-point moments class, the large scheduling sort), C5_0 (first cloud of the
     batch, seed 10), C2u (SURVEY 8d's generator taken literally: the axis-aligned C2 scene, two thirds of whose Taubin
     neighbourhoods are exactly planar -- the exhaustive argmax of quadric.cpp:283-284, deterministic normals)."""
     from agile_grasp_amd import synthetic
