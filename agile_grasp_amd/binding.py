@@ -153,7 +153,8 @@ def save_svm_file(path: str, w: np.ndarray, rho: float, kernel: int = SVM_LINEAR
 class AghLocalizeParams(C.Structure):
     _fields_ = [("size_left", C.c_int64), ("dense", C.c_int32), ("classify", C.c_int32), ("workspace", C.c_double * 6),
                 ("cell_size", C.c_double), ("sample_idx", C.POINTER(C.c_int32)), ("n_samples", C.c_int64),
-                ("sample_seed", C.c_uint64), ("min_inliers", C.c_int32), ("reserved", C.c_int32), ("min_length", C.c_double)]
+                ("sample_seed", C.c_uint64), ("min_inliers", C.c_int32), ("filters_boundaries", C.c_int32),
+                ("min_length", C.c_double)]
 
 
 class AghLocalizeResult(C.Structure):
@@ -360,9 +361,11 @@ class Context:
 
     def localize(self, xyz, size_left: int, workspace, samples=None, n_samples: int = 0, sample_seed: int = 1,
                  classify: bool = True, min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003,
-                 dense: bool = False, phase: str = "both"):
+                 dense: bool = False, phase: str = "both", filters_boundaries: bool = False):
         """agh_localize: raw capture -> voxels -> search -> SVM -> handles in one call with one synchronisation
         (grasp_localizer.cpp:95-103).  `samples`: indices into the voxelised cloud, or None: n_samples are drawn on the device.
+        filters_boundaries: Localization::filterHands (hands within 2 cm of a face of `workspace` dropped) between the search
+        and the classifier; an int passes through as is (the library refuses anything but 0 and 1).
         Returns a dict: handles, inlier_idx, hands (what the handle search ran on), samples, n_voxels, n_hypotheses."""
         on_device = hasattr(xyz, "is_cuda") and xyz.is_cuda  # a torch CUDA tensor (N, >= 3) float32: agh_localize_device
         if on_device:
@@ -387,6 +390,7 @@ class Context:
             lp.sample_idx = None
             S = int(n_samples)
         lp.n_samples, lp.sample_seed, lp.min_inliers, lp.min_length = S, sample_seed, min_inliers, min_length
+        lp.filters_boundaries = int(filters_boundaries)
         bufs = getattr(self, "_loc_bufs", None)
         hcap = max(min(8 * S, 8192), 1)
         if bufs is None or bufs[0].shape[0] < hcap or bufs[3].shape[0] < max(S, 1):

@@ -134,6 +134,27 @@ struct HostMirror
   int64_t* hdr;         // [0] hypotheses found, [1] flags[0] as the kernel saw it
 };
 
+// Localization::filterHands (localization.cpp:364-388) as a stage of the localize chain: a hypothesis whose grasp surface lies
+// closer than MIN_DIST to a face of the workspace box is dropped before the classifier.  The box reaches the kernels by value;
+// on = 0 is "no filter" (agh_classify*, the sharded calls, a chain without filters_boundaries).
+constexpr double kBoundaryMinDist = 0.02;  // MIN_DIST (localization.cpp:366)
+struct BoundaryBox
+{
+  double ws[6];  // {xmin, xmax, ymin, ymax, zmin, zmax}: the workspace the preprocessing cropped with
+  int32_t on;
+};
+inline BoundaryBox boundary_box(const double* ws)  // ws == nullptr: off
+{
+  BoundaryBox b{};
+  if (ws)
+  {
+    for (int k = 0; k < 6; k++)
+      b.ws[k] = ws[k];
+    b.on = 1;
+  }
+  return b;
+}
+
 // agh_localize_begin / _stage / _end (api.hip): the one chain in flight and the capture staged for the next one
 struct LocalizeState
 {
@@ -141,6 +162,7 @@ struct LocalizeState
   bool repeated = false;      // inside the one repeat of a whole call (the voxel lattice outgrew the speculative bitmap)
   bool deferred = false;      // the voxel count is still on the device
   bool classify = false, with_sequential = false, explicit_samples = false;
+  bool filters = false;       // filters_boundaries: Localization::filterHands between the search and the classifier
   int64_t S = 0, nv = 0;
   int32_t min_inliers = 0;
   double min_length = 0.0, x1 = 0.0, x2 = 0.0;
@@ -451,12 +473,14 @@ int hand_sweep(Ctx* c, const int32_t* d_samples, int64_t S, bool use_normals, hi
 int ball_counts(Ctx* c, int64_t S, hipStream_t st);  // d_nh of the last call's samples (agh_get_neighbor_counts)
 int compact_hypotheses(Ctx* c, int64_t S, agh_hypothesis* d_out, int64_t cap, int64_t* d_nout, hipStream_t st,
   int64_t* d_hdr_flags = nullptr);  // d_hdr_flags: sharded search, slices of at most 65536 samples (see shard.hip)
-int hog_svm(Ctx* c, int64_t n_hyp_cap, uint8_t* d_keep, hipStream_t st);
+// ws: the workspace of a chain with filters_boundaries (the hypotheses near its faces are labelled 0 and not classified), or null
+int hog_svm(Ctx* c, int64_t n_hyp_cap, uint8_t* d_keep, hipStream_t st, const double* ws = nullptr);
 int hog_images(Ctx* c, const uint32_t* d_images, const int32_t* d_order, int64_t n, float* d_desc, hipStream_t st);
-int svm_predict_general(Ctx* c, const float* d_desc, int64_t cap, uint8_t* d_keep, hipStream_t st);
+int svm_predict_general(Ctx* c, const float* d_desc, int64_t cap, uint8_t* d_keep, hipStream_t st,
+  const BoundaryBox& box = BoundaryBox{});
 int svm_predict_images(Ctx* c, const float* d_desc, int64_t n, uint8_t* d_keep, double* d_sums, hipStream_t st);
 int svm_predict_desc(Ctx* c, const float* d_desc, int64_t cap, const int64_t* d_nhyp, agh_hypothesis* d_out, uint8_t* d_keep,
-  double* d_sums, hipStream_t st);
+  double* d_sums, hipStream_t st, const BoundaryBox& box = BoundaryBox{});
 int svm_load_general(Ctx* c, int kernel_type, const float* sv, int n_sv, const double* alpha, double rho);
 void hog_tables_host(HogTablesDev* t);
 int64_t selftest_math(Ctx* c, int64_t n, uint64_t seed);
@@ -494,6 +518,18 @@ void plane_release(Ctx* c);
 
 // ---- device helpers ----
 #if defined(__HIPCC__)
+
+// Localization::filterHands' test (localization.cpp:374-378) on a record's own doubles: true iff some face k of the box is
+// closer than MIN_DIST, |surface[k / 2] - ws[k]| < 0.02, strictly.  Exact IEEE (no contraction, no fast math: the build's
+// flags), so it agrees with the host filterHands bit for bit; a NaN surface compares false everywhere and is kept, as there.
+__device__ __forceinline__ bool near_workspace_boundary(const double* surface, const double* ws)
+{
+  bool near = false;
+#pragma unroll
+  for (int k = 0; k < 6; k++)
+    near |= fabs(surface[k >> 1] - ws[k]) < kBoundaryMinDist;
+  return near;
+}
 
 __device__ __forceinline__ unsigned enc_float(float f)
 {

@@ -52,10 +52,12 @@ __global__ void k_draw_samples(const int* __restrict__ cloud_off, int n_clouds, 
     host_out[k] = v;
 }
 // The hands Learning::classify kept (svm_keep; all of them if !use_keep), in list order (learning.cpp:236-243), as the handle
-// search's input -- and a second time into pinned host memory.  One work-group: an ordered compaction is a scan.
+// search's input -- and a second time into pinned host memory.  One work-group: an ordered compaction is a scan.  box.on (a
+// chain with filters_boundaries and no classifier): the hands Localization::filterHands drops are left out too (with the
+// classifier their svm_keep is 0 already).
 // host_counts: [4] hypotheses, [5] kept, [6] the search's error word.
 __global__ __launch_bounds__(1024) void k_compact_kept(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
-  int64_t cap_in, int use_keep, agh_hypothesis* __restrict__ out, int out_cap, int* __restrict__ n_out,
+  int64_t cap_in, int use_keep, BoundaryBox box, agh_hypothesis* __restrict__ out, int out_cap, int* __restrict__ n_out,
   agh_hypothesis* __restrict__ host_out, int host_cap, int* __restrict__ host_counts, const int32_t* __restrict__ flags)
 {
   constexpr int kList = 8192;  // (the handle search takes no more)
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(1024) void k_compact_kept(const agh_hypothesis* __r
   for (int64_t b0 = 0; b0 < n; b0 += 1024)
   {
     const int64_t i = b0 + tid;
-    const bool keep = i < n && (!use_keep || in[i].svm_keep != 0);
+    const bool keep = i < n && (!use_keep || in[i].svm_keep != 0) && !(box.on && near_workspace_boundary(in[i].surface, box.ws));
     const unsigned long long m = __ballot(keep);
     if (lane == 0)
       wsum[wave] = __popcll(m);
@@ -277,11 +279,14 @@ static int localize_queue(agh_ctx* ctx, bool handles_only)
     c->mirror = HostMirror{ nullptr, 0, nullptr };
     if ((rc = agh_find_hands_device(ctx, c->d_idx_own, L.S, 0, c->d_out_own, c->s_cap * 8, c->d_nout, st)) != AGH_OK)
       return rc;
-    if (L.classify && (rc = agh_classify_device(ctx, c->d_keep, st)) != AGH_OK)
+    // (filters_boundaries: the classifier labels the hands near the workspace's faces 0 without classifying them; without it,
+    // the compaction drops them)
+    const double* ws = L.filters ? L.lp.workspace : nullptr;
+    if (L.classify && (rc = hog_svm(c, std::min<int64_t>(c->last_s * 8, c->last_cap), c->d_keep, st, ws)) != AGH_OK)
       return rc;
     hipLaunchKernelGGL(k_compact_kept, dim3(1), dim3(1024), 0, st, (const agh_hypothesis*) c->d_out_own, (const int64_t*) c->d_nout,
-      c->s_cap * 8, L.classify ? 1 : 0, c->d_h_hands, (int) hand_bound, d_hcount, h_hands, (int) c->h_pin_handles_cap, h_counts,
-      (const int32_t*) c->d_flags);
+      c->s_cap * 8, L.classify ? 1 : 0, boundary_box(L.classify ? nullptr : ws), c->d_h_hands, (int) hand_bound, d_hcount, h_hands,
+      (int) c->h_pin_handles_cap, h_counts, (const int32_t*) c->d_flags);
     if (hipGetLastError() != hipSuccess)
     {
       c->err = "k_compact_kept launch failed";
@@ -311,6 +316,11 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
       lp->size_left < 0 || lp->n_samples < 0 || lp->n_samples > (1 << 24) || lp->min_inliers < 1)
   {
     c->err = "agh_localize: bad arguments (see include/agh.h)";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  if (lp->filters_boundaries != 0 && lp->filters_boundaries != 1)
+  {
+    c->err = "agh_localize: filters_boundaries must be 0 or 1";
     return AGH_ERR_INVALID_ARGUMENT;
   }
   if (lp->classify && !c->has_svm)
@@ -369,6 +379,7 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   }
   L.S = S;
   L.classify = lp->classify != 0;
+  L.filters = lp->filters_boundaries != 0;
   L.min_inliers = lp->min_inliers;
   L.min_length = lp->min_length;
   L.lp = *lp;
@@ -559,7 +570,7 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
       if (rc != AGH_OK)
         return rc;
     }
-    if (h_counts[2] == 2 || h_counts[5] > 8192)
+    if (h_counts[2] == 2 || h_counts[5] > 8192)  // ([5]: the hands that survived the classifier and the boundary filter)
     {
       c->err = "agh_localize: more than 8192 hands for the handle search (classify first, or search fewer samples)";
       return AGH_ERR_CAPACITY;

@@ -3,13 +3,15 @@
 //
 //   g++ -std=c++11 -O2 -Iinclude examples/localize_pcd.cpp -o localize_pcd -Lagile_grasp_amd/lib -lagile_grasp_hip
 //       -Wl,-rpath,$PWD/agile_grasp_amd/lib -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
-//   ./localize_pcd <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]
+//   ./localize_pcd [--filters-boundaries] <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]
 //
 // Parameters are the node's defaults (find_grasps.cpp:10-21): finger width 0.01, outer diameter 0.09, hand depth 0.06,
 // hand height 0.02, init bite 0.01, 2000 samples, workspace [0.65 0.9 -0.1 0.1 -0.2 1.0], min_inliers 3, camera poses
-// of find_grasps.cpp:35-45.
+// of find_grasps.cpp:35-45.  --filters-boundaries builds the Localization as the nodes do (grasp_localizer.cpp:21,
+// nodes/test.cpp:72): hands within 2 cm of a face of the workspace are dropped before the classifier.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -19,9 +21,16 @@ using namespace agile_grasp_amd;
 
 int main(int argc, char** argv)
 {
+  const bool filters_boundaries = argc > 1 && std::strcmp(argv[1], "--filters-boundaries") == 0;
+  if (filters_boundaries)
+  {
+    argv[1] = argv[0];
+    argv++;
+    argc--;
+  }
   if (argc < 3)
   {
-    std::printf("usage: %s <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]\n", argv[0]);
+    std::printf("usage: %s [--filters-boundaries] <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]\n", argv[0]);
     return 2;
   }
   const std::string svm = argv[1], left = argv[2], right = argc > 3 ? argv[3] : "";
@@ -36,7 +45,7 @@ int main(int argc, char** argv)
     cam_left(r, 3) = tl[r];
     cam_right(r, 3) = tr[r];
   }
-  Localization loc(4, false, 0);  // num_threads (unused on the GPU), filters_boundaries, plotting mode
+  Localization loc(4, filters_boundaries, 0);  // num_threads (unused on the GPU), filters_boundaries, plotting mode
   loc.setCameraTransforms(cam_left, cam_right);
   VectorXd ws(6);
   const double w[6] = { 0.65, 0.9, -0.1, 0.1, -0.2, 1.0 };

@@ -204,6 +204,14 @@ int agh_find_handles(agh_ctx* ctx, const agh_hypothesis* hands, int64_t n_hands,
  * classify != 0: Learning::classify between the search and the handle search (needs agh_load_svm*); 0: every hypothesis
  * is handed to the handle search (at most 8192).
  * hands_out (optional, hands_cap records): the hands the handle search ran on, in list order -- inlier_idx_out indexes them.
+ * filters_boundaries != 0 (1; any other value but 0 is AGH_ERR_INVALID_ARGUMENT): Localization::filterHands
+ * (localization.cpp:364-388) between the search and the classifier, as the reference's nodes run it (grasp_localizer.cpp:21,
+ * nodes/test.cpp:72) -- a hypothesis whose grasp surface lies closer than MIN_DIST = 0.02 to a face of `workspace` (the box the
+ * preprocessing crops with), |surface[k / 2] - workspace[k]| < 0.02 for some k, is dropped.  The results then equal
+ * agh_find_hands -> filterHands -> agh_classify -> agh_find_handles on the same samples, bit for bit: hands_out, n_hands and
+ * inlier_idx_out refer to the filtered (and, with classify, kept) list; n_hypotheses stays the search's unfiltered count; the
+ * 8192-hand limit of the handle search counts the hands that survive the filter.  A filtered hypothesis is never classified:
+ * its device-side record carries svm_keep = 0, and no HOG descriptor or SVM sum is computed for it.
  * After the call the context holds the voxelised cloud and the search's results like after the separate calls
  * (agh_get_cloud, agh_get_frames, agh_get_images ...). */
 typedef struct agh_localize_params
@@ -217,7 +225,7 @@ typedef struct agh_localize_params
   int64_t n_samples;
   uint64_t sample_seed;
   int32_t min_inliers;     /* grasp_localizer.cpp:103: from the launch file */
-  int32_t reserved;
+  int32_t filters_boundaries; /* 0: off; 1: Localization::filterHands between the search and the classifier (above) */
   double min_length;       /* 0.005 */
 } agh_localize_params;
 typedef struct agh_localize_result
@@ -452,6 +460,9 @@ int agh_get_frames(agh_ctx* ctx, agh_frame* out, int64_t cap);
  * only visits the slab of that ball the hand can occupy. */
 int agh_get_neighbor_counts(agh_ctx* ctx, int32_t* n_taubin, int32_t* n_hands, int64_t cap);
 int agh_get_images(agh_ctx* ctx, uint8_t* images, int64_t cap_hyp); /* cap_hyp x 8000 bytes, 80 rows x 100 cols */
+/* agh_get_hog recomputes the descriptors and SVM sums of every hypothesis of the last search on demand (a chain with
+ * filters_boundaries computed none for the hypotheses it filtered; this getter does, unfiltered, and relabels svm_keep of the
+ * device-side records as agh_classify does). */
 int agh_get_hog(agh_ctx* ctx, float* desc, double* sums, int64_t cap_hyp); /* cap_hyp x 3528 floats (+ SVM sums) */
 int agh_get_normals(agh_ctx* ctx, double* normals, int64_t cap_points);  /* cloud_normals_ (3 doubles per point) */
 /* GraspHypothesis::getPointsForLearning and the split of its columns by camera (grasp_hypothesis.h:149-170; filled at

@@ -317,16 +317,19 @@ public:
   /** The online chain of grasp_localizer.cpp:95-103 -- preprocessing, search, Learning::classify, HandleSearch -- as ONE device
    *  call with one synchronisation (agh_localize): the raw capture goes in, the hands the classifier kept, the handles and
    *  their inlier lists come out as records.  indices empty: num_samples indices are drawn ON THE DEVICE (one per stratum of
-   *  the voxelised cloud, seeded like randomSample: setSampleSeed or the clock).
+   *  the voxelised cloud, seeded like randomSample: setSampleSeed or the clock).  filters_boundaries: Localization::filterHands
+   *  (the hands within 2 cm of a face of `workspace`) between the search and the classifier, on the device.
    *  @return false (after printing) on error */
   bool localize(const PointCloud::Ptr& cloud_in, int size_left, const VectorXd& workspace, double cell_size,
     const std::vector<int>& indices, const std::string& svm_filename, int min_inliers, double min_length,
-    std::vector<agh_hypothesis>& hands_out, std::vector<agh_handle>& handles_out, std::vector<std::int32_t>& inliers_out)
+    std::vector<agh_hypothesis>& hands_out, std::vector<agh_handle>& handles_out, std::vector<std::int32_t>& inliers_out,
+    bool filters_boundaries = false)
   {
     hands_out.clear();
     handles_out.clear();
     inliers_out.clear();
-    return localizeBegin(cloud_in, size_left, workspace, cell_size, indices, svm_filename, min_inliers, min_length) &&
+    return localizeBegin(cloud_in, size_left, workspace, cell_size, indices, svm_filename, min_inliers, min_length,
+             filters_boundaries) &&
            localizeEnd(hands_out, handles_out, inliers_out);
   }
 
@@ -335,7 +338,8 @@ public:
    *  localizeBegin that is later handed the same cloud object finds it on the device.  One chain may be in flight; `cloud_in`
    *  must stay alive and unchanged until localizeEnd has returned. */
   bool localizeBegin(const PointCloud::Ptr& cloud_in, int size_left, const VectorXd& workspace, double cell_size,
-    const std::vector<int>& indices, const std::string& svm_filename, int min_inliers, double min_length)
+    const std::vector<int>& indices, const std::string& svm_filename, int min_inliers, double min_length,
+    bool filters_boundaries = false)
   {
     if (!ensureContext())
       return false;
@@ -356,7 +360,7 @@ public:
     lp.n_samples = idx.empty() ? (std::int64_t) (num_samples_ < 0 ? 0 : num_samples_) : (std::int64_t) idx.size();
     lp.sample_seed = sample_seed_set_ ? (std::uint64_t) sample_seed_ : (std::uint64_t) std::time(nullptr);
     lp.min_inliers = min_inliers;
-    lp.reserved = 0;
+    lp.filters_boundaries = filters_boundaries ? 1 : 0;
     lp.min_length = min_length;
     loc_cap_ = lp.n_samples * 8 < 8192 ? lp.n_samples * 8 + 1 : 8193;
     last_samples_.assign((std::size_t) lp.n_samples, 0);

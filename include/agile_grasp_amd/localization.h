@@ -238,8 +238,9 @@ public:
    *  -- as ONE call into the device library with one synchronisation (agh_localize: no host round trip of the hypotheses
    *  between the stages).  Same handles as the three calls on the same sample indices; with `indices` empty the samples are
    *  drawn on the device (see HandSearch::localize).  The hands the classifier kept come back through `antipodal_hands`
-   *  (Handle::getHandList of every handle is that list).  With setFiltersBoundaries(true) -- a host-side filter BETWEEN the
-   *  search and the classifier -- the three separate calls are made. */
+   *  (Handle::getHandList of every handle is that list).  With filters_boundaries (the nodes' configuration,
+   *  grasp_localizer.cpp:21) the chain runs filterHands between the search and the classifier on the device: the same results
+   *  as localizeHands (which filters) -> predictAntipodalHands -> findHandles. */
   std::vector<Handle> localizeHandles(const PointCloud::Ptr& cloud_in, int size_left, const std::vector<int>& indices,
     const std::string& svm_filename, int min_inliers, double min_length, std::vector<GraspHypothesis>* antipodal_hands = nullptr)
   {
@@ -267,18 +268,6 @@ public:
       std::cout << " Error: localizeHandlesBegin while a chain is pending (localizeHandlesEnd first)\n";
       return false;
     }
-    pending_three_calls_ = false;
-    if (filters_boundaries_)  // (a host-side filter between the search and the classifier: the three calls, at End)
-    {
-      pending_cloud_ = cloud_in;
-      pending_three_calls_ = true;
-      pending_size_left_ = size_left;
-      pending_indices_ = indices;
-      pending_svm_ = svm_filename;
-      pending_min_inliers_ = min_inliers;
-      pending_min_length_ = min_length;
-      return true;
-    }
     if (size_left == 0 || !cloud_in || cloud_in->size() == 0)
     {
       std::cout << "Input cloud is empty!\n";
@@ -292,7 +281,8 @@ public:
       return false;
     }
     ensureSearch();
-    if (!search_->localizeBegin(cloud_in, size_left, workspace_, 0.003, indices, svm_filename, min_inliers, min_length))
+    if (!search_->localizeBegin(cloud_in, size_left, workspace_, 0.003, indices, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
       return false;
     pending_cloud_ = cloud_in;
     return true;
@@ -301,7 +291,7 @@ public:
   /** agh_localize_stage through the adapter: the next capture up, beside the chain in flight */
   bool stageNextCloud(const PointCloud::Ptr& next)
   {
-    if (filters_boundaries_ || !next || next->size() == 0)
+    if (!next || next->size() == 0)
       return false;
     ensureSearch();
     return search_->localizeStage(next);
@@ -316,19 +306,14 @@ public:
       return handle_list;
     PointCloud::Ptr cloud_in = pending_cloud_;
     pending_cloud_ = PointCloud::Ptr();
-    if (pending_three_calls_)
-    {
-      std::vector<GraspHypothesis> kept = predictAntipodalHands(localizeHands(cloud_in, pending_size_left_, pending_indices_, false, false), pending_svm_);
-      if (antipodal_hands)
-        *antipodal_hands = kept;
-      return findHandles(kept, pending_min_inliers_, pending_min_length_);
-    }
     std::vector<agh_hypothesis> hands;
     std::vector<agh_handle> handles;
     std::vector<std::int32_t> idx;
     if (!search_->localizeEnd(hands, handles, idx))
       return handle_list;
     remove_nan_in_place(*cloud_in);  // localization.cpp:27 filters the caller's cloud in place
+    if (filters_boundaries_)
+      std::cout << "Filtering out hands close to workspace boundaries ... (on the device, ahead of the classifier)\n";
     std::shared_ptr<std::vector<GraspHypothesis> > kept(new std::vector<GraspHypothesis>());
     kept->reserve(hands.size());
     for (std::size_t i = 0; i < hands.size(); i++)
@@ -414,11 +399,6 @@ private:
   bool keeps_training_images_ = false;
   // localizeHandlesBegin -> localizeHandlesEnd
   PointCloud::Ptr pending_cloud_;
-  bool pending_three_calls_ = false;
-  int pending_size_left_ = 0, pending_min_inliers_ = 0;
-  double pending_min_length_ = 0.0;
-  std::vector<int> pending_indices_;
-  std::string pending_svm_;
   std::unique_ptr<HandSearch> search_;
   PointCloud::Ptr last_cloud_;
   VectorXi last_cam_;
