@@ -80,7 +80,7 @@ assert HYP_DTYPE.itemsize == 160 and FRAME_DTYPE.itemsize == 200 and HANDLE_DTYP
 
 EXPORTS = [
     "agh_default_params", "agh_create", "agh_destroy", "agh_last_error", "agh_set_cloud", "agh_set_cloud_device", "agh_set_cloud_batch", "agh_set_cloud_batch_device",
-    "agh_preprocess", "agh_preprocess_device", "agh_localize", "agh_localize_device", "agh_localize_begin", "agh_localize_stage", "agh_localize_end", "agh_get_cloud", "agh_find_handles", "agh_find_hands", "agh_find_hands_device", "agh_load_svm", "agh_load_svm_file", "agh_classify",
+    "agh_preprocess", "agh_preprocess_device", "agh_localize", "agh_localize_device", "agh_localize_begin", "agh_localize_stage", "agh_localize_end", "agh_localize_batch", "agh_localize_batch_device", "agh_get_cloud", "agh_find_handles", "agh_find_hands", "agh_find_hands_device", "agh_load_svm", "agh_load_svm_file", "agh_classify",
     "agh_classify_device", "agh_get_frames", "agh_get_neighbor_counts", "agh_get_images", "agh_get_hog",
     "agh_get_normals", "agh_get_timing", "agh_get_timing_counts", "agh_get_grid_stats", "agh_set_profile", "agh_synchronize", "agh_selftest_math",
     "agh_set_training_images", "agh_get_training_images", "agh_hog_images", "agh_train_svm", "agh_save_svm_file",
@@ -160,6 +160,11 @@ class AghLocalizeParams(C.Structure):
 class AghLocalizeResult(C.Structure):
     _fields_ = [("n_voxels", C.c_int64), ("n_hypotheses", C.c_int64), ("n_hands", C.c_int64), ("n_handles", C.c_int64),
                 ("n_inlier_idx", C.c_int64)]
+
+
+class AghLocalizeBatchResult(C.Structure):
+    _fields_ = [("r", AghLocalizeResult), ("first_handle", C.c_int64), ("first_inlier_idx", C.c_int64), ("first_hand", C.c_int64),
+                ("first_sample", C.c_int64)]
 
 
 def draw_samples(n_points: int, n_samples: int, seed: int) -> np.ndarray:
@@ -409,6 +414,78 @@ class Context:
                        C.c_int64(hcap), _p(idx, C.c_int32), C.c_int64(hcap), hands.ctypes.data_as(C.c_void_p), C.c_int64(hcap),
                        _p(sout, C.c_int32), C.byref(res)))
         return self._localize_result(res, S)
+
+    def localize_batch(self, captures, sizes_left, workspaces, samples=None, n_samples=0, sample_seeds=None,
+                       classify: bool = True, min_inliers: int = 3, min_length: float = 0.005, filters_boundaries=0,
+                       cell_size: float = 0.003, dense=False, caps=None):
+        """agh_localize_batch: the chain of localize() over a batch of captures in one call with one synchronisation.
+        `captures`: a list of (N_k, >= 3) float32 arrays, or of torch CUDA tensors (agh_localize_batch_device, read in place
+        with their row stride).  Per capture: sizes_left, workspaces, samples (None, or a list of arrays / None per capture),
+        n_samples (an int for all, or a list), sample_seeds, dense (a bool for all, or a list).  caps: (handle_cap, idx_cap,
+        hands_cap) of the output buffers (default: large enough).  Returns a list of the dicts localize() returns, one per
+        capture; after an AghError, self.last_batch_counts holds the per-capture counts the library reported."""
+        Ck = len(captures)
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * Ck
+        sizes_left, dense_l, seeds = per(sizes_left), per(dense), per(1 if sample_seeds is None else sample_seeds)
+        samples_l = per(samples) if isinstance(samples, (list, tuple)) else [samples] * Ck
+        ns_l = per(n_samples)
+        ws_a = np.asarray(workspaces, np.float64)
+        ws_l = list(ws_a) if ws_a.ndim == 2 else [ws_a] * Ck
+        on_device = Ck > 0 and hasattr(captures[0], "is_cuda") and captures[0].is_cuda
+        keep, ptrs, strides, ns = [], (C.c_void_p * max(Ck, 1))(), (C.c_int64 * max(Ck, 1))(), (C.c_int64 * max(Ck, 1))()
+        lps = (AghLocalizeParams * max(Ck, 1))()
+        S_list = []
+        for k, xyz in enumerate(captures):
+            if on_device:
+                assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] >= 3 and xyz.stride(1) == 1
+                ptrs[k], ns[k], strides[k] = xyz.data_ptr(), int(xyz.shape[0]), int(xyz.stride(0)) * 4
+            else:
+                xyz = np.ascontiguousarray(xyz, np.float32)
+                assert xyz.ndim == 2 and xyz.shape[1] >= 3
+                ptrs[k], ns[k], strides[k] = xyz.ctypes.data, xyz.shape[0], xyz.shape[1] * 4
+            keep.append(xyz)
+            lp = lps[k]
+            lp.size_left, lp.dense, lp.classify = int(sizes_left[k]), 1 if dense_l[k] else 0, 1 if classify else 0
+            ws = np.ascontiguousarray(ws_l[k], np.float64)
+            assert ws.size == 6
+            for q in range(6):
+                lp.workspace[q] = float(ws[q])
+            lp.cell_size = cell_size
+            if samples_l[k] is not None:
+                s = np.ascontiguousarray(samples_l[k], np.int32)
+                keep.append(s)
+                lp.sample_idx = s.ctypes.data_as(C.POINTER(C.c_int32))
+                S = s.shape[0]
+            else:
+                lp.sample_idx = None
+                S = int(ns_l[k])
+            S_list.append(S)
+            lp.n_samples, lp.sample_seed, lp.min_inliers, lp.min_length = S, int(seeds[k]), min_inliers, min_length
+            lp.filters_boundaries = int(filters_boundaries)
+        hcap = max(sum(min(8 * S, 8192) for S in S_list), 1)
+        hc, ic, kc = caps if caps is not None else (hcap, hcap, hcap)
+        handles, idx, hands = np.zeros(max(hc, 1), HANDLE_DTYPE), np.zeros(max(ic, 1), np.int32), np.zeros(max(kc, 1), HYP_DTYPE)
+        sout = np.zeros(max(sum(S_list), 1), np.int32)
+        res = (AghLocalizeBatchResult * max(Ck, 1))()
+        fn = self.lib.agh_localize_batch_device if on_device else self.lib.agh_localize_batch
+        rc = fn(self._h, ptrs, strides, ns, lps, C.c_int32(Ck), handles.ctypes.data_as(C.c_void_p), C.c_int64(hc),
+                _p(idx, C.c_int32), C.c_int64(ic), hands.ctypes.data_as(C.c_void_p), C.c_int64(kc), _p(sout, C.c_int32), res)
+        self.last_batch_counts = [
+            {"n_voxels": r.r.n_voxels, "n_hypotheses": r.r.n_hypotheses, "n_hands": r.r.n_hands, "n_handles": r.r.n_handles,
+             "n_inlier_idx": r.r.n_inlier_idx, "first_handle": r.first_handle, "first_inlier_idx": r.first_inlier_idx,
+             "first_hand": r.first_hand, "first_sample": r.first_sample} for r in res[:Ck]]
+        self._check(rc)
+        out = []
+        for k in range(Ck):
+            r = res[k]
+            h0, i0, k0, s0 = r.first_handle, r.first_inlier_idx, r.first_hand, r.first_sample
+            out.append({"handles": handles[h0:h0 + r.r.n_handles].copy(), "inlier_idx": idx[i0:i0 + r.r.n_inlier_idx].copy(),
+                        "hands": hands[k0:k0 + r.r.n_hands].copy(), "samples": sout[s0:s0 + S_list[k]].copy(),
+                        "n_voxels": int(r.r.n_voxels), "n_hypotheses": int(r.r.n_hypotheses)})
+        self.n = sum(int(r.r.n_voxels) for r in res[:Ck])
+        self.last_samples = sum(S_list)
+        self.last_n = sum(int(r.r.n_hypotheses) for r in res[:Ck])
+        return out
 
     def localize_begin(self, xyz, size_left: int, workspace, **kw):
         """agh_localize_begin: the chain of this capture queued, nothing waited for (see include/agh.h)."""

@@ -102,6 +102,27 @@ enum SampleStatus : int
   kStatusSkipped = 5      // kSampleSkip: an unused slot of a device-drawn sample list
 };
 constexpr int32_t kSampleSkip = INT32_MIN;
+#ifdef __HIPCC__
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x)
+{
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+// Sample k of a device-drawn list of S over N points (include/agh.h, agh_localize): one per stratum [k N / S, (k + 1) N / S),
+// offset splitmix64(seed ^ k * 0x9E3779B97F4A7C15) % width; with N < S every point, then kSampleSkip.  agh_localize and
+// agh_localize_batch draw with this one function.
+__device__ __forceinline__ int32_t draw_stratum(long long N, int S, long long k, unsigned long long seed)
+{
+  if (N >= S)
+  {
+    const long long lo = (k * N) / S, hi = ((k + 1) * N) / S;
+    return (int32_t) (lo + (long long) (splitmix64(seed ^ ((unsigned long long) k * 0x9E3779B97F4A7C15ull)) % (unsigned long long) (hi - lo)));
+  }
+  return k < N ? (int32_t) k : kSampleSkip;
+}
+#endif
 constexpr int kBigCap = 4096;    // per-sample neighbour-list scratch (and the largest LDS-resident class of K1a) without ...
 constexpr int kHugeCap = 6144;   // ... and with the 6144 class (Ctx::huge_classes)
 constexpr int64_t kHugeEntries = 1ll << 21;  // pool of the neighbourhoods beyond 4096 points of ONE launch: points in all (AGH_ERR_CAPACITY beyond)
@@ -120,6 +141,24 @@ struct VoxDesc
 struct VoxWorkspace
 {
   double lo[3], hi[3];
+};
+// agh_localize_batch: one capture of a batched preprocessing pass (voxelize.hip, vox_batch)
+struct VoxCapture
+{
+  const float* xyz;  // read in place
+  int64_t stride;    // floats
+  int64_t n, size_left;
+  VoxWorkspace ws;
+  int64_t blk_off;   // its first entry among the raw block counts
+  int64_t code_off;  // its first point code
+  int32_t dense, pad;
+};
+struct VoxBatch
+{
+  const VoxCapture* cap = nullptr;  // device table, one per blockIdx.y; nullptr: the single cloud of the kernel's own arguments
+  VoxDesc* desc = nullptr;          // device descriptors, one per capture
+  VoxDesc* host_desc = nullptr;     // pinned mirrors, one per capture
+  int64_t slot_words = 0;           // bitmap words per capture (a multiple of the popcount block)
 };
 
 struct Comm;  // shard.hip
@@ -175,6 +214,7 @@ struct LocalizeState
 };
 
 struct PlaneState;
+struct LocalizeBatchState;
 
 struct Ctx
 {
@@ -233,6 +273,8 @@ struct Ctx
   LocalizeState loc;
   int64_t raw_cap = 0;             // floats
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
+  LocalizeBatchState* lbatch = nullptr;  // agh_localize_batch's buffers (localize_batch.hip), made by its first call
+  bool batch_active = false;       // inside agh_localize_batch (agh_localize_begin refuses)
 
   // handle search (K5)
   agh_hypothesis* d_h_hands = nullptr;
@@ -451,6 +493,8 @@ int vox_stage1(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, int
   const double workspace[6], double cell, hipStream_t st, int64_t cap_words, VoxDesc* host_desc, bool with_lattice);
 int vox_stage2(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, double cell, int64_t n_words, hipStream_t st,
   VoxDesc* host_desc, bool with_lattice, int* cloud_off_out = nullptr);
+int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
+  unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st);
 // host mirror of the handle search's results (pinned memory of the context; all nullptr / 0: none)
 struct HandleMirror
 {
@@ -462,6 +506,24 @@ struct HandleMirror
 };
 int handle_search(Ctx* c, int64_t H, double x1, double x2, int min_inliers, double min_length, hipStream_t st,
   const HandleMirror& hm, bool with_sequential, const int* d_H = nullptr);
+// the handle search's device buffers (the context's, or agh_localize_batch's slices of n_lists lists)
+struct HandleBufs
+{
+  agh_hypothesis* hands;
+  unsigned long long* bits;
+  int* rowcnt;
+  int* first;
+  int* n;
+  int* idx;
+  int* counts;  // HandleCounts (four ints) per list
+  int* tmp;
+  agh_handle* handles;
+};
+// agh_localize_batch: n_lists lists of at most H hands each, list k in slot k of `slot` hands of every buffer (the pair matrix:
+// slot x ceil(slot / 64) words per list); d_H[k] its count on the device.  The host mirror: list k's handles and inlier indices at
+// k x hm.handle_cap (hm.idx_cap must equal it), its counts at k x host_counts_stride ints.
+int handle_search_batch(const HandleBufs& b, int n_lists, int64_t slot, int64_t H, double x1, double x2, int min_inliers,
+  double min_length, hipStream_t st, const HandleMirror& hm, int host_counts_stride, bool with_sequential, const int* d_H);
 int grid_build(Ctx* c, hipStream_t st);
 int taubin_frames(Ctx* c, const int32_t* d_samples, int64_t S, double radius, agh_frame* d_frames, int32_t* d_nt,
   bool write_normals, hipStream_t st);
@@ -515,6 +577,7 @@ int ensure_draws(Ctx* c, int64_t count, hipStream_t st);
 int normals_pass(Ctx* c, int64_t p0, int64_t p1, hipStream_t st);
 void comm_release(Ctx* c);
 void plane_release(Ctx* c);
+void localize_batch_release(Ctx* c);
 
 // ---- device helpers ----
 #if defined(__HIPCC__)

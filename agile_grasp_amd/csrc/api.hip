@@ -516,6 +516,7 @@ void agh_destroy(agh_ctx* ctx)
     (void) hipStreamSynchronize(c->stream);
   comm_release(c);
   plane_release(c);
+  localize_batch_release(c);
   void* ptrs[] = { c->own_xyz, c->own_cam, c->d_desc, c->d_bbox_part, c->d_cell_start, c->d_cell_count, c->d_block_sums, c->d_cell_of,
     c->d_rank_of, c->d_sorted, c->d_samples, c->d_sums, c->d_nt, c->d_nh, c->d_status, c->d_nbr, c->d_eig, c->d_frames, c->d_slots,
     c->d_images, c->d_slot_index, c->d_scan_tmp, c->d_out_own, c->d_nout, c->d_out_images, c->d_draw_ofs, c->d_draws,
@@ -603,8 +604,9 @@ int agh_set_cloud_batch_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_
   c->d_cam = d_cam_source;
   c->has_normals = false;
   // agh_localize: n is only a BOUND of the cloud's size -- the voxeliser, still queued on this stream, writes the true offsets
-  // {0, count} into d_cloud_off itself; every kernel of the build and of the search reads them there
-  const bool bound = c->defer_cloud_count && n_clouds == 1;
+  // {0, count} into d_cloud_off itself; every kernel of the build and of the search reads them there (agh_localize_batch: the
+  // offsets of every capture, bounded by its raw point count)
+  const bool bound = c->defer_cloud_count;
   c->defer_cloud_count = false;
   c->n_is_bound = bound;
   // the offsets travel to the device only when they change (a stream of equally sized clouds re-uses them)
@@ -613,8 +615,8 @@ int agh_set_cloud_batch_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_
     same = c->cloud_off[(size_t) k] == offsets[k];
   if (bound)
   {
-    c->n_clouds = 1;
-    c->cloud_off.assign(offsets, offsets + 2);
+    c->n_clouds = n_clouds;
+    c->cloud_off.assign(offsets, offsets + n_clouds + 1);
     c->cloud_off_on_device = false;  // (what the device holds is the true count, not this bound)
   }
   else if (!same)

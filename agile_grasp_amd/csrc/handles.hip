@@ -27,11 +27,32 @@ constexpr int kHandleMaxHands = 8192;
 
 __device__ __forceinline__ double dot3d(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
+// agh_localize_batch: the hand lists of several captures side by side, one per blockIdx.y, each in a slice of every buffer at these
+// element strides (all 0 and a grid of one row: the single list of agh_find_handles / agh_localize).  counts and d_H are arrays
+// with one entry per capture.
+struct HandleSlots
+{
+  int64_t hands;     // hands, rowcnt, h_first, h_n, inlier_idx, tmp, the device-side handles
+  int64_t bits;      // the pair matrix
+  int64_t host;      // host_idx and the host-side handles
+  int host_counts;   // host_counts
+};
+#define AGH_HANDLE_SLICE(p, stride)      \
+  do                                     \
+  {                                      \
+    if (p)                               \
+      p += (int64_t) blockIdx.y * (stride); \
+  } while (0)
+
 // d_H (all kernels of this file): the number of hands in device memory, when the host does not know it (agh_localize: the
 // hands are what the SVM kept of a search still in flight); the launch is then sized for a bound and H, W are read here.
 __global__ __launch_bounds__(256) void k_handle_pairs(const agh_hypothesis* __restrict__ hands, int H, double x1, double x2,
-  unsigned long long* __restrict__ bits, int W, int* __restrict__ rowcnt, const int* __restrict__ d_H)
+  unsigned long long* __restrict__ bits, int W, int* __restrict__ rowcnt, const int* __restrict__ d_H, HandleSlots sl)
 {
+  AGH_HANDLE_SLICE(hands, sl.hands);
+  AGH_HANDLE_SLICE(bits, sl.bits);
+  AGH_HANDLE_SLICE(rowcnt, sl.hands);
+  AGH_HANDLE_SLICE(d_H, 1);
   if (d_H)
   {
     H = min(*d_H, kHandleMaxHands);
@@ -104,9 +125,19 @@ template <bool SMALL>
 __global__ __launch_bounds__(256) void k_handle_greedy(const agh_hypothesis* __restrict__ hands, int H,
   const unsigned long long* __restrict__ bits, int W, const int* __restrict__ rowcnt, int min_inliers, double min_length,
   int* __restrict__ h_first, int* __restrict__ h_n, int* __restrict__ inlier_idx, HandleCounts* __restrict__ counts,
-  int* __restrict__ host_idx, int host_idx_cap, int* __restrict__ host_counts, const int* __restrict__ d_H)
+  int* __restrict__ host_idx, int host_idx_cap, int* __restrict__ host_counts, const int* __restrict__ d_H, HandleSlots sl)
 {
   constexpr int kCap = SMALL ? 1024 : kHandleListCap;
+  AGH_HANDLE_SLICE(hands, sl.hands);
+  AGH_HANDLE_SLICE(bits, sl.bits);
+  AGH_HANDLE_SLICE(rowcnt, sl.hands);
+  AGH_HANDLE_SLICE(h_first, sl.hands);
+  AGH_HANDLE_SLICE(h_n, sl.hands);
+  AGH_HANDLE_SLICE(inlier_idx, sl.hands);
+  AGH_HANDLE_SLICE(counts, 1);
+  AGH_HANDLE_SLICE(host_idx, sl.host);
+  AGH_HANDLE_SLICE(host_counts, sl.host_counts);
+  AGH_HANDLE_SLICE(d_H, 1);
   if (d_H)
   {
     H = *d_H;
@@ -424,9 +455,21 @@ template <bool SMALL>
 __global__ __launch_bounds__(1024) void k_handle_batch(const agh_hypothesis* __restrict__ hands, int H,
   const unsigned long long* __restrict__ bits, int W, const int* __restrict__ rowcnt, int min_inliers, double min_length,
   int* __restrict__ h_first, int* __restrict__ h_n, int* __restrict__ inlier_idx, HandleCounts* __restrict__ counts,
-  int* __restrict__ host_idx, int host_idx_cap, int* __restrict__ host_counts, int* __restrict__ tmp, const int* __restrict__ d_H)
+  int* __restrict__ host_idx, int host_idx_cap, int* __restrict__ host_counts, int* __restrict__ tmp, const int* __restrict__ d_H,
+  HandleSlots sl)
 {
   constexpr int kBatch = 16;
+  AGH_HANDLE_SLICE(hands, sl.hands);
+  AGH_HANDLE_SLICE(bits, sl.bits);
+  AGH_HANDLE_SLICE(rowcnt, sl.hands);
+  AGH_HANDLE_SLICE(h_first, sl.hands);
+  AGH_HANDLE_SLICE(h_n, sl.hands);
+  AGH_HANDLE_SLICE(inlier_idx, sl.hands);
+  AGH_HANDLE_SLICE(counts, 1);
+  AGH_HANDLE_SLICE(host_idx, sl.host);
+  AGH_HANDLE_SLICE(host_counts, sl.host_counts);
+  AGH_HANDLE_SLICE(d_H, 1);
+  AGH_HANDLE_SLICE(tmp, sl.hands);
   if (d_H)
   {
     H = *d_H;
@@ -847,8 +890,15 @@ __global__ __launch_bounds__(1024) void k_handle_batch(const agh_hypothesis* __r
 
 __global__ __launch_bounds__(64) void k_handle_build(const agh_hypothesis* __restrict__ hands, const int* __restrict__ h_first,
   const int* __restrict__ h_n, const int* __restrict__ inlier_idx, const HandleCounts* __restrict__ counts,
-  agh_handle* __restrict__ out, agh_handle* __restrict__ host_out, int host_cap)
+  agh_handle* __restrict__ out, agh_handle* __restrict__ host_out, int host_cap, HandleSlots sl)
 {
+  AGH_HANDLE_SLICE(hands, sl.hands);
+  AGH_HANDLE_SLICE(h_first, sl.hands);
+  AGH_HANDLE_SLICE(h_n, sl.hands);
+  AGH_HANDLE_SLICE(inlier_idx, sl.hands);
+  AGH_HANDLE_SLICE(counts, 1);
+  AGH_HANDLE_SLICE(out, sl.hands);
+  AGH_HANDLE_SLICE(host_out, sl.host);
   // (one wave per handle; a grid smaller than the bound on the handles -- agh_localize -- strides over them)
   const int lane = threadIdx.x;
   const int n_handles = counts->n_handles;
@@ -969,41 +1019,60 @@ __global__ __launch_bounds__(64) void k_handle_build(const agh_hypothesis* __res
 // pair matrix longer than a wave).  Without it a declined search leaves counts[3] = 1 and no result: the caller repeats the call
 // with the kernel (agh_find_handles remembers what the previous set of hands needed, so a stream of similar clouds pays the
 // ~5 us of an unneeded launch only when it is needed).
-int handle_search(Ctx* c, int64_t H, double x1, double x2, int min_inliers, double min_length, hipStream_t st,
-  const HandleMirror& hm, bool with_sequential, const int* d_H)
+// n_lists > 1 (agh_localize_batch): that many lists side by side, in the slices of `b` at the strides of `sl`, one row of
+// work-groups each (blockIdx.y); H is then the bound of every list and d_H holds one count per list.
+static int handle_search_lists(const HandleBufs& b, int n_lists, const HandleSlots& sl, int64_t H, double x1, double x2,
+  int min_inliers, double min_length, hipStream_t st, const HandleMirror& hm, bool with_sequential, const int* d_H)
 {
   // d_H: the count lives on the device and H is only its bound (agh_localize) -- launches sized for the bound, both LDS
   // variants of the walk queued, each returning at once when the count is the other one's case
   const int Hi = (int) H, W = (Hi + 63) / 64;
+  const unsigned L = (unsigned) n_lists;
   if (Hi == 0)
-    return hipMemsetAsync(c->d_h_counts, 0, sizeof(HandleCounts), st) == hipSuccess ? AGH_OK : AGH_ERR_HIP;
-  hipLaunchKernelGGL(k_handle_pairs, dim3(Hi), dim3(256), 0, st, (const agh_hypothesis*) c->d_h_hands, Hi, x1, x2,
-    c->d_h_bits, W, c->d_h_rowcnt, d_H);
+    return hipMemsetAsync(b.counts, 0, sizeof(HandleCounts) * (size_t) n_lists, st) == hipSuccess ? AGH_OK : AGH_ERR_HIP;
+  HandleCounts* counts = reinterpret_cast<HandleCounts*>(b.counts);
+  hipLaunchKernelGGL(k_handle_pairs, dim3(Hi, L), dim3(256), 0, st, (const agh_hypothesis*) b.hands, Hi, x1, x2,
+    b.bits, W, b.rowcnt, d_H, sl);
   // the walk: sixteen seeds at a time (rows of at most 64 hands), else -- flagged on the device -- the sequential kernel
   if (Hi <= kHandleLdsHands || d_H)
-    hipLaunchKernelGGL(k_handle_batch<true>, dim3(1), dim3(1024), 0, st, (const agh_hypothesis*) c->d_h_hands, Hi,
-      (const unsigned long long*) c->d_h_bits, W, (const int*) c->d_h_rowcnt, min_inliers, min_length, c->d_h_first,
-      c->d_h_n, c->d_h_idx, reinterpret_cast<HandleCounts*>(c->d_h_counts), hm.idx, hm.idx_cap, hm.counts, c->d_h_tmp, d_H);
+    hipLaunchKernelGGL(k_handle_batch<true>, dim3(1, L), dim3(1024), 0, st, (const agh_hypothesis*) b.hands, Hi,
+      (const unsigned long long*) b.bits, W, (const int*) b.rowcnt, min_inliers, min_length, b.first,
+      b.n, b.idx, counts, hm.idx, hm.idx_cap, hm.counts, b.tmp, d_H, sl);
   if (Hi > kHandleLdsHands)
-    hipLaunchKernelGGL(k_handle_batch<false>, dim3(1), dim3(1024), 0, st, (const agh_hypothesis*) c->d_h_hands, Hi,
-      (const unsigned long long*) c->d_h_bits, W, (const int*) c->d_h_rowcnt, min_inliers, min_length, c->d_h_first,
-      c->d_h_n, c->d_h_idx, reinterpret_cast<HandleCounts*>(c->d_h_counts), hm.idx, hm.idx_cap, hm.counts, c->d_h_tmp, d_H);
+    hipLaunchKernelGGL(k_handle_batch<false>, dim3(1, L), dim3(1024), 0, st, (const agh_hypothesis*) b.hands, Hi,
+      (const unsigned long long*) b.bits, W, (const int*) b.rowcnt, min_inliers, min_length, b.first,
+      b.n, b.idx, counts, hm.idx, hm.idx_cap, hm.counts, b.tmp, d_H, sl);
   if (with_sequential)
   {
     if (Hi <= kHandleLdsHands || d_H)
-      hipLaunchKernelGGL(k_handle_greedy<true>, dim3(1), dim3(256), 0, st, (const agh_hypothesis*) c->d_h_hands, Hi,
-        (const unsigned long long*) c->d_h_bits, W, (const int*) c->d_h_rowcnt, min_inliers, min_length, c->d_h_first,
-        c->d_h_n, c->d_h_idx, reinterpret_cast<HandleCounts*>(c->d_h_counts), hm.idx, hm.idx_cap, hm.counts, d_H);
+      hipLaunchKernelGGL(k_handle_greedy<true>, dim3(1, L), dim3(256), 0, st, (const agh_hypothesis*) b.hands, Hi,
+        (const unsigned long long*) b.bits, W, (const int*) b.rowcnt, min_inliers, min_length, b.first,
+        b.n, b.idx, counts, hm.idx, hm.idx_cap, hm.counts, d_H, sl);
     if (Hi > kHandleLdsHands)
-      hipLaunchKernelGGL(k_handle_greedy<false>, dim3(1), dim3(256), 0, st, (const agh_hypothesis*) c->d_h_hands, Hi,
-        (const unsigned long long*) c->d_h_bits, W, (const int*) c->d_h_rowcnt, min_inliers, min_length, c->d_h_first,
-        c->d_h_n, c->d_h_idx, reinterpret_cast<HandleCounts*>(c->d_h_counts), hm.idx, hm.idx_cap, hm.counts, d_H);
+      hipLaunchKernelGGL(k_handle_greedy<false>, dim3(1, L), dim3(256), 0, st, (const agh_hypothesis*) b.hands, Hi,
+        (const unsigned long long*) b.bits, W, (const int*) b.rowcnt, min_inliers, min_length, b.first,
+        b.n, b.idx, counts, hm.idx, hm.idx_cap, hm.counts, d_H, sl);
   }
   // (a handle holds at least min_inliers >= 1 hands: H bounds the handles too)
-  hipLaunchKernelGGL(k_handle_build, dim3(d_H ? std::min(Hi, 1024) : Hi), dim3(64), 0, st, (const agh_hypothesis*) c->d_h_hands,
-    (const int*) c->d_h_first, (const int*) c->d_h_n, (const int*) c->d_h_idx,
-    (const HandleCounts*) reinterpret_cast<HandleCounts*>(c->d_h_counts), c->d_h_handles, hm.handles, hm.handle_cap);
+  hipLaunchKernelGGL(k_handle_build, dim3(d_H ? std::min(Hi, 1024) : Hi, L), dim3(64), 0, st, (const agh_hypothesis*) b.hands,
+    (const int*) b.first, (const int*) b.n, (const int*) b.idx, (const HandleCounts*) counts, b.handles, hm.handles,
+    hm.handle_cap, sl);
   return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
+}
+
+int handle_search(Ctx* c, int64_t H, double x1, double x2, int min_inliers, double min_length, hipStream_t st,
+  const HandleMirror& hm, bool with_sequential, const int* d_H)
+{
+  const HandleBufs b{ c->d_h_hands, c->d_h_bits, c->d_h_rowcnt, c->d_h_first, c->d_h_n, c->d_h_idx, c->d_h_counts, c->d_h_tmp,
+    c->d_h_handles };
+  return handle_search_lists(b, 1, HandleSlots{ 0, 0, 0, 0 }, H, x1, x2, min_inliers, min_length, st, hm, with_sequential, d_H);
+}
+
+int handle_search_batch(const HandleBufs& b, int n_lists, int64_t slot, int64_t H, double x1, double x2, int min_inliers,
+  double min_length, hipStream_t st, const HandleMirror& hm, int host_counts_stride, bool with_sequential, const int* d_H)
+{
+  const HandleSlots sl{ slot, slot * ((slot + 63) / 64), (int64_t) hm.handle_cap, host_counts_stride };
+  return handle_search_lists(b, n_lists, sl, H, x1, x2, min_inliers, min_length, st, hm, with_sequential, d_H);
 }
 
 }  // namespace agh

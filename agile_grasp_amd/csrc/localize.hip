@@ -24,13 +24,6 @@ extern "C" {
 
 namespace
 {
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x)
-{
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 // One sample per stratum of the cloud (include/agh.h, agh_localize); the point count is read on the device.
 __global__ void k_draw_samples(const int* __restrict__ cloud_off, int n_clouds, int S, unsigned long long seed,
   int32_t* __restrict__ out, int32_t* __restrict__ host_out)
@@ -39,14 +32,7 @@ __global__ void k_draw_samples(const int* __restrict__ cloud_off, int n_clouds, 
   if (k >= S)
     return;
   const long long N = cloud_off[n_clouds];
-  int32_t v;
-  if (N >= S)
-  {
-    const long long lo = ((long long) k * N) / S, hi = ((long long) (k + 1) * N) / S;
-    v = (int32_t) (lo + (long long) (splitmix64(seed ^ ((unsigned long long) k * 0x9E3779B97F4A7C15ull)) % (unsigned long long) (hi - lo)));
-  }
-  else
-    v = k < N ? k : kSampleSkip;
+  const int32_t v = draw_stratum(N, S, k, seed);
   out[k] = v;
   if (host_out)
     host_out[k] = v;
@@ -310,6 +296,11 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   if (L.active)
   {
     c->err = "agh_localize_begin: a chain is in flight (agh_localize_end first)";
+    return AGH_ERR_STATE;
+  }
+  if (c->batch_active)
+  {
+    c->err = "agh_localize_begin: an agh_localize_batch is running on this context";
     return AGH_ERR_STATE;
   }
   if (!lp || n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz) || !(lp->cell_size > 0.0) ||

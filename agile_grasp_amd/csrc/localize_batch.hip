@@ -1,0 +1,823 @@
+// localize_batch.hip -- agh_localize over a batch of captures in one call (agh_localize_batch / agh_localize_batch_device of
+// include/agh.h).  The captures are voxelised together, one launch per stage with the capture on blockIdx.y (voxelize.hip,
+// vox_batch), into one common voxel array (capture k at the device-side offsets d_cloud_off[k], d_cloud_off[k + 1], written by the
+// voxeliser itself), bound as a batch of clouds with a grid build
+// sized from the raw counts, searched and classified in one launch set, compacted one work-group per capture, and handed to the
+// handle search one list per capture side by side (blockIdx.y).  Nothing but the end of the call waits for the device.
+#include "agh_internal.h"
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+using namespace agh;
+
+#define HIPCHK(ctx, expr)                                                                             \
+  do                                                                                                  \
+  {                                                                                                   \
+    hipError_t e__ = (expr);                                                                          \
+    if (e__ != hipSuccess)                                                                            \
+    {                                                                                                 \
+      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                                \
+      return AGH_ERR_HIP;                                                                             \
+    }                                                                                                 \
+  } while (0)
+
+namespace agh
+{
+// one capture of the batch, as the device sees it
+struct BatchCapture
+{
+  int64_t soff;     // its first position in the batch's sample list
+  int32_t S;        // its samples
+  int32_t drawn;    // 1: drawn on the device (sample_idx NULL)
+  uint64_t seed;
+  double ws[6];     // its workspace (the boundary filter)
+};
+constexpr int kBatchCountsStride = 8;  // ints of host-side counts per capture (as agh_localize's [0..6])
+
+struct LocalizeBatchState
+{
+  BatchCapture* d_tab = nullptr;  // kMaxClouds
+  BatchCapture* h_tab = nullptr;  // pinned
+  int32_t* d_local = nullptr;     // explicit sample lists, capture-local (s_cap entries)
+  int32_t* h_samples = nullptr;   // pinned: the lists, capture-local (explicit: copied in; drawn: written by the device)
+  int64_t s_cap = 0;
+  int* h_counts = nullptr;        // pinned: kMaxClouds x kBatchCountsStride
+  int* h_bad = nullptr;           // pinned: kMaxClouds flags, a capture with a sample index outside its cloud
+  VoxDesc* h_desc = nullptr;      // pinned: kMaxClouds voxel descriptors
+  // the batched preprocessing: capture table, descriptors, raw block counts, and a bitmap slot of slot_words words per capture
+  VoxCapture* d_vcap = nullptr;   // kMaxClouds
+  VoxCapture* h_vcap = nullptr;   // pinned
+  VoxDesc* d_vdesc = nullptr;     // kMaxClouds
+  int* d_blk = nullptr;
+  int64_t blk_cap = 0;
+  unsigned* d_bitmap = nullptr;   // bitmap_slots x slot_words
+  int* d_blk2 = nullptr;          // bitmap_slots x slot_words / 4096
+  int64_t slot_words = 0, bitmap_words = 0, last_words = 0;
+  // the handle search's lists, slot hands per capture
+  HandleBufs d{};
+  int* d_count = nullptr;         // kMaxClouds kept-hand counts
+  int64_t slot = 0, slots = 0;
+  agh_hypothesis* h_hands = nullptr;  // pinned: slots x slot each
+  agh_handle* h_handles = nullptr;
+  int32_t* h_idx = nullptr;
+  int64_t h_slot = 0, h_slots = 0;
+};
+
+void localize_batch_release(Ctx* c)
+{
+  LocalizeBatchState* b = c->lbatch;
+  if (!b)
+    return;
+  void* dev[] = { b->d_tab, b->d_local, b->d.hands, b->d.bits, b->d.rowcnt, b->d.first, b->d.n, b->d.idx, b->d.counts, b->d.tmp,
+    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2 };
+  for (void* p : dev)
+    if (p)
+      (void) hipFree(p);
+  void* host[] = { b->h_tab, b->h_samples, b->h_counts, b->h_bad, b->h_desc, b->h_hands, b->h_handles, b->h_idx, b->h_vcap };
+  for (void* p : host)
+    if (p)
+      (void) hipHostFree(p);
+  delete b;
+  c->lbatch = nullptr;
+}
+}  // namespace agh
+
+namespace
+{
+// The batch's sample list: position j belongs to the capture whose span holds it.  Drawn: agh_localize's strata over that
+// capture's voxel count (localize.hip, k_draw_samples) with its seed; explicit: the caller's capture-local index, validated
+// against the capture's own voxel count.  Either way the search gets the index into the common voxel array (or kSampleSkip;
+// -1 for an index outside the capture: the search flags it), the host the capture-local one.
+__global__ void k_batch_samples(const BatchCapture* __restrict__ tab, int C, int64_t S_tot, const int* __restrict__ cloud_off,
+  const int32_t* __restrict__ local, int32_t* __restrict__ out, int32_t* __restrict__ host_out, int* __restrict__ bad)
+{
+  const int64_t j = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= S_tot)
+    return;
+  int k = 0;
+  for (int q = 1; q < C; q++)  // (the last capture whose span starts at or before j and is not empty)
+    if (tab[q].soff <= j && tab[q].S > 0)
+      k = q;
+  const int64_t t = j - tab[k].soff;
+  const int S = tab[k].S;
+  const long long base = cloud_off[k], N = cloud_off[k + 1] - base;
+  int32_t v, g;
+  if (tab[k].drawn)
+  {
+    v = draw_stratum(N, S, (long long) t, tab[k].seed);
+    host_out[j] = v;
+    g = v == kSampleSkip ? v : (int32_t) (v + base);
+  }
+  else
+  {
+    v = local[j];
+    if (v == kSampleSkip)
+      g = v;
+    else if (v >= 0 && v < N)
+      g = (int32_t) (v + base);
+    else
+    {
+      g = -1;
+      bad[k] = 1;
+    }
+  }
+  out[j] = g;
+}
+
+// k_compact_kept (localize.hip) once per capture, one work-group each: capture k's hypotheses are the contiguous run of the
+// batch's list whose samples lie in its span (the list is in sample order), its kept hands go to its own slot -- on the device
+// and in pinned host memory -- with `sample` made capture-local.  filters: the boundary filter against the capture's own
+// workspace (the classifier ran on every hypothesis of the batch).  host_counts: kBatchCountsStride ints per capture, [4]
+// hypotheses, [5] kept, [6] the search's error word.
+__global__ __launch_bounds__(1024) void k_compact_kept_batch(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
+  int64_t cap_in, int use_keep, int filters, const BatchCapture* __restrict__ tab, agh_hypothesis* __restrict__ out, int slot,
+  int* __restrict__ n_out, agh_hypothesis* __restrict__ host_out, int host_slot, int* __restrict__ host_counts,
+  const int32_t* __restrict__ flags)
+{
+  constexpr int kList = 8192;  // (the handle search takes no more)
+  __shared__ int src[kList];
+  __shared__ int wsum[16];
+  __shared__ int carry;
+  __shared__ int64_t range[2];
+  const int cap = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t n = min(*n_in, cap_in);
+  const int64_t s0 = tab[cap].soff, s1 = s0 + tab[cap].S;
+  if (tid < 2)
+  {
+    // first record whose sample is at or beyond the bound
+    const int64_t bound = tid == 0 ? s0 : s1;
+    int64_t lo = 0, hi = n;
+    while (lo < hi)
+    {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((int64_t) in[mid].sample < bound)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    range[tid] = lo;
+  }
+  if (tid == 0)
+    carry = 0;
+  __syncthreads();
+  const int64_t r0 = range[0], r1 = range[1];
+  double ws[6];
+  for (int q = 0; q < 6; q++)
+    ws[q] = tab[cap].ws[q];
+  for (int64_t b0 = r0; b0 < r1; b0 += 1024)
+  {
+    const int64_t i = b0 + tid;
+    const bool keep = i < r1 && (!use_keep || in[i].svm_keep != 0) && !(filters && near_workspace_boundary(in[i].surface, ws));
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0)
+      wsum[wave] = __popcll(m);
+    __syncthreads();
+    int base = carry, tot = 0;
+    for (int w = 0; w < 16; w++)
+    {
+      base += w < wave ? wsum[w] : 0;
+      tot += wsum[w];
+    }
+    const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+    if (keep && pos < kList)
+      src[pos] = (int) i;
+    __syncthreads();
+    if (tid == 0)
+      carry += tot;
+    __syncthreads();
+  }
+  const int K = carry, kw = min(K, min(min(slot, host_slot), kList));
+  agh_hypothesis* o = out + (int64_t) cap * slot;
+  agh_hypothesis* ho = host_out + (int64_t) cap * host_slot;
+  static_assert(offsetof(agh_hypothesis, sample) == 8 * 16, "sample is the first word of the ninth 16-byte part");
+  for (int t = tid; t < kw * 10; t += 1024)
+  {
+    const int k = t / 10, part = t - 10 * k;
+    uint4 v = reinterpret_cast<const uint4*>(in + src[k])[part];
+    if (part == 8)
+      v.x = (unsigned) ((int) v.x - (int) s0);
+    reinterpret_cast<uint4*>(o + k)[part] = v;
+    reinterpret_cast<uint4*>(ho + k)[part] = v;
+  }
+  if (tid == 0)
+  {
+    n_out[cap] = K;
+    int* hc = host_counts + cap * kBatchCountsStride;
+    hc[4] = (int) (r1 - r0);
+    hc[5] = K;
+    hc[6] = flags[0] | (*n_in > cap_in ? 2 : 0);
+  }
+}
+
+template <typename T>
+int pinned_alloc(Ctx* c, T** p, size_t count)
+{
+  if (*p)
+  {
+    (void) hipHostFree(*p);
+    *p = nullptr;
+  }
+  void* q = nullptr;
+  const hipError_t e = hipHostMalloc(&q, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault);
+  if (e != hipSuccess)
+  {
+    c->err = std::string("hipHostMalloc: ") + hipGetErrorString(e);
+    return AGH_ERR_HIP;
+  }
+  *p = static_cast<T*>(q);
+  return AGH_OK;
+}
+
+// the handle search's slots: C lists of `slot` hands (device), and their pinned mirrors
+int ensure_batch_slots(Ctx* c, LocalizeBatchState* b, int C, int64_t slot)
+{
+  slot = std::max<int64_t>(slot, 64);
+  if (slot > b->slot || C > b->slots || !b->d.hands)
+  {
+    const int64_t sl = std::max(slot, b->slot), ns = std::max<int64_t>(C, b->slots);
+    const size_t n = (size_t) (sl * ns);
+    int rc;
+    if ((rc = dev_alloc(c, &b->d.hands, n)) || (rc = dev_alloc(c, &b->d.bits, n * (size_t) ((sl + 63) / 64))) ||
+        (rc = dev_alloc(c, &b->d.rowcnt, n)) || (rc = dev_alloc(c, &b->d.first, n)) || (rc = dev_alloc(c, &b->d.n, n)) ||
+        (rc = dev_alloc(c, &b->d.idx, n)) || (rc = dev_alloc(c, &b->d.counts, (size_t) ns * 4)) || (rc = dev_alloc(c, &b->d.tmp, n)) ||
+        (rc = dev_alloc(c, &b->d.handles, n)))
+      return rc;
+    b->slot = sl;
+    b->slots = ns;
+  }
+  if (slot > b->h_slot || C > b->h_slots || !b->h_hands)
+  {
+    const int64_t sl = std::max(slot, b->h_slot), ns = std::max<int64_t>(C, b->h_slots);
+    const size_t n = (size_t) (sl * ns);
+    int rc;
+    if ((rc = pinned_alloc(c, &b->h_hands, n)) || (rc = pinned_alloc(c, &b->h_handles, n)) || (rc = pinned_alloc(c, &b->h_idx, n)))
+      return rc;
+    b->h_slot = sl;
+    b->h_slots = ns;
+  }
+  return AGH_OK;
+}
+}  // namespace
+
+namespace
+{
+// C bitmap slots of b->slot_words words (+ one popcount block of slack) and their popcount tables
+int ensure_vox_slots(Ctx* c, LocalizeBatchState* b, int C)
+{
+  const int64_t need = (int64_t) C * b->slot_words;
+  if (need > b->bitmap_words || !b->d_bitmap)
+  {
+    int rc;
+    if ((rc = dev_alloc(c, &b->d_bitmap, (size_t) need + 4096)) || (rc = dev_alloc(c, &b->d_blk2, (size_t) (need / 4096) + 1)))
+    {
+      b->bitmap_words = 0;
+      return rc;
+    }
+    b->bitmap_words = need;
+  }
+  return AGH_OK;
+}
+
+struct BatchCall
+{
+  int C = 0;
+  std::vector<const float*> d_raw;
+  std::vector<int64_t> dev_stride, n, soff, raw_off;  // raw_off: each capture's first point among all the batch's
+  std::vector<agh_localize_params> lp;
+  int64_t S_tot = 0, slot = 0;
+  bool classify = false, filters = false, with_sequential = false;
+  double x1 = 0.0, x2 = 0.0;
+};
+
+// search -> classification -> per-capture compaction -> handle search, queued (handles_only: the handle search once more)
+int batch_queue(agh_ctx* ctx, BatchCall& B, bool handles_only)
+{
+  Ctx* c = &ctx->c;
+  LocalizeBatchState* b = c->lbatch;
+  hipStream_t st = c->stream;
+  const int C = B.C;
+  int rc;
+  for (int k = 0; k < C; k++)
+    for (int q = 0; q < (handles_only ? 4 : kBatchCountsStride); q++)
+      b->h_counts[k * kBatchCountsStride + q] = 0;
+  B.with_sequential = c->handles_sequential;
+  if (!handles_only)
+  {
+    c->mirror = HostMirror{ nullptr, 0, nullptr };
+    if ((rc = agh_find_hands_device(ctx, c->d_idx_own, B.S_tot, 0, c->d_out_own, c->s_cap * 8, c->d_nout, st)) != AGH_OK)
+      return rc;
+    if (B.classify && (rc = hog_svm(c, std::min<int64_t>(c->last_s * 8, c->last_cap), c->d_keep, st, nullptr)) != AGH_OK)
+      return rc;
+    hipLaunchKernelGGL(k_compact_kept_batch, dim3(C), dim3(1024), 0, st, (const agh_hypothesis*) c->d_out_own,
+      (const int64_t*) c->d_nout, c->s_cap * 8, B.classify ? 1 : 0, B.filters ? 1 : 0, (const BatchCapture*) b->d_tab, b->d.hands,
+      (int) b->slot, b->d_count, b->h_hands, (int) b->h_slot, b->h_counts, (const int32_t*) c->d_flags);
+    if (hipGetLastError() != hipSuccess)
+    {
+      c->err = "k_compact_kept_batch launch failed";
+      return AGH_ERR_HIP;
+    }
+  }
+  const HandleMirror hm{ b->h_handles, (int) b->h_slot, b->h_idx, (int) b->h_slot, b->h_counts };
+  timing_begin(c, st);
+  rc = handle_search_batch(b->d, C, b->slot, B.slot, B.x1, B.x2, B.lp[0].min_inliers, B.lp[0].min_length, st, hm,
+    kBatchCountsStride, B.with_sequential, b->d_count);
+  timing_mark(c, "handle_search", st);
+  if (rc != AGH_OK)
+    c->err = "handle search launch failed";
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  const int C = n_captures;
+  if (results && C >= 1 && C <= kMaxClouds)
+    for (int k = 0; k < C; k++)
+      results[k] = agh_localize_batch_result{ { 0, 0, 0, 0, 0 }, 0, 0, 0, 0 };
+  if (c->loc.active)
+  {
+    c->err = "agh_localize_batch: a localize chain is in flight on this context (agh_localize_end first)";
+    return AGH_ERR_STATE;
+  }
+  if (C < 1 || C > kMaxClouds || !xyz || !stride_bytes || !n || !lp || handle_cap < 0 || idx_cap < 0 || hands_cap < 0 ||
+      (handle_cap > 0 && !handles_out) || (idx_cap > 0 && !inlier_idx_out) || (hands_cap > 0 && !hands_out))
+  {
+    c->err = "agh_localize_batch: bad arguments (1 <= n_captures <= 64; see include/agh.h)";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  int64_t n_tot = 0, S_tot = 0;
+  for (int k = 0; k < C; k++)
+  {
+    const agh_localize_params& p = lp[k];
+    if (n[k] < 0 || n[k] >= (1ll << 30) || stride_bytes[k] < 12 || (stride_bytes[k] % 4) != 0 || (n[k] > 0 && !xyz[k]) ||
+        !(p.cell_size > 0.0) || p.size_left < 0 || p.n_samples < 0 || p.n_samples > (1 << 24) || p.min_inliers < 1 ||
+        (p.filters_boundaries != 0 && p.filters_boundaries != 1))
+    {
+      c->err = "agh_localize_batch: bad arguments for capture " + std::to_string(k) + " (see include/agh.h)";
+      return AGH_ERR_INVALID_ARGUMENT;
+    }
+    if (p.classify != lp[0].classify || p.cell_size != lp[0].cell_size || p.min_inliers != lp[0].min_inliers ||
+        p.min_length != lp[0].min_length || p.filters_boundaries != lp[0].filters_boundaries)
+    {
+      c->err = "agh_localize_batch: classify, cell_size, min_inliers, min_length and filters_boundaries must be equal across the "
+               "batch (capture " + std::to_string(k) + " differs from capture 0)";
+      return AGH_ERR_INVALID_ARGUMENT;
+    }
+    n_tot += n[k];
+    S_tot += p.n_samples;
+  }
+  if (n_tot >= (1ll << 30) || S_tot > (1 << 24))
+  {
+    c->err = "agh_localize_batch: need fewer than 2^30 raw points and at most 2^24 samples in all";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  if (lp[0].classify && !c->has_svm)
+  {
+    c->err = "agh_localize_batch: classify needs a loaded SVM (agh_load_svm*)";
+    return AGH_ERR_NO_SVM;
+  }
+  BatchCall B;
+  B.C = C;
+  if (!handle_thresholds(&B.x1, &B.x2))
+  {
+    c->err = "agh_localize_batch: this libm's acos is not monotone around the 0.34 rad thresholds";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  int rc;
+  if (!c->lbatch)
+  {
+    c->lbatch = new LocalizeBatchState();
+    LocalizeBatchState* b = c->lbatch;
+    if ((rc = dev_alloc(c, &b->d_tab, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_tab, (size_t) kMaxClouds)) ||
+        (rc = pinned_alloc(c, &b->h_counts, (size_t) kMaxClouds * kBatchCountsStride)) ||
+        (rc = pinned_alloc(c, &b->h_bad, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_desc, (size_t) kMaxClouds)) ||
+        (rc = dev_alloc(c, &b->d_count, (size_t) kMaxClouds)) || (rc = dev_alloc(c, &b->d_vcap, (size_t) kMaxClouds)) ||
+        (rc = pinned_alloc(c, &b->h_vcap, (size_t) kMaxClouds)) || (rc = dev_alloc(c, &b->d_vdesc, (size_t) kMaxClouds)))
+    {
+      localize_batch_release(c);
+      return rc;
+    }
+  }
+  LocalizeBatchState* b = c->lbatch;
+  // ---- 1. the raw captures: packed end to end into the context's raw buffer, or read in place ----
+  B.d_raw.resize(C);
+  B.dev_stride.resize(C);
+  B.n.assign(n, n + C);
+  B.lp.assign(lp, lp + C);
+  B.raw_off.resize(C);
+  for (int k = 0, o = 0; k < C; o += (int) n[k], k++)
+    B.raw_off[k] = o;
+  B.soff.resize(C + 1);
+  B.soff[0] = 0;
+  for (int k = 0; k < C; k++)
+    B.soff[k + 1] = B.soff[k] + lp[k].n_samples;
+  B.S_tot = S_tot;
+  B.classify = lp[0].classify != 0;
+  B.filters = lp[0].filters_boundaries != 0;
+  int64_t slot = 0;
+  for (int k = 0; k < C; k++)
+    slot = std::max<int64_t>(slot, std::min<int64_t>(8 * lp[k].n_samples, 8192));
+  B.slot = slot;
+  if (on_device)
+    for (int k = 0; k < C; k++)
+    {
+      B.d_raw[k] = xyz[k];
+      B.dev_stride[k] = stride_bytes[k];
+    }
+  else
+  {
+    // (a staged capture of agh_localize_stage is dropped: its copy may still read the caller's source -- wait for it)
+    if (c->loc.staged)
+      HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
+    c->loc.staged = false;
+    int64_t need = 0;
+    for (int k = 0; k < C; k++)
+    {
+      B.dev_stride[k] = stride_bytes[k] <= 32 ? stride_bytes[k] : 12;  // (as agh_preprocess)
+      need += n[k] * (B.dev_stride[k] / 4);
+    }
+    if (need > c->raw_cap || !c->d_raw_xyz)
+    {
+      if ((rc = dev_alloc(c, &c->d_raw_xyz, (size_t) need)))
+        return rc;
+      c->raw_cap = need;
+    }
+    int64_t off = 0;
+    for (int k = 0; k < C; k++)
+    {
+      float* dst = c->d_raw_xyz + off;
+      if (n[k] > 0)
+      {
+        if (B.dev_stride[k] == stride_bytes[k])
+          HIPCHK(c, hipMemcpyAsync(dst, xyz[k], (size_t) (n[k] * stride_bytes[k] - (stride_bytes[k] - 12)), hipMemcpyHostToDevice, st));
+        else
+          HIPCHK(c, hipMemcpy2DAsync(dst, 12, xyz[k], (size_t) stride_bytes[k], 12, (size_t) n[k], hipMemcpyHostToDevice, st));
+      }
+      B.d_raw[k] = dst;
+      off += n[k] * (B.dev_stride[k] / 4);
+    }
+  }
+  c->batch_active = true;
+  struct ActiveGuard
+  {
+    Ctx* c;
+    ~ActiveGuard() { c->batch_active = false; }
+  } guard{ c };
+  auto drop_bound_cloud = [&]() {
+    if (c->n_is_bound)
+    {
+      c->n_is_bound = false;
+      c->has_cloud = false;
+      c->n = 0;
+      c->cloud_off_on_device = false;
+    }
+  };
+  auto fail = [&](int code) {
+    (void) hipStreamSynchronize(st);
+    drop_bound_cloud();
+    return code;
+  };
+#define LB_HIPCHK(expr)                                                   \
+  do                                                                      \
+  {                                                                       \
+    hipError_t e__ = (expr);                                              \
+    if (e__ != hipSuccess)                                                \
+    {                                                                     \
+      c->err = std::string(#expr) + ": " + hipGetErrorString(e__);        \
+      return fail(AGH_ERR_HIP);                                           \
+    }                                                                     \
+  } while (0)
+  const double cell = lp[0].cell_size;
+  for (int pass = 0;; pass++)
+  {
+    // ---- 2. preprocessing: one launch per stage for the whole batch, capture = blockIdx.y, each with its own descriptor and
+    // bitmap slot; the voxels of all captures go to one array at the device-side cloud offsets ----
+    if (n_tot > c->vox_cap || !c->d_vox_code)
+    {
+      if ((rc = dev_alloc(c, &c->d_vox_code, (size_t) n_tot)) || (rc = dev_alloc(c, &c->d_vox_blk, (size_t) n_tot / 1024 + 2)) ||
+          (rc = dev_alloc(c, &c->d_vox_xyz, (size_t) n_tot * 3)) || (rc = dev_alloc(c, &c->d_vox_cam, (size_t) n_tot)))
+        return fail(rc);
+      c->vox_cap = n_tot;
+    }
+    int64_t nb_max = 0, n_max = 0, blk_tot = 0;
+    bool any_scan = false;
+    for (int k = 0; k < C; k++)
+    {
+      VoxCapture& q = b->h_vcap[k];
+      q.xyz = B.d_raw[k];
+      q.stride = B.dev_stride[k] / 4;
+      q.n = n[k];
+      q.size_left = lp[k].size_left;
+      for (int a = 0; a < 3; a++)
+      {
+        q.ws.lo[a] = lp[k].workspace[2 * a];
+        q.ws.hi[a] = lp[k].workspace[2 * a + 1];
+      }
+      q.blk_off = blk_tot;
+      q.code_off = B.raw_off[k];
+      q.dense = lp[k].dense ? 1 : 0;
+      q.pad = 0;
+      const int64_t nb = (n[k] + 1023) / 1024;
+      blk_tot += nb;
+      nb_max = std::max(nb_max, nb);
+      n_max = std::max(n_max, n[k]);
+      any_scan |= n[k] > 0 && !lp[k].dense;
+    }
+    if (blk_tot + 1 > b->blk_cap || !b->d_blk)
+    {
+      if ((rc = dev_alloc(c, &b->d_blk, (size_t) blk_tot + 1)))
+        return fail(rc);
+      b->blk_cap = blk_tot + 1;
+    }
+    LB_HIPCHK(hipMemcpyAsync(b->d_vcap, b->h_vcap, sizeof(VoxCapture) * (size_t) C, hipMemcpyHostToDevice, st));
+    VoxBatch vb;
+    vb.cap = b->d_vcap;
+    vb.desc = b->d_vdesc;
+    vb.host_desc = b->h_desc;
+    // (slots kept from much larger lattices are dropped: every capture would clear and count all of its slot)
+    if (b->d_bitmap && b->last_words > 0 && b->slot_words > 8 * b->last_words + (1 << 20))
+      b->slot_words = 0;
+    if (b->slot_words <= 0)
+    {
+      // the first batch of a context: the lattices' sizes (one synchronisation) decide the slots
+      if ((rc = vox_batch(vb, C, nb_max, n_max, any_scan, cell, true, nullptr, b->d_blk, nullptr, c->d_vox_code, nullptr, nullptr,
+             nullptr, st)) != AGH_OK)
+      {
+        c->err = "preprocessing launch failed";
+        return fail(rc);
+      }
+      LB_HIPCHK(hipStreamSynchronize(st));
+      int64_t words = 0;
+      for (int k = 0; k < C; k++)
+      {
+        if (b->h_desc[k].error)
+        {
+          c->err = "agh_localize_batch: capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
+                   "(1 GiB bitmap): set a workspace that bounds the scene";
+          return fail(AGH_ERR_CAPACITY);
+        }
+        words = std::max<int64_t>(words, (int64_t) b->h_desc[k].n_words);
+      }
+      b->slot_words = std::min<int64_t>(((words + words / 4) / 4096 + 1) * 4096, (int64_t) kVoxMaxWords);
+    }
+    if ((rc = ensure_vox_slots(c, b, C)) != AGH_OK)
+      return fail(rc);
+    vb.slot_words = b->slot_words;
+    timing_begin(c, st);
+    if ((rc = vox_batch(vb, C, nb_max, n_max, any_scan, cell, false, b->d_bitmap, b->d_blk, b->d_blk2, c->d_vox_code, c->d_vox_xyz,
+           c->d_vox_cam, c->d_cloud_off, st)) != AGH_OK)
+    {
+      c->err = "preprocessing launch failed";
+      return fail(rc);
+    }
+    timing_mark(c, "preprocess", st);
+    c->cloud_async = false;
+    // ---- 3. the batch of clouds: a grid build sized from the raw counts (bounds of the voxel counts, which stay on the device) ----
+    {
+      std::vector<int64_t> bound(C + 1, 0);
+      for (int k = 0; k < C; k++)
+        bound[k + 1] = bound[k] + n[k];
+      c->defer_cloud_count = true;
+      rc = agh_set_cloud_batch_device(ctx, c->d_vox_xyz, 12, c->d_vox_cam, bound.data(), C, nullptr);
+      c->defer_cloud_count = false;
+      if (rc != AGH_OK)
+        return fail(rc);
+    }
+    // ---- 4. buffers for the bounds, the capture table and the sample list ----
+    if ((rc = ensure_call_buffers(c, std::max<int64_t>(S_tot, 1))) != AGH_OK)
+      return fail(rc);
+    if (S_tot > c->idx_cap || !c->d_idx_own)
+    {
+      if ((rc = dev_alloc(c, &c->d_idx_own, (size_t) std::max<int64_t>(S_tot, 1024))))
+        return fail(rc);
+      c->idx_cap = std::max<int64_t>(S_tot, 1024);
+    }
+    if (S_tot > b->s_cap || !b->h_samples)
+    {
+      const int64_t cap = std::max<int64_t>(S_tot, 1024);
+      if ((rc = dev_alloc(c, &b->d_local, (size_t) cap)) || (rc = pinned_alloc(c, &b->h_samples, (size_t) cap)))
+        return fail(rc);
+      b->s_cap = cap;
+    }
+    if ((rc = ensure_batch_slots(c, b, C, slot)) != AGH_OK)
+      return fail(rc);
+    if (B.classify && c->s_cap * 8 > c->keep_cap)
+    {
+      if (c->d_keep)
+        (void) hipFree(c->d_keep);
+      if (c->d_svm_sums)
+        (void) hipFree(c->d_svm_sums);
+      c->d_keep = nullptr;
+      c->d_svm_sums = nullptr;
+      c->keep_cap = 0;
+      LB_HIPCHK(hipMalloc((void**) &c->d_keep, (size_t) (c->s_cap * 8)));
+      LB_HIPCHK(hipMalloc((void**) &c->d_svm_sums, (size_t) (c->s_cap * 8) * sizeof(double)));
+      c->keep_cap = c->s_cap * 8;
+    }
+    bool any_explicit = false;
+    for (int k = 0; k < C; k++)
+    {
+      BatchCapture& t = b->h_tab[k];
+      t.soff = B.soff[k];
+      t.S = (int32_t) lp[k].n_samples;
+      t.drawn = lp[k].sample_idx ? 0 : 1;
+      t.seed = lp[k].sample_seed;
+      for (int q = 0; q < 6; q++)
+        t.ws[q] = lp[k].workspace[q];
+      b->h_bad[k] = 0;
+      if (lp[k].sample_idx && lp[k].n_samples > 0)
+      {
+        any_explicit = true;
+        if (lp[k].sample_idx != b->h_samples + B.soff[k])  // (the repeat of step 6 hands the pinned copy back in)
+          std::memcpy(b->h_samples + B.soff[k], lp[k].sample_idx, sizeof(int32_t) * (size_t) lp[k].n_samples);
+      }
+    }
+    LB_HIPCHK(hipMemcpyAsync(b->d_tab, b->h_tab, sizeof(BatchCapture) * (size_t) C, hipMemcpyHostToDevice, st));
+    if (any_explicit)
+      LB_HIPCHK(hipMemcpyAsync(b->d_local, b->h_samples, sizeof(int32_t) * (size_t) S_tot, hipMemcpyHostToDevice, st));
+    if (S_tot > 0)
+    {
+      hipLaunchKernelGGL(k_batch_samples, dim3((unsigned) ((S_tot + 255) / 256)), dim3(256), 0, st, (const BatchCapture*) b->d_tab, C,
+        S_tot, (const int*) c->d_cloud_off, (const int32_t*) b->d_local, c->d_idx_own, b->h_samples, b->h_bad);
+      LB_HIPCHK(hipGetLastError());
+    }
+    // ---- 5. search -> classification -> kept hands per capture -> handle search per capture, then the one synchronisation ----
+    if ((rc = batch_queue(ctx, B, false)) != AGH_OK)
+      return fail(rc);
+    LB_HIPCHK(hipStreamSynchronize(st));
+    // ---- 6. the voxel descriptors: a lattice that outgrew the kept bitmap -> the batch once more with one sized for all ----
+    int64_t words = 0;
+    bool outgrown = false;
+    for (int k = 0; k < C; k++)
+    {
+      const VoxDesc& h = b->h_desc[k];
+      if (h.error == 1)
+      {
+        drop_bound_cloud();
+        c->err = "agh_localize_batch: capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
+                 "(1 GiB bitmap): set a workspace that bounds the scene";
+        return AGH_ERR_CAPACITY;
+      }
+      outgrown |= h.error == 2;
+      words = std::max<int64_t>(words, (int64_t) h.n_words);
+    }
+    if (outgrown)
+    {
+      if (pass > 0)
+      {
+        drop_bound_cloud();
+        c->err = "agh_localize_batch: the voxel bitmap sized from the batch's lattices did not hold them";
+        return AGH_ERR_CAPACITY;
+      }
+      drop_bound_cloud();
+      b->slot_words = std::min<int64_t>(((words + words / 4) / 4096 + 1) * 4096, (int64_t) kVoxMaxWords);
+      for (int k = 0; k < C; k++)  // (explicit lists: from the pinned copy, which holds them at their spans already)
+        if (B.lp[k].sample_idx)
+          B.lp[k].sample_idx = b->h_samples + B.soff[k];
+      lp = B.lp.data();
+      continue;
+    }
+    b->last_words = words;
+    break;
+  }
+  // the bound batch is now the true one
+  std::vector<int64_t> voff(C + 1, 0), nv(C);
+  for (int k = 0; k < C; k++)
+  {
+    nv[k] = (int64_t) (b->h_desc[k].n_vox[0] + b->h_desc[k].n_vox[1]);
+    voff[k + 1] = voff[k] + nv[k];
+  }
+  c->n_is_bound = false;
+  c->n = voff[C];
+  c->cloud_off = voff;
+  c->cloud_off_on_device = true;
+  c->n_clouds = C;
+  int* hc = b->h_counts;
+  bool handles_only = false;
+  for (int attempt = 0;; attempt++)
+  {
+    if (attempt > 0)
+    {
+      if ((rc = batch_queue(ctx, B, handles_only)) != AGH_OK)
+        return fail(rc);
+      LB_HIPCHK(hipStreamSynchronize(st));
+    }
+    if (!handles_only)
+    {
+      int32_t flags[1] = { hc[6] };
+      rc = flags_to_status(c, flags);
+      if (rc == AGH_ERR_RETRY && attempt < 3)
+      {
+        if ((rc = ensure_call_buffers(c, std::max<int64_t>(S_tot, 1))) != AGH_OK)
+          return rc;
+        continue;
+      }
+      if (rc == AGH_ERR_INVALID_ARGUMENT && (flags[0] & 4))
+      {
+        for (int k = 0; k < C; k++)
+          if (b->h_bad[k])
+          {
+            c->err = "agh_localize_batch: a sample index of capture " + std::to_string(k) + " is outside its voxelised cloud";
+            break;
+          }
+      }
+      if (rc != AGH_OK)
+        return rc;
+    }
+    bool declined = false;
+    for (int k = 0; k < C; k++)
+    {
+      const int* h = hc + k * kBatchCountsStride;
+      if (h[2] == 2 || h[5] > 8192)
+      {
+        c->err = "agh_localize_batch: capture " + std::to_string(k) +
+                 ": more than 8192 hands for the handle search (classify first, or search fewer samples)";
+        return AGH_ERR_CAPACITY;
+      }
+      declined |= h[3] != 0;
+    }
+    c->handles_sequential = declined;
+    if (declined && !B.with_sequential && attempt < 3)
+    {
+      handles_only = true;
+      continue;
+    }
+    break;
+  }
+  int64_t n_hyp_tot = 0, tot_handles = 0, tot_idx = 0, tot_hands = 0;
+  for (int k = 0; k < C; k++)
+  {
+    const int* h = hc + k * kBatchCountsStride;
+    if (h[2])
+    {
+      c->err = "agh_localize_batch: capture " + std::to_string(k) + ": a seed hand has more than 2048 inliers";
+      return AGH_ERR_CAPACITY;
+    }
+  }
+  for (int k = 0; k < C; k++)
+  {
+    const int* h = hc + k * kBatchCountsStride;
+    if (results)
+      results[k] = agh_localize_batch_result{ { nv[k], h[4], h[5], h[0], h[1] }, tot_handles, tot_idx, tot_hands, B.soff[k] };
+    n_hyp_tot += h[4];
+    tot_handles += h[0];
+    tot_idx += h[1];
+    tot_hands += h[5];
+  }
+  c->last_nout = std::min<int64_t>(n_hyp_tot, c->s_cap * 8);
+  if (samples_out && S_tot > 0)
+    std::memcpy(samples_out, b->h_samples, sizeof(int32_t) * (size_t) S_tot);
+  if (tot_handles > handle_cap || tot_idx > idx_cap || (hands_out && tot_hands > hands_cap))
+  {
+    c->err = "agh_localize_batch: output buffers too small (the counts are in results)";
+    return AGH_ERR_CAPACITY;
+  }
+  int64_t oh = 0, oi = 0, ok = 0;
+  for (int k = 0; k < C; k++)
+  {
+    const int* h = hc + k * kBatchCountsStride;
+    const size_t base = (size_t) k * (size_t) b->h_slot;
+    if (h[0] > 0)
+    {
+      std::memcpy(handles_out + oh, b->h_handles + base, sizeof(agh_handle) * (size_t) h[0]);
+      std::memcpy(inlier_idx_out + oi, b->h_idx + base, sizeof(int32_t) * (size_t) h[1]);
+    }
+    if (hands_out && h[5] > 0)
+      std::memcpy(hands_out + ok, b->h_hands + base, sizeof(agh_hypothesis) * (size_t) h[5]);
+    oh += h[0];
+    oi += h[1];
+    ok += h[5];
+  }
+  return AGH_OK;
+}
+#undef LB_HIPCHK
+
+int agh_localize_batch(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  return localize_batch_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap,
+    hands_out, hands_cap, samples_out, results);
+}
+
+int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  return localize_batch_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap,
+    hands_out, hands_cap, samples_out, results);
+}
+
+}  // extern "C"

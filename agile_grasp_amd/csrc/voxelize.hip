@@ -21,6 +21,14 @@ constexpr int kPreBlock = 256;
 constexpr int kPrePerBlock = 1024;   // points per block (4 rounds of 256)
 constexpr int kWordsPerBlock = 4096; // bitmap words per block in the popcount passes (16 per thread)
 
+// agh_localize_batch: the kernels below with a VoxBatch whose `cap` is set run one capture per blockIdx.y -- its points, its
+// descriptor, its slice of the block tables and its slot of the bitmap (vb.slot_words words each); without it (cap == nullptr,
+// a grid of one row) they run the single cloud of their other arguments.
+__device__ __forceinline__ const VoxCapture* vox_capture(const VoxBatch& vb)
+{
+  return vb.cap ? vb.cap + blockIdx.y : nullptr;
+}
+
 __device__ __forceinline__ void vox_desc_init(VoxDesc* d)
 {
   for (int c = 0; c < 2; c++)
@@ -45,9 +53,20 @@ __device__ __forceinline__ bool finite3(float x, float y, float z)
 
 // Finite points per block of 1024 raw points (rank base of the NaN-free cloud).
 __global__ __launch_bounds__(kPreBlock) void k_vox_count(const float* __restrict__ xyz, int64_t stride, int64_t n,
-  int* __restrict__ blk_cnt)
+  int* __restrict__ blk_cnt, VoxBatch vb)
 {
+  if (const VoxCapture* q = vox_capture(vb))
+  {
+    if (q->dense)
+      return;
+    xyz = q->xyz;
+    stride = q->stride;
+    n = q->n;
+    blk_cnt += q->blk_off;
+  }
   const int64_t base = (int64_t) blockIdx.x * kPrePerBlock;
+  if (base >= n)  // (a batch's launch is sized for its largest capture)
+    return;
   int cnt = 0;
   for (int r = 0; r < 4; r++)
   {
@@ -75,9 +94,30 @@ __device__ void vox_totals(VoxDesc* d, const int* __restrict__ blk_prefix, long 
 // reset in front of k_vox_classify --, and totals_desc -- the voxel counts per camera and the host mirror behind the second scan.
 // cloud_off_out: the context's device-side cloud offsets {0, voxel count} -- so that a grid build queued behind this kernel
 // finds the count on the device, without the host having to wait for it (agh_localize).
+// vb (a batch): the first scan (init_desc set) runs over the capture's raw block counts, the second (totals_desc set) over its
+// bitmap slot's popcounts; descriptors and mirrors are the capture's, cloud_off_out and total are not written (k_vox_chain).
 __global__ __launch_bounds__(1024) void k_vox_scan(int* __restrict__ v, int64_t nb, long long* total, VoxDesc* init_desc,
-  VoxDesc* totals_desc, VoxDesc* host_desc, int* cloud_off_out)
+  VoxDesc* totals_desc, VoxDesc* host_desc, int* cloud_off_out, VoxBatch vb)
 {
+  if (const VoxCapture* q = vox_capture(vb))
+  {
+    const int y = blockIdx.y;
+    total = nullptr;
+    cloud_off_out = nullptr;
+    if (init_desc)
+    {
+      v += q->blk_off;
+      nb = q->dense ? 0 : (q->n + kPrePerBlock - 1) / kPrePerBlock;
+      init_desc = vb.desc + y;
+    }
+    if (totals_desc)
+    {
+      v += (int64_t) y * (vb.slot_words / kWordsPerBlock);
+      nb = q->n > 0 ? vb.slot_words / kWordsPerBlock : 0;
+      totals_desc = vb.desc + y;
+      host_desc = vb.host_desc ? vb.host_desc + y : nullptr;
+    }
+  }
   __shared__ long long carry;
   __shared__ int wsum[16];
   if (threadIdx.x == 0)
@@ -119,8 +159,21 @@ __global__ __launch_bounds__(1024) void k_vox_scan(int* __restrict__ v, int64_t 
 
 // Camera id (rank in the NaN-free cloud >= size_left), workspace test, per-camera minimum and maximum.
 __global__ __launch_bounds__(kPreBlock) void k_vox_classify(const float* __restrict__ xyz, int64_t stride, int64_t n,
-  const int* __restrict__ blk_prefix, int64_t size_left, VoxWorkspace ws, uint8_t* __restrict__ code, VoxDesc* d)
+  const int* __restrict__ blk_prefix, int64_t size_left, VoxWorkspace ws, uint8_t* __restrict__ code, VoxDesc* d, VoxBatch vb)
 {
+  if (const VoxCapture* q = vox_capture(vb))
+  {
+    xyz = q->xyz;
+    stride = q->stride;
+    n = q->n;
+    blk_prefix = q->dense ? nullptr : blk_prefix + q->blk_off;
+    size_left = q->size_left;
+    ws = q->ws;
+    code += q->code_off;
+    d = vb.desc + blockIdx.y;
+    if ((int64_t) blockIdx.x * kPrePerBlock >= n)
+      return;
+  }
   __shared__ int wcnt[4];
   __shared__ unsigned smn[2][3], smx[2][3];
   __shared__ int skept[2];
@@ -275,16 +328,28 @@ __device__ void vox_lattice(VoxDesc* d, double cell, unsigned long long max_word
   if (host_desc)
     *host_desc = *d;
 }
-__global__ void k_vox_lattice(VoxDesc* d, double cell, unsigned long long max_words, unsigned long long cap_words, VoxDesc* host_desc)
+__global__ void k_vox_lattice(VoxDesc* d, double cell, unsigned long long max_words, unsigned long long cap_words, VoxDesc* host_desc,
+  VoxBatch vb)
 {
+  if (vb.cap)
+  {
+    d = vb.desc + blockIdx.y;
+    host_desc = vb.host_desc ? vb.host_desc + blockIdx.y : nullptr;
+  }
   vox_lattice(d, cell, max_words, cap_words, host_desc);
 }
 // The speculative pass (agh_preprocess_device from the second cloud on): the bitmap of the size the context already has is
 // cleared by all work-groups while one thread computes the lattice -- one launch for what were a runtime fill kernel and a
 // one-thread kernel, ~5 us each.  (k_vox_mark, the next kernel, is the first reader of both.)
 __global__ __launch_bounds__(256) void k_vox_clear_lattice(uint4* __restrict__ bitmap16, int64_t n16, VoxDesc* d, double cell,
-  unsigned long long max_words, unsigned long long cap_words, VoxDesc* host_desc)
+  unsigned long long max_words, unsigned long long cap_words, VoxDesc* host_desc, VoxBatch vb)
 {
+  if (vb.cap)
+  {
+    bitmap16 += (int64_t) blockIdx.y * (vb.slot_words / 4);
+    d = vb.desc + blockIdx.y;
+    host_desc = vb.host_desc ? vb.host_desc + blockIdx.y : nullptr;
+  }
   if (blockIdx.x == 0 && threadIdx.x == 0)
     vox_lattice(d, cell, max_words, cap_words, host_desc);
   const uint4 z = make_uint4(0u, 0u, 0u, 0u);
@@ -293,8 +358,17 @@ __global__ __launch_bounds__(256) void k_vox_clear_lattice(uint4* __restrict__ b
 }
 
 __global__ __launch_bounds__(256) void k_vox_mark(const float* __restrict__ xyz, int64_t stride, int64_t n,
-  const uint8_t* __restrict__ code, const VoxDesc* __restrict__ d, double cell, unsigned* __restrict__ bitmap)
+  const uint8_t* __restrict__ code, const VoxDesc* __restrict__ d, double cell, unsigned* __restrict__ bitmap, VoxBatch vb)
 {
+  if (const VoxCapture* q = vox_capture(vb))
+  {
+    xyz = q->xyz;
+    stride = q->stride;
+    n = q->n;
+    code += q->code_off;
+    d = vb.desc + blockIdx.y;
+    bitmap += (int64_t) blockIdx.y * vb.slot_words;
+  }
   const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n)
     return;
@@ -310,8 +384,13 @@ __global__ __launch_bounds__(256) void k_vox_mark(const float* __restrict__ xyz,
   atomicOr(&bitmap[d->word_ofs[c] + (pos >> 5)], 1u << (unsigned) (pos & 31ull));
 }
 
-__global__ __launch_bounds__(256) void k_vox_popcount(const unsigned* __restrict__ bitmap, int* __restrict__ blk_cnt)
+__global__ __launch_bounds__(256) void k_vox_popcount(const unsigned* __restrict__ bitmap, int* __restrict__ blk_cnt, VoxBatch vb)
 {
+  if (vb.cap)
+  {
+    bitmap += (int64_t) blockIdx.y * vb.slot_words;
+    blk_cnt += (int64_t) blockIdx.y * (vb.slot_words / kWordsPerBlock);
+  }
   const uint4* w = (const uint4*) (bitmap + (size_t) blockIdx.x * kWordsPerBlock) + threadIdx.x * 4;
   int cnt = 0;
   for (int k = 0; k < 4; k++)
@@ -356,9 +435,19 @@ __device__ void vox_totals(VoxDesc* d, const int* __restrict__ blk_prefix, long 
 }
 
 // Emit the voxels in bitmap order = (camera, x, y, z) lexicographic order; coordinates as localization.cpp:313-324.
+// vb (a batch): capture y's voxels go to the common array from cloud_off[y] on (k_vox_chain).
 __global__ __launch_bounds__(256) void k_vox_emit(const unsigned* __restrict__ bitmap, const int* __restrict__ blk_prefix,
-  const VoxDesc* __restrict__ d, double cell, float* __restrict__ out_xyz, int32_t* __restrict__ out_cam)
+  const VoxDesc* __restrict__ d, double cell, float* __restrict__ out_xyz, int32_t* __restrict__ out_cam, VoxBatch vb,
+  const int* __restrict__ cloud_off)
 {
+  int64_t out0 = 0;
+  if (vb.cap)
+  {
+    bitmap += (int64_t) blockIdx.y * vb.slot_words;
+    blk_prefix += (int64_t) blockIdx.y * (vb.slot_words / kWordsPerBlock);
+    d = vb.desc + blockIdx.y;
+    out0 = cloud_off[blockIdx.y];
+  }
   const size_t w0 = (size_t) blockIdx.x * kWordsPerBlock + (size_t) threadIdx.x * 16;
   unsigned w[16];
   const uint4* src = (const uint4*) (bitmap + w0);
@@ -389,7 +478,7 @@ __global__ __launch_bounds__(256) void k_vox_emit(const unsigned* __restrict__ b
   const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
   if (!total || d->error)
     return;
-  const int64_t k0 = (int64_t) blk_prefix[blockIdx.x];
+  const int64_t k0 = out0 + (int64_t) blk_prefix[blockIdx.x];
   const size_t wg0 = (size_t) blockIdx.x * kWordsPerBlock;
   const int c = wg0 >= d->word_ofs[1] ? 1 : 0;  // (camera 1 starts on a block boundary: a work-group is of one camera)
   const unsigned long long ny = (unsigned long long) d->dim[c][1], nz = (unsigned long long) d->dim[c][2];
@@ -463,6 +552,18 @@ __global__ __launch_bounds__(256) void k_vox_emit(const unsigned* __restrict__ b
   }
 }
 
+// agh_localize_batch: the batch's device-side cloud offsets from the captures' voxel counts (capture k = cloud k)
+__global__ void k_vox_chain(const VoxDesc* __restrict__ d, int C, int* __restrict__ cloud_off)
+{
+  int off = 0;
+  cloud_off[0] = 0;
+  for (int k = 0; k < C; k++)
+  {
+    off += (int) (d[k].n_vox[0] + d[k].n_vox[1]);
+    cloud_off[k + 1] = off;
+  }
+}
+
 int vox_stage1(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, int64_t size_left, int dense,
   const double workspace[6], double cell, hipStream_t st, int64_t cap_words, VoxDesc* host_desc, bool with_lattice)
 {
@@ -480,16 +581,16 @@ int vox_stage1(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, int
   {
     if (!dense)
     {
-      hipLaunchKernelGGL(k_vox_count, dim3((unsigned) nb), dim3(kPreBlock), 0, st, d_xyz, stride_floats, n, c->d_vox_blk);
+      hipLaunchKernelGGL(k_vox_count, dim3((unsigned) nb), dim3(kPreBlock), 0, st, d_xyz, stride_floats, n, c->d_vox_blk, VoxBatch{});
       hipLaunchKernelGGL(k_vox_scan, dim3(1), dim3(1024), 0, st, c->d_vox_blk, nb, (long long*) nullptr, c->d_vox_desc,
-        (VoxDesc*) nullptr, (VoxDesc*) nullptr, (int*) nullptr);
+        (VoxDesc*) nullptr, (VoxDesc*) nullptr, (int*) nullptr, VoxBatch{});
     }
     hipLaunchKernelGGL(k_vox_classify, dim3((unsigned) nb), dim3(kPreBlock), 0, st, d_xyz, stride_floats, n,
-      dense ? (const int*) nullptr : (const int*) c->d_vox_blk, size_left, ws, c->d_vox_code, c->d_vox_desc);
+      dense ? (const int*) nullptr : (const int*) c->d_vox_blk, size_left, ws, c->d_vox_code, c->d_vox_desc, VoxBatch{});
   }
   if (with_lattice)  // (the speculative pass computes the lattice inside stage 2's first kernel)
     hipLaunchKernelGGL(k_vox_lattice, dim3(1), dim3(1), 0, st, c->d_vox_desc, cell, (unsigned long long) kVoxMaxWords,
-      (unsigned long long) cap_words, host_desc);
+      (unsigned long long) cap_words, host_desc, VoxBatch{});
   return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
 }
 
@@ -505,21 +606,60 @@ int vox_stage2(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, dou
   if (with_lattice)  // speculative pass: clear + lattice in one launch (n_words is a multiple of 4096 words)
     hipLaunchKernelGGL(k_vox_clear_lattice, dim3((unsigned) std::max<int64_t>(1, std::min<int64_t>(n_words / 4 / 256, 2048))), dim3(256), 0,
       st, reinterpret_cast<uint4*>(c->d_vox_bitmap), n_words / 4, c->d_vox_desc, cell, (unsigned long long) kVoxMaxWords,
-      (unsigned long long) cap_words, host_desc);
+      (unsigned long long) cap_words, host_desc, VoxBatch{});
   else if (hipMemsetAsync(c->d_vox_bitmap, 0, (size_t) n_words * 4, st) != hipSuccess)
     return AGH_ERR_HIP;
   if (n > 0 && n_words > 0)
   {
     hipLaunchKernelGGL(k_vox_mark, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, d_xyz, stride_floats, n,
-      (const uint8_t*) c->d_vox_code, (const VoxDesc*) c->d_vox_desc, cell, c->d_vox_bitmap);
+      (const uint8_t*) c->d_vox_code, (const VoxDesc*) c->d_vox_desc, cell, c->d_vox_bitmap, VoxBatch{});
     hipLaunchKernelGGL(k_vox_popcount, dim3((unsigned) nb2), dim3(256), 0, st, (const unsigned*) c->d_vox_bitmap,
-      c->d_vox_blk2);
+      c->d_vox_blk2, VoxBatch{});
   }
   hipLaunchKernelGGL(k_vox_scan, dim3(1), dim3(1024), 0, st, c->d_vox_blk2, nb2, c->d_vox_total, (VoxDesc*) nullptr, c->d_vox_desc,
-    host_desc, cloud_off_out);  // (+ the voxel counts per camera, the host mirror, the device-side cloud offsets)
+    host_desc, cloud_off_out, VoxBatch{});  // (+ the voxel counts per camera, the host mirror, the device-side cloud offsets)
   if (n > 0 && n_words > 0)
     hipLaunchKernelGGL(k_vox_emit, dim3((unsigned) nb2), dim3(256), 0, st, (const unsigned*) c->d_vox_bitmap,
-      (const int*) c->d_vox_blk2, (const VoxDesc*) c->d_vox_desc, cell, c->d_vox_xyz, c->d_vox_cam);
+      (const int*) c->d_vox_blk2, (const VoxDesc*) c->d_vox_desc, cell, c->d_vox_xyz, c->d_vox_cam, VoxBatch{}, (const int*) nullptr);
+  return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
+}
+
+// agh_localize_batch: the preprocessing of C captures, one launch per stage, capture = blockIdx.y (see VoxBatch).  Stage 1 (finite
+// counts, their scan with the descriptors' reset, camera ids, workspace, extrema); with probe, the lattices next (the caller waits
+// for them and sizes the slots); otherwise the speculative stage 2 on slots of vb.slot_words words: clear + lattice, mark,
+// popcount, scan + counts, the batch's cloud offsets into cloud_off, emit into out_xyz / out_cam.  blk: the raw block counts,
+// blk2: C x slot_words / kWordsPerBlock popcounts; nb_max, n_max: the largest capture's raw blocks and points.
+int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
+  unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st)
+{
+  const unsigned Cy = (unsigned) C;
+  if (nb_max > 0 && any_finite_scan)
+    hipLaunchKernelGGL(k_vox_count, dim3((unsigned) nb_max, Cy), dim3(kPreBlock), 0, st, (const float*) nullptr, (int64_t) 0,
+      (int64_t) 0, blk, vb);
+  hipLaunchKernelGGL(k_vox_scan, dim3(1, Cy), dim3(1024), 0, st, blk, (int64_t) 0, (long long*) nullptr, vb.desc, (VoxDesc*) nullptr,
+    (VoxDesc*) nullptr, (int*) nullptr, vb);
+  if (nb_max > 0)
+    hipLaunchKernelGGL(k_vox_classify, dim3((unsigned) nb_max, Cy), dim3(kPreBlock), 0, st, (const float*) nullptr, (int64_t) 0,
+      (int64_t) 0, (const int*) blk, (int64_t) 0, VoxWorkspace{}, code, vb.desc, vb);
+  if (probe)
+  {
+    hipLaunchKernelGGL(k_vox_lattice, dim3(1, Cy), dim3(1), 0, st, vb.desc, cell, (unsigned long long) kVoxMaxWords,
+      (unsigned long long) kVoxMaxWords, vb.host_desc, vb);
+    return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
+  }
+  const int64_t W = vb.slot_words, nb2 = W / kWordsPerBlock;
+  hipLaunchKernelGGL(k_vox_clear_lattice, dim3((unsigned) std::max<int64_t>(1, std::min<int64_t>(W / 4 / 256, 2048)), Cy), dim3(256), 0,
+    st, reinterpret_cast<uint4*>(bitmap), W / 4, vb.desc, cell, (unsigned long long) kVoxMaxWords, (unsigned long long) W,
+    vb.host_desc, vb);
+  if (n_max > 0)
+    hipLaunchKernelGGL(k_vox_mark, dim3((unsigned) ((n_max + 255) / 256), Cy), dim3(256), 0, st, (const float*) nullptr, (int64_t) 0,
+      (int64_t) 0, (const uint8_t*) code, (const VoxDesc*) vb.desc, cell, bitmap, vb);
+  hipLaunchKernelGGL(k_vox_popcount, dim3((unsigned) nb2, Cy), dim3(256), 0, st, (const unsigned*) bitmap, blk2, vb);
+  hipLaunchKernelGGL(k_vox_scan, dim3(1, Cy), dim3(1024), 0, st, blk2, (int64_t) 0, (long long*) nullptr, (VoxDesc*) nullptr,
+    vb.desc, vb.host_desc, (int*) nullptr, vb);
+  hipLaunchKernelGGL(k_vox_chain, dim3(1), dim3(1), 0, st, (const VoxDesc*) vb.desc, C, cloud_off);
+  hipLaunchKernelGGL(k_vox_emit, dim3((unsigned) nb2, Cy), dim3(256), 0, st, (const unsigned*) bitmap, (const int*) blk2,
+    (const VoxDesc*) vb.desc, cell, out_xyz, out_cam, vb, (const int*) cloud_off);
   return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
 }
 

@@ -270,6 +270,45 @@ int agh_localize_stage(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int
 int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result);
 
+/* The chain of agh_localize over a BATCH of captures in one call, with ONE synchronisation (offline evaluation over a
+ * directory of PCD pairs, a cell with several sensors or arms): 1 <= n_captures <= 64, fewer than 2^30 raw points in all.
+ * Capture k is xyz[k] (stride_bytes[k], n[k] points) with its own record lp[k]: size_left, dense, workspace, sample_idx /
+ * n_samples / sample_seed are per capture; classify, cell_size, min_inliers, min_length and filters_boundaries must be equal
+ * across the batch (AGH_ERR_INVALID_ARGUMENT otherwise).  Camera origins and hand geometry are the context's, as for
+ * agh_set_cloud_batch.  The voxelised captures lie end to end in one cloud batch (capture k = cloud k), are searched in one
+ * launch set, classified together, and their kept hands go through the handle search side by side, one list per capture.
+ * Capture k's results equal what agh_localize returns for capture k alone on the same samples, bit for bit: n_voxels,
+ * n_hypotheses, every field of every hand record but epoch (one call stamps one epoch), every handle field and the inlier
+ * lists.  agh_hypothesis::sample is the position in capture k's own sample list, samples_out holds capture-local voxel indices
+ * (sum of n_samples entries, in capture order), capture k's inlier indices point into capture k's own span of hands_out, and
+ * a drawn list is agh_localize's strata over capture k's own voxel count with capture k's seed.  Every output is the
+ * concatenation of the captures' spans in capture order; results[k] (n_captures records) holds capture k's counts and the
+ * start of its spans.  The 8192-hand limit of the handle search applies per capture.
+ * Errors: output buffers too small -> AGH_ERR_CAPACITY with every results[k] filled (size and repeat); a sample index outside
+ * its capture's voxelised cloud -> AGH_ERR_INVALID_ARGUMENT, the error text names the capture; classify without an SVM ->
+ * AGH_ERR_NO_SVM; a call while an agh_localize_begin chain is in flight -> AGH_ERR_STATE, the chain untouched (and
+ * agh_localize_begin refuses while a batch runs).  Capacity-class AGH_ERR_RETRY is repeated inside the call, as agh_localize
+ * does.  Synchronisations: one in the steady state.  The first batch of a context (no voxel bitmaps yet) takes one more, for the
+ * lattice sizes; a batch whose lattices outgrew the kept bitmap slots is run once more, in the same call, with slots sized from
+ * them.  Every stage -- preprocessing (a bitmap slot per capture), search, classification, compaction and handle search --
+ * runs once for the whole batch.  With filters_boundaries the boundary filter is applied at the
+ * compaction, against each hand's own capture's workspace (the classifier runs on every hypothesis of the batch).
+ * After the call the context holds the voxelised batch as its bound batch of clouds, as after agh_set_cloud_batch (agh_get_cloud,
+ * agh_get_frames, agh_get_images ... see the whole batch); a failed call leaves the context as a failed agh_localize does. */
+typedef struct agh_localize_batch_result
+{
+  agh_localize_result r; /* this capture's counts, exactly as agh_localize reports them for it */
+  int64_t first_handle, first_inlier_idx, first_hand, first_sample; /* its spans in the concatenated outputs */
+} agh_localize_batch_result;
+int agh_localize_batch(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+/* The same with the captures in device memory: xyz[k] (a host array of device pointers) is read in place with stride_bytes[k]
+ * and must stay valid until the call returns. */
+int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+
 /* The context's current cloud: packed xyz (3 floats per point) and camera ids; returns the number of points. */
 int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap);
 

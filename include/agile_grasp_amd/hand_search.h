@@ -373,6 +373,84 @@ public:
     return true;
   }
 
+  /** Additional: the chain of localize over several captures in one call (agh_localize_batch): capture k is clouds[k] with
+   *  sizes_left[k], workspaces[k] and indices[k] (empty: num_samples drawn on the device, seeded with the sample seed + k).
+   *  Per capture the hands the classifier kept, the handles and their inlier lists (indices into that capture's hands), exactly
+   *  what localize returns for it.  @return false (after printing) on error */
+  bool localizeBatch(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<VectorXd>& workspaces, double cell_size, const std::vector<std::vector<int> >& indices,
+    const std::string& svm_filename, int min_inliers, double min_length, std::vector<std::vector<agh_hypothesis> >& hands_out,
+    std::vector<std::vector<agh_handle> >& handles_out, std::vector<std::vector<std::int32_t> >& inliers_out,
+    bool filters_boundaries = false)
+  {
+    const std::size_t C = clouds.size();
+    hands_out.assign(C, std::vector<agh_hypothesis>());
+    handles_out.assign(C, std::vector<agh_handle>());
+    inliers_out.assign(C, std::vector<std::int32_t>());
+    if (C == 0 || sizes_left.size() != C || workspaces.size() != C || indices.size() != C)
+    {
+      std::cout << " Error: localizeBatch needs one size_left, workspace and index list per cloud\n";
+      return false;
+    }
+    if (!ensureContext())
+      return false;
+    if (agh_load_svm_file(ctx_, svm_filename.c_str()) != AGH_OK)
+    {
+      std::cout << " Exception: " << agh_last_error(ctx_) << "\n";  // learning.cpp:187-191
+      return false;
+    }
+    const std::uint64_t seed = sample_seed_set_ ? (std::uint64_t) sample_seed_ : (std::uint64_t) std::time(nullptr);
+    std::vector<agh_localize_params> lp(C);
+    std::vector<std::vector<std::int32_t> > idx(C);
+    std::vector<const float*> xyz(C);
+    std::vector<std::int64_t> stride(C), n(C);
+    std::int64_t cap = 1, n_samples = 0;
+    for (std::size_t k = 0; k < C; k++)
+    {
+      agh_localize_params& p = lp[k];
+      p.size_left = (std::int64_t) sizes_left[k];
+      p.dense = cloud_is_dense(*clouds[k]) ? 1 : 0;
+      p.classify = 1;
+      for (int i = 0; i < 6; i++)
+        p.workspace[i] = workspaces[k](i);
+      p.cell_size = cell_size;
+      idx[k].assign(indices[k].begin(), indices[k].end());
+      p.sample_idx = idx[k].empty() ? nullptr : idx[k].data();
+      p.n_samples = idx[k].empty() ? (std::int64_t) (num_samples_ < 0 ? 0 : num_samples_) : (std::int64_t) idx[k].size();
+      p.sample_seed = seed + (std::uint64_t) k;
+      p.min_inliers = min_inliers;
+      p.filters_boundaries = filters_boundaries ? 1 : 0;
+      p.min_length = min_length;
+      n[k] = (std::int64_t) clouds[k]->size();
+      xyz[k] = n[k] > 0 ? &clouds[k]->points[0].x : nullptr;
+      stride[k] = (std::int64_t) sizeof(clouds[k]->points[0]);
+      cap += p.n_samples * 8 < 8192 ? p.n_samples * 8 : 8192;
+      n_samples += p.n_samples;
+    }
+    std::vector<agh_hypothesis> hands((std::size_t) cap);
+    std::vector<agh_handle> handles((std::size_t) cap);
+    std::vector<std::int32_t> inl((std::size_t) cap);
+    std::vector<std::int32_t> samples((std::size_t) n_samples + 1);
+    std::vector<agh_localize_batch_result> res(C);
+    if (agh_localize_batch(ctx_, xyz.data(), stride.data(), n.data(), lp.data(), (std::int32_t) C, handles.data(), cap, inl.data(),
+          cap, hands.data(), cap, samples.data(), res.data()) != AGH_OK)
+    {
+      fail("agh_localize_batch");
+      return false;
+    }
+    searched_n_ = 0;
+    for (std::size_t k = 0; k < C; k++)
+    {
+      const agh_localize_batch_result& r = res[k];
+      hands_out[k].assign(hands.begin() + r.first_hand, hands.begin() + r.first_hand + r.r.n_hands);
+      handles_out[k].assign(handles.begin() + r.first_handle, handles.begin() + r.first_handle + r.r.n_handles);
+      inliers_out[k].assign(inl.begin() + r.first_inlier_idx, inl.begin() + r.first_inlier_idx + r.r.n_inlier_idx);
+      searched_n_ += r.r.n_voxels;
+    }
+    last_samples_.assign(samples.begin(), samples.begin() + n_samples);
+    return true;
+  }
+
   /** agh_localize_stage: the NEXT capture up, beside the chain in flight (keep `next` alive and unchanged until the
    *  localizeEnd of the chain that searches it has returned). */
   bool localizeStage(const PointCloud::Ptr& next)

@@ -311,6 +311,56 @@ public:
     std::vector<std::int32_t> idx;
     if (!search_->localizeEnd(hands, handles, idx))
       return handle_list;
+    return toHandles(cloud_in, hands, handles, idx, antipodal_hands);
+  }
+
+  /** Additional: localizeHandles over several captures in one call (agh_localize_batch, one synchronisation): capture k is
+   *  clouds[k] with sizes_left[k] and indices_per_cloud[k] (empty: drawn on the device, see HandSearch::localizeBatch), searched
+   *  in (*workspaces)[k] -- or, without `workspaces`, in this object's workspace.  Per capture the same handles as
+   *  localizeHandles on that capture and indices; (*antipodal_hands_per_cloud)[k] receives its kept hands. */
+  std::vector<std::vector<Handle> > localizeHandlesBatch(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<std::vector<int> >& indices_per_cloud, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_cloud = nullptr, const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    const std::size_t C = clouds.size();
+    std::vector<std::vector<Handle> > out(C);
+    if (antipodal_hands_per_cloud)
+      antipodal_hands_per_cloud->assign(C, std::vector<GraspHypothesis>());
+    if (pending_cloud_)
+    {
+      std::cout << " Error: localizeHandlesBatch while a chain is pending (localizeHandlesEnd first)\n";
+      return out;
+    }
+    for (std::size_t k = 0; k < C; k++)
+      if (!clouds[k] || clouds[k]->size() == 0 || k >= sizes_left.size() || sizes_left[k] == 0)
+      {
+        std::cout << "Input cloud is empty!\n";
+        return out;
+      }
+    std::ifstream f(svm_filename.c_str());
+    if (!f.good())
+    {
+      std::cout << " Error: File " << svm_filename << " does not exist!\n";  // learning.cpp:172-178
+      return out;
+    }
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(C, workspace_);
+    std::vector<std::vector<agh_hypothesis> > hands;
+    std::vector<std::vector<agh_handle> > handles;
+    std::vector<std::vector<std::int32_t> > idx;
+    if (!search_->localizeBatch(clouds, sizes_left, ws, 0.003, indices_per_cloud, svm_filename, min_inliers, min_length, hands, handles,
+          idx, filters_boundaries_))
+      return out;
+    for (std::size_t k = 0; k < C; k++)
+      out[k] = toHandles(clouds[k], hands[k], handles[k], idx[k], antipodal_hands_per_cloud ? &(*antipodal_hands_per_cloud)[k] : nullptr);
+    return out;
+  }
+
+  /** the searched hands, handles and inlier lists of one capture as the reference's objects (the tail of localizeHandlesEnd) */
+  std::vector<Handle> toHandles(const PointCloud::Ptr& cloud_in, const std::vector<agh_hypothesis>& hands,
+    const std::vector<agh_handle>& handles, const std::vector<std::int32_t>& idx, std::vector<GraspHypothesis>* antipodal_hands)
+  {
+    std::vector<Handle> handle_list;
     remove_nan_in_place(*cloud_in);  // localization.cpp:27 filters the caller's cloud in place
     if (filters_boundaries_)
       std::cout << "Filtering out hands close to workspace boundaries ... (on the device, ahead of the classifier)\n";

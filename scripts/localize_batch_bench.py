@@ -1,0 +1,84 @@
+"""agh_localize_batch against agh_localize one capture after the other, on C2-style raw captures (700k points, 2000 drawn
+samples, classifier on), batches of 1 / 4 / 8.  Medians over --reps calls, ms PER CAPTURE:
+  batch_host      agh_localize_batch (host buffers: the captures are packed end to end and uploaded)
+  batch_device    agh_localize_batch_device (torch CUDA tensors read in place)
+  sequential      agh_localize on each capture of the batch, one after the other, on one context
+  two_contexts    the same captures on two contexts taking turns: agh_localize_begin(k + 1) on the other context before
+                  agh_localize_end(k) (the two chains' kernels side by side) -- what a caller could do before the batch
+One JSON line; the GPU and the way it was run go in with --note.  scripts/localize_batch_trace.sh takes the kernel trace."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+from agile_grasp_amd import binding, synthetic
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def median_ms(fn, reps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(t))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--batches", default="1,4,8")
+    ap.add_argument("--note", default="")
+    ap.add_argument("--batch-only", action="store_true", help="the batch calls alone (for a kernel trace)")
+    a = ap.parse_args()
+    import torch
+
+    sizes = [int(b) for b in a.batches.split(",")]
+    caps = [synthetic.make_raw_cloud(700_000, 21 + k) for k in range(max(sizes))]
+    z = np.load(os.path.join(ROOT, "tests", "golden", "svm_weights.npz"))
+    ctx = binding.Context(caps[0].cam_origins)
+    ctx.load_svm(z["w"], float(z["rho"]))
+    other = binding.Context(caps[0].cam_origins)
+    other.load_svm(z["w"], float(z["rho"]))
+    dev = [torch.from_numpy(c.xyz).cuda() for c in caps]
+    kw = dict(classify=True, min_inliers=3, min_length=0.005)
+    out = {"points": 700_000, "samples": 2000, "reps": a.reps, "note": a.note}
+    for B in sizes:
+        cs = caps[:B]
+        sl, ws = [c.size_left for c in cs], [c.workspace for c in cs]
+        seeds = [5 + k for k in range(B)]
+        host = median_ms(lambda: ctx.localize_batch([c.xyz for c in cs], sl, ws, n_samples=2000, sample_seeds=seeds, **kw), a.reps)
+        devb = median_ms(lambda: ctx.localize_batch(dev[:B], sl, ws, n_samples=2000, sample_seeds=seeds, **kw), a.reps)
+        if a.batch_only:
+            out[f"b{B}"] = {"batch_host_ms": round(host / B, 4), "batch_device_ms": round(devb / B, 4)}
+            continue
+
+        def seq():
+            for k, c in enumerate(cs):
+                ctx.localize(c.xyz, c.size_left, c.workspace, n_samples=2000, sample_seed=seeds[k], **kw)
+
+        sq = median_ms(seq, a.reps)
+
+        def turns():
+            pair = (ctx, other)
+            for k, c in enumerate(cs):
+                pair[k % 2].localize_begin(c.xyz, c.size_left, c.workspace, n_samples=2000, sample_seed=seeds[k], **kw)
+                if k > 0:
+                    pair[(k - 1) % 2].localize_end()
+            pair[(len(cs) - 1) % 2].localize_end()
+
+        two = median_ms(turns, a.reps)
+        out[f"b{B}"] = {"batch_host_ms": round(host / B, 4), "batch_device_ms": round(devb / B, 4),
+                        "sequential_ms": round(sq / B, 4), "two_contexts_ms": round(two / B, 4)}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
