@@ -82,7 +82,7 @@ EXPORTS = [
     "agh_default_params", "agh_create", "agh_destroy", "agh_last_error", "agh_set_cloud", "agh_set_cloud_device", "agh_set_cloud_batch", "agh_set_cloud_batch_device",
     "agh_preprocess", "agh_preprocess_device", "agh_localize", "agh_localize_device", "agh_localize_begin", "agh_localize_stage", "agh_localize_end", "agh_localize_batch", "agh_localize_batch_device", "agh_get_cloud", "agh_find_handles", "agh_find_hands", "agh_find_hands_device", "agh_load_svm", "agh_load_svm_file", "agh_classify",
     "agh_classify_device", "agh_get_frames", "agh_get_neighbor_counts", "agh_get_images", "agh_get_hog",
-    "agh_get_normals", "agh_get_timing", "agh_get_timing_counts", "agh_get_grid_stats", "agh_set_profile", "agh_synchronize", "agh_selftest_math",
+    "agh_get_normals", "agh_get_timing", "agh_get_timing_counts", "agh_get_grid_stats", "agh_get_grid_desc", "agh_set_profile", "agh_synchronize", "agh_selftest_math",
     "agh_set_training_images", "agh_get_training_images", "agh_hog_images", "agh_train_svm", "agh_save_svm_file",
     "agh_load_svm_model", "agh_get_learning_points", "agh_get_epoch", "agh_get_packed_images", "agh_classify_images", "agh_comm_rccl_origin",
     "agh_save_svm_file_ex", "agh_comm_unique_id", "agh_comm_init", "agh_comm_init_local", "agh_comm_destroy", "agh_comm_rank", "agh_comm_last_count", "agh_comm_last_exchange", "agh_comm_set_segment_records", "agh_comm_inject_fault",
@@ -775,6 +775,14 @@ class Context:
         v = (C.c_int64 * 3)()
         self._check(self.lib.agh_get_grid_stats(self._h, v, C.c_int32(3)))
         return {"builds": int(v[0]), "cold": int(v[1]), "misses": int(v[2])}
+
+    def grid_desc(self, cloud: int = 0) -> dict:
+        """The grid descriptor the last build used for cloud `cloud` of the batch: origin, cell size, cells per axis, open faces."""
+        mn, dim = (C.c_double * 3)(), (C.c_int32 * 3)()
+        cell, opn = C.c_double(0.0), C.c_uint32(0)
+        self._check(self.lib.agh_get_grid_desc(self._h, C.c_int32(cloud), mn, C.byref(cell), dim, C.byref(opn)))
+        return {"mn": tuple(float(v) for v in mn), "cell": float(cell.value), "dim": tuple(int(v) for v in dim),
+                "open": int(opn.value)}
 
     def set_profile(self, level: int):
         self._check(self.lib.agh_set_profile(self._h, C.c_int32(level)))

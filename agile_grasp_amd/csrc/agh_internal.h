@@ -606,8 +606,10 @@ __device__ __forceinline__ float dec_float(unsigned u)
 
 __device__ __forceinline__ int cell_coord(const GridDesc& g, double v, int a)
 {
-  int c = (int) floor((v - g.mn[a]) * g.inv_cell);
-  return min(max(c, 0), g.dim[a] - 1);
+  // clamped in double, BEFORE the conversion: a finite point 1e30 m outside a kept descriptor is 5e31 cells away, which no int
+  // holds (the conversion of such a value is undefined).  A NaN ends in cell 0 (fmax returns its other argument).
+  const double f = floor((v - g.mn[a]) * g.inv_cell);
+  return (int) fmin(fmax(f, 0.0), (double) (g.dim[a] - 1));
 }
 
 // The view of the grid of cloud k / of the cloud that holds point p (uniform per work-group: scalar loads).

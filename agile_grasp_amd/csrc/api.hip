@@ -1602,6 +1602,39 @@ int agh_get_grid_stats(agh_ctx* ctx, int64_t* stats, int32_t cap)
   return k;
 }
 
+int agh_get_grid_desc(agh_ctx* ctx, int32_t cloud, double mn[3], double* cell, int32_t dim[3], uint32_t* open)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (cloud < 0 || cloud >= c->n_clouds)
+  {
+    c->err = "agh_get_grid_desc: no such cloud in the context's batch";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  if (c->grid_builds == 0 || !c->d_desc || cloud >= c->clouds_cap)
+  {
+    c->err = "agh_get_grid_desc: no grid has been built yet";
+    return AGH_ERR_NO_CLOUD;
+  }
+  GridDesc g;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipDeviceSynchronize());  // (as agh_get_grid_stats: the build may have run on any of the caller's streams)
+  HIPCHK(c, hipMemcpy(&g, c->d_desc + cloud, sizeof(GridDesc), hipMemcpyDeviceToHost));
+  for (int a = 0; a < 3; a++)
+  {
+    if (mn)
+      mn[a] = g.mn[a];
+    if (dim)
+      dim[a] = g.dim[a];
+  }
+  if (cell)
+    *cell = g.cell;
+  if (open)
+    *open = g.open;
+  return AGH_OK;
+}
+
 int64_t agh_selftest_math(agh_ctx* ctx, int64_t n, uint64_t seed)
 {
   if (!ctx)

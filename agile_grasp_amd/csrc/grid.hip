@@ -39,22 +39,29 @@ __device__ void desc_finish(GridDesc* d, double base_cell, int64_t n, const floa
     mn[a] = any ? (double) lo[a] : 0.0;
     mx[a] = any ? (double) hi[a] : 0.0;
   }
+  // The cell doubles until the grid fits kCellCap cells.  The counts stay in double until they do: an extent of 1e9 cells and
+  // more (two finite points 2e30 m apart are a valid float32 cloud) does not fit an int, and a converted count that wrapped
+  // would end the loop with a negative product.  Every count is >= 1, so a product <= kCellCap bounds each of them by kCellCap
+  // and the conversion below is exact.  The loop ends: a doubling halves every quotient, the largest one (float32 extents:
+  // below 2^129 / 0.02 < 2^135) drops below 1 after at most 135 of them, and 0.02 x 2^135 is far from overflowing a double.
   double cell = base_cell;
-  int dim[3];
+  double cnt[3];
   for (;;)
   {
     double prod = 1.0;
     for (int a = 0; a < 3; a++)
     {
-      dim[a] = (int) floor((mx[a] - mn[a]) / cell) + 1;
-      prod *= (double) dim[a];
+      cnt[a] = floor((mx[a] - mn[a]) / cell) + 1.0;
+      prod *= cnt[a];
     }
     if (prod <= (double) kCellCap)
       break;
     cell *= 2.0;
   }
+  int dim[3];
   for (int a = 0; a < 3; a++)
   {
+    dim[a] = (int) cnt[a];
     d->mn[a] = mn[a];
     d->dim[a] = dim[a];
   }
@@ -348,8 +355,21 @@ __device__ void desc_next(const GridDesc u, GridDesc* used, GridDesc* next, unsi
   *next = o;
 }
 
-// Exclusive scan of the cell histogram in ONE launch (decoupled look-back): tiles of 1024 cells are walked round-robin
-// by 256 resident work-groups, so a tile's predecessors are always running or done and the look-back cannot deadlock.  A tile
+// Exclusive scan of the cell histogram in ONE launch (decoupled look-back): tiles of kScanBlock cells are walked round-robin
+// by the G = gridDim.x work-groups of a cloud (256 for one cloud, 64 per cloud of a batch), so a tile's predecessors are always
+// running or done and the look-back cannot deadlock.
+// Forward progress, also for the tiles of a second and later pass (more than G tiles: above 8.4 m^3 of box at the base cell
+// for one cloud, above 2.1 m^3 per cloud of a batch).  A look-back only reads tiles of its OWN cloud, and tile t only waits
+// for tiles < t.  (i) While all G groups of a cloud are dispatched, every tile of that cloud completes, by induction over
+// t: tile 0 waits for nothing; the owner of tile t (group t mod G) reaches it after its earlier tiles t - G, t - 2G, ..., all
+// < t and complete by induction, and then waits only for tiles < t.  A group of a second pass may wait for the FIRST tile of a
+// higher-numbered group, which is why (i) asks for all G groups and not only the lower-numbered ones.  (ii) Groups are
+// dispatched in order, x fastest, then y: when a group of cloud k is dispatched, every group of the clouds < k has been.  Take
+// the lowest cloud that is not complete.  Either all its groups are dispatched, and it completes by (i), or the dispatcher
+// stands inside it; then no group of a later cloud holds a slot, the earlier clouds are complete and their groups have
+// left, so its remaining groups are dispatched as soon as the device has room for them.  What this needs from the device is
+// room for G groups of 256 threads at once (256 groups: one per CU of an MI355X; the batch's 64 x 64 = 4096 groups are more
+// than are resident at once, and need not be) and that nothing else on the device holds its slots for ever.  A tile
 // publishes (build number, flag, value) in one 64-bit word: flag 1 = the tile's own total, 2 = its inclusive prefix;
 // the build number makes stale words from earlier builds invisible, so the descriptors never need clearing.  The kernel
 // also zeroes the histogram it has read: the next build starts from a clean one without a memset.  And its last work-group, which

@@ -252,7 +252,7 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a
  * begin).  Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_end,
  * agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error, agh_destroy, the host-side
- * counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats) and the communicator's bookkeeping (agh_comm_rank,
+ * counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats, agh_get_grid_desc) and the communicator's bookkeeping (agh_comm_rank,
  * agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault, agh_comm_set_segment_records, agh_comm_last_*) may be called on
  * the context.  Every other call on it returns AGH_ERR_STATE without touching anything: agh_set_cloud*, agh_preprocess*,
  * agh_find_hands*, agh_classify*, agh_find_handles, agh_localize*, agh_remove_plane, agh_get_cloud and every getter of device
@@ -519,6 +519,11 @@ int agh_get_timing_counts(agh_ctx* ctx, int32_t* counts, int32_t cap);
  * outside the grid descriptor the build kept from the previous one (a miss: still exact, only slower).  Writes min(cap, 3)
  * values and returns how many; synchronises the context's device. */
 int agh_get_grid_stats(agh_ctx* ctx, int64_t* stats, int32_t cap);
+/* The grid descriptor the LAST build used for cloud `cloud` of the context's batch (0 for a single cloud): the origin mn, the
+ * cell size, the cells per axis and the open faces (bit 2a = low face of axis a, 2a + 1 = its high face: the cloud had points
+ * beyond it).  Read-only: a copy of the device's descriptor after a synchronisation of the context's device; any of the four
+ * outputs may be NULL.  AGH_ERR_INVALID_ARGUMENT for a cloud outside [0, n_clouds), AGH_ERR_NO_CLOUD before the first build. */
+int agh_get_grid_desc(agh_ctx* ctx, int32_t cloud, double mn[3], double* cell, int32_t dim[3], uint32_t* open);
 /* Change agh_params::profile of a live context (0 .. 3); pending timings are dropped. */
 int agh_set_profile(agh_ctx* ctx, int32_t level);
 int agh_synchronize(agh_ctx* ctx);

@@ -87,12 +87,14 @@ struct GridIndex
   std::vector<int64_t> start; /* CSR over cells */
   std::vector<int32_t> items;
 
+  /* clamped in double, before the conversion: a cell count of 1e30 and more (finite float32 points that far apart) fits no integer */
+  inline int64_t clamp_cell(double v, int a) const { return (int64_t) std::min(std::max(v, 0.0), (double) (dim[a] - 1)); }
+
   inline void coords(const float* p, int64_t c[3]) const
   {
     for (int a = 0; a < 3; a++)
     {
-      int64_t v = (int64_t) std::floor(((double) p[a] - mn[a]) / cell);
-      c[a] = std::min(std::max(v, (int64_t) 0), dim[a] - 1);
+      c[a] = clamp_cell(std::floor(((double) p[a] - mn[a]) / cell), a);
     }
   }
 
@@ -123,15 +125,18 @@ struct GridIndex
     if (n_finite == 0)
       for (int a = 0; a < 3; a++)
         mn[a] = mx[a] = 0;
-    for (int a = 0; a < 3; a++)
-      dim[a] = (int64_t) std::floor((mx[a] - mn[a]) / cell) + 1;
-    /* keep the table bounded for sparse far-flung clouds */
-    while ((double) dim[0] * (double) dim[1] * (double) dim[2] > 6.4e7)
+    /* keep the table bounded for sparse far-flung clouds (the counts in double until they fit: see clamp_cell) */
+    double cnt[3];
+    for (;;)
     {
-      cell *= 2.0;
       for (int a = 0; a < 3; a++)
-        dim[a] = (int64_t) std::floor((mx[a] - mn[a]) / cell) + 1;
+        cnt[a] = std::floor((mx[a] - mn[a]) / cell) + 1.0;
+      if (cnt[0] * cnt[1] * cnt[2] <= 6.4e7)
+        break;
+      cell *= 2.0;
     }
+    for (int a = 0; a < 3; a++)
+      dim[a] = (int64_t) cnt[a];
     int64_t ncell = dim[0] * dim[1] * dim[2];
     start.assign(ncell + 1, 0);
     std::vector<int64_t> key(cl.n);
@@ -166,10 +171,8 @@ struct GridIndex
     int64_t lo[3], hi[3];
     for (int a = 0; a < 3; a++)
     {
-      int64_t l = (int64_t) std::floor(((double) q[a] - radius - mn[a]) / cell) - 1;
-      int64_t h = (int64_t) std::floor(((double) q[a] + radius - mn[a]) / cell) + 1;
-      lo[a] = std::min(std::max(l, (int64_t) 0), dim[a] - 1);
-      hi[a] = std::min(std::max(h, (int64_t) 0), dim[a] - 1);
+      lo[a] = clamp_cell(std::floor(((double) q[a] - radius - mn[a]) / cell) - 1.0, a);
+      hi[a] = clamp_cell(std::floor(((double) q[a] + radius - mn[a]) / cell) + 1.0, a);
     }
     for (int64_t cz = lo[2]; cz <= hi[2]; cz++)
       for (int64_t cy = lo[1]; cy <= hi[1]; cy++)

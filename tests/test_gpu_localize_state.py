@@ -105,6 +105,7 @@ def test_the_calls_allowed_between_begin_and_end(tiny_scene, svm_model, raw, uni
     ctx.synchronize()
     ctx.timing(counts=True)
     ctx.grid_stats()
+    assert ctx.grid_desc()["cell"] > 0
     assert ctx.comm_rank() == (0, 1)
     assert ctx.selftest_math(1 << 10) == binding.AGH_ERR_STATE  # (it launches work on the context: refused)
     _same_chain(ctx.localize_end(), uninterrupted)
