@@ -88,7 +88,7 @@ EXPORTS = [
     "agh_save_svm_file_ex", "agh_comm_unique_id", "agh_comm_init", "agh_comm_init_local", "agh_comm_destroy", "agh_comm_rank", "agh_comm_last_count", "agh_comm_last_exchange", "agh_comm_set_segment_records", "agh_comm_inject_fault",
     "agh_shard_slice", "agh_find_hands_sharded_device", "agh_find_hands_sharded", "agh_classify_sharded_device",
     "agh_classify_sharded", "agh_default_plane_params", "agh_remove_plane", "agh_get_plane_inliers",
-    "agh_get_plane_candidates", "agh_plane_replay",
+    "agh_get_plane_candidates", "agh_plane_replay", "agh_set_cloud_cam_origins", "agh_get_cloud_cam_origins",
 ]
 
 
@@ -314,6 +314,22 @@ class Context:
                                                  _p(off, C.c_int64), C.c_int32(len(clouds))))
         self.n = xyz.shape[0]
         return off
+
+    def set_cloud_cam_origins(self, cam_origins):
+        """agh_set_cloud_cam_origins: an (n_clouds, 2, 3) array of camera origins, row k for cloud k of the batch in place of
+        the context's own; None clears the table.  Sticky until cleared or replaced."""
+        if cam_origins is None:
+            self._check(self.lib.agh_set_cloud_cam_origins(self._h, None, C.c_int32(0)))
+            return
+        tab = np.ascontiguousarray(cam_origins, np.float64)
+        assert tab.ndim == 3 and tab.shape[1:] == (2, 3)
+        self._check(self.lib.agh_set_cloud_cam_origins(self._h, _p(tab, C.c_double), C.c_int32(tab.shape[0])))
+
+    def get_cloud_cam_origins(self):
+        """The table set_cloud_cam_origins holds, (n_clouds, 2, 3) float64, or None."""
+        tab = np.zeros((64, 2, 3), np.float64)
+        k = self._check(self.lib.agh_get_cloud_cam_origins(self._h, _p(tab, C.c_double), C.c_int32(64)))
+        return tab[:k].copy() if k > 0 else None
 
     def set_cloud_batch_torch(self, xyz_t, cam_t, offsets, stream=None):
         assert xyz_t.is_cuda and xyz_t.is_contiguous()

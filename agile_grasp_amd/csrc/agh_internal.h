@@ -324,6 +324,13 @@ struct Ctx
   bool cloud_async = false;     // agh_set_cloud (host buffers) left the grid build running on `stream`; a search on ANOTHER
                                 // stream must first wait for it (order_after_cloud)
 
+  // agh_set_cloud_cam_origins: camera origins per cloud of the bound batch, in place of p.cam_origin (sticky; 0 rows = none)
+  int cam_tab_rows = 0;
+  double* d_cam_tab = nullptr;      // kMaxClouds x 6 doubles
+  double* h_cam_tab = nullptr;      // pinned staging of the upload, and what agh_get_cloud_cam_origins reads
+  hipEvent_t cam_tab_up = nullptr;  // recorded behind the upload on `stream`
+  bool cam_tab_async = false;       // the upload may still be running on `stream`: a search on ANOTHER stream waits for the event
+
   // per-call buffers (sized for s_cap samples)
   int64_t s_cap = 0;
   int32_t* d_samples = nullptr;
@@ -454,6 +461,27 @@ inline bool refuse_mid_chain(Ctx* c, const char* fn)
     return false;
   c->err = std::string(fn) + ": a localize chain is in flight on this context (agh_localize_end first)";
   return true;
+}
+
+// The table K1c and K2 take in place of the context's origins (null: none set).
+inline const double* cloud_cam_table(const Ctx* c) { return c->cam_tab_rows > 0 ? c->d_cam_tab : nullptr; }
+// A call about to use the origins on a batch of n_clouds clouds: a table must have exactly that many rows (include/agh.h).
+inline bool cam_table_mismatch(Ctx* c, const char* fn, int n_clouds)
+{
+  if (c->cam_tab_rows == 0 || c->cam_tab_rows == n_clouds)
+    return false;
+  c->err = std::string(fn) + ": the camera-origin table (agh_set_cloud_cam_origins) holds " + std::to_string(c->cam_tab_rows) +
+           " rows, the batch " + std::to_string(n_clouds) + " clouds; set a table of that many rows or clear it";
+  return true;
+}
+// ... and the upload of the table is in front of that call's kernels: a search on the context's own stream is in order behind
+// it; one on another stream waits for the event ON THE DEVICE (no host stall; a wait on a completed event costs next to nothing).
+// The flag comes down where the host is known to have waited for the context's stream: the next setter, agh_synchronize.
+inline hipError_t order_after_cam_table(Ctx* c, hipStream_t st)
+{
+  if (!c->cam_tab_async || st == c->stream)
+    return hipSuccess;
+  return hipStreamWaitEvent(st, c->cam_tab_up, 0);
 }
 
 // a search about to run on `st`: if the host-buffer agh_set_cloud left its grid build running on the context's stream and `st`

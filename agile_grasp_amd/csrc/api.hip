@@ -535,6 +535,12 @@ void agh_destroy(agh_ctx* ctx)
     (void) hipHostFree(c->h_pin_keep);
   if (c->h_vox_desc)
     (void) hipHostFree(c->h_vox_desc);
+  if (c->d_cam_tab)
+    (void) hipFree(c->d_cam_tab);
+  if (c->h_cam_tab)
+    (void) hipHostFree(c->h_cam_tab);
+  if (c->cam_tab_up)
+    (void) hipEventDestroy(c->cam_tab_up);
   for (hipEvent_t e : c->ev)
     (void) hipEventDestroy(e);
   if (c->copy_done)
@@ -1119,6 +1125,73 @@ int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap)
   return (int) std::min<int64_t>(c->n, 0x7fffffff);
 }
 
+// Camera origins per cloud of a batch (include/agh.h): staged in pinned memory of the context, uploaded on its stream.
+int agh_set_cloud_cam_origins(agh_ctx* ctx, const double* cam_origin, int32_t n_clouds)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_set_cloud_cam_origins"))
+    return AGH_ERR_STATE;
+  if (!cam_origin)  // clear: the kernels take the context's own origins again (nothing to upload)
+  {
+    c->cam_tab_rows = 0;
+    return AGH_OK;
+  }
+  if (n_clouds < 1 || n_clouds > kMaxClouds)
+  {
+    c->err = "agh_set_cloud_cam_origins: need 1 <= n_clouds <= 64";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  for (int k = 0; k < 6 * n_clouds; k++)
+    if (!std::isfinite(cam_origin[k]))
+    {
+      c->err = "agh_set_cloud_cam_origins: a non-finite origin in row " + std::to_string(k / 6);
+      return AGH_ERR_INVALID_ARGUMENT;
+    }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->d_cam_tab)
+  {
+    const int rc = dev_alloc(c, &c->d_cam_tab, (size_t) kMaxClouds * 6);
+    if (rc != AGH_OK)
+      return rc;
+  }
+  if (!c->h_cam_tab)
+    HIPCHK(c, hipHostMalloc((void**) &c->h_cam_tab, sizeof(double) * kMaxClouds * 6));
+  if (!c->cam_tab_up)
+    HIPCHK(c, hipEventCreateWithFlags(&c->cam_tab_up, hipEventDisableTiming));
+  else if (c->cam_tab_async)
+  {
+    HIPCHK(c, hipEventSynchronize(c->cam_tab_up));  // (the previous table's upload may still read the staging)
+    c->cam_tab_async = false;
+  }
+  c->cam_tab_rows = 0;  // (no table until the new one is on its way)
+  std::memcpy(c->h_cam_tab, cam_origin, sizeof(double) * 6 * (size_t) n_clouds);
+  // in order behind every search already queued on the context's stream (they keep the table they were launched with) and in
+  // front of the next one; a search on another stream waits for the event first (order_after_cam_table)
+  HIPCHK(c, hipMemcpyAsync(c->d_cam_tab, c->h_cam_tab, sizeof(double) * 6 * (size_t) n_clouds, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->cam_tab_up, c->stream));
+  c->cam_tab_async = true;
+  c->cam_tab_rows = n_clouds;
+  return AGH_OK;
+}
+
+int agh_get_cloud_cam_origins(agh_ctx* ctx, double* cam_origin_out, int32_t cap_clouds)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;  // (host-side: allowed while a localize chain is in flight)
+  if (c->cam_tab_rows == 0)
+    return 0;
+  if (cap_clouds < c->cam_tab_rows || !cam_origin_out)
+  {
+    c->err = "agh_get_cloud_cam_origins: room for " + std::to_string(c->cam_tab_rows) + " rows is needed";
+    return AGH_ERR_CAPACITY;
+  }
+  std::memcpy(cam_origin_out, c->h_cam_tab, sizeof(double) * 6 * (size_t) c->cam_tab_rows);
+  return c->cam_tab_rows;
+}
+
 int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_samples, int calculates_antipodal,
   agh_hypothesis* d_out, int64_t cap, int64_t* d_n_out, void* hip_stream)
 {
@@ -1137,9 +1210,12 @@ int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_s
     c->err = "agh_find_hands: bad arguments";
     return AGH_ERR_INVALID_ARGUMENT;
   }
+  if (cam_table_mismatch(c, "agh_find_hands", c->n_clouds))
+    return AGH_ERR_INVALID_ARGUMENT;
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t) hip_stream : c->stream;
   HIPCHK(c, order_after_cloud(c, st));
+  HIPCHK(c, order_after_cam_table(c, st));
   const int64_t S = n_samples;
   const int64_t chunk = kNormalsChunk;  // all-points pass batch
   int rc = ensure_call_buffers(c, std::max<int64_t>(S, calculates_antipodal ? std::min<int64_t>(c->n, chunk) : 0));
@@ -1334,6 +1410,8 @@ int agh_find_hands(agh_ctx* ctx, const int32_t* sample_idx, int64_t n_samples, i
       c->err = "agh_find_hands: sample index out of range";
       return AGH_ERR_INVALID_ARGUMENT;
     }
+  if (cam_table_mismatch(c, "agh_find_hands", c->n_clouds))
+    return AGH_ERR_INVALID_ARGUMENT;
   HIPCHK(c, hipSetDevice(c->device));
   // size the buffers for everything the device call will need, so that it does not reallocate d_out_own under us
   int rc = ensure_call_buffers(c, std::max<int64_t>(n_samples, calculates_antipodal ? std::min<int64_t>(c->n, kNormalsChunk) : 0));
@@ -1420,6 +1498,7 @@ int agh_synchronize(agh_ctx* ctx)
   Ctx* c = &ctx->c;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
+  c->cam_tab_async = false;  // (an upload of agh_set_cloud_cam_origins has landed)
   if (c->loc.active)  // (allowed mid-chain: it waits; the chain's flags and counts are agh_localize_end's to read)
     return AGH_OK;
 #ifdef AGH_DEBUG_HOOKS

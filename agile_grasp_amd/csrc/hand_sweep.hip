@@ -179,7 +179,8 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (WG4 ? 4 : AGH_SWEEP_WGS)) void
   const agh_frame* __restrict__ frames, const int32_t* __restrict__ samples, const int32_t* __restrict__ cam_source,
   int S, float r2f, double rpad, const double* __restrict__ normals, double img_cell,
   int32_t* __restrict__ status, agh_hypothesis* __restrict__ slots, uint32_t* __restrict__ images, int debug_stop, long long* __restrict__ dbg,
-  const int* __restrict__ order, uint8_t* __restrict__ vmask, uint32_t* __restrict__ images_cam)
+  const int* __restrict__ order, uint8_t* __restrict__ vmask, uint32_t* __restrict__ images_cam,
+  const double* __restrict__ cam_tab)
 {
   constexpr bool NORMALS = MODE != 0, TRAIN = MODE == 2;
   constexpr int NW = NT / 64, kOW = 8 / NW;  // waves; orientations a wave owns in the finger logic and the results
@@ -222,7 +223,8 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (WG4 ? 4 : AGH_SWEEP_WGS)) void
 #pragma unroll
   for (int k = 0; k < kGeomPer; k++)
     gw[k] = (tid + NT * k) < kGeomWords ? ((const unsigned*) geom_p)[tid + NT * k] : 0u;
-  gv = grid_of_cloud(gv, cloud_of_point(gv, samples[s]));  // the sample's cloud of the batch
+  const int cloud = cloud_of_point(gv, samples[s]);  // the sample's cloud of the batch
+  gv = grid_of_cloud(gv, cloud);
   const GridDesc gd = *gv.desc;
   const int to = tid / 9, tij = tid - 9 * to;  // thread (o, i, j) of the 72 entries of frame_ * rot^T (below)
   const double t_cs = tid < 72 ? geom_p->cos_a[to] : 0.0, t_sn = tid < 72 ? geom_p->sin_a[to] : 0.0;
@@ -242,6 +244,14 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : (WG4 ? 4 : AGH_SWEEP_WGS)) void
   for (int k = 0; k < kGeomPer; k++)
     if ((tid + NT * k) < kGeomWords)
       ((unsigned*) &G)[tid + NT * k] = gw[k];
+  // Per-cloud camera origins (agh_set_cloud_cam_origins; cam_tab is null without a table, uniform across the launch): the
+  // threads that have just staged the words of HandGeom::cam_origin overwrite them with the cloud's row of the table (the same
+  // thread, in program order), so the LDS copy G every later step reads -- the camera-side test of the orientations,
+  // source_to_center of the images -- holds that row.  Nothing of the table-less path's early loads is touched.
+  constexpr int kCamWord = (int) (offsetof(HandGeom, cam_origin) / 4), kCamWords = (int) (sizeof(HandGeom::cam_origin) / 4);
+  static_assert(kCamWord + kCamWords <= NT, "the origins' words are staged by the first pass of the geometry copy");
+  if (cam_tab && tid >= kCamWord && tid < kCamWord + kCamWords)
+    ((unsigned*) &G)[tid] = ((const unsigned*) cam_tab)[kCamWords * cloud + (tid - kCamWord)];
   if (tid == 0)
   {
     cnt_crop = 0;
@@ -1353,7 +1363,7 @@ int hand_sweep(Ctx* c, const int32_t* d_samples, int64_t S, bool use_normals, hi
   const bool timed = timing_launch_events(c, "hand_sweep", &ev_start, &ev_stop);
 #define AGH_SWEEP_ARGS                                                                                                  \
   gv, dg, (const agh_frame*) c->d_frames, d_samples, (const int32_t*) c->d_cam, Si, r2f, rpad, nrm, img_cell, c->d_status, \
-    c->d_slots, c->d_images, c->debug_stop_sweep, sweep_dbg, order, c->d_vmask, c->d_images_cam
+    c->d_slots, c->d_images, c->debug_stop_sweep, sweep_dbg, order, c->d_vmask, c->d_images_cam, cloud_cam_table(c)
 #ifndef AGH_SWEEP_NT
 #define AGH_SWEEP_NT 256  // threads of the online variant's work-groups (512: eight waves, two per CU, one 3712-point tile -- measured, not faster)
 #endif

@@ -319,6 +319,8 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     c->err = "agh_localize: classify needs a loaded SVM (agh_load_svm*)";
     return AGH_ERR_NO_SVM;
   }
+  if (cam_table_mismatch(c, "agh_localize", 1))  // (the chain's cloud is a batch of one; the table stays the context's for the
+    return AGH_ERR_INVALID_ARGUMENT;              // whole chain -- the setter refuses mid-chain -- so its repeats search with it too)
   if (!handle_thresholds(&L.x1, &L.x2))
   {
     c->err = "agh_localize: this libm's acos is not monotone around the 0.34 rad thresholds";

@@ -386,6 +386,8 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
     c->err = "agh_localize_batch: classify needs a loaded SVM (agh_load_svm*)";
     return AGH_ERR_NO_SVM;
   }
+  if (cam_table_mismatch(c, "agh_localize_batch", C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
+    return AGH_ERR_INVALID_ARGUMENT;                    // the table is the context's, so the repeats inside the call search with it too)
   BatchCall B;
   B.C = C;
   if (!handle_thresholds(&B.x1, &B.x2))

@@ -532,8 +532,9 @@ int agh_comm_unique_id(uint8_t id[AGH_COMM_ID_BYTES])
 // What every rank of a communicator must agree on: the parameters that decide WHICH collectives a call issues
 // (normals_mode: the RAND50 draw-count exchange) and what the shared result means (geometry, radii, camera origins, seed).
 // device and profile are per rank.  FNV-1a over the fields' bytes.
-static uint64_t params_fingerprint(const agh_params& p)
+static uint64_t params_fingerprint(const Ctx& ctx)
 {
+  const agh_params& p = ctx.p;
   uint64_t h = 1469598103934665603ull;
   auto eat = [&](const void* v, size_t n) {
     const unsigned char* b = (const unsigned char*) v;
@@ -551,10 +552,17 @@ static uint64_t params_fingerprint(const agh_params& p)
   eat(&p.cam_origin[0][0], sizeof(double) * 6);
   eat(&p.normals_mode, sizeof(p.normals_mode));
   eat(&p.rand_seed, sizeof(p.rand_seed));
+  // ... and the per-cloud origins the context holds when it joins (agh_set_cloud_cam_origins): presence, rows, bytes.  A table set
+  // or changed afterwards is, like the cloud, the caller's to keep equal on every rank.
+  const int32_t rows = ctx.cam_tab_rows;
+  eat(&rows, sizeof(rows));
+  if (rows > 0)
+    eat(ctx.h_cam_tab, sizeof(double) * 6 * (size_t) rows);
   return h;
 }
 static const char* kParamsDiffer = "the contexts of a communicator must be created with the same agh_params (hand geometry, radii, "
-                                   "camera origins, normals_mode, rand_seed): ranks that disagree issue different collectives";
+                                   "camera origins, normals_mode, rand_seed) and hold the same per-cloud origin table, if any: "
+                                   "ranks that disagree issue different collectives";
 
 int agh_comm_init(agh_ctx* ctx, int32_t rank, int32_t n_ranks, const uint8_t id[AGH_COMM_ID_BYTES])
 {
@@ -601,7 +609,7 @@ int agh_comm_init(agh_ctx* ctx, int32_t rank, int32_t n_ranks, const uint8_t id[
       int64_t have = 0;
       rc = grow(c, &c->d_xcnt, &have, kXcntWords);
     }
-    uint64_t mine = params_fingerprint(c->p), all[64];
+    uint64_t mine = params_fingerprint(*c), all[64];
     if (rc == AGH_OK && hipMemcpyAsync(c->d_xcnt + 64 + rank, &mine, sizeof(mine), hipMemcpyHostToDevice, c->stream) != hipSuccess)
       rc = AGH_ERR_HIP;
     if (rc == AGH_OK)
@@ -636,7 +644,7 @@ int agh_comm_init_local(agh_ctx* const* ctxs, int32_t n_ranks)
     if (!ctxs[q] || ctxs[q]->c.comm)
       return AGH_ERR_STATE;
   for (int q = 1; q < n_ranks; q++)
-    if (params_fingerprint(ctxs[q]->c.p) != params_fingerprint(ctxs[0]->c.p))
+    if (params_fingerprint(ctxs[q]->c) != params_fingerprint(ctxs[0]->c))
     {
       for (int k = 0; k < n_ranks; k++)
         ctxs[k]->c.err = kParamsDiffer;
@@ -817,9 +825,13 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
       kHdrRankFailed);
   if (!c->has_cloud)  // a caller's bug on this rank: it takes part like a rank with an empty cloud, and every rank hears of it
     degrade(AGH_ERR_NO_CLOUD, "agh_find_hands_sharded: no cloud set", kHdrRankNoCloud);
+  // a camera-origin table that does not fit this rank's batch: also a caller's bug on this rank, and it takes part without searching
+  if (c->has_cloud && !mid_chain && cam_table_mismatch(c, "agh_find_hands_sharded", c->n_clouds))
+    degrade(AGH_ERR_INVALID_ARGUMENT, c->err, kHdrRankFailed);
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t) hip_stream : c->stream;
   HIPCHK(c, order_after_cloud(c, st));
+  HIPCHK(c, order_after_cam_table(c, st));
   const int G = c->comm->n_ranks, r = c->comm->rank;
   const int64_t S = n_samples;
   const int64_t n_cloud = c->has_cloud && !mid_chain ? c->n : 0;  // (mid-chain, c->n may be a bound of the chain's cloud)

@@ -905,6 +905,29 @@ __device__ __forceinline__ double wave_max_f64_(double v)
   return v;
 }
 
+// s2s = sample - origin of the majority camera (quadric.cpp:294-296), the one origin site of K1c, shared by k_taubin_frame and
+// k_taubin_frame_huge.  The origins are the six scalar arguments or, with a table (agh_set_cloud_cam_origins; cam_tab non-null,
+// uniform across the launch), the row of the sample's cloud, scloud[s].  All six doubles of the row are loaded and the selects
+// stay as they were: selecting the camera first and loading three doubles from row + 3 * maj made the compiler index a stack
+// copy of the arguments (56 bytes of scratch per lane).  Called by the one thread that forms the frame.
+__device__ __forceinline__ void sample_to_source(double (&s2s)[3], const double (&sample)[3], int maj, double cam0x, double cam0y,
+  double cam0z, double cam1x, double cam1y, double cam1z, const double* __restrict__ cam_tab, const int32_t* __restrict__ scloud, int s)
+{
+  if (cam_tab)
+  {
+    const double* row = cam_tab + 6 * (int64_t) scloud[s];
+    cam0x = row[0];
+    cam0y = row[1];
+    cam0z = row[2];
+    cam1x = row[3];
+    cam1y = row[4];
+    cam1z = row[5];
+  }
+  s2s[0] = sample[0] - (maj ? cam1x : cam0x);
+  s2s[1] = sample[1] - (maj ? cam1y : cam0y);
+  s2s[2] = sample[2] - (maj ? cam1z : cam0z);
+}
+
 // THREADS = 256 (one work-group of four waves per sample) or 64 (one wave per sample: the class for at most 128 normals
 // of the r = 0.01 all-points pass).
 template <int CAP, int THREADS>
@@ -914,8 +937,11 @@ __global__ __launch_bounds__(THREADS, (CAP == 1152 && THREADS == 256) ? 5 : ((CA
   const int32_t* __restrict__ draw_ofs, const int32_t* __restrict__ draws, double cam0x, double cam0y, double cam0z,
   double cam1x, double cam1y, double cam1z, agh_frame* __restrict__ frames, double* __restrict__ normals_out, int nmin, int debug_stop,
   const int* __restrict__ order, long long* __restrict__ dbg, const float4* __restrict__ pool_sorted,
-  const long long* __restrict__ huge_base, const int32_t* __restrict__ ovf_list)
+  const long long* __restrict__ huge_base, const int32_t* __restrict__ ovf_list, const double* __restrict__ cam_tab,
+  const int32_t* __restrict__ scloud)
 {
+  // (cam_tab: agh_set_cloud_cam_origins' table, 2 x 3 doubles per cloud of the batch, or null: the six cam arguments.  With a table
+  // the sample's row -- scloud[s], which K1a wrote -- stands in for them, read once by the one thread that forms the frame.)
   // (ovf_list: the 4096 class walks the list of the samples beyond 1152 neighbours that k_taubin_moments<1152> made, a few hundred
   // work-groups instead of one per sample -- see there)
 #ifdef AGH_DEBUG_HOOKS  // scripts/frame_clocks.py: per-work-group phase timestamps (AGH_DEBUG_CLOCKS_KERNEL=frame)
@@ -1494,8 +1520,8 @@ __global__ __launch_bounds__(THREADS, (CAP == 1152 && THREADS == 256) ? 5 : ((CA
       axis[0] * normal[1] - axis[1] * normal[0] };  // quadric.cpp:291
     const int maj = (camcnt[1] > ks - camcnt[1]) ? 1 : 0;  // camera 1's count against camera 0's
     const double sample[3] = { (double) qp[0], (double) qp[1], (double) qp[2] };
-    const double s2s[3] = { sample[0] - (maj ? cam1x : cam0x), sample[1] - (maj ? cam1y : cam0y),
-      sample[2] - (maj ? cam1z : cam0z) };
+    double s2s[3];
+    sample_to_source(s2s, sample, maj, cam0x, cam0y, cam0z, cam1x, cam1y, cam1z, cam_tab, scloud, s);
     if ((normal[0] * s2s[0] + normal[1] * s2s[1]) + normal[2] * s2s[2] > 0)
       for (int r = 0; r < 3; r++)
         normal[r] *= -1.0;
@@ -1555,7 +1581,7 @@ __global__ __launch_bounds__(256) void k_taubin_frame_huge(const float4* __restr
   const long long* __restrict__ huge_base, const int32_t* __restrict__ nt, const double* __restrict__ eig,
   const int32_t* __restrict__ status, const float* __restrict__ xyz, int64_t stride, const int32_t* __restrict__ samples, int S,
   double cam0x, double cam0y, double cam0z, double cam1x, double cam1y, double cam1z, agh_frame* __restrict__ frames,
-  double* __restrict__ normals_out)
+  double* __restrict__ normals_out, const double* __restrict__ cam_tab, const int32_t* __restrict__ scloud)
 {
   __shared__ int camcnt1, next_col;
   __shared__ double sM3[6], sAxis[3];
@@ -1716,8 +1742,8 @@ __global__ __launch_bounds__(256) void k_taubin_frame_huge(const float4* __restr
       axis[0] * normal[1] - axis[1] * normal[0] };  // quadric.cpp:291
     const int maj = (camcnt1 > n - camcnt1) ? 1 : 0;  // camera 1's count against camera 0's
     const double sample[3] = { (double) qp[0], (double) qp[1], (double) qp[2] };
-    const double s2s[3] = { sample[0] - (maj ? cam1x : cam0x), sample[1] - (maj ? cam1y : cam0y),
-      sample[2] - (maj ? cam1z : cam0z) };
+    double s2s[3];
+    sample_to_source(s2s, sample, maj, cam0x, cam0y, cam0z, cam1x, cam1y, cam1z, cam_tab, scloud, s);
     if ((normal[0] * s2s[0] + normal[1] * s2s[1]) + normal[2] * s2s[2] > 0)
       for (int r = 0; r < 3; r++)
         normal[r] *= -1.0;
@@ -1866,6 +1892,12 @@ int taubin_frame_stage(Ctx* c, const int32_t* d_samples, int64_t S, double radiu
   if (rand_mode && !draw_offsets_done)
     hipLaunchKernelGGL(k_draw_offsets, dim3(1), dim3(64), 0, st, d_nt, Si, c->d_draw_ofs, c->d_flags + 2);
   const double* co = &c->p.cam_origin[0][0];
+  // per-cloud origins (agh_set_cloud_cam_origins), or null: co.  INVARIANT: with a table K1c finds a sample's row through
+  // c->d_scloud[s], which the first-class K1a launch of taubin_moments_eigen wrote for THIS launch set -- the same d_samples base
+  // and the same S (taubin_frames, normals_pass' chunks, the sharded search's my_idx / Sr all call the two stages as a pair).  A
+  // caller that ran K1c on another list than the preceding K1a would read other samples' clouds (K2 does not depend on this: it
+  // recomputes cloud_of_point itself).
+  const double* cam_tab = cloud_cam_table(c);
   // capacity classes (LDS = 24 B per normal) by the number of normals a sample needs: at most 128 (typical of the
   // r = 0.01 all-points pass) -> one wave per sample; voxelised clouds at r = 0.03 fit the 1280 class (4 blocks per CU); the 4096 class only does work for the
   // samples that need it
@@ -1886,7 +1918,7 @@ int taubin_frame_stage(Ctx* c, const int32_t* d_samples, int64_t S, double radiu
     c->d_eig, c->d_status, c->d_xyz, c->stride_floats, d_samples, Si, rand_mode, c->d_draw_ofs, c->d_draws, co[0], co[1], \
     co[2], co[3], co[4], co[5], d_frames, write_normals ? c->d_normals : nullptr, NMIN, c->debug_stop_frame,           \
     frame_order, frame_dbg, (const float4*) c->d_huge_sorted,                                                          \
-    (const long long*) (c->huge_classes ? c->d_huge_base : nullptr), LIST)
+    (const long long*) (c->huge_classes ? c->d_huge_base : nullptr), LIST, cam_tab, (const int32_t*) c->d_scloud)
   if (small_class)
     AGH_LAUNCH_FRAME(128, 64, 0);
   if (rand_mode && !small_class)
@@ -1913,7 +1945,8 @@ int taubin_frame_stage(Ctx* c, const int32_t* d_samples, int64_t S, double radiu
       // ... and what is beyond that, from the pool (all but the pooled samples return at once)
       hipLaunchKernelGGL(k_taubin_frame_huge, dim3(Si), dim3(256), 0, st, (const float4*) c->d_huge_sorted, c->d_huge_normals,
         (const long long*) c->d_huge_base, (const int32_t*) d_nt, (const double*) c->d_eig, (const int32_t*) c->d_status, c->d_xyz,
-        c->stride_floats, d_samples, Si, co[0], co[1], co[2], co[3], co[4], co[5], d_frames, write_normals ? c->d_normals : nullptr);
+        c->stride_floats, d_samples, Si, co[0], co[1], co[2], co[3], co[4], co[5], d_frames, write_normals ? c->d_normals : nullptr,
+        cam_tab, (const int32_t*) c->d_scloud);
     }
   }
 #undef AGH_LAUNCH_FRAME

@@ -147,12 +147,36 @@ int agh_set_cloud_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes,
  * points of its own cloud; point and sample indices of all later calls are positions in the common array.  One
  * agh_find_hands* call then searches samples of ALL clouds in one launch set -- thousands of independent work-groups more
  * per kernel, which is what fills the GPU when a single cloud's 2000 samples do not -- and agh_hypothesis::sample is the
- * position in that call's sample list, as always.  All clouds share the context's camera origins and hand geometry.
- * agh_set_cloud* is the batch of one. */
+ * position in that call's sample list, as always.  All clouds share the context's hand geometry; each may have its own camera
+ * origins (agh_set_cloud_cam_origins below; without it, the context's).  agh_set_cloud* is the batch of one. */
 int agh_set_cloud_batch(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, const int32_t* cam_source, const int64_t* offsets,
   int32_t n_clouds);
 int agh_set_cloud_batch_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, const int32_t* d_cam_source,
   const int64_t* offsets, int32_t n_clouds, void* hip_stream);
+
+/* Camera origins per cloud of a batch (two sensor pairs in one cell, two capture sessions in one directory -- the reference sets
+ * up one Localization per rig with setCameraTransforms): row k (2 x 3 doubles, as agh_params::cam_origin) is used for every sample
+ * and point of cloud k in place of the context's own origins -- the sign of the Taubin normals and the majority-camera vector, the
+ * camera-side test of the hand orientations, and source_to_center of every occupancy image (the classifier's and the three
+ * training images).  cam_origin == NULL (n_clouds ignored) clears the table.  1 <= n_clouds <= 64; a non-finite entry is
+ * AGH_ERR_INVALID_ARGUMENT.
+ * The table belongs to the context and is sticky: it survives new clouds and new batches until it is cleared or replaced.  The
+ * caller's buffer has been read when the call returns (it is staged in pinned memory of the context); the upload is queued on the
+ * context's stream, in front of whatever searches next -- a search on another stream waits for it first; searches of the previous
+ * table that still run on another stream must have finished, as before a new cloud.
+ * The table is checked against the bound batch at the calls that use the origins -- agh_find_hands*, agh_find_hands_sharded*,
+ * agh_localize* (a batch of one: one row) and agh_localize_batch* (capture k = cloud k: n_captures rows): if the batch does not have
+ * exactly the table's number of clouds, the call returns AGH_ERR_INVALID_ARGUMENT, the error text names both counts, and nothing is
+ * launched (a sharded call stays collective: the rank takes part without searching and every rank returns an error).  A table of
+ * one row on a single cloud is legal and gives exactly the results of a context created with those origins.  With no table every
+ * result and every launch is what it is without this call.  Between agh_localize_begin and _end the setter returns AGH_ERR_STATE;
+ * the chain and its in-call repeats search with the table that was set when it began.  The ranks of a communicator must hold the
+ * same table (the parameter check of agh_comm_init* covers the one held then).
+ * Hand geometry stays per context: per-cloud geometry would need per-cloud finger tables and is not offered.
+ * agh_get_cloud_cam_origins copies the table held (host-side, allowed mid-chain) and returns its rows, 0 = none; AGH_ERR_CAPACITY
+ * if cap_clouds is smaller. */
+int agh_set_cloud_cam_origins(agh_ctx* ctx, const double* cam_origin, int32_t n_clouds);
+int agh_get_cloud_cam_origins(agh_ctx* ctx, double* cam_origin_out, int32_t cap_clouds);
 
 /* The head of Localization::localizeHands (localization.cpp:17-45) on the GPU, followed by the grid build: camera id of
  * raw point i = (i >= size_left); removal of points with a non-finite coordinate (skipped when dense != 0, like
@@ -249,17 +273,18 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  *                                         beside cloud k's kernels (a pageable source: the call lasts as long as the copy)
  *   agh_localize_end(ctx, outputs)        the one synchronisation; cloud k's results, exactly agh_localize's
  *   agh_localize_begin(ctx, cloud k + 1)  recognises the staged capture (same pointer, stride and count): no upload
- * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a
- * begin).  Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_end,
- * agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error, agh_destroy, the host-side
- * counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats, agh_get_grid_desc) and the communicator's bookkeeping (agh_comm_rank,
- * agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault, agh_comm_set_segment_records, agh_comm_last_*) may be called on
- * the context.  Every other call on it returns AGH_ERR_STATE without touching anything: agh_set_cloud*, agh_preprocess*,
- * agh_find_hands*, agh_classify*, agh_find_handles, agh_localize*, agh_remove_plane, agh_get_cloud and every getter of device
- * results (frames, normals, neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*,
- * the training calls (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and
- * agh_selftest_math.  The sharded calls are collective and do not return early: on such a context they take part without
- * searching, and every rank of the call returns an error (this one AGH_ERR_STATE); the chain is not disturbed.
+ * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a begin).
+ * Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_end,
+ * agh_get_cloud_cam_origins, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
+ * agh_destroy, the host-side counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats, agh_get_grid_desc) and the
+ * communicator's bookkeeping (agh_comm_rank, agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault,
+ * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
+ * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
+ * agh_find_handles, agh_localize*, agh_remove_plane, agh_get_cloud and every getter of device results (frames, normals,
+ * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
+ * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
+ * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
+ * the call returns an error (this one AGH_ERR_STATE); the chain is not disturbed.
  * The capture handed to begin must stay valid
  * and unchanged until the agh_localize_end of its chain has returned, the one handed to stage until the agh_localize_end of the
  * chain that adopts it has (a pageable source has been read when agh_localize_stage returns; a pinned one is read asynchronously);
@@ -274,9 +299,10 @@ int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, 
  * directory of PCD pairs, a cell with several sensors or arms): 1 <= n_captures <= 64, fewer than 2^30 raw points in all.
  * Capture k is xyz[k] (stride_bytes[k], n[k] points) with its own record lp[k]: size_left, dense, workspace, sample_idx /
  * n_samples / sample_seed are per capture; classify, cell_size, min_inliers, min_length and filters_boundaries must be equal
- * across the batch (AGH_ERR_INVALID_ARGUMENT otherwise).  Camera origins and hand geometry are the context's, as for
- * agh_set_cloud_batch.  The voxelised captures lie end to end in one cloud batch (capture k = cloud k), are searched in one
- * launch set, classified together, and their kept hands go through the handle search side by side, one list per capture.
+ * across the batch (AGH_ERR_INVALID_ARGUMENT otherwise).  Hand geometry is the context's; camera origins are the context's, or
+ * per capture with agh_set_cloud_cam_origins (row k = capture k's rig).  The voxelised captures lie end to end in one cloud
+ * batch (capture k = cloud k), are searched in one launch set, classified together, and their kept hands go through the handle
+ * search side by side, one list per capture.
  * Capture k's results equal what agh_localize returns for capture k alone on the same samples, bit for bit: n_voxels,
  * n_hypotheses, every field of every hand record but epoch (one call stamps one epoch), every handle field and the inlier
  * lists.  agh_hypothesis::sample is the position in capture k's own sample list, samples_out holds capture-local voxel indices

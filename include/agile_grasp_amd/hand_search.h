@@ -451,6 +451,38 @@ public:
     return true;
   }
 
+  /** Additional: camera origins per cloud of a batch (agh_set_cloud_cam_origins): row k = the translations of cams_left[k] /
+   *  cams_right[k], as setCamTfLeft / setCamTfRight take them for the whole context.  Sticky until clearCloudCamOrigins.
+   *  @return false (after printing) on error */
+  bool setCloudCamOrigins(const std::vector<Matrix4d>& cams_left, const std::vector<Matrix4d>& cams_right)
+  {
+    if (cams_left.empty() || cams_left.size() != cams_right.size())
+    {
+      std::cout << " Error: setCloudCamOrigins needs one left and one right transform per cloud\n";
+      return false;
+    }
+    if (!ensureContext())
+      return false;
+    std::vector<double> tab(cams_left.size() * 6);
+    for (std::size_t k = 0; k < cams_left.size(); k++)
+      for (int r = 0; r < 3; r++)
+      {
+        tab[k * 6 + (std::size_t) r] = mat4(cams_left[k], r, 3);
+        tab[k * 6 + 3 + (std::size_t) r] = mat4(cams_right[k], r, 3);
+      }
+    if (agh_set_cloud_cam_origins(ctx_, tab.data(), (std::int32_t) cams_left.size()) != AGH_OK)
+    {
+      fail("agh_set_cloud_cam_origins");
+      return false;
+    }
+    return true;
+  }
+  void clearCloudCamOrigins()
+  {
+    if (ctx_)
+      (void) agh_set_cloud_cam_origins(ctx_, nullptr, 0);
+  }
+
   /** agh_localize_stage: the NEXT capture up, beside the chain in flight (keep `next` alive and unchanged until the
    *  localizeEnd of the chain that searches it has returned). */
   bool localizeStage(const PointCloud::Ptr& next)

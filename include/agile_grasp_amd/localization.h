@@ -356,6 +356,39 @@ public:
     return out;
   }
 
+  /** Additional: the same for captures of SEVERAL rigs -- capture k was taken with the camera transforms cams_left[k] /
+   *  cams_right[k] (translations only, as setCameraTransforms).  Sets the per-cloud origin table (agh_set_cloud_cam_origins),
+   *  runs the batch and clears the table: per capture the same handles as localizeHandles of a Localization set up with that
+   *  capture's transforms.  Hand geometry stays this object's.  The table is cleared afterwards in any case: one set before
+   *  through HandSearch::setCloudCamOrigins is replaced by this call's and is NOT restored. */
+  std::vector<std::vector<Handle> > localizeHandlesBatch(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<std::vector<int> >& indices_per_cloud, const std::string& svm_filename, int min_inliers, double min_length,
+    const std::vector<Matrix4d>& cams_left, const std::vector<Matrix4d>& cams_right,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_cloud = nullptr, const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (cams_left.size() != clouds.size() || cams_right.size() != clouds.size())
+    {
+      std::cout << " Error: localizeHandlesBatch needs one left and one right camera transform per cloud\n";
+      if (antipodal_hands_per_cloud)
+        antipodal_hands_per_cloud->assign(clouds.size(), std::vector<GraspHypothesis>());
+      return std::vector<std::vector<Handle> >(clouds.size());
+    }
+    if (pending_cloud_)  // (the plain overload prints the error and returns the empty lists; a chain in flight keeps the table it has)
+      return localizeHandlesBatch(clouds, sizes_left, indices_per_cloud, svm_filename, min_inliers, min_length, antipodal_hands_per_cloud,
+        workspaces);
+    ensureSearch();
+    if (!search_->setCloudCamOrigins(cams_left, cams_right))
+    {
+      if (antipodal_hands_per_cloud)
+        antipodal_hands_per_cloud->assign(clouds.size(), std::vector<GraspHypothesis>());
+      return std::vector<std::vector<Handle> >(clouds.size());
+    }
+    const std::vector<std::vector<Handle> > out = localizeHandlesBatch(clouds, sizes_left, indices_per_cloud, svm_filename,
+      min_inliers, min_length, antipodal_hands_per_cloud, workspaces);
+    search_->clearCloudCamOrigins();
+    return out;
+  }
+
   /** the searched hands, handles and inlier lists of one capture as the reference's objects (the tail of localizeHandlesEnd) */
   std::vector<Handle> toHandles(const PointCloud::Ptr& cloud_in, const std::vector<agh_hypothesis>& hands,
     const std::vector<agh_handle>& handles, const std::vector<std::int32_t>& idx, std::vector<GraspHypothesis>* antipodal_hands)

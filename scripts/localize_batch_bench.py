@@ -5,6 +5,10 @@ samples, classifier on), batches of 1 / 4 / 8.  Medians over --reps calls, ms PE
   sequential      agh_localize on each capture of the batch, one after the other, on one context
   two_contexts    the same captures on two contexts taking turns: agh_localize_begin(k + 1) on the other context before
                   agh_localize_end(k) (the two chains' kernels side by side) -- what a caller could do before the batch
+--mixed-origins: eight captures under FOUR origin pairs (captures 2j, 2j + 1 under pair j), ms per capture:
+  mixed_batch_host    one agh_localize_batch with the per-cloud origin table (agh_set_cloud_cam_origins)
+  mixed_four_contexts the same captures through four contexts, one per origin pair, agh_localize one after the other
+  shared_batch_host   the batch without a table (what the table costs)
 One JSON line; the GPU and the way it was run go in with --note.  scripts/localize_batch_trace.sh takes the kernel trace."""
 import argparse
 import json
@@ -31,13 +35,52 @@ def median_ms(fn, reps, warmup=3):
     return float(np.median(t))
 
 
+def mixed_origins(a):
+    caps = [synthetic.make_raw_cloud(700_000, 21 + k) for k in range(8)]
+    z = np.load(os.path.join(ROOT, "tests", "golden", "svm_weights.npz"))
+    base = np.asarray(caps[0].cam_origins, np.float64)
+    pairs = [base + np.array([0.0, 0.15 * j, 0.05 * j]) for j in range(4)]  # four rigs side by side
+    tab = np.stack([pairs[k // 2] for k in range(8)])
+    ctxs = [binding.Context(p) for p in pairs]
+    for c in ctxs:
+        c.load_svm(z["w"], float(z["rho"]))
+    kw = dict(classify=True, min_inliers=3, min_length=0.005)
+    sl, ws, seeds = [c.size_left for c in caps], [c.workspace for c in caps], [5 + k for k in range(8)]
+    batch = lambda: ctxs[0].localize_batch([c.xyz for c in caps], sl, ws, n_samples=2000, sample_seeds=seeds, **kw)
+    shared = median_ms(batch, a.reps)
+    ctxs[0].set_cloud_cam_origins(tab)
+    mixed = median_ms(batch, a.reps)
+    got = batch()
+    ctxs[0].set_cloud_cam_origins(None)
+
+    def four():
+        return [ctxs[k // 2].localize(c.xyz, c.size_left, c.workspace, n_samples=2000, sample_seed=seeds[k], **kw)
+                for k, c in enumerate(caps)]
+
+    per = median_ms(four, a.reps)
+    def equal(g, r):  # every field of every hand but the call's stamp, every handle field, the inlier lists and the counts
+        return (g["n_voxels"] == r["n_voxels"] and g["n_hypotheses"] == r["n_hypotheses"] and len(g["hands"]) == len(r["hands"]) and
+                all(np.array_equal(g["hands"][f], r["hands"][f]) for f in g["hands"].dtype.names if f != "epoch") and
+                len(g["handles"]) == len(r["handles"]) and
+                all(np.array_equal(g["handles"][f], r["handles"][f]) for f in g["handles"].dtype.names) and
+                np.array_equal(g["inlier_idx"], r["inlier_idx"]) and np.array_equal(g["samples"], r["samples"]))
+
+    same = all(equal(g, r) for g, r in zip(got, four()))
+    print(json.dumps({"points": 700_000, "samples": 2000, "reps": a.reps, "note": a.note, "captures": 8, "origin_pairs": 4,
+                      "mixed_batch_host_ms": round(mixed / 8, 4), "mixed_four_contexts_ms": round(per / 8, 4),
+                      "shared_batch_host_ms": round(shared / 8, 4), "results_equal": bool(same)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--batches", default="1,4,8")
     ap.add_argument("--note", default="")
     ap.add_argument("--batch-only", action="store_true", help="the batch calls alone (for a kernel trace)")
+    ap.add_argument("--mixed-origins", action="store_true", help="eight captures under four origin pairs: table batch against four contexts")
     a = ap.parse_args()
+    if a.mixed_origins:
+        return mixed_origins(a)
     import torch
 
     sizes = [int(b) for b in a.batches.split(",")]
