@@ -80,7 +80,8 @@ assert HYP_DTYPE.itemsize == 160 and FRAME_DTYPE.itemsize == 200 and HANDLE_DTYP
 
 EXPORTS = [
     "agh_default_params", "agh_create", "agh_destroy", "agh_last_error", "agh_set_cloud", "agh_set_cloud_device", "agh_set_cloud_batch", "agh_set_cloud_batch_device",
-    "agh_preprocess", "agh_preprocess_device", "agh_localize", "agh_localize_device", "agh_localize_begin", "agh_localize_stage", "agh_localize_end", "agh_localize_batch", "agh_localize_batch_device", "agh_get_cloud", "agh_find_handles", "agh_find_hands", "agh_find_hands_device", "agh_load_svm", "agh_load_svm_file", "agh_classify",
+    "agh_preprocess", "agh_preprocess_device", "agh_localize", "agh_localize_device", "agh_localize_begin", "agh_localize_stage", "agh_localize_end", "agh_localize_batch", "agh_localize_batch_device", "agh_localize_batch_begin", "agh_localize_batch_begin_device",
+    "agh_localize_batch_stage", "agh_localize_batch_end", "agh_get_cloud", "agh_find_handles", "agh_find_hands", "agh_find_hands_device", "agh_load_svm", "agh_load_svm_file", "agh_classify",
     "agh_classify_device", "agh_get_frames", "agh_get_neighbor_counts", "agh_get_images", "agh_get_hog",
     "agh_get_normals", "agh_get_timing", "agh_get_timing_counts", "agh_get_grid_stats", "agh_get_grid_desc", "agh_set_profile", "agh_synchronize", "agh_selftest_math",
     "agh_set_training_images", "agh_get_training_images", "agh_hog_images", "agh_train_svm", "agh_save_svm_file",
@@ -440,6 +441,15 @@ class Context:
         n_samples (an int for all, or a list), sample_seeds, dense (a bool for all, or a list).  caps: (handle_cap, idx_cap,
         hands_cap) of the output buffers (default: large enough).  Returns a list of the dicts localize() returns, one per
         capture; after an AghError, self.last_batch_counts holds the per-capture counts the library reported."""
+        a = self._batch_args(captures, sizes_left, workspaces, samples, n_samples, sample_seeds, classify, min_inliers,
+                             min_length, filters_boundaries, cell_size, dense)
+        fn = self.lib.agh_localize_batch_device if a["on_device"] else self.lib.agh_localize_batch
+        return self._batch_collect(a, caps, lambda *out: fn(self._h, a["ptrs"], a["strides"], a["ns"], a["lps"],
+                                                            C.c_int32(a["Ck"]), *out))
+
+    def _batch_args(self, captures, sizes_left, workspaces, samples, n_samples, sample_seeds, classify, min_inliers, min_length,
+                    filters_boundaries, cell_size, dense):
+        """The C arrays of a batch call: pointers, strides, counts and agh_localize_params records, and what keeps them alive."""
         Ck = len(captures)
         per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * Ck
         sizes_left, dense_l, seeds = per(sizes_left), per(dense), per(1 if sample_seeds is None else sample_seeds)
@@ -448,18 +458,10 @@ class Context:
         ws_a = np.asarray(workspaces, np.float64)
         ws_l = list(ws_a) if ws_a.ndim == 2 else [ws_a] * Ck
         on_device = Ck > 0 and hasattr(captures[0], "is_cuda") and captures[0].is_cuda
-        keep, ptrs, strides, ns = [], (C.c_void_p * max(Ck, 1))(), (C.c_int64 * max(Ck, 1))(), (C.c_int64 * max(Ck, 1))()
+        keep, ptrs, strides, ns = self._capture_arrays(captures, on_device)
         lps = (AghLocalizeParams * max(Ck, 1))()
-        S_list = []
-        for k, xyz in enumerate(captures):
-            if on_device:
-                assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] >= 3 and xyz.stride(1) == 1
-                ptrs[k], ns[k], strides[k] = xyz.data_ptr(), int(xyz.shape[0]), int(xyz.stride(0)) * 4
-            else:
-                xyz = np.ascontiguousarray(xyz, np.float32)
-                assert xyz.ndim == 2 and xyz.shape[1] >= 3
-                ptrs[k], ns[k], strides[k] = xyz.ctypes.data, xyz.shape[0], xyz.shape[1] * 4
-            keep.append(xyz)
+        S_list, sample_arrays = [], []
+        for k in range(Ck):
             lp = lps[k]
             lp.size_left, lp.dense, lp.classify = int(sizes_left[k]), 1 if dense_l[k] else 0, 1 if classify else 0
             ws = np.ascontiguousarray(ws_l[k], np.float64)
@@ -469,7 +471,7 @@ class Context:
             lp.cell_size = cell_size
             if samples_l[k] is not None:
                 s = np.ascontiguousarray(samples_l[k], np.int32)
-                keep.append(s)
+                sample_arrays.append(s)
                 lp.sample_idx = s.ctypes.data_as(C.POINTER(C.c_int32))
                 S = s.shape[0]
             else:
@@ -478,14 +480,34 @@ class Context:
             S_list.append(S)
             lp.n_samples, lp.sample_seed, lp.min_inliers, lp.min_length = S, int(seeds[k]), min_inliers, min_length
             lp.filters_boundaries = int(filters_boundaries)
+        return {"Ck": Ck, "on_device": on_device, "keep": keep, "sample_arrays": sample_arrays, "ptrs": ptrs, "strides": strides,
+                "ns": ns, "lps": lps, "S_list": S_list}
+
+    @staticmethod
+    def _capture_arrays(captures, on_device):
+        Ck = len(captures)
+        keep, ptrs, strides, ns = [], (C.c_void_p * max(Ck, 1))(), (C.c_int64 * max(Ck, 1))(), (C.c_int64 * max(Ck, 1))()
+        for k, xyz in enumerate(captures):
+            if on_device:
+                assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] >= 3 and xyz.stride(1) == 1
+                ptrs[k], ns[k], strides[k] = xyz.data_ptr(), int(xyz.shape[0]), int(xyz.stride(0)) * 4
+            else:
+                xyz = np.ascontiguousarray(xyz, np.float32)
+                assert xyz.ndim == 2 and xyz.shape[1] >= 3
+                ptrs[k], ns[k], strides[k] = xyz.ctypes.data, xyz.shape[0], xyz.shape[1] * 4
+            keep.append(xyz)
+        return keep, ptrs, strides, ns
+
+    def _batch_collect(self, a, caps, call):
+        """Output buffers for the batch `a`, the collecting call, and its results as a list of dicts."""
+        Ck, S_list = a["Ck"], a["S_list"]
         hcap = max(sum(min(8 * S, 8192) for S in S_list), 1)
         hc, ic, kc = caps if caps is not None else (hcap, hcap, hcap)
         handles, idx, hands = np.zeros(max(hc, 1), HANDLE_DTYPE), np.zeros(max(ic, 1), np.int32), np.zeros(max(kc, 1), HYP_DTYPE)
         sout = np.zeros(max(sum(S_list), 1), np.int32)
         res = (AghLocalizeBatchResult * max(Ck, 1))()
-        fn = self.lib.agh_localize_batch_device if on_device else self.lib.agh_localize_batch
-        rc = fn(self._h, ptrs, strides, ns, lps, C.c_int32(Ck), handles.ctypes.data_as(C.c_void_p), C.c_int64(hc),
-                _p(idx, C.c_int32), C.c_int64(ic), hands.ctypes.data_as(C.c_void_p), C.c_int64(kc), _p(sout, C.c_int32), res)
+        rc = call(handles.ctypes.data_as(C.c_void_p), C.c_int64(hc), _p(idx, C.c_int32), C.c_int64(ic),
+                  hands.ctypes.data_as(C.c_void_p), C.c_int64(kc), _p(sout, C.c_int32), res)
         self.last_batch_counts = [
             {"n_voxels": r.r.n_voxels, "n_hypotheses": r.r.n_hypotheses, "n_hands": r.r.n_hands, "n_handles": r.r.n_handles,
              "n_inlier_idx": r.r.n_inlier_idx, "first_handle": r.first_handle, "first_inlier_idx": r.first_inlier_idx,
@@ -502,6 +524,42 @@ class Context:
         self.last_samples = sum(S_list)
         self.last_n = sum(int(r.r.n_hypotheses) for r in res[:Ck])
         return out
+
+    def localize_batch_begin(self, captures, sizes_left, workspaces, samples=None, n_samples=0, sample_seeds=None,
+                             classify: bool = True, min_inliers: int = 3, min_length: float = 0.005, filters_boundaries=0,
+                             cell_size: float = 0.003, dense=False):
+        """agh_localize_batch_begin (torch CUDA tensors: _begin_device): the batch's chain queued, nothing waited for; arguments
+        as for localize_batch.  The captures are kept alive until localize_batch_end; the argument arrays the library copies
+        (self._batch_pending: ptrs, strides, ns, lps, sample_arrays) are kept too, although it no longer needs them."""
+        a = self._batch_args(captures, sizes_left, workspaces, samples, n_samples, sample_seeds, classify, min_inliers,
+                             min_length, filters_boundaries, cell_size, dense)
+        fn = self.lib.agh_localize_batch_begin_device if a["on_device"] else self.lib.agh_localize_batch_begin
+        self._check(fn(self._h, a["ptrs"], a["strides"], a["ns"], a["lps"], C.c_int32(a["Ck"])))
+        self._batch_pending = a
+
+    def localize_batch_stage(self, captures):
+        """agh_localize_batch_stage: the NEXT batch's host captures up on a second stream, beside the chain in flight.  Returns
+        the list of arrays to hand to the next localize_batch_begin (the library recognises the set by pointers, strides and
+        counts); they are kept alive until a later stage call replaces them."""
+        keep, ptrs, strides, ns = self._capture_arrays(captures, False)
+        self._batch_stage_keep = (keep, ptrs, strides, ns)
+        self._check(self.lib.agh_localize_batch_stage(self._h, ptrs, strides, ns, C.c_int32(len(keep))))
+        return keep
+
+    def localize_batch_end(self, caps=None):
+        """agh_localize_batch_end: the one synchronisation and the results of the batch localize_batch_begin queued, as
+        localize_batch returns them (caps and last_batch_counts likewise)."""
+        a = getattr(self, "_batch_pending", None)
+        self._batch_pending = None
+        if a is None:
+            # No localize_batch_begin of this object is pending: the library says so (AGH_ERR_STATE).  Should a chain be in flight
+            # all the same (begun through the raw library), it is ended with room for the records of any batch and for no
+            # output -- the library writes results[k] for up to 64 captures and skips a NULL samples_out.
+            res = (AghLocalizeBatchResult * 64)()
+            self._check(self.lib.agh_localize_batch_end(self._h, None, C.c_int64(0), None, C.c_int64(0), None, C.c_int64(0),
+                                                        None, res))
+            return []
+        return self._batch_collect(a, caps, lambda *out: self.lib.agh_localize_batch_end(self._h, *out))
 
     def localize_begin(self, xyz, size_left: int, workspace, **kw):
         """agh_localize_begin: the chain of this capture queued, nothing waited for (see include/agh.h)."""

@@ -211,6 +211,11 @@ struct LocalizeState
   bool staged = false;        // agh_localize_stage: a capture is (being) copied into d_stage_xyz
   const float* staged_src = nullptr;
   int64_t staged_stride = 0, staged_n = 0;
+  // agh_localize_batch_begin / _stage / _end (localize_batch.hip) share the one chain and the one staged set of the context
+  bool batch = false;         // the chain in flight is a batch's (agh_localize_batch_end collects it, not agh_localize_end)
+  int staged_captures = 0;    // staged: 0 = one capture of agh_localize_stage; C = the C captures of agh_localize_batch_stage,
+  std::vector<const float*> staged_batch_src;             // packed end to end in d_stage_xyz, with these sources
+  std::vector<int64_t> staged_batch_stride, staged_batch_n;
 };
 
 struct PlaneState;
@@ -270,6 +275,8 @@ struct Ctx
   int64_t stage_cap = 0;           // floats
   hipStream_t stage_stream = nullptr;
   hipEvent_t stage_done = nullptr;
+  hipEvent_t raw_read = nullptr, stage_read = nullptr;  // recorded on `stream` behind the last batch chain that read d_raw_xyz /
+  bool raw_read_set = false, stage_read_set = false;    // d_stage_xyz (they change places with the buffers)
   LocalizeState loc;
   int64_t raw_cap = 0;             // floats
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
@@ -461,6 +468,41 @@ inline bool refuse_mid_chain(Ctx* c, const char* fn)
     return false;
   c->err = std::string(fn) + ": a localize chain is in flight on this context (agh_localize_end first)";
   return true;
+}
+
+// The stage stream and its events, made by the first agh_localize_stage / agh_localize_batch_stage of a context.
+inline int ensure_stage_stream(Ctx* c, const char* fn)
+{
+  if (c->stage_stream)
+    return AGH_OK;
+  hipStream_t s = nullptr;
+  hipEvent_t e[3] = { nullptr, nullptr, nullptr };
+  bool ok = hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
+  for (int k = 0; k < 3 && ok; k++)
+    ok = hipEventCreateWithFlags(&e[k], hipEventDisableTiming) == hipSuccess;
+  if (!ok)
+  {
+    for (hipEvent_t q : e)
+      if (q)
+        (void) hipEventDestroy(q);
+    if (s)
+      (void) hipStreamDestroy(s);
+    c->err = std::string(fn) + ": no stream or event";
+    return AGH_ERR_HIP;
+  }
+  c->stage_stream = s;
+  c->stage_done = e[0];
+  c->raw_read = e[1];
+  c->stage_read = e[2];
+  return AGH_OK;
+}
+// A staged capture (or batch) is adopted: the two raw buffers change places, and so do the events behind their last readers.
+inline void swap_raw_buffers(Ctx* c)
+{
+  std::swap(c->d_raw_xyz, c->d_stage_xyz);
+  std::swap(c->raw_cap, c->stage_cap);
+  std::swap(c->raw_read, c->stage_read);
+  std::swap(c->raw_read_set, c->stage_read_set);
 }
 
 // The table K1c and K2 take in place of the context's origins (null: none set).

@@ -514,6 +514,8 @@ void agh_destroy(agh_ctx* ctx)
   (void) hipSetDevice(c->device);
   if (c->stream)
     (void) hipStreamSynchronize(c->stream);
+  if (c->stage_stream)  // (a staged capture's copy may still be running)
+    (void) hipStreamSynchronize(c->stage_stream);
   comm_release(c);
   plane_release(c);
   localize_batch_release(c);
@@ -553,6 +555,10 @@ void agh_destroy(agh_ctx* ctx)
     (void) hipStreamDestroy(c->copy_stream);
   if (c->stage_done)
     (void) hipEventDestroy(c->stage_done);
+  if (c->raw_read)
+    (void) hipEventDestroy(c->raw_read);
+  if (c->stage_read)
+    (void) hipEventDestroy(c->stage_read);
   if (c->stage_stream)
     (void) hipStreamDestroy(c->stage_stream);
   if (c->stream)

@@ -171,6 +171,11 @@ int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, 
     c->err = "agh_localize_end: no agh_localize_begin in flight";
     return AGH_ERR_STATE;
   }
+  if (c->loc.batch)
+  {
+    c->err = "agh_localize_end: the chain in flight is a batch's (agh_localize_batch_end collects it)";
+    return AGH_ERR_STATE;
+  }
   const int rc = localize_check_outputs(c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
   if (rc != AGH_OK)
   {
@@ -204,18 +209,25 @@ int agh_localize_stage(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int
     return AGH_ERR_INVALID_ARGUMENT;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  c->loc.staged = false;
-  if (!c->stage_stream)
-  {
-    HIPCHK(c, hipStreamCreateWithFlags(&c->stage_stream, hipStreamNonBlocking));
-    if (hipEventCreateWithFlags(&c->stage_done, hipEventDisableTiming) != hipSuccess)
-    {
-      (void) hipStreamDestroy(c->stage_stream);
-      c->stage_stream = nullptr;
-      c->err = "agh_localize_stage: no event";
-      return AGH_ERR_HIP;
-    }
-  }
+  if (int rc = ensure_stage_stream(c, "agh_localize_stage"))
+    return rc;
+  // A failure from here on leaves nothing staged -- and an earlier capture's copy may still be reading its (pinned) source, with no
+  // begin left to wait for stage_done: the stage stream is drained before the flag comes down.
+  auto stage_fail = [&](int code) {
+    (void) hipStreamSynchronize(c->stage_stream);
+    c->loc.staged = false;
+    return code;
+  };
+#define STAGE_HIPCHK(expr)                                                \
+  do                                                                      \
+  {                                                                       \
+    hipError_t e__ = (expr);                                              \
+    if (e__ != hipSuccess)                                                \
+    {                                                                     \
+      c->err = std::string(#expr) + ": " + hipGetErrorString(e__);        \
+      return stage_fail(AGH_ERR_HIP);                                     \
+    }                                                                     \
+  } while (0)
   const bool as_is = stride_bytes <= 32;
   const int64_t dev_stride = as_is ? stride_bytes : 12;
   const int64_t need = n * (dev_stride / 4);
@@ -224,18 +236,23 @@ int agh_localize_stage(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int
     // (nobody reads this buffer now: the chain in flight reads d_raw_xyz)
     int rc;
     if ((rc = dev_alloc(c, &c->d_stage_xyz, (size_t) std::max<int64_t>(need, 1))))
-      return rc;
+      return stage_fail(rc);
     c->stage_cap = need;
+    c->stage_read_set = false;
   }
+  if (c->stage_read_set)  // the last batch chain that read the buffer this copy overwrites (it has ended: see DESIGN.md)
+    STAGE_HIPCHK(hipStreamWaitEvent(c->stage_stream, c->stage_read, 0));
   if (n > 0)
   {
     if (as_is)
-      HIPCHK(c, hipMemcpyAsync(c->d_stage_xyz, xyz, (size_t) (n * stride_bytes - (stride_bytes - 12)), hipMemcpyHostToDevice, c->stage_stream));
+      STAGE_HIPCHK(hipMemcpyAsync(c->d_stage_xyz, xyz, (size_t) (n * stride_bytes - (stride_bytes - 12)), hipMemcpyHostToDevice, c->stage_stream));
     else
-      HIPCHK(c, hipMemcpy2DAsync(c->d_stage_xyz, 12, xyz, (size_t) stride_bytes, 12, (size_t) n, hipMemcpyHostToDevice, c->stage_stream));
+      STAGE_HIPCHK(hipMemcpy2DAsync(c->d_stage_xyz, 12, xyz, (size_t) stride_bytes, 12, (size_t) n, hipMemcpyHostToDevice, c->stage_stream));
   }
-  HIPCHK(c, hipEventRecord(c->stage_done, c->stage_stream));
+  STAGE_HIPCHK(hipEventRecord(c->stage_done, c->stage_stream));
+#undef STAGE_HIPCHK
   c->loc.staged = true;
+  c->loc.staged_captures = 0;
   c->loc.staged_src = xyz;
   c->loc.staged_stride = stride_bytes;
   c->loc.staged_n = n;
@@ -338,11 +355,10 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   const float* d_raw = xyz;
   if (!xyz_on_device)
   {
-    if (L.staged && L.staged_src == xyz && L.staged_stride == stride_bytes && L.staged_n == n && c->d_stage_xyz)
+    if (L.staged && L.staged_captures == 0 && L.staged_src == xyz && L.staged_stride == stride_bytes && L.staged_n == n && c->d_stage_xyz)
     {
       // the capture is (or is about to be) in the second raw buffer: the two buffers change places, the chain waits for the copy
-      std::swap(c->d_raw_xyz, c->d_stage_xyz);
-      std::swap(c->raw_cap, c->stage_cap);
+      swap_raw_buffers(c);
       L.staged = false;
       HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
     }

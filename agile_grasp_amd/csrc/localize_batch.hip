@@ -36,8 +36,22 @@ struct BatchCapture
 };
 constexpr int kBatchCountsStride = 8;  // ints of host-side counts per capture (as agh_localize's [0..6])
 
+// one batch, from agh_localize_batch_begin to agh_localize_batch_end: the caller's arrays are copied (explicit sample lists into
+// the pinned h_samples, where lp[k].sample_idx then points), the captures themselves are read where d_raw says
+struct BatchCall
+{
+  int C = 0;
+  std::vector<const float*> d_raw;
+  std::vector<int64_t> dev_stride, n, soff, raw_off;  // raw_off: each capture's first point among all the batch's
+  std::vector<agh_localize_params> lp;
+  int64_t S_tot = 0, n_tot = 0, slot = 0;
+  bool classify = false, filters = false, with_sequential = false;
+  double x1 = 0.0, x2 = 0.0;
+};
+
 struct LocalizeBatchState
 {
+  BatchCall call;                 // the batch in flight (loc.active && loc.batch), or the last one
   BatchCapture* d_tab = nullptr;  // kMaxClouds
   BatchCapture* h_tab = nullptr;  // pinned
   int32_t* d_local = nullptr;     // explicit sample lists, capture-local (s_cap entries)
@@ -281,17 +295,6 @@ int ensure_vox_slots(Ctx* c, LocalizeBatchState* b, int C)
   return AGH_OK;
 }
 
-struct BatchCall
-{
-  int C = 0;
-  std::vector<const float*> d_raw;
-  std::vector<int64_t> dev_stride, n, soff, raw_off;  // raw_off: each capture's first point among all the batch's
-  std::vector<agh_localize_params> lp;
-  int64_t S_tot = 0, slot = 0;
-  bool classify = false, filters = false, with_sequential = false;
-  double x1 = 0.0, x2 = 0.0;
-};
-
 // search -> classification -> per-capture compaction -> handle search, queued (handles_only: the handle search once more)
 int batch_queue(agh_ctx* ctx, BatchCall& B, bool handles_only)
 {
@@ -331,37 +334,254 @@ int batch_queue(agh_ctx* ctx, BatchCall& B, bool handles_only)
 }
 }  // namespace
 
-extern "C" {
-
-static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
-  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
-  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+namespace
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
+void drop_bound_cloud(Ctx* c)
+{
+  if (c->n_is_bound)
+  {
+    c->n_is_bound = false;
+    c->has_cloud = false;
+    c->n = 0;
+    c->cloud_off_on_device = false;
+  }
+}
+// an error between the launches and the synchronisation: the stream is drained (a pinned source may still be in flight, the caller
+// may free it as soon as the call returns), and the context must not be left believing the bound is the cloud
+int batch_fail(Ctx* c, int code)
+{
+  (void) hipStreamSynchronize(c->stream);
+  drop_bound_cloud(c);
+  return code;
+}
+#define LB_HIPCHK(expr)                                                   \
+  do                                                                      \
+  {                                                                       \
+    hipError_t e__ = (expr);                                              \
+    if (e__ != hipSuccess)                                                \
+    {                                                                     \
+      c->err = std::string(#expr) + ": " + hipGetErrorString(e__);        \
+      return batch_fail(c, AGH_ERR_HIP);                                  \
+    }                                                                     \
+  } while (0)
+
+struct ActiveGuard
+{
+  Ctx* c;
+  explicit ActiveGuard(Ctx* c_) : c(c_) { c->batch_active = true; }
+  ~ActiveGuard() { c->batch_active = false; }
+};
+
+bool bad_outputs(const agh_handle* handles_out, int64_t handle_cap, const int32_t* inlier_idx_out, int64_t idx_cap,
+  const agh_hypothesis* hands_out, int64_t hands_cap)
+{
+  return handle_cap < 0 || idx_cap < 0 || hands_cap < 0 || (handle_cap > 0 && !handles_out) || (idx_cap > 0 && !inlier_idx_out) ||
+         (hands_cap > 0 && !hands_out);
+}
+bool bad_capture(const float* xyz, int64_t stride_bytes, int64_t n)
+{
+  return n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz);
+}
+const char* const kBadArguments = "agh_localize_batch: bad arguments (1 <= n_captures <= 64; see include/agh.h)";
+
+// Steps 2 to 5 of the batch c->lbatch->call, queued on the context's stream: preprocessing, the batch of clouds, the sample list,
+// search -> classification -> kept hands per capture -> handle search.  Nothing waits, except the first batch of a context (or one
+// after the kept slots were dropped): one synchronisation for the lattice sizes.  An error has drained the stream (batch_fail).
+int batch_pass(agh_ctx* ctx)
+{
   Ctx* c = &ctx->c;
-  const int C = n_captures;
-  if (results && C >= 1 && C <= kMaxClouds)
+  LocalizeBatchState* b = c->lbatch;
+  BatchCall& B = b->call;
+  hipStream_t st = c->stream;
+  const int C = B.C;
+  const int64_t n_tot = B.n_tot, S_tot = B.S_tot;
+  const std::vector<int64_t>& n = B.n;
+  std::vector<agh_localize_params>& lp = B.lp;
+  const double cell = lp[0].cell_size;
+  int rc;
+  // ---- 2. preprocessing: one launch per stage for the whole batch, capture = blockIdx.y, each with its own descriptor and
+  // bitmap slot; the voxels of all captures go to one array at the device-side cloud offsets ----
+  if (n_tot > c->vox_cap || !c->d_vox_code)
+  {
+    if ((rc = dev_alloc(c, &c->d_vox_code, (size_t) n_tot)) || (rc = dev_alloc(c, &c->d_vox_blk, (size_t) n_tot / 1024 + 2)) ||
+        (rc = dev_alloc(c, &c->d_vox_xyz, (size_t) n_tot * 3)) || (rc = dev_alloc(c, &c->d_vox_cam, (size_t) n_tot)))
+      return batch_fail(c, rc);
+    c->vox_cap = n_tot;
+  }
+  int64_t nb_max = 0, n_max = 0, blk_tot = 0;
+  bool any_scan = false;
+  for (int k = 0; k < C; k++)
+  {
+    VoxCapture& q = b->h_vcap[k];
+    q.xyz = B.d_raw[k];
+    q.stride = B.dev_stride[k] / 4;
+    q.n = n[k];
+    q.size_left = lp[k].size_left;
+    for (int a = 0; a < 3; a++)
+    {
+      q.ws.lo[a] = lp[k].workspace[2 * a];
+      q.ws.hi[a] = lp[k].workspace[2 * a + 1];
+    }
+    q.blk_off = blk_tot;
+    q.code_off = B.raw_off[k];
+    q.dense = lp[k].dense ? 1 : 0;
+    q.pad = 0;
+    const int64_t nb = (n[k] + 1023) / 1024;
+    blk_tot += nb;
+    nb_max = std::max(nb_max, nb);
+    n_max = std::max(n_max, n[k]);
+    any_scan |= n[k] > 0 && !lp[k].dense;
+  }
+  if (blk_tot + 1 > b->blk_cap || !b->d_blk)
+  {
+    if ((rc = dev_alloc(c, &b->d_blk, (size_t) blk_tot + 1)))
+      return batch_fail(c, rc);
+    b->blk_cap = blk_tot + 1;
+  }
+  LB_HIPCHK(hipMemcpyAsync(b->d_vcap, b->h_vcap, sizeof(VoxCapture) * (size_t) C, hipMemcpyHostToDevice, st));
+  VoxBatch vb;
+  vb.cap = b->d_vcap;
+  vb.desc = b->d_vdesc;
+  vb.host_desc = b->h_desc;
+  // (slots kept from much larger lattices are dropped: every capture would clear and count all of its slot)
+  if (b->d_bitmap && b->last_words > 0 && b->slot_words > 8 * b->last_words + (1 << 20))
+    b->slot_words = 0;
+  if (b->slot_words <= 0)
+  {
+    // the first batch of a context: the lattices' sizes (one synchronisation) decide the slots
+    if ((rc = vox_batch(vb, C, nb_max, n_max, any_scan, cell, true, nullptr, b->d_blk, nullptr, c->d_vox_code, nullptr, nullptr,
+           nullptr, st)) != AGH_OK)
+    {
+      c->err = "preprocessing launch failed";
+      return batch_fail(c, rc);
+    }
+    LB_HIPCHK(hipStreamSynchronize(st));
+    int64_t words = 0;
     for (int k = 0; k < C; k++)
-      results[k] = agh_localize_batch_result{ { 0, 0, 0, 0, 0 }, 0, 0, 0, 0 };
-  if (c->loc.active)
+    {
+      if (b->h_desc[k].error)
+      {
+        c->err = "agh_localize_batch: capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
+                 "(1 GiB bitmap): set a workspace that bounds the scene";
+        return batch_fail(c, AGH_ERR_CAPACITY);
+      }
+      words = std::max<int64_t>(words, (int64_t) b->h_desc[k].n_words);
+    }
+    b->slot_words = std::min<int64_t>(((words + words / 4) / 4096 + 1) * 4096, (int64_t) kVoxMaxWords);
+  }
+  if ((rc = ensure_vox_slots(c, b, C)) != AGH_OK)
+    return batch_fail(c, rc);
+  vb.slot_words = b->slot_words;
+  timing_begin(c, st);
+  if ((rc = vox_batch(vb, C, nb_max, n_max, any_scan, cell, false, b->d_bitmap, b->d_blk, b->d_blk2, c->d_vox_code, c->d_vox_xyz,
+         c->d_vox_cam, c->d_cloud_off, st)) != AGH_OK)
+  {
+    c->err = "preprocessing launch failed";
+    return batch_fail(c, rc);
+  }
+  timing_mark(c, "preprocess", st);
+  c->cloud_async = false;
+  // ---- 3. the batch of clouds: a grid build sized from the raw counts (bounds of the voxel counts, which stay on the device) ----
+  {
+    std::vector<int64_t> bound(C + 1, 0);
+    for (int k = 0; k < C; k++)
+      bound[k + 1] = bound[k] + n[k];
+    c->defer_cloud_count = true;
+    rc = agh_set_cloud_batch_device(ctx, c->d_vox_xyz, 12, c->d_vox_cam, bound.data(), C, nullptr);
+    c->defer_cloud_count = false;
+    if (rc != AGH_OK)
+      return batch_fail(c, rc);
+  }
+  // ---- 4. buffers for the bounds, the capture table and the sample list ----
+  if ((rc = ensure_call_buffers(c, std::max<int64_t>(S_tot, 1))) != AGH_OK)
+    return batch_fail(c, rc);
+  if (S_tot > c->idx_cap || !c->d_idx_own)
+  {
+    if ((rc = dev_alloc(c, &c->d_idx_own, (size_t) std::max<int64_t>(S_tot, 1024))))
+      return batch_fail(c, rc);
+    c->idx_cap = std::max<int64_t>(S_tot, 1024);
+  }
+  if (S_tot > b->s_cap || !b->h_samples)
+  {
+    const int64_t cap = std::max<int64_t>(S_tot, 1024);
+    if ((rc = dev_alloc(c, &b->d_local, (size_t) cap)) || (rc = pinned_alloc(c, &b->h_samples, (size_t) cap)))
+      return batch_fail(c, rc);
+    b->s_cap = cap;
+  }
+  if ((rc = ensure_batch_slots(c, b, C, B.slot)) != AGH_OK)
+    return batch_fail(c, rc);
+  if (B.classify && c->s_cap * 8 > c->keep_cap)
+  {
+    if (c->d_keep)
+      (void) hipFree(c->d_keep);
+    if (c->d_svm_sums)
+      (void) hipFree(c->d_svm_sums);
+    c->d_keep = nullptr;
+    c->d_svm_sums = nullptr;
+    c->keep_cap = 0;
+    LB_HIPCHK(hipMalloc((void**) &c->d_keep, (size_t) (c->s_cap * 8)));
+    LB_HIPCHK(hipMalloc((void**) &c->d_svm_sums, (size_t) (c->s_cap * 8) * sizeof(double)));
+    c->keep_cap = c->s_cap * 8;
+  }
+  bool any_explicit = false;
+  for (int k = 0; k < C; k++)
+  {
+    BatchCapture& t = b->h_tab[k];
+    t.soff = B.soff[k];
+    t.S = (int32_t) lp[k].n_samples;
+    t.drawn = lp[k].sample_idx ? 0 : 1;
+    t.seed = lp[k].sample_seed;
+    for (int q = 0; q < 6; q++)
+      t.ws[q] = lp[k].workspace[q];
+    b->h_bad[k] = 0;
+    if (lp[k].sample_idx && lp[k].n_samples > 0)
+    {
+      any_explicit = true;
+      // (the caller's list is copied once: from here on the record names the pinned copy, which a repeat of the batch reads)
+      if (lp[k].sample_idx != b->h_samples + B.soff[k])
+        std::memcpy(b->h_samples + B.soff[k], lp[k].sample_idx, sizeof(int32_t) * (size_t) lp[k].n_samples);
+      lp[k].sample_idx = b->h_samples + B.soff[k];
+    }
+  }
+  LB_HIPCHK(hipMemcpyAsync(b->d_tab, b->h_tab, sizeof(BatchCapture) * (size_t) C, hipMemcpyHostToDevice, st));
+  if (any_explicit)
+    LB_HIPCHK(hipMemcpyAsync(b->d_local, b->h_samples, sizeof(int32_t) * (size_t) S_tot, hipMemcpyHostToDevice, st));
+  if (S_tot > 0)
+  {
+    hipLaunchKernelGGL(k_batch_samples, dim3((unsigned) ((S_tot + 255) / 256)), dim3(256), 0, st, (const BatchCapture*) b->d_tab, C,
+      S_tot, (const int*) c->d_cloud_off, (const int32_t*) b->d_local, c->d_idx_own, b->h_samples, b->h_bad);
+    LB_HIPCHK(hipGetLastError());
+  }
+  // ---- 5. search -> classification -> kept hands per capture -> handle search ----
+  if ((rc = batch_queue(ctx, B, false)) != AGH_OK)
+    return batch_fail(c, rc);
+  return AGH_OK;
+}
+
+// agh_localize_batch_begin: the arguments checked and copied, the captures up (or adopted from agh_localize_batch_stage, or read in
+// place), steps 2 to 5 queued.
+int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures)
+{
+  Ctx* c = &ctx->c;
+  LocalizeState& L = c->loc;
+  const int C = n_captures;
+  if (L.active)
   {
     c->err = "agh_localize_batch: a localize chain is in flight on this context (agh_localize_end first)";
     return AGH_ERR_STATE;
   }
-  if (C < 1 || C > kMaxClouds || !xyz || !stride_bytes || !n || !lp || handle_cap < 0 || idx_cap < 0 || hands_cap < 0 ||
-      (handle_cap > 0 && !handles_out) || (idx_cap > 0 && !inlier_idx_out) || (hands_cap > 0 && !hands_out))
+  if (C < 1 || C > kMaxClouds || !xyz || !stride_bytes || !n || !lp)
   {
-    c->err = "agh_localize_batch: bad arguments (1 <= n_captures <= 64; see include/agh.h)";
+    c->err = kBadArguments;
     return AGH_ERR_INVALID_ARGUMENT;
   }
   int64_t n_tot = 0, S_tot = 0;
   for (int k = 0; k < C; k++)
   {
     const agh_localize_params& p = lp[k];
-    if (n[k] < 0 || n[k] >= (1ll << 30) || stride_bytes[k] < 12 || (stride_bytes[k] % 4) != 0 || (n[k] > 0 && !xyz[k]) ||
-        !(p.cell_size > 0.0) || p.size_left < 0 || p.n_samples < 0 || p.n_samples > (1 << 24) || p.min_inliers < 1 ||
-        (p.filters_boundaries != 0 && p.filters_boundaries != 1))
+    if (bad_capture(xyz[k], stride_bytes[k], n[k]) || !(p.cell_size > 0.0) || p.size_left < 0 || p.n_samples < 0 ||
+        p.n_samples > (1 << 24) || p.min_inliers < 1 || (p.filters_boundaries != 0 && p.filters_boundaries != 1))
     {
       c->err = "agh_localize_batch: bad arguments for capture " + std::to_string(k) + " (see include/agh.h)";
       return AGH_ERR_INVALID_ARGUMENT;
@@ -387,10 +607,10 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
     return AGH_ERR_NO_SVM;
   }
   if (cam_table_mismatch(c, "agh_localize_batch", C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
-    return AGH_ERR_INVALID_ARGUMENT;                    // the table is the context's, so the repeats inside the call search with it too)
-  BatchCall B;
-  B.C = C;
-  if (!handle_thresholds(&B.x1, &B.x2))
+    return AGH_ERR_INVALID_ARGUMENT;                    // the table stays the context's until agh_localize_batch_end: the setter
+                                                        // refuses mid-chain, so the repeats search with it too)
+  double x1 = 0.0, x2 = 0.0;
+  if (!handle_thresholds(&x1, &x2))
   {
     c->err = "agh_localize_batch: this libm's acos is not monotone around the 0.34 rad thresholds";
     return AGH_ERR_INVALID_ARGUMENT;
@@ -413,6 +633,11 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
     }
   }
   LocalizeBatchState* b = c->lbatch;
+  BatchCall& B = b->call;
+  B = BatchCall();
+  B.C = C;
+  B.x1 = x1;
+  B.x2 = x2;
   // ---- 1. the raw captures: packed end to end into the context's raw buffer, or read in place ----
   B.d_raw.resize(C);
   B.dev_stride.resize(C);
@@ -426,6 +651,7 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
   for (int k = 0; k < C; k++)
     B.soff[k + 1] = B.soff[k] + lp[k].n_samples;
   B.S_tot = S_tot;
+  B.n_tot = n_tot;
   B.classify = lp[0].classify != 0;
   B.filters = lp[0].filters_boundaries != 0;
   int64_t slot = 0;
@@ -440,17 +666,24 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
     }
   else
   {
-    // (a staged capture of agh_localize_stage is dropped: its copy may still read the caller's source -- wait for it)
-    if (c->loc.staged)
-      HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
-    c->loc.staged = false;
     int64_t need = 0;
     for (int k = 0; k < C; k++)
     {
       B.dev_stride[k] = stride_bytes[k] <= 32 ? stride_bytes[k] : 12;  // (as agh_preprocess)
       need += n[k] * (B.dev_stride[k] / 4);
     }
-    if (need > c->raw_cap || !c->d_raw_xyz)
+    bool adopt = L.staged && L.staged_captures == C && c->d_stage_xyz;
+    for (int k = 0; k < C && adopt; k++)
+      adopt = L.staged_batch_src[k] == xyz[k] && L.staged_batch_stride[k] == stride_bytes[k] && L.staged_batch_n[k] == n[k];
+    // A staged batch that is this one: it is (or is about to be) in the second raw buffer -- the two buffers change places and the
+    // chain waits for the copies.  Anything else that is staged (another batch, a capture of agh_localize_stage) is dropped: its
+    // copy may still read the caller's source, so the chain waits for it too and agh_localize_batch_end's synchronisation covers it.
+    if (L.staged)
+      HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
+    L.staged = false;
+    if (adopt)
+      swap_raw_buffers(c);
+    else if (need > c->raw_cap || !c->d_raw_xyz)
     {
       if ((rc = dev_alloc(c, &c->d_raw_xyz, (size_t) need)))
         return rc;
@@ -460,7 +693,7 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
     for (int k = 0; k < C; k++)
     {
       float* dst = c->d_raw_xyz + off;
-      if (n[k] > 0)
+      if (n[k] > 0 && !adopt)
       {
         if (B.dev_stride[k] == stride_bytes[k])
           HIPCHK(c, hipMemcpyAsync(dst, xyz[k], (size_t) (n[k] * stride_bytes[k] - (stride_bytes[k] - 12)), hipMemcpyHostToDevice, st));
@@ -471,195 +704,42 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
       off += n[k] * (B.dev_stride[k] / 4);
     }
   }
-  c->batch_active = true;
-  struct ActiveGuard
+  ActiveGuard guard(c);
+  if ((rc = batch_pass(ctx)) != AGH_OK)
+    return rc;
+  // (the next agh_localize_batch_stage into this raw buffer -- after it has changed places -- waits for this chain's reads)
+  if (!on_device && c->raw_read)
   {
-    Ctx* c;
-    ~ActiveGuard() { c->batch_active = false; }
-  } guard{ c };
-  auto drop_bound_cloud = [&]() {
-    if (c->n_is_bound)
-    {
-      c->n_is_bound = false;
-      c->has_cloud = false;
-      c->n = 0;
-      c->cloud_off_on_device = false;
-    }
-  };
-  auto fail = [&](int code) {
-    (void) hipStreamSynchronize(st);
-    drop_bound_cloud();
-    return code;
-  };
-#define LB_HIPCHK(expr)                                                   \
-  do                                                                      \
-  {                                                                       \
-    hipError_t e__ = (expr);                                              \
-    if (e__ != hipSuccess)                                                \
-    {                                                                     \
-      c->err = std::string(#expr) + ": " + hipGetErrorString(e__);        \
-      return fail(AGH_ERR_HIP);                                           \
-    }                                                                     \
-  } while (0)
-  const double cell = lp[0].cell_size;
+    LB_HIPCHK(hipEventRecord(c->raw_read, st));
+    c->raw_read_set = true;
+  }
+  L.active = true;
+  L.batch = true;
+  return AGH_OK;
+}
+
+// agh_localize_batch_end: the one synchronisation and everything behind it -- the outgrown-bitmap repeat, the capacity-class
+// repeat, the sequential-handle-walk repeat, the copy-out.  The chain is over whatever this returns.
+int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  Ctx* c = &ctx->c;
+  LocalizeBatchState* b = c->lbatch;
+  BatchCall& B = b->call;
+  hipStream_t st = c->stream;
+  const int C = B.C;
+  const int64_t S_tot = B.S_tot;
+  c->loc.active = false;
+  c->loc.batch = false;
+  ActiveGuard guard(c);
+  int rc;
   for (int pass = 0;; pass++)
   {
-    // ---- 2. preprocessing: one launch per stage for the whole batch, capture = blockIdx.y, each with its own descriptor and
-    // bitmap slot; the voxels of all captures go to one array at the device-side cloud offsets ----
-    if (n_tot > c->vox_cap || !c->d_vox_code)
-    {
-      if ((rc = dev_alloc(c, &c->d_vox_code, (size_t) n_tot)) || (rc = dev_alloc(c, &c->d_vox_blk, (size_t) n_tot / 1024 + 2)) ||
-          (rc = dev_alloc(c, &c->d_vox_xyz, (size_t) n_tot * 3)) || (rc = dev_alloc(c, &c->d_vox_cam, (size_t) n_tot)))
-        return fail(rc);
-      c->vox_cap = n_tot;
-    }
-    int64_t nb_max = 0, n_max = 0, blk_tot = 0;
-    bool any_scan = false;
-    for (int k = 0; k < C; k++)
-    {
-      VoxCapture& q = b->h_vcap[k];
-      q.xyz = B.d_raw[k];
-      q.stride = B.dev_stride[k] / 4;
-      q.n = n[k];
-      q.size_left = lp[k].size_left;
-      for (int a = 0; a < 3; a++)
-      {
-        q.ws.lo[a] = lp[k].workspace[2 * a];
-        q.ws.hi[a] = lp[k].workspace[2 * a + 1];
-      }
-      q.blk_off = blk_tot;
-      q.code_off = B.raw_off[k];
-      q.dense = lp[k].dense ? 1 : 0;
-      q.pad = 0;
-      const int64_t nb = (n[k] + 1023) / 1024;
-      blk_tot += nb;
-      nb_max = std::max(nb_max, nb);
-      n_max = std::max(n_max, n[k]);
-      any_scan |= n[k] > 0 && !lp[k].dense;
-    }
-    if (blk_tot + 1 > b->blk_cap || !b->d_blk)
-    {
-      if ((rc = dev_alloc(c, &b->d_blk, (size_t) blk_tot + 1)))
-        return fail(rc);
-      b->blk_cap = blk_tot + 1;
-    }
-    LB_HIPCHK(hipMemcpyAsync(b->d_vcap, b->h_vcap, sizeof(VoxCapture) * (size_t) C, hipMemcpyHostToDevice, st));
-    VoxBatch vb;
-    vb.cap = b->d_vcap;
-    vb.desc = b->d_vdesc;
-    vb.host_desc = b->h_desc;
-    // (slots kept from much larger lattices are dropped: every capture would clear and count all of its slot)
-    if (b->d_bitmap && b->last_words > 0 && b->slot_words > 8 * b->last_words + (1 << 20))
-      b->slot_words = 0;
-    if (b->slot_words <= 0)
-    {
-      // the first batch of a context: the lattices' sizes (one synchronisation) decide the slots
-      if ((rc = vox_batch(vb, C, nb_max, n_max, any_scan, cell, true, nullptr, b->d_blk, nullptr, c->d_vox_code, nullptr, nullptr,
-             nullptr, st)) != AGH_OK)
-      {
-        c->err = "preprocessing launch failed";
-        return fail(rc);
-      }
-      LB_HIPCHK(hipStreamSynchronize(st));
-      int64_t words = 0;
-      for (int k = 0; k < C; k++)
-      {
-        if (b->h_desc[k].error)
-        {
-          c->err = "agh_localize_batch: capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
-                   "(1 GiB bitmap): set a workspace that bounds the scene";
-          return fail(AGH_ERR_CAPACITY);
-        }
-        words = std::max<int64_t>(words, (int64_t) b->h_desc[k].n_words);
-      }
-      b->slot_words = std::min<int64_t>(((words + words / 4) / 4096 + 1) * 4096, (int64_t) kVoxMaxWords);
-    }
-    if ((rc = ensure_vox_slots(c, b, C)) != AGH_OK)
-      return fail(rc);
-    vb.slot_words = b->slot_words;
-    timing_begin(c, st);
-    if ((rc = vox_batch(vb, C, nb_max, n_max, any_scan, cell, false, b->d_bitmap, b->d_blk, b->d_blk2, c->d_vox_code, c->d_vox_xyz,
-           c->d_vox_cam, c->d_cloud_off, st)) != AGH_OK)
-    {
-      c->err = "preprocessing launch failed";
-      return fail(rc);
-    }
-    timing_mark(c, "preprocess", st);
-    c->cloud_async = false;
-    // ---- 3. the batch of clouds: a grid build sized from the raw counts (bounds of the voxel counts, which stay on the device) ----
-    {
-      std::vector<int64_t> bound(C + 1, 0);
-      for (int k = 0; k < C; k++)
-        bound[k + 1] = bound[k] + n[k];
-      c->defer_cloud_count = true;
-      rc = agh_set_cloud_batch_device(ctx, c->d_vox_xyz, 12, c->d_vox_cam, bound.data(), C, nullptr);
-      c->defer_cloud_count = false;
-      if (rc != AGH_OK)
-        return fail(rc);
-    }
-    // ---- 4. buffers for the bounds, the capture table and the sample list ----
-    if ((rc = ensure_call_buffers(c, std::max<int64_t>(S_tot, 1))) != AGH_OK)
-      return fail(rc);
-    if (S_tot > c->idx_cap || !c->d_idx_own)
-    {
-      if ((rc = dev_alloc(c, &c->d_idx_own, (size_t) std::max<int64_t>(S_tot, 1024))))
-        return fail(rc);
-      c->idx_cap = std::max<int64_t>(S_tot, 1024);
-    }
-    if (S_tot > b->s_cap || !b->h_samples)
-    {
-      const int64_t cap = std::max<int64_t>(S_tot, 1024);
-      if ((rc = dev_alloc(c, &b->d_local, (size_t) cap)) || (rc = pinned_alloc(c, &b->h_samples, (size_t) cap)))
-        return fail(rc);
-      b->s_cap = cap;
-    }
-    if ((rc = ensure_batch_slots(c, b, C, slot)) != AGH_OK)
-      return fail(rc);
-    if (B.classify && c->s_cap * 8 > c->keep_cap)
-    {
-      if (c->d_keep)
-        (void) hipFree(c->d_keep);
-      if (c->d_svm_sums)
-        (void) hipFree(c->d_svm_sums);
-      c->d_keep = nullptr;
-      c->d_svm_sums = nullptr;
-      c->keep_cap = 0;
-      LB_HIPCHK(hipMalloc((void**) &c->d_keep, (size_t) (c->s_cap * 8)));
-      LB_HIPCHK(hipMalloc((void**) &c->d_svm_sums, (size_t) (c->s_cap * 8) * sizeof(double)));
-      c->keep_cap = c->s_cap * 8;
-    }
-    bool any_explicit = false;
-    for (int k = 0; k < C; k++)
-    {
-      BatchCapture& t = b->h_tab[k];
-      t.soff = B.soff[k];
-      t.S = (int32_t) lp[k].n_samples;
-      t.drawn = lp[k].sample_idx ? 0 : 1;
-      t.seed = lp[k].sample_seed;
-      for (int q = 0; q < 6; q++)
-        t.ws[q] = lp[k].workspace[q];
-      b->h_bad[k] = 0;
-      if (lp[k].sample_idx && lp[k].n_samples > 0)
-      {
-        any_explicit = true;
-        if (lp[k].sample_idx != b->h_samples + B.soff[k])  // (the repeat of step 6 hands the pinned copy back in)
-          std::memcpy(b->h_samples + B.soff[k], lp[k].sample_idx, sizeof(int32_t) * (size_t) lp[k].n_samples);
-      }
-    }
-    LB_HIPCHK(hipMemcpyAsync(b->d_tab, b->h_tab, sizeof(BatchCapture) * (size_t) C, hipMemcpyHostToDevice, st));
-    if (any_explicit)
-      LB_HIPCHK(hipMemcpyAsync(b->d_local, b->h_samples, sizeof(int32_t) * (size_t) S_tot, hipMemcpyHostToDevice, st));
-    if (S_tot > 0)
-    {
-      hipLaunchKernelGGL(k_batch_samples, dim3((unsigned) ((S_tot + 255) / 256)), dim3(256), 0, st, (const BatchCapture*) b->d_tab, C,
-        S_tot, (const int*) c->d_cloud_off, (const int32_t*) b->d_local, c->d_idx_own, b->h_samples, b->h_bad);
-      LB_HIPCHK(hipGetLastError());
-    }
-    // ---- 5. search -> classification -> kept hands per capture -> handle search per capture, then the one synchronisation ----
-    if ((rc = batch_queue(ctx, B, false)) != AGH_OK)
-      return fail(rc);
+    if (pass > 0 && (rc = batch_pass(ctx)) != AGH_OK)  // (pass 0 was queued by agh_localize_batch_begin)
+      return rc;
     LB_HIPCHK(hipStreamSynchronize(st));
-    // ---- 6. the voxel descriptors: a lattice that outgrew the kept bitmap -> the batch once more with one sized for all ----
+    // ---- 6. the voxel descriptors: a lattice that outgrew the kept bitmap -> the batch once more with one sized for all, from
+    // the raw buffer (or the caller's device memory) the chain read, which a capture staged meanwhile has not touched ----
     int64_t words = 0;
     bool outgrown = false;
     for (int k = 0; k < C; k++)
@@ -667,7 +747,7 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
       const VoxDesc& h = b->h_desc[k];
       if (h.error == 1)
       {
-        drop_bound_cloud();
+        drop_bound_cloud(c);
         c->err = "agh_localize_batch: capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
                  "(1 GiB bitmap): set a workspace that bounds the scene";
         return AGH_ERR_CAPACITY;
@@ -677,18 +757,13 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
     }
     if (outgrown)
     {
+      drop_bound_cloud(c);
       if (pass > 0)
       {
-        drop_bound_cloud();
         c->err = "agh_localize_batch: the voxel bitmap sized from the batch's lattices did not hold them";
         return AGH_ERR_CAPACITY;
       }
-      drop_bound_cloud();
       b->slot_words = std::min<int64_t>(((words + words / 4) / 4096 + 1) * 4096, (int64_t) kVoxMaxWords);
-      for (int k = 0; k < C; k++)  // (explicit lists: from the pinned copy, which holds them at their spans already)
-        if (B.lp[k].sample_idx)
-          B.lp[k].sample_idx = b->h_samples + B.soff[k];
-      lp = B.lp.data();
       continue;
     }
     b->last_words = words;
@@ -713,7 +788,7 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
     if (attempt > 0)
     {
       if ((rc = batch_queue(ctx, B, handles_only)) != AGH_OK)
-        return fail(rc);
+        return batch_fail(c, rc);
       LB_HIPCHK(hipStreamSynchronize(st));
     }
     if (!handles_only)
@@ -806,20 +881,184 @@ static int localize_batch_impl(agh_ctx* ctx, const float* const* xyz, bool on_de
 }
 #undef LB_HIPCHK
 
+void zero_results(agh_localize_batch_result* results, int C)
+{
+  if (results && C >= 1 && C <= kMaxClouds)
+    for (int k = 0; k < C; k++)
+      results[k] = agh_localize_batch_result{ { 0, 0, 0, 0, 0 }, 0, 0, 0, 0 };
+}
+
+// agh_localize_batch[_device] = begin + end
+int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  zero_results(results, n_captures);
+  if (c->loc.active)
+  {
+    c->err = "agh_localize_batch: a localize chain is in flight on this context (agh_localize_end first)";
+    return AGH_ERR_STATE;
+  }
+  if (bad_outputs(handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap))
+  {
+    c->err = kBadArguments;
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  const int rc = batch_begin_impl(ctx, xyz, on_device, stride_bytes, n, lp, n_captures);
+  if (rc != AGH_OK)
+    return rc;
+  return batch_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+}
+}  // namespace
+
+extern "C" {
+
 int agh_localize_batch(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  return localize_batch_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap,
-    hands_out, hands_cap, samples_out, results);
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results);
 }
 
 int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  return localize_batch_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap,
-    hands_out, hands_cap, samples_out, results);
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results);
+}
+
+int agh_localize_batch_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures);
+}
+
+int agh_localize_batch_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures);
+}
+
+// The NEXT batch's captures up, beside whatever runs on the context's stream: packed end to end (step 1's stride rule) into the
+// context's second raw buffer, on the stage stream.  A pageable source makes the call last as long as its copies; a pinned one is
+// read asynchronously and must stay valid until the agh_localize_batch_end of the chain that adopts (or drops) the set.
+int agh_localize_batch_stage(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  LocalizeState& L = c->loc;
+  const int C = n_captures;
+  if (C < 1 || C > kMaxClouds || !xyz || !stride_bytes || !n)
+  {
+    c->err = "agh_localize_batch_stage: bad arguments (1 <= n_captures <= 64; see include/agh.h)";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  int64_t n_tot = 0, need = 0;
+  for (int k = 0; k < C; k++)
+  {
+    if (bad_capture(xyz[k], stride_bytes[k], n[k]))
+    {
+      c->err = "agh_localize_batch_stage: bad arguments for capture " + std::to_string(k) + " (see include/agh.h)";
+      return AGH_ERR_INVALID_ARGUMENT;
+    }
+    n_tot += n[k];
+    need += n[k] * ((stride_bytes[k] <= 32 ? stride_bytes[k] : 12) / 4);
+  }
+  if (n_tot >= (1ll << 30))
+  {
+    c->err = "agh_localize_batch_stage: need fewer than 2^30 raw points in all";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_stage_stream(c, "agh_localize_batch_stage")) != AGH_OK)
+    return rc;
+  // A failure from here on leaves nothing staged -- and an earlier set's copies may still be reading their (pinned) sources, with no
+  // begin left to wait for stage_done: the stage stream is drained before the flag comes down.
+  auto stage_fail = [&](int code) {
+    (void) hipStreamSynchronize(c->stage_stream);
+    L.staged = false;
+    return code;
+  };
+#define STAGE_HIPCHK(expr)                                                \
+  do                                                                      \
+  {                                                                       \
+    hipError_t e__ = (expr);                                              \
+    if (e__ != hipSuccess)                                                \
+    {                                                                     \
+      c->err = std::string(#expr) + ": " + hipGetErrorString(e__);        \
+      return stage_fail(AGH_ERR_HIP);                                     \
+    }                                                                     \
+  } while (0)
+  if (need > c->stage_cap || !c->d_stage_xyz)
+  {
+    // (nobody reads this buffer now: the chain in flight reads d_raw_xyz)
+    if ((rc = dev_alloc(c, &c->d_stage_xyz, (size_t) std::max<int64_t>(need, 1))))
+      return stage_fail(rc);
+    c->stage_cap = need;
+    c->stage_read_set = false;
+  }
+  if (c->stage_read_set)  // the last chain that read the buffer these copies overwrite (it has ended: see DESIGN.md)
+    STAGE_HIPCHK(hipStreamWaitEvent(c->stage_stream, c->stage_read, 0));
+  // (whatever was staged before is replaced: its copies are ahead of these on the stage stream, so stage_done covers them too)
+  int64_t off = 0;
+  for (int k = 0; k < C; k++)
+  {
+    float* dst = c->d_stage_xyz + off;
+    const int64_t dev_stride = stride_bytes[k] <= 32 ? stride_bytes[k] : 12;
+    if (n[k] > 0)
+    {
+      if (dev_stride == stride_bytes[k])
+        STAGE_HIPCHK(hipMemcpyAsync(dst, xyz[k], (size_t) (n[k] * stride_bytes[k] - (stride_bytes[k] - 12)), hipMemcpyHostToDevice,
+          c->stage_stream));
+      else
+        STAGE_HIPCHK(hipMemcpy2DAsync(dst, 12, xyz[k], (size_t) stride_bytes[k], 12, (size_t) n[k], hipMemcpyHostToDevice,
+          c->stage_stream));
+    }
+    off += n[k] * (dev_stride / 4);
+  }
+  STAGE_HIPCHK(hipEventRecord(c->stage_done, c->stage_stream));
+#undef STAGE_HIPCHK
+  L.staged_batch_src.assign(xyz, xyz + C);
+  L.staged_batch_stride.assign(stride_bytes, stride_bytes + C);
+  L.staged_batch_n.assign(n, n + C);
+  L.staged_captures = C;
+  L.staged = true;
+  return AGH_OK;
+}
+
+int agh_localize_batch_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (!c->loc.active || !c->loc.batch)
+  {
+    c->err = c->loc.active ? "agh_localize_batch_end: the chain in flight is a single capture's (agh_localize_end collects it)"
+                           : "agh_localize_batch_end: no agh_localize_batch_begin in flight";
+    return AGH_ERR_STATE;
+  }
+  zero_results(results, c->lbatch->call.C);
+  if (bad_outputs(handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap))
+  {
+    // (the chain is queued: drain it, leave the context as a failed call does)
+    c->loc.active = false;
+    c->loc.batch = false;
+    c->err = kBadArguments;
+    return batch_fail(c, AGH_ERR_INVALID_ARGUMENT);
+  }
+  return batch_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
 }
 
 }  // extern "C"

@@ -334,6 +334,46 @@ int agh_localize_batch(agh_ctx* ctx, const float* const* xyz, const int64_t* str
 int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+/* The same batch as two calls, so that the NEXT batch's captures go up while this one is searched (a walk over a directory of
+ * PCD pairs; the upload of 8 x 8 MB is a third of a blocking call, serial in front of its first kernel):
+ *   agh_localize_batch_begin(ctx, batch k)      validates as agh_localize_batch does (same status codes and error texts), copies
+ *                                               the pointer, stride and count arrays, the lp records and every explicit
+ *                                               sample_idx list, queues the whole chain and returns without waiting.  The first
+ *                                               batch of a context, or one after the kept bitmap slots were dropped, takes the
+ *                                               synchronisation for the lattice sizes here.
+ *   agh_localize_batch_stage(ctx, batch k + 1)  copies the next batch's host captures, packed end to end, into the context's
+ *                                               second raw buffer on a stream of its own, beside batch k's kernels (pageable
+ *                                               sources: the call lasts as long as the copies; pinned ones are read
+ *                                               asynchronously).  Allowed with or without a chain in flight.
+ *   agh_localize_batch_end(ctx, outputs)        the one synchronisation, the repeats agh_localize_batch runs inside the call
+ *                                               (from the raw buffer the batch was read from: a staged set is not touched), and
+ *                                               batch k's outputs, results[k], status and bound batch, exactly
+ *                                               agh_localize_batch's -- AGH_ERR_CAPACITY with results filled included.  The chain
+ *                                               is over whatever it returns.
+ *   agh_localize_batch_begin(ctx, batch k + 1)  adopts the staged set if n_captures and every (xyz[k], stride_bytes[k], n[k])
+ *                                               are the staged ones: the two raw buffers change places, nothing is uploaded.
+ * agh_localize_batch(...) is begin + end; agh_localize_batch_begin_device reads device captures in place (nothing to stage).
+ * The context has ONE chain and ONE staged set, of either kind.  A begin of either kind while a chain of either kind is in
+ * flight, agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
+ * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
+ * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
+ * agh_localize_end; every other call returns AGH_ERR_STATE without touching anything, a sharded call makes the rank a bystander,
+ * agh_destroy waits for both streams.  agh_set_cloud_cam_origins is among the refused: the batch searches with the table held at
+ * begin, whose row count is checked there.
+ * A newer stage call of either kind replaces what was staged.  agh_localize_batch_begin adopts only a staged batch,
+ * agh_localize_begin only a capture of agh_localize_stage; a staged set that a begin (of host captures) does not adopt is
+ * dropped, and the chain waits for its copies.
+ * Lifetimes: the arrays, lp records and sample lists handed to begin may be freed when it returns.  The captures handed to
+ * begin must stay valid and unchanged until the agh_localize_batch_end of their chain has returned; those handed to stage until
+ * the end of the chain that adopts or drops them has (pageable ones have been read when stage returns), or an
+ * agh_synchronize. */
+int agh_localize_batch_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_batch_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_batch_stage(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int32_t n_captures);
+int agh_localize_batch_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
 
 /* The context's current cloud: packed xyz (3 floats per point) and camera ids; returns the number of points. */
 int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap);

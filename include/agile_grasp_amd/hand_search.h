@@ -451,6 +451,129 @@ public:
     return true;
   }
 
+  /** Additional: localizeBatch as two calls (agh_localize_batch_begin / agh_localize_batch_end), for a caller that walks over
+   *  many batches: between the two, localizeBatchStage(next clouds) uploads the next batch on a second stream under this batch's
+   *  kernels, and the localizeBatchBegin that is later handed the same cloud objects finds them on the device.  Arguments as for
+   *  localizeBatch.  One chain may be in flight: a Begin that fails (a chain in flight included) leaves the one in flight, and
+   *  what localizeBatchEnd needs for it, as they were.  The clouds must stay alive and unchanged until localizeBatchEnd has
+   *  returned.  @return false (after printing) on error */
+  bool localizeBatchBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<VectorXd>& workspaces, double cell_size, const std::vector<std::vector<int> >& indices,
+    const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    const std::size_t C = clouds.size();
+    if (C == 0 || sizes_left.size() != C || workspaces.size() != C || indices.size() != C)
+    {
+      std::cout << " Error: localizeBatchBegin needs one size_left, workspace and index list per cloud\n";
+      return false;
+    }
+    if (!ensureContext())
+      return false;
+    if (agh_load_svm_file(ctx_, svm_filename.c_str()) != AGH_OK)
+    {
+      std::cout << " Exception: " << agh_last_error(ctx_) << "\n";  // learning.cpp:187-191
+      return false;
+    }
+    const std::uint64_t seed = sample_seed_set_ ? (std::uint64_t) sample_seed_ : (std::uint64_t) std::time(nullptr);
+    std::vector<agh_localize_params> lp(C);
+    std::vector<std::vector<std::int32_t> > idx(C);  // (copied by agh_localize_batch_begin, like the arrays below)
+    std::vector<const float*> xyz(C);
+    std::vector<std::int64_t> stride(C), n(C);
+    std::int64_t cap = 1, n_samples = 0;
+    for (std::size_t k = 0; k < C; k++)
+    {
+      agh_localize_params& p = lp[k];
+      p.size_left = (std::int64_t) sizes_left[k];
+      p.dense = cloud_is_dense(*clouds[k]) ? 1 : 0;
+      p.classify = 1;
+      for (int i = 0; i < 6; i++)
+        p.workspace[i] = workspaces[k](i);
+      p.cell_size = cell_size;
+      idx[k].assign(indices[k].begin(), indices[k].end());
+      p.sample_idx = idx[k].empty() ? nullptr : idx[k].data();
+      p.n_samples = idx[k].empty() ? (std::int64_t) (num_samples_ < 0 ? 0 : num_samples_) : (std::int64_t) idx[k].size();
+      p.sample_seed = seed + (std::uint64_t) k;
+      p.min_inliers = min_inliers;
+      p.filters_boundaries = filters_boundaries ? 1 : 0;
+      p.min_length = min_length;
+      n[k] = (std::int64_t) clouds[k]->size();
+      xyz[k] = n[k] > 0 ? &clouds[k]->points[0].x : nullptr;
+      stride[k] = (std::int64_t) sizeof(clouds[k]->points[0]);
+      cap += p.n_samples * 8 < 8192 ? p.n_samples * 8 : 8192;
+      n_samples += p.n_samples;
+    }
+    if (agh_localize_batch_begin(ctx_, xyz.data(), stride.data(), n.data(), lp.data(), (std::int32_t) C) != AGH_OK)
+    {
+      fail("agh_localize_batch_begin");
+      return false;
+    }
+    batch_captures_ = C;  // (only a Begin that went through replaces what the End of the chain in flight reads)
+    batch_cap_ = cap;
+    batch_samples_ = n_samples;
+    return true;
+  }
+
+  /** agh_localize_batch_stage: the NEXT batch's clouds up, beside the chain in flight (keep them alive and unchanged until the
+   *  localizeBatchEnd of the chain that searches them has returned). */
+  bool localizeBatchStage(const std::vector<PointCloud::Ptr>& next)
+  {
+    if (next.empty() || !ensureContext())
+      return false;
+    const std::size_t C = next.size();
+    std::vector<const float*> xyz(C);
+    std::vector<std::int64_t> stride(C), n(C);
+    for (std::size_t k = 0; k < C; k++)
+    {
+      if (!next[k])
+        return false;
+      n[k] = (std::int64_t) next[k]->size();
+      xyz[k] = n[k] > 0 ? &next[k]->points[0].x : nullptr;
+      stride[k] = (std::int64_t) sizeof(next[k]->points[0]);
+    }
+    if (agh_localize_batch_stage(ctx_, xyz.data(), stride.data(), n.data(), (std::int32_t) C) != AGH_OK)
+    {
+      fail("agh_localize_batch_stage");
+      return false;
+    }
+    return true;
+  }
+
+  /** agh_localize_batch_end: the one synchronisation and the results of the batch localizeBatchBegin queued, per capture as
+   *  localizeBatch returns them. */
+  bool localizeBatchEnd(std::vector<std::vector<agh_hypothesis> >& hands_out, std::vector<std::vector<agh_handle> >& handles_out,
+    std::vector<std::vector<std::int32_t> >& inliers_out)
+  {
+    const std::size_t C = batch_captures_;
+    hands_out.assign(C, std::vector<agh_hypothesis>());
+    handles_out.assign(C, std::vector<agh_handle>());
+    inliers_out.assign(C, std::vector<std::int32_t>());
+    if (!ctx_)
+      return false;
+    const std::int64_t cap = batch_cap_, n_samples = batch_samples_;
+    std::vector<agh_hypothesis> hands((std::size_t) cap);
+    std::vector<agh_handle> handles((std::size_t) cap);
+    std::vector<std::int32_t> inl((std::size_t) cap);
+    std::vector<std::int32_t> samples((std::size_t) n_samples + 1);
+    std::vector<agh_localize_batch_result> res(C + 1);
+    batch_captures_ = 0;
+    if (agh_localize_batch_end(ctx_, handles.data(), cap, inl.data(), cap, hands.data(), cap, samples.data(), res.data()) != AGH_OK)
+    {
+      fail("agh_localize_batch_end");
+      return false;
+    }
+    searched_n_ = 0;
+    for (std::size_t k = 0; k < C; k++)
+    {
+      const agh_localize_batch_result& r = res[k];
+      hands_out[k].assign(hands.begin() + r.first_hand, hands.begin() + r.first_hand + r.r.n_hands);
+      handles_out[k].assign(handles.begin() + r.first_handle, handles.begin() + r.first_handle + r.r.n_handles);
+      inliers_out[k].assign(inl.begin() + r.first_inlier_idx, inl.begin() + r.first_inlier_idx + r.r.n_inlier_idx);
+      searched_n_ += r.r.n_voxels;
+    }
+    last_samples_.assign(samples.begin(), samples.begin() + n_samples);
+    return true;
+  }
+
   /** Additional: camera origins per cloud of a batch (agh_set_cloud_cam_origins): row k = the translations of cams_left[k] /
    *  cams_right[k], as setCamTfLeft / setCamTfRight take them for the whole context.  Sticky until clearCloudCamOrigins.
    *  @return false (after printing) on error */
@@ -647,6 +770,8 @@ private:
   agh_ctx* ctx_;
   std::int64_t searched_n_ = 0;
   std::int64_t loc_cap_ = 1;  // room for the results of the chain localizeBegin queued
+  std::size_t batch_captures_ = 0;  // ... and of the batch localizeBatchBegin queued: its captures, room, samples
+  std::int64_t batch_cap_ = 1, batch_samples_ = 0;
   agh_params params_;
   Matrix4d cam_tf_left_, cam_tf_right_;
   int num_threads_, num_samples_;

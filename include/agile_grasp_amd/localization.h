@@ -356,6 +356,77 @@ public:
     return out;
   }
 
+  /** Additional: localizeHandlesBatch as two calls, for a walk over a directory of captures, batch by batch:
+   *      loc.localizeHandlesBatchBegin(batch_k, sizes_left_k, indices_k, svm, min_inliers, 0.005);  // queued, not waited for
+   *      loc.stageNextBatch(batch_k1);                          // its uploads run under batch k's kernels
+   *      handles = loc.localizeHandlesBatchEnd(&antipodal_hands_per_cloud);                         // the one synchronisation
+   *      loc.localizeHandlesBatchBegin(batch_k1, ...);          // finds batch k + 1 on the device
+   *  Same results as localizeHandlesBatch.  One chain of either kind may be pending: a Begin while one is returns false and leaves
+   *  it as it was, and so does a Begin that fails for another reason.  The clouds must stay alive and unchanged until the
+   *  localizeHandlesBatchEnd of their chain has returned (which then filters NaNs out of them in place). */
+  bool localizeHandlesBatchBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<std::vector<int> >& indices_per_cloud, const std::string& svm_filename, int min_inliers, double min_length,
+    const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (pending_cloud_ || !pending_batch_.empty())  // (the chain in flight stays pending, for its End)
+    {
+      std::cout << " Error: localizeHandlesBatchBegin while a chain is pending (its End first)\n";
+      return false;
+    }
+    const std::size_t C = clouds.size();
+    for (std::size_t k = 0; k < C; k++)
+      if (!clouds[k] || clouds[k]->size() == 0 || k >= sizes_left.size() || sizes_left[k] == 0)
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    std::ifstream f(svm_filename.c_str());
+    if (!f.good())
+    {
+      std::cout << " Error: File " << svm_filename << " does not exist!\n";  // learning.cpp:172-178
+      return false;
+    }
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(C, workspace_);
+    if (!search_->localizeBatchBegin(clouds, sizes_left, ws, 0.003, indices_per_cloud, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
+      return false;
+    pending_batch_ = clouds;
+    return true;
+  }
+
+  /** agh_localize_batch_stage through the adapter: the next batch up, beside the chain in flight */
+  bool stageNextBatch(const std::vector<PointCloud::Ptr>& next)
+  {
+    for (std::size_t k = 0; k < next.size(); k++)
+      if (!next[k] || next[k]->size() == 0)
+        return false;
+    if (next.empty())
+      return false;
+    ensureSearch();
+    return search_->localizeBatchStage(next);
+  }
+
+  std::vector<std::vector<Handle> > localizeHandlesBatchEnd(std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_cloud = nullptr)
+  {
+    const std::vector<PointCloud::Ptr> clouds = pending_batch_;
+    pending_batch_.clear();
+    const std::size_t C = clouds.size();
+    std::vector<std::vector<Handle> > out(C);
+    if (antipodal_hands_per_cloud)
+      antipodal_hands_per_cloud->assign(C, std::vector<GraspHypothesis>());
+    if (C == 0)
+      return out;
+    std::vector<std::vector<agh_hypothesis> > hands;
+    std::vector<std::vector<agh_handle> > handles;
+    std::vector<std::vector<std::int32_t> > idx;
+    if (!search_->localizeBatchEnd(hands, handles, idx))
+      return out;
+    for (std::size_t k = 0; k < C; k++)
+      out[k] = toHandles(clouds[k], hands[k], handles[k], idx[k], antipodal_hands_per_cloud ? &(*antipodal_hands_per_cloud)[k] : nullptr);
+    return out;
+  }
+
   /** Additional: the same for captures of SEVERAL rigs -- capture k was taken with the camera transforms cams_left[k] /
    *  cams_right[k] (translations only, as setCameraTransforms).  Sets the per-cloud origin table (agh_set_cloud_cam_origins),
    *  runs the batch and clears the table: per capture the same handles as localizeHandles of a Localization set up with that
@@ -482,6 +553,8 @@ private:
   bool keeps_training_images_ = false;
   // localizeHandlesBegin -> localizeHandlesEnd
   PointCloud::Ptr pending_cloud_;
+  // localizeHandlesBatchBegin -> localizeHandlesBatchEnd
+  std::vector<PointCloud::Ptr> pending_batch_;
   std::unique_ptr<HandSearch> search_;
   PointCloud::Ptr last_cloud_;
   VectorXi last_cam_;
