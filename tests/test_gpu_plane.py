@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import plane_clouds
 from tests import plane_ref_lib as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,33 +16,9 @@ LIBDIR = os.path.join(ROOT, "agile_grasp_amd", "lib")
 
 
 def _check(ctx, xyz, cam, by_position):
-    """remove_plane on the context's cloud (xyz, cam as read back) against the restatement; returns the GPU result."""
-    ref = R.segment(xyz)
-    res = ctx.remove_plane(cam_ids_by_position=by_position)
-    assert res["found"] == ref["found"]
-    assert res["iterations"] == ref["iterations"]
-    g = ctx.plane_candidates()
-    k = ref["planes"].shape[0]
-    assert g["planes"].shape[0] >= k
-    assert np.array_equal(g["planes"][:k].view(np.uint32), ref["planes"].view(np.uint32))
-    assert np.array_equal(g["samples"][:k], ref["samples"]) and np.array_equal(g["counts"][:k], ref["counts"])
-    if not ref["found"]:
-        assert res["n_remaining"] == len(xyz) and res["n_inliers"] == 0
-        vx, vc = ctx.cloud()
-        assert np.array_equal(vx, xyz) and np.array_equal(vc, cam)
-        return res
-    from agile_grasp_amd import binding
-
-    assert binding.plane_replay(g["counts"], len(xyz)) == (ref["best"], ref["iterations"])
-    assert np.array_equal(res["coefficients"].view(np.uint32), ref["coefficients"].view(np.uint32))
-    assert np.array_equal(ctx.plane_inliers(), ref["inliers"])
-    m = ref["mask"]
-    M = int((~m).sum())
-    assert res["n_inliers"] == int(m.sum()) and res["n_remaining"] == M
-    kx, kc = ctx.cloud()
-    assert np.array_equal(kx, xyz[~m])
-    assert np.array_equal(kc, cam[:M] if by_position else cam[~m])
-    return res
+    """remove_plane with its defaults on the context's cloud (xyz, cam as read back) against the restatement (the shared check
+    of tests/plane_clouds.py); returns the GPU result."""
+    return plane_clouds.check(ctx, xyz, cam, by_position)
 
 
 def _context(sc):
