@@ -208,14 +208,22 @@ struct LocalizeState
   agh_localize_params lp{};   // (sample_idx cleared: the list lives in the pinned staging)
   const float* d_raw = nullptr;  // where the chain read the raw capture (the context's raw buffer or the caller's device memory)
   int64_t dev_stride = 0, n_raw = 0;
-  bool staged = false;        // agh_localize_stage: a capture is (being) copied into d_stage_xyz
-  const float* staged_src = nullptr;
-  int64_t staged_stride = 0, staged_n = 0;
   // agh_localize_batch_begin / _stage / _end (localize_batch.hip) share the one chain and the one staged set of the context
   bool batch = false;         // the chain in flight is a batch's (agh_localize_batch_end collects it, not agh_localize_end)
-  int staged_captures = 0;    // staged: 0 = one capture of agh_localize_stage; C = the C captures of agh_localize_batch_stage,
-  std::vector<const float*> staged_batch_src;             // packed end to end in d_stage_xyz, with these sources
-  std::vector<int64_t> staged_batch_stride, staged_batch_n;
+  bool staged = false;        // stage_captures: a set of captures is (being) copied into d_stage_xyz, packed end to end,
+  int staged_captures = 0;    // 0 = the one capture of agh_localize_stage; C = the C captures of agh_localize_batch_stage,
+  std::vector<const float*> staged_src;  // with these sources, strides and counts (one entry for agh_localize_stage's)
+  std::vector<int64_t> staged_stride, staged_n;
+  // the begin that may adopt the staged set: is it these `count` captures (as_batch: of a batch), by pointer, stride and count?
+  bool staged_is(const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int count, bool as_batch) const
+  {
+    if (!staged || staged_captures != (as_batch ? count : 0) || (int) staged_src.size() != count)
+      return false;
+    for (int k = 0; k < count; k++)
+      if (staged_src[k] != xyz[k] || staged_stride[k] != stride_bytes[k] || staged_n[k] != n[k])
+        return false;
+    return true;
+  }
 };
 
 struct PlaneState;
@@ -459,6 +467,99 @@ struct Ctx
 
 inline int class_level(const Ctx* c) { return c->huge_classes ? 2 : (c->big_classes ? 1 : 0); }
 
+// A HIP call that failed leaves its own text and HIP's in the context's error string, and the function returns AGH_ERR_HIP -- or
+// on_fail, evaluated after the string is set: whatever first undoes what the function has queued (chain_fail, stage_captures).
+inline bool hip_failed(Ctx* c, hipError_t e, const char* expr)
+{
+  if (e != hipSuccess)
+    c->err = std::string(expr) + ": " + hipGetErrorString(e);
+  return e != hipSuccess;
+}
+#define AGH_HIPCHK(c, expr) do { if (agh::hip_failed((c), (expr), #expr)) return AGH_ERR_HIP; } while (0)
+#define AGH_HIPCHK_OR(c, expr, on_fail) do { if (agh::hip_failed((c), (expr), #expr)) return (on_fail); } while (0)
+
+// ---- the localize chains' plumbing (localize.hip, localize_batch.hip; the uploads and the label buffers: api.hip, hog_svm.hip,
+// shard.hip too) ----
+// A chain failed between its launches and its synchronisation, while the host only knows a BOUND of the cloud's size: the context
+// must not be left believing the bound is the cloud.
+inline void drop_bound_cloud(Ctx* c)
+{
+  if (!c->n_is_bound)
+    return;
+  c->n_is_bound = false;
+  c->has_cloud = false;
+  c->n = 0;
+  c->cloud_off_on_device = false;
+}
+// ... and every such error return first drains the stream: a pinned source may still be in flight, and the caller may free it as
+// soon as the call returns.
+inline int chain_fail(Ctx* c, int code)
+{
+  (void) hipStreamSynchronize(c->stream);
+  drop_bound_cloud(c);
+  return code;
+}
+// a raw capture as the entry points take it: n points of stride_bytes each, x y z first
+inline bool bad_capture(const float* xyz, int64_t stride_bytes, int64_t n)
+{
+  return n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz);
+}
+// the output arguments of agh_localize* and agh_localize_batch*
+inline bool bad_outputs(const agh_handle* handles_out, int64_t handle_cap, const int32_t* inlier_idx_out, int64_t idx_cap,
+  const agh_hypothesis* hands_out, int64_t hands_cap)
+{
+  return handle_cap < 0 || idx_cap < 0 || hands_cap < 0 || (handle_cap > 0 && !handles_out) || (idx_cap > 0 && !inlier_idx_out) ||
+         (hands_cap > 0 && !hands_out);
+}
+// A host capture goes up as it lies in host memory -- one contiguous copy: a strided 2-D copy of 12 of every 32 bytes runs at a
+// fraction of the PCIe rate -- and the kernels read it with the caller's stride; strides above 32 bytes are repacked to 12.
+inline int64_t device_stride(int64_t stride_bytes) { return stride_bytes <= 32 ? stride_bytes : 12; }
+inline hipError_t upload_capture(float* dst, const float* xyz, int64_t stride_bytes, int64_t n, hipStream_t st)
+{
+  if (n <= 0)
+    return hipSuccess;
+  if (device_stride(stride_bytes) == stride_bytes)  // (all but the last point's padding, which may lie outside the caller's buffer)
+    return hipMemcpyAsync(dst, xyz, (size_t) (n * stride_bytes - (stride_bytes - 12)), hipMemcpyHostToDevice, st);
+  return hipMemcpy2DAsync(dst, 12, xyz, (size_t) stride_bytes, 12, (size_t) n, hipMemcpyHostToDevice, st);
+}
+// The classifier's labels and decision sums for `count` hypotheses.  Growing drops the old pair first and counts nothing as held
+// until both allocations have succeeded.
+inline hipError_t ensure_keep_buffers(Ctx* c, int64_t count)
+{
+  if (count <= c->keep_cap)
+    return hipSuccess;
+  if (c->d_keep)
+    (void) hipFree(c->d_keep);
+  if (c->d_svm_sums)
+    (void) hipFree(c->d_svm_sums);
+  c->d_keep = nullptr;
+  c->d_svm_sums = nullptr;
+  c->keep_cap = 0;
+  hipError_t e = hipMalloc((void**) &c->d_keep, (size_t) count);
+  if (e == hipSuccess)
+    e = hipMalloc((void**) &c->d_svm_sums, (size_t) count * sizeof(double));
+  if (e == hipSuccess)
+    c->keep_cap = count;
+  return e;
+}
+// the slices of h_pin_handles (ensure_handle_buffers: room for h_pin_handles_cap of each)
+struct HandlePins
+{
+  int* counts;            // the 256-byte header: [0..3] the handle search's (HandleMirror::counts), [4..6] k_compact_kept's
+  agh_hypothesis* hands;
+  agh_handle* handles;
+  int32_t* idx;
+};
+inline HandlePins handle_pins(const Ctx* c)
+{
+  HandlePins p;
+  p.counts = reinterpret_cast<int*>(c->h_pin_handles);
+  p.hands = reinterpret_cast<agh_hypothesis*>(c->h_pin_handles + 256);
+  p.handles = reinterpret_cast<agh_handle*>(p.hands + c->h_pin_handles_cap);
+  p.idx = reinterpret_cast<int32_t*>(p.handles + c->h_pin_handles_cap);
+  return p;
+}
+
 // include/agh.h: between agh_localize_begin and agh_localize_end only agh_localize_stage and the calls listed there may run on a
 // context.  The others refuse here, before they touch a buffer: the chain in flight owns the per-call buffers (d_out_own, d_flags,
 // d_idx_own, the pinned mirrors) and the cloud, whose size may still be only a bound (n_is_bound).
@@ -662,6 +763,58 @@ __device__ __forceinline__ bool near_workspace_boundary(const double* surface, c
   for (int k = 0; k < 6; k++)
     near |= fabs(surface[k >> 1] - ws[k]) < kBoundaryMinDist;
   return near;
+}
+
+// The body of k_compact_kept (localize.hip) and k_compact_kept_batch (localize_batch.hip), one work-group of 1024 threads: the
+// records of in[r0, r1) that are kept -- svm_keep if use_keep; not near a face of ws if filters -- leave in list order (an ordered
+// compaction is a scan: a ballot, sixteen wave sums, a carry), each as one 160-byte run, ten threads of sixteen bytes, to out and,
+// below host_cap, to host_out (pinned; null: none), `sample` less sample_base.  dev_cap bounds what is written, not what is
+// counted; the count is returned.  LDS of the caller: src[kCompactList] (position in the output -> position in the input),
+// wsum[16], carry.
+constexpr int kCompactList = 8192;  // (the handle search takes no more)
+__device__ __forceinline__ int compact_kept_records(const agh_hypothesis* __restrict__ in, int64_t r0, int64_t r1, int use_keep,
+  int filters, const double* ws, int* src, int* wsum, int* carry, agh_hypothesis* __restrict__ out, int dev_cap,
+  agh_hypothesis* __restrict__ host_out, int host_cap, int sample_base)
+{
+  static_assert(sizeof(agh_hypothesis) == 160 && offsetof(agh_hypothesis, sample) == 8 * 16,
+    "ten 16-byte parts; sample is the first word of the ninth");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0)
+    *carry = 0;
+  __syncthreads();
+  for (int64_t b0 = r0; b0 < r1; b0 += 1024)
+  {
+    const int64_t i = b0 + tid;
+    const bool keep = i < r1 && (!use_keep || in[i].svm_keep != 0) && !(filters && near_workspace_boundary(in[i].surface, ws));
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0)
+      wsum[wave] = __popcll(m);
+    __syncthreads();
+    int base = *carry, tot = 0;
+    for (int w = 0; w < 16; w++)
+    {
+      base += w < wave ? wsum[w] : 0;
+      tot += wsum[w];
+    }
+    const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+    if (keep && pos < kCompactList)
+      src[pos] = (int) i;
+    __syncthreads();
+    if (tid == 0)
+      *carry += tot;
+    __syncthreads();
+  }
+  const int K = *carry, kw = min(K, min(dev_cap, kCompactList));
+  for (int t = tid; t < kw * 10; t += 1024)
+  {
+    const int k = t / 10, part = t - 10 * k;
+    const uint4 raw = reinterpret_cast<const uint4*>(in + src[k])[part];
+    const uint4 v = make_uint4(part == 8 ? (unsigned) ((int) raw.x - sample_base) : raw.x, raw.y, raw.z, raw.w);
+    reinterpret_cast<uint4*>(out + k)[part] = v;
+    if (host_out && k < host_cap)
+      reinterpret_cast<uint4*>(host_out + k)[part] = v;
+  }
+  return K;
 }
 
 __device__ __forceinline__ unsigned enc_float(float f)
@@ -1101,3 +1254,9 @@ int preprocess_device_impl(agh_ctx* ctx, const float* d_xyz, int64_t stride_byte
 bool handle_thresholds(double* x1, double* x2);
 int ensure_handle_buffers(agh::Ctx* c, int64_t n_hands);
 int flags_to_status(agh::Ctx* c, const int32_t* flags);
+// localize.hip's pieces that localize_batch.hip runs too: the staging of the next chain's captures, and the end of a chain behind
+// its synchronisation (the capacity-class repeat, the sequential-walk repeat, the limits)
+int stage_captures(agh_ctx* ctx, const char* who, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int C,
+  bool as_batch);
+int chain_collect(agh_ctx* ctx, const char* who, bool label_captures, int C, const int* counts, int count_stride, int64_t S_tot,
+  const int* bad, int (*requeue)(agh_ctx*, bool handles_only));

@@ -39,17 +39,6 @@ int32_t next_epoch()
 namespace
 {
 
-#define HIPCHK(ctx, expr)                                                                             \
-  do                                                                                                  \
-  {                                                                                                   \
-    hipError_t e__ = (expr);                                                                          \
-    if (e__ != hipSuccess)                                                                            \
-    {                                                                                                 \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                                \
-      return AGH_ERR_HIP;                                                                             \
-    }                                                                                                 \
-  } while (0)
-
 // glibc rand() (TYPE_3 additive feedback) -- the generator behind quadric.cpp:184 in a default Linux build.
 struct GlibcRand
 {
@@ -251,13 +240,13 @@ int ensure_host_staging(Ctx* c, int64_t samples, int64_t records)
   const int64_t nr = std::max<int64_t>(std::max<int64_t>(records, c->h_pin_records), 1024);
   if (c->h_pin)
   {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
     (void) hipHostFree(c->h_pin);
     c->h_pin = nullptr;
     c->h_pin_samples = c->h_pin_records = 0;
   }
   void* p = nullptr;
-  HIPCHK(c, hipHostMalloc(&p, (size_t) (kPinHeaderBytes + pin_round(ns * 4) + nr * (int64_t) sizeof(agh_hypothesis)), hipHostMallocDefault));
+  AGH_HIPCHK(c, hipHostMalloc(&p, (size_t) (kPinHeaderBytes + pin_round(ns * 4) + nr * (int64_t) sizeof(agh_hypothesis)), hipHostMallocDefault));
   c->h_pin = static_cast<uint8_t*>(p);
   c->h_pin_samples = ns;
   c->h_pin_records = nr;
@@ -293,8 +282,8 @@ int ensure_draws(Ctx* c, int64_t count, hipStream_t st)
   int rc;
   if ((rc = dev_alloc(c, &c->d_draws, (size_t) count)))
     return rc;
-  HIPCHK(c, hipMemcpyAsync(c->d_draws, h.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  AGH_HIPCHK(c, hipMemcpyAsync(c->d_draws, h.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, st));
+  AGH_HIPCHK(c, hipStreamSynchronize(st));
   c->draws_cap = count;
   return AGH_OK;
 }
@@ -599,14 +588,14 @@ int agh_set_cloud_batch_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_
       return AGH_ERR_INVALID_ARGUMENT;
     }
   const int64_t n = offsets[n_clouds];
-  if (n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !d_xyz))
+  if (bad_capture(d_xyz, stride_bytes, n))
   {
     c->err = "agh_set_cloud: need 0 <= n < 2^30 points in total, stride_bytes >= 12 and a multiple of 4";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t) hip_stream : c->stream;
-  HIPCHK(c, order_after_cloud(c, st));  // (a build an earlier host-buffer agh_set_cloud left running writes the same tables)
+  AGH_HIPCHK(c, order_after_cloud(c, st));  // (a build an earlier host-buffer agh_set_cloud left running writes the same tables)
   int rc = ensure_clouds(c, n_clouds);
   if (rc != AGH_OK)
     return rc;
@@ -644,7 +633,7 @@ int agh_set_cloud_batch_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_
     for (int k = 0; k <= kMaxClouds; k++)
       a.v[k] = c->cloud_off_i32[(size_t) k];
     hipLaunchKernelGGL(k_set_cloud_off, dim3(1), dim3(128), 0, st, a, c->d_cloud_off);
-    HIPCHK(c, hipGetLastError());
+    AGH_HIPCHK(c, hipGetLastError());
     c->cloud_off_on_device = true;
   }
   if (n > c->grid_cap)
@@ -709,17 +698,13 @@ int agh_set_cloud_batch(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, co
     return AGH_ERR_INVALID_ARGUMENT;
   }
   const int64_t n = offsets[n_clouds];
-  if (n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz))
+  if (bad_capture(xyz, stride_bytes, n))
   {
     c->err = "agh_set_cloud: need 0 <= n < 2^30, stride_bytes >= 12 and a multiple of 4";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  // The points are uploaded as they lie in host memory (one contiguous copy: a strided 2-D copy of 12 of every 32
-  // bytes runs at a fraction of the PCIe rate) and the kernels read them with the caller's stride; strides above 32
-  // bytes are repacked to 12.
-  const bool as_is = stride_bytes <= 32;
-  const int64_t dev_stride = as_is ? stride_bytes : 12;
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  const int64_t dev_stride = device_stride(stride_bytes);  // (the points go up as they lie, or repacked: upload_capture)
   const int64_t need = n * (dev_stride / 4);
   if (need > c->own_cap_floats || n > c->own_cap)
   {
@@ -737,17 +722,12 @@ int agh_set_cloud_batch(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, co
   c->cam_copy_on_copy_stream = false;
   if (n > 0)
   {
-    if (as_is)
-      HIPCHK(c, hipMemcpyAsync(c->own_xyz, xyz, (size_t) (n * stride_bytes - (stride_bytes - 12)), hipMemcpyHostToDevice,
-                  c->stream));  // (the last point's padding may lie outside the caller's buffer)
-    else
-      HIPCHK(c, hipMemcpy2DAsync(c->own_xyz, 12, xyz, (size_t) stride_bytes, 12, (size_t) n, hipMemcpyHostToDevice,
-                  c->stream));
+    AGH_HIPCHK(c, upload_capture(c->own_xyz, xyz, stride_bytes, n, c->stream));
     if (xyz_pinned)
     {
       if (!c->xyz_copied)
-        HIPCHK(c, hipEventCreateWithFlags(&c->xyz_copied, hipEventDisableTiming));
-      HIPCHK(c, hipEventRecord(c->xyz_copied, c->stream));
+        AGH_HIPCHK(c, hipEventCreateWithFlags(&c->xyz_copied, hipEventDisableTiming));
+      AGH_HIPCHK(c, hipEventRecord(c->xyz_copied, c->stream));
     }
     if (cam_source)  // (uploaded by grid_build, overlapped with its coordinate-only kernels)
     {
@@ -755,7 +735,7 @@ int agh_set_cloud_batch(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, co
       c->pending_cam_n = n;
     }
     else
-      HIPCHK(c, hipMemsetAsync(c->own_cam, 0, sizeof(int32_t) * n, c->stream));
+      AGH_HIPCHK(c, hipMemsetAsync(c->own_cam, 0, sizeof(int32_t) * n, c->stream));
   }
   // (The pageable copies above return when the caller's buffers have been read, so they may be reused at once; the grid
   // build is left running on the context's stream -- whatever uses the cloud next is ordered behind it there, and an
@@ -765,16 +745,16 @@ int agh_set_cloud_batch(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, co
   {
     c->pending_cam_host = nullptr;
     if (rc == AGH_OK)
-      HIPCHK(c, hipMemcpyAsync(c->own_cam, cam_source, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+      AGH_HIPCHK(c, hipMemcpyAsync(c->own_cam, cam_source, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
   }
   if (xyz_pinned)
-    HIPCHK(c, hipEventSynchronize(c->xyz_copied));
+    AGH_HIPCHK(c, hipEventSynchronize(c->xyz_copied));
   if (cam_pinned)
   {
     if (c->cam_copy_on_copy_stream)
-      HIPCHK(c, hipEventSynchronize(c->copy_done));
+      AGH_HIPCHK(c, hipEventSynchronize(c->copy_done));
     else  // the ids went up on the context's stream (no copy stream, or the fallback above): behind the build's kernels
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+      AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   c->cloud_async = rc == AGH_OK;
   return rc;
@@ -802,13 +782,12 @@ extern "C++" int preprocess_device_impl(agh_ctx* ctx, const float* d_xyz, int64_
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
-  if (n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !d_xyz) || !workspace ||
-      !(cell_size > 0.0) || size_left < 0)
+  if (bad_capture(d_xyz, stride_bytes, n) || !workspace || !(cell_size > 0.0) || size_left < 0)
   {
     c->err = "agh_preprocess: need 0 <= n < 2^30, stride_bytes >= 12 and a multiple of 4, a workspace, cell_size > 0";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t) hip_stream : c->stream;
   int rc;
   if (!c->d_vox_desc)
@@ -827,7 +806,7 @@ extern "C++" int preprocess_device_impl(agh_ctx* ctx, const float* d_xyz, int64_
   if (!c->h_vox_desc)
   {
     void* p = nullptr;
-    HIPCHK(c, hipHostMalloc(&p, sizeof(VoxDesc), hipHostMallocDefault));
+    AGH_HIPCHK(c, hipHostMalloc(&p, sizeof(VoxDesc), hipHostMallocDefault));
     c->h_vox_desc = static_cast<VoxDesc*>(p);
   }
   timing_begin(c, st);
@@ -856,7 +835,7 @@ extern "C++" int preprocess_device_impl(agh_ctx* ctx, const float* d_xyz, int64_
     }
     if (!speculative)
     {
-      HIPCHK(c, hipStreamSynchronize(st));  // the first cloud of the context: the lattice size decides the bitmap allocation
+      AGH_HIPCHK(c, hipStreamSynchronize(st));  // the first cloud of the context: the lattice size decides the bitmap allocation
       h = *c->h_vox_desc;
       if (h.error)
         break;
@@ -883,7 +862,7 @@ extern "C++" int preprocess_device_impl(agh_ctx* ctx, const float* d_xyz, int64_
       c->defer_cloud_count = false;  // (also when the call left before it consumed the flag: it must never reach the caller's NEXT cloud)
       return rc_set;
     }
-    HIPCHK(c, hipStreamSynchronize(st));  // the voxel count sizes the search structure
+    AGH_HIPCHK(c, hipStreamSynchronize(st));  // the voxel count sizes the search structure
     h = *c->h_vox_desc;
     if (h.error != 2 || attempt >= 1)
       break;
@@ -913,14 +892,13 @@ int agh_preprocess(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t
   Ctx* c = &ctx->c;
   if (refuse_mid_chain(c, "agh_preprocess"))
     return AGH_ERR_STATE;
-  if (n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz))
+  if (bad_capture(xyz, stride_bytes, n))
   {
     c->err = "agh_preprocess: need 0 <= n < 2^30, stride_bytes >= 12 and a multiple of 4";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool as_is = stride_bytes <= 32;  // one contiguous upload, read with the caller's stride (see agh_set_cloud)
-  const int64_t dev_stride = as_is ? stride_bytes : 12;
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  const int64_t dev_stride = device_stride(stride_bytes);
   const int64_t need = n * (dev_stride / 4);
   if (need > c->raw_cap || !c->d_raw_xyz)
   {
@@ -929,15 +907,7 @@ int agh_preprocess(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t
       return rc;
     c->raw_cap = need;
   }
-  if (n > 0)
-  {
-    if (as_is)
-      HIPCHK(c, hipMemcpyAsync(c->d_raw_xyz, xyz, (size_t) (n * stride_bytes - (stride_bytes - 12)), hipMemcpyHostToDevice,
-                  c->stream));
-    else
-      HIPCHK(c, hipMemcpy2DAsync(c->d_raw_xyz, 12, xyz, (size_t) stride_bytes, 12, (size_t) n, hipMemcpyHostToDevice,
-                  c->stream));
-  }
+  AGH_HIPCHK(c, upload_capture(c->d_raw_xyz, xyz, stride_bytes, n, c->stream));
   // (the grid build is left running on the context's stream, as after agh_set_cloud)
   const int rc = agh_preprocess_device(ctx, c->d_raw_xyz, dev_stride, n, size_left, dense, workspace, cell_size, n_voxels_out,
     nullptr);
@@ -1016,13 +986,13 @@ extern "C++" int ensure_handle_buffers(Ctx* c, int64_t n_hands)
     const int64_t cap = std::max<int64_t>(n_hands, 1024);
     if (c->h_pin_handles)
     {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+      AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
       (void) hipHostFree(c->h_pin_handles);
       c->h_pin_handles = nullptr;
       c->h_pin_handles_cap = 0;
     }
     void* p = nullptr;
-    HIPCHK(c, hipHostMalloc(&p, (size_t) (256 + cap * (int64_t) (sizeof(agh_hypothesis) + sizeof(agh_handle) + sizeof(int32_t))),
+    AGH_HIPCHK(c, hipHostMalloc(&p, (size_t) (256 + cap * (int64_t) (sizeof(agh_hypothesis) + sizeof(agh_handle) + sizeof(int32_t))),
                 hipHostMallocDefault));
     c->h_pin_handles = static_cast<uint8_t*>(p);
     c->h_pin_handles_cap = cap;
@@ -1050,22 +1020,20 @@ int agh_find_handles(agh_ctx* ctx, const agh_hypothesis* hands, int64_t n_hands,
     c->err = "agh_find_handles: this libm's acos is not monotone around the 0.34 rad thresholds";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   {
     const int rc = ensure_handle_buffers(c, n_hands);
     if (rc != AGH_OK)
       return rc;
   }
-  int* h_counts = reinterpret_cast<int*>(c->h_pin_handles);
-  agh_hypothesis* h_hands = reinterpret_cast<agh_hypothesis*>(c->h_pin_handles + 256);
-  agh_handle* h_handles = reinterpret_cast<agh_handle*>(h_hands + c->h_pin_handles_cap);
-  int32_t* h_idx = reinterpret_cast<int32_t*>(h_handles + c->h_pin_handles_cap);
+  const HandlePins pin = handle_pins(c);
+  int* h_counts = pin.counts;
   if (n_hands > 0)
   {
-    std::memcpy(h_hands, hands, sizeof(agh_hypothesis) * (size_t) n_hands);
-    HIPCHK(c, hipMemcpyAsync(c->d_h_hands, h_hands, sizeof(agh_hypothesis) * n_hands, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(pin.hands, hands, sizeof(agh_hypothesis) * (size_t) n_hands);
+    AGH_HIPCHK(c, hipMemcpyAsync(c->d_h_hands, pin.hands, sizeof(agh_hypothesis) * n_hands, hipMemcpyHostToDevice, c->stream));
   }
-  const HandleMirror hm{ h_handles, (int) c->h_pin_handles_cap, h_idx, (int) c->h_pin_handles_cap, h_counts };
+  const HandleMirror hm{ pin.handles, (int) c->h_pin_handles_cap, pin.idx, (int) c->h_pin_handles_cap, h_counts };
   for (int attempt = 0; attempt < 2; attempt++)
   {
     h_counts[0] = h_counts[1] = h_counts[2] = h_counts[3] = 0;
@@ -1078,7 +1046,7 @@ int agh_find_handles(agh_ctx* ctx, const agh_hypothesis* hands, int64_t n_hands,
       c->err = "handle search launch failed";
       return rc;
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
     const bool declined = h_counts[3] != 0;  // a row of the pair matrix longer than a wave
     c->handles_sequential = declined;        // what this set of hands needed is the guess for the next one
     if (!declined || with_sequential)
@@ -1098,8 +1066,8 @@ int agh_find_handles(agh_ctx* ctx, const agh_hypothesis* hands, int64_t n_hands,
   }
   if (counts[0] > 0)
   {
-    std::memcpy(handles_out, h_handles, sizeof(agh_handle) * (size_t) counts[0]);
-    std::memcpy(inlier_idx_out, h_idx, sizeof(int32_t) * (size_t) counts[1]);
+    std::memcpy(handles_out, pin.handles, sizeof(agh_handle) * (size_t) counts[0]);
+    std::memcpy(inlier_idx_out, pin.idx, sizeof(int32_t) * (size_t) counts[1]);
   }
   return AGH_OK;
 }
@@ -1116,15 +1084,15 @@ int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap)
     c->err = "agh_get_cloud: no cloud set";
     return AGH_ERR_NO_CLOUD;
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipDeviceSynchronize());
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipDeviceSynchronize());
   const int64_t k = std::min<int64_t>(cap, c->n);
   if (k > 0 && xyz_out)
-    HIPCHK(c, hipMemcpy2D(xyz_out, 12, c->d_xyz, (size_t) c->stride_floats * 4, 12, (size_t) k, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy2D(xyz_out, 12, c->d_xyz, (size_t) c->stride_floats * 4, 12, (size_t) k, hipMemcpyDeviceToHost));
   if (k > 0 && cam_out)
   {
     if (c->d_cam)
-      HIPCHK(c, hipMemcpy(cam_out, c->d_cam, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
+      AGH_HIPCHK(c, hipMemcpy(cam_out, c->d_cam, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
     else
       std::memset(cam_out, 0, sizeof(int32_t) * k);
   }
@@ -1155,7 +1123,7 @@ int agh_set_cloud_cam_origins(agh_ctx* ctx, const double* cam_origin, int32_t n_
       c->err = "agh_set_cloud_cam_origins: a non-finite origin in row " + std::to_string(k / 6);
       return AGH_ERR_INVALID_ARGUMENT;
     }
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   if (!c->d_cam_tab)
   {
     const int rc = dev_alloc(c, &c->d_cam_tab, (size_t) kMaxClouds * 6);
@@ -1163,20 +1131,20 @@ int agh_set_cloud_cam_origins(agh_ctx* ctx, const double* cam_origin, int32_t n_
       return rc;
   }
   if (!c->h_cam_tab)
-    HIPCHK(c, hipHostMalloc((void**) &c->h_cam_tab, sizeof(double) * kMaxClouds * 6));
+    AGH_HIPCHK(c, hipHostMalloc((void**) &c->h_cam_tab, sizeof(double) * kMaxClouds * 6));
   if (!c->cam_tab_up)
-    HIPCHK(c, hipEventCreateWithFlags(&c->cam_tab_up, hipEventDisableTiming));
+    AGH_HIPCHK(c, hipEventCreateWithFlags(&c->cam_tab_up, hipEventDisableTiming));
   else if (c->cam_tab_async)
   {
-    HIPCHK(c, hipEventSynchronize(c->cam_tab_up));  // (the previous table's upload may still read the staging)
+    AGH_HIPCHK(c, hipEventSynchronize(c->cam_tab_up));  // (the previous table's upload may still read the staging)
     c->cam_tab_async = false;
   }
   c->cam_tab_rows = 0;  // (no table until the new one is on its way)
   std::memcpy(c->h_cam_tab, cam_origin, sizeof(double) * 6 * (size_t) n_clouds);
   // in order behind every search already queued on the context's stream (they keep the table they were launched with) and in
   // front of the next one; a search on another stream waits for the event first (order_after_cam_table)
-  HIPCHK(c, hipMemcpyAsync(c->d_cam_tab, c->h_cam_tab, sizeof(double) * 6 * (size_t) n_clouds, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->cam_tab_up, c->stream));
+  AGH_HIPCHK(c, hipMemcpyAsync(c->d_cam_tab, c->h_cam_tab, sizeof(double) * 6 * (size_t) n_clouds, hipMemcpyHostToDevice, c->stream));
+  AGH_HIPCHK(c, hipEventRecord(c->cam_tab_up, c->stream));
   c->cam_tab_async = true;
   c->cam_tab_rows = n_clouds;
   return AGH_OK;
@@ -1218,10 +1186,10 @@ int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_s
   }
   if (cam_table_mismatch(c, "agh_find_hands", c->n_clouds))
     return AGH_ERR_INVALID_ARGUMENT;
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t) hip_stream : c->stream;
-  HIPCHK(c, order_after_cloud(c, st));
-  HIPCHK(c, order_after_cam_table(c, st));
+  AGH_HIPCHK(c, order_after_cloud(c, st));
+  AGH_HIPCHK(c, order_after_cam_table(c, st));
   const int64_t S = n_samples;
   const int64_t chunk = kNormalsChunk;  // all-points pass batch
   int rc = ensure_call_buffers(c, std::max<int64_t>(S, calculates_antipodal ? std::min<int64_t>(c->n, chunk) : 0));
@@ -1244,9 +1212,9 @@ int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_s
   c->d_nout_last = d_n_out;
   if (S == 0 || c->n == 0)
   {
-    HIPCHK(c, hipMemsetAsync(c->d_flags, 0, 8 * sizeof(int32_t), st));
+    AGH_HIPCHK(c, hipMemsetAsync(c->d_flags, 0, 8 * sizeof(int32_t), st));
     c->zero_flags_pending = false;
-    HIPCHK(c, hipMemsetAsync(d_n_out, 0, sizeof(int64_t), st));
+    AGH_HIPCHK(c, hipMemsetAsync(d_n_out, 0, sizeof(int64_t), st));
     c->last_s = 0;
     return AGH_OK;
   }
@@ -1259,7 +1227,7 @@ int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_s
         return rc;
       c->normals_cap = c->n;
     }
-    HIPCHK(c, hipMemsetAsync(c->d_normals, 0, sizeof(double) * 3 * c->n, st));
+    AGH_HIPCHK(c, hipMemsetAsync(c->d_normals, 0, sizeof(double) * 3 * c->n, st));
     if ((rc = normals_pass(c, 0, c->n, st)) != AGH_OK)
     {
       c->err = "normals pass launch failed";
@@ -1275,7 +1243,7 @@ int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_s
   }
   if (c->debug_stop_moments || (c->debug_stop_frame && c->debug_stop_frame < 5))
   {
-    HIPCHK(c, hipMemsetAsync(d_n_out, 0, sizeof(int64_t), st));
+    AGH_HIPCHK(c, hipMemsetAsync(d_n_out, 0, sizeof(int64_t), st));
     return AGH_OK;
   }
 #ifdef AGH_DEBUG_HOOKS
@@ -1290,7 +1258,7 @@ int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_s
   }
   if (c->debug_stop_sweep && c->debug_stop_sweep < 10)
   {
-    HIPCHK(c, hipMemsetAsync(d_n_out, 0, sizeof(int64_t), st));
+    AGH_HIPCHK(c, hipMemsetAsync(d_n_out, 0, sizeof(int64_t), st));
     return AGH_OK;
   }
   rc = compact_hypotheses(c, S, d_out, cap, d_n_out, st);
@@ -1306,8 +1274,8 @@ int agh_find_hands_device(agh_ctx* ctx, const int32_t* d_sample_idx, int64_t n_s
 static int check_flags(Ctx* c, hipStream_t st)
 {
   int32_t flags[8];
-  HIPCHK(c, hipMemcpyAsync(flags, c->d_flags, sizeof(flags), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  AGH_HIPCHK(c, hipMemcpyAsync(flags, c->d_flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipStreamSynchronize(st));
   return flags_to_status(c, flags);
 }
 
@@ -1418,7 +1386,7 @@ int agh_find_hands(agh_ctx* ctx, const int32_t* sample_idx, int64_t n_samples, i
     }
   if (cam_table_mismatch(c, "agh_find_hands", c->n_clouds))
     return AGH_ERR_INVALID_ARGUMENT;
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   // size the buffers for everything the device call will need, so that it does not reallocate d_out_own under us
   int rc = ensure_call_buffers(c, std::max<int64_t>(n_samples, calculates_antipodal ? std::min<int64_t>(c->n, kNormalsChunk) : 0));
   if (rc != AGH_OK)
@@ -1444,7 +1412,7 @@ int agh_find_hands(agh_ctx* ctx, const int32_t* sample_idx, int64_t n_samples, i
   if (n_samples > 0)
   {
     std::memcpy(h_idx, sample_idx, sizeof(int32_t) * (size_t) n_samples);
-    HIPCHK(c, hipMemcpyAsync(d_idx, h_idx, sizeof(int32_t) * n_samples, hipMemcpyHostToDevice, c->stream));
+    AGH_HIPCHK(c, hipMemcpyAsync(d_idx, h_idx, sizeof(int32_t) * n_samples, hipMemcpyHostToDevice, c->stream));
   }
   int64_t n = 0;
   for (int attempt = 0; attempt < 3; attempt++)  // (AGH_ERR_RETRY: the context has enabled the larger classes; then, once, the 6144 class)
@@ -1461,7 +1429,7 @@ int agh_find_hands(agh_ctx* ctx, const int32_t* sample_idx, int64_t n_samples, i
     c->mirror = HostMirror{ nullptr, 0, nullptr };
     if (rc == AGH_OK)
     {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+      AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
       int32_t flags[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
       if (hdr[0] >= 0)
       {
@@ -1470,8 +1438,8 @@ int agh_find_hands(agh_ctx* ctx, const int32_t* sample_idx, int64_t n_samples, i
       }
       else  // no header was written: read the count and the error word the slow way
       {
-        HIPCHK(c, hipMemcpy(flags, c->d_flags, sizeof(flags), hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(&n, c->d_nout, sizeof(int64_t), hipMemcpyDeviceToHost));
+        AGH_HIPCHK(c, hipMemcpy(flags, c->d_flags, sizeof(flags), hipMemcpyDeviceToHost));
+        AGH_HIPCHK(c, hipMemcpy(&n, c->d_nout, sizeof(int64_t), hipMemcpyDeviceToHost));
       }
       rc = flags_to_status(c, flags);
     }
@@ -1493,7 +1461,7 @@ int agh_find_hands(agh_ctx* ctx, const int32_t* sample_idx, int64_t n_samples, i
   if (from_pin > 0)
     std::memcpy(out, h_rec, sizeof(agh_hypothesis) * (size_t) from_pin);
   if (n > from_pin)  // (lists beyond the mirror's room: the rest comes from the device copy)
-    HIPCHK(c, hipMemcpy(out + from_pin, c->d_out_own + from_pin, sizeof(agh_hypothesis) * (size_t) (n - from_pin), hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(out + from_pin, c->d_out_own + from_pin, sizeof(agh_hypothesis) * (size_t) (n - from_pin), hipMemcpyDeviceToHost));
   return AGH_OK;
 }
 
@@ -1502,8 +1470,8 @@ int agh_synchronize(agh_ctx* ctx)
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipDeviceSynchronize());
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipDeviceSynchronize());
   c->cam_tab_async = false;  // (an upload of agh_set_cloud_cam_origins has landed)
   if (c->loc.active)  // (allowed mid-chain: it waits; the chain's flags and counts are agh_localize_end's to read)
     return AGH_OK;
@@ -1552,9 +1520,9 @@ int agh_get_frames(agh_ctx* ctx, agh_frame* out, int64_t cap)
   if (refuse_mid_chain(c, "agh_get_frames"))
     return AGH_ERR_STATE;
   const int64_t n = std::min<int64_t>(cap, c->last_s);
-  HIPCHK(c, hipDeviceSynchronize());
+  AGH_HIPCHK(c, hipDeviceSynchronize());
   if (n > 0)
-    HIPCHK(c, hipMemcpy(out, c->d_frames, sizeof(agh_frame) * n, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(out, c->d_frames, sizeof(agh_frame) * n, hipMemcpyDeviceToHost));
   return (int) n;
 }
 
@@ -1566,9 +1534,9 @@ int agh_get_neighbor_counts(agh_ctx* ctx, int32_t* n_taubin, int32_t* n_hands, i
   if (refuse_mid_chain(c, "agh_get_neighbor_counts"))
     return AGH_ERR_STATE;
   const int64_t n = std::min<int64_t>(cap, c->last_s);
-  HIPCHK(c, hipDeviceSynchronize());
+  AGH_HIPCHK(c, hipDeviceSynchronize());
   if (n > 0 && n_taubin)
-    HIPCHK(c, hipMemcpy(n_taubin, c->d_nt, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(n_taubin, c->d_nt, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
   if (n > 0 && n_hands)  // counted on demand: the sweep only visits the part of the ball the hand can occupy
   {
     if (ball_counts(c, n, c->stream) != AGH_OK)
@@ -1576,10 +1544,10 @@ int agh_get_neighbor_counts(agh_ctx* ctx, int32_t* n_taubin, int32_t* n_hands, i
       c->err = "k_ball_count launch failed";
       return AGH_ERR_HIP;
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   if (n > 0 && n_hands)
-    HIPCHK(c, hipMemcpy(n_hands, c->d_nh, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(n_hands, c->d_nh, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
   return (int) n;
 }
 
@@ -1596,9 +1564,9 @@ int agh_get_normals(agh_ctx* ctx, double* normals, int64_t cap_points)
     return AGH_ERR_STATE;
   }
   const int64_t n = std::min<int64_t>(cap_points, c->n);
-  HIPCHK(c, hipDeviceSynchronize());
+  AGH_HIPCHK(c, hipDeviceSynchronize());
   if (n > 0)
-    HIPCHK(c, hipMemcpy(normals, c->d_normals, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(normals, c->d_normals, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
   return (int) n;
 }
 
@@ -1609,8 +1577,8 @@ int agh_set_profile(agh_ctx* ctx, int32_t level)
   Ctx* c = &ctx->c;
   if (refuse_mid_chain(c, "agh_set_profile"))
     return AGH_ERR_STATE;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipDeviceSynchronize());
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipDeviceSynchronize());
   c->p.profile = level;
   c->prof_calls = 0;
   c->ev_used = 0;
@@ -1629,7 +1597,7 @@ int agh_get_timing(agh_ctx* ctx, agh_timing* out)
   std::memset(c->timing_counts, 0, sizeof(c->timing_counts));
   if (!c->p.profile || c->ev_used < 2)
     return AGH_OK;
-  HIPCHK(c, hipEventSynchronize(c->ev[c->ev_used - 1]));
+  AGH_HIPCHK(c, hipEventSynchronize(c->ev[c->ev_used - 1]));
   int k = 0;
   for (int i = 1; i < c->ev_used; i++)
   {
@@ -1674,11 +1642,11 @@ int agh_get_grid_stats(agh_ctx* ctx, int64_t* stats, int32_t cap)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
   unsigned miss = 0;
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   if (c->d_grid_miss && c->grid_miss_zeroed)
   {
-    HIPCHK(c, hipDeviceSynchronize());  // (the context's device: its builds may have run on any of the caller's streams)
-    HIPCHK(c, hipMemcpy(&miss, c->d_grid_miss, sizeof(unsigned), hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipDeviceSynchronize());  // (the context's device: its builds may have run on any of the caller's streams)
+    AGH_HIPCHK(c, hipMemcpy(&miss, c->d_grid_miss, sizeof(unsigned), hipMemcpyDeviceToHost));
   }
   const int64_t v[3] = { c->grid_builds, c->grid_cold_builds, (int64_t) miss };
   int k = 0;
@@ -1703,9 +1671,9 @@ int agh_get_grid_desc(agh_ctx* ctx, int32_t cloud, double mn[3], double* cell, i
     return AGH_ERR_NO_CLOUD;
   }
   GridDesc g;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipDeviceSynchronize());  // (as agh_get_grid_stats: the build may have run on any of the caller's streams)
-  HIPCHK(c, hipMemcpy(&g, c->d_desc + cloud, sizeof(GridDesc), hipMemcpyDeviceToHost));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipDeviceSynchronize());  // (as agh_get_grid_stats: the build may have run on any of the caller's streams)
+  AGH_HIPCHK(c, hipMemcpy(&g, c->d_desc + cloud, sizeof(GridDesc), hipMemcpyDeviceToHost));
   for (int a = 0; a < 3; a++)
   {
     if (mn)

@@ -546,17 +546,6 @@ int64_t selftest_math(Ctx* c, int64_t n, uint64_t seed)
 // ---- C ABI: SVM + classify + introspection -------------------------------------------------------------------
 using namespace agh;
 
-#define HIPCHK2(ctx, expr)                                                                            \
-  do                                                                                                  \
-  {                                                                                                   \
-    hipError_t e__ = (expr);                                                                          \
-    if (e__ != hipSuccess)                                                                            \
-    {                                                                                                 \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                                \
-      return AGH_ERR_HIP;                                                                             \
-    }                                                                                                 \
-  } while (0)
-
 extern "C" {
 
 int agh_load_svm(agh_ctx* ctx, const float* weights, int32_t n_weights, double rho)
@@ -571,8 +560,8 @@ int agh_load_svm(agh_ctx* ctx, const float* weights, int32_t n_weights, double r
     c->err = "agh_load_svm: the HOG descriptor has 3528 entries (2 windows x 49 blocks x 36)";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  HIPCHK2(c, hipSetDevice(c->device));
-  HIPCHK2(c, hipMemcpy(c->d_svm_w, weights, sizeof(float) * 3528, hipMemcpyHostToDevice));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipMemcpy(c->d_svm_w, weights, sizeof(float) * 3528, hipMemcpyHostToDevice));
   c->svm_rho = rho;
   c->svm_general = false;
   c->svm_kernel = AGH_SVM_LINEAR;
@@ -710,7 +699,7 @@ int agh_classify_device(agh_ctx* ctx, uint8_t* d_keep, void* hip_stream)
     c->err = "agh_classify: call agh_find_hands first";
     return AGH_ERR_STATE;
   }
-  HIPCHK2(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t) hip_stream : c->stream;
   return hog_svm(c, std::min<int64_t>(c->last_s * 8, c->last_cap), d_keep, st);
 }
@@ -735,18 +724,7 @@ int agh_classify(agh_ctx* ctx, uint8_t* keep, int64_t cap, int64_t* n_kept)
     c->err = "agh_classify: keep buffer too small";
     return AGH_ERR_CAPACITY;
   }
-  if (n > c->keep_cap)
-  {
-    if (c->d_keep)
-      (void) hipFree(c->d_keep);
-    if (c->d_svm_sums)
-      (void) hipFree(c->d_svm_sums);
-    c->d_keep = nullptr;
-    c->d_svm_sums = nullptr;
-    HIPCHK2(c, hipMalloc((void**) &c->d_keep, n));
-    HIPCHK2(c, hipMalloc((void**) &c->d_svm_sums, n * sizeof(double)));
-    c->keep_cap = n;
-  }
+  AGH_HIPCHK(c, ensure_keep_buffers(c, n));
   if (n == 0)
     return AGH_OK;
   // K3 writes the flags straight into pinned host memory of the context: no read-back copy behind the kernel
@@ -757,14 +735,14 @@ int agh_classify(agh_ctx* ctx, uint8_t* keep, int64_t cap, int64_t* n_kept)
     c->h_pin_keep = nullptr;
     c->h_pin_keep_cap = 0;
     void* p = nullptr;
-    HIPCHK2(c, hipHostMalloc(&p, (size_t) std::max<int64_t>(n, 16384), hipHostMallocDefault));
+    AGH_HIPCHK(c, hipHostMalloc(&p, (size_t) std::max<int64_t>(n, 16384), hipHostMallocDefault));
     c->h_pin_keep = static_cast<uint8_t*>(p);
     c->h_pin_keep_cap = std::max<int64_t>(n, 16384);
   }
   int rc = agh_classify_device(ctx, c->h_pin_keep, nullptr);
   if (rc != AGH_OK)
     return rc;
-  HIPCHK2(c, hipStreamSynchronize(c->stream));
+  AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
   std::memcpy(keep, c->h_pin_keep, (size_t) n);
   int64_t k = 0;
   for (int64_t i = 0; i < n; i++)
@@ -789,13 +767,13 @@ int agh_get_packed_images(agh_ctx* ctx, uint32_t* images, int64_t cap_hyp)
   const int64_t n = std::min<int64_t>(cap_hyp, c->last_nout);
   if (n == 0)
     return 0;
-  HIPCHK2(c, hipSetDevice(c->device));
-  HIPCHK2(c, hipDeviceSynchronize());
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipDeviceSynchronize());
   // the images sit in the per-sample slots; hypothesis h is slot d_slot_index[h] (the compaction's record)
   std::vector<int32_t> slot((size_t) n);
   std::vector<uint32_t> words((size_t) c->last_s * 8 * kImageWords);
-  HIPCHK2(c, hipMemcpy(slot.data(), c->d_slot_index, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  HIPCHK2(c, hipMemcpy(words.data(), c->d_images, words.size() * 4, hipMemcpyDeviceToHost));
+  AGH_HIPCHK(c, hipMemcpy(slot.data(), c->d_slot_index, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  AGH_HIPCHK(c, hipMemcpy(words.data(), c->d_images, words.size() * 4, hipMemcpyDeviceToHost));
   for (int64_t h = 0; h < n; h++)
     std::memcpy(images + h * kImageWords, &words[(size_t) slot[(size_t) h] * kImageWords], kImageWords * 4);
   return (int) n;
@@ -820,7 +798,7 @@ int agh_classify_images(agh_ctx* ctx, const uint32_t* images, int64_t n, uint8_t
     c->err = "agh_classify_images: more than 2^24 images in one call";
     return AGH_ERR_CAPACITY;
   }
-  HIPCHK2(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   if (n > c->cls_images_cap)
   {
     for (void* p : { (void*) c->d_cls_images, (void*) c->d_cls_keep, (void*) c->d_cls_sums })
@@ -831,13 +809,13 @@ int agh_classify_images(agh_ctx* ctx, const uint32_t* images, int64_t n, uint8_t
     c->d_cls_sums = nullptr;
     c->cls_images_cap = 0;
     const int64_t cap = std::max<int64_t>(n, 1024);
-    HIPCHK2(c, hipMalloc((void**) &c->d_cls_images, (size_t) cap * kImageWords * 4));
-    HIPCHK2(c, hipMalloc((void**) &c->d_cls_keep, (size_t) cap));
-    HIPCHK2(c, hipMalloc((void**) &c->d_cls_sums, (size_t) cap * sizeof(double)));
+    AGH_HIPCHK(c, hipMalloc((void**) &c->d_cls_images, (size_t) cap * kImageWords * 4));
+    AGH_HIPCHK(c, hipMalloc((void**) &c->d_cls_keep, (size_t) cap));
+    AGH_HIPCHK(c, hipMalloc((void**) &c->d_cls_sums, (size_t) cap * sizeof(double)));
     c->cls_images_cap = cap;
   }
   hipStream_t st = c->stream;
-  HIPCHK2(c, hipMemcpyAsync(c->d_cls_images, images, (size_t) n * kImageWords * 4, hipMemcpyHostToDevice, st));
+  AGH_HIPCHK(c, hipMemcpyAsync(c->d_cls_images, images, (size_t) n * kImageWords * 4, hipMemcpyHostToDevice, st));
   int rc = AGH_OK;
   if (c->svm_general)
   {
@@ -847,7 +825,7 @@ int agh_classify_images(agh_ctx* ctx, const uint32_t* images, int64_t n, uint8_t
         (void) hipFree(c->d_cls_desc);
       c->d_cls_desc = nullptr;
       c->cls_desc_cap = 0;
-      HIPCHK2(c, hipMalloc((void**) &c->d_cls_desc, (size_t) n * 3528 * sizeof(float)));
+      AGH_HIPCHK(c, hipMalloc((void**) &c->d_cls_desc, (size_t) n * 3528 * sizeof(float)));
       c->cls_desc_cap = n;
     }
     rc = hog_images(c, c->d_cls_images, nullptr, n, c->d_cls_desc, st);
@@ -866,10 +844,10 @@ int agh_classify_images(agh_ctx* ctx, const uint32_t* images, int64_t n, uint8_t
     c->err = "agh_classify_images: launch failed";
     return rc;
   }
-  HIPCHK2(c, hipMemcpyAsync(keep, c->d_cls_keep, (size_t) n, hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipMemcpyAsync(keep, c->d_cls_keep, (size_t) n, hipMemcpyDeviceToHost, st));
   if (sums)
-    HIPCHK2(c, hipMemcpyAsync(sums, c->d_cls_sums, (size_t) n * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK2(c, hipStreamSynchronize(st));
+    AGH_HIPCHK(c, hipMemcpyAsync(sums, c->d_cls_sums, (size_t) n * sizeof(double), hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipStreamSynchronize(st));
   return AGH_OK;
 }
 
@@ -886,13 +864,13 @@ int agh_get_images(agh_ctx* ctx, uint8_t* images, int64_t cap_hyp)
     return AGH_ERR_STATE;
   }
   const int64_t n = std::min<int64_t>(cap_hyp, c->last_nout);
-  HIPCHK2(c, hipDeviceSynchronize());
+  AGH_HIPCHK(c, hipDeviceSynchronize());
   std::vector<int32_t> slot(n);
   std::vector<uint32_t> words((size_t) c->last_s * 8 * kImageWords);
   if (n > 0)
   {
-    HIPCHK2(c, hipMemcpy(slot.data(), c->d_slot_index, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    HIPCHK2(c, hipMemcpy(words.data(), c->d_images, words.size() * 4, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(slot.data(), c->d_slot_index, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(words.data(), c->d_images, words.size() * 4, hipMemcpyDeviceToHost));
   }
   for (int64_t h = 0; h < n; h++)
   {
@@ -922,9 +900,9 @@ int agh_get_hog(agh_ctx* ctx, float* desc, double* sums, int64_t cap_hyp)
   float* d_desc = nullptr;
   double* d_sums = nullptr;
   uint8_t* d_keep = nullptr;
-  HIPCHK2(c, hipMalloc((void**) &d_desc, (size_t) c->last_nout * 3528 * sizeof(float)));
-  HIPCHK2(c, hipMalloc((void**) &d_sums, (size_t) c->last_nout * sizeof(double)));
-  HIPCHK2(c, hipMalloc((void**) &d_keep, (size_t) c->last_nout));
+  AGH_HIPCHK(c, hipMalloc((void**) &d_desc, (size_t) c->last_nout * 3528 * sizeof(float)));
+  AGH_HIPCHK(c, hipMalloc((void**) &d_sums, (size_t) c->last_nout * sizeof(double)));
+  AGH_HIPCHK(c, hipMalloc((void**) &d_keep, (size_t) c->last_nout));
   float* save_desc = c->d_desc_out;
   double* save_sums = c->d_svm_sums;
   c->d_desc_out = d_desc;

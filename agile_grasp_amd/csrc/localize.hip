@@ -9,23 +9,11 @@
 
 using namespace agh;
 
-#define HIPCHK(ctx, expr)                                                                             \
-  do                                                                                                  \
-  {                                                                                                   \
-    hipError_t e__ = (expr);                                                                          \
-    if (e__ != hipSuccess)                                                                            \
-    {                                                                                                 \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                                \
-      return AGH_ERR_HIP;                                                                             \
-    }                                                                                                 \
-  } while (0)
-
-extern "C" {
-
 namespace
 {
+// (the two kernels keep C names: the traces under profiles/ know them by these)
 // One sample per stratum of the cloud (include/agh.h, agh_localize); the point count is read on the device.
-__global__ void k_draw_samples(const int* __restrict__ cloud_off, int n_clouds, int S, unsigned long long seed,
+extern "C" __global__ void k_draw_samples(const int* __restrict__ cloud_off, int n_clouds, int S, unsigned long long seed,
   int32_t* __restrict__ out, int32_t* __restrict__ host_out)
 {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -38,56 +26,20 @@ __global__ void k_draw_samples(const int* __restrict__ cloud_off, int n_clouds, 
     host_out[k] = v;
 }
 // The hands Learning::classify kept (svm_keep; all of them if !use_keep), in list order (learning.cpp:236-243), as the handle
-// search's input -- and a second time into pinned host memory.  One work-group: an ordered compaction is a scan.  box.on (a
-// chain with filters_boundaries and no classifier): the hands Localization::filterHands drops are left out too (with the
-// classifier their svm_keep is 0 already).
+// search's input -- and a second time into pinned host memory.  One work-group around compact_kept_records (agh_internal.h).
+// box.on (a chain with filters_boundaries and no classifier): the hands Localization::filterHands drops are left out too (with
+// the classifier their svm_keep is 0 already).
 // host_counts: [4] hypotheses, [5] kept, [6] the search's error word.
-__global__ __launch_bounds__(1024) void k_compact_kept(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
+extern "C" __global__ __launch_bounds__(1024) void k_compact_kept(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
   int64_t cap_in, int use_keep, BoundaryBox box, agh_hypothesis* __restrict__ out, int out_cap, int* __restrict__ n_out,
   agh_hypothesis* __restrict__ host_out, int host_cap, int* __restrict__ host_counts, const int32_t* __restrict__ flags)
 {
-  constexpr int kList = 8192;  // (the handle search takes no more)
-  __shared__ int src[kList];   // position in the output -> position in the input
+  __shared__ int src[kCompactList];
   __shared__ int wsum[16];
   __shared__ int carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t n = min(*n_in, cap_in);
-  if (tid == 0)
-    carry = 0;
-  __syncthreads();
-  for (int64_t b0 = 0; b0 < n; b0 += 1024)
-  {
-    const int64_t i = b0 + tid;
-    const bool keep = i < n && (!use_keep || in[i].svm_keep != 0) && !(box.on && near_workspace_boundary(in[i].surface, box.ws));
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0)
-      wsum[wave] = __popcll(m);
-    __syncthreads();
-    int base = carry, tot = 0;
-    for (int w = 0; w < 16; w++)
-    {
-      base += w < wave ? wsum[w] : 0;
-      tot += wsum[w];
-    }
-    const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-    if (keep && pos < kList)
-      src[pos] = (int) i;
-    __syncthreads();
-    if (tid == 0)
-      carry += tot;
-    __syncthreads();
-  }
-  const int K = carry, kw = min(K, min(out_cap, kList));
-  // ten threads per record, sixteen bytes each: every record leaves as one 160-byte run, to the device and to the host
-  for (int t = tid; t < kw * 10; t += 1024)
-  {
-    const int k = t / 10, part = t - 10 * k;
-    const uint4 v = reinterpret_cast<const uint4*>(in + src[k])[part];
-    reinterpret_cast<uint4*>(out + k)[part] = v;
-    if (host_out && k < host_cap)
-      reinterpret_cast<uint4*>(host_out + k)[part] = v;
-  }
-  if (tid == 0)
+  const int K = compact_kept_records(in, 0, n, use_keep, box.on, box.ws, src, wsum, &carry, out, out_cap, host_out, host_cap, 0);
+  if (threadIdx.x == 0)
   {
     *n_out = K;
     if (host_counts)
@@ -100,162 +52,141 @@ __global__ __launch_bounds__(1024) void k_compact_kept(const agh_hypothesis* __r
 }
 }  // namespace
 
-// agh_localize = agh_localize_begin (everything queued) + agh_localize_end (the one synchronisation, the results, the rare
-// repeats).  Between the two the caller may stage the NEXT capture (agh_localize_stage: upload on a second stream into a second
-// raw buffer, under this cloud's kernels), which the next begin adopts instead of uploading.  One chain is in flight at a time:
-// the context's device buffers, pinned mirrors and host-side cloud state are single.
-static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int64_t stride_bytes, int64_t n,
-  const agh_localize_params* lp);
-static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result);
+// ---- shared with localize_batch.hip (declared in agh_internal.h) ----
 
-static int localize_check_outputs(Ctx* c, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap)
+// The NEXT chain's captures up, beside whatever runs on the context's stream: packed end to end (device_stride's rule) into the
+// context's second raw buffer, on a stream of its own.  A pageable source makes the call last as long as its copies (the kernels of
+// the chain in flight run meanwhile: that is the overlap); a pinned one is read asynchronously and must stay valid until the copy
+// is done: until the begin that adopts (or drops) the set has returned for agh_localize_stage, until the matching end for
+// agh_localize_batch_stage (include/agh.h).  The callers have checked the arguments.
+int stage_captures(agh_ctx* ctx, const char* who, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int C,
+  bool as_batch)
 {
-  if (handle_cap < 0 || idx_cap < 0 || hands_cap < 0 || (handle_cap > 0 && !handles_out) || (idx_cap > 0 && !inlier_idx_out) ||
-      (hands_cap > 0 && !hands_out))
-  {
-    c->err = "agh_localize: bad arguments (see include/agh.h)";
-    return AGH_ERR_INVALID_ARGUMENT;
-  }
-  return AGH_OK;
-}
-
-int agh_localize(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp,
-  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
-  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
-{
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  if (result)
-    *result = agh_localize_result{ 0, 0, 0, 0, 0 };
-  int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
-  if (rc == AGH_OK)
-    rc = localize_begin_impl(ctx, xyz, false, stride_bytes, n, lp);
-  if (rc != AGH_OK)
-    return rc;
-  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
-}
-
-int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp,
-  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
-  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
-{
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  if (result)
-    *result = agh_localize_result{ 0, 0, 0, 0, 0 };
-  int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
-  if (rc == AGH_OK)
-    rc = localize_begin_impl(ctx, d_xyz, true, stride_bytes, n, lp);
-  if (rc != AGH_OK)
-    return rc;
-  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
-}
-
-int agh_localize_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp)
-{
-  return localize_begin_impl(ctx, xyz, false, stride_bytes, n, lp);
-}
-
-int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
-{
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  if (result)
-    *result = agh_localize_result{ 0, 0, 0, 0, 0 };
   Ctx* c = &ctx->c;
-  if (!c->loc.active)
-  {
-    c->err = "agh_localize_end: no agh_localize_begin in flight";
-    return AGH_ERR_STATE;
-  }
-  if (c->loc.batch)
-  {
-    c->err = "agh_localize_end: the chain in flight is a batch's (agh_localize_batch_end collects it)";
-    return AGH_ERR_STATE;
-  }
-  const int rc = localize_check_outputs(c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
-  if (rc != AGH_OK)
-  {
-    // (the chain is queued: drain it, leave the context as a failed call does)
-    (void) hipStreamSynchronize(c->stream);
-    c->loc.active = false;
-    if (c->n_is_bound)
-    {
-      c->n_is_bound = false;
-      c->has_cloud = false;
-      c->n = 0;
-      c->cloud_off_on_device = false;
-    }
+  LocalizeState& L = c->loc;
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = ensure_stage_stream(c, who))
     return rc;
-  }
-  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
-}
-
-// The NEXT capture up, beside the chain in flight: into the context's second raw buffer, on a stream of its own.  A pageable
-// source makes the call last as long as the copy (the kernels of the chain in flight run meanwhile: that is the overlap); a
-// pinned one returns at once.  The source must stay valid until the copy is done: until the agh_localize_begin that adopts the
-// capture has returned (it makes the chain wait for the copy; the copy itself is then behind a host-side event wait).
-int agh_localize_stage(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n)
-{
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  Ctx* c = &ctx->c;
-  if (n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz))
-  {
-    c->err = "agh_localize_stage: bad arguments";
-    return AGH_ERR_INVALID_ARGUMENT;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = ensure_stage_stream(c, "agh_localize_stage"))
-    return rc;
-  // A failure from here on leaves nothing staged -- and an earlier capture's copy may still be reading its (pinned) source, with no
+  // A failure from here on leaves nothing staged -- and an earlier set's copies may still be reading their (pinned) sources, with no
   // begin left to wait for stage_done: the stage stream is drained before the flag comes down.
-  auto stage_fail = [&](int code) {
+  auto stage_fail = [c](int code) {
     (void) hipStreamSynchronize(c->stage_stream);
     c->loc.staged = false;
     return code;
   };
-#define STAGE_HIPCHK(expr)                                                \
-  do                                                                      \
-  {                                                                       \
-    hipError_t e__ = (expr);                                              \
-    if (e__ != hipSuccess)                                                \
-    {                                                                     \
-      c->err = std::string(#expr) + ": " + hipGetErrorString(e__);        \
-      return stage_fail(AGH_ERR_HIP);                                     \
-    }                                                                     \
-  } while (0)
-  const bool as_is = stride_bytes <= 32;
-  const int64_t dev_stride = as_is ? stride_bytes : 12;
-  const int64_t need = n * (dev_stride / 4);
+  int64_t need = 0;
+  for (int k = 0; k < C; k++)
+    need += n[k] * (device_stride(stride_bytes[k]) / 4);
   if (need > c->stage_cap || !c->d_stage_xyz)
   {
     // (nobody reads this buffer now: the chain in flight reads d_raw_xyz)
-    int rc;
-    if ((rc = dev_alloc(c, &c->d_stage_xyz, (size_t) std::max<int64_t>(need, 1))))
+    if (int rc = dev_alloc(c, &c->d_stage_xyz, (size_t) std::max<int64_t>(need, 1)))
       return stage_fail(rc);
     c->stage_cap = need;
     c->stage_read_set = false;
   }
-  if (c->stage_read_set)  // the last batch chain that read the buffer this copy overwrites (it has ended: see DESIGN.md)
-    STAGE_HIPCHK(hipStreamWaitEvent(c->stage_stream, c->stage_read, 0));
-  if (n > 0)
+  if (c->stage_read_set)  // the last batch chain that read the buffer these copies overwrite (it has ended: see DESIGN.md)
   {
-    if (as_is)
-      STAGE_HIPCHK(hipMemcpyAsync(c->d_stage_xyz, xyz, (size_t) (n * stride_bytes - (stride_bytes - 12)), hipMemcpyHostToDevice, c->stage_stream));
-    else
-      STAGE_HIPCHK(hipMemcpy2DAsync(c->d_stage_xyz, 12, xyz, (size_t) stride_bytes, 12, (size_t) n, hipMemcpyHostToDevice, c->stage_stream));
+    AGH_HIPCHK_OR(c, hipStreamWaitEvent(c->stage_stream, c->stage_read, 0), stage_fail(AGH_ERR_HIP));
   }
-  STAGE_HIPCHK(hipEventRecord(c->stage_done, c->stage_stream));
-#undef STAGE_HIPCHK
-  c->loc.staged = true;
-  c->loc.staged_captures = 0;
-  c->loc.staged_src = xyz;
-  c->loc.staged_stride = stride_bytes;
-  c->loc.staged_n = n;
+  // (whatever was staged before is replaced: its copies are ahead of these on the stage stream, so stage_done covers them too)
+  int64_t off = 0;
+  for (int k = 0; k < C; k++)
+  {
+    AGH_HIPCHK_OR(c, upload_capture(c->d_stage_xyz + off, xyz[k], stride_bytes[k], n[k], c->stage_stream), stage_fail(AGH_ERR_HIP));
+    off += n[k] * (device_stride(stride_bytes[k]) / 4);
+  }
+  AGH_HIPCHK_OR(c, hipEventRecord(c->stage_done, c->stage_stream), stage_fail(AGH_ERR_HIP));
+  L.staged_src.assign(xyz, xyz + C);
+  L.staged_stride.assign(stride_bytes, stride_bytes + C);
+  L.staged_n.assign(n, n + C);
+  L.staged_captures = as_batch ? C : 0;
+  L.staged = true;
+  return AGH_OK;
+}
+
+// The end of a chain over C captures, after its one synchronisation: attempt 0 is on the host (capture k's counts at
+// counts + k * count_stride: [0..3] the handle search's, [4..6] the compaction's).  The search once more for a capacity class
+// (on the cloud that is already there), the handle search once more for a walk the batched kernel declined -- requeue queues
+// either on the context's stream -- then the limits.  Errors are `who`'s, and capture k's if the chain labels its captures; bad:
+// a batch's per-capture flags of a sample index outside the capture (null: flags_to_status' text stands).
+int chain_collect(agh_ctx* ctx, const char* who, bool label_captures, int C, const int* counts, int count_stride, int64_t S_tot,
+  const int* bad, int (*requeue)(agh_ctx*, bool handles_only))
+{
+  Ctx* c = &ctx->c;
+  auto of = [&](int k) { return std::string(who) + (label_captures ? ": capture " + std::to_string(k) : std::string()) + ": "; };
+  bool handles_only = false;
+  int rc;
+  for (int attempt = 0;; attempt++)
+  {
+    if (attempt > 0)
+    {
+      if ((rc = requeue(ctx, handles_only)) != AGH_OK)
+        return chain_fail(c, rc);
+      AGH_HIPCHK_OR(c, hipStreamSynchronize(c->stream), chain_fail(c, AGH_ERR_HIP));
+    }
+    if (!handles_only)
+    {
+      int32_t flags[1] = { counts[6] };
+      rc = flags_to_status(c, flags);
+      if (rc == AGH_ERR_RETRY && attempt < 3)
+      {
+        // (the larger capacity classes are on now)
+        if ((rc = ensure_call_buffers(c, std::max<int64_t>(S_tot, 1))) != AGH_OK)
+          return rc;
+        continue;
+      }
+      if (rc == AGH_ERR_INVALID_ARGUMENT && (flags[0] & 4) && bad)
+        for (int k = 0; k < C; k++)
+          if (bad[k])
+          {
+            c->err = std::string(who) + ": a sample index of capture " + std::to_string(k) + " is outside its voxelised cloud";
+            break;
+          }
+      if (rc != AGH_OK)
+        return rc;
+    }
+    bool declined = false;
+    for (int k = 0; k < C; k++)
+    {
+      const int* h = counts + k * count_stride;
+      if (h[2] == 2 || h[5] > 8192)  // ([5]: the hands that survived the classifier and the boundary filter)
+      {
+        c->err = of(k) + "more than 8192 hands for the handle search (classify first, or search fewer samples)";
+        return AGH_ERR_CAPACITY;
+      }
+      declined |= h[3] != 0;  // a row of the pair matrix longer than a wave (see agh_find_handles)
+    }
+    c->handles_sequential = declined;
+    if (declined && !c->loc.with_sequential && attempt < 3)
+    {
+      handles_only = true;
+      continue;
+    }
+    break;
+  }
+  for (int k = 0; k < C; k++)
+    if (counts[k * count_stride + 2])
+    {
+      c->err = of(k) + "a seed hand has more than 2048 inliers";
+      return AGH_ERR_CAPACITY;
+    }
+  return AGH_OK;
+}
+
+// ---- agh_localize = agh_localize_begin (everything queued) + agh_localize_end (the one synchronisation, the results, the rare
+// repeats).  Between the two the caller may stage the NEXT capture (agh_localize_stage: upload on a second stream into a second
+// raw buffer, under this cloud's kernels), which the next begin adopts instead of uploading.  One chain is in flight at a time:
+// the context's device buffers, pinned mirrors and host-side cloud state are single. ----
+
+static int localize_check_outputs(Ctx* c, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap)
+{
+  if (bad_outputs(handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap))
+  {
+    c->err = "agh_localize: bad arguments (see include/agh.h)";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
   return AGH_OK;
 }
 
@@ -266,16 +197,13 @@ static int localize_queue(agh_ctx* ctx, bool handles_only)
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
   hipStream_t st = c->stream;
-  int* h_counts = reinterpret_cast<int*>(c->h_pin_handles);
-  agh_hypothesis* h_hands = reinterpret_cast<agh_hypothesis*>(c->h_pin_handles + 256);
-  agh_handle* h_handles = reinterpret_cast<agh_handle*>(h_hands + c->h_pin_handles_cap);
-  int32_t* h_hidx = reinterpret_cast<int32_t*>(h_handles + c->h_pin_handles_cap);
-  const HandleMirror hm{ h_handles, (int) c->h_pin_handles_cap, h_hidx, (int) c->h_pin_handles_cap, h_counts };
+  const HandlePins pin = handle_pins(c);
+  const HandleMirror hm{ pin.handles, (int) c->h_pin_handles_cap, pin.idx, (int) c->h_pin_handles_cap, pin.counts };
   int* d_hcount = c->d_h_counts + 4;  // (behind the HandleCounts record)
   const int64_t hand_bound = std::min<int64_t>(8 * L.S, 8192);
   int rc;
   for (int k = 0; k < (handles_only ? 4 : 8); k++)  // ([4..6], the search's counts, outlive a repeat of the handle search alone)
-    h_counts[k] = 0;
+    pin.counts[k] = 0;
   L.with_sequential = c->handles_sequential;
   if (!handles_only)
   {
@@ -288,8 +216,8 @@ static int localize_queue(agh_ctx* ctx, bool handles_only)
     if (L.classify && (rc = hog_svm(c, std::min<int64_t>(c->last_s * 8, c->last_cap), c->d_keep, st, ws)) != AGH_OK)
       return rc;
     hipLaunchKernelGGL(k_compact_kept, dim3(1), dim3(1024), 0, st, (const agh_hypothesis*) c->d_out_own, (const int64_t*) c->d_nout,
-      c->s_cap * 8, L.classify ? 1 : 0, boundary_box(L.classify ? nullptr : ws), c->d_h_hands, (int) hand_bound, d_hcount, h_hands,
-      (int) c->h_pin_handles_cap, h_counts, (const int32_t*) c->d_flags);
+      c->s_cap * 8, L.classify ? 1 : 0, boundary_box(L.classify ? nullptr : ws), c->d_h_hands, (int) hand_bound, d_hcount, pin.hands,
+      (int) c->h_pin_handles_cap, pin.counts, (const int32_t*) c->d_flags);
     if (hipGetLastError() != hipSuccess)
     {
       c->err = "k_compact_kept launch failed";
@@ -320,8 +248,8 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     c->err = "agh_localize_begin: an agh_localize_batch is running on this context";
     return AGH_ERR_STATE;
   }
-  if (!lp || n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz) || !(lp->cell_size > 0.0) ||
-      lp->size_left < 0 || lp->n_samples < 0 || lp->n_samples > (1 << 24) || lp->min_inliers < 1)
+  if (!lp || bad_capture(xyz, stride_bytes, n) || !(lp->cell_size > 0.0) || lp->size_left < 0 || lp->n_samples < 0 ||
+      lp->n_samples > (1 << 24) || lp->min_inliers < 1)
   {
     c->err = "agh_localize: bad arguments (see include/agh.h)";
     return AGH_ERR_INVALID_ARGUMENT;
@@ -343,31 +271,30 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     c->err = "agh_localize: this libm's acos is not monotone around the 0.34 rad thresholds";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   const int64_t S = lp->n_samples;
   hipStream_t st = c->stream;
   int rc;
   // ---- 1. raw cloud up (unless it is on the device already: agh_localize_device, which reads it in place with the caller's
   // stride -- or was staged: agh_localize_stage), voxelisation and grid build queued; the voxel count stays on the device when it
   // can ----
-  const bool as_is = stride_bytes <= 32;  // (as agh_preprocess)
-  const int64_t dev_stride = (as_is || xyz_on_device) ? stride_bytes : 12;
+  const int64_t dev_stride = xyz_on_device ? stride_bytes : device_stride(stride_bytes);
   const float* d_raw = xyz;
   if (!xyz_on_device)
   {
-    if (L.staged && L.staged_captures == 0 && L.staged_src == xyz && L.staged_stride == stride_bytes && L.staged_n == n && c->d_stage_xyz)
+    if (L.staged_is(&xyz, &stride_bytes, &n, 1, false) && c->d_stage_xyz)
     {
       // the capture is (or is about to be) in the second raw buffer: the two buffers change places, the chain waits for the copy
       swap_raw_buffers(c);
       L.staged = false;
-      HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
+      AGH_HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
     }
     else
     {
-      // (a staged capture that is not this one is dropped -- its copy may still be reading the caller's source: the chain waits
+      // (a staged set that is not this capture is dropped -- its copy may still be reading the caller's source: the chain waits
       // for it too, so that agh_localize_end's synchronisation covers it, as include/agh.h promises)
       if (L.staged)
-        HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
+        AGH_HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
       L.staged = false;
       const int64_t need = n * (dev_stride / 4);
       if (need > c->raw_cap || !c->d_raw_xyz)
@@ -376,13 +303,7 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
           return rc;
         c->raw_cap = need;
       }
-      if (n > 0)
-      {
-        if (as_is)
-          HIPCHK(c, hipMemcpyAsync(c->d_raw_xyz, xyz, (size_t) (n * stride_bytes - (stride_bytes - 12)), hipMemcpyHostToDevice, st));
-        else
-          HIPCHK(c, hipMemcpy2DAsync(c->d_raw_xyz, 12, xyz, (size_t) stride_bytes, 12, (size_t) n, hipMemcpyHostToDevice, st));
-      }
+      AGH_HIPCHK(c, upload_capture(c->d_raw_xyz, xyz, stride_bytes, n, st));
     }
     d_raw = c->d_raw_xyz;
   }
@@ -404,62 +325,24 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   if (rc != AGH_OK)
     return rc;
   c->cloud_async = false;  // (everything below is queued on the context's own stream, and the call ends with its synchronisation)
-  // a failure between the launches and the synchronisation, while the host only knows a BOUND of the cloud's size: the context
-  // must not be left believing the bound is the cloud
-  auto drop_bound_cloud = [&]() {
-    if (c->n_is_bound)
-    {
-      c->n_is_bound = false;
-      c->has_cloud = false;
-      c->n = 0;
-      c->cloud_off_on_device = false;
-    }
-  };
-  // (every error return from here on first drains the stream -- a pinned source may still be in flight, the caller may free it
-  // as soon as the call returns -- and drops the bound)
-  auto fail = [&](int code) {
-    (void) hipStreamSynchronize(st);
-    drop_bound_cloud();
-    return code;
-  };
-#define LOC_HIPCHK(expr)                                                  \
-  do                                                                      \
-  {                                                                       \
-    hipError_t e__ = (expr);                                              \
-    if (e__ != hipSuccess)                                                \
-    {                                                                     \
-      c->err = std::string(#expr) + ": " + hipGetErrorString(e__);        \
-      return fail(AGH_ERR_HIP);                                           \
-    }                                                                     \
-  } while (0)
+  // (every error return from here on is a chain_fail: the host may only know a BOUND of the cloud's size)
   // ---- 2. buffers for the bounds ----
   if ((rc = ensure_call_buffers(c, std::max<int64_t>(S, 1))) != AGH_OK)  // (S = 0: the later stages still want their buffers)
-    return fail(rc);
+    return chain_fail(c, rc);
   if (S > c->idx_cap || !c->d_idx_own)
   {
     if ((rc = dev_alloc(c, &c->d_idx_own, (size_t) std::max<int64_t>(S, 1024))))
-      return fail(rc);
+      return chain_fail(c, rc);
     c->idx_cap = std::max<int64_t>(S, 1024);
   }
   if ((rc = ensure_host_staging(c, S, 1024)) != AGH_OK)
-    return fail(rc);
+    return chain_fail(c, rc);
   int32_t* h_idx = reinterpret_cast<int32_t*>(c->h_pin + kPinHeaderBytes);
-  const int64_t hyp_bound = 8 * S;
-  const int64_t hand_bound = std::min<int64_t>(hyp_bound, 8192);
-  if ((rc = ensure_handle_buffers(c, hand_bound)) != AGH_OK)
-    return fail(rc);
-  if (lp->classify && c->s_cap * 8 > c->keep_cap)
+  if ((rc = ensure_handle_buffers(c, std::min<int64_t>(8 * S, 8192))) != AGH_OK)
+    return chain_fail(c, rc);
+  if (lp->classify)
   {
-    if (c->d_keep)
-      (void) hipFree(c->d_keep);
-    if (c->d_svm_sums)
-      (void) hipFree(c->d_svm_sums);
-    c->d_keep = nullptr;
-    c->d_svm_sums = nullptr;
-    c->keep_cap = 0;
-    LOC_HIPCHK(hipMalloc((void**) &c->d_keep, (size_t) (c->s_cap * 8)));
-    LOC_HIPCHK(hipMalloc((void**) &c->d_svm_sums, (size_t) (c->s_cap * 8) * sizeof(double)));
-    c->keep_cap = c->s_cap * 8;
+    AGH_HIPCHK_OR(c, ensure_keep_buffers(c, c->s_cap * 8), chain_fail(c, AGH_ERR_HIP));
   }
   // ---- 3. the sample list ----
   if (S > 0)
@@ -468,136 +351,78 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     {
       if (lp->sample_idx != h_idx)  // (a repeat of the whole call hands the pinned copy back in)
         std::memcpy(h_idx, lp->sample_idx, sizeof(int32_t) * (size_t) S);
-      LOC_HIPCHK(hipMemcpyAsync(c->d_idx_own, h_idx, sizeof(int32_t) * S, hipMemcpyHostToDevice, st));
+      AGH_HIPCHK_OR(c, hipMemcpyAsync(c->d_idx_own, h_idx, sizeof(int32_t) * S, hipMemcpyHostToDevice, st), chain_fail(c, AGH_ERR_HIP));
     }
     else
     {
       hipLaunchKernelGGL(k_draw_samples, dim3((unsigned) ((S + 255) / 256)), dim3(256), 0, st, (const int*) c->d_cloud_off, 1, (int) S,
         (unsigned long long) lp->sample_seed, c->d_idx_own, h_idx);
-      LOC_HIPCHK(hipGetLastError());
+      AGH_HIPCHK_OR(c, hipGetLastError(), chain_fail(c, AGH_ERR_HIP));
     }
   }
   // ---- 4. search -> classification -> kept hands -> handle search: queued; agh_localize_end waits ----
   if ((rc = localize_queue(ctx, false)) != AGH_OK)
-    return fail(rc);
+    return chain_fail(c, rc);
   L.active = true;
   return AGH_OK;
 }
-#undef LOC_HIPCHK
 
 static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
 {
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
-  hipStream_t st = c->stream;
   L.active = false;
   const int64_t S = L.S;
-  int* h_counts = reinterpret_cast<int*>(c->h_pin_handles);
-  agh_hypothesis* h_hands = reinterpret_cast<agh_hypothesis*>(c->h_pin_handles + 256);
-  agh_handle* h_handles = reinterpret_cast<agh_handle*>(h_hands + c->h_pin_handles_cap);
-  int32_t* h_hidx = reinterpret_cast<int32_t*>(h_handles + c->h_pin_handles_cap);
+  const HandlePins pin = handle_pins(c);
+  const int* h_counts = pin.counts;
   int32_t* h_idx = reinterpret_cast<int32_t*>(c->h_pin + kPinHeaderBytes);
-  auto drop_bound_cloud = [&]() {
-    if (c->n_is_bound)
-    {
-      c->n_is_bound = false;
-      c->has_cloud = false;
-      c->n = 0;
-      c->cloud_off_on_device = false;
-    }
-  };
   int rc;
-  bool handles_only = false;
-  for (int attempt = 0;; attempt++)
+  if (hipStreamSynchronize(c->stream) != hipSuccess)
   {
-    if (attempt > 0)  // (attempt 0 was queued by agh_localize_begin)
+    drop_bound_cloud(c);
+    c->err = "agh_localize: hipStreamSynchronize failed";
+    return AGH_ERR_HIP;
+  }
+  if (L.deferred)  // the descriptor of the speculative voxelisation, now on the host
+  {
+    L.deferred = false;
+    const VoxDesc h = *c->h_vox_desc;
+    L.nv = (int64_t) (h.n_vox[0] + h.n_vox[1]);
+    if (h.error)
     {
-      if ((rc = localize_queue(ctx, handles_only)) != AGH_OK)
+      // error 2: the lattice outgrew the bitmap kept from the previous cloud -- the whole call once more, sized from this
+      // cloud's lattice (the context then has no bitmap to speculate with: the preprocessing takes its own round trips).  The
+      // raw capture is still where the chain read it: in the context's raw buffer, or in the caller's device memory.
+      drop_bound_cloud(c);
+      if (h.error == 2 && !L.repeated)
       {
-        (void) hipStreamSynchronize(st);
-        drop_bound_cloud();
+        (void) hipFree(c->d_vox_bitmap);
+        c->d_vox_bitmap = nullptr;
+        c->vox_bitmap_cap = 0;
+        agh_localize_params lp = L.lp;
+        lp.sample_idx = L.explicit_samples ? h_idx : nullptr;
+        L.repeated = true;
+        rc = localize_begin_impl(ctx, L.d_raw, true, L.dev_stride, L.n_raw, &lp);
+        if (rc == AGH_OK)
+          rc = localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
+        c->loc.repeated = false;
         return rc;
       }
-    }
-    const bool with_sequential = L.with_sequential;
-    if (hipStreamSynchronize(st) != hipSuccess)
-    {
-      drop_bound_cloud();
-      c->err = "agh_localize: hipStreamSynchronize failed";
-      return AGH_ERR_HIP;
-    }
-    if (L.deferred)  // the descriptor of the speculative voxelisation, now on the host
-    {
-      L.deferred = false;
-      const VoxDesc h = *c->h_vox_desc;
-      L.nv = (int64_t) (h.n_vox[0] + h.n_vox[1]);
-      c->n_is_bound = false;
-      if (h.error)
-      {
-        // error 2: the lattice outgrew the bitmap kept from the previous cloud -- the whole call once more, sized from this
-        // cloud's lattice (the context then has no bitmap to speculate with: the preprocessing takes its own round trips).  The
-        // raw capture is still where the chain read it: in the context's raw buffer, or in the caller's device memory.
-        c->has_cloud = false;
-        c->n = 0;
-        c->cloud_off_on_device = false;
-        if (h.error == 2 && !L.repeated)
-        {
-          (void) hipFree(c->d_vox_bitmap);
-          c->d_vox_bitmap = nullptr;
-          c->vox_bitmap_cap = 0;
-          agh_localize_params lp = L.lp;
-          lp.sample_idx = L.explicit_samples ? h_idx : nullptr;
-          L.repeated = true;
-          rc = localize_begin_impl(ctx, L.d_raw, true, L.dev_stride, L.n_raw, &lp);
-          if (rc == AGH_OK)
-            rc = localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
-          c->loc.repeated = false;
-          return rc;
-        }
-        c->err = "the voxel lattice of the kept points exceeds 2^33 cells (1 GiB bitmap): set a workspace "
-                 "(Localization::setWorkspace) that bounds the scene";
-        return AGH_ERR_CAPACITY;
-      }
-      c->vox_last_words = (int64_t) h.n_words;
-      c->n = L.nv;
-      c->cloud_off.assign({ (int64_t) 0, L.nv });
-      c->cloud_off_on_device = true;  // ({0, nv}: what the voxeliser wrote)
-      c->n_clouds = 1;
-    }
-    if (!handles_only)
-    {
-      int32_t flags[1] = { h_counts[6] };
-      rc = flags_to_status(c, flags);
-      if (rc == AGH_ERR_RETRY && attempt < 3)
-      {
-        // (the larger capacity classes are on now: the search once more, on the cloud that is already there)
-        if ((rc = ensure_call_buffers(c, std::max<int64_t>(S, 1))) != AGH_OK)
-          return rc;
-        continue;
-      }
-      if (rc != AGH_OK)
-        return rc;
-    }
-    if (h_counts[2] == 2 || h_counts[5] > 8192)  // ([5]: the hands that survived the classifier and the boundary filter)
-    {
-      c->err = "agh_localize: more than 8192 hands for the handle search (classify first, or search fewer samples)";
+      c->err = "the voxel lattice of the kept points exceeds 2^33 cells (1 GiB bitmap): set a workspace "
+               "(Localization::setWorkspace) that bounds the scene";
       return AGH_ERR_CAPACITY;
     }
-    const bool declined = h_counts[3] != 0;  // a row of the pair matrix longer than a wave (see agh_find_handles)
-    c->handles_sequential = declined;
-    if (declined && !with_sequential && attempt < 3)
-    {
-      handles_only = true;
-      continue;
-    }
-    break;
+    // the bound cloud is now the true one
+    c->n_is_bound = false;
+    c->vox_last_words = (int64_t) h.n_words;
+    c->n = L.nv;
+    c->cloud_off.assign({ (int64_t) 0, L.nv });
+    c->cloud_off_on_device = true;  // ({0, nv}: what the voxeliser wrote)
+    c->n_clouds = 1;
   }
-  if (h_counts[2])
-  {
-    c->err = "agh_localize: a seed hand has more than 2048 inliers";
-    return AGH_ERR_CAPACITY;
-  }
+  if ((rc = chain_collect(ctx, "agh_localize", false, 1, h_counts, 0, S, nullptr, localize_queue)) != AGH_OK)
+    return rc;
   const int64_t n_hyp = h_counts[4], n_kept = h_counts[5];
   c->last_nout = std::min<int64_t>(n_hyp, c->s_cap * 8);
   if (result)
@@ -611,12 +436,93 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
   }
   if (h_counts[0] > 0)
   {
-    std::memcpy(handles_out, h_handles, sizeof(agh_handle) * (size_t) h_counts[0]);
-    std::memcpy(inlier_idx_out, h_hidx, sizeof(int32_t) * (size_t) h_counts[1]);
+    std::memcpy(handles_out, pin.handles, sizeof(agh_handle) * (size_t) h_counts[0]);
+    std::memcpy(inlier_idx_out, pin.idx, sizeof(int32_t) * (size_t) h_counts[1]);
   }
   if (hands_out && n_kept > 0)
-    std::memcpy(hands_out, h_hands, sizeof(agh_hypothesis) * (size_t) n_kept);
+    std::memcpy(hands_out, pin.hands, sizeof(agh_hypothesis) * (size_t) n_kept);
   return AGH_OK;
+}
+
+// agh_localize[_device] = begin + end
+static int localize_call(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int64_t stride_bytes, int64_t n,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  if (result)
+    *result = agh_localize_result{ 0, 0, 0, 0, 0 };
+  int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
+  if (rc == AGH_OK)
+    rc = localize_begin_impl(ctx, xyz, xyz_on_device, stride_bytes, n, lp);
+  if (rc != AGH_OK)
+    return rc;
+  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
+}
+
+extern "C" {
+
+int agh_localize(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  return localize_call(ctx, xyz, false, stride_bytes, n, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
+    samples_out, result);
+}
+
+int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  return localize_call(ctx, d_xyz, true, stride_bytes, n, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
+    samples_out, result);
+}
+
+int agh_localize_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp)
+{
+  return localize_begin_impl(ctx, xyz, false, stride_bytes, n, lp);
+}
+
+int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  if (result)
+    *result = agh_localize_result{ 0, 0, 0, 0, 0 };
+  Ctx* c = &ctx->c;
+  if (!c->loc.active)
+  {
+    c->err = "agh_localize_end: no agh_localize_begin in flight";
+    return AGH_ERR_STATE;
+  }
+  if (c->loc.batch)
+  {
+    c->err = "agh_localize_end: the chain in flight is a batch's (agh_localize_batch_end collects it)";
+    return AGH_ERR_STATE;
+  }
+  const int rc = localize_check_outputs(c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
+  if (rc != AGH_OK)
+  {
+    // (the chain is queued: drain it, leave the context as a failed call does)
+    c->loc.active = false;
+    return chain_fail(c, rc);
+  }
+  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
+}
+
+// The NEXT capture up, beside the chain in flight (stage_captures, for a set of one).
+int agh_localize_stage(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  if (bad_capture(xyz, stride_bytes, n))
+  {
+    ctx->c.err = "agh_localize_stage: bad arguments";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  return stage_captures(ctx, "agh_localize_stage", &xyz, &stride_bytes, &n, 1, false);
 }
 
 }  // extern "C"

@@ -12,17 +12,6 @@
 
 using namespace agh;
 
-#define HIPCHK(ctx, expr)                                                                             \
-  do                                                                                                  \
-  {                                                                                                   \
-    hipError_t e__ = (expr);                                                                          \
-    if (e__ != hipSuccess)                                                                            \
-    {                                                                                                 \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                                \
-      return AGH_ERR_HIP;                                                                             \
-    }                                                                                                 \
-  } while (0)
-
 namespace agh
 {
 // one capture of the batch, as the device sees it
@@ -45,7 +34,7 @@ struct BatchCall
   std::vector<int64_t> dev_stride, n, soff, raw_off;  // raw_off: each capture's first point among all the batch's
   std::vector<agh_localize_params> lp;
   int64_t S_tot = 0, n_tot = 0, slot = 0;
-  bool classify = false, filters = false, with_sequential = false;
+  bool classify = false, filters = false;
   double x1 = 0.0, x2 = 0.0;
 };
 
@@ -140,23 +129,22 @@ __global__ void k_batch_samples(const BatchCapture* __restrict__ tab, int C, int
   out[j] = g;
 }
 
-// k_compact_kept (localize.hip) once per capture, one work-group each: capture k's hypotheses are the contiguous run of the
-// batch's list whose samples lie in its span (the list is in sample order), its kept hands go to its own slot -- on the device
-// and in pinned host memory -- with `sample` made capture-local.  filters: the boundary filter against the capture's own
-// workspace (the classifier ran on every hypothesis of the batch).  host_counts: kBatchCountsStride ints per capture, [4]
-// hypotheses, [5] kept, [6] the search's error word.
+// k_compact_kept (localize.hip) once per capture, one work-group each around the same compact_kept_records (agh_internal.h):
+// capture k's hypotheses are the contiguous run of the batch's list whose samples lie in its span (the list is in sample order),
+// its kept hands go to its own slot -- on the device and in pinned host memory -- with `sample` made capture-local.  filters: the
+// boundary filter against the capture's own workspace (the classifier ran on every hypothesis of the batch).  host_counts:
+// kBatchCountsStride ints per capture, [4] hypotheses, [5] kept, [6] the search's error word.
 __global__ __launch_bounds__(1024) void k_compact_kept_batch(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
   int64_t cap_in, int use_keep, int filters, const BatchCapture* __restrict__ tab, agh_hypothesis* __restrict__ out, int slot,
   int* __restrict__ n_out, agh_hypothesis* __restrict__ host_out, int host_slot, int* __restrict__ host_counts,
   const int32_t* __restrict__ flags)
 {
-  constexpr int kList = 8192;  // (the handle search takes no more)
-  __shared__ int src[kList];
+  __shared__ int src[kCompactList];
   __shared__ int wsum[16];
   __shared__ int carry;
   __shared__ int64_t range[2];
   const int cap = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t n = min(*n_in, cap_in);
   const int64_t s0 = tab[cap].soff, s1 = s0 + tab[cap].S;
   if (tid < 2)
@@ -174,48 +162,14 @@ __global__ __launch_bounds__(1024) void k_compact_kept_batch(const agh_hypothesi
     }
     range[tid] = lo;
   }
-  if (tid == 0)
-    carry = 0;
   __syncthreads();
   const int64_t r0 = range[0], r1 = range[1];
   double ws[6];
   for (int q = 0; q < 6; q++)
     ws[q] = tab[cap].ws[q];
-  for (int64_t b0 = r0; b0 < r1; b0 += 1024)
-  {
-    const int64_t i = b0 + tid;
-    const bool keep = i < r1 && (!use_keep || in[i].svm_keep != 0) && !(filters && near_workspace_boundary(in[i].surface, ws));
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0)
-      wsum[wave] = __popcll(m);
-    __syncthreads();
-    int base = carry, tot = 0;
-    for (int w = 0; w < 16; w++)
-    {
-      base += w < wave ? wsum[w] : 0;
-      tot += wsum[w];
-    }
-    const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-    if (keep && pos < kList)
-      src[pos] = (int) i;
-    __syncthreads();
-    if (tid == 0)
-      carry += tot;
-    __syncthreads();
-  }
-  const int K = carry, kw = min(K, min(min(slot, host_slot), kList));
-  agh_hypothesis* o = out + (int64_t) cap * slot;
-  agh_hypothesis* ho = host_out + (int64_t) cap * host_slot;
-  static_assert(offsetof(agh_hypothesis, sample) == 8 * 16, "sample is the first word of the ninth 16-byte part");
-  for (int t = tid; t < kw * 10; t += 1024)
-  {
-    const int k = t / 10, part = t - 10 * k;
-    uint4 v = reinterpret_cast<const uint4*>(in + src[k])[part];
-    if (part == 8)
-      v.x = (unsigned) ((int) v.x - (int) s0);
-    reinterpret_cast<uint4*>(o + k)[part] = v;
-    reinterpret_cast<uint4*>(ho + k)[part] = v;
-  }
+  const int room = min(slot, host_slot);
+  const int K = compact_kept_records(in, r0, r1, use_keep, filters, ws, src, wsum, &carry, out + (int64_t) cap * slot, room,
+    host_out + (int64_t) cap * host_slot, room, (int) s0);
   if (tid == 0)
   {
     n_out[cap] = K;
@@ -274,10 +228,7 @@ int ensure_batch_slots(Ctx* c, LocalizeBatchState* b, int C, int64_t slot)
   }
   return AGH_OK;
 }
-}  // namespace
 
-namespace
-{
 // C bitmap slots of b->slot_words words (+ one popcount block of slack) and their popcount tables
 int ensure_vox_slots(Ctx* c, LocalizeBatchState* b, int C)
 {
@@ -296,17 +247,18 @@ int ensure_vox_slots(Ctx* c, LocalizeBatchState* b, int C)
 }
 
 // search -> classification -> per-capture compaction -> handle search, queued (handles_only: the handle search once more)
-int batch_queue(agh_ctx* ctx, BatchCall& B, bool handles_only)
+int batch_queue(agh_ctx* ctx, bool handles_only)
 {
   Ctx* c = &ctx->c;
   LocalizeBatchState* b = c->lbatch;
+  const BatchCall& B = b->call;
   hipStream_t st = c->stream;
   const int C = B.C;
   int rc;
   for (int k = 0; k < C; k++)
     for (int q = 0; q < (handles_only ? 4 : kBatchCountsStride); q++)
       b->h_counts[k * kBatchCountsStride + q] = 0;
-  B.with_sequential = c->handles_sequential;
+  c->loc.with_sequential = c->handles_sequential;
   if (!handles_only)
   {
     c->mirror = HostMirror{ nullptr, 0, nullptr };
@@ -326,44 +278,12 @@ int batch_queue(agh_ctx* ctx, BatchCall& B, bool handles_only)
   const HandleMirror hm{ b->h_handles, (int) b->h_slot, b->h_idx, (int) b->h_slot, b->h_counts };
   timing_begin(c, st);
   rc = handle_search_batch(b->d, C, b->slot, B.slot, B.x1, B.x2, B.lp[0].min_inliers, B.lp[0].min_length, st, hm,
-    kBatchCountsStride, B.with_sequential, b->d_count);
+    kBatchCountsStride, c->loc.with_sequential, b->d_count);
   timing_mark(c, "handle_search", st);
   if (rc != AGH_OK)
     c->err = "handle search launch failed";
   return rc;
 }
-}  // namespace
-
-namespace
-{
-void drop_bound_cloud(Ctx* c)
-{
-  if (c->n_is_bound)
-  {
-    c->n_is_bound = false;
-    c->has_cloud = false;
-    c->n = 0;
-    c->cloud_off_on_device = false;
-  }
-}
-// an error between the launches and the synchronisation: the stream is drained (a pinned source may still be in flight, the caller
-// may free it as soon as the call returns), and the context must not be left believing the bound is the cloud
-int batch_fail(Ctx* c, int code)
-{
-  (void) hipStreamSynchronize(c->stream);
-  drop_bound_cloud(c);
-  return code;
-}
-#define LB_HIPCHK(expr)                                                   \
-  do                                                                      \
-  {                                                                       \
-    hipError_t e__ = (expr);                                              \
-    if (e__ != hipSuccess)                                                \
-    {                                                                     \
-      c->err = std::string(#expr) + ": " + hipGetErrorString(e__);        \
-      return batch_fail(c, AGH_ERR_HIP);                                  \
-    }                                                                     \
-  } while (0)
 
 struct ActiveGuard
 {
@@ -372,21 +292,11 @@ struct ActiveGuard
   ~ActiveGuard() { c->batch_active = false; }
 };
 
-bool bad_outputs(const agh_handle* handles_out, int64_t handle_cap, const int32_t* inlier_idx_out, int64_t idx_cap,
-  const agh_hypothesis* hands_out, int64_t hands_cap)
-{
-  return handle_cap < 0 || idx_cap < 0 || hands_cap < 0 || (handle_cap > 0 && !handles_out) || (idx_cap > 0 && !inlier_idx_out) ||
-         (hands_cap > 0 && !hands_out);
-}
-bool bad_capture(const float* xyz, int64_t stride_bytes, int64_t n)
-{
-  return n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz);
-}
 const char* const kBadArguments = "agh_localize_batch: bad arguments (1 <= n_captures <= 64; see include/agh.h)";
 
 // Steps 2 to 5 of the batch c->lbatch->call, queued on the context's stream: preprocessing, the batch of clouds, the sample list,
 // search -> classification -> kept hands per capture -> handle search.  Nothing waits, except the first batch of a context (or one
-// after the kept slots were dropped): one synchronisation for the lattice sizes.  An error has drained the stream (batch_fail).
+// after the kept slots were dropped): one synchronisation for the lattice sizes.  An error has drained the stream (chain_fail).
 int batch_pass(agh_ctx* ctx)
 {
   Ctx* c = &ctx->c;
@@ -405,7 +315,7 @@ int batch_pass(agh_ctx* ctx)
   {
     if ((rc = dev_alloc(c, &c->d_vox_code, (size_t) n_tot)) || (rc = dev_alloc(c, &c->d_vox_blk, (size_t) n_tot / 1024 + 2)) ||
         (rc = dev_alloc(c, &c->d_vox_xyz, (size_t) n_tot * 3)) || (rc = dev_alloc(c, &c->d_vox_cam, (size_t) n_tot)))
-      return batch_fail(c, rc);
+      return chain_fail(c, rc);
     c->vox_cap = n_tot;
   }
   int64_t nb_max = 0, n_max = 0, blk_tot = 0;
@@ -435,10 +345,10 @@ int batch_pass(agh_ctx* ctx)
   if (blk_tot + 1 > b->blk_cap || !b->d_blk)
   {
     if ((rc = dev_alloc(c, &b->d_blk, (size_t) blk_tot + 1)))
-      return batch_fail(c, rc);
+      return chain_fail(c, rc);
     b->blk_cap = blk_tot + 1;
   }
-  LB_HIPCHK(hipMemcpyAsync(b->d_vcap, b->h_vcap, sizeof(VoxCapture) * (size_t) C, hipMemcpyHostToDevice, st));
+  AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_vcap, b->h_vcap, sizeof(VoxCapture) * (size_t) C, hipMemcpyHostToDevice, st), chain_fail(c, AGH_ERR_HIP));
   VoxBatch vb;
   vb.cap = b->d_vcap;
   vb.desc = b->d_vdesc;
@@ -453,9 +363,9 @@ int batch_pass(agh_ctx* ctx)
            nullptr, st)) != AGH_OK)
     {
       c->err = "preprocessing launch failed";
-      return batch_fail(c, rc);
+      return chain_fail(c, rc);
     }
-    LB_HIPCHK(hipStreamSynchronize(st));
+    AGH_HIPCHK_OR(c, hipStreamSynchronize(st), chain_fail(c, AGH_ERR_HIP));
     int64_t words = 0;
     for (int k = 0; k < C; k++)
     {
@@ -463,21 +373,21 @@ int batch_pass(agh_ctx* ctx)
       {
         c->err = "agh_localize_batch: capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
                  "(1 GiB bitmap): set a workspace that bounds the scene";
-        return batch_fail(c, AGH_ERR_CAPACITY);
+        return chain_fail(c, AGH_ERR_CAPACITY);
       }
       words = std::max<int64_t>(words, (int64_t) b->h_desc[k].n_words);
     }
     b->slot_words = std::min<int64_t>(((words + words / 4) / 4096 + 1) * 4096, (int64_t) kVoxMaxWords);
   }
   if ((rc = ensure_vox_slots(c, b, C)) != AGH_OK)
-    return batch_fail(c, rc);
+    return chain_fail(c, rc);
   vb.slot_words = b->slot_words;
   timing_begin(c, st);
   if ((rc = vox_batch(vb, C, nb_max, n_max, any_scan, cell, false, b->d_bitmap, b->d_blk, b->d_blk2, c->d_vox_code, c->d_vox_xyz,
          c->d_vox_cam, c->d_cloud_off, st)) != AGH_OK)
   {
     c->err = "preprocessing launch failed";
-    return batch_fail(c, rc);
+    return chain_fail(c, rc);
   }
   timing_mark(c, "preprocess", st);
   c->cloud_async = false;
@@ -490,38 +400,29 @@ int batch_pass(agh_ctx* ctx)
     rc = agh_set_cloud_batch_device(ctx, c->d_vox_xyz, 12, c->d_vox_cam, bound.data(), C, nullptr);
     c->defer_cloud_count = false;
     if (rc != AGH_OK)
-      return batch_fail(c, rc);
+      return chain_fail(c, rc);
   }
   // ---- 4. buffers for the bounds, the capture table and the sample list ----
   if ((rc = ensure_call_buffers(c, std::max<int64_t>(S_tot, 1))) != AGH_OK)
-    return batch_fail(c, rc);
+    return chain_fail(c, rc);
   if (S_tot > c->idx_cap || !c->d_idx_own)
   {
     if ((rc = dev_alloc(c, &c->d_idx_own, (size_t) std::max<int64_t>(S_tot, 1024))))
-      return batch_fail(c, rc);
+      return chain_fail(c, rc);
     c->idx_cap = std::max<int64_t>(S_tot, 1024);
   }
   if (S_tot > b->s_cap || !b->h_samples)
   {
     const int64_t cap = std::max<int64_t>(S_tot, 1024);
     if ((rc = dev_alloc(c, &b->d_local, (size_t) cap)) || (rc = pinned_alloc(c, &b->h_samples, (size_t) cap)))
-      return batch_fail(c, rc);
+      return chain_fail(c, rc);
     b->s_cap = cap;
   }
   if ((rc = ensure_batch_slots(c, b, C, B.slot)) != AGH_OK)
-    return batch_fail(c, rc);
-  if (B.classify && c->s_cap * 8 > c->keep_cap)
+    return chain_fail(c, rc);
+  if (B.classify)
   {
-    if (c->d_keep)
-      (void) hipFree(c->d_keep);
-    if (c->d_svm_sums)
-      (void) hipFree(c->d_svm_sums);
-    c->d_keep = nullptr;
-    c->d_svm_sums = nullptr;
-    c->keep_cap = 0;
-    LB_HIPCHK(hipMalloc((void**) &c->d_keep, (size_t) (c->s_cap * 8)));
-    LB_HIPCHK(hipMalloc((void**) &c->d_svm_sums, (size_t) (c->s_cap * 8) * sizeof(double)));
-    c->keep_cap = c->s_cap * 8;
+    AGH_HIPCHK_OR(c, ensure_keep_buffers(c, c->s_cap * 8), chain_fail(c, AGH_ERR_HIP));
   }
   bool any_explicit = false;
   for (int k = 0; k < C; k++)
@@ -543,18 +444,21 @@ int batch_pass(agh_ctx* ctx)
       lp[k].sample_idx = b->h_samples + B.soff[k];
     }
   }
-  LB_HIPCHK(hipMemcpyAsync(b->d_tab, b->h_tab, sizeof(BatchCapture) * (size_t) C, hipMemcpyHostToDevice, st));
+  AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_tab, b->h_tab, sizeof(BatchCapture) * (size_t) C, hipMemcpyHostToDevice, st), chain_fail(c, AGH_ERR_HIP));
   if (any_explicit)
-    LB_HIPCHK(hipMemcpyAsync(b->d_local, b->h_samples, sizeof(int32_t) * (size_t) S_tot, hipMemcpyHostToDevice, st));
+  {
+    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_local, b->h_samples, sizeof(int32_t) * (size_t) S_tot, hipMemcpyHostToDevice, st),
+      chain_fail(c, AGH_ERR_HIP));
+  }
   if (S_tot > 0)
   {
     hipLaunchKernelGGL(k_batch_samples, dim3((unsigned) ((S_tot + 255) / 256)), dim3(256), 0, st, (const BatchCapture*) b->d_tab, C,
       S_tot, (const int*) c->d_cloud_off, (const int32_t*) b->d_local, c->d_idx_own, b->h_samples, b->h_bad);
-    LB_HIPCHK(hipGetLastError());
+    AGH_HIPCHK_OR(c, hipGetLastError(), chain_fail(c, AGH_ERR_HIP));
   }
   // ---- 5. search -> classification -> kept hands per capture -> handle search ----
-  if ((rc = batch_queue(ctx, B, false)) != AGH_OK)
-    return batch_fail(c, rc);
+  if ((rc = batch_queue(ctx, false)) != AGH_OK)
+    return chain_fail(c, rc);
   return AGH_OK;
 }
 
@@ -615,7 +519,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     c->err = "agh_localize_batch: this libm's acos is not monotone around the 0.34 rad thresholds";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   int rc;
   if (!c->lbatch)
@@ -669,17 +573,15 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     int64_t need = 0;
     for (int k = 0; k < C; k++)
     {
-      B.dev_stride[k] = stride_bytes[k] <= 32 ? stride_bytes[k] : 12;  // (as agh_preprocess)
+      B.dev_stride[k] = device_stride(stride_bytes[k]);
       need += n[k] * (B.dev_stride[k] / 4);
     }
-    bool adopt = L.staged && L.staged_captures == C && c->d_stage_xyz;
-    for (int k = 0; k < C && adopt; k++)
-      adopt = L.staged_batch_src[k] == xyz[k] && L.staged_batch_stride[k] == stride_bytes[k] && L.staged_batch_n[k] == n[k];
+    const bool adopt = L.staged_is(xyz, stride_bytes, n, C, true) && c->d_stage_xyz;
     // A staged batch that is this one: it is (or is about to be) in the second raw buffer -- the two buffers change places and the
     // chain waits for the copies.  Anything else that is staged (another batch, a capture of agh_localize_stage) is dropped: its
     // copy may still read the caller's source, so the chain waits for it too and agh_localize_batch_end's synchronisation covers it.
     if (L.staged)
-      HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
+      AGH_HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
     L.staged = false;
     if (adopt)
       swap_raw_buffers(c);
@@ -693,13 +595,8 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     for (int k = 0; k < C; k++)
     {
       float* dst = c->d_raw_xyz + off;
-      if (n[k] > 0 && !adopt)
-      {
-        if (B.dev_stride[k] == stride_bytes[k])
-          HIPCHK(c, hipMemcpyAsync(dst, xyz[k], (size_t) (n[k] * stride_bytes[k] - (stride_bytes[k] - 12)), hipMemcpyHostToDevice, st));
-        else
-          HIPCHK(c, hipMemcpy2DAsync(dst, 12, xyz[k], (size_t) stride_bytes[k], 12, (size_t) n[k], hipMemcpyHostToDevice, st));
-      }
+      if (!adopt)
+        AGH_HIPCHK(c, upload_capture(dst, xyz[k], stride_bytes[k], n[k], st));
       B.d_raw[k] = dst;
       off += n[k] * (B.dev_stride[k] / 4);
     }
@@ -710,7 +607,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   // (the next agh_localize_batch_stage into this raw buffer -- after it has changed places -- waits for this chain's reads)
   if (!on_device && c->raw_read)
   {
-    LB_HIPCHK(hipEventRecord(c->raw_read, st));
+    AGH_HIPCHK_OR(c, hipEventRecord(c->raw_read, st), chain_fail(c, AGH_ERR_HIP));
     c->raw_read_set = true;
   }
   L.active = true;
@@ -737,7 +634,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   {
     if (pass > 0 && (rc = batch_pass(ctx)) != AGH_OK)  // (pass 0 was queued by agh_localize_batch_begin)
       return rc;
-    LB_HIPCHK(hipStreamSynchronize(st));
+    AGH_HIPCHK_OR(c, hipStreamSynchronize(st), chain_fail(c, AGH_ERR_HIP));
     // ---- 6. the voxel descriptors: a lattice that outgrew the kept bitmap -> the batch once more with one sized for all, from
     // the raw buffer (or the caller's device memory) the chain read, which a capture staged meanwhile has not touched ----
     int64_t words = 0;
@@ -781,68 +678,10 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   c->cloud_off = voff;
   c->cloud_off_on_device = true;
   c->n_clouds = C;
-  int* hc = b->h_counts;
-  bool handles_only = false;
-  for (int attempt = 0;; attempt++)
-  {
-    if (attempt > 0)
-    {
-      if ((rc = batch_queue(ctx, B, handles_only)) != AGH_OK)
-        return batch_fail(c, rc);
-      LB_HIPCHK(hipStreamSynchronize(st));
-    }
-    if (!handles_only)
-    {
-      int32_t flags[1] = { hc[6] };
-      rc = flags_to_status(c, flags);
-      if (rc == AGH_ERR_RETRY && attempt < 3)
-      {
-        if ((rc = ensure_call_buffers(c, std::max<int64_t>(S_tot, 1))) != AGH_OK)
-          return rc;
-        continue;
-      }
-      if (rc == AGH_ERR_INVALID_ARGUMENT && (flags[0] & 4))
-      {
-        for (int k = 0; k < C; k++)
-          if (b->h_bad[k])
-          {
-            c->err = "agh_localize_batch: a sample index of capture " + std::to_string(k) + " is outside its voxelised cloud";
-            break;
-          }
-      }
-      if (rc != AGH_OK)
-        return rc;
-    }
-    bool declined = false;
-    for (int k = 0; k < C; k++)
-    {
-      const int* h = hc + k * kBatchCountsStride;
-      if (h[2] == 2 || h[5] > 8192)
-      {
-        c->err = "agh_localize_batch: capture " + std::to_string(k) +
-                 ": more than 8192 hands for the handle search (classify first, or search fewer samples)";
-        return AGH_ERR_CAPACITY;
-      }
-      declined |= h[3] != 0;
-    }
-    c->handles_sequential = declined;
-    if (declined && !B.with_sequential && attempt < 3)
-    {
-      handles_only = true;
-      continue;
-    }
-    break;
-  }
+  const int* hc = b->h_counts;
+  if ((rc = chain_collect(ctx, "agh_localize_batch", true, C, hc, kBatchCountsStride, S_tot, b->h_bad, batch_queue)) != AGH_OK)
+    return rc;
   int64_t n_hyp_tot = 0, tot_handles = 0, tot_idx = 0, tot_hands = 0;
-  for (int k = 0; k < C; k++)
-  {
-    const int* h = hc + k * kBatchCountsStride;
-    if (h[2])
-    {
-      c->err = "agh_localize_batch: capture " + std::to_string(k) + ": a seed hand has more than 2048 inliers";
-      return AGH_ERR_CAPACITY;
-    }
-  }
   for (int k = 0; k < C; k++)
   {
     const int* h = hc + k * kBatchCountsStride;
@@ -879,7 +718,6 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   }
   return AGH_OK;
 }
-#undef LB_HIPCHK
 
 void zero_results(agh_localize_batch_result* results, int C)
 {
@@ -948,22 +786,20 @@ int agh_localize_batch_begin_device(agh_ctx* ctx, const float* const* xyz, const
   return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures);
 }
 
-// The NEXT batch's captures up, beside whatever runs on the context's stream: packed end to end (step 1's stride rule) into the
-// context's second raw buffer, on the stage stream.  A pageable source makes the call last as long as its copies; a pinned one is
-// read asynchronously and must stay valid until the agh_localize_batch_end of the chain that adopts (or drops) the set.
+// The NEXT batch's captures up, beside whatever runs on the context's stream (stage_captures, localize.hip).  A pinned source must
+// stay valid until the agh_localize_batch_end of the chain that adopts (or drops) the set.
 int agh_localize_batch_stage(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int32_t n_captures)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
-  LocalizeState& L = c->loc;
   const int C = n_captures;
   if (C < 1 || C > kMaxClouds || !xyz || !stride_bytes || !n)
   {
     c->err = "agh_localize_batch_stage: bad arguments (1 <= n_captures <= 64; see include/agh.h)";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  int64_t n_tot = 0, need = 0;
+  int64_t n_tot = 0;
   for (int k = 0; k < C; k++)
   {
     if (bad_capture(xyz[k], stride_bytes[k], n[k]))
@@ -972,69 +808,13 @@ int agh_localize_batch_stage(agh_ctx* ctx, const float* const* xyz, const int64_
       return AGH_ERR_INVALID_ARGUMENT;
     }
     n_tot += n[k];
-    need += n[k] * ((stride_bytes[k] <= 32 ? stride_bytes[k] : 12) / 4);
   }
   if (n_tot >= (1ll << 30))
   {
     c->err = "agh_localize_batch_stage: need fewer than 2^30 raw points in all";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = ensure_stage_stream(c, "agh_localize_batch_stage")) != AGH_OK)
-    return rc;
-  // A failure from here on leaves nothing staged -- and an earlier set's copies may still be reading their (pinned) sources, with no
-  // begin left to wait for stage_done: the stage stream is drained before the flag comes down.
-  auto stage_fail = [&](int code) {
-    (void) hipStreamSynchronize(c->stage_stream);
-    L.staged = false;
-    return code;
-  };
-#define STAGE_HIPCHK(expr)                                                \
-  do                                                                      \
-  {                                                                       \
-    hipError_t e__ = (expr);                                              \
-    if (e__ != hipSuccess)                                                \
-    {                                                                     \
-      c->err = std::string(#expr) + ": " + hipGetErrorString(e__);        \
-      return stage_fail(AGH_ERR_HIP);                                     \
-    }                                                                     \
-  } while (0)
-  if (need > c->stage_cap || !c->d_stage_xyz)
-  {
-    // (nobody reads this buffer now: the chain in flight reads d_raw_xyz)
-    if ((rc = dev_alloc(c, &c->d_stage_xyz, (size_t) std::max<int64_t>(need, 1))))
-      return stage_fail(rc);
-    c->stage_cap = need;
-    c->stage_read_set = false;
-  }
-  if (c->stage_read_set)  // the last chain that read the buffer these copies overwrite (it has ended: see DESIGN.md)
-    STAGE_HIPCHK(hipStreamWaitEvent(c->stage_stream, c->stage_read, 0));
-  // (whatever was staged before is replaced: its copies are ahead of these on the stage stream, so stage_done covers them too)
-  int64_t off = 0;
-  for (int k = 0; k < C; k++)
-  {
-    float* dst = c->d_stage_xyz + off;
-    const int64_t dev_stride = stride_bytes[k] <= 32 ? stride_bytes[k] : 12;
-    if (n[k] > 0)
-    {
-      if (dev_stride == stride_bytes[k])
-        STAGE_HIPCHK(hipMemcpyAsync(dst, xyz[k], (size_t) (n[k] * stride_bytes[k] - (stride_bytes[k] - 12)), hipMemcpyHostToDevice,
-          c->stage_stream));
-      else
-        STAGE_HIPCHK(hipMemcpy2DAsync(dst, 12, xyz[k], (size_t) stride_bytes[k], 12, (size_t) n[k], hipMemcpyHostToDevice,
-          c->stage_stream));
-    }
-    off += n[k] * (dev_stride / 4);
-  }
-  STAGE_HIPCHK(hipEventRecord(c->stage_done, c->stage_stream));
-#undef STAGE_HIPCHK
-  L.staged_batch_src.assign(xyz, xyz + C);
-  L.staged_batch_stride.assign(stride_bytes, stride_bytes + C);
-  L.staged_batch_n.assign(n, n + C);
-  L.staged_captures = C;
-  L.staged = true;
-  return AGH_OK;
+  return stage_captures(ctx, "agh_localize_batch_stage", xyz, stride_bytes, n, C, true);
 }
 
 int agh_localize_batch_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
@@ -1056,7 +836,7 @@ int agh_localize_batch_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle
     c->loc.active = false;
     c->loc.batch = false;
     c->err = kBadArguments;
-    return batch_fail(c, AGH_ERR_INVALID_ARGUMENT);
+    return chain_fail(c, AGH_ERR_INVALID_ARGUMENT);
   }
   return batch_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
 }

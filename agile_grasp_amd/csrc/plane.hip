@@ -30,17 +30,6 @@
 #include <limits>
 #include <vector>
 
-#define PLANECHK(ctx, expr)                                                                                         \
-  do                                                                                                                \
-  {                                                                                                                 \
-    hipError_t e__ = (expr);                                                                                        \
-    if (e__ != hipSuccess)                                                                                          \
-    {                                                                                                               \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                                              \
-      return AGH_ERR_HIP;                                                                                           \
-    }                                                                                                               \
-  } while (0)
-
 namespace agh
 {
 
@@ -663,7 +652,7 @@ int agh_remove_plane(agh_ctx* ctx, const agh_plane_params* pp, agh_plane_result*
     c->err = "agh_remove_plane: needs one cloud (agh_set_cloud* or agh_preprocess*), not none and not a batch";
     return AGH_ERR_STATE;
   }
-  PLANECHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   if (!c->plane)
     c->plane = new PlaneState;
   PlaneState& P = *c->plane;
@@ -705,14 +694,14 @@ int agh_remove_plane(agh_ctx* ctx, const agh_plane_params* pp, agh_plane_result*
   const int64_t per_blk = 256 * kPlaneScorePts;
   hipLaunchKernelGGL(k_plane_score, dim3((unsigned) ((n + per_blk - 1) / per_blk)), dim3(256), 0, st, xyz, sf, n,
     (const PlaneCand*) P.d_cand, (const PlaneHdr*) P.d_hdr, thr, P.d_counts);
-  PLANECHK(c, hipGetLastError());
+  AGH_HIPCHK(c, hipGetLastError());
   PlaneHdr hdr;
   std::vector<unsigned> cnt((size_t) max_cand);
   P.cand.resize((size_t) max_cand);
-  PLANECHK(c, hipMemcpyAsync(&hdr, P.d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
-  PLANECHK(c, hipMemcpyAsync(P.cand.data(), P.d_cand, sizeof(PlaneCand) * (size_t) max_cand, hipMemcpyDeviceToHost, st));
-  PLANECHK(c, hipMemcpyAsync(cnt.data(), P.d_counts, sizeof(unsigned) * (size_t) max_cand, hipMemcpyDeviceToHost, st));
-  PLANECHK(c, hipStreamSynchronize(st));
+  AGH_HIPCHK(c, hipMemcpyAsync(&hdr, P.d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipMemcpyAsync(P.cand.data(), P.d_cand, sizeof(PlaneCand) * (size_t) max_cand, hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipMemcpyAsync(cnt.data(), P.d_counts, sizeof(unsigned) * (size_t) max_cand, hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipStreamSynchronize(st));
   P.cand.resize((size_t) hdr.n_cand);
   P.counts.assign(cnt.begin(), cnt.begin() + hdr.n_cand);
 
@@ -741,11 +730,11 @@ int agh_remove_plane(agh_ctx* ctx, const agh_plane_params* pp, agh_plane_result*
       P.d_terms, m_in);
     hipLaunchKernelGGL(k_plane_moments, dim3(1), dim3(256), 0, st, (const float*) P.d_terms, m_in, (const PlaneHdr*) P.d_hdr,
       P.d_accu);
-    PLANECHK(c, hipGetLastError());
+    AGH_HIPCHK(c, hipGetLastError());
     float accu[9];
-    PLANECHK(c, hipMemcpyAsync(accu, P.d_accu, sizeof(accu), hipMemcpyDeviceToHost, st));
-    PLANECHK(c, hipMemcpyAsync(&hdr, P.d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
-    PLANECHK(c, hipStreamSynchronize(st));
+    AGH_HIPCHK(c, hipMemcpyAsync(accu, P.d_accu, sizeof(accu), hipMemcpyDeviceToHost, st));
+    AGH_HIPCHK(c, hipMemcpyAsync(&hdr, P.d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
+    AGH_HIPCHK(c, hipStreamSynchronize(st));
     if (hdr.n_in != m_in)
     {
       c->err = "agh_remove_plane: the inliers of the chosen plane do not match its score";
@@ -767,9 +756,9 @@ int agh_remove_plane(agh_ctx* ctx, const agh_plane_params* pp, agh_plane_result*
   hipLaunchKernelGGL(k_plane_scan, dim3(1), dim3(1024), 0, st, (const int*) P.d_blk, (int) nblk, P.d_blk_off, P.d_hdr);
   hipLaunchKernelGGL(k_plane_split, dim3((unsigned) nblk), dim3(256), 0, st, xyz, sf, n, cam, p, thr, (const int*) P.d_blk_off,
     P.d_idx, P.d_xyz[slot], P.d_cam[slot], pp->cam_ids_by_position ? 1 : 0);
-  PLANECHK(c, hipGetLastError());
-  PLANECHK(c, hipMemcpyAsync(&hdr, P.d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
-  PLANECHK(c, hipStreamSynchronize(st));
+  AGH_HIPCHK(c, hipGetLastError());
+  AGH_HIPCHK(c, hipMemcpyAsync(&hdr, P.d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipStreamSynchronize(st));
   const int64_t n_in = hdr.n_in;
   const int64_t kept = n - n_in;
   rc = agh_set_cloud_device(ctx, P.d_xyz[slot], 12, P.d_cam[slot], kept, nullptr);
@@ -805,9 +794,9 @@ int agh_get_plane_inliers(agh_ctx* ctx, int32_t* idx, int64_t cap)
   }
   if (idx && P.n_inliers > 0)
   {
-    PLANECHK(c, hipSetDevice(c->device));
-    PLANECHK(c, hipMemcpyAsync(idx, P.d_idx, sizeof(int32_t) * (size_t) P.n_inliers, hipMemcpyDeviceToHost, c->stream));
-    PLANECHK(c, hipStreamSynchronize(c->stream));
+    AGH_HIPCHK(c, hipSetDevice(c->device));
+    AGH_HIPCHK(c, hipMemcpyAsync(idx, P.d_idx, sizeof(int32_t) * (size_t) P.n_inliers, hipMemcpyDeviceToHost, c->stream));
+    AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return (int) P.n_inliers;
 }

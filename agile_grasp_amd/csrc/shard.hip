@@ -206,17 +206,6 @@ void comm_release(Ctx* c)
 
 namespace
 {
-#define HIPCHK(ctx, expr)                                                                             \
-  do                                                                                                  \
-  {                                                                                                   \
-    hipError_t e__ = (expr);                                                                          \
-    if (e__ != hipSuccess)                                                                            \
-    {                                                                                                 \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                                \
-      return AGH_ERR_HIP;                                                                             \
-    }                                                                                                 \
-  } while (0)
-
 // In-place all-gather: rank r's contribution already sits at buf + r * bytes.
 int all_gather(Ctx* c, void* buf, size_t bytes, hipStream_t st)
 {
@@ -234,7 +223,7 @@ int all_gather(Ctx* c, void* buf, size_t bytes, hipStream_t st)
     return AGH_OK;
   }
   LocalGroup* g = cm->local.get();
-  HIPCHK(c, hipStreamSynchronize(st));  // my segment is complete
+  AGH_HIPCHK(c, hipStreamSynchronize(st));  // my segment is complete
   {
     std::lock_guard<std::mutex> lk(g->m);
     g->send[(size_t) cm->rank] = (const char*) buf + (size_t) cm->rank * bytes;
@@ -247,8 +236,8 @@ int all_gather(Ctx* c, void* buf, size_t bytes, hipStream_t st)
   }
   for (int q = 0; q < cm->n_ranks; q++)
     if (q != cm->rank)
-      HIPCHK(c, hipMemcpyAsync((char*) buf + (size_t) q * bytes, g->send[(size_t) q], bytes, hipMemcpyDeviceToDevice, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+      AGH_HIPCHK(c, hipMemcpyAsync((char*) buf + (size_t) q * bytes, g->send[(size_t) q], bytes, hipMemcpyDeviceToDevice, st));
+  AGH_HIPCHK(c, hipStreamSynchronize(st));
   if (!g->barrier())  // nobody reuses a segment before everyone has copied it
   {
     c->err = broken;
@@ -451,12 +440,12 @@ int shard_agree(Ctx* c, hipStream_t st, bool mine_ok, int64_t word, bool* all_ok
   const int G = cm->n_ranks, r = cm->rank;
   const int64_t mine = (word << 1) | (mine_ok ? 1 : 0);
   int64_t all[64];
-  HIPCHK(c, hipMemcpyAsync(c->d_xcnt + 64 + r, &mine, sizeof(int64_t), hipMemcpyHostToDevice, st));
+  AGH_HIPCHK(c, hipMemcpyAsync(c->d_xcnt + 64 + r, &mine, sizeof(int64_t), hipMemcpyHostToDevice, st));
   const int rc = all_gather(c, c->d_xcnt + 64, sizeof(int64_t), st);
   if (rc != AGH_OK)
     return rc;
-  HIPCHK(c, hipMemcpyAsync(all, c->d_xcnt + 64, sizeof(int64_t) * (size_t) G, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  AGH_HIPCHK(c, hipMemcpyAsync(all, c->d_xcnt + 64, sizeof(int64_t) * (size_t) G, hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipStreamSynchronize(st));
   *all_ok = true;
   for (int q = 0; q < G; q++)
   {
@@ -585,7 +574,7 @@ int agh_comm_init(agh_ctx* ctx, int32_t rank, int32_t n_ranks, const uint8_t id[
     c->err = r->err;
     return AGH_ERR_STATE;
   }
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   ncclUniqueId u;
   std::memcpy(u.internal, id, AGH_COMM_ID_BYTES);
   ncclComm_t comm = nullptr;
@@ -828,10 +817,10 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
   // a camera-origin table that does not fit this rank's batch: also a caller's bug on this rank, and it takes part without searching
   if (c->has_cloud && !mid_chain && cam_table_mismatch(c, "agh_find_hands_sharded", c->n_clouds))
     degrade(AGH_ERR_INVALID_ARGUMENT, c->err, kHdrRankFailed);
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t) hip_stream : c->stream;
-  HIPCHK(c, order_after_cloud(c, st));
-  HIPCHK(c, order_after_cam_table(c, st));
+  AGH_HIPCHK(c, order_after_cloud(c, st));
+  AGH_HIPCHK(c, order_after_cam_table(c, st));
   const int G = c->comm->n_ranks, r = c->comm->rank;
   const int64_t S = n_samples;
   const int64_t n_cloud = c->has_cloud && !mid_chain ? c->n : 0;  // (mid-chain, c->n may be a bound of the chain's cloud)
@@ -931,7 +920,7 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
       (void) hipFree(c->d_normals);
     c->d_normals = nullptr;
     c->normals_cap = 0;
-    HIPCHK(c, hipMalloc((void**) &c->d_normals, sizeof(double) * 3 * (size_t) std::max<int64_t>(pcnt, 1)));
+    AGH_HIPCHK(c, hipMalloc((void**) &c->d_normals, sizeof(double) * 3 * (size_t) std::max<int64_t>(pcnt, 1)));
     c->normals_cap = pcnt;
   }
   if (!mid_chain)
@@ -962,9 +951,9 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
   }
   if (S == 0)  // (the same on every rank: nobody starts a collective)
   {
-    HIPCHK(c, hipMemsetAsync(d_flags, 0, 8 * sizeof(int32_t), st));
-    HIPCHK(c, hipMemsetAsync(d_n_out, 0, sizeof(int64_t), st));
-    HIPCHK(c, hipMemsetAsync(c->d_xbuf, 0, (size_t) G * seg_bytes, st));
+    AGH_HIPCHK(c, hipMemsetAsync(d_flags, 0, 8 * sizeof(int32_t), st));
+    AGH_HIPCHK(c, hipMemsetAsync(d_n_out, 0, sizeof(int64_t), st));
+    AGH_HIPCHK(c, hipMemsetAsync(c->d_xbuf, 0, (size_t) G * seg_bytes, st));
     if (!mid_chain)
     {
       c->zero_flags_pending = false;
@@ -982,7 +971,7 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
   auto ok = [&]() { return local_rc == AGH_OK; };
   if (calculates_antipodal)
   {
-    HIPCHK(c, hipMemsetAsync(c->d_normals, 0, sizeof(double) * 3 * (size_t) (G * pcnt), st));
+    AGH_HIPCHK(c, hipMemsetAsync(c->d_normals, 0, sizeof(double) * 3 * (size_t) (G * pcnt), st));
     const int64_t p0 = std::min<int64_t>(n_cloud, (int64_t) r * pcnt), p1 = std::min<int64_t>(n_cloud, (int64_t) (r + 1) * pcnt);
     if (ok() && (rc = normals_pass(c, p0, p1, st)) != AGH_OK)
       degrade(rc, "normals pass launch failed", kHdrRankFailed);
@@ -998,7 +987,7 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
   }
   if (mid_chain || c->zero_flags_pending)  // (no Taubin launch cleared them: an empty or a degraded slice)
   {
-    HIPCHK(c, hipMemsetAsync(d_flags, 0, 8 * sizeof(int32_t), st));
+    AGH_HIPCHK(c, hipMemsetAsync(d_flags, 0, 8 * sizeof(int32_t), st));
     if (!mid_chain)
       c->zero_flags_pending = false;
   }
@@ -1017,7 +1006,7 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
       hipLaunchKernelGGL(k_shard_pack_normals, dim3((unsigned) ((Sr + 255) / 256)), dim3(256), 0, st, (const agh_frame*) c->d_frames,
         (int) Sr, c->d_nbuf + (int64_t) r * seg_d);
     else  // (nothing of this rank's: every "valid" word zero)
-      HIPCHK(c, hipMemsetAsync(c->d_nbuf + (int64_t) r * seg_d, 0, sizeof(double) * (size_t) seg_d, st));
+      AGH_HIPCHK(c, hipMemsetAsync(c->d_nbuf + (int64_t) r * seg_d, 0, sizeof(double) * (size_t) seg_d, st));
     if ((rc = all_gather(c, c->d_nbuf, sizeof(double) * (size_t) seg_d, st)) != AGH_OK)
       return rc;
     if (ok())  // (a degraded rank searches nothing: it needs nobody's normals -- and its sample list may not exist)
@@ -1038,7 +1027,7 @@ static int find_hands_sharded_device_impl(agh_ctx* ctx, const int32_t* d_sample_
     // of a capacity-class retry from EVERY rank, or this one would repeat the collective alone); a degraded rank: count 0 and
     // the word that makes the call fail on every rank
     hipLaunchKernelGGL(k_shard_empty_header, dim3(1), dim3(1), 0, st, my_count, (const int32_t*) d_flags, class_level(c), hdr_extra);
-    HIPCHK(c, hipGetLastError());
+    AGH_HIPCHK(c, hipGetLastError());
   }
   if (!ok())
   {
@@ -1103,7 +1092,7 @@ static int classify_sharded_device_impl(agh_ctx* ctx, uint8_t* d_keep, void* hip
     local_rc = AGH_ERR_NO_SVM;
     local_err = "agh_classify_sharded: no SVM loaded";
   }
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = hip_stream ? (hipStream_t) hip_stream : c->stream;
   // K3 on my own hypotheses: their images are here, svm_keep lands in my segment's records
   int rc;
@@ -1120,11 +1109,11 @@ static int classify_sharded_device_impl(agh_ctx* ctx, uint8_t* d_keep, void* hip
   {
     int64_t* my_hdr = reinterpret_cast<int64_t*>(c->d_xbuf + (int64_t) c->comm->rank * c->shard_seg_bytes);
     hipLaunchKernelGGL(k_shard_flag_header, dim3(1), dim3(1), 0, st, my_hdr, hdr_bits);
-    HIPCHK(c, hipGetLastError());
+    AGH_HIPCHK(c, hipGetLastError());
     c->shard_hdr_bits = hdr_bits;
   }
   // (the merge derives the call's flags word from the headers afresh: a failed classification's peer bit must not outlive it either)
-  HIPCHK(c, hipMemsetAsync(mid_chain ? bystander_flags(c) : c->d_flags, 0, mid_chain ? 8 * sizeof(int32_t) : sizeof(int32_t), st));
+  AGH_HIPCHK(c, hipMemsetAsync(mid_chain ? bystander_flags(c) : c->d_flags, 0, mid_chain ? 8 * sizeof(int32_t) : sizeof(int32_t), st));
   rc = mid_chain ? exchange_and_merge(c, nullptr, reinterpret_cast<agh_hypothesis*>(bystander_flags(c)), 0, bystander_nout(c),
                      bystander_flags(c), st)
                  : exchange_and_merge(c, local_rc == AGH_OK ? d_keep : nullptr, c->shard_out, c->shard_cap, c->shard_nout, c->d_flags, st);
@@ -1144,10 +1133,10 @@ static int classify_sharded_device_impl(agh_ctx* ctx, uint8_t* d_keep, void* hip
 static int shard_flags(Ctx* c, hipStream_t st, int64_t* n)
 {
   int32_t flags[8];
-  HIPCHK(c, hipMemcpyAsync(flags, c->d_flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipMemcpyAsync(flags, c->d_flags, sizeof(flags), hipMemcpyDeviceToHost, st));
   if (n)
-    HIPCHK(c, hipMemcpyAsync(n, c->shard_nout, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+    AGH_HIPCHK(c, hipMemcpyAsync(n, c->shard_nout, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  AGH_HIPCHK(c, hipStreamSynchronize(st));
   // A rank that failed (it returned its own error after the exchange) comes first: every rank returns with this call, and none
   // switches a capacity class or the segment size on it -- the failed rank could not, and the next call's segment sizes and
   // launches must agree.  A retry this call would have asked for is asked for again by the next one, on every rank.
@@ -1245,7 +1234,7 @@ static int find_hands_sharded_host_impl(agh_ctx* ctx, const int32_t* sample_idx,
   // leave before the collectives the others wait in.  The kernels validate every index they read
   // (kStatusBadIndex), the finding travels in the rank's segment header, and every rank returns AGH_ERR_INVALID_ARGUMENT
   // together after the exchange.)
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   // (a localize chain in flight owns d_out_own, d_idx_own and the per-call buffers: this rank touches none of them and takes part
   // as a bystander, include/agh.h)
   if (c->loc.active)
@@ -1320,10 +1309,10 @@ static int find_hands_sharded_host_impl(agh_ctx* ctx, const int32_t* sample_idx,
     return AGH_ERR_CAPACITY;
   }
   if (n > 0)
-    HIPCHK(c, hipMemcpy(out, c->d_out_own, sizeof(agh_hypothesis) * n, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(out, c->d_out_own, sizeof(agh_hypothesis) * n, hipMemcpyDeviceToHost));
   // (last_nout stays -1 for the merged list: the per-rank state the getters see is this rank's own part)
   int64_t mine = 0;
-  HIPCHK(c, hipMemcpy(&mine, c->d_nout_last, sizeof(int64_t), hipMemcpyDeviceToHost));
+  AGH_HIPCHK(c, hipMemcpy(&mine, c->d_nout_last, sizeof(int64_t), hipMemcpyDeviceToHost));
   c->last_nout = std::min<int64_t>(mine, c->shard_seg_records);
   return AGH_OK;
 }
@@ -1352,27 +1341,15 @@ static int classify_sharded_host_impl(agh_ctx* ctx, agh_hypothesis* out, uint8_t
     return AGH_ERR_STATE;
   }
   *entered = true;
-  HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipSetDevice(c->device));
   int pre_rc = AGH_OK;
   const char* pre_err = nullptr;
   const int64_t room = c->s_cap * 8;
-  if (room > c->keep_cap && !c->loc.active)  // (mid-chain the chain's classification writes d_keep)
+  // (mid-chain the chain's classification writes d_keep)
+  if (!c->loc.active && ensure_keep_buffers(c, room) != hipSuccess)
   {
-    if (c->d_keep)
-      (void) hipFree(c->d_keep);
-    if (c->d_svm_sums)
-      (void) hipFree(c->d_svm_sums);
-    c->d_keep = nullptr;
-    c->d_svm_sums = nullptr;
-    c->keep_cap = 0;
-    if (hipMalloc((void**) &c->d_keep, (size_t) room) == hipSuccess &&
-        hipMalloc((void**) &c->d_svm_sums, (size_t) room * sizeof(double)) == hipSuccess)
-      c->keep_cap = room;
-    else
-    {
-      pre_rc = AGH_ERR_HIP;  // (this rank still takes part in the exchange: agh_classify_sharded_device's comment)
-      pre_err = "out of device memory for the labels";
-    }
+    pre_rc = AGH_ERR_HIP;  // (this rank still takes part in the exchange: agh_classify_sharded_device's comment)
+    pre_err = "out of device memory for the labels";
   }
   bool in_coll = false;
   int rc = classify_sharded_device_impl(ctx, c->d_keep, c->stream, &in_coll, pre_rc, pre_err);
@@ -1393,10 +1370,10 @@ static int classify_sharded_host_impl(agh_ctx* ctx, agh_hypothesis* out, uint8_t
     return AGH_ERR_CAPACITY;
   }
   if (n > 0 && out)
-    HIPCHK(c, hipMemcpy(out, c->d_out_own, sizeof(agh_hypothesis) * n, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(out, c->d_out_own, sizeof(agh_hypothesis) * n, hipMemcpyDeviceToHost));
   if (n > 0 && keep)
   {
-    HIPCHK(c, hipMemcpy(keep, c->d_keep, (size_t) n, hipMemcpyDeviceToHost));
+    AGH_HIPCHK(c, hipMemcpy(keep, c->d_keep, (size_t) n, hipMemcpyDeviceToHost));
     int64_t k = 0;
     for (int64_t i = 0; i < n; i++)
       k += keep[i] ? 1 : 0;
