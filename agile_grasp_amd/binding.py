@@ -90,6 +90,7 @@ EXPORTS = [
     "agh_shard_slice", "agh_find_hands_sharded_device", "agh_find_hands_sharded", "agh_classify_sharded_device",
     "agh_classify_sharded", "agh_default_plane_params", "agh_remove_plane", "agh_get_plane_inliers",
     "agh_get_plane_candidates", "agh_plane_replay", "agh_set_cloud_cam_origins", "agh_get_cloud_cam_origins",
+    "agh_deproject", "agh_localize_depth", "agh_localize_depth_device", "agh_localize_depth_begin", "agh_localize_depth_stage",
 ]
 
 
@@ -166,6 +167,46 @@ class AghLocalizeResult(C.Structure):
 class AghLocalizeBatchResult(C.Structure):
     _fields_ = [("r", AghLocalizeResult), ("first_handle", C.c_int64), ("first_inlier_idx", C.c_int64), ("first_hand", C.c_int64),
                 ("first_sample", C.c_int64)]
+
+
+DEPTH_U16, DEPTH_F32 = 0, 1
+
+
+class AghDepthImage(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("row_stride_bytes", C.c_int64),
+                ("format", C.c_int32), ("depth_scale", C.c_float), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("pose", C.c_double * 12)]
+
+
+def depth_image_records(images):
+    """The agh_depth_image records of a capture.  `images`: one or two dicts with `data` (an (H, W) uint16 or float32 array whose
+    rows may be padded -- a column slice of a wider array -- or a torch CUDA tensor for the _device call), fx, fy, cx, cy, `pose`
+    (3 x 4, camera optical frame -> cloud frame) and, for uint16, depth_scale (default 0.001).  Returns (records, what keeps the
+    pixel buffers alive, on_device)."""
+    recs = (AghDepthImage * len(images))()
+    keep = []
+    on_device = any(hasattr(im["data"], "is_cuda") and im["data"].is_cuda for im in images)
+    for r, im in zip(recs, images):
+        d = im["data"]
+        if on_device:
+            assert d.is_cuda and d.dim() == 2 and d.stride(1) == 1
+            es = d.element_size()
+            r.data, r.height, r.width, r.row_stride_bytes = d.data_ptr(), int(d.shape[0]), int(d.shape[1]), int(d.stride(0)) * es
+            is_u16 = es == 2
+        else:
+            assert isinstance(d, np.ndarray) and d.ndim == 2 and d.dtype in (np.uint16, np.float32), "uint16 or float32 (H, W)"
+            assert d.strides[1] == d.itemsize and d.strides[0] >= d.shape[1] * d.itemsize, "rows must be contiguous"
+            r.data, r.height, r.width, r.row_stride_bytes = d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]
+            is_u16 = d.dtype == np.uint16
+        keep.append(d)
+        r.format = DEPTH_U16 if is_u16 else DEPTH_F32
+        r.depth_scale = float(im.get("depth_scale", 0.001))
+        r.fx, r.fy, r.cx, r.cy = float(im["fx"]), float(im["fy"]), float(im["cx"]), float(im["cy"])
+        pose = np.asarray(im["pose"], np.float64).reshape(-1)
+        assert pose.size == 12
+        for q in range(12):
+            r.pose[q] = float(pose[q])
+    return recs, keep, on_device
 
 
 def draw_samples(n_points: int, n_samples: int, seed: int) -> np.ndarray:
@@ -397,6 +438,25 @@ class Context:
             xyz = np.ascontiguousarray(xyz, np.float32)
             assert xyz.ndim == 2 and xyz.shape[1] >= 3
             xyz_ptr, n_pts, stride_b = _p(xyz, C.c_float), xyz.shape[0], xyz.shape[1] * 4
+        lp, samples, S, hcap = self._localize_params(size_left, workspace, samples, n_samples, sample_seed, classify, min_inliers,
+                                                     min_length, cell_size, dense, filters_boundaries)
+        handles, idx, hands, sout = self._loc_bufs
+        res = AghLocalizeResult()
+        if phase == "begin":  # agh_localize_begin: everything queued; localize_end() collects
+            assert not on_device
+            self._loc_keep = (xyz, samples, lp)  # (the capture must stay valid until the end call)
+            self._loc_S = S
+            self._check(self.lib.agh_localize_begin(self._h, xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts), C.byref(lp)))
+            return None
+        fn = self.lib.agh_localize_device if on_device else self.lib.agh_localize
+        self._check(fn(self._h, xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts), C.byref(lp), handles.ctypes.data_as(C.c_void_p),
+                       C.c_int64(hcap), _p(idx, C.c_int32), C.c_int64(hcap), hands.ctypes.data_as(C.c_void_p), C.c_int64(hcap),
+                       _p(sout, C.c_int32), C.byref(res)))
+        return self._localize_result(res, S)
+
+    def _localize_params(self, size_left, workspace, samples, n_samples, sample_seed, classify, min_inliers, min_length, cell_size,
+                         dense, filters_boundaries):
+        """The agh_localize_params record of a single-capture chain, and output buffers large enough for it (self._loc_bufs)."""
         lp = AghLocalizeParams()
         lp.size_left, lp.dense, lp.classify = size_left, 1 if dense else 0, 1 if classify else 0
         ws = np.ascontiguousarray(workspace, np.float64)
@@ -416,21 +476,55 @@ class Context:
         bufs = getattr(self, "_loc_bufs", None)
         hcap = max(min(8 * S, 8192), 1)
         if bufs is None or bufs[0].shape[0] < hcap or bufs[3].shape[0] < max(S, 1):
-            bufs = self._loc_bufs = (np.zeros(hcap, HANDLE_DTYPE), np.zeros(hcap, np.int32), np.zeros(hcap, HYP_DTYPE),
-                                     np.zeros(max(S, 1), np.int32))
-        handles, idx, hands, sout = bufs
+            self._loc_bufs = (np.zeros(hcap, HANDLE_DTYPE), np.zeros(hcap, np.int32), np.zeros(hcap, HYP_DTYPE),
+                              np.zeros(max(S, 1), np.int32))
+        return lp, samples, S, hcap
+
+    def deproject(self, images) -> np.ndarray:
+        """agh_deproject: the points k_deproject makes of a capture's depth images (see depth_image_records), (sum W x H, 3)
+        float32, image 0 first, pixels row-major, invalid pixels NaN."""
+        recs, _keep, on_device = depth_image_records(images)
+        assert not on_device
+        n = sum(int(r.width) * int(r.height) for r in recs)
+        out = np.empty((n, 3), np.float32)
+        got = self._check(self.lib.agh_deproject(self._h, recs, C.c_int32(len(recs)), _p(out, C.c_float), C.c_int64(n)))
+        assert got == n
+        return out
+
+    def localize_depth(self, images, workspace, samples=None, n_samples: int = 0, sample_seed: int = 1, classify: bool = True,
+                       min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003, phase: str = "both",
+                       filters_boundaries: bool = False):
+        """agh_localize_depth (torch CUDA tensors: agh_localize_depth_device): localize() straight from one or two depth images
+        (see depth_image_records); image k is camera k.  phase="begin": agh_localize_depth_begin, collected by localize_end()."""
+        recs, keep, on_device = depth_image_records(images)
+        lp, samples, S, hcap = self._localize_params(0, workspace, samples, n_samples, sample_seed, classify, min_inliers, min_length,
+                                                     cell_size, False, filters_boundaries)
+        handles, idx, hands, sout = self._loc_bufs
         res = AghLocalizeResult()
-        if phase == "begin":  # agh_localize_begin: everything queued; localize_end() collects
+        if phase == "begin":
             assert not on_device
-            self._loc_keep = (xyz, samples, lp)  # (the capture must stay valid until the end call)
+            self._loc_keep = (keep, samples, lp)  # (the pixel buffers must stay valid until the end call)
             self._loc_S = S
-            self._check(self.lib.agh_localize_begin(self._h, xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts), C.byref(lp)))
+            self._check(self.lib.agh_localize_depth_begin(self._h, recs, C.c_int32(len(recs)), C.byref(lp)))
             return None
-        fn = self.lib.agh_localize_device if on_device else self.lib.agh_localize
-        self._check(fn(self._h, xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts), C.byref(lp), handles.ctypes.data_as(C.c_void_p),
-                       C.c_int64(hcap), _p(idx, C.c_int32), C.c_int64(hcap), hands.ctypes.data_as(C.c_void_p), C.c_int64(hcap),
-                       _p(sout, C.c_int32), C.byref(res)))
+        fn = self.lib.agh_localize_depth_device if on_device else self.lib.agh_localize_depth
+        self._check(fn(self._h, recs, C.c_int32(len(recs)), C.byref(lp), handles.ctypes.data_as(C.c_void_p), C.c_int64(hcap),
+                       _p(idx, C.c_int32), C.c_int64(hcap), hands.ctypes.data_as(C.c_void_p), C.c_int64(hcap), _p(sout, C.c_int32),
+                       C.byref(res)))
         return self._localize_result(res, S)
+
+    def localize_depth_begin(self, images, workspace, **kw):
+        """agh_localize_depth_begin: the chain of this capture queued, nothing waited for; localize_end() collects it."""
+        return self.localize_depth(images, workspace, phase="begin", **kw)
+
+    def localize_depth_stage(self, images):
+        """agh_localize_depth_stage: the NEXT capture's images up on a second stream, beside the chain in flight.  Pass images
+        with the same pixel arrays to the next localize_depth_begin (the library recognises the set by pointers, sizes, strides
+        and formats)."""
+        recs, keep, on_device = depth_image_records(images)
+        assert not on_device
+        self._stage_keep = keep
+        self._check(self.lib.agh_localize_depth_stage(self._h, recs, C.c_int32(len(recs))))
 
     def localize_batch(self, captures, sizes_left, workspaces, samples=None, n_samples=0, sample_seeds=None,
                        classify: bool = True, min_inliers: int = 3, min_length: float = 0.005, filters_boundaries=0,

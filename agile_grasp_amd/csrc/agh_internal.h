@@ -214,10 +214,27 @@ struct LocalizeState
   int staged_captures = 0;    // 0 = the one capture of agh_localize_stage; C = the C captures of agh_localize_batch_stage,
   std::vector<const float*> staged_src;  // with these sources, strides and counts (one entry for agh_localize_stage's)
   std::vector<int64_t> staged_stride, staged_n;
+  // ... or, staged_depth, the depth images of agh_localize_depth_stage, rows packed, in d_depth_stage (depth.hip): one staged set
+  // of any kind; a points begin never adopts images, a depth begin never adopts points
+  bool staged_depth = false;
+  std::vector<agh_depth_image> staged_images;  // (data, width, height, row_stride_bytes and format identify the set)
+  bool staged_depth_is(const agh_depth_image* im, int count) const
+  {
+    if (!staged || !staged_depth || (int) staged_images.size() != count)
+      return false;
+    for (int k = 0; k < count; k++)
+    {
+      const agh_depth_image& s = staged_images[k];
+      if (s.data != im[k].data || s.width != im[k].width || s.height != im[k].height ||
+          s.row_stride_bytes != im[k].row_stride_bytes || s.format != im[k].format)
+        return false;
+    }
+    return true;
+  }
   // the begin that may adopt the staged set: is it these `count` captures (as_batch: of a batch), by pointer, stride and count?
   bool staged_is(const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int count, bool as_batch) const
   {
-    if (!staged || staged_captures != (as_batch ? count : 0) || (int) staged_src.size() != count)
+    if (!staged || staged_depth || staged_captures != (as_batch ? count : 0) || (int) staged_src.size() != count)
       return false;
     for (int k = 0; k < count; k++)
       if (staged_src[k] != xyz[k] || staged_stride[k] != stride_bytes[k] || staged_n[k] != n[k])
@@ -287,6 +304,12 @@ struct Ctx
   bool raw_read_set = false, stage_read_set = false;    // d_stage_xyz (they change places with the buffers)
   LocalizeState loc;
   int64_t raw_cap = 0;             // floats
+  // agh_localize_depth* (depth.hip): a host capture's depth images, rows packed, image k at depth_image_offset(k); the NEXT
+  // capture's (agh_localize_depth_stage) in the second buffer; the two change places when a staged set is adopted
+  uint8_t* d_depth = nullptr;
+  uint8_t* d_depth_stage = nullptr;
+  int64_t depth_cap = 0, depth_stage_cap = 0;  // bytes
+  hipEvent_t depth_read = nullptr;  // recorded on `stream` behind the last k_deproject that read one of the two
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
   LocalizeBatchState* lbatch = nullptr;  // agh_localize_batch's buffers (localize_batch.hip), made by its first call
   bool batch_active = false;       // inside agh_localize_batch (agh_localize_begin refuses)
@@ -1258,5 +1281,11 @@ int flags_to_status(agh::Ctx* c, const int32_t* flags);
 // its synchronisation (the capacity-class repeat, the sequential-walk repeat, the limits)
 int stage_captures(agh_ctx* ctx, const char* who, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int C,
   bool as_batch);
+// depth.hip: the third source kind of the localize chain.  depth_check: the argument rules of include/agh.h (the error text names
+// the image and the field).  depth_to_raw: the images (host: uploaded into d_depth on `st`, or adopted from a staged set when
+// use_staged; device: read in place) back-projected by k_deproject on `st` into d_raw_xyz, packed, stride 12.
+int depth_check(agh::Ctx* c, const char* who, const agh_depth_image* images, int32_t n_images, bool on_device, int64_t* n_points);
+int depth_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, int n_images, bool on_device, bool use_staged,
+  hipStream_t st);
 int chain_collect(agh_ctx* ctx, const char* who, bool label_captures, int C, const int* counts, int count_stride, int64_t S_tot,
   const int* bad, int (*requeue)(agh_ctx*, bool handles_only));

@@ -1,6 +1,7 @@
 // localize.hip -- the online chain of the reference's only online caller as one call (or two halves of one):
 // GraspLocalizer::localizeGrasps, grasp_localizer.cpp:95-103 = localizeHands -> predictAntipodalHands -> findHandles per capture.
-// agh_localize / agh_localize_device / agh_localize_begin / agh_localize_stage / agh_localize_end of include/agh.h; the stages
+// agh_localize / agh_localize_device / agh_localize_begin / agh_localize_stage / agh_localize_end and agh_localize_depth* of
+// include/agh.h (the back-projection of depth images: depth.hip); the stages
 // themselves (preprocessing, search, classification, handle search) are api.hip's, voxelize.hip's, hog_svm.hip's and handles.hip's.
 #include "agh_internal.h"
 
@@ -101,6 +102,7 @@ int stage_captures(agh_ctx* ctx, const char* who, const float* const* xyz, const
   L.staged_stride.assign(stride_bytes, stride_bytes + C);
   L.staged_n.assign(n, n + C);
   L.staged_captures = as_batch ? C : 0;
+  L.staged_depth = false;
   L.staged = true;
   return AGH_OK;
 }
@@ -232,7 +234,18 @@ static int localize_queue(agh_ctx* ctx, bool handles_only)
   return rc;
 }
 
-static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int64_t stride_bytes, int64_t n, const agh_localize_params* lp)
+// A capture given as depth images (include/agh.h, agh_localize_depth*): the chain's third source kind, beside host points and
+// device points.  k_deproject (depth.hip) fills the context's raw buffer; from there on the chain is the points chain's.
+struct DepthSource
+{
+  const agh_depth_image* images;
+  int32_t n_images;
+  bool on_device;
+  const char* who;  // the entry point, for the error texts
+};
+
+static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int64_t stride_bytes, int64_t n,
+  const agh_localize_params* lp, const DepthSource* depth = nullptr)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
@@ -240,15 +253,27 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   LocalizeState& L = c->loc;
   if (L.active)
   {
-    c->err = "agh_localize_begin: a chain is in flight (agh_localize_end first)";
+    c->err = std::string(depth ? depth->who : "agh_localize_begin") + ": a chain is in flight (agh_localize_end first)";
     return AGH_ERR_STATE;
   }
   if (c->batch_active)
   {
-    c->err = "agh_localize_begin: an agh_localize_batch is running on this context";
+    c->err = std::string(depth ? depth->who : "agh_localize_begin") + ": an agh_localize_batch is running on this context";
     return AGH_ERR_STATE;
   }
-  if (!lp || bad_capture(xyz, stride_bytes, n) || !(lp->cell_size > 0.0) || lp->size_left < 0 || lp->n_samples < 0 ||
+  agh_localize_params lp_depth;
+  if (depth && lp)
+  {
+    // (the arguments of the images first: their sizes are the capture's; then size_left and dense as include/agh.h fixes them)
+    if (int rc = depth_check(c, depth->who, depth->images, depth->n_images, depth->on_device, &n))
+      return rc;
+    lp_depth = *lp;
+    lp_depth.size_left = (int64_t) depth->images[0].width * depth->images[0].height;
+    lp_depth.dense = 1;
+    lp = &lp_depth;
+    stride_bytes = 12;
+  }
+  if (!lp || (!depth && bad_capture(xyz, stride_bytes, n)) || !(lp->cell_size > 0.0) || lp->size_left < 0 || lp->n_samples < 0 ||
       lp->n_samples > (1 << 24) || lp->min_inliers < 1)
   {
     c->err = "agh_localize: bad arguments (see include/agh.h)";
@@ -280,7 +305,13 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   // can ----
   const int64_t dev_stride = xyz_on_device ? stride_bytes : device_stride(stride_bytes);
   const float* d_raw = xyz;
-  if (!xyz_on_device)
+  if (depth)
+  {
+    if ((rc = depth_to_raw(ctx, depth->who, depth->images, depth->n_images, depth->on_device, true, st)) != AGH_OK)
+      return rc;
+    d_raw = c->d_raw_xyz;
+  }
+  else if (!xyz_on_device)
   {
     if (L.staged_is(&xyz, &stride_bytes, &n, 1, false) && c->d_stage_xyz)
     {
@@ -447,7 +478,7 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
 // agh_localize[_device] = begin + end
 static int localize_call(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int64_t stride_bytes, int64_t n,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result, const DepthSource* depth = nullptr)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
@@ -455,7 +486,7 @@ static int localize_call(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int
     *result = agh_localize_result{ 0, 0, 0, 0, 0 };
   int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
   if (rc == AGH_OK)
-    rc = localize_begin_impl(ctx, xyz, xyz_on_device, stride_bytes, n, lp);
+    rc = localize_begin_impl(ctx, xyz, xyz_on_device, stride_bytes, n, lp, depth);
   if (rc != AGH_OK)
     return rc;
   return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
@@ -482,6 +513,30 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
 int agh_localize_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp)
 {
   return localize_begin_impl(ctx, xyz, false, stride_bytes, n, lp);
+}
+
+int agh_localize_depth(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  const DepthSource src{ images, n_images, false, "agh_localize_depth" };
+  return localize_call(ctx, nullptr, false, 12, 0, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
+    samples_out, result, &src);
+}
+
+int agh_localize_depth_device(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  const DepthSource src{ images, n_images, true, "agh_localize_depth_device" };
+  return localize_call(ctx, nullptr, false, 12, 0, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
+    samples_out, result, &src);
+}
+
+int agh_localize_depth_begin(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp)
+{
+  const DepthSource src{ images, n_images, false, "agh_localize_depth_begin" };
+  return localize_begin_impl(ctx, nullptr, false, 12, 0, lp, &src);
 }
 
 int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,

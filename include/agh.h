@@ -274,13 +274,14 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  *   agh_localize_end(ctx, outputs)        the one synchronisation; cloud k's results, exactly agh_localize's
  *   agh_localize_begin(ctx, cloud k + 1)  recognises the staged capture (same pointer, stride and count): no upload
  * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a begin).
- * Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_end,
+ * Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_depth_stage,
+ * agh_localize_end,
  * agh_get_cloud_cam_origins, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
  * agh_destroy, the host-side counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats, agh_get_grid_desc) and the
  * communicator's bookkeeping (agh_comm_rank, agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault,
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
  * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
- * agh_find_handles, agh_localize*, agh_remove_plane, agh_get_cloud and every getter of device results (frames, normals,
+ * agh_find_handles, agh_localize*, agh_deproject, agh_remove_plane, agh_get_cloud and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -294,6 +295,65 @@ int agh_localize_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int
 int agh_localize_stage(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n);
 int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result);
+
+/* The same chain straight from DEPTH IMAGES: a depth sensor's driver produces a depth image per camera, and a host-side
+ * nodelet expands it into the points agh_localize takes (/camera/depth_registered/points, launch/single_camera_grasps.launch).
+ * Here the images go up as they are (2 or 4 bytes per pixel instead of 12..32 per point) and one kernel, k_deproject,
+ * back-projects them on the context's stream into the raw buffer an upload would have filled; the chain then runs unchanged on
+ * that packed stride-12 array of sum W x H points, image 0 first, pixels row-major.
+ * n_images is 1 or 2; image k is camera k: a point's camera id is its image's index.  lp->size_left and lp->dense are
+ * ignored: the chain runs with size_left = W0 x H0 and dense = 1.  With dense = 1 the voxeliser ranks by RAW index and its
+ * workspace comparisons are false for NaN, so the invalid pixels fall out there and every kept point keeps the right id;
+ * dense = 0 would shift camera 1's first points into camera 0 (the reference does not re-index after its NaN removal) --
+ * harmless for a few drop-outs, wrong for the 10-40 % invalid pixels of a depth image.
+ * Arithmetic, all float32, evaluated left to right, never contracted: the host rounds once, kx = (float) (1.0 / fx), ky,
+ * cxf = (float) cx, cyf, and the twelve pose entries; per pixel (u, v): z = (float) raw * depth_scale (U16) or the pixel
+ * (F32); x = (((float) u - cxf) * z) * kx, y likewise with v, cyf, ky; X = ((r00 * x + r01 * y) + r02 * z) + t0, Y and Z
+ * with their rows of the pose.  An invalid pixel (U16: raw 0; F32: a value not in (0, +inf)) writes three quiet NaNs.
+ * agh_localize_depth returns, bit for bit (epoch aside), what agh_localize returns for the array agh_deproject writes, with
+ * stride 12, size_left = W0 x H0, dense = 1 and the same lp.
+ * The pose does NOT set the camera origins, which stay the context's (agh_params::cam_origin, or the one-row table of
+ * agh_set_cloud_cam_origins): a caller sets cam_origin[k] to the translation of image k's pose.
+ * AGH_ERR_INVALID_ARGUMENT, the text naming the image and the field, nothing launched: NULL images or data; n_images not 1
+ * or 2; width or height outside 1..8192; a row_stride_bytes below width x element size or no multiple of the element size;
+ * an unknown format; for agh_localize_depth_device a data pointer that is no multiple of the element size (a host image may
+ * lie anywhere: its copy repacks it); fx or fy zero or non-finite; a non-finite cx, cy or pose entry; for U16 a depth_scale that is non-finite
+ * or <= 0.  Everything else -- AGH_ERR_NO_SVM, AGH_ERR_CAPACITY, AGH_ERR_STATE mid-chain, the one-row rule for a camera-origin
+ * table, the repeats inside the call -- is as for agh_localize. */
+#define AGH_DEPTH_U16 0   /* uint16 raw units (ROS 16UC1); 0 = no reading */
+#define AGH_DEPTH_F32 1   /* float32 metres (ROS 32FC1); valid iff 0 < z < +inf */
+typedef struct agh_depth_image
+{
+  const void* data;          /* row-major, row v at data + v * row_stride_bytes */
+  int32_t width, height;     /* 1 .. 8192 each */
+  int64_t row_stride_bytes;  /* >= width * element size, a multiple of the element size */
+  int32_t format;            /* AGH_DEPTH_* */
+  float depth_scale;         /* U16: metres per unit (0.001f); F32: ignored */
+  double fx, fy, cx, cy;     /* pinhole intrinsics, pixels */
+  double pose[12];           /* row-major 3x4 [R|t]: camera optical frame -> cloud frame */
+} agh_depth_image;
+/* Introspection and tests: the points k_deproject makes of the images, sum W x H packed float32 triples, into host memory.
+ * Returns the point count, or AGH_ERR_CAPACITY if cap_points is smaller.  Refused (AGH_ERR_STATE) while a chain is in flight. */
+int agh_deproject(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, float* xyz_out, int64_t cap_points);
+/* Host images (uploaded with their rows packed into a depth buffer of the context) ... */
+int agh_localize_depth(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result);
+/* ... or images whose `data` are device pointers, aligned to the element size, read in place with their row strides (valid
+ * until the call returns). */
+int agh_localize_depth_device(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result);
+/* The two halves, as agh_localize_begin / agh_localize_stage: a chain begun with agh_localize_depth_begin is collected with
+ * agh_localize_end; agh_localize_depth_stage copies the NEXT capture's images into a second depth buffer on the stage stream
+ * (allowed between begin and end, and without a chain), and the next agh_localize_depth_begin adopts them when n_images and
+ * every (data, width, height, row_stride_bytes, format) match: the depth buffers change places, the chain waits for the copy,
+ * nothing is uploaded (intrinsics, scale and pose are read at begin).  The context still has ONE staged set, of any kind: a
+ * newer stage of any kind replaces it; a begin of another kind drops it, and the chain waits for its copy; a points begin
+ * never adopts depth images and a depth begin never adopts points.  The image records are copied by the calls; the pixel
+ * buffers follow agh_localize_begin's lifetime rules. */
+int agh_localize_depth_begin(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp);
+int agh_localize_depth_stage(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images);
 
 /* The chain of agh_localize over a BATCH of captures in one call, with ONE synchronisation (offline evaluation over a
  * directory of PCD pairs, a cell with several sensors or arms): 1 <= n_captures <= 64, fewer than 2^30 raw points in all.

@@ -373,6 +373,74 @@ public:
     return true;
   }
 
+  /** Additional: the chain of localize straight from the sensor's depth images (agh_localize_depth): one or two images, image k
+   *  is camera k; no host-side expansion to points, and 2 or 4 bytes per pixel go up instead of a 32-byte point.  An image
+   *  without a pose takes this search's k-th camera transform.  Outputs as for localize.  @return false (after printing) on error */
+  bool localizeDepth(const std::vector<DepthImage>& images, const VectorXd& workspace, double cell_size,
+    const std::vector<int>& indices, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<agh_hypothesis>& hands_out, std::vector<agh_handle>& handles_out, std::vector<std::int32_t>& inliers_out,
+    bool filters_boundaries = false)
+  {
+    hands_out.clear();
+    handles_out.clear();
+    inliers_out.clear();
+    return localizeDepthBegin(images, workspace, cell_size, indices, svm_filename, min_inliers, min_length, filters_boundaries) &&
+           localizeEnd(hands_out, handles_out, inliers_out);
+  }
+
+  /** agh_localize_depth_begin: the chain queued, collected by localizeEnd; between the two, localizeDepthStage(next) uploads the
+   *  next capture's images on a second stream, and the localizeDepthBegin that is later handed the same pixel buffers finds them
+   *  on the device.  The pixel buffers must stay alive and unchanged until localizeEnd has returned. */
+  bool localizeDepthBegin(const std::vector<DepthImage>& images, const VectorXd& workspace, double cell_size,
+    const std::vector<int>& indices, const std::string& svm_filename, int min_inliers, double min_length,
+    bool filters_boundaries = false)
+  {
+    if (!ensureContext())
+      return false;
+    if (agh_load_svm_file(ctx_, svm_filename.c_str()) != AGH_OK)
+    {
+      std::cout << " Exception: " << agh_last_error(ctx_) << "\n";  // learning.cpp:187-191
+      return false;
+    }
+    agh_localize_params lp;
+    lp.size_left = 0;  // (ignored: the first image's pixels are camera 0's)
+    lp.dense = 1;
+    lp.classify = 1;
+    for (int i = 0; i < 6; i++)
+      lp.workspace[i] = workspace(i);
+    lp.cell_size = cell_size;
+    std::vector<std::int32_t> idx(indices.begin(), indices.end());  // (copied by agh_localize_depth_begin)
+    lp.sample_idx = idx.empty() ? nullptr : idx.data();
+    lp.n_samples = idx.empty() ? (std::int64_t) (num_samples_ < 0 ? 0 : num_samples_) : (std::int64_t) idx.size();
+    lp.sample_seed = sample_seed_set_ ? (std::uint64_t) sample_seed_ : (std::uint64_t) std::time(nullptr);
+    lp.min_inliers = min_inliers;
+    lp.filters_boundaries = filters_boundaries ? 1 : 0;
+    lp.min_length = min_length;
+    const std::vector<agh_depth_image> recs = depthRecords(images);
+    if (agh_localize_depth_begin(ctx_, recs.empty() ? nullptr : recs.data(), (std::int32_t) recs.size(), &lp) != AGH_OK)
+    {
+      fail("agh_localize_depth_begin");
+      return false;
+    }
+    loc_cap_ = lp.n_samples * 8 < 8192 ? lp.n_samples * 8 + 1 : 8193;  // (only a Begin that went through: see localizeBatchBegin)
+    last_samples_.assign((std::size_t) lp.n_samples, 0);
+    return true;
+  }
+
+  /** agh_localize_depth_stage: the NEXT capture's images up, beside the chain in flight */
+  bool localizeDepthStage(const std::vector<DepthImage>& next)
+  {
+    if (!ensureContext())
+      return false;
+    const std::vector<agh_depth_image> recs = depthRecords(next);
+    if (agh_localize_depth_stage(ctx_, recs.empty() ? nullptr : recs.data(), (std::int32_t) recs.size()) != AGH_OK)
+    {
+      fail("agh_localize_depth_stage");
+      return false;
+    }
+    return true;
+  }
+
   /** Additional: the chain of localize over several captures in one call (agh_localize_batch): capture k is clouds[k] with
    *  sizes_left[k], workspaces[k] and indices[k] (empty: num_samples drawn on the device, seeded with the sample seed + k).
    *  Per capture the hands the classifier kept, the handles and their inlier lists (indices into that capture's hands), exactly
@@ -734,6 +802,32 @@ public:
   }
 
 private:
+  // the ABI's records of the images (the library checks them, and their number)
+  std::vector<agh_depth_image> depthRecords(const std::vector<DepthImage>& images) const
+  {
+    std::vector<agh_depth_image> recs(images.size());
+    for (std::size_t k = 0; k < images.size(); k++)
+    {
+      const DepthImage& im = images[k];
+      agh_depth_image& r = recs[k];
+      r.data = im.data;
+      r.width = (std::int32_t) im.width;
+      r.height = (std::int32_t) im.height;
+      r.row_stride_bytes = im.row_stride_bytes;
+      r.format = im.is_float ? AGH_DEPTH_F32 : AGH_DEPTH_U16;
+      r.depth_scale = im.depth_scale;
+      r.fx = im.fx;
+      r.fy = im.fy;
+      r.cx = im.cx;
+      r.cy = im.cy;
+      const Matrix4d& tf = im.has_pose ? im.pose : (k == 0 ? cam_tf_left_ : cam_tf_right_);
+      for (int row = 0; row < 3; row++)
+        for (int col = 0; col < 4; col++)
+          r.pose[4 * row + col] = mat4(tf, row, col);
+    }
+    return recs;
+  }
+
   std::vector<GraspHypothesis> fail(const char* what)
   {
     std::cout << " Error in " << what << ": " << agh_last_error(ctx_) << "\n";

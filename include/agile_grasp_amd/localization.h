@@ -263,7 +263,7 @@ public:
   bool localizeHandlesBegin(const PointCloud::Ptr& cloud_in, int size_left, const std::vector<int>& indices,
     const std::string& svm_filename, int min_inliers, double min_length)
   {
-    if (pending_cloud_)  // (one chain at a time: the one in flight stays pending, for its localizeHandlesEnd)
+    if (pending_cloud_ || pending_depth_)  // (one chain at a time: the one in flight stays pending, for its localizeHandlesEnd)
     {
       std::cout << " Error: localizeHandlesBegin while a chain is pending (localizeHandlesEnd first)\n";
       return false;
@@ -302,16 +302,71 @@ public:
     std::vector<Handle> handle_list;
     if (antipodal_hands)
       antipodal_hands->clear();
-    if (!pending_cloud_)
+    if (!pending_cloud_ && !pending_depth_)
       return handle_list;
-    PointCloud::Ptr cloud_in = pending_cloud_;
+    PointCloud::Ptr cloud_in = pending_cloud_;  // (none for a chain begun from depth images)
     pending_cloud_ = PointCloud::Ptr();
+    pending_depth_ = false;
     std::vector<agh_hypothesis> hands;
     std::vector<agh_handle> handles;
     std::vector<std::int32_t> idx;
     if (!search_->localizeEnd(hands, handles, idx))
       return handle_list;
     return toHandles(cloud_in, hands, handles, idx, antipodal_hands);
+  }
+
+  /** Additional: localizeHandles straight from the sensor's depth images (agh_localize_depth): one or two images, image k is
+   *  camera k, an image without a pose takes the k-th transform of setCameraTransforms (whose translations are the camera
+   *  origins of the search either way).  No cloud is built on the host; otherwise as localizeHandles. */
+  std::vector<Handle> localizeHandlesDepth(const std::vector<DepthImage>& images, const std::vector<int>& indices,
+    const std::string& svm_filename, int min_inliers, double min_length, std::vector<GraspHypothesis>* antipodal_hands = nullptr)
+  {
+    if (antipodal_hands)
+      antipodal_hands->clear();
+    if (!localizeHandlesDepthBegin(images, indices, svm_filename, min_inliers, min_length))
+      return std::vector<Handle>();
+    return localizeHandlesEnd(antipodal_hands);
+  }
+
+  /** ... and as two calls, for a node that holds the NEXT pair of images while this one is searched:
+   *      loc.localizeHandlesDepthBegin(images_k, indices, svm, min_inliers, 0.005);   // queued, not waited for
+   *      loc.stageNextDepth(images_k1);                                               // their upload runs under capture k's kernels
+   *      handles = loc.localizeHandlesEnd(&antipodal_hands);                          // the one synchronisation
+   *      loc.localizeHandlesDepthBegin(images_k1, ...);                               // finds capture k + 1 on the device
+   *  The pixel buffers must stay alive and unchanged until the localizeHandlesEnd of their chain has returned. */
+  bool localizeHandlesDepthBegin(const std::vector<DepthImage>& images, const std::vector<int>& indices,
+    const std::string& svm_filename, int min_inliers, double min_length)
+  {
+    if (pending_cloud_ || pending_depth_ || !pending_batch_.empty())
+    {
+      std::cout << " Error: localizeHandlesDepthBegin while a chain is pending (localizeHandlesEnd first)\n";
+      return false;
+    }
+    if (images.empty())
+    {
+      std::cout << "Input cloud is empty!\n";
+      return false;
+    }
+    std::ifstream f(svm_filename.c_str());
+    if (!f.good())
+    {
+      std::cout << " Error: File " << svm_filename << " does not exist!\n";  // learning.cpp:172-178
+      return false;
+    }
+    ensureSearch();
+    if (!search_->localizeDepthBegin(images, workspace_, 0.003, indices, svm_filename, min_inliers, min_length, filters_boundaries_))
+      return false;
+    pending_depth_ = true;
+    return true;
+  }
+
+  /** agh_localize_depth_stage through the adapter: the next capture's images up, beside the chain in flight */
+  bool stageNextDepth(const std::vector<DepthImage>& next)
+  {
+    if (next.empty())
+      return false;
+    ensureSearch();
+    return search_->localizeDepthStage(next);
   }
 
   /** Additional: localizeHandles over several captures in one call (agh_localize_batch, one synchronisation): capture k is
@@ -326,7 +381,7 @@ public:
     std::vector<std::vector<Handle> > out(C);
     if (antipodal_hands_per_cloud)
       antipodal_hands_per_cloud->assign(C, std::vector<GraspHypothesis>());
-    if (pending_cloud_)
+    if (pending_cloud_ || pending_depth_)
     {
       std::cout << " Error: localizeHandlesBatch while a chain is pending (localizeHandlesEnd first)\n";
       return out;
@@ -368,7 +423,7 @@ public:
     const std::vector<std::vector<int> >& indices_per_cloud, const std::string& svm_filename, int min_inliers, double min_length,
     const std::vector<VectorXd>* workspaces = nullptr)
   {
-    if (pending_cloud_ || !pending_batch_.empty())  // (the chain in flight stays pending, for its End)
+    if (pending_cloud_ || pending_depth_ || !pending_batch_.empty())  // (the chain in flight stays pending, for its End)
     {
       std::cout << " Error: localizeHandlesBatchBegin while a chain is pending (its End first)\n";
       return false;
@@ -444,7 +499,7 @@ public:
         antipodal_hands_per_cloud->assign(clouds.size(), std::vector<GraspHypothesis>());
       return std::vector<std::vector<Handle> >(clouds.size());
     }
-    if (pending_cloud_)  // (the plain overload prints the error and returns the empty lists; a chain in flight keeps the table it has)
+    if (pending_cloud_ || pending_depth_)  // (the plain overload prints the error and returns the empty lists; a chain in flight keeps the table it has)
       return localizeHandlesBatch(clouds, sizes_left, indices_per_cloud, svm_filename, min_inliers, min_length, antipodal_hands_per_cloud,
         workspaces);
     ensureSearch();
@@ -465,7 +520,8 @@ public:
     const std::vector<agh_handle>& handles, const std::vector<std::int32_t>& idx, std::vector<GraspHypothesis>* antipodal_hands)
   {
     std::vector<Handle> handle_list;
-    remove_nan_in_place(*cloud_in);  // localization.cpp:27 filters the caller's cloud in place
+    if (cloud_in)  // (a chain begun from depth images has no host cloud)
+      remove_nan_in_place(*cloud_in);  // localization.cpp:27 filters the caller's cloud in place
     if (filters_boundaries_)
       std::cout << "Filtering out hands close to workspace boundaries ... (on the device, ahead of the classifier)\n";
     std::shared_ptr<std::vector<GraspHypothesis> > kept(new std::vector<GraspHypothesis>());
@@ -553,6 +609,7 @@ private:
   bool keeps_training_images_ = false;
   // localizeHandlesBegin -> localizeHandlesEnd
   PointCloud::Ptr pending_cloud_;
+  bool pending_depth_ = false;  // (localizeHandlesDepthBegin -> localizeHandlesEnd: a chain without a host cloud)
   // localizeHandlesBatchBegin -> localizeHandlesBatchEnd
   std::vector<PointCloud::Ptr> pending_batch_;
   std::unique_ptr<HandSearch> search_;

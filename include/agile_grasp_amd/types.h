@@ -135,6 +135,30 @@ inline void remove_nan_in_place(PointCloud& c)
 }  // namespace agile_grasp_amd
 #endif
 
+namespace agile_grasp_amd
+{
+// One camera's depth image as the sensor's driver hands it over (sensor_msgs/Image, 16UC1 or 32FC1), for the chain that starts
+// from depth images (agh_localize_depth, include/agh.h): the pixels stay the caller's.  Without a pose (has_pose = false) image k
+// takes the k-th camera transform of the object it is handed to (HandSearch's cam_tf_left / setCamTfRight,
+// Localization::setCameraTransforms).
+struct DepthImage
+{
+  const void* data;                // row-major; row v at data + v * row_stride_bytes
+  int width, height;
+  std::int64_t row_stride_bytes;   // sensor_msgs/Image::step
+  bool is_float;                   // false: uint16 raw units (16UC1, 0 = no reading); true: float32 metres (32FC1)
+  float depth_scale;               // uint16: metres per unit
+  double fx, fy, cx, cy;           // sensor_msgs/CameraInfo::K
+  bool has_pose;
+  Matrix4d pose;                   // camera optical frame -> cloud frame
+  DepthImage()
+    : data(nullptr), width(0), height(0), row_stride_bytes(0), is_float(false), depth_scale(0.001f), fx(0), fy(0), cx(0), cy(0),
+      has_pose(false)
+  {
+  }
+};
+}  // namespace agile_grasp_amd
+
 static_assert(sizeof(float) == 4, "float32 expected");
 
 #endif
