@@ -440,18 +440,22 @@ class Context:
             xyz_ptr, n_pts, stride_b = _p(xyz, C.c_float), xyz.shape[0], xyz.shape[1] * 4
         lp, samples, S, hcap = self._localize_params(size_left, workspace, samples, n_samples, sample_seed, classify, min_inliers,
                                                      min_length, cell_size, dense, filters_boundaries)
-        handles, idx, hands, sout = self._loc_bufs
-        res = AghLocalizeResult()
         if phase == "begin":  # agh_localize_begin: everything queued; localize_end() collects
             assert not on_device
-            self._loc_keep = (xyz, samples, lp)  # (the capture must stay valid until the end call)
-            self._loc_S = S
             self._check(self.lib.agh_localize_begin(self._h, xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts), C.byref(lp)))
+            self._loc_keep = (xyz, samples, lp)  # (the capture must stay valid until the end call)
+            self._loc_S = S  # (like _loc_keep only once the chain is queued: a refused begin leaves the one in flight its own)
             return None
         fn = self.lib.agh_localize_device if on_device else self.lib.agh_localize
-        self._check(fn(self._h, xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts), C.byref(lp), handles.ctypes.data_as(C.c_void_p),
-                       C.c_int64(hcap), _p(idx, C.c_int32), C.c_int64(hcap), hands.ctypes.data_as(C.c_void_p), C.c_int64(hcap),
-                       _p(sout, C.c_int32), C.byref(res)))
+        return self._localize_blocking(fn, (xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts)), lp, S, hcap)
+
+    def _localize_blocking(self, fn, capture_args, lp, S, hcap):
+        """The tail of the one-call forms: the output buffers, the blocking library call, the result dict."""
+        handles, idx, hands, sout = self._loc_bufs
+        res = AghLocalizeResult()
+        self._check(fn(self._h, *capture_args, C.byref(lp), handles.ctypes.data_as(C.c_void_p), C.c_int64(hcap),
+                       _p(idx, C.c_int32), C.c_int64(hcap), hands.ctypes.data_as(C.c_void_p), C.c_int64(hcap), _p(sout, C.c_int32),
+                       C.byref(res)))
         return self._localize_result(res, S)
 
     def _localize_params(self, size_left, workspace, samples, n_samples, sample_seed, classify, min_inliers, min_length, cell_size,
@@ -499,19 +503,14 @@ class Context:
         recs, keep, on_device = depth_image_records(images)
         lp, samples, S, hcap = self._localize_params(0, workspace, samples, n_samples, sample_seed, classify, min_inliers, min_length,
                                                      cell_size, False, filters_boundaries)
-        handles, idx, hands, sout = self._loc_bufs
-        res = AghLocalizeResult()
         if phase == "begin":
             assert not on_device
+            self._check(self.lib.agh_localize_depth_begin(self._h, recs, C.c_int32(len(recs)), C.byref(lp)))
             self._loc_keep = (keep, samples, lp)  # (the pixel buffers must stay valid until the end call)
             self._loc_S = S
-            self._check(self.lib.agh_localize_depth_begin(self._h, recs, C.c_int32(len(recs)), C.byref(lp)))
             return None
         fn = self.lib.agh_localize_depth_device if on_device else self.lib.agh_localize_depth
-        self._check(fn(self._h, recs, C.c_int32(len(recs)), C.byref(lp), handles.ctypes.data_as(C.c_void_p), C.c_int64(hcap),
-                       _p(idx, C.c_int32), C.c_int64(hcap), hands.ctypes.data_as(C.c_void_p), C.c_int64(hcap), _p(sout, C.c_int32),
-                       C.byref(res)))
-        return self._localize_result(res, S)
+        return self._localize_blocking(fn, (recs, C.c_int32(len(recs))), lp, S, hcap)
 
     def localize_depth_begin(self, images, workspace, **kw):
         """agh_localize_depth_begin: the chain of this capture queued, nothing waited for; localize_end() collects it."""

@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <ctime>
+#include <fstream>
 #include <iostream>
 #include <memory>
 #include <string>
@@ -29,6 +30,25 @@
 
 namespace agile_grasp_amd
 {
+
+namespace detail
+{
+/** The two SVM-file steps of Learning::classify, shared by every call that classifies (Learning, HandSearch, Localization). */
+inline bool svmFileExists(const std::string& svm_filename)
+{
+  std::ifstream f(svm_filename.c_str());
+  if (!f.good())
+    std::cout << " Error: File " << svm_filename << " does not exist!\n";  // learning.cpp:172-178
+  return f.good();
+}
+inline bool loadSvm(agh_ctx* ctx, const std::string& svm_filename)
+{
+  if (agh_load_svm_file(ctx, svm_filename.c_str()) == AGH_OK)
+    return true;
+  std::cout << " Exception: " << agh_last_error(ctx) << "\n";  // learning.cpp:187-191
+  return false;
+}
+}  // namespace detail
 
 class HandSearch
 {
@@ -246,33 +266,14 @@ public:
     for (int i = 0; i < 6; i++)
       ws[i] = workspace(i);
     std::int64_t nv = 0;
-    const std::int64_t n = (std::int64_t) cloud_in->size();
-    int rc = agh_preprocess(ctx_, n > 0 ? &cloud_in->points[0].x : nullptr, (std::int64_t) sizeof(cloud_in->points[0]), n,
-      (std::int64_t) size_left, cloud_is_dense(*cloud_in) ? 1 : 0, ws, cell_size, &nv);
-    if (rc != AGH_OK)
+    const RawPoints in = rawPoints(*cloud_in);
+    if (agh_preprocess(ctx_, in.xyz, in.stride, in.n, (std::int64_t) size_left, cloud_is_dense(*cloud_in) ? 1 : 0, ws, cell_size,
+          &nv) != AGH_OK)
     {
       fail("agh_preprocess");
       return false;
     }
-    std::vector<float> xyz(3 * (std::size_t) nv + 3);
-    std::vector<std::int32_t> cam((std::size_t) nv + 1);
-    if (agh_get_cloud(ctx_, xyz.data(), cam.data(), nv) < 0)
-    {
-      fail("agh_get_cloud");
-      return false;
-    }
-    voxels_out.reset(new PointCloud);
-    voxels_out->points.resize((std::size_t) nv);
-    pts_cam_source_out = VectorXi((std::size_t) nv);
-    for (std::int64_t i = 0; i < nv; i++)
-    {
-      voxels_out->points[(std::size_t) i].x = xyz[3 * (std::size_t) i];
-      voxels_out->points[(std::size_t) i].y = xyz[3 * (std::size_t) i + 1];
-      voxels_out->points[(std::size_t) i].z = xyz[3 * (std::size_t) i + 2];
-      pts_cam_source_out((std::size_t) i) = cam[(std::size_t) i];
-    }
-    searched_n_ = nv;
-    return true;
+    return readBackCloud(nv, voxels_out, pts_cam_source_out);
   }
 
   /** The table-plane removal of localization.cpp:51-98 (pcl::SACSegmentation, RANSAC plane, then ExtractIndices with
@@ -292,26 +293,7 @@ public:
       fail("agh_remove_plane");
       return false;
     }
-    const std::int64_t m = result.n_remaining;
-    std::vector<float> xyz(3 * (std::size_t) m + 3);
-    std::vector<std::int32_t> cam((std::size_t) m + 1);
-    if (agh_get_cloud(ctx_, xyz.data(), cam.data(), m) < 0)
-    {
-      fail("agh_get_cloud");
-      return false;
-    }
-    cloud_out.reset(new PointCloud);
-    cloud_out->points.resize((std::size_t) m);
-    pts_cam_source_out = VectorXi((std::size_t) m);
-    for (std::int64_t i = 0; i < m; i++)
-    {
-      cloud_out->points[(std::size_t) i].x = xyz[3 * (std::size_t) i];
-      cloud_out->points[(std::size_t) i].y = xyz[3 * (std::size_t) i + 1];
-      cloud_out->points[(std::size_t) i].z = xyz[3 * (std::size_t) i + 2];
-      pts_cam_source_out((std::size_t) i) = cam[(std::size_t) i];
-    }
-    searched_n_ = m;
-    return true;
+    return readBackCloud(result.n_remaining, cloud_out, pts_cam_source_out);
   }
 
   /** The online chain of grasp_localizer.cpp:95-103 -- preprocessing, search, Learning::classify, HandleSearch -- as ONE device
@@ -341,35 +323,18 @@ public:
     const std::vector<int>& indices, const std::string& svm_filename, int min_inliers, double min_length,
     bool filters_boundaries = false)
   {
-    if (!ensureContext())
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
       return false;
-    if (agh_load_svm_file(ctx_, svm_filename.c_str()) != AGH_OK)
-    {
-      std::cout << " Exception: " << agh_last_error(ctx_) << "\n";  // learning.cpp:187-191
-      return false;
-    }
-    agh_localize_params lp;
-    lp.size_left = (std::int64_t) size_left;
-    lp.dense = cloud_is_dense(*cloud_in) ? 1 : 0;
-    lp.classify = 1;
-    for (int i = 0; i < 6; i++)
-      lp.workspace[i] = workspace(i);
-    lp.cell_size = cell_size;
-    std::vector<std::int32_t> idx(indices.begin(), indices.end());  // (copied by agh_localize_begin)
-    lp.sample_idx = idx.empty() ? nullptr : idx.data();
-    lp.n_samples = idx.empty() ? (std::int64_t) (num_samples_ < 0 ? 0 : num_samples_) : (std::int64_t) idx.size();
-    lp.sample_seed = sample_seed_set_ ? (std::uint64_t) sample_seed_ : (std::uint64_t) std::time(nullptr);
-    lp.min_inliers = min_inliers;
-    lp.filters_boundaries = filters_boundaries ? 1 : 0;
-    lp.min_length = min_length;
-    loc_cap_ = lp.n_samples * 8 < 8192 ? lp.n_samples * 8 + 1 : 8193;
-    last_samples_.assign((std::size_t) lp.n_samples, 0);
-    const std::int64_t n = (std::int64_t) cloud_in->size();
-    if (agh_localize_begin(ctx_, n > 0 ? &cloud_in->points[0].x : nullptr, (std::int64_t) sizeof(cloud_in->points[0]), n, &lp) != AGH_OK)
+    const std::vector<std::int32_t> idx(indices.begin(), indices.end());  // (copied by agh_localize_begin)
+    const agh_localize_params lp = chainParams(size_left, cloud_is_dense(*cloud_in), workspace, cell_size, idx, sampleSeed(),
+      min_inliers, min_length, filters_boundaries);
+    const RawPoints in = rawPoints(*cloud_in);
+    if (agh_localize_begin(ctx_, in.xyz, in.stride, in.n, &lp) != AGH_OK)
     {
       fail("agh_localize_begin");
       return false;
     }
+    chainBegun(lp.n_samples);
     return true;
   }
 
@@ -395,35 +360,19 @@ public:
     const std::vector<int>& indices, const std::string& svm_filename, int min_inliers, double min_length,
     bool filters_boundaries = false)
   {
-    if (!ensureContext())
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
       return false;
-    if (agh_load_svm_file(ctx_, svm_filename.c_str()) != AGH_OK)
-    {
-      std::cout << " Exception: " << agh_last_error(ctx_) << "\n";  // learning.cpp:187-191
-      return false;
-    }
-    agh_localize_params lp;
-    lp.size_left = 0;  // (ignored: the first image's pixels are camera 0's)
-    lp.dense = 1;
-    lp.classify = 1;
-    for (int i = 0; i < 6; i++)
-      lp.workspace[i] = workspace(i);
-    lp.cell_size = cell_size;
-    std::vector<std::int32_t> idx(indices.begin(), indices.end());  // (copied by agh_localize_depth_begin)
-    lp.sample_idx = idx.empty() ? nullptr : idx.data();
-    lp.n_samples = idx.empty() ? (std::int64_t) (num_samples_ < 0 ? 0 : num_samples_) : (std::int64_t) idx.size();
-    lp.sample_seed = sample_seed_set_ ? (std::uint64_t) sample_seed_ : (std::uint64_t) std::time(nullptr);
-    lp.min_inliers = min_inliers;
-    lp.filters_boundaries = filters_boundaries ? 1 : 0;
-    lp.min_length = min_length;
+    const std::vector<std::int32_t> idx(indices.begin(), indices.end());  // (copied by agh_localize_depth_begin)
+    // (size_left is ignored: the first image's pixels are camera 0's)
+    const agh_localize_params lp = chainParams(0, true, workspace, cell_size, idx, sampleSeed(), min_inliers, min_length,
+      filters_boundaries);
     const std::vector<agh_depth_image> recs = depthRecords(images);
     if (agh_localize_depth_begin(ctx_, recs.empty() ? nullptr : recs.data(), (std::int32_t) recs.size(), &lp) != AGH_OK)
     {
       fail("agh_localize_depth_begin");
       return false;
     }
-    loc_cap_ = lp.n_samples * 8 < 8192 ? lp.n_samples * 8 + 1 : 8193;  // (only a Begin that went through: see localizeBatchBegin)
-    last_samples_.assign((std::size_t) lp.n_samples, 0);
+    chainBegun(lp.n_samples);
     return true;
   }
 
@@ -441,7 +390,7 @@ public:
     return true;
   }
 
-  /** Additional: the chain of localize over several captures in one call (agh_localize_batch): capture k is clouds[k] with
+  /** Additional: the chain of localize over several captures in one call (localizeBatchBegin + localizeBatchEnd): capture k is clouds[k] with
    *  sizes_left[k], workspaces[k] and indices[k] (empty: num_samples drawn on the device, seeded with the sample seed + k).
    *  Per capture the hands the classifier kept, the handles and their inlier lists (indices into that capture's hands), exactly
    *  what localize returns for it.  @return false (after printing) on error */
@@ -460,63 +409,9 @@ public:
       std::cout << " Error: localizeBatch needs one size_left, workspace and index list per cloud\n";
       return false;
     }
-    if (!ensureContext())
-      return false;
-    if (agh_load_svm_file(ctx_, svm_filename.c_str()) != AGH_OK)
-    {
-      std::cout << " Exception: " << agh_last_error(ctx_) << "\n";  // learning.cpp:187-191
-      return false;
-    }
-    const std::uint64_t seed = sample_seed_set_ ? (std::uint64_t) sample_seed_ : (std::uint64_t) std::time(nullptr);
-    std::vector<agh_localize_params> lp(C);
-    std::vector<std::vector<std::int32_t> > idx(C);
-    std::vector<const float*> xyz(C);
-    std::vector<std::int64_t> stride(C), n(C);
-    std::int64_t cap = 1, n_samples = 0;
-    for (std::size_t k = 0; k < C; k++)
-    {
-      agh_localize_params& p = lp[k];
-      p.size_left = (std::int64_t) sizes_left[k];
-      p.dense = cloud_is_dense(*clouds[k]) ? 1 : 0;
-      p.classify = 1;
-      for (int i = 0; i < 6; i++)
-        p.workspace[i] = workspaces[k](i);
-      p.cell_size = cell_size;
-      idx[k].assign(indices[k].begin(), indices[k].end());
-      p.sample_idx = idx[k].empty() ? nullptr : idx[k].data();
-      p.n_samples = idx[k].empty() ? (std::int64_t) (num_samples_ < 0 ? 0 : num_samples_) : (std::int64_t) idx[k].size();
-      p.sample_seed = seed + (std::uint64_t) k;
-      p.min_inliers = min_inliers;
-      p.filters_boundaries = filters_boundaries ? 1 : 0;
-      p.min_length = min_length;
-      n[k] = (std::int64_t) clouds[k]->size();
-      xyz[k] = n[k] > 0 ? &clouds[k]->points[0].x : nullptr;
-      stride[k] = (std::int64_t) sizeof(clouds[k]->points[0]);
-      cap += p.n_samples * 8 < 8192 ? p.n_samples * 8 : 8192;
-      n_samples += p.n_samples;
-    }
-    std::vector<agh_hypothesis> hands((std::size_t) cap);
-    std::vector<agh_handle> handles((std::size_t) cap);
-    std::vector<std::int32_t> inl((std::size_t) cap);
-    std::vector<std::int32_t> samples((std::size_t) n_samples + 1);
-    std::vector<agh_localize_batch_result> res(C);
-    if (agh_localize_batch(ctx_, xyz.data(), stride.data(), n.data(), lp.data(), (std::int32_t) C, handles.data(), cap, inl.data(),
-          cap, hands.data(), cap, samples.data(), res.data()) != AGH_OK)
-    {
-      fail("agh_localize_batch");
-      return false;
-    }
-    searched_n_ = 0;
-    for (std::size_t k = 0; k < C; k++)
-    {
-      const agh_localize_batch_result& r = res[k];
-      hands_out[k].assign(hands.begin() + r.first_hand, hands.begin() + r.first_hand + r.r.n_hands);
-      handles_out[k].assign(handles.begin() + r.first_handle, handles.begin() + r.first_handle + r.r.n_handles);
-      inliers_out[k].assign(inl.begin() + r.first_inlier_idx, inl.begin() + r.first_inlier_idx + r.r.n_inlier_idx);
-      searched_n_ += r.r.n_voxels;
-    }
-    last_samples_.assign(samples.begin(), samples.begin() + n_samples);
-    return true;
+    return localizeBatchBegin(clouds, sizes_left, workspaces, cell_size, indices, svm_filename, min_inliers, min_length,
+             filters_boundaries) &&
+           localizeBatchEnd(hands_out, handles_out, inliers_out);
   }
 
   /** Additional: localizeBatch as two calls (agh_localize_batch_begin / agh_localize_batch_end), for a caller that walks over
@@ -535,47 +430,29 @@ public:
       std::cout << " Error: localizeBatchBegin needs one size_left, workspace and index list per cloud\n";
       return false;
     }
-    if (!ensureContext())
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
       return false;
-    if (agh_load_svm_file(ctx_, svm_filename.c_str()) != AGH_OK)
-    {
-      std::cout << " Exception: " << agh_last_error(ctx_) << "\n";  // learning.cpp:187-191
+    RawBatch in;
+    if (!rawPoints(clouds, in))
       return false;
-    }
-    const std::uint64_t seed = sample_seed_set_ ? (std::uint64_t) sample_seed_ : (std::uint64_t) std::time(nullptr);
+    const std::uint64_t seed = sampleSeed();
     std::vector<agh_localize_params> lp(C);
     std::vector<std::vector<std::int32_t> > idx(C);  // (copied by agh_localize_batch_begin, like the arrays below)
-    std::vector<const float*> xyz(C);
-    std::vector<std::int64_t> stride(C), n(C);
     std::int64_t cap = 1, n_samples = 0;
     for (std::size_t k = 0; k < C; k++)
     {
-      agh_localize_params& p = lp[k];
-      p.size_left = (std::int64_t) sizes_left[k];
-      p.dense = cloud_is_dense(*clouds[k]) ? 1 : 0;
-      p.classify = 1;
-      for (int i = 0; i < 6; i++)
-        p.workspace[i] = workspaces[k](i);
-      p.cell_size = cell_size;
       idx[k].assign(indices[k].begin(), indices[k].end());
-      p.sample_idx = idx[k].empty() ? nullptr : idx[k].data();
-      p.n_samples = idx[k].empty() ? (std::int64_t) (num_samples_ < 0 ? 0 : num_samples_) : (std::int64_t) idx[k].size();
-      p.sample_seed = seed + (std::uint64_t) k;
-      p.min_inliers = min_inliers;
-      p.filters_boundaries = filters_boundaries ? 1 : 0;
-      p.min_length = min_length;
-      n[k] = (std::int64_t) clouds[k]->size();
-      xyz[k] = n[k] > 0 ? &clouds[k]->points[0].x : nullptr;
-      stride[k] = (std::int64_t) sizeof(clouds[k]->points[0]);
-      cap += p.n_samples * 8 < 8192 ? p.n_samples * 8 : 8192;
-      n_samples += p.n_samples;
+      lp[k] = chainParams(sizes_left[k], cloud_is_dense(*clouds[k]), workspaces[k], cell_size, idx[k], seed + (std::uint64_t) k,
+        min_inliers, min_length, filters_boundaries);
+      cap += handsRoom(lp[k].n_samples);
+      n_samples += lp[k].n_samples;
     }
-    if (agh_localize_batch_begin(ctx_, xyz.data(), stride.data(), n.data(), lp.data(), (std::int32_t) C) != AGH_OK)
+    if (agh_localize_batch_begin(ctx_, in.xyz.data(), in.stride.data(), in.n.data(), lp.data(), (std::int32_t) C) != AGH_OK)
     {
       fail("agh_localize_batch_begin");
       return false;
     }
-    batch_captures_ = C;  // (only a Begin that went through replaces what the End of the chain in flight reads)
+    batch_captures_ = C;
     batch_cap_ = cap;
     batch_samples_ = n_samples;
     return true;
@@ -587,18 +464,10 @@ public:
   {
     if (next.empty() || !ensureContext())
       return false;
-    const std::size_t C = next.size();
-    std::vector<const float*> xyz(C);
-    std::vector<std::int64_t> stride(C), n(C);
-    for (std::size_t k = 0; k < C; k++)
-    {
-      if (!next[k])
-        return false;
-      n[k] = (std::int64_t) next[k]->size();
-      xyz[k] = n[k] > 0 ? &next[k]->points[0].x : nullptr;
-      stride[k] = (std::int64_t) sizeof(next[k]->points[0]);
-    }
-    if (agh_localize_batch_stage(ctx_, xyz.data(), stride.data(), n.data(), (std::int32_t) C) != AGH_OK)
+    RawBatch in;
+    if (!rawPoints(next, in))
+      return false;
+    if (agh_localize_batch_stage(ctx_, in.xyz.data(), in.stride.data(), in.n.data(), (std::int32_t) next.size()) != AGH_OK)
     {
       fail("agh_localize_batch_stage");
       return false;
@@ -680,8 +549,8 @@ public:
   {
     if (!ensureContext() || !next)
       return false;
-    const std::int64_t n = (std::int64_t) next->size();
-    if (agh_localize_stage(ctx_, n > 0 ? &next->points[0].x : nullptr, (std::int64_t) sizeof(next->points[0]), n) != AGH_OK)
+    const RawPoints in = rawPoints(*next);
+    if (agh_localize_stage(ctx_, in.xyz, in.stride, in.n) != AGH_OK)
     {
       fail("agh_localize_stage");
       return false;
@@ -734,7 +603,7 @@ public:
     if (indices.empty())
     {
       std::cout << "Generating uniform random indices ...\n";  // hand_search.cpp:34
-      idx = randomSample(n, num_samples_, sample_seed_set_ ? (unsigned) sample_seed_ : (unsigned) std::time(nullptr));
+      idx = randomSample(n, num_samples_, (unsigned) sampleSeed());
     }
     else
       idx.assign(indices.begin(), indices.end());
@@ -802,6 +671,97 @@ public:
   }
 
 private:
+  // the sample seed of a draw: setSampleSeed's, else the clock like pcl::RandomSample
+  std::uint64_t sampleSeed() const { return sample_seed_set_ ? sample_seed_ : (std::uint64_t) std::time(nullptr); }
+
+  // room for the hands (and so the handles and inlier indices) a chain over n_samples samples can return
+  static std::int64_t handsRoom(std::int64_t n_samples) { return n_samples * 8 < 8192 ? n_samples * 8 : 8192; }
+
+  // the one place that fills the library's chain record.  `idx`: the explicit samples (the library's begin copies them, so
+  // they only have to outlive that call); empty: num_samples_ indices drawn on the device with `seed`
+  agh_localize_params chainParams(std::int64_t size_left, bool dense, const VectorXd& workspace, double cell_size,
+    const std::vector<std::int32_t>& idx, std::uint64_t seed, int min_inliers, double min_length, bool filters_boundaries) const
+  {
+    agh_localize_params lp;
+    lp.size_left = size_left;
+    lp.dense = dense ? 1 : 0;
+    lp.classify = 1;
+    for (int i = 0; i < 6; i++)
+      lp.workspace[i] = workspace(i);
+    lp.cell_size = cell_size;
+    lp.sample_idx = idx.empty() ? nullptr : idx.data();
+    lp.n_samples = idx.empty() ? (std::int64_t) (num_samples_ < 0 ? 0 : num_samples_) : (std::int64_t) idx.size();
+    lp.sample_seed = seed;
+    lp.min_inliers = min_inliers;
+    lp.filters_boundaries = filters_boundaries ? 1 : 0;
+    lp.min_length = min_length;
+    return lp;
+  }
+
+  // a single-capture chain is queued: what localizeEnd reads for it
+  void chainBegun(std::int64_t n_samples)
+  {
+    loc_cap_ = handsRoom(n_samples) + 1;
+    last_samples_.assign((std::size_t) n_samples, 0);
+  }
+
+  // a host cloud as the library takes it: no pointer for an empty one
+  struct RawPoints
+  {
+    const float* xyz;
+    std::int64_t stride, n;
+  };
+  static RawPoints rawPoints(const PointCloud& cloud)
+  {
+    RawPoints r;
+    r.n = (std::int64_t) cloud.size();
+    r.xyz = r.n > 0 ? &cloud.points[0].x : nullptr;
+    r.stride = (std::int64_t) sizeof(cloud.points[0]);
+    return r;
+  }
+  struct RawBatch
+  {
+    std::vector<const float*> xyz;
+    std::vector<std::int64_t> stride, n;
+  };
+  static bool rawPoints(const std::vector<PointCloud::Ptr>& clouds, RawBatch& out)  // false: a cloud is missing
+  {
+    for (std::size_t k = 0; k < clouds.size(); k++)
+    {
+      if (!clouds[k])
+        return false;
+      const RawPoints r = rawPoints(*clouds[k]);
+      out.xyz.push_back(r.xyz);
+      out.stride.push_back(r.stride);
+      out.n.push_back(r.n);
+    }
+    return true;
+  }
+
+  // the cloud the context holds (n points) as a host cloud with its camera ids; it is the searched cloud from here on
+  bool readBackCloud(std::int64_t n, PointCloud::Ptr& cloud_out, VectorXi& pts_cam_source_out)
+  {
+    std::vector<float> xyz(3 * (std::size_t) n + 3);
+    std::vector<std::int32_t> cam((std::size_t) n + 1);
+    if (agh_get_cloud(ctx_, xyz.data(), cam.data(), n) < 0)
+    {
+      fail("agh_get_cloud");
+      return false;
+    }
+    cloud_out.reset(new PointCloud);
+    cloud_out->points.resize((std::size_t) n);
+    pts_cam_source_out = VectorXi((std::size_t) n);
+    for (std::int64_t i = 0; i < n; i++)
+    {
+      cloud_out->points[(std::size_t) i].x = xyz[3 * (std::size_t) i];
+      cloud_out->points[(std::size_t) i].y = xyz[3 * (std::size_t) i + 1];
+      cloud_out->points[(std::size_t) i].z = xyz[3 * (std::size_t) i + 2];
+      pts_cam_source_out((std::size_t) i) = cam[(std::size_t) i];
+    }
+    searched_n_ = n;
+    return true;
+  }
+
   // the ABI's records of the images (the library checks them, and their number)
   std::vector<agh_depth_image> depthRecords(const std::vector<DepthImage>& images) const
   {
@@ -863,7 +823,10 @@ private:
 
   agh_ctx* ctx_;
   std::int64_t searched_n_ = 0;
-  std::int64_t loc_cap_ = 1;  // room for the results of the chain localizeBegin queued
+  // What an End reads of the chain in flight.  The rule for every Begin: these (and last_samples_, sized by chainBegun for
+  // localizeEnd) are written only after the library's begin has returned AGH_OK, so a Begin that fails for any reason -- a
+  // chain in flight included -- leaves that chain's End what it needs.
+  std::int64_t loc_cap_ = 1;  // room for the results of the chain localizeBegin / localizeDepthBegin queued
   std::size_t batch_captures_ = 0;  // ... and of the batch localizeBatchBegin queued: its captures, room, samples
   std::int64_t batch_cap_ = 1, batch_samples_ = 0;
   agh_params params_;

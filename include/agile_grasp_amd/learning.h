@@ -20,7 +20,6 @@
 #define AGILE_GRASP_AMD_LEARNING_H
 
 #include <cstdlib>
-#include <fstream>
 #include <iostream>
 #include <memory>
 #include <set>
@@ -50,20 +49,11 @@ public:
     (void) num_threads_;
     std::cout << "Predicting ...\n";
     std::vector<GraspHypothesis> antipodal_hands;
-    std::ifstream f(svm_filename.c_str());
-    if (!f.good())
-    {
-      std::cout << " Error: File " << svm_filename << " does not exist!\n";  // learning.cpp:172-178
+    if (!detail::svmFileExists(svm_filename))
       return antipodal_hands;
-    }
     agh_ctx* ctx = contextFor(hands_list);
-    if (!ctx)
+    if (!ctx || !detail::loadSvm(ctx, svm_filename))
       return antipodal_hands;
-    if (agh_load_svm_file(ctx, svm_filename.c_str()) != AGH_OK)
-    {
-      std::cout << " Exception: " << agh_last_error(ctx) << "\n";  // learning.cpp:187-191
-      return antipodal_hands;
-    }
     const std::size_t n = hands_list.size();
     std::vector<unsigned char> keep_of(n, 0);  // per list entry
     // the list of a sharded findHands (HandSearch::joinCommunicator)?  Then classify is a COLLECTIVE like that search was:

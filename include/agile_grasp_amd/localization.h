@@ -263,23 +263,16 @@ public:
   bool localizeHandlesBegin(const PointCloud::Ptr& cloud_in, int size_left, const std::vector<int>& indices,
     const std::string& svm_filename, int min_inliers, double min_length)
   {
-    if (pending_cloud_ || pending_depth_)  // (one chain at a time: the one in flight stays pending, for its localizeHandlesEnd)
-    {
-      std::cout << " Error: localizeHandlesBegin while a chain is pending (localizeHandlesEnd first)\n";
+    if (chainPending("localizeHandlesBegin"))
       return false;
-    }
     if (size_left == 0 || !cloud_in || cloud_in->size() == 0)
     {
       std::cout << "Input cloud is empty!\n";
       std::cout << size_left << std::endl;
       return false;
     }
-    std::ifstream f(svm_filename.c_str());
-    if (!f.good())
-    {
-      std::cout << " Error: File " << svm_filename << " does not exist!\n";  // learning.cpp:172-178
+    if (!detail::svmFileExists(svm_filename))
       return false;
-    }
     ensureSearch();
     if (!search_->localizeBegin(cloud_in, size_left, workspace_, 0.003, indices, svm_filename, min_inliers, min_length,
           filters_boundaries_))
@@ -337,22 +330,15 @@ public:
   bool localizeHandlesDepthBegin(const std::vector<DepthImage>& images, const std::vector<int>& indices,
     const std::string& svm_filename, int min_inliers, double min_length)
   {
-    if (pending_cloud_ || pending_depth_ || !pending_batch_.empty())
-    {
-      std::cout << " Error: localizeHandlesDepthBegin while a chain is pending (localizeHandlesEnd first)\n";
+    if (chainPending("localizeHandlesDepthBegin"))
       return false;
-    }
     if (images.empty())
     {
       std::cout << "Input cloud is empty!\n";
       return false;
     }
-    std::ifstream f(svm_filename.c_str());
-    if (!f.good())
-    {
-      std::cout << " Error: File " << svm_filename << " does not exist!\n";  // learning.cpp:172-178
+    if (!detail::svmFileExists(svm_filename))
       return false;
-    }
     ensureSearch();
     if (!search_->localizeDepthBegin(images, workspace_, 0.003, indices, svm_filename, min_inliers, min_length, filters_boundaries_))
       return false;
@@ -369,46 +355,18 @@ public:
     return search_->localizeDepthStage(next);
   }
 
-  /** Additional: localizeHandles over several captures in one call (agh_localize_batch, one synchronisation): capture k is
-   *  clouds[k] with sizes_left[k] and indices_per_cloud[k] (empty: drawn on the device, see HandSearch::localizeBatch), searched
-   *  in (*workspaces)[k] -- or, without `workspaces`, in this object's workspace.  Per capture the same handles as
-   *  localizeHandles on that capture and indices; (*antipodal_hands_per_cloud)[k] receives its kept hands. */
+  /** Additional: localizeHandles over several captures in one call (localizeHandlesBatchBegin + localizeHandlesBatchEnd, one
+   *  synchronisation): capture k is clouds[k] with sizes_left[k] and indices_per_cloud[k] (empty: drawn on the device, see
+   *  HandSearch::localizeBatch), searched in (*workspaces)[k] -- or, without `workspaces`, in this object's workspace.  Per capture
+   *  the same handles as localizeHandles on that capture and indices; (*antipodal_hands_per_cloud)[k] receives its kept hands. */
   std::vector<std::vector<Handle> > localizeHandlesBatch(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
     const std::vector<std::vector<int> >& indices_per_cloud, const std::string& svm_filename, int min_inliers, double min_length,
     std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_cloud = nullptr, const std::vector<VectorXd>* workspaces = nullptr)
   {
-    const std::size_t C = clouds.size();
-    std::vector<std::vector<Handle> > out(C);
-    if (antipodal_hands_per_cloud)
-      antipodal_hands_per_cloud->assign(C, std::vector<GraspHypothesis>());
-    if (pending_cloud_ || pending_depth_)
-    {
-      std::cout << " Error: localizeHandlesBatch while a chain is pending (localizeHandlesEnd first)\n";
-      return out;
-    }
-    for (std::size_t k = 0; k < C; k++)
-      if (!clouds[k] || clouds[k]->size() == 0 || k >= sizes_left.size() || sizes_left[k] == 0)
-      {
-        std::cout << "Input cloud is empty!\n";
-        return out;
-      }
-    std::ifstream f(svm_filename.c_str());
-    if (!f.good())
-    {
-      std::cout << " Error: File " << svm_filename << " does not exist!\n";  // learning.cpp:172-178
-      return out;
-    }
-    ensureSearch();
-    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(C, workspace_);
-    std::vector<std::vector<agh_hypothesis> > hands;
-    std::vector<std::vector<agh_handle> > handles;
-    std::vector<std::vector<std::int32_t> > idx;
-    if (!search_->localizeBatch(clouds, sizes_left, ws, 0.003, indices_per_cloud, svm_filename, min_inliers, min_length, hands, handles,
-          idx, filters_boundaries_))
-      return out;
-    for (std::size_t k = 0; k < C; k++)
-      out[k] = toHandles(clouds[k], hands[k], handles[k], idx[k], antipodal_hands_per_cloud ? &(*antipodal_hands_per_cloud)[k] : nullptr);
-    return out;
+    if (chainPending("localizeHandlesBatch") ||
+        !localizeHandlesBatchBegin(clouds, sizes_left, indices_per_cloud, svm_filename, min_inliers, min_length, workspaces))
+      return noHandles(clouds.size(), antipodal_hands_per_cloud);
+    return localizeHandlesBatchEnd(antipodal_hands_per_cloud);
   }
 
   /** Additional: localizeHandlesBatch as two calls, for a walk over a directory of captures, batch by batch:
@@ -423,26 +381,18 @@ public:
     const std::vector<std::vector<int> >& indices_per_cloud, const std::string& svm_filename, int min_inliers, double min_length,
     const std::vector<VectorXd>* workspaces = nullptr)
   {
-    if (pending_cloud_ || pending_depth_ || !pending_batch_.empty())  // (the chain in flight stays pending, for its End)
-    {
-      std::cout << " Error: localizeHandlesBatchBegin while a chain is pending (its End first)\n";
+    if (chainPending("localizeHandlesBatchBegin", "its End"))
       return false;
-    }
-    const std::size_t C = clouds.size();
-    for (std::size_t k = 0; k < C; k++)
+    for (std::size_t k = 0; k < clouds.size(); k++)
       if (!clouds[k] || clouds[k]->size() == 0 || k >= sizes_left.size() || sizes_left[k] == 0)
       {
         std::cout << "Input cloud is empty!\n";
         return false;
       }
-    std::ifstream f(svm_filename.c_str());
-    if (!f.good())
-    {
-      std::cout << " Error: File " << svm_filename << " does not exist!\n";  // learning.cpp:172-178
+    if (!detail::svmFileExists(svm_filename))
       return false;
-    }
     ensureSearch();
-    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(C, workspace_);
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(clouds.size(), workspace_);
     if (!search_->localizeBatchBegin(clouds, sizes_left, ws, 0.003, indices_per_cloud, svm_filename, min_inliers, min_length,
           filters_boundaries_))
       return false;
@@ -466,18 +416,13 @@ public:
   {
     const std::vector<PointCloud::Ptr> clouds = pending_batch_;
     pending_batch_.clear();
-    const std::size_t C = clouds.size();
-    std::vector<std::vector<Handle> > out(C);
-    if (antipodal_hands_per_cloud)
-      antipodal_hands_per_cloud->assign(C, std::vector<GraspHypothesis>());
-    if (C == 0)
-      return out;
+    std::vector<std::vector<Handle> > out = noHandles(clouds.size(), antipodal_hands_per_cloud);
     std::vector<std::vector<agh_hypothesis> > hands;
     std::vector<std::vector<agh_handle> > handles;
     std::vector<std::vector<std::int32_t> > idx;
-    if (!search_->localizeBatchEnd(hands, handles, idx))
+    if (clouds.empty() || !search_->localizeBatchEnd(hands, handles, idx))
       return out;
-    for (std::size_t k = 0; k < C; k++)
+    for (std::size_t k = 0; k < clouds.size(); k++)
       out[k] = toHandles(clouds[k], hands[k], handles[k], idx[k], antipodal_hands_per_cloud ? &(*antipodal_hands_per_cloud)[k] : nullptr);
     return out;
   }
@@ -495,20 +440,13 @@ public:
     if (cams_left.size() != clouds.size() || cams_right.size() != clouds.size())
     {
       std::cout << " Error: localizeHandlesBatch needs one left and one right camera transform per cloud\n";
-      if (antipodal_hands_per_cloud)
-        antipodal_hands_per_cloud->assign(clouds.size(), std::vector<GraspHypothesis>());
-      return std::vector<std::vector<Handle> >(clouds.size());
+      return noHandles(clouds.size(), antipodal_hands_per_cloud);
     }
-    if (pending_cloud_ || pending_depth_)  // (the plain overload prints the error and returns the empty lists; a chain in flight keeps the table it has)
-      return localizeHandlesBatch(clouds, sizes_left, indices_per_cloud, svm_filename, min_inliers, min_length, antipodal_hands_per_cloud,
-        workspaces);
+    if (chainPending("localizeHandlesBatch"))  // (a chain in flight keeps the table it has)
+      return noHandles(clouds.size(), antipodal_hands_per_cloud);
     ensureSearch();
     if (!search_->setCloudCamOrigins(cams_left, cams_right))
-    {
-      if (antipodal_hands_per_cloud)
-        antipodal_hands_per_cloud->assign(clouds.size(), std::vector<GraspHypothesis>());
-      return std::vector<std::vector<Handle> >(clouds.size());
-    }
+      return noHandles(clouds.size(), antipodal_hands_per_cloud);
     const std::vector<std::vector<Handle> > out = localizeHandlesBatch(clouds, sizes_left, indices_per_cloud, svm_filename,
       min_inliers, min_length, antipodal_hands_per_cloud, workspaces);
     search_->clearCloudCamOrigins();
@@ -570,6 +508,22 @@ public:
   }
 
 private:
+  // One chain at a time: a Begin (or a blocking batch call) while one is pending prints this and fails, and the chain in flight
+  // stays pending for its End.
+  bool chainPending(const char* who, const char* end = "localizeHandlesEnd") const
+  {
+    if (!pending_cloud_ && !pending_depth_ && pending_batch_.empty())
+      return false;
+    std::cout << " Error: " << who << " while a chain is pending (" << end << " first)\n";
+    return true;
+  }
+  // what a batch call returns when it fails: an empty list of handles, and of kept hands, per capture
+  static std::vector<std::vector<Handle> > noHandles(std::size_t C, std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_cloud)
+  {
+    if (antipodal_hands_per_cloud)
+      antipodal_hands_per_cloud->assign(C, std::vector<GraspHypothesis>());
+    return std::vector<std::vector<Handle> >(C);
+  }
   void init()
   {
     workspace_ = VectorXd(6);

@@ -4,7 +4,7 @@
 // (grasp_hypothesis.h:149-170), the empty-`indices` sampling path (hand_search.cpp:31-44).
 //   boundary_test sampler <n_points> <num_samples> <seed>                 (needs no GPU)
 //   boundary_test filtered|stale|drawn <raw.bin> <svm file>
-// raw.bin as localization_test.cpp reads it.
+// raw.bin as chain_common.h reads it.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>

@@ -9,23 +9,7 @@
 #include <cstring>
 #include <vector>
 
-#include "agile_grasp_amd/localization.h"
-
-using namespace agile_grasp_amd;
-
-// the same kept hands and the same handles (inlier lists included)
-static bool same_chain(const std::vector<GraspHypothesis>& kept, const std::vector<Handle>& handles,
-  const std::vector<GraspHypothesis>& kept1, const std::vector<Handle>& handles1)
-{
-  bool same = kept.size() == kept1.size() && handles.size() == handles1.size();
-  for (size_t i = 0; same && i < kept.size(); i++)
-    same = kept[i].getGraspSurface()(0) == kept1[i].getGraspSurface()(0) && kept[i].getGraspBottom()(1) == kept1[i].getGraspBottom()(1) &&
-           kept[i].getApproach()(2) == kept1[i].getApproach()(2) && kept[i].getGraspWidth() == kept1[i].getGraspWidth();
-  for (size_t i = 0; same && i < handles.size(); i++)
-    same = handles[i].getInliers() == handles1[i].getInliers() && handles[i].getAxis()(0) == handles1[i].getAxis()(0) &&
-           handles[i].getCenter()(1) == handles1[i].getCenter()(1) && handles[i].getWidth() == handles1[i].getWidth();
-  return same;
-}
+#include "chain_common.h"
 
 static void set_up(Localization& loc, const Matrix4d& tl, const Matrix4d& tr, const VectorXd& w)
 {

@@ -2,73 +2,30 @@
 // (NaNs, points outside the workspace, no voxelisation), like src/tests/test_local_axes.cpp drives the reference's.
 //   localization_test <raw.bin> <svm file> <mode: voxels|hands|antipodal|chain|stream|rebegin>
 //   (antipodal: src/tests/antipodal_test.cpp)
-// raw.bin: int64 n, int64 size_left, int64 n_idx, double ws[6], double cam_left[3], double cam_right[3], n*3 float xyz,
-// n_idx int32 indices (into the voxelised cloud).
+// raw.bin as chain_common.h reads it.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "agile_grasp_amd/localization.h"
-
-using namespace agile_grasp_amd;
-
-// the same kept hands and the same handles (inlier lists included)
-static bool same_chain(const std::vector<GraspHypothesis>& kept, const std::vector<Handle>& handles,
-  const std::vector<GraspHypothesis>& kept1, const std::vector<Handle>& handles1)
-{
-  bool same = kept.size() == kept1.size() && handles.size() == handles1.size();
-  for (size_t i = 0; same && i < kept.size(); i++)
-    same = kept[i].getGraspSurface()(0) == kept1[i].getGraspSurface()(0) && kept[i].getGraspBottom()(1) == kept1[i].getGraspBottom()(1) &&
-           kept[i].getApproach()(2) == kept1[i].getApproach()(2) && kept[i].getGraspWidth() == kept1[i].getGraspWidth();
-  for (size_t i = 0; same && i < handles.size(); i++)
-    same = handles[i].getInliers() == handles1[i].getInliers() && handles[i].getAxis()(0) == handles1[i].getAxis()(0) &&
-           handles[i].getCenter()(1) == handles1[i].getCenter()(1) && handles[i].getWidth() == handles1[i].getWidth();
-  return same;
-}
+#include "chain_common.h"
 
 int main(int argc, char** argv)
 {
   if (argc < 4)
     return 2;
-  FILE* f = std::fopen(argv[1], "rb");
-  if (!f)
+  Capture c;
+  if (!read_capture(argv[1], c))
     return 2;
-  long long n = 0, size_left = 0, n_idx = 0;
-  double ws[6], cl[3], cr[3];
-  if (std::fread(&n, 8, 1, f) != 1 || std::fread(&size_left, 8, 1, f) != 1 || std::fread(&n_idx, 8, 1, f) != 1 ||
-      std::fread(ws, 8, 6, f) != 6 || std::fread(cl, 8, 3, f) != 3 || std::fread(cr, 8, 3, f) != 3)
-    return 2;
-  std::vector<float> xyz(3 * (size_t) n);
-  std::vector<int> idx((size_t) n_idx);
-  if (std::fread(xyz.data(), 4, xyz.size(), f) != xyz.size() || std::fread(idx.data(), 4, idx.size(), f) != idx.size())
-    return 2;
-  std::fclose(f);
-  PointCloud::Ptr cloud(new PointCloud);
-  cloud->points.resize((size_t) n);
-  for (long long i = 0; i < n; i++)
-  {
-    cloud->points[(size_t) i].x = xyz[3 * i];
-    cloud->points[(size_t) i].y = xyz[3 * i + 1];
-    cloud->points[(size_t) i].z = xyz[3 * i + 2];
-  }
-  Matrix4d tl, tr;
-  for (int r = 0; r < 3; r++)
-  {
-    tl(r, 3) = cl[r];
-    tr(r, 3) = cr[r];
-  }
+  const PointCloud::Ptr cloud = c.cloud;
+  const int size_left = c.size_left;
+  const std::vector<int>& idx = c.idx;
   Localization loc(1, false, 0);
-  loc.setCameraTransforms(tl, tr);
-  VectorXd w(6);
-  for (int i = 0; i < 6; i++)
-    w(i) = ws[i];
-  loc.setWorkspace(w);
-  loc.setDeterministicNormalEstimation(true);
+  setup(loc, c);
   if (std::strcmp(argv[3], "voxels") == 0)
   {
     // preprocessing as localizeHands runs it (on the GPU): print the cloud the search worked on
-    std::vector<GraspHypothesis> hands = loc.localizeHands(cloud, (int) size_left, idx, false, false);
+    std::vector<GraspHypothesis> hands = loc.localizeHands(cloud, size_left, idx, false, false);
     const PointCloud::Ptr& vox = loc.getSearchedCloud();
     if (!vox)
     {
@@ -85,11 +42,11 @@ int main(int argc, char** argv)
   {
     // grasp_localizer.cpp:95-103 twice: the three calls of the reference's caller, then the one-call form; the two must print
     // the same kept hands and the same handles
-    std::vector<GraspHypothesis> hands3 = loc.localizeHands(cloud, (int) size_left, idx, false, false);
+    std::vector<GraspHypothesis> hands3 = loc.localizeHands(cloud, size_left, idx, false, false);
     std::vector<GraspHypothesis> kept3 = loc.predictAntipodalHands(hands3, argv[2]);
     std::vector<Handle> handles3 = loc.findHandles(kept3, 2, 0.005);
     std::vector<GraspHypothesis> kept1;
-    std::vector<Handle> handles1 = loc.localizeHandles(cloud, (int) size_left, idx, argv[2], 2, 0.005, &kept1);
+    std::vector<Handle> handles1 = loc.localizeHandles(cloud, size_left, idx, argv[2], 2, 0.005, &kept1);
     for (int pass = 0; pass < 2; pass++)
     {
       const std::vector<GraspHypothesis>& kept = pass == 0 ? kept3 : kept1;
@@ -118,9 +75,9 @@ int main(int argc, char** argv)
       clouds[k] = PointCloud::Ptr(new PointCloud(*cloud));
     std::vector<GraspHypothesis> kept1;
     PointCloud::Ptr ref_cloud(new PointCloud(*cloud));
-    std::vector<Handle> handles1 = loc.localizeHandles(ref_cloud, (int) size_left, idx, argv[2], 2, 0.005, &kept1);
+    std::vector<Handle> handles1 = loc.localizeHandles(ref_cloud, size_left, idx, argv[2], 2, 0.005, &kept1);
     std::printf("CHAIN1 %zu %zu\n", kept1.size(), handles1.size());
-    if (!loc.localizeHandlesBegin(clouds[0], (int) size_left, idx, argv[2], 2, 0.005))
+    if (!loc.localizeHandlesBegin(clouds[0], size_left, idx, argv[2], 2, 0.005))
       return 3;
     for (int k = 0; k < 3; k++)
     {
@@ -128,7 +85,7 @@ int main(int argc, char** argv)
         return 4;
       std::vector<GraspHypothesis> kept;
       std::vector<Handle> handles = loc.localizeHandlesEnd(&kept);
-      if (k + 1 < 3 && !loc.localizeHandlesBegin(clouds[k + 1], (int) size_left, idx, argv[2], 2, 0.005))
+      if (k + 1 < 3 && !loc.localizeHandlesBegin(clouds[k + 1], size_left, idx, argv[2], 2, 0.005))
         return 5;
       std::printf("STREAM %d %zu %zu %d\n", k, kept.size(), handles.size(), same_chain(kept, handles, kept1, handles1) ? 1 : 0);
     }
@@ -142,27 +99,25 @@ int main(int argc, char** argv)
     PointCloud::Ptr b(new PointCloud(*cloud));
     std::reverse(b->points.begin(), b->points.end());
     std::vector<GraspHypothesis> kept_a, kept_b_ref;
-    std::vector<Handle> handles_a = loc.localizeHandles(a_ref, (int) size_left, idx, argv[2], 2, 0.005, &kept_a);
+    std::vector<Handle> handles_a = loc.localizeHandles(a_ref, size_left, idx, argv[2], 2, 0.005, &kept_a);
     Localization loc_b(1, false, 0);  // (B's results on an object of its own)
-    loc_b.setCameraTransforms(tl, tr);
-    loc_b.setWorkspace(w);
-    loc_b.setDeterministicNormalEstimation(true);
+    setup(loc_b, c);
     PointCloud::Ptr b_ref(new PointCloud(*b));
-    std::vector<Handle> handles_b_ref = loc_b.localizeHandles(b_ref, (int) size_left, idx, argv[2], 2, 0.005, &kept_b_ref);
+    std::vector<Handle> handles_b_ref = loc_b.localizeHandles(b_ref, size_left, idx, argv[2], 2, 0.005, &kept_b_ref);
     std::printf("CHAIN1 %zu %zu\n", kept_a.size(), handles_a.size());
-    if (!loc.localizeHandlesBegin(a, (int) size_left, idx, argv[2], 2, 0.005))
+    if (!loc.localizeHandlesBegin(a, size_left, idx, argv[2], 2, 0.005))
       return 3;
-    const bool b_refused = !loc.localizeHandlesBegin(b, (int) size_left, idx, argv[2], 2, 0.005);
-    const bool no_svm_refused = !loc.localizeHandlesBegin(a_again, (int) size_left, idx, "no_such_svm_file", 2, 0.005);
+    const bool b_refused = !loc.localizeHandlesBegin(b, size_left, idx, argv[2], 2, 0.005);
+    const bool no_svm_refused = !loc.localizeHandlesBegin(a_again, size_left, idx, "no_such_svm_file", 2, 0.005);
     std::vector<GraspHypothesis> kept;
     std::vector<Handle> handles = loc.localizeHandlesEnd(&kept);
     std::printf("REBEGIN %d %d %zu %zu %d\n", b_refused ? 1 : 0, no_svm_refused ? 1 : 0, kept.size(), handles.size(),
       same_chain(kept, handles, kept_a, handles_a) ? 1 : 0);
     // the object is usable afterwards: B in one call, then a fresh Begin / End of A
     std::vector<GraspHypothesis> kept_b;
-    std::vector<Handle> handles_b = loc.localizeHandles(b, (int) size_left, idx, argv[2], 2, 0.005, &kept_b);
+    std::vector<Handle> handles_b = loc.localizeHandles(b, size_left, idx, argv[2], 2, 0.005, &kept_b);
     PointCloud::Ptr a_fresh(new PointCloud(*cloud));
-    const bool begun = loc.localizeHandlesBegin(a_fresh, (int) size_left, idx, argv[2], 2, 0.005);
+    const bool begun = loc.localizeHandlesBegin(a_fresh, size_left, idx, argv[2], 2, 0.005);
     std::vector<GraspHypothesis> kept2;
     std::vector<Handle> handles2 = loc.localizeHandlesEnd(&kept2);
     std::printf("AFTER %zu %zu %d %d %d\n", kept_b.size(), handles_b.size(), same_chain(kept_b, handles_b, kept_b_ref, handles_b_ref) ? 1 : 0,
@@ -170,7 +125,7 @@ int main(int argc, char** argv)
     return 0;
   }
   const bool antipodal = std::strcmp(argv[3], "antipodal") == 0;  // calculates_antipodal (antipodal_test.cpp:61)
-  std::vector<GraspHypothesis> hands = loc.localizeHands(cloud, (int) size_left, idx, antipodal, false);
+  std::vector<GraspHypothesis> hands = loc.localizeHands(cloud, size_left, idx, antipodal, false);
   if (antipodal)
   {
     for (size_t i = 0; i < hands.size(); i++)

@@ -1,87 +1,18 @@
-// localize_batch_test.cpp -- Localization::localizeHandlesBatch (agh_localize_batch through the adapter) against
-// localizeHandles per capture: the same kept hands and handles, every double exactly.
-// raw.bin as localization_test.cpp reads it (the camera origins of the first file hold for all).
+// localize_batch_test.cpp -- Localization::localizeHandlesBatch against localizeHandles per capture: the same kept hands and
+// handles, every double exactly; then localizeHandlesBatchBegin / stageNextBatch / localizeHandlesBatchEnd against the blocking call.
+// raw.bin as chain_common.h reads it (the camera origins of the first file hold for all).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "agile_grasp_amd/localization.h"
-
-using namespace agile_grasp_amd;
-
-struct Capture
-{
-  PointCloud::Ptr cloud;
-  int size_left = 0;
-  std::vector<int> idx;
-  double ws[6], cl[3], cr[3];
-};
-
-static bool read_capture(const char* path, Capture& c)
-{
-  FILE* f = std::fopen(path, "rb");
-  if (!f)
-    return false;
-  long long n = 0, size_left = 0, n_idx = 0;
-  bool ok = std::fread(&n, 8, 1, f) == 1 && std::fread(&size_left, 8, 1, f) == 1 && std::fread(&n_idx, 8, 1, f) == 1 &&
-            std::fread(c.ws, 8, 6, f) == 6 && std::fread(c.cl, 8, 3, f) == 3 && std::fread(c.cr, 8, 3, f) == 3;
-  std::vector<float> xyz(ok ? 3 * (size_t) n : 0);
-  c.idx.resize(ok ? (size_t) n_idx : 0);
-  ok = ok && std::fread(xyz.data(), 4, xyz.size(), f) == xyz.size() && std::fread(c.idx.data(), 4, c.idx.size(), f) == c.idx.size();
-  std::fclose(f);
-  if (!ok)
-    return false;
-  c.size_left = (int) size_left;
-  c.cloud = PointCloud::Ptr(new PointCloud);
-  c.cloud->points.resize((size_t) n);
-  for (long long i = 0; i < n; i++)
-  {
-    c.cloud->points[(size_t) i].x = xyz[3 * i];
-    c.cloud->points[(size_t) i].y = xyz[3 * i + 1];
-    c.cloud->points[(size_t) i].z = xyz[3 * i + 2];
-  }
-  return true;
-}
-
-static void setup(Localization& loc, const Capture& c)
-{
-  Matrix4d tl, tr;
-  for (int r = 0; r < 3; r++)
-  {
-    tl(r, 3) = c.cl[r];
-    tr(r, 3) = c.cr[r];
-  }
-  loc.setCameraTransforms(tl, tr);
-  VectorXd w(6);
-  for (int i = 0; i < 6; i++)
-    w(i) = c.ws[i];
-  loc.setWorkspace(w);
-  loc.setDeterministicNormalEstimation(true);
-}
-
-// every double of every kept hand and handle, exactly
-static bool same_chain(const std::vector<GraspHypothesis>& ka, const std::vector<Handle>& ha, const std::vector<GraspHypothesis>& kb,
-  const std::vector<Handle>& hb)
-{
-  bool same = ka.size() == kb.size() && ha.size() == hb.size();
-  for (size_t i = 0; same && i < ka.size(); i++)
-    for (int r = 0; same && r < 3; r++)
-      same = ka[i].getGraspSurface()(r) == kb[i].getGraspSurface()(r) && ka[i].getGraspBottom()(r) == kb[i].getGraspBottom()(r) &&
-             ka[i].getApproach()(r) == kb[i].getApproach()(r) && ka[i].getAxis()(r) == kb[i].getAxis()(r) &&
-             ka[i].getGraspWidth() == kb[i].getGraspWidth() && ka[i].isFullAntipodal() == kb[i].isFullAntipodal();
-  for (size_t i = 0; same && i < ha.size(); i++)
-    for (int r = 0; same && r < 3; r++)
-      same = ha[i].getInliers() == hb[i].getInliers() && ha[i].getAxis()(r) == hb[i].getAxis()(r) &&
-             ha[i].getCenter()(r) == hb[i].getCenter()(r) && ha[i].getApproach()(r) == hb[i].getApproach()(r) &&
-             ha[i].getBinormal()(r) == hb[i].getBinormal()(r) && ha[i].getWidth() == hb[i].getWidth();
-  return same;
-}
+#include "chain_common.h"
 
 int main(int argc, char** argv)
 {
   // localize_batch_test <filters 0|1> <svm file> <raw.bin>...: localizeHandlesBatch on one object against localizeHandles per
-  // capture on another, once with a workspace per capture and once with the object's own workspace for all
+  // capture on another, once with a workspace per capture and once with the object's own workspace for all; then the streamed
+  // calls on the first object, one STREAM row per check
   if (argc < 4)
     return 2;
   const bool filters = std::atoi(argv[1]) != 0;
@@ -112,6 +43,8 @@ int main(int argc, char** argv)
   std::vector<std::vector<Handle> > got = loc.localizeHandlesBatch(clouds, sizes_left, idx, svm, 2, 0.005, &kept, &ws);
   if ((int) got.size() != C || (int) kept.size() != C)
     return 3;
+  std::vector<GraspHypothesis> kept_ref0;  // (capture 0's reference, for the last STREAM row)
+  std::vector<Handle> handles_ref0;
   for (int k = 0; k < C; k++)
   {
     ref.setWorkspace(ws[(size_t) k]);
@@ -120,6 +53,11 @@ int main(int argc, char** argv)
     std::vector<Handle> h = ref.localizeHandles(copy, c[(size_t) k].size_left, c[(size_t) k].idx, svm, 2, 0.005, &kept_ref);
     std::printf("BATCH %d %zu %zu %d\n", k, kept[(size_t) k].size(), got[(size_t) k].size(),
       same_chain(kept[(size_t) k], got[(size_t) k], kept_ref, h) ? 1 : 0);
+    if (k == 0)
+    {
+      kept_ref0 = kept_ref;
+      handles_ref0 = h;
+    }
   }
   // without workspaces: every capture in the object's workspace (capture 0's)
   std::vector<PointCloud::Ptr> clouds2;
@@ -136,5 +74,39 @@ int main(int argc, char** argv)
     std::printf("OWNWS %d %zu %zu %d\n", k, kept2[(size_t) k].size(), got2[(size_t) k].size(),
       same_chain(kept2[(size_t) k], got2[(size_t) k], kept_ref, h) ? 1 : 0);
   }
+  // the streamed calls, with the blocking call's results (kept, got: a workspace per capture) as the expectation: batch A is the
+  // captures, batch B the same captures in reverse order (fresh cloud objects: an End filters the NaNs out of its clouds in place)
+  std::vector<PointCloud::Ptr> a, b;
+  std::vector<int> sizes_left_b;
+  std::vector<std::vector<int> > idx_b;
+  std::vector<VectorXd> ws_b;
+  for (int k = 0; k < C; k++)
+  {
+    a.push_back(PointCloud::Ptr(new PointCloud(*c[(size_t) k].cloud)));
+    b.push_back(PointCloud::Ptr(new PointCloud(*c[(size_t) (C - 1 - k)].cloud)));
+    sizes_left_b.push_back(sizes_left[(size_t) (C - 1 - k)]);
+    idx_b.push_back(idx[(size_t) (C - 1 - k)]);
+    ws_b.push_back(ws[(size_t) (C - 1 - k)]);
+  }
+  std::printf("STREAM begin_a %d\n", loc.localizeHandlesBatchBegin(a, sizes_left, idx, svm, 2, 0.005, &ws) ? 1 : 0);
+  std::printf("STREAM rebegin_refused %d\n", loc.localizeHandlesBatchBegin(b, sizes_left_b, idx_b, svm, 2, 0.005, &ws_b) ? 0 : 1);
+  std::printf("STREAM stage_b %d\n", loc.stageNextBatch(b) ? 1 : 0);
+  std::vector<std::vector<GraspHypothesis> > kept_a, kept_b;
+  std::vector<std::vector<Handle> > got_a = loc.localizeHandlesBatchEnd(&kept_a);
+  bool same = (int) got_a.size() == C && (int) kept_a.size() == C;
+  for (int k = 0; same && k < C; k++)
+    same = same_chain(kept_a[(size_t) k], got_a[(size_t) k], kept[(size_t) k], got[(size_t) k]);
+  std::printf("STREAM end_a %d\n", same ? 1 : 0);
+  same = loc.localizeHandlesBatchBegin(b, sizes_left_b, idx_b, svm, 2, 0.005, &ws_b);  // (adopts the staged set)
+  std::vector<std::vector<Handle> > got_b = loc.localizeHandlesBatchEnd(&kept_b);
+  same = same && (int) got_b.size() == C && (int) kept_b.size() == C;
+  for (int k = 0; same && k < C; k++)
+    same = same_chain(kept_b[(size_t) k], got_b[(size_t) k], kept[(size_t) (C - 1 - k)], got[(size_t) (C - 1 - k)]);
+  std::printf("STREAM batch_b %d\n", same ? 1 : 0);
+  // the object is usable afterwards: capture 0 in one call (the object's workspace is capture 0's)
+  std::vector<GraspHypothesis> kept0;
+  PointCloud::Ptr copy0(new PointCloud(*c[0].cloud));
+  std::vector<Handle> handles0 = loc.localizeHandles(copy0, c[0].size_left, c[0].idx, svm, 2, 0.005, &kept0);
+  std::printf("STREAM after %d\n", same_chain(kept0, handles0, kept_ref0, handles_ref0) ? 1 : 0);
   return 0;
 }

@@ -229,7 +229,9 @@ def test_batch_capture_against_the_stage_wise_calls(svm_model):
 @pytest.mark.parametrize("filters", [0, 1])
 def test_adapter_batch_equals_localize_handles_per_capture(tmp_path, svm_model, filters):
     """Localization::localizeHandlesBatch against localizeHandles per capture (tests/cpp/localize_batch_test.cpp), with a
-    workspace per capture and with the object's own workspace."""
+    workspace per capture and with the object's own workspace; then localizeHandlesBatchBegin / stageNextBatch /
+    localizeHandlesBatchEnd on the same object against the blocking call's results (the STREAM rows: Begin, a refused second
+    Begin, the reversed batch staged, End, the staged batch adopted and collected, a plain localizeHandles afterwards)."""
     import os
     import subprocess
 
@@ -256,3 +258,6 @@ def test_adapter_batch_equals_localize_handles_per_capture(tmp_path, svm_model, 
     assert len(rows) == 6, out.stdout[-2000:]
     assert all(r[4] == "1" for r in rows), rows
     assert sum(int(r[3]) for r in rows if r[0] == "BATCH") > 0  # handles found
+    stream = [l.split() for l in out.stdout.splitlines() if l.startswith("STREAM ")]
+    assert len(stream) == 6, out.stdout[-2000:]
+    assert all(r[2] == "1" for r in stream), stream
