@@ -91,6 +91,8 @@ EXPORTS = [
     "agh_classify_sharded", "agh_default_plane_params", "agh_remove_plane", "agh_get_plane_inliers",
     "agh_get_plane_candidates", "agh_plane_replay", "agh_set_cloud_cam_origins", "agh_get_cloud_cam_origins",
     "agh_deproject", "agh_localize_depth", "agh_localize_depth_device", "agh_localize_depth_begin", "agh_localize_depth_stage",
+    "agh_deproject_batch", "agh_localize_depth_batch", "agh_localize_depth_batch_device", "agh_localize_depth_batch_begin",
+    "agh_localize_depth_batch_begin_device",
 ]
 
 
@@ -525,6 +527,54 @@ class Context:
         self._stage_keep = keep
         self._check(self.lib.agh_localize_depth_stage(self._h, recs, C.c_int32(len(recs))))
 
+    @staticmethod
+    def depth_batch_records(captures):
+        """The flat agh_depth_image array of a batch and its n_images: `captures` is a list of image lists (see
+        depth_image_records), capture k's images are the next n_images[k] records.  Returns (records, n_images, what keeps the
+        pixel buffers alive, on_device); torch CUDA tensors as `data` (in every image) select the device form."""
+        flat = [im for images in captures for im in images]
+        recs, keep, on_device = depth_image_records(flat)
+        n_images = (C.c_int32 * max(len(captures), 1))(*[len(images) for images in captures])
+        return recs, n_images, keep, on_device
+
+    def deproject_batch(self, captures) -> np.ndarray:
+        """agh_deproject_batch: the points k_deproject_batch makes of a batch of captures' depth images, (sum W x H, 3) float32,
+        capture after capture, each as deproject() returns it."""
+        recs, n_images, _keep, on_device = self.depth_batch_records(captures)
+        assert not on_device
+        n = sum(int(r.width) * int(r.height) for r in recs)
+        out = np.empty((n, 3), np.float32)
+        got = self._check(self.lib.agh_deproject_batch(self._h, recs, n_images, C.c_int32(len(captures)), _p(out, C.c_float),
+                                                       C.c_int64(n)))
+        assert got == n
+        return out
+
+    def _depth_batch_args(self, captures, workspaces, kw):
+        recs, n_images, keep, on_device = self.depth_batch_records(captures)
+        a = self._batch_args([], 0, workspaces, kw.pop("samples", None), kw.pop("n_samples", 0), kw.pop("sample_seeds", None),
+                             kw.pop("classify", True), kw.pop("min_inliers", 3), kw.pop("min_length", 0.005),
+                             kw.pop("filters_boundaries", 0), kw.pop("cell_size", 0.003), False, Ck=len(captures))
+        assert not kw, f"unknown arguments {sorted(kw)}"
+        a.update(recs=recs, n_images=n_images, keep=keep, on_device=on_device)
+        return a
+
+    def localize_depth_batch(self, captures, workspaces, caps=None, **kw):
+        """agh_localize_depth_batch (torch CUDA tensors as `data`: agh_localize_depth_batch_device): localize_batch() straight
+        from depth images.  `captures`: a list of image lists (one or two images each, see depth_image_records); image j of a
+        capture is its camera j.  workspaces, samples, n_samples, sample_seeds, classify, min_inliers, min_length,
+        filters_boundaries, cell_size and caps as for localize_batch.  Returns a list of dicts, one per capture."""
+        a = self._depth_batch_args(captures, workspaces, kw)
+        fn = self.lib.agh_localize_depth_batch_device if a["on_device"] else self.lib.agh_localize_depth_batch
+        return self._batch_collect(a, caps, lambda *out: fn(self._h, a["recs"], a["n_images"], a["lps"], C.c_int32(a["Ck"]), *out))
+
+    def localize_depth_batch_begin(self, captures, workspaces, **kw):
+        """agh_localize_depth_batch_begin (torch CUDA tensors: _begin_device): the depth batch's chain queued, nothing waited
+        for; collected by localize_batch_end().  The pixel buffers are kept alive until then."""
+        a = self._depth_batch_args(captures, workspaces, kw)
+        fn = self.lib.agh_localize_depth_batch_begin_device if a["on_device"] else self.lib.agh_localize_depth_batch_begin
+        self._check(fn(self._h, a["recs"], a["n_images"], a["lps"], C.c_int32(a["Ck"])))
+        self._batch_pending = a
+
     def localize_batch(self, captures, sizes_left, workspaces, samples=None, n_samples=0, sample_seeds=None,
                        classify: bool = True, min_inliers: int = 3, min_length: float = 0.005, filters_boundaries=0,
                        cell_size: float = 0.003, dense=False, caps=None):
@@ -541,16 +591,17 @@ class Context:
                                                             C.c_int32(a["Ck"]), *out))
 
     def _batch_args(self, captures, sizes_left, workspaces, samples, n_samples, sample_seeds, classify, min_inliers, min_length,
-                    filters_boundaries, cell_size, dense):
-        """The C arrays of a batch call: pointers, strides, counts and agh_localize_params records, and what keeps them alive."""
-        Ck = len(captures)
+                    filters_boundaries, cell_size, dense, Ck=None):
+        """The C arrays of a batch call: pointers, strides, counts and agh_localize_params records, and what keeps them alive.
+        (Ck: the number of captures of a depth batch, which has no point arrays.)"""
+        Ck = len(captures) if Ck is None else Ck
         per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * Ck
         sizes_left, dense_l, seeds = per(sizes_left), per(dense), per(1 if sample_seeds is None else sample_seeds)
         samples_l = per(samples) if isinstance(samples, (list, tuple)) else [samples] * Ck
         ns_l = per(n_samples)
         ws_a = np.asarray(workspaces, np.float64)
         ws_l = list(ws_a) if ws_a.ndim == 2 else [ws_a] * Ck
-        on_device = Ck > 0 and hasattr(captures[0], "is_cuda") and captures[0].is_cuda
+        on_device = len(captures) > 0 and hasattr(captures[0], "is_cuda") and captures[0].is_cuda
         keep, ptrs, strides, ns = self._capture_arrays(captures, on_device)
         lps = (AghLocalizeParams * max(Ck, 1))()
         S_list, sample_arrays = [], []

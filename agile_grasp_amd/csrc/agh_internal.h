@@ -310,6 +310,10 @@ struct Ctx
   uint8_t* d_depth_stage = nullptr;
   int64_t depth_cap = 0, depth_stage_cap = 0;  // bytes
   hipEvent_t depth_read = nullptr;  // recorded on `stream` behind the last k_deproject that read one of the two
+  // agh_localize_depth_batch* (depth.hip): the view table of k_deproject_batch, kMaxDepthViews records, filled in the pinned copy
+  // and uploaded on `stream` in front of the launch (a batch's host images lie in d_depth too, each at a 256-byte boundary)
+  uint8_t* d_depth_views = nullptr;
+  uint8_t* h_depth_views = nullptr;  // pinned
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
   LocalizeBatchState* lbatch = nullptr;  // agh_localize_batch's buffers (localize_batch.hip), made by its first call
   bool batch_active = false;       // inside agh_localize_batch (agh_localize_begin refuses)
@@ -1284,8 +1288,20 @@ int stage_captures(agh_ctx* ctx, const char* who, const float* const* xyz, const
 // depth.hip: the third source kind of the localize chain.  depth_check: the argument rules of include/agh.h (the error text names
 // the image and the field).  depth_to_raw: the images (host: uploaded into d_depth on `st`, or adopted from a staged set when
 // use_staged; device: read in place) back-projected by k_deproject on `st` into d_raw_xyz, packed, stride 12.
-int depth_check(agh::Ctx* c, const char* who, const agh_depth_image* images, int32_t n_images, bool on_device, int64_t* n_points);
+// capture >= 0: the images are capture `capture`'s of a batch, and the error text names it too ("capture 3, image 1: ...").
+int depth_check(agh::Ctx* c, const char* who, const agh_depth_image* images, int32_t n_images, bool on_device, int64_t* n_points,
+  int capture = -1);
 int depth_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, int n_images, bool on_device, bool use_staged,
   hipStream_t st);
+// The fourth source kind, a batch of captures as depth images (agh_localize_depth_batch*): `images` is the flat array in capture
+// order, capture k's are the next n_images[k].  depth_batch_check: 1 <= C <= 64, every n_images[k] 1 or 2, fewer than 2^30 points
+// in all, depth_check's rules per image; first[k] (C + 1 entries) = capture k's first point among the batch's, left0[k] = W0 x H0
+// of its image 0.  depth_batch_to_raw: every image of the batch back-projected by ONE k_deproject_batch on `st` into d_raw_xyz,
+// capture after capture, packed, stride 12 (host images uploaded into d_depth on `st`; drop_staged: a pending staged set of any
+// kind is dropped and `st` waits for its copies); a failure has drained `st`.
+int depth_batch_check(agh::Ctx* c, const char* who, const agh_depth_image* images, const int32_t* n_images, int32_t C, bool on_device,
+  std::vector<int64_t>* first, std::vector<int64_t>* left0);
+int depth_batch_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, const int32_t* n_images, int C, bool on_device,
+  bool drop_staged, hipStream_t st);
 int chain_collect(agh_ctx* ctx, const char* who, bool label_captures, int C, const int* counts, int count_stride, int64_t S_tot,
   const int* bad, int (*requeue)(agh_ctx*, bool handles_only));

@@ -14,6 +14,11 @@ namespace
 {
 constexpr int kRun = 4;       // consecutive pixels of one row per lane: 8 (U16) or 16 (F32) bytes in, 48 bytes = three 16-byte stores out
 constexpr int kDeprojBlock = 256;
+constexpr int kMaxDepthViews = 2 * kMaxClouds;  // k_deproject_batch's table: two images for each of a batch's captures
+
+typedef __attribute__((address_space(1))) uint8_t GlobalBytes;
+typedef uint32_t U32x2 __attribute__((ext_vector_type(2)));
+typedef float F32x4 __attribute__((ext_vector_type(4)));
 
 struct DepthView
 {
@@ -31,31 +36,30 @@ struct DepthArgs
   DepthView v[2];
 };
 
-// One lane = kRun consecutive pixels of one row of one image (a block belongs to ONE image, so the view is read with scalar loads).
+// One lane = kRun consecutive pixels of one row of one image (a block belongs to ONE image, so the view is read with scalar loads):
+// run g of the view `im`, runs row-major, im.runs per row.  The one copy of the per-run body, k_deproject's and k_deproject_batch's.
 // The contract's arithmetic (include/agh.h): float32, left to right, not contracted (-ffp-contract=off is the build's).
 // Wide accesses where the addresses allow them -- an 8-byte (U16) or 16-byte (F32) load of the run, three 16-byte stores of its
 // twelve floats -- element accesses on unaligned rows, on row tails and where the run's first point is not a multiple of four
 // points into the output.  Plain vector stores: the voxeliser reads the array next, from the L2.
-extern "C" __global__ __launch_bounds__(kDeprojBlock) void k_deproject(DepthArgs a, int n_images, float* __restrict__ out)
+__device__ __forceinline__ void deproject_run(const DepthView& im, int64_t g, float* __restrict__ out)
 {
-  const int k = (n_images > 1 && blockIdx.x >= a.v[1].first_block) ? 1 : 0;
-  const DepthView& im = a.v[k];
-  const int64_t g = (int64_t) (blockIdx.x - im.first_block) * kDeprojBlock + threadIdx.x;
   if (g >= (int64_t) im.runs * im.h)
     return;
   const int v = (int) (g / im.runs);
   const int u0 = (int) (g - (int64_t) v * im.runs) * kRun;
   const int cnt = min(kRun, im.w - u0);
-  const uint8_t* row = im.data + (int64_t) v * im.stride;
+  // (global, not flat, loads also where the pointer comes from the table and not from the kernel's arguments)
+  const GlobalBytes* row = (const GlobalBytes*) im.data + (int64_t) v * im.stride;
   float z[kRun];
   bool ok[kRun];
   if (im.fmt == AGH_DEPTH_U16)
   {
-    const uint16_t* p = reinterpret_cast<const uint16_t*>(row) + u0;
+    const __attribute__((address_space(1))) uint16_t* p = (const __attribute__((address_space(1))) uint16_t*) row + u0;
     uint32_t raw[kRun] = { 0, 0, 0, 0 };
-    if (cnt == kRun && (reinterpret_cast<uintptr_t>(p) & 7) == 0)
+    if (cnt == kRun && ((uintptr_t) p & 7) == 0)
     {
-      const uint2 q = *reinterpret_cast<const uint2*>(p);
+      const U32x2 q = *(const __attribute__((address_space(1))) U32x2*) p;
       raw[0] = q.x & 0xffffu;
       raw[1] = q.x >> 16;
       raw[2] = q.y & 0xffffu;
@@ -77,10 +81,10 @@ extern "C" __global__ __launch_bounds__(kDeprojBlock) void k_deproject(DepthArgs
   }
   else
   {
-    const float* p = reinterpret_cast<const float*>(row) + u0;
-    if (cnt == kRun && (reinterpret_cast<uintptr_t>(p) & 15) == 0)
+    const __attribute__((address_space(1))) float* p = (const __attribute__((address_space(1))) float*) row + u0;
+    if (cnt == kRun && ((uintptr_t) p & 15) == 0)
     {
-      const float4 q = *reinterpret_cast<const float4*>(p);
+      const F32x4 q = *(const __attribute__((address_space(1))) F32x4*) p;
       z[0] = q.x;
       z[1] = q.y;
       z[2] = q.z;
@@ -130,19 +134,55 @@ extern "C" __global__ __launch_bounds__(kDeprojBlock) void k_deproject(DepthArgs
   }
 }
 
+extern "C" __global__ __launch_bounds__(kDeprojBlock) void k_deproject(DepthArgs a, int n_images, float* __restrict__ out)
+{
+  const int k = (n_images > 1 && blockIdx.x >= a.v[1].first_block) ? 1 : 0;
+  const DepthView& im = a.v[k];
+  deproject_run(im, (int64_t) (blockIdx.x - im.first_block) * kDeprojBlock + threadIdx.x, out);
+}
+
+// Every image of every capture of a batch in one launch: the views (up to kMaxDepthViews, more than kernel arguments hold) are a
+// device table in launch order, `base` the index of the view's first point in the whole batch's array.  A work-group finds its
+// view with a uniform bisection over first_block -- the last view whose first block is at or before this one; every view has at
+// least one block -- and reads the record with scalar loads, as k_deproject reads its arguments.
+extern "C" __global__ __launch_bounds__(kDeprojBlock) void k_deproject_batch(const DepthView* __restrict__ views, int n_views,
+  float* __restrict__ out)
+{
+  int lo = 0, hi = n_views - 1;
+  while (lo < hi)
+  {
+    const int mid = (lo + hi + 1) >> 1;
+    if (views[mid].first_block <= blockIdx.x)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const DepthView& im = views[lo];
+  deproject_run(im, (int64_t) (blockIdx.x - im.first_block) * kDeprojBlock + threadIdx.x, out);
+}
+
 inline int64_t elem_size(int32_t format) { return format == AGH_DEPTH_U16 ? 2 : 4; }
 inline int64_t packed_bytes(const agh_depth_image& im) { return (int64_t) im.width * im.height * elem_size(im.format); }
-// where image k's packed rows start in a depth buffer of the context (256-byte aligned: the wide loads hold whenever the width does)
-inline int64_t depth_image_offset(const agh_depth_image* im, int k) { return k == 0 ? 0 : (packed_bytes(im[0]) + 255) / 256 * 256; }
+// where image k's packed rows start in a depth buffer of the context: the images of a capture (or of a whole batch, in capture
+// order) one after the other, each at a 256-byte boundary (the wide loads hold whenever the width does)
+inline int64_t aligned_bytes(const agh_depth_image& im) { return (packed_bytes(im) + 255) / 256 * 256; }
+inline int64_t depth_image_offset(const agh_depth_image* im, int k)
+{
+  int64_t off = 0;
+  for (int j = 0; j < k; j++)
+    off += aligned_bytes(im[j]);
+  return off;
+}
 inline int64_t depth_buffer_bytes(const agh_depth_image* im, int n) { return depth_image_offset(im, n - 1) + packed_bytes(im[n - 1]); }
 
 // host images into a depth buffer, rows packed (what was staged before stays ahead of these copies on its stream)
 hipError_t upload_images(uint8_t* dst, const agh_depth_image* im, int n, hipStream_t st)
 {
-  for (int k = 0; k < n; k++)
+  int64_t off = 0;
+  for (int k = 0; k < n; off += aligned_bytes(im[k]), k++)
   {
     const size_t row = (size_t) im[k].width * (size_t) elem_size(im[k].format);
-    uint8_t* d = dst + depth_image_offset(im, k);
+    uint8_t* d = dst + off;
     const hipError_t e = (size_t) im[k].row_stride_bytes == row
       ? hipMemcpyAsync(d, im[k].data, row * (size_t) im[k].height, hipMemcpyHostToDevice, st)
       : hipMemcpy2DAsync(d, row, im[k].data, (size_t) im[k].row_stride_bytes, row, (size_t) im[k].height, hipMemcpyHostToDevice, st);
@@ -150,6 +190,54 @@ hipError_t upload_images(uint8_t* dst, const agh_depth_image* im, int n, hipStre
       return e;
   }
   return hipSuccess;
+}
+
+// image `im` as k_deproject reads it: rows at `data` with `stride` bytes, its first point at `base`, its blocks from first_block on
+DepthView make_view(const agh_depth_image& im, const uint8_t* data, int64_t stride, int64_t base, uint32_t first_block)
+{
+  DepthView v;
+  std::memset(&v, 0, sizeof(v));
+  v.data = data;
+  v.stride = stride;
+  v.base = base;
+  v.w = im.width;
+  v.h = im.height;
+  v.fmt = im.format;
+  v.runs = (im.width + kRun - 1) / kRun;
+  v.first_block = first_block;
+  v.scale = im.depth_scale;
+  v.kx = (float) (1.0 / im.fx);
+  v.ky = (float) (1.0 / im.fy);
+  v.cx = (float) im.cx;
+  v.cy = (float) im.cy;
+  for (int q = 0; q < 12; q++)
+    v.p[q] = (float) im.pose[q];
+  return v;
+}
+inline uint32_t view_blocks(const DepthView& v) { return (uint32_t) (((int64_t) v.runs * v.h + kDeprojBlock - 1) / kDeprojBlock); }
+
+// the raw buffer for `total` points, and `st` behind the last batch chain that read it (as stage_captures waits, localize.hip)
+int raw_buffer_for(Ctx* c, int64_t total, hipStream_t st)
+{
+  if (3 * total > c->raw_cap || !c->d_raw_xyz)
+  {
+    if (int rc = dev_alloc(c, &c->d_raw_xyz, (size_t) (3 * total)))
+      return rc;
+    c->raw_cap = 3 * total;
+    c->raw_read_set = false;
+  }
+  if (c->raw_read_set)
+    AGH_HIPCHK(c, hipStreamWaitEvent(st, c->raw_read, 0));
+  return AGH_OK;
+}
+
+// behind the last reader of the context's depth buffers: a later agh_localize_depth_stage overwrites one of them
+int record_depth_read(Ctx* c, hipStream_t st)
+{
+  if (!c->depth_read)
+    AGH_HIPCHK(c, hipEventCreateWithFlags(&c->depth_read, hipEventDisableTiming));
+  AGH_HIPCHK(c, hipEventRecord(c->depth_read, st));
+  return AGH_OK;
 }
 
 int ensure_depth_buffer(Ctx* c, uint8_t** buf, int64_t* cap, int64_t need)
@@ -172,7 +260,7 @@ void swap_depth_buffers(Ctx* c)
 }
 }  // namespace
 
-int depth_check(Ctx* c, const char* who, const agh_depth_image* images, int32_t n_images, bool on_device, int64_t* n_points)
+int depth_check(Ctx* c, const char* who, const agh_depth_image* images, int32_t n_images, bool on_device, int64_t* n_points, int capture)
 {
   auto bad = [&](const std::string& what) {
     c->err = std::string(who) + ": " + what;
@@ -180,13 +268,14 @@ int depth_check(Ctx* c, const char* who, const agh_depth_image* images, int32_t 
   };
   if (!images)
     return bad("images is NULL");
+  const std::string cap = capture >= 0 ? "capture " + std::to_string(capture) : std::string();
   if (n_images != 1 && n_images != 2)
-    return bad("n_images must be 1 or 2");
+    return bad((capture >= 0 ? cap + ": " : cap) + "n_images must be 1 or 2");
   int64_t total = 0;
   for (int k = 0; k < n_images; k++)
   {
     const agh_depth_image& im = images[k];
-    const std::string at = "image " + std::to_string(k) + ": ";
+    const std::string at = (capture >= 0 ? cap + ", " : cap) + "image " + std::to_string(k) + ": ";
     if (!im.data)
       return bad(at + "data is NULL");
     if (im.width < 1 || im.width > 8192)
@@ -253,15 +342,8 @@ int depth_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, i
   int64_t total = 0;
   for (int k = 0; k < n_images; k++)
     total += (int64_t) images[k].width * images[k].height;
-  if (3 * total > c->raw_cap || !c->d_raw_xyz)
-  {
-    if ((rc = dev_alloc(c, &c->d_raw_xyz, (size_t) (3 * total))))
-      return rc;
-    c->raw_cap = 3 * total;
-    c->raw_read_set = false;
-  }
-  if (c->raw_read_set)  // the last batch chain that read the raw buffer the kernel overwrites (as stage_captures waits, localize.hip)
-    AGH_HIPCHK(c, hipStreamWaitEvent(st, c->raw_read, 0));
+  if ((rc = raw_buffer_for(c, total, st)))
+    return rc;
   DepthArgs a;
   std::memset(&a, 0, sizeof(a));
   int64_t base = 0;
@@ -269,25 +351,10 @@ int depth_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, i
   for (int k = 0; k < n_images; k++)
   {
     const agh_depth_image& im = images[k];
-    DepthView& v = a.v[k];
-    const int64_t es = elem_size(im.format);
-    v.data = on_device ? static_cast<const uint8_t*>(im.data) : c->d_depth + depth_image_offset(images, k);
-    v.stride = on_device ? im.row_stride_bytes : (int64_t) im.width * es;
-    v.base = base;
-    v.w = im.width;
-    v.h = im.height;
-    v.fmt = im.format;
-    v.runs = (im.width + kRun - 1) / kRun;
-    v.first_block = blocks;
-    v.scale = im.depth_scale;
-    v.kx = (float) (1.0 / im.fx);
-    v.ky = (float) (1.0 / im.fy);
-    v.cx = (float) im.cx;
-    v.cy = (float) im.cy;
-    for (int q = 0; q < 12; q++)
-      v.p[q] = (float) im.pose[q];
+    a.v[k] = on_device ? make_view(im, static_cast<const uint8_t*>(im.data), im.row_stride_bytes, base, blocks)
+                       : make_view(im, c->d_depth + depth_image_offset(images, k), (int64_t) im.width * elem_size(im.format), base, blocks);
     base += (int64_t) im.width * im.height;
-    blocks += (uint32_t) (((int64_t) v.runs * im.height + kDeprojBlock - 1) / kDeprojBlock);
+    blocks += view_blocks(a.v[k]);
   }
   hipLaunchKernelGGL(k_deproject, dim3(blocks), dim3(kDeprojBlock), 0, st, a, n_images, c->d_raw_xyz);
   if (hipGetLastError() != hipSuccess)
@@ -296,12 +363,99 @@ int depth_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, i
     return AGH_ERR_HIP;
   }
   if (!on_device)
+    return record_depth_read(c, st);
+  return AGH_OK;
+}
+
+int depth_batch_check(Ctx* c, const char* who, const agh_depth_image* images, const int32_t* n_images, int32_t C, bool on_device,
+  std::vector<int64_t>* first, std::vector<int64_t>* left0)
+{
+  auto bad = [&](const std::string& what) {
+    c->err = std::string(who) + ": " + what;
+    return AGH_ERR_INVALID_ARGUMENT;
+  };
+  if (C < 1 || C > kMaxClouds)
+    return bad("n_captures must be 1..64");
+  if (!images || !n_images)
+    return bad("images or n_images is NULL");
+  for (int k = 0; k < C; k++)
+    if (n_images[k] != 1 && n_images[k] != 2)
+      return bad("capture " + std::to_string(k) + ": n_images must be 1 or 2");
+  first->assign((size_t) C + 1, 0);
+  left0->assign((size_t) C, 0);
+  const agh_depth_image* im = images;
+  for (int k = 0; k < C; im += n_images[k], k++)
   {
-    // behind the last reader of the context's depth buffers: a later agh_localize_depth_stage overwrites one of them
-    if (!c->depth_read)
-      AGH_HIPCHK(c, hipEventCreateWithFlags(&c->depth_read, hipEventDisableTiming));
-    AGH_HIPCHK(c, hipEventRecord(c->depth_read, st));
+    int64_t n = 0;
+    if (int rc = depth_check(c, who, im, n_images[k], on_device, &n, k))
+      return rc;
+    (*first)[k + 1] = (*first)[k] + n;
+    (*left0)[k] = (int64_t) im[0].width * im[0].height;
   }
+  if ((*first)[C] >= (1ll << 30))
+    return bad("need fewer than 2^30 points in all");
+  return AGH_OK;
+}
+
+int depth_batch_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, const int32_t* n_images, int C, bool on_device,
+  bool drop_staged, hipStream_t st)
+{
+  Ctx* c = &ctx->c;
+  LocalizeState& L = c->loc;
+  static_assert(sizeof(DepthView) % 8 == 0, "the table's records are read with scalar loads");
+  auto fail = [c, st](int code) {
+    (void) hipStreamSynchronize(st);
+    return code;
+  };
+  int rc;
+  int views = 0;
+  for (int k = 0; k < C; k++)
+    views += n_images[k];
+  if (!c->d_depth_views)
+  {
+    void* pin = nullptr;
+    if ((rc = dev_alloc(c, &c->d_depth_views, sizeof(DepthView) * (size_t) kMaxDepthViews)))
+      return rc;
+    AGH_HIPCHK(c, hipHostMalloc(&pin, sizeof(DepthView) * (size_t) kMaxDepthViews, hipHostMallocDefault));
+    c->h_depth_views = static_cast<uint8_t*>(pin);
+  }
+  if (!on_device)
+  {
+    if (drop_staged)
+    {
+      // (a staged set of any kind is dropped; the chain waits for its copy, as every begin that does not adopt it does)
+      if (L.staged)
+        AGH_HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
+      L.staged = false;
+    }
+    if ((rc = ensure_depth_buffer(c, &c->d_depth, &c->depth_cap, depth_buffer_bytes(images, views))))
+      return rc;
+    AGH_HIPCHK_OR(c, upload_images(c->d_depth, images, views, st), fail(AGH_ERR_HIP));
+  }
+  DepthView* tab = reinterpret_cast<DepthView*>(c->h_depth_views);
+  int64_t base = 0, off = 0;
+  uint32_t blocks = 0;
+  for (int j = 0; j < views; j++)
+  {
+    const agh_depth_image& im = images[j];
+    tab[j] = on_device ? make_view(im, static_cast<const uint8_t*>(im.data), im.row_stride_bytes, base, blocks)
+                       : make_view(im, c->d_depth + off, (int64_t) im.width * elem_size(im.format), base, blocks);
+    base += (int64_t) im.width * im.height;
+    off += aligned_bytes(im);
+    blocks += view_blocks(tab[j]);
+  }
+  if ((rc = raw_buffer_for(c, base, st)))
+    return fail(rc);
+  AGH_HIPCHK_OR(c, hipMemcpyAsync(c->d_depth_views, tab, sizeof(DepthView) * (size_t) views, hipMemcpyHostToDevice, st), fail(AGH_ERR_HIP));
+  hipLaunchKernelGGL(k_deproject_batch, dim3(blocks), dim3(kDeprojBlock), 0, st, reinterpret_cast<const DepthView*>(c->d_depth_views),
+    views, c->d_raw_xyz);
+  if (hipGetLastError() != hipSuccess)
+  {
+    c->err = std::string(who) + ": k_deproject_batch launch failed";
+    return fail(AGH_ERR_HIP);
+  }
+  if (!on_device && (rc = record_depth_read(c, st)))
+    return fail(rc);
   return AGH_OK;
 }
 
@@ -339,6 +493,44 @@ int agh_deproject(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images,
     (void) hipStreamSynchronize(c->stream);
     return rc;
   }
+  AGH_HIPCHK_OR(c, hipMemcpyAsync(xyz_out, c->d_raw_xyz, sizeof(float) * 3 * (size_t) total, hipMemcpyDeviceToHost, c->stream),
+    ((void) hipStreamSynchronize(c->stream), AGH_ERR_HIP));
+  AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
+  return (int) total;
+}
+
+// agh_deproject for a batch: the points k_deproject_batch makes of every capture's images, capture after capture.
+int agh_deproject_batch(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images, int32_t n_captures, float* xyz_out,
+  int64_t cap_points)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_deproject_batch"))
+    return AGH_ERR_STATE;
+  if (c->batch_active)
+  {
+    c->err = "agh_deproject_batch: an agh_localize_batch is running on this context";
+    return AGH_ERR_STATE;
+  }
+  std::vector<int64_t> first, left0;
+  if (int rc = depth_batch_check(c, "agh_deproject_batch", images, n_images, n_captures, false, &first, &left0))
+    return rc;
+  const int64_t total = first[n_captures];
+  if (cap_points < 0 || (cap_points > 0 && !xyz_out))
+  {
+    c->err = "agh_deproject_batch: xyz_out is NULL or cap_points negative";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  if (total > cap_points)
+  {
+    c->err = "agh_deproject_batch: xyz_out holds fewer than the images' " + std::to_string(total) + " points";
+    return AGH_ERR_CAPACITY;
+  }
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  // (a staged set is left alone, as by agh_deproject)
+  if (int rc = depth_batch_to_raw(ctx, "agh_deproject_batch", images, n_images, n_captures, false, false, c->stream))
+    return rc;
   AGH_HIPCHK_OR(c, hipMemcpyAsync(xyz_out, c->d_raw_xyz, sizeof(float) * 3 * (size_t) total, hipMemcpyDeviceToHost, c->stream),
     ((void) hipStreamSynchronize(c->stream), AGH_ERR_HIP));
   AGH_HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -294,6 +294,17 @@ struct ActiveGuard
 
 const char* const kBadArguments = "agh_localize_batch: bad arguments (1 <= n_captures <= 64; see include/agh.h)";
 
+// A batch given as depth images (include/agh.h, agh_localize_depth_batch*): the batch chain's fourth source kind, beside host
+// points, device points and the staged batch.  k_deproject_batch (depth.hip) fills the context's raw buffer, capture after
+// capture; from there on the chain is the points batch's.
+struct DepthBatchSource
+{
+  const agh_depth_image* images;  // the flat array in capture order: capture k's are the next n_images[k]
+  const int32_t* n_images;
+  bool on_device;
+  const char* who;  // the entry point, for the error texts
+};
+
 // Steps 2 to 5 of the batch c->lbatch->call, queued on the context's stream: preprocessing, the batch of clouds, the sample list,
 // search -> classification -> kept hands per capture -> handle search.  Nothing waits, except the first batch of a context (or one
 // after the kept slots were dropped): one synchronisation for the lattice sizes.  An error has drained the stream (chain_fail).
@@ -465,17 +476,42 @@ int batch_pass(agh_ctx* ctx)
 // agh_localize_batch_begin: the arguments checked and copied, the captures up (or adopted from agh_localize_batch_stage, or read in
 // place), steps 2 to 5 queued.
 int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
-  const agh_localize_params* lp, int32_t n_captures)
+  const agh_localize_params* lp, int32_t n_captures, const DepthBatchSource* depth = nullptr)
 {
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
   const int C = n_captures;
+  const std::string who = depth ? depth->who : "agh_localize_batch";
   if (L.active)
   {
-    c->err = "agh_localize_batch: a localize chain is in flight on this context (agh_localize_end first)";
+    c->err = who + ": a localize chain is in flight on this context (agh_localize_end first)";
     return AGH_ERR_STATE;
   }
-  if (C < 1 || C > kMaxClouds || !xyz || !stride_bytes || !n || !lp)
+  std::vector<int64_t> depth_first, depth_left0, depth_n;
+  std::vector<agh_localize_params> depth_lp;
+  if (depth)
+  {
+    // (the arguments of the images first: their sizes are the captures'; then size_left and dense as include/agh.h fixes them)
+    if (int rc = depth_batch_check(c, depth->who, depth->images, depth->n_images, C, depth->on_device, &depth_first, &depth_left0))
+      return rc;
+    if (!lp)
+    {
+      c->err = who + ": lp is NULL";
+      return AGH_ERR_INVALID_ARGUMENT;
+    }
+    depth_lp.assign(lp, lp + C);
+    depth_n.resize((size_t) C);
+    for (int k = 0; k < C; k++)
+    {
+      depth_lp[k].size_left = depth_left0[k];
+      depth_lp[k].dense = 1;
+      depth_n[k] = depth_first[k + 1] - depth_first[k];
+    }
+    lp = depth_lp.data();
+    n = depth_n.data();
+    on_device = false;  // (the chain reads the context's raw buffer, whichever memory the images lie in)
+  }
+  else if (C < 1 || C > kMaxClouds || !xyz || !stride_bytes || !n || !lp)
   {
     c->err = kBadArguments;
     return AGH_ERR_INVALID_ARGUMENT;
@@ -484,16 +520,16 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   for (int k = 0; k < C; k++)
   {
     const agh_localize_params& p = lp[k];
-    if (bad_capture(xyz[k], stride_bytes[k], n[k]) || !(p.cell_size > 0.0) || p.size_left < 0 || p.n_samples < 0 ||
+    if ((!depth && bad_capture(xyz[k], stride_bytes[k], n[k])) || !(p.cell_size > 0.0) || p.size_left < 0 || p.n_samples < 0 ||
         p.n_samples > (1 << 24) || p.min_inliers < 1 || (p.filters_boundaries != 0 && p.filters_boundaries != 1))
     {
-      c->err = "agh_localize_batch: bad arguments for capture " + std::to_string(k) + " (see include/agh.h)";
+      c->err = who + ": bad arguments for capture " + std::to_string(k) + " (see include/agh.h)";
       return AGH_ERR_INVALID_ARGUMENT;
     }
     if (p.classify != lp[0].classify || p.cell_size != lp[0].cell_size || p.min_inliers != lp[0].min_inliers ||
         p.min_length != lp[0].min_length || p.filters_boundaries != lp[0].filters_boundaries)
     {
-      c->err = "agh_localize_batch: classify, cell_size, min_inliers, min_length and filters_boundaries must be equal across the "
+      c->err = who + ": classify, cell_size, min_inliers, min_length and filters_boundaries must be equal across the "
                "batch (capture " + std::to_string(k) + " differs from capture 0)";
       return AGH_ERR_INVALID_ARGUMENT;
     }
@@ -502,21 +538,21 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   }
   if (n_tot >= (1ll << 30) || S_tot > (1 << 24))
   {
-    c->err = "agh_localize_batch: need fewer than 2^30 raw points and at most 2^24 samples in all";
+    c->err = who + ": need fewer than 2^30 raw points and at most 2^24 samples in all";
     return AGH_ERR_INVALID_ARGUMENT;
   }
   if (lp[0].classify && !c->has_svm)
   {
-    c->err = "agh_localize_batch: classify needs a loaded SVM (agh_load_svm*)";
+    c->err = who + ": classify needs a loaded SVM (agh_load_svm*)";
     return AGH_ERR_NO_SVM;
   }
-  if (cam_table_mismatch(c, "agh_localize_batch", C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
+  if (cam_table_mismatch(c, who.c_str(), C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
     return AGH_ERR_INVALID_ARGUMENT;                    // the table stays the context's until agh_localize_batch_end: the setter
                                                         // refuses mid-chain, so the repeats search with it too)
   double x1 = 0.0, x2 = 0.0;
   if (!handle_thresholds(&x1, &x2))
   {
-    c->err = "agh_localize_batch: this libm's acos is not monotone around the 0.34 rad thresholds";
+    c->err = who + ": this libm's acos is not monotone around the 0.34 rad thresholds";
     return AGH_ERR_INVALID_ARGUMENT;
   }
   AGH_HIPCHK(c, hipSetDevice(c->device));
@@ -562,7 +598,18 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   for (int k = 0; k < C; k++)
     slot = std::max<int64_t>(slot, std::min<int64_t>(8 * lp[k].n_samples, 8192));
   B.slot = slot;
-  if (on_device)
+  if (depth)
+  {
+    // one launch back-projects the whole batch into the raw buffer, packed, capture after capture (an error has drained the stream)
+    if ((rc = depth_batch_to_raw(ctx, depth->who, depth->images, depth->n_images, C, depth->on_device, true, st)) != AGH_OK)
+      return rc;
+    for (int k = 0; k < C; k++)
+    {
+      B.d_raw[k] = c->d_raw_xyz + 3 * B.raw_off[k];
+      B.dev_stride[k] = 12;
+    }
+  }
+  else if (on_device)
     for (int k = 0; k < C; k++)
     {
       B.d_raw[k] = xyz[k];
@@ -729,7 +776,8 @@ void zero_results(agh_localize_batch_result* results, int C)
 // agh_localize_batch[_device] = begin + end
 int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
   const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
-  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results,
+  const DepthBatchSource* depth = nullptr)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
@@ -737,15 +785,15 @@ int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int6
   zero_results(results, n_captures);
   if (c->loc.active)
   {
-    c->err = "agh_localize_batch: a localize chain is in flight on this context (agh_localize_end first)";
+    c->err = std::string(depth ? depth->who : "agh_localize_batch") + ": a localize chain is in flight on this context (agh_localize_end first)";
     return AGH_ERR_STATE;
   }
   if (bad_outputs(handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap))
   {
-    c->err = kBadArguments;
+    c->err = depth ? std::string(depth->who) + ": bad output arguments (see include/agh.h)" : std::string(kBadArguments);
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  const int rc = batch_begin_impl(ctx, xyz, on_device, stride_bytes, n, lp, n_captures);
+  const int rc = batch_begin_impl(ctx, xyz, on_device, stride_bytes, n, lp, n_captures, depth);
   if (rc != AGH_OK)
     return rc;
   return batch_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
@@ -784,6 +832,43 @@ int agh_localize_batch_begin_device(agh_ctx* ctx, const float* const* xyz, const
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures);
+}
+
+// The batch chain straight from depth images: agh_localize_depth_batch[_device] = begin + agh_localize_batch_end.
+int agh_localize_depth_batch(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images, const agh_localize_params* lp,
+  int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch" };
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src);
+}
+
+int agh_localize_depth_batch_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_device" };
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src);
+}
+
+int agh_localize_depth_batch_begin(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_begin" };
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src);
+}
+
+int agh_localize_depth_batch_begin_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_begin_device" };
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src);
 }
 
 // The NEXT batch's captures up, beside whatever runs on the context's stream (stage_captures, localize.hip).  A pinned source must

@@ -281,7 +281,7 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * communicator's bookkeeping (agh_comm_rank, agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault,
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
  * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
- * agh_find_handles, agh_localize*, agh_deproject, agh_remove_plane, agh_get_cloud and every getter of device results (frames, normals,
+ * agh_find_handles, agh_localize* (agh_localize_depth_batch* among them), agh_deproject, agh_deproject_batch, agh_remove_plane, agh_get_cloud and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -414,7 +414,8 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  *                                               are the staged ones: the two raw buffers change places, nothing is uploaded.
  * agh_localize_batch(...) is begin + end; agh_localize_batch_begin_device reads device captures in place (nothing to stage).
  * The context has ONE chain and ONE staged set, of either kind.  A begin of either kind while a chain of either kind is in
- * flight, agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
+ * flight (agh_localize_depth_batch* and agh_localize_depth_batch_begin* included; agh_deproject_batch is refused too),
+ * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
  * agh_localize_end; every other call returns AGH_ERR_STATE without touching anything, a sharded call makes the rank a bystander,
@@ -434,6 +435,52 @@ int agh_localize_batch_begin_device(agh_ctx* ctx, const float* const* xyz, const
 int agh_localize_batch_stage(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int32_t n_captures);
 int agh_localize_batch_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+
+/* The batch chain straight from DEPTH IMAGES: the two fast ways into the chain together (a cell with several sensor pairs owns
+ * depth images, not points).  `images` is ONE flat array in capture order: n_images[k] is 1 or 2, capture k's images are the
+ * next n_images[k] records, image j of a capture is its camera j.  One kernel, k_deproject_batch, back-projects every image of
+ * every capture (up to 64 x 2 = 128 views, a table in device memory) on the context's stream into the raw buffer: capture k's
+ * points packed, stride 12, image 0 first, pixels row-major, the captures end to end in capture order -- what
+ * agh_localize_batch builds from host points -- and the batch chain runs unchanged from there.  lp[k].size_left and
+ * lp[k].dense are ignored: capture k runs with size_left = W0 x H0 of its own image 0 and dense = 1 (see agh_localize_depth).
+ * The arithmetic is agh_localize_depth's, word for word.
+ * Equality: capture k's results equal, bit for bit (epoch aside), what agh_localize_depth returns for capture k's images alone
+ * with lp[k]; they therefore also equal agh_localize_batch on the arrays agh_deproject writes, with stride 12,
+ * size_left = W0 x H0 and dense = 1.
+ * Everything of agh_localize_batch holds unchanged: the concatenated outputs and their spans, results[k], the per-capture
+ * 8192-hand limit, AGH_ERR_CAPACITY with every results[k] filled (size and repeat), the fields of lp that must be equal
+ * across the batch, the synchronisations, the repeats inside the call (they re-run from the points in the raw buffer), and the
+ * voxelised batch bound as the context's batch of clouds afterwards (camera id = image index).
+ * Camera origins stay the context's, or row k of agh_set_cloud_cam_origins for capture k: the poses do NOT set them.
+ * AGH_ERR_INVALID_ARGUMENT, nothing launched: n_captures outside 1..64; an n_images[k] other than 1 or 2; 2^30 points or more
+ * in all; every per-image rule of agh_localize_depth, the text naming the capture and the image ("capture 3, image 1: fx must
+ * be finite and not zero").  AGH_ERR_NO_SVM, the row count of a camera-origin table (n_captures rows) and AGH_ERR_STATE while a
+ * chain of any kind is in flight are as for agh_localize_batch.
+ * agh_localize_depth_batch_device: the images' `data` are device pointers, aligned to the element size, read in place with
+ * their row strides, valid until the call (or the chain's agh_localize_batch_end) has returned.
+ * agh_localize_depth_batch_begin[_device] queue the chain as agh_localize_batch_begin does and are collected with
+ * agh_localize_batch_end; between the two the rules of agh_localize_batch_begin hold.  The records, n_images and lp are copied
+ * by begin; host pixel buffers must stay valid and unchanged until agh_localize_batch_end has returned.  A begin of host images
+ * drops a pending staged set of any kind (agh_localize_stage, agh_localize_depth_stage, agh_localize_batch_stage), and the
+ * chain waits for its copies.
+ * agh_deproject_batch: introspection and tests, as agh_deproject -- the points k_deproject_batch makes of host images, into
+ * host memory; returns the point count, AGH_ERR_CAPACITY if cap_points is smaller, AGH_ERR_STATE while a chain is in flight or
+ * a batch runs.
+ * Not built: a _stage call for depth batches (for a single capture the staged depth stream measured 0.035 to 0.04 ms slower
+ * than the staged points stream, and the images are a sixth of the bytes: to be revisited only with a measurement), and
+ * points and depth captures mixed in one batch. */
+int agh_localize_depth_batch(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images, const agh_localize_params* lp,
+  int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+int agh_localize_depth_batch_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+int agh_localize_depth_batch_begin(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_depth_batch_begin_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_localize_params* lp, int32_t n_captures);
+int agh_deproject_batch(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images, int32_t n_captures, float* xyz_out,
+  int64_t cap_points);
 
 /* The context's current cloud: packed xyz (3 floats per point) and camera ids; returns the number of points. */
 int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap);

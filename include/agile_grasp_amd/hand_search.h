@@ -390,6 +390,68 @@ public:
     return true;
   }
 
+  /** Additional: localizeBatch straight from depth images (agh_localize_depth_batch = localizeDepthBatchBegin +
+   *  localizeBatchEnd): capture k is captures[k], one or two images (image j is camera j; an image without a pose takes this
+   *  search's j-th camera transform), with workspaces[k] and indices[k] (empty: num_samples drawn on the device, seeded with
+   *  the sample seed + k).  Outputs per capture as for localizeBatch.  @return false (after printing) on error */
+  bool localizeDepthBatch(const std::vector<std::vector<DepthImage> >& captures, const std::vector<VectorXd>& workspaces,
+    double cell_size, const std::vector<std::vector<int> >& indices, const std::string& svm_filename, int min_inliers,
+    double min_length, std::vector<std::vector<agh_hypothesis> >& hands_out, std::vector<std::vector<agh_handle> >& handles_out,
+    std::vector<std::vector<std::int32_t> >& inliers_out, bool filters_boundaries = false)
+  {
+    const std::size_t C = captures.size();
+    hands_out.assign(C, std::vector<agh_hypothesis>());
+    handles_out.assign(C, std::vector<agh_handle>());
+    inliers_out.assign(C, std::vector<std::int32_t>());
+    return localizeDepthBatchBegin(captures, workspaces, cell_size, indices, svm_filename, min_inliers, min_length,
+             filters_boundaries) &&
+           localizeBatchEnd(hands_out, handles_out, inliers_out);
+  }
+
+  /** agh_localize_depth_batch_begin: the batch's chain queued, collected by localizeBatchEnd.  The pixel buffers must stay alive
+   *  and unchanged until localizeBatchEnd has returned.  A Begin that fails leaves a chain in flight as it was. */
+  bool localizeDepthBatchBegin(const std::vector<std::vector<DepthImage> >& captures, const std::vector<VectorXd>& workspaces,
+    double cell_size, const std::vector<std::vector<int> >& indices, const std::string& svm_filename, int min_inliers,
+    double min_length, bool filters_boundaries = false)
+  {
+    const std::size_t C = captures.size();
+    if (C == 0 || workspaces.size() != C || indices.size() != C)
+    {
+      std::cout << " Error: localizeDepthBatchBegin needs one workspace and index list per capture\n";
+      return false;
+    }
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    const std::uint64_t seed = sampleSeed();
+    std::vector<agh_depth_image> recs;  // (the flat array in capture order; copied by the library's begin, like the arrays below)
+    std::vector<std::int32_t> n_images(C);
+    std::vector<agh_localize_params> lp(C);
+    std::vector<std::vector<std::int32_t> > idx(C);
+    std::int64_t cap = 1, n_samples = 0;
+    for (std::size_t k = 0; k < C; k++)
+    {
+      const std::vector<agh_depth_image> r = depthRecords(captures[k]);
+      recs.insert(recs.end(), r.begin(), r.end());
+      n_images[k] = (std::int32_t) r.size();
+      idx[k].assign(indices[k].begin(), indices[k].end());
+      // (size_left and dense are ignored: each capture's first image holds its camera 0's pixels)
+      lp[k] = chainParams(0, true, workspaces[k], cell_size, idx[k], seed + (std::uint64_t) k, min_inliers, min_length,
+        filters_boundaries);
+      cap += handsRoom(lp[k].n_samples);
+      n_samples += lp[k].n_samples;
+    }
+    if (agh_localize_depth_batch_begin(ctx_, recs.empty() ? nullptr : recs.data(), n_images.data(), lp.data(), (std::int32_t) C) !=
+        AGH_OK)
+    {
+      fail("agh_localize_depth_batch_begin");
+      return false;
+    }
+    batch_captures_ = C;
+    batch_cap_ = cap;
+    batch_samples_ = n_samples;
+    return true;
+  }
+
   /** Additional: the chain of localize over several captures in one call (localizeBatchBegin + localizeBatchEnd): capture k is clouds[k] with
    *  sizes_left[k], workspaces[k] and indices[k] (empty: num_samples drawn on the device, seeded with the sample seed + k).
    *  Per capture the hands the classifier kept, the handles and their inlier lists (indices into that capture's hands), exactly

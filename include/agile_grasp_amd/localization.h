@@ -453,6 +453,69 @@ public:
     return out;
   }
 
+  /** Additional: localizeHandlesBatch straight from depth images (agh_localize_depth_batch): capture k is captures[k], one or
+   *  two images as localizeHandlesDepth takes them, with indices_per_capture[k], searched in (*workspaces)[k] or this object's
+   *  workspace.  No clouds are built on the host.  Per capture the same handles as localizeHandlesDepth on that capture. */
+  std::vector<std::vector<Handle> > localizeHandlesDepthBatch(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<std::vector<int> >& indices_per_capture, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_capture = nullptr, const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatch") ||
+        !localizeHandlesDepthBatchBegin(captures, indices_per_capture, svm_filename, min_inliers, min_length, workspaces))
+      return noHandles(captures.size(), antipodal_hands_per_capture);
+    return localizeHandlesBatchEnd(antipodal_hands_per_capture);
+  }
+
+  /** ... and as two calls: the chain queued here is collected by localizeHandlesBatchEnd (it has no host clouds).  The pixel
+   *  buffers must stay alive and unchanged until then.  A Begin while a chain of any kind is pending returns false and leaves it
+   *  as it was, and so does a Begin that fails for another reason. */
+  bool localizeHandlesDepthBatchBegin(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<std::vector<int> >& indices_per_capture, const std::string& svm_filename, int min_inliers, double min_length,
+    const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatchBegin", "its End"))
+      return false;
+    for (std::size_t k = 0; k < captures.size(); k++)
+      if (captures[k].empty())
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    if (!detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(captures.size(), workspace_);
+    if (!search_->localizeDepthBatchBegin(captures, ws, 0.003, indices_per_capture, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
+      return false;
+    pending_batch_.assign(captures.size(), PointCloud::Ptr());  // (one entry per capture, none with a host cloud)
+    return true;
+  }
+
+  /** Additional: the same for captures of SEVERAL rigs, as the points batch has it: capture k was taken with the camera
+   *  transforms cams_left[k] / cams_right[k], whose translations become row k of the per-cloud origin table for this call (the
+   *  images' poses do not set origins).  The table is cleared afterwards in any case. */
+  std::vector<std::vector<Handle> > localizeHandlesDepthBatch(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<std::vector<int> >& indices_per_capture, const std::string& svm_filename, int min_inliers, double min_length,
+    const std::vector<Matrix4d>& cams_left, const std::vector<Matrix4d>& cams_right,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_capture = nullptr, const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (cams_left.size() != captures.size() || cams_right.size() != captures.size())
+    {
+      std::cout << " Error: localizeHandlesDepthBatch needs one left and one right camera transform per capture\n";
+      return noHandles(captures.size(), antipodal_hands_per_capture);
+    }
+    if (chainPending("localizeHandlesDepthBatch"))  // (a chain in flight keeps the table it has)
+      return noHandles(captures.size(), antipodal_hands_per_capture);
+    ensureSearch();
+    if (!search_->setCloudCamOrigins(cams_left, cams_right))
+      return noHandles(captures.size(), antipodal_hands_per_capture);
+    const std::vector<std::vector<Handle> > out = localizeHandlesDepthBatch(captures, indices_per_capture, svm_filename, min_inliers,
+      min_length, antipodal_hands_per_capture, workspaces);
+    search_->clearCloudCamOrigins();
+    return out;
+  }
+
   /** the searched hands, handles and inlier lists of one capture as the reference's objects (the tail of localizeHandlesEnd) */
   std::vector<Handle> toHandles(const PointCloud::Ptr& cloud_in, const std::vector<agh_hypothesis>& hands,
     const std::vector<agh_handle>& handles, const std::vector<std::int32_t>& idx, std::vector<GraspHypothesis>* antipodal_hands)
@@ -564,7 +627,7 @@ private:
   // localizeHandlesBegin -> localizeHandlesEnd
   PointCloud::Ptr pending_cloud_;
   bool pending_depth_ = false;  // (localizeHandlesDepthBegin -> localizeHandlesEnd: a chain without a host cloud)
-  // localizeHandlesBatchBegin -> localizeHandlesBatchEnd
+  // localizeHandlesBatchBegin -> localizeHandlesBatchEnd (localizeHandlesDepthBatchBegin: one empty pointer per capture)
   std::vector<PointCloud::Ptr> pending_batch_;
   std::unique_ptr<HandSearch> search_;
   PointCloud::Ptr last_cloud_;
