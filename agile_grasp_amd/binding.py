@@ -93,6 +93,8 @@ EXPORTS = [
     "agh_deproject", "agh_localize_depth", "agh_localize_depth_device", "agh_localize_depth_begin", "agh_localize_depth_stage",
     "agh_deproject_batch", "agh_localize_depth_batch", "agh_localize_depth_batch_device", "agh_localize_depth_batch_begin",
     "agh_localize_depth_batch_begin_device",
+    "agh_localize_masked", "agh_localize_masked_device", "agh_localize_masked_begin", "agh_localize_depth_masked",
+    "agh_localize_depth_masked_device", "agh_localize_depth_masked_begin", "agh_get_sample_mask_count",
 ]
 
 
@@ -229,6 +231,39 @@ def draw_samples(n_points: int, n_samples: int, seed: int) -> np.ndarray:
         else:
             out[k] = k if k < n_points else -(1 << 31)
     return out
+
+
+def masked_samples(eligible, n_samples: int, seed: int) -> np.ndarray:
+    """The sample list agh_localize_masked draws (include/agh.h): draw_samples' strata over the ascending list `eligible` of the
+    eligible voxel indices; with fewer eligible voxels than samples the list itself, then INT32_MIN."""
+    E = np.ascontiguousarray(eligible, np.int32)
+    pos = draw_samples(E.shape[0], n_samples, seed)
+    out = np.full(n_samples, -(1 << 31), np.int32)
+    ok = pos >= 0
+    out[ok] = E[pos[ok]]
+    return out
+
+
+class AghSampleMask(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("row_stride_bytes", C.c_int64)]
+
+
+def sample_mask_records(masks, on_device: bool):
+    """The agh_sample_mask records of a depth capture's masks: per image an (H, W) uint8 array whose rows may be padded (a torch
+    CUDA tensor for the _device call), or None: no pixel of that image is eligible.  Returns (records, what keeps them alive)."""
+    recs = (AghSampleMask * max(len(masks), 1))()
+    keep = []
+    for r, m in zip(recs, masks):
+        if m is None:
+            r.data, r.row_stride_bytes = None, 0
+        elif on_device:
+            assert m.is_cuda and m.dim() == 2 and m.stride(1) == 1 and m.element_size() == 1
+            r.data, r.row_stride_bytes = m.data_ptr(), int(m.stride(0))
+        else:
+            assert isinstance(m, np.ndarray) and m.ndim == 2 and m.dtype in (np.uint8, np.bool_) and m.strides[1] == 1
+            r.data, r.row_stride_bytes = m.ctypes.data, m.strides[0]
+        keep.append(m)
+    return recs, keep
 
 
 class AghPlaneParams(C.Structure):
@@ -513,6 +548,66 @@ class Context:
             return None
         fn = self.lib.agh_localize_depth_device if on_device else self.lib.agh_localize_depth
         return self._localize_blocking(fn, (recs, C.c_int32(len(recs))), lp, S, hcap)
+
+    def localize_masked(self, xyz, size_left: int, workspace, mask, n_samples: int = 0, sample_seed: int = 1, classify: bool = True,
+                        min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003, dense: bool = False,
+                        phase: str = "both", filters_boundaries: bool = False, samples=None):
+        """agh_localize_masked (torch CUDA tensors: agh_localize_masked_device): localize() with its n_samples drawn among the
+        voxels that hold a kept raw point with a non-zero byte in `mask` (one uint8 per raw point; None passes NULL, and
+        `samples` goes through for the library to refuse).  phase="begin": agh_localize_masked_begin, collected by
+        localize_end().  sample_mask_count() then gives the number of eligible voxels."""
+        on_device = hasattr(xyz, "is_cuda") and xyz.is_cuda
+        if on_device:
+            assert xyz.is_contiguous() and xyz.dim() == 2 and xyz.shape[1] >= 3
+            xyz_ptr, n_pts, stride_b = C.c_void_p(xyz.data_ptr()), int(xyz.shape[0]), int(xyz.stride(0)) * 4
+            if mask is not None:
+                assert mask.is_cuda and mask.dim() == 1 and mask.element_size() == 1 and mask.shape[0] == n_pts
+                assert n_pts <= 1 or mask.stride(0) == 1
+            mask_ptr = C.c_void_p(mask.data_ptr()) if mask is not None else None
+        else:
+            xyz = np.ascontiguousarray(xyz, np.float32)
+            assert xyz.ndim == 2 and xyz.shape[1] >= 3
+            xyz_ptr, n_pts, stride_b = _p(xyz, C.c_float), xyz.shape[0], xyz.shape[1] * 4
+            if mask is not None:
+                mask = np.ascontiguousarray(mask).view(np.uint8) if np.asarray(mask).dtype == np.bool_ else np.ascontiguousarray(mask, np.uint8)
+                assert mask.shape == (n_pts,)
+            mask_ptr = C.c_void_p(mask.ctypes.data) if mask is not None else None
+        lp, samples, S, hcap = self._localize_params(size_left, workspace, samples, n_samples, sample_seed, classify, min_inliers,
+                                                     min_length, cell_size, dense, filters_boundaries)
+        if phase == "begin":
+            assert not on_device
+            self._check(self.lib.agh_localize_masked_begin(self._h, xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts), mask_ptr,
+                                                           C.byref(lp)))
+            self._loc_keep = (xyz, mask, samples, lp)
+            self._loc_S = S
+            return None
+        fn = self.lib.agh_localize_masked_device if on_device else self.lib.agh_localize_masked
+        return self._localize_blocking(fn, (xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts), mask_ptr), lp, S, hcap)
+
+    def localize_depth_masked(self, images, masks, workspace, n_samples: int = 0, sample_seed: int = 1, classify: bool = True,
+                              min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003, phase: str = "both",
+                              filters_boundaries: bool = False, samples=None):
+        """agh_localize_depth_masked (torch CUDA tensors: agh_localize_depth_masked_device): localize_depth() with its samples
+        drawn under per-image masks (see sample_mask_records; `masks` None passes NULL).  phase="begin":
+        agh_localize_depth_masked_begin, collected by localize_end()."""
+        recs, keep, on_device = depth_image_records(images)
+        mrecs, mkeep = sample_mask_records(masks, on_device) if masks is not None else (None, [])
+        lp, samples, S, hcap = self._localize_params(0, workspace, samples, n_samples, sample_seed, classify, min_inliers, min_length,
+                                                     cell_size, False, filters_boundaries)
+        if phase == "begin":
+            assert not on_device
+            self._check(self.lib.agh_localize_depth_masked_begin(self._h, recs, mrecs, C.c_int32(len(recs)), C.byref(lp)))
+            self._loc_keep = (keep, mkeep, samples, lp)
+            self._loc_S = S
+            return None
+        fn = self.lib.agh_localize_depth_masked_device if on_device else self.lib.agh_localize_depth_masked
+        return self._localize_blocking(fn, (recs, mrecs, C.c_int32(len(recs))), lp, S, hcap)
+
+    def sample_mask_count(self) -> int:
+        """agh_get_sample_mask_count: the eligible voxels of the last masked chain this context collected."""
+        m = C.c_int64(0)
+        self._check(self.lib.agh_get_sample_mask_count(self._h, C.byref(m)))
+        return m.value
 
     def localize_depth_begin(self, images, workspace, **kw):
         """agh_localize_depth_begin: the chain of this capture queued, nothing waited for; localize_end() collects it."""

@@ -208,6 +208,10 @@ struct LocalizeState
   agh_localize_params lp{};   // (sample_idx cleared: the list lives in the pinned staging)
   const float* d_raw = nullptr;  // where the chain read the raw capture (the context's raw buffer or the caller's device memory)
   int64_t dev_stride = 0, n_raw = 0;
+  // agh_localize_masked* (sample_mask.hip): the chain draws its samples among the eligible voxels of a mask, one byte per raw
+  // point, packed -- in the context's d_mask or in the caller's device memory, where a repeat of the whole call reads it again
+  bool masked = false;
+  const uint8_t* d_mask = nullptr;
   // agh_localize_batch_begin / _stage / _end (localize_batch.hip) share the one chain and the one staged set of the context
   bool batch = false;         // the chain in flight is a batch's (agh_localize_batch_end collects it, not agh_localize_end)
   bool staged = false;        // stage_captures: a set of captures is (being) copied into d_stage_xyz, packed end to end,
@@ -304,6 +308,16 @@ struct Ctx
   bool raw_read_set = false, stage_read_set = false;    // d_stage_xyz (they change places with the buffers)
   LocalizeState loc;
   int64_t raw_cap = 0;             // floats
+  // sample masks (sample_mask.hip), allocated by the first masked call
+  uint8_t* d_mask = nullptr;       // the chain's copy of a host mask (depth masks: rows packed, image after image)
+  int64_t mask_cap = 0;            // bytes
+  unsigned* d_mask_bitmap = nullptr;  // eligibility bitmap: the voxel bitmap's layout, grown with it
+  int64_t mask_bitmap_cap = 0;     // words
+  int* d_mask_blk = nullptr;       // eligible bits per 4096 bitmap words, then their exclusive scan
+  long long* d_mask_total = nullptr;  // M, the eligible voxels
+  int32_t* d_mask_list = nullptr;  // E: the eligible voxel indices, ascending
+  int64_t mask_list_cap = 0;
+  int64_t mask_count = -1;         // M of the last chain agh_localize_end collected, -1 if that chain had no mask
   // agh_localize_depth* (depth.hip): a host capture's depth images, rows packed, image k at depth_image_offset(k); the NEXT
   // capture's (agh_localize_depth_stage) in the second buffer; the two change places when a staged set is adopted
   uint8_t* d_depth = nullptr;
@@ -691,6 +705,12 @@ int vox_stage1(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, int
   const double workspace[6], double cell, hipStream_t st, int64_t cap_words, VoxDesc* host_desc, bool with_lattice);
 int vox_stage2(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, double cell, int64_t n_words, hipStream_t st,
   VoxDesc* host_desc, bool with_lattice, int* cloud_off_out = nullptr);
+// voxelize.hip's block popcount and one-block scan on a bitmap of the voxel bitmap's layout (sample_mask.hip: the eligibility
+// bitmap): counts per 4096 words into blk, then their exclusive scan in place and the total
+int vox_count_blocks(const unsigned* d_bitmap, int64_t n_blocks, int* d_blk, long long* d_total, hipStream_t st);
+// sample_mask.hip: the masked sample list of a chain whose voxelisation is queued on st (include/agh.h, agh_localize_masked)
+int sample_mask_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, const uint8_t* d_mask, double cell, int64_t S,
+  unsigned long long seed, int32_t* d_out, int32_t* h_out, long long* h_count, hipStream_t st);
 int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
   unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st);
 // host mirror of the handle search's results (pinned memory of the context; all nullptr / 0: none)
@@ -753,6 +773,7 @@ int32_t next_epoch();
 int ensure_call_buffers(Ctx* c, int64_t S);
 int ensure_host_staging(Ctx* c, int64_t samples, int64_t records);
 constexpr int64_t kPinHeaderBytes = 256;  // pinned staging of the host-buffer entry points: [header | sample indices | records]
+constexpr int kPinMaskCount = 8;  // int64 word of that header that a masked chain writes M into (words 0 and 1: HostMirror::hdr)
 // (re)allocation of one of the context's device buffers
 template <typename T>
 inline int dev_alloc(Ctx* c, T** p, size_t count)
@@ -852,6 +873,20 @@ __device__ __forceinline__ unsigned enc_float(float f)
 __device__ __forceinline__ float dec_float(unsigned u)
 {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// Voxel index along one axis exactly as localization.cpp:288: floor((double(p) - min) / cell).
+__device__ __forceinline__ long long vox_index(float p, double mn, double cell)
+{
+  return (long long) floor(((double) p - mn) / cell);
+}
+// ... and the bit of a kept point of camera c in the lattice of its camera: x-major, z-fastest (voxelize.hip)
+__device__ __forceinline__ unsigned long long vox_bit(const VoxDesc* d, int c, const float* p, double cell)
+{
+  const unsigned long long ix = (unsigned long long) vox_index(p[0], d->mn[c][0], cell);
+  const unsigned long long iy = (unsigned long long) vox_index(p[1], d->mn[c][1], cell);
+  const unsigned long long iz = (unsigned long long) vox_index(p[2], d->mn[c][2], cell);
+  return (ix * (unsigned long long) d->dim[c][1] + iy) * (unsigned long long) d->dim[c][2] + iz;
 }
 
 __device__ __forceinline__ int cell_coord(const GridDesc& g, double v, int a)

@@ -1,7 +1,8 @@
 // localize.hip -- the online chain of the reference's only online caller as one call (or two halves of one):
 // GraspLocalizer::localizeGrasps, grasp_localizer.cpp:95-103 = localizeHands -> predictAntipodalHands -> findHandles per capture.
-// agh_localize / agh_localize_device / agh_localize_begin / agh_localize_stage / agh_localize_end and agh_localize_depth* of
-// include/agh.h (the back-projection of depth images: depth.hip); the stages
+// agh_localize / agh_localize_device / agh_localize_begin / agh_localize_stage / agh_localize_end, agh_localize_depth* and the
+// masked forms of both (agh_localize_masked*, agh_localize_depth_masked*) of include/agh.h (the back-projection of depth
+// images: depth.hip; the sample list under a mask: sample_mask.hip); the stages
 // themselves (preprocessing, search, classification, handle search) are api.hip's, voxelize.hip's, hog_svm.hip's and handles.hip's.
 #include "agh_internal.h"
 
@@ -244,21 +245,94 @@ struct DepthSource
   const char* who;  // the entry point, for the error texts
 };
 
+// A sample mask (include/agh.h, agh_localize_masked*): one byte per raw point for a points capture, one agh_sample_mask per
+// image for a depth capture.  Host masks are copied into the context's d_mask, depth masks row by row, packed, image after image
+// (a NULL image: zeros); a device points mask is read in place.
+struct MaskSource
+{
+  const uint8_t* points;          // points form: n bytes
+  const agh_sample_mask* images;  // depth form: one per image
+  bool on_device;
+  const char* who;
+};
+
+static int mask_check(Ctx* c, const MaskSource* mask, const DepthSource* depth, const agh_localize_params* lp)
+{
+  auto bad = [&](const std::string& what) {
+    c->err = std::string(mask->who) + ": " + what;
+    return AGH_ERR_INVALID_ARGUMENT;
+  };
+  if (lp->sample_idx)
+    return bad("a mask together with sample_idx (an explicit list needs no mask)");
+  if (!depth)
+    return mask->points ? AGH_OK : bad("the mask is NULL");
+  if (!mask->images)
+    return bad("masks is NULL");
+  bool any = false;
+  for (int k = 0; k < depth->n_images; k++)
+  {
+    if (!mask->images[k].data)
+      continue;
+    any = true;
+    if (mask->images[k].row_stride_bytes < depth->images[k].width)
+      return bad("mask " + std::to_string(k) + ": row_stride_bytes is below the image's width");
+  }
+  return any ? AGH_OK : bad("every mask's data is NULL (no pixel would be eligible)");
+}
+
+// the mask into d_mask on st (see MaskSource); *d_mask_out: where the chain reads it
+static int mask_to_device(Ctx* c, const MaskSource* mask, const DepthSource* depth, int64_t n, hipStream_t st, const uint8_t** d_mask_out)
+{
+  if (!depth && mask->on_device)
+  {
+    *d_mask_out = mask->points;
+    return AGH_OK;
+  }
+  if (n > c->mask_cap || !c->d_mask)
+  {
+    c->mask_cap = 0;
+    if (int rc = dev_alloc(c, &c->d_mask, (size_t) std::max<int64_t>(n, 1)))
+      return rc;
+    c->mask_cap = std::max<int64_t>(n, 1);
+  }
+  *d_mask_out = c->d_mask;
+  const hipMemcpyKind kind = mask->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (!depth)
+  {
+    if (n > 0)
+      AGH_HIPCHK(c, hipMemcpyAsync(c->d_mask, mask->points, (size_t) n, kind, st));
+    return AGH_OK;
+  }
+  int64_t off = 0;
+  for (int k = 0; k < depth->n_images; k++)
+  {
+    const size_t W = (size_t) depth->images[k].width, H = (size_t) depth->images[k].height;
+    const agh_sample_mask& m = mask->images[k];
+    if (!m.data)
+      AGH_HIPCHK(c, hipMemsetAsync(c->d_mask + off, 0, W * H, st));
+    else
+      AGH_HIPCHK(c, hipMemcpy2DAsync(c->d_mask + off, W, m.data, (size_t) m.row_stride_bytes, W, H, kind, st));
+    off += (int64_t) (W * H);
+  }
+  return AGH_OK;
+}
+
 static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int64_t stride_bytes, int64_t n,
-  const agh_localize_params* lp, const DepthSource* depth = nullptr)
+  const agh_localize_params* lp, const DepthSource* depth = nullptr, const MaskSource* mask = nullptr)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
+  const char* who = mask ? mask->who : (depth ? depth->who : "agh_localize_begin");
   if (L.active)
   {
-    c->err = std::string(depth ? depth->who : "agh_localize_begin") + ": a chain is in flight (agh_localize_end first)";
+    c->err = std::string(who) + ": a chain is in flight (agh_localize_end first)";
     return AGH_ERR_STATE;
   }
   if (c->batch_active)
   {
-    c->err = std::string(depth ? depth->who : "agh_localize_begin") + ": an agh_localize_batch is running on this context";
+    c->err = std::string(who) + ": an agh_localize_batch is running on this context";
     return AGH_ERR_STATE;
   }
   agh_localize_params lp_depth;
@@ -296,6 +370,9 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     c->err = "agh_localize: this libm's acos is not monotone around the 0.34 rad thresholds";
     return AGH_ERR_INVALID_ARGUMENT;
   }
+  if (mask)
+    if (int rc = mask_check(c, mask, depth, lp))
+      return rc;
   AGH_HIPCHK(c, hipSetDevice(c->device));
   const int64_t S = lp->n_samples;
   hipStream_t st = c->stream;
@@ -305,15 +382,23 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   // can ----
   const int64_t dev_stride = xyz_on_device ? stride_bytes : device_stride(stride_bytes);
   const float* d_raw = xyz;
+  // (a masked begin of host data never adopts a staged set: it drops a pending one as a begin of another kind does)
+  const bool adopts = !mask;
   if (depth)
   {
-    if ((rc = depth_to_raw(ctx, depth->who, depth->images, depth->n_images, depth->on_device, true, st)) != AGH_OK)
+    if (!adopts && !depth->on_device)
+    {
+      if (L.staged)
+        AGH_HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
+      L.staged = false;
+    }
+    if ((rc = depth_to_raw(ctx, depth->who, depth->images, depth->n_images, depth->on_device, adopts, st)) != AGH_OK)
       return rc;
     d_raw = c->d_raw_xyz;
   }
   else if (!xyz_on_device)
   {
-    if (L.staged_is(&xyz, &stride_bytes, &n, 1, false) && c->d_stage_xyz)
+    if (adopts && L.staged_is(&xyz, &stride_bytes, &n, 1, false) && c->d_stage_xyz)
     {
       // the capture is (or is about to be) in the second raw buffer: the two buffers change places, the chain waits for the copy
       swap_raw_buffers(c);
@@ -338,6 +423,11 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     }
     d_raw = c->d_raw_xyz;
   }
+  const uint8_t* d_mask = nullptr;
+  if (mask && (rc = mask_to_device(c, mask, depth, n, st, &d_mask)) != AGH_OK)
+    return chain_fail(c, rc);  // (the capture's copy may be in flight)
+  L.masked = mask != nullptr;
+  L.d_mask = d_mask;
   L.S = S;
   L.classify = lp->classify != 0;
   L.filters = lp->filters_boundaries != 0;
@@ -376,7 +466,13 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     AGH_HIPCHK_OR(c, ensure_keep_buffers(c, c->s_cap * 8), chain_fail(c, AGH_ERR_HIP));
   }
   // ---- 3. the sample list ----
-  if (S > 0)
+  if (mask)  // (for S = 0 too: the count of eligible voxels is what a caller sizes S with)
+  {
+    if ((rc = sample_mask_stage(c, d_raw, dev_stride / 4, n, d_mask, lp->cell_size, S, (unsigned long long) lp->sample_seed,
+           c->d_idx_own, h_idx, reinterpret_cast<long long*>(c->h_pin) + kPinMaskCount, st)) != AGH_OK)
+      return chain_fail(c, rc);
+  }
+  else if (S > 0)
   {
     if (lp->sample_idx)
     {
@@ -404,6 +500,7 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
   L.active = false;
+  c->mask_count = -1;
   const int64_t S = L.S;
   const HandlePins pin = handle_pins(c);
   const int* h_counts = pin.counts;
@@ -434,7 +531,9 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
         agh_localize_params lp = L.lp;
         lp.sample_idx = L.explicit_samples ? h_idx : nullptr;
         L.repeated = true;
-        rc = localize_begin_impl(ctx, L.d_raw, true, L.dev_stride, L.n_raw, &lp);
+        // (a mask is where the chain read it, as the capture is: in the context's buffer, or in the caller's device memory)
+        const MaskSource again{ L.d_mask, nullptr, true, "agh_localize_masked" };
+        rc = localize_begin_impl(ctx, L.d_raw, true, L.dev_stride, L.n_raw, &lp, nullptr, L.masked ? &again : nullptr);
         if (rc == AGH_OK)
           rc = localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
         c->loc.repeated = false;
@@ -452,6 +551,8 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
     c->cloud_off_on_device = true;  // ({0, nv}: what the voxeliser wrote)
     c->n_clouds = 1;
   }
+  if (L.masked)
+    c->mask_count = (int64_t) reinterpret_cast<const long long*>(c->h_pin)[kPinMaskCount];
   if ((rc = chain_collect(ctx, "agh_localize", false, 1, h_counts, 0, S, nullptr, localize_queue)) != AGH_OK)
     return rc;
   const int64_t n_hyp = h_counts[4], n_kept = h_counts[5];
@@ -478,7 +579,8 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
 // agh_localize[_device] = begin + end
 static int localize_call(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int64_t stride_bytes, int64_t n,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result, const DepthSource* depth = nullptr)
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result, const DepthSource* depth = nullptr,
+  const MaskSource* mask = nullptr)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
@@ -486,7 +588,7 @@ static int localize_call(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int
     *result = agh_localize_result{ 0, 0, 0, 0, 0 };
   int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
   if (rc == AGH_OK)
-    rc = localize_begin_impl(ctx, xyz, xyz_on_device, stride_bytes, n, lp, depth);
+    rc = localize_begin_impl(ctx, xyz, xyz_on_device, stride_bytes, n, lp, depth, mask);
   if (rc != AGH_OK)
     return rc;
   return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
@@ -565,6 +667,77 @@ int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, 
     return chain_fail(c, rc);
   }
   return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
+}
+
+// ---- the masked forms (include/agh.h): the chain with its samples drawn among the eligible voxels of a mask ----
+
+int agh_localize_masked(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const uint8_t* mask,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  const MaskSource m{ mask, nullptr, false, "agh_localize_masked" };
+  return localize_call(ctx, xyz, false, stride_bytes, n, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
+    samples_out, result, nullptr, &m);
+}
+
+int agh_localize_masked_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const uint8_t* d_mask,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  const MaskSource m{ d_mask, nullptr, true, "agh_localize_masked_device" };
+  return localize_call(ctx, d_xyz, true, stride_bytes, n, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
+    samples_out, result, nullptr, &m);
+}
+
+int agh_localize_masked_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const uint8_t* mask,
+  const agh_localize_params* lp)
+{
+  const MaskSource m{ mask, nullptr, false, "agh_localize_masked_begin" };
+  return localize_begin_impl(ctx, xyz, false, stride_bytes, n, lp, nullptr, &m);
+}
+
+int agh_localize_depth_masked(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, int32_t n_images,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  const DepthSource src{ images, n_images, false, "agh_localize_depth_masked" };
+  const MaskSource m{ nullptr, masks, false, src.who };
+  return localize_call(ctx, nullptr, false, 12, 0, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
+    samples_out, result, &src, &m);
+}
+
+int agh_localize_depth_masked_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, int32_t n_images,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+{
+  const DepthSource src{ images, n_images, true, "agh_localize_depth_masked_device" };
+  const MaskSource m{ nullptr, masks, true, src.who };
+  return localize_call(ctx, nullptr, false, 12, 0, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
+    samples_out, result, &src, &m);
+}
+
+int agh_localize_depth_masked_begin(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, int32_t n_images,
+  const agh_localize_params* lp)
+{
+  const DepthSource src{ images, n_images, false, "agh_localize_depth_masked_begin" };
+  const MaskSource m{ nullptr, masks, false, src.who };
+  return localize_begin_impl(ctx, nullptr, false, 12, 0, lp, &src, &m);
+}
+
+int agh_get_sample_mask_count(agh_ctx* ctx, int64_t* n_eligible)
+{
+  if (!ctx || !n_eligible)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_sample_mask_count"))
+    return AGH_ERR_STATE;
+  if (c->mask_count < 0)
+  {
+    c->err = "agh_get_sample_mask_count: the last chain this context collected had no mask (or there was none)";
+    return AGH_ERR_STATE;
+  }
+  *n_eligible = c->mask_count;
+  return AGH_OK;
 }
 
 // The NEXT capture up, beside the chain in flight (stage_captures, for a set of one).

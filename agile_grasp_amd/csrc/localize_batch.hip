@@ -675,6 +675,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   const int64_t S_tot = B.S_tot;
   c->loc.active = false;
   c->loc.batch = false;
+  c->mask_count = -1;  // (agh_get_sample_mask_count: the last chain collected had no mask)
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)

@@ -1,0 +1,182 @@
+// sample_mask.hip -- the sample list of a masked chain (include/agh.h, agh_localize_masked*; DESIGN.md, "Sample masks").
+//
+// The whole cloud stays in the search; only WHERE the samples are drawn is restricted: to the voxels that hold at least one kept
+// raw point with a non-zero mask byte.  The voxeliser (voxelize.hip) has left on the device what that takes: the per-raw-point
+// code[] (kept flag, camera id), the descriptor of the two lattices, the voxel bitmap and the exclusive scan of its 4096-word
+// blocks.  A second bitmap of the same layout takes the masked kept points (k_mask_mark); a bit set there is set in the voxel
+// bitmap too, and its rank among the voxel bits IS its index in the voxelised cloud (k_mask_emit); the list of those indices, E,
+// is ascending by construction, and the samples are draw_stratum's strata over it (k_draw_samples_masked).  Everything is queued
+// on the chain's stream behind the voxeliser: no synchronisation is added.
+#include "agh_internal.h"
+
+#include <algorithm>
+
+namespace agh
+{
+
+constexpr int kMaskWordsPerBlock = 4096;  // voxelize.hip's kWordsPerBlock: 16 words per thread of 256
+
+// Raw point i with mask[i] != 0 and code[i] != 0 sets the bit k_vox_mark set for it (vox_bit), in the eligibility bitmap.
+// A thread takes the four mask bytes of one ALIGNED 32-bit word: with the base `a` bytes into a word, word w holds the points
+// 4 w - a .. 4 w - a + 3; the words that straddle either end of the mask are read a byte at a time.
+__global__ __launch_bounds__(256) void k_mask_mark(const float* __restrict__ xyz, int64_t stride, int64_t n,
+  const uint8_t* __restrict__ code, const uint8_t* __restrict__ mask, const VoxDesc* __restrict__ d, double cell,
+  unsigned* __restrict__ elig)
+{
+  const int64_t a = (int64_t) (reinterpret_cast<uintptr_t>(mask) & 3u);
+  const int64_t i0 = 4 * ((int64_t) blockIdx.x * blockDim.x + threadIdx.x) - a;
+  if (i0 >= n || d->error)
+    return;
+  unsigned m = 0;
+  if (i0 >= 0 && i0 + 3 < n)
+    m = *reinterpret_cast<const unsigned*>(mask + i0);
+  else
+    for (int b = 0; b < 4; b++)
+      if (i0 + b >= 0 && i0 + b < n)
+        m |= (unsigned) mask[i0 + b] << (8 * b);
+  if (!m)
+    return;
+  for (int b = 0; b < 4; b++)
+  {
+    if (!((m >> (8 * b)) & 0xffu))
+      continue;
+    const int64_t i = i0 + b;
+    const unsigned cd = code[i];
+    if (!cd)
+      continue;
+    const int c = (int) (cd >> 1);
+    const unsigned long long pos = vox_bit(d, c, xyz + i * stride, cell);
+    atomicOr(&elig[d->word_ofs[c] + (pos >> 5)], 1u << (unsigned) (pos & 31ull));
+  }
+}
+
+// One work-group per block of 4096 words, a thread holding its 16 words of BOTH bitmaps.  An eligible bit's voxel index is the
+// block's voxel prefix + the voxel bits before it in the block (camera 1 starts on a block boundary: its offset is in the
+// prefix); it goes to E at the block's eligible prefix + the eligible bits before it in the block.
+__global__ __launch_bounds__(256) void k_mask_emit(const unsigned* __restrict__ vox, const unsigned* __restrict__ elig,
+  const int* __restrict__ vox_prefix, const int* __restrict__ elig_prefix, const VoxDesc* __restrict__ d, int32_t* __restrict__ E)
+{
+  const size_t w0 = (size_t) blockIdx.x * kMaskWordsPerBlock + (size_t) threadIdx.x * 16;
+  unsigned v[16], e[16];
+  const uint4* vs = reinterpret_cast<const uint4*>(vox + w0);
+  const uint4* es = reinterpret_cast<const uint4*>(elig + w0);
+  int vcnt = 0, ecnt = 0;
+  for (int k = 0; k < 4; k++)
+  {
+    const uint4 x = vs[k], y = es[k];
+    v[4 * k] = x.x, v[4 * k + 1] = x.y, v[4 * k + 2] = x.z, v[4 * k + 3] = x.w;
+    e[4 * k] = y.x, e[4 * k + 1] = y.y, e[4 * k + 2] = y.z, e[4 * k + 3] = y.w;
+    vcnt += __popc(x.x) + __popc(x.y) + __popc(x.z) + __popc(x.w);
+    ecnt += __popc(y.x) + __popc(y.y) + __popc(y.z) + __popc(y.w);
+  }
+  int vincl = vcnt, eincl = ecnt;
+  for (int o = 1; o < 64; o <<= 1)
+  {
+    const int a = __shfl_up(vincl, o), b = __shfl_up(eincl, o);
+    if ((int) (threadIdx.x & 63) >= o)
+    {
+      vincl += a;
+      eincl += b;
+    }
+  }
+  __shared__ int vsum[4], esum[4];
+  if ((threadIdx.x & 63) == 63)
+  {
+    vsum[threadIdx.x >> 6] = vincl;
+    esum[threadIdx.x >> 6] = eincl;
+  }
+  __syncthreads();
+  if (!(esum[0] + esum[1] + esum[2] + esum[3]) || d->error)  // (most blocks of an object mask)
+    return;
+  int vr = vox_prefix[blockIdx.x] + vincl - vcnt, er = elig_prefix[blockIdx.x] + eincl - ecnt;
+  for (int q = 0; q < (int) (threadIdx.x >> 6); q++)
+  {
+    vr += vsum[q];
+    er += esum[q];
+  }
+  for (int j = 0; j < 16; j++)
+  {
+    unsigned bits = e[j];
+    while (bits)
+    {
+      const int b = __ffs(bits) - 1;
+      bits &= bits - 1;
+      E[er++] = (int32_t) (vr + __popc(v[j] & ((1u << b) - 1u)));
+    }
+    vr += __popc(v[j]);
+  }
+}
+
+// Sample k of S over the M eligible voxels: E[draw_stratum(M, S, k, seed)], and with M < S the list itself, then kSampleSkip
+// (agh_internal.h).  Written to the device list and to its pinned mirror as k_draw_samples does; M goes to the pinned header.
+__global__ void k_draw_samples_masked(const int32_t* __restrict__ E, const long long* __restrict__ total, int S,
+  unsigned long long seed, int32_t* __restrict__ out, int32_t* __restrict__ host_out, long long* __restrict__ host_count)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const long long M = *total;
+  if (k == 0 && host_count)
+    *host_count = M;
+  if (k >= S)
+    return;
+  int32_t v = draw_stratum(M, S, k, seed);
+  if (v != kSampleSkip)
+    v = E[v];
+  out[k] = v;
+  if (host_out)
+    host_out[k] = v;
+}
+
+int sample_mask_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, const uint8_t* d_mask, double cell, int64_t S,
+  unsigned long long seed, int32_t* d_out, int32_t* h_out, long long* h_count, hipStream_t st)
+{
+  int rc;
+  // (the voxel bitmap exists: the preprocessing queued in front of this stage sized or kept it)
+  const int64_t words = c->vox_bitmap_cap;
+  if (!c->d_mask_blk)
+  {
+    if ((rc = dev_alloc(c, &c->d_mask_blk, (size_t) (kVoxMaxWords / kMaskWordsPerBlock) + 1)) ||
+        (rc = dev_alloc(c, &c->d_mask_total, 1)))
+      return rc;
+  }
+  if (words > c->mask_bitmap_cap || !c->d_mask_bitmap)
+  {
+    c->mask_bitmap_cap = 0;
+    if ((rc = dev_alloc(c, &c->d_mask_bitmap, (size_t) words + kMaskWordsPerBlock)))
+      return rc;
+    c->mask_bitmap_cap = words;
+  }
+  if (n > c->mask_list_cap || !c->d_mask_list)  // (M <= the voxel count <= n)
+  {
+    c->mask_list_cap = 0;
+    if ((rc = dev_alloc(c, &c->d_mask_list, (size_t) std::max<int64_t>(n, 1024))))
+      return rc;
+    c->mask_list_cap = std::max<int64_t>(n, 1024);
+  }
+  const int64_t nb = n > 0 ? words / kMaskWordsPerBlock : 0;  // (no point, no bit: vox_stage2 wrote no block counts either)
+  if (nb > 0)
+  {
+    AGH_HIPCHK(c, hipMemsetAsync(c->d_mask_bitmap, 0, (size_t) words * 4, st));
+    const int64_t mask_words = (n + 3 + 3) / 4;  // (aligned words that a base up to 3 bytes into one can touch)
+    hipLaunchKernelGGL(k_mask_mark, dim3((unsigned) ((mask_words + 255) / 256)), dim3(256), 0, st, d_xyz, stride_floats, n,
+      (const uint8_t*) c->d_vox_code, d_mask, (const VoxDesc*) c->d_vox_desc, cell, c->d_mask_bitmap);
+  }
+  if ((rc = vox_count_blocks(c->d_mask_bitmap, nb, c->d_mask_blk, c->d_mask_total, st)) != AGH_OK)
+  {
+    c->err = "sample mask launch failed";
+    return rc;
+  }
+  if (nb > 0)
+    hipLaunchKernelGGL(k_mask_emit, dim3((unsigned) nb), dim3(256), 0, st, (const unsigned*) c->d_vox_bitmap,
+      (const unsigned*) c->d_mask_bitmap, (const int*) c->d_vox_blk2, (const int*) c->d_mask_blk, (const VoxDesc*) c->d_vox_desc,
+      c->d_mask_list);
+  hipLaunchKernelGGL(k_draw_samples_masked, dim3((unsigned) std::max<int64_t>(1, (S + 255) / 256)), dim3(256), 0, st,
+    (const int32_t*) c->d_mask_list, (const long long*) c->d_mask_total, (int) S, seed, d_out, h_out, h_count);
+  if (hipGetLastError() != hipSuccess)
+  {
+    c->err = "sample mask launch failed";
+    return AGH_ERR_HIP;
+  }
+  return AGH_OK;
+}
+
+}  // namespace agh

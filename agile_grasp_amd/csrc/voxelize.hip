@@ -272,11 +272,7 @@ __global__ __launch_bounds__(kPreBlock) void k_vox_classify(const float* __restr
     atomicAdd((unsigned long long*) &d->n_kept[threadIdx.x], (unsigned long long) skept[threadIdx.x]);
 }
 
-// Voxel index along one axis exactly as localization.cpp:288: floor((double(p) - min) / cell).
-__device__ __forceinline__ long long vox_index(float p, double mn, double cell)
-{
-  return (long long) floor(((double) p - mn) / cell);
-}
+// (vox_index, the voxel index along one axis, exactly as localization.cpp:288: agh_internal.h)
 
 // error: 1 = the lattice exceeds max_words (the hard limit), 2 = it exceeds cap_words, the bitmap the host has allocated from an
 // earlier cloud (stage 2 was launched speculatively for that size and does nothing; the host enlarges and repeats).
@@ -376,11 +372,7 @@ __global__ __launch_bounds__(256) void k_vox_mark(const float* __restrict__ xyz,
   if (!cd || d->error)
     return;
   const int c = (int) (cd >> 1);
-  const float* p = xyz + i * stride;
-  const unsigned long long ix = (unsigned long long) vox_index(p[0], d->mn[c][0], cell);
-  const unsigned long long iy = (unsigned long long) vox_index(p[1], d->mn[c][1], cell);
-  const unsigned long long iz = (unsigned long long) vox_index(p[2], d->mn[c][2], cell);
-  const unsigned long long pos = (ix * (unsigned long long) d->dim[c][1] + iy) * (unsigned long long) d->dim[c][2] + iz;
+  const unsigned long long pos = vox_bit(d, c, xyz + i * stride, cell);  // (agh_internal.h: k_mask_mark sets the same bit)
   atomicOr(&bitmap[d->word_ofs[c] + (pos >> 5)], 1u << (unsigned) (pos & 31ull));
 }
 
@@ -621,6 +613,15 @@ int vox_stage2(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, dou
   if (n > 0 && n_words > 0)
     hipLaunchKernelGGL(k_vox_emit, dim3((unsigned) nb2), dim3(256), 0, st, (const unsigned*) c->d_vox_bitmap,
       (const int*) c->d_vox_blk2, (const VoxDesc*) c->d_vox_desc, cell, c->d_vox_xyz, c->d_vox_cam, VoxBatch{}, (const int*) nullptr);
+  return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
+}
+
+int vox_count_blocks(const unsigned* d_bitmap, int64_t n_blocks, int* d_blk, long long* d_total, hipStream_t st)
+{
+  if (n_blocks > 0)
+    hipLaunchKernelGGL(k_vox_popcount, dim3((unsigned) n_blocks), dim3(256), 0, st, d_bitmap, d_blk, VoxBatch{});
+  hipLaunchKernelGGL(k_vox_scan, dim3(1), dim3(1024), 0, st, d_blk, n_blocks, d_total, (VoxDesc*) nullptr, (VoxDesc*) nullptr,
+    (VoxDesc*) nullptr, (int*) nullptr, VoxBatch{});
   return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
 }
 

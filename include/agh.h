@@ -281,7 +281,9 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * communicator's bookkeeping (agh_comm_rank, agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault,
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
  * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
- * agh_find_handles, agh_localize* (agh_localize_depth_batch* among them), agh_deproject, agh_deproject_batch, agh_remove_plane, agh_get_cloud and every getter of device results (frames, normals,
+ * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
+ * agh_localize_depth_masked* and agh_localize_depth_masked_begin among them), agh_deproject, agh_deproject_batch,
+ * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -355,6 +357,70 @@ int agh_localize_depth_device(agh_ctx* ctx, const agh_depth_image* images, int32
 int agh_localize_depth_begin(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp);
 int agh_localize_depth_stage(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images);
 
+/* The same chains with their samples drawn UNDER A MASK: "find grasps on this object".  A caller of the chain owns a capture and
+ * a per-point (per-pixel) object mask from a detector or segmenter; explicit sample_idx cannot express it, because they index
+ * the voxelised cloud, which is built inside the call.  The whole cloud stays in the search (the hand sweep needs the scene for
+ * its collision tests); only where the SAMPLES are drawn is restricted.
+ * mask: one byte per raw point of the capture, packed, entry i belongs to raw point i; any non-zero byte means "eligible".
+ *  1. A voxel of the voxelised cloud is eligible iff at least one raw point with a non-zero mask byte was kept by the
+ *     preprocessing (finite unless dense, inside workspace) and falls into it -- into the voxel of the point's own camera block
+ *     (camera ids by the voxeliser's rule: rank in the NaN-free cloud >= size_left for dense = 0, the raw index for dense = 1).
+ *     A masked point that the preprocessing drops makes nothing eligible.
+ *  2. E is the list of the eligible voxel indices, ascending; M = |E|.
+ *  3. Sample k of S = n_samples is E[stratum draw of agh_localize with M in the place of N]; with M < S the first M samples are
+ *     E[0..M) and the rest are unused slots, INT32_MIN in samples_out, as for N < S.  M = 0 is no error: AGH_OK with zero
+ *     hypotheses, hands and handles.
+ *  4. Everything behind the sample list is the chain of agh_localize, unchanged: the results equal, bit for bit (epoch aside),
+ *     what agh_localize returns on the same capture and lp with sample_idx set to the list samples_out reports (INT32_MIN
+ *     slots included: an explicit list may carry them, they are skipped).  With an all-ones mask the call equals agh_localize
+ *     with sample_idx = NULL and the same seed.
+ *  5. A mask together with lp->sample_idx != NULL is AGH_ERR_INVALID_ARGUMENT: an explicit list needs no mask.
+ *  6. The mask stage runs for n_samples = 0 too: agh_get_sample_mask_count is what a caller sizes S with.
+ * agh_localize_masked_device: d_xyz and d_mask are device pointers, read in place (valid until the call returns); d_mask may
+ * have any byte alignment.  agh_localize_masked_begin queues the chain as agh_localize_begin does; agh_localize_end collects it.
+ * The depth forms: masks[k] belongs to images[k], same width and height, one byte per pixel, row v at
+ * data + v * row_stride_bytes (>= width).  data == NULL: NO pixel of that image is eligible (a caller with one mask for a
+ * two-camera capture wants samples on the masked view only); all NULL is AGH_ERR_INVALID_ARGUMENT.
+ * agh_localize_depth_masked equals agh_localize_masked on the array agh_deproject writes (stride 12, size_left = W0 x H0,
+ * dense = 1) with the masks' rows packed end to end in image order, a NULL mask contributing zeros; a masked invalid pixel is a
+ * NaN point and is dropped like any other.  agh_localize_depth_masked_device: the images' and the masks' data are device
+ * pointers.
+ * Errors, nothing launched: a NULL mask (points) or NULL masks (depth), or a mask row stride below the width ->
+ * AGH_ERR_INVALID_ARGUMENT; every validation, error text and status of the unmasked twin; AGH_ERR_STATE while a chain or a
+ * batch is in flight.
+ * Staging: a masked begin of host data never adopts a staged set; it drops a pending one as a begin of another kind does (the
+ * chain waits for its copy).  The mask is copied by begin into a buffer of the context (depth masks repacked to one byte per
+ * pixel, image after image); a device mask of the points form is read in place and follows the capture's lifetime rules.  The
+ * repeats inside the call (the lattice that outgrew the kept bitmap, the capacity classes) need the caller's mask in no other
+ * way than they need the caller's capture.  One more bitmap of the voxel bitmap's size is held by a context that made a masked
+ * call; the chain's one synchronisation stays one.
+ * Not built: a _stage call for masks; masks for agh_localize_batch* and agh_localize_depth_batch*; label images (several
+ * objects, one sample list each); sharded variants. */
+typedef struct agh_sample_mask
+{
+  const uint8_t* data;       /* one byte per pixel, non-zero = eligible; NULL: no pixel of this image is */
+  int64_t row_stride_bytes;  /* >= the image's width */
+} agh_sample_mask;
+int agh_localize_masked(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const uint8_t* mask,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result);
+int agh_localize_masked_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const uint8_t* d_mask,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result);
+int agh_localize_masked_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const uint8_t* mask,
+  const agh_localize_params* lp);
+int agh_localize_depth_masked(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, int32_t n_images,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result);
+int agh_localize_depth_masked_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, int32_t n_images,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result);
+int agh_localize_depth_masked_begin(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, int32_t n_images,
+  const agh_localize_params* lp);
+/* The eligible voxels (M) of the last masked chain this context collected.  AGH_ERR_STATE if the last chain collected had no
+ * mask, if there was none, or while a chain is in flight. */
+int agh_get_sample_mask_count(agh_ctx* ctx, int64_t* n_eligible);
+
 /* The chain of agh_localize over a BATCH of captures in one call, with ONE synchronisation (offline evaluation over a
  * directory of PCD pairs, a cell with several sensors or arms): 1 <= n_captures <= 64, fewer than 2^30 raw points in all.
  * Capture k is xyz[k] (stride_bytes[k], n[k] points) with its own record lp[k]: size_left, dense, workspace, sample_idx /
@@ -414,7 +480,9 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  *                                               are the staged ones: the two raw buffers change places, nothing is uploaded.
  * agh_localize_batch(...) is begin + end; agh_localize_batch_begin_device reads device captures in place (nothing to stage).
  * The context has ONE chain and ONE staged set, of either kind.  A begin of either kind while a chain of either kind is in
- * flight (agh_localize_depth_batch* and agh_localize_depth_batch_begin* included; agh_deproject_batch is refused too),
+ * flight (agh_localize_depth_batch* and agh_localize_depth_batch_begin* included, agh_localize_masked*,
+ * agh_localize_masked_begin, agh_localize_depth_masked* and agh_localize_depth_masked_begin too; agh_deproject_batch and
+ * agh_get_sample_mask_count are refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of

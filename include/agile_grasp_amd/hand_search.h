@@ -376,6 +376,73 @@ public:
     return true;
   }
 
+  /** Additional: the chain of localizeBegin with its num_samples drawn UNDER A MASK (agh_localize_masked_begin): `mask` holds one
+   *  byte per point of cloud_in, non-zero = a sample may be drawn in the voxel this point falls into.  The whole cloud stays in
+   *  the search.  Collected by localizeEnd; sampleMaskCount() then tells how many voxels were eligible.  `mask` is copied by the
+   *  call; cloud_in must stay alive and unchanged until localizeEnd has returned. */
+  bool localizeMaskedBegin(const PointCloud::Ptr& cloud_in, int size_left, const std::vector<std::uint8_t>& mask,
+    const VectorXd& workspace, double cell_size, const std::string& svm_filename, int min_inliers, double min_length,
+    bool filters_boundaries = false)
+  {
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    if (mask.size() != cloud_in->points.size())
+    {
+      std::cout << " Error: localizeMaskedBegin needs one mask byte per point of the cloud\n";
+      return false;
+    }
+    const agh_localize_params lp = chainParams(size_left, cloud_is_dense(*cloud_in), workspace, cell_size, std::vector<std::int32_t>(),
+      sampleSeed(), min_inliers, min_length, filters_boundaries);
+    const RawPoints in = rawPoints(*cloud_in);
+    if (agh_localize_masked_begin(ctx_, in.xyz, in.stride, in.n, mask.data(), &lp) != AGH_OK)
+    {
+      fail("agh_localize_masked_begin");
+      return false;
+    }
+    chainBegun(lp.n_samples);
+    return true;
+  }
+
+  /** ... and straight from depth images (agh_localize_depth_masked_begin): masks[k] belongs to images[k]; a mask without data
+   *  makes no pixel of its image eligible. */
+  bool localizeDepthMaskedBegin(const std::vector<DepthImage>& images, const std::vector<SampleMask>& masks, const VectorXd& workspace,
+    double cell_size, const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    if (masks.size() != images.size())
+    {
+      std::cout << " Error: localizeDepthMaskedBegin needs one mask per image\n";
+      return false;
+    }
+    const agh_localize_params lp = chainParams(0, true, workspace, cell_size, std::vector<std::int32_t>(), sampleSeed(), min_inliers,
+      min_length, filters_boundaries);
+    const std::vector<agh_depth_image> recs = depthRecords(images);
+    std::vector<agh_sample_mask> mrecs(masks.size());
+    for (std::size_t k = 0; k < masks.size(); k++)
+    {
+      mrecs[k].data = masks[k].data;
+      mrecs[k].row_stride_bytes = masks[k].row_stride_bytes;
+    }
+    if (agh_localize_depth_masked_begin(ctx_, recs.empty() ? nullptr : recs.data(), mrecs.empty() ? nullptr : mrecs.data(),
+          (std::int32_t) recs.size(), &lp) != AGH_OK)
+    {
+      fail("agh_localize_depth_masked_begin");
+      return false;
+    }
+    chainBegun(lp.n_samples);
+    return true;
+  }
+
+  /** agh_get_sample_mask_count: the eligible voxels of the last masked chain localizeEnd collected, -1 if it had no mask */
+  std::int64_t sampleMaskCount()
+  {
+    std::int64_t m = -1;
+    if (!ctx_ || agh_get_sample_mask_count(ctx_, &m) != AGH_OK)
+      return -1;
+    return m;
+  }
+
   /** agh_localize_depth_stage: the NEXT capture's images up, beside the chain in flight */
   bool localizeDepthStage(const std::vector<DepthImage>& next)
   {

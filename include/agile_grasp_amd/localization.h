@@ -346,6 +346,96 @@ public:
     return true;
   }
 
+  /** Additional: localizeHandles with the samples drawn UNDER A MASK ("find grasps on this object"): `mask` holds one byte per
+   *  point of cloud_in, as a detector or segmenter labels the capture; num_samples samples are drawn among the voxels that hold a
+   *  masked point, and the whole cloud stays in the search for the hand's collision tests.  Otherwise as localizeHandles. */
+  std::vector<Handle> localizeHandlesMasked(const PointCloud::Ptr& cloud_in, int size_left, const std::vector<std::uint8_t>& mask,
+    const std::string& svm_filename, int min_inliers, double min_length, std::vector<GraspHypothesis>* antipodal_hands = nullptr)
+  {
+    if (antipodal_hands)
+      antipodal_hands->clear();
+    if (!localizeHandlesMaskedBegin(cloud_in, size_left, mask, svm_filename, min_inliers, min_length))
+      return std::vector<Handle>();
+    return localizeHandlesEnd(antipodal_hands);
+  }
+
+  /** ... as Begin + localizeHandlesEnd.  A Begin while a chain is pending returns false and leaves that chain as it was. */
+  bool localizeHandlesMaskedBegin(const PointCloud::Ptr& cloud_in, int size_left, const std::vector<std::uint8_t>& mask,
+    const std::string& svm_filename, int min_inliers, double min_length)
+  {
+    if (chainPending("localizeHandlesMaskedBegin"))
+      return false;
+    if (size_left == 0 || !cloud_in || cloud_in->size() == 0)
+    {
+      std::cout << "Input cloud is empty!\n";
+      std::cout << size_left << std::endl;
+      return false;
+    }
+    if (!detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    if (!search_->localizeMaskedBegin(cloud_in, size_left, mask, workspace_, 0.003, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
+      return false;
+    pending_cloud_ = cloud_in;
+    return true;
+  }
+
+  /** ... and straight from depth images with one mask per image (agh_localize_depth_masked); a mask without data makes no
+   *  pixel of its image eligible.  Otherwise as localizeHandlesDepth. */
+  std::vector<Handle> localizeHandlesDepthMasked(const std::vector<DepthImage>& images, const std::vector<SampleMask>& masks,
+    const std::string& svm_filename, int min_inliers, double min_length, std::vector<GraspHypothesis>* antipodal_hands = nullptr)
+  {
+    if (antipodal_hands)
+      antipodal_hands->clear();
+    if (!localizeHandlesDepthMaskedBegin(images, masks, svm_filename, min_inliers, min_length))
+      return std::vector<Handle>();
+    return localizeHandlesEnd(antipodal_hands);
+  }
+
+  bool localizeHandlesDepthMaskedBegin(const std::vector<DepthImage>& images, const std::vector<SampleMask>& masks,
+    const std::string& svm_filename, int min_inliers, double min_length)
+  {
+    if (chainPending("localizeHandlesDepthMaskedBegin"))
+      return false;
+    if (images.empty())
+    {
+      std::cout << "Input cloud is empty!\n";
+      return false;
+    }
+    if (!detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    if (!search_->localizeDepthMaskedBegin(images, masks, workspace_, 0.003, svm_filename, min_inliers, min_length, filters_boundaries_))
+      return false;
+    pending_depth_ = true;
+    return true;
+  }
+
+  /** The seed of the samples a chain draws on the device (HandSearch::setSampleSeed; default: the clock, like pcl::RandomSample),
+   *  and the list the last collected chain searched (HandSearch::getLastSampleIndices): together they make a masked call
+   *  repeatable with explicit indices. */
+  void setSampleSeed(std::uint64_t seed)
+  {
+    sample_seed_ = seed;
+    sample_seed_set_ = true;
+    if (search_)
+      search_->setSampleSeed(seed);
+  }
+  std::vector<int> getLastSampleIndices() const
+  {
+    if (!search_)
+      return std::vector<int>();
+    return std::vector<int>(search_->getLastSampleIndices().begin(), search_->getLastSampleIndices().end());
+  }
+
+  /** The eligible voxels of the last masked chain localizeHandlesEnd collected (agh_get_sample_mask_count); -1 if that chain had
+   *  no mask, if there was none, or while a chain is pending. */
+  std::int64_t getSampleMaskCount()
+  {
+    return search_ ? search_->sampleMaskCount() : -1;
+  }
+
   /** agh_localize_depth_stage through the adapter: the next capture's images up, beside the chain in flight */
   bool stageNextDepth(const std::vector<DepthImage>& next)
   {
@@ -613,6 +703,8 @@ private:
     search_->setDeterministicNormalEstimation(deterministic_);
     search_->setDevice(device_);
     search_->setKeepsTrainingImages(keeps_training_images_);
+    if (sample_seed_set_)
+      search_->setSampleSeed(sample_seed_);
   }
 
   int num_threads_, num_samples_;
@@ -624,6 +716,8 @@ private:
   bool deterministic_;
   int device_;
   bool keeps_training_images_ = false;
+  std::uint64_t sample_seed_ = 1;
+  bool sample_seed_set_ = false;
   // localizeHandlesBegin -> localizeHandlesEnd
   PointCloud::Ptr pending_cloud_;
   bool pending_depth_ = false;  // (localizeHandlesDepthBegin -> localizeHandlesEnd: a chain without a host cloud)

@@ -157,6 +157,16 @@ struct DepthImage
   {
   }
 };
+// A per-pixel object mask for one DepthImage (a detector's or segmenter's output), for the chains that draw their samples under a
+// mask (agh_localize_depth_masked, include/agh.h): one byte per pixel, non-zero = samples may be drawn here; the bytes stay the
+// caller's.  data == nullptr: no pixel of that image is eligible.
+struct SampleMask
+{
+  const std::uint8_t* data;        // row-major; row v at data + v * row_stride_bytes
+  std::int64_t row_stride_bytes;   // >= the image's width
+  SampleMask() : data(nullptr), row_stride_bytes(0) {}
+  SampleMask(const std::uint8_t* d, std::int64_t stride) : data(d), row_stride_bytes(stride) {}
+};
 }  // namespace agile_grasp_amd
 
 static_assert(sizeof(float) == 4, "float32 expected");
