@@ -95,6 +95,8 @@ EXPORTS = [
     "agh_localize_depth_batch_begin_device",
     "agh_localize_masked", "agh_localize_masked_device", "agh_localize_masked_begin", "agh_localize_depth_masked",
     "agh_localize_depth_masked_device", "agh_localize_depth_masked_begin", "agh_get_sample_mask_count",
+    "agh_localize_labeled", "agh_localize_labeled_device", "agh_localize_depth_labeled", "agh_localize_depth_labeled_device",
+    "agh_get_label_counts",
 ]
 
 
@@ -261,6 +263,36 @@ def sample_mask_records(masks, on_device: bool):
             r.data, r.row_stride_bytes = m.data_ptr(), int(m.stride(0))
         else:
             assert isinstance(m, np.ndarray) and m.ndim == 2 and m.dtype in (np.uint8, np.bool_) and m.strides[1] == 1
+            r.data, r.row_stride_bytes = m.ctypes.data, m.strides[0]
+        keep.append(m)
+    return recs, keep
+
+
+def labeled_samples(eligible_lists, n_samples: int, seed: int) -> np.ndarray:
+    """The sample list agh_localize_labeled draws (include/agh.h): masked_samples of every object's ascending list of eligible
+    voxel indices with the one seed, object after object (n_objects x n_samples entries)."""
+    if not len(eligible_lists) or n_samples == 0:
+        return np.zeros(0, np.int32)
+    return np.concatenate([masked_samples(E, n_samples, seed) for E in eligible_lists])
+
+
+class AghLabelImage(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("row_stride_bytes", C.c_int64)]
+
+
+def label_image_records(labels, on_device: bool):
+    """The agh_label_image records of a depth capture's label images: as sample_mask_records, the bytes being labels (0: no
+    object, j + 1: object j), or None: no pixel of that image belongs to an object."""
+    recs = (AghLabelImage * max(len(labels), 1))()
+    keep = []
+    for r, m in zip(recs, labels):
+        if m is None:
+            r.data, r.row_stride_bytes = None, 0
+        elif on_device:
+            assert m.is_cuda and m.dim() == 2 and m.stride(1) == 1 and m.element_size() == 1
+            r.data, r.row_stride_bytes = m.data_ptr(), int(m.stride(0))
+        else:
+            assert isinstance(m, np.ndarray) and m.ndim == 2 and m.dtype == np.uint8 and m.strides[1] == 1
             r.data, r.row_stride_bytes = m.ctypes.data, m.strides[0]
         keep.append(m)
     return recs, keep
@@ -608,6 +640,61 @@ class Context:
         m = C.c_int64(0)
         self._check(self.lib.agh_get_sample_mask_count(self._h, C.byref(m)))
         return m.value
+
+    def _localize_labeled(self, fn, capture_args, n_objects, lp, S, caps):
+        """The tail of the labelled forms: the blocking call and one dict per object, as localize_batch's per capture."""
+        K = int(n_objects)
+        a = {"Ck": K if 1 <= K <= 64 else 0, "S_list": [S] * (K if 1 <= K <= 64 else 0)}
+        out = self._batch_collect(a, caps, lambda *o: fn(self._h, *capture_args, C.c_int32(K), C.byref(lp), *o))
+        self.n = out[0]["n_voxels"] if out else 0  # (one cloud, whose voxel count every object reports)
+        return out
+
+    def localize_labeled(self, xyz, size_left: int, workspace, labels, n_objects: int, n_samples: int = 0, sample_seed: int = 1,
+                         classify: bool = True, min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003,
+                         dense: bool = False, filters_boundaries: bool = False, samples=None, caps=None):
+        """agh_localize_labeled (torch CUDA tensors: agh_localize_labeled_device): one capture, one label byte per raw point (0:
+        no object, j + 1: object j), n_samples drawn for EACH of the n_objects objects among its own eligible voxels; one search,
+        one handle search per object side by side, one synchronisation.  Returns a list of n_objects dicts shaped like
+        localize_batch's; object j's equal localize_masked(mask = labels == j + 1).  label_counts() then gives the M_j.
+        (`labels` None passes NULL and `samples` goes through, for the library to refuse.)"""
+        on_device = hasattr(xyz, "is_cuda") and xyz.is_cuda
+        if on_device:
+            assert xyz.is_contiguous() and xyz.dim() == 2 and xyz.shape[1] >= 3
+            xyz_ptr, n_pts, stride_b = C.c_void_p(xyz.data_ptr()), int(xyz.shape[0]), int(xyz.stride(0)) * 4
+            if labels is not None:
+                assert labels.is_cuda and labels.dim() == 1 and labels.element_size() == 1 and labels.shape[0] == n_pts
+                assert n_pts <= 1 or labels.stride(0) == 1
+            lab_ptr = C.c_void_p(labels.data_ptr()) if labels is not None else None
+        else:
+            xyz = np.ascontiguousarray(xyz, np.float32)
+            assert xyz.ndim == 2 and xyz.shape[1] >= 3
+            xyz_ptr, n_pts, stride_b = _p(xyz, C.c_float), xyz.shape[0], xyz.shape[1] * 4
+            if labels is not None:
+                labels = np.ascontiguousarray(labels, np.uint8)
+                assert labels.shape == (n_pts,)
+            lab_ptr = C.c_void_p(labels.ctypes.data) if labels is not None else None
+        lp, samples, S, _ = self._localize_params(size_left, workspace, samples, n_samples, sample_seed, classify, min_inliers,
+                                                  min_length, cell_size, dense, filters_boundaries)
+        fn = self.lib.agh_localize_labeled_device if on_device else self.lib.agh_localize_labeled
+        return self._localize_labeled(fn, (xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts), lab_ptr), n_objects, lp, S, caps)
+
+    def localize_depth_labeled(self, images, labels, workspace, n_objects: int, n_samples: int = 0, sample_seed: int = 1,
+                               classify: bool = True, min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003,
+                               filters_boundaries: bool = False, samples=None, caps=None):
+        """agh_localize_depth_labeled (torch CUDA tensors: agh_localize_depth_labeled_device): localize_labeled() straight from
+        depth images with one label image per depth image (see label_image_records; `labels` None passes NULL)."""
+        recs, keep, on_device = depth_image_records(images)
+        lrecs, lkeep = label_image_records(labels, on_device) if labels is not None else (None, [])
+        lp, samples, S, _ = self._localize_params(0, workspace, samples, n_samples, sample_seed, classify, min_inliers, min_length,
+                                                  cell_size, False, filters_boundaries)
+        fn = self.lib.agh_localize_depth_labeled_device if on_device else self.lib.agh_localize_depth_labeled
+        return self._localize_labeled(fn, (recs, lrecs, C.c_int32(len(recs))), n_objects, lp, S, caps)
+
+    def label_counts(self, cap_objects: int = 64) -> np.ndarray:
+        """agh_get_label_counts: the eligible voxels M_j of every object of the last labelled chain this context collected."""
+        m = np.full(max(cap_objects, 1), -1, np.int64)  # (the call writes n_objects counts, none of them negative)
+        self._check(self.lib.agh_get_label_counts(self._h, _p(m, C.c_int64), C.c_int32(cap_objects)))
+        return m[m >= 0].copy()
 
     def localize_depth_begin(self, images, workspace, **kw):
         """agh_localize_depth_begin: the chain of this capture queued, nothing waited for; localize_end() collects it."""

@@ -212,6 +212,9 @@ struct LocalizeState
   // point, packed -- in the context's d_mask or in the caller's device memory, where a repeat of the whole call reads it again
   bool masked = false;
   const uint8_t* d_mask = nullptr;
+  // agh_localize_labeled* (sample_labels.hip): the bytes are labels, 1 .. n_objects, and the chain draws S samples for each
+  // object (0: a mask); from the classifier on its tail is the batch chain's, one list per object (localize_batch.hip)
+  int32_t n_objects = 0;
   // agh_localize_batch_begin / _stage / _end (localize_batch.hip) share the one chain and the one staged set of the context
   bool batch = false;         // the chain in flight is a batch's (agh_localize_batch_end collects it, not agh_localize_end)
   bool staged = false;        // stage_captures: a set of captures is (being) copied into d_stage_xyz, packed end to end,
@@ -318,6 +321,17 @@ struct Ctx
   int32_t* d_mask_list = nullptr;  // E: the eligible voxel indices, ascending
   int64_t mask_list_cap = 0;
   int64_t mask_count = -1;         // M of the last chain agh_localize_end collected, -1 if that chain had no mask
+  // label images (sample_labels.hip), allocated by the first labelled call; the lists E_j share d_mask_list
+  unsigned* d_label_rank = nullptr;   // per bitmap word: the voxel bits in front of it inside its 4096-word block
+  int64_t label_rank_cap = 0;         // words
+  unsigned long long* d_label_set = nullptr;  // per voxel: the set of the objects eligible there
+  int64_t label_set_cap = 0;
+  int* d_label_groups = nullptr;      // per object and work-group of 256 voxels: eligible voxels, then their exclusive scan
+  int64_t label_group_cap = 0;
+  long long* d_label_totals = nullptr;  // kMaxClouds: the M_j
+  long long* h_label_counts = nullptr;  // pinned: the M_j, written by the chain
+  int32_t label_objects = 0;          // n_objects of the last chain collected if it was labelled, else 0
+  int64_t label_counts[kMaxClouds] = {};  // ... and its M_j
   // agh_localize_depth* (depth.hip): a host capture's depth images, rows packed, image k at depth_image_offset(k); the NEXT
   // capture's (agh_localize_depth_stage) in the second buffer; the two change places when a staged set is adopted
   uint8_t* d_depth = nullptr;
@@ -711,6 +725,10 @@ int vox_count_blocks(const unsigned* d_bitmap, int64_t n_blocks, int* d_blk, lon
 // sample_mask.hip: the masked sample list of a chain whose voxelisation is queued on st (include/agh.h, agh_localize_masked)
 int sample_mask_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, const uint8_t* d_mask, double cell, int64_t S,
   unsigned long long seed, int32_t* d_out, int32_t* h_out, long long* h_count, hipStream_t st);
+// sample_labels.hip: the K sample lists of a labelled chain, S each, object after object (include/agh.h, agh_localize_labeled);
+// the M_j go to c->h_label_counts
+int sample_label_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, const uint8_t* d_labels, int K, double cell,
+  int64_t S, unsigned long long seed, int32_t* d_out, int32_t* h_out, hipStream_t st);
 int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
   unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st);
 // host mirror of the handle search's results (pinned memory of the context; all nullptr / 0: none)
@@ -1338,5 +1356,16 @@ int depth_batch_check(agh::Ctx* c, const char* who, const agh_depth_image* image
   std::vector<int64_t>* first, std::vector<int64_t>* left0);
 int depth_batch_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, const int32_t* n_images, int C, bool on_device,
   bool drop_staged, hipStream_t st);
-int chain_collect(agh_ctx* ctx, const char* who, bool label_captures, int C, const int* counts, int count_stride, int64_t S_tot,
+// (unit: what the chain's C lists are, "capture" or "object", for the error texts; nullptr: the one list of a single chain)
+int chain_collect(agh_ctx* ctx, const char* who, const char* unit, int C, const int* counts, int count_stride, int64_t S_tot,
   const int* bad, int (*requeue)(agh_ctx*, bool handles_only));
+// localize_batch.hip's tail as the labelled chain of localize.hip runs it, one list per OBJECT of the one capture.
+// labeled_tail_prepare: the batch state's table of K spans of S samples (soff = j * S, the one workspace), its handle-search slots
+// and its pinned sample mirror (*h_samples), everything queued on the context's stream.  batch_queue: search -> classification ->
+// kept hands per list -> handle search.  batch_collect: chain_collect over the lists, results[k] (nv[k]: list k's voxel count)
+// and the outputs' assembly, spans in list order.
+int labeled_tail_prepare(agh_ctx* ctx, int K, int64_t S, const agh_localize_params* lp, double x1, double x2, int32_t** h_samples);
+int batch_queue(agh_ctx* ctx, bool handles_only);
+int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t* nv, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);

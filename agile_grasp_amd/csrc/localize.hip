@@ -1,12 +1,14 @@
 // localize.hip -- the online chain of the reference's only online caller as one call (or two halves of one):
 // GraspLocalizer::localizeGrasps, grasp_localizer.cpp:95-103 = localizeHands -> predictAntipodalHands -> findHandles per capture.
 // agh_localize / agh_localize_device / agh_localize_begin / agh_localize_stage / agh_localize_end, agh_localize_depth* and the
-// masked forms of both (agh_localize_masked*, agh_localize_depth_masked*) of include/agh.h (the back-projection of depth
-// images: depth.hip; the sample list under a mask: sample_mask.hip); the stages
+// masked forms of both (agh_localize_masked*, agh_localize_depth_masked*) and the labelled ones (agh_localize_labeled*,
+// agh_localize_depth_labeled*) of include/agh.h (the back-projection of depth images: depth.hip; the sample list under a mask:
+// sample_mask.hip; one list per object of a label image: sample_labels.hip, with localize_batch.hip's tail); the stages
 // themselves (preprocessing, search, classification, handle search) are api.hip's, voxelize.hip's, hog_svm.hip's and handles.hip's.
 #include "agh_internal.h"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 
 using namespace agh;
@@ -111,13 +113,13 @@ int stage_captures(agh_ctx* ctx, const char* who, const float* const* xyz, const
 // The end of a chain over C captures, after its one synchronisation: attempt 0 is on the host (capture k's counts at
 // counts + k * count_stride: [0..3] the handle search's, [4..6] the compaction's).  The search once more for a capacity class
 // (on the cloud that is already there), the handle search once more for a walk the batched kernel declined -- requeue queues
-// either on the context's stream -- then the limits.  Errors are `who`'s, and capture k's if the chain labels its captures; bad:
-// a batch's per-capture flags of a sample index outside the capture (null: flags_to_status' text stands).
-int chain_collect(agh_ctx* ctx, const char* who, bool label_captures, int C, const int* counts, int count_stride, int64_t S_tot,
+// either on the context's stream -- then the limits.  Errors are `who`'s, and `unit` k's ("capture 3", "object 3") if the chain
+// has several lists; bad: a batch's per-capture flags of a sample index outside the capture (null: flags_to_status' text stands).
+int chain_collect(agh_ctx* ctx, const char* who, const char* unit, int C, const int* counts, int count_stride, int64_t S_tot,
   const int* bad, int (*requeue)(agh_ctx*, bool handles_only))
 {
   Ctx* c = &ctx->c;
-  auto of = [&](int k) { return std::string(who) + (label_captures ? ": capture " + std::to_string(k) : std::string()) + ": "; };
+  auto of = [&](int k) { return std::string(who) + (unit ? ": " + std::string(unit) + " " + std::to_string(k) : std::string()) + ": "; };
   bool handles_only = false;
   int rc;
   for (int attempt = 0;; attempt++)
@@ -254,7 +256,12 @@ struct MaskSource
   const agh_sample_mask* images;  // depth form: one per image
   bool on_device;
   const char* who;
+  int32_t n_objects = 0;          // agh_localize_labeled*: the bytes are labels 1 .. n_objects (0: a mask)
+  bool labeled = false;
 };
+static_assert(sizeof(agh_label_image) == sizeof(agh_sample_mask) && offsetof(agh_label_image, data) == offsetof(agh_sample_mask, data) &&
+                offsetof(agh_label_image, row_stride_bytes) == offsetof(agh_sample_mask, row_stride_bytes),
+  "a label image is read as a sample mask whose bytes are labels");
 
 static int mask_check(Ctx* c, const MaskSource* mask, const DepthSource* depth, const agh_localize_params* lp)
 {
@@ -262,6 +269,10 @@ static int mask_check(Ctx* c, const MaskSource* mask, const DepthSource* depth, 
     c->err = std::string(mask->who) + ": " + what;
     return AGH_ERR_INVALID_ARGUMENT;
   };
+  if (mask->labeled && (mask->n_objects < 1 || mask->n_objects > kMaxClouds))
+    return bad("n_objects must be 1 .. 64");
+  if (mask->labeled && (int64_t) mask->n_objects * lp->n_samples > (1 << 24))
+    return bad("n_objects x n_samples exceeds 2^24");
   if (lp->sample_idx)
     return bad("a mask together with sample_idx (an explicit list needs no mask)");
   if (!depth)
@@ -375,6 +386,8 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
       return rc;
   AGH_HIPCHK(c, hipSetDevice(c->device));
   const int64_t S = lp->n_samples;
+  const int K = mask && mask->labeled ? mask->n_objects : 0;  // (a labelled chain: K lists of S samples)
+  const int64_t S_all = K ? K * S : S;
   hipStream_t st = c->stream;
   int rc;
   // ---- 1. raw cloud up (unless it is on the device already: agh_localize_device, which reads it in place with the caller's
@@ -428,6 +441,7 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     return chain_fail(c, rc);  // (the capture's copy may be in flight)
   L.masked = mask != nullptr;
   L.d_mask = d_mask;
+  L.n_objects = K;
   L.S = S;
   L.classify = lp->classify != 0;
   L.filters = lp->filters_boundaries != 0;
@@ -448,25 +462,32 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   c->cloud_async = false;  // (everything below is queued on the context's own stream, and the call ends with its synchronisation)
   // (every error return from here on is a chain_fail: the host may only know a BOUND of the cloud's size)
   // ---- 2. buffers for the bounds ----
-  if ((rc = ensure_call_buffers(c, std::max<int64_t>(S, 1))) != AGH_OK)  // (S = 0: the later stages still want their buffers)
+  if ((rc = ensure_call_buffers(c, std::max<int64_t>(S_all, 1))) != AGH_OK)  // (S = 0: the later stages still want their buffers)
     return chain_fail(c, rc);
-  if (S > c->idx_cap || !c->d_idx_own)
+  if (S_all > c->idx_cap || !c->d_idx_own)
   {
-    if ((rc = dev_alloc(c, &c->d_idx_own, (size_t) std::max<int64_t>(S, 1024))))
+    if ((rc = dev_alloc(c, &c->d_idx_own, (size_t) std::max<int64_t>(S_all, 1024))))
       return chain_fail(c, rc);
-    c->idx_cap = std::max<int64_t>(S, 1024);
+    c->idx_cap = std::max<int64_t>(S_all, 1024);
   }
   if ((rc = ensure_host_staging(c, S, 1024)) != AGH_OK)
     return chain_fail(c, rc);
   int32_t* h_idx = reinterpret_cast<int32_t*>(c->h_pin + kPinHeaderBytes);
-  if ((rc = ensure_handle_buffers(c, std::min<int64_t>(8 * S, 8192))) != AGH_OK)
+  int32_t* h_idx_labeled = nullptr;  // (a labelled chain: the batch tail's slots, table and pinned sample mirror)
+  if ((rc = K ? labeled_tail_prepare(ctx, K, S, lp, L.x1, L.x2, &h_idx_labeled) : ensure_handle_buffers(c, std::min<int64_t>(8 * S, 8192))) != AGH_OK)
     return chain_fail(c, rc);
   if (lp->classify)
   {
     AGH_HIPCHK_OR(c, ensure_keep_buffers(c, c->s_cap * 8), chain_fail(c, AGH_ERR_HIP));
   }
   // ---- 3. the sample list ----
-  if (mask)  // (for S = 0 too: the count of eligible voxels is what a caller sizes S with)
+  if (K)  // (for S = 0 too, as the mask's)
+  {
+    if ((rc = sample_label_stage(c, d_raw, dev_stride / 4, n, d_mask, K, lp->cell_size, S, (unsigned long long) lp->sample_seed,
+           c->d_idx_own, h_idx_labeled, st)) != AGH_OK)
+      return chain_fail(c, rc);
+  }
+  else if (mask)  // (for S = 0 too: the count of eligible voxels is what a caller sizes S with)
   {
     if ((rc = sample_mask_stage(c, d_raw, dev_stride / 4, n, d_mask, lp->cell_size, S, (unsigned long long) lp->sample_seed,
            c->d_idx_own, h_idx, reinterpret_cast<long long*>(c->h_pin) + kPinMaskCount, st)) != AGH_OK)
@@ -488,19 +509,22 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     }
   }
   // ---- 4. search -> classification -> kept hands -> handle search: queued; agh_localize_end waits ----
-  if ((rc = localize_queue(ctx, false)) != AGH_OK)
+  if ((rc = K ? batch_queue(ctx, false) : localize_queue(ctx, false)) != AGH_OK)
     return chain_fail(c, rc);
   L.active = true;
   return AGH_OK;
 }
 
+// (results: a labelled chain's, one record per object, where a chain of another kind has *result)
 static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result,
+  agh_localize_batch_result* results = nullptr)
 {
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
   L.active = false;
   c->mask_count = -1;
+  c->label_objects = 0;
   const int64_t S = L.S;
   const HandlePins pin = handle_pins(c);
   const int* h_counts = pin.counts;
@@ -532,10 +556,12 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
         lp.sample_idx = L.explicit_samples ? h_idx : nullptr;
         L.repeated = true;
         // (a mask is where the chain read it, as the capture is: in the context's buffer, or in the caller's device memory)
-        const MaskSource again{ L.d_mask, nullptr, true, "agh_localize_masked" };
+        const MaskSource again{ L.d_mask, nullptr, true, L.n_objects ? "agh_localize_labeled" : "agh_localize_masked", L.n_objects,
+          L.n_objects != 0 };
         rc = localize_begin_impl(ctx, L.d_raw, true, L.dev_stride, L.n_raw, &lp, nullptr, L.masked ? &again : nullptr);
         if (rc == AGH_OK)
-          rc = localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
+          rc = localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result,
+            results);
         c->loc.repeated = false;
         return rc;
       }
@@ -551,9 +577,20 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
     c->cloud_off_on_device = true;  // ({0, nv}: what the voxeliser wrote)
     c->n_clouds = 1;
   }
+  if (L.n_objects)
+  {
+    // the tail of the batch chain: one list per object, every object on the one cloud
+    const int K = L.n_objects;
+    c->label_objects = K;
+    for (int j = 0; j < K; j++)
+      c->label_counts[j] = (int64_t) c->h_label_counts[j];
+    const std::vector<int64_t> nv((size_t) K, L.nv);
+    return batch_collect(ctx, "agh_localize_labeled", "object", nv.data(), handles_out, handle_cap, inlier_idx_out, idx_cap,
+      hands_out, hands_cap, samples_out, results);
+  }
   if (L.masked)
     c->mask_count = (int64_t) reinterpret_cast<const long long*>(c->h_pin)[kPinMaskCount];
-  if ((rc = chain_collect(ctx, "agh_localize", false, 1, h_counts, 0, S, nullptr, localize_queue)) != AGH_OK)
+  if ((rc = chain_collect(ctx, "agh_localize", nullptr, 1, h_counts, 0, S, nullptr, localize_queue)) != AGH_OK)
     return rc;
   const int64_t n_hyp = h_counts[4], n_kept = h_counts[5];
   c->last_nout = std::min<int64_t>(n_hyp, c->s_cap * 8);
@@ -722,6 +759,82 @@ int agh_localize_depth_masked_begin(agh_ctx* ctx, const agh_depth_image* images,
   const DepthSource src{ images, n_images, false, "agh_localize_depth_masked_begin" };
   const MaskSource m{ nullptr, masks, false, src.who };
   return localize_begin_impl(ctx, nullptr, false, 12, 0, lp, &src, &m);
+}
+
+// ---- the labelled forms (include/agh.h): one capture, one list of samples per object of a label image ----
+
+static int labeled_call(agh_ctx* ctx, const float* xyz, bool on_device, int64_t stride_bytes, int64_t n, const uint8_t* labels,
+  const agh_label_image* label_images, const DepthSource* depth, const char* who, int32_t n_objects, const agh_localize_params* lp,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  if (results && n_objects >= 1 && n_objects <= kMaxClouds)
+    for (int j = 0; j < n_objects; j++)
+      results[j] = agh_localize_batch_result{ { 0, 0, 0, 0, 0 }, 0, 0, 0, 0 };
+  const MaskSource m{ labels, reinterpret_cast<const agh_sample_mask*>(label_images), on_device, who, n_objects, true };
+  int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
+  if (rc == AGH_OK)
+    rc = localize_begin_impl(ctx, xyz, depth ? false : on_device, stride_bytes, n, lp, depth, &m);
+  if (rc != AGH_OK)
+    return rc;
+  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, nullptr, results);
+}
+
+int agh_localize_labeled(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const uint8_t* labels, int32_t n_objects,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  return labeled_call(ctx, xyz, false, stride_bytes, n, labels, nullptr, nullptr, "agh_localize_labeled", n_objects, lp, handles_out,
+    handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+}
+
+int agh_localize_labeled_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const uint8_t* d_labels,
+  int32_t n_objects, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  return labeled_call(ctx, d_xyz, true, stride_bytes, n, d_labels, nullptr, nullptr, "agh_localize_labeled_device", n_objects, lp,
+    handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+}
+
+int agh_localize_depth_labeled(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels, int32_t n_images,
+  int32_t n_objects, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthSource src{ images, n_images, false, "agh_localize_depth_labeled" };
+  return labeled_call(ctx, nullptr, false, 12, 0, nullptr, labels, &src, src.who, n_objects, lp, handles_out, handle_cap,
+    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+}
+
+int agh_localize_depth_labeled_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels, int32_t n_images,
+  int32_t n_objects, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthSource src{ images, n_images, true, "agh_localize_depth_labeled_device" };
+  return labeled_call(ctx, nullptr, true, 12, 0, nullptr, labels, &src, src.who, n_objects, lp, handles_out, handle_cap,
+    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+}
+
+int agh_get_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_objects)
+{
+  if (!ctx || !n_eligible)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_label_counts"))
+    return AGH_ERR_STATE;
+  if (c->label_objects < 1)
+  {
+    c->err = "agh_get_label_counts: the last chain this context collected had no label image (or there was none)";
+    return AGH_ERR_STATE;
+  }
+  if (cap_objects < c->label_objects)
+  {
+    c->err = "agh_get_label_counts: cap_objects is below the call's n_objects";
+    return AGH_ERR_CAPACITY;
+  }
+  std::copy(c->label_counts, c->label_counts + c->label_objects, n_eligible);
+  return AGH_OK;
 }
 
 int agh_get_sample_mask_count(agh_ctx* ctx, int64_t* n_eligible)

@@ -199,6 +199,40 @@ int pinned_alloc(Ctx* c, T** p, size_t count)
   return AGH_OK;
 }
 
+// the context's batch state with its tables of kMaxClouds records, made by the first call that needs it
+int ensure_batch_state(Ctx* c)
+{
+  if (c->lbatch)
+    return AGH_OK;
+  c->lbatch = new LocalizeBatchState();
+  LocalizeBatchState* b = c->lbatch;
+  int rc;
+  if ((rc = dev_alloc(c, &b->d_tab, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_tab, (size_t) kMaxClouds)) ||
+      (rc = pinned_alloc(c, &b->h_counts, (size_t) kMaxClouds * kBatchCountsStride)) ||
+      (rc = pinned_alloc(c, &b->h_bad, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_desc, (size_t) kMaxClouds)) ||
+      (rc = dev_alloc(c, &b->d_count, (size_t) kMaxClouds)) || (rc = dev_alloc(c, &b->d_vcap, (size_t) kMaxClouds)) ||
+      (rc = pinned_alloc(c, &b->h_vcap, (size_t) kMaxClouds)) || (rc = dev_alloc(c, &b->d_vdesc, (size_t) kMaxClouds)))
+  {
+    localize_batch_release(c);
+    return rc;
+  }
+  return AGH_OK;
+}
+
+// the sample lists of the chain: S_tot entries, capture-local, on the device (explicit lists) and pinned
+int ensure_batch_samples(Ctx* c, LocalizeBatchState* b, int64_t S_tot)
+{
+  if (S_tot > b->s_cap || !b->h_samples)
+  {
+    const int64_t cap = std::max<int64_t>(S_tot, 1024);
+    int rc;
+    if ((rc = dev_alloc(c, &b->d_local, (size_t) cap)) || (rc = pinned_alloc(c, &b->h_samples, (size_t) cap)))
+      return rc;
+    b->s_cap = cap;
+  }
+  return AGH_OK;
+}
+
 // the handle search's slots: C lists of `slot` hands (device), and their pinned mirrors
 int ensure_batch_slots(Ctx* c, LocalizeBatchState* b, int C, int64_t slot)
 {
@@ -246,7 +280,10 @@ int ensure_vox_slots(Ctx* c, LocalizeBatchState* b, int C)
   return AGH_OK;
 }
 
-// search -> classification -> per-capture compaction -> handle search, queued (handles_only: the handle search once more)
+}  // namespace
+
+// search -> classification -> per-capture compaction -> handle search, queued (handles_only: the handle search once more); the
+// labelled chain of localize.hip queues its tail with this too, one list per object (agh_internal.h)
 int batch_queue(agh_ctx* ctx, bool handles_only)
 {
   Ctx* c = &ctx->c;
@@ -285,6 +322,8 @@ int batch_queue(agh_ctx* ctx, bool handles_only)
   return rc;
 }
 
+namespace
+{
 struct ActiveGuard
 {
   Ctx* c;
@@ -422,13 +461,8 @@ int batch_pass(agh_ctx* ctx)
       return chain_fail(c, rc);
     c->idx_cap = std::max<int64_t>(S_tot, 1024);
   }
-  if (S_tot > b->s_cap || !b->h_samples)
-  {
-    const int64_t cap = std::max<int64_t>(S_tot, 1024);
-    if ((rc = dev_alloc(c, &b->d_local, (size_t) cap)) || (rc = pinned_alloc(c, &b->h_samples, (size_t) cap)))
-      return chain_fail(c, rc);
-    b->s_cap = cap;
-  }
+  if ((rc = ensure_batch_samples(c, b, S_tot)) != AGH_OK)
+    return chain_fail(c, rc);
   if ((rc = ensure_batch_slots(c, b, C, B.slot)) != AGH_OK)
     return chain_fail(c, rc);
   if (B.classify)
@@ -558,20 +592,8 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   AGH_HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   int rc;
-  if (!c->lbatch)
-  {
-    c->lbatch = new LocalizeBatchState();
-    LocalizeBatchState* b = c->lbatch;
-    if ((rc = dev_alloc(c, &b->d_tab, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_tab, (size_t) kMaxClouds)) ||
-        (rc = pinned_alloc(c, &b->h_counts, (size_t) kMaxClouds * kBatchCountsStride)) ||
-        (rc = pinned_alloc(c, &b->h_bad, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_desc, (size_t) kMaxClouds)) ||
-        (rc = dev_alloc(c, &b->d_count, (size_t) kMaxClouds)) || (rc = dev_alloc(c, &b->d_vcap, (size_t) kMaxClouds)) ||
-        (rc = pinned_alloc(c, &b->h_vcap, (size_t) kMaxClouds)) || (rc = dev_alloc(c, &b->d_vdesc, (size_t) kMaxClouds)))
-    {
-      localize_batch_release(c);
-      return rc;
-    }
-  }
+  if ((rc = ensure_batch_state(c)) != AGH_OK)
+    return rc;
   LocalizeBatchState* b = c->lbatch;
   BatchCall& B = b->call;
   B = BatchCall();
@@ -676,6 +698,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   c->loc.active = false;
   c->loc.batch = false;
   c->mask_count = -1;  // (agh_get_sample_mask_count: the last chain collected had no mask)
+  c->label_objects = 0;  // (... and no label image)
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)
@@ -726,45 +749,8 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   c->cloud_off = voff;
   c->cloud_off_on_device = true;
   c->n_clouds = C;
-  const int* hc = b->h_counts;
-  if ((rc = chain_collect(ctx, "agh_localize_batch", true, C, hc, kBatchCountsStride, S_tot, b->h_bad, batch_queue)) != AGH_OK)
-    return rc;
-  int64_t n_hyp_tot = 0, tot_handles = 0, tot_idx = 0, tot_hands = 0;
-  for (int k = 0; k < C; k++)
-  {
-    const int* h = hc + k * kBatchCountsStride;
-    if (results)
-      results[k] = agh_localize_batch_result{ { nv[k], h[4], h[5], h[0], h[1] }, tot_handles, tot_idx, tot_hands, B.soff[k] };
-    n_hyp_tot += h[4];
-    tot_handles += h[0];
-    tot_idx += h[1];
-    tot_hands += h[5];
-  }
-  c->last_nout = std::min<int64_t>(n_hyp_tot, c->s_cap * 8);
-  if (samples_out && S_tot > 0)
-    std::memcpy(samples_out, b->h_samples, sizeof(int32_t) * (size_t) S_tot);
-  if (tot_handles > handle_cap || tot_idx > idx_cap || (hands_out && tot_hands > hands_cap))
-  {
-    c->err = "agh_localize_batch: output buffers too small (the counts are in results)";
-    return AGH_ERR_CAPACITY;
-  }
-  int64_t oh = 0, oi = 0, ok = 0;
-  for (int k = 0; k < C; k++)
-  {
-    const int* h = hc + k * kBatchCountsStride;
-    const size_t base = (size_t) k * (size_t) b->h_slot;
-    if (h[0] > 0)
-    {
-      std::memcpy(handles_out + oh, b->h_handles + base, sizeof(agh_handle) * (size_t) h[0]);
-      std::memcpy(inlier_idx_out + oi, b->h_idx + base, sizeof(int32_t) * (size_t) h[1]);
-    }
-    if (hands_out && h[5] > 0)
-      std::memcpy(hands_out + ok, b->h_hands + base, sizeof(agh_hypothesis) * (size_t) h[5]);
-    oh += h[0];
-    oi += h[1];
-    ok += h[5];
-  }
-  return AGH_OK;
+  return batch_collect(ctx, "agh_localize_batch", "capture", nv.data(), handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results);
 }
 
 void zero_results(agh_localize_batch_result* results, int C)
@@ -800,6 +786,101 @@ int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int6
   return batch_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
 }
 }  // namespace
+
+// The end of a chain over the batch state's C lists, behind its synchronisation and with its cloud bound: chain_collect's repeats
+// and limits, results[k], and the outputs' assembly from the pinned slots, spans in list order (agh_internal.h).
+int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t* nv, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  Ctx* c = &ctx->c;
+  LocalizeBatchState* b = c->lbatch;
+  const BatchCall& B = b->call;
+  const int C = B.C;
+  const int64_t S_tot = B.S_tot;
+  int rc;
+  const int* hc = b->h_counts;
+  if ((rc = chain_collect(ctx, who, unit, C, hc, kBatchCountsStride, S_tot, b->h_bad, batch_queue)) != AGH_OK)
+    return rc;
+  int64_t n_hyp_tot = 0, tot_handles = 0, tot_idx = 0, tot_hands = 0;
+  for (int k = 0; k < C; k++)
+  {
+    const int* h = hc + k * kBatchCountsStride;
+    if (results)
+      results[k] = agh_localize_batch_result{ { nv[k], h[4], h[5], h[0], h[1] }, tot_handles, tot_idx, tot_hands, B.soff[k] };
+    n_hyp_tot += h[4];
+    tot_handles += h[0];
+    tot_idx += h[1];
+    tot_hands += h[5];
+  }
+  c->last_nout = std::min<int64_t>(n_hyp_tot, c->s_cap * 8);
+  if (samples_out && S_tot > 0)
+    std::memcpy(samples_out, b->h_samples, sizeof(int32_t) * (size_t) S_tot);
+  if (tot_handles > handle_cap || tot_idx > idx_cap || (hands_out && tot_hands > hands_cap))
+  {
+    c->err = std::string(who) + ": output buffers too small (the counts are in results)";
+    return AGH_ERR_CAPACITY;
+  }
+  int64_t oh = 0, oi = 0, ok = 0;
+  for (int k = 0; k < C; k++)
+  {
+    const int* h = hc + k * kBatchCountsStride;
+    const size_t base = (size_t) k * (size_t) b->h_slot;
+    if (h[0] > 0)
+    {
+      std::memcpy(handles_out + oh, b->h_handles + base, sizeof(agh_handle) * (size_t) h[0]);
+      std::memcpy(inlier_idx_out + oi, b->h_idx + base, sizeof(int32_t) * (size_t) h[1]);
+    }
+    if (hands_out && h[5] > 0)
+      std::memcpy(hands_out + ok, b->h_hands + base, sizeof(agh_hypothesis) * (size_t) h[5]);
+    oh += h[0];
+    oi += h[1];
+    ok += h[5];
+  }
+  return AGH_OK;
+}
+
+
+// The batch state for the tail of a labelled chain (localize.hip): K lists, list j the samples j * S .. j * S + S - 1 of the one
+// capture, every list with the capture's workspace (agh_internal.h).
+int labeled_tail_prepare(agh_ctx* ctx, int K, int64_t S, const agh_localize_params* lp, double x1, double x2, int32_t** h_samples)
+{
+  Ctx* c = &ctx->c;
+  int rc;
+  if ((rc = ensure_batch_state(c)) != AGH_OK)
+    return rc;
+  LocalizeBatchState* b = c->lbatch;
+  BatchCall& B = b->call;
+  B = BatchCall();
+  B.C = K;
+  B.x1 = x1;
+  B.x2 = x2;
+  B.lp.assign(1, *lp);
+  B.lp[0].sample_idx = nullptr;
+  B.soff.resize(K + 1);
+  for (int j = 0; j <= K; j++)
+    B.soff[j] = (int64_t) j * S;
+  B.S_tot = (int64_t) K * S;
+  B.classify = lp->classify != 0;
+  B.filters = lp->filters_boundaries != 0;
+  B.slot = std::min<int64_t>(8 * S, 8192);
+  if ((rc = ensure_batch_samples(c, b, B.S_tot)) != AGH_OK || (rc = ensure_batch_slots(c, b, K, B.slot)) != AGH_OK)
+    return rc;
+  for (int j = 0; j < K; j++)
+  {
+    BatchCapture& t = b->h_tab[j];
+    t.soff = B.soff[j];
+    t.S = (int32_t) S;
+    t.drawn = 1;
+    t.seed = lp->sample_seed;
+    for (int q = 0; q < 6; q++)
+      t.ws[q] = lp->workspace[q];
+    b->h_bad[j] = 0;
+  }
+  AGH_HIPCHK(c, hipMemcpyAsync(b->d_tab, b->h_tab, sizeof(BatchCapture) * (size_t) K, hipMemcpyHostToDevice, c->stream));
+  *h_samples = b->h_samples;
+  return AGH_OK;
+}
 
 extern "C" {
 

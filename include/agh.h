@@ -282,8 +282,9 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
  * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
- * agh_localize_depth_masked* and agh_localize_depth_masked_begin among them), agh_deproject, agh_deproject_batch,
- * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count and every getter of device results (frames, normals,
+ * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled* and agh_localize_depth_labeled* among
+ * them), agh_deproject, agh_deproject_batch,
+ * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -394,8 +395,8 @@ int agh_localize_depth_stage(agh_ctx* ctx, const agh_depth_image* images, int32_
  * repeats inside the call (the lattice that outgrew the kept bitmap, the capacity classes) need the caller's mask in no other
  * way than they need the caller's capture.  One more bitmap of the voxel bitmap's size is held by a context that made a masked
  * call; the chain's one synchronisation stays one.
- * Not built: a _stage call for masks; masks for agh_localize_batch* and agh_localize_depth_batch*; label images (several
- * objects, one sample list each); sharded variants. */
+ * Not built: a _stage call for masks; masks for agh_localize_batch* and agh_localize_depth_batch*; label images in the batch
+ * chains (for ONE capture, several objects with one sample list each: agh_localize_labeled* below); sharded variants. */
 typedef struct agh_sample_mask
 {
   const uint8_t* data;       /* one byte per pixel, non-zero = eligible; NULL: no pixel of this image is */
@@ -420,6 +421,71 @@ int agh_localize_depth_masked_begin(agh_ctx* ctx, const agh_depth_image* images,
 /* The eligible voxels (M) of the last masked chain this context collected.  AGH_ERR_STATE if the last chain collected had no
  * mask, if there was none, or while a chain is in flight. */
 int agh_get_sample_mask_count(agh_ctx* ctx, int64_t* n_eligible);
+
+/* The same chains with one sample list PER OBJECT of a LABEL IMAGE: "grasps on each of these objects" (bin picking).  An instance
+ * segmenter hands over one label image with several objects in it; K calls of agh_localize_masked would upload, voxelise and
+ * grid the same capture K times and synchronise K times.  Here the capture is preprocessed ONCE, the search runs ONCE over the
+ * n_objects x S samples, the kept hands are compacted into one list per object and the handle search runs ONCE for all lists,
+ * side by side (the tail of agh_localize_batch, with "object" in the place of "capture"); one synchronisation.
+ * labels: one byte per raw point (per pixel); 0 = no object, j + 1 = object j, 0 <= j < n_objects; a byte above n_objects
+ * belongs to no object (it is not an error: a device label array cannot be validated without a round trip).
+ *  1. 1 <= n_objects <= 64 (the lists the batch tail holds).
+ *  2. lp->n_samples = S is the number of samples of EACH object and lp->sample_seed is every object's seed;
+ *     n_objects x S <= 2^24.  A violation of 1 or 2 is AGH_ERR_INVALID_ARGUMENT, nothing launched; so is lp->sample_idx != NULL,
+ *     as with a mask.
+ *  3. Eligibility is the mask rule, per object: a voxel is eligible for object j iff at least one raw point with label j + 1
+ *     was kept by the preprocessing and falls into it, in its own camera block.  One voxel may be eligible for several objects.
+ *     E_j is the ascending list of object j's eligible voxel indices, M_j = |E_j|.
+ *  4. Sample k of object j is E_j[stratum draw of agh_localize with M_j in the place of N]; with M_j < S the list is E_j followed
+ *     by INT32_MIN slots.  M_j = 0 is no error: that object has zero hypotheses, hands and handles.
+ *  5. The search runs once over the n_objects x S samples in object order, on the whole cloud; classification, the boundary
+ *     filter (filters_boundaries) and the handle search are those of agh_localize.
+ *  6. Outputs are laid out as agh_localize_batch's: every output is the concatenation of the objects' spans in object order;
+ *     results[j] (n_objects records) holds object j's counts and the starts of its spans; samples_out holds n_objects x S voxel
+ *     indices; agh_hypothesis::sample is the position in object j's own list; object j's inlier indices point into its own span
+ *     of hands_out; results[j].r.n_voxels is the cloud's voxel count, for every j.  The 8192-hand limit applies per object (the
+ *     error text names the object).  Buffers that are too small: AGH_ERR_CAPACITY with every results[j] filled.
+ *  7. Equality, with AGH_NORMALS_DETERMINISTIC: object j's span of every output and results[j].r equal, bit for bit (epoch
+ *     aside), what agh_localize_masked returns for the same capture and lp with mask[i] = (labels[i] == j + 1), and M_j equals
+ *     that call's agh_get_sample_mask_count; with n_objects = 1 and labels 0 / 1 the call equals agh_localize_masked.
+ *     With AGH_NORMALS_RAND50 the rand() stream runs through the call's whole sample list, hence through the objects in order:
+ *     only object 0 equals its masked twin.
+ *  8. The depth forms: labels[k] belongs to images[k] as a mask does (same width and height, row v at data + v *
+ *     row_stride_bytes); data == NULL: no pixel of that image belongs to an object; all NULL is AGH_ERR_INVALID_ARGUMENT.  The
+ *     chain runs with size_left = W0 x H0 and dense = 1, and the call equals agh_localize_labeled on the array agh_deproject
+ *     writes, with the label rows packed end to end and a NULL image contributing zeros.
+ *  9. Every validation, status and error text not named here is the masked twin's: AGH_ERR_STATE while a chain or a batch of any
+ *     kind is in flight; a pending staged set is dropped, as a masked begin drops it; the repeats inside the call (a lattice that
+ *     outgrew the kept bitmap, the capacity classes, the declined handle walk) work as in the masked call and read the labels
+ *     where the first pass left them.  agh_localize_labeled_device / agh_localize_depth_labeled_device: the points (images') and
+ *     labels' data are device pointers, read in place, the labels at any byte alignment.
+ * 10. One synchronisation in the steady state, as agh_localize; the label stage adds none.  After the call the context holds
+ *     the voxelised cloud as a single bound cloud.  A context that made a labelled call holds one 32-bit word per word of the
+ *     voxel bitmap and one 64-bit object set per raw point -- nothing of n_objects x the lattice.
+ * agh_get_label_counts: the M_j of the last labelled chain this context collected (n_objects entries).  AGH_ERR_STATE if the
+ * last chain collected was not labelled (agh_get_sample_mask_count returns AGH_ERR_STATE after a labelled call), if there was
+ * none, or while a chain is in flight; AGH_ERR_CAPACITY if cap_objects is below n_objects.
+ * Not built: _begin / _end and _stage forms; labels in the batch chains; more than 64 objects; labels wider than a byte;
+ * sharded variants. */
+typedef struct agh_label_image   /* depth form: as agh_sample_mask, the bytes being labels */
+{
+  const uint8_t* data;           /* NULL: no pixel of this image belongs to an object */
+  int64_t row_stride_bytes;      /* >= the image's width */
+} agh_label_image;
+struct agh_localize_batch_result;  /* (defined below, with agh_localize_batch) */
+int agh_localize_labeled(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const uint8_t* labels, int32_t n_objects,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_localize_labeled_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const uint8_t* d_labels,
+  int32_t n_objects, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_localize_depth_labeled(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels, int32_t n_images,
+  int32_t n_objects, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_localize_depth_labeled_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels, int32_t n_images,
+  int32_t n_objects, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_get_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_objects);
 
 /* The chain of agh_localize over a BATCH of captures in one call, with ONE synchronisation (offline evaluation over a
  * directory of PCD pairs, a cell with several sensors or arms): 1 <= n_captures <= 64, fewer than 2^30 raw points in all.
@@ -481,8 +547,8 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * agh_localize_batch(...) is begin + end; agh_localize_batch_begin_device reads device captures in place (nothing to stage).
  * The context has ONE chain and ONE staged set, of either kind.  A begin of either kind while a chain of either kind is in
  * flight (agh_localize_depth_batch* and agh_localize_depth_batch_begin* included, agh_localize_masked*,
- * agh_localize_masked_begin, agh_localize_depth_masked* and agh_localize_depth_masked_begin too; agh_deproject_batch and
- * agh_get_sample_mask_count are refused as well),
+ * agh_localize_masked_begin, agh_localize_depth_masked* and agh_localize_depth_masked_begin too, and agh_localize_labeled*
+ * and agh_localize_depth_labeled*; agh_deproject_batch, agh_get_sample_mask_count and agh_get_label_counts are refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of

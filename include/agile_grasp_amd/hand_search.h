@@ -443,6 +443,88 @@ public:
     return m;
   }
 
+  /** Additional: one capture, one sample list PER OBJECT of a label array (agh_localize_labeled): `labels` holds one byte per
+   *  point of cloud_in, 0 = no object, j + 1 = object j of n_objects (1 .. 64); num_samples samples are drawn for EACH object
+   *  among the voxels that hold one of its points, the search runs once over all of them on the whole cloud, and the handle
+   *  search once per object, side by side.  Outputs per object, as localizeBatch's per capture; labelCounts() then gives the
+   *  eligible voxels per object.  One blocking call.  @return false (after printing) on error */
+  bool localizeLabeled(const PointCloud::Ptr& cloud_in, int size_left, const std::vector<std::uint8_t>& labels, int n_objects,
+    const VectorXd& workspace, double cell_size, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<agh_hypothesis> >& hands_out, std::vector<std::vector<agh_handle> >& handles_out,
+    std::vector<std::vector<std::int32_t> >& inliers_out, bool filters_boundaries = false)
+  {
+    labeledClear(n_objects, hands_out, handles_out, inliers_out);
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    if (!cloud_in || labels.size() != cloud_in->points.size())
+    {
+      std::cout << " Error: localizeLabeled needs one label byte per point of the cloud\n";
+      return false;
+    }
+    const agh_localize_params lp = chainParams(size_left, cloud_is_dense(*cloud_in), workspace, cell_size, std::vector<std::int32_t>(),
+      sampleSeed(), min_inliers, min_length, filters_boundaries);
+    const RawPoints in = rawPoints(*cloud_in);
+    LabeledOutputs o(n_objects, lp.n_samples);
+    if (agh_localize_labeled(ctx_, in.xyz, in.stride, in.n, labels.data(), (std::int32_t) n_objects, &lp, o.handles.data(), o.cap,
+          o.inl.data(), o.cap, o.hands.data(), o.cap, o.samples.data(), o.res.data()) != AGH_OK)
+    {
+      fail("agh_localize_labeled");
+      return false;
+    }
+    labeledCollect(o, hands_out, handles_out, inliers_out);
+    return true;
+  }
+
+  /** ... and straight from depth images (agh_localize_depth_labeled): labels[k] belongs to images[k]; a label image without data
+   *  puts no pixel of its image into an object. */
+  bool localizeDepthLabeled(const std::vector<DepthImage>& images, const std::vector<LabelImage>& labels, int n_objects,
+    const VectorXd& workspace, double cell_size, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<agh_hypothesis> >& hands_out, std::vector<std::vector<agh_handle> >& handles_out,
+    std::vector<std::vector<std::int32_t> >& inliers_out, bool filters_boundaries = false)
+  {
+    labeledClear(n_objects, hands_out, handles_out, inliers_out);
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    if (labels.size() != images.size())
+    {
+      std::cout << " Error: localizeDepthLabeled needs one label image per depth image\n";
+      return false;
+    }
+    const agh_localize_params lp = chainParams(0, true, workspace, cell_size, std::vector<std::int32_t>(), sampleSeed(), min_inliers,
+      min_length, filters_boundaries);
+    const std::vector<agh_depth_image> recs = depthRecords(images);
+    std::vector<agh_label_image> lrecs(labels.size());
+    for (std::size_t k = 0; k < labels.size(); k++)
+    {
+      lrecs[k].data = labels[k].data;
+      lrecs[k].row_stride_bytes = labels[k].row_stride_bytes;
+    }
+    LabeledOutputs o(n_objects, lp.n_samples);
+    if (agh_localize_depth_labeled(ctx_, recs.empty() ? nullptr : recs.data(), lrecs.empty() ? nullptr : lrecs.data(),
+          (std::int32_t) recs.size(), (std::int32_t) n_objects, &lp, o.handles.data(), o.cap, o.inl.data(), o.cap, o.hands.data(),
+          o.cap, o.samples.data(), o.res.data()) != AGH_OK)
+    {
+      fail("agh_localize_depth_labeled");
+      return false;
+    }
+    labeledCollect(o, hands_out, handles_out, inliers_out);
+    return true;
+  }
+
+  /** agh_get_label_counts: the eligible voxels of every object of the last labelled call; empty if the last chain collected
+   *  was not labelled */
+  std::vector<std::int64_t> labelCounts()
+  {
+    std::vector<std::int64_t> m(64, -1);
+    if (!ctx_ || agh_get_label_counts(ctx_, m.data(), 64) != AGH_OK)
+      return std::vector<std::int64_t>();
+    std::size_t k = 0;
+    while (k < m.size() && m[k] >= 0)
+      k++;
+    m.resize(k);
+    return m;
+  }
+
   /** agh_localize_depth_stage: the NEXT capture's images up, beside the chain in flight */
   bool localizeDepthStage(const std::vector<DepthImage>& next)
   {
@@ -832,6 +914,44 @@ private:
   {
     loc_cap_ = handsRoom(n_samples) + 1;
     last_samples_.assign((std::size_t) n_samples, 0);
+  }
+
+  // the output buffers of a labelled call (the library refuses an n_objects outside 1 .. 64: room for one then), and their
+  // spans per object
+  struct LabeledOutputs
+  {
+    std::size_t K;
+    std::int64_t n_samples, cap;
+    std::vector<agh_hypothesis> hands;
+    std::vector<agh_handle> handles;
+    std::vector<std::int32_t> inl, samples;
+    std::vector<agh_localize_batch_result> res;
+    LabeledOutputs(int n_objects, std::int64_t S)
+      : K(n_objects >= 1 && n_objects <= 64 ? (std::size_t) n_objects : 1), n_samples(S), cap((std::int64_t) K * handsRoom(S) + 1),
+        hands((std::size_t) cap), handles((std::size_t) cap), inl((std::size_t) cap), samples(K * (std::size_t) S + 1), res(K + 1)
+    {
+    }
+  };
+  static void labeledClear(int n_objects, std::vector<std::vector<agh_hypothesis> >& hands_out,
+    std::vector<std::vector<agh_handle> >& handles_out, std::vector<std::vector<std::int32_t> >& inliers_out)
+  {
+    const std::size_t K = n_objects >= 1 && n_objects <= 64 ? (std::size_t) n_objects : 0;
+    hands_out.assign(K, std::vector<agh_hypothesis>());
+    handles_out.assign(K, std::vector<agh_handle>());
+    inliers_out.assign(K, std::vector<std::int32_t>());
+  }
+  void labeledCollect(const LabeledOutputs& o, std::vector<std::vector<agh_hypothesis> >& hands_out,
+    std::vector<std::vector<agh_handle> >& handles_out, std::vector<std::vector<std::int32_t> >& inliers_out)
+  {
+    for (std::size_t k = 0; k < o.K; k++)
+    {
+      const agh_localize_batch_result& r = o.res[k];
+      hands_out[k].assign(o.hands.begin() + r.first_hand, o.hands.begin() + r.first_hand + r.r.n_hands);
+      handles_out[k].assign(o.handles.begin() + r.first_handle, o.handles.begin() + r.first_handle + r.r.n_handles);
+      inliers_out[k].assign(o.inl.begin() + r.first_inlier_idx, o.inl.begin() + r.first_inlier_idx + r.r.n_inlier_idx);
+    }
+    searched_n_ = o.res[0].r.n_voxels;  // (one cloud, whose voxel count every object reports)
+    last_samples_.assign(o.samples.begin(), o.samples.begin() + (std::ptrdiff_t) (o.K * (std::size_t) o.n_samples));
   }
 
   // a host cloud as the library takes it: no pointer for an empty one

@@ -412,6 +412,72 @@ public:
     return true;
   }
 
+  /** Additional: localizeHandles for EVERY OBJECT of a label array in one call ("grasps on each of these objects", bin picking):
+   *  `labels` holds one byte per point of cloud_in, as an instance segmenter labels the capture (0 = no object, j + 1 = object j
+   *  of n_objects, 1 .. 64); num_samples samples are drawn per object among the voxels that hold one of its points.  The capture
+   *  is preprocessed and searched once, on the whole cloud; the handle search runs per object.  Returns the handles per object
+   *  (and the kept hands per object): object j's are those of localizeHandlesMasked with the mask labels == j + 1.  An error
+   *  returns n_objects empty lists. */
+  std::vector<std::vector<Handle> > localizeHandlesLabeled(const PointCloud::Ptr& cloud_in, int size_left,
+    const std::vector<std::uint8_t>& labels, int n_objects, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object = nullptr)
+  {
+    const std::size_t K = n_objects >= 1 && n_objects <= 64 ? (std::size_t) n_objects : 0;
+    std::vector<std::vector<Handle> > out = noHandles(K, antipodal_hands_per_object);
+    if (chainPending("localizeHandlesLabeled"))
+      return out;
+    if (size_left == 0 || !cloud_in || cloud_in->size() == 0)
+    {
+      std::cout << "Input cloud is empty!\n";
+      std::cout << size_left << std::endl;
+      return out;
+    }
+    if (!detail::svmFileExists(svm_filename))
+      return out;
+    ensureSearch();
+    std::vector<std::vector<agh_hypothesis> > hands;
+    std::vector<std::vector<agh_handle> > handles;
+    std::vector<std::vector<std::int32_t> > idx;
+    if (!search_->localizeLabeled(cloud_in, size_left, labels, n_objects, workspace_, 0.003, svm_filename, min_inliers, min_length,
+          hands, handles, idx, filters_boundaries_))
+      return out;
+    return labeledHandles(cloud_in, hands, handles, idx, antipodal_hands_per_object);
+  }
+
+  /** ... and straight from depth images with one label image per depth image (agh_localize_depth_labeled); a label image
+   *  without data puts no pixel of its image into an object. */
+  std::vector<std::vector<Handle> > localizeHandlesDepthLabeled(const std::vector<DepthImage>& images,
+    const std::vector<LabelImage>& labels, int n_objects, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object = nullptr)
+  {
+    const std::size_t K = n_objects >= 1 && n_objects <= 64 ? (std::size_t) n_objects : 0;
+    std::vector<std::vector<Handle> > out = noHandles(K, antipodal_hands_per_object);
+    if (chainPending("localizeHandlesDepthLabeled"))
+      return out;
+    if (images.empty())
+    {
+      std::cout << "Input cloud is empty!\n";
+      return out;
+    }
+    if (!detail::svmFileExists(svm_filename))
+      return out;
+    ensureSearch();
+    std::vector<std::vector<agh_hypothesis> > hands;
+    std::vector<std::vector<agh_handle> > handles;
+    std::vector<std::vector<std::int32_t> > idx;
+    if (!search_->localizeDepthLabeled(images, labels, n_objects, workspace_, 0.003, svm_filename, min_inliers, min_length, hands,
+          handles, idx, filters_boundaries_))
+      return out;
+    return labeledHandles(PointCloud::Ptr(), hands, handles, idx, antipodal_hands_per_object);
+  }
+
+  /** The eligible voxels of every object of the last labelled call (agh_get_label_counts); empty if the last chain collected was
+   *  not labelled, if there was none, or while a chain is pending. */
+  std::vector<std::int64_t> getLabelCounts()
+  {
+    return search_ ? search_->labelCounts() : std::vector<std::int64_t>();
+  }
+
   /** The seed of the samples a chain draws on the device (HandSearch::setSampleSeed; default: the clock, like pcl::RandomSample),
    *  and the list the last collected chain searched (HandSearch::getLastSampleIndices): together they make a masked call
    *  repeatable with explicit indices. */
@@ -669,6 +735,17 @@ private:
       return false;
     std::cout << " Error: " << who << " while a chain is pending (" << end << " first)\n";
     return true;
+  }
+  // the per-object results of a labelled call as the reference's objects (the caller's cloud is filtered once, by the first)
+  std::vector<std::vector<Handle> > labeledHandles(const PointCloud::Ptr& cloud_in, const std::vector<std::vector<agh_hypothesis> >& hands,
+    const std::vector<std::vector<agh_handle> >& handles, const std::vector<std::vector<std::int32_t> >& idx,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object)
+  {
+    std::vector<std::vector<Handle> > out = noHandles(hands.size(), antipodal_hands_per_object);
+    for (std::size_t j = 0; j < hands.size(); j++)
+      out[j] = toHandles(j == 0 ? cloud_in : PointCloud::Ptr(), hands[j], handles[j], idx[j],
+        antipodal_hands_per_object ? &(*antipodal_hands_per_object)[j] : nullptr);
+    return out;
   }
   // what a batch call returns when it fails: an empty list of handles, and of kept hands, per capture
   static std::vector<std::vector<Handle> > noHandles(std::size_t C, std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_cloud)

@@ -167,6 +167,16 @@ struct SampleMask
   SampleMask() : data(nullptr), row_stride_bytes(0) {}
   SampleMask(const std::uint8_t* d, std::int64_t stride) : data(d), row_stride_bytes(stride) {}
 };
+// A per-pixel label image for one DepthImage (an instance segmenter's output), for the chains that draw one sample list per
+// object (agh_localize_depth_labeled, include/agh.h): one byte per pixel, 0 = no object, j + 1 = object j; the bytes stay the
+// caller's.  data == nullptr: no pixel of that image belongs to an object.
+struct LabelImage
+{
+  const std::uint8_t* data;        // row-major; row v at data + v * row_stride_bytes
+  std::int64_t row_stride_bytes;   // >= the image's width
+  LabelImage() : data(nullptr), row_stride_bytes(0) {}
+  LabelImage(const std::uint8_t* d, std::int64_t stride) : data(d), row_stride_bytes(stride) {}
+};
 }  // namespace agile_grasp_amd
 
 static_assert(sizeof(float) == 4, "float32 expected");
