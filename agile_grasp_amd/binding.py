@@ -97,6 +97,9 @@ EXPORTS = [
     "agh_localize_depth_masked_device", "agh_localize_depth_masked_begin", "agh_get_sample_mask_count",
     "agh_localize_labeled", "agh_localize_labeled_device", "agh_localize_depth_labeled", "agh_localize_depth_labeled_device",
     "agh_get_label_counts",
+    "agh_localize_batch_masked", "agh_localize_batch_masked_device", "agh_localize_batch_masked_begin",
+    "agh_localize_batch_masked_begin_device", "agh_localize_depth_batch_masked", "agh_localize_depth_batch_masked_device",
+    "agh_localize_depth_batch_masked_begin", "agh_localize_depth_batch_masked_begin_device", "agh_get_batch_mask_counts",
 ]
 
 
@@ -862,6 +865,89 @@ class Context:
         fn = self.lib.agh_localize_batch_begin_device if a["on_device"] else self.lib.agh_localize_batch_begin
         self._check(fn(self._h, a["ptrs"], a["strides"], a["ns"], a["lps"], C.c_int32(a["Ck"])))
         self._batch_pending = a
+
+    @staticmethod
+    def _batch_mask_pointers(a, masks):
+        """The masks array of a masked points batch: one uint8 per raw point per capture (torch CUDA tensors, 1-D with unit
+        stride, for device captures).  `masks` None passes NULL and a None entry a NULL mask, for the library to refuse."""
+        if masks is None:
+            return None, []
+        Ck = a["Ck"]
+        assert len(masks) == Ck
+        ptrs, keep = (C.c_void_p * max(Ck, 1))(), []
+        for k, m in enumerate(masks):
+            n_pts = int(a["ns"][k])
+            if m is None:
+                ptrs[k] = None
+            elif a["on_device"]:
+                assert m.is_cuda and m.dim() == 1 and m.element_size() == 1 and m.shape[0] == n_pts
+                assert n_pts <= 1 or m.stride(0) == 1
+                ptrs[k] = m.data_ptr()
+            else:
+                m = np.ascontiguousarray(m).view(np.uint8) if np.asarray(m).dtype == np.bool_ else np.ascontiguousarray(m, np.uint8)
+                assert m.shape == (n_pts,)
+                ptrs[k] = m.ctypes.data
+            keep.append(m)
+        return ptrs, keep
+
+    def _batch_masked_args(self, captures, sizes_left, workspaces, masks, kw):
+        a = self._batch_args(captures, sizes_left, workspaces, kw.pop("samples", None), kw.pop("n_samples", 0),
+                             kw.pop("sample_seeds", None), kw.pop("classify", True), kw.pop("min_inliers", 3),
+                             kw.pop("min_length", 0.005), kw.pop("filters_boundaries", 0), kw.pop("cell_size", 0.003),
+                             kw.pop("dense", False))
+        assert not kw, f"unknown arguments {sorted(kw)}"
+        a["mptrs"], a["mkeep"] = self._batch_mask_pointers(a, masks)
+        return a
+
+    def localize_batch_masked(self, captures, sizes_left, workspaces, masks, caps=None, **kw):
+        """agh_localize_batch_masked (torch CUDA tensors: agh_localize_batch_masked_device): localize_batch() with capture k's
+        n_samples drawn among the voxels that hold a kept raw point with a non-zero byte in masks[k] (one uint8 per raw point).
+        The other arguments (by keyword) as for localize_batch; `samples` goes through for the library to refuse.
+        batch_mask_counts() then gives the eligible voxels per capture."""
+        a = self._batch_masked_args(captures, sizes_left, workspaces, masks, kw)
+        fn = self.lib.agh_localize_batch_masked_device if a["on_device"] else self.lib.agh_localize_batch_masked
+        return self._batch_collect(a, caps, lambda *out: fn(self._h, a["ptrs"], a["strides"], a["ns"], a["mptrs"], a["lps"],
+                                                            C.c_int32(a["Ck"]), *out))
+
+    def localize_batch_masked_begin(self, captures, sizes_left, workspaces, masks, **kw):
+        """agh_localize_batch_masked_begin (torch CUDA tensors: _begin_device): the masked batch's chain queued, nothing waited
+        for; collected by localize_batch_end().  Captures and masks are kept alive until then."""
+        a = self._batch_masked_args(captures, sizes_left, workspaces, masks, kw)
+        fn = self.lib.agh_localize_batch_masked_begin_device if a["on_device"] else self.lib.agh_localize_batch_masked_begin
+        self._check(fn(self._h, a["ptrs"], a["strides"], a["ns"], a["mptrs"], a["lps"], C.c_int32(a["Ck"])))
+        self._batch_pending = a
+
+    def _depth_batch_masked_args(self, captures, masks, workspaces, kw):
+        a = self._depth_batch_args(captures, workspaces, kw)
+        if masks is None:
+            a["mrecs"], a["mkeep"] = None, []
+        else:
+            assert len(masks) == len(captures) and all(len(m) == len(images) for m, images in zip(masks, captures))
+            a["mrecs"], a["mkeep"] = sample_mask_records([m for ms in masks for m in ms], a["on_device"])
+        return a
+
+    def localize_depth_batch_masked(self, captures, masks, workspaces, caps=None, **kw):
+        """agh_localize_depth_batch_masked (torch CUDA tensors: agh_localize_depth_batch_masked_device): localize_depth_batch()
+        with every capture's samples drawn under its own masks.  `masks`: per capture a list with one entry per image (see
+        sample_mask_records: an (H, W) uint8 array, or None for no eligible pixel); None passes NULL."""
+        a = self._depth_batch_masked_args(captures, masks, workspaces, kw)
+        fn = self.lib.agh_localize_depth_batch_masked_device if a["on_device"] else self.lib.agh_localize_depth_batch_masked
+        return self._batch_collect(a, caps, lambda *out: fn(self._h, a["recs"], a["mrecs"], a["n_images"], a["lps"],
+                                                            C.c_int32(a["Ck"]), *out))
+
+    def localize_depth_batch_masked_begin(self, captures, masks, workspaces, **kw):
+        """agh_localize_depth_batch_masked_begin (torch CUDA tensors: _begin_device): the masked depth batch's chain queued;
+        collected by localize_batch_end().  Pixel and mask buffers are kept alive until then."""
+        a = self._depth_batch_masked_args(captures, masks, workspaces, kw)
+        fn = self.lib.agh_localize_depth_batch_masked_begin_device if a["on_device"] else self.lib.agh_localize_depth_batch_masked_begin
+        self._check(fn(self._h, a["recs"], a["mrecs"], a["n_images"], a["lps"], C.c_int32(a["Ck"])))
+        self._batch_pending = a
+
+    def batch_mask_counts(self, cap_captures: int = 64) -> np.ndarray:
+        """agh_get_batch_mask_counts: the eligible voxels M_k of every capture of the last masked batch this context collected."""
+        m = np.full(max(cap_captures, 1), -1, np.int64)  # (the call writes n_captures counts, none of them negative)
+        self._check(self.lib.agh_get_batch_mask_counts(self._h, _p(m, C.c_int64), C.c_int32(cap_captures)))
+        return m[m >= 0].copy()
 
     def localize_batch_stage(self, captures):
         """agh_localize_batch_stage: the NEXT batch's host captures up on a second stream, beside the chain in flight.  Returns

@@ -161,6 +161,16 @@ struct VoxBatch
   int64_t slot_words = 0;           // bitmap words per capture (a multiple of the popcount block)
 };
 
+// one capture of a batch chain, as the device sees it (localize_batch.hip; sample_mask.hip draws a masked batch's lists with it)
+struct BatchCapture
+{
+  int64_t soff;     // its first position in the batch's sample list
+  int32_t S;        // its samples
+  int32_t drawn;    // 1: drawn on the device (sample_idx NULL)
+  uint64_t seed;
+  double ws[6];     // its workspace (the boundary filter)
+};
+
 struct Comm;  // shard.hip
 
 // Host-buffer entry points: the concatenation kernel (K4) writes every record a second time, straight into pinned host
@@ -332,6 +342,8 @@ struct Ctx
   long long* h_label_counts = nullptr;  // pinned: the M_j, written by the chain
   int32_t label_objects = 0;          // n_objects of the last chain collected if it was labelled, else 0
   int64_t label_counts[kMaxClouds] = {};  // ... and its M_j
+  int32_t batch_mask_captures = 0;    // n_captures of the last chain collected if it was a masked batch, else 0
+  int64_t batch_mask_counts[kMaxClouds] = {};  // ... and its M_k
   // agh_localize_depth* (depth.hip): a host capture's depth images, rows packed, image k at depth_image_offset(k); the NEXT
   // capture's (agh_localize_depth_stage) in the second buffer; the two change places when a staged set is adopted
   uint8_t* d_depth = nullptr;
@@ -729,6 +741,31 @@ int sample_mask_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t
 // the M_j go to c->h_label_counts
 int sample_label_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, const uint8_t* d_labels, int K, double cell,
   int64_t S, unsigned long long seed, int32_t* d_out, int32_t* h_out, hipStream_t st);
+// ... and on the C slots of a batch's bitmap (vb.slot_words words each): slot k's counts at blk + k * slot_words / 4096, not scanned
+int vox_count_blocks_batch(const VoxBatch& vb, int C, const unsigned* d_bitmap, int* d_blk, hipStream_t st);
+// sample_mask.hip: the masked sample list of a batch chain whose preprocessing (vox_batch) is queued on st (include/agh.h,
+// agh_localize_batch_masked); see BatchMaskStage
+struct BatchMaskStage
+{
+  VoxBatch vb;                      // the batch's capture table, descriptors and slot size
+  int C = 0;
+  int64_t n_max = 0, S_tot = 0;     // the largest capture's raw points; the samples of all captures
+  double cell = 0.0;
+  const uint8_t* code = nullptr;    // the per-point codes of all captures (VoxCapture::code_off)
+  const uint8_t* const* mask = nullptr;  // device table: capture k's mask, one byte per raw point, at any byte alignment
+  const unsigned* bitmap = nullptr;      // the voxel bitmap slots
+  const int* blk2 = nullptr;             // ... and their capture-local block prefixes
+  const int* cloud_off = nullptr;        // the batch's device-side cloud offsets
+  unsigned* elig = nullptr;         // C eligibility slots of the voxel slots' layout
+  int* eblk = nullptr;              // their block counts, then capture-local prefixes
+  long long* total = nullptr;       // C: the M_k
+  int32_t* list = nullptr;          // the E_k, capture k's at its code_off
+  const BatchCapture* tab = nullptr;  // the chain's capture table (soff, S, seed)
+  int32_t* d_out = nullptr;         // S_tot indices into the common voxel array (or kSampleSkip), for the search
+  int32_t* h_out = nullptr;         // pinned: S_tot capture-local indices
+  long long* h_total = nullptr;     // pinned: C counts M_k
+};
+int sample_mask_stage_batch(Ctx* c, const BatchMaskStage& m, hipStream_t st);
 int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
   unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st);
 // host mirror of the handle search's results (pinned memory of the context; all nullptr / 0: none)

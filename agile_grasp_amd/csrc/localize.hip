@@ -525,6 +525,7 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
   L.active = false;
   c->mask_count = -1;
   c->label_objects = 0;
+  c->batch_mask_captures = 0;
   const int64_t S = L.S;
   const HandlePins pin = handle_pins(c);
   const int* h_counts = pin.counts;

@@ -14,15 +14,7 @@ using namespace agh;
 
 namespace agh
 {
-// one capture of the batch, as the device sees it
-struct BatchCapture
-{
-  int64_t soff;     // its first position in the batch's sample list
-  int32_t S;        // its samples
-  int32_t drawn;    // 1: drawn on the device (sample_idx NULL)
-  uint64_t seed;
-  double ws[6];     // its workspace (the boundary filter)
-};
+// (BatchCapture, one capture of the batch as the device sees it: agh_internal.h)
 constexpr int kBatchCountsStride = 8;  // ints of host-side counts per capture (as agh_localize's [0..6])
 
 // one batch, from agh_localize_batch_begin to agh_localize_batch_end: the caller's arrays are copied (explicit sample lists into
@@ -36,6 +28,10 @@ struct BatchCall
   int64_t S_tot = 0, n_tot = 0, slot = 0;
   bool classify = false, filters = false;
   double x1 = 0.0, x2 = 0.0;
+  // agh_localize_batch_masked*: capture k's mask, one byte per raw point, where the chain (and a repeat of it) reads it -- in the
+  // state's d_mask at raw_off[k], or in the caller's device memory
+  bool masked = false;
+  std::vector<const uint8_t*> d_mask;
 };
 
 struct LocalizeBatchState
@@ -66,6 +62,18 @@ struct LocalizeBatchState
   agh_handle* h_handles = nullptr;
   int32_t* h_idx = nullptr;
   int64_t h_slot = 0, h_slots = 0;
+  // sample masks (sample_mask.hip, sample_mask_stage_batch), made by the first masked batch
+  uint8_t* d_mask = nullptr;          // the chain's copy of host masks and of depth masks, packed: capture k's at raw_off[k]
+  int64_t mask_cap = 0;               // bytes
+  const uint8_t** d_mptr = nullptr;   // kMaxClouds: where each capture's mask lies
+  const uint8_t** h_mptr = nullptr;   // pinned
+  unsigned* d_elig = nullptr;         // eligibility slots, the voxel bitmap slots' layout
+  int* d_eblk = nullptr;              // their block counts, then capture-local prefixes
+  int64_t elig_words = 0;
+  long long* d_mtotal = nullptr;      // kMaxClouds: the M_k
+  long long* h_mtotal = nullptr;      // pinned, written by the chain
+  int32_t* d_elist = nullptr;         // the E_k, capture k's at raw_off[k]
+  int64_t elist_cap = 0;
 };
 
 void localize_batch_release(Ctx* c)
@@ -74,11 +82,11 @@ void localize_batch_release(Ctx* c)
   if (!b)
     return;
   void* dev[] = { b->d_tab, b->d_local, b->d.hands, b->d.bits, b->d.rowcnt, b->d.first, b->d.n, b->d.idx, b->d.counts, b->d.tmp,
-    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2 };
+    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2, b->d_mask, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist };
   for (void* p : dev)
     if (p)
       (void) hipFree(p);
-  void* host[] = { b->h_tab, b->h_samples, b->h_counts, b->h_bad, b->h_desc, b->h_hands, b->h_handles, b->h_idx, b->h_vcap };
+  void* host[] = { b->h_tab, b->h_samples, b->h_counts, b->h_bad, b->h_desc, b->h_hands, b->h_handles, b->h_idx, b->h_vcap, b->h_mptr, b->h_mtotal };
   for (void* p : host)
     if (p)
       (void) hipHostFree(p);
@@ -280,6 +288,32 @@ int ensure_vox_slots(Ctx* c, LocalizeBatchState* b, int C)
   return AGH_OK;
 }
 
+// a masked batch's buffers: the mask table, the M_k, eligibility slots as large as the voxel slots, one list entry per raw point
+int ensure_mask_slots(Ctx* c, LocalizeBatchState* b, int64_t n_tot)
+{
+  int rc;
+  // (all four or none: a table that failed half-way is made again by the next masked batch)
+  if ((!b->d_mptr || !b->h_mptr || !b->d_mtotal || !b->h_mtotal) &&
+      ((rc = dev_alloc(c, &b->d_mptr, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_mptr, (size_t) kMaxClouds)) ||
+       (rc = dev_alloc(c, &b->d_mtotal, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_mtotal, (size_t) kMaxClouds))))
+    return rc;
+  if (b->bitmap_words > b->elig_words || !b->d_elig)
+  {
+    b->elig_words = 0;
+    if ((rc = dev_alloc(c, &b->d_elig, (size_t) b->bitmap_words + 4096)) || (rc = dev_alloc(c, &b->d_eblk, (size_t) (b->bitmap_words / 4096) + 1)))
+      return rc;
+    b->elig_words = b->bitmap_words;
+  }
+  if (n_tot > b->elist_cap || !b->d_elist)
+  {
+    b->elist_cap = 0;
+    if ((rc = dev_alloc(c, &b->d_elist, (size_t) std::max<int64_t>(n_tot, 1024))))
+      return rc;
+    b->elist_cap = std::max<int64_t>(n_tot, 1024);
+  }
+  return AGH_OK;
+}
+
 }  // namespace
 
 // search -> classification -> per-capture compaction -> handle search, queued (handles_only: the handle search once more); the
@@ -343,6 +377,100 @@ struct DepthBatchSource
   bool on_device;
   const char* who;  // the entry point, for the error texts
 };
+
+// The masks of a masked batch (include/agh.h, agh_localize_batch_masked*): one byte per raw point per capture (points), or one
+// agh_sample_mask per image, parallel to the images (depth).  Host masks and all depth masks are copied, packed in point order,
+// into the state's d_mask; a device points mask is read in place.
+struct BatchMaskSource
+{
+  const uint8_t* const* points;   // points form: n_captures pointers
+  const agh_sample_mask* images;  // depth form: one per image of the flat array
+  bool on_device;
+  const char* who;
+};
+
+// the rules a masked batch adds to its unmasked twin's; the text names the capture (and the image)
+int batch_mask_check(Ctx* c, const BatchMaskSource* mask, const DepthBatchSource* depth, const agh_localize_params* lp, int C)
+{
+  auto bad = [&](const std::string& what) {
+    c->err = std::string(mask->who) + ": " + what;
+    return AGH_ERR_INVALID_ARGUMENT;
+  };
+  if (depth ? !mask->images : !mask->points)
+    return bad("masks is NULL (every capture of a masked batch has a mask)");
+  for (int k = 0, i0 = 0; k < C; k++)
+  {
+    const std::string cap = "capture " + std::to_string(k);
+    if (lp[k].sample_idx)
+      return bad(cap + ": a mask together with sample_idx (an explicit list needs no mask)");
+    if (!depth)
+    {
+      if (!mask->points[k])
+        return bad(cap + ": the mask is NULL");
+      continue;
+    }
+    bool any = false;
+    for (int j = 0; j < depth->n_images[k]; j++)
+    {
+      const agh_sample_mask& m = mask->images[i0 + j];
+      if (!m.data)
+        continue;
+      any = true;
+      if (m.row_stride_bytes < depth->images[i0 + j].width)
+        return bad(cap + ", image " + std::to_string(j) + ": the mask's row_stride_bytes is below the image's width");
+    }
+    if (!any)
+      return bad(cap + ": every mask's data is NULL (no pixel would be eligible)");
+    i0 += depth->n_images[k];
+  }
+  return AGH_OK;
+}
+
+// the masks to where the chain reads them, on st (see BatchMaskSource); B.d_mask[k] says where
+int batch_masks_to_device(Ctx* c, LocalizeBatchState* b, const BatchMaskSource* mask, const DepthBatchSource* depth, hipStream_t st)
+{
+  BatchCall& B = b->call;
+  const int C = B.C;
+  B.masked = true;
+  B.d_mask.resize((size_t) C);
+  if (!depth && mask->on_device)
+  {
+    for (int k = 0; k < C; k++)
+      B.d_mask[k] = mask->points[k];
+    return AGH_OK;
+  }
+  if (B.n_tot > b->mask_cap || !b->d_mask)
+  {
+    b->mask_cap = 0;
+    if (int rc = dev_alloc(c, &b->d_mask, (size_t) std::max<int64_t>(B.n_tot, 1)))
+      return rc;
+    b->mask_cap = std::max<int64_t>(B.n_tot, 1);
+  }
+  const hipMemcpyKind kind = mask->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  for (int k = 0, i0 = 0; k < C; k++)
+  {
+    uint8_t* dst = b->d_mask + B.raw_off[k];
+    B.d_mask[k] = dst;
+    if (!depth)
+    {
+      if (B.n[k] > 0)
+        AGH_HIPCHK(c, hipMemcpyAsync(dst, mask->points[k], (size_t) B.n[k], kind, st));
+      continue;
+    }
+    for (int j = 0; j < depth->n_images[k]; j++)
+    {
+      const size_t W = (size_t) depth->images[i0 + j].width, H = (size_t) depth->images[i0 + j].height;
+      const agh_sample_mask& m = mask->images[i0 + j];
+      if (!m.data)
+        AGH_HIPCHK(c, hipMemsetAsync(dst, 0, W * H, st));
+      else
+        AGH_HIPCHK(c, hipMemcpy2DAsync(dst, W, m.data, (size_t) m.row_stride_bytes, W, H, kind, st));
+      dst += W * H;
+    }
+    i0 += depth->n_images[k];
+  }
+  return AGH_OK;
+}
 
 // Steps 2 to 5 of the batch c->lbatch->call, queued on the context's stream: preprocessing, the batch of clouds, the sample list,
 // search -> classification -> kept hands per capture -> handle search.  Nothing waits, except the first batch of a context (or one
@@ -475,7 +603,7 @@ int batch_pass(agh_ctx* ctx)
     BatchCapture& t = b->h_tab[k];
     t.soff = B.soff[k];
     t.S = (int32_t) lp[k].n_samples;
-    t.drawn = lp[k].sample_idx ? 0 : 1;
+    t.drawn = lp[k].sample_idx ? 0 : 1;  // (a masked batch has no explicit list)
     t.seed = lp[k].sample_seed;
     for (int q = 0; q < 6; q++)
       t.ws[q] = lp[k].workspace[q];
@@ -495,7 +623,37 @@ int batch_pass(agh_ctx* ctx)
     AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_local, b->h_samples, sizeof(int32_t) * (size_t) S_tot, hipMemcpyHostToDevice, st),
       chain_fail(c, AGH_ERR_HIP));
   }
-  if (S_tot > 0)
+  if (B.masked)  // (for S_tot = 0 too: the M_k are what a caller sizes the S_k with)
+  {
+    if ((rc = ensure_mask_slots(c, b, n_tot)) != AGH_OK)
+      return chain_fail(c, rc);
+    for (int k = 0; k < C; k++)
+      b->h_mptr[k] = B.d_mask[k];
+    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_mptr, b->h_mptr, sizeof(const uint8_t*) * (size_t) C, hipMemcpyHostToDevice, st),
+      chain_fail(c, AGH_ERR_HIP));
+    BatchMaskStage m;
+    m.vb = vb;
+    m.C = C;
+    m.n_max = n_max;
+    m.S_tot = S_tot;
+    m.cell = cell;
+    m.code = c->d_vox_code;
+    m.mask = b->d_mptr;
+    m.bitmap = b->d_bitmap;
+    m.blk2 = b->d_blk2;
+    m.cloud_off = c->d_cloud_off;
+    m.elig = b->d_elig;
+    m.eblk = b->d_eblk;
+    m.total = b->d_mtotal;
+    m.list = b->d_elist;
+    m.tab = b->d_tab;
+    m.d_out = c->d_idx_own;
+    m.h_out = b->h_samples;
+    m.h_total = b->h_mtotal;
+    if ((rc = sample_mask_stage_batch(c, m, st)) != AGH_OK)
+      return chain_fail(c, rc);
+  }
+  else if (S_tot > 0)
   {
     hipLaunchKernelGGL(k_batch_samples, dim3((unsigned) ((S_tot + 255) / 256)), dim3(256), 0, st, (const BatchCapture*) b->d_tab, C,
       S_tot, (const int*) c->d_cloud_off, (const int32_t*) b->d_local, c->d_idx_own, b->h_samples, b->h_bad);
@@ -510,12 +668,12 @@ int batch_pass(agh_ctx* ctx)
 // agh_localize_batch_begin: the arguments checked and copied, the captures up (or adopted from agh_localize_batch_stage, or read in
 // place), steps 2 to 5 queued.
 int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
-  const agh_localize_params* lp, int32_t n_captures, const DepthBatchSource* depth = nullptr)
+  const agh_localize_params* lp, int32_t n_captures, const DepthBatchSource* depth = nullptr, const BatchMaskSource* mask = nullptr)
 {
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
   const int C = n_captures;
-  const std::string who = depth ? depth->who : "agh_localize_batch";
+  const std::string who = mask ? mask->who : (depth ? depth->who : "agh_localize_batch");
   if (L.active)
   {
     c->err = who + ": a localize chain is in flight on this context (agh_localize_end first)";
@@ -547,7 +705,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   }
   else if (C < 1 || C > kMaxClouds || !xyz || !stride_bytes || !n || !lp)
   {
-    c->err = kBadArguments;
+    c->err = mask ? who + ": bad arguments (1 <= n_captures <= 64; see include/agh.h)" : std::string(kBadArguments);
     return AGH_ERR_INVALID_ARGUMENT;
   }
   int64_t n_tot = 0, S_tot = 0;
@@ -583,6 +741,9 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   if (cam_table_mismatch(c, who.c_str(), C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
     return AGH_ERR_INVALID_ARGUMENT;                    // the table stays the context's until agh_localize_batch_end: the setter
                                                         // refuses mid-chain, so the repeats search with it too)
+  if (mask)
+    if (int rc = batch_mask_check(c, mask, depth, lp, C))
+      return rc;
   double x1 = 0.0, x2 = 0.0;
   if (!handle_thresholds(&x1, &x2))
   {
@@ -645,7 +806,8 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
       B.dev_stride[k] = device_stride(stride_bytes[k]);
       need += n[k] * (B.dev_stride[k] / 4);
     }
-    const bool adopt = L.staged_is(xyz, stride_bytes, n, C, true) && c->d_stage_xyz;
+    // (a masked begin of host data never adopts a staged set: it drops a pending one as a begin of another kind does)
+    const bool adopt = !mask && L.staged_is(xyz, stride_bytes, n, C, true) && c->d_stage_xyz;
     // A staged batch that is this one: it is (or is about to be) in the second raw buffer -- the two buffers change places and the
     // chain waits for the copies.  Anything else that is staged (another batch, a capture of agh_localize_stage) is dropped: its
     // copy may still read the caller's source, so the chain waits for it too and agh_localize_batch_end's synchronisation covers it.
@@ -670,6 +832,8 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
       off += n[k] * (B.dev_stride[k] / 4);
     }
   }
+  if (mask && (rc = batch_masks_to_device(c, b, mask, depth, st)) != AGH_OK)
+    return chain_fail(c, rc);  // (the captures' copies may be in flight)
   ActiveGuard guard(c);
   if ((rc = batch_pass(ctx)) != AGH_OK)
     return rc;
@@ -699,6 +863,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   c->loc.batch = false;
   c->mask_count = -1;  // (agh_get_sample_mask_count: the last chain collected had no mask)
   c->label_objects = 0;  // (... and no label image)
+  c->batch_mask_captures = 0;  // (agh_get_batch_mask_counts: set below, behind the synchronisation, if this batch is masked)
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)
@@ -737,6 +902,12 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
     b->last_words = words;
     break;
   }
+  if (B.masked)
+  {
+    for (int k = 0; k < C; k++)
+      c->batch_mask_counts[k] = (int64_t) b->h_mtotal[k];
+    c->batch_mask_captures = C;
+  }
   // the bound batch is now the true one
   std::vector<int64_t> voff(C + 1, 0), nv(C);
   for (int k = 0; k < C; k++)
@@ -764,7 +935,7 @@ void zero_results(agh_localize_batch_result* results, int C)
 int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
   const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results,
-  const DepthBatchSource* depth = nullptr)
+  const DepthBatchSource* depth = nullptr, const BatchMaskSource* mask = nullptr)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
@@ -772,15 +943,15 @@ int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int6
   zero_results(results, n_captures);
   if (c->loc.active)
   {
-    c->err = std::string(depth ? depth->who : "agh_localize_batch") + ": a localize chain is in flight on this context (agh_localize_end first)";
+    c->err = std::string(mask ? mask->who : (depth ? depth->who : "agh_localize_batch")) + ": a localize chain is in flight on this context (agh_localize_end first)";
     return AGH_ERR_STATE;
   }
   if (bad_outputs(handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap))
   {
-    c->err = depth ? std::string(depth->who) + ": bad output arguments (see include/agh.h)" : std::string(kBadArguments);
+    c->err = depth || mask ? std::string(mask ? mask->who : depth->who) + ": bad output arguments (see include/agh.h)" : std::string(kBadArguments);
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  const int rc = batch_begin_impl(ctx, xyz, on_device, stride_bytes, n, lp, n_captures, depth);
+  const int rc = batch_begin_impl(ctx, xyz, on_device, stride_bytes, n, lp, n_captures, depth, mask);
   if (rc != AGH_OK)
     return rc;
   return batch_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
@@ -951,6 +1122,108 @@ int agh_localize_depth_batch_begin_device(agh_ctx* ctx, const agh_depth_image* i
     return AGH_ERR_INVALID_ARGUMENT;
   const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_begin_device" };
   return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src);
+}
+
+// ---- the masked forms (include/agh.h): the batch chains with every capture's samples drawn under its own mask ----
+
+int agh_localize_batch_masked(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  const BatchMaskSource m{ masks, nullptr, false, "agh_localize_batch_masked" };
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, nullptr, &m);
+}
+
+int agh_localize_batch_masked_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  const BatchMaskSource m{ masks, nullptr, true, "agh_localize_batch_masked_device" };
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, nullptr, &m);
+}
+
+int agh_localize_batch_masked_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const BatchMaskSource m{ masks, nullptr, false, "agh_localize_batch_masked_begin" };
+  return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, nullptr, &m);
+}
+
+int agh_localize_batch_masked_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const BatchMaskSource m{ masks, nullptr, true, "agh_localize_batch_masked_begin_device" };
+  return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, nullptr, &m);
+}
+
+int agh_localize_depth_batch_masked(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, const int32_t* n_images,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_masked" };
+  const BatchMaskSource m{ nullptr, masks, false, src.who };
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src, &m);
+}
+
+int agh_localize_depth_batch_masked_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
+  const int32_t* n_images, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_masked_device" };
+  const BatchMaskSource m{ nullptr, masks, true, src.who };
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src, &m);
+}
+
+int agh_localize_depth_batch_masked_begin(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
+  const int32_t* n_images, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_masked_begin" };
+  const BatchMaskSource m{ nullptr, masks, false, src.who };
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+}
+
+int agh_localize_depth_batch_masked_begin_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
+  const int32_t* n_images, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_masked_begin_device" };
+  const BatchMaskSource m{ nullptr, masks, true, src.who };
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+}
+
+int agh_get_batch_mask_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_captures)
+{
+  if (!ctx || !n_eligible)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_batch_mask_counts"))
+    return AGH_ERR_STATE;
+  if (c->batch_mask_captures < 1)
+  {
+    c->err = "agh_get_batch_mask_counts: the last chain this context collected was no masked batch (or there was none)";
+    return AGH_ERR_STATE;
+  }
+  if (cap_captures < c->batch_mask_captures)
+  {
+    c->err = "agh_get_batch_mask_counts: cap_captures is below the batch's n_captures";
+    return AGH_ERR_CAPACITY;
+  }
+  std::copy(c->batch_mask_counts, c->batch_mask_counts + c->batch_mask_captures, n_eligible);
+  return AGH_OK;
 }
 
 // The NEXT batch's captures up, beside whatever runs on the context's stream (stage_captures, localize.hip).  A pinned source must

@@ -625,6 +625,14 @@ int vox_count_blocks(const unsigned* d_bitmap, int64_t n_blocks, int* d_blk, lon
   return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
 }
 
+int vox_count_blocks_batch(const VoxBatch& vb, int C, const unsigned* d_bitmap, int* d_blk, hipStream_t st)
+{
+  if (vb.slot_words > 0)
+    hipLaunchKernelGGL(k_vox_popcount, dim3((unsigned) (vb.slot_words / kWordsPerBlock), (unsigned) C), dim3(256), 0, st, d_bitmap,
+      d_blk, vb);
+  return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
+}
+
 // agh_localize_batch: the preprocessing of C captures, one launch per stage, capture = blockIdx.y (see VoxBatch).  Stage 1 (finite
 // counts, their scan with the descriptors' reset, camera ids, workspace, extrema); with probe, the lattices next (the caller waits
 // for them and sizes the slots); otherwise the speculative stage 2 on slots of vb.slot_words words: clear + lattice, mark,

@@ -282,9 +282,10 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
  * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
- * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled* and agh_localize_depth_labeled* among
- * them), agh_deproject, agh_deproject_batch,
- * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts and every getter of device results (frames, normals,
+ * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled*, agh_localize_depth_labeled*,
+ * agh_localize_batch_masked*, agh_localize_batch_masked_begin*, agh_localize_depth_batch_masked* and
+ * agh_localize_depth_batch_masked_begin* among them), agh_deproject, agh_deproject_batch,
+ * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_batch_mask_counts and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -395,8 +396,9 @@ int agh_localize_depth_stage(agh_ctx* ctx, const agh_depth_image* images, int32_
  * repeats inside the call (the lattice that outgrew the kept bitmap, the capacity classes) need the caller's mask in no other
  * way than they need the caller's capture.  One more bitmap of the voxel bitmap's size is held by a context that made a masked
  * call; the chain's one synchronisation stays one.
- * Not built: a _stage call for masks; masks for agh_localize_batch* and agh_localize_depth_batch*; label images in the batch
- * chains (for ONE capture, several objects with one sample list each: agh_localize_labeled* below); sharded variants. */
+ * Not built: a _stage call for masks, for one capture or a batch (the batch forms are agh_localize_batch_masked* below);
+ * label images in the batch chains (agh_localize_batch*, agh_localize_depth_batch*; for ONE capture, several objects with one
+ * sample list each: agh_localize_labeled* below); sharded variants. */
 typedef struct agh_sample_mask
 {
   const uint8_t* data;       /* one byte per pixel, non-zero = eligible; NULL: no pixel of this image is */
@@ -548,7 +550,9 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * The context has ONE chain and ONE staged set, of either kind.  A begin of either kind while a chain of either kind is in
  * flight (agh_localize_depth_batch* and agh_localize_depth_batch_begin* included, agh_localize_masked*,
  * agh_localize_masked_begin, agh_localize_depth_masked* and agh_localize_depth_masked_begin too, and agh_localize_labeled*
- * and agh_localize_depth_labeled*; agh_deproject_batch, agh_get_sample_mask_count and agh_get_label_counts are refused as well),
+ * and agh_localize_depth_labeled*, agh_localize_batch_masked*, agh_localize_batch_masked_begin*,
+ * agh_localize_depth_batch_masked* and agh_localize_depth_batch_masked_begin*; agh_deproject_batch, agh_get_sample_mask_count,
+ * agh_get_label_counts and agh_get_batch_mask_counts are refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
@@ -615,6 +619,75 @@ int agh_localize_depth_batch_begin_device(agh_ctx* ctx, const agh_depth_image* i
   const agh_localize_params* lp, int32_t n_captures);
 int agh_deproject_batch(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images, int32_t n_captures, float* xyz_out,
   int64_t cap_points);
+
+/* The batch chains with every capture's samples drawn UNDER ITS OWN MASK: a cell with several sensor pairs and one detector per
+ * sensor hands over, per rig, a capture and an object mask, and wants handles on the masked object of every rig from one call.
+ * agh_localize_masked once per capture pays the single chain per capture, one after the other; an explicit sample_idx cannot
+ * stand in for a mask, because it indexes the voxelised cloud, which only exists inside the call.
+ * Points forms: masks is a host array of n_captures pointers; masks[k] holds one byte per raw point of capture k, packed, any
+ * non-zero byte means "eligible".  Depth forms: masks is ONE flat array parallel to `images`: masks[i] belongs to images[i], has
+ * its width and height, row v at data + v * row_stride_bytes (>= width); data == NULL: no pixel of that image is eligible.
+ *  1. Rules 1 to 3 of agh_localize_masked hold per capture: E_k is the ascending list of capture k's eligible CAPTURE-LOCAL voxel
+ *     indices, M_k = |E_k|, and sample t of capture k is E_k[stratum draw of agh_localize with M_k in the place of N,
+ *     lp[k].n_samples and lp[k].sample_seed]; with M_k < lp[k].n_samples the list is E_k followed by INT32_MIN slots.  M_k = 0
+ *     is no error: that capture has zero hypotheses, hands and handles, and the other captures are not affected.
+ *  2. Equality per capture with the masked call: capture k's span of every output and results[k].r equal, bit for bit (epoch
+ *     aside), what agh_localize_masked returns for capture k alone with masks[k] and lp[k], and M_k equals that call's
+ *     agh_get_sample_mask_count.  The depth form's twin is agh_localize_depth_masked on capture k's images and masks.
+ *  3. Equality with the unmasked batch: the results equal agh_localize_batch (agh_localize_depth_batch) on the same captures
+ *     with each lp[k].sample_idx set to capture k's reported list; with all-ones masks the call equals the unmasked batch with
+ *     sample_idx = NULL and the same seeds.
+ *  4. Every capture of a masked batch has a mask.  AGH_ERR_INVALID_ARGUMENT, nothing launched, the text naming the capture (and
+ *     the image, for a stride): masks == NULL; a NULL masks[k] (points); a depth capture whose mask records ALL have
+ *     data == NULL; an lp[k].sample_idx != NULL; a mask row stride below the width.  Every validation, status and text of the
+ *     unmasked batch twin holds as well: the fields that must be equal across the batch, n_captures in 1..64, 2^30 points,
+ *     AGH_ERR_NO_SVM, the row count of a camera-origin table, the per-image rules.
+ *  5. The output layout of agh_localize_batch* holds unchanged: samples_out holds capture-local indices, the per-capture spans
+ *     and results[k], the per-capture 8192-hand limit, AGH_ERR_CAPACITY with every results[k] filled, one synchronisation in the
+ *     steady state, and the first batch of a context takes the synchronisation for the lattice sizes.  The repeats inside the
+ *     call -- the batch once more when the lattices outgrew the kept slots, the capacity classes -- read the masks where the
+ *     first pass left them and search the lists already drawn.
+ *  6. The mask stage runs for n_samples = 0 too.  agh_get_batch_mask_counts writes the M_k (n_captures entries) of the last
+ *     batch chain this context collected, if that chain was masked; AGH_ERR_CAPACITY if cap_captures is below its n_captures;
+ *     AGH_ERR_STATE if no chain was collected, if the last one was not a masked batch, or while a chain is in flight.  After a
+ *     masked batch agh_get_sample_mask_count and agh_get_label_counts return AGH_ERR_STATE.
+ *  7. A call while a chain of any kind is in flight returns AGH_ERR_STATE with the chain untouched.  The _begin forms queue the
+ *     chain as agh_localize_batch_begin does and are collected with agh_localize_batch_end (the blocking forms are begin + end);
+ *     between the two the rules of agh_localize_batch_begin hold.  A masked begin of host data never adopts a staged set: it
+ *     drops a pending one, and the chain waits for its copies.
+ *  8. Lifetimes: host masks are copied by begin into a buffer of the context, depth masks repacked to one byte per pixel in
+ *     point order (a pageable mask has been read when begin returns; a pinned one follows the captures' lifetime rules, as
+ *     the captures' own copies do).  Device points masks (_device: xyz[k] and masks[k] are device pointers) are read in place,
+ *     at any byte alignment, and follow the captures' lifetime rules.  Device depth masks are repacked into the same buffer by
+ *     device-to-device copies queued at begin; they must stay valid until the call (or agh_localize_batch_end) has returned.
+ *  9. A context's first masked batch adds: one more set of bitmap slots of the batch's bitmap size, one byte and one 32-bit
+ *     word per raw point, and the slots' block counts -- nothing else that scales with n_captures x the largest lattice.
+ * Not built: a _stage call for masks; label images in the batch chains; masked and unmasked captures mixed in one batch (an
+ * all-ones mask says "unmasked"); sharded variants. */
+int agh_localize_batch_masked(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);
+int agh_localize_batch_masked_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);
+int agh_localize_batch_masked_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_batch_masked_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_depth_batch_masked(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, const int32_t* n_images,
+  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+int agh_localize_depth_batch_masked_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
+  const int32_t* n_images, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);
+int agh_localize_depth_batch_masked_begin(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
+  const int32_t* n_images, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_depth_batch_masked_begin_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
+  const int32_t* n_images, const agh_localize_params* lp, int32_t n_captures);
+int agh_get_batch_mask_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_captures);
 
 /* The context's current cloud: packed xyz (3 floats per point) and camera ids; returns the number of points. */
 int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap);

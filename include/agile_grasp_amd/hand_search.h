@@ -669,6 +669,123 @@ public:
     return true;
   }
 
+  /** Additional: localizeBatchBegin with every capture's num_samples drawn UNDER ITS OWN MASK (agh_localize_batch_masked_begin):
+   *  masks[k] holds one byte per point of clouds[k], non-zero = a sample may be drawn in the voxel this point falls into; the
+   *  whole capture stays in the search.  Capture k is seeded with the sample seed + k.  Collected by localizeBatchEnd;
+   *  batchMaskCounts() then gives the eligible voxels per capture.  The masks are copied by the call; the clouds must stay alive
+   *  and unchanged until localizeBatchEnd has returned.  A Begin that fails leaves a chain in flight as it was. */
+  bool localizeBatchMaskedBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<std::vector<std::uint8_t> >& masks, const std::vector<VectorXd>& workspaces, double cell_size,
+    const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    const std::size_t C = clouds.size();
+    if (C == 0 || sizes_left.size() != C || workspaces.size() != C || masks.size() != C)
+    {
+      std::cout << " Error: localizeBatchMaskedBegin needs one size_left, workspace and mask per cloud\n";
+      return false;
+    }
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    RawBatch in;
+    if (!rawPoints(clouds, in))
+      return false;
+    const std::uint64_t seed = sampleSeed();
+    std::vector<agh_localize_params> lp(C);
+    std::vector<const std::uint8_t*> mptr(C);
+    std::int64_t cap = 1, n_samples = 0;
+    for (std::size_t k = 0; k < C; k++)
+    {
+      if (masks[k].size() != clouds[k]->points.size())
+      {
+        std::cout << " Error: localizeBatchMaskedBegin needs one mask byte per point of every cloud\n";
+        return false;
+      }
+      mptr[k] = masks[k].data();
+      lp[k] = chainParams(sizes_left[k], cloud_is_dense(*clouds[k]), workspaces[k], cell_size, std::vector<std::int32_t>(),
+        seed + (std::uint64_t) k, min_inliers, min_length, filters_boundaries);
+      cap += handsRoom(lp[k].n_samples);
+      n_samples += lp[k].n_samples;
+    }
+    if (agh_localize_batch_masked_begin(ctx_, in.xyz.data(), in.stride.data(), in.n.data(), mptr.data(), lp.data(), (std::int32_t) C) !=
+        AGH_OK)
+    {
+      fail("agh_localize_batch_masked_begin");
+      return false;
+    }
+    batch_captures_ = C;
+    batch_cap_ = cap;
+    batch_samples_ = n_samples;
+    return true;
+  }
+
+  /** ... and straight from depth images (agh_localize_depth_batch_masked_begin): masks[k][j] belongs to captures[k][j]; a mask
+   *  without data makes no pixel of its image eligible, and every capture needs at least one mask with data. */
+  bool localizeDepthBatchMaskedBegin(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<std::vector<SampleMask> >& masks, const std::vector<VectorXd>& workspaces, double cell_size,
+    const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    const std::size_t C = captures.size();
+    if (C == 0 || workspaces.size() != C || masks.size() != C)
+    {
+      std::cout << " Error: localizeDepthBatchMaskedBegin needs one workspace and mask list per capture\n";
+      return false;
+    }
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    const std::uint64_t seed = sampleSeed();
+    std::vector<agh_depth_image> recs;  // (the flat arrays in capture order; copied by the library's begin, like the arrays below)
+    std::vector<agh_sample_mask> mrecs;
+    std::vector<std::int32_t> n_images(C);
+    std::vector<agh_localize_params> lp(C);
+    std::int64_t cap = 1, n_samples = 0;
+    for (std::size_t k = 0; k < C; k++)
+    {
+      if (masks[k].size() != captures[k].size())
+      {
+        std::cout << " Error: localizeDepthBatchMaskedBegin needs one mask per image\n";
+        return false;
+      }
+      const std::vector<agh_depth_image> r = depthRecords(captures[k]);
+      recs.insert(recs.end(), r.begin(), r.end());
+      for (std::size_t j = 0; j < masks[k].size(); j++)
+      {
+        agh_sample_mask m;
+        m.data = masks[k][j].data;
+        m.row_stride_bytes = masks[k][j].row_stride_bytes;
+        mrecs.push_back(m);
+      }
+      n_images[k] = (std::int32_t) r.size();
+      lp[k] = chainParams(0, true, workspaces[k], cell_size, std::vector<std::int32_t>(), seed + (std::uint64_t) k, min_inliers,
+        min_length, filters_boundaries);
+      cap += handsRoom(lp[k].n_samples);
+      n_samples += lp[k].n_samples;
+    }
+    if (agh_localize_depth_batch_masked_begin(ctx_, recs.empty() ? nullptr : recs.data(), mrecs.empty() ? nullptr : mrecs.data(),
+          n_images.data(), lp.data(), (std::int32_t) C) != AGH_OK)
+    {
+      fail("agh_localize_depth_batch_masked_begin");
+      return false;
+    }
+    batch_captures_ = C;
+    batch_cap_ = cap;
+    batch_samples_ = n_samples;
+    return true;
+  }
+
+  /** agh_get_batch_mask_counts: the eligible voxels of every capture of the last masked batch localizeBatchEnd collected; empty
+   *  if the last chain collected was no masked batch */
+  std::vector<std::int64_t> batchMaskCounts()
+  {
+    std::vector<std::int64_t> m(64, -1);
+    if (!ctx_ || agh_get_batch_mask_counts(ctx_, m.data(), 64) != AGH_OK)
+      return std::vector<std::int64_t>();
+    std::size_t k = 0;
+    while (k < m.size() && m[k] >= 0)
+      k++;
+    m.resize(k);
+    return m;
+  }
+
   /** agh_localize_batch_stage: the NEXT batch's clouds up, beside the chain in flight (keep them alive and unchanged until the
    *  localizeBatchEnd of the chain that searches them has returned). */
   bool localizeBatchStage(const std::vector<PointCloud::Ptr>& next)

@@ -672,6 +672,89 @@ public:
     return out;
   }
 
+  /** Additional: localizeHandlesBatch with every capture's samples drawn UNDER ITS OWN MASK (agh_localize_batch_masked): a cell
+   *  with one detector per sensor pair hands over masks[k], one byte per point of clouds[k]; num_samples samples are drawn per
+   *  capture among the voxels that hold one of its masked points, and the whole capture stays in the search.  Per capture the
+   *  same handles as localizeHandlesMasked on that capture and mask (seeded with the sample seed + k). */
+  std::vector<std::vector<Handle> > localizeHandlesBatchMasked(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<std::vector<std::uint8_t> >& masks, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_cloud = nullptr, const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesBatchMasked") ||
+        !localizeHandlesBatchMaskedBegin(clouds, sizes_left, masks, svm_filename, min_inliers, min_length, workspaces))
+      return noHandles(clouds.size(), antipodal_hands_per_cloud);
+    return localizeHandlesBatchEnd(antipodal_hands_per_cloud);
+  }
+
+  /** ... as two calls: the chain queued here is collected by localizeHandlesBatchEnd.  A Begin while a chain of any kind is
+   *  pending returns false and leaves it as it was, and so does a Begin that fails for another reason.  The masks are copied by
+   *  the call; the clouds must stay alive and unchanged until localizeHandlesBatchEnd has returned. */
+  bool localizeHandlesBatchMaskedBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<std::vector<std::uint8_t> >& masks, const std::string& svm_filename, int min_inliers, double min_length,
+    const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesBatchMaskedBegin", "its End"))
+      return false;
+    for (std::size_t k = 0; k < clouds.size(); k++)
+      if (!clouds[k] || clouds[k]->size() == 0 || k >= sizes_left.size() || sizes_left[k] == 0)
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    if (!detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(clouds.size(), workspace_);
+    if (!search_->localizeBatchMaskedBegin(clouds, sizes_left, masks, ws, 0.003, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
+      return false;
+    pending_batch_ = clouds;
+    return true;
+  }
+
+  /** ... and straight from depth images with one mask per image (agh_localize_depth_batch_masked): masks[k][j] belongs to
+   *  captures[k][j]; a mask without data makes no pixel of its image eligible.  Per capture the same handles as
+   *  localizeHandlesDepthMasked on that capture and its masks. */
+  std::vector<std::vector<Handle> > localizeHandlesDepthBatchMasked(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<std::vector<SampleMask> >& masks, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_capture = nullptr, const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatchMasked") ||
+        !localizeHandlesDepthBatchMaskedBegin(captures, masks, svm_filename, min_inliers, min_length, workspaces))
+      return noHandles(captures.size(), antipodal_hands_per_capture);
+    return localizeHandlesBatchEnd(antipodal_hands_per_capture);
+  }
+
+  bool localizeHandlesDepthBatchMaskedBegin(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<std::vector<SampleMask> >& masks, const std::string& svm_filename, int min_inliers, double min_length,
+    const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatchMaskedBegin", "its End"))
+      return false;
+    for (std::size_t k = 0; k < captures.size(); k++)
+      if (captures[k].empty())
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    if (!detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(captures.size(), workspace_);
+    if (!search_->localizeDepthBatchMaskedBegin(captures, masks, ws, 0.003, svm_filename, min_inliers, min_length, filters_boundaries_))
+      return false;
+    pending_batch_.assign(captures.size(), PointCloud::Ptr());  // (one entry per capture, none with a host cloud)
+    return true;
+  }
+
+  /** The eligible voxels of every capture of the last masked batch localizeHandlesBatchEnd collected
+   *  (agh_get_batch_mask_counts); empty if the last chain collected was no masked batch, if there was none, or while a chain is
+   *  pending. */
+  std::vector<std::int64_t> getBatchMaskCounts()
+  {
+    return search_ ? search_->batchMaskCounts() : std::vector<std::int64_t>();
+  }
+
   /** the searched hands, handles and inlier lists of one capture as the reference's objects (the tail of localizeHandlesEnd) */
   std::vector<Handle> toHandles(const PointCloud::Ptr& cloud_in, const std::vector<agh_hypothesis>& hands,
     const std::vector<agh_handle>& handles, const std::vector<std::int32_t>& idx, std::vector<GraspHypothesis>* antipodal_hands)
