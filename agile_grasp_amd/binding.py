@@ -100,6 +100,9 @@ EXPORTS = [
     "agh_localize_batch_masked", "agh_localize_batch_masked_device", "agh_localize_batch_masked_begin",
     "agh_localize_batch_masked_begin_device", "agh_localize_depth_batch_masked", "agh_localize_depth_batch_masked_device",
     "agh_localize_depth_batch_masked_begin", "agh_localize_depth_batch_masked_begin_device", "agh_get_batch_mask_counts",
+    "agh_localize_batch_labeled", "agh_localize_batch_labeled_device", "agh_localize_batch_labeled_begin",
+    "agh_localize_batch_labeled_begin_device", "agh_localize_depth_batch_labeled", "agh_localize_depth_batch_labeled_device",
+    "agh_localize_depth_batch_labeled_begin", "agh_localize_depth_batch_labeled_begin_device", "agh_get_batch_label_counts",
 ]
 
 
@@ -277,6 +280,16 @@ def labeled_samples(eligible_lists, n_samples: int, seed: int) -> np.ndarray:
     if not len(eligible_lists) or n_samples == 0:
         return np.zeros(0, np.int32)
     return np.concatenate([masked_samples(E, n_samples, seed) for E in eligible_lists])
+
+
+def batch_labeled_samples(eligible_lists, n_samples, seeds) -> np.ndarray:
+    """The sample list agh_localize_batch_labeled draws (include/agh.h): labeled_samples of every capture, capture after
+    capture.  eligible_lists[k]: capture k's per-object ascending lists of eligible CAPTURE-LOCAL voxel indices; n_samples and
+    seeds: an int for all captures, or one per capture."""
+    Ck = len(eligible_lists)
+    per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * Ck
+    parts = [labeled_samples(E, int(S), int(seed)) for E, S, seed in zip(eligible_lists, per(n_samples), per(seeds))]
+    return np.concatenate(parts) if parts else np.zeros(0, np.int32)
 
 
 class AghLabelImage(C.Structure):
@@ -949,6 +962,94 @@ class Context:
         self._check(self.lib.agh_get_batch_mask_counts(self._h, _p(m, C.c_int64), C.c_int32(cap_captures)))
         return m[m >= 0].copy()
 
+    # ---- label images in the batch chains (include/agh.h, agh_localize_batch_labeled*) ----
+
+    @staticmethod
+    def _batch_label_lists(a, n_objects):
+        """A labelled batch has a list per (capture, object): a["Ck"] and a["S_list"] become the lists' (what _batch_collect
+        sizes the outputs and reads results[] with), a["groups"] the objects per capture.  n_objects the library will refuse
+        (None, an entry outside 1..64, more than 64 lists) leave no list to collect."""
+        Ck = a["Ck"]
+        a["n_captures"] = Ck
+        if n_objects is None:
+            a["n_obj"], groups = None, None
+        else:
+            groups = [int(K) for K in n_objects]
+            assert len(groups) == Ck
+            a["n_obj"] = (C.c_int32 * max(Ck, 1))(*groups)
+            if any(K < 1 or K > 64 for K in groups) or sum(groups) > 64:
+                groups = None
+        a["groups"] = groups if groups is not None else []
+        a["S_list"] = [S for K, S in zip(a["groups"], a["S_list"]) for _ in range(K)]
+        a["Ck"] = len(a["S_list"])
+        return a
+
+    def _batch_labeled_collect(self, a, caps, call):
+        """_batch_collect over the lists, regrouped: a list per capture of a list per object of the usual dicts."""
+        flat = self._batch_collect(a, caps, call)
+        out, l = [], 0
+        for K in a["groups"]:
+            out.append(flat[l:l + K])
+            l += K
+        self.n = sum(objs[0]["n_voxels"] for objs in out)  # (every list reports its capture's voxel count)
+        return out
+
+    def _batch_labeled_args(self, captures, sizes_left, workspaces, labels, n_objects, kw):
+        a = self._batch_masked_args(captures, sizes_left, workspaces, labels, kw)
+        return self._batch_label_lists(a, n_objects)
+
+    def localize_batch_labeled(self, captures, sizes_left, workspaces, labels, n_objects, caps=None, **kw):
+        """agh_localize_batch_labeled (torch CUDA tensors: agh_localize_batch_labeled_device): localize_batch() with one sample
+        list per object of every capture.  labels[k]: one uint8 per raw point of capture k (0: no object, j + 1: object j of
+        that capture); n_objects[k]: its objects; n_samples is per OBJECT.  The other arguments (by keyword) as for
+        localize_batch.  Returns a list per capture of a list per object of the dicts localize_batch returns; capture k's equal
+        localize_labeled on that capture alone.  batch_label_counts() then gives the eligible voxels per list."""
+        a = self._batch_labeled_args(captures, sizes_left, workspaces, labels, n_objects, kw)
+        fn = self.lib.agh_localize_batch_labeled_device if a["on_device"] else self.lib.agh_localize_batch_labeled
+        return self._batch_labeled_collect(a, caps, lambda *out: fn(self._h, a["ptrs"], a["strides"], a["ns"], a["mptrs"], a["n_obj"],
+                                                                    a["lps"], C.c_int32(a["n_captures"]), *out))
+
+    def localize_batch_labeled_begin(self, captures, sizes_left, workspaces, labels, n_objects, **kw):
+        """agh_localize_batch_labeled_begin (torch CUDA tensors: _begin_device): the labelled batch's chain queued, nothing
+        waited for; collected by localize_batch_end().  Captures and labels are kept alive until then."""
+        a = self._batch_labeled_args(captures, sizes_left, workspaces, labels, n_objects, kw)
+        fn = self.lib.agh_localize_batch_labeled_begin_device if a["on_device"] else self.lib.agh_localize_batch_labeled_begin
+        self._check(fn(self._h, a["ptrs"], a["strides"], a["ns"], a["mptrs"], a["n_obj"], a["lps"], C.c_int32(a["n_captures"])))
+        self._batch_pending = a
+
+    def _depth_batch_labeled_args(self, captures, labels, workspaces, n_objects, kw):
+        a = self._depth_batch_args(captures, workspaces, kw)
+        if labels is None:
+            a["mrecs"], a["mkeep"] = None, []
+        else:
+            assert len(labels) == len(captures) and all(len(m) == len(images) for m, images in zip(labels, captures))
+            a["mrecs"], a["mkeep"] = label_image_records([m for ms in labels for m in ms], a["on_device"])
+        return self._batch_label_lists(a, n_objects)
+
+    def localize_depth_batch_labeled(self, captures, labels, workspaces, n_objects, caps=None, **kw):
+        """agh_localize_depth_batch_labeled (torch CUDA tensors: agh_localize_depth_batch_labeled_device):
+        localize_depth_batch() with one sample list per object of every capture.  `labels`: per capture a list with one entry
+        per image (see label_image_records: an (H, W) uint8 array, or None for no object in that image); None passes NULL."""
+        a = self._depth_batch_labeled_args(captures, labels, workspaces, n_objects, kw)
+        fn = self.lib.agh_localize_depth_batch_labeled_device if a["on_device"] else self.lib.agh_localize_depth_batch_labeled
+        return self._batch_labeled_collect(a, caps, lambda *out: fn(self._h, a["recs"], a["mrecs"], a["n_images"], a["n_obj"], a["lps"],
+                                                                    C.c_int32(a["n_captures"]), *out))
+
+    def localize_depth_batch_labeled_begin(self, captures, labels, workspaces, n_objects, **kw):
+        """agh_localize_depth_batch_labeled_begin (torch CUDA tensors: _begin_device): the labelled depth batch's chain queued;
+        collected by localize_batch_end().  Pixel and label buffers are kept alive until then."""
+        a = self._depth_batch_labeled_args(captures, labels, workspaces, n_objects, kw)
+        fn = self.lib.agh_localize_depth_batch_labeled_begin_device if a["on_device"] else self.lib.agh_localize_depth_batch_labeled_begin
+        self._check(fn(self._h, a["recs"], a["mrecs"], a["n_images"], a["n_obj"], a["lps"], C.c_int32(a["n_captures"])))
+        self._batch_pending = a
+
+    def batch_label_counts(self, cap_lists: int = 64) -> np.ndarray:
+        """agh_get_batch_label_counts: the eligible voxels M_{k,j} of every list of the last labelled batch this context
+        collected, in list order (capture after capture, object after object)."""
+        m = np.full(max(cap_lists, 1), -1, np.int64)  # (the call writes L counts, none of them negative)
+        self._check(self.lib.agh_get_batch_label_counts(self._h, _p(m, C.c_int64), C.c_int32(cap_lists)))
+        return m[m >= 0].copy()
+
     def localize_batch_stage(self, captures):
         """agh_localize_batch_stage: the NEXT batch's host captures up on a second stream, beside the chain in flight.  Returns
         the list of arrays to hand to the next localize_batch_begin (the library recognises the set by pointers, strides and
@@ -971,7 +1072,8 @@ class Context:
             self._check(self.lib.agh_localize_batch_end(self._h, None, C.c_int64(0), None, C.c_int64(0), None, C.c_int64(0),
                                                         None, res))
             return []
-        return self._batch_collect(a, caps, lambda *out: self.lib.agh_localize_batch_end(self._h, *out))
+        collect = self._batch_labeled_collect if "groups" in a else self._batch_collect  # (a labelled batch: a list per capture)
+        return collect(a, caps, lambda *out: self.lib.agh_localize_batch_end(self._h, *out))
 
     def localize_begin(self, xyz, size_left: int, workspace, **kw):
         """agh_localize_begin: the chain of this capture queued, nothing waited for (see include/agh.h)."""

@@ -169,6 +169,8 @@ struct BatchCapture
   int32_t drawn;    // 1: drawn on the device (sample_idx NULL)
   uint64_t seed;
   double ws[6];     // its workspace (the boundary filter)
+  int32_t capture;  // the capture the list belongs to (a labelled batch has a list per object; otherwise list k is capture k) ...
+  int32_t object;   // ... and its object there (0 without labels)
 };
 
 struct Comm;  // shard.hip
@@ -344,6 +346,8 @@ struct Ctx
   int64_t label_counts[kMaxClouds] = {};  // ... and its M_j
   int32_t batch_mask_captures = 0;    // n_captures of the last chain collected if it was a masked batch, else 0
   int64_t batch_mask_counts[kMaxClouds] = {};  // ... and its M_k
+  int32_t batch_label_lists = 0;      // the lists of the last chain collected if it was a labelled batch, else 0
+  int64_t batch_label_counts[kMaxClouds] = {};  // ... and its M_{k,j}, in list order
   // agh_localize_depth* (depth.hip): a host capture's depth images, rows packed, image k at depth_image_offset(k); the NEXT
   // capture's (agh_localize_depth_stage) in the second buffer; the two change places when a staged set is adopted
   uint8_t* d_depth = nullptr;
@@ -766,6 +770,29 @@ struct BatchMaskStage
   long long* h_total = nullptr;     // pinned: C counts M_k
 };
 int sample_mask_stage_batch(Ctx* c, const BatchMaskStage& m, hipStream_t st);
+// sample_labels.hip: the sample lists of a labelled batch chain (include/agh.h, agh_localize_batch_labeled), one list per (capture,
+// object); the label buffers are the context's (the single labelled chain's, grown); the M_l go to c->h_label_counts
+struct LabelCapture  // the lists of a labelled batch, per capture: its objects and its first list among the call's
+{
+  int32_t K, first_list;
+};
+struct BatchLabelStage
+{
+  VoxBatch vb;                      // the batch's capture table, descriptors and slot size
+  int C = 0, L = 0;                 // captures; lists
+  int64_t n_max = 0, n_tot = 0, S_tot = 0;  // the largest capture's raw points; all captures'; the samples of all lists
+  double cell = 0.0;
+  const uint8_t* code = nullptr;    // the per-point codes of all captures (VoxCapture::code_off)
+  const uint8_t* const* labels = nullptr;  // device table: capture k's labels, one byte per raw point, at any byte alignment
+  const LabelCapture* lists = nullptr;  // device table, one per capture
+  const unsigned* bitmap = nullptr; // the voxel bitmap slots
+  const int* blk2 = nullptr;        // ... and their capture-local block prefixes
+  const int* cloud_off = nullptr;   // the batch's device-side cloud offsets
+  const BatchCapture* tab = nullptr;  // the chain's list table (soff, S, seed, capture, object)
+  int32_t* d_out = nullptr;         // S_tot indices into the common voxel array (or kSampleSkip), for the search
+  int32_t* h_out = nullptr;         // pinned: S_tot capture-local indices
+};
+int sample_label_stage_batch(Ctx* c, const BatchLabelStage& m, hipStream_t st);
 int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
   unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st);
 // host mirror of the handle search's results (pinned memory of the context; all nullptr / 0: none)
@@ -1394,8 +1421,9 @@ int depth_batch_check(agh::Ctx* c, const char* who, const agh_depth_image* image
 int depth_batch_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, const int32_t* n_images, int C, bool on_device,
   bool drop_staged, hipStream_t st);
 // (unit: what the chain's C lists are, "capture" or "object", for the error texts; nullptr: the one list of a single chain)
+// (names: what list k is called when it is no plain "unit k" -- "capture 2, object 5" of a labelled batch)
 int chain_collect(agh_ctx* ctx, const char* who, const char* unit, int C, const int* counts, int count_stride, int64_t S_tot,
-  const int* bad, int (*requeue)(agh_ctx*, bool handles_only));
+  const int* bad, int (*requeue)(agh_ctx*, bool handles_only), const std::vector<std::string>* names = nullptr);
 // localize_batch.hip's tail as the labelled chain of localize.hip runs it, one list per OBJECT of the one capture.
 // labeled_tail_prepare: the batch state's table of K spans of S samples (soff = j * S, the one workspace), its handle-search slots
 // and its pinned sample mirror (*h_samples), everything queued on the context's stream.  batch_queue: search -> classification ->

@@ -116,10 +116,14 @@ int stage_captures(agh_ctx* ctx, const char* who, const float* const* xyz, const
 // either on the context's stream -- then the limits.  Errors are `who`'s, and `unit` k's ("capture 3", "object 3") if the chain
 // has several lists; bad: a batch's per-capture flags of a sample index outside the capture (null: flags_to_status' text stands).
 int chain_collect(agh_ctx* ctx, const char* who, const char* unit, int C, const int* counts, int count_stride, int64_t S_tot,
-  const int* bad, int (*requeue)(agh_ctx*, bool handles_only))
+  const int* bad, int (*requeue)(agh_ctx*, bool handles_only), const std::vector<std::string>* names)
 {
   Ctx* c = &ctx->c;
-  auto of = [&](int k) { return std::string(who) + (unit ? ": " + std::string(unit) + " " + std::to_string(k) : std::string()) + ": "; };
+  auto of = [&](int k) {
+    if (names)
+      return std::string(who) + ": " + (*names)[(size_t) k] + ": ";
+    return std::string(who) + (unit ? ": " + std::string(unit) + " " + std::to_string(k) : std::string()) + ": ";
+  };
   bool handles_only = false;
   int rc;
   for (int attempt = 0;; attempt++)
@@ -526,6 +530,7 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
   c->mask_count = -1;
   c->label_objects = 0;
   c->batch_mask_captures = 0;
+  c->batch_label_lists = 0;
   const int64_t S = L.S;
   const HandlePins pin = handle_pins(c);
   const int* h_counts = pin.counts;

@@ -19,9 +19,13 @@ constexpr int kBatchCountsStride = 8;  // ints of host-side counts per capture (
 
 // one batch, from agh_localize_batch_begin to agh_localize_batch_end: the caller's arrays are copied (explicit sample lists into
 // the pinned h_samples, where lp[k].sample_idx then points), the captures themselves are read where d_raw says
+// C captures and L lists: preprocessing, grid, bound batch and raw offsets run over the captures; sample spans, the kept-hand
+// compaction, the handle search, the collection and the outputs over the lists.  Without labels L = C and list k is capture k; a
+// labelled batch has a list per (capture, object) in capture order; the labelled single chain (labeled_tail_prepare) is C = 1.
 struct BatchCall
 {
-  int C = 0;
+  int C = 0, L = 0;
+  std::vector<int> list_cap, list_obj;  // L: list l's capture and its object there
   std::vector<const float*> d_raw;
   std::vector<int64_t> dev_stride, n, soff, raw_off;  // raw_off: each capture's first point among all the batch's
   std::vector<agh_localize_params> lp;
@@ -32,6 +36,11 @@ struct BatchCall
   // state's d_mask at raw_off[k], or in the caller's device memory
   bool masked = false;
   std::vector<const uint8_t*> d_mask;
+  // agh_localize_batch_labeled*: the bytes there are labels 1 .. n_objects[k]; first_list: the exclusive prefix sum of n_objects
+  bool labeled = false;
+  std::vector<int32_t> n_objects, first_list;
+  // the chain's name in the texts of the errors found behind a synchronisation
+  const char* who() const { return labeled ? "agh_localize_batch_labeled" : "agh_localize_batch"; }
 };
 
 struct LocalizeBatchState
@@ -74,6 +83,10 @@ struct LocalizeBatchState
   long long* h_mtotal = nullptr;      // pinned, written by the chain
   int32_t* d_elist = nullptr;         // the E_k, capture k's at raw_off[k]
   int64_t elist_cap = 0;
+  // label images (sample_labels.hip, sample_label_stage_batch), made by the first labelled batch; the labels travel as masks do
+  // (d_mask, d_mptr), the stage's own buffers are the context's
+  LabelCapture* d_lcap = nullptr;     // kMaxClouds
+  LabelCapture* h_lcap = nullptr;     // pinned
 };
 
 void localize_batch_release(Ctx* c)
@@ -82,11 +95,11 @@ void localize_batch_release(Ctx* c)
   if (!b)
     return;
   void* dev[] = { b->d_tab, b->d_local, b->d.hands, b->d.bits, b->d.rowcnt, b->d.first, b->d.n, b->d.idx, b->d.counts, b->d.tmp,
-    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2, b->d_mask, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist };
+    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2, b->d_mask, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist, b->d_lcap };
   for (void* p : dev)
     if (p)
       (void) hipFree(p);
-  void* host[] = { b->h_tab, b->h_samples, b->h_counts, b->h_bad, b->h_desc, b->h_hands, b->h_handles, b->h_idx, b->h_vcap, b->h_mptr, b->h_mtotal };
+  void* host[] = { b->h_tab, b->h_samples, b->h_counts, b->h_bad, b->h_desc, b->h_hands, b->h_handles, b->h_idx, b->h_vcap, b->h_mptr, b->h_mtotal, b->h_lcap };
   for (void* p : host)
     if (p)
       (void) hipHostFree(p);
@@ -314,6 +327,42 @@ int ensure_mask_slots(Ctx* c, LocalizeBatchState* b, int64_t n_tot)
   return AGH_OK;
 }
 
+// a labelled batch's tables: where each capture's labels lie, and its lists
+int ensure_label_tables(Ctx* c, LocalizeBatchState* b)
+{
+  int rc;
+  if ((!b->d_mptr || !b->h_mptr) &&
+      ((rc = dev_alloc(c, &b->d_mptr, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_mptr, (size_t) kMaxClouds))))
+    return rc;
+  if ((!b->d_lcap || !b->h_lcap) &&
+      ((rc = dev_alloc(c, &b->d_lcap, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_lcap, (size_t) kMaxClouds))))
+    return rc;
+  return AGH_OK;
+}
+
+// The list table of the call, on the host and queued to the device: list l's span of the sample list, its capture's sample
+// count, seed and workspace (B.lp[list_cap[l]]), and which object of it the list is.
+int fill_list_table(Ctx* c, LocalizeBatchState* b, hipStream_t st)
+{
+  const BatchCall& B = b->call;
+  for (int l = 0; l < B.L; l++)
+  {
+    const agh_localize_params& p = B.lp[(size_t) B.list_cap[l]];
+    BatchCapture& t = b->h_tab[l];
+    t.soff = B.soff[l];
+    t.S = (int32_t) p.n_samples;
+    t.drawn = p.sample_idx ? 0 : 1;  // (a masked or labelled chain has no explicit list)
+    t.seed = p.sample_seed;
+    for (int q = 0; q < 6; q++)
+      t.ws[q] = p.workspace[q];
+    t.capture = B.list_cap[l];
+    t.object = B.list_obj[l];
+    b->h_bad[l] = 0;
+  }
+  AGH_HIPCHK(c, hipMemcpyAsync(b->d_tab, b->h_tab, sizeof(BatchCapture) * (size_t) B.L, hipMemcpyHostToDevice, st));
+  return AGH_OK;
+}
+
 }  // namespace
 
 // search -> classification -> per-capture compaction -> handle search, queued (handles_only: the handle search once more); the
@@ -324,7 +373,7 @@ int batch_queue(agh_ctx* ctx, bool handles_only)
   LocalizeBatchState* b = c->lbatch;
   const BatchCall& B = b->call;
   hipStream_t st = c->stream;
-  const int C = B.C;
+  const int C = B.L;  // (the lists)
   int rc;
   for (int k = 0; k < C; k++)
     for (int q = 0; q < (handles_only ? 4 : kBatchCountsStride); q++)
@@ -387,7 +436,57 @@ struct BatchMaskSource
   const agh_sample_mask* images;  // depth form: one per image of the flat array
   bool on_device;
   const char* who;
+  const int32_t* n_objects = nullptr;  // agh_localize_batch_labeled*: the bytes are labels 1 .. n_objects[k] (NULL: masks)
+  bool labeled = false;
 };
+
+// the rules a labelled batch adds (include/agh.h, agh_localize_batch_labeled*, 1 and 2); the text names the capture (and the image)
+int batch_label_check(Ctx* c, const BatchMaskSource* mask, const DepthBatchSource* depth, const agh_localize_params* lp, int C)
+{
+  auto bad = [&](const std::string& what) {
+    c->err = std::string(mask->who) + ": " + what;
+    return AGH_ERR_INVALID_ARGUMENT;
+  };
+  if (!mask->n_objects)
+    return bad("n_objects is NULL");
+  if (depth ? !mask->images : !mask->points)
+    return bad("labels is NULL (every capture of a labelled batch has labels)");
+  int64_t lists = 0, samples = 0;
+  for (int k = 0, i0 = 0; k < C; k++)
+  {
+    const std::string cap = "capture " + std::to_string(k);
+    if (mask->n_objects[k] < 1 || mask->n_objects[k] > kMaxClouds)
+      return bad(cap + ": n_objects must be 1 .. 64");
+    lists += mask->n_objects[k];
+    samples += (int64_t) mask->n_objects[k] * lp[k].n_samples;
+    if (lists > kMaxClouds)
+      return bad(cap + ": more than 64 lists in all (the sum of n_objects up to this capture)");
+    if (samples > (1 << 24))
+      return bad(cap + ": more than 2^24 samples in all (the sum of n_objects x n_samples up to this capture)");
+    if (lp[k].sample_idx)
+      return bad(cap + ": labels together with sample_idx (an explicit list needs no labels)");
+    if (!depth)
+    {
+      if (!mask->points[k])
+        return bad(cap + ": the label array is NULL");
+      continue;
+    }
+    bool any = false;
+    for (int j = 0; j < depth->n_images[k]; j++)
+    {
+      const agh_sample_mask& m = mask->images[i0 + j];
+      if (!m.data)
+        continue;
+      any = true;
+      if (m.row_stride_bytes < depth->images[i0 + j].width)
+        return bad(cap + ", image " + std::to_string(j) + ": the label image's row_stride_bytes is below the image's width");
+    }
+    if (!any)
+      return bad(cap + ": every label image's data is NULL (no pixel would belong to an object)");
+    i0 += depth->n_images[k];
+  }
+  return AGH_OK;
+}
 
 // the rules a masked batch adds to its unmasked twin's; the text names the capture (and the image)
 int batch_mask_check(Ctx* c, const BatchMaskSource* mask, const DepthBatchSource* depth, const agh_localize_params* lp, int C)
@@ -431,7 +530,7 @@ int batch_masks_to_device(Ctx* c, LocalizeBatchState* b, const BatchMaskSource* 
 {
   BatchCall& B = b->call;
   const int C = B.C;
-  B.masked = true;
+  B.masked = !mask->labeled;
   B.d_mask.resize((size_t) C);
   if (!depth && mask->on_device)
   {
@@ -549,7 +648,7 @@ int batch_pass(agh_ctx* ctx)
     {
       if (b->h_desc[k].error)
       {
-        c->err = "agh_localize_batch: capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
+        c->err = std::string(B.who()) + ": capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
                  "(1 GiB bitmap): set a workspace that bounds the scene";
         return chain_fail(c, AGH_ERR_CAPACITY);
       }
@@ -591,7 +690,7 @@ int batch_pass(agh_ctx* ctx)
   }
   if ((rc = ensure_batch_samples(c, b, S_tot)) != AGH_OK)
     return chain_fail(c, rc);
-  if ((rc = ensure_batch_slots(c, b, C, B.slot)) != AGH_OK)
+  if ((rc = ensure_batch_slots(c, b, B.L, B.slot)) != AGH_OK)
     return chain_fail(c, rc);
   if (B.classify)
   {
@@ -599,16 +698,7 @@ int batch_pass(agh_ctx* ctx)
   }
   bool any_explicit = false;
   for (int k = 0; k < C; k++)
-  {
-    BatchCapture& t = b->h_tab[k];
-    t.soff = B.soff[k];
-    t.S = (int32_t) lp[k].n_samples;
-    t.drawn = lp[k].sample_idx ? 0 : 1;  // (a masked batch has no explicit list)
-    t.seed = lp[k].sample_seed;
-    for (int q = 0; q < 6; q++)
-      t.ws[q] = lp[k].workspace[q];
-    b->h_bad[k] = 0;
-    if (lp[k].sample_idx && lp[k].n_samples > 0)
+    if (lp[k].sample_idx && lp[k].n_samples > 0)  // (never with masks or labels: list k is capture k)
     {
       any_explicit = true;
       // (the caller's list is copied once: from here on the record names the pinned copy, which a repeat of the batch reads)
@@ -616,8 +706,8 @@ int batch_pass(agh_ctx* ctx)
         std::memcpy(b->h_samples + B.soff[k], lp[k].sample_idx, sizeof(int32_t) * (size_t) lp[k].n_samples);
       lp[k].sample_idx = b->h_samples + B.soff[k];
     }
-  }
-  AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_tab, b->h_tab, sizeof(BatchCapture) * (size_t) C, hipMemcpyHostToDevice, st), chain_fail(c, AGH_ERR_HIP));
+  if ((rc = fill_list_table(c, b, st)) != AGH_OK)
+    return chain_fail(c, rc);
   if (any_explicit)
   {
     AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_local, b->h_samples, sizeof(int32_t) * (size_t) S_tot, hipMemcpyHostToDevice, st),
@@ -651,6 +741,39 @@ int batch_pass(agh_ctx* ctx)
     m.h_out = b->h_samples;
     m.h_total = b->h_mtotal;
     if ((rc = sample_mask_stage_batch(c, m, st)) != AGH_OK)
+      return chain_fail(c, rc);
+  }
+  else if (B.labeled)  // (for S_tot = 0 too, as the masks')
+  {
+    if ((rc = ensure_label_tables(c, b)) != AGH_OK)
+      return chain_fail(c, rc);
+    for (int k = 0; k < C; k++)
+    {
+      b->h_mptr[k] = B.d_mask[k];
+      b->h_lcap[k] = LabelCapture{ B.n_objects[k], B.first_list[k] };
+    }
+    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_mptr, b->h_mptr, sizeof(const uint8_t*) * (size_t) C, hipMemcpyHostToDevice, st),
+      chain_fail(c, AGH_ERR_HIP));
+    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_lcap, b->h_lcap, sizeof(LabelCapture) * (size_t) C, hipMemcpyHostToDevice, st),
+      chain_fail(c, AGH_ERR_HIP));
+    BatchLabelStage m;
+    m.vb = vb;
+    m.C = C;
+    m.L = B.L;
+    m.n_max = n_max;
+    m.n_tot = n_tot;
+    m.S_tot = S_tot;
+    m.cell = cell;
+    m.code = c->d_vox_code;
+    m.labels = b->d_mptr;
+    m.lists = b->d_lcap;
+    m.bitmap = b->d_bitmap;
+    m.blk2 = b->d_blk2;
+    m.cloud_off = c->d_cloud_off;
+    m.tab = b->d_tab;
+    m.d_out = c->d_idx_own;
+    m.h_out = b->h_samples;
+    if ((rc = sample_label_stage_batch(c, m, st)) != AGH_OK)
       return chain_fail(c, rc);
   }
   else if (S_tot > 0)
@@ -728,6 +851,15 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     n_tot += n[k];
     S_tot += p.n_samples;
   }
+  const bool labeled = mask && mask->labeled;
+  if (labeled)  // (before the sums' limits: a labelled batch counts its samples per list, and says which capture went too far)
+  {
+    if (int rc = batch_label_check(c, mask, depth, lp, C))
+      return rc;
+    S_tot = 0;
+    for (int k = 0; k < C; k++)
+      S_tot += (int64_t) mask->n_objects[k] * lp[k].n_samples;
+  }
   if (n_tot >= (1ll << 30) || S_tot > (1 << 24))
   {
     c->err = who + ": need fewer than 2^30 raw points and at most 2^24 samples in all";
@@ -741,7 +873,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   if (cam_table_mismatch(c, who.c_str(), C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
     return AGH_ERR_INVALID_ARGUMENT;                    // the table stays the context's until agh_localize_batch_end: the setter
                                                         // refuses mid-chain, so the repeats search with it too)
-  if (mask)
+  if (mask && !labeled)
     if (int rc = batch_mask_check(c, mask, depth, lp, C))
       return rc;
   double x1 = 0.0, x2 = 0.0;
@@ -769,10 +901,26 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   B.raw_off.resize(C);
   for (int k = 0, o = 0; k < C; o += (int) n[k], k++)
     B.raw_off[k] = o;
-  B.soff.resize(C + 1);
-  B.soff[0] = 0;
   for (int k = 0; k < C; k++)
-    B.soff[k + 1] = B.soff[k] + lp[k].n_samples;
+  {
+    const int K = labeled ? mask->n_objects[k] : 1;
+    if (labeled)
+    {
+      B.n_objects.push_back(K);
+      B.first_list.push_back((int32_t) B.list_cap.size());
+    }
+    for (int j = 0; j < K; j++)
+    {
+      B.list_cap.push_back(k);
+      B.list_obj.push_back(j);
+    }
+  }
+  B.L = (int) B.list_cap.size();
+  B.labeled = labeled;
+  B.soff.resize((size_t) B.L + 1);
+  B.soff[0] = 0;
+  for (int l = 0; l < B.L; l++)
+    B.soff[l + 1] = B.soff[l] + lp[B.list_cap[l]].n_samples;
   B.S_tot = S_tot;
   B.n_tot = n_tot;
   B.classify = lp[0].classify != 0;
@@ -864,6 +1012,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   c->mask_count = -1;  // (agh_get_sample_mask_count: the last chain collected had no mask)
   c->label_objects = 0;  // (... and no label image)
   c->batch_mask_captures = 0;  // (agh_get_batch_mask_counts: set below, behind the synchronisation, if this batch is masked)
+  c->batch_label_lists = 0;    // (agh_get_batch_label_counts likewise, if it is labelled)
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)
@@ -881,7 +1030,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
       if (h.error == 1)
       {
         drop_bound_cloud(c);
-        c->err = "agh_localize_batch: capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
+        c->err = std::string(B.who()) + ": capture " + std::to_string(k) + ": the voxel lattice of the kept points exceeds 2^33 cells "
                  "(1 GiB bitmap): set a workspace that bounds the scene";
         return AGH_ERR_CAPACITY;
       }
@@ -893,7 +1042,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
       drop_bound_cloud(c);
       if (pass > 0)
       {
-        c->err = "agh_localize_batch: the voxel bitmap sized from the batch's lattices did not hold them";
+        c->err = std::string(B.who()) + ": the voxel bitmap sized from the batch's lattices did not hold them";
         return AGH_ERR_CAPACITY;
       }
       b->slot_words = std::min<int64_t>(((words + words / 4) / 4096 + 1) * 4096, (int64_t) kVoxMaxWords);
@@ -908,19 +1057,24 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
       c->batch_mask_counts[k] = (int64_t) b->h_mtotal[k];
     c->batch_mask_captures = C;
   }
-  // the bound batch is now the true one
-  std::vector<int64_t> voff(C + 1, 0), nv(C);
-  for (int k = 0; k < C; k++)
+  if (B.labeled)
   {
-    nv[k] = (int64_t) (b->h_desc[k].n_vox[0] + b->h_desc[k].n_vox[1]);
-    voff[k + 1] = voff[k] + nv[k];
+    for (int l = 0; l < B.L; l++)
+      c->batch_label_counts[l] = (int64_t) c->h_label_counts[l];
+    c->batch_label_lists = B.L;
   }
+  // the bound batch is now the true one
+  std::vector<int64_t> voff(C + 1, 0), nv((size_t) B.L);
+  for (int k = 0; k < C; k++)
+    voff[k + 1] = voff[k] + (int64_t) (b->h_desc[k].n_vox[0] + b->h_desc[k].n_vox[1]);
+  for (int l = 0; l < B.L; l++)  // (a list's voxel count is its capture's)
+    nv[l] = voff[B.list_cap[l] + 1] - voff[B.list_cap[l]];
   c->n_is_bound = false;
   c->n = voff[C];
   c->cloud_off = voff;
   c->cloud_off_on_device = true;
   c->n_clouds = C;
-  return batch_collect(ctx, "agh_localize_batch", "capture", nv.data(), handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+  return batch_collect(ctx, B.who(), "capture", nv.data(), handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
     hands_cap, samples_out, results);
 }
 
@@ -940,7 +1094,18 @@ int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int6
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
-  zero_results(results, n_captures);
+  {
+    // (a labelled batch has a record per list; arguments that do not say how many lists there are get none zeroed)
+    int64_t lists = n_captures;
+    if (mask && mask->labeled)
+    {
+      lists = 0;
+      if (mask->n_objects && n_captures >= 1 && n_captures <= kMaxClouds)
+        for (int k = 0; k < n_captures && lists <= kMaxClouds; k++)
+          lists = mask->n_objects[k] >= 1 && mask->n_objects[k] <= kMaxClouds ? lists + mask->n_objects[k] : kMaxClouds + 1;
+    }
+    zero_results(results, lists <= kMaxClouds ? (int) lists : 0);
+  }
   if (c->loc.active)
   {
     c->err = std::string(mask ? mask->who : (depth ? depth->who : "agh_localize_batch")) + ": a localize chain is in flight on this context (agh_localize_end first)";
@@ -967,11 +1132,15 @@ int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t
   Ctx* c = &ctx->c;
   LocalizeBatchState* b = c->lbatch;
   const BatchCall& B = b->call;
-  const int C = B.C;
+  const int C = B.L;  // (the lists)
   const int64_t S_tot = B.S_tot;
   int rc;
   const int* hc = b->h_counts;
-  if ((rc = chain_collect(ctx, who, unit, C, hc, kBatchCountsStride, S_tot, b->h_bad, batch_queue)) != AGH_OK)
+  std::vector<std::string> names;
+  if (B.labeled)
+    for (int l = 0; l < C; l++)
+      names.push_back("capture " + std::to_string(B.list_cap[l]) + ", object " + std::to_string(B.list_obj[l]));
+  if ((rc = chain_collect(ctx, who, unit, C, hc, kBatchCountsStride, S_tot, b->h_bad, batch_queue, B.labeled ? &names : nullptr)) != AGH_OK)
     return rc;
   int64_t n_hyp_tot = 0, tot_handles = 0, tot_idx = 0, tot_hands = 0;
   for (int k = 0; k < C; k++)
@@ -1023,7 +1192,11 @@ int labeled_tail_prepare(agh_ctx* ctx, int K, int64_t S, const agh_localize_para
   LocalizeBatchState* b = c->lbatch;
   BatchCall& B = b->call;
   B = BatchCall();
-  B.C = K;
+  B.C = 1;
+  B.L = K;
+  B.list_cap.assign((size_t) K, 0);
+  for (int j = 0; j < K; j++)
+    B.list_obj.push_back(j);
   B.x1 = x1;
   B.x2 = x2;
   B.lp.assign(1, *lp);
@@ -1037,18 +1210,8 @@ int labeled_tail_prepare(agh_ctx* ctx, int K, int64_t S, const agh_localize_para
   B.slot = std::min<int64_t>(8 * S, 8192);
   if ((rc = ensure_batch_samples(c, b, B.S_tot)) != AGH_OK || (rc = ensure_batch_slots(c, b, K, B.slot)) != AGH_OK)
     return rc;
-  for (int j = 0; j < K; j++)
-  {
-    BatchCapture& t = b->h_tab[j];
-    t.soff = B.soff[j];
-    t.S = (int32_t) S;
-    t.drawn = 1;
-    t.seed = lp->sample_seed;
-    for (int q = 0; q < 6; q++)
-      t.ws[q] = lp->workspace[q];
-    b->h_bad[j] = 0;
-  }
-  AGH_HIPCHK(c, hipMemcpyAsync(b->d_tab, b->h_tab, sizeof(BatchCapture) * (size_t) K, hipMemcpyHostToDevice, c->stream));
+  if ((rc = fill_list_table(c, b, c->stream)) != AGH_OK)
+    return rc;
   *h_samples = b->h_samples;
   return AGH_OK;
 }
@@ -1226,6 +1389,113 @@ int agh_get_batch_mask_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_cap
   return AGH_OK;
 }
 
+// ---- the labelled forms (include/agh.h): the batch chains with one list per object of every capture's label image ----
+
+int agh_localize_batch_labeled(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const BatchMaskSource m{ labels, nullptr, false, "agh_localize_batch_labeled", n_objects, true };
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, nullptr, &m);
+}
+
+int agh_localize_batch_labeled_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const BatchMaskSource m{ labels, nullptr, true, "agh_localize_batch_labeled_device", n_objects, true };
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, nullptr, &m);
+}
+
+int agh_localize_batch_labeled_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const BatchMaskSource m{ labels, nullptr, false, "agh_localize_batch_labeled_begin", n_objects, true };
+  return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, nullptr, &m);
+}
+
+int agh_localize_batch_labeled_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const BatchMaskSource m{ labels, nullptr, true, "agh_localize_batch_labeled_begin_device", n_objects, true };
+  return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, nullptr, &m);
+}
+
+// (a label image is read as a sample mask whose bytes are labels: the layouts are asserted equal in localize.hip)
+static const agh_sample_mask* as_masks(const agh_label_image* labels) { return reinterpret_cast<const agh_sample_mask*>(labels); }
+static_assert(sizeof(agh_label_image) == sizeof(agh_sample_mask), "a label image is read as a sample mask whose bytes are labels");
+
+int agh_localize_depth_batch_labeled(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
+  const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_labeled" };
+  const BatchMaskSource m{ nullptr, as_masks(labels), false, src.who, n_objects, true };
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src, &m);
+}
+
+int agh_localize_depth_batch_labeled_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
+  const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_labeled_device" };
+  const BatchMaskSource m{ nullptr, as_masks(labels), true, src.who, n_objects, true };
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src, &m);
+}
+
+int agh_localize_depth_batch_labeled_begin(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
+  const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_labeled_begin" };
+  const BatchMaskSource m{ nullptr, as_masks(labels), false, src.who, n_objects, true };
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+}
+
+int agh_localize_depth_batch_labeled_begin_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
+  const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_labeled_begin_device" };
+  const BatchMaskSource m{ nullptr, as_masks(labels), true, src.who, n_objects, true };
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+}
+
+int agh_get_batch_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_lists)
+{
+  if (!ctx || !n_eligible)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_batch_label_counts"))
+    return AGH_ERR_STATE;
+  if (c->batch_label_lists < 1)
+  {
+    c->err = "agh_get_batch_label_counts: the last chain this context collected was no labelled batch (or there was none)";
+    return AGH_ERR_STATE;
+  }
+  if (cap_lists < c->batch_label_lists)
+  {
+    c->err = "agh_get_batch_label_counts: cap_lists is below the call's number of lists";
+    return AGH_ERR_CAPACITY;
+  }
+  std::copy(c->batch_label_counts, c->batch_label_counts + c->batch_label_lists, n_eligible);
+  return AGH_OK;
+}
+
 // The NEXT batch's captures up, beside whatever runs on the context's stream (stage_captures, localize.hip).  A pinned source must
 // stay valid until the agh_localize_batch_end of the chain that adopts (or drops) the set.
 int agh_localize_batch_stage(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n, int32_t n_captures)
@@ -1269,7 +1539,7 @@ int agh_localize_batch_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle
                            : "agh_localize_batch_end: no agh_localize_batch_begin in flight";
     return AGH_ERR_STATE;
   }
-  zero_results(results, c->lbatch->call.C);
+  zero_results(results, c->lbatch->call.L);
   if (bad_outputs(handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap))
   {
     // (the chain is queued: drain it, leave the context as a failed call does)

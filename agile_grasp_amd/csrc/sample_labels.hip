@@ -14,6 +14,12 @@
 // The lists share one buffer of n entries (a raw point adds at most one (voxel, object) pair), object after object.  Launches are
 // sized from the raw point count; the voxel count is read on the device.  Everything is queued on the chain's stream behind the
 // voxeliser: no synchronisation is added.
+//
+// The batch forms (include/agh.h, agh_localize_batch_labeled*; DESIGN.md, "Label images in the batch chains") run the same steps
+// once for all captures, capture = blockIdx.y as in vox_batch: k_vox_word_rank_batch over the bitmap slots, k_label_mark_batch
+// into one object set per voxel of the COMMON voxel array (bit j = the capture-local object: a voxel belongs to one capture),
+// k_label_count_batch / k_label_scan / k_label_emit_batch with one row of group counts per LIST (capture k's object j is list
+// first_list[k] + j), and k_batch_samples_labeled.  Capture k's lists lie inside [raw_off[k], raw_off[k] + n[k]) of the one buffer.
 #include "agh_internal.h"
 
 #include <algorithm>
@@ -25,12 +31,9 @@ constexpr int kLabelWordsPerBlock = 4096;  // voxelize.hip's kWordsPerBlock: 16 
 constexpr int kLabelGroup = 256;           // voxels per work-group of count / emit: four waves
 
 // One work-group per block of 4096 bitmap words, a thread holding its 16: rank[w] = the voxel bits of the block in front of w.
-__global__ __launch_bounds__(256) void k_vox_word_rank(const unsigned* __restrict__ vox, const VoxDesc* __restrict__ d,
-  unsigned* __restrict__ rank)
+// (the block of 4096 words at w0 - 16 * threadIdx.x; the whole work-group comes here)
+__device__ __forceinline__ void vox_word_rank_block(const unsigned* __restrict__ vox, unsigned* __restrict__ rank, size_t w0)
 {
-  if (d->error || (unsigned long long) blockIdx.x >= d->n_words / kLabelWordsPerBlock)
-    return;
-  const size_t w0 = (size_t) blockIdx.x * kLabelWordsPerBlock + (size_t) threadIdx.x * 16;
   unsigned v[16];
   const uint4* vs = reinterpret_cast<const uint4*>(vox + w0);
   int cnt = 0;
@@ -65,9 +68,29 @@ __global__ __launch_bounds__(256) void k_vox_word_rank(const unsigned* __restric
     rs[k] = make_uint4(out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]);
 }
 
+__global__ __launch_bounds__(256) void k_vox_word_rank(const unsigned* __restrict__ vox, const VoxDesc* __restrict__ d,
+  unsigned* __restrict__ rank)
+{
+  if (d->error || (unsigned long long) blockIdx.x >= d->n_words / kLabelWordsPerBlock)
+    return;
+  vox_word_rank_block(vox, rank, (size_t) blockIdx.x * kLabelWordsPerBlock + (size_t) threadIdx.x * 16);
+}
+
+// ... and over the bitmap slots of a batch, slot blockIdx.y (VoxBatch::slot_words words, a multiple of the block): the ranks are
+// inside the block, so they go with the capture-local block prefixes of vox_batch (d_blk2) as they are
+__global__ __launch_bounds__(256) void k_vox_word_rank_batch(VoxBatch vb, const unsigned* __restrict__ vox, unsigned* __restrict__ rank)
+{
+  const VoxDesc* d = vb.desc + blockIdx.y;
+  if (d->error || (unsigned long long) blockIdx.x * kLabelWordsPerBlock >= d->n_words)  // (the slot beyond the lattice holds no bit)
+    return;
+  vox_word_rank_block(vox, rank,
+    (size_t) blockIdx.y * (size_t) vb.slot_words + (size_t) blockIdx.x * kLabelWordsPerBlock + (size_t) threadIdx.x * 16);
+}
+
 // Raw point i with label 1..K and code[i] != 0: its object's bit into the set of its voxel.  A thread takes the four label bytes
-// of one ALIGNED 32-bit word, the words that straddle either end a byte at a time (k_mask_mark, sample_mask.hip).
-__global__ __launch_bounds__(256) void k_label_mark(const float* __restrict__ xyz, int64_t stride, int64_t n,
+// of one ALIGNED 32-bit word, the words that straddle either end a byte at a time (k_mask_mark, sample_mask.hip).  vox, rank: the
+// cloud's bitmap (slot); vox_prefix: its block prefixes; objset: the sets of ITS voxels.
+__device__ __forceinline__ void label_mark_points(const float* __restrict__ xyz, int64_t stride, int64_t n,
   const uint8_t* __restrict__ code, const uint8_t* __restrict__ labels, int K, const VoxDesc* __restrict__ d, double cell,
   const unsigned* __restrict__ vox, const int* __restrict__ vox_prefix, const unsigned* __restrict__ rank,
   unsigned long long* __restrict__ objset)
@@ -104,6 +127,30 @@ __global__ __launch_bounds__(256) void k_label_mark(const float* __restrict__ xy
   }
 }
 
+__global__ __launch_bounds__(256) void k_label_mark(const float* __restrict__ xyz, int64_t stride, int64_t n,
+  const uint8_t* __restrict__ code, const uint8_t* __restrict__ labels, int K, const VoxDesc* __restrict__ d, double cell,
+  const unsigned* __restrict__ vox, const int* __restrict__ vox_prefix, const unsigned* __restrict__ rank,
+  unsigned long long* __restrict__ objset)
+{
+  label_mark_points(xyz, stride, n, code, labels, K, d, cell, vox, vox_prefix, rank, objset);
+}
+
+// k_label_mark's loop for capture blockIdx.y: its points, codes (code_off), labels (a table of pointers, any byte alignment --
+// the straddling words are the capture's own, see k_mask_mark_batch), bitmap slot and block prefixes; its voxels' sets start at
+// cloud_off[capture] of the common array, which lies at or below the capture's first raw point: a voxel index below the
+// capture's n stays inside the array's one entry per raw point.
+__global__ __launch_bounds__(256) void k_label_mark_batch(VoxBatch vb, const uint8_t* __restrict__ code,
+  const uint8_t* const* __restrict__ labels, const LabelCapture* __restrict__ lc, double cell, const unsigned* __restrict__ vox,
+  const int* __restrict__ vox_prefix, const unsigned* __restrict__ rank, const int* __restrict__ cloud_off,
+  unsigned long long* __restrict__ objset)
+{
+  const VoxCapture* q = vb.cap + blockIdx.y;
+  const int64_t slot0 = (int64_t) blockIdx.y * vb.slot_words;
+  // (a capture whose descriptor carries an error has no voxels: label_mark_points returns at once)
+  label_mark_points(q->xyz, q->stride, q->n, code + q->code_off, labels[blockIdx.y], lc[blockIdx.y].K, vb.desc + blockIdx.y, cell,
+    vox + slot0, vox_prefix + slot0 / kLabelWordsPerBlock, rank + slot0, objset + cloud_off[blockIdx.y]);
+}
+
 // The voxels of the cloud (device side; none after a voxeliser's error, whose repeat runs this stage again).
 __device__ __forceinline__ int64_t label_voxels(const VoxDesc* d, int64_t n)
 {
@@ -126,16 +173,17 @@ __device__ __forceinline__ void label_wave_objects(unsigned long long set, F f)
   }
 }
 
-// counts[j * n_groups + g]: the voxels of work-group g (256 voxel indices) that are eligible for object j.
-__global__ __launch_bounds__(kLabelGroup) void k_label_count(const unsigned long long* __restrict__ objset,
-  const VoxDesc* __restrict__ d, int64_t n, int K, int64_t n_groups, int* __restrict__ counts)
+// counts[j * n_groups + g]: the voxels of work-group g (256 voxel indices) that are eligible for object j.  (The whole
+// work-group comes here; objset: the sets of the cloud's nv voxels.)
+__device__ __forceinline__ void label_count_group(const unsigned long long* __restrict__ objset, int64_t nv, int K, int64_t n_groups,
+  int* __restrict__ counts)
 {
   __shared__ int cnt[4][64];
   const int tid = threadIdx.x, wave = tid >> 6;
   cnt[wave][tid & 63] = 0;
   __syncthreads();
   const int64_t v = (int64_t) blockIdx.x * kLabelGroup + tid;
-  const unsigned long long set = v < label_voxels(d, n) ? objset[v] : 0ull;
+  const unsigned long long set = v < nv ? objset[v] : 0ull;
   label_wave_objects(set, [&](int j, unsigned long long ballot) {
     if ((tid & 63) == 0)
       cnt[wave][j] = __popcll(ballot);
@@ -143,6 +191,22 @@ __global__ __launch_bounds__(kLabelGroup) void k_label_count(const unsigned long
   __syncthreads();
   if (tid < K)
     counts[(int64_t) tid * n_groups + blockIdx.x] = cnt[0][tid] + cnt[1][tid] + cnt[2][tid] + cnt[3][tid];
+}
+
+__global__ __launch_bounds__(kLabelGroup) void k_label_count(const unsigned long long* __restrict__ objset,
+  const VoxDesc* __restrict__ d, int64_t n, int K, int64_t n_groups, int* __restrict__ counts)
+{
+  label_count_group(objset, label_voxels(d, n), K, n_groups, counts);
+}
+
+// ... for capture blockIdx.y of a batch: its voxels' sets at cloud_off, its objects' rows first_list .. first_list + K - 1 of the
+// call's L rows.  n_groups is sized for the largest capture, so every row is written whole.
+__global__ __launch_bounds__(kLabelGroup) void k_label_count_batch(VoxBatch vb, const unsigned long long* __restrict__ objset,
+  const LabelCapture* __restrict__ lc, const int* __restrict__ cloud_off, int64_t n_groups, int* __restrict__ counts)
+{
+  const int64_t nv = label_voxels(vb.desc + blockIdx.y, vb.cap[blockIdx.y].n);  // (0 for a capture with an error)
+  label_count_group(objset + cloud_off[blockIdx.y], nv, lc[blockIdx.y].K, n_groups,
+    counts + (int64_t) lc[blockIdx.y].first_list * n_groups);
 }
 
 // One wave per object: its work-groups' counts become their exclusive scan, in place; the sum is M_j.
@@ -182,14 +246,13 @@ __device__ __forceinline__ void label_bases(const long long* __restrict__ totals
   }
 }
 
-// E[base_j + the work-group's offset + the waves in front + the lanes in front] = the voxel index: ascending per object.
-__global__ __launch_bounds__(kLabelGroup) void k_label_emit(const unsigned long long* __restrict__ objset,
-  const VoxDesc* __restrict__ d, int64_t n, int K, int64_t n_groups, const int* __restrict__ offsets,
-  const long long* __restrict__ totals, int32_t* __restrict__ E)
+// E[base_j + the work-group's offset + the waves in front + the lanes in front] = the voxel index: ascending per object.  (The
+// whole work-group comes here; objset, offsets, totals, E: the cloud's own, E with room for `room` entries.)
+__device__ __forceinline__ void label_emit_group(const unsigned long long* __restrict__ objset, int64_t nv, int64_t room, int K,
+  int64_t n_groups, const int* __restrict__ offsets, const long long* __restrict__ totals, int32_t* __restrict__ E)
 {
   __shared__ int cnt[4][64];
   __shared__ long long base[64];
-  const int64_t nv = label_voxels(d, n);
   if ((int64_t) blockIdx.x * kLabelGroup >= nv)  // (uniform over the work-group)
     return;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -209,9 +272,28 @@ __global__ __launch_bounds__(kLabelGroup) void k_label_emit(const unsigned long 
     int64_t at = base[j] + offsets[(int64_t) j * n_groups + blockIdx.x] + __popcll(ballot & ((1ull << lane) - 1ull));
     for (int q = 0; q < wave; q++)
       at += cnt[q][j];
-    if (at < n)  // (the pairs are at most the raw points: always)
+    if (at < room)  // (the pairs are at most the raw points: always)
       E[at] = (int32_t) v;
   });
+}
+
+__global__ __launch_bounds__(kLabelGroup) void k_label_emit(const unsigned long long* __restrict__ objset,
+  const VoxDesc* __restrict__ d, int64_t n, int K, int64_t n_groups, const int* __restrict__ offsets,
+  const long long* __restrict__ totals, int32_t* __restrict__ E)
+{
+  label_emit_group(objset, label_voxels(d, n), n, K, n_groups, offsets, totals, E);
+}
+
+// ... for capture blockIdx.y of a batch: the indices written are capture-local, its lists start at its code_off of the common
+// buffer, object after object, and hold at most its n entries
+__global__ __launch_bounds__(kLabelGroup) void k_label_emit_batch(VoxBatch vb, const unsigned long long* __restrict__ objset,
+  const LabelCapture* __restrict__ lc, const int* __restrict__ cloud_off, int64_t n_groups, const int* __restrict__ offsets,
+  const long long* __restrict__ totals, int32_t* __restrict__ E)
+{
+  const VoxCapture* q = vb.cap + blockIdx.y;
+  const int first = lc[blockIdx.y].first_list;
+  label_emit_group(objset + cloud_off[blockIdx.y], label_voxels(vb.desc + blockIdx.y, q->n), q->n, lc[blockIdx.y].K, n_groups,
+    offsets + (int64_t) first * n_groups, totals + first, E + q->code_off);
 }
 
 // Sample k of object j: position j * S + k of the call's list.  E_j[draw_stratum(M_j, S, k, seed)], and with M_j < S the list
@@ -235,13 +317,40 @@ __global__ __launch_bounds__(256) void k_draw_samples_labeled(const int32_t* __r
   host_out[t] = v;
 }
 
-int sample_label_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, const uint8_t* d_labels, int K, double cell,
-  int64_t S, unsigned long long seed, int32_t* d_out, int32_t* h_out, hipStream_t st)
+// The batch's sample lists under its labels: position p belongs to the list whose span holds it (as k_batch_samples finds the
+// capture), list l = object j of capture k, and is E_{k,j}[draw_stratum(M_l, S_k, t, seed_k)] -- capture-local to the pinned
+// list, + cloud_off[k] to the search's -- or kSampleSkip.  The first L threads write the M_l to the pinned table (the kernel runs
+// for S_tot = 0 too).
+__global__ __launch_bounds__(256) void k_batch_samples_labeled(const BatchCapture* __restrict__ tab, const VoxCapture* __restrict__ cap,
+  const LabelCapture* __restrict__ lc, int L, int64_t S_tot, const int* __restrict__ cloud_off, const int32_t* __restrict__ E,
+  const long long* __restrict__ totals, int32_t* __restrict__ out, int32_t* __restrict__ host_out, long long* __restrict__ host_counts)
+{
+  const int64_t p = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < L)
+    host_counts[p] = totals[p];
+  if (p >= S_tot)
+    return;
+  int l = 0;
+  for (int q = 1; q < L; q++)  // (the last list whose span starts at or before p and is not empty)
+    if (tab[q].soff <= p && tab[q].S > 0)
+      l = q;
+  const int k = tab[l].capture, j = tab[l].object;
+  int32_t v = draw_stratum(totals[l], tab[l].S, (long long) (p - tab[l].soff), tab[l].seed);
+  if (v != kSampleSkip)
+  {
+    long long at = cap[k].code_off + v;
+    for (int q = 0; q < j; q++)  // (E_{k,j} lies behind the capture's lists in front of it)
+      at += totals[lc[k].first_list + q];
+    v = E[at];
+  }
+  host_out[p] = v;
+  out[p] = v == kSampleSkip ? v : (int32_t) (v + cloud_off[k]);
+}
+
+// the buffers of the stage, for a bitmap of `words` words, n raw points and `groups` group counts: kept and grown by the context
+static int ensure_label_buffers(Ctx* c, int64_t words, int64_t n, int64_t groups)
 {
   int rc;
-  // (the voxel bitmap exists: the preprocessing queued in front of this stage sized or kept it)
-  const int64_t words = c->vox_bitmap_cap;
-  const int64_t n_groups = (n + kLabelGroup - 1) / kLabelGroup;
   if (!c->d_label_totals)
   {
     if ((rc = dev_alloc(c, &c->d_label_totals, (size_t) kMaxClouds)))
@@ -274,13 +383,25 @@ int sample_label_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_
       return rc;
     c->mask_list_cap = std::max<int64_t>(n, 1024);
   }
-  if ((int64_t) K * n_groups > c->label_group_cap || !c->d_label_groups)
+  if (groups > c->label_group_cap || !c->d_label_groups)
   {
     c->label_group_cap = 0;
-    if ((rc = dev_alloc(c, &c->d_label_groups, (size_t) std::max<int64_t>((int64_t) K * n_groups, 1024))))
+    if ((rc = dev_alloc(c, &c->d_label_groups, (size_t) std::max<int64_t>(groups, 1024))))
       return rc;
-    c->label_group_cap = std::max<int64_t>((int64_t) K * n_groups, 1024);
+    c->label_group_cap = std::max<int64_t>(groups, 1024);
   }
+  return AGH_OK;
+}
+
+int sample_label_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, const uint8_t* d_labels, int K, double cell,
+  int64_t S, unsigned long long seed, int32_t* d_out, int32_t* h_out, hipStream_t st)
+{
+  int rc;
+  // (the voxel bitmap exists: the preprocessing queued in front of this stage sized or kept it)
+  const int64_t words = c->vox_bitmap_cap;
+  const int64_t n_groups = (n + kLabelGroup - 1) / kLabelGroup;
+  if ((rc = ensure_label_buffers(c, words, n, (int64_t) K * n_groups)) != AGH_OK)
+    return rc;
   const VoxDesc* desc = (const VoxDesc*) c->d_vox_desc;
   const int64_t nb = n > 0 ? words / kLabelWordsPerBlock : 0;  // (no point, no bit: vox_stage2 wrote no block counts either)
   if (nb > 0)
@@ -303,6 +424,43 @@ int sample_label_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_
     AGH_HIPCHK(c, hipMemsetAsync(c->d_label_totals, 0, sizeof(long long) * kMaxClouds, st));
   hipLaunchKernelGGL(k_draw_samples_labeled, dim3((unsigned) std::max<int64_t>(1, ((int64_t) K * S + 255) / 256)), dim3(256), 0, st,
     (const int32_t*) c->d_mask_list, (const long long*) c->d_label_totals, K, (int) S, seed, d_out, h_out, c->h_label_counts);
+  if (hipGetLastError() != hipSuccess)
+  {
+    c->err = "sample label launch failed";
+    return AGH_ERR_HIP;
+  }
+  return AGH_OK;
+}
+
+// The stage over a batch (BatchLabelStage, agh_internal.h): one launch per step, none that depends on n_captures or L.
+int sample_label_stage_batch(Ctx* c, const BatchLabelStage& m, hipStream_t st)
+{
+  int rc;
+  const int64_t W = m.vb.slot_words, nb = W / kLabelWordsPerBlock;
+  const int64_t n_groups = (m.n_max + kLabelGroup - 1) / kLabelGroup;
+  if ((rc = ensure_label_buffers(c, (int64_t) m.C * W, m.n_tot, (int64_t) m.L * n_groups)) != AGH_OK)
+    return rc;
+  const unsigned Cy = (unsigned) m.C;
+  const LabelCapture* lc = m.lists;
+  if (m.n_max > 0 && nb > 0)
+  {
+    AGH_HIPCHK(c, hipMemsetAsync(c->d_label_set, 0, (size_t) m.n_tot * 8, st));
+    hipLaunchKernelGGL(k_vox_word_rank_batch, dim3((unsigned) nb, Cy), dim3(256), 0, st, m.vb, m.bitmap, c->d_label_rank);
+    const int64_t label_words = (m.n_max + 3 + 3) / 4;  // (aligned words that a base up to 3 bytes into one can touch)
+    hipLaunchKernelGGL(k_label_mark_batch, dim3((unsigned) ((label_words + 255) / 256), Cy), dim3(256), 0, st, m.vb, m.code, m.labels,
+      lc, m.cell, m.bitmap, m.blk2, (const unsigned*) c->d_label_rank, m.cloud_off, c->d_label_set);
+    hipLaunchKernelGGL(k_label_count_batch, dim3((unsigned) n_groups, Cy), dim3(kLabelGroup), 0, st, m.vb,
+      (const unsigned long long*) c->d_label_set, lc, m.cloud_off, n_groups, c->d_label_groups);
+    hipLaunchKernelGGL(k_label_scan, dim3((unsigned) m.L), dim3(64), 0, st, c->d_label_groups, n_groups, c->d_label_totals);
+    hipLaunchKernelGGL(k_label_emit_batch, dim3((unsigned) n_groups, Cy), dim3(kLabelGroup), 0, st, m.vb,
+      (const unsigned long long*) c->d_label_set, lc, m.cloud_off, n_groups, (const int*) c->d_label_groups,
+      (const long long*) c->d_label_totals, c->d_mask_list);
+  }
+  else
+    AGH_HIPCHK(c, hipMemsetAsync(c->d_label_totals, 0, sizeof(long long) * kMaxClouds, st));
+  const int64_t threads = std::max<int64_t>(m.S_tot, m.L);
+  hipLaunchKernelGGL(k_batch_samples_labeled, dim3((unsigned) ((threads + 255) / 256)), dim3(256), 0, st, m.tab, m.vb.cap, lc, m.L,
+    m.S_tot, m.cloud_off, (const int32_t*) c->d_mask_list, (const long long*) c->d_label_totals, m.d_out, m.h_out, c->h_label_counts);
   if (hipGetLastError() != hipSuccess)
   {
     c->err = "sample label launch failed";

@@ -283,9 +283,11 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
  * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled*, agh_localize_depth_labeled*,
- * agh_localize_batch_masked*, agh_localize_batch_masked_begin*, agh_localize_depth_batch_masked* and
- * agh_localize_depth_batch_masked_begin* among them), agh_deproject, agh_deproject_batch,
- * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_batch_mask_counts and every getter of device results (frames, normals,
+ * agh_localize_batch_masked*, agh_localize_batch_masked_begin*, agh_localize_depth_batch_masked*,
+ * agh_localize_depth_batch_masked_begin*, agh_localize_batch_labeled*, agh_localize_batch_labeled_begin*,
+ * agh_localize_depth_batch_labeled* and agh_localize_depth_batch_labeled_begin* among them), agh_deproject, agh_deproject_batch,
+ * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_batch_mask_counts,
+ * agh_get_batch_label_counts and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -397,8 +399,9 @@ int agh_localize_depth_stage(agh_ctx* ctx, const agh_depth_image* images, int32_
  * way than they need the caller's capture.  One more bitmap of the voxel bitmap's size is held by a context that made a masked
  * call; the chain's one synchronisation stays one.
  * Not built: a _stage call for masks, for one capture or a batch (the batch forms are agh_localize_batch_masked* below);
- * label images in the batch chains (agh_localize_batch*, agh_localize_depth_batch*; for ONE capture, several objects with one
- * sample list each: agh_localize_labeled* below); sharded variants. */
+ * masks and label images in the batch chains mixed in one call (agh_localize_batch*, agh_localize_depth_batch*; label images
+ * alone: agh_localize_batch_labeled* below; for ONE capture, several objects with one sample list each:
+ * agh_localize_labeled* below); sharded variants. */
 typedef struct agh_sample_mask
 {
   const uint8_t* data;       /* one byte per pixel, non-zero = eligible; NULL: no pixel of this image is */
@@ -467,7 +470,8 @@ int agh_get_sample_mask_count(agh_ctx* ctx, int64_t* n_eligible);
  * agh_get_label_counts: the M_j of the last labelled chain this context collected (n_objects entries).  AGH_ERR_STATE if the
  * last chain collected was not labelled (agh_get_sample_mask_count returns AGH_ERR_STATE after a labelled call), if there was
  * none, or while a chain is in flight; AGH_ERR_CAPACITY if cap_objects is below n_objects.
- * Not built: _begin / _end and _stage forms; labels in the batch chains; more than 64 objects; labels wider than a byte;
+ * Not built: _begin / _end and _stage forms; labels in the batch chains beyond 64 lists per call (the batch forms are
+ * agh_localize_batch_labeled* below); more than 64 objects; labels wider than a byte;
  * sharded variants. */
 typedef struct agh_label_image   /* depth form: as agh_sample_mask, the bytes being labels */
 {
@@ -551,8 +555,10 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * flight (agh_localize_depth_batch* and agh_localize_depth_batch_begin* included, agh_localize_masked*,
  * agh_localize_masked_begin, agh_localize_depth_masked* and agh_localize_depth_masked_begin too, and agh_localize_labeled*
  * and agh_localize_depth_labeled*, agh_localize_batch_masked*, agh_localize_batch_masked_begin*,
- * agh_localize_depth_batch_masked* and agh_localize_depth_batch_masked_begin*; agh_deproject_batch, agh_get_sample_mask_count,
- * agh_get_label_counts and agh_get_batch_mask_counts are refused as well),
+ * agh_localize_depth_batch_masked* and agh_localize_depth_batch_masked_begin*, agh_localize_batch_labeled*,
+ * agh_localize_batch_labeled_begin*, agh_localize_depth_batch_labeled* and agh_localize_depth_batch_labeled_begin*;
+ * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_batch_mask_counts and
+ * agh_get_batch_label_counts are refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
@@ -662,7 +668,8 @@ int agh_deproject_batch(agh_ctx* ctx, const agh_depth_image* images, const int32
  *     device-to-device copies queued at begin; they must stay valid until the call (or agh_localize_batch_end) has returned.
  *  9. A context's first masked batch adds: one more set of bitmap slots of the batch's bitmap size, one byte and one 32-bit
  *     word per raw point, and the slots' block counts -- nothing else that scales with n_captures x the largest lattice.
- * Not built: a _stage call for masks; label images in the batch chains; masked and unmasked captures mixed in one batch (an
+ * Not built: a _stage call for masks; masks and label images in the batch chains mixed in one call (label images in the batch
+ * chains alone: agh_localize_batch_labeled* below); masked and unmasked captures mixed in one batch (an
  * all-ones mask says "unmasked"); sharded variants. */
 int agh_localize_batch_masked(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
@@ -688,6 +695,86 @@ int agh_localize_depth_batch_masked_begin(agh_ctx* ctx, const agh_depth_image* i
 int agh_localize_depth_batch_masked_begin_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
   const int32_t* n_images, const agh_localize_params* lp, int32_t n_captures);
 int agh_get_batch_mask_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_captures);
+
+/* The batch chains with one sample list PER OBJECT of every capture's LABEL IMAGE: "grasps on each object, for every rig of the
+ * cell" -- several sensor pairs, each with an instance segmenter.  agh_localize_labeled once per capture pays the single chain
+ * and one synchronisation per capture, one after the other.  Here the batch is preprocessed once (agh_localize_batch*), one
+ * label stage runs for all captures (capture on blockIdx.y, no launch per capture or per list), the search runs once over all
+ * lists, and the batch tail compacts and walks one list per (capture, object) side by side; one synchronisation.
+ * Points forms: labels is a host array of n_captures pointers.  Depth forms: labels is ONE flat array parallel to `images`, as
+ * masks is in the masked batch.
+ *  1. Lists.  n_objects[k] is the number of objects of capture k; list l = first_list[k] + j is object j of capture k, first_list
+ *     being the exclusive prefix sum of n_objects; L = sum of n_objects[k] is the number of lists of the call.
+ *     1 <= n_objects[k] <= 64 and L <= 64 (the lists the batch tail holds; this is not lifted here).  lp[k].n_samples = S_k is
+ *     the number of samples of EACH object of capture k and lp[k].sample_seed the seed of every object of capture k;
+ *     sum of n_objects[k] x S_k <= 2^24.  Any violation, or lp[k].sample_idx != NULL, is AGH_ERR_INVALID_ARGUMENT with nothing
+ *     launched; the error text names the capture.
+ *  2. Labels.  Points forms: labels[k] holds one byte per raw point of capture k; all n_captures entries are required, a NULL
+ *     entry is an error that names the capture.  Depth forms: labels[i] belongs to images[i], has its width and height, row v
+ *     at data + v * row_stride_bytes; data == NULL: no pixel of that image belongs to an object; a capture whose label records
+ *     ALL have data == NULL is an error, and so is a row stride below the image width (the text names the capture and the
+ *     image).  Byte 0: no object; byte j + 1: object j of THIS capture; a byte above n_objects[k]: no object, and no error.
+ *  3. Eligibility and draw are rules 3 and 4 of agh_localize_labeled, per capture: E_{k,j} is the ascending list of the
+ *     CAPTURE-LOCAL voxel indices that hold a kept raw point of capture k with label j + 1, in its own camera block;
+ *     M_{k,j} = |E_{k,j}|; sample t of list (k, j) is E_{k,j}[stratum draw of agh_localize with M_{k,j}, S_k, seed_k]; with
+ *     M_{k,j} < S_k the list is E_{k,j} followed by INT32_MIN slots.  M_{k,j} = 0 is no error: that list has no hypotheses,
+ *     hands or handles, and no other list is affected.  The label stage runs for S_k = 0 too.
+ *  4. Outputs: the layout of agh_localize_batch with L spans in list order.  results has L records; results[l].r holds list l's
+ *     counts, its n_voxels is capture k's voxel count; first_* are the starts of list l's spans.  samples_out holds capture-local
+ *     voxel indices, sum of n_objects[k] x S_k entries.  agh_hypothesis::sample is the position in the list's own sample list;
+ *     inlier indices point into the list's own span of hands_out.  The 8192-hand limit holds per list (the error text says
+ *     "capture k, object j").  Buffers that are too small: AGH_ERR_CAPACITY with every results[l] filled.
+ *  5. Equality, with AGH_NORMALS_DETERMINISTIC: the spans of lists first_list[k] .. first_list[k] + n_objects[k] - 1 equal, bit
+ *     for bit (epoch aside), what agh_localize_labeled returns for capture k alone with labels[k], n_objects[k] and lp[k] (the
+ *     depth form's twin is agh_localize_depth_labeled); list (k, j) therefore equals agh_localize_masked on capture k with the
+ *     mask labels[k] == j + 1, and M_{k,j} equals the twin's agh_get_label_counts.  With AGH_NORMALS_RAND50 the rand() stream
+ *     runs through the whole sample list of the call: only list 0 equals its twin.
+ *  6. Everything else is the unmasked batch twin's: classify, cell_size, min_inliers, min_length and filters_boundaries must be
+ *     equal across the batch; n_captures in 1..64, fewer than 2^30 points; AGH_ERR_NO_SVM; a camera-origin table needs
+ *     n_captures rows -- origins are per CAPTURE, not per list (the search derives a sample's cloud from its index in the
+ *     common voxel array); the boundary filter uses the list's capture's workspace; one synchronisation in the steady state,
+ *     the first batch of a context takes the one for the lattice sizes; an outgrown-slot repeat reads the labels where the
+ *     first pass left them, capacity-class and declined-walk repeats work on the lists already drawn; AGH_ERR_STATE while a
+ *     chain of any kind is in flight, that chain untouched; a begin of host data never adopts a staged set and drops a pending
+ *     one; after the call the voxelised batch is the context's bound batch of n_captures clouds.  The _begin forms are collected
+ *     with agh_localize_batch_end; the blocking forms are begin + end.
+ *  7. agh_get_batch_label_counts writes the L values M_{k,j} of the last chain collected, in list order.  AGH_ERR_STATE if that
+ *     chain was not a labelled batch, if there was none, or while a chain is in flight; AGH_ERR_CAPACITY if cap_lists < L.
+ *     After a labelled batch agh_get_sample_mask_count, agh_get_label_counts and agh_get_batch_mask_counts return
+ *     AGH_ERR_STATE; agh_get_batch_label_counts returns AGH_ERR_STATE after any other chain.
+ *  8. Lifetimes and alignment are the masked batch's: host labels are copied by begin, depth labels repacked to one byte per
+ *     pixel in point order; device points labels (_device) are read in place at any byte alignment; device depth labels are
+ *     repacked by device-to-device copies queued at begin.
+ *  9. A context's first labelled batch adds: one 32-bit word per word of the batch's bitmap slots, one 64-bit object set and
+ *     one list entry per raw point of the batch, and L x ceil(n_max / 256) ints of group counts -- nothing that scales with L
+ *     x a lattice, or with n_captures x 64.
+ * 10. Not built: more than 64 lists per call; labels wider than a byte; a _stage call for labels; labelled, masked and unmasked
+ *     captures mixed in one batch; sharded variants. */
+int agh_localize_batch_labeled(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+int agh_localize_batch_labeled_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+int agh_localize_batch_labeled_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_batch_labeled_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_depth_batch_labeled(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
+  const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out,
+  int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);
+int agh_localize_depth_batch_labeled_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
+  const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out,
+  int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);
+int agh_localize_depth_batch_labeled_begin(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
+  const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_depth_batch_labeled_begin_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
+  const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures);
+int agh_get_batch_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_lists);
 
 /* The context's current cloud: packed xyz (3 floats per point) and camera ids; returns the number of points. */
 int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap);

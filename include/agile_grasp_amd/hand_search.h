@@ -598,6 +598,7 @@ public:
     batch_captures_ = C;
     batch_cap_ = cap;
     batch_samples_ = n_samples;
+    batch_objects_.clear();
     return true;
   }
 
@@ -666,6 +667,7 @@ public:
     batch_captures_ = C;
     batch_cap_ = cap;
     batch_samples_ = n_samples;
+    batch_objects_.clear();
     return true;
   }
 
@@ -715,6 +717,7 @@ public:
     batch_captures_ = C;
     batch_cap_ = cap;
     batch_samples_ = n_samples;
+    batch_objects_.clear();
     return true;
   }
 
@@ -769,6 +772,7 @@ public:
     batch_captures_ = C;
     batch_cap_ = cap;
     batch_samples_ = n_samples;
+    batch_objects_.clear();
     return true;
   }
 
@@ -778,6 +782,120 @@ public:
   {
     std::vector<std::int64_t> m(64, -1);
     if (!ctx_ || agh_get_batch_mask_counts(ctx_, m.data(), 64) != AGH_OK)
+      return std::vector<std::int64_t>();
+    std::size_t k = 0;
+    while (k < m.size() && m[k] >= 0)
+      k++;
+    m.resize(k);
+    return m;
+  }
+
+  /** Additional: localizeBatchBegin with one sample list PER OBJECT of every capture's label array
+   *  (agh_localize_batch_labeled_begin): labels[k] holds one byte per point of clouds[k] (0 = no object, j + 1 = object j of
+   *  n_objects[k]), num_samples samples are drawn per object, capture k's objects seeded with the sample seed + k.  The call has
+   *  a LIST per (capture, object), at most 64 in all: localizeBatchEnd returns one entry per list, capture after capture, object
+   *  after object (batchObjects() says how many of them belong to each capture), and batchLabelCounts() then gives the eligible
+   *  voxels per list.  The labels are copied by the call; the clouds must stay alive and unchanged until localizeBatchEnd has
+   *  returned.  A Begin that fails leaves a chain in flight as it was. */
+  bool localizeBatchLabeledBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<std::vector<std::uint8_t> >& labels, const std::vector<int>& n_objects, const std::vector<VectorXd>& workspaces,
+    double cell_size, const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    const std::size_t C = clouds.size();
+    if (C == 0 || sizes_left.size() != C || workspaces.size() != C || labels.size() != C || n_objects.size() != C)
+    {
+      std::cout << " Error: localizeBatchLabeledBegin needs one size_left, workspace, label array and object count per cloud\n";
+      return false;
+    }
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    RawBatch in;
+    if (!rawPoints(clouds, in))
+      return false;
+    const std::uint64_t seed = sampleSeed();
+    std::vector<agh_localize_params> lp(C);
+    std::vector<const std::uint8_t*> lptr(C);
+    std::vector<std::int32_t> objects(n_objects.begin(), n_objects.end());
+    for (std::size_t k = 0; k < C; k++)
+    {
+      if (labels[k].size() != clouds[k]->points.size())
+      {
+        std::cout << " Error: localizeBatchLabeledBegin needs one label byte per point of every cloud\n";
+        return false;
+      }
+      lptr[k] = labels[k].data();
+      lp[k] = chainParams(sizes_left[k], cloud_is_dense(*clouds[k]), workspaces[k], cell_size, std::vector<std::int32_t>(),
+        seed + (std::uint64_t) k, min_inliers, min_length, filters_boundaries);
+    }
+    if (agh_localize_batch_labeled_begin(ctx_, in.xyz.data(), in.stride.data(), in.n.data(), lptr.data(), objects.data(), lp.data(),
+          (std::int32_t) C) != AGH_OK)
+    {
+      fail("agh_localize_batch_labeled_begin");
+      return false;
+    }
+    labeledBatchQueued(n_objects, lp);
+    return true;
+  }
+
+  /** ... and straight from depth images (agh_localize_depth_batch_labeled_begin): labels[k][j] belongs to captures[k][j]; a
+   *  label image without data puts no pixel of its image into an object, and every capture needs at least one with data. */
+  bool localizeDepthBatchLabeledBegin(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<std::vector<LabelImage> >& labels, const std::vector<int>& n_objects, const std::vector<VectorXd>& workspaces,
+    double cell_size, const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    const std::size_t C = captures.size();
+    if (C == 0 || workspaces.size() != C || labels.size() != C || n_objects.size() != C)
+    {
+      std::cout << " Error: localizeDepthBatchLabeledBegin needs one workspace, label image list and object count per capture\n";
+      return false;
+    }
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    const std::uint64_t seed = sampleSeed();
+    std::vector<agh_depth_image> recs;  // (the flat arrays in capture order; copied by the library's begin, like the arrays below)
+    std::vector<agh_label_image> lrecs;
+    std::vector<std::int32_t> n_images(C);
+    std::vector<std::int32_t> objects(n_objects.begin(), n_objects.end());
+    std::vector<agh_localize_params> lp(C);
+    for (std::size_t k = 0; k < C; k++)
+    {
+      if (labels[k].size() != captures[k].size())
+      {
+        std::cout << " Error: localizeDepthBatchLabeledBegin needs one label image per image\n";
+        return false;
+      }
+      const std::vector<agh_depth_image> r = depthRecords(captures[k]);
+      recs.insert(recs.end(), r.begin(), r.end());
+      for (std::size_t j = 0; j < labels[k].size(); j++)
+      {
+        agh_label_image m;
+        m.data = labels[k][j].data;
+        m.row_stride_bytes = labels[k][j].row_stride_bytes;
+        lrecs.push_back(m);
+      }
+      n_images[k] = (std::int32_t) r.size();
+      lp[k] = chainParams(0, true, workspaces[k], cell_size, std::vector<std::int32_t>(), seed + (std::uint64_t) k, min_inliers,
+        min_length, filters_boundaries);
+    }
+    if (agh_localize_depth_batch_labeled_begin(ctx_, recs.empty() ? nullptr : recs.data(), lrecs.empty() ? nullptr : lrecs.data(),
+          n_images.data(), objects.data(), lp.data(), (std::int32_t) C) != AGH_OK)
+    {
+      fail("agh_localize_depth_batch_labeled_begin");
+      return false;
+    }
+    labeledBatchQueued(n_objects, lp);
+    return true;
+  }
+
+  /** the objects per capture of the labelled batch in flight or last collected (empty: that batch was not labelled) */
+  const std::vector<int>& batchObjects() const { return batch_objects_; }
+
+  /** agh_get_batch_label_counts: the eligible voxels of every list of the last labelled batch localizeBatchEnd collected, in
+   *  list order; empty if the last chain collected was no labelled batch */
+  std::vector<std::int64_t> batchLabelCounts()
+  {
+    std::vector<std::int64_t> m(64, -1);
+    if (!ctx_ || agh_get_batch_label_counts(ctx_, m.data(), 64) != AGH_OK)
       return std::vector<std::int64_t>();
     std::size_t k = 0;
     while (k < m.size() && m[k] >= 0)
@@ -1057,6 +1175,22 @@ private:
     handles_out.assign(K, std::vector<agh_handle>());
     inliers_out.assign(K, std::vector<std::int32_t>());
   }
+  // what localizeBatchEnd needs for the labelled batch just queued: a list per (capture, object), n_samples each
+  void labeledBatchQueued(const std::vector<int>& n_objects, const std::vector<agh_localize_params>& lp)
+  {
+    std::size_t lists = 0;
+    std::int64_t cap = 1, n_samples = 0;
+    for (std::size_t k = 0; k < n_objects.size(); k++)
+    {
+      lists += (std::size_t) n_objects[k];
+      cap += (std::int64_t) n_objects[k] * handsRoom(lp[k].n_samples);
+      n_samples += (std::int64_t) n_objects[k] * lp[k].n_samples;
+    }
+    batch_captures_ = lists;
+    batch_cap_ = cap;
+    batch_samples_ = n_samples;
+    batch_objects_ = n_objects;
+  }
   void labeledCollect(const LabeledOutputs& o, std::vector<std::vector<agh_hypothesis> >& hands_out,
     std::vector<std::vector<agh_handle> >& handles_out, std::vector<std::vector<std::int32_t> >& inliers_out)
   {
@@ -1194,6 +1328,7 @@ private:
   // chain in flight included -- leaves that chain's End what it needs.
   std::int64_t loc_cap_ = 1;  // room for the results of the chain localizeBegin / localizeDepthBegin queued
   std::size_t batch_captures_ = 0;  // ... and of the batch localizeBatchBegin queued: its captures, room, samples
+  std::vector<int> batch_objects_;  // a labelled batch: the objects per capture (batch_captures_ then counts its LISTS)
   std::int64_t batch_cap_ = 1, batch_samples_ = 0;
   agh_params params_;
   Matrix4d cam_tf_left_, cam_tf_right_;

@@ -755,6 +755,123 @@ public:
     return search_ ? search_->batchMaskCounts() : std::vector<std::int64_t>();
   }
 
+  /** Additional: localizeHandlesBatch with one sample list PER OBJECT of every capture's label array
+   *  (agh_localize_batch_labeled): a cell with one instance segmenter per sensor pair hands over labels[k], one byte per point
+   *  of clouds[k] (0 = no object, j + 1 = object j of n_objects[k]; at most 64 objects in all); num_samples samples are drawn
+   *  per object.  Returns the handles per capture and object -- out[k][j] are those of localizeHandlesLabeled on capture k alone
+   *  (seeded with the sample seed + k) -- and likewise the kept hands.  An error returns empty lists, per capture and object
+   *  where the object counts say how many. */
+  std::vector<std::vector<std::vector<Handle> > > localizeHandlesBatchLabeled(const std::vector<PointCloud::Ptr>& clouds,
+    const std::vector<int>& sizes_left, const std::vector<std::vector<std::uint8_t> >& labels, const std::vector<int>& n_objects,
+    const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<std::vector<GraspHypothesis> > >* antipodal_hands_per_object = nullptr,
+    const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesBatchLabeled") ||
+        !localizeHandlesBatchLabeledBegin(clouds, sizes_left, labels, n_objects, svm_filename, min_inliers, min_length, workspaces))
+      return noLabeledHandles(n_objects, antipodal_hands_per_object);
+    return localizeHandlesBatchLabeledEnd(antipodal_hands_per_object);
+  }
+
+  /** ... as two calls: the chain queued here is collected by localizeHandlesBatchLabeledEnd (or by localizeHandlesBatchEnd, which
+   *  returns one entry per LIST: capture after capture, object after object).  A Begin while a chain of any kind is pending
+   *  returns false and leaves it as it was, and so does a Begin that fails for another reason.  The labels are copied by the
+   *  call; the clouds must stay alive and unchanged until the End has returned. */
+  bool localizeHandlesBatchLabeledBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<std::vector<std::uint8_t> >& labels, const std::vector<int>& n_objects, const std::string& svm_filename,
+    int min_inliers, double min_length, const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesBatchLabeledBegin", "its End"))
+      return false;
+    for (std::size_t k = 0; k < clouds.size(); k++)
+      if (!clouds[k] || clouds[k]->size() == 0 || k >= sizes_left.size() || sizes_left[k] == 0)
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    if (!detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(clouds.size(), workspace_);
+    if (!search_->localizeBatchLabeledBegin(clouds, sizes_left, labels, n_objects, ws, 0.003, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
+      return false;
+    pendingLists(clouds, n_objects);
+    return true;
+  }
+
+  /** ... and straight from depth images with one label image per image (agh_localize_depth_batch_labeled): labels[k][j] belongs
+   *  to captures[k][j]; a label image without data puts no pixel of its image into an object.  out[k][j] are the handles of
+   *  localizeHandlesDepthLabeled on capture k alone. */
+  std::vector<std::vector<std::vector<Handle> > > localizeHandlesDepthBatchLabeled(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<std::vector<LabelImage> >& labels, const std::vector<int>& n_objects, const std::string& svm_filename,
+    int min_inliers, double min_length, std::vector<std::vector<std::vector<GraspHypothesis> > >* antipodal_hands_per_object = nullptr,
+    const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatchLabeled") ||
+        !localizeHandlesDepthBatchLabeledBegin(captures, labels, n_objects, svm_filename, min_inliers, min_length, workspaces))
+      return noLabeledHandles(n_objects, antipodal_hands_per_object);
+    return localizeHandlesBatchLabeledEnd(antipodal_hands_per_object);
+  }
+
+  bool localizeHandlesDepthBatchLabeledBegin(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<std::vector<LabelImage> >& labels, const std::vector<int>& n_objects, const std::string& svm_filename,
+    int min_inliers, double min_length, const std::vector<VectorXd>* workspaces = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatchLabeledBegin", "its End"))
+      return false;
+    for (std::size_t k = 0; k < captures.size(); k++)
+      if (captures[k].empty())
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    if (!detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(captures.size(), workspace_);
+    if (!search_->localizeDepthBatchLabeledBegin(captures, labels, n_objects, ws, 0.003, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
+      return false;
+    pendingLists(std::vector<PointCloud::Ptr>(captures.size()), n_objects);  // (no capture with a host cloud)
+    return true;
+  }
+
+  /** the results of the labelled batch a labelled Begin queued, per capture and object.  A pending batch of another kind is not
+   *  this call's to collect: it is refused (after printing) with an empty result, and that chain stays pending for
+   *  localizeHandlesBatchEnd. */
+  std::vector<std::vector<std::vector<Handle> > > localizeHandlesBatchLabeledEnd(
+    std::vector<std::vector<std::vector<GraspHypothesis> > >* antipodal_hands_per_object = nullptr)
+  {
+    const std::vector<int> objects = search_ ? search_->batchObjects() : std::vector<int>();
+    std::vector<std::vector<std::vector<Handle> > > out = noLabeledHandles(objects, antipodal_hands_per_object);
+    if (!pending_batch_.empty() && objects.empty())
+    {
+      std::cout << " Error: localizeHandlesBatchLabeledEnd while the pending batch is not a labelled one (localizeHandlesBatchEnd "
+                   "collects it)\n";
+      return out;
+    }
+    std::vector<std::vector<GraspHypothesis> > kept;
+    const std::vector<std::vector<Handle> > flat = localizeHandlesBatchEnd(antipodal_hands_per_object ? &kept : nullptr);
+    std::size_t l = 0;
+    for (std::size_t k = 0; k < objects.size(); k++)
+      for (std::size_t j = 0; j < (std::size_t) objects[k] && l < flat.size(); j++, l++)
+      {
+        out[k][j] = flat[l];
+        if (antipodal_hands_per_object)
+          (*antipodal_hands_per_object)[k][j] = kept[l];
+      }
+    return out;
+  }
+
+  /** The eligible voxels of every list of the last labelled batch collected (agh_get_batch_label_counts), capture after capture,
+   *  object after object; empty if the last chain collected was no labelled batch, if there was none, or while a chain is
+   *  pending. */
+  std::vector<std::int64_t> getBatchLabelCounts()
+  {
+    return search_ ? search_->batchLabelCounts() : std::vector<std::int64_t>();
+  }
+
   /** the searched hands, handles and inlier lists of one capture as the reference's objects (the tail of localizeHandlesEnd) */
   std::vector<Handle> toHandles(const PointCloud::Ptr& cloud_in, const std::vector<agh_hypothesis>& hands,
     const std::vector<agh_handle>& handles, const std::vector<std::int32_t>& idx, std::vector<GraspHypothesis>* antipodal_hands)
@@ -828,6 +945,30 @@ private:
     for (std::size_t j = 0; j < hands.size(); j++)
       out[j] = toHandles(j == 0 ? cloud_in : PointCloud::Ptr(), hands[j], handles[j], idx[j],
         antipodal_hands_per_object ? &(*antipodal_hands_per_object)[j] : nullptr);
+    return out;
+  }
+  // a labelled batch is pending with one entry per LIST: a capture's host cloud (filtered once, in place) goes with its first
+  void pendingLists(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& n_objects)
+  {
+    pending_batch_.clear();
+    for (std::size_t k = 0; k < clouds.size(); k++)
+      for (int j = 0; j < n_objects[k]; j++)
+        pending_batch_.push_back(j == 0 ? clouds[k] : PointCloud::Ptr());
+  }
+  // what a labelled batch call returns when it fails: empty lists per capture and object (object counts outside 1 .. 64: none)
+  static std::vector<std::vector<std::vector<Handle> > > noLabeledHandles(const std::vector<int>& n_objects,
+    std::vector<std::vector<std::vector<GraspHypothesis> > >* antipodal_hands_per_object)
+  {
+    std::vector<std::vector<std::vector<Handle> > > out(n_objects.size());
+    if (antipodal_hands_per_object)
+      antipodal_hands_per_object->assign(n_objects.size(), std::vector<std::vector<GraspHypothesis> >());
+    for (std::size_t k = 0; k < n_objects.size(); k++)
+    {
+      const std::size_t K = n_objects[k] >= 1 && n_objects[k] <= 64 ? (std::size_t) n_objects[k] : 0;
+      out[k].resize(K);
+      if (antipodal_hands_per_object)
+        (*antipodal_hands_per_object)[k].resize(K);
+    }
     return out;
   }
   // what a batch call returns when it fails: an empty list of handles, and of kept hands, per capture
