@@ -97,6 +97,8 @@ EXPORTS = [
     "agh_localize_depth_masked_device", "agh_localize_depth_masked_begin", "agh_get_sample_mask_count",
     "agh_localize_labeled", "agh_localize_labeled_device", "agh_localize_depth_labeled", "agh_localize_depth_labeled_device",
     "agh_get_label_counts",
+    "agh_default_cluster_params", "agh_localize_clustered", "agh_localize_clustered_device", "agh_localize_depth_clustered",
+    "agh_localize_depth_clustered_device", "agh_get_cluster_info", "agh_get_cluster_labels",
     "agh_localize_batch_masked", "agh_localize_batch_masked_device", "agh_localize_batch_masked_begin",
     "agh_localize_batch_masked_begin_device", "agh_localize_depth_batch_masked", "agh_localize_depth_batch_masked_device",
     "agh_localize_depth_batch_masked_begin", "agh_localize_depth_batch_masked_begin_device", "agh_get_batch_mask_counts",
@@ -179,6 +181,28 @@ class AghLocalizeResult(C.Structure):
 class AghLocalizeBatchResult(C.Structure):
     _fields_ = [("r", AghLocalizeResult), ("first_handle", C.c_int64), ("first_inlier_idx", C.c_int64), ("first_hand", C.c_int64),
                 ("first_sample", C.c_int64)]
+
+
+class AghClusterParams(C.Structure):
+    _fields_ = [("plane", C.c_double * 4), ("min_height", C.c_double), ("max_height", C.c_double), ("tolerance", C.c_double),
+                ("min_voxels", C.c_int32), ("max_objects", C.c_int32)]
+
+
+class AghClusterInfo(C.Structure):
+    _fields_ = [("n_foreground", C.c_int64), ("n_components", C.c_int64), ("n_objects", C.c_int64)]
+
+
+def cluster_params(**fields) -> AghClusterParams:
+    """agh_default_cluster_params, then the given fields (plane: four numbers)."""
+    cp = AghClusterParams()
+    load_library().agh_default_cluster_params(C.byref(cp))
+    for k, v in fields.items():
+        if k == "plane":
+            v = (C.c_double * 4)(*[float(x) for x in v])
+        elif not hasattr(cp, k):
+            raise TypeError(f"agh_cluster_params has no field {k}")
+        setattr(cp, k, v)
+    return cp
 
 
 DEPTH_U16, DEPTH_F32 = 0, 1
@@ -372,6 +396,7 @@ def load_library():
         lib.agh_shard_slice.restype = None
         lib.agh_plane_replay.restype = None
         lib.agh_default_plane_params.restype = None
+        lib.agh_default_cluster_params.restype = None
         _LIB = lib
     return _LIB
 
@@ -705,6 +730,63 @@ class Context:
                                                   cell_size, False, filters_boundaries)
         fn = self.lib.agh_localize_depth_labeled_device if on_device else self.lib.agh_localize_depth_labeled
         return self._localize_labeled(fn, (recs, lrecs, C.c_int32(len(recs))), n_objects, lp, S, caps)
+
+    # ---- clusters as the label source (include/agh.h, agh_localize_clustered*) ----
+    def _localize_clustered(self, fn, capture_args, cp, lp, S, caps):
+        K = int(cp.max_objects) if cp is not None else 0
+        a = {"Ck": K if 1 <= K <= 64 else 0, "S_list": [S] * (K if 1 <= K <= 64 else 0)}
+        cp_arg = C.byref(cp) if cp is not None else None
+        out = self._batch_collect(a, caps, lambda *o: fn(self._h, *capture_args, cp_arg, C.byref(lp), *o))
+        self.n = out[0]["n_voxels"] if out else 0
+        return out
+
+    def localize_clustered(self, xyz, size_left: int, workspace, cp, n_samples: int = 0, sample_seed: int = 1,
+                           classify: bool = True, min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003,
+                           dense: bool = False, filters_boundaries: bool = False, samples=None, caps=None):
+        """agh_localize_clustered (torch CUDA tensors: agh_localize_clustered_device): localize_labeled() whose objects are the
+        connected components of the voxels above the support plane of `cp` (cluster_params(); None passes NULL), found on the
+        device inside the call.  Returns cp.max_objects dicts; cluster_info() and cluster_labels() then describe the objects.
+        (`samples` goes through, for the library to refuse.)"""
+        on_device = hasattr(xyz, "is_cuda") and xyz.is_cuda
+        if on_device:
+            assert xyz.dim() == 2 and xyz.shape[1] >= 3 and xyz.stride(1) == 1
+            xyz_ptr, n_pts, stride_b = C.c_void_p(xyz.data_ptr()), int(xyz.shape[0]), int(xyz.stride(0)) * 4
+        else:
+            xyz = np.ascontiguousarray(xyz, np.float32)
+            assert xyz.ndim == 2 and xyz.shape[1] >= 3
+            xyz_ptr, n_pts, stride_b = _p(xyz, C.c_float), xyz.shape[0], xyz.shape[1] * 4
+        lp, samples, S, _ = self._localize_params(size_left, workspace, samples, n_samples, sample_seed, classify, min_inliers,
+                                                  min_length, cell_size, dense, filters_boundaries)
+        fn = self.lib.agh_localize_clustered_device if on_device else self.lib.agh_localize_clustered
+        return self._localize_clustered(fn, (xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts)), cp, lp, S, caps)
+
+    def localize_depth_clustered(self, images, workspace, cp, n_samples: int = 0, sample_seed: int = 1, classify: bool = True,
+                                 min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003,
+                                 filters_boundaries: bool = False, samples=None, caps=None):
+        """agh_localize_depth_clustered (torch CUDA tensors: agh_localize_depth_clustered_device): localize_clustered() straight
+        from depth images (see depth_image_records)."""
+        recs, keep, on_device = depth_image_records(images)
+        lp, samples, S, _ = self._localize_params(0, workspace, samples, n_samples, sample_seed, classify, min_inliers, min_length,
+                                                  cell_size, False, filters_boundaries)
+        fn = self.lib.agh_localize_depth_clustered_device if on_device else self.lib.agh_localize_depth_clustered
+        return self._localize_clustered(fn, (recs, C.c_int32(len(recs))), cp, lp, S, caps)
+
+    def cluster_info(self, cap_objects: int = 64):
+        """agh_get_cluster_info of the last clustered chain this context collected: a dict with n_foreground, n_components,
+        n_objects, and per list of the call n_voxels (M_j) and ids (the object's smallest voxel index, -1: none)."""
+        info = AghClusterInfo()
+        m = np.full(max(cap_objects, 1), -2, np.int64)
+        ids = np.full(max(cap_objects, 1), -2, np.int32)
+        self._check(self.lib.agh_get_cluster_info(self._h, C.byref(info), _p(m, C.c_int64), _p(ids, C.c_int32), C.c_int32(cap_objects)))
+        return {"n_foreground": info.n_foreground, "n_components": info.n_components, "n_objects": info.n_objects,
+                "n_voxels": m[m > -2].copy(), "ids": ids[ids > -2].copy()}
+
+    def cluster_labels(self, cap: int | None = None) -> np.ndarray:
+        """agh_get_cluster_labels: per voxel of the bound cloud 0 or object + 1, of the last clustered chain collected."""
+        cap = int(self.n) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), np.uint8)
+        nv = self._check(self.lib.agh_get_cluster_labels(self._h, C.c_void_p(out.ctypes.data), C.c_int64(cap)))
+        return out[:nv].copy()
 
     def label_counts(self, cap_objects: int = 64) -> np.ndarray:
         """agh_get_label_counts: the eligible voxels M_j of every object of the last labelled chain this context collected."""

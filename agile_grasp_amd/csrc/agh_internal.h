@@ -227,6 +227,10 @@ struct LocalizeState
   // agh_localize_labeled* (sample_labels.hip): the bytes are labels, 1 .. n_objects, and the chain draws S samples for each
   // object (0: a mask); from the classifier on its tail is the batch chain's, one list per object (localize_batch.hip)
   int32_t n_objects = 0;
+  // agh_localize_clustered* (sample_cluster.hip): the objects are connected components of the cloud; n_objects = max_objects, no
+  // label bytes; a repeat of the whole call re-enters with these
+  bool clustered = false;
+  agh_cluster_params cluster{};
   // agh_localize_batch_begin / _stage / _end (localize_batch.hip) share the one chain and the one staged set of the context
   bool batch = false;         // the chain in flight is a batch's (agh_localize_batch_end collects it, not agh_localize_end)
   bool staged = false;        // stage_captures: a set of captures is (being) copied into d_stage_xyz, packed end to end,
@@ -344,6 +348,18 @@ struct Ctx
   long long* h_label_counts = nullptr;  // pinned: the M_j, written by the chain
   int32_t label_objects = 0;          // n_objects of the last chain collected if it was labelled, else 0
   int64_t label_counts[kMaxClouds] = {};  // ... and its M_j
+  // clusters as the label source (sample_cluster.hip), allocated by the first clustered call
+  int* d_cluster_parent = nullptr;    // per voxel: the union-find's parent, then its root (-1: background)
+  int* d_cluster_size = nullptr;      // per voxel: a root's size, then -1 - rank for the roots that are objects
+  uint8_t* d_cluster_label = nullptr; // per voxel: 0 or object + 1 (agh_get_cluster_labels)
+  int64_t cluster_cap = 0;
+  unsigned long long* d_cluster_counts = nullptr;  // foreground voxels, components
+  long long* h_cluster_table = nullptr;  // pinned: counts, M_j and ids, written by the chain (k_cluster_select)
+  int32_t cluster_objects = 0;        // max_objects of the last chain collected if it was clustered, else 0
+  int64_t cluster_nv = 0;             // ... its voxel count
+  int64_t cluster_info[4] = {};       // ... foreground, components, objects, qualifying
+  int64_t cluster_sizes[kMaxClouds] = {};  // ... M_j
+  int32_t cluster_ids[kMaxClouds] = {};    // ... and the smallest voxel index of object j (-1: none)
   int32_t batch_mask_captures = 0;    // n_captures of the last chain collected if it was a masked batch, else 0
   int64_t batch_mask_counts[kMaxClouds] = {};  // ... and its M_k
   int32_t batch_label_lists = 0;      // the lists of the last chain collected if it was a labelled batch, else 0
@@ -745,6 +761,22 @@ int sample_mask_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t
 // the M_j go to c->h_label_counts
 int sample_label_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, const uint8_t* d_labels, int K, double cell,
   int64_t S, unsigned long long seed, int32_t* d_out, int32_t* h_out, hipStream_t st);
+// ... in two parts, so that another source of the object sets shares the second: the label buffers (a bitmap of `words` words, n
+// raw points, `groups` group counts), and the compaction of c->d_label_set into the K lists with their draw
+constexpr int kLabelGroup = 256;  // voxels per work-group of the compaction: four waves
+int ensure_label_buffers(Ctx* c, int64_t words, int64_t n, int64_t groups);
+int label_compact_stage(Ctx* c, int64_t n, int K, bool any, int64_t S, unsigned long long seed, int32_t* d_out, int32_t* h_out,
+  hipStream_t st);
+// sample_cluster.hip: the same K lists with the object sets taken from the cloud itself (include/agh.h, agh_localize_clustered):
+// the connected components of the voxels above a support plane; the parameters as the kernels take them
+struct ClusterDev
+{
+  double plane[4], min_height, max_height, tolerance;
+  float tol2;          // (float) (tolerance * tolerance): the bound of the float32 adjacency rule
+  int32_t min_voxels;
+};
+int sample_cluster_stage(Ctx* c, int64_t n, const ClusterDev& cp, int K, int64_t S, unsigned long long seed, int32_t* d_out,
+  int32_t* h_out, hipStream_t st);
 // ... and on the C slots of a batch's bitmap (vb.slot_words words each): slot k's counts at blk + k * slot_words / 4096, not scanned
 int vox_count_blocks_batch(const VoxBatch& vb, int C, const unsigned* d_bitmap, int* d_blk, hipStream_t st);
 // sample_mask.hip: the masked sample list of a batch chain whose preprocessing (vox_batch) is queued on st (include/agh.h,
@@ -969,6 +1001,12 @@ __device__ __forceinline__ unsigned long long vox_bit(const VoxDesc* d, int c, c
   const unsigned long long iy = (unsigned long long) vox_index(p[1], d->mn[c][1], cell);
   const unsigned long long iz = (unsigned long long) vox_index(p[2], d->mn[c][2], cell);
   return (ix * (unsigned long long) d->dim[c][1] + iy) * (unsigned long long) d->dim[c][2] + iz;
+}
+
+// The voxels of the cloud (device side; none after a voxeliser's error, whose repeat runs the stage again): n = the raw points.
+__device__ __forceinline__ int64_t label_voxels(const VoxDesc* d, int64_t n)
+{
+  return d->error ? 0 : min((int64_t) (d->n_vox[0] + d->n_vox[1]), n);
 }
 
 __device__ __forceinline__ int cell_coord(const GridDesc& g, double v, int a)

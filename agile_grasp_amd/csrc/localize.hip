@@ -2,12 +2,14 @@
 // GraspLocalizer::localizeGrasps, grasp_localizer.cpp:95-103 = localizeHands -> predictAntipodalHands -> findHandles per capture.
 // agh_localize / agh_localize_device / agh_localize_begin / agh_localize_stage / agh_localize_end, agh_localize_depth* and the
 // masked forms of both (agh_localize_masked*, agh_localize_depth_masked*) and the labelled ones (agh_localize_labeled*,
-// agh_localize_depth_labeled*) of include/agh.h (the back-projection of depth images: depth.hip; the sample list under a mask:
-// sample_mask.hip; one list per object of a label image: sample_labels.hip, with localize_batch.hip's tail); the stages
+// agh_localize_depth_labeled*) and the clustered ones (agh_localize_clustered*, agh_localize_depth_clustered*) of include/agh.h
+// (the back-projection of depth images: depth.hip; the sample list under a mask: sample_mask.hip; one list per object of a label
+// image: sample_labels.hip, or per connected component of the cloud: sample_cluster.hip, with localize_batch.hip's tail); the stages
 // themselves (preprocessing, search, classification, handle search) are api.hip's, voxelize.hip's, hog_svm.hip's and handles.hip's.
 #include "agh_internal.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 
@@ -262,6 +264,7 @@ struct MaskSource
   const char* who;
   int32_t n_objects = 0;          // agh_localize_labeled*: the bytes are labels 1 .. n_objects (0: a mask)
   bool labeled = false;
+  const agh_cluster_params* cluster = nullptr;  // agh_localize_clustered*: no bytes at all, the objects are the cloud's components
 };
 static_assert(sizeof(agh_label_image) == sizeof(agh_sample_mask) && offsetof(agh_label_image, data) == offsetof(agh_sample_mask, data) &&
                 offsetof(agh_label_image, row_stride_bytes) == offsetof(agh_sample_mask, row_stride_bytes),
@@ -273,6 +276,31 @@ static int mask_check(Ctx* c, const MaskSource* mask, const DepthSource* depth, 
     c->err = std::string(mask->who) + ": " + what;
     return AGH_ERR_INVALID_ARGUMENT;
   };
+  if (mask->cluster)
+  {
+    const agh_cluster_params& cp = *mask->cluster;
+    const double* q = cp.plane;
+    const char* field[7] = { "plane[0]", "plane[1]", "plane[2]", "plane[3]", "min_height", "max_height", "tolerance" };
+    const double value[7] = { q[0], q[1], q[2], q[3], cp.min_height, cp.max_height, cp.tolerance };
+    for (int k = 0; k < 7; k++)
+      if (!std::isfinite(value[k]))
+        return bad(std::string(field[k]) + " is not finite");
+    if (std::fabs(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) - 1.0) > 1e-6)
+      return bad("plane: (a, b, c) must be a unit vector (|a^2 + b^2 + c^2 - 1| <= 1e-6)");
+    if (cp.min_height >= cp.max_height)
+      return bad("min_height must be below max_height");
+    if (!(cp.tolerance > 0.0) || cp.tolerance > 0.05)
+      return bad("tolerance must be in (0, 0.05]");
+    if (cp.min_voxels < 1)
+      return bad("min_voxels must be >= 1");
+    if (cp.max_objects < 1 || cp.max_objects > kMaxClouds)
+      return bad("max_objects must be 1 .. 64");
+    if ((int64_t) cp.max_objects * lp->n_samples > (1 << 24))
+      return bad("max_objects x n_samples exceeds 2^24");
+    if (lp->sample_idx)
+      return bad("sample_idx must be NULL (the lists are drawn on the objects the call finds)");
+    return AGH_OK;
+  }
   if (mask->labeled && (mask->n_objects < 1 || mask->n_objects > kMaxClouds))
     return bad("n_objects must be 1 .. 64");
   if (mask->labeled && (int64_t) mask->n_objects * lp->n_samples > (1 << 24))
@@ -441,11 +469,14 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     d_raw = c->d_raw_xyz;
   }
   const uint8_t* d_mask = nullptr;
-  if (mask && (rc = mask_to_device(c, mask, depth, n, st, &d_mask)) != AGH_OK)
+  if (mask && !mask->cluster && (rc = mask_to_device(c, mask, depth, n, st, &d_mask)) != AGH_OK)
     return chain_fail(c, rc);  // (the capture's copy may be in flight)
   L.masked = mask != nullptr;
   L.d_mask = d_mask;
   L.n_objects = K;
+  L.clustered = mask && mask->cluster;
+  if (L.clustered)
+    L.cluster = *mask->cluster;
   L.S = S;
   L.classify = lp->classify != 0;
   L.filters = lp->filters_boundaries != 0;
@@ -485,7 +516,15 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     AGH_HIPCHK_OR(c, ensure_keep_buffers(c, c->s_cap * 8), chain_fail(c, AGH_ERR_HIP));
   }
   // ---- 3. the sample list ----
-  if (K)  // (for S = 0 too, as the mask's)
+  if (L.clustered)  // (the grid build is queued: the preprocessing above bound the voxelised cloud)
+  {
+    const agh_cluster_params& q = L.cluster;
+    const ClusterDev cp{ { q.plane[0], q.plane[1], q.plane[2], q.plane[3] }, q.min_height, q.max_height, q.tolerance,
+      (float) (q.tolerance * q.tolerance), q.min_voxels };
+    if ((rc = sample_cluster_stage(c, n, cp, K, S, (unsigned long long) lp->sample_seed, c->d_idx_own, h_idx_labeled, st)) != AGH_OK)
+      return chain_fail(c, rc);
+  }
+  else if (K)  // (for S = 0 too, as the mask's)
   {
     if ((rc = sample_label_stage(c, d_raw, dev_stride / 4, n, d_mask, K, lp->cell_size, S, (unsigned long long) lp->sample_seed,
            c->d_idx_own, h_idx_labeled, st)) != AGH_OK)
@@ -529,6 +568,7 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
   L.active = false;
   c->mask_count = -1;
   c->label_objects = 0;
+  c->cluster_objects = 0;
   c->batch_mask_captures = 0;
   c->batch_label_lists = 0;
   const int64_t S = L.S;
@@ -562,8 +602,10 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
         lp.sample_idx = L.explicit_samples ? h_idx : nullptr;
         L.repeated = true;
         // (a mask is where the chain read it, as the capture is: in the context's buffer, or in the caller's device memory)
-        const MaskSource again{ L.d_mask, nullptr, true, L.n_objects ? "agh_localize_labeled" : "agh_localize_masked", L.n_objects,
-          L.n_objects != 0 };
+        const agh_cluster_params cluster = L.cluster;
+        const MaskSource again{ L.d_mask, nullptr, true,
+          L.clustered ? "agh_localize_clustered" : (L.n_objects ? "agh_localize_labeled" : "agh_localize_masked"), L.n_objects,
+          L.n_objects != 0, L.clustered ? &cluster : nullptr };
         rc = localize_begin_impl(ctx, L.d_raw, true, L.dev_stride, L.n_raw, &lp, nullptr, L.masked ? &again : nullptr);
         if (rc == AGH_OK)
           rc = localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result,
@@ -587,11 +629,27 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
   {
     // the tail of the batch chain: one list per object, every object on the one cloud
     const int K = L.n_objects;
-    c->label_objects = K;
-    for (int j = 0; j < K; j++)
-      c->label_counts[j] = (int64_t) c->h_label_counts[j];
+    if (L.clustered)
+    {
+      // (the table of k_cluster_select: counts, then the M_j and the ids; the M_j equal the compaction's h_label_counts)
+      const long long* t = c->h_cluster_table;
+      c->cluster_objects = K;
+      c->cluster_nv = L.nv;
+      std::copy(t, t + 4, c->cluster_info);
+      for (int j = 0; j < kMaxClouds; j++)
+      {
+        c->cluster_sizes[j] = (int64_t) t[8 + j];
+        c->cluster_ids[j] = (int32_t) t[8 + kMaxClouds + j];
+      }
+    }
+    else
+    {
+      c->label_objects = K;
+      for (int j = 0; j < K; j++)
+        c->label_counts[j] = (int64_t) c->h_label_counts[j];
+    }
     const std::vector<int64_t> nv((size_t) K, L.nv);
-    return batch_collect(ctx, "agh_localize_labeled", "object", nv.data(), handles_out, handle_cap, inlier_idx_out, idx_cap,
+    return batch_collect(ctx, L.clustered ? "agh_localize_clustered" : "agh_localize_labeled", "object", nv.data(), handles_out, handle_cap, inlier_idx_out, idx_cap,
       hands_out, hands_cap, samples_out, results);
   }
   if (L.masked)
@@ -820,6 +878,125 @@ int agh_localize_depth_labeled_device(agh_ctx* ctx, const agh_depth_image* image
   const DepthSource src{ images, n_images, true, "agh_localize_depth_labeled_device" };
   return labeled_call(ctx, nullptr, true, 12, 0, nullptr, labels, &src, src.who, n_objects, lp, handles_out, handle_cap,
     inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+}
+
+// ---- the clustered forms (include/agh.h): the labelled chain with the cloud's own connected components as its objects ----
+
+static int clustered_call(agh_ctx* ctx, const float* xyz, bool on_device, int64_t stride_bytes, int64_t n, const DepthSource* depth,
+  const char* who, const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  if (!cp)
+  {
+    ctx->c.err = std::string(who) + ": cp is NULL";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  const int K = cp->max_objects;
+  if (results && K >= 1 && K <= kMaxClouds)
+    for (int j = 0; j < K; j++)
+      results[j] = agh_localize_batch_result{ { 0, 0, 0, 0, 0 }, 0, 0, 0, 0 };
+  const MaskSource m{ nullptr, nullptr, on_device, who, K, true, cp };
+  int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
+  if (rc == AGH_OK)
+    rc = localize_begin_impl(ctx, xyz, depth ? false : on_device, stride_bytes, n, lp, depth, &m);
+  if (rc != AGH_OK)
+    return rc;
+  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, nullptr, results);
+}
+
+void agh_default_cluster_params(agh_cluster_params* p)
+{
+  if (!p)
+    return;
+  *p = agh_cluster_params{ { 0.0, 0.0, 1.0, 0.0 }, 0.01, 0.5, 0.01, 50, 16 };
+}
+
+int agh_localize_clustered(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_cluster_params* cp,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  return clustered_call(ctx, xyz, false, stride_bytes, n, nullptr, "agh_localize_clustered", cp, lp, handles_out, handle_cap,
+    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+}
+
+int agh_localize_clustered_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const agh_cluster_params* cp,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  return clustered_call(ctx, d_xyz, true, stride_bytes, n, nullptr, "agh_localize_clustered_device", cp, lp, handles_out, handle_cap,
+    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+}
+
+int agh_localize_depth_clustered(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_cluster_params* cp,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthSource src{ images, n_images, false, "agh_localize_depth_clustered" };
+  return clustered_call(ctx, nullptr, false, 12, 0, &src, src.who, cp, lp, handles_out, handle_cap, inlier_idx_out, idx_cap,
+    hands_out, hands_cap, samples_out, results);
+}
+
+int agh_localize_depth_clustered_device(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_cluster_params* cp,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthSource src{ images, n_images, true, "agh_localize_depth_clustered_device" };
+  return clustered_call(ctx, nullptr, true, 12, 0, &src, src.who, cp, lp, handles_out, handle_cap, inlier_idx_out, idx_cap,
+    hands_out, hands_cap, samples_out, results);
+}
+
+// the last chain collected, if it was clustered (`fn` refuses otherwise, and mid-chain)
+static int cluster_getter_check(Ctx* c, const char* fn)
+{
+  if (refuse_mid_chain(c, fn))
+    return AGH_ERR_STATE;
+  if (c->cluster_objects < 1)
+  {
+    c->err = std::string(fn) + ": the last chain this context collected was not clustered (or there was none)";
+    return AGH_ERR_STATE;
+  }
+  return AGH_OK;
+}
+
+int agh_get_cluster_info(agh_ctx* ctx, agh_cluster_info* info, int64_t* n_voxels, int32_t* ids, int32_t cap_objects)
+{
+  if (!ctx || !info)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (int rc = cluster_getter_check(c, "agh_get_cluster_info"))
+    return rc;
+  *info = agh_cluster_info{ c->cluster_info[0], c->cluster_info[1], c->cluster_info[2] };
+  if ((n_voxels || ids) && cap_objects < c->cluster_objects)
+  {
+    c->err = "agh_get_cluster_info: cap_objects is below the call's max_objects";
+    return AGH_ERR_CAPACITY;
+  }
+  if (n_voxels)
+    std::copy(c->cluster_sizes, c->cluster_sizes + c->cluster_objects, n_voxels);
+  if (ids)
+    std::copy(c->cluster_ids, c->cluster_ids + c->cluster_objects, ids);
+  return AGH_OK;
+}
+
+int agh_get_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap)
+{
+  if (!ctx || (cap > 0 && !labels_out) || cap < 0)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (int rc = cluster_getter_check(c, "agh_get_cluster_labels"))
+    return rc;
+  if (cap < c->cluster_nv)
+  {
+    c->err = "agh_get_cluster_labels: cap is below the cloud's voxel count";
+    return AGH_ERR_CAPACITY;
+  }
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  if (c->cluster_nv > 0)
+    AGH_HIPCHK(c, hipMemcpy(labels_out, c->d_cluster_label, (size_t) c->cluster_nv, hipMemcpyDeviceToHost));
+  return (int) c->cluster_nv;
 }
 
 int agh_get_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_objects)

@@ -1011,6 +1011,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   c->loc.batch = false;
   c->mask_count = -1;  // (agh_get_sample_mask_count: the last chain collected had no mask)
   c->label_objects = 0;  // (... and no label image)
+  c->cluster_objects = 0;  // (... and no clusters)
   c->batch_mask_captures = 0;  // (agh_get_batch_mask_counts: set below, behind the synchronisation, if this batch is masked)
   c->batch_label_lists = 0;    // (agh_get_batch_label_counts likewise, if it is labelled)
   ActiveGuard guard(c);

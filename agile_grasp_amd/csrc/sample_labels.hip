@@ -28,7 +28,6 @@ namespace agh
 {
 
 constexpr int kLabelWordsPerBlock = 4096;  // voxelize.hip's kWordsPerBlock: 16 words per thread of 256
-constexpr int kLabelGroup = 256;           // voxels per work-group of count / emit: four waves
 
 // One work-group per block of 4096 bitmap words, a thread holding its 16: rank[w] = the voxel bits of the block in front of w.
 // (the block of 4096 words at w0 - 16 * threadIdx.x; the whole work-group comes here)
@@ -149,12 +148,6 @@ __global__ __launch_bounds__(256) void k_label_mark_batch(VoxBatch vb, const uin
   // (a capture whose descriptor carries an error has no voxels: label_mark_points returns at once)
   label_mark_points(q->xyz, q->stride, q->n, code + q->code_off, labels[blockIdx.y], lc[blockIdx.y].K, vb.desc + blockIdx.y, cell,
     vox + slot0, vox_prefix + slot0 / kLabelWordsPerBlock, rank + slot0, objset + cloud_off[blockIdx.y]);
-}
-
-// The voxels of the cloud (device side; none after a voxeliser's error, whose repeat runs this stage again).
-__device__ __forceinline__ int64_t label_voxels(const VoxDesc* d, int64_t n)
-{
-  return d->error ? 0 : min((int64_t) (d->n_vox[0] + d->n_vox[1]), n);
 }
 
 // One wave's share of the compaction: lane = voxel, set = its objects.  For each object present in the wave one ballot; f(j,
@@ -348,7 +341,7 @@ __global__ __launch_bounds__(256) void k_batch_samples_labeled(const BatchCaptur
 }
 
 // the buffers of the stage, for a bitmap of `words` words, n raw points and `groups` group counts: kept and grown by the context
-static int ensure_label_buffers(Ctx* c, int64_t words, int64_t n, int64_t groups)
+int ensure_label_buffers(Ctx* c, int64_t words, int64_t n, int64_t groups)
 {
   int rc;
   if (!c->d_label_totals)
@@ -393,6 +386,7 @@ static int ensure_label_buffers(Ctx* c, int64_t words, int64_t n, int64_t groups
   return AGH_OK;
 }
 
+// The stage's first part for a label image: the object sets of the voxels (any: there is a point, hence a bitmap block).
 int sample_label_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, const uint8_t* d_labels, int K, double cell,
   int64_t S, unsigned long long seed, int32_t* d_out, int32_t* h_out, hipStream_t st)
 {
@@ -413,6 +407,20 @@ int sample_label_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_
     hipLaunchKernelGGL(k_label_mark, dim3((unsigned) ((label_words + 255) / 256)), dim3(256), 0, st, d_xyz, stride_floats, n,
       (const uint8_t*) c->d_vox_code, d_labels, K, desc, cell, (const unsigned*) c->d_vox_bitmap, (const int*) c->d_vox_blk2,
       (const unsigned*) c->d_label_rank, c->d_label_set);
+  }
+  return label_compact_stage(c, n, K, nb > 0, S, seed, d_out, h_out, st);
+}
+
+// ... and its second, shared with the clustered chain (sample_cluster.hip), whose object sets come from the cloud: the
+// compaction of c->d_label_set into the lists and the draw (any == false: no voxel, every list is empty).  The label buffers
+// are there (ensure_label_buffers).
+int label_compact_stage(Ctx* c, int64_t n, int K, bool any, int64_t S, unsigned long long seed, int32_t* d_out, int32_t* h_out,
+  hipStream_t st)
+{
+  const VoxDesc* desc = (const VoxDesc*) c->d_vox_desc;
+  const int64_t n_groups = (n + kLabelGroup - 1) / kLabelGroup;
+  if (any)
+  {
     hipLaunchKernelGGL(k_label_count, dim3((unsigned) n_groups), dim3(kLabelGroup), 0, st,
       (const unsigned long long*) c->d_label_set, desc, n, K, n_groups, c->d_label_groups);
     hipLaunchKernelGGL(k_label_scan, dim3((unsigned) K), dim3(64), 0, st, c->d_label_groups, n_groups, c->d_label_totals);

@@ -3,12 +3,17 @@
 //
 //   g++ -std=c++11 -O2 -Iinclude examples/localize_pcd.cpp -o localize_pcd -Lagile_grasp_amd/lib -lagile_grasp_hip
 //       -Wl,-rpath,$PWD/agile_grasp_amd/lib -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
-//   ./localize_pcd [--filters-boundaries] <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]
+//   ./localize_pcd [--filters-boundaries] [--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd> [right.pcd]
+//                  [num_samples] [min_inliers]
 //
 // Parameters are the node's defaults (find_grasps.cpp:10-21): finger width 0.01, outer diameter 0.09, hand depth 0.06,
 // hand height 0.02, init bite 0.01, 2000 samples, workspace [0.65 0.9 -0.1 0.1 -0.2 1.0], min_inliers 3, camera poses
 // of find_grasps.cpp:35-45.  --filters-boundaries builds the Localization as the nodes do (grasp_localizer.cpp:21,
 // nodes/test.cpp:72): hands within 2 cm of a face of the workspace are dropped before the classifier.
+// --table a,b,c,d names the support plane ((a, b, c) a unit vector pointing from the table towards the objects): the objects are
+// the connected components of the points above it (Localization::localizeHandlesClustered), num_samples samples are drawn on
+// EACH of them and the handles are printed per object; --cluster-tolerance t (metres, default 0.01) is the distance up to which
+// two voxels belong to one object.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,9 +33,22 @@ int main(int argc, char** argv)
     argv++;
     argc--;
   }
+  bool table = false;
+  double plane[4] = { 0.0, 0.0, 1.0, 0.0 }, cluster_tolerance = 0.01;
+  while (argc > 2 && (std::strcmp(argv[1], "--table") == 0 || std::strcmp(argv[1], "--cluster-tolerance") == 0))
+  {
+    if (std::strcmp(argv[1], "--table") == 0)
+      table = std::sscanf(argv[2], "%lf,%lf,%lf,%lf", &plane[0], &plane[1], &plane[2], &plane[3]) == 4;
+    else
+      cluster_tolerance = std::atof(argv[2]);
+    argv[2] = argv[0];
+    argv += 2;
+    argc -= 2;
+  }
   if (argc < 3)
   {
-    std::printf("usage: %s [--filters-boundaries] <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]\n", argv[0]);
+    std::printf("usage: %s [--filters-boundaries] [--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd> [right.pcd] "
+                "[num_samples] [min_inliers]\n", argv[0]);
     return 2;
   }
   const std::string svm = argv[1], left = argv[2], right = argc > 3 ? argv[3] : "";
@@ -59,6 +77,35 @@ int main(int argc, char** argv)
   loc.setInitBite(0.01);
   loc.setHandHeight(0.02);
 
+  if (table)
+  {
+    // handles per object on the table: the clouds are read as localizeHands(left, right) reads them
+    PointCloud::Ptr cloud(new PointCloud), cloud_right(new PointCloud);
+    if (loadPCDFile(left, *cloud) == -1 || (right.length() > 0 && loadPCDFile(right, *cloud_right) == -1))
+    {
+      std::printf("could not read the PCD files\n");
+      return 1;
+    }
+    const int size_left = (int) cloud->size();
+    cloud->points.insert(cloud->points.end(), cloud_right->points.begin(), cloud_right->points.end());
+    cloud->is_dense = cloud->is_dense && cloud_right->is_dense;
+    VectorXd pl(4);
+    for (int i = 0; i < 4; i++)
+      pl(i) = plane[i];
+    loc.setClusterParams(0.01, 0.5, cluster_tolerance, 50, 16);
+    const std::vector<std::vector<Handle> > per_object = loc.localizeHandlesClustered(cloud, size_left, pl, svm, min_inliers, 0.005);
+    const std::vector<std::int64_t> sizes = loc.getClusterSizes();
+    for (std::size_t j = 0; j < per_object.size() && j < sizes.size() && sizes[j] > 0; j++)
+    {
+      const Grasps msg = createGraspsMsg(per_object[j]);
+      std::printf("object %zu: %lld voxels, %zu handles\n", j, (long long) sizes[j], per_object[j].size());
+      for (std::size_t i = 0; i < msg.grasps.size(); i++)
+        std::printf("  grasp %zu: center %.4f %.4f %.4f  axis %.4f %.4f %.4f  width %.4f\n", i, msg.grasps[i].center(0),
+          msg.grasps[i].center(1), msg.grasps[i].center(2), msg.grasps[i].axis(0), msg.grasps[i].axis(1), msg.grasps[i].axis(2),
+          (double) msg.grasps[i].width);
+    }
+    return 0;
+  }
   std::vector<GraspHypothesis> hands = loc.localizeHands(left, right, false, false);      // grasp_localizer.cpp:95
   std::vector<GraspHypothesis> antipodal = loc.predictAntipodalHands(hands, svm);          // :102
   std::vector<Handle> handles = loc.findHandles(antipodal, min_inliers, 0.005);            // :103

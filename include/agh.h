@@ -283,10 +283,12 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
  * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled*, agh_localize_depth_labeled*,
+ * agh_localize_clustered*, agh_localize_depth_clustered*,
  * agh_localize_batch_masked*, agh_localize_batch_masked_begin*, agh_localize_depth_batch_masked*,
  * agh_localize_depth_batch_masked_begin*, agh_localize_batch_labeled*, agh_localize_batch_labeled_begin*,
  * agh_localize_depth_batch_labeled* and agh_localize_depth_batch_labeled_begin* among them), agh_deproject, agh_deproject_batch,
- * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_batch_mask_counts,
+ * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info,
+ * agh_get_cluster_labels, agh_get_batch_mask_counts,
  * agh_get_batch_label_counts and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
@@ -493,6 +495,78 @@ int agh_localize_depth_labeled_device(agh_ctx* ctx, const agh_depth_image* image
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
 int agh_get_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_objects);
 
+/* The labelled chain WITHOUT A SEGMENTER: "grasps on each object on this table".  A fixed cell knows its support plane from
+ * calibration; given that plane, the objects are the connected components of the voxels that stand above it.  The call finds them
+ * on the device, behind the grid build and in front of the sample draw, and from there on it IS agh_localize_labeled with
+ * n_objects = max_objects: one preprocessing, one search over max_objects x S samples on the WHOLE cloud (the table stays in the
+ * hand sweep's collision tests: nothing is removed), one handle search for all lists, one synchronisation, no host round trip.
+ * Everything below is stated on the voxelised cloud of the call: voxel v is a position in it, p_v its float32 point.  Both
+ * cameras' voxels take part; camera ids play no role.
+ *  1. Height: h = ((a * x + b * y) + c * z) + d in double on the float coordinates, evaluated left to right, never contracted.
+ *     Voxel v is FOREGROUND iff min_height < h < max_height, both strict; a non-finite h is background.
+ *  2. Adjacency: dx = p_u.x - p_v.x, dy, dz likewise, in float32; d2 = (dx * dx + dy * dy) + dz * dz in float32, never
+ *     contracted; u and v are adjacent iff d2 <= (float) (tolerance * tolerance).  The rule is symmetric by construction.
+ *  3. Components are the connected components of that graph over the foreground voxels; a component's id is its smallest voxel
+ *     index, its size its voxel count.
+ *  4. Objects are the components of size >= min_voxels, ordered by size descending, ties to the smaller id; object j is the j-th
+ *     of them, j < K = max_objects.  Further components are counted (agh_cluster_info::n_components) but get no list; with
+ *     fewer than K objects the remaining lists are empty (M_j = 0 is a legal empty object, as for labels).  A voxel belongs to
+ *     at most one object.
+ *  5. E_j is the ascending list of object j's voxel indices, M_j its length; sample k of object j is E_j[stratum draw of
+ *     agh_localize with M_j in the place of N], and with M_j < S the list is E_j followed by INT32_MIN slots: rule 4 of
+ *     agh_localize_labeled with another source of the object sets.
+ *  6. Outputs are laid out as agh_localize_labeled's, results[j] for j < K.  Equality, with AGH_NORMALS_DETERMINISTIC: object
+ *     j's span of every output (handles, inlier indices, hands, samples) and results[j].r equal, bit for bit (epoch aside), what
+ *     agh_localize returns on the same capture and lp with object j's reported list as explicit sample_idx, INT32_MIN slots
+ *     carried.  The result does not depend on the order of any atomic operation.
+ *  7. AGH_ERR_INVALID_ARGUMENT, the text naming the field, nothing launched: a non-finite field; |a^2 + b^2 + c^2 - 1| > 1e-6;
+ *     min_height >= max_height; tolerance <= 0 or > 0.05 (a larger ball walks hundreds of grid cells per voxel; the bound is a
+ *     stated limit, not a measured one); min_voxels < 1; max_objects outside 1 .. 64; max_objects x n_samples > 2^24;
+ *     lp->sample_idx != NULL; cp == NULL.
+ *  8. Everything else is as agh_localize_labeled: AGH_ERR_NO_SVM; AGH_ERR_CAPACITY with results filled; AGH_ERR_STATE while a
+ *     chain or a batch of any kind is in flight; the one-row rule for a camera-origin table; the repeats inside the call (the
+ *     lattice that outgrew the kept bitmap re-enters with the same agh_cluster_params; the capacity classes and the declined
+ *     handle walk run on the lists already drawn); no foreground at all is AGH_OK with K empty objects.  The _device forms read
+ *     device points (images) in place; the depth forms run with size_left = W0 x H0 and dense = 1 and equal the points form on
+ *     the array agh_deproject writes.
+ *  9. agh_get_cluster_info / agh_get_cluster_labels describe the last chain this context collected if it was clustered: the
+ *     counts, the M_j and ids (max_objects entries each, 0 and -1 for a list without an object; either array may be NULL), and
+ *     per voxel of the bound cloud 0 or j + 1 (the return value is the voxel count; AGH_ERR_CAPACITY if cap is below it).
+ *     AGH_ERR_STATE after a chain of another kind, if there was none, or while a chain is in flight; after a clustered call
+ *     agh_get_label_counts and agh_get_sample_mask_count return AGH_ERR_STATE.
+ * 10. A context that made a clustered call holds two 32-bit words and a byte per raw point beside the labelled chain's buffers.
+ * Not built: a fitted plane (the caller supplies it); more than one capture per call; more than 64 objects; _begin / _end,
+ * _stage, batch and sharded forms.  The 8192-hand limit holds per object. */
+typedef struct agh_cluster_params
+{
+  double plane[4];      /* a, b, c, d of the support plane, (a, b, c) a unit vector pointing from the table towards the objects */
+  double min_height;    /* a voxel is FOREGROUND iff min_height < h < max_height, both strict */
+  double max_height;
+  double tolerance;     /* two foreground voxels are adjacent iff their distance is <= tolerance (rule 2) */
+  int32_t min_voxels;   /* components with fewer voxels are no objects (>= 1) */
+  int32_t max_objects;  /* K: 1 .. 64; the call has K lists, as agh_localize_labeled with n_objects = K */
+} agh_cluster_params;
+void agh_default_cluster_params(agh_cluster_params* p);  /* plane 0,0,1,0; heights 0.01 / 0.5; tolerance 0.01; min_voxels 50; max_objects 16 */
+int agh_localize_clustered(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_cluster_params* cp,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_localize_clustered_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const agh_cluster_params* cp,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_localize_depth_clustered(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_cluster_params* cp,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_localize_depth_clustered_device(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_cluster_params* cp,
+  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
+  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+typedef struct agh_cluster_info
+{
+  int64_t n_foreground, n_components, n_objects;  /* n_components: all, before min_voxels; n_objects: those with a list (<= K) */
+} agh_cluster_info;
+int agh_get_cluster_info(agh_ctx* ctx, agh_cluster_info* info, int64_t* n_voxels /* M_j */, int32_t* ids /* smallest voxel index */,
+  int32_t cap_objects);
+int agh_get_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap);  /* per voxel of the bound cloud: 0 or j + 1 */
+
 /* The chain of agh_localize over a BATCH of captures in one call, with ONE synchronisation (offline evaluation over a
  * directory of PCD pairs, a cell with several sensors or arms): 1 <= n_captures <= 64, fewer than 2^30 raw points in all.
  * Capture k is xyz[k] (stride_bytes[k], n[k] points) with its own record lp[k]: size_left, dense, workspace, sample_idx /
@@ -557,8 +631,9 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * and agh_localize_depth_labeled*, agh_localize_batch_masked*, agh_localize_batch_masked_begin*,
  * agh_localize_depth_batch_masked* and agh_localize_depth_batch_masked_begin*, agh_localize_batch_labeled*,
  * agh_localize_batch_labeled_begin*, agh_localize_depth_batch_labeled* and agh_localize_depth_batch_labeled_begin*;
- * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_batch_mask_counts and
- * agh_get_batch_label_counts are refused as well),
+ * agh_localize_clustered* and agh_localize_depth_clustered*;
+ * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info, agh_get_cluster_labels,
+ * agh_get_batch_mask_counts and agh_get_batch_label_counts are refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of

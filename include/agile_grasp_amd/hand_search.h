@@ -525,6 +525,88 @@ public:
     return m;
   }
 
+  /** Additional: one capture, one sample list PER OBJECT THE CALL FINDS (agh_localize_clustered): the objects are the connected
+   *  components of the voxels that stand above the support plane of `cp` (include/agh.h has the rules), at most cp.max_objects
+   *  of them, largest first; from there on the call is localizeLabeled's.  Outputs per object (cp.max_objects lists);
+   *  clusterInfo() and clusterLabels() then describe the objects.  One blocking call.  @return false (after printing) on error */
+  bool localizeClustered(const PointCloud::Ptr& cloud_in, int size_left, const agh_cluster_params& cp, const VectorXd& workspace,
+    double cell_size, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<agh_hypothesis> >& hands_out, std::vector<std::vector<agh_handle> >& handles_out,
+    std::vector<std::vector<std::int32_t> >& inliers_out, bool filters_boundaries = false)
+  {
+    labeledClear(cp.max_objects, hands_out, handles_out, inliers_out);
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    if (!cloud_in)
+    {
+      std::cout << " Error: localizeClustered needs a cloud\n";
+      return false;
+    }
+    const agh_localize_params lp = chainParams(size_left, cloud_is_dense(*cloud_in), workspace, cell_size, std::vector<std::int32_t>(),
+      sampleSeed(), min_inliers, min_length, filters_boundaries);
+    const RawPoints in = rawPoints(*cloud_in);
+    LabeledOutputs o(cp.max_objects, lp.n_samples);
+    if (agh_localize_clustered(ctx_, in.xyz, in.stride, in.n, &cp, &lp, o.handles.data(), o.cap, o.inl.data(), o.cap, o.hands.data(),
+          o.cap, o.samples.data(), o.res.data()) != AGH_OK)
+    {
+      fail("agh_localize_clustered");
+      return false;
+    }
+    labeledCollect(o, hands_out, handles_out, inliers_out);
+    return true;
+  }
+
+  /** ... and straight from depth images (agh_localize_depth_clustered) */
+  bool localizeDepthClustered(const std::vector<DepthImage>& images, const agh_cluster_params& cp, const VectorXd& workspace,
+    double cell_size, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<agh_hypothesis> >& hands_out, std::vector<std::vector<agh_handle> >& handles_out,
+    std::vector<std::vector<std::int32_t> >& inliers_out, bool filters_boundaries = false)
+  {
+    labeledClear(cp.max_objects, hands_out, handles_out, inliers_out);
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    const agh_localize_params lp = chainParams(0, true, workspace, cell_size, std::vector<std::int32_t>(), sampleSeed(), min_inliers,
+      min_length, filters_boundaries);
+    const std::vector<agh_depth_image> recs = depthRecords(images);
+    LabeledOutputs o(cp.max_objects, lp.n_samples);
+    if (agh_localize_depth_clustered(ctx_, recs.empty() ? nullptr : recs.data(), (std::int32_t) recs.size(), &cp, &lp, o.handles.data(),
+          o.cap, o.inl.data(), o.cap, o.hands.data(), o.cap, o.samples.data(), o.res.data()) != AGH_OK)
+    {
+      fail("agh_localize_depth_clustered");
+      return false;
+    }
+    labeledCollect(o, hands_out, handles_out, inliers_out);
+    return true;
+  }
+
+  /** agh_get_cluster_info: the counts of the last clustered call, the voxels M_j and the smallest voxel index of every list
+   *  (0 and -1 for a list without an object); false, with everything cleared, if the last chain collected was not clustered */
+  bool clusterInfo(agh_cluster_info& info, std::vector<std::int64_t>& n_voxels, std::vector<std::int32_t>& ids)
+  {
+    std::vector<std::int64_t> m(64, -2);
+    std::vector<std::int32_t> id(64, -2);
+    info = agh_cluster_info();
+    n_voxels.clear();
+    ids.clear();
+    if (!ctx_ || agh_get_cluster_info(ctx_, &info, m.data(), id.data(), 64) != AGH_OK)
+      return false;
+    std::size_t k = 0;
+    while (k < m.size() && m[k] > -2)
+      k++;
+    n_voxels.assign(m.begin(), m.begin() + (std::ptrdiff_t) k);
+    ids.assign(id.begin(), id.begin() + (std::ptrdiff_t) k);
+    return true;
+  }
+
+  /** agh_get_cluster_labels: per voxel of the searched cloud 0 or object + 1; empty if the last chain was not clustered */
+  std::vector<std::uint8_t> clusterLabels()
+  {
+    std::vector<std::uint8_t> out((std::size_t) (searched_n_ > 0 ? searched_n_ : 0) + 1);
+    const int nv = ctx_ ? agh_get_cluster_labels(ctx_, out.data(), (std::int64_t) out.size()) : -1;
+    out.resize(nv > 0 ? (std::size_t) nv : 0);
+    return out;
+  }
+
   /** agh_localize_depth_stage: the NEXT capture's images up, beside the chain in flight */
   bool localizeDepthStage(const std::vector<DepthImage>& next)
   {

@@ -478,6 +478,99 @@ public:
     return search_ ? search_->labelCounts() : std::vector<std::int64_t>();
   }
 
+  /** Additional: localizeHandles for every object ON A TABLE, without a segmenter (agh_localize_clustered): `plane` = (a, b, c, d),
+   *  four entries, is the support plane the cell knows from calibration, (a, b, c) a unit vector pointing from the table towards the objects.
+   *  The objects are the connected components of the voxels that stand above it (setClusterParams: the height band, the
+   *  tolerance, the smallest object and the number of lists), found on the device inside the one call; nothing is removed from
+   *  the cloud, so the hand search still sees the table.  Returns the handles per object, largest object first (and the kept hands
+   *  per object), shaped like localizeHandlesLabeled's: max_objects lists, empty ones behind the objects found.  An error returns
+   *  max_objects empty lists. */
+  std::vector<std::vector<Handle> > localizeHandlesClustered(const PointCloud::Ptr& cloud_in, int size_left, const VectorXd& plane,
+    const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object = nullptr)
+  {
+    const agh_cluster_params cp = clusterParams(plane);
+    const std::size_t K = cp.max_objects >= 1 && cp.max_objects <= 64 ? (std::size_t) cp.max_objects : 0;
+    std::vector<std::vector<Handle> > out = noHandles(K, antipodal_hands_per_object);
+    if (chainPending("localizeHandlesClustered"))
+      return out;
+    if (size_left == 0 || !cloud_in || cloud_in->size() == 0)
+    {
+      std::cout << "Input cloud is empty!\n";
+      std::cout << size_left << std::endl;
+      return out;
+    }
+    if (!detail::svmFileExists(svm_filename))
+      return out;
+    ensureSearch();
+    std::vector<std::vector<agh_hypothesis> > hands;
+    std::vector<std::vector<agh_handle> > handles;
+    std::vector<std::vector<std::int32_t> > idx;
+    if (!search_->localizeClustered(cloud_in, size_left, cp, workspace_, 0.003, svm_filename, min_inliers, min_length, hands, handles,
+          idx, filters_boundaries_))
+      return out;
+    return labeledHandles(cloud_in, hands, handles, idx, antipodal_hands_per_object);
+  }
+
+  /** ... and straight from depth images (agh_localize_depth_clustered) */
+  std::vector<std::vector<Handle> > localizeHandlesDepthClustered(const std::vector<DepthImage>& images, const VectorXd& plane,
+    const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object = nullptr)
+  {
+    const agh_cluster_params cp = clusterParams(plane);
+    const std::size_t K = cp.max_objects >= 1 && cp.max_objects <= 64 ? (std::size_t) cp.max_objects : 0;
+    std::vector<std::vector<Handle> > out = noHandles(K, antipodal_hands_per_object);
+    if (chainPending("localizeHandlesDepthClustered"))
+      return out;
+    if (images.empty())
+    {
+      std::cout << "Input cloud is empty!\n";
+      return out;
+    }
+    if (!detail::svmFileExists(svm_filename))
+      return out;
+    ensureSearch();
+    std::vector<std::vector<agh_hypothesis> > hands;
+    std::vector<std::vector<agh_handle> > handles;
+    std::vector<std::vector<std::int32_t> > idx;
+    if (!search_->localizeDepthClustered(images, cp, workspace_, 0.003, svm_filename, min_inliers, min_length, hands, handles, idx,
+          filters_boundaries_))
+      return out;
+    return labeledHandles(PointCloud::Ptr(), hands, handles, idx, antipodal_hands_per_object);
+  }
+
+  // the call's agh_cluster_params: what setClusterParams holds, with this plane
+  agh_cluster_params clusterParams(const VectorXd& plane) const
+  {
+    agh_cluster_params cp = cluster_;
+    for (int k = 0; k < 4; k++)
+      cp.plane[k] = plane(k);
+    return cp;
+  }
+
+  /** The height band above the plane, the adjacency tolerance, the smallest object in voxels and the number of lists of the
+   *  clustered calls (agh_cluster_params; the defaults are agh_default_cluster_params': 0.01 / 0.5, 0.01, 50, 16). */
+  void setClusterParams(double min_height, double max_height, double tolerance, int min_voxels, int max_objects)
+  {
+    cluster_.min_height = min_height;
+    cluster_.max_height = max_height;
+    cluster_.tolerance = tolerance;
+    cluster_.min_voxels = min_voxels;
+    cluster_.max_objects = max_objects;
+  }
+
+  /** The objects of the last clustered call (agh_get_cluster_info): their voxel counts, largest first, one entry per list; empty
+   *  if the last chain collected was not clustered, if there was none, or while a chain is pending. */
+  std::vector<std::int64_t> getClusterSizes()
+  {
+    agh_cluster_info info;
+    std::vector<std::int64_t> m;
+    std::vector<std::int32_t> ids;
+    if (search_)
+      search_->clusterInfo(info, m, ids);
+    return m;
+  }
+
   /** The seed of the samples a chain draws on the device (HandSearch::setSampleSeed; default: the clock, like pcl::RandomSample),
    *  and the list the last collected chain searched (HandSearch::getLastSampleIndices): together they make a masked call
    *  repeatable with explicit indices. */
@@ -984,6 +1077,7 @@ private:
     const double ws[6] = { -1.0, 1.0, -1.0, 1.0, -1.0, 1.0 };  // find_grasps.cpp:19
     for (int i = 0; i < 6; i++)
       workspace_(i) = ws[i];
+    agh_default_cluster_params(&cluster_);
     finger_width_ = 0.01;  // find_grasps.cpp:13-17
     hand_outer_diameter_ = 0.09;
     hand_depth_ = 0.06;
@@ -1010,6 +1104,7 @@ private:
 
   int num_threads_, num_samples_;
   bool filters_boundaries_;
+  agh_cluster_params cluster_;  // setClusterParams (the plane comes with each call)
   int plotting_mode_;
   Matrix4d cam_tf_left_, cam_tf_right_;
   VectorXd workspace_;
