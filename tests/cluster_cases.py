@@ -5,8 +5,8 @@ A case is a dict: `points` ((N, 3) float32), `size_left`, `dense`, `workspace`, 
 voxel_model: per camera the unique voxels in lexicographic order, each at ijk * cell + the camera's minimum), so a case places
 voxels, on mask_cases.lattice, and pins each camera's minimum with a point at the lattice's origin.
 
-  cluster_model    labels, counts, ids, sizes and the lists E_j of a voxelised cloud: brute force, pairwise float32 d2 and a
-                   Python union-find
+  cluster_model    labels, counts, ids, sizes and the lists E_j of a voxelised cloud: brute force, pairwise float32 d2
+                   (adjacent_pairs), then the components of that graph
   cases            the inputs the tests run, each named after the regime tests/test_cluster_cases.py proves it is in
   table_scene      a table with three boxes, both cameras: the chain-equality scene of the GPU tests
 """
@@ -47,44 +47,73 @@ def tol2(tolerance: float) -> np.float32:
     return F32(np.float64(tolerance) * np.float64(tolerance))
 
 
-def cluster_model(xyz: np.ndarray, cp: dict) -> dict:
-    """The contract of agh_localize_clustered on the voxelised cloud `xyz`: `labels` (per voxel 0 or j + 1), n_foreground,
-    n_components, n_objects, `sizes` and `ids` (K entries: M_j, and the smallest voxel index or -1) and `lists` (E_j)."""
+def adjacent_pairs(xyz: np.ndarray, cp: dict):
+    """(fg, a, b): the foreground voxel indices (ascending) and every adjacent pair fg[a] < fg[b] of them, by brute force: the
+    float32 rule on all pairs, 256 rows at a time -- against the voxels whose x lies within the tolerance of the rows' only (the
+    voxels sorted by x: what is left out is further away along x alone than any adjacent pair can be).  No cell structure."""
     xyz = np.ascontiguousarray(xyz, F32)
-    K = int(cp["max_objects"])
     fg = np.flatnonzero(foreground(xyz, cp))
     p = xyz[fg]
     t2 = tol2(cp["tolerance"])
-    parent = np.arange(len(fg))
-
-    def find(a):
-        while parent[a] != a:
-            parent[a] = parent[parent[a]]
-            a = parent[a]
-        return a
-
-    # every pair within the bound, 256 rows at a time -- against the voxels whose x lies within the tolerance of the rows' only
-    # (the voxels sorted by x: what is left out is further away along x alone than any adjacent pair can be)
     order = np.argsort(p[:, 0], kind="stable")
     ps, xs = p[order], p[order, 0].astype(np.float64)
     margin = 1.001 * float(cp["tolerance"]) + 1e-6
+    out_a, out_b = [], []
     for i0 in range(0, len(fg), 256):
         i1 = min(i0 + 256, len(fg))
         hi = int(np.searchsorted(xs, xs[i1 - 1] + margin, "right"))
-        adj = d2_f32(ps[i0:i1], ps[i0:hi]) <= t2
-        for i, j in zip(*np.nonzero(adj)):
-            if i < j:
-                a, b = find(order[i0 + i]), find(order[i0 + j])
-                if a != b:
-                    parent[max(a, b)] = min(a, b)  # (fg ascends: the root is the component's smallest voxel index)
-    roots = np.array([find(a) for a in range(len(fg))], np.int64)
-    comp_ids, sizes = np.unique(fg[roots], return_counts=True) if len(fg) else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+        i, j = np.nonzero(d2_f32(ps[i0:i1], ps[i0:hi]) <= t2)
+        keep = i < j
+        a, b = order[i0 + i[keep]], order[i0 + j[keep]]
+        out_a.append(np.minimum(a, b))
+        out_b.append(np.maximum(a, b))
+    cat = lambda parts: np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, np.int64)
+    return fg, cat(out_a), cat(out_b)
+
+
+def component_roots(n: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """per node 0 .. n - 1 the smallest node of its component under the edges (a, b)"""
+    try:
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+    except ImportError:
+        parent = np.arange(n)
+
+        def find(q):
+            while parent[q] != q:
+                parent[q] = parent[parent[q]]
+                q = parent[q]
+            return q
+
+        for i, j in zip(a, b):
+            i, j = find(i), find(j)
+            if i != j:
+                parent[max(i, j)] = min(i, j)
+        return np.array([find(q) for q in range(n)], np.int64)
+    _, comp = connected_components(coo_matrix((np.ones(len(a), np.int8), (a, b)), shape=(n, n)), directed=False)
+    first = np.full(int(comp.max()) + 1 if n else 0, n, np.int64)
+    np.minimum.at(first, comp, np.arange(n))
+    return first[comp]
+
+
+def cluster_model(xyz: np.ndarray, cp: dict, pairs=None) -> dict:
+    """The contract of agh_localize_clustered on the voxelised cloud `xyz`: `labels` (per voxel 0 or j + 1), n_foreground,
+    n_components, n_objects, `sizes` and `ids` (K entries: M_j, and the smallest voxel index or -1) and `lists` (E_j).  `pairs`:
+    (fg, a, b) in place of adjacent_pairs' -- what a stage that lost some pairs would compute."""
+    xyz = np.ascontiguousarray(xyz, F32)
+    K = int(cp["max_objects"])
+    fg, a, b = adjacent_pairs(xyz, cp) if pairs is None else pairs
+    roots = component_roots(len(fg), a, b)  # (fg ascends: the root is the component's smallest voxel index)
+    comp_ids, inv, sizes = (np.unique(fg[roots], return_inverse=True, return_counts=True) if len(fg)
+                            else (np.zeros(0, np.int64),) * 3)
     ok = sizes >= int(cp["min_voxels"])
-    order = sorted(np.flatnonzero(ok), key=lambda q: (-sizes[q], comp_ids[q]))[:K]
+    cand = np.flatnonzero(ok)
+    order = cand[np.lexsort((comp_ids[cand], -sizes[cand]))][:K]
     labels = np.zeros(len(xyz), np.uint8)
     out_sizes, out_ids, lists = np.zeros(K, np.int64), np.full(K, -1, np.int32), []
+    inv = np.asarray(inv).reshape(-1)
     for j, q in enumerate(order):
-        members = fg[fg[roots] == comp_ids[q]]
+        members = fg[inv == q]
         labels[members] = j + 1
         out_sizes[j], out_ids[j] = len(members), comp_ids[q]
         lists.append(members.astype(np.int32))
