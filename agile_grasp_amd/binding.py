@@ -105,6 +105,10 @@ EXPORTS = [
     "agh_localize_batch_labeled", "agh_localize_batch_labeled_device", "agh_localize_batch_labeled_begin",
     "agh_localize_batch_labeled_begin_device", "agh_localize_depth_batch_labeled", "agh_localize_depth_batch_labeled_device",
     "agh_localize_depth_batch_labeled_begin", "agh_localize_depth_batch_labeled_begin_device", "agh_get_batch_label_counts",
+    "agh_localize_batch_clustered", "agh_localize_batch_clustered_device", "agh_localize_batch_clustered_begin",
+    "agh_localize_batch_clustered_begin_device", "agh_localize_depth_batch_clustered", "agh_localize_depth_batch_clustered_device",
+    "agh_localize_depth_batch_clustered_begin", "agh_localize_depth_batch_clustered_begin_device", "agh_get_batch_cluster_info",
+    "agh_get_batch_cluster_labels",
 ]
 
 
@@ -1131,6 +1135,85 @@ class Context:
         m = np.full(max(cap_lists, 1), -1, np.int64)  # (the call writes L counts, none of them negative)
         self._check(self.lib.agh_get_batch_label_counts(self._h, _p(m, C.c_int64), C.c_int32(cap_lists)))
         return m[m >= 0].copy()
+
+    # ---- clusters in the batch chains (include/agh.h, agh_localize_batch_clustered*) ----
+
+    def _batch_cluster_lists(self, a, cps):
+        """A clustered batch has cps[k].max_objects lists for capture k.  `cps`: a list of cluster_params() records, one per
+        capture, or one record for all captures; None passes NULL, for the library to refuse."""
+        Ck = a["Ck"]
+        if cps is None:
+            a["cps"] = None
+            return self._batch_label_lists(a, None)
+        if isinstance(cps, AghClusterParams):
+            cps = [cps] * Ck
+        assert len(cps) == Ck
+        recs = (AghClusterParams * max(Ck, 1))()
+        for k, cp in enumerate(cps):
+            C.memmove(C.byref(recs[k]), C.byref(cp), C.sizeof(AghClusterParams))
+        a["cps"] = recs
+        return self._batch_label_lists(a, [int(cp.max_objects) for cp in cps])
+
+    def localize_batch_clustered(self, captures, sizes_left, workspaces, cps, caps=None, **kw):
+        """agh_localize_batch_clustered (torch CUDA tensors: agh_localize_batch_clustered_device): localize_batch_labeled()
+        whose objects are, per capture, the connected components of its own voxels above the support plane of cps[k]
+        (cluster_params(); a single record serves every capture), found on the device inside the call; n_samples is per OBJECT.
+        Returns a list per capture of cps[k].max_objects dicts; capture k's equal localize_clustered on that capture alone.
+        batch_cluster_info() and batch_cluster_labels() then describe the objects."""
+        a = self._batch_cluster_lists(self._batch_masked_args(captures, sizes_left, workspaces, None, kw), cps)
+        fn = self.lib.agh_localize_batch_clustered_device if a["on_device"] else self.lib.agh_localize_batch_clustered
+        return self._batch_labeled_collect(a, caps, lambda *out: fn(self._h, a["ptrs"], a["strides"], a["ns"], a["cps"], a["lps"],
+                                                                    C.c_int32(a["n_captures"]), *out))
+
+    def localize_batch_clustered_begin(self, captures, sizes_left, workspaces, cps, **kw):
+        """agh_localize_batch_clustered_begin (torch CUDA tensors: _begin_device): the clustered batch's chain queued, nothing
+        waited for; collected by localize_batch_end().  The captures are kept alive until then."""
+        a = self._batch_cluster_lists(self._batch_masked_args(captures, sizes_left, workspaces, None, kw), cps)
+        fn = self.lib.agh_localize_batch_clustered_begin_device if a["on_device"] else self.lib.agh_localize_batch_clustered_begin
+        self._check(fn(self._h, a["ptrs"], a["strides"], a["ns"], a["cps"], a["lps"], C.c_int32(a["n_captures"])))
+        self._batch_pending = a
+
+    def localize_depth_batch_clustered(self, captures, workspaces, cps, caps=None, **kw):
+        """agh_localize_depth_batch_clustered (torch CUDA tensors as `data`: agh_localize_depth_batch_clustered_device):
+        localize_batch_clustered() straight from depth images (`captures` as for localize_depth_batch)."""
+        a = self._batch_cluster_lists(self._depth_batch_args(captures, workspaces, kw), cps)
+        fn = self.lib.agh_localize_depth_batch_clustered_device if a["on_device"] else self.lib.agh_localize_depth_batch_clustered
+        return self._batch_labeled_collect(a, caps, lambda *out: fn(self._h, a["recs"], a["n_images"], a["cps"], a["lps"],
+                                                                    C.c_int32(a["n_captures"]), *out))
+
+    def localize_depth_batch_clustered_begin(self, captures, workspaces, cps, **kw):
+        """agh_localize_depth_batch_clustered_begin (torch CUDA tensors: _begin_device): the clustered depth batch's chain
+        queued; collected by localize_batch_end().  The pixel buffers are kept alive until then."""
+        a = self._batch_cluster_lists(self._depth_batch_args(captures, workspaces, kw), cps)
+        fn = (self.lib.agh_localize_depth_batch_clustered_begin_device if a["on_device"]
+              else self.lib.agh_localize_depth_batch_clustered_begin)
+        self._check(fn(self._h, a["recs"], a["n_images"], a["cps"], a["lps"], C.c_int32(a["n_captures"])))
+        self._batch_pending = a
+
+    def batch_cluster_info(self, cap_captures: int = 64, cap_lists: int = 64):
+        """agh_get_batch_cluster_info of the last clustered batch this context collected: a dict with, per capture,
+        n_foreground, n_components and n_objects (arrays), and per list of the call n_voxels (M_l) and ids (the object's
+        smallest capture-local voxel index, -1: none), in list order."""
+        info = (AghClusterInfo * max(cap_captures, 1))()
+        for r in info:
+            r.n_foreground = -2
+        m = np.full(max(cap_lists, 1), -2, np.int64)
+        ids = np.full(max(cap_lists, 1), -2, np.int32)
+        self._check(self.lib.agh_get_batch_cluster_info(self._h, info, _p(m, C.c_int64), _p(ids, C.c_int32), C.c_int32(cap_captures),
+                                                        C.c_int32(cap_lists)))
+        rows = [r for r in info if r.n_foreground > -2]
+        return {"n_foreground": np.array([r.n_foreground for r in rows], np.int64),
+                "n_components": np.array([r.n_components for r in rows], np.int64),
+                "n_objects": np.array([r.n_objects for r in rows], np.int64),
+                "n_voxels": m[m > -2].copy(), "ids": ids[ids > -2].copy()}
+
+    def batch_cluster_labels(self, cap: int | None = None) -> np.ndarray:
+        """agh_get_batch_cluster_labels: per voxel of the bound batch, in cloud()'s order, 0 or object + 1 (the object being
+        capture-local), of the last clustered batch collected."""
+        cap = int(self.n) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), np.uint8)
+        nv = self._check(self.lib.agh_get_batch_cluster_labels(self._h, C.c_void_p(out.ctypes.data), C.c_int64(cap)))
+        return out[:nv].copy()
 
     def localize_batch_stage(self, captures):
         """agh_localize_batch_stage: the NEXT batch's host captures up on a second stream, beside the chain in flight.  Returns

@@ -364,6 +364,13 @@ struct Ctx
   int64_t batch_mask_counts[kMaxClouds] = {};  // ... and its M_k
   int32_t batch_label_lists = 0;      // the lists of the last chain collected if it was a labelled batch, else 0
   int64_t batch_label_counts[kMaxClouds] = {};  // ... and its M_{k,j}, in list order
+  // agh_localize_batch_clustered*: the captures of the last chain collected if it was a clustered batch, else 0; its lists, the
+  // voxels of its bound batch, per capture foreground / components / objects / qualifying, per list M_l and the capture-local id
+  int32_t batch_cluster_captures = 0, batch_cluster_lists = 0;
+  int64_t batch_cluster_nv = 0;
+  int64_t batch_cluster_info[kMaxClouds][4] = {};
+  int64_t batch_cluster_sizes[kMaxClouds] = {};
+  int32_t batch_cluster_ids[kMaxClouds] = {};
   // agh_localize_depth* (depth.hip): a host capture's depth images, rows packed, image k at depth_image_offset(k); the NEXT
   // capture's (agh_localize_depth_stage) in the second buffer; the two change places when a staged set is adopted
   uint8_t* d_depth = nullptr;
@@ -777,6 +784,14 @@ struct ClusterDev
 };
 int sample_cluster_stage(Ctx* c, int64_t n, const ClusterDev& cp, int K, int64_t S, unsigned long long seed, int32_t* d_out,
   int32_t* h_out, hipStream_t st);
+inline ClusterDev cluster_dev(const agh_cluster_params& q)
+{
+  return ClusterDev{ { q.plane[0], q.plane[1], q.plane[2], q.plane[3] }, q.min_height, q.max_height, q.tolerance,
+    (float) (q.tolerance * q.tolerance), q.min_voxels };
+}
+// the rules of one agh_cluster_params record (include/agh.h, agh_localize_clustered, 7): what is wrong with it, naming the field,
+// or "" -- the single call's text as it is, a batch's behind "capture k: " (localize.hip)
+std::string cluster_params_fault(const agh_cluster_params& cp);
 // ... and on the C slots of a batch's bitmap (vb.slot_words words each): slot k's counts at blk + k * slot_words / 4096, not scanned
 int vox_count_blocks_batch(const VoxBatch& vb, int C, const unsigned* d_bitmap, int* d_blk, hipStream_t st);
 // sample_mask.hip: the masked sample list of a batch chain whose preprocessing (vox_batch) is queued on st (include/agh.h,
@@ -825,6 +840,10 @@ struct BatchLabelStage
   int32_t* h_out = nullptr;         // pinned: S_tot capture-local indices
 };
 int sample_label_stage_batch(Ctx* c, const BatchLabelStage& m, hipStream_t st);
+// ... in two parts, as the single chain's: the compaction of c->d_label_set into the L lists with their draw, shared with
+// sample_cluster.hip's batch stage, which fills the object sets from the clouds with one ClusterDev record per capture
+int label_compact_stage_batch(Ctx* c, const BatchLabelStage& m, bool any, hipStream_t st);
+int sample_cluster_stage_batch(Ctx* c, const BatchLabelStage& m, const ClusterDev* cps, hipStream_t st);
 int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
   unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st);
 // host mirror of the handle search's results (pinned memory of the context; all nullptr / 0: none)

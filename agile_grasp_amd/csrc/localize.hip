@@ -270,6 +270,27 @@ static_assert(sizeof(agh_label_image) == sizeof(agh_sample_mask) && offsetof(agh
                 offsetof(agh_label_image, row_stride_bytes) == offsetof(agh_sample_mask, row_stride_bytes),
   "a label image is read as a sample mask whose bytes are labels");
 
+std::string agh::cluster_params_fault(const agh_cluster_params& cp)
+{
+  const double* q = cp.plane;
+  const char* field[7] = { "plane[0]", "plane[1]", "plane[2]", "plane[3]", "min_height", "max_height", "tolerance" };
+  const double value[7] = { q[0], q[1], q[2], q[3], cp.min_height, cp.max_height, cp.tolerance };
+  for (int k = 0; k < 7; k++)
+    if (!std::isfinite(value[k]))
+      return std::string(field[k]) + " is not finite";
+  if (std::fabs(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) - 1.0) > 1e-6)
+    return "plane: (a, b, c) must be a unit vector (|a^2 + b^2 + c^2 - 1| <= 1e-6)";
+  if (cp.min_height >= cp.max_height)
+    return "min_height must be below max_height";
+  if (!(cp.tolerance > 0.0) || cp.tolerance > 0.05)
+    return "tolerance must be in (0, 0.05]";
+  if (cp.min_voxels < 1)
+    return "min_voxels must be >= 1";
+  if (cp.max_objects < 1 || cp.max_objects > kMaxClouds)
+    return "max_objects must be 1 .. 64";
+  return std::string();
+}
+
 static int mask_check(Ctx* c, const MaskSource* mask, const DepthSource* depth, const agh_localize_params* lp)
 {
   auto bad = [&](const std::string& what) {
@@ -279,22 +300,9 @@ static int mask_check(Ctx* c, const MaskSource* mask, const DepthSource* depth, 
   if (mask->cluster)
   {
     const agh_cluster_params& cp = *mask->cluster;
-    const double* q = cp.plane;
-    const char* field[7] = { "plane[0]", "plane[1]", "plane[2]", "plane[3]", "min_height", "max_height", "tolerance" };
-    const double value[7] = { q[0], q[1], q[2], q[3], cp.min_height, cp.max_height, cp.tolerance };
-    for (int k = 0; k < 7; k++)
-      if (!std::isfinite(value[k]))
-        return bad(std::string(field[k]) + " is not finite");
-    if (std::fabs(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) - 1.0) > 1e-6)
-      return bad("plane: (a, b, c) must be a unit vector (|a^2 + b^2 + c^2 - 1| <= 1e-6)");
-    if (cp.min_height >= cp.max_height)
-      return bad("min_height must be below max_height");
-    if (!(cp.tolerance > 0.0) || cp.tolerance > 0.05)
-      return bad("tolerance must be in (0, 0.05]");
-    if (cp.min_voxels < 1)
-      return bad("min_voxels must be >= 1");
-    if (cp.max_objects < 1 || cp.max_objects > kMaxClouds)
-      return bad("max_objects must be 1 .. 64");
+    const std::string fault = cluster_params_fault(cp);
+    if (!fault.empty())
+      return bad(fault);
     if ((int64_t) cp.max_objects * lp->n_samples > (1 << 24))
       return bad("max_objects x n_samples exceeds 2^24");
     if (lp->sample_idx)
@@ -518,10 +526,7 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   // ---- 3. the sample list ----
   if (L.clustered)  // (the grid build is queued: the preprocessing above bound the voxelised cloud)
   {
-    const agh_cluster_params& q = L.cluster;
-    const ClusterDev cp{ { q.plane[0], q.plane[1], q.plane[2], q.plane[3] }, q.min_height, q.max_height, q.tolerance,
-      (float) (q.tolerance * q.tolerance), q.min_voxels };
-    if ((rc = sample_cluster_stage(c, n, cp, K, S, (unsigned long long) lp->sample_seed, c->d_idx_own, h_idx_labeled, st)) != AGH_OK)
+    if ((rc = sample_cluster_stage(c, n, cluster_dev(L.cluster), K, S, (unsigned long long) lp->sample_seed, c->d_idx_own, h_idx_labeled, st)) != AGH_OK)
       return chain_fail(c, rc);
   }
   else if (K)  // (for S = 0 too, as the mask's)
@@ -571,6 +576,7 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
   c->cluster_objects = 0;
   c->batch_mask_captures = 0;
   c->batch_label_lists = 0;
+  c->batch_cluster_captures = 0;
   const int64_t S = L.S;
   const HandlePins pin = handle_pins(c);
   const int* h_counts = pin.counts;

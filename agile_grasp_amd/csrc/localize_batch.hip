@@ -39,8 +39,16 @@ struct BatchCall
   // agh_localize_batch_labeled*: the bytes there are labels 1 .. n_objects[k]; first_list: the exclusive prefix sum of n_objects
   bool labeled = false;
   std::vector<int32_t> n_objects, first_list;
+  // agh_localize_batch_clustered*: no bytes; capture k's objects are the components of its own cloud under cp[k], n_objects[k] =
+  // cp[k].max_objects lists each (first_list as the labelled batch's).  A repeat of the pass reads the records here.
+  bool clustered = false;
+  std::vector<agh_cluster_params> cp;
+  bool per_object() const { return labeled || clustered; }  // (a list per (capture, object))
   // the chain's name in the texts of the errors found behind a synchronisation
-  const char* who() const { return labeled ? "agh_localize_batch_labeled" : "agh_localize_batch"; }
+  const char* who() const
+  {
+    return clustered ? "agh_localize_batch_clustered" : (labeled ? "agh_localize_batch_labeled" : "agh_localize_batch");
+  }
 };
 
 struct LocalizeBatchState
@@ -87,6 +95,10 @@ struct LocalizeBatchState
   // (d_mask, d_mptr), the stage's own buffers are the context's
   LabelCapture* d_lcap = nullptr;     // kMaxClouds
   LabelCapture* h_lcap = nullptr;     // pinned
+  // clusters (sample_cluster.hip, sample_cluster_stage_batch), made by the first clustered batch: the captures' records as the
+  // kernels take them; the lists' table is the labelled batch's (d_lcap), the stage's own buffers are the context's
+  ClusterDev* d_ccap = nullptr;       // kMaxClouds
+  ClusterDev* h_ccap = nullptr;       // pinned
 };
 
 void localize_batch_release(Ctx* c)
@@ -95,11 +107,11 @@ void localize_batch_release(Ctx* c)
   if (!b)
     return;
   void* dev[] = { b->d_tab, b->d_local, b->d.hands, b->d.bits, b->d.rowcnt, b->d.first, b->d.n, b->d.idx, b->d.counts, b->d.tmp,
-    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2, b->d_mask, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist, b->d_lcap };
+    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2, b->d_mask, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist, b->d_lcap, b->d_ccap };
   for (void* p : dev)
     if (p)
       (void) hipFree(p);
-  void* host[] = { b->h_tab, b->h_samples, b->h_counts, b->h_bad, b->h_desc, b->h_hands, b->h_handles, b->h_idx, b->h_vcap, b->h_mptr, b->h_mtotal, b->h_lcap };
+  void* host[] = { b->h_tab, b->h_samples, b->h_counts, b->h_bad, b->h_desc, b->h_hands, b->h_handles, b->h_idx, b->h_vcap, b->h_mptr, b->h_mtotal, b->h_lcap, b->h_ccap };
   for (void* p : host)
     if (p)
       (void) hipHostFree(p);
@@ -340,6 +352,19 @@ int ensure_label_tables(Ctx* c, LocalizeBatchState* b)
   return AGH_OK;
 }
 
+// a clustered batch's tables: its lists, and the captures' cluster records
+int ensure_cluster_tables(Ctx* c, LocalizeBatchState* b)
+{
+  int rc;
+  if ((!b->d_lcap || !b->h_lcap) &&
+      ((rc = dev_alloc(c, &b->d_lcap, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_lcap, (size_t) kMaxClouds))))
+    return rc;
+  if ((!b->d_ccap || !b->h_ccap) &&
+      ((rc = dev_alloc(c, &b->d_ccap, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_ccap, (size_t) kMaxClouds))))
+    return rc;
+  return AGH_OK;
+}
+
 // The list table of the call, on the host and queued to the device: list l's span of the sample list, its capture's sample
 // count, seed and workspace (B.lp[list_cap[l]]), and which object of it the list is.
 int fill_list_table(Ctx* c, LocalizeBatchState* b, hipStream_t st)
@@ -438,7 +463,40 @@ struct BatchMaskSource
   const char* who;
   const int32_t* n_objects = nullptr;  // agh_localize_batch_labeled*: the bytes are labels 1 .. n_objects[k] (NULL: masks)
   bool labeled = false;
+  // agh_localize_batch_clustered*: no bytes at all, n_captures records; capture k has cluster[k].max_objects lists
+  const agh_cluster_params* cluster = nullptr;
+  bool clustered = false;
+  bool per_object() const { return labeled || clustered; }
+  int32_t objects(int k) const { return clustered ? cluster[k].max_objects : n_objects[k]; }
 };
+
+// the rules a clustered batch adds (include/agh.h, agh_localize_batch_clustered*, 4); the text names the capture and the field
+int batch_cluster_check(Ctx* c, const BatchMaskSource* mask, const agh_localize_params* lp, int C)
+{
+  auto bad = [&](const std::string& what) {
+    c->err = std::string(mask->who) + ": " + what;
+    return AGH_ERR_INVALID_ARGUMENT;
+  };
+  if (!mask->cluster)
+    return bad("cp is NULL (every capture of a clustered batch has its agh_cluster_params record)");
+  int64_t lists = 0, samples = 0;
+  for (int k = 0; k < C; k++)
+  {
+    const std::string cap = "capture " + std::to_string(k);
+    const std::string fault = cluster_params_fault(mask->cluster[k]);
+    if (!fault.empty())
+      return bad(cap + ": " + fault);
+    lists += mask->cluster[k].max_objects;
+    samples += (int64_t) mask->cluster[k].max_objects * lp[k].n_samples;
+    if (lists > kMaxClouds)
+      return bad(cap + ": more than 64 lists in all (the sum of max_objects up to this capture)");
+    if (samples > (1 << 24))
+      return bad(cap + ": more than 2^24 samples in all (the sum of max_objects x n_samples up to this capture)");
+    if (lp[k].sample_idx)
+      return bad(cap + ": sample_idx must be NULL (the lists are drawn on the objects the call finds)");
+  }
+  return AGH_OK;
+}
 
 // the rules a labelled batch adds (include/agh.h, agh_localize_batch_labeled*, 1 and 2); the text names the capture (and the image)
 int batch_label_check(Ctx* c, const BatchMaskSource* mask, const DepthBatchSource* depth, const agh_localize_params* lp, int C)
@@ -743,6 +801,35 @@ int batch_pass(agh_ctx* ctx)
     if ((rc = sample_mask_stage_batch(c, m, st)) != AGH_OK)
       return chain_fail(c, rc);
   }
+  else if (B.clustered)  // (for S_tot = 0 too: the objects found are a result of their own)
+  {
+    if ((rc = ensure_cluster_tables(c, b)) != AGH_OK)
+      return chain_fail(c, rc);
+    for (int k = 0; k < C; k++)
+    {
+      b->h_lcap[k] = LabelCapture{ B.n_objects[k], B.first_list[k] };
+      b->h_ccap[k] = cluster_dev(B.cp[k]);
+    }
+    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_lcap, b->h_lcap, sizeof(LabelCapture) * (size_t) C, hipMemcpyHostToDevice, st),
+      chain_fail(c, AGH_ERR_HIP));
+    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_ccap, b->h_ccap, sizeof(ClusterDev) * (size_t) C, hipMemcpyHostToDevice, st),
+      chain_fail(c, AGH_ERR_HIP));
+    BatchLabelStage m;  // (no labels, codes or bitmaps: the object sets come from the clouds, behind the grid build queued above)
+    m.vb = vb;
+    m.C = C;
+    m.L = B.L;
+    m.n_max = n_max;
+    m.n_tot = n_tot;
+    m.S_tot = S_tot;
+    m.cell = cell;
+    m.lists = b->d_lcap;
+    m.cloud_off = c->d_cloud_off;
+    m.tab = b->d_tab;
+    m.d_out = c->d_idx_own;
+    m.h_out = b->h_samples;
+    if ((rc = sample_cluster_stage_batch(c, m, b->d_ccap, st)) != AGH_OK)
+      return chain_fail(c, rc);
+  }
   else if (B.labeled)  // (for S_tot = 0 too, as the masks')
   {
     if ((rc = ensure_label_tables(c, b)) != AGH_OK)
@@ -851,14 +938,14 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     n_tot += n[k];
     S_tot += p.n_samples;
   }
-  const bool labeled = mask && mask->labeled;
-  if (labeled)  // (before the sums' limits: a labelled batch counts its samples per list, and says which capture went too far)
+  const bool labeled = mask && mask->labeled, clustered = mask && mask->clustered;
+  if (labeled || clustered)  // (before the sums' limits: such a batch counts its samples per list, and says which capture went too far)
   {
-    if (int rc = batch_label_check(c, mask, depth, lp, C))
+    if (int rc = clustered ? batch_cluster_check(c, mask, lp, C) : batch_label_check(c, mask, depth, lp, C))
       return rc;
     S_tot = 0;
     for (int k = 0; k < C; k++)
-      S_tot += (int64_t) mask->n_objects[k] * lp[k].n_samples;
+      S_tot += (int64_t) mask->objects(k) * lp[k].n_samples;
   }
   if (n_tot >= (1ll << 30) || S_tot > (1 << 24))
   {
@@ -873,7 +960,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   if (cam_table_mismatch(c, who.c_str(), C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
     return AGH_ERR_INVALID_ARGUMENT;                    // the table stays the context's until agh_localize_batch_end: the setter
                                                         // refuses mid-chain, so the repeats search with it too)
-  if (mask && !labeled)
+  if (mask && !labeled && !clustered)
     if (int rc = batch_mask_check(c, mask, depth, lp, C))
       return rc;
   double x1 = 0.0, x2 = 0.0;
@@ -903,8 +990,8 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     B.raw_off[k] = o;
   for (int k = 0; k < C; k++)
   {
-    const int K = labeled ? mask->n_objects[k] : 1;
-    if (labeled)
+    const int K = labeled || clustered ? mask->objects(k) : 1;
+    if (labeled || clustered)
     {
       B.n_objects.push_back(K);
       B.first_list.push_back((int32_t) B.list_cap.size());
@@ -917,6 +1004,9 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   }
   B.L = (int) B.list_cap.size();
   B.labeled = labeled;
+  B.clustered = clustered;
+  if (clustered)
+    B.cp.assign(mask->cluster, mask->cluster + C);
   B.soff.resize((size_t) B.L + 1);
   B.soff[0] = 0;
   for (int l = 0; l < B.L; l++)
@@ -980,7 +1070,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
       off += n[k] * (B.dev_stride[k] / 4);
     }
   }
-  if (mask && (rc = batch_masks_to_device(c, b, mask, depth, st)) != AGH_OK)
+  if (mask && !mask->clustered && (rc = batch_masks_to_device(c, b, mask, depth, st)) != AGH_OK)
     return chain_fail(c, rc);  // (the captures' copies may be in flight)
   ActiveGuard guard(c);
   if ((rc = batch_pass(ctx)) != AGH_OK)
@@ -1014,6 +1104,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   c->cluster_objects = 0;  // (... and no clusters)
   c->batch_mask_captures = 0;  // (agh_get_batch_mask_counts: set below, behind the synchronisation, if this batch is masked)
   c->batch_label_lists = 0;    // (agh_get_batch_label_counts likewise, if it is labelled)
+  c->batch_cluster_captures = 0;  // (agh_get_batch_cluster_info / _labels likewise, if it is clustered)
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)
@@ -1068,6 +1159,22 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   std::vector<int64_t> voff(C + 1, 0), nv((size_t) B.L);
   for (int k = 0; k < C; k++)
     voff[k + 1] = voff[k] + (int64_t) (b->h_desc[k].n_vox[0] + b->h_desc[k].n_vox[1]);
+  if (B.clustered)
+  {
+    // (the table of k_cluster_select_batch: four counts per capture, then the M_l and the capture-local ids in list order; the
+    // M_l equal the compaction's h_label_counts)
+    const long long* t = c->h_cluster_table;
+    for (int k = 0; k < C; k++)
+      std::copy(t + 4 * k, t + 4 * k + 4, c->batch_cluster_info[k]);
+    for (int l = 0; l < B.L; l++)
+    {
+      c->batch_cluster_sizes[l] = (int64_t) t[4 * kMaxClouds + l];
+      c->batch_cluster_ids[l] = (int32_t) t[5 * kMaxClouds + l];
+    }
+    c->batch_cluster_nv = voff[C];
+    c->batch_cluster_lists = B.L;
+    c->batch_cluster_captures = C;
+  }
   for (int l = 0; l < B.L; l++)  // (a list's voxel count is its capture's)
     nv[l] = voff[B.list_cap[l] + 1] - voff[B.list_cap[l]];
   c->n_is_bound = false;
@@ -1098,12 +1205,12 @@ int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int6
   {
     // (a labelled batch has a record per list; arguments that do not say how many lists there are get none zeroed)
     int64_t lists = n_captures;
-    if (mask && mask->labeled)
+    if (mask && mask->per_object())
     {
       lists = 0;
-      if (mask->n_objects && n_captures >= 1 && n_captures <= kMaxClouds)
+      if ((mask->clustered ? mask->cluster != nullptr : mask->n_objects != nullptr) && n_captures >= 1 && n_captures <= kMaxClouds)
         for (int k = 0; k < n_captures && lists <= kMaxClouds; k++)
-          lists = mask->n_objects[k] >= 1 && mask->n_objects[k] <= kMaxClouds ? lists + mask->n_objects[k] : kMaxClouds + 1;
+          lists = mask->objects(k) >= 1 && mask->objects(k) <= kMaxClouds ? lists + mask->objects(k) : kMaxClouds + 1;
     }
     zero_results(results, lists <= kMaxClouds ? (int) lists : 0);
   }
@@ -1138,10 +1245,10 @@ int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t
   int rc;
   const int* hc = b->h_counts;
   std::vector<std::string> names;
-  if (B.labeled)
+  if (B.per_object())
     for (int l = 0; l < C; l++)
       names.push_back("capture " + std::to_string(B.list_cap[l]) + ", object " + std::to_string(B.list_obj[l]));
-  if ((rc = chain_collect(ctx, who, unit, C, hc, kBatchCountsStride, S_tot, b->h_bad, batch_queue, B.labeled ? &names : nullptr)) != AGH_OK)
+  if ((rc = chain_collect(ctx, who, unit, C, hc, kBatchCountsStride, S_tot, b->h_bad, batch_queue, B.per_object() ? &names : nullptr)) != AGH_OK)
     return rc;
   int64_t n_hyp_tot = 0, tot_handles = 0, tot_idx = 0, tot_hands = 0;
   for (int k = 0; k < C; k++)
@@ -1495,6 +1602,155 @@ int agh_get_batch_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_li
   }
   std::copy(c->batch_label_counts, c->batch_label_counts + c->batch_label_lists, n_eligible);
   return AGH_OK;
+}
+
+// ---- the clustered forms (include/agh.h): the labelled batch chains with every capture's own connected components as its objects ----
+
+static BatchMaskSource cluster_source(const agh_cluster_params* cp, const char* who)
+{
+  BatchMaskSource m{ nullptr, nullptr, false, who };
+  m.cluster = cp;
+  m.clustered = true;
+  return m;
+}
+
+int agh_localize_batch_clustered(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  const BatchMaskSource m = cluster_source(cp, "agh_localize_batch_clustered");
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, nullptr, &m);
+}
+
+int agh_localize_batch_clustered_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  const BatchMaskSource m = cluster_source(cp, "agh_localize_batch_clustered_device");
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, nullptr, &m);
+}
+
+int agh_localize_batch_clustered_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const BatchMaskSource m = cluster_source(cp, "agh_localize_batch_clustered_begin");
+  return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, nullptr, &m);
+}
+
+int agh_localize_batch_clustered_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const BatchMaskSource m = cluster_source(cp, "agh_localize_batch_clustered_begin_device");
+  return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, nullptr, &m);
+}
+
+int agh_localize_depth_batch_clustered(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_clustered" };
+  const BatchMaskSource m = cluster_source(cp, src.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src, &m);
+}
+
+int agh_localize_depth_batch_clustered_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_clustered_device" };
+  const BatchMaskSource m = cluster_source(cp, src.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src, &m);
+}
+
+int agh_localize_depth_batch_clustered_begin(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_clustered_begin" };
+  const BatchMaskSource m = cluster_source(cp, src.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+}
+
+int agh_localize_depth_batch_clustered_begin_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_clustered_begin_device" };
+  const BatchMaskSource m = cluster_source(cp, src.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+}
+
+// the last chain collected, if it was a clustered batch (`fn` refuses otherwise, and mid-chain)
+static int batch_cluster_getter_check(Ctx* c, const char* fn)
+{
+  if (refuse_mid_chain(c, fn))
+    return AGH_ERR_STATE;
+  if (c->batch_cluster_captures < 1)
+  {
+    c->err = std::string(fn) + ": the last chain this context collected was no clustered batch (or there was none)";
+    return AGH_ERR_STATE;
+  }
+  return AGH_OK;
+}
+
+int agh_get_batch_cluster_info(agh_ctx* ctx, agh_cluster_info* info, int64_t* n_voxels, int32_t* ids, int32_t cap_captures,
+  int32_t cap_lists)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (int rc = batch_cluster_getter_check(c, "agh_get_batch_cluster_info"))
+    return rc;
+  if (info && cap_captures < c->batch_cluster_captures)
+  {
+    c->err = "agh_get_batch_cluster_info: cap_captures is below the batch's n_captures";
+    return AGH_ERR_CAPACITY;
+  }
+  if ((n_voxels || ids) && cap_lists < c->batch_cluster_lists)
+  {
+    c->err = "agh_get_batch_cluster_info: cap_lists is below the call's number of lists";
+    return AGH_ERR_CAPACITY;
+  }
+  if (info)
+    for (int k = 0; k < c->batch_cluster_captures; k++)
+      info[k] = agh_cluster_info{ c->batch_cluster_info[k][0], c->batch_cluster_info[k][1], c->batch_cluster_info[k][2] };
+  if (n_voxels)
+    std::copy(c->batch_cluster_sizes, c->batch_cluster_sizes + c->batch_cluster_lists, n_voxels);
+  if (ids)
+    std::copy(c->batch_cluster_ids, c->batch_cluster_ids + c->batch_cluster_lists, ids);
+  return AGH_OK;
+}
+
+int agh_get_batch_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap)
+{
+  if (!ctx || !labels_out)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (int rc = batch_cluster_getter_check(c, "agh_get_batch_cluster_labels"))
+    return rc;
+  if (cap < c->batch_cluster_nv)
+  {
+    c->err = "agh_get_batch_cluster_labels: cap is below the bound batch's voxel count";
+    return AGH_ERR_CAPACITY;
+  }
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  if (c->batch_cluster_nv > 0)
+    AGH_HIPCHK(c, hipMemcpy(labels_out, c->d_cluster_label, (size_t) c->batch_cluster_nv, hipMemcpyDeviceToHost));
+  return (int) c->batch_cluster_nv;
 }
 
 // The NEXT batch's captures up, beside whatever runs on the context's stream (stage_captures, localize.hip).  A pinned source must

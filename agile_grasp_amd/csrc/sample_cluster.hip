@@ -14,6 +14,15 @@
 // From there the label stage's compaction runs unchanged (label_compact_stage).  Everything is queued on the chain's stream behind
 // the grid build; launches are sized from the raw point count, the voxel count and the grid's descriptor are read on the device.
 //
+// The batch forms (include/agh.h, agh_localize_batch_clustered*; DESIGN.md, "Clusters in the batch chains") run the same five steps
+// once for all captures, capture = blockIdx.y (blockIdx.x for the selection): k_cluster_init_batch, k_cluster_link_batch,
+// k_cluster_flatten_batch, k_cluster_select_batch, k_cluster_mark_batch around the SAME bodies (cluster_init_voxel ...
+// cluster_mark_voxel below).  parent / size / label lie over the COMMON voxel array, capture k's voxels at cloud_off[k]; the
+// union-find's indices are the ones the cell-sorted array carries, positions in that common array, so capture k's roots are its
+// smallest COMMON indices, which are its smallest capture-local ones too (ids are reported less cloud_off[k]).  Capture k walks
+// its own grid descriptor and cell table and unites only what ITS cells hold: no pair is formed across captures.  From there the
+// labelled batch's compaction runs unchanged (label_compact_stage_batch).
+//
 // Nothing depends on the order of an atomic operation: the union-find hooks the LARGER root under the smaller one, so a finished
 // component's root is its smallest voxel index whatever the order; sizes and counts are integer sums; the selection's keys are
 // distinct.
@@ -86,23 +95,40 @@ __device__ __forceinline__ void cluster_unite(int* parent, int a, int b)
   }
 }
 
-// counts: [0] foreground voxels, [1] components (zeroed in front of the launch)
-__global__ __launch_bounds__(256) void k_cluster_init(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
-  int64_t n, ClusterDev cp, int* __restrict__ parent, int* __restrict__ size, unsigned long long* __restrict__ counts)
+// counts: [0] foreground voxels, [1] components (zeroed in front of the launch).  The cloud's nv voxels start at `base` of the
+// voxel array (0 for a single cloud, cloud_off[k] in a batch): the index a voxel is known by is base + its local one.
+__device__ __forceinline__ void cluster_init_voxel(const float* __restrict__ xyz, int64_t stride, int64_t base, int64_t nv,
+  const ClusterDev& cp, int* __restrict__ parent, int* __restrict__ size, unsigned long long* __restrict__ counts)
 {
-  const int64_t nv = label_voxels(d, n);
   const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
   bool fg = false;
   if (v < nv)
   {
-    const float* p = xyz + v * stride;
+    const float* p = xyz + (base + v) * stride;
     fg = cluster_foreground(cp, p[0], p[1], p[2]);
-    parent[v] = fg ? (int) v : -1;
-    size[v] = 0;
+    parent[base + v] = fg ? (int) (base + v) : -1;
+    size[base + v] = 0;
   }
   const unsigned long long m = __ballot(fg);
   if ((threadIdx.x & 63) == 0 && m)
     atomicAdd(counts, (unsigned long long) __popcll(m));
+}
+
+__global__ __launch_bounds__(256) void k_cluster_init(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
+  int64_t n, ClusterDev cp, int* __restrict__ parent, int* __restrict__ size, unsigned long long* __restrict__ counts)
+{
+  cluster_init_voxel(xyz, stride, 0, label_voxels(d, n), cp, parent, size, counts);
+}
+
+// ... for capture blockIdx.y of a batch, with ITS record of the device table and its four counters (no voxel for a capture whose
+// descriptor carries an error: label_voxels)
+__global__ __launch_bounds__(256) void k_cluster_init_batch(VoxBatch vb, const float* __restrict__ xyz, int64_t stride,
+  const int* __restrict__ cloud_off, const ClusterDev* __restrict__ cps, int* __restrict__ parent, int* __restrict__ size,
+  unsigned long long* __restrict__ counts)
+{
+  const int k = blockIdx.y;
+  const ClusterDev cp = cps[k];
+  cluster_init_voxel(xyz, stride, cloud_off[k], label_voxels(vb.desc + k, vb.cap[k].n), cp, parent, size, counts + 4 * k);
 }
 
 // Work goes out by GROUP of kClusterGroupX cells along x of one (y, z) row of the search grid: the group's voxels are one run
@@ -113,13 +139,13 @@ __global__ __launch_bounds__(256) void k_cluster_init(const float* __restrict__ 
 // offsets -- where a geometric ball would have to reach outwards through an open face -- find such pairs too.
 // The candidates pass through LDS a tile at a time, background ones already marked, and every owner tests the whole tile with the
 // float32 rule; a pair is united once, from the side with the larger voxel index.
-__global__ __launch_bounds__(kClusterTile) void k_cluster_link(GridView gv, const VoxDesc* __restrict__ d, ClusterDev cp, int* parent)
+// (gv: the view of ONE cloud's grid -- its descriptor, its cell table; the whole work-group comes here, and the work-groups
+// along x share the cloud's cell groups)
+__device__ __forceinline__ void cluster_link_groups(const GridView& gv, const ClusterDev& cp, int* parent)
 {
   __shared__ float4 cand[kClusterTile];
   __shared__ int row_begin[kClusterRows];
   __shared__ int row_prefix[64 + 1];
-  if (d->error)
-    return;
   const GridDesc g = *gv.desc;
   const int tid = threadIdx.x;
   // (the margin covers the rounding of the float32 rule: a pair may pass it a few ulp beyond `tolerance`)
@@ -224,15 +250,37 @@ __global__ __launch_bounds__(kClusterTile) void k_cluster_link(GridView gv, cons
   }
 }
 
+__global__ __launch_bounds__(kClusterTile) void k_cluster_link(GridView gv, const VoxDesc* __restrict__ d, ClusterDev cp, int* parent)
+{
+  if (d->error)
+    return;
+  cluster_link_groups(gv, cp, parent);
+}
+
+// ... for capture blockIdx.y of a batch: the cell groups of ITS descriptor and cell table, shared among the gridDim.x work-groups
+// of its row of the launch.  The voxel indices in the cell-sorted array are positions in the common voxel array, and so are the
+// parents: the invariant parent[x] <= x, a word only ever decreases, the larger root under the smaller, reads the same, and a
+// finished component's root is its smallest common index.  Its candidates come from its own cell table, whose runs lie inside the
+// capture's span of the sorted array: no pair reaches into another capture, whatever the coordinates.
+__global__ __launch_bounds__(kClusterTile) void k_cluster_link_batch(GridView gv, VoxBatch vb, const ClusterDev* __restrict__ cps,
+  int* parent)
+{
+  const int k = blockIdx.y;
+  if (vb.desc[k].error)
+    return;
+  const ClusterDev cp = cps[k];
+  cluster_link_groups(grid_of_cloud(gv, k), cp, parent);
+}
+
 // parent[v] = the root of v (the links are all made: the kernel before this one has ended), the roots' sizes and their number.
 // The lanes of a wave that share a root -- most of them do -- add to its counter once.
-__global__ __launch_bounds__(256) void k_cluster_flatten(const VoxDesc* __restrict__ d, int64_t n, int* parent, int* size,
+// (the cloud's nv voxels at `base` of the voxel array, as cluster_init_voxel)
+__device__ __forceinline__ void cluster_flatten_voxel(int64_t base, int64_t nv, int* parent, int* size,
   unsigned long long* __restrict__ counts)
 {
-  const int64_t nv = label_voxels(d, n);
-  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t v = base + (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
   int r = -1;
-  if (v < nv && cluster_load(parent + v) >= 0)
+  if (v < base + nv && cluster_load(parent + v) >= 0)
   {
     r = cluster_find(parent, (int) v);
     atomicMin(parent + v, r);
@@ -253,25 +301,39 @@ __global__ __launch_bounds__(256) void k_cluster_flatten(const VoxDesc* __restri
   }
 }
 
+__global__ __launch_bounds__(256) void k_cluster_flatten(const VoxDesc* __restrict__ d, int64_t n, int* parent, int* size,
+  unsigned long long* __restrict__ counts)
+{
+  cluster_flatten_voxel(0, label_voxels(d, n), parent, size, counts);
+}
+
+__global__ __launch_bounds__(256) void k_cluster_flatten_batch(VoxBatch vb, const int* __restrict__ cloud_off, int* parent, int* size,
+  unsigned long long* __restrict__ counts)
+{
+  const int k = blockIdx.y;
+  cluster_flatten_voxel(cloud_off[k], label_voxels(vb.desc + k, vb.cap[k].n), parent, size, counts + 4 * k);
+}
+
 // One work-group.  list (n entries of scratch): the roots of size >= min_voxels, in any order; then at most K passes, pass j
 // taking the largest key (size << 32) | (0xFFFFFFFF - id) below pass j - 1's -- the keys are distinct, so nothing is marked and
 // the outcome does not depend on the list's order.  table (pinned): [0] foreground, [1] components, [2] objects = min(qualifying,
 // K), [3] qualifying; [8 + j] M_j; [8 + 64 + j] id_j (-1: none).
 constexpr int kClusterTableSizes = 8, kClusterTableIds = 8 + kMaxClouds, kClusterTableWords = 8 + 2 * kMaxClouds;
-__global__ __launch_bounds__(1024) void k_cluster_select(const VoxDesc* __restrict__ d, int64_t n, int min_voxels, int K,
-  const int* __restrict__ parent, int* size, int32_t* __restrict__ list, const unsigned long long* __restrict__ counts,
-  long long* __restrict__ table)
+// (the body: one cloud's nv voxels at `base`; list holds LOCAL indices, at most nv of them; info: 4 words; sizes, ids: n_out
+// entries each, the ids local)
+__device__ __forceinline__ void cluster_select_roots(int64_t base, int64_t nv, int min_voxels, int K, const int* __restrict__ parent,
+  int* size, int32_t* __restrict__ list, const unsigned long long* __restrict__ counts, long long* __restrict__ info,
+  long long* __restrict__ sizes, long long* __restrict__ ids, int n_out)
 {
   __shared__ int n_list;
   __shared__ unsigned long long best;
   __shared__ unsigned long long picked[kMaxClouds];
-  const int64_t nv = label_voxels(d, n);
   const int tid = threadIdx.x;
   if (tid == 0)
     n_list = 0;
   __syncthreads();
   for (int64_t v = tid; v < nv; v += 1024)
-    if (parent[v] == (int) v && size[v] >= min_voxels)
+    if (parent[base + v] == (int) (base + v) && size[base + v] >= min_voxels)
       list[atomicAdd(&n_list, 1)] = (int32_t) v;  // (at most nv <= n entries)
   __syncthreads();
   const int L = n_list;
@@ -286,7 +348,8 @@ __global__ __launch_bounds__(1024) void k_cluster_select(const VoxDesc* __restri
     for (int i = tid; i < L; i += 1024)
     {
       const int r = list[i];
-      const unsigned long long key = ((unsigned long long) (unsigned) size[r] << 32) | (unsigned long long) (0xFFFFFFFFu - (unsigned) r);
+      const unsigned long long key =
+        ((unsigned long long) (unsigned) size[base + r] << 32) | (unsigned long long) (0xFFFFFFFFu - (unsigned) r);
       if (key < prev && key > mine)
         mine = key;
     }
@@ -300,50 +363,92 @@ __global__ __launch_bounds__(1024) void k_cluster_select(const VoxDesc* __restri
     __syncthreads();
   }
   // (the passes have read the sizes: now the picked roots' words become their ranks)
-  if (tid < kMaxClouds)
+  if (tid < n_out)
   {
     long long m = 0, id = -1;
     if (tid < n_obj)
     {
       m = (long long) (picked[tid] >> 32);
       id = (long long) (0xFFFFFFFFu - (unsigned) (picked[tid] & 0xFFFFFFFFull));
-      size[id] = -1 - tid;
+      size[base + id] = -1 - tid;
     }
-    table[kClusterTableSizes + tid] = m;
-    table[kClusterTableIds + tid] = id;
+    sizes[tid] = m;
+    ids[tid] = id;
   }
   if (tid == 0)
   {
-    table[0] = (long long) counts[0];
-    table[1] = (long long) counts[1];
-    table[2] = n_obj;
-    table[3] = L;
+    info[0] = (long long) counts[0];
+    info[1] = (long long) counts[1];
+    info[2] = n_obj;
+    info[3] = L;
   }
+}
+
+__global__ __launch_bounds__(1024) void k_cluster_select(const VoxDesc* __restrict__ d, int64_t n, int min_voxels, int K,
+  const int* __restrict__ parent, int* size, int32_t* __restrict__ list, const unsigned long long* __restrict__ counts,
+  long long* __restrict__ table)
+{
+  cluster_select_roots(0, label_voxels(d, n), min_voxels, K, parent, size, list, counts, table, table + kClusterTableSizes,
+    table + kClusterTableIds, kMaxClouds);
+}
+
+// One work-group PER CAPTURE, capture blockIdx.x.  Its scratch list is its own region [code_off, code_off + n) of the list buffer
+// (code_off = raw_off[k]: the capture's first raw point; free until the compaction's emit), at most K_k picks, and the batch's
+// pinned table: [4 k .. 4 k + 3] capture k's counts as the single table's [0 .. 3]; [4 x 64 + l] M_l and [5 x 64 + l] id_l, the
+// capture-local smallest voxel index, for its lists l = first_list[k] + j, j < K_k.
+constexpr int kClusterBatchSizes = 4 * kMaxClouds, kClusterBatchIds = 5 * kMaxClouds, kClusterBatchWords = 6 * kMaxClouds;
+__global__ __launch_bounds__(1024) void k_cluster_select_batch(VoxBatch vb, const int* __restrict__ cloud_off,
+  const ClusterDev* __restrict__ cps, const LabelCapture* __restrict__ lc, const int* __restrict__ parent, int* size,
+  int32_t* __restrict__ list, const unsigned long long* __restrict__ counts, long long* __restrict__ table)
+{
+  const int k = blockIdx.x;
+  const VoxCapture* q = vb.cap + k;
+  const int first = lc[k].first_list;
+  cluster_select_roots(cloud_off[k], label_voxels(vb.desc + k, q->n), cps[k].min_voxels, lc[k].K, parent, size, list + q->code_off,
+    counts + 4 * k, table + 4 * k, table + kClusterBatchSizes + first, table + kClusterBatchIds + first, lc[k].K);
+}
+
+// (the cloud's nv voxels at `base` of the voxel array: objset and label are indexed as parent is)
+__device__ __forceinline__ void cluster_mark_voxel(int64_t base, int64_t nv, const int* __restrict__ parent,
+  const int* __restrict__ size, unsigned long long* __restrict__ objset, uint8_t* __restrict__ label)
+{
+  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv)
+    return;
+  const int r = parent[base + v];
+  const int s = r >= 0 ? size[r] : 0;
+  const int j = s < 0 ? -1 - s : -1;
+  objset[base + v] = j >= 0 ? 1ull << j : 0ull;
+  label[base + v] = (uint8_t) (j + 1);
 }
 
 __global__ __launch_bounds__(256) void k_cluster_mark(const VoxDesc* __restrict__ d, int64_t n, const int* __restrict__ parent,
   const int* __restrict__ size, unsigned long long* __restrict__ objset, uint8_t* __restrict__ label)
 {
-  const int64_t nv = label_voxels(d, n);
-  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= nv)
-    return;
-  const int r = parent[v];
-  const int s = r >= 0 ? size[r] : 0;
-  const int j = s < 0 ? -1 - s : -1;
-  objset[v] = j >= 0 ? 1ull << j : 0ull;
-  label[v] = (uint8_t) (j + 1);
+  cluster_mark_voxel(0, label_voxels(d, n), parent, size, objset, label);
 }
 
-// two ints and a byte per raw point, the counters and the pinned table: made by the first clustered call, grown with n
+// ... for capture blockIdx.y of a batch: objset[cloud_off[k] + v] = 1 << rank, bit j the capture-local object, where the labelled
+// batch's compaction reads it
+__global__ __launch_bounds__(256) void k_cluster_mark_batch(VoxBatch vb, const int* __restrict__ cloud_off,
+  const int* __restrict__ parent, const int* __restrict__ size, unsigned long long* __restrict__ objset, uint8_t* __restrict__ label)
+{
+  const int k = blockIdx.y;
+  cluster_mark_voxel(cloud_off[k], label_voxels(vb.desc + k, vb.cap[k].n), parent, size, objset, label);
+}
+
+// two ints and a byte per raw point, the counters and the pinned table: made by the first clustered call, grown with n.  The
+// counters (four per capture) and the table (4 words per capture, 2 per list) are sized for a batch of kMaxClouds captures and
+// lists at once: 2 KiB and 3 KiB, which the single chain shares.
+static_assert(kClusterBatchWords >= kClusterTableWords, "one pinned table serves the single chain and the batch");
 static int ensure_cluster_buffers(Ctx* c, int64_t n)
 {
   int rc;
   if (!c->d_cluster_counts)
   {
-    if ((rc = dev_alloc(c, &c->d_cluster_counts, 4)))
+    if ((rc = dev_alloc(c, &c->d_cluster_counts, (size_t) 4 * kMaxClouds)))
       return rc;
-    if (hipHostMalloc((void**) &c->h_cluster_table, sizeof(long long) * kClusterTableWords, hipHostMallocDefault) != hipSuccess)
+    if (hipHostMalloc((void**) &c->h_cluster_table, sizeof(long long) * kClusterBatchWords, hipHostMallocDefault) != hipSuccess)
     {
       c->h_cluster_table = nullptr;
       c->err = "hipHostMalloc failed (cluster table)";
@@ -397,6 +502,50 @@ int sample_cluster_stage(Ctx* c, int64_t n, const ClusterDev& cp, int K, int64_t
     return AGH_ERR_HIP;
   }
   return label_compact_stage(c, n, K, n > 0, S, seed, d_out, h_out, st);
+}
+
+// The stage over a batch (BatchLabelStage, agh_internal.h; its labels, codes and bitmaps are not read): one launch per step, the
+// capture on blockIdx.y (blockIdx.x for the selection), none that depends on n_captures or L.  cps: the device table of the
+// captures' records.  The launches are sized from n_max; k_cluster_link_batch takes min(ceil(n_max / 64), max(256, 32768 / C))
+// work-groups per capture, at most 32 768 in all (C <= 64): the single form gives one capture up to 4096, and a capture's busy
+// cell groups should not queue behind one another in a batch either -- with 4096 in all, eight captures of the bench scene
+// took 1676 us in this kernel, with 4096 each 1305 us (profiles/NOTES.md).  Work-groups beyond a capture's groups leave at once.
+int sample_cluster_stage_batch(Ctx* c, const BatchLabelStage& m, const ClusterDev* cps, hipStream_t st)
+{
+  int rc;
+  const int64_t n_groups = (m.n_max + kLabelGroup - 1) / kLabelGroup;
+  // (no label bytes, so no word ranks: the rank buffer keeps whatever size it has)
+  if ((rc = ensure_label_buffers(c, 0, m.n_tot, (int64_t) m.L * n_groups)) != AGH_OK ||
+      (rc = ensure_cluster_buffers(c, m.n_tot)) != AGH_OK)
+    return rc;
+  const unsigned Cy = (unsigned) m.C;
+  AGH_HIPCHK(c, hipMemsetAsync(c->d_cluster_counts, 0, sizeof(unsigned long long) * 4 * (size_t) m.C, st));
+  const unsigned blocks = (unsigned) ((m.n_max + 255) / 256);
+  if (m.n_max > 0)
+  {
+    // (the voxelised batch is the context's bound batch: the preprocessing queued in front of this stage bound it)
+    hipLaunchKernelGGL(k_cluster_init_batch, dim3(blocks, Cy), dim3(256), 0, st, m.vb, (const float*) c->d_xyz, c->stride_floats,
+      m.cloud_off, cps, c->d_cluster_parent, c->d_cluster_size, c->d_cluster_counts);
+    const GridView gv{ c->d_desc, c->d_cell_start, c->d_sorted, c->d_cloud_off, m.C };
+    const int64_t per_capture = std::min<int64_t>((m.n_max + 63) / 64, std::max(256, 32768 / m.C));
+    hipLaunchKernelGGL(k_cluster_link_batch, dim3((unsigned) per_capture, Cy), dim3(kClusterTile), 0, st, gv, m.vb, cps,
+      c->d_cluster_parent);
+    hipLaunchKernelGGL(k_cluster_flatten_batch, dim3(blocks, Cy), dim3(256), 0, st, m.vb, m.cloud_off, c->d_cluster_parent,
+      c->d_cluster_size, c->d_cluster_counts);
+  }
+  // (the lists' buffer is free until the compaction's emit: every capture's selection borrows its own region of it)
+  hipLaunchKernelGGL(k_cluster_select_batch, dim3(Cy), dim3(1024), 0, st, m.vb, m.cloud_off, cps, m.lists,
+    (const int*) c->d_cluster_parent, c->d_cluster_size, c->d_mask_list, (const unsigned long long*) c->d_cluster_counts,
+    c->h_cluster_table);
+  if (m.n_max > 0)
+    hipLaunchKernelGGL(k_cluster_mark_batch, dim3(blocks, Cy), dim3(256), 0, st, m.vb, m.cloud_off, (const int*) c->d_cluster_parent,
+      (const int*) c->d_cluster_size, c->d_label_set, c->d_cluster_label);
+  if (hipGetLastError() != hipSuccess)
+  {
+    c->err = "sample cluster launch failed";
+    return AGH_ERR_HIP;
+  }
+  return label_compact_stage_batch(c, m, m.n_max > 0, st);
 }
 
 }  // namespace agh

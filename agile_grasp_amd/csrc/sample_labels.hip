@@ -449,14 +449,28 @@ int sample_label_stage_batch(Ctx* c, const BatchLabelStage& m, hipStream_t st)
   if ((rc = ensure_label_buffers(c, (int64_t) m.C * W, m.n_tot, (int64_t) m.L * n_groups)) != AGH_OK)
     return rc;
   const unsigned Cy = (unsigned) m.C;
-  const LabelCapture* lc = m.lists;
-  if (m.n_max > 0 && nb > 0)
+  const bool any = m.n_max > 0 && nb > 0;
+  if (any)
   {
     AGH_HIPCHK(c, hipMemsetAsync(c->d_label_set, 0, (size_t) m.n_tot * 8, st));
     hipLaunchKernelGGL(k_vox_word_rank_batch, dim3((unsigned) nb, Cy), dim3(256), 0, st, m.vb, m.bitmap, c->d_label_rank);
     const int64_t label_words = (m.n_max + 3 + 3) / 4;  // (aligned words that a base up to 3 bytes into one can touch)
     hipLaunchKernelGGL(k_label_mark_batch, dim3((unsigned) ((label_words + 255) / 256), Cy), dim3(256), 0, st, m.vb, m.code, m.labels,
-      lc, m.cell, m.bitmap, m.blk2, (const unsigned*) c->d_label_rank, m.cloud_off, c->d_label_set);
+      m.lists, m.cell, m.bitmap, m.blk2, (const unsigned*) c->d_label_rank, m.cloud_off, c->d_label_set);
+  }
+  return label_compact_stage_batch(c, m, any, st);
+}
+
+// ... and its second part, shared with the clustered batch (sample_cluster.hip, sample_cluster_stage_batch), whose object sets
+// come from the clouds: the compaction of c->d_label_set into the L lists and the draw (any == false: no voxel, every list is
+// empty).  The label buffers are there (ensure_label_buffers).
+int label_compact_stage_batch(Ctx* c, const BatchLabelStage& m, bool any, hipStream_t st)
+{
+  const int64_t n_groups = (m.n_max + kLabelGroup - 1) / kLabelGroup;
+  const unsigned Cy = (unsigned) m.C;
+  const LabelCapture* lc = m.lists;
+  if (any)
+  {
     hipLaunchKernelGGL(k_label_count_batch, dim3((unsigned) n_groups, Cy), dim3(kLabelGroup), 0, st, m.vb,
       (const unsigned long long*) c->d_label_set, lc, m.cloud_off, n_groups, c->d_label_groups);
     hipLaunchKernelGGL(k_label_scan, dim3((unsigned) m.L), dim3(64), 0, st, c->d_label_groups, n_groups, c->d_label_totals);

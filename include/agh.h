@@ -286,10 +286,12 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_localize_clustered*, agh_localize_depth_clustered*,
  * agh_localize_batch_masked*, agh_localize_batch_masked_begin*, agh_localize_depth_batch_masked*,
  * agh_localize_depth_batch_masked_begin*, agh_localize_batch_labeled*, agh_localize_batch_labeled_begin*,
- * agh_localize_depth_batch_labeled* and agh_localize_depth_batch_labeled_begin* among them), agh_deproject, agh_deproject_batch,
+ * agh_localize_depth_batch_labeled*, agh_localize_depth_batch_labeled_begin*, agh_localize_batch_clustered*,
+ * agh_localize_batch_clustered_begin*, agh_localize_depth_batch_clustered* and agh_localize_depth_batch_clustered_begin* among
+ * them), agh_deproject, agh_deproject_batch,
  * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info,
  * agh_get_cluster_labels, agh_get_batch_mask_counts,
- * agh_get_batch_label_counts and every getter of device results (frames, normals,
+ * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -535,8 +537,9 @@ int agh_get_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_objects)
  *     AGH_ERR_STATE after a chain of another kind, if there was none, or while a chain is in flight; after a clustered call
  *     agh_get_label_counts and agh_get_sample_mask_count return AGH_ERR_STATE.
  * 10. A context that made a clustered call holds two 32-bit words and a byte per raw point beside the labelled chain's buffers.
- * Not built: a fitted plane (the caller supplies it); more than one capture per call; more than 64 objects; _begin / _end,
- * _stage, batch and sharded forms.  The 8192-hand limit holds per object. */
+ * Not built: a fitted plane (the caller supplies it); more than 64 objects; _begin / _end, _stage and sharded forms of this
+ * single-capture call.  Several captures per call, _begin / _end included, are agh_localize_batch_clustered* below; batch and sharded
+ * chains do not combine.  The 8192-hand limit holds per object. */
 typedef struct agh_cluster_params
 {
   double plane[4];      /* a, b, c, d of the support plane, (a, b, c) a unit vector pointing from the table towards the objects */
@@ -631,9 +634,11 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * and agh_localize_depth_labeled*, agh_localize_batch_masked*, agh_localize_batch_masked_begin*,
  * agh_localize_depth_batch_masked* and agh_localize_depth_batch_masked_begin*, agh_localize_batch_labeled*,
  * agh_localize_batch_labeled_begin*, agh_localize_depth_batch_labeled* and agh_localize_depth_batch_labeled_begin*;
- * agh_localize_clustered* and agh_localize_depth_clustered*;
+ * agh_localize_clustered* and agh_localize_depth_clustered*; agh_localize_batch_clustered*,
+ * agh_localize_batch_clustered_begin*, agh_localize_depth_batch_clustered* and agh_localize_depth_batch_clustered_begin*;
  * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info, agh_get_cluster_labels,
- * agh_get_batch_mask_counts and agh_get_batch_label_counts are refused as well),
+ * agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info and agh_get_batch_cluster_labels are
+ * refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
@@ -850,6 +855,83 @@ int agh_localize_depth_batch_labeled_begin(agh_ctx* ctx, const agh_depth_image* 
 int agh_localize_depth_batch_labeled_begin_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
   const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures);
 int agh_get_batch_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_lists);
+
+/* The batch chains with one sample list per CONNECTED COMPONENT of every capture's own cloud: "grasps on each object, for every
+ * rig of the cell", WITHOUT A SEGMENTER on any rig.  agh_localize_clustered once per capture pays the single chain and one
+ * synchronisation per capture, one after the other, and a cluster stage that cannot fill the device from one capture.  Here the
+ * batch is preprocessed once (agh_localize_batch*), ONE cluster stage runs for all captures (capture on blockIdx.y; the selection
+ * one work-group per capture; no launch per capture or per list), and from the object sets on the call IS
+ * agh_localize_batch_labeled: one compaction, one search over all lists, one batch tail, one synchronisation.
+ * cp is an array of n_captures records, cp[k] capture k's own: rigs have their own planes.
+ *  1. Lists.  K_k = cp[k].max_objects; list l = first_list[k] + j is object j of capture k, first_list being the exclusive prefix
+ *     sum of the K_k; L = sum of K_k is the number of lists of the call, L <= 64 (the lists the batch tail holds; this is not
+ *     lifted here).  lp[k].n_samples = S_k is the number of samples of EACH object of capture k and lp[k].sample_seed the seed of
+ *     every object of capture k; sum of K_k x S_k <= 2^24.
+ *  2. Objects per capture.  Rules 1 to 5 of agh_localize_clustered hold on capture k's own voxelised cloud with cp[k]: height,
+ *     float32 adjacency, components, selection by size then smaller id, E_{k,j} ascending.  Voxel indices, ids and samples_out
+ *     are CAPTURE-LOCAL.  No pair is ever formed across captures, whatever their coordinates: capture k's voxels are united only
+ *     through capture k's own search grid, whose reach comes from its own grid descriptor and cp[k].tolerance.
+ *  3. Equality, with AGH_NORMALS_DETERMINISTIC: the spans of lists first_list[k] .. first_list[k] + K_k - 1 and their
+ *     results[l].r equal, bit for bit (epoch aside), what agh_localize_clustered returns on capture k alone with cp[k] and lp[k]
+ *     (the depth form's twin is agh_localize_depth_clustered); capture k's counts, M_l, ids and label bytes equal the twin's
+ *     agh_get_cluster_info / agh_get_cluster_labels; the whole call equals agh_localize_batch_labeled fed the label bytes the
+ *     clusters imply.  With AGH_NORMALS_RAND50 the rand() stream runs through the whole sample list of the call: only list 0
+ *     equals its twin.  No result depends on the order of an atomic operation.
+ *  4. AGH_ERR_INVALID_ARGUMENT, nothing launched, the text naming the capture and the field: cp == NULL; any violation of rule 7
+ *     of agh_localize_clustered by cp[k] (a non-finite field, the unit vector, the heights, tolerance, min_voxels, max_objects);
+ *     L > 64; sum of K_k x S_k > 2^24; lp[k].sample_idx != NULL; and every validation of the unclustered batch twin: classify,
+ *     cell_size, min_inliers, min_length and filters_boundaries equal across the batch, n_captures in 1..64, fewer than 2^30
+ *     points, AGH_ERR_NO_SVM, a camera-origin table of n_captures rows -- origins are per CAPTURE, not per list -- and the
+ *     per-image rules of the depth forms.
+ *  5. Everything else is the labelled batch's: the output layout with L spans, results has L records; the 8192-hand limit per
+ *     list (the error text says "capture k, object j"); AGH_ERR_CAPACITY with every results[l] filled; one synchronisation in
+ *     the steady state, the first batch of a context takes the one for the lattice sizes; an outgrown-slot repeat re-enters
+ *     with the cp records the chain holds (they are copied by begin), capacity-class and declined-walk repeats work on the
+ *     lists already drawn; the cluster stage runs for S_k = 0 too; AGH_ERR_STATE while a chain of any kind is in flight, that
+ *     chain untouched; a begin of host data never adopts a staged set and drops a pending one; after the call the voxelised
+ *     batch is the context's bound batch of n_captures clouds.  The _begin forms are collected with agh_localize_batch_end; the
+ *     blocking forms are begin + end.  The _device forms read device points (images) in place.
+ *  6. agh_get_batch_cluster_info writes, for the last chain collected if it was a clustered batch, info[k] in capture order
+ *     (cap_captures >= n_captures) and the M_l and capture-local ids in list order (cap_lists >= L; 0 and -1 for a list without
+ *     an object); any of the three arrays may be NULL; AGH_ERR_CAPACITY if a cap is too small.  agh_get_batch_cluster_labels
+ *     writes 0 or j + 1 per voxel of the bound batch, in agh_get_cloud's order, and returns the voxel count (AGH_ERR_CAPACITY if
+ *     cap is below it).  Both return AGH_ERR_STATE after any other chain, with none collected, or while a chain is in flight.
+ *     After a clustered batch agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info, agh_get_cluster_labels,
+ *     agh_get_batch_mask_counts and agh_get_batch_label_counts return AGH_ERR_STATE.
+ *  7. A context's first clustered batch adds, beside the labelled batch's object sets, list entries and group counts: two
+ *     32-bit words and a byte per raw point of the batch; four 64-bit counters per capture; one record of cp per capture on the
+ *     device and pinned; a pinned table of 4 words per capture plus 2 per list (counters, records and table are allocated once
+ *     for 64 captures and lists, 10 KiB in all, and shared with the single clustered chain).  Nothing scales with L x a
+ *     lattice, or with n_captures x 64.
+ *  8. Not built: a _stage call; more than 64 lists per call; a fitted plane; clustered captures mixed with labelled, masked or
+ *     unmasked ones in one batch; sharded forms. */
+int agh_localize_batch_clustered(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);
+int agh_localize_batch_clustered_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);
+int agh_localize_batch_clustered_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_batch_clustered_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_depth_batch_clustered(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);
+int agh_localize_depth_batch_clustered_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
+  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results);
+int agh_localize_depth_batch_clustered_begin(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_depth_batch_clustered_begin_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures);
+int agh_get_batch_cluster_info(agh_ctx* ctx, agh_cluster_info* info /* n_captures */, int64_t* n_voxels /* L: M_l */,
+  int32_t* ids /* L: capture-local */, int32_t cap_captures, int32_t cap_lists);
+int agh_get_batch_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap);  /* per voxel of the bound batch: 0 or j + 1 */
 
 /* The context's current cloud: packed xyz (3 floats per point) and camera ids; returns the number of points. */
 int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap);

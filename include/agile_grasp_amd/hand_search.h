@@ -969,6 +969,110 @@ public:
     return true;
   }
 
+  /** Additional: localizeBatchLabeledBegin WITHOUT A SEGMENTER (agh_localize_batch_clustered_begin): capture k's objects are the
+   *  connected components of its own voxels above the support plane of cp[k], cp[k].max_objects lists each (at most 64 in all),
+   *  found on the device inside the one chain; num_samples samples are drawn per object, capture k's objects seeded with the
+   *  sample seed + k.  localizeBatchEnd returns one entry per list (batchObjects() says how many belong to each capture), and
+   *  batchClusterInfo() then describes the objects.  The records are copied by the call; the clouds must stay alive and unchanged
+   *  until localizeBatchEnd has returned.  A Begin that fails leaves a chain in flight as it was. */
+  bool localizeBatchClusteredBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<agh_cluster_params>& cp, const std::vector<VectorXd>& workspaces, double cell_size,
+    const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    const std::size_t C = clouds.size();
+    if (C == 0 || sizes_left.size() != C || workspaces.size() != C || cp.size() != C)
+    {
+      std::cout << " Error: localizeBatchClusteredBegin needs one size_left, workspace and cluster record per cloud\n";
+      return false;
+    }
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    RawBatch in;
+    if (!rawPoints(clouds, in))
+      return false;
+    const std::uint64_t seed = sampleSeed();
+    std::vector<agh_localize_params> lp(C);
+    for (std::size_t k = 0; k < C; k++)
+      lp[k] = chainParams(sizes_left[k], cloud_is_dense(*clouds[k]), workspaces[k], cell_size, std::vector<std::int32_t>(),
+        seed + (std::uint64_t) k, min_inliers, min_length, filters_boundaries);
+    if (agh_localize_batch_clustered_begin(ctx_, in.xyz.data(), in.stride.data(), in.n.data(), cp.data(), lp.data(),
+          (std::int32_t) C) != AGH_OK)
+    {
+      fail("agh_localize_batch_clustered_begin");
+      return false;
+    }
+    labeledBatchQueued(clusterObjects(cp), lp);
+    return true;
+  }
+
+  /** ... and straight from depth images (agh_localize_depth_batch_clustered_begin) */
+  bool localizeDepthBatchClusteredBegin(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<agh_cluster_params>& cp, const std::vector<VectorXd>& workspaces, double cell_size,
+    const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    const std::size_t C = captures.size();
+    if (C == 0 || workspaces.size() != C || cp.size() != C)
+    {
+      std::cout << " Error: localizeDepthBatchClusteredBegin needs one workspace and cluster record per capture\n";
+      return false;
+    }
+    if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
+      return false;
+    const std::uint64_t seed = sampleSeed();
+    std::vector<agh_depth_image> recs;  // (the flat array in capture order; copied by the library's begin, like the arrays below)
+    std::vector<std::int32_t> n_images(C);
+    std::vector<agh_localize_params> lp(C);
+    for (std::size_t k = 0; k < C; k++)
+    {
+      const std::vector<agh_depth_image> r = depthRecords(captures[k]);
+      recs.insert(recs.end(), r.begin(), r.end());
+      n_images[k] = (std::int32_t) r.size();
+      lp[k] = chainParams(0, true, workspaces[k], cell_size, std::vector<std::int32_t>(), seed + (std::uint64_t) k, min_inliers,
+        min_length, filters_boundaries);
+    }
+    if (agh_localize_depth_batch_clustered_begin(ctx_, recs.empty() ? nullptr : recs.data(), n_images.data(), cp.data(), lp.data(),
+          (std::int32_t) C) != AGH_OK)
+    {
+      fail("agh_localize_depth_batch_clustered_begin");
+      return false;
+    }
+    labeledBatchQueued(clusterObjects(cp), lp);
+    return true;
+  }
+
+  /** the lists per capture of a clustered batch: max_objects of every record */
+  static std::vector<int> clusterObjects(const std::vector<agh_cluster_params>& cp)
+  {
+    std::vector<int> objects(cp.size());
+    for (std::size_t k = 0; k < cp.size(); k++)
+      objects[k] = (int) cp[k].max_objects;
+    return objects;
+  }
+
+  /** agh_get_batch_cluster_info: per capture of the last clustered batch localizeBatchEnd collected its counts, and per list, in
+   *  list order, the object's voxel count and its smallest capture-local voxel index (0 and -1: a list without an object).
+   *  @return false if the last chain collected was no clustered batch */
+  bool batchClusterInfo(std::vector<agh_cluster_info>& info, std::vector<std::int64_t>& n_voxels, std::vector<std::int32_t>& ids)
+  {
+    std::size_t lists = 0;
+    for (std::size_t k = 0; k < batch_objects_.size(); k++)
+      lists += (std::size_t) batch_objects_[k];
+    info.assign(64, agh_cluster_info());
+    n_voxels.assign(64, 0);
+    ids.assign(64, -1);
+    if (!ctx_ || agh_get_batch_cluster_info(ctx_, info.data(), n_voxels.data(), ids.data(), 64, 64) != AGH_OK)
+    {
+      info.clear();
+      n_voxels.clear();
+      ids.clear();
+      return false;
+    }
+    info.resize(batch_objects_.size());
+    n_voxels.resize(lists);
+    ids.resize(lists);
+    return true;
+  }
+
   /** the objects per capture of the labelled batch in flight or last collected (empty: that batch was not labelled) */
   const std::vector<int>& batchObjects() const { return batch_objects_; }
 

@@ -930,6 +930,126 @@ public:
     return true;
   }
 
+  /** Additional: localizeHandlesBatchLabeled WITHOUT A SEGMENTER on any rig (agh_localize_batch_clustered): planes[k] = (a, b, c, d)
+   *  is capture k's own support plane -- rigs have their own.  Capture k's objects are the connected components of its voxels
+   *  above planes[k]; the height band, tolerance, smallest object and number of lists are setClusterParams' for every capture,
+   *  or cluster_params[k] (its plane is replaced by planes[k]) where that vector is given.  At most 64 lists in all.  Returns the
+   *  handles per capture and object, largest object first -- out[k][j] are those of localizeHandlesClustered on capture k alone
+   *  (seeded with the sample seed + k) -- and likewise the kept hands.  An error returns empty lists, per capture and object
+   *  where the records say how many. */
+  std::vector<std::vector<std::vector<Handle> > > localizeHandlesBatchClustered(const std::vector<PointCloud::Ptr>& clouds,
+    const std::vector<int>& sizes_left, const std::vector<VectorXd>& planes, const std::string& svm_filename, int min_inliers,
+    double min_length, std::vector<std::vector<std::vector<GraspHypothesis> > >* antipodal_hands_per_object = nullptr,
+    const std::vector<VectorXd>* workspaces = nullptr, const std::vector<agh_cluster_params>* cluster_params = nullptr)
+  {
+    if (chainPending("localizeHandlesBatchClustered") ||
+        !localizeHandlesBatchClusteredBegin(clouds, sizes_left, planes, svm_filename, min_inliers, min_length, workspaces, cluster_params))
+      return noLabeledHandles(HandSearch::clusterObjects(batchClusterParams(planes, cluster_params)), antipodal_hands_per_object);
+    return localizeHandlesBatchLabeledEnd(antipodal_hands_per_object);
+  }
+
+  /** ... as two calls: the chain queued here is collected by localizeHandlesBatchLabeledEnd.  A Begin while a chain of any kind
+   *  is pending returns false and leaves it as it was, and so does a Begin that fails for another reason.  The clouds must stay
+   *  alive and unchanged until the End has returned. */
+  bool localizeHandlesBatchClusteredBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<VectorXd>& planes, const std::string& svm_filename, int min_inliers, double min_length,
+    const std::vector<VectorXd>* workspaces = nullptr, const std::vector<agh_cluster_params>* cluster_params = nullptr)
+  {
+    if (chainPending("localizeHandlesBatchClusteredBegin", "its End"))
+      return false;
+    for (std::size_t k = 0; k < clouds.size(); k++)
+      if (!clouds[k] || clouds[k]->size() == 0 || k >= sizes_left.size() || sizes_left[k] == 0)
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    if (!batchPlanesGiven("localizeHandlesBatchClusteredBegin", clouds.size(), planes, cluster_params) ||
+        !detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(clouds.size(), workspace_);
+    const std::vector<agh_cluster_params> cp = batchClusterParams(planes, cluster_params);
+    if (!search_->localizeBatchClusteredBegin(clouds, sizes_left, cp, ws, 0.003, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
+      return false;
+    pendingLists(clouds, HandSearch::clusterObjects(cp));
+    return true;
+  }
+
+  /** ... and straight from depth images (agh_localize_depth_batch_clustered): out[k][j] are the handles of
+   *  localizeHandlesDepthClustered on capture k alone. */
+  std::vector<std::vector<std::vector<Handle> > > localizeHandlesDepthBatchClustered(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<VectorXd>& planes, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<std::vector<GraspHypothesis> > >* antipodal_hands_per_object = nullptr,
+    const std::vector<VectorXd>* workspaces = nullptr, const std::vector<agh_cluster_params>* cluster_params = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatchClustered") ||
+        !localizeHandlesDepthBatchClusteredBegin(captures, planes, svm_filename, min_inliers, min_length, workspaces, cluster_params))
+      return noLabeledHandles(HandSearch::clusterObjects(batchClusterParams(planes, cluster_params)), antipodal_hands_per_object);
+    return localizeHandlesBatchLabeledEnd(antipodal_hands_per_object);
+  }
+
+  bool localizeHandlesDepthBatchClusteredBegin(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<VectorXd>& planes, const std::string& svm_filename, int min_inliers, double min_length,
+    const std::vector<VectorXd>* workspaces = nullptr, const std::vector<agh_cluster_params>* cluster_params = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatchClusteredBegin", "its End"))
+      return false;
+    for (std::size_t k = 0; k < captures.size(); k++)
+      if (captures[k].empty())
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    if (!batchPlanesGiven("localizeHandlesDepthBatchClusteredBegin", captures.size(), planes, cluster_params) ||
+        !detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(captures.size(), workspace_);
+    const std::vector<agh_cluster_params> cp = batchClusterParams(planes, cluster_params);
+    if (!search_->localizeDepthBatchClusteredBegin(captures, cp, ws, 0.003, svm_filename, min_inliers, min_length, filters_boundaries_))
+      return false;
+    pendingLists(std::vector<PointCloud::Ptr>(captures.size()), HandSearch::clusterObjects(cp));  // (no capture with a host cloud)
+    return true;
+  }
+
+  // the records of a clustered batch: cluster_params[k] (or what setClusterParams holds) with planes[k]; a capture without a
+  // plane or a record gets none, and the Begin refuses the batch
+  std::vector<agh_cluster_params> batchClusterParams(const std::vector<VectorXd>& planes,
+    const std::vector<agh_cluster_params>* cluster_params) const
+  {
+    std::vector<agh_cluster_params> cp;
+    for (std::size_t k = 0; k < planes.size() && planes[k].size() >= 4 && (!cluster_params || k < cluster_params->size()); k++)
+    {
+      cp.push_back(cluster_params ? (*cluster_params)[k] : cluster_);
+      for (int q = 0; q < 4; q++)
+        cp.back().plane[q] = planes[k](q);
+    }
+    return cp;
+  }
+  bool batchPlanesGiven(const char* fn, std::size_t n_captures, const std::vector<VectorXd>& planes,
+    const std::vector<agh_cluster_params>* cluster_params) const
+  {
+    if (batchClusterParams(planes, cluster_params).size() == n_captures && planes.size() == n_captures &&
+        (!cluster_params || cluster_params->size() == n_captures))
+      return true;
+    std::cout << " Error: " << fn << " needs one plane of four entries (and, where given, one cluster record) per capture\n";
+    return false;
+  }
+
+  /** The objects of the last clustered batch collected (agh_get_batch_cluster_info): per list, capture after capture, the voxel
+   *  count of its object (0: none); empty if the last chain collected was no clustered batch, if there was none, or while a
+   *  chain is pending. */
+  std::vector<std::int64_t> getBatchClusterSizes()
+  {
+    std::vector<agh_cluster_info> info;
+    std::vector<std::int64_t> m;
+    std::vector<std::int32_t> ids;
+    if (search_)
+      search_->batchClusterInfo(info, m, ids);
+    return m;
+  }
+
   /** the results of the labelled batch a labelled Begin queued, per capture and object.  A pending batch of another kind is not
    *  this call's to collect: it is refused (after printing) with an empty result, and that chain stays pending for
    *  localizeHandlesBatchEnd. */
