@@ -9,9 +9,9 @@
 //                          for the <= 16 chord-clipped grid rows the ball touches (row per wave, loads one segment
 //                          ahead), FLANN float32 distance filter, LDS compaction, LDS bucket sort into the radius
 //                          search's (d2, index) order, then the 37 distinct sums behind M and N accumulated
-//                          SEQUENTIALLY in that order (56-neighbour chunks: all four waves form the products, 37 lanes
-//                          run the 37 dependent add chains) -- the same fp64 operation order as the reference loop, so
-//                          the sums are bit-identical to the CPU path.
+//                          SEQUENTIALLY in that order (56-neighbour chunks: two waves form the products of the next chunk
+//                          while 37 lanes of a third run the 37 dependent add chains of this one) -- the same fp64
+//                          operation order as the reference loop, so the sums are bit-identical to the CPU path.
 //   k_taubin_eigen         one sample per LANE (taubin_eigen.h): eliminates the 10th unknown, Cholesky of N9 with deflation of
 //                          rank-deficient coordinates, in-place reduction, Householder tridiagonalisation, bisection,
 //                          twisted factorisation -> the ONE eigenpair the reference uses -> quadric parameters; every
@@ -58,12 +58,14 @@ __device__ __forceinline__ void taubin_moments_sample(const int s, GridView gv, 
 #define AGH_MLAP(acc) do { } while (0)
 #endif
   AGH_MSTAMP(0);
-  // LDS: the staged neighbours and their sorted order live for the whole kernel; the sort scratch (keys, bucket
-  // permutation, histogram) is dead once `slot` is known, so the term tile of the summation phase reuses its space.
+  // LDS: the staged neighbours and their sorted order live until the sorted list has been written; the sort scratch (keys, bucket
+  // permutation, histogram) is dead once `slot` is known, so the term tile of the summation phase reuses its space -- and in the
+  // classes whose `stage` holds one (kOverlap) a second term tile reuses that.
   constexpr int kSortBytes = CAP * 8 + CAP * 2 + (kSortBins + 1) * 4 + kSortBins * 4;
   constexpr int kTS = kChunk + 2;  // row stride of the term-major tile (doubles): spreads the chain's lanes over the LDS banks
   constexpr int kTermBytes = kNumSums * kTS * 8;
   constexpr int kScratch = ((kSortBytes > kTermBytes ? kSortBytes : kTermBytes) + 15) & ~15;
+  constexpr bool kOverlap = CAP * 16 >= kTermBytes;  // a second term tile fits over `stage` (dead once the sorted list is written)
   __shared__ float4 stage[CAP];
   __shared__ unsigned short slot[CAP];
   __shared__ __attribute__((aligned(16))) unsigned char scratch[kScratch];
@@ -299,75 +301,114 @@ __device__ __forceinline__ void taubin_moments_sample(const int s, GridView gv, 
     }
   }
   // ---- 37 sequential sums (quadric.cpp:40-131) ----
+  // Waves 1 and 2 form the 37 terms of a 56-neighbour chunk into a term tile, wave 0 runs the 37 dependent add chains over it.  With
+  // kOverlap the two run side by side: while wave 0 chains chunk c out of one tile the producers form chunk c + 1 into the other, and
+  // the ONE barrier per chunk both publishes chunk c + 1 and frees the tile of chunk c.  The second tile lies over `stage`: the
+  // producers take their points from the sorted list this work-group has just written (the same points in the same order), so
+  // past the barrier below nothing reads `stage` or `slot` any more.  The 256 class, whose `stage` is too small for a tile and whose
+  // lists are a chunk or two, forms and chains in turn on the one tile (two barriers per chunk).
+  double* tw = termbuf;        // the tile the producers fill
+  const double* tr = termbuf;  // the tile the chain reads
+  const float4* const list = nbr + (int64_t) s * nbr_stride;
+  const int n_last = n > 0 ? n - 1 : 0;
+  // (a chunk's point is fetched a chunk ahead; the first chunk's comes out of LDS while the list's stores are still on their way)
+  typedef float float3v __attribute__((ext_vector_type(3)));
+  float3v p_next = *reinterpret_cast<const float3v*>(&stage[slot[min(lane, n_last)]]);
+  if constexpr (kOverlap)
+  {
+    static_assert(sizeof(stage) >= kTermBytes, "the second term tile lies over stage");
+    // (the barrier orders the work-group's own stores to the list in front of its loads from it -- one CU, one L1: no device-wide
+    // fence is needed for that -- and the last reads of stage / slot in front of the first store to the tile over them)
+    __syncthreads();
+    tw = reinterpret_cast<double*>(stage);  // (swapped before the first use: the prologue fills the tile over the sort scratch)
+  }
   double acc = 0.0;
 #ifdef AGH_DEBUG_HOOKS
   mt_last = wall_clock64();
 #endif
-  // (the chunk's point is fetched a chunk ahead: the two-deep look-up stage[slot[.]] then hides behind the chain of the
-  // chunk before instead of opening every chunk)
-  const int n_last = n > 0 ? n - 1 : 0;
-  float4 p_next = stage[slot[min(lane, n_last)]];
-  for (int c0 = 0; c0 < n; c0 += kChunk)
+  // iteration c0: the producers form chunk cp (kOverlap: the one after c0; the first iteration is the prologue and chains nothing)
+  for (int c0 = kOverlap ? -kChunk : 0; c0 < n; c0 += kChunk)
   {
-    const int rows = min(kChunk, n - c0);
-    const float4 p = p_next;
-    p_next = stage[slot[min(c0 + kChunk + lane, n_last)]];
-    // TWO waves form the 37 terms of a chunk (19 + 18), not four (10 + 9 + 9 + 9): every producing wave converts the point and
-    // forms the six squares and mixed products for itself, so four producers issue 4 x 9 + 31 fp64 instructions per chunk where
-    // two issue 2 x 9 + 31 -- and the phase is bound by the fp64 issue slots of a CU that runs sixteen such waves.
-    if (lane < rows && wave < 2)
+    const int cp = kOverlap ? c0 + kChunk : c0;
+    const int rows_p = min(kChunk, n - cp);
+    if constexpr (kOverlap)
     {
-      const double x = (double) p.x, y = (double) p.y, z = (double) p.z;
-      const double x2 = x * x, y2 = y * y, z2 = z * z;
-      const double xy = x * y, yz = y * z, xz = x * z;
-      double* t = &termbuf[lane];  // term-major tile: term k of row r at [k * kTS + r]
-      if (wave == 0)
-      {
-        t[0 * kTS] = x2 * x2;
-        t[1 * kTS] = x2 * y2;
-        t[2 * kTS] = x2 * z2;
-        t[3 * kTS] = x2 * xy;
-        t[4 * kTS] = x2 * yz;
-        t[5 * kTS] = x2 * xz;
-        t[6 * kTS] = x2 * x;
-        t[7 * kTS] = x2 * y;
-        t[8 * kTS] = x2 * z;
-        t[9 * kTS] = x2;
-        t[10 * kTS] = y2 * y2;
-        t[11 * kTS] = y2 * z2;
-        t[12 * kTS] = y2 * xy;
-        t[13 * kTS] = y2 * yz;
-        t[14 * kTS] = y2 * xz;
-        t[15 * kTS] = y2 * x;
-        t[16 * kTS] = y2 * y;
-        t[17 * kTS] = y2 * z;
-        t[18 * kTS] = y2;
-      }
-      else
-      {
-        t[19 * kTS] = z2 * z2;
-        t[20 * kTS] = z2 * xy;
-        t[21 * kTS] = z2 * yz;
-        t[22 * kTS] = z2 * xz;
-        t[23 * kTS] = z2 * x;
-        t[24 * kTS] = z2 * y;
-        t[25 * kTS] = z2 * z;
-        t[26 * kTS] = z2;
-        t[27 * kTS] = x * yz;
-        t[28 * kTS] = xy;
-        t[29 * kTS] = yz;
-        t[30 * kTS] = xz;
-        t[31 * kTS] = x;
-        t[32 * kTS] = y;
-        t[33 * kTS] = z;
-        t[34 * kTS] = x2 + y2;
-        t[35 * kTS] = y2 + z2;
-        t[36 * kTS] = x2 + z2;
-      }
+      const double* const t_ = tr;
+      tr = tw;
+      tw = const_cast<double*>(t_);
     }
-    __syncthreads();
-    AGH_MLAP(mt_prod);
-    if (wave == 0 && lane < kNumSums && rows == kChunk)
+    // TWO waves form the 37 terms of a chunk (19 + 18), not three or four: every producing wave converts the point and forms the six
+    // squares and mixed products for itself, so four producers issue 4 x 9 + 31 fp64 instructions per chunk where two issue
+    // 2 x 9 + 31 -- and the phase is bound by the fp64 issue slots of a CU that runs sixteen such waves.
+    if (wave == 1 || wave == 2)
+    {
+      // (the point is converted before the next one is asked for: the load then lands in the registers the loop carries, and what
+      // waits for it is the next iteration's conversion, not a copy at the end of this one)
+      asm volatile("" : "+v"(p_next));  // (one register triple, the one the load below fills)
+      double x = (double) p_next.x, y = (double) p_next.y, z = (double) p_next.z;
+      asm volatile("" : "+v"(x), "+v"(y), "+v"(z) : : "memory");  // (keeps the conversions here, in front of the load)
+      if constexpr (kOverlap)
+        p_next = *reinterpret_cast<const float3v*>(&list[min(cp + kChunk + lane, n_last)]);
+      else
+        p_next = *reinterpret_cast<const float3v*>(&stage[slot[min(cp + kChunk + lane, n_last)]]);
+      if (lane < rows_p)
+      {
+        const double x2 = x * x, y2 = y * y, z2 = z * z;
+        const double xy = x * y, yz = y * z, xz = x * z;
+        double* t = &tw[lane];  // term-major tile: term k of row r at [k * kTS + r]
+        if (wave == 1)
+        {
+          t[0 * kTS] = x2 * x2;
+          t[1 * kTS] = x2 * y2;
+          t[2 * kTS] = x2 * z2;
+          t[3 * kTS] = x2 * xy;
+          t[4 * kTS] = x2 * yz;
+          t[5 * kTS] = x2 * xz;
+          t[6 * kTS] = x2 * x;
+          t[7 * kTS] = x2 * y;
+          t[8 * kTS] = x2 * z;
+          t[9 * kTS] = x2;
+          t[10 * kTS] = y2 * y2;
+          t[11 * kTS] = y2 * z2;
+          t[12 * kTS] = y2 * xy;
+          t[13 * kTS] = y2 * yz;
+          t[14 * kTS] = y2 * xz;
+          t[15 * kTS] = y2 * x;
+          t[16 * kTS] = y2 * y;
+          t[17 * kTS] = y2 * z;
+          t[18 * kTS] = y2;
+        }
+        else
+        {
+          t[19 * kTS] = z2 * z2;
+          t[20 * kTS] = z2 * xy;
+          t[21 * kTS] = z2 * yz;
+          t[22 * kTS] = z2 * xz;
+          t[23 * kTS] = z2 * x;
+          t[24 * kTS] = z2 * y;
+          t[25 * kTS] = z2 * z;
+          t[26 * kTS] = z2;
+          t[27 * kTS] = x * yz;
+          t[28 * kTS] = xy;
+          t[29 * kTS] = yz;
+          t[30 * kTS] = xz;
+          t[31 * kTS] = x;
+          t[32 * kTS] = y;
+          t[33 * kTS] = z;
+          t[34 * kTS] = x2 + y2;
+          t[35 * kTS] = y2 + z2;
+          t[36 * kTS] = x2 + z2;
+        }
+      }
+      AGH_MLAP(mt_prod);
+    }
+    if constexpr (!kOverlap)
+    {
+      __syncthreads();
+      AGH_MLAP(mt_wait);
+    }
+    const int rows = min(kChunk, n - c0);  // (the chunk the chain adds: chunk c0, in the tile filled one iteration ago)
+    if (wave == 0 && lane < kNumSums && c0 >= 0 && rows == kChunk)
     {
       // full chunk: all 56 loads are issued up front (two register halves), so the dependent add chain -- the critical
       // path of the block -- pays one LDS round trip per chunk instead of one per eight rows
@@ -376,7 +417,7 @@ __device__ __forceinline__ void taubin_moments_sample(const int s, GridView gv, 
       double2 va[kChunk / 2];
 #pragma unroll
       for (int u = 0; u < kChunk / 2; u++)
-        va[u] = reinterpret_cast<const double2*>(termbuf + lane * kTS)[u];
+        va[u] = reinterpret_cast<const double2*>(tr + lane * kTS)[u];
 #pragma unroll
       for (int u = 0; u < kChunk / 2; u++)
       {
@@ -384,7 +425,7 @@ __device__ __forceinline__ void taubin_moments_sample(const int s, GridView gv, 
         acc += va[u].y;
       }
     }
-    else if (wave == 0 && lane < kNumSums)
+    else if (wave == 0 && lane < kNumSums && c0 >= 0)
     {
       int k = 0;
       for (; k + 8 <= rows; k += 8)  // 8 LDS loads in flight; the adds stay in neighbour order
@@ -392,19 +433,20 @@ __device__ __forceinline__ void taubin_moments_sample(const int s, GridView gv, 
         double v_[8];
 #pragma unroll
         for (int u = 0; u < 8; u++)
-          v_[u] = termbuf[lane * kTS + k + u];
+          v_[u] = tr[lane * kTS + k + u];
 #pragma unroll
         for (int u = 0; u < 8; u++)
           acc += v_[u];
       }
       for (; k < rows; k++)
-        acc += termbuf[lane * kTS + k];
+        acc += tr[lane * kTS + k];
     }
 #ifdef AGH_DEBUG_HOOKS
     if (dbg && acc == 1.2345e300)  // (keeps the adds in front of the clock read)
       mt_cons++;
+    if (wave == 0)
+      AGH_MLAP(mt_cons);
 #endif
-    AGH_MLAP(mt_cons);
     __syncthreads();
     AGH_MLAP(mt_wait);
   }
@@ -417,9 +459,10 @@ __device__ __forceinline__ void taubin_moments_sample(const int s, GridView gv, 
   }
   AGH_MSTAMP(4);
 #ifdef AGH_DEBUG_HOOKS
-  if (dbg && threadIdx.x == 0)
-  {
+  if (dbg && threadIdx.x == 64)  // (the first producing wave: forming the products)
     dbg[(int64_t) blockIdx.x * 8 + 5] = mt_prod;
+  if (dbg && threadIdx.x == 0)  // (the chain wave: its adds, and what it waits at the chunk barriers)
+  {
     dbg[(int64_t) blockIdx.x * 8 + 6] = mt_cons;
     dbg[(int64_t) blockIdx.x * 8 + 7] = mt_wait;
   }
@@ -447,7 +490,7 @@ __global__ __launch_bounds__(256, CAP <= 1152 ? 4 : 1) void k_taubin_moments(Gri
       taubin_moments_sample<CAP>(ovf_list ? ovf_list[1 + it] : it, gv, xyz, stride, samples, S, r2f, rpad, first_class, sums, nt, status,
         nbr, nbr_stride, debug_stop, n_points, zero_flags, scloud, dbg, ovf_out);
       if (it + (int) gridDim.x < n_items)
-        __syncthreads();  // (the next sample reuses the tiles)
+        __syncthreads();  // (the next sample reuses the tiles: its gather writes `stage`, the second term tile, and the sort scratch, the first)
     }
   }
   else
