@@ -344,6 +344,46 @@ def train_svm(features, labels, C=1.0, max_iter=1000, eps=float(np.finfo(np.floa
                 alpha=alpha_out, sv_order=order[np.abs(a) > 0])
 
 
+# ---- CvSVM::predict (C_SVC, two classes, LINEAR or POLY degree 2) for a model (kernel, sv, alpha, rho) ------------------------
+SVM_MAX_VAL = np.float32(np.finfo(np.float32).max * 1e-3)  # CvSVMKernel::calc: (float)(FLT_MAX * 1e-3)
+
+
+def svm_kernel_values(desc, kernel, sv, clamp=True):
+    """K(sv_v, desc_h) as CvSVMKernel::calc leaves it in predict's float buffer, (n, n_sv) float32, one support vector at a
+    time: float products, each group of four added left to right in float, the group sums accumulated in double strictly in
+    index order, the result stored as float, squared in float for POLY2 (kernel = 1), clamped to SVM_MAX_VAL.  clamp=False
+    returns the value before the clamp (inf where the square overflows)."""
+    desc = np.ascontiguousarray(desc, np.float32)
+    sv = np.ascontiguousarray(sv, np.float32).reshape(-1, desc.shape[1])
+    n, d = desc.shape
+    assert d % 4 == 0
+    out = np.zeros((n, sv.shape[0]), np.float32)
+    with np.errstate(over="ignore"):
+        for v in range(sv.shape[0]):
+            g = (sv[v][None, :] * desc).reshape(n, d // 4, 4)  # float32
+            gs = ((g[:, :, 0] + g[:, :, 1]) + g[:, :, 2]) + g[:, :, 3]  # float32
+            s = np.cumsum(gs.astype(np.float64), axis=1)[:, -1]  # (cumsum adds in order; sum adds pairwise)
+            q = (s * 1.0 + 0.0).astype(np.float32)
+            if kernel == 1:
+                q = q * q
+            out[:, v] = np.minimum(q, SVM_MAX_VAL) if clamp else q
+    return out
+
+
+def svm_decide(q, alpha, rho):
+    """sum = -rho, then += alpha[v] * (double) q[v] in index order; class_labels[sum > 0 ? 0 : 1] = {-1, +1} and
+    Learning::classify keeps prediction == 1: (keep, sums)."""
+    alpha = np.asarray(alpha, np.float64)
+    sums = np.full(q.shape[0], -np.float64(rho))
+    for v in range(q.shape[1]):
+        sums = sums + alpha[v] * q[:, v].astype(np.float64)
+    return np.where(sums > 0, 0, 1).astype(np.uint8), sums
+
+
+def classify_model(desc, kernel, sv, alpha, rho):
+    return svm_decide(svm_kernel_values(desc, kernel, sv), alpha, rho)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # An INDEPENDENT HOG (row a18: cv::HOGDescriptor::compute, call site learning.cpp:194-195,220), written from the PUBLISHED
 # algorithm (Dalal & Triggs 2005 with OpenCV's documented parameters: 64x64 window, 16x16 blocks at stride 8, 8x8 cells,
