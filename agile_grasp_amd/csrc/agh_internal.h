@@ -301,7 +301,7 @@ struct Ctx
   HostMirror mirror{ nullptr, 0, nullptr };  // set by agh_find_hands around its device call
   uint8_t* h_pin_handles = nullptr;  // agh_find_handles: [256-byte header | hands in | handles out | inlier indices out]
   int64_t h_pin_handles_cap = 0;     // in hands
-  bool handles_sequential = false;   // the previous agh_find_handles needed k_handle_greedy: launch it along
+  bool handles_sequential = false;   // the previous handle search needed k_handle_greedy (a row longer than kMaxRow, two waves' worth): launch it along
   uint8_t* h_pin_keep = nullptr;     // agh_classify: the keep flags, written by K3 itself
   int64_t h_pin_keep_cap = 0;
 

@@ -1058,7 +1058,7 @@ int agh_find_handles(agh_ctx* ctx, const agh_hypothesis* hands, int64_t n_hands,
       return rc;
     }
     AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
-    const bool declined = h_counts[3] != 0;  // a row of the pair matrix longer than a wave
+    const bool declined = h_counts[3] != 0;  // a row of the pair matrix longer than kMaxRow (two waves' worth)
     c->handles_sequential = declined;        // what this set of hands needed is the guess for the next one
     if (!declined || with_sequential)
       break;  // (declined without the sequential kernel behind it: once more, with it)

@@ -10,7 +10,7 @@
 //                        distance along the seed's axis, cut at the first 2 cm gap (shortenHandle, :88-118, with the meaning
 //                        the oracle states for its out-of-range read), accept if long enough, retire the members.
 //       k_handle_batch   (round 4) sixteen open seeds per round, one wave each, everything in registers, committed as if in
-//                        index order -- for pair matrices whose rows hold at most 64 hands (what the search meets on the
+//                        index order -- for pair matrices whose rows hold at most kMaxRow = 128 hands (what the search meets on the
 //                        hands Learning::classify keeps); 15 rounds of ~4.7 us for the pipeline's 499 hands
 //       k_handle_greedy  the sequential walk by one wave, for longer rows (launched along only when the previous set of
 //                        hands needed it)
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void k_handle_pairs(const agh_hypothesis* __re
 struct HandleCounts
 {
   int n_handles, n_idx, error;
-  int sequential;  // set by k_handle_batch when it declines (a seed with more than 64 potential inliers): k_handle_greedy runs
+  int sequential;  // set by k_handle_batch when it declines (a row longer than kMaxRow, two waves' worth): k_handle_greedy runs
 };
 
 constexpr int kHandleLdsHands = 640;  // hands whose axis, bottom and pair-matrix rows fit the LDS of the small variant
@@ -438,8 +438,8 @@ __global__ __launch_bounds__(256) void k_handle_greedy(const agh_hypothesis* __r
 // K5b', the walk of handle_search.cpp:11-80 with its seeds evaluated SIXTEEN AT A TIME (round 4).  The walk is sequential in its
 // seeds, but a seed only ever interacts with the hands of its own row of the pair matrix: a REJECTED seed changes nothing, an
 // accepted one retires members of its row.  So the next sixteen open seeds (in index order) are evaluated in parallel against
-// the availability at the start of the round, one wave each, everything in registers (one inlier per lane: this kernel serves
-// pair matrices whose rows hold at most 64 hands, k_handle_greedy the others), and then committed AS IF in index order:
+// the availability at the start of the round, one wave each (one inlier per lane, two for rows of more than 64 hands: this kernel
+// serves pair matrices whose rows hold at most kMaxRow = 128 hands, k_handle_greedy the others), and then committed AS IF in index order:
 //   * a seed that shares a hand with an EARLIER seed of the batch which was accepted in this round (its evaluation may be
 //     stale, or the seed itself is gone) or which stays open itself (whatever that one may yet retire must not be judged
 //     before it) stays open: it is evaluated again next round, after everything it depends on;
@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(64) void k_handle_build(const agh_hypothesis* __res
 }
 
 // with_sequential: also launch k_handle_greedy, which does the search when k_handle_batch declines it on the device (a row of the
-// pair matrix longer than a wave).  Without it a declined search leaves counts[3] = 1 and no result: the caller repeats the call
+// pair matrix longer than kMaxRow (two waves' worth)).  Without it a declined search leaves counts[3] = 1 and no result: the caller repeats the call
 // with the kernel (agh_find_handles remembers what the previous set of hands needed, so a stream of similar clouds pays the
 // ~5 us of an unneeded launch only when it is needed).
 // n_lists > 1 (agh_localize_batch): that many lists side by side, in the slices of `b` at the strides of `sl`, one row of
@@ -1033,7 +1033,7 @@ static int handle_search_lists(const HandleBufs& b, int n_lists, const HandleSlo
   HandleCounts* counts = reinterpret_cast<HandleCounts*>(b.counts);
   hipLaunchKernelGGL(k_handle_pairs, dim3(Hi, L), dim3(256), 0, st, (const agh_hypothesis*) b.hands, Hi, x1, x2,
     b.bits, W, b.rowcnt, d_H, sl);
-  // the walk: sixteen seeds at a time (rows of at most 64 hands), else -- flagged on the device -- the sequential kernel
+  // the walk: sixteen seeds at a time (rows of at most kMaxRow hands), else -- flagged on the device -- the sequential kernel
   if (Hi <= kHandleLdsHands || d_H)
     hipLaunchKernelGGL(k_handle_batch<true>, dim3(1, L), dim3(1024), 0, st, (const agh_hypothesis*) b.hands, Hi,
       (const unsigned long long*) b.bits, W, (const int*) b.rowcnt, min_inliers, min_length, b.first,

@@ -166,7 +166,7 @@ int chain_collect(agh_ctx* ctx, const char* who, const char* unit, int C, const 
         c->err = of(k) + "more than 8192 hands for the handle search (classify first, or search fewer samples)";
         return AGH_ERR_CAPACITY;
       }
-      declined |= h[3] != 0;  // a row of the pair matrix longer than a wave (see agh_find_handles)
+      declined |= h[3] != 0;  // a row of the pair matrix longer than kMaxRow (two waves' worth; see agh_find_handles)
     }
     c->handles_sequential = declined;
     if (declined && !c->loc.with_sequential && attempt < 3)

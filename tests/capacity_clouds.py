@@ -231,7 +231,8 @@ def handle_hands(H, big=0, seed=0, per=14):
 
 
 def seed_inliers(hands, i):
-    """Potential inliers of seed i before any hand is retired (handle_search.cpp:19-28)."""
+    """Potential inliers of seed i before any hand is retired (handle_search.cpp:19-28) -- of ALL hands, the ones with
+    width = -1 included: what k_handle_pairs writes into rowcnt."""
     ia, ip, inn = hands["axis"][i], hands["bottom"][i], hands["approach"][i]
     d = hands["bottom"] - ip
     P = np.eye(3) - np.outer(ia, ia)
@@ -241,6 +242,57 @@ def seed_inliers(hands, i):
     nn = np.clip(hands["approach"] @ inn, -1, 1)
     ang = np.arccos(aa)
     return int(((dist < 0.01) & (np.minimum(ang, np.pi - ang) < 0.34) & (np.arccos(nn) < 0.34)).sum())
+
+
+def along_seed(hands, i, members):
+    """dist_along_line of `members` from seed i (handle_search.cpp:34), in the oracle's order of operations."""
+    ia = hands["axis"][i]
+    d = hands["bottom"][members] - hands["bottom"][i]
+    return (ia[0] * d[:, 0] + ia[1] * d[:, 1]) + ia[2] * d[:, 2]
+
+
+def big_row_sorted(hands):
+    """The big row as its first seed (the member with the lowest index) sorts it: (seed, members in (distance, index) order,
+    their distances) -- std::sort's order on (dist_along_line, j), the order the walk cuts."""
+    members = np.flatnonzero(big_members(hands))
+    seed = int(members[0])
+    dist = along_seed(hands, seed, members)
+    order = np.lexsort((members, dist))
+    return seed, members[order], dist[order]
+
+
+def handle_row_hands(H, big, seed=0, gap_after=None, ties=0, dead=0):
+    """handle_hands(H, big, seed) with the big row reshaped (no option: the same arrays, bit for bit).  Positions are those of
+    big_row_sorted, i.e. of the list the first seed of the row sorts.
+      gap_after = k  the hands after sorted position k move 3 cm on along the seed's axis (bottom and surface): the gap
+                     between positions k and k + 1 is more than the 2 cm of shortenHandle, which keeps the k hands before it
+      ties = m       m pairs of neighbours of the sorted list share one `bottom` exactly: their distance along ANY seed's axis
+                     is equal and the index decides.  The pairs are the sorted positions (63, 64), (61, 62), (65, 66),
+                     (59, 60), ...: the first straddles the two slots of the sorted list
+      dead = d       d hands of the row (spread evenly over it, its first seed left out) get width = -1: retired before the search
+                     begins, and still counted in rowcnt (k_handle_pairs does not look at the width)"""
+    hands = handle_hands(H, big, seed)
+    if gap_after is None and not ties and not dead:
+        return hands
+    first, members, dist = big_row_sorted(hands)
+    ax = hands["axis"][first]
+    if gap_after is not None:
+        assert 0 < gap_after < big - 1, (gap_after, big)
+        moved = members[gap_after + 1:]
+        hands["bottom"][moved] += 0.03 * ax
+        hands["surface"][moved] += 0.03 * ax
+    for t in range(ties):
+        p = 63 + (-1 if t % 2 else 1) * 2 * ((t + 1) // 2)
+        assert 0 < p and p + 1 < big, (p, big)
+        a, b = members[p], members[p + 1]
+        hands["surface"][b] += hands["bottom"][a] - hands["bottom"][b]
+        hands["bottom"][b] = hands["bottom"][a]
+    if dead:
+        rest = members[members != first]  # (the row's first seed stays alive: the positions are its list's)
+        pos = np.unique(np.round(np.linspace(0, big - 2, dead)).astype(int))
+        assert len(pos) == dead, (dead, big)
+        hands["width"][rest[pos]] = -1.0
+    return hands
 
 
 # ---- the cases (shared by the CPU check and the GPU tests; the threshold table ties each one to its source constant) ----
@@ -254,6 +306,36 @@ SAMPLE_COUNTS = (1, 7, 9, 127, 128, 4095, 4096, 4097, 65536, 65537)
 MIRROR_COUNTS = (65536, 65537)  # hypotheses: the pinned host mirror's room and one beyond
 HANDLE_COUNTS = (640, 641, 1024, 1025, 4096, 4097, 8192)
 HANDLE_SEEDS = ((600, 64), (600, 65), (1500, 64), (1500, 65), (3000, 2048), (3000, 2049))  # (H, inliers of one seed)
+# rows around kMaxRow (k_handle_batch declines beyond) in the LDS variant (H <= 640) and the general one: (H, big)
+HANDLE_ROWS = tuple((H, big) for H in (600, 1500) for big in (127, 128, 129))
+
+
+def _row_shapes():
+    """(H, big, options of handle_row_hands): rows of 128 (the longest k_handle_batch takes) and of 100 hands, in two slots per
+    lane.  A gap at the last lanes of the first slot, across the slots, at the first lane of the second, before the row's last
+    hand (big - 2: the clamped read at position 127 for big = 128) and at position 100 of the full row; ties across the slots;
+    and rows with more than 64 potential members of which fewer than 64 are alive."""
+    out = []
+    for H in (600, 1500):
+        for big in (128, 100):
+            gaps = (62, 63, 64, big - 2) + ((100,) if big == 128 else ())
+            out += [(H, big, dict(gap_after=g)) for g in gaps]
+            out.append((H, big, dict(ties=4)))
+            out.append((H, big, dict(dead=big - 58 if big == 128 else big - 60)))
+    return tuple(out)
+
+
+HANDLE_ROW_SHAPES = _row_shapes()
+
+
+def row_shape_id(case):
+    H, big, opt = case
+    return f"{H}-{big}-" + "-".join(f"{k}{v}" for k, v in opt.items())
+
+
+def row_shape_hands(case):
+    H, big, opt = case
+    return handle_row_hands(H, big, seed=H + big, **opt)
 
 
 def tile_targets(T):

@@ -65,6 +65,11 @@ THRESHOLDS = [
     ("handle search: at most hands", "handles.hip", r"constexpr int kHandleMaxHands = (\d+);", ("8192",), None),
     ("handle search: one-word-per-lane scan", "handles.hip", r"if \(W <= (\d+)\)", ("16",), None),
     ("handle search: two-half walk", "handles.hip", r"half < \(W > (\d+) \? 2 : 1\)", ("64",), None),
+    ("handle search: longest row of the batched walk", "handles.hip", r"constexpr int kMaxRow = (\d+)", ("128",),
+     tuple(k for _, k in cc.HANDLE_ROWS)),
+    ("handle search: one slot per lane", "handles.hip", r"if \(s_maxrow <= (\d+)\)", ("64",),
+     tuple(k for _, k in cc.HANDLE_SEEDS)),
+    ("handle search: the batched walk declines", "handles.hip", r"if \(s_maxrow (>) kMaxRow\)", (">",), None),
 ]
 
 
@@ -89,7 +94,12 @@ def test_derived_boundaries_are_straddled():
         assert _straddles(cc.HANDLE_COUNTS, H)
     assert max(cc.HANDLE_COUNTS) == 8192
     seeds = [k for _, k in cc.HANDLE_SEEDS]
-    assert _straddles(seeds, 64) and _straddles(seeds, 2048)  # one wave's row (k_handle_batch declines beyond)
+    # one wave's row (beyond it k_handle_batch takes two members per lane), kHandleListCap, and kMaxRow = two waves' worth
+    # (k_handle_batch declines beyond) in both LDS variants
+    assert _straddles(seeds, 64) and _straddles(seeds, 2048)
+    for H in (600, 1500):
+        assert _straddles([k for h, k in cc.HANDLE_ROWS if h == H], 128) and _straddles([k for h, k in cc.HANDLE_SEEDS if h == H], 64)
+    assert max(h for h, _ in cc.HANDLE_ROWS if h <= 640) <= 640 < min(h for h, _ in cc.HANDLE_ROWS if h > 640)
     for T in cc.TILES.values():
         assert cc.tile_targets(T) == (T - 1, T, T + 1, 2 * T, 2 * T + 1)
 
@@ -158,3 +168,62 @@ def test_handle_cases_hit_their_counts():
         assert len(hands) == H and int(hd["n_inliers"].max()) == big
         members = np.flatnonzero(cc.big_members(hands))
         assert len(members) == big and cc.seed_inliers(hands, members[0]) == big
+
+
+def _rows(hands):
+    return [cc.seed_inliers(hands, i) for i in range(len(hands))]
+
+
+@pytest.mark.parametrize("H,big", cc.HANDLE_ROWS)
+def test_handle_rows_hit_kmaxrow(H, big):
+    """127 / 128 / 129 hands in the longest row of the pair matrix, with at most 640 hands and with more: no other row is
+    longer, and the oracle finds the whole row as one handle."""
+    from oracle import oracle_py as O
+
+    hands = cc.handle_hands(H, big, seed=H + big)
+    rows = _rows(hands)
+    hd, _ = O.find_handles(hands, 3, 0.005)
+    print(H, big, "longest rows", sorted(rows)[-3:], "largest handle", int(hd["n_inliers"].max()))
+    assert len(hands) == H and max(rows) == big <= 2048
+    assert rows[np.flatnonzero(cc.big_members(hands))[0]] == big and int(hd["n_inliers"].max()) == big
+
+
+def test_handle_row_options_leave_the_defaults_alone():
+    for H, big in cc.HANDLE_SEEDS[:4] + cc.HANDLE_ROWS:
+        assert cc.handle_row_hands(H, big, seed=H + big).tobytes() == cc.handle_hands(H, big, seed=H + big).tobytes()
+
+
+@pytest.mark.parametrize("case", cc.HANDLE_ROW_SHAPES, ids=cc.row_shape_id)
+def test_handle_row_shapes_sit_on_their_edges(case):
+    """Every shaped row: the longest row of the pair matrix is the big one (so the search takes k_handle_batch's two-slot
+    evaluation and does not decline); a gap case is cut by its gap; a tie case has equal distances at sorted positions
+    (63, 64), and a tied pair whose members sit in different slots of the UNSORTED member list (bit order: by index); a dead
+    case has more than 64 potential members and fewer than 64 live ones."""
+    from oracle import oracle_py as O
+
+    H, big, opt = case
+    hands = cc.row_shape_hands(case)
+    rows = _rows(hands)
+    first, members, dist = cc.big_row_sorted(hands)
+    hd, idx = O.find_handles(hands, 3, 0.005)
+    print(cc.row_shape_id(case), "longest rows", sorted(rows)[-3:], "handles", sorted(hd["n_inliers"].tolist())[-3:])
+    assert len(hands) == H and len(members) == big and 64 < max(rows) == rows[first] == big <= 128
+    if "gap_after" in opt:
+        k = opt["gap_after"]
+        assert dist[k + 1] - dist[k] > 0.02 + 1e-3 and (np.diff(dist)[:k] < 0.02 - 1e-3).all()
+        lists = [idx[h["first_inlier"]:h["first_inlier"] + h["n_inliers"]] for h in hd]
+        # the handle the row's first seed makes: the k hands before the gap, in order (the seed itself may lie beyond it)
+        assert sum(len(l) == k and np.array_equal(l, members[:k]) for l in lists) == 1
+    if "ties" in opt:
+        assert dist[63] == dist[64] and members[63] < members[64]
+        tied = np.flatnonzero(dist[1:] == dist[:-1])
+        assert len(tied) == opt["ties"]
+        slot = np.argsort(np.argsort(members)) // 64  # a member's slot in the unsorted list
+        assert any(slot[p] != slot[p + 1] for p in tied)
+        other = members[-1]  # equal along any other seed's axis too
+        assert np.ptp(cc.along_seed(hands, other, members[63:65])) == 0.0
+        assert int(hd["n_inliers"].max()) == big
+    if "dead" in opt:
+        live = int((hands["width"][members] != -1.0).sum())
+        assert live == big - opt["dead"] and 3 <= live < 64 and hands["width"][first] != -1.0
+        assert int(hd["n_inliers"].max()) == live

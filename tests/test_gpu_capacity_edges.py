@@ -282,8 +282,8 @@ def test_handle_search_hand_counts(H):
 
 
 def test_handle_search_inliers_of_one_seed():
-    """64 / 65 inliers (k_handle_batch declines a row longer than a wave: k_handle_greedy) in both variants, 2048 inliers
-    (kHandleListCap) and 2049: AGH_ERR_CAPACITY, after which the context still works."""
+    """64 / 65 inliers (k_handle_batch takes two members per lane beyond one wave's row) in both variants, 2048 inliers
+    (kHandleListCap, far beyond kMaxRow: k_handle_greedy) and 2049: AGH_ERR_CAPACITY, after which the context still works."""
     from agile_grasp_amd import binding
 
     ctx = _ctx()
@@ -298,3 +298,51 @@ def test_handle_search_inliers_of_one_seed():
             assert int(hd["n_inliers"].max()) == big
     _handles_equal(ctx, cc.handle_hands(3000, 2048, seed=5048))
     _handles_equal(ctx, cc.handle_hands(600, 65, seed=665))
+
+
+def _searches(ctx):
+    """Timed handle searches since the previous look (profile level 1 records one event pair per queued search)."""
+    return ctx.timing(counts=True)[1].get("handle_search", 0)
+
+
+@pytest.mark.parametrize("H,big", cc.HANDLE_ROWS)
+def test_handle_search_rows_around_kmaxrow(H, big):
+    """127 / 128 hands in the longest row (k_handle_batch, two members per lane) and 129 (declined: k_handle_greedy, the LDS
+    variant for H = 600), twice on one context: the second call starts with the sequential kernel queued or not as the first
+    left it."""
+    hands = cc.handle_hands(H, big, seed=H + big)
+    ctx = _ctx()
+    for _ in range(2):
+        hd = _handles_equal(ctx, hands)
+        assert int(hd["n_inliers"].max()) == big
+
+
+@pytest.mark.parametrize("case", cc.HANDLE_ROW_SHAPES, ids=cc.row_shape_id)
+def test_handle_search_two_slot_rows(case):
+    """Rows of 128 and 100 hands in k_handle_batch's two-slot evaluation: a shortenHandle gap at the end of the first slot,
+    across the slots, in the second and before the row's last hand; equal distances whose order the index decides across the
+    slots; rows with more than 64 potential and fewer than 64 live members (tests/test_capacity_clouds.py proves each)."""
+    hands = cc.row_shape_hands(case)
+    ctx = _ctx()
+    for _ in range(2):
+        hd = _handles_equal(ctx, hands)
+    H, big, opt = case
+    if "gap_after" in opt:
+        assert opt["gap_after"] in hd["n_inliers"]
+    else:
+        assert int(hd["n_inliers"].max()) == big - opt.get("dead", 0)
+
+
+@pytest.mark.parametrize("H", [600, 1500])
+def test_handle_search_decline_order_on_one_context(H):
+    """Declined (129) -> not declined (128) -> declined (129) on one context, then 129 again: the sequential kernel not queued
+    and needed (the search is repeated with it), queued and not needed, not queued and needed again, queued and needed.  The
+    context is a profiling one and the count of timed handle searches shows each repeat: profile level 1 records one event
+    pair per queued search and agh_get_timing_counts counts the pairs, so the counter is exact."""
+    sets = {big: cc.handle_hands(H, big, seed=H + big) for big in (128, 129)}
+    ctx = _ctx(profile=True)
+    _searches(ctx)
+    for big, want in ((129, 2), (129, 1), (128, 1), (129, 2), (129, 1), (128, 1), (128, 1)):
+        hd = _handles_equal(ctx, sets[big])
+        assert int(hd["n_inliers"].max()) == big
+        assert _searches(ctx) == want, (big, want)
