@@ -181,7 +181,15 @@ def preprocess(xyz, size_left, ws, cell=0.003, dense=False):
         if len(q) == 0:
             continue
         mn = np.minimum(q.min(0), 10000.0)
-        vx = np.unique(np.floor((q - mn) / cell).astype(np.int64), axis=0)
+        vx = np.floor((q - mn) / cell).astype(np.int64)
+        ny, nz = (int(d) + 1 for d in vx.max(0)[1:])
+        if (int(vx[:, 0].max()) + 1) * ny * nz < 2 ** 62:
+            # (the rows as one integer each, x-major and z-fastest: its order IS the lexicographic order of the rows, and a
+            # sort of integers takes a sixth of the time of np.unique's row sort on a cloud of a million points)
+            key = np.unique((vx[:, 0] * ny + vx[:, 1]) * nz + vx[:, 2])
+            vx = np.stack([key // (ny * nz), key // nz % ny, key % nz], axis=1)
+        else:
+            vx = np.unique(vx, axis=0)
         outs.append((vx.astype(np.float64) * cell + mn).astype(np.float32))
         cams.append(np.full(len(vx), c, np.int32))
     return np.concatenate(outs), np.concatenate(cams)

@@ -13,6 +13,7 @@ import pytest
 from tests import depth_captures as D
 from tests import mask_batch_cases as MB
 from tests import mask_cases as M
+from tests import vox_edge_clouds as V
 
 WORDS_PER_BLOCK = 4096
 
@@ -91,12 +92,7 @@ def test_the_regimes_of_m_and_the_slots():
 
 def _lattice_words(c):
     """the words of the capture's voxel bitmap: per camera the lattice's bits in words, rounded up to whole blocks"""
-    cams = M.camera_ids(c["points"], c["size_left"], c["dense"])
-    words = 0
-    for _sel, _cam, _pos, dim in M.bit_positions(c["points"], cams, c["workspace"], c["cell"]):
-        w = (int(np.prod(dim)) + 31) // 32
-        words += (w + WORDS_PER_BLOCK - 1) // WORDS_PER_BLOCK * WORDS_PER_BLOCK
-    return words
+    return V.lattice_words(c["points"], c["size_left"], c["workspace"], c["cell"], c["dense"])
 
 
 def test_the_sequence_takes_the_kept_slot_path():
