@@ -300,8 +300,11 @@ TAUBIN_DET = (1, 2, 9, 10, 63, 64, 65, 128, 129, 256, 257, 1151, 1152, 1153, 409
 RAND50_EDGE = (49, 50, 51, 1152, 1153)  # early in the list, ordinary samples follow
 ALLPOINTS = (128, 129, 256, 257, 1152, 1153)  # r = nn_radius_normals = 0.01
 ALLPOINTS_SIZES = (16384, 16385)  # kNormalsChunk and one point beyond: a last chunk of one point
-TILES = {"default": 2176, "wg4": 1408, "probe4": 2176, "normals": 1728, "train": 1280}
-PROBE4 = dict(finger_width=0.01, hand_outer_diameter=0.1)  # test_other_hand_geometries_bit_exact's 4-probe geometry
+TILES = {"default": 2176, "wg4": 1408, "probe4": 2176, "normals": 1728, "train": 1280, "normals_probe3": 1728, "train_probe3": 1280}
+# test_other_hand_geometries_bit_exact's general-probe geometry (the kLutProbe instantiations): three thresholds in its fullest
+# look-up cell, not four (tests/hand_geometries.py: three_a)
+PROBE4 = dict(finger_width=0.01, hand_outer_diameter=0.1)
+PROBE4_KINDS = ("probe4", "normals_probe3", "train_probe3")
 SAMPLE_COUNTS = (1, 7, 9, 127, 128, 4095, 4096, 4097, 65536, 65537)
 MIRROR_COUNTS = (65536, 65537)  # hypotheses: the pinned host mirror's room and one beyond
 HANDLE_COUNTS = (640, 641, 1024, 1025, 4096, 4097, 8192)
@@ -351,6 +354,6 @@ def rand50_cloud(seed=5):
 def tile_cloud(kind):
     """The crop cases of one sweep tile: (xyz, cam, samples, geometry, frames)."""
     T = TILES[kind]
-    geom = PROBE4 if kind == "probe4" else {}
+    geom = PROBE4 if kind in PROBE4_KINDS else {}
     xyz, cam, s, fr = crop_cloud(tile_targets(T), geom, seed=len(kind), pad_samples=4100 if kind == "wg4" else 0)
     return xyz, cam, s, geom, fr

@@ -94,7 +94,8 @@ def test_all_points_pass_at_class_and_chunk_edges(total):
 def test_sweep_tile_edges(kind):
     """Hand crops of T - 1, T, T + 1, 2T and 2T + 1 points for every tile size of k_hand_sweep: the reservation that does
     not fit closes the tile and the wave resumes from its cursor.  The crop's points sit in the hands' closing region, so
-    a point lost or doubled at the hand-off changes n_in_box."""
+    a point lost or doubled at the hand-off changes n_in_box.  normals_probe3 and train_probe3 repeat the antipodal and the
+    training tile with the general-probe geometry: <1, kLutProbe, kLutProbe> and <2, ..> with a hand that needs a third probe."""
     from agile_grasp_amd import binding
     from oracle import oracle_py as O
 
@@ -103,13 +104,14 @@ def test_sweep_tile_edges(kind):
     k = len(cc.tile_targets(T))
     g = {**cc.HAND_DEFAULTS, **geom}
     p = _oracle(geom)
-    anti = kind in ("normals", "train")
+    train = kind in ("train", "train_probe3")
+    anti = train or kind in ("normals", "normals_probe3")
     ctx = _ctx(**geom)
-    if kind == "train":
+    if train:
         ctx.set_training_images(True)
     ctx.set_cloud(xyz, cam)
     hyps = ctx.find_hands(s, calculates_antipodal=anti)
-    if kind == "train":
+    if train:
         ref = O.find_hands_training(p, xyz, cam, s)
         ref_fr = O.fit_frames(p, xyz, cam, s, g["nn_radius_taubin"])
     else:
@@ -124,7 +126,7 @@ def test_sweep_tile_edges(kind):
     for j in range(k):
         assert (hyps["n_in_box"][hyps["sample"] == j] > 400).any(), j  # (more points than the sample's own patch holds)
     assert_hyps_equal(hyps, ref["hyps"])
-    if kind == "train":
+    if train:
         packed = ctx.training_images()
         images = binding.unpack_images(packed.reshape(-1, 250)).reshape(-1, 3, 8000)
         assert np.array_equal(images, ref["images"])

@@ -73,7 +73,8 @@ def test_full_path_bit_exact(scene_name, svm_model):
     # radii that change the grid (cell = max(0.02, r_hands / 4)) and the number of rows a ball touches
     dict(nn_radius_taubin=0.02, nn_radius_hands=0.05),
     dict(nn_radius_taubin=0.04, nn_radius_hands=0.1, hand_outer_diameter=0.12, hand_depth=0.08),
-    # finger width = slot spacing: coincident thresholds share a look-up cell (the 4-probe kernel instantiation)
+    # finger width = slot spacing: coincident thresholds leave three to a look-up cell (the kLutProbe kernel instantiation,
+    # which probes up to four)
     dict(finger_width=0.01, hand_outer_diameter=0.1),
     dict(finger_width=0.015, hand_outer_diameter=0.105, hand_depth=0.05, init_bite=0.02, hand_height=0.03),
 ])
