@@ -99,6 +99,9 @@ EXPORTS = [
     "agh_get_label_counts",
     "agh_default_cluster_params", "agh_localize_clustered", "agh_localize_clustered_device", "agh_localize_depth_clustered",
     "agh_localize_depth_clustered_device", "agh_get_cluster_info", "agh_get_cluster_labels",
+    "agh_default_plane_fit_params", "agh_localize_clustered_fit", "agh_localize_clustered_fit_device",
+    "agh_localize_depth_clustered_fit", "agh_localize_depth_clustered_fit_device", "agh_get_plane_fit",
+    "agh_get_plane_fit_candidates",
     "agh_localize_batch_masked", "agh_localize_batch_masked_device", "agh_localize_batch_masked_begin",
     "agh_localize_batch_masked_begin_device", "agh_localize_depth_batch_masked", "agh_localize_depth_batch_masked_device",
     "agh_localize_depth_batch_masked_begin", "agh_localize_depth_batch_masked_begin_device", "agh_get_batch_mask_counts",
@@ -207,6 +210,27 @@ def cluster_params(**fields) -> AghClusterParams:
             raise TypeError(f"agh_cluster_params has no field {k}")
         setattr(cp, k, v)
     return cp
+
+
+class AghPlaneFitParams(C.Structure):
+    _fields_ = [("n_candidates", C.c_int32), ("refine", C.c_int32), ("min_inliers", C.c_int32), ("reserved", C.c_int32),
+                ("distance_threshold", C.c_double), ("seed", C.c_uint64)]
+
+
+class AghPlaneFitResult(C.Structure):
+    _fields_ = [("plane", C.c_double * 4), ("n_voxels", C.c_int64), ("n_inliers", C.c_int64), ("n_refit", C.c_int64),
+                ("best_candidate", C.c_int32), ("found", C.c_int32), ("refined", C.c_int32), ("reserved", C.c_int32)]
+
+
+def plane_fit_params(**fields) -> AghPlaneFitParams:
+    """agh_default_plane_fit_params, then the given fields."""
+    fp = AghPlaneFitParams()
+    load_library().agh_default_plane_fit_params(C.byref(fp))
+    for k, v in fields.items():
+        if not hasattr(fp, k):
+            raise TypeError(f"agh_plane_fit_params has no field {k}")
+        setattr(fp, k, v)
+    return fp
 
 
 DEPTH_U16, DEPTH_F32 = 0, 1
@@ -401,12 +425,16 @@ def load_library():
         lib.agh_plane_replay.restype = None
         lib.agh_default_plane_params.restype = None
         lib.agh_default_cluster_params.restype = None
+        lib.agh_default_plane_fit_params.restype = None
         _LIB = lib
     return _LIB
 
 
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
+
+
+_NO_FIT = object()  # localize_clustered's fp when the call is no fitted one (None there passes a NULL record)
 
 
 class Context:
@@ -736,17 +764,19 @@ class Context:
         return self._localize_labeled(fn, (recs, lrecs, C.c_int32(len(recs))), n_objects, lp, S, caps)
 
     # ---- clusters as the label source (include/agh.h, agh_localize_clustered*) ----
-    def _localize_clustered(self, fn, capture_args, cp, lp, S, caps):
+    def _localize_clustered(self, fn, capture_args, cp, lp, S, caps, fp=()):
+        """(fp: a one-tuple with the agh_plane_fit_params record, or None for NULL, of a fitted call)"""
         K = int(cp.max_objects) if cp is not None else 0
         a = {"Ck": K if 1 <= K <= 64 else 0, "S_list": [S] * (K if 1 <= K <= 64 else 0)}
         cp_arg = C.byref(cp) if cp is not None else None
-        out = self._batch_collect(a, caps, lambda *o: fn(self._h, *capture_args, cp_arg, C.byref(lp), *o))
+        fp_args = tuple(C.byref(f) if f is not None else None for f in fp)
+        out = self._batch_collect(a, caps, lambda *o: fn(self._h, *capture_args, *fp_args, cp_arg, C.byref(lp), *o))
         self.n = out[0]["n_voxels"] if out else 0
         return out
 
     def localize_clustered(self, xyz, size_left: int, workspace, cp, n_samples: int = 0, sample_seed: int = 1,
                            classify: bool = True, min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003,
-                           dense: bool = False, filters_boundaries: bool = False, samples=None, caps=None):
+                           dense: bool = False, filters_boundaries: bool = False, samples=None, caps=None, fp=_NO_FIT):
         """agh_localize_clustered (torch CUDA tensors: agh_localize_clustered_device): localize_labeled() whose objects are the
         connected components of the voxels above the support plane of `cp` (cluster_params(); None passes NULL), found on the
         device inside the call.  Returns cp.max_objects dicts; cluster_info() and cluster_labels() then describe the objects.
@@ -761,19 +791,55 @@ class Context:
             xyz_ptr, n_pts, stride_b = _p(xyz, C.c_float), xyz.shape[0], xyz.shape[1] * 4
         lp, samples, S, _ = self._localize_params(size_left, workspace, samples, n_samples, sample_seed, classify, min_inliers,
                                                   min_length, cell_size, dense, filters_boundaries)
+        if fp is not _NO_FIT:
+            fn = self.lib.agh_localize_clustered_fit_device if on_device else self.lib.agh_localize_clustered_fit
+            return self._localize_clustered(fn, (xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts)), cp, lp, S, caps, (fp,))
         fn = self.lib.agh_localize_clustered_device if on_device else self.lib.agh_localize_clustered
         return self._localize_clustered(fn, (xyz_ptr, C.c_int64(stride_b), C.c_int64(n_pts)), cp, lp, S, caps)
 
     def localize_depth_clustered(self, images, workspace, cp, n_samples: int = 0, sample_seed: int = 1, classify: bool = True,
                                  min_inliers: int = 3, min_length: float = 0.005, cell_size: float = 0.003,
-                                 filters_boundaries: bool = False, samples=None, caps=None):
+                                 filters_boundaries: bool = False, samples=None, caps=None, fp=_NO_FIT):
         """agh_localize_depth_clustered (torch CUDA tensors: agh_localize_depth_clustered_device): localize_clustered() straight
         from depth images (see depth_image_records)."""
         recs, keep, on_device = depth_image_records(images)
         lp, samples, S, _ = self._localize_params(0, workspace, samples, n_samples, sample_seed, classify, min_inliers, min_length,
                                                   cell_size, False, filters_boundaries)
+        if fp is not _NO_FIT:
+            fn = self.lib.agh_localize_depth_clustered_fit_device if on_device else self.lib.agh_localize_depth_clustered_fit
+            return self._localize_clustered(fn, (recs, C.c_int32(len(recs))), cp, lp, S, caps, (fp,))
         fn = self.lib.agh_localize_depth_clustered_device if on_device else self.lib.agh_localize_depth_clustered
         return self._localize_clustered(fn, (recs, C.c_int32(len(recs))), cp, lp, S, caps)
+
+    # ---- a fitted plane for the clustered chain (include/agh.h, agh_localize_clustered_fit*) ----
+    def localize_clustered_fit(self, xyz, size_left: int, workspace, fp, cp, **kw):
+        """agh_localize_clustered_fit (torch CUDA tensors: agh_localize_clustered_fit_device): localize_clustered() with the
+        support plane found on the device inside the call (`fp`: plane_fit_params(); None passes NULL); cp.plane is not read.
+        plane_fit() and plane_fit_candidates() then describe the fit, cluster_info() and cluster_labels() the objects."""
+        return self.localize_clustered(xyz, size_left, workspace, cp, fp=fp, **kw)
+
+    def localize_depth_clustered_fit(self, images, workspace, fp, cp, **kw):
+        """agh_localize_depth_clustered_fit (torch CUDA tensors: agh_localize_depth_clustered_fit_device): localize_clustered_fit()
+        straight from depth images (see depth_image_records)."""
+        return self.localize_depth_clustered(images, workspace, cp, fp=fp, **kw)
+
+    def plane_fit(self) -> dict:
+        """agh_get_plane_fit of the last fitted chain this context collected: plane (four doubles, zeros without a plane),
+        n_voxels, n_inliers, n_refit, best_candidate (-1: none), found, refined."""
+        r = AghPlaneFitResult()
+        self._check(self.lib.agh_get_plane_fit(self._h, C.byref(r)))
+        return {"plane": np.array(list(r.plane), np.float64), "n_voxels": r.n_voxels, "n_inliers": r.n_inliers, "n_refit": r.n_refit,
+                "best_candidate": r.best_candidate, "found": r.found, "refined": r.refined}
+
+    def plane_fit_candidates(self, cap: int = 256) -> dict:
+        """agh_get_plane_fit_candidates: per candidate of the last fitted chain its three voxel indices (`idx`, (C, 3)), its plane
+        before refit and orientation (`planes`, (C, 4)) and its inlier count (`counts`)."""
+        idx = np.zeros((max(cap, 1), 3), np.int32)
+        planes = np.zeros((max(cap, 1), 4), np.float64)
+        counts = np.zeros(max(cap, 1), np.int64)
+        n = self._check(self.lib.agh_get_plane_fit_candidates(self._h, _p(idx, C.c_int32), _p(planes, C.c_double), _p(counts, C.c_int64),
+                                                              C.c_int32(cap)))
+        return {"idx": idx[:n].copy(), "planes": planes[:n].copy(), "counts": counts[:n].copy()}
 
     def cluster_info(self, cap_objects: int = 64):
         """agh_get_cluster_info of the last clustered chain this context collected: a dict with n_foreground, n_components,

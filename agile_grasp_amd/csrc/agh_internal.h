@@ -231,6 +231,10 @@ struct LocalizeState
   // label bytes; a repeat of the whole call re-enters with these
   bool clustered = false;
   agh_cluster_params cluster{};
+  // agh_localize_clustered_fit* (plane_fit.hip): the support plane is fitted on the device in front of the cluster stage; a
+  // repeat of the whole call re-enters with these too
+  bool fitted = false;
+  agh_plane_fit_params fit{};
   // agh_localize_batch_begin / _stage / _end (localize_batch.hip) share the one chain and the one staged set of the context
   bool batch = false;         // the chain in flight is a batch's (agh_localize_batch_end collects it, not agh_localize_end)
   bool staged = false;        // stage_captures: a set of captures is (being) copied into d_stage_xyz, packed end to end,
@@ -360,6 +364,12 @@ struct Ctx
   int64_t cluster_info[4] = {};       // ... foreground, components, objects, qualifying
   int64_t cluster_sizes[kMaxClouds] = {};  // ... M_j
   int32_t cluster_ids[kMaxClouds] = {};    // ... and the smallest voxel index of object j (-1: none)
+  // a fitted plane for the clustered chain (plane_fit.hip), allocated by the first fitted call: nothing per point
+  void* d_fit = nullptr;                       // candidates' indices and planes, counts, sums and the ClusterDev record (PlaneFitBuffers)
+  agh_plane_fit_result* h_fit_result = nullptr;  // pinned: written by the chain (k_fit_finish)
+  bool fit_valid = false;                      // the last chain collected was a fitted one
+  int32_t fit_candidates = 0;                  // ... its n_candidates
+  agh_plane_fit_result fit_result{};           // ... and its result
   int32_t batch_mask_captures = 0;    // n_captures of the last chain collected if it was a masked batch, else 0
   int64_t batch_mask_counts[kMaxClouds] = {};  // ... and its M_k
   int32_t batch_label_lists = 0;      // the lists of the last chain collected if it was a labelled batch, else 0
@@ -782,8 +792,30 @@ struct ClusterDev
   float tol2;          // (float) (tolerance * tolerance): the bound of the float32 adjacency rule
   int32_t min_voxels;
 };
+// (d_cp: the record in device memory that a fitted chain's k_fit_finish writes -- the kernels read plane and bounds there, the
+// host's cp serves min_voxels alone; nullptr: the record goes by value, as agh_localize_clustered*)
 int sample_cluster_stage(Ctx* c, int64_t n, const ClusterDev& cp, int K, int64_t S, unsigned long long seed, int32_t* d_out,
-  int32_t* h_out, hipStream_t st);
+  int32_t* h_out, hipStream_t st, const ClusterDev* d_cp = nullptr);
+// plane_fit.hip: the support plane of a fitted chain (include/agh.h, agh_localize_clustered_fit), found on the voxelised cloud
+// whose preprocessing is queued on st; *d_cp_out: the device record the cluster stage reads.  origin: camera 0's, in force
+struct PlaneFitDev
+{
+  int32_t C, refine, min_inliers, pad;
+  double threshold;
+  unsigned long long seed;
+  double origin[3];
+};
+constexpr int kPlaneFitMaxCandidates = 256;
+struct PlaneFitBuffers  // the one device block of a context's fitted calls
+{
+  double planes[kPlaneFitMaxCandidates][4];
+  int32_t idx[kPlaneFitMaxCandidates][3];
+  unsigned counts[kPlaneFitMaxCandidates];
+  unsigned long long sums[16];  // [0] n_refit, [1 .. 3] Sx Sy Sz, [4 .. 9] Sxx Sxy Sxz Syy Syz Szz
+  ClusterDev record;
+};
+std::string plane_fit_params_fault(const agh_plane_fit_params& fp);
+int plane_fit_stage(Ctx* c, int64_t n, const agh_plane_fit_params& fp, const ClusterDev& cp, hipStream_t st, const ClusterDev** d_cp_out);
 inline ClusterDev cluster_dev(const agh_cluster_params& q)
 {
   return ClusterDev{ { q.plane[0], q.plane[1], q.plane[2], q.plane[3] }, q.min_height, q.max_height, q.tolerance,

@@ -517,7 +517,7 @@ void agh_destroy(agh_ctx* ctx)
     c->d_desc_next, c->d_count_part, c->d_grid_miss, c->d_depth, c->d_depth_stage, c->d_depth_views,
     c->d_mask, c->d_mask_bitmap, c->d_mask_blk, c->d_mask_total, c->d_mask_list,
     c->d_label_rank, c->d_label_set, c->d_label_groups, c->d_label_totals,
-    c->d_cluster_parent, c->d_cluster_size, c->d_cluster_label, c->d_cluster_counts };
+    c->d_cluster_parent, c->d_cluster_size, c->d_cluster_label, c->d_cluster_counts, c->d_fit };
   for (void* p : ptrs)
     if (p)
       (void) hipFree(p);
@@ -527,6 +527,8 @@ void agh_destroy(agh_ctx* ctx)
     (void) hipHostFree(c->h_label_counts);
   if (c->h_cluster_table)
     (void) hipHostFree(c->h_cluster_table);
+  if (c->h_fit_result)
+    (void) hipHostFree(c->h_fit_result);
   if (c->h_pin_handles)
     (void) hipHostFree(c->h_pin_handles);
   if (c->h_pin_keep)

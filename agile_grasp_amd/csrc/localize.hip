@@ -265,6 +265,7 @@ struct MaskSource
   int32_t n_objects = 0;          // agh_localize_labeled*: the bytes are labels 1 .. n_objects (0: a mask)
   bool labeled = false;
   const agh_cluster_params* cluster = nullptr;  // agh_localize_clustered*: no bytes at all, the objects are the cloud's components
+  const agh_plane_fit_params* fit = nullptr;    // agh_localize_clustered_fit*: ... above a plane the chain fits (cluster->plane unread)
 };
 static_assert(sizeof(agh_label_image) == sizeof(agh_sample_mask) && offsetof(agh_label_image, data) == offsetof(agh_sample_mask, data) &&
                 offsetof(agh_label_image, row_stride_bytes) == offsetof(agh_sample_mask, row_stride_bytes),
@@ -299,7 +300,15 @@ static int mask_check(Ctx* c, const MaskSource* mask, const DepthSource* depth, 
   };
   if (mask->cluster)
   {
-    const agh_cluster_params& cp = *mask->cluster;
+    agh_cluster_params cp = *mask->cluster;
+    if (mask->fit)  // (the plane is the chain's to find: the caller's is neither read nor validated)
+    {
+      const std::string fit_fault = plane_fit_params_fault(*mask->fit);
+      if (!fit_fault.empty())
+        return bad(fit_fault);
+      cp.plane[0] = cp.plane[1] = cp.plane[3] = 0.0;
+      cp.plane[2] = 1.0;
+    }
     const std::string fault = cluster_params_fault(cp);
     if (!fault.empty())
       return bad(fault);
@@ -485,6 +494,9 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   L.clustered = mask && mask->cluster;
   if (L.clustered)
     L.cluster = *mask->cluster;
+  L.fitted = L.clustered && mask->fit;
+  if (L.fitted)
+    L.fit = *mask->fit;
   L.S = S;
   L.classify = lp->classify != 0;
   L.filters = lp->filters_boundaries != 0;
@@ -526,7 +538,11 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   // ---- 3. the sample list ----
   if (L.clustered)  // (the grid build is queued: the preprocessing above bound the voxelised cloud)
   {
-    if ((rc = sample_cluster_stage(c, n, cluster_dev(L.cluster), K, S, (unsigned long long) lp->sample_seed, c->d_idx_own, h_idx_labeled, st)) != AGH_OK)
+    // (a fitted chain: the plane is found first, on the same stream, and the cluster kernels read the record it leaves on the device)
+    const ClusterDev* d_cp = nullptr;
+    if (L.fitted && (rc = plane_fit_stage(c, n, L.fit, cluster_dev(L.cluster), st, &d_cp)) != AGH_OK)
+      return chain_fail(c, rc);
+    if ((rc = sample_cluster_stage(c, n, cluster_dev(L.cluster), K, S, (unsigned long long) lp->sample_seed, c->d_idx_own, h_idx_labeled, st, d_cp)) != AGH_OK)
       return chain_fail(c, rc);
   }
   else if (K)  // (for S = 0 too, as the mask's)
@@ -574,6 +590,7 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
   c->mask_count = -1;
   c->label_objects = 0;
   c->cluster_objects = 0;
+  c->fit_valid = false;
   c->batch_mask_captures = 0;
   c->batch_label_lists = 0;
   c->batch_cluster_captures = 0;
@@ -609,9 +626,10 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
         L.repeated = true;
         // (a mask is where the chain read it, as the capture is: in the context's buffer, or in the caller's device memory)
         const agh_cluster_params cluster = L.cluster;
+        const agh_plane_fit_params fit = L.fit;
         const MaskSource again{ L.d_mask, nullptr, true,
           L.clustered ? "agh_localize_clustered" : (L.n_objects ? "agh_localize_labeled" : "agh_localize_masked"), L.n_objects,
-          L.n_objects != 0, L.clustered ? &cluster : nullptr };
+          L.n_objects != 0, L.clustered ? &cluster : nullptr, L.fitted ? &fit : nullptr };
         rc = localize_begin_impl(ctx, L.d_raw, true, L.dev_stride, L.n_raw, &lp, nullptr, L.masked ? &again : nullptr);
         if (rc == AGH_OK)
           rc = localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result,
@@ -646,6 +664,12 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
       {
         c->cluster_sizes[j] = (int64_t) t[8 + j];
         c->cluster_ids[j] = (int32_t) t[8 + kMaxClouds + j];
+      }
+      if (L.fitted)  // (the record k_fit_finish wrote into pinned memory: here with the chain's one synchronisation)
+      {
+        c->fit_valid = true;
+        c->fit_candidates = L.fit.n_candidates;
+        c->fit_result = *c->h_fit_result;
       }
     }
     else
@@ -891,10 +915,15 @@ int agh_localize_depth_labeled_device(agh_ctx* ctx, const agh_depth_image* image
 static int clustered_call(agh_ctx* ctx, const float* xyz, bool on_device, int64_t stride_bytes, int64_t n, const DepthSource* depth,
   const char* who, const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap,
   int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
-  agh_localize_batch_result* results)
+  agh_localize_batch_result* results, const agh_plane_fit_params* fp = nullptr, bool fitted = false)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
+  if (fitted && !fp)
+  {
+    ctx->c.err = std::string(who) + ": fp is NULL";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
   if (!cp)
   {
     ctx->c.err = std::string(who) + ": cp is NULL";
@@ -904,7 +933,7 @@ static int clustered_call(agh_ctx* ctx, const float* xyz, bool on_device, int64_
   if (results && K >= 1 && K <= kMaxClouds)
     for (int j = 0; j < K; j++)
       results[j] = agh_localize_batch_result{ { 0, 0, 0, 0, 0 }, 0, 0, 0, 0 };
-  const MaskSource m{ nullptr, nullptr, on_device, who, K, true, cp };
+  const MaskSource m{ nullptr, nullptr, on_device, who, K, true, cp, fp };
   int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
   if (rc == AGH_OK)
     rc = localize_begin_impl(ctx, xyz, depth ? false : on_device, stride_bytes, n, lp, depth, &m);
@@ -952,6 +981,105 @@ int agh_localize_depth_clustered_device(agh_ctx* ctx, const agh_depth_image* ima
   const DepthSource src{ images, n_images, true, "agh_localize_depth_clustered_device" };
   return clustered_call(ctx, nullptr, true, 12, 0, &src, src.who, cp, lp, handles_out, handle_cap, inlier_idx_out, idx_cap,
     hands_out, hands_cap, samples_out, results);
+}
+
+// ---- the fitted forms (include/agh.h, agh_localize_clustered_fit*): the clustered call with the plane found by plane_fit.hip ----
+
+void agh_default_plane_fit_params(agh_plane_fit_params* p)
+{
+  if (!p)
+    return;
+  *p = agh_plane_fit_params{ 128, 1, 3, 0, 0.01, 1 };
+}
+
+int agh_localize_clustered_fit(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_plane_fit_params* fp,
+  const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  return clustered_call(ctx, xyz, false, stride_bytes, n, nullptr, "agh_localize_clustered_fit", cp, lp, handles_out, handle_cap,
+    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results, fp, true);
+}
+
+int agh_localize_clustered_fit_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const agh_plane_fit_params* fp,
+  const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  return clustered_call(ctx, d_xyz, true, stride_bytes, n, nullptr, "agh_localize_clustered_fit_device", cp, lp, handles_out,
+    handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results, fp, true);
+}
+
+int agh_localize_depth_clustered_fit(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_plane_fit_params* fp,
+  const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthSource src{ images, n_images, false, "agh_localize_depth_clustered_fit" };
+  return clustered_call(ctx, nullptr, false, 12, 0, &src, src.who, cp, lp, handles_out, handle_cap, inlier_idx_out, idx_cap,
+    hands_out, hands_cap, samples_out, results, fp, true);
+}
+
+int agh_localize_depth_clustered_fit_device(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out,
+  int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
+{
+  const DepthSource src{ images, n_images, true, "agh_localize_depth_clustered_fit_device" };
+  return clustered_call(ctx, nullptr, true, 12, 0, &src, src.who, cp, lp, handles_out, handle_cap, inlier_idx_out, idx_cap,
+    hands_out, hands_cap, samples_out, results, fp, true);
+}
+
+// the last chain collected, if it was a fitted one (`fn` refuses otherwise, and mid-chain)
+static int plane_fit_getter_check(Ctx* c, const char* fn)
+{
+  if (refuse_mid_chain(c, fn))
+    return AGH_ERR_STATE;
+  if (c->cluster_objects < 1 || !c->fit_valid)
+  {
+    c->err = std::string(fn) + ": the last chain this context collected was not a fitted one (or there was none)";
+    return AGH_ERR_STATE;
+  }
+  return AGH_OK;
+}
+
+int agh_get_plane_fit(agh_ctx* ctx, agh_plane_fit_result* out)
+{
+  if (!ctx || !out)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (int rc = plane_fit_getter_check(c, "agh_get_plane_fit"))
+    return rc;
+  *out = c->fit_result;
+  return AGH_OK;
+}
+
+int agh_get_plane_fit_candidates(agh_ctx* ctx, int32_t* idx, double* planes, int64_t* counts, int32_t cap)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (int rc = plane_fit_getter_check(c, "agh_get_plane_fit_candidates"))
+    return rc;
+  const int C = c->fit_candidates;
+  if ((idx || planes || counts) && cap < C)
+  {
+    c->err = "agh_get_plane_fit_candidates: cap is below the call's n_candidates";
+    return AGH_ERR_CAPACITY;
+  }
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  // (the candidates stay on the device until somebody asks: a blocking copy each, behind whatever the context's stream holds)
+  const PlaneFitBuffers* fb = static_cast<const PlaneFitBuffers*>(c->d_fit);
+  AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (idx)
+    AGH_HIPCHK(c, hipMemcpy(idx, fb->idx, sizeof(int32_t) * 3 * (size_t) C, hipMemcpyDeviceToHost));
+  if (planes)
+    AGH_HIPCHK(c, hipMemcpy(planes, fb->planes, sizeof(double) * 4 * (size_t) C, hipMemcpyDeviceToHost));
+  if (counts)
+  {
+    unsigned h[kPlaneFitMaxCandidates];
+    AGH_HIPCHK(c, hipMemcpy(h, fb->counts, sizeof(unsigned) * (size_t) C, hipMemcpyDeviceToHost));
+    for (int k = 0; k < C; k++)
+      counts[k] = (int64_t) h[k];
+  }
+  return C;
 }
 
 // the last chain collected, if it was clustered (`fn` refuses otherwise, and mid-chain)

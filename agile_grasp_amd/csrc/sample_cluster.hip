@@ -11,6 +11,8 @@
 //   k_cluster_select    one work-group: the roots of size >= min_voxels, the K largest of them by (size, smaller id), their rank
 //                       into size[root] (as -1 - rank), ids, sizes and counts into the pinned table
 //   k_cluster_mark      objset[v] = 1 << rank of v's root (or 0), and the label byte of agh_get_cluster_labels
+// A fitted chain (agh_localize_clustered_fit*, plane_fit.hip) finds the plane on the device: k_cluster_init_dev and
+// k_cluster_link_dev read the ClusterDev record from device memory, where k_fit_finish left it, around the same bodies.
 // From there the label stage's compaction runs unchanged (label_compact_stage).  Everything is queued on the chain's stream behind
 // the grid build; launches are sized from the raw point count, the voxel count and the grid's descriptor are read on the device.
 //
@@ -114,10 +116,25 @@ __device__ __forceinline__ void cluster_init_voxel(const float* __restrict__ xyz
     atomicAdd(counts, (unsigned long long) __popcll(m));
 }
 
+// (the single cloud's form, wherever its record lies)
+__device__ __forceinline__ void cluster_init_single(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
+  int64_t n, const ClusterDev& cp, int* __restrict__ parent, int* __restrict__ size, unsigned long long* __restrict__ counts)
+{
+  cluster_init_voxel(xyz, stride, 0, label_voxels(d, n), cp, parent, size, counts);
+}
+
 __global__ __launch_bounds__(256) void k_cluster_init(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
   int64_t n, ClusterDev cp, int* __restrict__ parent, int* __restrict__ size, unsigned long long* __restrict__ counts)
 {
-  cluster_init_voxel(xyz, stride, 0, label_voxels(d, n), cp, parent, size, counts);
+  cluster_init_single(xyz, stride, d, n, cp, parent, size, counts);
+}
+
+// ... with the record read from device memory: a fitted chain's, which k_fit_finish (plane_fit.hip) wrote in front of this launch
+__global__ __launch_bounds__(256) void k_cluster_init_dev(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
+  int64_t n, const ClusterDev* __restrict__ cpd, int* __restrict__ parent, int* __restrict__ size, unsigned long long* __restrict__ counts)
+{
+  const ClusterDev cp = *cpd;
+  cluster_init_single(xyz, stride, d, n, cp, parent, size, counts);
 }
 
 // ... for capture blockIdx.y of a batch, with ITS record of the device table and its four counters (no voxel for a capture whose
@@ -250,11 +267,25 @@ __device__ __forceinline__ void cluster_link_groups(const GridView& gv, const Cl
   }
 }
 
-__global__ __launch_bounds__(kClusterTile) void k_cluster_link(GridView gv, const VoxDesc* __restrict__ d, ClusterDev cp, int* parent)
+// (the single cloud's form, wherever its record lies)
+__device__ __forceinline__ void cluster_link_single(const GridView& gv, const VoxDesc* __restrict__ d, const ClusterDev& cp, int* parent)
 {
   if (d->error)
     return;
   cluster_link_groups(gv, cp, parent);
+}
+
+__global__ __launch_bounds__(kClusterTile) void k_cluster_link(GridView gv, const VoxDesc* __restrict__ d, ClusterDev cp, int* parent)
+{
+  cluster_link_single(gv, d, cp, parent);
+}
+
+// ... with the record read from device memory (a fitted chain's, as k_cluster_init_dev)
+__global__ __launch_bounds__(kClusterTile) void k_cluster_link_dev(GridView gv, const VoxDesc* __restrict__ d,
+  const ClusterDev* __restrict__ cpd, int* parent)
+{
+  const ClusterDev cp = *cpd;
+  cluster_link_single(gv, d, cp, parent);
 }
 
 // ... for capture blockIdx.y of a batch: the cell groups of ITS descriptor and cell table, shared among the gridDim.x work-groups
@@ -467,8 +498,10 @@ static int ensure_cluster_buffers(Ctx* c, int64_t n)
   return AGH_OK;
 }
 
+// (d_cp: a fitted chain's record in device memory -- k_cluster_init_dev and k_cluster_link_dev read it in place of cp, same
+// shapes; the selection takes min_voxels from the host's cp either way)
 int sample_cluster_stage(Ctx* c, int64_t n, const ClusterDev& cp, int K, int64_t S, unsigned long long seed, int32_t* d_out,
-  int32_t* h_out, hipStream_t st)
+  int32_t* h_out, hipStream_t st, const ClusterDev* d_cp)
 {
   int rc;
   const int64_t n_groups = (n + kLabelGroup - 1) / kLabelGroup;
@@ -481,12 +514,20 @@ int sample_cluster_stage(Ctx* c, int64_t n, const ClusterDev& cp, int K, int64_t
   {
     const unsigned blocks = (unsigned) ((n + 255) / 256);
     // (the voxelised cloud is the context's bound cloud: the preprocessing queued in front of this stage bound it)
-    hipLaunchKernelGGL(k_cluster_init, dim3(blocks), dim3(256), 0, st, c->d_xyz, c->stride_floats, desc, n, cp, c->d_cluster_parent,
-      c->d_cluster_size, c->d_cluster_counts);
+    if (d_cp)
+      hipLaunchKernelGGL(k_cluster_init_dev, dim3(blocks), dim3(256), 0, st, c->d_xyz, c->stride_floats, desc, n, d_cp,
+        c->d_cluster_parent, c->d_cluster_size, c->d_cluster_counts);
+    else
+      hipLaunchKernelGGL(k_cluster_init, dim3(blocks), dim3(256), 0, st, c->d_xyz, c->stride_floats, desc, n, cp, c->d_cluster_parent,
+        c->d_cluster_size, c->d_cluster_counts);
     const GridView gv{ c->d_desc, c->d_cell_start, c->d_sorted, c->d_cloud_off, 1 };
     // (a work-group per 64 raw points, at most 4096: each walks its share of the grid's cell groups)
-    hipLaunchKernelGGL(k_cluster_link, dim3((unsigned) std::min<int64_t>((n + 63) / 64, 4096)), dim3(kClusterTile), 0, st, gv, desc, cp,
-      c->d_cluster_parent);
+    if (d_cp)
+      hipLaunchKernelGGL(k_cluster_link_dev, dim3((unsigned) std::min<int64_t>((n + 63) / 64, 4096)), dim3(kClusterTile), 0, st, gv,
+        desc, d_cp, c->d_cluster_parent);
+    else
+      hipLaunchKernelGGL(k_cluster_link, dim3((unsigned) std::min<int64_t>((n + 63) / 64, 4096)), dim3(kClusterTile), 0, st, gv, desc,
+        cp, c->d_cluster_parent);
     hipLaunchKernelGGL(k_cluster_flatten, dim3(blocks), dim3(256), 0, st, desc, n, c->d_cluster_parent, c->d_cluster_size,
       c->d_cluster_counts);
   }

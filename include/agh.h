@@ -283,14 +283,14 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
  * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled*, agh_localize_depth_labeled*,
- * agh_localize_clustered*, agh_localize_depth_clustered*,
+ * agh_localize_clustered*, agh_localize_depth_clustered*, agh_localize_clustered_fit*, agh_localize_depth_clustered_fit*,
  * agh_localize_batch_masked*, agh_localize_batch_masked_begin*, agh_localize_depth_batch_masked*,
  * agh_localize_depth_batch_masked_begin*, agh_localize_batch_labeled*, agh_localize_batch_labeled_begin*,
  * agh_localize_depth_batch_labeled*, agh_localize_depth_batch_labeled_begin*, agh_localize_batch_clustered*,
  * agh_localize_batch_clustered_begin*, agh_localize_depth_batch_clustered* and agh_localize_depth_batch_clustered_begin* among
  * them), agh_deproject, agh_deproject_batch,
  * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info,
- * agh_get_cluster_labels, agh_get_batch_mask_counts,
+ * agh_get_cluster_labels, agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts,
  * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
@@ -537,7 +537,8 @@ int agh_get_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_objects)
  *     AGH_ERR_STATE after a chain of another kind, if there was none, or while a chain is in flight; after a clustered call
  *     agh_get_label_counts and agh_get_sample_mask_count return AGH_ERR_STATE.
  * 10. A context that made a clustered call holds two 32-bit words and a byte per raw point beside the labelled chain's buffers.
- * Not built: a fitted plane (the caller supplies it); more than 64 objects; _begin / _end, _stage and sharded forms of this
+ * Not built: more than 64 objects (a caller without a calibrated plane: agh_localize_clustered_fit below finds it inside the
+ * call); _begin / _end, _stage and sharded forms of this
  * single-capture call.  Several captures per call, _begin / _end included, are agh_localize_batch_clustered* below; batch and sharded
  * chains do not combine.  The 8192-hand limit holds per object. */
 typedef struct agh_cluster_params
@@ -569,6 +570,90 @@ typedef struct agh_cluster_info
 int agh_get_cluster_info(agh_ctx* ctx, agh_cluster_info* info, int64_t* n_voxels /* M_j */, int32_t* ids /* smallest voxel index */,
   int32_t cap_objects);
 int agh_get_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap);  /* per voxel of the bound cloud: 0 or j + 1 */
+
+/* The clustered chain WITH THE SUPPORT PLANE FITTED ON THE DEVICE: a mobile base, a hand-held sensor or a cell whose table moves
+ * has no calibrated plane.  agh_localize_clustered_fit finds the dominant plane of the voxelised cloud behind the preprocessing
+ * and in front of the cluster stage, writes it into a record in device memory that the cluster kernels read, and from there on IS
+ * agh_localize_clustered: nothing returns to the host, the chain keeps its one synchronisation, the table stays in the cloud.  The
+ * finder is this project's own, made for the device (agh_remove_plane restates PCL's serial RANSAC and deletes the plane):
+ * candidates drawn in parallel, one scoring pass with integer counts, a refit from exact integer moments.
+ * Everything is stated on the voxelised cloud of the call: N its voxels, p_v voxel v's float32 point promoted to double; all
+ * arithmetic is double, never contracted, products and sums evaluated in the order written.
+ *  1. Draw.  Candidate c < C = n_candidates takes the voxels i_s = splitmix64(seed ^ ((3 c + s) * 0x9E3779B97F4A7C15)) % N,
+ *     s = 0, 1, 2 (the generator of agh_localize's sample strata; the product wraps at 2^64).  N < 3 is "no plane": every
+ *     candidate is invalid and its reported indices are -1.
+ *  2. Candidate.  u = p1 - p0, v = p2 - p0; n = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x);
+ *     l2 = (n_x n_x + n_y n_y) + n_z n_z.  The candidate is INVALID, count 0 and a reported plane of zeros, unless l2 is finite
+ *     and > 0 (a repeated index is such a case).  Otherwise n /= sqrt(l2), three divisions, and d = -((n_x x0 + n_y y0) + n_z z0).
+ *  3. Score.  Voxel v is an inlier of c iff fabs(((a x + b y) + c z) + d) <= distance_threshold: rule 1 of
+ *     agh_localize_clustered's evaluation order.  The count is an integer.
+ *  4. Choice.  The candidate with the largest count, ties to the smaller c; found = (its count >= max(min_inliers, 3)).  No
+ *     early termination: every candidate is scored.
+ *  5. Refit (refine and found).  Over the chosen candidate's inliers the float32 differences dx = x - x0, dy, dz against the
+ *     candidate's own p0; an inlier with any |difference| >= 8 is left out; q = (int64) rint((double) dx * 65536.0) and likewise;
+ *     n_refit and the int64 sums Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz of the q and their products (|q| < 2^19 and at most
+ *     2^24 contributors: no sum can overflow; derived, not measured).  Skipped when n_refit < 3 or > 2^24.  Nn = (double) n_refit;
+ *     m_x = ((double) Sx / Nn) * 2^-16 and likewise; M00 = ((double) Sxx / Nn) * 2^-32 - m_x m_x, and likewise M01, M02, M11,
+ *     M12, M22; (a, b, c) = the unit eigenvector of M's smallest eigenvalue (the library's smallest_eigvec3: one Householder
+ *     reflection, bisection, twisted factorisation).  A non-finite component leaves the candidate's plane standing; otherwise
+ *     c_x = (double) x0 + m_x and likewise, d = -((a c_x + b c_y) + c c_z), refined = 1.
+ *  6. Orientation.  s = ((a o_x + b o_y) + c o_z) + d at camera 0's origin in force for the call (agh_params::cam_origin[0], or
+ *     row 0 of a one-row agh_set_cloud_cam_origins table); s < 0 negates all four numbers; s == 0 or a non-finite s leaves them.
+ *  7. Use.  With found, the call equals agh_localize_clustered on the same capture, lp and cp with cp.plane set to the reported
+ *     plane, bit for bit (epoch aside): every output, results[j], agh_get_cluster_info and agh_get_cluster_labels.  Without found
+ *     it returns AGH_OK with K empty objects and no foreground (the device record carries a NaN plane, background by rule 1 of
+ *     agh_localize_clustered), and the reported plane is zeros.
+ *  8. The same call twice gives the same bits: counts and sums are integers, nothing depends on the order of an atomic operation.
+ *  9. The _device forms read device points (images) in place; the depth forms equal the points form on the array agh_deproject
+ *     writes, as agh_localize_depth_clustered does.
+ * 10. cp->plane is ignored and not validated; every other field of cp and lp follows agh_localize_clustered's rules 7 and 8.
+ *     AGH_ERR_INVALID_ARGUMENT, the text naming the field, nothing launched: n_candidates outside 1 .. 256; refine not 0 or 1;
+ *     min_inliers < 3; reserved != 0; distance_threshold not finite, <= 0 or > 0.05; fp == NULL.  AGH_ERR_NO_SVM, AGH_ERR_CAPACITY
+ *     with results filled, AGH_ERR_STATE while a chain or a batch is in flight, the one-row rule for a camera-origin table and the
+ *     repeats inside the call (a lattice that outgrew the kept bitmap re-enters with the same fit parameters) are the clustered
+ *     call's.
+ * 11. agh_get_plane_fit and agh_get_plane_fit_candidates describe the last chain this context collected if it was a fitted one
+ *     (AGH_ERR_STATE otherwise, and while a chain is in flight): the result record -- it arrives in pinned memory with the chain's
+ *     one synchronisation -- and, for introspection (the call copies from the device and may synchronise), per candidate its three
+ *     voxel indices, its plane BEFORE refit and orientation, and its count; any of the three arrays may be NULL, the return value
+ *     is C, AGH_ERR_CAPACITY if cap is below it.  After a fitted call agh_get_cluster_info and agh_get_cluster_labels work as
+ *     after agh_localize_clustered; agh_get_label_counts and agh_get_sample_mask_count return AGH_ERR_STATE.
+ * 12. A context's first fitted call allocates 256 candidates (indices, planes, counts), ten sums and one record on the device,
+ *     and one result record in pinned memory: nothing per point.
+ * Not built: batch forms; _begin / _end forms; _stage forms; sharded forms; more than 256 candidates; a termination rule. */
+typedef struct agh_plane_fit_params
+{
+  int32_t  n_candidates;        /* C: 1 .. 256 */
+  int32_t  refine;              /* 0 or 1 */
+  int32_t  min_inliers;         /* >= 3: a best count below it is "no plane" */
+  int32_t  reserved;            /* must be 0 */
+  double   distance_threshold;  /* finite, > 0, <= 0.05 */
+  uint64_t seed;
+} agh_plane_fit_params;
+typedef struct agh_plane_fit_result
+{
+  double  plane[4];             /* the plane the cluster stage used; zeros when found == 0 */
+  int64_t n_voxels, n_inliers, n_refit;
+  int32_t best_candidate;       /* -1: none */
+  int32_t found, refined, reserved;
+} agh_plane_fit_result;
+void agh_default_plane_fit_params(agh_plane_fit_params* p);  /* 128 candidates; refine 1; min_inliers 3; threshold 0.01; seed 1 */
+int agh_localize_clustered_fit(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_plane_fit_params* fp,
+  const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_localize_clustered_fit_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const agh_plane_fit_params* fp,
+  const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_localize_depth_clustered_fit(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_plane_fit_params* fp,
+  const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
+  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, struct agh_localize_batch_result* results);
+int agh_localize_depth_clustered_fit_device(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out,
+  int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  struct agh_localize_batch_result* results);
+int agh_get_plane_fit(agh_ctx* ctx, agh_plane_fit_result* out);
+int agh_get_plane_fit_candidates(agh_ctx* ctx, int32_t* idx /* 3 per candidate */, double* planes /* 4 per candidate */,
+  int64_t* counts, int32_t cap);
 
 /* The chain of agh_localize over a BATCH of captures in one call, with ONE synchronisation (offline evaluation over a
  * directory of PCD pairs, a cell with several sensors or arms): 1 <= n_captures <= 64, fewer than 2^30 raw points in all.
@@ -634,10 +719,11 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * and agh_localize_depth_labeled*, agh_localize_batch_masked*, agh_localize_batch_masked_begin*,
  * agh_localize_depth_batch_masked* and agh_localize_depth_batch_masked_begin*, agh_localize_batch_labeled*,
  * agh_localize_batch_labeled_begin*, agh_localize_depth_batch_labeled* and agh_localize_depth_batch_labeled_begin*;
- * agh_localize_clustered* and agh_localize_depth_clustered*; agh_localize_batch_clustered*,
+ * agh_localize_clustered* and agh_localize_depth_clustered*; agh_localize_clustered_fit* and
+ * agh_localize_depth_clustered_fit*; agh_localize_batch_clustered*,
  * agh_localize_batch_clustered_begin*, agh_localize_depth_batch_clustered* and agh_localize_depth_batch_clustered_begin*;
  * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info, agh_get_cluster_labels,
- * agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info and agh_get_batch_cluster_labels are
+ * agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info and agh_get_batch_cluster_labels are
  * refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those

@@ -528,11 +528,13 @@ public:
   /** Additional: one capture, one sample list PER OBJECT THE CALL FINDS (agh_localize_clustered): the objects are the connected
    *  components of the voxels that stand above the support plane of `cp` (include/agh.h has the rules), at most cp.max_objects
    *  of them, largest first; from there on the call is localizeLabeled's.  Outputs per object (cp.max_objects lists);
-   *  clusterInfo() and clusterLabels() then describe the objects.  One blocking call.  @return false (after printing) on error */
+   *  clusterInfo() and clusterLabels() then describe the objects.  One blocking call.  With `fp` the support plane is found on
+   *  the device inside the call (agh_localize_clustered_fit: cp.plane is not read; planeFit() then reports it).
+   *  @return false (after printing) on error */
   bool localizeClustered(const PointCloud::Ptr& cloud_in, int size_left, const agh_cluster_params& cp, const VectorXd& workspace,
     double cell_size, const std::string& svm_filename, int min_inliers, double min_length,
     std::vector<std::vector<agh_hypothesis> >& hands_out, std::vector<std::vector<agh_handle> >& handles_out,
-    std::vector<std::vector<std::int32_t> >& inliers_out, bool filters_boundaries = false)
+    std::vector<std::vector<std::int32_t> >& inliers_out, bool filters_boundaries = false, const agh_plane_fit_params* fp = nullptr)
   {
     labeledClear(cp.max_objects, hands_out, handles_out, inliers_out);
     if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
@@ -546,21 +548,24 @@ public:
       sampleSeed(), min_inliers, min_length, filters_boundaries);
     const RawPoints in = rawPoints(*cloud_in);
     LabeledOutputs o(cp.max_objects, lp.n_samples);
-    if (agh_localize_clustered(ctx_, in.xyz, in.stride, in.n, &cp, &lp, o.handles.data(), o.cap, o.inl.data(), o.cap, o.hands.data(),
-          o.cap, o.samples.data(), o.res.data()) != AGH_OK)
+    const int rc = fp ? agh_localize_clustered_fit(ctx_, in.xyz, in.stride, in.n, fp, &cp, &lp, o.handles.data(), o.cap, o.inl.data(),
+                          o.cap, o.hands.data(), o.cap, o.samples.data(), o.res.data())
+                      : agh_localize_clustered(ctx_, in.xyz, in.stride, in.n, &cp, &lp, o.handles.data(), o.cap, o.inl.data(), o.cap,
+                          o.hands.data(), o.cap, o.samples.data(), o.res.data());
+    if (rc != AGH_OK)
     {
-      fail("agh_localize_clustered");
+      fail(fp ? "agh_localize_clustered_fit" : "agh_localize_clustered");
       return false;
     }
     labeledCollect(o, hands_out, handles_out, inliers_out);
     return true;
   }
 
-  /** ... and straight from depth images (agh_localize_depth_clustered) */
+  /** ... and straight from depth images (agh_localize_depth_clustered; with `fp`: agh_localize_depth_clustered_fit) */
   bool localizeDepthClustered(const std::vector<DepthImage>& images, const agh_cluster_params& cp, const VectorXd& workspace,
     double cell_size, const std::string& svm_filename, int min_inliers, double min_length,
     std::vector<std::vector<agh_hypothesis> >& hands_out, std::vector<std::vector<agh_handle> >& handles_out,
-    std::vector<std::vector<std::int32_t> >& inliers_out, bool filters_boundaries = false)
+    std::vector<std::vector<std::int32_t> >& inliers_out, bool filters_boundaries = false, const agh_plane_fit_params* fp = nullptr)
   {
     labeledClear(cp.max_objects, hands_out, handles_out, inliers_out);
     if (!ensureContext() || !detail::loadSvm(ctx_, svm_filename))
@@ -569,10 +574,14 @@ public:
       min_length, filters_boundaries);
     const std::vector<agh_depth_image> recs = depthRecords(images);
     LabeledOutputs o(cp.max_objects, lp.n_samples);
-    if (agh_localize_depth_clustered(ctx_, recs.empty() ? nullptr : recs.data(), (std::int32_t) recs.size(), &cp, &lp, o.handles.data(),
-          o.cap, o.inl.data(), o.cap, o.hands.data(), o.cap, o.samples.data(), o.res.data()) != AGH_OK)
+    const agh_depth_image* im = recs.empty() ? nullptr : recs.data();
+    const int rc = fp ? agh_localize_depth_clustered_fit(ctx_, im, (std::int32_t) recs.size(), fp, &cp, &lp, o.handles.data(), o.cap,
+                          o.inl.data(), o.cap, o.hands.data(), o.cap, o.samples.data(), o.res.data())
+                      : agh_localize_depth_clustered(ctx_, im, (std::int32_t) recs.size(), &cp, &lp, o.handles.data(), o.cap,
+                          o.inl.data(), o.cap, o.hands.data(), o.cap, o.samples.data(), o.res.data());
+    if (rc != AGH_OK)
     {
-      fail("agh_localize_depth_clustered");
+      fail(fp ? "agh_localize_depth_clustered_fit" : "agh_localize_depth_clustered");
       return false;
     }
     labeledCollect(o, hands_out, handles_out, inliers_out);
@@ -596,6 +605,14 @@ public:
     n_voxels.assign(m.begin(), m.begin() + (std::ptrdiff_t) k);
     ids.assign(id.begin(), id.begin() + (std::ptrdiff_t) k);
     return true;
+  }
+
+  /** agh_get_plane_fit: the plane, the counts and the flags of the last fitted call; false, with a zeroed record, if the last
+   *  chain collected was not a fitted one */
+  bool planeFit(agh_plane_fit_result& result)
+  {
+    result = agh_plane_fit_result();
+    return ctx_ && agh_get_plane_fit(ctx_, &result) == AGH_OK;
   }
 
   /** agh_get_cluster_labels: per voxel of the searched cloud 0 or object + 1; empty if the last chain was not clustered */

@@ -489,10 +489,29 @@ public:
     const std::string& svm_filename, int min_inliers, double min_length,
     std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object = nullptr)
   {
-    const agh_cluster_params cp = clusterParams(plane);
+    return clusteredHandles("localizeHandlesClustered", cloud_in, size_left, clusterParams(plane), nullptr, svm_filename, min_inliers,
+      min_length, antipodal_hands_per_object);
+  }
+
+  /** ... WITHOUT A CALIBRATED PLANE (agh_localize_clustered_fit): the dominant plane of the voxelised cloud is found on the device
+   *  inside the call (setPlaneFitParams), oriented towards camera 0, and used as the support plane; fittedPlane() reports it.  No
+   *  plane found: max_objects empty lists, as for an empty table. */
+  std::vector<std::vector<Handle> > localizeHandlesClusteredFit(const PointCloud::Ptr& cloud_in, int size_left,
+    const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object = nullptr)
+  {
+    return clusteredHandles("localizeHandlesClusteredFit", cloud_in, size_left, cluster_, &plane_fit_, svm_filename, min_inliers,
+      min_length, antipodal_hands_per_object);
+  }
+
+  // the body of the two: fp == nullptr takes cp's plane
+  std::vector<std::vector<Handle> > clusteredHandles(const char* fn, const PointCloud::Ptr& cloud_in, int size_left,
+    const agh_cluster_params& cp, const agh_plane_fit_params* fp, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object)
+  {
     const std::size_t K = cp.max_objects >= 1 && cp.max_objects <= 64 ? (std::size_t) cp.max_objects : 0;
     std::vector<std::vector<Handle> > out = noHandles(K, antipodal_hands_per_object);
-    if (chainPending("localizeHandlesClustered"))
+    if (chainPending(fn))
       return out;
     if (size_left == 0 || !cloud_in || cloud_in->size() == 0)
     {
@@ -507,7 +526,7 @@ public:
     std::vector<std::vector<agh_handle> > handles;
     std::vector<std::vector<std::int32_t> > idx;
     if (!search_->localizeClustered(cloud_in, size_left, cp, workspace_, 0.003, svm_filename, min_inliers, min_length, hands, handles,
-          idx, filters_boundaries_))
+          idx, filters_boundaries_, fp))
       return out;
     return labeledHandles(cloud_in, hands, handles, idx, antipodal_hands_per_object);
   }
@@ -517,10 +536,26 @@ public:
     const std::string& svm_filename, int min_inliers, double min_length,
     std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object = nullptr)
   {
-    const agh_cluster_params cp = clusterParams(plane);
+    return depthClusteredHandles("localizeHandlesDepthClustered", images, clusterParams(plane), nullptr, svm_filename, min_inliers,
+      min_length, antipodal_hands_per_object);
+  }
+
+  /** ... and localizeHandlesClusteredFit straight from depth images (agh_localize_depth_clustered_fit) */
+  std::vector<std::vector<Handle> > localizeHandlesDepthClusteredFit(const std::vector<DepthImage>& images,
+    const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object = nullptr)
+  {
+    return depthClusteredHandles("localizeHandlesDepthClusteredFit", images, cluster_, &plane_fit_, svm_filename, min_inliers,
+      min_length, antipodal_hands_per_object);
+  }
+
+  std::vector<std::vector<Handle> > depthClusteredHandles(const char* fn, const std::vector<DepthImage>& images,
+    const agh_cluster_params& cp, const agh_plane_fit_params* fp, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<GraspHypothesis> >* antipodal_hands_per_object)
+  {
     const std::size_t K = cp.max_objects >= 1 && cp.max_objects <= 64 ? (std::size_t) cp.max_objects : 0;
     std::vector<std::vector<Handle> > out = noHandles(K, antipodal_hands_per_object);
-    if (chainPending("localizeHandlesDepthClustered"))
+    if (chainPending(fn))
       return out;
     if (images.empty())
     {
@@ -534,7 +569,7 @@ public:
     std::vector<std::vector<agh_handle> > handles;
     std::vector<std::vector<std::int32_t> > idx;
     if (!search_->localizeDepthClustered(images, cp, workspace_, 0.003, svm_filename, min_inliers, min_length, hands, handles, idx,
-          filters_boundaries_))
+          filters_boundaries_, fp))
       return out;
     return labeledHandles(PointCloud::Ptr(), hands, handles, idx, antipodal_hands_per_object);
   }
@@ -557,6 +592,32 @@ public:
     cluster_.tolerance = tolerance;
     cluster_.min_voxels = min_voxels;
     cluster_.max_objects = max_objects;
+  }
+
+  /** The plane finder of the fitted calls (agh_plane_fit_params; the defaults are agh_default_plane_fit_params': 128 candidates,
+   *  1 cm, 3 inliers, refit on, seed 1). */
+  void setPlaneFitParams(int n_candidates, double distance_threshold, int min_inliers = 3, bool refine = true, std::uint64_t seed = 1)
+  {
+    plane_fit_.n_candidates = n_candidates;
+    plane_fit_.distance_threshold = distance_threshold;
+    plane_fit_.min_inliers = min_inliers;
+    plane_fit_.refine = refine ? 1 : 0;
+    plane_fit_.seed = seed;
+  }
+
+  /** The plane the last fitted call used (agh_get_plane_fit): (a, b, c, d), the normal towards camera 0; zeros, and *found false,
+   *  if it found none, if the last chain collected was not a fitted one, or while a chain is pending. */
+  VectorXd fittedPlane(bool* found = nullptr)
+  {
+    agh_plane_fit_result r = agh_plane_fit_result();
+    if (search_)
+      search_->planeFit(r);
+    VectorXd plane(4);
+    for (int k = 0; k < 4; k++)
+      plane(k) = r.plane[k];
+    if (found)
+      *found = r.found != 0;
+    return plane;
   }
 
   /** The objects of the last clustered call (agh_get_cluster_info): their voxel counts, largest first, one entry per list; empty
@@ -1198,6 +1259,7 @@ private:
     for (int i = 0; i < 6; i++)
       workspace_(i) = ws[i];
     agh_default_cluster_params(&cluster_);
+    agh_default_plane_fit_params(&plane_fit_);
     finger_width_ = 0.01;  // find_grasps.cpp:13-17
     hand_outer_diameter_ = 0.09;
     hand_depth_ = 0.06;
@@ -1225,6 +1287,7 @@ private:
   int num_threads_, num_samples_;
   bool filters_boundaries_;
   agh_cluster_params cluster_;  // setClusterParams (the plane comes with each call)
+  agh_plane_fit_params plane_fit_;  // setPlaneFitParams
   int plotting_mode_;
   Matrix4d cam_tf_left_, cam_tf_right_;
   VectorXd workspace_;
