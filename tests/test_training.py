@@ -281,14 +281,11 @@ def test_train_svm_argument_errors(tiny_scene):
 def test_solver_sizes_around_the_tile_boundaries(tiny_scene, n):
     """Instance counts below, at and above the 64-instance tile and the 256-thread work-group, random images."""
     from agile_grasp_amd import binding
+    from tests.svm_train_cases import stroke_images
 
     ctx = binding.Context(tiny_scene.cam_origins)
     rng = np.random.default_rng(n)
-    images = np.zeros((n, 80, 100), np.uint8)
-    for im in images:  # a few random strokes: descriptors with many exact zeros, like real grasp images
-        for _ in range(int(rng.integers(1, 6))):
-            r, c = int(rng.integers(0, 80)), int(rng.integers(0, 100))
-            im[r:r + int(rng.integers(1, 30)), c:c + int(rng.integers(1, 4))] = 255
+    images = stroke_images(n, rng)  # a few random strokes: descriptors with many exact zeros, like real grasp images
     packed = binding.pack_images(images.reshape(n, 8000))
     labels = np.where(rng.random(n) < 0.4, 1, -1)
     labels[0], labels[1] = 1, -1
