@@ -112,6 +112,10 @@ EXPORTS = [
     "agh_localize_batch_clustered_begin_device", "agh_localize_depth_batch_clustered", "agh_localize_depth_batch_clustered_device",
     "agh_localize_depth_batch_clustered_begin", "agh_localize_depth_batch_clustered_begin_device", "agh_get_batch_cluster_info",
     "agh_get_batch_cluster_labels",
+    "agh_localize_batch_clustered_fit", "agh_localize_batch_clustered_fit_device", "agh_localize_batch_clustered_fit_begin",
+    "agh_localize_batch_clustered_fit_begin_device", "agh_localize_depth_batch_clustered_fit",
+    "agh_localize_depth_batch_clustered_fit_device", "agh_localize_depth_batch_clustered_fit_begin",
+    "agh_localize_depth_batch_clustered_fit_begin_device", "agh_get_batch_plane_fit", "agh_get_batch_plane_fit_candidates",
 ]
 
 
@@ -1280,6 +1284,85 @@ class Context:
         out = np.zeros(max(cap, 1), np.uint8)
         nv = self._check(self.lib.agh_get_batch_cluster_labels(self._h, C.c_void_p(out.ctypes.data), C.c_int64(cap)))
         return out[:nv].copy()
+
+    # ---- a fitted plane in the batch chains (include/agh.h, agh_localize_batch_clustered_fit*) ----
+
+    @staticmethod
+    def _batch_fit_records(a, fps):
+        """`fps`: a list of plane_fit_params() records, one per capture, or one record for all captures; None passes NULL, for
+        the library to refuse.  (Behind _batch_cluster_lists: a["Ck"] counts the lists by then.)"""
+        Ck = a["n_captures"]
+        if fps is None:
+            a["fps"] = None
+            return a
+        if isinstance(fps, AghPlaneFitParams):
+            fps = [fps] * Ck
+        assert len(fps) == Ck
+        recs = (AghPlaneFitParams * max(Ck, 1))()
+        for k, fp in enumerate(fps):
+            C.memmove(C.byref(recs[k]), C.byref(fp), C.sizeof(AghPlaneFitParams))
+        a["fps"] = recs
+        return a
+
+    def localize_batch_clustered_fit(self, captures, sizes_left, workspaces, fps, cps, caps=None, **kw):
+        """agh_localize_batch_clustered_fit (torch CUDA tensors: agh_localize_batch_clustered_fit_device):
+        localize_batch_clustered() with every capture's support plane found on the device inside the call, on its own voxels
+        with fps[k] (plane_fit_params(); a single record serves every capture); cps[k].plane is not read.  batch_plane_fit()
+        and batch_plane_fit_candidates(k) then describe the fits, batch_cluster_info() and batch_cluster_labels() the objects."""
+        a = self._batch_cluster_lists(self._batch_masked_args(captures, sizes_left, workspaces, None, kw), cps)
+        self._batch_fit_records(a, fps)
+        fn = self.lib.agh_localize_batch_clustered_fit_device if a["on_device"] else self.lib.agh_localize_batch_clustered_fit
+        return self._batch_labeled_collect(a, caps, lambda *out: fn(self._h, a["ptrs"], a["strides"], a["ns"], a["fps"], a["cps"],
+                                                                    a["lps"], C.c_int32(a["n_captures"]), *out))
+
+    def localize_batch_clustered_fit_begin(self, captures, sizes_left, workspaces, fps, cps, **kw):
+        """agh_localize_batch_clustered_fit_begin (torch CUDA tensors: _begin_device): the fitted batch's chain queued, nothing
+        waited for; collected by localize_batch_end().  The captures are kept alive until then."""
+        a = self._batch_cluster_lists(self._batch_masked_args(captures, sizes_left, workspaces, None, kw), cps)
+        self._batch_fit_records(a, fps)
+        fn = (self.lib.agh_localize_batch_clustered_fit_begin_device if a["on_device"]
+              else self.lib.agh_localize_batch_clustered_fit_begin)
+        self._check(fn(self._h, a["ptrs"], a["strides"], a["ns"], a["fps"], a["cps"], a["lps"], C.c_int32(a["n_captures"])))
+        self._batch_pending = a
+
+    def localize_depth_batch_clustered_fit(self, captures, workspaces, fps, cps, caps=None, **kw):
+        """agh_localize_depth_batch_clustered_fit (torch CUDA tensors as `data`: agh_localize_depth_batch_clustered_fit_device):
+        localize_batch_clustered_fit() straight from depth images (`captures` as for localize_depth_batch)."""
+        a = self._batch_cluster_lists(self._depth_batch_args(captures, workspaces, kw), cps)
+        self._batch_fit_records(a, fps)
+        fn = (self.lib.agh_localize_depth_batch_clustered_fit_device if a["on_device"]
+              else self.lib.agh_localize_depth_batch_clustered_fit)
+        return self._batch_labeled_collect(a, caps, lambda *out: fn(self._h, a["recs"], a["n_images"], a["fps"], a["cps"], a["lps"],
+                                                                    C.c_int32(a["n_captures"]), *out))
+
+    def localize_depth_batch_clustered_fit_begin(self, captures, workspaces, fps, cps, **kw):
+        """agh_localize_depth_batch_clustered_fit_begin (torch CUDA tensors: _begin_device): the fitted depth batch's chain
+        queued; collected by localize_batch_end().  The pixel buffers are kept alive until then."""
+        a = self._batch_cluster_lists(self._depth_batch_args(captures, workspaces, kw), cps)
+        self._batch_fit_records(a, fps)
+        fn = (self.lib.agh_localize_depth_batch_clustered_fit_begin_device if a["on_device"]
+              else self.lib.agh_localize_depth_batch_clustered_fit_begin)
+        self._check(fn(self._h, a["recs"], a["n_images"], a["fps"], a["cps"], a["lps"], C.c_int32(a["n_captures"])))
+        self._batch_pending = a
+
+    def batch_plane_fit(self, cap_captures: int = 64) -> list:
+        """agh_get_batch_plane_fit of the last fitted batch this context collected: a list, in capture order, of the dicts
+        plane_fit() returns."""
+        recs = (AghPlaneFitResult * max(cap_captures, 1))()
+        n = self._check(self.lib.agh_get_batch_plane_fit(self._h, recs, C.c_int32(cap_captures)))
+        return [{"plane": np.array(list(r.plane), np.float64), "n_voxels": r.n_voxels, "n_inliers": r.n_inliers,
+                 "n_refit": r.n_refit, "best_candidate": r.best_candidate, "found": r.found, "refined": r.refined}
+                for r in recs[:n]]
+
+    def batch_plane_fit_candidates(self, capture: int, cap: int = 256) -> dict:
+        """agh_get_batch_plane_fit_candidates: plane_fit_candidates() for one capture of the last fitted batch (the voxel indices
+        are capture-local)."""
+        idx = np.zeros((max(cap, 1), 3), np.int32)
+        planes = np.zeros((max(cap, 1), 4), np.float64)
+        counts = np.zeros(max(cap, 1), np.int64)
+        n = self._check(self.lib.agh_get_batch_plane_fit_candidates(self._h, C.c_int32(capture), _p(idx, C.c_int32),
+                                                                    _p(planes, C.c_double), _p(counts, C.c_int64), C.c_int32(cap)))
+        return {"idx": idx[:n].copy(), "planes": planes[:n].copy(), "counts": counts[:n].copy()}
 
     def localize_batch_stage(self, captures):
         """agh_localize_batch_stage: the NEXT batch's host captures up on a second stream, beside the chain in flight.  Returns

@@ -381,6 +381,11 @@ struct Ctx
   int64_t batch_cluster_info[kMaxClouds][4] = {};
   int64_t batch_cluster_sizes[kMaxClouds] = {};
   int32_t batch_cluster_ids[kMaxClouds] = {};
+  // agh_localize_batch_clustered_fit*: the captures of the last chain collected if it was a fitted clustered batch, else 0 (the
+  // single chains leave it: it counts only beside batch_cluster_captures), each capture's n_candidates and result record
+  int32_t batch_fit_captures = 0;
+  int32_t batch_fit_candidates[kMaxClouds] = {};
+  agh_plane_fit_result batch_fit_results[kMaxClouds] = {};
   // agh_localize_depth* (depth.hip): a host capture's depth images, rows packed, image k at depth_image_offset(k); the NEXT
   // capture's (agh_localize_depth_stage) in the second buffer; the two change places when a staged set is adopted
   uint8_t* d_depth = nullptr;
@@ -876,6 +881,20 @@ int sample_label_stage_batch(Ctx* c, const BatchLabelStage& m, hipStream_t st);
 // sample_cluster.hip's batch stage, which fills the object sets from the clouds with one ClusterDev record per capture
 int label_compact_stage_batch(Ctx* c, const BatchLabelStage& m, bool any, hipStream_t st);
 int sample_cluster_stage_batch(Ctx* c, const BatchLabelStage& m, const ClusterDev* cps, hipStream_t st);
+// plane_fit.hip's batch stage (include/agh.h, agh_localize_batch_clustered_fit), queued behind the upload of the ClusterDev table
+// and in front of sample_cluster_stage_batch: capture k's plane, found on its own voxels with fps[k], goes into cps[k].plane
+struct BatchFitStage
+{
+  VoxBatch vb;                      // the batch's capture table and descriptors
+  int C = 0;
+  int64_t n_max = 0;                // the largest capture's raw points
+  const int* cloud_off = nullptr;   // the batch's device-side cloud offsets
+  const PlaneFitDev* fps = nullptr; // device table: capture k's parameters and camera 0's origin in force for it
+  PlaneFitBuffers* fbs = nullptr;   // device: a block per capture
+  ClusterDev* cps = nullptr;        // device table of the cluster stage: the plane of record k is written
+  agh_plane_fit_result* h_results = nullptr;  // pinned: C records
+};
+int plane_fit_stage_batch(Ctx* c, const BatchFitStage& m, hipStream_t st);
 int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
   unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st);
 // host mirror of the handle search's results (pinned memory of the context; all nullptr / 0: none)

@@ -43,11 +43,14 @@ struct BatchCall
   // cp[k].max_objects lists each (first_list as the labelled batch's).  A repeat of the pass reads the records here.
   bool clustered = false;
   std::vector<agh_cluster_params> cp;
+  // agh_localize_batch_clustered_fit*: cp[k].plane is found by the chain (plane_fit.hip) with fp[k]; a repeat reads both copies
+  bool fitted = false;
+  std::vector<agh_plane_fit_params> fp;
   bool per_object() const { return labeled || clustered; }  // (a list per (capture, object))
   // the chain's name in the texts of the errors found behind a synchronisation
   const char* who() const
   {
-    return clustered ? "agh_localize_batch_clustered" : (labeled ? "agh_localize_batch_labeled" : "agh_localize_batch");
+    return fitted ? "agh_localize_batch_clustered_fit" : clustered ? "agh_localize_batch_clustered" : (labeled ? "agh_localize_batch_labeled" : "agh_localize_batch");
   }
 };
 
@@ -99,6 +102,12 @@ struct LocalizeBatchState
   // kernels take them; the lists' table is the labelled batch's (d_lcap), the stage's own buffers are the context's
   ClusterDev* d_ccap = nullptr;       // kMaxClouds
   ClusterDev* h_ccap = nullptr;       // pinned
+  // fitted planes (plane_fit.hip, plane_fit_stage_batch), made by the first fitted batch: a block of candidates, counts and sums
+  // per capture, the captures' parameters as the kernels take them, and the result records the chain writes
+  PlaneFitBuffers* d_fit = nullptr;        // kMaxClouds
+  PlaneFitDev* d_fcap = nullptr;           // kMaxClouds
+  PlaneFitDev* h_fcap = nullptr;           // pinned
+  agh_plane_fit_result* h_fit_result = nullptr;  // pinned: kMaxClouds
 };
 
 void localize_batch_release(Ctx* c)
@@ -107,11 +116,11 @@ void localize_batch_release(Ctx* c)
   if (!b)
     return;
   void* dev[] = { b->d_tab, b->d_local, b->d.hands, b->d.bits, b->d.rowcnt, b->d.first, b->d.n, b->d.idx, b->d.counts, b->d.tmp,
-    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2, b->d_mask, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist, b->d_lcap, b->d_ccap };
+    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2, b->d_mask, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist, b->d_lcap, b->d_ccap, b->d_fit, b->d_fcap };
   for (void* p : dev)
     if (p)
       (void) hipFree(p);
-  void* host[] = { b->h_tab, b->h_samples, b->h_counts, b->h_bad, b->h_desc, b->h_hands, b->h_handles, b->h_idx, b->h_vcap, b->h_mptr, b->h_mtotal, b->h_lcap, b->h_ccap };
+  void* host[] = { b->h_tab, b->h_samples, b->h_counts, b->h_bad, b->h_desc, b->h_hands, b->h_handles, b->h_idx, b->h_vcap, b->h_mptr, b->h_mtotal, b->h_lcap, b->h_ccap, b->h_fcap, b->h_fit_result };
   for (void* p : host)
     if (p)
       (void) hipHostFree(p);
@@ -365,6 +374,17 @@ int ensure_cluster_tables(Ctx* c, LocalizeBatchState* b)
   return AGH_OK;
 }
 
+// a fitted batch's tables: a block per capture, the captures' parameters, the results
+int ensure_fit_tables(Ctx* c, LocalizeBatchState* b)
+{
+  int rc;
+  if ((!b->d_fit || !b->d_fcap || !b->h_fcap || !b->h_fit_result) &&
+      ((rc = dev_alloc(c, &b->d_fit, (size_t) kMaxClouds)) || (rc = dev_alloc(c, &b->d_fcap, (size_t) kMaxClouds)) ||
+       (rc = pinned_alloc(c, &b->h_fcap, (size_t) kMaxClouds)) || (rc = pinned_alloc(c, &b->h_fit_result, (size_t) kMaxClouds))))
+    return rc;
+  return AGH_OK;
+}
+
 // The list table of the call, on the host and queued to the device: list l's span of the sample list, its capture's sample
 // count, seed and workspace (B.lp[list_cap[l]]), and which object of it the list is.
 int fill_list_table(Ctx* c, LocalizeBatchState* b, hipStream_t st)
@@ -466,6 +486,9 @@ struct BatchMaskSource
   // agh_localize_batch_clustered*: no bytes at all, n_captures records; capture k has cluster[k].max_objects lists
   const agh_cluster_params* cluster = nullptr;
   bool clustered = false;
+  // agh_localize_batch_clustered_fit*: ... and n_captures records of the fit, cluster[k].plane unread
+  const agh_plane_fit_params* fit = nullptr;
+  bool fitted = false;
   bool per_object() const { return labeled || clustered; }
   int32_t objects(int k) const { return clustered ? cluster[k].max_objects : n_objects[k]; }
 };
@@ -477,13 +500,24 @@ int batch_cluster_check(Ctx* c, const BatchMaskSource* mask, const agh_localize_
     c->err = std::string(mask->who) + ": " + what;
     return AGH_ERR_INVALID_ARGUMENT;
   };
+  if (mask->fitted && !mask->fit)
+    return bad("fp is NULL (every capture of a fitted batch has its agh_plane_fit_params record)");
   if (!mask->cluster)
     return bad("cp is NULL (every capture of a clustered batch has its agh_cluster_params record)");
   int64_t lists = 0, samples = 0;
   for (int k = 0; k < C; k++)
   {
     const std::string cap = "capture " + std::to_string(k);
-    const std::string fault = cluster_params_fault(mask->cluster[k]);
+    agh_cluster_params q = mask->cluster[k];
+    if (mask->fitted)  // (the plane is the chain's to find: the caller's is neither read nor validated)
+    {
+      const std::string fit_fault = plane_fit_params_fault(mask->fit[k]);
+      if (!fit_fault.empty())
+        return bad(cap + ": " + fit_fault);
+      q.plane[0] = q.plane[1] = q.plane[3] = 0.0;
+      q.plane[2] = 1.0;
+    }
+    const std::string fault = cluster_params_fault(q);
     if (!fault.empty())
       return bad(cap + ": " + fault);
     lists += mask->cluster[k].max_objects;
@@ -814,6 +848,32 @@ int batch_pass(agh_ctx* ctx)
       chain_fail(c, AGH_ERR_HIP));
     AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_ccap, b->h_ccap, sizeof(ClusterDev) * (size_t) C, hipMemcpyHostToDevice, st),
       chain_fail(c, AGH_ERR_HIP));
+    if (B.fitted)  // (behind the records' upload: k_fit_finish_batch writes capture k's plane into d_ccap[k])
+    {
+      if ((rc = ensure_fit_tables(c, b)) != AGH_OK)
+        return chain_fail(c, rc);
+      for (int k = 0; k < C; k++)
+      {
+        // (camera 0's origin in force for capture k: its row of the table, or the context's own; the setter refuses mid-chain)
+        const double* o = c->cam_tab_rows == C ? c->h_cam_tab + 6 * k : c->p.cam_origin[0];
+        const agh_plane_fit_params& f = B.fp[k];
+        b->h_fcap[k] = PlaneFitDev{ f.n_candidates, f.refine, f.min_inliers, 0, f.distance_threshold, (unsigned long long) f.seed,
+          { o[0], o[1], o[2] } };
+      }
+      AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_fcap, b->h_fcap, sizeof(PlaneFitDev) * (size_t) C, hipMemcpyHostToDevice, st),
+        chain_fail(c, AGH_ERR_HIP));
+      BatchFitStage f;
+      f.vb = vb;
+      f.C = C;
+      f.n_max = n_max;
+      f.cloud_off = c->d_cloud_off;
+      f.fps = b->d_fcap;
+      f.fbs = b->d_fit;
+      f.cps = b->d_ccap;
+      f.h_results = b->h_fit_result;
+      if ((rc = plane_fit_stage_batch(c, f, st)) != AGH_OK)
+        return chain_fail(c, rc);
+    }
     BatchLabelStage m;  // (no labels, codes or bitmaps: the object sets come from the clouds, behind the grid build queued above)
     m.vb = vb;
     m.C = C;
@@ -1007,6 +1067,16 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   B.clustered = clustered;
   if (clustered)
     B.cp.assign(mask->cluster, mask->cluster + C);
+  B.fitted = clustered && mask->fitted;
+  if (B.fitted)
+  {
+    B.fp.assign(mask->fit, mask->fit + C);
+    for (int k = 0; k < C; k++)  // (the caller's plane is not read: the uploaded record carries a placeholder until the fit's)
+    {
+      B.cp[k].plane[0] = B.cp[k].plane[1] = B.cp[k].plane[3] = 0.0;
+      B.cp[k].plane[2] = 1.0;
+    }
+  }
   B.soff.resize((size_t) B.L + 1);
   B.soff[0] = 0;
   for (int l = 0; l < B.L; l++)
@@ -1105,6 +1175,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   c->batch_mask_captures = 0;  // (agh_get_batch_mask_counts: set below, behind the synchronisation, if this batch is masked)
   c->batch_label_lists = 0;    // (agh_get_batch_label_counts likewise, if it is labelled)
   c->batch_cluster_captures = 0;  // (agh_get_batch_cluster_info / _labels likewise, if it is clustered)
+  c->batch_fit_captures = 0;      // (agh_get_batch_plane_fit / _candidates likewise, if it is fitted)
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)
@@ -1174,6 +1245,15 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
     c->batch_cluster_nv = voff[C];
     c->batch_cluster_lists = B.L;
     c->batch_cluster_captures = C;
+    if (B.fitted)  // (the records k_fit_finish_batch wrote into pinned memory: here with the chain's one synchronisation)
+    {
+      for (int k = 0; k < C; k++)
+      {
+        c->batch_fit_results[k] = b->h_fit_result[k];
+        c->batch_fit_candidates[k] = B.fp[k].n_candidates;
+      }
+      c->batch_fit_captures = C;
+    }
   }
   for (int l = 0; l < B.L; l++)  // (a list's voxel count is its capture's)
     nv[l] = voff[B.list_cap[l] + 1] - voff[B.list_cap[l]];
@@ -1751,6 +1831,162 @@ int agh_get_batch_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap)
   if (c->batch_cluster_nv > 0)
     AGH_HIPCHK(c, hipMemcpy(labels_out, c->d_cluster_label, (size_t) c->batch_cluster_nv, hipMemcpyDeviceToHost));
   return (int) c->batch_cluster_nv;
+}
+
+// ---- the fitted forms (include/agh.h, agh_localize_batch_clustered_fit*): the clustered batch chains with every capture's
+// support plane found on its own voxels by plane_fit.hip, in front of the one cluster stage ----
+
+static BatchMaskSource fit_source(const agh_plane_fit_params* fp, const agh_cluster_params* cp, const char* who)
+{
+  BatchMaskSource m = cluster_source(cp, who);
+  m.fit = fp;
+  m.fitted = true;
+  return m;
+}
+
+int agh_localize_batch_clustered_fit(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const BatchMaskSource m = fit_source(fp, cp, "agh_localize_batch_clustered_fit");
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, nullptr, &m);
+}
+
+int agh_localize_batch_clustered_fit_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const BatchMaskSource m = fit_source(fp, cp, "agh_localize_batch_clustered_fit_device");
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, nullptr, &m);
+}
+
+int agh_localize_batch_clustered_fit_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const BatchMaskSource m = fit_source(fp, cp, "agh_localize_batch_clustered_fit_begin");
+  return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, nullptr, &m);
+}
+
+int agh_localize_batch_clustered_fit_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes,
+  const int64_t* n, const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const BatchMaskSource m = fit_source(fp, cp, "agh_localize_batch_clustered_fit_begin_device");
+  return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, nullptr, &m);
+}
+
+int agh_localize_depth_batch_clustered_fit(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_clustered_fit" };
+  const BatchMaskSource m = fit_source(fp, cp, src.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src, &m);
+}
+
+int agh_localize_depth_batch_clustered_fit_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+{
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_clustered_fit_device" };
+  const BatchMaskSource m = fit_source(fp, cp, src.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
+    hands_cap, samples_out, results, &src, &m);
+}
+
+int agh_localize_depth_batch_clustered_fit_begin(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_clustered_fit_begin" };
+  const BatchMaskSource m = fit_source(fp, cp, src.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+}
+
+int agh_localize_depth_batch_clustered_fit_begin_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_clustered_fit_begin_device" };
+  const BatchMaskSource m = fit_source(fp, cp, src.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+}
+
+// the last chain collected, if it was a fitted clustered batch (`fn` refuses otherwise, and mid-chain)
+static int batch_fit_getter_check(Ctx* c, const char* fn)
+{
+  if (refuse_mid_chain(c, fn))
+    return AGH_ERR_STATE;
+  if (c->batch_cluster_captures < 1 || c->batch_fit_captures < 1)
+  {
+    c->err = std::string(fn) + ": the last chain this context collected was no fitted clustered batch (or there was none)";
+    return AGH_ERR_STATE;
+  }
+  return AGH_OK;
+}
+
+int agh_get_batch_plane_fit(agh_ctx* ctx, agh_plane_fit_result* out, int32_t cap_captures)
+{
+  if (!ctx || !out)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (int rc = batch_fit_getter_check(c, "agh_get_batch_plane_fit"))
+    return rc;
+  if (cap_captures < c->batch_fit_captures)
+  {
+    c->err = "agh_get_batch_plane_fit: cap_captures is below the batch's n_captures";
+    return AGH_ERR_CAPACITY;
+  }
+  std::copy(c->batch_fit_results, c->batch_fit_results + c->batch_fit_captures, out);
+  return c->batch_fit_captures;
+}
+
+int agh_get_batch_plane_fit_candidates(agh_ctx* ctx, int32_t capture, int32_t* idx, double* planes, int64_t* counts, int32_t cap)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (int rc = batch_fit_getter_check(c, "agh_get_batch_plane_fit_candidates"))
+    return rc;
+  if (capture < 0 || capture >= c->batch_fit_captures)
+  {
+    c->err = "agh_get_batch_plane_fit_candidates: capture must be 0 .. n_captures - 1 of the batch";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  const int C = c->batch_fit_candidates[capture];
+  if ((idx || planes || counts) && cap < C)
+  {
+    c->err = "agh_get_batch_plane_fit_candidates: cap is below the capture's n_candidates";
+    return AGH_ERR_CAPACITY;
+  }
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  // (the candidates stay on the device until somebody asks: a blocking copy each, behind whatever the context's stream holds)
+  const PlaneFitBuffers* fb = c->lbatch->d_fit + capture;
+  AGH_HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (idx)
+    AGH_HIPCHK(c, hipMemcpy(idx, fb->idx, sizeof(int32_t) * 3 * (size_t) C, hipMemcpyDeviceToHost));
+  if (planes)
+    AGH_HIPCHK(c, hipMemcpy(planes, fb->planes, sizeof(double) * 4 * (size_t) C, hipMemcpyDeviceToHost));
+  if (counts)
+  {
+    unsigned h[kPlaneFitMaxCandidates];
+    AGH_HIPCHK(c, hipMemcpy(h, fb->counts, sizeof(unsigned) * (size_t) C, hipMemcpyDeviceToHost));
+    for (int k = 0; k < C; k++)
+      counts[k] = (int64_t) h[k];
+  }
+  return C;
 }
 
 // The NEXT batch's captures up, beside whatever runs on the context's stream (stage_captures, localize.hip).  A pinned source must

@@ -15,6 +15,13 @@
 // launches are sized from the raw point count, the voxel count is read on the device (label_voxels); no launch count depends on
 // C or N, nothing returns to the host.
 //
+// A fitted batch (agh_localize_batch_clustered_fit*; DESIGN.md, "A fitted plane in the batch chains") runs the same four bodies
+// (fit_candidates, fit_score, fit_moments, fit_finish: __device__ functions, one copy of the arithmetic) with the capture on
+// blockIdx.y: k_fit_*_batch read capture k's parameters and origin from a device table of PlaneFitDev, its voxel count from its
+// own descriptor and its points at cloud_off[k] of the common voxel array, keep its candidates, counts and sums in block k of an
+// array of PlaneFitBuffers, and write the plane into record k of the cluster stage's table.  One launch per step whatever
+// n_captures and C_k are.
+//
 // Nothing depends on the order of an atomic operation: counts and sums are integers (no float atomic anywhere), the arg-max keys
 // are distinct.
 #include "agh_internal.h"
@@ -38,8 +45,9 @@ __device__ __forceinline__ double fit_height(double a, double b, double c, doubl
 
 // One work-group of 256.  counts and sums zeroed for the kernels behind this one; candidate tid < C drawn and its plane formed
 // (rules 1 and 2): an invalid candidate's plane is zeros, and with N < 3 its indices are -1.
-__global__ __launch_bounds__(256) void k_fit_candidates(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
-  int64_t n, PlaneFitDev fp, PlaneFitBuffers* __restrict__ fb)
+// xyz: the cloud's first voxel, N its voxels (a capture of a batch: its own, whatever lies beside them in the array).
+__device__ __forceinline__ void fit_candidates(const float* __restrict__ xyz, int64_t stride, int64_t N, const PlaneFitDev& fp,
+  PlaneFitBuffers* __restrict__ fb)
 {
   const int c = threadIdx.x;
   fb->counts[c] = 0u;
@@ -47,7 +55,6 @@ __global__ __launch_bounds__(256) void k_fit_candidates(const float* __restrict_
     fb->sums[c] = 0ull;
   if (c >= fp.C)
     return;
-  const int64_t N = label_voxels(d, n);
   double pl[4] = { 0.0, 0.0, 0.0, 0.0 };
   int32_t id[3] = { -1, -1, -1 };
   if (N >= 3)
@@ -86,6 +93,22 @@ __global__ __launch_bounds__(256) void k_fit_candidates(const float* __restrict_
     fb->idx[c][s] = id[s];
 }
 
+__global__ __launch_bounds__(256) void k_fit_candidates(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
+  int64_t n, PlaneFitDev fp, PlaneFitBuffers* __restrict__ fb)
+{
+  fit_candidates(xyz, stride, label_voxels(d, n), fp, fb);
+}
+
+// ... for capture blockIdx.y of a batch: its record of the device table (uniform per work-group: scalar loads, as the cluster
+// kernels' ClusterDev), its voxels at cloud_off[k] (none for a capture whose descriptor carries an error: label_voxels), block k
+__global__ __launch_bounds__(256) void k_fit_candidates_batch(VoxBatch vb, const float* __restrict__ xyz, int64_t stride,
+  const int* __restrict__ cloud_off, const PlaneFitDev* __restrict__ fps, PlaneFitBuffers* __restrict__ fbs)
+{
+  const int k = blockIdx.y;
+  const PlaneFitDev fp = fps[k];
+  fit_candidates(xyz + (int64_t) cloud_off[k] * stride, stride, label_voxels(vb.desc + k, vb.cap[k].n), fp, fbs + k);
+}
+
 // The voxels of this thread: v = v0 + k * 256 + tid, k < kFitPts (a wave reads a run of 64 records per k); a position at or
 // beyond N holds NaN, which is no plane's inlier.
 __device__ __forceinline__ void fit_load_voxels(const float* __restrict__ xyz, int64_t stride, int64_t v0, int64_t N, float (&x)[kFitPts],
@@ -107,13 +130,13 @@ __device__ __forceinline__ void fit_load_voxels(const float* __restrict__ xyz, i
 }
 
 // Rule 3.  (an invalid candidate, plane zeros, gets a NaN offset in LDS: no inlier)
-__global__ __launch_bounds__(256) void k_fit_score(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
-  int64_t n, PlaneFitDev fp, PlaneFitBuffers* __restrict__ fb)
+__device__ __forceinline__ void fit_score(const float* __restrict__ xyz, int64_t stride, int64_t N, const PlaneFitDev& fp,
+  PlaneFitBuffers* __restrict__ fb)
 {
   __shared__ double pl[kPlaneFitMaxCandidates][4];
   __shared__ unsigned cnt[kPlaneFitMaxCandidates];
-  const int64_t N = label_voxels(d, n), v0 = (int64_t) blockIdx.x * kFitTile;
-  if (v0 >= N)  // (uniform: the launch is sized from the raw points)
+  const int64_t v0 = (int64_t) blockIdx.x * kFitTile;
+  if (v0 >= N)  // (uniform: the launch is sized from the raw points -- in a batch from the largest capture's)
     return;
   const int tid = threadIdx.x;
   if (tid < fp.C)
@@ -152,6 +175,20 @@ __global__ __launch_bounds__(256) void k_fit_score(const float* __restrict__ xyz
     atomicAdd(&fb->counts[tid], cnt[tid]);
 }
 
+__global__ __launch_bounds__(256) void k_fit_score(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
+  int64_t n, PlaneFitDev fp, PlaneFitBuffers* __restrict__ fb)
+{
+  fit_score(xyz, stride, label_voxels(d, n), fp, fb);
+}
+
+__global__ __launch_bounds__(256) void k_fit_score_batch(VoxBatch vb, const float* __restrict__ xyz, int64_t stride,
+  const int* __restrict__ cloud_off, const PlaneFitDev* __restrict__ fps, PlaneFitBuffers* __restrict__ fbs)
+{
+  const int k = blockIdx.y;
+  const PlaneFitDev fp = fps[k];
+  fit_score(xyz + (int64_t) cloud_off[k] * stride, stride, label_voxels(vb.desc + k, vb.cap[k].n), fp, fbs + k);
+}
+
 // Rule 4, by the whole work-group of 256: the largest key (count << 32) | (0xFFFFFFFF - c) over c < C -- the keys are distinct,
 // ties go to the smaller c.  part: four words of LDS.
 __device__ __forceinline__ unsigned long long fit_best_key(const unsigned* counts, int C, unsigned long long* part)
@@ -177,12 +214,12 @@ __device__ __forceinline__ unsigned long long fit_best_key(const unsigned* count
 }
 
 // Rule 5's sums over the chosen candidate's inliers (the scoring has ended: the counts are final).
-__global__ __launch_bounds__(256) void k_fit_moments(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
-  int64_t n, PlaneFitDev fp, PlaneFitBuffers* __restrict__ fb)
+__device__ __forceinline__ void fit_moments(const float* __restrict__ xyz, int64_t stride, int64_t N, const PlaneFitDev& fp,
+  PlaneFitBuffers* __restrict__ fb)
 {
   __shared__ unsigned long long part[4];
   __shared__ unsigned long long acc[10];
-  const int64_t N = label_voxels(d, n), v0 = (int64_t) blockIdx.x * kFitTile;
+  const int64_t v0 = (int64_t) blockIdx.x * kFitTile;
   if (v0 >= N || !fp.refine)  // (uniform)
     return;
   const int tid = threadIdx.x;
@@ -238,20 +275,34 @@ __global__ __launch_bounds__(256) void k_fit_moments(const float* __restrict__ x
     atomicAdd(&fb->sums[tid], acc[tid]);
 }
 
-// One work-group of 256 for the arg-max; lane 0 does rules 4 to 6, writes the record the cluster kernels read (cp with the plane
-// in place; a NaN plane without one: every voxel background) and the pinned result.
-__global__ __launch_bounds__(256) void k_fit_finish(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
-  int64_t n, PlaneFitDev fp, ClusterDev cp, PlaneFitBuffers* __restrict__ fb, agh_plane_fit_result* __restrict__ h_result)
+__global__ __launch_bounds__(256) void k_fit_moments(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
+  int64_t n, PlaneFitDev fp, PlaneFitBuffers* __restrict__ fb)
+{
+  fit_moments(xyz, stride, label_voxels(d, n), fp, fb);
+}
+
+__global__ __launch_bounds__(256) void k_fit_moments_batch(VoxBatch vb, const float* __restrict__ xyz, int64_t stride,
+  const int* __restrict__ cloud_off, const PlaneFitDev* __restrict__ fps, PlaneFitBuffers* __restrict__ fbs)
+{
+  const int k = blockIdx.y;
+  const PlaneFitDev fp = fps[k];
+  fit_moments(xyz + (int64_t) cloud_off[k] * stride, stride, label_voxels(vb.desc + k, vb.cap[k].n), fp, fbs + k);
+}
+
+// One work-group of 256 for the arg-max; lane 0 does rules 4 to 6 and returns true with the plane the cluster kernels are to read
+// (NaN without one: every voxel background) and the result record.
+__device__ __forceinline__ bool fit_finish(const float* __restrict__ xyz, int64_t stride, int64_t N, const PlaneFitDev& fp,
+  const PlaneFitBuffers* fb, double (&pl)[4], agh_plane_fit_result& r)
 {
   __shared__ unsigned long long part[4];
   const unsigned long long key = fit_best_key(fb->counts, fp.C, part);
   if (threadIdx.x != 0)
-    return;
+    return false;
   const long long count = (long long) (key >> 32);
   const int best = (int) (0xFFFFFFFFu - (unsigned) (key & 0xFFFFFFFFull));
   const bool found = count >= (long long) max(fp.min_inliers, 3);
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  double pl[4] = { nan, nan, nan, nan };
+  pl[0] = pl[1] = pl[2] = pl[3] = nan;
   long long n_refit = 0;
   int refined = 0;
   if (found)
@@ -299,22 +350,50 @@ __global__ __launch_bounds__(256) void k_fit_finish(const float* __restrict__ xy
         pl[k] = -pl[k];
     }
   }
-  agh_plane_fit_result r;
 #pragma unroll
   for (int k = 0; k < 4; k++)
-  {
-    cp.plane[k] = pl[k];
     r.plane[k] = found ? pl[k] : 0.0;
-  }
-  r.n_voxels = label_voxels(d, n);
+  r.n_voxels = N;
   r.n_inliers = count;
   r.n_refit = n_refit;
   r.best_candidate = count > 0 ? best : -1;
   r.found = found ? 1 : 0;
   r.refined = refined;
   r.reserved = 0;
+  return true;
+}
+
+// ... lane 0 writes the record the cluster kernels read (cp with the plane in place) and the pinned result.
+__global__ __launch_bounds__(256) void k_fit_finish(const float* __restrict__ xyz, int64_t stride, const VoxDesc* __restrict__ d,
+  int64_t n, PlaneFitDev fp, ClusterDev cp, PlaneFitBuffers* __restrict__ fb, agh_plane_fit_result* __restrict__ h_result)
+{
+  double pl[4];
+  agh_plane_fit_result r;
+  if (!fit_finish(xyz, stride, label_voxels(d, n), fp, fb, pl, r))
+    return;
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    cp.plane[k] = pl[k];
   fb->record = cp;
   *h_result = r;
+}
+
+// ... a work-group per capture: lane 0 writes the plane into capture k's record of the cluster stage's table -- the plane only:
+// bounds, tol2 and min_voxels are the uploaded record's -- and the pinned result[k].
+__global__ __launch_bounds__(256) void k_fit_finish_batch(VoxBatch vb, const float* __restrict__ xyz, int64_t stride,
+  const int* __restrict__ cloud_off, const PlaneFitDev* __restrict__ fps, const PlaneFitBuffers* __restrict__ fbs,
+  ClusterDev* __restrict__ cps, agh_plane_fit_result* __restrict__ h_results)
+{
+  const int k = blockIdx.x;
+  const PlaneFitDev fp = fps[k];
+  double pl[4];
+  agh_plane_fit_result r;
+  if (!fit_finish(xyz + (int64_t) cloud_off[k] * stride, stride, label_voxels(vb.desc + k, vb.cap[k].n), fp, fbs + k, pl, r))
+    return;
+#pragma unroll
+  for (int q = 0; q < 4; q++)
+    cps[k].plane[q] = pl[q];
+  h_results[k] = r;
 }
 
 std::string plane_fit_params_fault(const agh_plane_fit_params& fp)
@@ -370,6 +449,31 @@ int plane_fit_stage(Ctx* c, int64_t n, const agh_plane_fit_params& fp, const Clu
     return AGH_ERR_HIP;
   }
   *d_cp_out = &fb->record;
+  return AGH_OK;
+}
+
+// The stage over a batch (BatchFitStage, agh_internal.h): four launches whatever C and the C_k are, sized from n_max; work-groups
+// whose tile starts at or beyond their capture's N_k leave at once.  The ClusterDev table must be uploaded in front (on st).
+int plane_fit_stage_batch(Ctx* c, const BatchFitStage& m, hipStream_t st)
+{
+  const unsigned Cy = (unsigned) m.C;
+  // (the voxelised batch is the context's bound batch: the preprocessing queued in front of this stage bound it)
+  const float* xyz = c->d_xyz;
+  const int64_t stride = c->stride_floats;
+  hipLaunchKernelGGL(k_fit_candidates_batch, dim3(1, Cy), dim3(256), 0, st, m.vb, xyz, stride, m.cloud_off, m.fps, m.fbs);
+  if (m.n_max > 0)
+  {
+    const unsigned blocks = (unsigned) ((m.n_max + kFitTile - 1) / kFitTile);
+    hipLaunchKernelGGL(k_fit_score_batch, dim3(blocks, Cy), dim3(256), 0, st, m.vb, xyz, stride, m.cloud_off, m.fps, m.fbs);
+    hipLaunchKernelGGL(k_fit_moments_batch, dim3(blocks, Cy), dim3(256), 0, st, m.vb, xyz, stride, m.cloud_off, m.fps, m.fbs);
+  }
+  hipLaunchKernelGGL(k_fit_finish_batch, dim3(Cy), dim3(256), 0, st, m.vb, xyz, stride, m.cloud_off, m.fps,
+    (const PlaneFitBuffers*) m.fbs, m.cps, m.h_results);
+  if (hipGetLastError() != hipSuccess)
+  {
+    c->err = "plane fit launch failed";
+    return AGH_ERR_HIP;
+  }
   return AGH_OK;
 }
 

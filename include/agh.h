@@ -287,11 +287,13 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_localize_batch_masked*, agh_localize_batch_masked_begin*, agh_localize_depth_batch_masked*,
  * agh_localize_depth_batch_masked_begin*, agh_localize_batch_labeled*, agh_localize_batch_labeled_begin*,
  * agh_localize_depth_batch_labeled*, agh_localize_depth_batch_labeled_begin*, agh_localize_batch_clustered*,
- * agh_localize_batch_clustered_begin*, agh_localize_depth_batch_clustered* and agh_localize_depth_batch_clustered_begin* among
- * them), agh_deproject, agh_deproject_batch,
+ * agh_localize_batch_clustered_begin*, agh_localize_depth_batch_clustered*, agh_localize_depth_batch_clustered_begin*,
+ * agh_localize_batch_clustered_fit*, agh_localize_batch_clustered_fit_begin*, agh_localize_depth_batch_clustered_fit* and
+ * agh_localize_depth_batch_clustered_fit_begin* among them), agh_deproject, agh_deproject_batch,
  * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info,
  * agh_get_cluster_labels, agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts,
- * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels and every getter of device results (frames, normals,
+ * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels, agh_get_batch_plane_fit,
+ * agh_get_batch_plane_fit_candidates and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -620,7 +622,9 @@ int agh_get_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap);  /* 
  *     after agh_localize_clustered; agh_get_label_counts and agh_get_sample_mask_count return AGH_ERR_STATE.
  * 12. A context's first fitted call allocates 256 candidates (indices, planes, counts), ten sums and one record on the device,
  *     and one result record in pinned memory: nothing per point.
- * Not built: batch forms; _begin / _end forms; _stage forms; sharded forms; more than 256 candidates; a termination rule. */
+ * Not built: batch forms of THIS call's own (the batch forms are agh_localize_batch_clustered_fit* below, _begin / _end forms
+ * among them: one fit stage for up to 64 captures); _begin / _end forms for a single capture; _stage forms; sharded forms; more
+ * than 256 candidates; a termination rule. */
 typedef struct agh_plane_fit_params
 {
   int32_t  n_candidates;        /* C: 1 .. 256 */
@@ -722,9 +726,11 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * agh_localize_clustered* and agh_localize_depth_clustered*; agh_localize_clustered_fit* and
  * agh_localize_depth_clustered_fit*; agh_localize_batch_clustered*,
  * agh_localize_batch_clustered_begin*, agh_localize_depth_batch_clustered* and agh_localize_depth_batch_clustered_begin*;
+ * agh_localize_batch_clustered_fit*, agh_localize_batch_clustered_fit_begin*, agh_localize_depth_batch_clustered_fit* and
+ * agh_localize_depth_batch_clustered_fit_begin*;
  * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info, agh_get_cluster_labels,
- * agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info and agh_get_batch_cluster_labels are
- * refused as well),
+ * agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info,
+ * agh_get_batch_cluster_labels, agh_get_batch_plane_fit and agh_get_batch_plane_fit_candidates are refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
@@ -989,8 +995,9 @@ int agh_get_batch_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_li
  *     device and pinned; a pinned table of 4 words per capture plus 2 per list (counters, records and table are allocated once
  *     for 64 captures and lists, 10 KiB in all, and shared with the single clustered chain).  Nothing scales with L x a
  *     lattice, or with n_captures x 64.
- *  8. Not built: a _stage call; more than 64 lists per call; a fitted plane; clustered captures mixed with labelled, masked or
- *     unmasked ones in one batch; sharded forms. */
+ *  8. Not built: a _stage call; more than 64 lists per call; clustered captures mixed with labelled, masked or unmasked ones in
+ *     one batch; sharded forms.  (These calls take every cp[k].plane from the caller: a fitted plane per capture is
+ *     agh_localize_batch_clustered_fit* below.) */
 int agh_localize_batch_clustered(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
   int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
@@ -1018,6 +1025,72 @@ int agh_localize_depth_batch_clustered_begin_device(agh_ctx* ctx, const agh_dept
 int agh_get_batch_cluster_info(agh_ctx* ctx, agh_cluster_info* info /* n_captures */, int64_t* n_voxels /* L: M_l */,
   int32_t* ids /* L: capture-local */, int32_t cap_captures, int32_t cap_lists);
 int agh_get_batch_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap);  /* per voxel of the bound batch: 0 or j + 1 */
+
+/* The clustered batch chains WITH EVERY CAPTURE'S SUPPORT PLANE FITTED ON THE DEVICE: a cell with several rigs and no calibration
+ * on any of them.  agh_localize_clustered_fit takes one capture per call and pays the single chain each time;
+ * agh_localize_batch_clustered* wants every cp[k].plane from the caller.  Here ONE fit stage (four launches, the capture on
+ * blockIdx.y, whatever n_captures and the candidate counts are) runs behind the batch's preprocessing and in front of its one
+ * cluster stage, writes capture k's plane into record k of the device table the cluster kernels read, and from there on the call
+ * IS agh_localize_batch_clustered: nothing returns to the host, the chain keeps its one synchronisation.  The signatures are the
+ * clustered batch's with one more argument, fp, in front of cp: an array of n_captures records, fp[k] capture k's own -- rigs
+ * have their own noise, thresholds and seeds, as they have their own cp[k].
+ *  1. Rules per capture.  Rules 1 to 6 of agh_localize_clustered_fit hold per capture, on capture k's own voxelised cloud: N_k its
+ *     voxel count, voxel indices capture-local, fp[k] its parameters.  Rule 6 uses camera 0's origin in force for capture k: row
+ *     k of an n_captures-row agh_set_cloud_cam_origins table, else agh_params::cam_origin[0].  No voxel of another capture is
+ *     ever drawn, scored or summed for capture k, whatever the coordinates.
+ *  2. Equality per capture.  result[k] (agh_get_batch_plane_fit) and capture k's candidates (agh_get_batch_plane_fit_candidates)
+ *     equal, bit for bit, what agh_localize_clustered_fit reports on capture k alone with fp[k], cp[k], lp[k] and that origin
+ *     (the depth forms' twin is agh_localize_depth_clustered_fit); capture k's lists, results[l], cluster info and label bytes
+ *     equal that twin's (epoch aside, AGH_NORMALS_DETERMINISTIC as for the clustered batch).
+ *  3. Equality of the whole call.  The whole call equals agh_localize_batch_clustered with cp[k].plane set to the reported plane
+ *     for every found capture.  A capture without a plane has K_k empty lists, no foreground and a reported plane of zeros (its
+ *     device record carries a NaN plane), and the other captures are unaffected; the return value is AGH_OK.
+ *  4. Repeatability.  The same call twice gives the same bits, on one context and on a fresh one: counts and sums are integers,
+ *     nothing depends on the order of an atomic operation.
+ *  5. Refusals.  AGH_ERR_INVALID_ARGUMENT, nothing launched, the text naming the capture and the field: fp == NULL; any violation
+ *     of agh_localize_clustered_fit's rule 10 by fp[k] (reported as "capture k: ..."); and every refusal of the clustered batch
+ *     (its rule 4).  cp[k].plane is ignored and not validated.
+ *  6. Repeats inside the call.  The chain holds a copy of the fp records beside the cp records: an outgrown-slot repeat re-enters
+ *     with both, and fits again on the lattice that holds the captures.
+ *  7. State.  After a fitted batch agh_get_batch_cluster_info and agh_get_batch_cluster_labels work as after a clustered batch;
+ *     agh_get_plane_fit and agh_get_plane_fit_candidates (the single call's) return AGH_ERR_STATE, as every getter does that
+ *     returns it after a clustered batch.  agh_get_batch_plane_fit writes result[k] in capture order and returns n_captures
+ *     (AGH_ERR_CAPACITY if cap_captures is below it): the records arrive in pinned memory with the chain's one synchronisation.
+ *     agh_get_batch_plane_fit_candidates is agh_get_plane_fit_candidates for one capture of the batch: capture-local indices,
+ *     planes BEFORE refit and orientation, counts; any array may be NULL; it returns C_k = fp[capture].n_candidates
+ *     (AGH_ERR_CAPACITY if cap is below it, AGH_ERR_INVALID_ARGUMENT for a capture outside the batch).  Both return AGH_ERR_STATE
+ *     after any other chain, with none collected, or while one is in flight.
+ *  8. Memory.  A context's first fitted batch adds 64 blocks of 256 candidates, counts and sums (about 0.8 MB on the device), 64
+ *     parameter records on the device and pinned, and 64 pinned result records.  Nothing is allocated per point.
+ *  9. Not built: a _stage call; fitted captures mixed with captures whose plane is given, in one batch; more than 256 candidates;
+ *     sharded forms. */
+int agh_localize_batch_clustered_fit(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+int agh_localize_batch_clustered_fit_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+int agh_localize_batch_clustered_fit_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_batch_clustered_fit_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes,
+  const int64_t* n, const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_depth_batch_clustered_fit(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+int agh_localize_depth_batch_clustered_fit_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures,
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
+  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results);
+int agh_localize_depth_batch_clustered_fit_begin(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures);
+int agh_localize_depth_batch_clustered_fit_begin_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures);
+int agh_get_batch_plane_fit(agh_ctx* ctx, agh_plane_fit_result* out /* n_captures */, int32_t cap_captures);
+int agh_get_batch_plane_fit_candidates(agh_ctx* ctx, int32_t capture, int32_t* idx /* 3 per candidate, capture-local */,
+  double* planes /* 4 per candidate */, int64_t* counts, int32_t cap);
 
 /* The context's current cloud: packed xyz (3 floats per point) and camera ids; returns the number of points. */
 int agh_get_cloud(agh_ctx* ctx, float* xyz_out, int32_t* cam_out, int64_t cap);

@@ -996,8 +996,28 @@ public:
     const std::vector<agh_cluster_params>& cp, const std::vector<VectorXd>& workspaces, double cell_size,
     const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
   {
+    return batchClusteredBegin(clouds, sizes_left, nullptr, cp, workspaces, cell_size, svm_filename, min_inliers, min_length,
+      filters_boundaries);
+  }
+
+  /** Additional: localizeBatchClusteredBegin WITHOUT A CALIBRATED PLANE (agh_localize_batch_clustered_fit_begin): capture k's
+   *  support plane is found on the device inside the chain, on its own voxels, with fp[k] (one record per capture: rigs have
+   *  their own thresholds and seeds); cp[k].plane is not read, and batchPlaneFit() then reports the planes. */
+  bool localizeBatchClusteredFitBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<agh_plane_fit_params>& fp, const std::vector<agh_cluster_params>& cp, const std::vector<VectorXd>& workspaces,
+    double cell_size, const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    return batchClusteredBegin(clouds, sizes_left, &fp, cp, workspaces, cell_size, svm_filename, min_inliers, min_length,
+      filters_boundaries);
+  }
+
+  // the two calls above (fp: the fitted one's records, or nullptr)
+  bool batchClusteredBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::vector<agh_plane_fit_params>* fp, const std::vector<agh_cluster_params>& cp, const std::vector<VectorXd>& workspaces,
+    double cell_size, const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries)
+  {
     const std::size_t C = clouds.size();
-    if (C == 0 || sizes_left.size() != C || workspaces.size() != C || cp.size() != C)
+    if (C == 0 || sizes_left.size() != C || workspaces.size() != C || cp.size() != C || (fp && fp->size() != C))
     {
       std::cout << " Error: localizeBatchClusteredBegin needs one size_left, workspace and cluster record per cloud\n";
       return false;
@@ -1012,10 +1032,13 @@ public:
     for (std::size_t k = 0; k < C; k++)
       lp[k] = chainParams(sizes_left[k], cloud_is_dense(*clouds[k]), workspaces[k], cell_size, std::vector<std::int32_t>(),
         seed + (std::uint64_t) k, min_inliers, min_length, filters_boundaries);
-    if (agh_localize_batch_clustered_begin(ctx_, in.xyz.data(), in.stride.data(), in.n.data(), cp.data(), lp.data(),
-          (std::int32_t) C) != AGH_OK)
+    const int rc = fp ? agh_localize_batch_clustered_fit_begin(ctx_, in.xyz.data(), in.stride.data(), in.n.data(), fp->data(),
+                          cp.data(), lp.data(), (std::int32_t) C)
+                      : agh_localize_batch_clustered_begin(ctx_, in.xyz.data(), in.stride.data(), in.n.data(), cp.data(), lp.data(),
+                          (std::int32_t) C);
+    if (rc != AGH_OK)
     {
-      fail("agh_localize_batch_clustered_begin");
+      fail(fp ? "agh_localize_batch_clustered_fit_begin" : "agh_localize_batch_clustered_begin");
       return false;
     }
     labeledBatchQueued(clusterObjects(cp), lp);
@@ -1027,8 +1050,25 @@ public:
     const std::vector<agh_cluster_params>& cp, const std::vector<VectorXd>& workspaces, double cell_size,
     const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
   {
+    return depthBatchClusteredBegin(captures, nullptr, cp, workspaces, cell_size, svm_filename, min_inliers, min_length,
+      filters_boundaries);
+  }
+
+  /** ... and localizeBatchClusteredFitBegin straight from depth images (agh_localize_depth_batch_clustered_fit_begin) */
+  bool localizeDepthBatchClusteredFitBegin(const std::vector<std::vector<DepthImage> >& captures,
+    const std::vector<agh_plane_fit_params>& fp, const std::vector<agh_cluster_params>& cp, const std::vector<VectorXd>& workspaces,
+    double cell_size, const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries = false)
+  {
+    return depthBatchClusteredBegin(captures, &fp, cp, workspaces, cell_size, svm_filename, min_inliers, min_length,
+      filters_boundaries);
+  }
+
+  bool depthBatchClusteredBegin(const std::vector<std::vector<DepthImage> >& captures, const std::vector<agh_plane_fit_params>* fp,
+    const std::vector<agh_cluster_params>& cp, const std::vector<VectorXd>& workspaces, double cell_size,
+    const std::string& svm_filename, int min_inliers, double min_length, bool filters_boundaries)
+  {
     const std::size_t C = captures.size();
-    if (C == 0 || workspaces.size() != C || cp.size() != C)
+    if (C == 0 || workspaces.size() != C || cp.size() != C || (fp && fp->size() != C))
     {
       std::cout << " Error: localizeDepthBatchClusteredBegin needs one workspace and cluster record per capture\n";
       return false;
@@ -1047,10 +1087,13 @@ public:
       lp[k] = chainParams(0, true, workspaces[k], cell_size, std::vector<std::int32_t>(), seed + (std::uint64_t) k, min_inliers,
         min_length, filters_boundaries);
     }
-    if (agh_localize_depth_batch_clustered_begin(ctx_, recs.empty() ? nullptr : recs.data(), n_images.data(), cp.data(), lp.data(),
-          (std::int32_t) C) != AGH_OK)
+    const agh_depth_image* images = recs.empty() ? nullptr : recs.data();
+    const int rc = fp ? agh_localize_depth_batch_clustered_fit_begin(ctx_, images, n_images.data(), fp->data(), cp.data(), lp.data(),
+                          (std::int32_t) C)
+                      : agh_localize_depth_batch_clustered_begin(ctx_, images, n_images.data(), cp.data(), lp.data(), (std::int32_t) C);
+    if (rc != AGH_OK)
     {
-      fail("agh_localize_depth_batch_clustered_begin");
+      fail(fp ? "agh_localize_depth_batch_clustered_fit_begin" : "agh_localize_depth_batch_clustered_begin");
       return false;
     }
     labeledBatchQueued(clusterObjects(cp), lp);
@@ -1088,6 +1131,16 @@ public:
     n_voxels.resize(lists);
     ids.resize(lists);
     return true;
+  }
+
+  /** agh_get_batch_plane_fit: one record per capture of the last fitted batch localizeBatchEnd collected.
+   *  @return false (and no record) if the last chain collected was no fitted batch */
+  bool batchPlaneFit(std::vector<agh_plane_fit_result>& results)
+  {
+    results.assign(64, agh_plane_fit_result());
+    const int n = ctx_ ? agh_get_batch_plane_fit(ctx_, results.data(), 64) : -1;
+    results.resize(n > 0 ? (std::size_t) n : 0);
+    return n > 0;
   }
 
   /** the objects per capture of the labelled batch in flight or last collected (empty: that batch was not labelled) */

@@ -1074,6 +1074,124 @@ public:
     return true;
   }
 
+  /** Additional: localizeHandlesBatchClustered WITHOUT A CALIBRATED PLANE on any rig (agh_localize_batch_clustered_fit): every
+   *  capture's dominant plane is found on the device inside the one chain, on the capture's own voxels (setPlaneFitParams, the
+   *  same record for every capture; the sample seed + k is NOT added to its seed), oriented towards camera 0 of the capture's
+   *  rig, and used as its support plane; fittedPlanes() reports them.  The other cluster parameters are setClusterParams' for
+   *  every capture, or cluster_params[k] (its plane is not read).  out[k][j] are the handles of localizeHandlesClusteredFit on
+   *  capture k alone (seeded with the sample seed + k). */
+  std::vector<std::vector<std::vector<Handle> > > localizeHandlesBatchClusteredFit(const std::vector<PointCloud::Ptr>& clouds,
+    const std::vector<int>& sizes_left, const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<std::vector<GraspHypothesis> > >* antipodal_hands_per_object = nullptr,
+    const std::vector<VectorXd>* workspaces = nullptr, const std::vector<agh_cluster_params>* cluster_params = nullptr)
+  {
+    if (chainPending("localizeHandlesBatchClusteredFit") ||
+        !localizeHandlesBatchClusteredFitBegin(clouds, sizes_left, svm_filename, min_inliers, min_length, workspaces, cluster_params))
+      return noLabeledHandles(HandSearch::clusterObjects(batchFitClusterParams(clouds.size(), cluster_params)), antipodal_hands_per_object);
+    return localizeHandlesBatchLabeledEnd(antipodal_hands_per_object);
+  }
+
+  /** ... as two calls: the chain queued here is collected by localizeHandlesBatchLabeledEnd, as a clustered Begin's. */
+  bool localizeHandlesBatchClusteredFitBegin(const std::vector<PointCloud::Ptr>& clouds, const std::vector<int>& sizes_left,
+    const std::string& svm_filename, int min_inliers, double min_length, const std::vector<VectorXd>* workspaces = nullptr,
+    const std::vector<agh_cluster_params>* cluster_params = nullptr)
+  {
+    if (chainPending("localizeHandlesBatchClusteredFitBegin", "its End"))
+      return false;
+    for (std::size_t k = 0; k < clouds.size(); k++)
+      if (!clouds[k] || clouds[k]->size() == 0 || k >= sizes_left.size() || sizes_left[k] == 0)
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    if (!batchFitRecordsGiven("localizeHandlesBatchClusteredFitBegin", clouds.size(), cluster_params) || !detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(clouds.size(), workspace_);
+    const std::vector<agh_cluster_params> cp = batchFitClusterParams(clouds.size(), cluster_params);
+    const std::vector<agh_plane_fit_params> fp(clouds.size(), plane_fit_);
+    if (!search_->localizeBatchClusteredFitBegin(clouds, sizes_left, fp, cp, ws, 0.003, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
+      return false;
+    pendingLists(clouds, HandSearch::clusterObjects(cp));
+    return true;
+  }
+
+  /** ... and straight from depth images (agh_localize_depth_batch_clustered_fit): out[k][j] are the handles of
+   *  localizeHandlesDepthClusteredFit on capture k alone. */
+  std::vector<std::vector<std::vector<Handle> > > localizeHandlesDepthBatchClusteredFit(const std::vector<std::vector<DepthImage> >& captures,
+    const std::string& svm_filename, int min_inliers, double min_length,
+    std::vector<std::vector<std::vector<GraspHypothesis> > >* antipodal_hands_per_object = nullptr,
+    const std::vector<VectorXd>* workspaces = nullptr, const std::vector<agh_cluster_params>* cluster_params = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatchClusteredFit") ||
+        !localizeHandlesDepthBatchClusteredFitBegin(captures, svm_filename, min_inliers, min_length, workspaces, cluster_params))
+      return noLabeledHandles(HandSearch::clusterObjects(batchFitClusterParams(captures.size(), cluster_params)), antipodal_hands_per_object);
+    return localizeHandlesBatchLabeledEnd(antipodal_hands_per_object);
+  }
+
+  bool localizeHandlesDepthBatchClusteredFitBegin(const std::vector<std::vector<DepthImage> >& captures, const std::string& svm_filename,
+    int min_inliers, double min_length, const std::vector<VectorXd>* workspaces = nullptr,
+    const std::vector<agh_cluster_params>* cluster_params = nullptr)
+  {
+    if (chainPending("localizeHandlesDepthBatchClusteredFitBegin", "its End"))
+      return false;
+    for (std::size_t k = 0; k < captures.size(); k++)
+      if (captures[k].empty())
+      {
+        std::cout << "Input cloud is empty!\n";
+        return false;
+      }
+    if (!batchFitRecordsGiven("localizeHandlesDepthBatchClusteredFitBegin", captures.size(), cluster_params) ||
+        !detail::svmFileExists(svm_filename))
+      return false;
+    ensureSearch();
+    const std::vector<VectorXd> ws = workspaces ? *workspaces : std::vector<VectorXd>(captures.size(), workspace_);
+    const std::vector<agh_cluster_params> cp = batchFitClusterParams(captures.size(), cluster_params);
+    const std::vector<agh_plane_fit_params> fp(captures.size(), plane_fit_);
+    if (!search_->localizeDepthBatchClusteredFitBegin(captures, fp, cp, ws, 0.003, svm_filename, min_inliers, min_length,
+          filters_boundaries_))
+      return false;
+    pendingLists(std::vector<PointCloud::Ptr>(captures.size()), HandSearch::clusterObjects(cp));  // (no capture with a host cloud)
+    return true;
+  }
+
+  // the cluster records of a fitted batch: cluster_params[k], or what setClusterParams holds, for every capture (no plane is read)
+  std::vector<agh_cluster_params> batchFitClusterParams(std::size_t n_captures, const std::vector<agh_cluster_params>* cluster_params) const
+  {
+    if (cluster_params)
+      return cluster_params->size() == n_captures ? *cluster_params : std::vector<agh_cluster_params>();
+    return std::vector<agh_cluster_params>(n_captures, cluster_);
+  }
+  bool batchFitRecordsGiven(const char* fn, std::size_t n_captures, const std::vector<agh_cluster_params>* cluster_params) const
+  {
+    if (!cluster_params || cluster_params->size() == n_captures)
+      return true;
+    std::cout << " Error: " << fn << " needs, where cluster records are given, one per capture\n";
+    return false;
+  }
+
+  /** The planes of the last fitted batch collected (agh_get_batch_plane_fit): one (a, b, c, d) per capture, zeros for a capture
+   *  without a plane, (*found)[k] saying which; empty if the last chain collected was no fitted batch, if there was none, or
+   *  while a chain is pending. */
+  std::vector<VectorXd> fittedPlanes(std::vector<bool>* found = nullptr)
+  {
+    std::vector<agh_plane_fit_result> r;
+    if (search_)
+      search_->batchPlaneFit(r);
+    std::vector<VectorXd> planes(r.size(), VectorXd(4));
+    if (found)
+      found->assign(r.size(), false);
+    for (std::size_t k = 0; k < r.size(); k++)
+    {
+      for (int q = 0; q < 4; q++)
+        planes[k](q) = r[k].plane[q];
+      if (found)
+        (*found)[k] = r[k].found != 0;
+    }
+    return planes;
+  }
+
   // the records of a clustered batch: cluster_params[k] (or what setClusterParams holds) with planes[k]; a capture without a
   // plane or a record gets none, and the Begin refuses the batch
   std::vector<agh_cluster_params> batchClusterParams(const std::vector<VectorXd>& planes,
