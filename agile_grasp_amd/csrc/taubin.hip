@@ -971,6 +971,16 @@ __device__ __forceinline__ void sample_to_source(double (&s2s)[3], const double 
   s2s[2] = sample[2] - (maj ? cam1z : cam0z);
 }
 
+// A column sum of quadric.cpp:283-284 as the argmax compares it.  A neighbour at which the quadric's gradient is exactly zero (a
+// point on the zero line of a planar fit's second linear factor) has the normal 0 / 0, and then EVERY column's sum holds a NaN
+// term.  The oracle's sequential `s > best` never leaves column 0 in that case.  The argmax here runs over columns in no fixed
+// order, where a NaN compares false both ways and the column a lane happened to take first would stay: a NaN sum counts as -1,
+// below every real sum (sums of sixth powers), so that the first-index rule among equals yields column 0.
+__device__ __forceinline__ double column_sum_key(double s)
+{
+  return s == s ? s : -1.0;
+}
+
 // THREADS = 256 (one work-group of four waves per sample) or 64 (one wave per sample: the class for at most 128 normals
 // of the r = 0.01 all-points pass).
 template <int CAP, int THREADS>
@@ -1239,7 +1249,7 @@ __global__ __launch_bounds__(THREADS, (CAP == 1152 && THREADS == 256) ? 5 : ((CA
       }
       if (lane < ks)
       {
-        small_best = s0;
+        small_best = column_sum_key(s0);
         small_best_j = lane;
       }
     }
@@ -1459,6 +1469,7 @@ __global__ __launch_bounds__(THREADS, (CAP == 1152 && THREADS == 256) ? 5 : ((CA
       x = x + xor_partner_f64<4>(x);
       x = x + xor_partner_f64<2>(x);
       x = x + xor_partner_f64<1>(x);  // lane l: the total of column c + (l >> 3)
+      x = column_sum_key(x);
       const int u = lane >> 3;
       const int jcol = cand[min(c + u, ncnd - 1)];
       if (c + u < ncnd && (x > best || (x == best && jcol < best_j) || best_j == 0x7fffffff))
@@ -1496,7 +1507,7 @@ __global__ __launch_bounds__(THREADS, (CAP == 1152 && THREADS == 256) ? 5 : ((CA
       const double g2 = gdot * gdot;
       acc += (g2 * g2) * g2;
     }
-    acc = wave_allsum_f64(acc);
+    acc = column_sum_key(wave_allsum_f64(acc));
     if (acc > best || (acc == best && j < best_j) || best_j == 0x7fffffff)
     {
       best = acc;
@@ -1739,7 +1750,7 @@ __global__ __launch_bounds__(256) void k_taubin_frame_huge(const float4* __restr
 #pragma unroll
     for (int u = 0; u < 4; u++)
     {
-      const double sum = wave_allsum_f64(acc[u]);
+      const double sum = column_sum_key(wave_allsum_f64(acc[u]));
       if (c0 + u < n && (sum > best || (sum == best && jj[u] < best_j) || best_j == 0x7fffffff))
       {
         best = sum;
