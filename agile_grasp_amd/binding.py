@@ -116,6 +116,7 @@ EXPORTS = [
     "agh_localize_batch_clustered_fit_begin_device", "agh_localize_depth_batch_clustered_fit",
     "agh_localize_depth_batch_clustered_fit_device", "agh_localize_depth_batch_clustered_fit_begin",
     "agh_localize_depth_batch_clustered_fit_begin_device", "agh_get_batch_plane_fit", "agh_get_batch_plane_fit_candidates",
+    "agh_default_depth_filter_params", "agh_set_depth_filter", "agh_get_depth_filter", "agh_get_depth_filter_counts",
 ]
 
 
@@ -244,6 +245,26 @@ class AghDepthImage(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("row_stride_bytes", C.c_int64),
                 ("format", C.c_int32), ("depth_scale", C.c_float), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
                 ("cy", C.c_double), ("pose", C.c_double * 12)]
+
+
+class AghDepthFilterParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("min_support", C.c_int32), ("max_jump_abs", C.c_double), ("max_jump_rel", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double)]
+
+
+class AghDepthFilterCounts(C.Structure):
+    _fields_ = [("n_valid", C.c_int64), ("n_out_of_range", C.c_int64), ("n_unsupported", C.c_int64), ("n_kept", C.c_int64)]
+
+
+def depth_filter_params(**fields) -> AghDepthFilterParams:
+    """agh_default_depth_filter_params, then the given fields."""
+    fp = AghDepthFilterParams()
+    load_library().agh_default_depth_filter_params(C.byref(fp))
+    for k, v in fields.items():
+        if not hasattr(fp, k):
+            raise TypeError(f"agh_depth_filter_params has no field {k}")
+        setattr(fp, k, v)
+    return fp
 
 
 def depth_image_records(images):
@@ -430,6 +451,7 @@ def load_library():
         lib.agh_default_plane_params.restype = None
         lib.agh_default_cluster_params.restype = None
         lib.agh_default_plane_fit_params.restype = None
+        lib.agh_default_depth_filter_params.restype = None
         _LIB = lib
     return _LIB
 
@@ -518,6 +540,34 @@ class Context:
         tab = np.zeros((64, 2, 3), np.float64)
         k = self._check(self.lib.agh_get_cloud_cam_origins(self._h, _p(tab, C.c_double), C.c_int32(64)))
         return tab[:k].copy() if k > 0 else None
+
+    def set_depth_filter(self, fp=None, **fields):
+        """agh_set_depth_filter: every later deprojection of this context (deproject*, localize_depth*) rejects flying pixels,
+        speckles and out-of-range readings.  `fp`: a depth_filter_params() record, or None for the defaults; the keyword fields
+        (radius, min_support, max_jump_abs, max_jump_rel, z_min, z_max) are set on top.  Sticky until clear_depth_filter()."""
+        rec = depth_filter_params()
+        if fp is not None:
+            C.memmove(C.byref(rec), C.byref(fp), C.sizeof(AghDepthFilterParams))
+        for k, v in fields.items():
+            if not hasattr(rec, k):
+                raise TypeError(f"agh_depth_filter_params has no field {k}")
+            setattr(rec, k, v)
+        self._check(self.lib.agh_set_depth_filter(self._h, C.byref(rec)))
+
+    def clear_depth_filter(self):
+        self._check(self.lib.agh_set_depth_filter(self._h, None))
+
+    def depth_filter(self):
+        """The agh_depth_filter_params record held, or None."""
+        rec = AghDepthFilterParams()
+        return rec if self._check(self.lib.agh_get_depth_filter(self._h, C.byref(rec))) == 1 else None
+
+    def depth_filter_counts(self) -> np.ndarray:
+        """agh_get_depth_filter_counts: an (n_views, 4) int64 array, a row per view of the last deprojection in launch order --
+        n_valid, n_out_of_range, n_unsupported, n_kept -- or an empty one if that deprojection ran without a filter."""
+        recs = (AghDepthFilterCounts * 128)()
+        k = self._check(self.lib.agh_get_depth_filter_counts(self._h, recs, C.c_int32(128)))
+        return np.array([[r.n_valid, r.n_out_of_range, r.n_unsupported, r.n_kept] for r in recs[:k]], np.int64).reshape(k, 4)
 
     def set_cloud_batch_torch(self, xyz_t, cam_t, offsets, stream=None):
         assert xyz_t.is_cuda and xyz_t.is_contiguous()

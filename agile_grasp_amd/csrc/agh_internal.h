@@ -396,6 +396,14 @@ struct Ctx
   // and uploaded on `stream` in front of the launch (a batch's host images lie in d_depth too, each at a 256-byte boundary)
   uint8_t* d_depth_views = nullptr;
   uint8_t* h_depth_views = nullptr;  // pinned
+  // agh_set_depth_filter (depth.hip): the sticky filter every deprojection of this context applies, host-side (the kernels take it
+  // as arguments); the per-view counters of k_deproject_filtered*, kMaxDepthViews x 4, zeroed on the launch's stream in front of
+  // it; filter_views: the views of the LAST deprojection if it ran with a filter, else 0, and the stream it ran on
+  bool depth_filter_set = false;
+  agh_depth_filter_params depth_filter = {};
+  int64_t* d_filter_counts = nullptr;
+  int filter_views = 0;
+  hipStream_t filter_stream = nullptr;
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
   LocalizeBatchState* lbatch = nullptr;  // agh_localize_batch's buffers (localize_batch.hip), made by its first call
   bool batch_active = false;       // inside agh_localize_batch (agh_localize_begin refuses)
@@ -1514,6 +1522,9 @@ int stage_captures(agh_ctx* ctx, const char* who, const float* const* xyz, const
 // the image and the field).  depth_to_raw: the images (host: uploaded into d_depth on `st`, or adopted from a staged set when
 // use_staged; device: read in place) back-projected by k_deproject on `st` into d_raw_xyz, packed, stride 12.
 // capture >= 0: the images are capture `capture`'s of a batch, and the error text names it too ("capture 3, image 1: ...").
+// With a depth filter set (agh_set_depth_filter) depth_to_raw and depth_batch_to_raw launch k_deproject_filtered /
+// k_deproject_filtered_batch in the plain kernels' place, behind a memset of the views' counters on `st`; without one they launch
+// what they always launched.
 int depth_check(agh::Ctx* c, const char* who, const agh_depth_image* images, int32_t n_images, bool on_device, int64_t* n_points,
   int capture = -1);
 int depth_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, int n_images, bool on_device, bool use_staged,

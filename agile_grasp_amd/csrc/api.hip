@@ -514,7 +514,7 @@ void agh_destroy(agh_ctx* ctx)
     c->d_flags, c->d_normals, c->d_svm_w, c->d_hog, c->d_geom, c->d_desc_out, c->d_svm_sums, c->d_keep, c->d_vox_desc,
     c->d_weight, c->d_order, c->d_order_sweep, c->d_vmask, c->d_cloud_off, c->d_scloud, c->d_idx_own, c->d_tile_state, c->d_h_hands, c->d_h_bits, c->d_h_rowcnt, c->d_h_first,
     c->d_h_n, c->d_h_idx, c->d_h_counts, c->d_h_handles, c->d_h_tmp, c->d_images_cam, c->d_xbuf, c->d_nbuf, c->d_xcnt, c->d_cls_images, c->d_cls_keep, c->d_cls_sums, c->d_dbg, c->d_svm_svT, c->d_svm_alpha, c->d_cls_desc, c->d_cls_kbuf, c->d_vox_code, c->d_vox_blk, c->d_vox_blk2, c->d_vox_total, c->d_vox_bitmap, c->d_vox_xyz, c->d_vox_cam, c->d_raw_xyz, c->d_huge_stage, c->d_huge_key, c->d_huge_count, c->d_huge_sorted, c->d_huge_normals, c->d_huge_base, c->d_stage_xyz, c->d_ovf,
-    c->d_desc_next, c->d_count_part, c->d_grid_miss, c->d_depth, c->d_depth_stage, c->d_depth_views,
+    c->d_desc_next, c->d_count_part, c->d_grid_miss, c->d_depth, c->d_depth_stage, c->d_depth_views, c->d_filter_counts,
     c->d_mask, c->d_mask_bitmap, c->d_mask_blk, c->d_mask_total, c->d_mask_list,
     c->d_label_rank, c->d_label_set, c->d_label_groups, c->d_label_totals,
     c->d_cluster_parent, c->d_cluster_size, c->d_cluster_label, c->d_cluster_counts, c->d_fit };

@@ -1,12 +1,15 @@
 // depth.hip -- the localize chain's third source kind (include/agh.h, agh_localize_depth*): a capture as the sensor's driver hands it
 // over, one depth image per camera, back-projected on the device into the raw buffer an upload of points would have filled.
 // k_deproject and its launch, the argument rules, the context's two depth buffers (this capture's images and the staged next
-// ones), agh_deproject and agh_localize_depth_stage; the chain itself is localize.hip's.
+// ones), agh_deproject and agh_localize_depth_stage; the chain itself is localize.hip's.  The depth filter (agh_set_depth_filter):
+// its setting, k_deproject_filtered / k_deproject_filtered_batch, which take the plain kernels' place while a filter is set, and
+// their per-view counters.
 #include "agh_internal.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 
 using namespace agh;
 
@@ -161,6 +164,292 @@ extern "C" __global__ __launch_bounds__(kDeprojBlock) void k_deproject_batch(con
   deproject_run(im, (int64_t) (blockIdx.x - im.first_block) * kDeprojBlock + threadIdx.x, out);
 }
 
+// ---- the depth filter (include/agh.h, agh_set_depth_filter): k_deproject with a look at every pixel's neighbours ----
+// A work-group owns one tile of kTileW x kTileH pixels of ONE image (first_block counts tiles here), lane t the run of kRun pixels
+// at row t / 16, columns 4 (t % 16)...: the lanes 16r..16r+15 hold one row of the tile.  The tile's depths and a halo of `radius`
+// rows and columns go into LDS as float32, NaN for every pixel that is outside the image, invalid or out of range -- so the one
+// comparison fabsf(z_q - z_p) <= tol decides support, NaN comparing false.
+// The LDS image: row y of the tile at row y + kHaloMax, column x at word kTileCol0 + x of the row, so that a lane's own run, the
+// run to its left and the run to its right are three aligned 16-byte reads.  The row pitch is 128 words, a multiple of the 64 banks:
+// a 16-byte read's lane groups ({0-3, 12-15, 20-27}, ...) then take 64 consecutive words of two rows at the same columns modulo
+// 64 -- words 0..15 and 48..63 of one row, 16..47 of the next -- which are 64 distinct banks ("Depth filter").
+constexpr int kTileW = 64, kTileH = 16;
+constexpr int kHaloMax = 2;      // the largest radius
+constexpr int kTileCol0 = 4;     // the word of tile column 0 in an LDS row: the left halo lies in the run before it
+constexpr int kTilePitch = 128;  // words
+constexpr int kTileRows = kTileH + 2 * kHaloMax;
+constexpr int kFilterCounters = 4;  // agh_depth_filter_counts: n_valid, n_out_of_range, n_unsupported, n_kept
+static_assert(kTileW * kTileH == kRun * kDeprojBlock && kTileW == 16 * kRun, "a lane's run is one of its tile's");
+static_assert(kTileCol0 + kTileW + kRun <= kTilePitch && kTileCol0 >= kHaloMax && kRun >= kHaloMax, "the three reads stay in the row");
+
+typedef __attribute__((address_space(3))) F32x4 LdsF32x4;
+
+struct DepthFilterArgs
+{
+  int32_t radius, min_support;
+  float ja, jr, zlo, zhi;
+};
+
+// The depths of the run at row v, columns u0.. of `im`, by deproject_run's loads and its arithmetic: z[j] and the format's
+// validity.  A run (or its tail) outside the image is invalid and is not read.
+__device__ __forceinline__ void filter_load_run(const DepthView& im, int v, int u0, float z[kRun], bool ok[kRun])
+{
+#pragma unroll
+  for (int j = 0; j < kRun; j++)
+  {
+    z[j] = 0.0f;
+    ok[j] = false;
+  }
+  if (v < 0 || v >= im.h || u0 < 0 || u0 >= im.w)
+    return;
+  const int cnt = min(kRun, im.w - u0);
+  const GlobalBytes* row = (const GlobalBytes*) im.data + (int64_t) v * im.stride;
+  if (im.fmt == AGH_DEPTH_U16)
+  {
+    const __attribute__((address_space(1))) uint16_t* p = (const __attribute__((address_space(1))) uint16_t*) row + u0;
+    uint32_t raw[kRun] = { 0, 0, 0, 0 };
+    if (cnt == kRun && ((uintptr_t) p & 7) == 0)
+    {
+      const U32x2 q = *(const __attribute__((address_space(1))) U32x2*) p;
+      raw[0] = q.x & 0xffffu;
+      raw[1] = q.x >> 16;
+      raw[2] = q.y & 0xffffu;
+      raw[3] = q.y >> 16;
+    }
+    else
+    {
+#pragma unroll
+      for (int j = 0; j < kRun; j++)
+        if (j < cnt)
+          raw[j] = p[j];
+    }
+#pragma unroll
+    for (int j = 0; j < kRun; j++)
+    {
+      z[j] = (float) raw[j] * im.scale;
+      ok[j] = raw[j] != 0;
+    }
+  }
+  else
+  {
+    const __attribute__((address_space(1))) float* p = (const __attribute__((address_space(1))) float*) row + u0;
+    if (cnt == kRun && ((uintptr_t) p & 15) == 0)
+    {
+      const F32x4 q = *(const __attribute__((address_space(1))) F32x4*) p;
+      z[0] = q.x;
+      z[1] = q.y;
+      z[2] = q.z;
+      z[3] = q.w;
+    }
+    else
+    {
+#pragma unroll
+      for (int j = 0; j < kRun; j++)
+        z[j] = j < cnt ? p[j] : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < kRun; j++)
+      ok[j] = z[j] > 0.0f && z[j] < __builtin_huge_valf();
+  }
+}
+
+// one pixel of the halo's side columns: its depth if it is inside the image, valid and in range, else NaN
+__device__ __forceinline__ float filter_load_pixel(const DepthView& im, int v, int u, const DepthFilterArgs& f)
+{
+  const float qnan = __builtin_nanf("");
+  if (v < 0 || v >= im.h || u < 0 || u >= im.w)
+    return qnan;
+  const GlobalBytes* row = (const GlobalBytes*) im.data + (int64_t) v * im.stride;
+  float z;
+  bool ok;
+  if (im.fmt == AGH_DEPTH_U16)
+  {
+    const uint32_t raw = ((const __attribute__((address_space(1))) uint16_t*) row)[u];
+    z = (float) raw * im.scale;
+    ok = raw != 0;
+  }
+  else
+  {
+    z = ((const __attribute__((address_space(1))) float*) row)[u];
+    ok = z > 0.0f && z < __builtin_huge_valf();
+  }
+  return ok && z >= f.zlo && z <= f.zhi ? z : qnan;
+}
+
+// Tile `tile` of `im` (tiles row-major, ceil(w / kTileW) per row): the one copy of the body, k_deproject_filtered's and
+// k_deproject_filtered_batch's, for radius R.  Every lane reaches both barriers; lanes whose run lies outside the image stage NaNs
+// and write nothing.  cnt: the view's four counters.
+template <int R>
+__device__ __forceinline__ void deproject_filtered_tile(const DepthView& im, uint32_t tile, const DepthFilterArgs& f,
+  float* __restrict__ out, unsigned long long* __restrict__ cnt, float* s_z, unsigned* s_cnt)
+{
+  const float qnan = __builtin_nanf("");
+  const int tiles_x = (im.w + kTileW - 1) / kTileW;
+  const int ty = (int) (tile / (uint32_t) tiles_x);
+  const int x0 = (int) (tile - (uint32_t) ty * (uint32_t) tiles_x) * kTileW, y0 = ty * kTileH;
+  const int t = threadIdx.x;
+  const int r = t >> 4, cg = t & 15;
+  const int v = y0 + r, u0 = x0 + kRun * cg;
+  // ---- 1. the lane's own run, and one piece of the halo: a run of the rows above and below (lanes 0 .. 32 R - 1), or one pixel of
+  // the columns left and right of the tile and of the halo's corners (the next (kTileH + 2 R) x 2 R lanes) ----
+  float z[kRun];
+  bool valid[kRun], inr[kRun];
+  filter_load_run(im, v, u0, z, valid);
+  {
+    float zs[kRun];
+#pragma unroll
+    for (int j = 0; j < kRun; j++)
+    {
+      inr[j] = valid[j] && z[j] >= f.zlo && z[j] <= f.zhi;
+      zs[j] = inr[j] ? z[j] : qnan;
+    }
+    *reinterpret_cast<float4*>(&s_z[(r + kHaloMax) * kTilePitch + kTileCol0 + kRun * cg]) = make_float4(zs[0], zs[1], zs[2], zs[3]);
+  }
+  constexpr int kRowRuns = 2 * R * (kTileW / kRun);
+  constexpr int kSidePixels = (kTileH + 2 * R) * 2 * R;
+  static_assert(kRowRuns + kSidePixels <= kDeprojBlock, "one halo piece per lane");
+  if (t < kRowRuns)
+  {
+    const int j = t >> 4;
+    const int yoff = j < R ? j - R : kTileH + (j - R);
+    float hz[kRun];
+    bool hok[kRun];
+    filter_load_run(im, y0 + yoff, u0, hz, hok);
+#pragma unroll
+    for (int q = 0; q < kRun; q++)
+      hz[q] = hok[q] && hz[q] >= f.zlo && hz[q] <= f.zhi ? hz[q] : qnan;
+    *reinterpret_cast<float4*>(&s_z[(yoff + kHaloMax) * kTilePitch + kTileCol0 + kRun * cg]) = make_float4(hz[0], hz[1], hz[2], hz[3]);
+  }
+  else if (t < kRowRuns + kSidePixels)
+  {
+    const int s = t - kRowRuns;
+    const int yoff = s / (2 * R) - R;
+    const int k = s % (2 * R);
+    const int xoff = k < R ? k - R : kTileW + (k - R);
+    s_z[(yoff + kHaloMax) * kTilePitch + kTileCol0 + xoff] = filter_load_pixel(im, y0 + yoff, x0 + xoff, f);
+  }
+  __syncthreads();
+  // ---- 2. support, counted on the in-range set: per window row the run to the left, the lane's own and the run to the right ----
+  float tol[kRun];
+  int sup[kRun];
+#pragma unroll
+  for (int j = 0; j < kRun; j++)
+  {
+    tol[j] = f.ja + (f.jr * z[j]);
+    sup[j] = 0;
+  }
+#pragma unroll
+  for (int dy = -R; dy <= R; dy++)
+  {
+    // (volatile: three whole 16-byte reads, conflict-free at this pitch; left to itself the compiler reads only the words the
+    // radius needs, with 4-byte pairs whose lanes share banks)
+    const volatile LdsF32x4* rp = (const volatile LdsF32x4*) &s_z[(r + kHaloMax + dy) * kTilePitch + kRun * cg];
+    const F32x4 a = rp[0], b = rp[1], c = rp[2];
+    const float w[3 * kRun] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w };
+#pragma unroll
+    for (int j = 0; j < kRun; j++)
+#pragma unroll
+      for (int dx = -R; dx <= R; dx++)
+        if (dy != 0 || dx != 0)
+          sup[j] += fabsf(w[kRun + j + dx] - z[j]) <= tol[j] ? 1 : 0;
+  }
+  bool keep[kRun];
+#pragma unroll
+  for (int j = 0; j < kRun; j++)
+    keep[j] = inr[j] && sup[j] >= f.min_support;
+  // ---- 3. the points, deproject_run's expression and stores ----
+  if (v < im.h && u0 < im.w)
+  {
+    const int cntp = min(kRun, im.w - u0);
+    const float fv = (float) v;
+    float o[3 * kRun];
+#pragma unroll
+    for (int j = 0; j < kRun; j++)
+    {
+      const float x = (((float) (u0 + j) - im.cx) * z[j]) * im.kx;
+      const float y = ((fv - im.cy) * z[j]) * im.ky;
+      o[3 * j + 0] = keep[j] ? ((im.p[0] * x + im.p[1] * y) + im.p[2] * z[j]) + im.p[3] : qnan;
+      o[3 * j + 1] = keep[j] ? ((im.p[4] * x + im.p[5] * y) + im.p[6] * z[j]) + im.p[7] : qnan;
+      o[3 * j + 2] = keep[j] ? ((im.p[8] * x + im.p[9] * y) + im.p[10] * z[j]) + im.p[11] : qnan;
+    }
+    const int64_t idx = im.base + (int64_t) v * im.w + u0;
+    float* dst = out + 3 * idx;
+    if (cntp == kRun && (idx & 3) == 0)
+    {
+      float4* d4 = reinterpret_cast<float4*>(dst);
+      d4[0] = make_float4(o[0], o[1], o[2], o[3]);
+      d4[1] = make_float4(o[4], o[5], o[6], o[7]);
+      d4[2] = make_float4(o[8], o[9], o[10], o[11]);
+    }
+    else
+    {
+#pragma unroll
+      for (int j = 0; j < kRun; j++)
+        if (j < cntp)
+        {
+          dst[3 * j + 0] = o[3 * j + 0];
+          dst[3 * j + 1] = o[3 * j + 1];
+          dst[3 * j + 2] = o[3 * j + 2];
+        }
+    }
+  }
+  // ---- 4. the view's counters: ballots per wave, the waves' sums through LDS, one atomic per counter and work-group ----
+  unsigned n[kFilterCounters] = { 0, 0, 0, 0 };
+#pragma unroll
+  for (int j = 0; j < kRun; j++)
+  {
+    n[0] += (unsigned) __popcll(__ballot(valid[j]));
+    n[1] += (unsigned) __popcll(__ballot(valid[j] && !inr[j]));
+    n[2] += (unsigned) __popcll(__ballot(inr[j] && !keep[j]));
+    n[3] += (unsigned) __popcll(__ballot(keep[j]));
+  }
+  if ((t & 63) == 0)
+  {
+#pragma unroll
+    for (int q = 0; q < kFilterCounters; q++)
+      s_cnt[(t >> 6) * kFilterCounters + q] = n[q];
+  }
+  __syncthreads();
+  if (t < kFilterCounters)
+    atomicAdd(&cnt[t], (unsigned long long) (s_cnt[t] + s_cnt[kFilterCounters + t] + s_cnt[2 * kFilterCounters + t] + s_cnt[3 * kFilterCounters + t]));
+}
+
+__device__ __forceinline__ void deproject_filtered(const DepthView& im, uint32_t tile, const DepthFilterArgs& f, float* __restrict__ out,
+  unsigned long long* __restrict__ cnt)
+{
+  __shared__ __attribute__((aligned(16))) float s_z[kTileRows * kTilePitch];
+  __shared__ unsigned s_cnt[(kDeprojBlock / 64) * kFilterCounters];
+  if (f.radius == 1)
+    deproject_filtered_tile<1>(im, tile, f, out, cnt, s_z, s_cnt);
+  else
+    deproject_filtered_tile<2>(im, tile, f, out, cnt, s_z, s_cnt);
+}
+
+extern "C" __global__ __launch_bounds__(kDeprojBlock) void k_deproject_filtered(DepthArgs a, int n_images, DepthFilterArgs f,
+  float* __restrict__ out, unsigned long long* __restrict__ counts)
+{
+  const int k = (n_images > 1 && blockIdx.x >= a.v[1].first_block) ? 1 : 0;
+  const DepthView& im = a.v[k];
+  deproject_filtered(im, blockIdx.x - im.first_block, f, out, counts + kFilterCounters * k);
+}
+
+// (the views as k_deproject_batch finds them; counts: kFilterCounters per view, in launch order)
+extern "C" __global__ __launch_bounds__(kDeprojBlock) void k_deproject_filtered_batch(const DepthView* __restrict__ views, int n_views,
+  DepthFilterArgs f, float* __restrict__ out, unsigned long long* __restrict__ counts)
+{
+  int lo = 0, hi = n_views - 1;
+  while (lo < hi)
+  {
+    const int mid = (lo + hi + 1) >> 1;
+    if (views[mid].first_block <= blockIdx.x)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const DepthView& im = views[lo];
+  deproject_filtered(im, blockIdx.x - im.first_block, f, out, counts + kFilterCounters * lo);
+}
+
 inline int64_t elem_size(int32_t format) { return format == AGH_DEPTH_U16 ? 2 : 4; }
 inline int64_t packed_bytes(const agh_depth_image& im) { return (int64_t) im.width * im.height * elem_size(im.format); }
 // where image k's packed rows start in a depth buffer of the context: the images of a capture (or of a whole batch, in capture
@@ -215,6 +504,32 @@ DepthView make_view(const agh_depth_image& im, const uint8_t* data, int64_t stri
   return v;
 }
 inline uint32_t view_blocks(const DepthView& v) { return (uint32_t) (((int64_t) v.runs * v.h + kDeprojBlock - 1) / kDeprojBlock); }
+// ... and as the filtered kernels count them: first_block and the launch in tiles
+inline uint32_t view_tiles(const DepthView& v) { return (uint32_t) ((v.w + kTileW - 1) / kTileW) * (uint32_t) ((v.h + kTileH - 1) / kTileH); }
+
+// the filter held by the context as the kernels take it: the four doubles rounded once to float32
+DepthFilterArgs filter_args(const Ctx* c)
+{
+  DepthFilterArgs f;
+  f.radius = c->depth_filter.radius;
+  f.min_support = c->depth_filter.min_support;
+  f.ja = (float) c->depth_filter.max_jump_abs;
+  f.jr = (float) c->depth_filter.max_jump_rel;
+  f.zlo = (float) c->depth_filter.z_min;
+  f.zhi = (float) c->depth_filter.z_max;
+  return f;
+}
+
+// the per-view counters of the filtered launch that follows on `st`, zeroed in front of it
+int filter_counts_for(Ctx* c, int views, hipStream_t st)
+{
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are read back as int64_t");
+  if (!c->d_filter_counts)
+    if (int rc = dev_alloc(c, &c->d_filter_counts, (size_t) kMaxDepthViews * kFilterCounters))
+      return rc;
+  AGH_HIPCHK(c, hipMemsetAsync(c->d_filter_counts, 0, sizeof(int64_t) * kFilterCounters * (size_t) views, st));
+  return AGH_OK;
+}
 
 // the raw buffer for `total` points, and `st` behind the last batch chain that read it (as stage_captures waits, localize.hip)
 int raw_buffer_for(Ctx* c, int64_t total, hipStream_t st)
@@ -344,6 +659,8 @@ int depth_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, i
     total += (int64_t) images[k].width * images[k].height;
   if ((rc = raw_buffer_for(c, total, st)))
     return rc;
+  const bool filtered = c->depth_filter_set;
+  c->filter_views = 0;  // (agh_get_depth_filter_counts: the views of the last deprojection, if it ran with a filter)
   DepthArgs a;
   std::memset(&a, 0, sizeof(a));
   int64_t base = 0;
@@ -354,7 +671,24 @@ int depth_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, i
     a.v[k] = on_device ? make_view(im, static_cast<const uint8_t*>(im.data), im.row_stride_bytes, base, blocks)
                        : make_view(im, c->d_depth + depth_image_offset(images, k), (int64_t) im.width * elem_size(im.format), base, blocks);
     base += (int64_t) im.width * im.height;
-    blocks += view_blocks(a.v[k]);
+    blocks += filtered ? view_tiles(a.v[k]) : view_blocks(a.v[k]);
+  }
+  if (filtered)
+  {
+    if ((rc = filter_counts_for(c, n_images, st)))
+      return rc;
+    hipLaunchKernelGGL(k_deproject_filtered, dim3(blocks), dim3(kDeprojBlock), 0, st, a, n_images, filter_args(c), c->d_raw_xyz,
+      reinterpret_cast<unsigned long long*>(c->d_filter_counts));
+    if (hipGetLastError() != hipSuccess)
+    {
+      c->err = std::string(who) + ": k_deproject_filtered launch failed";
+      return AGH_ERR_HIP;
+    }
+    c->filter_views = n_images;
+    c->filter_stream = st;
+    if (!on_device)
+      return record_depth_read(c, st);
+    return AGH_OK;
   }
   hipLaunchKernelGGL(k_deproject, dim3(blocks), dim3(kDeprojBlock), 0, st, a, n_images, c->d_raw_xyz);
   if (hipGetLastError() != hipSuccess)
@@ -432,6 +766,8 @@ int depth_batch_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* ima
       return rc;
     AGH_HIPCHK_OR(c, upload_images(c->d_depth, images, views, st), fail(AGH_ERR_HIP));
   }
+  const bool filtered = c->depth_filter_set;
+  c->filter_views = 0;
   DepthView* tab = reinterpret_cast<DepthView*>(c->h_depth_views);
   int64_t base = 0, off = 0;
   uint32_t blocks = 0;
@@ -442,11 +778,29 @@ int depth_batch_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* ima
                        : make_view(im, c->d_depth + off, (int64_t) im.width * elem_size(im.format), base, blocks);
     base += (int64_t) im.width * im.height;
     off += aligned_bytes(im);
-    blocks += view_blocks(tab[j]);
+    blocks += filtered ? view_tiles(tab[j]) : view_blocks(tab[j]);
   }
   if ((rc = raw_buffer_for(c, base, st)))
     return fail(rc);
   AGH_HIPCHK_OR(c, hipMemcpyAsync(c->d_depth_views, tab, sizeof(DepthView) * (size_t) views, hipMemcpyHostToDevice, st), fail(AGH_ERR_HIP));
+  if (filtered)
+  {
+    if ((rc = filter_counts_for(c, views, st)))
+      return fail(rc);
+    hipLaunchKernelGGL(k_deproject_filtered_batch, dim3(blocks), dim3(kDeprojBlock), 0, st,
+      reinterpret_cast<const DepthView*>(c->d_depth_views), views, filter_args(c), c->d_raw_xyz,
+      reinterpret_cast<unsigned long long*>(c->d_filter_counts));
+    if (hipGetLastError() != hipSuccess)
+    {
+      c->err = std::string(who) + ": k_deproject_filtered_batch launch failed";
+      return fail(AGH_ERR_HIP);
+    }
+    c->filter_views = views;
+    c->filter_stream = st;
+    if (!on_device && (rc = record_depth_read(c, st)))
+      return fail(rc);
+    return AGH_OK;
+  }
   hipLaunchKernelGGL(k_deproject_batch, dim3(blocks), dim3(kDeprojBlock), 0, st, reinterpret_cast<const DepthView*>(c->d_depth_views),
     views, c->d_raw_xyz);
   if (hipGetLastError() != hipSuccess)
@@ -461,7 +815,92 @@ int depth_batch_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* ima
 
 extern "C" {
 
-int agh_deproject(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, float* xyz_out, int64_t cap_points)
+// ---- the depth filter's setting (include/agh.h): host-side, the parameters travel as kernel arguments ----
+void agh_default_depth_filter_params(agh_depth_filter_params* p)
+{
+  if (!p)
+    return;
+  p->radius = 1;
+  p->min_support = 3;
+  p->max_jump_abs = 0.01;
+  p->max_jump_rel = 0.01;
+  p->z_min = 0.0;
+  p->z_max = std::numeric_limits<double>::infinity();
+}
+
+int agh_set_depth_filter(agh_ctx* ctx, const agh_depth_filter_params* fp)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_set_depth_filter"))
+    return AGH_ERR_STATE;
+  if (!fp)
+  {
+    c->depth_filter_set = false;
+    return AGH_OK;
+  }
+  auto bad = [c](const char* what) {
+    c->err = std::string("agh_set_depth_filter: ") + what;
+    return AGH_ERR_INVALID_ARGUMENT;
+  };
+  if (fp->radius != 1 && fp->radius != 2)
+    return bad("radius must be 1 or 2");
+  const int window = (2 * fp->radius + 1) * (2 * fp->radius + 1);
+  if (fp->min_support < 1 || fp->min_support > window - 1)
+    return bad("min_support must be 1 .. (2 radius + 1)^2 - 1");
+  if (!(std::isfinite(fp->max_jump_abs) && fp->max_jump_abs >= 0.0))
+    return bad("max_jump_abs must be finite and >= 0");
+  if (!(std::isfinite(fp->max_jump_rel) && fp->max_jump_rel >= 0.0))
+    return bad("max_jump_rel must be finite and >= 0");
+  if (!(std::isfinite(fp->z_min) && fp->z_min >= 0.0))
+    return bad("z_min must be finite and >= 0");
+  if (!(fp->z_max > fp->z_min))  // (a NaN fails; +inf passes)
+    return bad("z_max must be greater than z_min");
+  c->depth_filter = *fp;
+  c->depth_filter_set = true;
+  return AGH_OK;
+}
+
+int agh_get_depth_filter(agh_ctx* ctx, agh_depth_filter_params* out)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;  // (host-side: allowed while a localize chain is in flight)
+  if (!c->depth_filter_set)
+    return 0;
+  if (!out)
+  {
+    c->err = "agh_get_depth_filter: out is NULL";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  *out = c->depth_filter;
+  return 1;
+}
+
+int agh_get_depth_filter_counts(agh_ctx* ctx, agh_depth_filter_counts* out, int32_t cap_views)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_depth_filter_counts"))
+    return AGH_ERR_STATE;
+  if (c->filter_views == 0)
+    return 0;
+  if (cap_views < c->filter_views || !out)
+  {
+    c->err = "agh_get_depth_filter_counts: room for " + std::to_string(c->filter_views) + " views is needed";
+    return AGH_ERR_CAPACITY;
+  }
+  static_assert(sizeof(agh_depth_filter_counts) == sizeof(int64_t) * kFilterCounters, "a view's record is its four counters");
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK_OR(c, hipMemcpyAsync(out, c->d_filter_counts, sizeof(agh_depth_filter_counts) * (size_t) c->filter_views, hipMemcpyDeviceToHost,
+    c->filter_stream), ((void) hipStreamSynchronize(c->filter_stream), AGH_ERR_HIP));
+  AGH_HIPCHK(c, hipStreamSynchronize(c->filter_stream));
+  return c->filter_views;
+}
+
+int agh_deproject(agh_ctx* ctx,const agh_depth_image* images, int32_t n_images, float* xyz_out, int64_t cap_points)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;

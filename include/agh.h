@@ -276,11 +276,11 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a begin).
  * Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_depth_stage,
  * agh_localize_end,
- * agh_get_cloud_cam_origins, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
+ * agh_get_cloud_cam_origins, agh_get_depth_filter, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
  * agh_destroy, the host-side counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats, agh_get_grid_desc) and the
  * communicator's bookkeeping (agh_comm_rank, agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault,
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
- * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_preprocess*, agh_find_hands*, agh_classify*,
+ * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_set_depth_filter, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
  * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled*, agh_localize_depth_labeled*,
  * agh_localize_clustered*, agh_localize_depth_clustered*, agh_localize_clustered_fit*, agh_localize_depth_clustered_fit*,
@@ -293,7 +293,7 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info,
  * agh_get_cluster_labels, agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts,
  * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels, agh_get_batch_plane_fit,
- * agh_get_batch_plane_fit_candidates and every getter of device results (frames, normals,
+ * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -730,7 +730,8 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * agh_localize_depth_batch_clustered_fit_begin*;
  * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info, agh_get_cluster_labels,
  * agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info,
- * agh_get_batch_cluster_labels, agh_get_batch_plane_fit and agh_get_batch_plane_fit_candidates are refused as well),
+ * agh_get_batch_cluster_labels, agh_get_batch_plane_fit, agh_get_batch_plane_fit_candidates, agh_set_depth_filter and
+ * agh_get_depth_filter_counts are refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
@@ -797,6 +798,63 @@ int agh_localize_depth_batch_begin_device(agh_ctx* ctx, const agh_depth_image* i
   const agh_localize_params* lp, int32_t n_captures);
 int agh_deproject_batch(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images, int32_t n_captures, float* xyz_out,
   int64_t cap_points);
+
+/* A DEPTH FILTER for every call that back-projects depth images: a real sensor's image holds, along every depth edge, flying
+ * pixels -- readings interpolated between an object and what lies behind it -- besides speckles and readings outside the
+ * sensor's trusted range.  Back-projected they are voxels floating in the free space beside objects, exactly where the hand
+ * sweep tests finger clearance, and one of them vetoes a placement.  agh_set_depth_filter makes the deprojection itself look at
+ * every pixel's neighbours; no host pass over the pixels, no new agh_localize_* variant.
+ * The setting is sticky, per context, as agh_set_cloud_cam_origins' table is: it holds until it is cleared (NULL) or replaced,
+ * across clouds, batches and chains, and costs no device work (the parameters travel as kernel arguments).  With a filter
+ * set, EVERY call that deprojects applies it: agh_deproject and agh_deproject_batch, and all agh_localize_depth* and
+ * agh_localize_depth_batch* forms (_device, _begin, _begin_device, _masked, _labeled, _clustered, _clustered_fit).
+ * agh_localize_depth_stage stays a pure copy: the filter that counts is the one set when the adopting begin deprojects.  The
+ * repeats inside a call re-run from the points already in the raw buffer: they neither filter again nor count again.  With no
+ * filter set every launch is exactly what it was: k_deproject / k_deproject_batch with their arguments.
+ * The filter, per image, independently of every other image (an image's neighbours are its own pixels only: the two images of a
+ * capture, and the captures of a batch, never support one another).  The host rounds the four doubles once to float32:
+ * ja = (float) max_jump_abs, jr = (float) max_jump_rel, zlo = (float) z_min, zhi = (float) z_max.
+ *  1. Depth and validity are k_deproject's: U16: z = (float) raw * depth_scale, valid iff raw != 0; F32: z is the pixel, valid
+ *     iff 0 < z < +inf.
+ *  2. A valid pixel is IN RANGE iff z >= zlo && z <= zhi (both ends inclusive).
+ *  3. For an in-range pixel p: tol = ja + (jr * z_p), float32, not contracted.  Its support is the number of pixels q != p of the
+ *     (2 radius + 1)^2 window around p that are inside the image, in range, and satisfy fabsf(z_q - z_p) <= tol.  Pixels outside
+ *     the image never support.  Support is counted on the in-range set of step 2, NOT on the filter's own output: one pass,
+ *     independent of any order.  The tolerance follows the CENTRE pixel, so support is not symmetric: with jr > 0 a far pixel
+ *     may count a nearer one that does not count it back.
+ *  4. p is kept iff it is in range and its support is at least min_support.  A kept pixel's point is exactly what k_deproject
+ *     writes for it (the same float32 expression, left to right); every other pixel writes the three quiet NaNs an invalid
+ *     pixel writes, which the voxeliser, the masks, labels, clusters and the plane fit already handle.
+ * agh_set_depth_filter checks every field: radius 1 or 2; min_support in 1 .. (2 radius + 1)^2 - 1; max_jump_abs and
+ * max_jump_rel finite and >= 0; z_min finite and >= 0; z_max > z_min (+inf allowed).  A violation returns
+ * AGH_ERR_INVALID_ARGUMENT, the text names the field, and the filter held before stays in force.  NULL clears the filter.
+ * Mid-chain (single or batch) it returns AGH_ERR_STATE without touching the chain.
+ * agh_get_depth_filter copies the filter held and returns 1, or returns 0 if none is set (host-side, allowed mid-chain).
+ * agh_get_depth_filter_counts: per view of the last deprojection that ran with a filter, in launch order (capture k's images
+ * follow capture k - 1's): n_valid = n_out_of_range + n_unsupported + n_kept.  Returns the number of views, or 0 if the last
+ * deprojection ran unfiltered (or none ran); AGH_ERR_CAPACITY if cap_views is smaller; AGH_ERR_STATE mid-chain.  One small copy
+ * and one synchronisation.
+ * Not built: temporal filtering over frames, hole filling, lens distortion, per-image parameters, a filter for the points
+ * forms. */
+typedef struct agh_depth_filter_params
+{
+  int32_t radius;        /* 1 or 2: window (2 radius + 1)^2 */
+  int32_t min_support;   /* 1 .. (2 radius + 1)^2 - 1 */
+  double max_jump_abs;   /* metres, finite, >= 0 */
+  double max_jump_rel;   /* per metre of depth, finite, >= 0 */
+  double z_min, z_max;   /* metres; z_min finite >= 0; z_max > z_min, may be +inf */
+} agh_depth_filter_params;
+typedef struct agh_depth_filter_counts
+{
+  int64_t n_valid;         /* pixels the format calls valid */
+  int64_t n_out_of_range;  /* valid, outside [z_min, z_max] */
+  int64_t n_unsupported;   /* in range, support below min_support */
+  int64_t n_kept;
+} agh_depth_filter_counts;
+void agh_default_depth_filter_params(agh_depth_filter_params* p);  /* radius 1; min_support 3; 0.01 / 0.01; z_min 0; z_max +inf */
+int agh_set_depth_filter(agh_ctx* ctx, const agh_depth_filter_params* fp);
+int agh_get_depth_filter(agh_ctx* ctx, agh_depth_filter_params* out);
+int agh_get_depth_filter_counts(agh_ctx* ctx, agh_depth_filter_counts* out, int32_t cap_views);
 
 /* The batch chains with every capture's samples drawn UNDER ITS OWN MASK: a cell with several sensor pairs and one detector per
  * sensor hands over, per rig, a capture and an object mask, and wants handles on the masked object of every rig from one call.

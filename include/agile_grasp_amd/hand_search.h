@@ -1245,6 +1245,50 @@ public:
       (void) agh_set_cloud_cam_origins(ctx_, nullptr, 0);
   }
 
+  /** Additional: the depth filter (agh_set_depth_filter) -- every later call of this search that back-projects depth images
+   *  rejects flying pixels, speckles and readings outside [z_min, z_max] on the device.  Sticky until clearDepthFilter, also
+   *  across a context this search re-creates (a changed hand geometry or device).  Refused while a chain is pending.
+   *  @return false (after printing) on error; the filter held before stays in force */
+  bool setDepthFilter(const agh_depth_filter_params& fp)
+  {
+    if (!ensureContext())
+      return false;
+    if (agh_set_depth_filter(ctx_, &fp) != AGH_OK)
+    {
+      fail("agh_set_depth_filter");
+      return false;
+    }
+    depth_filter_ = fp;
+    depth_filter_set_ = true;
+    return true;
+  }
+  bool clearDepthFilter()
+  {
+    if (ctx_ && agh_set_depth_filter(ctx_, nullptr) != AGH_OK)
+    {
+      fail("agh_set_depth_filter");
+      return false;
+    }
+    depth_filter_set_ = false;
+    return true;
+  }
+  /** the filter held (agh_get_depth_filter); false: none */
+  bool depthFilter(agh_depth_filter_params& out) const
+  {
+    if (depth_filter_set_)
+      out = depth_filter_;
+    return depth_filter_set_;
+  }
+  /** agh_get_depth_filter_counts: per view of the last deprojection, in launch order, what the filter did; empty if that
+   *  deprojection ran without a filter, if there was none, or while a chain is pending */
+  std::vector<agh_depth_filter_counts> depthFilterCounts()
+  {
+    std::vector<agh_depth_filter_counts> out(128);
+    const int n = ctx_ ? agh_get_depth_filter_counts(ctx_, out.data(), (std::int32_t) out.size()) : 0;
+    out.resize(n > 0 ? (std::size_t) n : 0);
+    return out;
+  }
+
   /** agh_localize_stage: the NEXT capture up, beside the chain in flight (keep `next` alive and unchanged until the
    *  localizeEnd of the chain that searches it has returned). */
   bool localizeStage(const PointCloud::Ptr& next)
@@ -1574,10 +1618,17 @@ private:
     }
     dirty_ = false;
     link_->ctx = ctx_;
+    if (depth_filter_set_ && agh_set_depth_filter(ctx_, &depth_filter_) != AGH_OK)  // (the setting follows the search, not the context)
+    {
+      fail("agh_set_depth_filter");
+      return false;
+    }
     return true;
   }
 
   agh_ctx* ctx_;
+  agh_depth_filter_params depth_filter_ = agh_depth_filter_params();  // setDepthFilter
+  bool depth_filter_set_ = false;
   std::int64_t searched_n_ = 0;
   // What an End reads of the chain in flight.  The rule for every Begin: these (and last_samples_, sized by chainBegun for
   // localizeEnd) are written only after the library's begin has returned AGH_OK, so a Begin that fails for any reason -- a

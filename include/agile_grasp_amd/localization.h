@@ -605,6 +605,43 @@ public:
     plane_fit_.seed = seed;
   }
 
+  /** Additional: the depth filter of the calls that take depth images (agh_set_depth_filter; agh_default_depth_filter_params
+   *  fills a record: 3 x 3 window, 3 supporters, 1 cm + 1 % of the depth, any range).  With a filter set the deprojection rejects
+   *  flying pixels, speckles and readings outside [z_min, z_max] on the device; the points forms are not affected.  Sticky until
+   *  clearDepthFilter, also across the setters that re-create the search.  Refused while a chain is pending.
+   *  @return false (after printing) on error; the filter held before stays in force */
+  bool setDepthFilter(const agh_depth_filter_params& fp)
+  {
+    if (chainPending("setDepthFilter"))
+      return false;
+    ensureSearch();
+    if (!search_->setDepthFilter(fp))
+      return false;
+    depth_filter_ = fp;
+    depth_filter_set_ = true;
+    return true;
+  }
+  bool clearDepthFilter()
+  {
+    if (chainPending("clearDepthFilter") || (search_ && !search_->clearDepthFilter()))
+      return false;
+    depth_filter_set_ = false;
+    return true;
+  }
+  /** the filter held; false: none */
+  bool depthFilter(agh_depth_filter_params& out) const
+  {
+    if (depth_filter_set_)
+      out = depth_filter_;
+    return depth_filter_set_;
+  }
+  /** What the filter did in the last depth call (agh_get_depth_filter_counts): one record per image, in capture order; empty if
+   *  that call ran without a filter, if there was none, or while a chain is pending. */
+  std::vector<agh_depth_filter_counts> depthFilterCounts()
+  {
+    return search_ ? search_->depthFilterCounts() : std::vector<agh_depth_filter_counts>();
+  }
+
   /** The plane the last fitted call used (agh_get_plane_fit): (a, b, c, d), the normal towards camera 0; zeros, and *found false,
    *  if it found none, if the last chain collected was not a fitted one, or while a chain is pending. */
   VectorXd fittedPlane(bool* found = nullptr)
@@ -1400,12 +1437,16 @@ private:
     search_->setKeepsTrainingImages(keeps_training_images_);
     if (sample_seed_set_)
       search_->setSampleSeed(sample_seed_);
+    if (depth_filter_set_)
+      search_->setDepthFilter(depth_filter_);
   }
 
   int num_threads_, num_samples_;
   bool filters_boundaries_;
   agh_cluster_params cluster_;  // setClusterParams (the plane comes with each call)
   agh_plane_fit_params plane_fit_;  // setPlaneFitParams
+  agh_depth_filter_params depth_filter_ = agh_depth_filter_params();  // setDepthFilter
+  bool depth_filter_set_ = false;
   int plotting_mode_;
   Matrix4d cam_tf_left_, cam_tf_right_;
   VectorXd workspace_;
