@@ -117,6 +117,7 @@ EXPORTS = [
     "agh_localize_depth_batch_clustered_fit_device", "agh_localize_depth_batch_clustered_fit_begin",
     "agh_localize_depth_batch_clustered_fit_begin_device", "agh_get_batch_plane_fit", "agh_get_batch_plane_fit_candidates",
     "agh_default_depth_filter_params", "agh_set_depth_filter", "agh_get_depth_filter", "agh_get_depth_filter_counts",
+    "agh_default_voxel_filter_params", "agh_set_voxel_filter", "agh_get_voxel_filter", "agh_get_voxel_filter_counts",
 ]
 
 
@@ -254,6 +255,25 @@ class AghDepthFilterParams(C.Structure):
 
 class AghDepthFilterCounts(C.Structure):
     _fields_ = [("n_valid", C.c_int64), ("n_out_of_range", C.c_int64), ("n_unsupported", C.c_int64), ("n_kept", C.c_int64)]
+
+
+class AghVoxelFilterParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("min_neighbors", C.c_int32)]
+
+
+class AghVoxelFilterCounts(C.Structure):
+    _fields_ = [("n_occupied", C.c_int64 * 2), ("n_pruned", C.c_int64 * 2), ("n_kept", C.c_int64 * 2)]
+
+
+def voxel_filter_params(**fields) -> AghVoxelFilterParams:
+    """agh_default_voxel_filter_params, then the given fields."""
+    fp = AghVoxelFilterParams()
+    load_library().agh_default_voxel_filter_params(C.byref(fp))
+    for k, v in fields.items():
+        if not hasattr(fp, k):
+            raise TypeError(f"agh_voxel_filter_params has no field {k}")
+        setattr(fp, k, v)
+    return fp
 
 
 def depth_filter_params(**fields) -> AghDepthFilterParams:
@@ -452,6 +472,7 @@ def load_library():
         lib.agh_default_cluster_params.restype = None
         lib.agh_default_plane_fit_params.restype = None
         lib.agh_default_depth_filter_params.restype = None
+        lib.agh_default_voxel_filter_params.restype = None
         _LIB = lib
     return _LIB
 
@@ -568,6 +589,35 @@ class Context:
         recs = (AghDepthFilterCounts * 128)()
         k = self._check(self.lib.agh_get_depth_filter_counts(self._h, recs, C.c_int32(128)))
         return np.array([[r.n_valid, r.n_out_of_range, r.n_unsupported, r.n_kept] for r in recs[:k]], np.int64).reshape(k, 4)
+
+    def set_voxel_filter(self, fp=None, **fields):
+        """agh_set_voxel_filter: every later voxelisation of this context (preprocess*, every localize* form) prunes the voxels
+        with fewer than min_neighbors occupied voxels of their own camera within `radius` voxels.  `fp`: a voxel_filter_params()
+        record, or None for the defaults; the keyword fields (radius, min_neighbors) are set on top.  Sticky until
+        clear_voxel_filter()."""
+        rec = voxel_filter_params()
+        if fp is not None:
+            C.memmove(C.byref(rec), C.byref(fp), C.sizeof(AghVoxelFilterParams))
+        for k, v in fields.items():
+            if not hasattr(rec, k):
+                raise TypeError(f"agh_voxel_filter_params has no field {k}")
+            setattr(rec, k, v)
+        self._check(self.lib.agh_set_voxel_filter(self._h, C.byref(rec)))
+
+    def clear_voxel_filter(self):
+        self._check(self.lib.agh_set_voxel_filter(self._h, None))
+
+    def voxel_filter(self):
+        """The agh_voxel_filter_params record held, or None."""
+        rec = AghVoxelFilterParams()
+        return rec if self._check(self.lib.agh_get_voxel_filter(self._h, C.byref(rec))) == 1 else None
+
+    def voxel_filter_counts(self) -> np.ndarray:
+        """agh_get_voxel_filter_counts: an (n_captures, 6) int64 array, a row per capture of the last voxelisation -- n_occupied,
+        n_pruned, n_kept, each for camera 0 and camera 1 -- or an empty one if that voxelisation ran without a filter."""
+        recs = (AghVoxelFilterCounts * 64)()
+        k = self._check(self.lib.agh_get_voxel_filter_counts(self._h, recs, C.c_int32(64)))
+        return np.array([list(r.n_occupied) + list(r.n_pruned) + list(r.n_kept) for r in recs[:k]], np.int64).reshape(k, 6)
 
     def set_cloud_batch_torch(self, xyz_t, cam_t, offsets, stream=None):
         assert xyz_t.is_cuda and xyz_t.is_contiguous()

@@ -136,6 +136,7 @@ struct VoxDesc
   int dim[2][3];
   unsigned long long bits[2], word_ofs[2], n_words;
   long long n_kept[2], n_vox[2];
+  long long n_occupied[2], n_pruned[2];  // k_vox_prune (agh_set_voxel_filter): the bits k_vox_mark set, and those it took out
   int error;
 };
 struct VoxWorkspace
@@ -318,6 +319,17 @@ struct Ctx
   unsigned* d_vox_bitmap = nullptr;
   int64_t vox_bitmap_cap = 0;      // words (a multiple of the popcount block)
   int64_t vox_last_words = 0;   // lattice words of the last preprocessed cloud (a much larger kept bitmap is dropped)
+  // agh_set_voxel_filter (voxelize.hip, k_vox_prune): the sticky filter every voxelisation of this context applies, host-side (the
+  // kernel takes the two ints as arguments); d_vox_pruned: the second bitmap, of d_vox_bitmap's capacity, made by the first filtered
+  // voxelisation -- k_vox_prune writes it and the two pointers are swapped, so that d_vox_bitmap is the pruned one to all later
+  // code; vox_filter_captures: the captures of the LAST voxelisation if it ran filtered (their counts are in the pinned descriptor
+  // mirrors at vox_filter_mirror: h_vox_desc, or the batch's), else 0
+  bool voxel_filter_set = false;
+  agh_voxel_filter_params voxel_filter = {};
+  unsigned* d_vox_pruned = nullptr;
+  int64_t vox_pruned_cap = 0;
+  int vox_filter_captures = 0;
+  const VoxDesc* vox_filter_mirror = nullptr;
   VoxDesc* h_vox_desc = nullptr;   // pinned host mirror of the descriptor, written by k_vox_lattice / k_vox_totals
   float* d_vox_xyz = nullptr;      // voxelised cloud (packed xyz) and camera ids
   int32_t* d_vox_cam = nullptr;
@@ -904,7 +916,8 @@ struct BatchFitStage
 };
 int plane_fit_stage_batch(Ctx* c, const BatchFitStage& m, hipStream_t st);
 int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
-  unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st);
+  unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st,
+  unsigned* pruned = nullptr, const agh_voxel_filter_params* filter = nullptr);
 // host mirror of the handle search's results (pinned memory of the context; all nullptr / 0: none)
 struct HandleMirror
 {
@@ -982,6 +995,14 @@ inline int dev_alloc(Ctx* c, T** p, size_t count)
     return AGH_ERR_HIP;
   }
   return AGH_OK;
+}
+// the voxel bitmap of the context, and the voxel filter's second one with it (the next voxelisation sizes new ones)
+inline void drop_vox_bitmaps(Ctx* c)
+{
+  (void) hipFree(c->d_vox_bitmap);
+  (void) hipFree(c->d_vox_pruned);
+  c->d_vox_bitmap = c->d_vox_pruned = nullptr;
+  c->vox_bitmap_cap = c->vox_pruned_cap = 0;
 }
 int ensure_clouds(Ctx* c, int C);
 int ensure_draws(Ctx* c, int64_t count, hipStream_t st);

@@ -513,7 +513,7 @@ void agh_destroy(agh_ctx* ctx)
     c->d_images, c->d_slot_index, c->d_scan_tmp, c->d_out_own, c->d_nout, c->d_out_images, c->d_draw_ofs, c->d_draws,
     c->d_flags, c->d_normals, c->d_svm_w, c->d_hog, c->d_geom, c->d_desc_out, c->d_svm_sums, c->d_keep, c->d_vox_desc,
     c->d_weight, c->d_order, c->d_order_sweep, c->d_vmask, c->d_cloud_off, c->d_scloud, c->d_idx_own, c->d_tile_state, c->d_h_hands, c->d_h_bits, c->d_h_rowcnt, c->d_h_first,
-    c->d_h_n, c->d_h_idx, c->d_h_counts, c->d_h_handles, c->d_h_tmp, c->d_images_cam, c->d_xbuf, c->d_nbuf, c->d_xcnt, c->d_cls_images, c->d_cls_keep, c->d_cls_sums, c->d_dbg, c->d_svm_svT, c->d_svm_alpha, c->d_cls_desc, c->d_cls_kbuf, c->d_vox_code, c->d_vox_blk, c->d_vox_blk2, c->d_vox_total, c->d_vox_bitmap, c->d_vox_xyz, c->d_vox_cam, c->d_raw_xyz, c->d_huge_stage, c->d_huge_key, c->d_huge_count, c->d_huge_sorted, c->d_huge_normals, c->d_huge_base, c->d_stage_xyz, c->d_ovf,
+    c->d_h_n, c->d_h_idx, c->d_h_counts, c->d_h_handles, c->d_h_tmp, c->d_images_cam, c->d_xbuf, c->d_nbuf, c->d_xcnt, c->d_cls_images, c->d_cls_keep, c->d_cls_sums, c->d_dbg, c->d_svm_svT, c->d_svm_alpha, c->d_cls_desc, c->d_cls_kbuf, c->d_vox_code, c->d_vox_blk, c->d_vox_blk2, c->d_vox_total, c->d_vox_bitmap, c->d_vox_pruned, c->d_vox_xyz, c->d_vox_cam, c->d_raw_xyz, c->d_huge_stage, c->d_huge_key, c->d_huge_count, c->d_huge_sorted, c->d_huge_normals, c->d_huge_base, c->d_stage_xyz, c->d_ovf,
     c->d_desc_next, c->d_count_part, c->d_grid_miss, c->d_depth, c->d_depth_stage, c->d_depth_views, c->d_filter_counts,
     c->d_mask, c->d_mask_bitmap, c->d_mask_blk, c->d_mask_total, c->d_mask_list,
     c->d_label_rank, c->d_label_set, c->d_label_groups, c->d_label_totals,
@@ -835,9 +835,7 @@ extern "C++" int preprocess_device_impl(agh_ctx* ctx, const float* d_xyz, int64_
     // (a bitmap kept from a much larger lattice is dropped: every later cloud would clear and count all of it)
     if (c->d_vox_bitmap && c->vox_last_words > 0 && c->vox_bitmap_cap > 8 * c->vox_last_words + (1 << 20))
     {
-      (void) hipFree(c->d_vox_bitmap);
-      c->d_vox_bitmap = nullptr;
-      c->vox_bitmap_cap = 0;
+      drop_vox_bitmaps(c);
     }
     const bool speculative = c->d_vox_bitmap && c->vox_bitmap_cap > 0;
     if ((rc = vox_stage1(c, d_xyz, stride_bytes / 4, n, size_left, dense, workspace, cell_size, st,
@@ -880,9 +878,7 @@ extern "C++" int preprocess_device_impl(agh_ctx* ctx, const float* d_xyz, int64_
     if (h.error != 2 || attempt >= 1)
       break;
     // the lattice outgrew the bitmap: drop it, so that the next pass sizes a new one from this cloud's lattice
-    (void) hipFree(c->d_vox_bitmap);
-    c->d_vox_bitmap = nullptr;
-    c->vox_bitmap_cap = 0;
+    drop_vox_bitmaps(c);
   }
   if (h.error)
   {

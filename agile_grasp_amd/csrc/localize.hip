@@ -618,9 +618,7 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
       drop_bound_cloud(c);
       if (h.error == 2 && !L.repeated)
       {
-        (void) hipFree(c->d_vox_bitmap);
-        c->d_vox_bitmap = nullptr;
-        c->vox_bitmap_cap = 0;
+        drop_vox_bitmaps(c);
         agh_localize_params lp = L.lp;
         lp.sample_idx = L.explicit_samples ? h_idx : nullptr;
         L.repeated = true;

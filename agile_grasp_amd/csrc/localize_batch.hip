@@ -72,6 +72,8 @@ struct LocalizeBatchState
   int* d_blk = nullptr;
   int64_t blk_cap = 0;
   unsigned* d_bitmap = nullptr;   // bitmap_slots x slot_words
+  unsigned* d_pruned = nullptr;   // agh_set_voxel_filter: k_vox_prune's output, as large; swapped with d_bitmap once queued
+  int64_t pruned_words = 0;
   int* d_blk2 = nullptr;          // bitmap_slots x slot_words / 4096
   int64_t slot_words = 0, bitmap_words = 0, last_words = 0;
   // the handle search's lists, slot hands per capture
@@ -116,7 +118,7 @@ void localize_batch_release(Ctx* c)
   if (!b)
     return;
   void* dev[] = { b->d_tab, b->d_local, b->d.hands, b->d.bits, b->d.rowcnt, b->d.first, b->d.n, b->d.idx, b->d.counts, b->d.tmp,
-    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_blk2, b->d_mask, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist, b->d_lcap, b->d_ccap, b->d_fit, b->d_fcap };
+    b->d.handles, b->d_count, b->d_vcap, b->d_vdesc, b->d_blk, b->d_bitmap, b->d_pruned, b->d_blk2, b->d_mask, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist, b->d_lcap, b->d_ccap, b->d_fit, b->d_fcap };
   for (void* p : dev)
     if (p)
       (void) hipFree(p);
@@ -318,6 +320,14 @@ int ensure_vox_slots(Ctx* c, LocalizeBatchState* b, int C)
       return rc;
     }
     b->bitmap_words = need;
+  }
+  // (agh_set_voxel_filter: the second set of slots, made by the first filtered batch and regrown with the first set)
+  if (c->voxel_filter_set && (b->pruned_words != b->bitmap_words || !b->d_pruned))
+  {
+    b->pruned_words = 0;
+    if (int rc = dev_alloc(c, &b->d_pruned, (size_t) b->bitmap_words + 4096))
+      return rc;
+    b->pruned_words = b->bitmap_words;
   }
   return AGH_OK;
 }
@@ -753,10 +763,17 @@ int batch_pass(agh_ctx* ctx)
   vb.slot_words = b->slot_words;
   timing_begin(c, st);
   if ((rc = vox_batch(vb, C, nb_max, n_max, any_scan, cell, false, b->d_bitmap, b->d_blk, b->d_blk2, c->d_vox_code, c->d_vox_xyz,
-         c->d_vox_cam, c->d_cloud_off, st)) != AGH_OK)
+         c->d_vox_cam, c->d_cloud_off, st, b->d_pruned, c->voxel_filter_set ? &c->voxel_filter : nullptr)) != AGH_OK)
   {
     c->err = "preprocessing launch failed";
     return chain_fail(c, rc);
+  }
+  c->vox_filter_captures = 0;
+  if (c->voxel_filter_set)
+  {
+    std::swap(b->d_bitmap, b->d_pruned);  // (queued: "the" bitmap of the batch is the pruned one to every later stage)
+    c->vox_filter_captures = C;
+    c->vox_filter_mirror = b->h_desc;
   }
   timing_mark(c, "preprocess", st);
   c->cloud_async = false;

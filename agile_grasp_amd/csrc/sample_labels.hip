@@ -119,7 +119,10 @@ __device__ __forceinline__ void label_mark_points(const float* __restrict__ xyz,
     const int c = (int) (cd >> 1);
     const unsigned long long pos = vox_bit(d, c, xyz + i * stride, cell);
     const unsigned long long w = d->word_ofs[c] + (pos >> 5);
-    const unsigned below = vox[w] & ((1u << (unsigned) (pos & 31ull)) - 1u);
+    const unsigned word = vox[w], bit = 1u << (unsigned) (pos & 31ull);
+    if (!(word & bit))  // (agh_set_voxel_filter: the point's voxel was pruned -- the index below would be its neighbour's)
+      continue;
+    const unsigned below = word & (bit - 1u);
     const int64_t v = (int64_t) vox_prefix[w >> 12] + (int64_t) rank[w] + __popc(below);
     if (v < n)  // (the voxel count is at most the kept points': always)
       atomicOr(&objset[v], 1ull << (label - 1));

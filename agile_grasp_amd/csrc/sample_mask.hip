@@ -17,11 +17,13 @@ namespace agh
 constexpr int kMaskWordsPerBlock = 4096;  // voxelize.hip's kWordsPerBlock: 16 words per thread of 256
 
 // Raw point i with mask[i] != 0 and code[i] != 0 sets the bit k_vox_mark set for it (vox_bit), in the eligibility bitmap.
+// vox (agh_set_voxel_filter; nullptr without a filter, when every such bit is set in the voxel bitmap): the pruned voxel bitmap --
+// a point whose own voxel was taken out marks nothing, or its bit would count as the next surviving voxel's.
 // A thread takes the four mask bytes of one ALIGNED 32-bit word: with the base `a` bytes into a word, word w holds the points
 // 4 w - a .. 4 w - a + 3; the words that straddle either end of the mask are read a byte at a time.
 __global__ __launch_bounds__(256) void k_mask_mark(const float* __restrict__ xyz, int64_t stride, int64_t n,
   const uint8_t* __restrict__ code, const uint8_t* __restrict__ mask, const VoxDesc* __restrict__ d, double cell,
-  unsigned* __restrict__ elig)
+  unsigned* __restrict__ elig, const unsigned* __restrict__ vox)
 {
   const int64_t a = (int64_t) (reinterpret_cast<uintptr_t>(mask) & 3u);
   const int64_t i0 = 4 * ((int64_t) blockIdx.x * blockDim.x + threadIdx.x) - a;
@@ -46,7 +48,11 @@ __global__ __launch_bounds__(256) void k_mask_mark(const float* __restrict__ xyz
       continue;
     const int c = (int) (cd >> 1);
     const unsigned long long pos = vox_bit(d, c, xyz + i * stride, cell);
-    atomicOr(&elig[d->word_ofs[c] + (pos >> 5)], 1u << (unsigned) (pos & 31ull));
+    const unsigned long long w = d->word_ofs[c] + (pos >> 5);
+    const unsigned bit = 1u << (unsigned) (pos & 31ull);
+    if (vox && !(vox[w] & bit))  // (agh_set_voxel_filter: the point's voxel was pruned)
+      continue;
+    atomicOr(&elig[w], bit);
   }
 }
 
@@ -158,7 +164,8 @@ int sample_mask_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t
     AGH_HIPCHK(c, hipMemsetAsync(c->d_mask_bitmap, 0, (size_t) words * 4, st));
     const int64_t mask_words = (n + 3 + 3) / 4;  // (aligned words that a base up to 3 bytes into one can touch)
     hipLaunchKernelGGL(k_mask_mark, dim3((unsigned) ((mask_words + 255) / 256)), dim3(256), 0, st, d_xyz, stride_floats, n,
-      (const uint8_t*) c->d_vox_code, d_mask, (const VoxDesc*) c->d_vox_desc, cell, c->d_mask_bitmap);
+      (const uint8_t*) c->d_vox_code, d_mask, (const VoxDesc*) c->d_vox_desc, cell, c->d_mask_bitmap,
+      c->voxel_filter_set ? (const unsigned*) c->d_vox_bitmap : (const unsigned*) nullptr);
   }
   if ((rc = vox_count_blocks(c->d_mask_bitmap, nb, c->d_mask_blk, c->d_mask_total, st)) != AGH_OK)
   {
@@ -187,7 +194,7 @@ int sample_mask_stage(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t
 // a word that straddles either end of ITS n bytes is read a byte at a time -- in a packed buffer the bytes beside them are a
 // neighbour capture's.
 __global__ __launch_bounds__(256) void k_mask_mark_batch(VoxBatch vb, const uint8_t* __restrict__ code,
-  const uint8_t* const* __restrict__ masks, double cell, unsigned* __restrict__ elig)
+  const uint8_t* const* __restrict__ masks, double cell, unsigned* __restrict__ elig, const unsigned* __restrict__ vox)
 {
   const VoxCapture* q = vb.cap + blockIdx.y;
   const VoxDesc* d = vb.desc + blockIdx.y;
@@ -210,6 +217,8 @@ __global__ __launch_bounds__(256) void k_mask_mark_batch(VoxBatch vb, const uint
   const int64_t stride = q->stride;
   code += q->code_off;
   elig += (int64_t) blockIdx.y * vb.slot_words;
+  if (vox)
+    vox += (int64_t) blockIdx.y * vb.slot_words;
   for (int b = 0; b < 4; b++)
   {
     if (!((m >> (8 * b)) & 0xffu))
@@ -220,7 +229,11 @@ __global__ __launch_bounds__(256) void k_mask_mark_batch(VoxBatch vb, const uint
       continue;
     const int c = (int) (cd >> 1);
     const unsigned long long pos = vox_bit(d, c, xyz + i * stride, cell);
-    atomicOr(&elig[d->word_ofs[c] + (pos >> 5)], 1u << (unsigned) (pos & 31ull));
+    const unsigned long long w = d->word_ofs[c] + (pos >> 5);
+    const unsigned bit = 1u << (unsigned) (pos & 31ull);
+    if (vox && !(vox[w] & bit))  // (agh_set_voxel_filter: the point's voxel was pruned)
+      continue;
+    atomicOr(&elig[w], bit);
   }
 }
 
@@ -353,7 +366,7 @@ int sample_mask_stage_batch(Ctx* c, const BatchMaskStage& m, hipStream_t st)
   {
     const int64_t mask_words = (m.n_max + 3 + 3) / 4;  // (aligned words that a base up to 3 bytes into one can touch)
     hipLaunchKernelGGL(k_mask_mark_batch, dim3((unsigned) ((mask_words + 255) / 256), Cy), dim3(256), 0, st, m.vb, m.code, m.mask,
-      m.cell, m.elig);
+      m.cell, m.elig, c->voxel_filter_set ? m.bitmap : (const unsigned*) nullptr);
   }
   int rc = vox_count_blocks_batch(m.vb, m.C, m.elig, m.eblk, st);
   if (rc == AGH_OK)

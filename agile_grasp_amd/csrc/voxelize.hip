@@ -14,12 +14,15 @@
 // without contraction.
 #include "agh_internal.h"
 
+#include <utility>
+
 namespace agh
 {
 
 constexpr int kPreBlock = 256;
 constexpr int kPrePerBlock = 1024;   // points per block (4 rounds of 256)
 constexpr int kWordsPerBlock = 4096; // bitmap words per block in the popcount passes (16 per thread)
+constexpr int kPruneWords = 1024;    // bitmap words per work-group of k_vox_prune (4 per thread): a quarter block
 
 // agh_localize_batch: the kernels below with a VoxBatch whose `cap` is set run one capture per blockIdx.y -- its points, its
 // descriptor, its slice of the block tables and its slot of the bitmap (vb.slot_words words each); without it (cap == nullptr,
@@ -39,6 +42,8 @@ __device__ __forceinline__ void vox_desc_init(VoxDesc* d)
     }
   d->n_kept[0] = d->n_kept[1] = 0;
   d->n_vox[0] = d->n_vox[1] = 0;
+  d->n_occupied[0] = d->n_occupied[1] = 0;
+  d->n_pruned[0] = d->n_pruned[1] = 0;
   d->error = 0;
 }
 __global__ void k_vox_init(VoxDesc* d)
@@ -426,6 +431,186 @@ __device__ void vox_totals(VoxDesc* d, const int* __restrict__ blk_prefix, long 
   }
 }
 
+// a / b and a % b for a below 2^33 by way of b's double reciprocal: the quotient estimate is off by at most one and is corrected
+// (k_vox_emit says why not three 64-bit integer divisions per voxel)
+__device__ __forceinline__ void vox_divmod(unsigned long long a, unsigned long long b, double inv_b, unsigned long long& q,
+  unsigned long long& r)
+{
+  q = (unsigned long long) ((double) a * inv_b);
+  long long rr = (long long) a - (long long) (q * b);
+  if (rr < 0)
+  {
+    q--;
+    rr += (long long) b;
+  }
+  else if (rr >= (long long) b)
+  {
+    q++;
+    rr -= (long long) b;
+  }
+  r = (unsigned long long) rr;
+}
+
+// agh_set_voxel_filter (include/agh.h; DESIGN.md, "Voxel filter"): the marked bitmap `src` without the voxels that have fewer than
+// min_neighbors other set voxels of their own camera's lattice within the integer ball of `radius`, into `dst`.  Out of place: the
+// support is counted on what k_vox_mark set, never on this kernel's output.  It works as k_vox_emit does, on a QUARTER of a
+// 4096-word block per work-group (kPruneWords, a word quad per thread: a 3 mm capture's lattice is under 200 blocks, fewer than the
+// CUs, and a voxel's count is a chain of dependent loads that only other work-groups hide): the quarter's set bits are listed in
+// LDS and dealt to the lanes, a copy of its words in LDS loses the pruned bits, and EVERY word is written -- dst is never cleared,
+// and the blocks beyond the lattice (all zero in src) come out zero.
+// For a fixed (dx, dy) the ball is one z-run of 2 h + 1 <= 9 adjacent bits, h = floor(sqrt(r^2 - dx^2 - dy^2)): clipped
+// to the row [0, nz) and to the lattice BEFORE its bit address is formed (the bits beside a row's end are another row's), read
+// from at most two adjacent words.  A clipped run lies inside the camera's lattice, so inside the slot.
+template <int R>
+__global__ __launch_bounds__(256) void k_vox_prune(const unsigned* __restrict__ src, unsigned* __restrict__ dst, VoxDesc* d,
+  int min_neighbors, VoxBatch vb)
+{
+  if (vb.cap)
+  {
+    src += (int64_t) blockIdx.y * vb.slot_words;
+    dst += (int64_t) blockIdx.y * vb.slot_words;
+    d = vb.desc + blockIdx.y;
+  }
+  constexpr int kListCap = 4096;
+  __shared__ unsigned list[kListCap];
+  __shared__ unsigned out[kPruneWords];
+  __shared__ int wsum[4];
+  __shared__ int s_pruned;
+  const size_t wg0 = (size_t) blockIdx.x * kPruneWords;
+  const size_t w0 = wg0 + (size_t) threadIdx.x * 4;
+  uint4* dst16 = reinterpret_cast<uint4*>(dst + w0);
+  const uint4 v = *reinterpret_cast<const uint4*>(src + w0);
+  const unsigned w[4] = { v.x, v.y, v.z, v.w };
+  const int cnt = __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
+  int incl = cnt;
+  for (int o = 1; o < 64; o <<= 1)
+  {
+    const int y = __shfl_up(incl, o);
+    if ((int) (threadIdx.x & 63) >= o)
+      incl += y;
+  }
+  if ((threadIdx.x & 63) == 63)
+    wsum[threadIdx.x >> 6] = incl;
+  if (threadIdx.x == 0)
+    s_pruned = 0;
+  __syncthreads();
+  int loff = incl - cnt;
+  for (int q = 0; q < (int) (threadIdx.x >> 6); q++)
+    loff += wsum[q];
+  const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  if (!total || d->error)  // (uniform: an empty block, or a lattice that does not fit -- nothing downstream reads bits then)
+  {
+    *dst16 = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  for (int j = 0; j < 4; j++)
+    out[threadIdx.x * 4 + j] = w[j];
+  const int c = wg0 >= d->word_ofs[1] ? 1 : 0;  // (camera 1 starts on a 4096-word boundary: a work-group is of one camera)
+  const long long nx = d->dim[c][0], ny = d->dim[c][1], nz = d->dim[c][2];
+  const double inv_nz = 1.0 / (double) nz, inv_ny = 1.0 / (double) ny;
+  const unsigned* lat = src + d->word_ofs[c];  // the camera's lattice, bit 0
+  const unsigned long long pos0 = ((unsigned long long) wg0 - d->word_ofs[c]) * 32ull;
+  auto test = [&](unsigned rel_bit) {  // rel_bit: bit position inside the work-group's words
+    unsigned long long t, uz, ux, uy;
+    vox_divmod(pos0 + rel_bit, (unsigned long long) nz, inv_nz, t, uz);
+    vox_divmod(t, (unsigned long long) ny, inv_ny, ux, uy);
+    const long long ix = (long long) ux, iy = (long long) uy, iz = (long long) uz;
+    int support = -1;  // (the run of dx = dy = 0 counts the voxel itself)
+    // The planes in the order dx = 0, -1, 1, -2, 2, ...: a surface voxel reaches min_neighbors in the first one or two.  Both loops
+    // are unrolled (R is the template's), so a plane's runs -- up to 2 R + 1 pairs of loads -- are in flight together; the loop
+    // leaves between planes as soon as the count is reached.
+#pragma unroll
+    for (int i = 0; i <= 2 * R; i++)
+    {
+      const int dx = (i & 1) ? -((i + 1) / 2) : i / 2;
+      const long long x = ix + dx;
+      if (x < 0 || x >= nx)
+        continue;
+      int plane = 0;
+#pragma unroll
+      for (int dy = -R; dy <= R; dy++)
+      {
+        const int rem = R * R - dx * dx - dy * dy;
+        const long long y = iy + dy;
+        if (rem < 0 || y < 0 || y >= ny)
+          continue;
+        const int h = rem >= 16 ? 4 : rem >= 9 ? 3 : rem >= 4 ? 2 : rem >= 1 ? 1 : 0;
+        const long long z0 = max(iz - h, 0ll), z1 = min(iz + h, nz - 1);
+        const int len = (int) (z1 - z0) + 1;
+        const unsigned long long b0 = (unsigned long long) ((x * ny + y) * nz + z0);
+        const unsigned long long word = b0 >> 5;
+        const unsigned sh = (unsigned) (b0 & 31ull);
+        unsigned run = lat[word] >> sh;
+        if (sh + (unsigned) len > 32u)  // (then sh > 0; the run's last bit is the lattice's: the next word is the camera's)
+          run |= lat[word + 1] << (32u - sh);
+        plane += __popc(run & ((1u << len) - 1u));
+      }
+      support += plane;
+      if (support >= min_neighbors)
+        break;
+    }
+    if (support < min_neighbors)
+    {
+      atomicAnd(&out[rel_bit >> 5], ~(1u << (rel_bit & 31u)));
+      atomicAdd(&s_pruned, 1);
+    }
+  };
+  if (total <= kListCap)
+  {
+    int q = loff;
+    for (int j = 0; j < 4; j++)
+    {
+      unsigned bits = w[j];
+      while (bits)
+      {
+        const int b = __ffs(bits) - 1;
+        bits &= bits - 1;
+        list[q++] = (unsigned) (threadIdx.x * 4 + j) * 32u + (unsigned) b;
+      }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < total; i += 256)
+      test(list[i]);
+  }
+  else  // (a dense block: every thread walks its own words)
+  {
+    __syncthreads();
+    for (int j = 0; j < 4; j++)
+    {
+      unsigned bits = w[j];
+      while (bits)
+      {
+        const int b = __ffs(bits) - 1;
+        bits &= bits - 1;
+        test((unsigned) (threadIdx.x * 4 + j) * 32u + (unsigned) b);
+      }
+    }
+  }
+  __syncthreads();
+  *dst16 = *reinterpret_cast<const uint4*>(out + threadIdx.x * 4);
+  if (threadIdx.x == 0)  // one integer atomic per work-group and counter: order free
+  {
+    atomicAdd((unsigned long long*) &d->n_occupied[c], (unsigned long long) total);
+    if (s_pruned)
+      atomicAdd((unsigned long long*) &d->n_pruned[c], (unsigned long long) s_pruned);
+  }
+}
+
+// (one instantiation per radius the setter admits)
+static void vox_prune(dim3 grid, hipStream_t st, const unsigned* src, unsigned* dst, VoxDesc* d, const agh_voxel_filter_params& fp,
+  const VoxBatch& vb)
+{
+  const int k = (int) fp.min_neighbors;
+  grid.x *= kWordsPerBlock / kPruneWords;  // (grid: the 4096-word blocks, as for k_vox_popcount)
+  switch (fp.radius)
+  {
+    case 1: hipLaunchKernelGGL(k_vox_prune<1>, grid, dim3(256), 0, st, src, dst, d, k, vb); break;
+    case 2: hipLaunchKernelGGL(k_vox_prune<2>, grid, dim3(256), 0, st, src, dst, d, k, vb); break;
+    case 3: hipLaunchKernelGGL(k_vox_prune<3>, grid, dim3(256), 0, st, src, dst, d, k, vb); break;
+    default: hipLaunchKernelGGL(k_vox_prune<4>, grid, dim3(256), 0, st, src, dst, d, k, vb); break;
+  }
+}
+
 // Emit the voxels in bitmap order = (camera, x, y, z) lexicographic order; coordinates as localization.cpp:313-324.
 // vb (a batch): capture y's voxels go to the common array from cloud_off[y] on (k_vox_chain).
 __global__ __launch_bounds__(256) void k_vox_emit(const unsigned* __restrict__ bitmap, const int* __restrict__ blk_prefix,
@@ -479,26 +664,11 @@ __global__ __launch_bounds__(256) void k_vox_emit(const unsigned* __restrict__ b
   // quotient estimate is off by at most one and is corrected) -- three 64-bit integer divisions per VOXEL, ~100 instructions
   // each on this part, made the kernel 52 us for 250k voxels
   const double inv_nz = 1.0 / (double) nz, inv_ny = 1.0 / (double) ny;
-  auto divmod = [](unsigned long long a, unsigned long long b, double inv_b, unsigned long long& q, unsigned long long& r) {
-    q = (unsigned long long) ((double) a * inv_b);
-    long long rr = (long long) a - (long long) (q * b);
-    if (rr < 0)
-    {
-      q--;
-      rr += (long long) b;
-    }
-    else if (rr >= (long long) b)
-    {
-      q++;
-      rr -= (long long) b;
-    }
-    r = (unsigned long long) rr;
-  };
   auto emit = [&](unsigned rel_bit, int64_t k) {  // rel_bit: bit position inside the work-group's 4096 words
     const unsigned long long pos = ((unsigned long long) wg0 - d->word_ofs[c]) * 32ull + rel_bit;
     unsigned long long t, uz, ux, uy;
-    divmod(pos, nz, inv_nz, t, uz);
-    divmod(t, ny, inv_ny, ux, uy);
+    vox_divmod(pos, nz, inv_nz, t, uz);
+    vox_divmod(t, ny, inv_ny, ux, uy);
     const long long iz = (long long) uz, iy = (long long) uy, ix = (long long) ux;
     out_xyz[3 * k] = (float) ((double) ix * cell + 1.0 * m0);
     out_xyz[3 * k + 1] = (float) ((double) iy * cell + 1.0 * m1);
@@ -592,6 +762,20 @@ int vox_stage2(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, dou
   VoxDesc* host_desc, bool with_lattice, int* cloud_off_out)
 {
   const int64_t cap_words = n_words;
+  c->vox_filter_captures = 0;
+  if (c->voxel_filter_set)
+  {
+    // the second bitmap, of the first one's capacity (+ its slack): made on first use, regrown with the first
+    if (!c->d_vox_pruned || c->vox_pruned_cap != cap_words)
+    {
+      c->vox_pruned_cap = 0;
+      if (int rc = dev_alloc(c, &c->d_vox_pruned, (size_t) cap_words + 4096))
+        return rc;
+      c->vox_pruned_cap = cap_words;
+    }
+    c->vox_filter_captures = 1;
+    c->vox_filter_mirror = host_desc;
+  }
   if (n == 0)
     n_words = 0;  // (no point, no bit: nothing to clear, count or emit; the block counts are not even written)
   const int64_t nb2 = n_words / kWordsPerBlock;
@@ -605,6 +789,13 @@ int vox_stage2(Ctx* c, const float* d_xyz, int64_t stride_floats, int64_t n, dou
   {
     hipLaunchKernelGGL(k_vox_mark, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, d_xyz, stride_floats, n,
       (const uint8_t*) c->d_vox_code, (const VoxDesc*) c->d_vox_desc, cell, c->d_vox_bitmap, VoxBatch{});
+    if (c->voxel_filter_set)
+    {
+      // marked -> pruned, out of place; from here on "the" bitmap of the context is the pruned one (the next cloud clears and
+      // marks it, and prunes into the other: both have the same capacity)
+      vox_prune(dim3((unsigned) nb2), st, c->d_vox_bitmap, c->d_vox_pruned, c->d_vox_desc, c->voxel_filter, VoxBatch{});
+      std::swap(c->d_vox_bitmap, c->d_vox_pruned);
+    }
     hipLaunchKernelGGL(k_vox_popcount, dim3((unsigned) nb2), dim3(256), 0, st, (const unsigned*) c->d_vox_bitmap,
       c->d_vox_blk2, VoxBatch{});
   }
@@ -637,9 +828,12 @@ int vox_count_blocks_batch(const VoxBatch& vb, int C, const unsigned* d_bitmap, 
 // counts, their scan with the descriptors' reset, camera ids, workspace, extrema); with probe, the lattices next (the caller waits
 // for them and sizes the slots); otherwise the speculative stage 2 on slots of vb.slot_words words: clear + lattice, mark,
 // popcount, scan + counts, the batch's cloud offsets into cloud_off, emit into out_xyz / out_cam.  blk: the raw block counts,
-// blk2: C x slot_words / kWordsPerBlock popcounts; nb_max, n_max: the largest capture's raw blocks and points.
+// blk2: C x slot_words / kWordsPerBlock popcounts; nb_max, n_max: the largest capture's raw blocks and points.  filter
+// (agh_set_voxel_filter; nullptr: none): k_vox_prune behind the mark, from bitmap into `pruned`, slots of the same layout, which
+// everything after it reads -- the caller swaps its two pointers once this is queued.
 int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any_finite_scan, double cell, bool probe,
-  unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st)
+  unsigned* bitmap, int* blk, int* blk2, uint8_t* code, float* out_xyz, int32_t* out_cam, int* cloud_off, hipStream_t st,
+  unsigned* pruned, const agh_voxel_filter_params* filter)
 {
   const unsigned Cy = (unsigned) C;
   if (nb_max > 0 && any_finite_scan)
@@ -663,6 +857,11 @@ int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any
   if (n_max > 0)
     hipLaunchKernelGGL(k_vox_mark, dim3((unsigned) ((n_max + 255) / 256), Cy), dim3(256), 0, st, (const float*) nullptr, (int64_t) 0,
       (int64_t) 0, (const uint8_t*) code, (const VoxDesc*) vb.desc, cell, bitmap, vb);
+  if (filter)  // (every slot, also with n_max == 0: the pruned slots are never cleared)
+  {
+    vox_prune(dim3((unsigned) nb2, Cy), st, bitmap, pruned, vb.desc, *filter, vb);
+    bitmap = pruned;
+  }
   hipLaunchKernelGGL(k_vox_popcount, dim3((unsigned) nb2, Cy), dim3(256), 0, st, (const unsigned*) bitmap, blk2, vb);
   hipLaunchKernelGGL(k_vox_scan, dim3(1, Cy), dim3(1024), 0, st, blk2, (int64_t) 0, (long long*) nullptr, (VoxDesc*) nullptr,
     vb.desc, vb.host_desc, (int*) nullptr, vb);
@@ -673,3 +872,89 @@ int vox_batch(const VoxBatch& vb, int C, int64_t nb_max, int64_t n_max, bool any
 }
 
 }  // namespace agh
+
+using namespace agh;
+
+extern "C" {
+
+// ---- the voxel filter's setting (include/agh.h): host-side, the two ints travel as k_vox_prune's arguments ----
+void agh_default_voxel_filter_params(agh_voxel_filter_params* p)
+{
+  if (!p)
+    return;
+  p->radius = 2;
+  p->min_neighbors = 4;
+}
+
+int agh_set_voxel_filter(agh_ctx* ctx, const agh_voxel_filter_params* fp)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_set_voxel_filter"))
+    return AGH_ERR_STATE;
+  if (!fp)
+  {
+    c->voxel_filter_set = false;
+    return AGH_OK;
+  }
+  auto bad = [c](const char* what) {
+    c->err = std::string("agh_set_voxel_filter: ") + what;
+    return AGH_ERR_INVALID_ARGUMENT;
+  };
+  if (fp->radius < 1 || fp->radius > 4)
+    return bad("radius must be 1 .. 4");
+  static const int ball[5] = { 1, 7, 33, 123, 257 };  // positions of the integer ball, its centre among them
+  if (fp->min_neighbors < 1 || fp->min_neighbors > ball[fp->radius] - 1)
+    return bad("min_neighbors must be 1 .. B(radius) - 1 (B = 7, 33, 123, 257)");
+  c->voxel_filter = *fp;
+  c->voxel_filter_set = true;
+  return AGH_OK;
+}
+
+int agh_get_voxel_filter(agh_ctx* ctx, agh_voxel_filter_params* out)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;  // (host-side: allowed while a localize chain is in flight)
+  if (!c->voxel_filter_set)
+    return 0;
+  if (!out)
+  {
+    c->err = "agh_get_voxel_filter: out is NULL";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  *out = c->voxel_filter;
+  return 1;
+}
+
+int agh_get_voxel_filter_counts(agh_ctx* ctx, agh_voxel_filter_counts* out, int32_t cap_captures)
+{
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  Ctx* c = &ctx->c;
+  if (refuse_mid_chain(c, "agh_get_voxel_filter_counts"))
+    return AGH_ERR_STATE;
+  if (c->vox_filter_captures == 0)
+    return 0;
+  if (cap_captures < c->vox_filter_captures || !out)
+  {
+    c->err = "agh_get_voxel_filter_counts: room for " + std::to_string(c->vox_filter_captures) + " captures is needed";
+    return AGH_ERR_CAPACITY;
+  }
+  AGH_HIPCHK(c, hipSetDevice(c->device));
+  AGH_HIPCHK(c, hipStreamSynchronize(c->stream));  // (the mirrors are written by the voxeliser's second scan)
+  for (int k = 0; k < c->vox_filter_captures; k++)
+  {
+    const VoxDesc& h = c->vox_filter_mirror[k];
+    for (int cam = 0; cam < 2; cam++)
+    {
+      out[k].n_occupied[cam] = (int64_t) h.n_occupied[cam];
+      out[k].n_pruned[cam] = (int64_t) h.n_pruned[cam];
+      out[k].n_kept[cam] = (int64_t) h.n_vox[cam];
+    }
+  }
+  return c->vox_filter_captures;
+}
+
+}  // extern "C"

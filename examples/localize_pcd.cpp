@@ -3,8 +3,8 @@
 //
 //   g++ -std=c++11 -O2 -Iinclude examples/localize_pcd.cpp -o localize_pcd -Lagile_grasp_amd/lib -lagile_grasp_hip
 //       -Wl,-rpath,$PWD/agile_grasp_amd/lib -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
-//   ./localize_pcd [--filters-boundaries] [--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd> [right.pcd]
-//                  [num_samples] [min_inliers]
+//   ./localize_pcd [--filters-boundaries] [--voxel-filter R,K] [--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd>
+//                  [right.pcd] [num_samples] [min_inliers]
 //
 // Parameters are the node's defaults (find_grasps.cpp:10-21): finger width 0.01, outer diameter 0.09, hand depth 0.06,
 // hand height 0.02, init bite 0.01, 2000 samples, workspace [0.65 0.9 -0.1 0.1 -0.2 1.0], min_inliers 3, camera poses
@@ -14,6 +14,8 @@
 // the connected components of the points above it (Localization::localizeHandlesClustered), num_samples samples are drawn on
 // EACH of them and the handles are printed per object; --cluster-tolerance t (metres, default 0.01) is the distance up to which
 // two voxels belong to one object.
+// --voxel-filter R,K prunes, on the device, the voxels with fewer than K occupied voxels of their own camera within R voxels
+// (Localization::setVoxelFilter): stray returns in free space, which would veto placements beside them.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -33,12 +35,16 @@ int main(int argc, char** argv)
     argv++;
     argc--;
   }
-  bool table = false;
+  bool table = false, voxel_filter = false;
+  int vf_radius = 0, vf_neighbors = 0;
   double plane[4] = { 0.0, 0.0, 1.0, 0.0 }, cluster_tolerance = 0.01;
-  while (argc > 2 && (std::strcmp(argv[1], "--table") == 0 || std::strcmp(argv[1], "--cluster-tolerance") == 0))
+  while (argc > 2 && (std::strcmp(argv[1], "--table") == 0 || std::strcmp(argv[1], "--cluster-tolerance") == 0 ||
+                      std::strcmp(argv[1], "--voxel-filter") == 0))
   {
     if (std::strcmp(argv[1], "--table") == 0)
       table = std::sscanf(argv[2], "%lf,%lf,%lf,%lf", &plane[0], &plane[1], &plane[2], &plane[3]) == 4;
+    else if (std::strcmp(argv[1], "--voxel-filter") == 0)
+      voxel_filter = std::sscanf(argv[2], "%d,%d", &vf_radius, &vf_neighbors) == 2;
     else
       cluster_tolerance = std::atof(argv[2]);
     argv[2] = argv[0];
@@ -47,8 +53,8 @@ int main(int argc, char** argv)
   }
   if (argc < 3)
   {
-    std::printf("usage: %s [--filters-boundaries] [--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd> [right.pcd] "
-                "[num_samples] [min_inliers]\n", argv[0]);
+    std::printf("usage: %s [--filters-boundaries] [--voxel-filter R,K] [--table a,b,c,d [--cluster-tolerance t]] <svm file> "
+                "<left.pcd> [right.pcd] [num_samples] [min_inliers]\n", argv[0]);
     return 2;
   }
   const std::string svm = argv[1], left = argv[2], right = argc > 3 ? argv[3] : "";
@@ -76,6 +82,14 @@ int main(int argc, char** argv)
   loc.setHandDepth(0.06);
   loc.setInitBite(0.01);
   loc.setHandHeight(0.02);
+  if (voxel_filter)
+  {
+    agh_voxel_filter_params fp;
+    fp.radius = vf_radius;
+    fp.min_neighbors = vf_neighbors;
+    if (!loc.setVoxelFilter(fp))  // (the library's message says which field it refused)
+      return 1;
+  }
 
   if (table)
   {

@@ -276,11 +276,11 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a begin).
  * Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_depth_stage,
  * agh_localize_end,
- * agh_get_cloud_cam_origins, agh_get_depth_filter, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
+ * agh_get_cloud_cam_origins, agh_get_depth_filter, agh_get_voxel_filter, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
  * agh_destroy, the host-side counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats, agh_get_grid_desc) and the
  * communicator's bookkeeping (agh_comm_rank, agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault,
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
- * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_set_depth_filter, agh_preprocess*, agh_find_hands*, agh_classify*,
+ * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_set_depth_filter, agh_set_voxel_filter, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
  * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled*, agh_localize_depth_labeled*,
  * agh_localize_clustered*, agh_localize_depth_clustered*, agh_localize_clustered_fit*, agh_localize_depth_clustered_fit*,
@@ -293,7 +293,7 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info,
  * agh_get_cluster_labels, agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts,
  * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels, agh_get_batch_plane_fit,
- * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts and every getter of device results (frames, normals,
+ * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts, agh_get_voxel_filter_counts and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -730,8 +730,8 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * agh_localize_depth_batch_clustered_fit_begin*;
  * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info, agh_get_cluster_labels,
  * agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info,
- * agh_get_batch_cluster_labels, agh_get_batch_plane_fit, agh_get_batch_plane_fit_candidates, agh_set_depth_filter and
- * agh_get_depth_filter_counts are refused as well),
+ * agh_get_batch_cluster_labels, agh_get_batch_plane_fit, agh_get_batch_plane_fit_candidates, agh_set_depth_filter,
+ * agh_get_depth_filter_counts, agh_set_voxel_filter and agh_get_voxel_filter_counts are refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
@@ -834,8 +834,8 @@ int agh_deproject_batch(agh_ctx* ctx, const agh_depth_image* images, const int32
  * follow capture k - 1's): n_valid = n_out_of_range + n_unsupported + n_kept.  Returns the number of views, or 0 if the last
  * deprojection ran unfiltered (or none ran); AGH_ERR_CAPACITY if cap_views is smaller; AGH_ERR_STATE mid-chain.  One small copy
  * and one synchronisation.
- * Not built: temporal filtering over frames, hole filling, lens distortion, per-image parameters, a filter for the points
- * forms. */
+ * Not built: temporal filtering over frames, hole filling, lens distortion, per-image parameters (the points forms have a
+ * filter of their own: agh_set_voxel_filter below). */
 typedef struct agh_depth_filter_params
 {
   int32_t radius;        /* 1 or 2: window (2 radius + 1)^2 */
@@ -855,6 +855,62 @@ void agh_default_depth_filter_params(agh_depth_filter_params* p);  /* radius 1; 
 int agh_set_depth_filter(agh_ctx* ctx, const agh_depth_filter_params* fp);
 int agh_get_depth_filter(agh_ctx* ctx, agh_depth_filter_params* out);
 int agh_get_depth_filter_counts(agh_ctx* ctx, agh_depth_filter_counts* out, int32_t cap_views);
+
+/* A VOXEL FILTER for every call that voxelises: the depth filter above only helps callers who hand over depth images.  A cloud
+ * from a stereo matcher, a lidar, a fused map or a driver that already deprojected carries stray returns in free space; each
+ * becomes a voxel of its own, in the space where the hand sweep tests finger clearance, and vetoes a placement.
+ * agh_set_voxel_filter prunes voxels without enough occupied neighbours inside the voxeliser, on the bitmap it already holds
+ * (k_vox_prune, between the mark and the count): no host pass over the points, no new agh_localize_* variant, and everything
+ * downstream simply sees a smaller cloud.
+ *  1. The lattice of each camera -- its origin (the per-camera minimum of the kept raw points), its dims, the voxel of a point
+ *     -- is the unfiltered voxeliser's, unchanged: the filter never moves the minimum.  The result is the UNFILTERED voxel list
+ *     with rows taken out: same order, same float32 coordinates for the survivors.  It is NOT the voxelisation of the raw points
+ *     that survive, whose minimum, and with it every coordinate, could differ.
+ *  2. Let O_c be the voxels camera c's kept points occupy.  The support of v = (ix, iy, iz) in O_c is the number of w in O_c,
+ *     w != v, with dx^2 + dy^2 + dz^2 <= radius^2 in voxel units (an integer ball of B(radius) = 7, 33, 123, 257 positions for
+ *     radius 1, 2, 3, 4).  Positions outside the lattice (a coordinate < 0 or >= its dim) never support.  The two cameras of a
+ *     capture never support one another (their lattices have different origins), nor do the captures of a batch.
+ *  3. v is kept iff its support is at least min_neighbors.  Support is counted on O_c, never on the filter's own output: one
+ *     pass, independent of any order, not iterated.
+ *  4. After the stage THE voxel bitmap is the pruned one: the voxel counts (n_voxels), the cloud (agh_get_cloud), the drawn
+ *     samples' strata, masks, labels, clusters (agh_get_cluster_labels) and the plane fit all refer to the survivors.
+ *  5. Masks and labels: a voxel is eligible, or carries object j, iff a masked / labelled kept raw point falls into a SURVIVING
+ *     voxel; a point whose voxel was pruned marks nothing.
+ *  6. The setting is sticky, per context, until it is cleared (NULL) or replaced, across clouds, batches and chains.  With a
+ *     filter set EVERY call that voxelises applies it: agh_preprocess*, every agh_localize* form on points and on depth images
+ *     (there it runs after the depth filter, if both are set), every batch form including _begin / _stage / _end streams, and the
+ *     repeat inside a call after the lattice outgrew the bitmap.  agh_set_cloud* takes clouds as they are.  It costs no device
+ *     work at set time (the two ints travel as kernel arguments); with no filter set every launch is exactly what it was.
+ *  7. agh_set_voxel_filter checks both fields: radius 1 .. 4; min_neighbors 1 .. B(radius) - 1.  A violation returns
+ *     AGH_ERR_INVALID_ARGUMENT, the text names the field, and the filter held before stays in force.  Mid-chain (single or
+ *     batch) it returns AGH_ERR_STATE without touching the chain.  agh_get_voxel_filter copies the filter held and returns 1, or
+ *     returns 0 if none is set (host-side, allowed mid-chain).
+ *  8. agh_get_voxel_filter_counts: per capture of the last voxelisation, if it ran filtered: n_occupied = n_pruned + n_kept per
+ *     camera, n_kept being the voxel count.  Returns the number of captures (1 for the single forms), or 0 if it ran unfiltered
+ *     (or none ran); AGH_ERR_CAPACITY if cap_captures is smaller; AGH_ERR_STATE mid-chain.  One synchronisation, no copy: the
+ *     counts ride in the voxeliser's pinned descriptor.
+ *  9. A capture whose voxels are all pruned behaves as one whose points all fall outside the workspace: zero voxels, empty
+ *     lists, no error; the other captures of a batch are untouched.
+ * 10. The lattice limit stays 2^28 words.  With a filter set the context holds a SECOND bitmap of the first one's capacity (the
+ *     voxeliser's bitmap memory doubles: 2 x 4 bytes x the lattice's words, per slot of a batch), made by the first filtered
+ *     voxelisation, dropped and regrown with the first; AGH_ERR_HIP with hipMalloc's text if it does not fit.
+ * Not built: iterated or statistical (mean-distance) removal; support across cameras or captures; per-capture parameters in a
+ * batch; a filter for agh_set_cloud*, whose clouds the caller has voxelised. */
+typedef struct agh_voxel_filter_params
+{
+  int32_t radius;         /* 1 .. 4, in voxels */
+  int32_t min_neighbors;  /* 1 .. B(radius) - 1;  B = 7, 33, 123, 257 for radius 1, 2, 3, 4 */
+} agh_voxel_filter_params;
+typedef struct agh_voxel_filter_counts
+{
+  int64_t n_occupied[2];  /* voxels the kept points occupy, per camera */
+  int64_t n_pruned[2];
+  int64_t n_kept[2];      /* n_occupied = n_pruned + n_kept; the voxel count per camera */
+} agh_voxel_filter_counts;
+void agh_default_voxel_filter_params(agh_voxel_filter_params* p);  /* radius 2; min_neighbors 4 */
+int agh_set_voxel_filter(agh_ctx* ctx, const agh_voxel_filter_params* fp);
+int agh_get_voxel_filter(agh_ctx* ctx, agh_voxel_filter_params* out);
+int agh_get_voxel_filter_counts(agh_ctx* ctx, agh_voxel_filter_counts* out, int32_t cap_captures);
 
 /* The batch chains with every capture's samples drawn UNDER ITS OWN MASK: a cell with several sensor pairs and one detector per
  * sensor hands over, per rig, a capture and an object mask, and wants handles on the masked object of every rig from one call.

@@ -1279,6 +1279,50 @@ public:
       out = depth_filter_;
     return depth_filter_set_;
   }
+  /** Additional: the voxel filter (agh_set_voxel_filter) -- every later call of this search that voxelises a capture (points
+   *  or depth images, single or batch) prunes the voxels with fewer than min_neighbors occupied voxels of their own camera
+   *  within `radius` voxels, on the device.  Sticky until clearVoxelFilter, also across a context this search re-creates.
+   *  Refused while a chain is pending.
+   *  @return false (after printing) on error; the filter held before stays in force */
+  bool setVoxelFilter(const agh_voxel_filter_params& fp)
+  {
+    if (!ensureContext())
+      return false;
+    if (agh_set_voxel_filter(ctx_, &fp) != AGH_OK)
+    {
+      fail("agh_set_voxel_filter");
+      return false;
+    }
+    voxel_filter_ = fp;
+    voxel_filter_set_ = true;
+    return true;
+  }
+  bool clearVoxelFilter()
+  {
+    if (ctx_ && agh_set_voxel_filter(ctx_, nullptr) != AGH_OK)
+    {
+      fail("agh_set_voxel_filter");
+      return false;
+    }
+    voxel_filter_set_ = false;
+    return true;
+  }
+  /** the filter held (agh_get_voxel_filter); false: none */
+  bool voxelFilter(agh_voxel_filter_params& out) const
+  {
+    if (voxel_filter_set_)
+      out = voxel_filter_;
+    return voxel_filter_set_;
+  }
+  /** agh_get_voxel_filter_counts: per capture of the last voxelisation what the filter did; empty if that voxelisation ran
+   *  without a filter, if there was none, or while a chain is pending */
+  std::vector<agh_voxel_filter_counts> voxelFilterCounts()
+  {
+    std::vector<agh_voxel_filter_counts> out(64);
+    const int n = ctx_ ? agh_get_voxel_filter_counts(ctx_, out.data(), (std::int32_t) out.size()) : 0;
+    out.resize(n > 0 ? (std::size_t) n : 0);
+    return out;
+  }
   /** agh_get_depth_filter_counts: per view of the last deprojection, in launch order, what the filter did; empty if that
    *  deprojection ran without a filter, if there was none, or while a chain is pending */
   std::vector<agh_depth_filter_counts> depthFilterCounts()
@@ -1623,12 +1667,19 @@ private:
       fail("agh_set_depth_filter");
       return false;
     }
+    if (voxel_filter_set_ && agh_set_voxel_filter(ctx_, &voxel_filter_) != AGH_OK)
+    {
+      fail("agh_set_voxel_filter");
+      return false;
+    }
     return true;
   }
 
   agh_ctx* ctx_;
   agh_depth_filter_params depth_filter_ = agh_depth_filter_params();  // setDepthFilter
   bool depth_filter_set_ = false;
+  agh_voxel_filter_params voxel_filter_ = agh_voxel_filter_params();  // setVoxelFilter
+  bool voxel_filter_set_ = false;
   std::int64_t searched_n_ = 0;
   // What an End reads of the chain in flight.  The rule for every Begin: these (and last_samples_, sized by chainBegun for
   // localizeEnd) are written only after the library's begin has returned AGH_OK, so a Begin that fails for any reason -- a

@@ -635,6 +635,43 @@ public:
       out = depth_filter_;
     return depth_filter_set_;
   }
+  /** Additional: the voxel filter of every call that voxelises a capture (agh_set_voxel_filter; agh_default_voxel_filter_params
+   *  fills a record: radius 2 voxels, 4 neighbours).  With a filter set the voxeliser prunes, on the device, the voxels with fewer
+   *  occupied neighbours of their own camera -- stray returns in free space --, for points and depth images alike.  Sticky until
+   *  clearVoxelFilter, also across the setters that re-create the search.  Refused while a chain is pending.
+   *  @return false (after printing) on error; the filter held before stays in force */
+  bool setVoxelFilter(const agh_voxel_filter_params& fp)
+  {
+    if (chainPending("setVoxelFilter"))
+      return false;
+    ensureSearch();
+    if (!search_->setVoxelFilter(fp))
+      return false;
+    voxel_filter_ = fp;
+    voxel_filter_set_ = true;
+    return true;
+  }
+  bool clearVoxelFilter()
+  {
+    if (chainPending("clearVoxelFilter") || (search_ && !search_->clearVoxelFilter()))
+      return false;
+    voxel_filter_set_ = false;
+    return true;
+  }
+  /** the filter held; false: none */
+  bool voxelFilter(agh_voxel_filter_params& out) const
+  {
+    if (voxel_filter_set_)
+      out = voxel_filter_;
+    return voxel_filter_set_;
+  }
+  /** What the filter did in the last call that voxelised (agh_get_voxel_filter_counts): one record per capture; empty if that
+   *  call ran without a filter, if there was none, or while a chain is pending. */
+  std::vector<agh_voxel_filter_counts> voxelFilterCounts()
+  {
+    return search_ ? search_->voxelFilterCounts() : std::vector<agh_voxel_filter_counts>();
+  }
+
   /** What the filter did in the last depth call (agh_get_depth_filter_counts): one record per image, in capture order; empty if
    *  that call ran without a filter, if there was none, or while a chain is pending. */
   std::vector<agh_depth_filter_counts> depthFilterCounts()
@@ -1439,6 +1476,8 @@ private:
       search_->setSampleSeed(sample_seed_);
     if (depth_filter_set_)
       search_->setDepthFilter(depth_filter_);
+    if (voxel_filter_set_)
+      search_->setVoxelFilter(voxel_filter_);
   }
 
   int num_threads_, num_samples_;
@@ -1447,6 +1486,8 @@ private:
   agh_plane_fit_params plane_fit_;  // setPlaneFitParams
   agh_depth_filter_params depth_filter_ = agh_depth_filter_params();  // setDepthFilter
   bool depth_filter_set_ = false;
+  agh_voxel_filter_params voxel_filter_ = agh_voxel_filter_params();  // setVoxelFilter
+  bool voxel_filter_set_ = false;
   int plotting_mode_;
   Matrix4d cam_tf_left_, cam_tf_right_;
   VectorXd workspace_;
