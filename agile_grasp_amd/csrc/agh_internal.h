@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -207,6 +208,118 @@ inline BoundaryBox boundary_box(const double* ws)  // ws == nullptr: off
   return b;
 }
 
+// ---- what a localize chain draws its samples under (include/agh.h: agh_localize_masked*, _labeled*, _clustered*, _clustered_fit*
+// and their batch forms), described once for the single chain and the batch chain ----
+enum class SourceKind : int
+{
+  None = 0,        // the whole cloud (or an explicit list)
+  Mask,            // a byte per raw point, non-zero: eligible
+  Labels,          // a byte per raw point, 1 .. n_objects: a list per object
+  Clusters,        // no bytes: a list per connected component above a support plane
+  FittedClusters   // ... above a plane the chain fits itself (plane_fit.hip; the caller's plane is not read)
+};
+// As the entry points take it: arrays of one entry per capture.  The single chain is the view of one capture, its entry points
+// pass pointers to their own scalars.  Host bytes and all image masks are copied into a buffer of the chain; device point bytes
+// are read in place (sample_source_to_device).
+struct SampleSource
+{
+  SourceKind kind = SourceKind::None;
+  const uint8_t* const* points = nullptr;       // points form: capture k's bytes, one per raw point
+  const agh_sample_mask* images = nullptr;      // depth form: one record per image, parallel to the DepthCaptures' flat array
+  const int32_t* n_objects = nullptr;           // Labels: capture k's objects
+  const agh_cluster_params* cluster = nullptr;  // Clusters, FittedClusters: capture k's record (max_objects lists)
+  const agh_plane_fit_params* fit = nullptr;    // FittedClusters: capture k's record
+  bool on_device = false;
+  const char* who = nullptr;                    // the entry point, for the error texts
+  bool has_bytes() const { return kind == SourceKind::Mask || kind == SourceKind::Labels; }
+  bool per_object() const { return kind >= SourceKind::Labels; }  // (a list per (capture, object))
+  bool clustered() const { return kind >= SourceKind::Clusters; }
+  bool fitted() const { return kind == SourceKind::FittedClusters; }
+  int32_t objects(int k) const { return clustered() ? cluster[k].max_objects : n_objects[k]; }
+};
+static_assert(sizeof(agh_label_image) == sizeof(agh_sample_mask) && offsetof(agh_label_image, data) == offsetof(agh_sample_mask, data) &&
+                offsetof(agh_label_image, row_stride_bytes) == offsetof(agh_sample_mask, row_stride_bytes),
+  "a label image is read as a sample mask whose bytes are labels");
+inline SampleSource mask_source(const uint8_t* const* points, const agh_sample_mask* images, bool on_device, const char* who)
+{
+  return SampleSource{ SourceKind::Mask, points, images, nullptr, nullptr, nullptr, on_device, who };
+}
+inline SampleSource label_source(const uint8_t* const* points, const agh_label_image* images, const int32_t* n_objects, bool on_device,
+  const char* who)
+{
+  return SampleSource{ SourceKind::Labels, points, reinterpret_cast<const agh_sample_mask*>(images), n_objects, nullptr, nullptr, on_device, who };
+}
+inline SampleSource cluster_source(const agh_cluster_params* cp, const agh_plane_fit_params* fp, bool fitted, const char* who)
+{
+  return SampleSource{ fitted ? SourceKind::FittedClusters : SourceKind::Clusters, nullptr, nullptr, nullptr, cp, fp, false, who };
+}
+// Captures given as depth images (include/agh.h, agh_localize_depth*, agh_localize_depth_batch*): the flat array in capture order,
+// capture k's are the next n_images[k].  k_deproject* (depth.hip) fills the context's raw buffer; from there on a chain is the
+// points chain's.
+struct DepthCaptures
+{
+  const agh_depth_image* images;
+  const int32_t* n_images;
+  bool on_device;
+  const char* who;  // the entry point, for the error texts
+};
+// A fitted chain finds the plane itself: the caller's is neither read nor validated, and the record the chain keeps (and uploads)
+// carries this one until the fit's.
+inline void placeholder_plane(agh_cluster_params* cp)
+{
+  cp->plane[0] = cp->plane[1] = cp->plane[3] = 0.0;
+  cp->plane[2] = 1.0;
+}
+// The name of a chain in the texts of the errors found behind its synchronisation.
+inline const char* chain_name(bool single, SourceKind kind)
+{
+  switch (kind)
+  {
+    case SourceKind::Labels: return single ? "agh_localize_labeled" : "agh_localize_batch_labeled";
+    case SourceKind::Clusters: return single ? "agh_localize_clustered" : "agh_localize_batch_clustered";
+    case SourceKind::FittedClusters: return single ? "agh_localize_clustered" : "agh_localize_batch_clustered_fit";
+    default: return single ? "agh_localize" : "agh_localize_batch";
+  }
+}
+// The device-resident form of a source, which a chain keeps for a repeat of the whole call: where each capture's bytes lie (the
+// chain's own copy, or the caller's device memory) and copies of the caller's records.
+struct StoredSource
+{
+  SourceKind kind = SourceKind::None;
+  const char* who = "";                   // chain_name
+  std::vector<const uint8_t*> d_bytes;    // has_bytes: per capture (sample_source_to_device)
+  std::vector<int32_t> n_objects;         // per_object: per capture
+  std::vector<agh_cluster_params> cluster;
+  std::vector<agh_plane_fit_params> fit;
+  bool per_object() const { return kind >= SourceKind::Labels; }
+  bool clustered() const { return kind >= SourceKind::Clusters; }
+  bool fitted() const { return kind == SourceKind::FittedClusters; }
+  // (src: null for a chain without a source)
+  void keep(const SampleSource* src, int C, bool single)
+  {
+    *this = StoredSource();
+    kind = src ? src->kind : SourceKind::None;
+    who = chain_name(single, kind);
+    if (!src)
+      return;
+    for (int k = 0; k < C && src->per_object(); k++)
+      n_objects.push_back(src->objects(k));
+    if (src->clustered())
+      cluster.assign(src->cluster, src->cluster + C);
+    if (src->fitted())
+    {
+      fit.assign(src->fit, src->fit + C);
+      for (agh_cluster_params& q : cluster)
+        placeholder_plane(&q);
+    }
+  }
+  // the source a repeat re-enters with
+  SampleSource view() const
+  {
+    return SampleSource{ kind, d_bytes.data(), nullptr, n_objects.data(), cluster.data(), fit.data(), true, who };
+  }
+};
+
 // agh_localize_begin / _stage / _end (api.hip): the one chain in flight and the capture staged for the next one
 struct LocalizeState
 {
@@ -221,21 +334,12 @@ struct LocalizeState
   agh_localize_params lp{};   // (sample_idx cleared: the list lives in the pinned staging)
   const float* d_raw = nullptr;  // where the chain read the raw capture (the context's raw buffer or the caller's device memory)
   int64_t dev_stride = 0, n_raw = 0;
-  // agh_localize_masked* (sample_mask.hip): the chain draws its samples among the eligible voxels of a mask, one byte per raw
-  // point, packed -- in the context's d_mask or in the caller's device memory, where a repeat of the whole call reads it again
-  bool masked = false;
-  const uint8_t* d_mask = nullptr;
-  // agh_localize_labeled* (sample_labels.hip): the bytes are labels, 1 .. n_objects, and the chain draws S samples for each
-  // object (0: a mask); from the classifier on its tail is the batch chain's, one list per object (localize_batch.hip)
-  int32_t n_objects = 0;
-  // agh_localize_clustered* (sample_cluster.hip): the objects are connected components of the cloud; n_objects = max_objects, no
-  // label bytes; a repeat of the whole call re-enters with these
-  bool clustered = false;
-  agh_cluster_params cluster{};
-  // agh_localize_clustered_fit* (plane_fit.hip): the support plane is fitted on the device in front of the cluster stage; a
-  // repeat of the whole call re-enters with these too
-  bool fitted = false;
-  agh_plane_fit_params fit{};
+  // What the samples are drawn under, as a repeat of the whole call re-enters with it: a mask (sample_mask.hip) in the context's
+  // d_mask or in the caller's device memory; labels there (sample_labels.hip), S samples for each object; the cloud's own
+  // components (sample_cluster.hip), above a given or a fitted plane (plane_fit.hip).  From the classifier on the tail of a chain
+  // with a list per object is the batch chain's (localize_batch.hip).
+  StoredSource source;
+  int objects() const { return source.per_object() ? source.n_objects[0] : 0; }  // the lists of such a chain (0: the one list)
   // agh_localize_batch_begin / _stage / _end (localize_batch.hip) share the one chain and the one staged set of the context
   bool batch = false;         // the chain in flight is a batch's (agh_localize_batch_end collects it, not agh_localize_end)
   bool staged = false;        // stage_captures: a set of captures is (being) copied into d_stage_xyz, packed end to end,
@@ -273,6 +377,27 @@ struct LocalizeState
 
 struct PlaneState;
 struct LocalizeBatchState;
+
+// What the last chain a context collected left for the getters of the chains (agh_get_sample_mask_count, _label_counts,
+// _cluster_info, _cluster_labels, _plane_fit*, and the agh_get_batch_* ones).  Value-initialised: no chain, or one that left
+// nothing.  agh_localize_end and agh_localize_batch_end start with `results = ChainResults{}` and fill it behind their
+// synchronisation; a getter answers for exactly one (kind, batch) -- a single getter refuses after a batch of its kind, and the
+// reverse.
+struct ChainResults
+{
+  SourceKind kind = SourceKind::None;
+  bool batch = false;
+  int32_t captures = 0;                   // a batch's captures (the single chain: 1)
+  int32_t lists = 0;                      // the entries of counts: 1 (a single mask), the captures (a masked batch), else the lists
+  int64_t counts[kMaxClouds] = {};        // eligible voxels: M, M_k, or per list M_j / M_{k,j} (a clustered chain: the objects' sizes)
+  int64_t nv = 0;                         // clustered: the voxels of the bound cloud (batch), which agh_get_*cluster_labels copies
+  int64_t cluster_info[kMaxClouds][4] = {};  // clustered, per capture: foreground, components, objects, qualifying
+  int32_t cluster_ids[kMaxClouds] = {};      // ... per list: the smallest (capture-local) voxel index of the object, -1: none
+  int32_t fit_candidates[kMaxClouds] = {};   // fitted, per capture: n_candidates
+  agh_plane_fit_result fit_results[kMaxClouds] = {};  // ... and the result record
+  bool is(SourceKind k, bool of_batch) const { return kind == k && batch == of_batch; }
+  bool is_clustered(bool of_batch) const { return kind >= SourceKind::Clusters && batch == of_batch; }
+};
 
 struct Ctx
 {
@@ -352,7 +477,6 @@ struct Ctx
   long long* d_mask_total = nullptr;  // M, the eligible voxels
   int32_t* d_mask_list = nullptr;  // E: the eligible voxel indices, ascending
   int64_t mask_list_cap = 0;
-  int64_t mask_count = -1;         // M of the last chain agh_localize_end collected, -1 if that chain had no mask
   // label images (sample_labels.hip), allocated by the first labelled call; the lists E_j share d_mask_list
   unsigned* d_label_rank = nullptr;   // per bitmap word: the voxel bits in front of it inside its 4096-word block
   int64_t label_rank_cap = 0;         // words
@@ -362,8 +486,6 @@ struct Ctx
   int64_t label_group_cap = 0;
   long long* d_label_totals = nullptr;  // kMaxClouds: the M_j
   long long* h_label_counts = nullptr;  // pinned: the M_j, written by the chain
-  int32_t label_objects = 0;          // n_objects of the last chain collected if it was labelled, else 0
-  int64_t label_counts[kMaxClouds] = {};  // ... and its M_j
   // clusters as the label source (sample_cluster.hip), allocated by the first clustered call
   int* d_cluster_parent = nullptr;    // per voxel: the union-find's parent, then its root (-1: background)
   int* d_cluster_size = nullptr;      // per voxel: a root's size, then -1 - rank for the roots that are objects
@@ -371,33 +493,10 @@ struct Ctx
   int64_t cluster_cap = 0;
   unsigned long long* d_cluster_counts = nullptr;  // foreground voxels, components
   long long* h_cluster_table = nullptr;  // pinned: counts, M_j and ids, written by the chain (k_cluster_select)
-  int32_t cluster_objects = 0;        // max_objects of the last chain collected if it was clustered, else 0
-  int64_t cluster_nv = 0;             // ... its voxel count
-  int64_t cluster_info[4] = {};       // ... foreground, components, objects, qualifying
-  int64_t cluster_sizes[kMaxClouds] = {};  // ... M_j
-  int32_t cluster_ids[kMaxClouds] = {};    // ... and the smallest voxel index of object j (-1: none)
   // a fitted plane for the clustered chain (plane_fit.hip), allocated by the first fitted call: nothing per point
   void* d_fit = nullptr;                       // candidates' indices and planes, counts, sums and the ClusterDev record (PlaneFitBuffers)
   agh_plane_fit_result* h_fit_result = nullptr;  // pinned: written by the chain (k_fit_finish)
-  bool fit_valid = false;                      // the last chain collected was a fitted one
-  int32_t fit_candidates = 0;                  // ... its n_candidates
-  agh_plane_fit_result fit_result{};           // ... and its result
-  int32_t batch_mask_captures = 0;    // n_captures of the last chain collected if it was a masked batch, else 0
-  int64_t batch_mask_counts[kMaxClouds] = {};  // ... and its M_k
-  int32_t batch_label_lists = 0;      // the lists of the last chain collected if it was a labelled batch, else 0
-  int64_t batch_label_counts[kMaxClouds] = {};  // ... and its M_{k,j}, in list order
-  // agh_localize_batch_clustered*: the captures of the last chain collected if it was a clustered batch, else 0; its lists, the
-  // voxels of its bound batch, per capture foreground / components / objects / qualifying, per list M_l and the capture-local id
-  int32_t batch_cluster_captures = 0, batch_cluster_lists = 0;
-  int64_t batch_cluster_nv = 0;
-  int64_t batch_cluster_info[kMaxClouds][4] = {};
-  int64_t batch_cluster_sizes[kMaxClouds] = {};
-  int32_t batch_cluster_ids[kMaxClouds] = {};
-  // agh_localize_batch_clustered_fit*: the captures of the last chain collected if it was a fitted clustered batch, else 0 (the
-  // single chains leave it: it counts only beside batch_cluster_captures), each capture's n_candidates and result record
-  int32_t batch_fit_captures = 0;
-  int32_t batch_fit_candidates[kMaxClouds] = {};
-  agh_plane_fit_result batch_fit_results[kMaxClouds] = {};
+  ChainResults results;               // what the last chain collected left for the agh_get_* getters of the chains
   // agh_localize_depth* (depth.hip): a host capture's depth images, rows packed, image k at depth_image_offset(k); the NEXT
   // capture's (agh_localize_depth_stage) in the second buffer; the two change places when a staged set is adopted
   uint8_t* d_depth = nullptr;
@@ -633,13 +732,22 @@ inline bool bad_capture(const float* xyz, int64_t stride_bytes, int64_t n)
 {
   return n < 0 || n >= (1ll << 30) || stride_bytes < 12 || (stride_bytes % 4) != 0 || (n > 0 && !xyz);
 }
-// the output arguments of agh_localize* and agh_localize_batch*
-inline bool bad_outputs(const agh_handle* handles_out, int64_t handle_cap, const int32_t* inlier_idx_out, int64_t idx_cap,
-  const agh_hypothesis* hands_out, int64_t hands_cap)
+// the output arguments of agh_localize* and agh_localize_batch*, as the entry points take them
+struct ChainOutputs
 {
-  return handle_cap < 0 || idx_cap < 0 || hands_cap < 0 || (handle_cap > 0 && !handles_out) || (idx_cap > 0 && !inlier_idx_out) ||
-         (hands_cap > 0 && !hands_out);
-}
+  agh_handle* handles;
+  int64_t handle_cap;
+  int32_t* inlier_idx;
+  int64_t idx_cap;
+  agh_hypothesis* hands;
+  int64_t hands_cap;
+  int32_t* samples;
+  bool bad() const
+  {
+    return handle_cap < 0 || idx_cap < 0 || hands_cap < 0 || (handle_cap > 0 && !handles) || (idx_cap > 0 && !inlier_idx) ||
+           (hands_cap > 0 && !hands);
+  }
+};
 // A host capture goes up as it lies in host memory -- one contiguous copy: a strided 2-D copy of 12 of every 32 bytes runs at a
 // fraction of the PCIe rate -- and the kernels read it with the caller's stride; strides above 32 bytes are repacked to 12.
 inline int64_t device_stride(int64_t stride_bytes) { return stride_bytes <= 32 ? stride_bytes : 12; }
@@ -851,26 +959,30 @@ inline ClusterDev cluster_dev(const agh_cluster_params& q)
 std::string cluster_params_fault(const agh_cluster_params& cp);
 // ... and on the C slots of a batch's bitmap (vb.slot_words words each): slot k's counts at blk + k * slot_words / 4096, not scanned
 int vox_count_blocks_batch(const VoxBatch& vb, int C, const unsigned* d_bitmap, int* d_blk, hipStream_t st);
-// sample_mask.hip: the masked sample list of a batch chain whose preprocessing (vox_batch) is queued on st (include/agh.h,
-// agh_localize_batch_masked); see BatchMaskStage
-struct BatchMaskStage
+// What every sample stage of a batch chain is given (localize_batch.hip, batch_pass fills it once, behind the queued preprocessing
+// vox_batch and grid build); the stages' own records below add what only they read.
+struct BatchStageCommon
 {
   VoxBatch vb;                      // the batch's capture table, descriptors and slot size
-  int C = 0;
-  int64_t n_max = 0, S_tot = 0;     // the largest capture's raw points; the samples of all captures
+  int C = 0, L = 0;                 // captures; lists (C without a list per object)
+  int64_t n_max = 0, n_tot = 0, S_tot = 0;  // the largest capture's raw points; all captures'; the samples of all lists
   double cell = 0.0;
   const uint8_t* code = nullptr;    // the per-point codes of all captures (VoxCapture::code_off)
+  const unsigned* bitmap = nullptr; // the voxel bitmap slots
+  const int* blk2 = nullptr;        // ... and their capture-local block prefixes
+  const int* cloud_off = nullptr;   // the batch's device-side cloud offsets
+  const BatchCapture* tab = nullptr;  // the chain's list table (soff, S, seed, capture, object)
+  int32_t* d_out = nullptr;         // S_tot indices into the common voxel array (or kSampleSkip), for the search
+  int32_t* h_out = nullptr;         // pinned: S_tot capture-local indices
+};
+// sample_mask.hip: the masked sample list of a batch chain (include/agh.h, agh_localize_batch_masked)
+struct BatchMaskStage : BatchStageCommon
+{
   const uint8_t* const* mask = nullptr;  // device table: capture k's mask, one byte per raw point, at any byte alignment
-  const unsigned* bitmap = nullptr;      // the voxel bitmap slots
-  const int* blk2 = nullptr;             // ... and their capture-local block prefixes
-  const int* cloud_off = nullptr;        // the batch's device-side cloud offsets
   unsigned* elig = nullptr;         // C eligibility slots of the voxel slots' layout
   int* eblk = nullptr;              // their block counts, then capture-local prefixes
   long long* total = nullptr;       // C: the M_k
   int32_t* list = nullptr;          // the E_k, capture k's at its code_off
-  const BatchCapture* tab = nullptr;  // the chain's capture table (soff, S, seed)
-  int32_t* d_out = nullptr;         // S_tot indices into the common voxel array (or kSampleSkip), for the search
-  int32_t* h_out = nullptr;         // pinned: S_tot capture-local indices
   long long* h_total = nullptr;     // pinned: C counts M_k
 };
 int sample_mask_stage_batch(Ctx* c, const BatchMaskStage& m, hipStream_t st);
@@ -880,35 +992,21 @@ struct LabelCapture  // the lists of a labelled batch, per capture: its objects 
 {
   int32_t K, first_list;
 };
-struct BatchLabelStage
+struct BatchLabelStage : BatchStageCommon
 {
-  VoxBatch vb;                      // the batch's capture table, descriptors and slot size
-  int C = 0, L = 0;                 // captures; lists
-  int64_t n_max = 0, n_tot = 0, S_tot = 0;  // the largest capture's raw points; all captures'; the samples of all lists
-  double cell = 0.0;
-  const uint8_t* code = nullptr;    // the per-point codes of all captures (VoxCapture::code_off)
   const uint8_t* const* labels = nullptr;  // device table: capture k's labels, one byte per raw point, at any byte alignment
-  const LabelCapture* lists = nullptr;  // device table, one per capture
-  const unsigned* bitmap = nullptr; // the voxel bitmap slots
-  const int* blk2 = nullptr;        // ... and their capture-local block prefixes
-  const int* cloud_off = nullptr;   // the batch's device-side cloud offsets
-  const BatchCapture* tab = nullptr;  // the chain's list table (soff, S, seed, capture, object)
-  int32_t* d_out = nullptr;         // S_tot indices into the common voxel array (or kSampleSkip), for the search
-  int32_t* h_out = nullptr;         // pinned: S_tot capture-local indices
+  const LabelCapture* lists = nullptr;     // device table, one per capture
 };
 int sample_label_stage_batch(Ctx* c, const BatchLabelStage& m, hipStream_t st);
 // ... in two parts, as the single chain's: the compaction of c->d_label_set into the L lists with their draw, shared with
-// sample_cluster.hip's batch stage, which fills the object sets from the clouds with one ClusterDev record per capture
+// sample_cluster.hip's batch stage, which fills the object sets from the clouds with one ClusterDev record per capture (and reads
+// neither labels, codes nor bitmaps)
 int label_compact_stage_batch(Ctx* c, const BatchLabelStage& m, bool any, hipStream_t st);
 int sample_cluster_stage_batch(Ctx* c, const BatchLabelStage& m, const ClusterDev* cps, hipStream_t st);
 // plane_fit.hip's batch stage (include/agh.h, agh_localize_batch_clustered_fit), queued behind the upload of the ClusterDev table
 // and in front of sample_cluster_stage_batch: capture k's plane, found on its own voxels with fps[k], goes into cps[k].plane
-struct BatchFitStage
+struct BatchFitStage : BatchStageCommon
 {
-  VoxBatch vb;                      // the batch's capture table and descriptors
-  int C = 0;
-  int64_t n_max = 0;                // the largest capture's raw points
-  const int* cloud_off = nullptr;   // the batch's device-side cloud offsets
   const PlaneFitDev* fps = nullptr; // device table: capture k's parameters and camera 0's origin in force for it
   PlaneFitBuffers* fbs = nullptr;   // device: a block per capture
   ClusterDev* cps = nullptr;        // device table of the cluster stage: the plane of record k is written
@@ -1560,6 +1658,14 @@ int depth_batch_check(agh::Ctx* c, const char* who, const agh_depth_image* image
   std::vector<int64_t>* first, std::vector<int64_t>* left0);
 int depth_batch_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, const int32_t* n_images, int C, bool on_device,
   bool drop_staged, hipStream_t st);
+// The rules a source adds to a chain's arguments (include/agh.h; C captures with lp[k], single: the single chain's texts, which name
+// no capture), and its bytes to where the chain reads them, queued on st: device point bytes are read in place; host bytes and
+// all image masks go, packed in point order, into *buf (grown to n_tot bytes, *cap its capacity), capture k's n[k] bytes at
+// byte_off[k]; (*d_bytes)[k] says where capture k's lie.  The single chain owns c->d_mask, the batch chain its state's.
+int sample_source_check(agh::Ctx* c, const agh::SampleSource& src, const agh::DepthCaptures* depth, const agh_localize_params* lp, int C,
+  bool single);
+int sample_source_to_device(agh::Ctx* c, const agh::SampleSource& src, const agh::DepthCaptures* depth, int C, const int64_t* n,
+  const int64_t* byte_off, int64_t n_tot, uint8_t** buf, int64_t* cap, hipStream_t st, std::vector<const uint8_t*>* d_bytes);
 // (unit: what the chain's C lists are, "capture" or "object", for the error texts; nullptr: the one list of a single chain)
 // (names: what list k is called when it is no plain "unit k" -- "capture 2, object 5" of a labelled batch)
 int chain_collect(agh_ctx* ctx, const char* who, const char* unit, int C, const int* counts, int count_stride, int64_t S_tot,
@@ -1571,6 +1677,5 @@ int chain_collect(agh_ctx* ctx, const char* who, const char* unit, int C, const 
 // and the outputs' assembly, spans in list order.
 int labeled_tail_prepare(agh_ctx* ctx, int K, int64_t S, const agh_localize_params* lp, double x1, double x2, int32_t** h_samples);
 int batch_queue(agh_ctx* ctx, bool handles_only);
-int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t* nv, agh_handle* handles_out, int64_t handle_cap,
-  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t* nv, const agh::ChainOutputs& out,
   agh_localize_batch_result* results);

@@ -190,17 +190,6 @@ int chain_collect(agh_ctx* ctx, const char* who, const char* unit, int C, const 
 // raw buffer, under this cloud's kernels), which the next begin adopts instead of uploading.  One chain is in flight at a time:
 // the context's device buffers, pinned mirrors and host-side cloud state are single. ----
 
-static int localize_check_outputs(Ctx* c, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap)
-{
-  if (bad_outputs(handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap))
-  {
-    c->err = "agh_localize: bad arguments (see include/agh.h)";
-    return AGH_ERR_INVALID_ARGUMENT;
-  }
-  return AGH_OK;
-}
-
 // search -> classification -> kept hands -> handle search, queued on the context's stream (handles_only: the handle search alone,
 // once more, on the hands that are already there)
 static int localize_queue(agh_ctx* ctx, bool handles_only)
@@ -243,34 +232,6 @@ static int localize_queue(agh_ctx* ctx, bool handles_only)
   return rc;
 }
 
-// A capture given as depth images (include/agh.h, agh_localize_depth*): the chain's third source kind, beside host points and
-// device points.  k_deproject (depth.hip) fills the context's raw buffer; from there on the chain is the points chain's.
-struct DepthSource
-{
-  const agh_depth_image* images;
-  int32_t n_images;
-  bool on_device;
-  const char* who;  // the entry point, for the error texts
-};
-
-// A sample mask (include/agh.h, agh_localize_masked*): one byte per raw point for a points capture, one agh_sample_mask per
-// image for a depth capture.  Host masks are copied into the context's d_mask, depth masks row by row, packed, image after image
-// (a NULL image: zeros); a device points mask is read in place.
-struct MaskSource
-{
-  const uint8_t* points;          // points form: n bytes
-  const agh_sample_mask* images;  // depth form: one per image
-  bool on_device;
-  const char* who;
-  int32_t n_objects = 0;          // agh_localize_labeled*: the bytes are labels 1 .. n_objects (0: a mask)
-  bool labeled = false;
-  const agh_cluster_params* cluster = nullptr;  // agh_localize_clustered*: no bytes at all, the objects are the cloud's components
-  const agh_plane_fit_params* fit = nullptr;    // agh_localize_clustered_fit*: ... above a plane the chain fits (cluster->plane unread)
-};
-static_assert(sizeof(agh_label_image) == sizeof(agh_sample_mask) && offsetof(agh_label_image, data) == offsetof(agh_sample_mask, data) &&
-                offsetof(agh_label_image, row_stride_bytes) == offsetof(agh_sample_mask, row_stride_bytes),
-  "a label image is read as a sample mask whose bytes are labels");
-
 std::string agh::cluster_params_fault(const agh_cluster_params& cp)
 {
   const double* q = cp.plane;
@@ -292,99 +253,165 @@ std::string agh::cluster_params_fault(const agh_cluster_params& cp)
   return std::string();
 }
 
-static int mask_check(Ctx* c, const MaskSource* mask, const DepthSource* depth, const agh_localize_params* lp)
+// The texts of sample_source_check, where the single and the batch chains word a rule differently.  The single labelled chain
+// speaks of its labels as a mask; a batch's texts name the capture (and the image) in front.
+namespace
 {
+struct SourceWording
+{
+  const char* array_null;       // no array of the captures' bytes (or no image records) at all
+  const char* bytes_null;       // one capture's bytes
+  const char* with_sample_idx;
+  const char* image;            // what a batch calls an image's record, in front of "row_stride_bytes is below the image's width"
+  const char* all_null;         // no image of a capture has bytes
+};
+const SourceWording& source_wording(bool single, SourceKind kind)
+{
+  static const SourceWording mask{ "masks is NULL", "the mask is NULL", "a mask together with sample_idx (an explicit list needs no mask)",
+    "", "every mask's data is NULL (no pixel would be eligible)" };
+  static const SourceWording batch_mask{ "masks is NULL (every capture of a masked batch has a mask)", mask.bytes_null,
+    mask.with_sample_idx, "the mask's ", mask.all_null };
+  static const SourceWording batch_labels{ "labels is NULL (every capture of a labelled batch has labels)", "the label array is NULL",
+    "labels together with sample_idx (an explicit list needs no labels)", "the label image's ",
+    "every label image's data is NULL (no pixel would belong to an object)" };
+  static const SourceWording clusters{ "", "", "sample_idx must be NULL (the lists are drawn on the objects the call finds)", "", "" };
+  if (kind >= SourceKind::Clusters)
+    return clusters;
+  return single ? mask : (kind == SourceKind::Labels ? batch_labels : batch_mask);
+}
+}  // namespace
+
+// (the order of the rules decides which of two faults a call reports: it is part of the contract)
+int sample_source_check(Ctx* c, const SampleSource& src, const DepthCaptures* depth, const agh_localize_params* lp, int C, bool single)
+{
+  const SourceWording& w = source_wording(single, src.kind);
+  const std::string objects = src.clustered() ? "max_objects" : "n_objects";
   auto bad = [&](const std::string& what) {
-    c->err = std::string(mask->who) + ": " + what;
+    c->err = std::string(src.who) + ": " + what;
     return AGH_ERR_INVALID_ARGUMENT;
   };
-  if (mask->cluster)
+  if (!single)  // (the single entry points pass pointers to their own scalars; their image records are tested behind sample_idx)
   {
-    agh_cluster_params cp = *mask->cluster;
-    if (mask->fit)  // (the plane is the chain's to find: the caller's is neither read nor validated)
+    if (src.fitted() && !src.fit)
+      return bad("fp is NULL (every capture of a fitted batch has its agh_plane_fit_params record)");
+    if (src.clustered() && !src.cluster)
+      return bad("cp is NULL (every capture of a clustered batch has its agh_cluster_params record)");
+    if (src.kind == SourceKind::Labels && !src.n_objects)
+      return bad("n_objects is NULL");
+    if (src.has_bytes() && (depth ? !src.images : !src.points))
+      return bad(w.array_null);
+  }
+  int64_t lists = 0, samples = 0;
+  for (int k = 0, i0 = 0; k < C; k++)
+  {
+    const std::string cap = "capture " + std::to_string(k);
+    const std::string at = single ? std::string() : cap + ": ";
+    if (src.clustered())
     {
-      const std::string fit_fault = plane_fit_params_fault(*mask->fit);
-      if (!fit_fault.empty())
-        return bad(fit_fault);
-      cp.plane[0] = cp.plane[1] = cp.plane[3] = 0.0;
-      cp.plane[2] = 1.0;
+      agh_cluster_params q = src.cluster[k];
+      if (src.fitted())
+      {
+        const std::string fit_fault = plane_fit_params_fault(src.fit[k]);
+        if (!fit_fault.empty())
+          return bad(at + fit_fault);
+        placeholder_plane(&q);
+      }
+      const std::string fault = cluster_params_fault(q);
+      if (!fault.empty())
+        return bad(at + fault);
     }
-    const std::string fault = cluster_params_fault(cp);
-    if (!fault.empty())
-      return bad(fault);
-    if ((int64_t) cp.max_objects * lp->n_samples > (1 << 24))
-      return bad("max_objects x n_samples exceeds 2^24");
-    if (lp->sample_idx)
-      return bad("sample_idx must be NULL (the lists are drawn on the objects the call finds)");
-    return AGH_OK;
-  }
-  if (mask->labeled && (mask->n_objects < 1 || mask->n_objects > kMaxClouds))
-    return bad("n_objects must be 1 .. 64");
-  if (mask->labeled && (int64_t) mask->n_objects * lp->n_samples > (1 << 24))
-    return bad("n_objects x n_samples exceeds 2^24");
-  if (lp->sample_idx)
-    return bad("a mask together with sample_idx (an explicit list needs no mask)");
-  if (!depth)
-    return mask->points ? AGH_OK : bad("the mask is NULL");
-  if (!mask->images)
-    return bad("masks is NULL");
-  bool any = false;
-  for (int k = 0; k < depth->n_images; k++)
-  {
-    if (!mask->images[k].data)
+    else if (src.kind == SourceKind::Labels && (src.n_objects[k] < 1 || src.n_objects[k] > kMaxClouds))
+      return bad(at + "n_objects must be 1 .. 64");
+    if (src.per_object())
+    {
+      lists += src.objects(k);
+      samples += (int64_t) src.objects(k) * lp[k].n_samples;
+      if (lists > kMaxClouds)
+        return bad(at + "more than 64 lists in all (the sum of " + objects + " up to this capture)");
+      if (samples > (1 << 24))
+        return bad(single ? objects + " x n_samples exceeds 2^24"
+                          : at + "more than 2^24 samples in all (the sum of " + objects + " x n_samples up to this capture)");
+    }
+    if (lp[k].sample_idx)
+      return bad(at + w.with_sample_idx);
+    if (!src.has_bytes())
       continue;
-    any = true;
-    if (mask->images[k].row_stride_bytes < depth->images[k].width)
-      return bad("mask " + std::to_string(k) + ": row_stride_bytes is below the image's width");
+    if (!depth)
+    {
+      if (!src.points[k])
+        return bad(at + w.bytes_null);
+      continue;
+    }
+    if (!src.images)
+      return bad(w.array_null);
+    bool any = false;
+    for (int j = 0; j < depth->n_images[k]; j++)
+    {
+      const agh_sample_mask& m = src.images[i0 + j];
+      if (!m.data)
+        continue;
+      any = true;
+      if (m.row_stride_bytes < depth->images[i0 + j].width)
+        return bad((single ? "mask " + std::to_string(j) + ": " : cap + ", image " + std::to_string(j) + ": " + w.image) +
+                   "row_stride_bytes is below the image's width");
+    }
+    if (!any)
+      return bad(at + w.all_null);
+    i0 += depth->n_images[k];
   }
-  return any ? AGH_OK : bad("every mask's data is NULL (no pixel would be eligible)");
+  return AGH_OK;
 }
 
-// the mask into d_mask on st (see MaskSource); *d_mask_out: where the chain reads it
-static int mask_to_device(Ctx* c, const MaskSource* mask, const DepthSource* depth, int64_t n, hipStream_t st, const uint8_t** d_mask_out)
+int sample_source_to_device(Ctx* c, const SampleSource& src, const DepthCaptures* depth, int C, const int64_t* n, const int64_t* byte_off,
+  int64_t n_tot, uint8_t** buf, int64_t* cap, hipStream_t st, std::vector<const uint8_t*>* d_bytes)
 {
-  if (!depth && mask->on_device)
+  d_bytes->resize((size_t) C);
+  if (!depth && src.on_device)
   {
-    *d_mask_out = mask->points;
+    std::copy(src.points, src.points + C, d_bytes->begin());
     return AGH_OK;
   }
-  if (n > c->mask_cap || !c->d_mask)
+  if (n_tot > *cap || !*buf)
   {
-    c->mask_cap = 0;
-    if (int rc = dev_alloc(c, &c->d_mask, (size_t) std::max<int64_t>(n, 1)))
+    *cap = 0;
+    if (int rc = dev_alloc(c, buf, (size_t) std::max<int64_t>(n_tot, 1)))
       return rc;
-    c->mask_cap = std::max<int64_t>(n, 1);
+    *cap = std::max<int64_t>(n_tot, 1);
   }
-  *d_mask_out = c->d_mask;
-  const hipMemcpyKind kind = mask->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  if (!depth)
+  const hipMemcpyKind kind = src.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  for (int k = 0, i0 = 0; k < C; k++)
   {
-    if (n > 0)
-      AGH_HIPCHK(c, hipMemcpyAsync(c->d_mask, mask->points, (size_t) n, kind, st));
-    return AGH_OK;
-  }
-  int64_t off = 0;
-  for (int k = 0; k < depth->n_images; k++)
-  {
-    const size_t W = (size_t) depth->images[k].width, H = (size_t) depth->images[k].height;
-    const agh_sample_mask& m = mask->images[k];
-    if (!m.data)
-      AGH_HIPCHK(c, hipMemsetAsync(c->d_mask + off, 0, W * H, st));
-    else
-      AGH_HIPCHK(c, hipMemcpy2DAsync(c->d_mask + off, W, m.data, (size_t) m.row_stride_bytes, W, H, kind, st));
-    off += (int64_t) (W * H);
+    uint8_t* dst = *buf + byte_off[k];
+    (*d_bytes)[k] = dst;
+    if (!depth)
+    {
+      if (n[k] > 0)
+        AGH_HIPCHK(c, hipMemcpyAsync(dst, src.points[k], (size_t) n[k], kind, st));
+      continue;
+    }
+    for (int j = 0; j < depth->n_images[k]; j++)
+    {
+      const size_t W = (size_t) depth->images[i0 + j].width, H = (size_t) depth->images[i0 + j].height;
+      const agh_sample_mask& m = src.images[i0 + j];
+      if (!m.data)
+        AGH_HIPCHK(c, hipMemsetAsync(dst, 0, W * H, st));
+      else
+        AGH_HIPCHK(c, hipMemcpy2DAsync(dst, W, m.data, (size_t) m.row_stride_bytes, W, H, kind, st));
+      dst += W * H;
+    }
+    i0 += depth->n_images[k];
   }
   return AGH_OK;
 }
 
 static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int64_t stride_bytes, int64_t n,
-  const agh_localize_params* lp, const DepthSource* depth = nullptr, const MaskSource* mask = nullptr)
+  const agh_localize_params* lp, const DepthCaptures* depth = nullptr, const SampleSource* src = nullptr)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
-  const char* who = mask ? mask->who : (depth ? depth->who : "agh_localize_begin");
+  const char* who = src ? src->who : (depth ? depth->who : "agh_localize_begin");
   if (L.active)
   {
     c->err = std::string(who) + ": a chain is in flight (agh_localize_end first)";
@@ -399,7 +426,7 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   if (depth && lp)
   {
     // (the arguments of the images first: their sizes are the capture's; then size_left and dense as include/agh.h fixes them)
-    if (int rc = depth_check(c, depth->who, depth->images, depth->n_images, depth->on_device, &n))
+    if (int rc = depth_check(c, depth->who, depth->images, depth->n_images[0], depth->on_device, &n))
       return rc;
     lp_depth = *lp;
     lp_depth.size_left = (int64_t) depth->images[0].width * depth->images[0].height;
@@ -430,12 +457,12 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     c->err = "agh_localize: this libm's acos is not monotone around the 0.34 rad thresholds";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  if (mask)
-    if (int rc = mask_check(c, mask, depth, lp))
+  if (src)
+    if (int rc = sample_source_check(c, *src, depth, lp, 1, true))
       return rc;
   AGH_HIPCHK(c, hipSetDevice(c->device));
   const int64_t S = lp->n_samples;
-  const int K = mask && mask->labeled ? mask->n_objects : 0;  // (a labelled chain: K lists of S samples)
+  const int K = src && src->per_object() ? src->objects(0) : 0;  // (a chain with a list per object: K lists of S samples)
   const int64_t S_all = K ? K * S : S;
   hipStream_t st = c->stream;
   int rc;
@@ -445,7 +472,7 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   const int64_t dev_stride = xyz_on_device ? stride_bytes : device_stride(stride_bytes);
   const float* d_raw = xyz;
   // (a masked begin of host data never adopts a staged set: it drops a pending one as a begin of another kind does)
-  const bool adopts = !mask;
+  const bool adopts = !src;
   if (depth)
   {
     if (!adopts && !depth->on_device)
@@ -454,7 +481,7 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
         AGH_HIPCHK(c, hipStreamWaitEvent(st, c->stage_done, 0));
       L.staged = false;
     }
-    if ((rc = depth_to_raw(ctx, depth->who, depth->images, depth->n_images, depth->on_device, adopts, st)) != AGH_OK)
+    if ((rc = depth_to_raw(ctx, depth->who, depth->images, depth->n_images[0], depth->on_device, adopts, st)) != AGH_OK)
       return rc;
     d_raw = c->d_raw_xyz;
   }
@@ -485,18 +512,12 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     }
     d_raw = c->d_raw_xyz;
   }
-  const uint8_t* d_mask = nullptr;
-  if (mask && !mask->cluster && (rc = mask_to_device(c, mask, depth, n, st, &d_mask)) != AGH_OK)
+  L.source.keep(src, 1, true);
+  const int64_t byte_off = 0;
+  if (src && src->has_bytes() &&
+      (rc = sample_source_to_device(c, *src, depth, 1, &n, &byte_off, n, &c->d_mask, &c->mask_cap, st, &L.source.d_bytes)) != AGH_OK)
     return chain_fail(c, rc);  // (the capture's copy may be in flight)
-  L.masked = mask != nullptr;
-  L.d_mask = d_mask;
-  L.n_objects = K;
-  L.clustered = mask && mask->cluster;
-  if (L.clustered)
-    L.cluster = *mask->cluster;
-  L.fitted = L.clustered && mask->fit;
-  if (L.fitted)
-    L.fit = *mask->fit;
+  const uint8_t* d_mask = L.source.d_bytes.empty() ? nullptr : L.source.d_bytes[0];
   L.S = S;
   L.classify = lp->classify != 0;
   L.filters = lp->filters_boundaries != 0;
@@ -536,13 +557,14 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
     AGH_HIPCHK_OR(c, ensure_keep_buffers(c, c->s_cap * 8), chain_fail(c, AGH_ERR_HIP));
   }
   // ---- 3. the sample list ----
-  if (L.clustered)  // (the grid build is queued: the preprocessing above bound the voxelised cloud)
+  if (L.source.clustered())  // (the grid build is queued: the preprocessing above bound the voxelised cloud)
   {
     // (a fitted chain: the plane is found first, on the same stream, and the cluster kernels read the record it leaves on the device)
     const ClusterDev* d_cp = nullptr;
-    if (L.fitted && (rc = plane_fit_stage(c, n, L.fit, cluster_dev(L.cluster), st, &d_cp)) != AGH_OK)
+    const ClusterDev cp = cluster_dev(L.source.cluster[0]);
+    if (L.source.fitted() && (rc = plane_fit_stage(c, n, L.source.fit[0], cp, st, &d_cp)) != AGH_OK)
       return chain_fail(c, rc);
-    if ((rc = sample_cluster_stage(c, n, cluster_dev(L.cluster), K, S, (unsigned long long) lp->sample_seed, c->d_idx_own, h_idx_labeled, st, d_cp)) != AGH_OK)
+    if ((rc = sample_cluster_stage(c, n, cp, K, S, (unsigned long long) lp->sample_seed, c->d_idx_own, h_idx_labeled, st, d_cp)) != AGH_OK)
       return chain_fail(c, rc);
   }
   else if (K)  // (for S = 0 too, as the mask's)
@@ -551,7 +573,7 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
            c->d_idx_own, h_idx_labeled, st)) != AGH_OK)
       return chain_fail(c, rc);
   }
-  else if (mask)  // (for S = 0 too: the count of eligible voxels is what a caller sizes S with)
+  else if (src)  // (for S = 0 too: the count of eligible voxels is what a caller sizes S with)
   {
     if ((rc = sample_mask_stage(c, d_raw, dev_stride / 4, n, d_mask, lp->cell_size, S, (unsigned long long) lp->sample_seed,
            c->d_idx_own, h_idx, reinterpret_cast<long long*>(c->h_pin) + kPinMaskCount, st)) != AGH_OK)
@@ -580,20 +602,12 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
 }
 
 // (results: a labelled chain's, one record per object, where a chain of another kind has *result)
-static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result,
-  agh_localize_batch_result* results = nullptr)
+static int localize_end_impl(agh_ctx* ctx, const ChainOutputs& out, agh_localize_result* result, agh_localize_batch_result* results = nullptr)
 {
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
   L.active = false;
-  c->mask_count = -1;
-  c->label_objects = 0;
-  c->cluster_objects = 0;
-  c->fit_valid = false;
-  c->batch_mask_captures = 0;
-  c->batch_label_lists = 0;
-  c->batch_cluster_captures = 0;
+  c->results = ChainResults{};
   const int64_t S = L.S;
   const HandlePins pin = handle_pins(c);
   const int* h_counts = pin.counts;
@@ -622,16 +636,13 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
         agh_localize_params lp = L.lp;
         lp.sample_idx = L.explicit_samples ? h_idx : nullptr;
         L.repeated = true;
-        // (a mask is where the chain read it, as the capture is: in the context's buffer, or in the caller's device memory)
-        const agh_cluster_params cluster = L.cluster;
-        const agh_plane_fit_params fit = L.fit;
-        const MaskSource again{ L.d_mask, nullptr, true,
-          L.clustered ? "agh_localize_clustered" : (L.n_objects ? "agh_localize_labeled" : "agh_localize_masked"), L.n_objects,
-          L.n_objects != 0, L.clustered ? &cluster : nullptr, L.fitted ? &fit : nullptr };
-        rc = localize_begin_impl(ctx, L.d_raw, true, L.dev_stride, L.n_raw, &lp, nullptr, L.masked ? &again : nullptr);
+        // (the source is where the chain read it, as the capture is: in the context's buffer, or in the caller's device memory; the
+        // begin stores it anew, so it re-enters with a copy)
+        const StoredSource kept = L.source;
+        const SampleSource again = kept.view();
+        rc = localize_begin_impl(ctx, L.d_raw, true, L.dev_stride, L.n_raw, &lp, nullptr, kept.kind != SourceKind::None ? &again : nullptr);
         if (rc == AGH_OK)
-          rc = localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result,
-            results);
+          rc = localize_end_impl(ctx, out, result, results);
         c->loc.repeated = false;
         return rc;
       }
@@ -647,98 +658,118 @@ static int localize_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t hand
     c->cloud_off_on_device = true;  // ({0, nv}: what the voxeliser wrote)
     c->n_clouds = 1;
   }
-  if (L.n_objects)
+  ChainResults& R = c->results;
+  R.kind = L.source.kind;
+  R.captures = 1;
+  if (const int K = L.objects())
   {
     // the tail of the batch chain: one list per object, every object on the one cloud
-    const int K = L.n_objects;
-    if (L.clustered)
+    R.lists = K;
+    if (L.source.clustered())
     {
       // (the table of k_cluster_select: counts, then the M_j and the ids; the M_j equal the compaction's h_label_counts)
       const long long* t = c->h_cluster_table;
-      c->cluster_objects = K;
-      c->cluster_nv = L.nv;
-      std::copy(t, t + 4, c->cluster_info);
-      for (int j = 0; j < kMaxClouds; j++)
+      R.nv = L.nv;
+      std::copy(t, t + 4, R.cluster_info[0]);
+      for (int j = 0; j < K; j++)
       {
-        c->cluster_sizes[j] = (int64_t) t[8 + j];
-        c->cluster_ids[j] = (int32_t) t[8 + kMaxClouds + j];
+        R.counts[j] = (int64_t) t[8 + j];
+        R.cluster_ids[j] = (int32_t) t[8 + kMaxClouds + j];
       }
-      if (L.fitted)  // (the record k_fit_finish wrote into pinned memory: here with the chain's one synchronisation)
+      if (L.source.fitted())  // (the record k_fit_finish wrote into pinned memory: here with the chain's one synchronisation)
       {
-        c->fit_valid = true;
-        c->fit_candidates = L.fit.n_candidates;
-        c->fit_result = *c->h_fit_result;
+        R.fit_candidates[0] = L.source.fit[0].n_candidates;
+        R.fit_results[0] = *c->h_fit_result;
       }
     }
     else
-    {
-      c->label_objects = K;
       for (int j = 0; j < K; j++)
-        c->label_counts[j] = (int64_t) c->h_label_counts[j];
-    }
+        R.counts[j] = (int64_t) c->h_label_counts[j];
     const std::vector<int64_t> nv((size_t) K, L.nv);
-    return batch_collect(ctx, L.clustered ? "agh_localize_clustered" : "agh_localize_labeled", "object", nv.data(), handles_out, handle_cap, inlier_idx_out, idx_cap,
-      hands_out, hands_cap, samples_out, results);
+    return batch_collect(ctx, L.source.who, "object", nv.data(), out, results);
   }
-  if (L.masked)
-    c->mask_count = (int64_t) reinterpret_cast<const long long*>(c->h_pin)[kPinMaskCount];
+  if (R.kind == SourceKind::Mask)
+  {
+    R.lists = 1;
+    R.counts[0] = (int64_t) reinterpret_cast<const long long*>(c->h_pin)[kPinMaskCount];
+  }
   if ((rc = chain_collect(ctx, "agh_localize", nullptr, 1, h_counts, 0, S, nullptr, localize_queue)) != AGH_OK)
     return rc;
   const int64_t n_hyp = h_counts[4], n_kept = h_counts[5];
   c->last_nout = std::min<int64_t>(n_hyp, c->s_cap * 8);
   if (result)
     *result = agh_localize_result{ L.nv, n_hyp, n_kept, h_counts[0], h_counts[1] };
-  if (samples_out && S > 0)
-    std::memcpy(samples_out, h_idx, sizeof(int32_t) * (size_t) S);
-  if (h_counts[0] > handle_cap || h_counts[1] > idx_cap || (hands_out && n_kept > hands_cap))
+  if (out.samples && S > 0)
+    std::memcpy(out.samples, h_idx, sizeof(int32_t) * (size_t) S);
+  if (h_counts[0] > out.handle_cap || h_counts[1] > out.idx_cap || (out.hands && n_kept > out.hands_cap))
   {
     c->err = "agh_localize: output buffers too small (the counts are in *result)";
     return AGH_ERR_CAPACITY;
   }
   if (h_counts[0] > 0)
   {
-    std::memcpy(handles_out, pin.handles, sizeof(agh_handle) * (size_t) h_counts[0]);
-    std::memcpy(inlier_idx_out, pin.idx, sizeof(int32_t) * (size_t) h_counts[1]);
+    std::memcpy(out.handles, pin.handles, sizeof(agh_handle) * (size_t) h_counts[0]);
+    std::memcpy(out.inlier_idx, pin.idx, sizeof(int32_t) * (size_t) h_counts[1]);
   }
-  if (hands_out && n_kept > 0)
-    std::memcpy(hands_out, pin.hands, sizeof(agh_hypothesis) * (size_t) n_kept);
+  if (out.hands && n_kept > 0)
+    std::memcpy(out.hands, pin.hands, sizeof(agh_hypothesis) * (size_t) n_kept);
   return AGH_OK;
 }
 
 // agh_localize[_device] = begin + end
 static int localize_call(agh_ctx* ctx, const float* xyz, bool xyz_on_device, int64_t stride_bytes, int64_t n,
-  const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result, const DepthSource* depth = nullptr,
-  const MaskSource* mask = nullptr)
+  const agh_localize_params* lp, const ChainOutputs& out, agh_localize_result* result, const DepthCaptures* depth = nullptr,
+  const SampleSource* src = nullptr)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   if (result)
     *result = agh_localize_result{ 0, 0, 0, 0, 0 };
-  int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
-  if (rc == AGH_OK)
-    rc = localize_begin_impl(ctx, xyz, xyz_on_device, stride_bytes, n, lp, depth, mask);
+  if (out.bad())
+  {
+    ctx->c.err = "agh_localize: bad arguments (see include/agh.h)";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  const int rc = localize_begin_impl(ctx, xyz, xyz_on_device, stride_bytes, n, lp, depth, src);
   if (rc != AGH_OK)
     return rc;
-  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
+  return localize_end_impl(ctx, out, result);
+}
+
+// the forms with a list per object (labelled, clustered, fitted) = begin + end; K: the objects, as far as the arguments say
+static int per_object_call(agh_ctx* ctx, const float* xyz, bool on_device, int64_t stride_bytes, int64_t n, const DepthCaptures* depth,
+  const SampleSource& src, int K, const agh_localize_params* lp, const ChainOutputs& out, agh_localize_batch_result* results)
+{
+  if (results && K >= 1 && K <= kMaxClouds)
+    for (int j = 0; j < K; j++)
+      results[j] = agh_localize_batch_result{ { 0, 0, 0, 0, 0 }, 0, 0, 0, 0 };
+  if (out.bad())
+  {
+    ctx->c.err = "agh_localize: bad arguments (see include/agh.h)";
+    return AGH_ERR_INVALID_ARGUMENT;
+  }
+  const int rc = localize_begin_impl(ctx, xyz, depth ? false : on_device, stride_bytes, n, lp, depth, &src);
+  if (rc != AGH_OK)
+    return rc;
+  return localize_end_impl(ctx, out, nullptr, results);
 }
 
 extern "C" {
 
 int agh_localize(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp,
-  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
-  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap,
+  int32_t* samples_out, agh_localize_result* result)
 {
-  return localize_call(ctx, xyz, false, stride_bytes, n, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
-    samples_out, result);
+  return localize_call(ctx, xyz, false, stride_bytes, n, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, result);
 }
 
 int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp,
-  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
-  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap,
+  int32_t* samples_out, agh_localize_result* result)
 {
-  return localize_call(ctx, d_xyz, true, stride_bytes, n, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
-    samples_out, result);
+  return localize_call(ctx, d_xyz, true, stride_bytes, n, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, result);
 }
 
 int agh_localize_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const agh_localize_params* lp)
@@ -747,27 +778,27 @@ int agh_localize_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int
 }
 
 int agh_localize_depth(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp,
-  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
-  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap,
+  int32_t* samples_out, agh_localize_result* result)
 {
-  const DepthSource src{ images, n_images, false, "agh_localize_depth" };
-  return localize_call(ctx, nullptr, false, 12, 0, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
-    samples_out, result, &src);
+  const DepthCaptures depth{ images, &n_images, false, "agh_localize_depth" };
+  return localize_call(ctx, nullptr, false, 12, 0, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, result, &depth);
 }
 
 int agh_localize_depth_device(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp,
-  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
-  int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
+  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap,
+  int32_t* samples_out, agh_localize_result* result)
 {
-  const DepthSource src{ images, n_images, true, "agh_localize_depth_device" };
-  return localize_call(ctx, nullptr, false, 12, 0, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
-    samples_out, result, &src);
+  const DepthCaptures depth{ images, &n_images, true, "agh_localize_depth_device" };
+  return localize_call(ctx, nullptr, false, 12, 0, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, result, &depth);
 }
 
 int agh_localize_depth_begin(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_localize_params* lp)
 {
-  const DepthSource src{ images, n_images, false, "agh_localize_depth_begin" };
-  return localize_begin_impl(ctx, nullptr, false, 12, 0, lp, &src);
+  const DepthCaptures depth{ images, &n_images, false, "agh_localize_depth_begin" };
+  return localize_begin_impl(ctx, nullptr, false, 12, 0, lp, &depth);
 }
 
 int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
@@ -788,14 +819,15 @@ int agh_localize_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, 
     c->err = "agh_localize_end: the chain in flight is a batch's (agh_localize_batch_end collects it)";
     return AGH_ERR_STATE;
   }
-  const int rc = localize_check_outputs(c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
-  if (rc != AGH_OK)
+  const ChainOutputs out{ handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out };
+  if (out.bad())
   {
     // (the chain is queued: drain it, leave the context as a failed call does)
     c->loc.active = false;
-    return chain_fail(c, rc);
+    c->err = "agh_localize: bad arguments (see include/agh.h)";
+    return chain_fail(c, AGH_ERR_INVALID_ARGUMENT);
   }
-  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, result);
+  return localize_end_impl(ctx, out, result);
 }
 
 // ---- the masked forms (include/agh.h): the chain with its samples drawn among the eligible voxels of a mask ----
@@ -804,115 +836,105 @@ int agh_localize_masked(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, in
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
 {
-  const MaskSource m{ mask, nullptr, false, "agh_localize_masked" };
-  return localize_call(ctx, xyz, false, stride_bytes, n, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
-    samples_out, result, nullptr, &m);
+  const SampleSource src = mask_source(&mask, nullptr, false, "agh_localize_masked");
+  return localize_call(ctx, xyz, false, stride_bytes, n, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, result, nullptr, &src);
 }
 
 int agh_localize_masked_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const uint8_t* d_mask,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
 {
-  const MaskSource m{ d_mask, nullptr, true, "agh_localize_masked_device" };
-  return localize_call(ctx, d_xyz, true, stride_bytes, n, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
-    samples_out, result, nullptr, &m);
+  const SampleSource src = mask_source(&d_mask, nullptr, true, "agh_localize_masked_device");
+  return localize_call(ctx, d_xyz, true, stride_bytes, n, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, result, nullptr, &src);
 }
 
 int agh_localize_masked_begin(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const uint8_t* mask,
   const agh_localize_params* lp)
 {
-  const MaskSource m{ mask, nullptr, false, "agh_localize_masked_begin" };
-  return localize_begin_impl(ctx, xyz, false, stride_bytes, n, lp, nullptr, &m);
+  const SampleSource src = mask_source(&mask, nullptr, false, "agh_localize_masked_begin");
+  return localize_begin_impl(ctx, xyz, false, stride_bytes, n, lp, nullptr, &src);
 }
 
 int agh_localize_depth_masked(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, int32_t n_images,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
 {
-  const DepthSource src{ images, n_images, false, "agh_localize_depth_masked" };
-  const MaskSource m{ nullptr, masks, false, src.who };
-  return localize_call(ctx, nullptr, false, 12, 0, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
-    samples_out, result, &src, &m);
+  const DepthCaptures depth{ images, &n_images, false, "agh_localize_depth_masked" };
+  const SampleSource src = mask_source(nullptr, masks, false, depth.who);
+  return localize_call(ctx, nullptr, false, 12, 0, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, result, &depth, &src);
 }
 
 int agh_localize_depth_masked_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, int32_t n_images,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_result* result)
 {
-  const DepthSource src{ images, n_images, true, "agh_localize_depth_masked_device" };
-  const MaskSource m{ nullptr, masks, true, src.who };
-  return localize_call(ctx, nullptr, false, 12, 0, lp, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap,
-    samples_out, result, &src, &m);
+  const DepthCaptures depth{ images, &n_images, true, "agh_localize_depth_masked_device" };
+  const SampleSource src = mask_source(nullptr, masks, true, depth.who);
+  return localize_call(ctx, nullptr, false, 12, 0, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, result, &depth, &src);
 }
 
 int agh_localize_depth_masked_begin(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks, int32_t n_images,
   const agh_localize_params* lp)
 {
-  const DepthSource src{ images, n_images, false, "agh_localize_depth_masked_begin" };
-  const MaskSource m{ nullptr, masks, false, src.who };
-  return localize_begin_impl(ctx, nullptr, false, 12, 0, lp, &src, &m);
+  const DepthCaptures depth{ images, &n_images, false, "agh_localize_depth_masked_begin" };
+  const SampleSource src = mask_source(nullptr, masks, false, depth.who);
+  return localize_begin_impl(ctx, nullptr, false, 12, 0, lp, &depth, &src);
 }
 
 // ---- the labelled forms (include/agh.h): one capture, one list of samples per object of a label image ----
-
-static int labeled_call(agh_ctx* ctx, const float* xyz, bool on_device, int64_t stride_bytes, int64_t n, const uint8_t* labels,
-  const agh_label_image* label_images, const DepthSource* depth, const char* who, int32_t n_objects, const agh_localize_params* lp,
-  agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
-  int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
-{
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  if (results && n_objects >= 1 && n_objects <= kMaxClouds)
-    for (int j = 0; j < n_objects; j++)
-      results[j] = agh_localize_batch_result{ { 0, 0, 0, 0, 0 }, 0, 0, 0, 0 };
-  const MaskSource m{ labels, reinterpret_cast<const agh_sample_mask*>(label_images), on_device, who, n_objects, true };
-  int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
-  if (rc == AGH_OK)
-    rc = localize_begin_impl(ctx, xyz, depth ? false : on_device, stride_bytes, n, lp, depth, &m);
-  if (rc != AGH_OK)
-    return rc;
-  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, nullptr, results);
-}
 
 int agh_localize_labeled(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int64_t n, const uint8_t* labels, int32_t n_objects,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  return labeled_call(ctx, xyz, false, stride_bytes, n, labels, nullptr, nullptr, "agh_localize_labeled", n_objects, lp, handles_out,
-    handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  return per_object_call(ctx, xyz, false, stride_bytes, n, nullptr, label_source(&labels, nullptr, &n_objects, false, "agh_localize_labeled"),
+    n_objects, lp, { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
 
 int agh_localize_labeled_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const uint8_t* d_labels,
   int32_t n_objects, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  return labeled_call(ctx, d_xyz, true, stride_bytes, n, d_labels, nullptr, nullptr, "agh_localize_labeled_device", n_objects, lp,
-    handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  return per_object_call(ctx, d_xyz, true, stride_bytes, n, nullptr,
+    label_source(&d_labels, nullptr, &n_objects, true, "agh_localize_labeled_device"), n_objects, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
 
 int agh_localize_depth_labeled(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels, int32_t n_images,
   int32_t n_objects, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthSource src{ images, n_images, false, "agh_localize_depth_labeled" };
-  return labeled_call(ctx, nullptr, false, 12, 0, nullptr, labels, &src, src.who, n_objects, lp, handles_out, handle_cap,
-    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthCaptures depth{ images, &n_images, false, "agh_localize_depth_labeled" };
+  return per_object_call(ctx, nullptr, false, 12, 0, &depth, label_source(nullptr, labels, &n_objects, false, depth.who), n_objects, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
 
 int agh_localize_depth_labeled_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels, int32_t n_images,
   int32_t n_objects, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthSource src{ images, n_images, true, "agh_localize_depth_labeled_device" };
-  return labeled_call(ctx, nullptr, true, 12, 0, nullptr, labels, &src, src.who, n_objects, lp, handles_out, handle_cap,
-    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
+  const DepthCaptures depth{ images, &n_images, true, "agh_localize_depth_labeled_device" };
+  return per_object_call(ctx, nullptr, true, 12, 0, &depth, label_source(nullptr, labels, &n_objects, true, depth.who), n_objects, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
 
-// ---- the clustered forms (include/agh.h): the labelled chain with the cloud's own connected components as its objects ----
+// ---- the clustered forms (include/agh.h): the labelled chain with the cloud's own connected components as its objects; the
+// fitted forms (agh_localize_clustered_fit*): with the plane found by plane_fit.hip ----
 
-static int clustered_call(agh_ctx* ctx, const float* xyz, bool on_device, int64_t stride_bytes, int64_t n, const DepthSource* depth,
-  const char* who, const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap,
-  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+static int clustered_call(agh_ctx* ctx, const float* xyz, bool on_device, int64_t stride_bytes, int64_t n, const DepthCaptures* depth,
+  const char* who, const agh_cluster_params* cp, const agh_localize_params* lp, const ChainOutputs& out,
   agh_localize_batch_result* results, const agh_plane_fit_params* fp = nullptr, bool fitted = false)
 {
   if (!ctx)
@@ -927,17 +949,7 @@ static int clustered_call(agh_ctx* ctx, const float* xyz, bool on_device, int64_
     ctx->c.err = std::string(who) + ": cp is NULL";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  const int K = cp->max_objects;
-  if (results && K >= 1 && K <= kMaxClouds)
-    for (int j = 0; j < K; j++)
-      results[j] = agh_localize_batch_result{ { 0, 0, 0, 0, 0 }, 0, 0, 0, 0 };
-  const MaskSource m{ nullptr, nullptr, on_device, who, K, true, cp, fp };
-  int rc = localize_check_outputs(&ctx->c, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap);
-  if (rc == AGH_OK)
-    rc = localize_begin_impl(ctx, xyz, depth ? false : on_device, stride_bytes, n, lp, depth, &m);
-  if (rc != AGH_OK)
-    return rc;
-  return localize_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, nullptr, results);
+  return per_object_call(ctx, xyz, on_device, stride_bytes, n, depth, cluster_source(cp, fp, fitted, who), cp->max_objects, lp, out, results);
 }
 
 void agh_default_cluster_params(agh_cluster_params* p)
@@ -951,37 +963,35 @@ int agh_localize_clustered(agh_ctx* ctx, const float* xyz, int64_t stride_bytes,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  return clustered_call(ctx, xyz, false, stride_bytes, n, nullptr, "agh_localize_clustered", cp, lp, handles_out, handle_cap,
-    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+  return clustered_call(ctx, xyz, false, stride_bytes, n, nullptr, "agh_localize_clustered", cp, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
 
 int agh_localize_clustered_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const agh_cluster_params* cp,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  return clustered_call(ctx, d_xyz, true, stride_bytes, n, nullptr, "agh_localize_clustered_device", cp, lp, handles_out, handle_cap,
-    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+  return clustered_call(ctx, d_xyz, true, stride_bytes, n, nullptr, "agh_localize_clustered_device", cp, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
 
 int agh_localize_depth_clustered(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_cluster_params* cp,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthSource src{ images, n_images, false, "agh_localize_depth_clustered" };
-  return clustered_call(ctx, nullptr, false, 12, 0, &src, src.who, cp, lp, handles_out, handle_cap, inlier_idx_out, idx_cap,
-    hands_out, hands_cap, samples_out, results);
+  const DepthCaptures depth{ images, &n_images, false, "agh_localize_depth_clustered" };
+  return clustered_call(ctx, nullptr, false, 12, 0, &depth, depth.who, cp, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
 
 int agh_localize_depth_clustered_device(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_cluster_params* cp,
   const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthSource src{ images, n_images, true, "agh_localize_depth_clustered_device" };
-  return clustered_call(ctx, nullptr, true, 12, 0, &src, src.who, cp, lp, handles_out, handle_cap, inlier_idx_out, idx_cap,
-    hands_out, hands_cap, samples_out, results);
+  const DepthCaptures depth{ images, &n_images, true, "agh_localize_depth_clustered_device" };
+  return clustered_call(ctx, nullptr, true, 12, 0, &depth, depth.who, cp, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
-
-// ---- the fitted forms (include/agh.h, agh_localize_clustered_fit*): the clustered call with the plane found by plane_fit.hip ----
 
 void agh_default_plane_fit_params(agh_plane_fit_params* p)
 {
@@ -994,25 +1004,26 @@ int agh_localize_clustered_fit(agh_ctx* ctx, const float* xyz, int64_t stride_by
   const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  return clustered_call(ctx, xyz, false, stride_bytes, n, nullptr, "agh_localize_clustered_fit", cp, lp, handles_out, handle_cap,
-    inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results, fp, true);
+  return clustered_call(ctx, xyz, false, stride_bytes, n, nullptr, "agh_localize_clustered_fit", cp, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, fp, true);
 }
 
-int agh_localize_clustered_fit_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n, const agh_plane_fit_params* fp,
-  const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
-  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+int agh_localize_clustered_fit_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, int64_t n,
+  const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out,
+  int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+  agh_localize_batch_result* results)
 {
-  return clustered_call(ctx, d_xyz, true, stride_bytes, n, nullptr, "agh_localize_clustered_fit_device", cp, lp, handles_out,
-    handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results, fp, true);
+  return clustered_call(ctx, d_xyz, true, stride_bytes, n, nullptr, "agh_localize_clustered_fit_device", cp, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, fp, true);
 }
 
 int agh_localize_depth_clustered_fit(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images, const agh_plane_fit_params* fp,
   const agh_cluster_params* cp, const agh_localize_params* lp, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthSource src{ images, n_images, false, "agh_localize_depth_clustered_fit" };
-  return clustered_call(ctx, nullptr, false, 12, 0, &src, src.who, cp, lp, handles_out, handle_cap, inlier_idx_out, idx_cap,
-    hands_out, hands_cap, samples_out, results, fp, true);
+  const DepthCaptures depth{ images, &n_images, false, "agh_localize_depth_clustered_fit" };
+  return clustered_call(ctx, nullptr, false, 12, 0, &depth, depth.who, cp, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, fp, true);
 }
 
 int agh_localize_depth_clustered_fit_device(agh_ctx* ctx, const agh_depth_image* images, int32_t n_images,
@@ -1020,9 +1031,9 @@ int agh_localize_depth_clustered_fit_device(agh_ctx* ctx, const agh_depth_image*
   int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
   agh_localize_batch_result* results)
 {
-  const DepthSource src{ images, n_images, true, "agh_localize_depth_clustered_fit_device" };
-  return clustered_call(ctx, nullptr, true, 12, 0, &src, src.who, cp, lp, handles_out, handle_cap, inlier_idx_out, idx_cap,
-    hands_out, hands_cap, samples_out, results, fp, true);
+  const DepthCaptures depth{ images, &n_images, true, "agh_localize_depth_clustered_fit_device" };
+  return clustered_call(ctx, nullptr, true, 12, 0, &depth, depth.who, cp, lp,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, fp, true);
 }
 
 // the last chain collected, if it was a fitted one (`fn` refuses otherwise, and mid-chain)
@@ -1030,7 +1041,7 @@ static int plane_fit_getter_check(Ctx* c, const char* fn)
 {
   if (refuse_mid_chain(c, fn))
     return AGH_ERR_STATE;
-  if (c->cluster_objects < 1 || !c->fit_valid)
+  if (!c->results.is(SourceKind::FittedClusters, false))
   {
     c->err = std::string(fn) + ": the last chain this context collected was not a fitted one (or there was none)";
     return AGH_ERR_STATE;
@@ -1045,7 +1056,7 @@ int agh_get_plane_fit(agh_ctx* ctx, agh_plane_fit_result* out)
   Ctx* c = &ctx->c;
   if (int rc = plane_fit_getter_check(c, "agh_get_plane_fit"))
     return rc;
-  *out = c->fit_result;
+  *out = c->results.fit_results[0];
   return AGH_OK;
 }
 
@@ -1056,7 +1067,7 @@ int agh_get_plane_fit_candidates(agh_ctx* ctx, int32_t* idx, double* planes, int
   Ctx* c = &ctx->c;
   if (int rc = plane_fit_getter_check(c, "agh_get_plane_fit_candidates"))
     return rc;
-  const int C = c->fit_candidates;
+  const int C = c->results.fit_candidates[0];
   if ((idx || planes || counts) && cap < C)
   {
     c->err = "agh_get_plane_fit_candidates: cap is below the call's n_candidates";
@@ -1085,7 +1096,7 @@ static int cluster_getter_check(Ctx* c, const char* fn)
 {
   if (refuse_mid_chain(c, fn))
     return AGH_ERR_STATE;
-  if (c->cluster_objects < 1)
+  if (!c->results.is_clustered(false))
   {
     c->err = std::string(fn) + ": the last chain this context collected was not clustered (or there was none)";
     return AGH_ERR_STATE;
@@ -1100,16 +1111,17 @@ int agh_get_cluster_info(agh_ctx* ctx, agh_cluster_info* info, int64_t* n_voxels
   Ctx* c = &ctx->c;
   if (int rc = cluster_getter_check(c, "agh_get_cluster_info"))
     return rc;
-  *info = agh_cluster_info{ c->cluster_info[0], c->cluster_info[1], c->cluster_info[2] };
-  if ((n_voxels || ids) && cap_objects < c->cluster_objects)
+  const ChainResults& R = c->results;
+  *info = agh_cluster_info{ R.cluster_info[0][0], R.cluster_info[0][1], R.cluster_info[0][2] };
+  if ((n_voxels || ids) && cap_objects < R.lists)
   {
     c->err = "agh_get_cluster_info: cap_objects is below the call's max_objects";
     return AGH_ERR_CAPACITY;
   }
   if (n_voxels)
-    std::copy(c->cluster_sizes, c->cluster_sizes + c->cluster_objects, n_voxels);
+    std::copy(R.counts, R.counts + R.lists, n_voxels);
   if (ids)
-    std::copy(c->cluster_ids, c->cluster_ids + c->cluster_objects, ids);
+    std::copy(R.cluster_ids, R.cluster_ids + R.lists, ids);
   return AGH_OK;
 }
 
@@ -1120,15 +1132,16 @@ int agh_get_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap)
   Ctx* c = &ctx->c;
   if (int rc = cluster_getter_check(c, "agh_get_cluster_labels"))
     return rc;
-  if (cap < c->cluster_nv)
+  const int64_t nv = c->results.nv;
+  if (cap < nv)
   {
     c->err = "agh_get_cluster_labels: cap is below the cloud's voxel count";
     return AGH_ERR_CAPACITY;
   }
   AGH_HIPCHK(c, hipSetDevice(c->device));
-  if (c->cluster_nv > 0)
-    AGH_HIPCHK(c, hipMemcpy(labels_out, c->d_cluster_label, (size_t) c->cluster_nv, hipMemcpyDeviceToHost));
-  return (int) c->cluster_nv;
+  if (nv > 0)
+    AGH_HIPCHK(c, hipMemcpy(labels_out, c->d_cluster_label, (size_t) nv, hipMemcpyDeviceToHost));
+  return (int) nv;
 }
 
 int agh_get_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_objects)
@@ -1138,17 +1151,17 @@ int agh_get_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_objects)
   Ctx* c = &ctx->c;
   if (refuse_mid_chain(c, "agh_get_label_counts"))
     return AGH_ERR_STATE;
-  if (c->label_objects < 1)
+  if (!c->results.is(SourceKind::Labels, false))
   {
     c->err = "agh_get_label_counts: the last chain this context collected had no label image (or there was none)";
     return AGH_ERR_STATE;
   }
-  if (cap_objects < c->label_objects)
+  if (cap_objects < c->results.lists)
   {
     c->err = "agh_get_label_counts: cap_objects is below the call's n_objects";
     return AGH_ERR_CAPACITY;
   }
-  std::copy(c->label_counts, c->label_counts + c->label_objects, n_eligible);
+  std::copy(c->results.counts, c->results.counts + c->results.lists, n_eligible);
   return AGH_OK;
 }
 
@@ -1159,12 +1172,12 @@ int agh_get_sample_mask_count(agh_ctx* ctx, int64_t* n_eligible)
   Ctx* c = &ctx->c;
   if (refuse_mid_chain(c, "agh_get_sample_mask_count"))
     return AGH_ERR_STATE;
-  if (c->mask_count < 0)
+  if (!c->results.is(SourceKind::Mask, false))
   {
     c->err = "agh_get_sample_mask_count: the last chain this context collected had no mask (or there was none)";
     return AGH_ERR_STATE;
   }
-  *n_eligible = c->mask_count;
+  *n_eligible = c->results.counts[0];
   return AGH_OK;
 }
 

@@ -32,26 +32,13 @@ struct BatchCall
   int64_t S_tot = 0, n_tot = 0, slot = 0;
   bool classify = false, filters = false;
   double x1 = 0.0, x2 = 0.0;
-  // agh_localize_batch_masked*: capture k's mask, one byte per raw point, where the chain (and a repeat of it) reads it -- in the
-  // state's d_mask at raw_off[k], or in the caller's device memory
-  bool masked = false;
-  std::vector<const uint8_t*> d_mask;
-  // agh_localize_batch_labeled*: the bytes there are labels 1 .. n_objects[k]; first_list: the exclusive prefix sum of n_objects
-  bool labeled = false;
-  std::vector<int32_t> n_objects, first_list;
-  // agh_localize_batch_clustered*: no bytes; capture k's objects are the components of its own cloud under cp[k], n_objects[k] =
-  // cp[k].max_objects lists each (first_list as the labelled batch's).  A repeat of the pass reads the records here.
-  bool clustered = false;
-  std::vector<agh_cluster_params> cp;
-  // agh_localize_batch_clustered_fit*: cp[k].plane is found by the chain (plane_fit.hip) with fp[k]; a repeat reads both copies
-  bool fitted = false;
-  std::vector<agh_plane_fit_params> fp;
-  bool per_object() const { return labeled || clustered; }  // (a list per (capture, object))
-  // the chain's name in the texts of the errors found behind a synchronisation
-  const char* who() const
-  {
-    return fitted ? "agh_localize_batch_clustered_fit" : clustered ? "agh_localize_batch_clustered" : (labeled ? "agh_localize_batch_labeled" : "agh_localize_batch");
-  }
+  // What the samples are drawn under (agh_localize_batch_masked*, _labeled*, _clustered*, _clustered_fit*), as a repeat of the pass
+  // reads it: capture k's bytes in the state's d_mask at raw_off[k] or in the caller's device memory, and copies of the records;
+  // first_list: the exclusive prefix sum of the captures' objects
+  StoredSource source;
+  std::vector<int32_t> first_list;
+  bool per_object() const { return source.per_object(); }  // (a list per (capture, object))
+  const char* who() const { return source.who; }  // the chain's name in the texts of the errors found behind a synchronisation
 };
 
 struct LocalizeBatchState
@@ -395,6 +382,14 @@ int ensure_fit_tables(Ctx* c, LocalizeBatchState* b)
   return AGH_OK;
 }
 
+// A per-capture host table (pinned) up to its device twin, queued on st; a failure has drained the stream (chain_fail).
+template <typename T>
+int table_to_device(Ctx* c, T* d_table, const T* h_table, int count, hipStream_t st)
+{
+  AGH_HIPCHK_OR(c, hipMemcpyAsync(d_table, h_table, sizeof(T) * (size_t) count, hipMemcpyHostToDevice, st), chain_fail(c, AGH_ERR_HIP));
+  return AGH_OK;
+}
+
 // The list table of the call, on the host and queued to the device: list l's span of the sample list, its capture's sample
 // count, seed and workspace (B.lp[list_cap[l]]), and which object of it the list is.
 int fill_list_table(Ctx* c, LocalizeBatchState* b, hipStream_t st)
@@ -470,208 +465,6 @@ struct ActiveGuard
 };
 
 const char* const kBadArguments = "agh_localize_batch: bad arguments (1 <= n_captures <= 64; see include/agh.h)";
-
-// A batch given as depth images (include/agh.h, agh_localize_depth_batch*): the batch chain's fourth source kind, beside host
-// points, device points and the staged batch.  k_deproject_batch (depth.hip) fills the context's raw buffer, capture after
-// capture; from there on the chain is the points batch's.
-struct DepthBatchSource
-{
-  const agh_depth_image* images;  // the flat array in capture order: capture k's are the next n_images[k]
-  const int32_t* n_images;
-  bool on_device;
-  const char* who;  // the entry point, for the error texts
-};
-
-// The masks of a masked batch (include/agh.h, agh_localize_batch_masked*): one byte per raw point per capture (points), or one
-// agh_sample_mask per image, parallel to the images (depth).  Host masks and all depth masks are copied, packed in point order,
-// into the state's d_mask; a device points mask is read in place.
-struct BatchMaskSource
-{
-  const uint8_t* const* points;   // points form: n_captures pointers
-  const agh_sample_mask* images;  // depth form: one per image of the flat array
-  bool on_device;
-  const char* who;
-  const int32_t* n_objects = nullptr;  // agh_localize_batch_labeled*: the bytes are labels 1 .. n_objects[k] (NULL: masks)
-  bool labeled = false;
-  // agh_localize_batch_clustered*: no bytes at all, n_captures records; capture k has cluster[k].max_objects lists
-  const agh_cluster_params* cluster = nullptr;
-  bool clustered = false;
-  // agh_localize_batch_clustered_fit*: ... and n_captures records of the fit, cluster[k].plane unread
-  const agh_plane_fit_params* fit = nullptr;
-  bool fitted = false;
-  bool per_object() const { return labeled || clustered; }
-  int32_t objects(int k) const { return clustered ? cluster[k].max_objects : n_objects[k]; }
-};
-
-// the rules a clustered batch adds (include/agh.h, agh_localize_batch_clustered*, 4); the text names the capture and the field
-int batch_cluster_check(Ctx* c, const BatchMaskSource* mask, const agh_localize_params* lp, int C)
-{
-  auto bad = [&](const std::string& what) {
-    c->err = std::string(mask->who) + ": " + what;
-    return AGH_ERR_INVALID_ARGUMENT;
-  };
-  if (mask->fitted && !mask->fit)
-    return bad("fp is NULL (every capture of a fitted batch has its agh_plane_fit_params record)");
-  if (!mask->cluster)
-    return bad("cp is NULL (every capture of a clustered batch has its agh_cluster_params record)");
-  int64_t lists = 0, samples = 0;
-  for (int k = 0; k < C; k++)
-  {
-    const std::string cap = "capture " + std::to_string(k);
-    agh_cluster_params q = mask->cluster[k];
-    if (mask->fitted)  // (the plane is the chain's to find: the caller's is neither read nor validated)
-    {
-      const std::string fit_fault = plane_fit_params_fault(mask->fit[k]);
-      if (!fit_fault.empty())
-        return bad(cap + ": " + fit_fault);
-      q.plane[0] = q.plane[1] = q.plane[3] = 0.0;
-      q.plane[2] = 1.0;
-    }
-    const std::string fault = cluster_params_fault(q);
-    if (!fault.empty())
-      return bad(cap + ": " + fault);
-    lists += mask->cluster[k].max_objects;
-    samples += (int64_t) mask->cluster[k].max_objects * lp[k].n_samples;
-    if (lists > kMaxClouds)
-      return bad(cap + ": more than 64 lists in all (the sum of max_objects up to this capture)");
-    if (samples > (1 << 24))
-      return bad(cap + ": more than 2^24 samples in all (the sum of max_objects x n_samples up to this capture)");
-    if (lp[k].sample_idx)
-      return bad(cap + ": sample_idx must be NULL (the lists are drawn on the objects the call finds)");
-  }
-  return AGH_OK;
-}
-
-// the rules a labelled batch adds (include/agh.h, agh_localize_batch_labeled*, 1 and 2); the text names the capture (and the image)
-int batch_label_check(Ctx* c, const BatchMaskSource* mask, const DepthBatchSource* depth, const agh_localize_params* lp, int C)
-{
-  auto bad = [&](const std::string& what) {
-    c->err = std::string(mask->who) + ": " + what;
-    return AGH_ERR_INVALID_ARGUMENT;
-  };
-  if (!mask->n_objects)
-    return bad("n_objects is NULL");
-  if (depth ? !mask->images : !mask->points)
-    return bad("labels is NULL (every capture of a labelled batch has labels)");
-  int64_t lists = 0, samples = 0;
-  for (int k = 0, i0 = 0; k < C; k++)
-  {
-    const std::string cap = "capture " + std::to_string(k);
-    if (mask->n_objects[k] < 1 || mask->n_objects[k] > kMaxClouds)
-      return bad(cap + ": n_objects must be 1 .. 64");
-    lists += mask->n_objects[k];
-    samples += (int64_t) mask->n_objects[k] * lp[k].n_samples;
-    if (lists > kMaxClouds)
-      return bad(cap + ": more than 64 lists in all (the sum of n_objects up to this capture)");
-    if (samples > (1 << 24))
-      return bad(cap + ": more than 2^24 samples in all (the sum of n_objects x n_samples up to this capture)");
-    if (lp[k].sample_idx)
-      return bad(cap + ": labels together with sample_idx (an explicit list needs no labels)");
-    if (!depth)
-    {
-      if (!mask->points[k])
-        return bad(cap + ": the label array is NULL");
-      continue;
-    }
-    bool any = false;
-    for (int j = 0; j < depth->n_images[k]; j++)
-    {
-      const agh_sample_mask& m = mask->images[i0 + j];
-      if (!m.data)
-        continue;
-      any = true;
-      if (m.row_stride_bytes < depth->images[i0 + j].width)
-        return bad(cap + ", image " + std::to_string(j) + ": the label image's row_stride_bytes is below the image's width");
-    }
-    if (!any)
-      return bad(cap + ": every label image's data is NULL (no pixel would belong to an object)");
-    i0 += depth->n_images[k];
-  }
-  return AGH_OK;
-}
-
-// the rules a masked batch adds to its unmasked twin's; the text names the capture (and the image)
-int batch_mask_check(Ctx* c, const BatchMaskSource* mask, const DepthBatchSource* depth, const agh_localize_params* lp, int C)
-{
-  auto bad = [&](const std::string& what) {
-    c->err = std::string(mask->who) + ": " + what;
-    return AGH_ERR_INVALID_ARGUMENT;
-  };
-  if (depth ? !mask->images : !mask->points)
-    return bad("masks is NULL (every capture of a masked batch has a mask)");
-  for (int k = 0, i0 = 0; k < C; k++)
-  {
-    const std::string cap = "capture " + std::to_string(k);
-    if (lp[k].sample_idx)
-      return bad(cap + ": a mask together with sample_idx (an explicit list needs no mask)");
-    if (!depth)
-    {
-      if (!mask->points[k])
-        return bad(cap + ": the mask is NULL");
-      continue;
-    }
-    bool any = false;
-    for (int j = 0; j < depth->n_images[k]; j++)
-    {
-      const agh_sample_mask& m = mask->images[i0 + j];
-      if (!m.data)
-        continue;
-      any = true;
-      if (m.row_stride_bytes < depth->images[i0 + j].width)
-        return bad(cap + ", image " + std::to_string(j) + ": the mask's row_stride_bytes is below the image's width");
-    }
-    if (!any)
-      return bad(cap + ": every mask's data is NULL (no pixel would be eligible)");
-    i0 += depth->n_images[k];
-  }
-  return AGH_OK;
-}
-
-// the masks to where the chain reads them, on st (see BatchMaskSource); B.d_mask[k] says where
-int batch_masks_to_device(Ctx* c, LocalizeBatchState* b, const BatchMaskSource* mask, const DepthBatchSource* depth, hipStream_t st)
-{
-  BatchCall& B = b->call;
-  const int C = B.C;
-  B.masked = !mask->labeled;
-  B.d_mask.resize((size_t) C);
-  if (!depth && mask->on_device)
-  {
-    for (int k = 0; k < C; k++)
-      B.d_mask[k] = mask->points[k];
-    return AGH_OK;
-  }
-  if (B.n_tot > b->mask_cap || !b->d_mask)
-  {
-    b->mask_cap = 0;
-    if (int rc = dev_alloc(c, &b->d_mask, (size_t) std::max<int64_t>(B.n_tot, 1)))
-      return rc;
-    b->mask_cap = std::max<int64_t>(B.n_tot, 1);
-  }
-  const hipMemcpyKind kind = mask->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  for (int k = 0, i0 = 0; k < C; k++)
-  {
-    uint8_t* dst = b->d_mask + B.raw_off[k];
-    B.d_mask[k] = dst;
-    if (!depth)
-    {
-      if (B.n[k] > 0)
-        AGH_HIPCHK(c, hipMemcpyAsync(dst, mask->points[k], (size_t) B.n[k], kind, st));
-      continue;
-    }
-    for (int j = 0; j < depth->n_images[k]; j++)
-    {
-      const size_t W = (size_t) depth->images[i0 + j].width, H = (size_t) depth->images[i0 + j].height;
-      const agh_sample_mask& m = mask->images[i0 + j];
-      if (!m.data)
-        AGH_HIPCHK(c, hipMemsetAsync(dst, 0, W * H, st));
-      else
-        AGH_HIPCHK(c, hipMemcpy2DAsync(dst, W, m.data, (size_t) m.row_stride_bytes, W, H, kind, st));
-      dst += W * H;
-    }
-    i0 += depth->n_images[k];
-  }
-  return AGH_OK;
-}
 
 // Steps 2 to 5 of the batch c->lbatch->call, queued on the context's stream: preprocessing, the batch of clouds, the sample list,
 // search -> classification -> kept hands per capture -> handle search.  Nothing waits, except the first batch of a context (or one
@@ -822,50 +615,45 @@ int batch_pass(agh_ctx* ctx)
     AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_local, b->h_samples, sizeof(int32_t) * (size_t) S_tot, hipMemcpyHostToDevice, st),
       chain_fail(c, AGH_ERR_HIP));
   }
-  if (B.masked)  // (for S_tot = 0 too: the M_k are what a caller sizes the S_k with)
+  const StoredSource& src = B.source;
+  BatchStageCommon common;  // (what every sample stage is given: the preprocessing and the grid build are queued)
+  common.vb = vb;
+  common.C = C;
+  common.L = B.L;
+  common.n_max = n_max;
+  common.n_tot = n_tot;
+  common.S_tot = S_tot;
+  common.cell = cell;
+  common.code = c->d_vox_code;
+  common.bitmap = b->d_bitmap;
+  common.blk2 = b->d_blk2;
+  common.cloud_off = c->d_cloud_off;
+  common.tab = b->d_tab;
+  common.d_out = c->d_idx_own;
+  common.h_out = b->h_samples;
+  if (src.kind == SourceKind::Mask)  // (for S_tot = 0 too: the M_k are what a caller sizes the S_k with)
   {
     if ((rc = ensure_mask_slots(c, b, n_tot)) != AGH_OK)
       return chain_fail(c, rc);
-    for (int k = 0; k < C; k++)
-      b->h_mptr[k] = B.d_mask[k];
-    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_mptr, b->h_mptr, sizeof(const uint8_t*) * (size_t) C, hipMemcpyHostToDevice, st),
-      chain_fail(c, AGH_ERR_HIP));
-    BatchMaskStage m;
-    m.vb = vb;
-    m.C = C;
-    m.n_max = n_max;
-    m.S_tot = S_tot;
-    m.cell = cell;
-    m.code = c->d_vox_code;
-    m.mask = b->d_mptr;
-    m.bitmap = b->d_bitmap;
-    m.blk2 = b->d_blk2;
-    m.cloud_off = c->d_cloud_off;
-    m.elig = b->d_elig;
-    m.eblk = b->d_eblk;
-    m.total = b->d_mtotal;
-    m.list = b->d_elist;
-    m.tab = b->d_tab;
-    m.d_out = c->d_idx_own;
-    m.h_out = b->h_samples;
-    m.h_total = b->h_mtotal;
+    std::copy(src.d_bytes.begin(), src.d_bytes.end(), b->h_mptr);
+    if ((rc = table_to_device(c, b->d_mptr, b->h_mptr, C, st)) != AGH_OK)
+      return rc;
+    BatchMaskStage m{ common, b->d_mptr, b->d_elig, b->d_eblk, b->d_mtotal, b->d_elist, b->h_mtotal };
     if ((rc = sample_mask_stage_batch(c, m, st)) != AGH_OK)
       return chain_fail(c, rc);
   }
-  else if (B.clustered)  // (for S_tot = 0 too: the objects found are a result of their own)
+  else if (src.clustered())  // (for S_tot = 0 too: the objects found are a result of their own)
   {
     if ((rc = ensure_cluster_tables(c, b)) != AGH_OK)
       return chain_fail(c, rc);
     for (int k = 0; k < C; k++)
     {
-      b->h_lcap[k] = LabelCapture{ B.n_objects[k], B.first_list[k] };
-      b->h_ccap[k] = cluster_dev(B.cp[k]);
+      b->h_lcap[k] = LabelCapture{ src.n_objects[k], B.first_list[k] };
+      b->h_ccap[k] = cluster_dev(src.cluster[k]);
     }
-    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_lcap, b->h_lcap, sizeof(LabelCapture) * (size_t) C, hipMemcpyHostToDevice, st),
-      chain_fail(c, AGH_ERR_HIP));
-    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_ccap, b->h_ccap, sizeof(ClusterDev) * (size_t) C, hipMemcpyHostToDevice, st),
-      chain_fail(c, AGH_ERR_HIP));
-    if (B.fitted)  // (behind the records' upload: k_fit_finish_batch writes capture k's plane into d_ccap[k])
+    if ((rc = table_to_device(c, b->d_lcap, b->h_lcap, C, st)) != AGH_OK || (rc = table_to_device(c, b->d_ccap, b->h_ccap, C, st)) != AGH_OK)
+      return rc;
+    if (src.fitted())  // (behind the records' upload: k_fit_finish_batch writes capture k's plane into d_ccap[k])
     {
       if ((rc = ensure_fit_tables(c, b)) != AGH_OK)
         return chain_fail(c, rc);
@@ -873,70 +661,33 @@ int batch_pass(agh_ctx* ctx)
       {
         // (camera 0's origin in force for capture k: its row of the table, or the context's own; the setter refuses mid-chain)
         const double* o = c->cam_tab_rows == C ? c->h_cam_tab + 6 * k : c->p.cam_origin[0];
-        const agh_plane_fit_params& f = B.fp[k];
+        const agh_plane_fit_params& f = src.fit[k];
         b->h_fcap[k] = PlaneFitDev{ f.n_candidates, f.refine, f.min_inliers, 0, f.distance_threshold, (unsigned long long) f.seed,
           { o[0], o[1], o[2] } };
       }
-      AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_fcap, b->h_fcap, sizeof(PlaneFitDev) * (size_t) C, hipMemcpyHostToDevice, st),
-        chain_fail(c, AGH_ERR_HIP));
-      BatchFitStage f;
-      f.vb = vb;
-      f.C = C;
-      f.n_max = n_max;
-      f.cloud_off = c->d_cloud_off;
-      f.fps = b->d_fcap;
-      f.fbs = b->d_fit;
-      f.cps = b->d_ccap;
-      f.h_results = b->h_fit_result;
+      if ((rc = table_to_device(c, b->d_fcap, b->h_fcap, C, st)) != AGH_OK)
+        return rc;
+      BatchFitStage f{ common, b->d_fcap, b->d_fit, b->d_ccap, b->h_fit_result };
       if ((rc = plane_fit_stage_batch(c, f, st)) != AGH_OK)
         return chain_fail(c, rc);
     }
-    BatchLabelStage m;  // (no labels, codes or bitmaps: the object sets come from the clouds, behind the grid build queued above)
-    m.vb = vb;
-    m.C = C;
-    m.L = B.L;
-    m.n_max = n_max;
-    m.n_tot = n_tot;
-    m.S_tot = S_tot;
-    m.cell = cell;
-    m.lists = b->d_lcap;
-    m.cloud_off = c->d_cloud_off;
-    m.tab = b->d_tab;
-    m.d_out = c->d_idx_own;
-    m.h_out = b->h_samples;
+    // (no labels: the object sets come from the clouds, behind the grid build queued above)
+    BatchLabelStage m{ common, nullptr, b->d_lcap };
     if ((rc = sample_cluster_stage_batch(c, m, b->d_ccap, st)) != AGH_OK)
       return chain_fail(c, rc);
   }
-  else if (B.labeled)  // (for S_tot = 0 too, as the masks')
+  else if (src.kind == SourceKind::Labels)  // (for S_tot = 0 too, as the masks')
   {
     if ((rc = ensure_label_tables(c, b)) != AGH_OK)
       return chain_fail(c, rc);
     for (int k = 0; k < C; k++)
     {
-      b->h_mptr[k] = B.d_mask[k];
-      b->h_lcap[k] = LabelCapture{ B.n_objects[k], B.first_list[k] };
+      b->h_mptr[k] = src.d_bytes[k];
+      b->h_lcap[k] = LabelCapture{ src.n_objects[k], B.first_list[k] };
     }
-    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_mptr, b->h_mptr, sizeof(const uint8_t*) * (size_t) C, hipMemcpyHostToDevice, st),
-      chain_fail(c, AGH_ERR_HIP));
-    AGH_HIPCHK_OR(c, hipMemcpyAsync(b->d_lcap, b->h_lcap, sizeof(LabelCapture) * (size_t) C, hipMemcpyHostToDevice, st),
-      chain_fail(c, AGH_ERR_HIP));
-    BatchLabelStage m;
-    m.vb = vb;
-    m.C = C;
-    m.L = B.L;
-    m.n_max = n_max;
-    m.n_tot = n_tot;
-    m.S_tot = S_tot;
-    m.cell = cell;
-    m.code = c->d_vox_code;
-    m.labels = b->d_mptr;
-    m.lists = b->d_lcap;
-    m.bitmap = b->d_bitmap;
-    m.blk2 = b->d_blk2;
-    m.cloud_off = c->d_cloud_off;
-    m.tab = b->d_tab;
-    m.d_out = c->d_idx_own;
-    m.h_out = b->h_samples;
+    if ((rc = table_to_device(c, b->d_mptr, b->h_mptr, C, st)) != AGH_OK || (rc = table_to_device(c, b->d_lcap, b->h_lcap, C, st)) != AGH_OK)
+      return rc;
+    BatchLabelStage m{ common, b->d_mptr, b->d_lcap };
     if ((rc = sample_label_stage_batch(c, m, st)) != AGH_OK)
       return chain_fail(c, rc);
   }
@@ -955,12 +706,14 @@ int batch_pass(agh_ctx* ctx)
 // agh_localize_batch_begin: the arguments checked and copied, the captures up (or adopted from agh_localize_batch_stage, or read in
 // place), steps 2 to 5 queued.
 int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
-  const agh_localize_params* lp, int32_t n_captures, const DepthBatchSource* depth = nullptr, const BatchMaskSource* mask = nullptr)
+  const agh_localize_params* lp, int32_t n_captures, const DepthCaptures* depth = nullptr, const SampleSource* src = nullptr)
 {
+  if (!ctx)
+    return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
   LocalizeState& L = c->loc;
   const int C = n_captures;
-  const std::string who = mask ? mask->who : (depth ? depth->who : "agh_localize_batch");
+  const std::string who = src ? src->who : (depth ? depth->who : "agh_localize_batch");
   if (L.active)
   {
     c->err = who + ": a localize chain is in flight on this context (agh_localize_end first)";
@@ -992,7 +745,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   }
   else if (C < 1 || C > kMaxClouds || !xyz || !stride_bytes || !n || !lp)
   {
-    c->err = mask ? who + ": bad arguments (1 <= n_captures <= 64; see include/agh.h)" : std::string(kBadArguments);
+    c->err = src ? who + ": bad arguments (1 <= n_captures <= 64; see include/agh.h)" : std::string(kBadArguments);
     return AGH_ERR_INVALID_ARGUMENT;
   }
   int64_t n_tot = 0, S_tot = 0;
@@ -1015,14 +768,14 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     n_tot += n[k];
     S_tot += p.n_samples;
   }
-  const bool labeled = mask && mask->labeled, clustered = mask && mask->clustered;
-  if (labeled || clustered)  // (before the sums' limits: such a batch counts its samples per list, and says which capture went too far)
+  const bool per_object = src && src->per_object();
+  if (per_object)  // (before the sums' limits: such a batch counts its samples per list, and says which capture went too far)
   {
-    if (int rc = clustered ? batch_cluster_check(c, mask, lp, C) : batch_label_check(c, mask, depth, lp, C))
+    if (int rc = sample_source_check(c, *src, depth, lp, C, false))
       return rc;
     S_tot = 0;
     for (int k = 0; k < C; k++)
-      S_tot += (int64_t) mask->objects(k) * lp[k].n_samples;
+      S_tot += (int64_t) src->objects(k) * lp[k].n_samples;
   }
   if (n_tot >= (1ll << 30) || S_tot > (1 << 24))
   {
@@ -1037,8 +790,8 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   if (cam_table_mismatch(c, who.c_str(), C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
     return AGH_ERR_INVALID_ARGUMENT;                    // the table stays the context's until agh_localize_batch_end: the setter
                                                         // refuses mid-chain, so the repeats search with it too)
-  if (mask && !labeled && !clustered)
-    if (int rc = batch_mask_check(c, mask, depth, lp, C))
+  if (src && !per_object)  // (a mask adds nothing to the sums: its rules come behind the limits and the origin table)
+    if (int rc = sample_source_check(c, *src, depth, lp, C, false))
       return rc;
   double x1 = 0.0, x2 = 0.0;
   if (!handle_thresholds(&x1, &x2))
@@ -1067,12 +820,9 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     B.raw_off[k] = o;
   for (int k = 0; k < C; k++)
   {
-    const int K = labeled || clustered ? mask->objects(k) : 1;
-    if (labeled || clustered)
-    {
-      B.n_objects.push_back(K);
+    const int K = per_object ? src->objects(k) : 1;
+    if (per_object)
       B.first_list.push_back((int32_t) B.list_cap.size());
-    }
     for (int j = 0; j < K; j++)
     {
       B.list_cap.push_back(k);
@@ -1080,20 +830,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     }
   }
   B.L = (int) B.list_cap.size();
-  B.labeled = labeled;
-  B.clustered = clustered;
-  if (clustered)
-    B.cp.assign(mask->cluster, mask->cluster + C);
-  B.fitted = clustered && mask->fitted;
-  if (B.fitted)
-  {
-    B.fp.assign(mask->fit, mask->fit + C);
-    for (int k = 0; k < C; k++)  // (the caller's plane is not read: the uploaded record carries a placeholder until the fit's)
-    {
-      B.cp[k].plane[0] = B.cp[k].plane[1] = B.cp[k].plane[3] = 0.0;
-      B.cp[k].plane[2] = 1.0;
-    }
-  }
+  B.source.keep(src, C, false);
   B.soff.resize((size_t) B.L + 1);
   B.soff[0] = 0;
   for (int l = 0; l < B.L; l++)
@@ -1132,7 +869,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
       need += n[k] * (B.dev_stride[k] / 4);
     }
     // (a masked begin of host data never adopts a staged set: it drops a pending one as a begin of another kind does)
-    const bool adopt = !mask && L.staged_is(xyz, stride_bytes, n, C, true) && c->d_stage_xyz;
+    const bool adopt = !src && L.staged_is(xyz, stride_bytes, n, C, true) && c->d_stage_xyz;
     // A staged batch that is this one: it is (or is about to be) in the second raw buffer -- the two buffers change places and the
     // chain waits for the copies.  Anything else that is staged (another batch, a capture of agh_localize_stage) is dropped: its
     // copy may still read the caller's source, so the chain waits for it too and agh_localize_batch_end's synchronisation covers it.
@@ -1157,7 +894,9 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
       off += n[k] * (B.dev_stride[k] / 4);
     }
   }
-  if (mask && !mask->clustered && (rc = batch_masks_to_device(c, b, mask, depth, st)) != AGH_OK)
+  if (src && src->has_bytes() &&
+      (rc = sample_source_to_device(c, *src, depth, C, B.n.data(), B.raw_off.data(), n_tot, &b->d_mask, &b->mask_cap, st,
+         &B.source.d_bytes)) != AGH_OK)
     return chain_fail(c, rc);  // (the captures' copies may be in flight)
   ActiveGuard guard(c);
   if ((rc = batch_pass(ctx)) != AGH_OK)
@@ -1175,8 +914,7 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
 
 // agh_localize_batch_end: the one synchronisation and everything behind it -- the outgrown-bitmap repeat, the capacity-class
 // repeat, the sequential-handle-walk repeat, the copy-out.  The chain is over whatever this returns.
-int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
-  agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
+int batch_end_impl(agh_ctx* ctx, const ChainOutputs& out, agh_localize_batch_result* results)
 {
   Ctx* c = &ctx->c;
   LocalizeBatchState* b = c->lbatch;
@@ -1186,13 +924,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   const int64_t S_tot = B.S_tot;
   c->loc.active = false;
   c->loc.batch = false;
-  c->mask_count = -1;  // (agh_get_sample_mask_count: the last chain collected had no mask)
-  c->label_objects = 0;  // (... and no label image)
-  c->cluster_objects = 0;  // (... and no clusters)
-  c->batch_mask_captures = 0;  // (agh_get_batch_mask_counts: set below, behind the synchronisation, if this batch is masked)
-  c->batch_label_lists = 0;    // (agh_get_batch_label_counts likewise, if it is labelled)
-  c->batch_cluster_captures = 0;  // (agh_get_batch_cluster_info / _labels likewise, if it is clustered)
-  c->batch_fit_captures = 0;      // (agh_get_batch_plane_fit / _candidates likewise, if it is fitted)
+  c->results = ChainResults{};
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)
@@ -1231,45 +963,44 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
     b->last_words = words;
     break;
   }
-  if (B.masked)
-  {
-    for (int k = 0; k < C; k++)
-      c->batch_mask_counts[k] = (int64_t) b->h_mtotal[k];
-    c->batch_mask_captures = C;
-  }
-  if (B.labeled)
-  {
-    for (int l = 0; l < B.L; l++)
-      c->batch_label_counts[l] = (int64_t) c->h_label_counts[l];
-    c->batch_label_lists = B.L;
-  }
   // the bound batch is now the true one
   std::vector<int64_t> voff(C + 1, 0), nv((size_t) B.L);
   for (int k = 0; k < C; k++)
     voff[k + 1] = voff[k] + (int64_t) (b->h_desc[k].n_vox[0] + b->h_desc[k].n_vox[1]);
-  if (B.clustered)
+  ChainResults& R = c->results;
+  R.kind = B.source.kind;
+  R.batch = true;
+  R.captures = C;
+  if (R.kind == SourceKind::Mask)
+  {
+    R.lists = C;
+    for (int k = 0; k < C; k++)
+      R.counts[k] = (int64_t) b->h_mtotal[k];
+  }
+  else if (R.kind == SourceKind::Labels)
+  {
+    R.lists = B.L;
+    for (int l = 0; l < B.L; l++)
+      R.counts[l] = (int64_t) c->h_label_counts[l];
+  }
+  else if (B.source.clustered())
   {
     // (the table of k_cluster_select_batch: four counts per capture, then the M_l and the capture-local ids in list order; the
     // M_l equal the compaction's h_label_counts)
     const long long* t = c->h_cluster_table;
+    R.lists = B.L;
+    R.nv = voff[C];
     for (int k = 0; k < C; k++)
-      std::copy(t + 4 * k, t + 4 * k + 4, c->batch_cluster_info[k]);
+      std::copy(t + 4 * k, t + 4 * k + 4, R.cluster_info[k]);
     for (int l = 0; l < B.L; l++)
     {
-      c->batch_cluster_sizes[l] = (int64_t) t[4 * kMaxClouds + l];
-      c->batch_cluster_ids[l] = (int32_t) t[5 * kMaxClouds + l];
+      R.counts[l] = (int64_t) t[4 * kMaxClouds + l];
+      R.cluster_ids[l] = (int32_t) t[5 * kMaxClouds + l];
     }
-    c->batch_cluster_nv = voff[C];
-    c->batch_cluster_lists = B.L;
-    c->batch_cluster_captures = C;
-    if (B.fitted)  // (the records k_fit_finish_batch wrote into pinned memory: here with the chain's one synchronisation)
+    for (int k = 0; k < C && B.source.fitted(); k++)  // (the records k_fit_finish_batch wrote into pinned memory)
     {
-      for (int k = 0; k < C; k++)
-      {
-        c->batch_fit_results[k] = b->h_fit_result[k];
-        c->batch_fit_candidates[k] = B.fp[k].n_candidates;
-      }
-      c->batch_fit_captures = C;
+      R.fit_results[k] = b->h_fit_result[k];
+      R.fit_candidates[k] = B.source.fit[k].n_candidates;
     }
   }
   for (int l = 0; l < B.L; l++)  // (a list's voxel count is its capture's)
@@ -1279,8 +1010,7 @@ int batch_end_impl(agh_ctx* ctx, agh_handle* handles_out, int64_t handle_cap, in
   c->cloud_off = voff;
   c->cloud_off_on_device = true;
   c->n_clouds = C;
-  return batch_collect(ctx, B.who(), "capture", nv.data(), handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results);
+  return batch_collect(ctx, B.who(), "capture", nv.data(), out, results);
 }
 
 void zero_results(agh_localize_batch_result* results, int C)
@@ -1292,9 +1022,8 @@ void zero_results(agh_localize_batch_result* results, int C)
 
 // agh_localize_batch[_device] = begin + end
 int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int64_t* stride_bytes, const int64_t* n,
-  const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
-  int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results,
-  const DepthBatchSource* depth = nullptr, const BatchMaskSource* mask = nullptr)
+  const agh_localize_params* lp, int32_t n_captures, const ChainOutputs& out, agh_localize_batch_result* results,
+  const DepthCaptures* depth = nullptr, const SampleSource* src = nullptr)
 {
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
@@ -1302,36 +1031,35 @@ int batch_call(agh_ctx* ctx, const float* const* xyz, bool on_device, const int6
   {
     // (a labelled batch has a record per list; arguments that do not say how many lists there are get none zeroed)
     int64_t lists = n_captures;
-    if (mask && mask->per_object())
+    if (src && src->per_object())
     {
       lists = 0;
-      if ((mask->clustered ? mask->cluster != nullptr : mask->n_objects != nullptr) && n_captures >= 1 && n_captures <= kMaxClouds)
+      if ((src->clustered() ? src->cluster != nullptr : src->n_objects != nullptr) && n_captures >= 1 && n_captures <= kMaxClouds)
         for (int k = 0; k < n_captures && lists <= kMaxClouds; k++)
-          lists = mask->objects(k) >= 1 && mask->objects(k) <= kMaxClouds ? lists + mask->objects(k) : kMaxClouds + 1;
+          lists = src->objects(k) >= 1 && src->objects(k) <= kMaxClouds ? lists + src->objects(k) : kMaxClouds + 1;
     }
     zero_results(results, lists <= kMaxClouds ? (int) lists : 0);
   }
   if (c->loc.active)
   {
-    c->err = std::string(mask ? mask->who : (depth ? depth->who : "agh_localize_batch")) + ": a localize chain is in flight on this context (agh_localize_end first)";
+    c->err = std::string(src ? src->who : (depth ? depth->who : "agh_localize_batch")) + ": a localize chain is in flight on this context (agh_localize_end first)";
     return AGH_ERR_STATE;
   }
-  if (bad_outputs(handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap))
+  if (out.bad())
   {
-    c->err = depth || mask ? std::string(mask ? mask->who : depth->who) + ": bad output arguments (see include/agh.h)" : std::string(kBadArguments);
+    c->err = depth || src ? std::string(src ? src->who : depth->who) + ": bad output arguments (see include/agh.h)" : std::string(kBadArguments);
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  const int rc = batch_begin_impl(ctx, xyz, on_device, stride_bytes, n, lp, n_captures, depth, mask);
+  const int rc = batch_begin_impl(ctx, xyz, on_device, stride_bytes, n, lp, n_captures, depth, src);
   if (rc != AGH_OK)
     return rc;
-  return batch_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+  return batch_end_impl(ctx, out, results);
 }
 }  // namespace
 
 // The end of a chain over the batch state's C lists, behind its synchronisation and with its cloud bound: chain_collect's repeats
 // and limits, results[k], and the outputs' assembly from the pinned slots, spans in list order (agh_internal.h).
-int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t* nv, agh_handle* handles_out, int64_t handle_cap,
-  int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
+int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t* nv, const ChainOutputs& out,
   agh_localize_batch_result* results)
 {
   Ctx* c = &ctx->c;
@@ -1359,9 +1087,9 @@ int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t
     tot_hands += h[5];
   }
   c->last_nout = std::min<int64_t>(n_hyp_tot, c->s_cap * 8);
-  if (samples_out && S_tot > 0)
-    std::memcpy(samples_out, b->h_samples, sizeof(int32_t) * (size_t) S_tot);
-  if (tot_handles > handle_cap || tot_idx > idx_cap || (hands_out && tot_hands > hands_cap))
+  if (out.samples && S_tot > 0)
+    std::memcpy(out.samples, b->h_samples, sizeof(int32_t) * (size_t) S_tot);
+  if (tot_handles > out.handle_cap || tot_idx > out.idx_cap || (out.hands && tot_hands > out.hands_cap))
   {
     c->err = std::string(who) + ": output buffers too small (the counts are in results)";
     return AGH_ERR_CAPACITY;
@@ -1373,11 +1101,11 @@ int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t
     const size_t base = (size_t) k * (size_t) b->h_slot;
     if (h[0] > 0)
     {
-      std::memcpy(handles_out + oh, b->h_handles + base, sizeof(agh_handle) * (size_t) h[0]);
-      std::memcpy(inlier_idx_out + oi, b->h_idx + base, sizeof(int32_t) * (size_t) h[1]);
+      std::memcpy(out.handles + oh, b->h_handles + base, sizeof(agh_handle) * (size_t) h[0]);
+      std::memcpy(out.inlier_idx + oi, b->h_idx + base, sizeof(int32_t) * (size_t) h[1]);
     }
-    if (hands_out && h[5] > 0)
-      std::memcpy(hands_out + ok, b->h_hands + base, sizeof(agh_hypothesis) * (size_t) h[5]);
+    if (out.hands && h[5] > 0)
+      std::memcpy(out.hands + ok, b->h_hands + base, sizeof(agh_hypothesis) * (size_t) h[5]);
     oh += h[0];
     oi += h[1];
     ok += h[5];
@@ -1427,31 +1155,27 @@ int agh_localize_batch(agh_ctx* ctx, const float* const* xyz, const int64_t* str
   const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results);
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
 
 int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results);
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results);
 }
 
 int agh_localize_batch_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
   return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures);
 }
 
 int agh_localize_batch_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
   return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures);
 }
 
@@ -1460,36 +1184,32 @@ int agh_localize_depth_batch(agh_ctx* ctx, const agh_depth_image* images, const 
   int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap,
   agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch" };
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch" };
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth);
 }
 
 int agh_localize_depth_batch_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
   const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_device" };
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_device" };
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth);
 }
 
 int agh_localize_depth_batch_begin(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
   const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_begin" };
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch_begin" };
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth);
 }
 
 int agh_localize_depth_batch_begin_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
   const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_begin_device" };
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_begin_device" };
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth);
 }
 
 // ---- the masked forms (include/agh.h): the batch chains with every capture's samples drawn under its own mask ----
@@ -1499,9 +1219,9 @@ int agh_localize_batch_masked(agh_ctx* ctx, const float* const* xyz, const int64
   int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
   agh_localize_batch_result* results)
 {
-  const BatchMaskSource m{ masks, nullptr, false, "agh_localize_batch_masked" };
-  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, nullptr, &m);
+  const SampleSource m = mask_source(masks, nullptr, false, "agh_localize_batch_masked");
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, nullptr, &m);
 }
 
 int agh_localize_batch_masked_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
@@ -1509,26 +1229,22 @@ int agh_localize_batch_masked_device(agh_ctx* ctx, const float* const* xyz, cons
   int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
   agh_localize_batch_result* results)
 {
-  const BatchMaskSource m{ masks, nullptr, true, "agh_localize_batch_masked_device" };
-  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, nullptr, &m);
+  const SampleSource m = mask_source(masks, nullptr, true, "agh_localize_batch_masked_device");
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, nullptr, &m);
 }
 
 int agh_localize_batch_masked_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const BatchMaskSource m{ masks, nullptr, false, "agh_localize_batch_masked_begin" };
+  const SampleSource m = mask_source(masks, nullptr, false, "agh_localize_batch_masked_begin");
   return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, nullptr, &m);
 }
 
 int agh_localize_batch_masked_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const uint8_t* const* masks, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const BatchMaskSource m{ masks, nullptr, true, "agh_localize_batch_masked_begin_device" };
+  const SampleSource m = mask_source(masks, nullptr, true, "agh_localize_batch_masked_begin_device");
   return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, nullptr, &m);
 }
 
@@ -1536,10 +1252,10 @@ int agh_localize_depth_batch_masked(agh_ctx* ctx, const agh_depth_image* images,
   const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out,
   int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_masked" };
-  const BatchMaskSource m{ nullptr, masks, false, src.who };
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src, &m);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch_masked" };
+  const SampleSource m = mask_source(nullptr, masks, false, depth.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth, &m);
 }
 
 int agh_localize_depth_batch_masked_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
@@ -1547,30 +1263,26 @@ int agh_localize_depth_batch_masked_device(agh_ctx* ctx, const agh_depth_image* 
   int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
   agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_masked_device" };
-  const BatchMaskSource m{ nullptr, masks, true, src.who };
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src, &m);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_masked_device" };
+  const SampleSource m = mask_source(nullptr, masks, true, depth.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth, &m);
 }
 
 int agh_localize_depth_batch_masked_begin(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
   const int32_t* n_images, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_masked_begin" };
-  const BatchMaskSource m{ nullptr, masks, false, src.who };
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch_masked_begin" };
+  const SampleSource m = mask_source(nullptr, masks, false, depth.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth, &m);
 }
 
 int agh_localize_depth_batch_masked_begin_device(agh_ctx* ctx, const agh_depth_image* images, const agh_sample_mask* masks,
   const int32_t* n_images, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_masked_begin_device" };
-  const BatchMaskSource m{ nullptr, masks, true, src.who };
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_masked_begin_device" };
+  const SampleSource m = mask_source(nullptr, masks, true, depth.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth, &m);
 }
 
 int agh_get_batch_mask_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_captures)
@@ -1580,17 +1292,17 @@ int agh_get_batch_mask_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_cap
   Ctx* c = &ctx->c;
   if (refuse_mid_chain(c, "agh_get_batch_mask_counts"))
     return AGH_ERR_STATE;
-  if (c->batch_mask_captures < 1)
+  if (!c->results.is(SourceKind::Mask, true))
   {
     c->err = "agh_get_batch_mask_counts: the last chain this context collected was no masked batch (or there was none)";
     return AGH_ERR_STATE;
   }
-  if (cap_captures < c->batch_mask_captures)
+  if (cap_captures < c->results.captures)
   {
     c->err = "agh_get_batch_mask_counts: cap_captures is below the batch's n_captures";
     return AGH_ERR_CAPACITY;
   }
-  std::copy(c->batch_mask_counts, c->batch_mask_counts + c->batch_mask_captures, n_eligible);
+  std::copy(c->results.counts, c->results.counts + c->results.captures, n_eligible);
   return AGH_OK;
 }
 
@@ -1601,9 +1313,9 @@ int agh_localize_batch_labeled(agh_ctx* ctx, const float* const* xyz, const int6
   agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
   int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const BatchMaskSource m{ labels, nullptr, false, "agh_localize_batch_labeled", n_objects, true };
-  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, nullptr, &m);
+  const SampleSource m = label_source(labels, nullptr, n_objects, false, "agh_localize_batch_labeled");
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, nullptr, &m);
 }
 
 int agh_localize_batch_labeled_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
@@ -1611,42 +1323,34 @@ int agh_localize_batch_labeled_device(agh_ctx* ctx, const float* const* xyz, con
   agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
   int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const BatchMaskSource m{ labels, nullptr, true, "agh_localize_batch_labeled_device", n_objects, true };
-  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, nullptr, &m);
+  const SampleSource m = label_source(labels, nullptr, n_objects, true, "agh_localize_batch_labeled_device");
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, nullptr, &m);
 }
 
 int agh_localize_batch_labeled_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const BatchMaskSource m{ labels, nullptr, false, "agh_localize_batch_labeled_begin", n_objects, true };
+  const SampleSource m = label_source(labels, nullptr, n_objects, false, "agh_localize_batch_labeled_begin");
   return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, nullptr, &m);
 }
 
 int agh_localize_batch_labeled_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const uint8_t* const* labels, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const BatchMaskSource m{ labels, nullptr, true, "agh_localize_batch_labeled_begin_device", n_objects, true };
+  const SampleSource m = label_source(labels, nullptr, n_objects, true, "agh_localize_batch_labeled_begin_device");
   return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, nullptr, &m);
 }
-
-// (a label image is read as a sample mask whose bytes are labels: the layouts are asserted equal in localize.hip)
-static const agh_sample_mask* as_masks(const agh_label_image* labels) { return reinterpret_cast<const agh_sample_mask*>(labels); }
-static_assert(sizeof(agh_label_image) == sizeof(agh_sample_mask), "a label image is read as a sample mask whose bytes are labels");
 
 int agh_localize_depth_batch_labeled(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
   const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures,
   agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
   int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_labeled" };
-  const BatchMaskSource m{ nullptr, as_masks(labels), false, src.who, n_objects, true };
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src, &m);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch_labeled" };
+  const SampleSource m = label_source(nullptr, labels, n_objects, false, depth.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth, &m);
 }
 
 int agh_localize_depth_batch_labeled_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
@@ -1654,30 +1358,26 @@ int agh_localize_depth_batch_labeled_device(agh_ctx* ctx, const agh_depth_image*
   agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
   int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_labeled_device" };
-  const BatchMaskSource m{ nullptr, as_masks(labels), true, src.who, n_objects, true };
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src, &m);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_labeled_device" };
+  const SampleSource m = label_source(nullptr, labels, n_objects, true, depth.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth, &m);
 }
 
 int agh_localize_depth_batch_labeled_begin(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
   const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_labeled_begin" };
-  const BatchMaskSource m{ nullptr, as_masks(labels), false, src.who, n_objects, true };
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch_labeled_begin" };
+  const SampleSource m = label_source(nullptr, labels, n_objects, false, depth.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth, &m);
 }
 
 int agh_localize_depth_batch_labeled_begin_device(agh_ctx* ctx, const agh_depth_image* images, const agh_label_image* labels,
   const int32_t* n_images, const int32_t* n_objects, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_labeled_begin_device" };
-  const BatchMaskSource m{ nullptr, as_masks(labels), true, src.who, n_objects, true };
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_labeled_begin_device" };
+  const SampleSource m = label_source(nullptr, labels, n_objects, true, depth.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth, &m);
 }
 
 int agh_get_batch_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_lists)
@@ -1687,38 +1387,30 @@ int agh_get_batch_label_counts(agh_ctx* ctx, int64_t* n_eligible, int32_t cap_li
   Ctx* c = &ctx->c;
   if (refuse_mid_chain(c, "agh_get_batch_label_counts"))
     return AGH_ERR_STATE;
-  if (c->batch_label_lists < 1)
+  if (!c->results.is(SourceKind::Labels, true))
   {
     c->err = "agh_get_batch_label_counts: the last chain this context collected was no labelled batch (or there was none)";
     return AGH_ERR_STATE;
   }
-  if (cap_lists < c->batch_label_lists)
+  if (cap_lists < c->results.lists)
   {
     c->err = "agh_get_batch_label_counts: cap_lists is below the call's number of lists";
     return AGH_ERR_CAPACITY;
   }
-  std::copy(c->batch_label_counts, c->batch_label_counts + c->batch_label_lists, n_eligible);
+  std::copy(c->results.counts, c->results.counts + c->results.lists, n_eligible);
   return AGH_OK;
 }
 
 // ---- the clustered forms (include/agh.h): the labelled batch chains with every capture's own connected components as its objects ----
-
-static BatchMaskSource cluster_source(const agh_cluster_params* cp, const char* who)
-{
-  BatchMaskSource m{ nullptr, nullptr, false, who };
-  m.cluster = cp;
-  m.clustered = true;
-  return m;
-}
 
 int agh_localize_batch_clustered(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures, agh_handle* handles_out, int64_t handle_cap,
   int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
   agh_localize_batch_result* results)
 {
-  const BatchMaskSource m = cluster_source(cp, "agh_localize_batch_clustered");
-  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, nullptr, &m);
+  const SampleSource m = cluster_source(cp, nullptr, false, "agh_localize_batch_clustered");
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, nullptr, &m);
 }
 
 int agh_localize_batch_clustered_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
@@ -1726,26 +1418,22 @@ int agh_localize_batch_clustered_device(agh_ctx* ctx, const float* const* xyz, c
   int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
   agh_localize_batch_result* results)
 {
-  const BatchMaskSource m = cluster_source(cp, "agh_localize_batch_clustered_device");
-  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, nullptr, &m);
+  const SampleSource m = cluster_source(cp, nullptr, false, "agh_localize_batch_clustered_device");
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, nullptr, &m);
 }
 
 int agh_localize_batch_clustered_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const BatchMaskSource m = cluster_source(cp, "agh_localize_batch_clustered_begin");
+  const SampleSource m = cluster_source(cp, nullptr, false, "agh_localize_batch_clustered_begin");
   return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, nullptr, &m);
 }
 
 int agh_localize_batch_clustered_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const BatchMaskSource m = cluster_source(cp, "agh_localize_batch_clustered_begin_device");
+  const SampleSource m = cluster_source(cp, nullptr, false, "agh_localize_batch_clustered_begin_device");
   return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, nullptr, &m);
 }
 
@@ -1754,10 +1442,10 @@ int agh_localize_depth_batch_clustered(agh_ctx* ctx, const agh_depth_image* imag
   int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
   agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_clustered" };
-  const BatchMaskSource m = cluster_source(cp, src.who);
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src, &m);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch_clustered" };
+  const SampleSource m = cluster_source(cp, nullptr, false, depth.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth, &m);
 }
 
 int agh_localize_depth_batch_clustered_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
@@ -1765,30 +1453,26 @@ int agh_localize_depth_batch_clustered_device(agh_ctx* ctx, const agh_depth_imag
   int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out, int64_t hands_cap, int32_t* samples_out,
   agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_clustered_device" };
-  const BatchMaskSource m = cluster_source(cp, src.who);
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src, &m);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_clustered_device" };
+  const SampleSource m = cluster_source(cp, nullptr, false, depth.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth, &m);
 }
 
 int agh_localize_depth_batch_clustered_begin(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
   const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_clustered_begin" };
-  const BatchMaskSource m = cluster_source(cp, src.who);
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch_clustered_begin" };
+  const SampleSource m = cluster_source(cp, nullptr, false, depth.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth, &m);
 }
 
 int agh_localize_depth_batch_clustered_begin_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
   const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_clustered_begin_device" };
-  const BatchMaskSource m = cluster_source(cp, src.who);
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_clustered_begin_device" };
+  const SampleSource m = cluster_source(cp, nullptr, false, depth.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth, &m);
 }
 
 // the last chain collected, if it was a clustered batch (`fn` refuses otherwise, and mid-chain)
@@ -1796,7 +1480,7 @@ static int batch_cluster_getter_check(Ctx* c, const char* fn)
 {
   if (refuse_mid_chain(c, fn))
     return AGH_ERR_STATE;
-  if (c->batch_cluster_captures < 1)
+  if (!c->results.is_clustered(true))
   {
     c->err = std::string(fn) + ": the last chain this context collected was no clustered batch (or there was none)";
     return AGH_ERR_STATE;
@@ -1812,23 +1496,24 @@ int agh_get_batch_cluster_info(agh_ctx* ctx, agh_cluster_info* info, int64_t* n_
   Ctx* c = &ctx->c;
   if (int rc = batch_cluster_getter_check(c, "agh_get_batch_cluster_info"))
     return rc;
-  if (info && cap_captures < c->batch_cluster_captures)
+  const ChainResults& R = c->results;
+  if (info && cap_captures < R.captures)
   {
     c->err = "agh_get_batch_cluster_info: cap_captures is below the batch's n_captures";
     return AGH_ERR_CAPACITY;
   }
-  if ((n_voxels || ids) && cap_lists < c->batch_cluster_lists)
+  if ((n_voxels || ids) && cap_lists < R.lists)
   {
     c->err = "agh_get_batch_cluster_info: cap_lists is below the call's number of lists";
     return AGH_ERR_CAPACITY;
   }
   if (info)
-    for (int k = 0; k < c->batch_cluster_captures; k++)
-      info[k] = agh_cluster_info{ c->batch_cluster_info[k][0], c->batch_cluster_info[k][1], c->batch_cluster_info[k][2] };
+    for (int k = 0; k < R.captures; k++)
+      info[k] = agh_cluster_info{ R.cluster_info[k][0], R.cluster_info[k][1], R.cluster_info[k][2] };
   if (n_voxels)
-    std::copy(c->batch_cluster_sizes, c->batch_cluster_sizes + c->batch_cluster_lists, n_voxels);
+    std::copy(R.counts, R.counts + R.lists, n_voxels);
   if (ids)
-    std::copy(c->batch_cluster_ids, c->batch_cluster_ids + c->batch_cluster_lists, ids);
+    std::copy(R.cluster_ids, R.cluster_ids + R.lists, ids);
   return AGH_OK;
 }
 
@@ -1839,36 +1524,29 @@ int agh_get_batch_cluster_labels(agh_ctx* ctx, uint8_t* labels_out, int64_t cap)
   Ctx* c = &ctx->c;
   if (int rc = batch_cluster_getter_check(c, "agh_get_batch_cluster_labels"))
     return rc;
-  if (cap < c->batch_cluster_nv)
+  const int64_t nv = c->results.nv;
+  if (cap < nv)
   {
     c->err = "agh_get_batch_cluster_labels: cap is below the bound batch's voxel count";
     return AGH_ERR_CAPACITY;
   }
   AGH_HIPCHK(c, hipSetDevice(c->device));
-  if (c->batch_cluster_nv > 0)
-    AGH_HIPCHK(c, hipMemcpy(labels_out, c->d_cluster_label, (size_t) c->batch_cluster_nv, hipMemcpyDeviceToHost));
-  return (int) c->batch_cluster_nv;
+  if (nv > 0)
+    AGH_HIPCHK(c, hipMemcpy(labels_out, c->d_cluster_label, (size_t) nv, hipMemcpyDeviceToHost));
+  return (int) nv;
 }
 
 // ---- the fitted forms (include/agh.h, agh_localize_batch_clustered_fit*): the clustered batch chains with every capture's
 // support plane found on its own voxels by plane_fit.hip, in front of the one cluster stage ----
-
-static BatchMaskSource fit_source(const agh_plane_fit_params* fp, const agh_cluster_params* cp, const char* who)
-{
-  BatchMaskSource m = cluster_source(cp, who);
-  m.fit = fp;
-  m.fitted = true;
-  return m;
-}
 
 int agh_localize_batch_clustered_fit(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures,
   agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
   int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const BatchMaskSource m = fit_source(fp, cp, "agh_localize_batch_clustered_fit");
-  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, nullptr, &m);
+  const SampleSource m = cluster_source(cp, fp, true, "agh_localize_batch_clustered_fit");
+  return batch_call(ctx, xyz, false, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, nullptr, &m);
 }
 
 int agh_localize_batch_clustered_fit_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
@@ -1876,26 +1554,22 @@ int agh_localize_batch_clustered_fit_device(agh_ctx* ctx, const float* const* xy
   agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
   int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const BatchMaskSource m = fit_source(fp, cp, "agh_localize_batch_clustered_fit_device");
-  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, nullptr, &m);
+  const SampleSource m = cluster_source(cp, fp, true, "agh_localize_batch_clustered_fit_device");
+  return batch_call(ctx, xyz, true, stride_bytes, n, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, nullptr, &m);
 }
 
 int agh_localize_batch_clustered_fit_begin(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes, const int64_t* n,
   const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const BatchMaskSource m = fit_source(fp, cp, "agh_localize_batch_clustered_fit_begin");
+  const SampleSource m = cluster_source(cp, fp, true, "agh_localize_batch_clustered_fit_begin");
   return batch_begin_impl(ctx, xyz, false, stride_bytes, n, lp, n_captures, nullptr, &m);
 }
 
 int agh_localize_batch_clustered_fit_begin_device(agh_ctx* ctx, const float* const* xyz, const int64_t* stride_bytes,
   const int64_t* n, const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const BatchMaskSource m = fit_source(fp, cp, "agh_localize_batch_clustered_fit_begin_device");
+  const SampleSource m = cluster_source(cp, fp, true, "agh_localize_batch_clustered_fit_begin_device");
   return batch_begin_impl(ctx, xyz, true, stride_bytes, n, lp, n_captures, nullptr, &m);
 }
 
@@ -1904,10 +1578,10 @@ int agh_localize_depth_batch_clustered_fit(agh_ctx* ctx, const agh_depth_image* 
   agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
   int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_clustered_fit" };
-  const BatchMaskSource m = fit_source(fp, cp, src.who);
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src, &m);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch_clustered_fit" };
+  const SampleSource m = cluster_source(cp, fp, true, depth.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth, &m);
 }
 
 int agh_localize_depth_batch_clustered_fit_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
@@ -1915,30 +1589,26 @@ int agh_localize_depth_batch_clustered_fit_device(agh_ctx* ctx, const agh_depth_
   agh_handle* handles_out, int64_t handle_cap, int32_t* inlier_idx_out, int64_t idx_cap, agh_hypothesis* hands_out,
   int64_t hands_cap, int32_t* samples_out, agh_localize_batch_result* results)
 {
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_clustered_fit_device" };
-  const BatchMaskSource m = fit_source(fp, cp, src.who);
-  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out,
-    hands_cap, samples_out, results, &src, &m);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_clustered_fit_device" };
+  const SampleSource m = cluster_source(cp, fp, true, depth.who);
+  return batch_call(ctx, nullptr, false, nullptr, nullptr, lp, n_captures,
+    { handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out }, results, &depth, &m);
 }
 
 int agh_localize_depth_batch_clustered_fit_begin(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
   const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, false, "agh_localize_depth_batch_clustered_fit_begin" };
-  const BatchMaskSource m = fit_source(fp, cp, src.who);
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+  const DepthCaptures depth{ images, n_images, false, "agh_localize_depth_batch_clustered_fit_begin" };
+  const SampleSource m = cluster_source(cp, fp, true, depth.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth, &m);
 }
 
 int agh_localize_depth_batch_clustered_fit_begin_device(agh_ctx* ctx, const agh_depth_image* images, const int32_t* n_images,
   const agh_plane_fit_params* fp, const agh_cluster_params* cp, const agh_localize_params* lp, int32_t n_captures)
 {
-  if (!ctx)
-    return AGH_ERR_INVALID_ARGUMENT;
-  const DepthBatchSource src{ images, n_images, true, "agh_localize_depth_batch_clustered_fit_begin_device" };
-  const BatchMaskSource m = fit_source(fp, cp, src.who);
-  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &src, &m);
+  const DepthCaptures depth{ images, n_images, true, "agh_localize_depth_batch_clustered_fit_begin_device" };
+  const SampleSource m = cluster_source(cp, fp, true, depth.who);
+  return batch_begin_impl(ctx, nullptr, false, nullptr, nullptr, lp, n_captures, &depth, &m);
 }
 
 // the last chain collected, if it was a fitted clustered batch (`fn` refuses otherwise, and mid-chain)
@@ -1946,7 +1616,7 @@ static int batch_fit_getter_check(Ctx* c, const char* fn)
 {
   if (refuse_mid_chain(c, fn))
     return AGH_ERR_STATE;
-  if (c->batch_cluster_captures < 1 || c->batch_fit_captures < 1)
+  if (!c->results.is(SourceKind::FittedClusters, true))
   {
     c->err = std::string(fn) + ": the last chain this context collected was no fitted clustered batch (or there was none)";
     return AGH_ERR_STATE;
@@ -1961,13 +1631,13 @@ int agh_get_batch_plane_fit(agh_ctx* ctx, agh_plane_fit_result* out, int32_t cap
   Ctx* c = &ctx->c;
   if (int rc = batch_fit_getter_check(c, "agh_get_batch_plane_fit"))
     return rc;
-  if (cap_captures < c->batch_fit_captures)
+  if (cap_captures < c->results.captures)
   {
     c->err = "agh_get_batch_plane_fit: cap_captures is below the batch's n_captures";
     return AGH_ERR_CAPACITY;
   }
-  std::copy(c->batch_fit_results, c->batch_fit_results + c->batch_fit_captures, out);
-  return c->batch_fit_captures;
+  std::copy(c->results.fit_results, c->results.fit_results + c->results.captures, out);
+  return c->results.captures;
 }
 
 int agh_get_batch_plane_fit_candidates(agh_ctx* ctx, int32_t capture, int32_t* idx, double* planes, int64_t* counts, int32_t cap)
@@ -1977,12 +1647,12 @@ int agh_get_batch_plane_fit_candidates(agh_ctx* ctx, int32_t capture, int32_t* i
   Ctx* c = &ctx->c;
   if (int rc = batch_fit_getter_check(c, "agh_get_batch_plane_fit_candidates"))
     return rc;
-  if (capture < 0 || capture >= c->batch_fit_captures)
+  if (capture < 0 || capture >= c->results.captures)
   {
     c->err = "agh_get_batch_plane_fit_candidates: capture must be 0 .. n_captures - 1 of the batch";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  const int C = c->batch_fit_candidates[capture];
+  const int C = c->results.fit_candidates[capture];
   if ((idx || planes || counts) && cap < C)
   {
     c->err = "agh_get_batch_plane_fit_candidates: cap is below the capture's n_candidates";
@@ -2050,7 +1720,8 @@ int agh_localize_batch_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle
     return AGH_ERR_STATE;
   }
   zero_results(results, c->lbatch->call.L);
-  if (bad_outputs(handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap))
+  const ChainOutputs out{ handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out };
+  if (out.bad())
   {
     // (the chain is queued: drain it, leave the context as a failed call does)
     c->loc.active = false;
@@ -2058,7 +1729,7 @@ int agh_localize_batch_end(agh_ctx* ctx, agh_handle* handles_out, int64_t handle
     c->err = kBadArguments;
     return chain_fail(c, AGH_ERR_INVALID_ARGUMENT);
   }
-  return batch_end_impl(ctx, handles_out, handle_cap, inlier_idx_out, idx_cap, hands_out, hands_cap, samples_out, results);
+  return batch_end_impl(ctx, out, results);
 }
 
 }  // extern "C"

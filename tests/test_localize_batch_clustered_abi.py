@@ -147,7 +147,11 @@ def test_design_and_sources_name_the_stage():
     assert re.search(r"\bint label_compact_stage_batch\(", labels) and "return label_compact_stage_batch(c, m, any, st);" in labels
     assert len(re.findall(r"hipLaunchKernelGGL\(k_label_emit_batch", labels)) == 1
     batch = open(os.path.join(ROOT, "agile_grasp_amd", "csrc", "localize_batch.hip")).read()
-    assert "sample_cluster_stage_batch(c, m, b->d_ccap, st)" in batch and "std::vector<agh_cluster_params> cp;" in batch
+    assert "sample_cluster_stage_batch(c, m, b->d_ccap, st)" in batch
+    # the batch keeps a copy of the records for a repeat of the pass: in the stored source, which the single chain keeps too
+    internal = open(os.path.join(ROOT, "agile_grasp_amd", "csrc", "agh_internal.h")).read()
+    assert "std::vector<agh_cluster_params> cluster;" in internal[internal.index("struct StoredSource"):internal.index("struct LocalizeState")]
+    assert "StoredSource source;" in batch[batch.index("struct BatchCall"):batch.index("struct LocalizeBatchState")]
     assert "sample_cluster.hip" in build.SRC
     integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for name in ("agh_localize_batch_clustered", "agh_localize_depth_batch_clustered", "localizeHandlesBatchClustered"):

@@ -168,9 +168,13 @@ def test_documents_and_sources_name_the_stage():
     targets = set(re.findall(r"atomicAdd\(&([A-Za-z_>-]+)\[", src))  # no float atomic anywhere: every target is an integer array
     assert targets == {"cnt", "acc", "fb->counts", "fb->sums"} and len(re.findall(r"atomic[A-Z][A-Za-z]*\(", src)) == 4
     batch = open(os.path.join(ROOT, "agile_grasp_amd", "csrc", "localize_batch.hip")).read()
-    assert "std::vector<agh_plane_fit_params> fp;" in batch and "std::vector<agh_cluster_params> cp;" in batch
+    # the batch keeps copies of both records for a repeat of the pass: in the stored source, which the single chain keeps too
+    internal = open(os.path.join(ROOT, "agile_grasp_amd", "csrc", "agh_internal.h")).read()
+    stored = internal[internal.index("struct StoredSource"):internal.index("struct LocalizeState")]
+    assert "std::vector<agh_plane_fit_params> fit;" in stored and "std::vector<agh_cluster_params> cluster;" in stored
+    assert "StoredSource source;" in batch[batch.index("struct BatchCall"):batch.index("struct LocalizeBatchState")]
     stage, cluster = batch.index("plane_fit_stage_batch(c, f, st)"), batch.index("sample_cluster_stage_batch(c, m, b->d_ccap, st)")
-    upload = batch.index("hipMemcpyAsync(b->d_ccap, b->h_ccap")
+    upload = batch.index("table_to_device(c, b->d_ccap, b->h_ccap")
     assert upload < stage < cluster  # behind the records' upload, in front of the cluster stage
     # no new .hip file: INTEGRATION's source list stays equal to build.SRC
     integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
