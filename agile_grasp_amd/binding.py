@@ -118,6 +118,7 @@ EXPORTS = [
     "agh_localize_depth_batch_clustered_fit_begin_device", "agh_get_batch_plane_fit", "agh_get_batch_plane_fit_candidates",
     "agh_default_depth_filter_params", "agh_set_depth_filter", "agh_get_depth_filter", "agh_get_depth_filter_counts",
     "agh_default_voxel_filter_params", "agh_set_voxel_filter", "agh_get_voxel_filter", "agh_get_voxel_filter_counts",
+    "agh_default_hand_filter_params", "agh_set_hand_filter", "agh_get_hand_filter", "agh_get_hand_filter_counts",
 ]
 
 
@@ -263,6 +264,28 @@ class AghVoxelFilterParams(C.Structure):
 
 class AghVoxelFilterCounts(C.Structure):
     _fields_ = [("n_occupied", C.c_int64 * 2), ("n_pruned", C.c_int64 * 2), ("n_kept", C.c_int64 * 2)]
+
+
+class AghHandFilterParams(C.Structure):
+    _fields_ = [("approach_on", C.c_int32), ("width_on", C.c_int32), ("view_on", C.c_int32), ("probes_per_finger", C.c_int32),
+                ("approach_dir", C.c_double * 3), ("min_approach_cos", C.c_double), ("min_width", C.c_double),
+                ("max_width", C.c_double), ("depth_margin", C.c_double), ("max_unobserved", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AghHandFilterCounts(C.Structure):
+    _fields_ = [("n_hypotheses", C.c_int64), ("n_dropped_approach", C.c_int64), ("n_dropped_width", C.c_int64),
+                ("n_dropped_unobserved", C.c_int64), ("n_kept", C.c_int64)]
+
+
+def hand_filter_params(**fields) -> AghHandFilterParams:
+    """agh_default_hand_filter_params, then the given fields (approach_dir: any sequence of three floats)."""
+    fp = AghHandFilterParams()
+    load_library().agh_default_hand_filter_params(C.byref(fp))
+    for k, v in fields.items():
+        if not hasattr(fp, k):
+            raise TypeError(f"agh_hand_filter_params has no field {k}")
+        setattr(fp, k, (C.c_double * 3)(*[float(x) for x in v]) if k == "approach_dir" else v)
+    return fp
 
 
 def voxel_filter_params(**fields) -> AghVoxelFilterParams:
@@ -473,6 +496,7 @@ def load_library():
         lib.agh_default_plane_fit_params.restype = None
         lib.agh_default_depth_filter_params.restype = None
         lib.agh_default_voxel_filter_params.restype = None
+        lib.agh_default_hand_filter_params.restype = None
         _LIB = lib
     return _LIB
 
@@ -618,6 +642,36 @@ class Context:
         recs = (AghVoxelFilterCounts * 64)()
         k = self._check(self.lib.agh_get_voxel_filter_counts(self._h, recs, C.c_int32(64)))
         return np.array([list(r.n_occupied) + list(r.n_pruned) + list(r.n_kept) for r in recs[:k]], np.int64).reshape(k, 6)
+
+    def set_hand_filter(self, fp=None, **fields):
+        """agh_set_hand_filter: every later localize* chain of this context drops, between the search and the classifier, the
+        hands outside an approach cone (approach_on, approach_dir, min_approach_cos), outside the gripper's stroke (width_on,
+        min_width, max_width) or with fingers in space no depth image saw (view_on, probes_per_finger, depth_margin,
+        max_unobserved; the depth forms only).  `fp`: a hand_filter_params() record, or None for the defaults (every criterion
+        off); the keyword fields are set on top.  Sticky until clear_hand_filter()."""
+        rec = hand_filter_params(**fields)
+        if fp is not None:
+            C.memmove(C.byref(rec), C.byref(fp), C.sizeof(AghHandFilterParams))
+            for k, v in fields.items():
+                setattr(rec, k, (C.c_double * 3)(*[float(x) for x in v]) if k == "approach_dir" else v)
+        self._check(self.lib.agh_set_hand_filter(self._h, C.byref(rec)))
+
+    def clear_hand_filter(self):
+        self._check(self.lib.agh_set_hand_filter(self._h, None))
+
+    def get_hand_filter(self):
+        """The agh_hand_filter_params record held, or None."""
+        rec = AghHandFilterParams()
+        return rec if self._check(self.lib.agh_get_hand_filter(self._h, C.byref(rec))) == 1 else None
+
+    def hand_filter_counts(self) -> np.ndarray:
+        """agh_get_hand_filter_counts: an (n_lists, 5) int64 array, a row per list of the last chain in the order of its results
+        -- n_hypotheses, n_dropped_approach, n_dropped_width, n_dropped_unobserved, n_kept -- or an empty one if that chain ran
+        without a filter."""
+        recs = (AghHandFilterCounts * 64)()
+        k = self._check(self.lib.agh_get_hand_filter_counts(self._h, recs, C.c_int32(64)))
+        return np.array([[r.n_hypotheses, r.n_dropped_approach, r.n_dropped_width, r.n_dropped_unobserved, r.n_kept]
+                         for r in recs[:k]], np.int64).reshape(k, 5)
 
     def set_cloud_batch_torch(self, xyz_t, cam_t, offsets, stream=None):
         assert xyz_t.is_cuda and xyz_t.is_contiguous()

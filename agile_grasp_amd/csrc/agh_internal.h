@@ -208,6 +208,37 @@ inline BoundaryBox boundary_box(const double* ws)  // ws == nullptr: off
   return b;
 }
 
+// agh_set_hand_filter (hand_filter.hip; DESIGN.md, "Hand filter"): the second drop decision between the search and the classifier,
+// one byte per hypothesis (1: dropped), which k_hog_svm, k_svm_decide and compact_kept_records honour beside BoundaryBox; a null
+// pointer is "no filter" (every chain without one, agh_classify*, the sharded calls).
+// One depth image as the observed-space test reads it: the bytes where the chain's deprojection read them, the float64
+// intrinsics and pose of the caller's record (DepthView holds their float32 roundings, which the contract does not use here).
+struct HandView
+{
+  const uint8_t* data;  // row v at data + v * stride
+  int64_t stride;       // bytes
+  int32_t w, h, fmt;
+  float scale;
+  double fx, fy, cx, cy;
+  double R[9], t[3];    // pose: row-major rotation, translation
+};
+constexpr int kMaxHandViews = 2 * kMaxClouds;
+struct HandViewPair  // a single capture's views, by value
+{
+  HandView v[2];
+  int32_t n, pad;
+};
+struct HandFilterArgs
+{
+  agh_hand_filter_params p;
+  double finger_off;   // hand_outer_diameter / 2 - finger_width / 2
+  double hand_depth, hand_height;
+  double step;         // hand_depth / probes_per_finger
+  double depths[16];   // HandGeom::depths
+  int32_t n_depths, pad;
+};
+constexpr int kHandFilterCounters = 4;  // per list: dropped by approach, by width, unobserved, (unused)
+
 // ---- what a localize chain draws its samples under (include/agh.h: agh_localize_masked*, _labeled*, _clustered*, _clustered_fit*
 // and their batch forms), described once for the single chain and the batch chain ----
 enum class SourceKind : int
@@ -515,6 +546,26 @@ struct Ctx
   int64_t* d_filter_counts = nullptr;
   int filter_views = 0;
   hipStream_t filter_stream = nullptr;
+  // agh_set_hand_filter (hand_filter.hip): the sticky filter every localize chain of this context applies, host-side (it travels
+  // as a kernel argument).  d_hand_drop: the drop bytes, one per record of d_out_own, made by the first filtered chain and regrown
+  // with s_cap; d_hand_counts / h_hand_counts: kMaxClouds x kHandFilterCounters counters, the device's (zeroed on the chain's
+  // stream in front of k_hand_filter) and the pinned copy the compaction writes; hand_views: the views of the depth chain in
+  // flight (capture k's are hand_view_first[k] .. hand_view_first[k + 1] - 1), kept for its repeats; d_hand_views / h_hand_views:
+  // a batch's table and the captures' first views behind it; hand_filter_ran: the chain in flight (then the last one collected)
+  // queued the filter, and hand_filter_lists the lists whose counts it left.
+  bool hand_filter_set = false;
+  agh_hand_filter_params hand_filter = {};
+  uint8_t* d_hand_drop = nullptr;
+  int64_t hand_drop_cap = 0;
+  unsigned* d_hand_counts = nullptr;
+  int* h_hand_counts = nullptr;
+  std::vector<HandView> hand_views;
+  std::vector<int32_t> hand_view_first;
+  uint8_t* d_hand_views = nullptr;
+  uint8_t* h_hand_views = nullptr;
+  bool hand_filter_ran = false;
+  int hand_filter_lists = 0;
+  int64_t hand_filter_hyp[kMaxClouds] = {};
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
   LocalizeBatchState* lbatch = nullptr;  // agh_localize_batch's buffers (localize_batch.hip), made by its first call
   bool batch_active = false;       // inside agh_localize_batch (agh_localize_begin refuses)
@@ -1057,13 +1108,25 @@ int ball_counts(Ctx* c, int64_t S, hipStream_t st);  // d_nh of the last call's 
 int compact_hypotheses(Ctx* c, int64_t S, agh_hypothesis* d_out, int64_t cap, int64_t* d_nout, hipStream_t st,
   int64_t* d_hdr_flags = nullptr);  // d_hdr_flags: sharded search, slices of at most 65536 samples (see shard.hip)
 // ws: the workspace of a chain with filters_boundaries (the hypotheses near its faces are labelled 0 and not classified), or null
-int hog_svm(Ctx* c, int64_t n_hyp_cap, uint8_t* d_keep, hipStream_t st, const double* ws = nullptr);
+// drop: the hand filter's bytes (agh_set_hand_filter), or null: a dropped hypothesis is labelled 0 and not classified either
+int hog_svm(Ctx* c, int64_t n_hyp_cap, uint8_t* d_keep, hipStream_t st, const double* ws = nullptr, const uint8_t* drop = nullptr);
+// hand_filter.hip: k_hand_filter queued on st behind the search (the records of d_out_own, *d_nout of them, at most `bound`), if
+// a filter is set: *drop = the drop bytes, else *drop = nullptr and nothing is launched.  tab / n_lists: the batch chain's list
+// table (null: the one list of the single chain).
+int hand_filter_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st, const uint8_t** drop);
+// the views of a depth chain's images, as the chain's deprojection read them (depth.hip), kept while a filter with view_on is set
+void hand_filter_keep_views(Ctx* c, const agh_depth_image* images, const int32_t* n_images, int C, const uint8_t* const* data,
+  const int64_t* stride);
+// the rules a set filter adds to a chain's arguments: view_on needs depth images with orthonormal poses (C captures, capture k's
+// images the next n_images[k] of the flat array; the text names the image, and for C > 1 its capture)
+int hand_filter_check(Ctx* c, const char* who, const agh_depth_image* images, const int32_t* n_images, int C, bool has_depth);
+void hand_filter_release(Ctx* c);
 int hog_images(Ctx* c, const uint32_t* d_images, const int32_t* d_order, int64_t n, float* d_desc, hipStream_t st);
 int svm_predict_general(Ctx* c, const float* d_desc, int64_t cap, uint8_t* d_keep, hipStream_t st,
-  const BoundaryBox& box = BoundaryBox{});
+  const BoundaryBox& box = BoundaryBox{}, const uint8_t* drop = nullptr);
 int svm_predict_images(Ctx* c, const float* d_desc, int64_t n, uint8_t* d_keep, double* d_sums, hipStream_t st);
 int svm_predict_desc(Ctx* c, const float* d_desc, int64_t cap, const int64_t* d_nhyp, agh_hypothesis* d_out, uint8_t* d_keep,
-  double* d_sums, hipStream_t st, const BoundaryBox& box = BoundaryBox{});
+  double* d_sums, hipStream_t st, const BoundaryBox& box = BoundaryBox{}, const uint8_t* drop = nullptr);
 int svm_load_general(Ctx* c, int kernel_type, const float* sv, int n_sv, const double* alpha, double rho);
 void hog_tables_host(HogTablesDev* t);
 int64_t selftest_math(Ctx* c, int64_t n, uint64_t seed);
@@ -1125,7 +1188,8 @@ __device__ __forceinline__ bool near_workspace_boundary(const double* surface, c
 }
 
 // The body of k_compact_kept (localize.hip) and k_compact_kept_batch (localize_batch.hip), one work-group of 1024 threads: the
-// records of in[r0, r1) that are kept -- svm_keep if use_keep; not near a face of ws if filters -- leave in list order (an ordered
+// records of in[r0, r1) that are kept -- svm_keep if use_keep; not near a face of ws if filters; not dropped by the hand filter if
+// drop (its bytes, indexed as `in`; null: none) -- leave in list order (an ordered
 // compaction is a scan: a ballot, sixteen wave sums, a carry), each as one 160-byte run, ten threads of sixteen bytes, to out and,
 // below host_cap, to host_out (pinned; null: none), `sample` less sample_base.  dev_cap bounds what is written, not what is
 // counted; the count is returned.  LDS of the caller: src[kCompactList] (position in the output -> position in the input),
@@ -1133,7 +1197,7 @@ __device__ __forceinline__ bool near_workspace_boundary(const double* surface, c
 constexpr int kCompactList = 8192;  // (the handle search takes no more)
 __device__ __forceinline__ int compact_kept_records(const agh_hypothesis* __restrict__ in, int64_t r0, int64_t r1, int use_keep,
   int filters, const double* ws, int* src, int* wsum, int* carry, agh_hypothesis* __restrict__ out, int dev_cap,
-  agh_hypothesis* __restrict__ host_out, int host_cap, int sample_base)
+  agh_hypothesis* __restrict__ host_out, int host_cap, int sample_base, const uint8_t* __restrict__ drop)
 {
   static_assert(sizeof(agh_hypothesis) == 160 && offsetof(agh_hypothesis, sample) == 8 * 16,
     "ten 16-byte parts; sample is the first word of the ninth");
@@ -1144,7 +1208,8 @@ __device__ __forceinline__ int compact_kept_records(const agh_hypothesis* __rest
   for (int64_t b0 = r0; b0 < r1; b0 += 1024)
   {
     const int64_t i = b0 + tid;
-    const bool keep = i < r1 && (!use_keep || in[i].svm_keep != 0) && !(filters && near_workspace_boundary(in[i].surface, ws));
+    const bool keep = i < r1 && (!use_keep || in[i].svm_keep != 0) && !(filters && near_workspace_boundary(in[i].surface, ws)) &&
+                      !(drop && drop[i]);
     const unsigned long long m = __ballot(keep);
     if (lane == 0)
       wsum[wave] = __popcll(m);

@@ -673,6 +673,13 @@ int depth_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* images, i
     base += (int64_t) im.width * im.height;
     blocks += filtered ? view_tiles(a.v[k]) : view_blocks(a.v[k]);
   }
+  {
+    // (agh_set_hand_filter's observed-space criterion reads the same bytes behind the search: they stay until the chain ends)
+    const uint8_t* data[2] = { a.v[0].data, a.v[1].data };
+    const int64_t stride[2] = { a.v[0].stride, a.v[1].stride };
+    const int32_t count = n_images;
+    hand_filter_keep_views(c, images, &count, 1, data, stride);
+  }
   if (filtered)
   {
     if ((rc = filter_counts_for(c, n_images, st)))
@@ -779,6 +786,17 @@ int depth_batch_to_raw(agh_ctx* ctx, const char* who, const agh_depth_image* ima
     base += (int64_t) im.width * im.height;
     off += aligned_bytes(im);
     blocks += filtered ? view_tiles(tab[j]) : view_blocks(tab[j]);
+  }
+  {
+    // (agh_set_hand_filter's observed-space criterion reads the same bytes behind the search: they stay until the chain ends)
+    std::vector<const uint8_t*> data((size_t) views);
+    std::vector<int64_t> stride((size_t) views);
+    for (int j = 0; j < views; j++)
+    {
+      data[(size_t) j] = tab[j].data;
+      stride[(size_t) j] = tab[j].stride;
+    }
+    hand_filter_keep_views(c, images, n_images, C, data.data(), stride.data());
   }
   if ((rc = raw_buffer_for(c, base, st)))
     return fail(rc);

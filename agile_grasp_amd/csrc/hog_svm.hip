@@ -191,7 +191,7 @@ constexpr int kCodeW = 96, kCodeH = 64;
 __global__ __launch_bounds__(256) void k_hog_svm(const uint32_t* __restrict__ images,
   const int32_t* __restrict__ slot_of_hyp, const int64_t* __restrict__ n_hyp, const HogTablesDev* __restrict__ Tg,
   const float* __restrict__ svm_w, double rho, agh_hypothesis* __restrict__ out, uint8_t* __restrict__ keep,
-  double* __restrict__ sums, float* __restrict__ desc_out, int debug_stop, BoundaryBox box)
+  double* __restrict__ sums, float* __restrict__ desc_out, int debug_stop, BoundaryBox box, const uint8_t* __restrict__ drop)
 {
   __shared__ uint32_t bm[kImageWords + 2];
   __shared__ __attribute__((aligned(4))) uint8_t code[kCodeH * kCodeW];
@@ -205,10 +205,10 @@ __global__ __launch_bounds__(256) void k_hog_svm(const uint32_t* __restrict__ im
   const int h = blockIdx.x;
   if (n_hyp && (int64_t) h >= *n_hyp)  // (n_hyp == nullptr: the grid is exact -- the training path's descriptor pass)
     return;
-  if (box.on && near_workspace_boundary(out[h].surface, box.ws))
+  if ((box.on && near_workspace_boundary(out[h].surface, box.ws)) || (drop && drop[h]))
   {
-    // Localization::filterHands dropped this hypothesis ahead of the classifier (a localize chain with filters_boundaries):
-    // labelled 0, its image never loaded, no descriptor, no sum
+    // Localization::filterHands dropped this hypothesis ahead of the classifier (a localize chain with filters_boundaries), or
+    // the hand filter did (agh_set_hand_filter: drop, null without one): labelled 0, its image never loaded, no descriptor, no sum
     if (threadIdx.x == 0)
     {
       if (keep)
@@ -418,7 +418,7 @@ __global__ __launch_bounds__(256) void k_hog_svm(const uint32_t* __restrict__ im
   }
 }
 
-int hog_svm(Ctx* c, int64_t n_hyp_cap, uint8_t* d_keep, hipStream_t st, const double* ws)
+int hog_svm(Ctx* c, int64_t n_hyp_cap, uint8_t* d_keep, hipStream_t st, const double* ws, const uint8_t* drop)
 {
   const BoundaryBox box = boundary_box(ws);
   if (n_hyp_cap <= 0)
@@ -449,14 +449,14 @@ int hog_svm(Ctx* c, int64_t n_hyp_cap, uint8_t* d_keep, hipStream_t st, const do
     // (with the filter on, the records go in for their surfaces: without a model the kernel labels none but the filtered ones,
     // and the decision kernel skips those as well)
     hipLaunchKernelGGL(k_hog_svm, dim3((unsigned) n_hyp_cap), dim3(256), 0, st, c->d_images, c->d_slot_index, c->d_nout_last,
-      c->d_hog, (const float*) nullptr, 0.0, box.on ? c->d_out_last : (agh_hypothesis*) nullptr, (uint8_t*) nullptr,
-      (double*) nullptr, desc, 0, box);
-    const int rc = svm_predict_general(c, desc, n_hyp_cap, d_keep, st, box);
+      c->d_hog, (const float*) nullptr, 0.0, box.on || drop ? c->d_out_last : (agh_hypothesis*) nullptr, (uint8_t*) nullptr,
+      (double*) nullptr, desc, 0, box, drop);
+    const int rc = svm_predict_general(c, desc, n_hyp_cap, d_keep, st, box, drop);
     timing_mark(c, "hog_svm", st);
     return rc;
   }
   hipLaunchKernelGGL(k_hog_svm, dim3((unsigned) n_hyp_cap), dim3(256), 0, st, c->d_images, c->d_slot_index, c->d_nout_last,
-    c->d_hog, c->d_svm_w, c->svm_rho, c->d_out_last, d_keep, c->d_svm_sums, c->d_desc_out, c->debug_stop_hog, box);
+    c->d_hog, c->d_svm_w, c->svm_rho, c->d_out_last, d_keep, c->d_svm_sums, c->d_desc_out, c->debug_stop_hog, box, drop);
   timing_mark(c, "hog_svm", st);
   return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
 }
@@ -468,7 +468,8 @@ int hog_images(Ctx* c, const uint32_t* d_images, const int32_t* d_order, int64_t
   if (n <= 0)
     return AGH_OK;
   hipLaunchKernelGGL(k_hog_svm, dim3((unsigned) n), dim3(256), 0, st, d_images, d_order, (const int64_t*) nullptr, c->d_hog,
-    (const float*) nullptr, 0.0, (agh_hypothesis*) nullptr, (uint8_t*) nullptr, (double*) nullptr, d_desc, 0, BoundaryBox{});
+    (const float*) nullptr, 0.0, (agh_hypothesis*) nullptr, (uint8_t*) nullptr, (double*) nullptr, d_desc, 0, BoundaryBox{},
+    (const uint8_t*) nullptr);
   return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
 }
 
@@ -836,7 +837,7 @@ int agh_classify_images(agh_ctx* ctx, const uint32_t* images, int64_t n, uint8_t
   {
     hipLaunchKernelGGL(k_hog_svm, dim3((unsigned) n), dim3(256), 0, st, (const uint32_t*) c->d_cls_images,
       (const int32_t*) nullptr, (const int64_t*) nullptr, c->d_hog, (const float*) c->d_svm_w, c->svm_rho,
-      (agh_hypothesis*) nullptr, c->d_cls_keep, c->d_cls_sums, (float*) nullptr, 0, BoundaryBox{});
+      (agh_hypothesis*) nullptr, c->d_cls_keep, c->d_cls_sums, (float*) nullptr, 0, BoundaryBox{}, (const uint8_t*) nullptr);
     rc = hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
   }
   if (rc != AGH_OK)

@@ -168,7 +168,7 @@ __global__ void k_batch_samples(const BatchCapture* __restrict__ tab, int C, int
 __global__ __launch_bounds__(1024) void k_compact_kept_batch(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
   int64_t cap_in, int use_keep, int filters, const BatchCapture* __restrict__ tab, agh_hypothesis* __restrict__ out, int slot,
   int* __restrict__ n_out, agh_hypothesis* __restrict__ host_out, int host_slot, int* __restrict__ host_counts,
-  const int32_t* __restrict__ flags)
+  const int32_t* __restrict__ flags, const uint8_t* __restrict__ drop, const unsigned* __restrict__ hf_counts, int* __restrict__ hf_host)
 {
   __shared__ int src[kCompactList];
   __shared__ int wsum[16];
@@ -200,7 +200,9 @@ __global__ __launch_bounds__(1024) void k_compact_kept_batch(const agh_hypothesi
     ws[q] = tab[cap].ws[q];
   const int room = min(slot, host_slot);
   const int K = compact_kept_records(in, r0, r1, use_keep, filters, ws, src, wsum, &carry, out + (int64_t) cap * slot, room,
-    host_out + (int64_t) cap * host_slot, room, (int) s0);
+    host_out + (int64_t) cap * host_slot, room, (int) s0, drop);
+  if (drop && tid < kHandFilterCounters)  // (agh_set_hand_filter: the list's counters to pinned memory with its counts)
+    hf_host[cap * kHandFilterCounters + tid] = (int) hf_counts[cap * kHandFilterCounters + tid];
   if (tid == 0)
   {
     n_out[cap] = K;
@@ -434,11 +436,16 @@ int batch_queue(agh_ctx* ctx, bool handles_only)
     c->mirror = HostMirror{ nullptr, 0, nullptr };
     if ((rc = agh_find_hands_device(ctx, c->d_idx_own, B.S_tot, 0, c->d_out_own, c->s_cap * 8, c->d_nout, st)) != AGH_OK)
       return rc;
-    if (B.classify && (rc = hog_svm(c, std::min<int64_t>(c->last_s * 8, c->last_cap), c->d_keep, st, nullptr)) != AGH_OK)
+    // (agh_set_hand_filter: as in localize_queue, with the list table to find a hand's list, capture and views)
+    const uint8_t* drop = nullptr;
+    if ((rc = hand_filter_stage(c, std::min<int64_t>(c->last_s * 8, c->last_cap), b->d_tab, C, st, &drop)) != AGH_OK)
+      return rc;
+    if (B.classify && (rc = hog_svm(c, std::min<int64_t>(c->last_s * 8, c->last_cap), c->d_keep, st, nullptr, drop)) != AGH_OK)
       return rc;
     hipLaunchKernelGGL(k_compact_kept_batch, dim3(C), dim3(1024), 0, st, (const agh_hypothesis*) c->d_out_own,
       (const int64_t*) c->d_nout, c->s_cap * 8, B.classify ? 1 : 0, B.filters ? 1 : 0, (const BatchCapture*) b->d_tab, b->d.hands,
-      (int) b->slot, b->d_count, b->h_hands, (int) b->h_slot, b->h_counts, (const int32_t*) c->d_flags);
+      (int) b->slot, b->d_count, b->h_hands, (int) b->h_slot, b->h_counts, (const int32_t*) c->d_flags, drop,
+      (const unsigned*) c->d_hand_counts, c->h_hand_counts);
     if (hipGetLastError() != hipSuccess)
     {
       c->err = "k_compact_kept_batch launch failed";
@@ -787,6 +794,10 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
     c->err = who + ": classify needs a loaded SVM (agh_load_svm*)";
     return AGH_ERR_NO_SVM;
   }
+  // (agh_set_hand_filter's observed-space criterion reads the batch's depth images)
+  if (int rc = hand_filter_check(c, who.c_str(), depth ? depth->images : nullptr, depth ? depth->n_images : nullptr, depth ? C : 0,
+        depth != nullptr))
+    return rc;
   if (cam_table_mismatch(c, who.c_str(), C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
     return AGH_ERR_INVALID_ARGUMENT;                    // the table stays the context's until agh_localize_batch_end: the setter
                                                         // refuses mid-chain, so the repeats search with it too)
@@ -925,6 +936,7 @@ int batch_end_impl(agh_ctx* ctx, const ChainOutputs& out, agh_localize_batch_res
   c->loc.active = false;
   c->loc.batch = false;
   c->results = ChainResults{};
+  c->hand_filter_lists = 0;
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)
@@ -1076,9 +1088,11 @@ int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t
   if ((rc = chain_collect(ctx, who, unit, C, hc, kBatchCountsStride, S_tot, b->h_bad, batch_queue, B.per_object() ? &names : nullptr)) != AGH_OK)
     return rc;
   int64_t n_hyp_tot = 0, tot_handles = 0, tot_idx = 0, tot_hands = 0;
+  c->hand_filter_lists = C;  // (agh_get_hand_filter_counts)
   for (int k = 0; k < C; k++)
   {
     const int* h = hc + k * kBatchCountsStride;
+    c->hand_filter_hyp[k] = h[4];
     if (results)
       results[k] = agh_localize_batch_result{ { nv[k], h[4], h[5], h[0], h[1] }, tot_handles, tot_idx, tot_hands, B.soff[k] };
     n_hyp_tot += h[4];

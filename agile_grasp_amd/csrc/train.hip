@@ -478,12 +478,12 @@ __global__ __launch_bounds__(256) void k_svm_kvals(const float* __restrict__ des
 
 __global__ __launch_bounds__(64) void k_svm_decide(const float* __restrict__ kbuf, const int64_t* __restrict__ n_hyp, int n_sv,
   const double* __restrict__ alpha, double rho, agh_hypothesis* __restrict__ out, uint8_t* __restrict__ keep,
-  double* __restrict__ sums, int64_t cap, BoundaryBox box)
+  double* __restrict__ sums, int64_t cap, BoundaryBox box, const uint8_t* __restrict__ drop)
 {
   const int64_t h = (int64_t) blockIdx.x * 64 + threadIdx.x;
   if (h >= cap || (n_hyp && h >= *n_hyp))
     return;
-  if (box.on && near_workspace_boundary(out[h].surface, box.ws))  // (filtered ahead of the classifier: see k_hog_svm)
+  if ((box.on && near_workspace_boundary(out[h].surface, box.ws)) || (drop && drop[h]))  // (filtered ahead of the classifier: see k_hog_svm)
   {
     if (keep)
       keep[h] = 0;
@@ -719,9 +719,10 @@ int svm_train(Ctx* c, const uint32_t* h_images, int64_t n_images, const int32_t*
 }
 
 // CvSVM::predict with a model that is not the compacted linear vector (Learning::classify, learning.cpp:220-225).
-int svm_predict_general(Ctx* c, const float* d_desc, int64_t cap, uint8_t* d_keep, hipStream_t st, const BoundaryBox& box)
+int svm_predict_general(Ctx* c, const float* d_desc, int64_t cap, uint8_t* d_keep, hipStream_t st, const BoundaryBox& box,
+  const uint8_t* drop)
 {
-  return svm_predict_desc(c, d_desc, cap, c->d_nout_last, c->d_out_last, d_keep, c->d_svm_sums, st, box);
+  return svm_predict_desc(c, d_desc, cap, c->d_nout_last, c->d_out_last, d_keep, c->d_svm_sums, st, box, drop);
 }
 
 // The same for `cap` descriptors that belong to no search (agh_classify_images): exact count, no records to mark.
@@ -731,7 +732,7 @@ int svm_predict_images(Ctx* c, const float* d_desc, int64_t n, uint8_t* d_keep, 
 }
 
 int svm_predict_desc(Ctx* c, const float* d_desc, int64_t cap, const int64_t* d_nhyp, agh_hypothesis* d_out, uint8_t* d_keep,
-  double* d_sums, hipStream_t st, const BoundaryBox& box)
+  double* d_sums, hipStream_t st, const BoundaryBox& box, const uint8_t* drop)
 {
   if (cap <= 0)
     return AGH_OK;
@@ -756,7 +757,7 @@ int svm_predict_desc(Ctx* c, const float* d_desc, int64_t cap, const int64_t* d_
       d_nhyp, (const float*) c->d_svm_svT, n_sv, c->svm_kernel == AGH_SVM_POLY2 ? 1 : 0, c->d_cls_kbuf, h_base, cap);
   }
   hipLaunchKernelGGL(k_svm_decide, dim3((unsigned) ((cap + 63) / 64)), dim3(64), 0, st, (const float*) c->d_cls_kbuf,
-    d_nhyp, n_sv, (const double*) c->d_svm_alpha, c->svm_rho, d_out, d_keep, d_sums, cap, box);
+    d_nhyp, n_sv, (const double*) c->d_svm_alpha, c->svm_rho, d_out, d_keep, d_sums, cap, box, drop);
   return hipGetLastError() == hipSuccess ? AGH_OK : AGH_ERR_HIP;
 }
 

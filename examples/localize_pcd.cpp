@@ -3,8 +3,8 @@
 //
 //   g++ -std=c++11 -O2 -Iinclude examples/localize_pcd.cpp -o localize_pcd -Lagile_grasp_amd/lib -lagile_grasp_hip
 //       -Wl,-rpath,$PWD/agile_grasp_amd/lib -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
-//   ./localize_pcd [--filters-boundaries] [--voxel-filter R,K] [--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd>
-//                  [right.pcd] [num_samples] [min_inliers]
+//   ./localize_pcd [--filters-boundaries] [--voxel-filter R,K] [--approach dx,dy,dz,cos] [--aperture lo,hi]
+//                  [--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]
 //
 // Parameters are the node's defaults (find_grasps.cpp:10-21): finger width 0.01, outer diameter 0.09, hand depth 0.06,
 // hand height 0.02, init bite 0.01, 2000 samples, workspace [0.65 0.9 -0.1 0.1 -0.2 1.0], min_inliers 3, camera poses
@@ -16,6 +16,10 @@
 // two voxels belong to one object.
 // --voxel-filter R,K prunes, on the device, the voxels with fewer than K occupied voxels of their own camera within R voxels
 // (Localization::setVoxelFilter): stray returns in free space, which would veto placements beside them.
+// --approach dx,dy,dz,cos keeps the hands whose approach vector (hand -> object) has a dot product of at least cos with the unit
+// vector (dx, dy, dz) -- 0,0,-1,0.7 is a top-down cell -- and --aperture lo,hi those whose grasp width lies in [lo, hi] metres,
+// the gripper's stroke (Localization::setHandFilter): the others are dropped on the device, ahead of the classifier.  (The filter's
+// third criterion, fingers in observed space, needs depth images, which a PCD file does not hold.)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,16 +39,24 @@ int main(int argc, char** argv)
     argv++;
     argc--;
   }
-  bool table = false, voxel_filter = false;
+  bool table = false, voxel_filter = false, approach = false, aperture = false;
   int vf_radius = 0, vf_neighbors = 0;
+  agh_hand_filter_params hand_filter;
+  agh_default_hand_filter_params(&hand_filter);
   double plane[4] = { 0.0, 0.0, 1.0, 0.0 }, cluster_tolerance = 0.01;
   while (argc > 2 && (std::strcmp(argv[1], "--table") == 0 || std::strcmp(argv[1], "--cluster-tolerance") == 0 ||
-                      std::strcmp(argv[1], "--voxel-filter") == 0))
+                      std::strcmp(argv[1], "--voxel-filter") == 0 || std::strcmp(argv[1], "--approach") == 0 ||
+                      std::strcmp(argv[1], "--aperture") == 0))
   {
     if (std::strcmp(argv[1], "--table") == 0)
       table = std::sscanf(argv[2], "%lf,%lf,%lf,%lf", &plane[0], &plane[1], &plane[2], &plane[3]) == 4;
     else if (std::strcmp(argv[1], "--voxel-filter") == 0)
       voxel_filter = std::sscanf(argv[2], "%d,%d", &vf_radius, &vf_neighbors) == 2;
+    else if (std::strcmp(argv[1], "--approach") == 0)
+      approach = std::sscanf(argv[2], "%lf,%lf,%lf,%lf", &hand_filter.approach_dir[0], &hand_filter.approach_dir[1],
+                   &hand_filter.approach_dir[2], &hand_filter.min_approach_cos) == 4;
+    else if (std::strcmp(argv[1], "--aperture") == 0)
+      aperture = std::sscanf(argv[2], "%lf,%lf", &hand_filter.min_width, &hand_filter.max_width) == 2;
     else
       cluster_tolerance = std::atof(argv[2]);
     argv[2] = argv[0];
@@ -53,8 +65,8 @@ int main(int argc, char** argv)
   }
   if (argc < 3)
   {
-    std::printf("usage: %s [--filters-boundaries] [--voxel-filter R,K] [--table a,b,c,d [--cluster-tolerance t]] <svm file> "
-                "<left.pcd> [right.pcd] [num_samples] [min_inliers]\n", argv[0]);
+    std::printf("usage: %s [--filters-boundaries] [--voxel-filter R,K] [--approach dx,dy,dz,cos] [--aperture lo,hi] "
+                "[--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]\n", argv[0]);
     return 2;
   }
   const std::string svm = argv[1], left = argv[2], right = argc > 3 ? argv[3] : "";
@@ -88,6 +100,13 @@ int main(int argc, char** argv)
     fp.radius = vf_radius;
     fp.min_neighbors = vf_neighbors;
     if (!loc.setVoxelFilter(fp))  // (the library's message says which field it refused)
+      return 1;
+  }
+  if (approach || aperture)
+  {
+    hand_filter.approach_on = approach ? 1 : 0;
+    hand_filter.width_on = aperture ? 1 : 0;
+    if (!loc.setHandFilter(hand_filter))  // (likewise)
       return 1;
   }
 

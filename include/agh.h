@@ -276,11 +276,11 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a begin).
  * Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_depth_stage,
  * agh_localize_end,
- * agh_get_cloud_cam_origins, agh_get_depth_filter, agh_get_voxel_filter, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
+ * agh_get_cloud_cam_origins, agh_get_depth_filter, agh_get_voxel_filter, agh_get_hand_filter, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
  * agh_destroy, the host-side counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats, agh_get_grid_desc) and the
  * communicator's bookkeeping (agh_comm_rank, agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault,
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
- * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_set_depth_filter, agh_set_voxel_filter, agh_preprocess*, agh_find_hands*, agh_classify*,
+ * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_set_depth_filter, agh_set_voxel_filter, agh_set_hand_filter, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
  * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled*, agh_localize_depth_labeled*,
  * agh_localize_clustered*, agh_localize_depth_clustered*, agh_localize_clustered_fit*, agh_localize_depth_clustered_fit*,
@@ -293,7 +293,7 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info,
  * agh_get_cluster_labels, agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts,
  * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels, agh_get_batch_plane_fit,
- * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts, agh_get_voxel_filter_counts and every getter of device results (frames, normals,
+ * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts, agh_get_voxel_filter_counts, agh_get_hand_filter_counts and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -731,7 +731,8 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info, agh_get_cluster_labels,
  * agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info,
  * agh_get_batch_cluster_labels, agh_get_batch_plane_fit, agh_get_batch_plane_fit_candidates, agh_set_depth_filter,
- * agh_get_depth_filter_counts, agh_set_voxel_filter and agh_get_voxel_filter_counts are refused as well),
+ * agh_get_depth_filter_counts, agh_set_voxel_filter, agh_get_voxel_filter_counts, agh_set_hand_filter and
+ * agh_get_hand_filter_counts are refused as well),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
@@ -911,6 +912,72 @@ void agh_default_voxel_filter_params(agh_voxel_filter_params* p);  /* radius 2; 
 int agh_set_voxel_filter(agh_ctx* ctx, const agh_voxel_filter_params* fp);
 int agh_get_voxel_filter(agh_ctx* ctx, agh_voxel_filter_params* out);
 int agh_get_voxel_filter_counts(agh_ctx* ctx, agh_voxel_filter_counts* out, int32_t cap_captures);
+
+/* A HAND FILTER on the way out: every agh_localize* call hands back each hand the sweep found collision-free, and a cell can
+ * execute only some of them.  agh_set_hand_filter makes the chain itself drop, between the search and the classifier, the hands
+ * that fail up to three tests (k_hand_filter, one drop byte per hypothesis): no second synchronisation, no classifier work on
+ * hands nobody can use, and the 8192-hand limit of the handle search counts the survivors.  Each criterion is off in the
+ * defaults; a hand counts under the FIRST criterion that drops it, in the order below.
+ *  1. APPROACH CONE (approach_on): approach_dir is a unit vector, |a^2 + b^2 + c^2 - 1| <= 1e-6, min_approach_cos in [-1, 1].  A
+ *     hand is dropped iff ((a0 * d0 + a1 * d1) + a2 * d2) < min_approach_cos, a = agh_hypothesis::approach (hand -> object),
+ *     d = approach_dir: float64, left to right, never contracted.  The threshold is a cosine, so that it can lie exactly on a hand.
+ *  2. APERTURE (width_on): finite, 0 <= min_width <= max_width.  Dropped iff width < min_width || width > max_width.
+ *  3. OBSERVED SPACE (view_on; the depth forms only): the sweep treats everything without a point as free, so with one view
+ *     the far side of every object is "free".  2 x probes_per_finger x 3 probes per hand sample the volume the two fingers
+ *     sweep: with s the sample's point of the voxelised cloud (float32 widened), h = (bottom - s) . binormal, d the bite of
+ *     the record's depth_index (the sweep's own table: init_bite, then += 0.005 depth_index times), n = probes_per_finger,
+ *       c = h -+ (hand_outer_diameter / 2 - finger_width / 2)        (finger 0, finger 1)
+ *       y = (d - hand_depth) + (j + 0.5) x (hand_depth / n)          (j = 0 .. n - 1)
+ *       z = -hand_height, 0, +hand_height
+ *       w = ((s + c x binormal) + y x approach) + z x axis           (per coordinate)
+ *     and a probe is SEEN in image k iff, with e = w - t and q = R^T e from the image's float64 pose (q.x = (R00 e0 + R10 e1)
+ *     + R20 e2, ...): q.z > 0; the pixel (floor(((fx q.x) / q.z + cx) + 0.5), floor(((fy q.y) / q.z + cy) + 0.5)) lies inside
+ *     the image; the pixel is valid by its format's rule; and q.z <= (double) z_pix + depth_margin, z_pix the float32 depth
+ *     as k_deproject computes it.  A probe seen in no image of its capture is unobserved; the hand is dropped iff more than
+ *     max_unobserved probes are.  The images are read AS UPLOADED: the depth filter (agh_set_depth_filter) changes the points
+ *     the chain makes of them, never what this test sees.  A pose whose rotation part is not orthonormal (an entry of
+ *     |R^T R - I| above 1e-4) is AGH_ERR_INVALID_ARGUMENT, the text naming the image.  With view_on set EVERY agh_localize* form
+ *     that takes points is refused with AGH_ERR_INVALID_ARGUMENT, nothing launched: the criterion needs depth images, and a
+ *     safety filter must not silently not apply.
+ *  A NaN in a tested field compares false and the hand is kept, as the boundary filter keeps it (a probe with a NaN coordinate
+ *  is not counted as unobserved).  tests/hand_filter_cases.py is the numpy model the kernel matches decision for decision.
+ *  The setting is sticky per context until cleared (fp == NULL) or replaced; setting it does no device work; an invalid field
+ *  returns AGH_ERR_INVALID_ARGUMENT, the text names it, and the filter held before stays; mid-chain (single or batch) it
+ *  returns AGH_ERR_STATE.  agh_get_hand_filter copies the filter held and returns 1, or 0 if none is set (host-side, allowed
+ *  mid-chain).  It applies to every agh_localize* chain form, batches and _begin / _stage / _end streams included, and to
+ *  their repeats; with filters_boundaries too a hand is dropped if either filter says so.  hands_out, the handles and the inlier
+ *  lists are those of the stage-wise route over the surviving hands; n_hypotheses stays the search's unfiltered count.  The
+ *  stage-wise and sharded calls (agh_find_hands*, agh_classify*) are not touched.  With no filter set nothing new is launched.
+ *  agh_get_hand_filter_counts: one record per list of the last chain collected, in the order of its results (the call
+ *  itself, a batch's captures, or the (capture, object) pairs), if it ran with a filter.  Returns the number of lists, 0 if it
+ *  ran unfiltered (or none ran), AGH_ERR_CAPACITY if cap_lists is smaller, AGH_ERR_STATE mid-chain.  No copy, no
+ *  synchronisation: the counts arrive in pinned memory with the chain's own synchronisation. */
+typedef struct agh_hand_filter_params
+{
+  int32_t approach_on;        /* 0 / 1 */
+  int32_t width_on;           /* 0 / 1 */
+  int32_t view_on;            /* 0 / 1 */
+  int32_t probes_per_finger;  /* 1 .. 16 */
+  double approach_dir[3];     /* unit vector, cloud frame */
+  double min_approach_cos;    /* -1 .. 1 */
+  double min_width, max_width;  /* metres, 0 <= min <= max */
+  double depth_margin;        /* metres, finite, >= 0 */
+  int32_t max_unobserved;     /* >= 0 */
+  int32_t reserved;           /* 0 */
+} agh_hand_filter_params;
+typedef struct agh_hand_filter_counts
+{
+  int64_t n_hypotheses;        /* what the search found for the list */
+  int64_t n_dropped_approach;
+  int64_t n_dropped_width;
+  int64_t n_dropped_unobserved;
+  int64_t n_kept;              /* n_hypotheses less the three (before the classifier and the boundary filter) */
+} agh_hand_filter_counts;
+/* every criterion off; approach_dir (0, 0, 1), min_approach_cos -1; widths 0 .. 0.1; 4 probes, margin 0.01, max_unobserved 0 */
+void agh_default_hand_filter_params(agh_hand_filter_params* p);
+int agh_set_hand_filter(agh_ctx* ctx, const agh_hand_filter_params* fp);
+int agh_get_hand_filter(agh_ctx* ctx, agh_hand_filter_params* out);
+int agh_get_hand_filter_counts(agh_ctx* ctx, agh_hand_filter_counts* out, int32_t cap_lists);
 
 /* The batch chains with every capture's samples drawn UNDER ITS OWN MASK: a cell with several sensor pairs and one detector per
  * sensor hands over, per rig, a capture and an object mask, and wants handles on the masked object of every rig from one call.

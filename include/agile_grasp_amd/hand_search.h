@@ -1323,6 +1323,51 @@ public:
     out.resize(n > 0 ? (std::size_t) n : 0);
     return out;
   }
+  /** Additional: the hand filter (agh_set_hand_filter) -- every later localize chain of this search (points or depth images,
+   *  single or batch) drops, on the device and ahead of the classifier, the hands outside an approach cone, outside the
+   *  gripper's stroke, or with fingers in space no depth image saw (that criterion: the depth forms only; a points form then
+   *  fails).  Sticky until clearHandFilter, also across a context this search re-creates.  Refused while a chain is pending.
+   *  @return false (after printing) on error; the filter held before stays in force */
+  bool setHandFilter(const agh_hand_filter_params& fp)
+  {
+    if (!ensureContext())
+      return false;
+    if (agh_set_hand_filter(ctx_, &fp) != AGH_OK)
+    {
+      fail("agh_set_hand_filter");
+      return false;
+    }
+    hand_filter_ = fp;
+    hand_filter_set_ = true;
+    return true;
+  }
+  bool clearHandFilter()
+  {
+    if (ctx_ && agh_set_hand_filter(ctx_, nullptr) != AGH_OK)
+    {
+      fail("agh_set_hand_filter");
+      return false;
+    }
+    hand_filter_set_ = false;
+    return true;
+  }
+  /** the filter held (agh_get_hand_filter); false: none */
+  bool handFilter(agh_hand_filter_params& out) const
+  {
+    if (hand_filter_set_)
+      out = hand_filter_;
+    return hand_filter_set_;
+  }
+  /** agh_get_hand_filter_counts: per list of the last chain collected (the call, a batch's captures, or the (capture, object)
+   *  pairs, in the order of its results) what the filter did; empty if that chain ran without a filter, if there was none, or
+   *  while a chain is pending */
+  std::vector<agh_hand_filter_counts> handFilterCounts()
+  {
+    std::vector<agh_hand_filter_counts> out(64);
+    const int n = ctx_ ? agh_get_hand_filter_counts(ctx_, out.data(), (std::int32_t) out.size()) : 0;
+    out.resize(n > 0 ? (std::size_t) n : 0);
+    return out;
+  }
   /** agh_get_depth_filter_counts: per view of the last deprojection, in launch order, what the filter did; empty if that
    *  deprojection ran without a filter, if there was none, or while a chain is pending */
   std::vector<agh_depth_filter_counts> depthFilterCounts()
@@ -1672,6 +1717,11 @@ private:
       fail("agh_set_voxel_filter");
       return false;
     }
+    if (hand_filter_set_ && agh_set_hand_filter(ctx_, &hand_filter_) != AGH_OK)
+    {
+      fail("agh_set_hand_filter");
+      return false;
+    }
     return true;
   }
 
@@ -1680,6 +1730,8 @@ private:
   bool depth_filter_set_ = false;
   agh_voxel_filter_params voxel_filter_ = agh_voxel_filter_params();  // setVoxelFilter
   bool voxel_filter_set_ = false;
+  agh_hand_filter_params hand_filter_ = agh_hand_filter_params();  // setHandFilter
+  bool hand_filter_set_ = false;
   std::int64_t searched_n_ = 0;
   // What an End reads of the chain in flight.  The rule for every Begin: these (and last_samples_, sized by chainBegun for
   // localizeEnd) are written only after the library's begin has returned AGH_OK, so a Begin that fails for any reason -- a

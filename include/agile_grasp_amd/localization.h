@@ -672,6 +672,45 @@ public:
     return search_ ? search_->voxelFilterCounts() : std::vector<agh_voxel_filter_counts>();
   }
 
+  /** Additional: the hand filter of every localizeHandles* form (agh_set_hand_filter; agh_default_hand_filter_params fills a
+   *  record with every criterion off).  With a filter set the chain drops, on the device and ahead of the classifier, the hands
+   *  outside an approach cone (approach_on), outside the gripper's stroke (width_on), or with fingers in space no depth image saw
+   *  (view_on: the depth forms only -- a points form then fails, it does not silently skip the test).  The handles are those of
+   *  the surviving hands.  Sticky until clearHandFilter, also across the setters that re-create the search.  Refused while a
+   *  chain is pending.
+   *  @return false (after printing) on error; the filter held before stays in force */
+  bool setHandFilter(const agh_hand_filter_params& fp)
+  {
+    if (chainPending("setHandFilter"))
+      return false;
+    ensureSearch();
+    if (!search_->setHandFilter(fp))
+      return false;
+    hand_filter_ = fp;
+    hand_filter_set_ = true;
+    return true;
+  }
+  bool clearHandFilter()
+  {
+    if (chainPending("clearHandFilter") || (search_ && !search_->clearHandFilter()))
+      return false;
+    hand_filter_set_ = false;
+    return true;
+  }
+  /** the filter held; false: none */
+  bool handFilter(agh_hand_filter_params& out) const
+  {
+    if (hand_filter_set_)
+      out = hand_filter_;
+    return hand_filter_set_;
+  }
+  /** What the filter did in the last localizeHandles* call (agh_get_hand_filter_counts): one record per list of its results;
+   *  empty if that call ran without a filter, if there was none, or while a chain is pending. */
+  std::vector<agh_hand_filter_counts> handFilterCounts()
+  {
+    return search_ ? search_->handFilterCounts() : std::vector<agh_hand_filter_counts>();
+  }
+
   /** What the filter did in the last depth call (agh_get_depth_filter_counts): one record per image, in capture order; empty if
    *  that call ran without a filter, if there was none, or while a chain is pending. */
   std::vector<agh_depth_filter_counts> depthFilterCounts()
@@ -1478,6 +1517,8 @@ private:
       search_->setDepthFilter(depth_filter_);
     if (voxel_filter_set_)
       search_->setVoxelFilter(voxel_filter_);
+    if (hand_filter_set_)
+      search_->setHandFilter(hand_filter_);
   }
 
   int num_threads_, num_samples_;
@@ -1488,6 +1529,8 @@ private:
   bool depth_filter_set_ = false;
   agh_voxel_filter_params voxel_filter_ = agh_voxel_filter_params();  // setVoxelFilter
   bool voxel_filter_set_ = false;
+  agh_hand_filter_params hand_filter_ = agh_hand_filter_params();  // setHandFilter
+  bool hand_filter_set_ = false;
   int plotting_mode_;
   Matrix4d cam_tf_left_, cam_tf_right_;
   VectorXd workspace_;
