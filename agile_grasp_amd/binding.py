@@ -119,6 +119,7 @@ EXPORTS = [
     "agh_default_depth_filter_params", "agh_set_depth_filter", "agh_get_depth_filter", "agh_get_depth_filter_counts",
     "agh_default_voxel_filter_params", "agh_set_voxel_filter", "agh_get_voxel_filter", "agh_get_voxel_filter_counts",
     "agh_default_hand_filter_params", "agh_set_hand_filter", "agh_get_hand_filter", "agh_get_hand_filter_counts",
+    "agh_default_hand_clearance_params", "agh_set_hand_clearance", "agh_get_hand_clearance", "agh_get_hand_clearance_counts",
 ]
 
 
@@ -275,6 +276,26 @@ class AghHandFilterParams(C.Structure):
 class AghHandFilterCounts(C.Structure):
     _fields_ = [("n_hypotheses", C.c_int64), ("n_dropped_approach", C.c_int64), ("n_dropped_width", C.c_int64),
                 ("n_dropped_unobserved", C.c_int64), ("n_kept", C.c_int64)]
+
+
+class AghHandClearanceParams(C.Structure):
+    _fields_ = [("near_offset", C.c_double), ("far_offset", C.c_double), ("half_width", C.c_double), ("half_height", C.c_double),
+                ("max_points", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AghHandClearanceCounts(C.Structure):
+    _fields_ = [("n_tested", C.c_int64), ("n_dropped", C.c_int64), ("n_kept", C.c_int64)]
+
+
+def hand_clearance_params(**fields) -> AghHandClearanceParams:
+    """agh_default_hand_clearance_params, then the given fields."""
+    cp = AghHandClearanceParams()
+    load_library().agh_default_hand_clearance_params(C.byref(cp))
+    for k, v in fields.items():
+        if not hasattr(cp, k):
+            raise TypeError(f"agh_hand_clearance_params has no field {k}")
+        setattr(cp, k, v)
+    return cp
 
 
 def hand_filter_params(**fields) -> AghHandFilterParams:
@@ -497,6 +518,7 @@ def load_library():
         lib.agh_default_depth_filter_params.restype = None
         lib.agh_default_voxel_filter_params.restype = None
         lib.agh_default_hand_filter_params.restype = None
+        lib.agh_default_hand_clearance_params.restype = None
         _LIB = lib
     return _LIB
 
@@ -672,6 +694,34 @@ class Context:
         k = self._check(self.lib.agh_get_hand_filter_counts(self._h, recs, C.c_int32(64)))
         return np.array([[r.n_hypotheses, r.n_dropped_approach, r.n_dropped_width, r.n_dropped_unobserved, r.n_kept]
                          for r in recs[:k]], np.int64).reshape(k, 5)
+
+    def set_hand_clearance(self, cp=None, **fields):
+        """agh_set_hand_clearance: every later localize* chain of this context drops, between the search and the classifier and
+        behind the hand filter, the hands whose approach corridor -- the oriented box near_offset .. far_offset behind the palm,
+        +- half_width along the binormal, +- half_height along the axis -- holds more than max_points points of the capture's own
+        voxelised cloud.  `cp`: a hand_clearance_params() record, or None for the defaults (0, 0.12, 0.05, 0.04, 0); the keyword
+        fields are set on top.  Sticky until clear_hand_clearance()."""
+        rec = hand_clearance_params(**fields)
+        if cp is not None:
+            C.memmove(C.byref(rec), C.byref(cp), C.sizeof(AghHandClearanceParams))
+            for k, v in fields.items():
+                setattr(rec, k, v)
+        self._check(self.lib.agh_set_hand_clearance(self._h, C.byref(rec)))
+
+    def clear_hand_clearance(self):
+        self._check(self.lib.agh_set_hand_clearance(self._h, None))
+
+    def get_hand_clearance(self):
+        """The agh_hand_clearance_params record held, or None."""
+        rec = AghHandClearanceParams()
+        return rec if self._check(self.lib.agh_get_hand_clearance(self._h, C.byref(rec))) == 1 else None
+
+    def hand_clearance_counts(self) -> np.ndarray:
+        """agh_get_hand_clearance_counts: an (n_lists, 3) int64 array, a row per list of the last chain in the order of its results
+        -- n_tested, n_dropped, n_kept -- or an empty one if that chain ran without a clearance."""
+        recs = (AghHandClearanceCounts * 64)()
+        k = self._check(self.lib.agh_get_hand_clearance_counts(self._h, recs, C.c_int32(64)))
+        return np.array([[r.n_tested, r.n_dropped, r.n_kept] for r in recs[:k]], np.int64).reshape(k, 3)
 
     def set_cloud_batch_torch(self, xyz_t, cam_t, offsets, stream=None):
         assert xyz_t.is_cuda and xyz_t.is_contiguous()

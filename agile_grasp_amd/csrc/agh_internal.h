@@ -237,7 +237,15 @@ struct HandFilterArgs
   double depths[16];   // HandGeom::depths
   int32_t n_depths, pad;
 };
-constexpr int kHandFilterCounters = 4;  // per list: dropped by approach, by width, unobserved, (unused)
+constexpr int kHandFilterCounters = 4;  // per list: dropped by approach, by width, unobserved; by the clearance (hand_clearance.hip)
+// agh_set_hand_clearance (hand_clearance.hip; DESIGN.md, "Hand clearance"): what k_hand_clearance needs beside the record
+struct HandClearanceArgs
+{
+  agh_hand_clearance_params p;
+  double hand_depth;
+  double depths[16];   // HandGeom::depths
+  int32_t n_depths, pad;
+};
 
 // ---- what a localize chain draws its samples under (include/agh.h: agh_localize_masked*, _labeled*, _clustered*, _clustered_fit*
 // and their batch forms), described once for the single chain and the batch chain ----
@@ -564,6 +572,13 @@ struct Ctx
   uint8_t* d_hand_views = nullptr;
   uint8_t* h_hand_views = nullptr;
   bool hand_filter_ran = false;
+  // agh_set_hand_clearance (hand_clearance.hip): the sticky corridor test, host-side.  It shares the hand filter's drop bytes and
+  // counters (the fourth of a list's kHandFilterCounters is its own), so either setting makes hand_filter_stage provide them;
+  // hand_clearance_ran: the chain in flight (then the last one collected) queued k_hand_clearance -- hand_filter_ran alone no longer
+  // stands for "a drop buffer exists".  hand_filter_lists and hand_filter_hyp serve both getters.
+  bool hand_clearance_set = false;
+  agh_hand_clearance_params hand_clearance = {};
+  bool hand_clearance_ran = false;
   int hand_filter_lists = 0;
   int64_t hand_filter_hyp[kMaxClouds] = {};
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
@@ -1111,9 +1126,12 @@ int compact_hypotheses(Ctx* c, int64_t S, agh_hypothesis* d_out, int64_t cap, in
 // drop: the hand filter's bytes (agh_set_hand_filter), or null: a dropped hypothesis is labelled 0 and not classified either
 int hog_svm(Ctx* c, int64_t n_hyp_cap, uint8_t* d_keep, hipStream_t st, const double* ws = nullptr, const uint8_t* drop = nullptr);
 // hand_filter.hip: k_hand_filter queued on st behind the search (the records of d_out_own, *d_nout of them, at most `bound`), if
-// a filter is set: *drop = the drop bytes, else *drop = nullptr and nothing is launched.  tab / n_lists: the batch chain's list
+// a filter or a clearance (agh_set_hand_clearance) is set: *drop = the drop bytes, else *drop = nullptr and nothing is launched.  tab / n_lists: the batch chain's list
 // table (null: the one list of the single chain).
 int hand_filter_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st, const uint8_t** drop);
+// hand_clearance.hip: k_hand_clearance queued on st behind k_hand_filter by hand_filter_stage, if a clearance is set.  has_drop: the
+// hand filter wrote the bytes already (the kernel skips the hands it dropped); else the kernel writes every byte itself.
+int hand_clearance_launch(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st, bool has_drop);
 // the views of a depth chain's images, as the chain's deprojection read them (depth.hip), kept while a filter with view_on is set
 void hand_filter_keep_views(Ctx* c, const agh_depth_image* images, const int32_t* n_images, int C, const uint8_t* const* data,
   const int64_t* stride);

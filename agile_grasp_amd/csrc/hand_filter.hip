@@ -277,7 +277,8 @@ int hand_filter_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_list
 {
   *drop = nullptr;
   c->hand_filter_ran = false;
-  if (!c->hand_filter_set)
+  c->hand_clearance_ran = false;
+  if (!c->hand_filter_set && !c->hand_clearance_set)
     return AGH_OK;
   static_assert(sizeof(HandView) % 8 == 0, "the table's records are read with scalar loads");
   const agh_hand_filter_params& p = c->hand_filter;
@@ -306,10 +307,14 @@ int hand_filter_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_list
   for (int k = 0; k < lists * kHandFilterCounters; k++)
     c->h_hand_counts[k] = 0;
   AGH_HIPCHK(c, hipMemsetAsync(c->d_hand_counts, 0, sizeof(unsigned) * (size_t) kMaxClouds * kHandFilterCounters, st));
-  c->hand_filter_ran = true;
+  c->hand_filter_ran = c->hand_filter_set;
+  c->hand_clearance_ran = c->hand_clearance_set;
   *drop = c->d_hand_drop;
   if (bound <= 0)
     return AGH_OK;
+  // (agh_set_hand_clearance alone: k_hand_clearance writes every drop byte itself)
+  if (!c->hand_filter_set)
+    return hand_clearance_launch(c, bound, tab, n_lists, st, false);
   HandFilterArgs a;
   std::memset(&a, 0, sizeof(a));
   a.p = p;
@@ -363,7 +368,7 @@ int hand_filter_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_list
     c->err = "k_hand_filter launch failed";
     return AGH_ERR_HIP;
   }
-  return AGH_OK;
+  return c->hand_clearance_set ? hand_clearance_launch(c, bound, tab, n_lists, st, true) : AGH_OK;
 }
 }  // namespace agh
 

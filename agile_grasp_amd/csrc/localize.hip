@@ -1216,3 +1216,5 @@ int agh_localize_stage(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int
 
 // ---- the hand filter's stage, kernel and entry points (agh_set_hand_filter): a file of its own, compiled here ----
 #include "hand_filter.hip"
+// ---- the corridor test behind it (agh_set_hand_clearance), likewise ----
+#include "hand_clearance.hip"

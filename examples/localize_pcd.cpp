@@ -4,6 +4,7 @@
 //   g++ -std=c++11 -O2 -Iinclude examples/localize_pcd.cpp -o localize_pcd -Lagile_grasp_amd/lib -lagile_grasp_hip
 //       -Wl,-rpath,$PWD/agile_grasp_amd/lib -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
 //   ./localize_pcd [--filters-boundaries] [--voxel-filter R,K] [--approach dx,dy,dz,cos] [--aperture lo,hi]
+//                  [--clearance near,far,half_w,half_h[,max_points]]
 //                  [--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]
 //
 // Parameters are the node's defaults (find_grasps.cpp:10-21): finger width 0.01, outer diameter 0.09, hand depth 0.06,
@@ -20,6 +21,9 @@
 // vector (dx, dy, dz) -- 0,0,-1,0.7 is a top-down cell -- and --aperture lo,hi those whose grasp width lies in [lo, hi] metres,
 // the gripper's stroke (Localization::setHandFilter): the others are dropped on the device, ahead of the classifier.  (The filter's
 // third criterion, fingers in observed space, needs depth images, which a PCD file does not hold.)
+// --clearance near,far,half_w,half_h[,max_points] drops the hands whose approach corridor -- the box from near to far metres behind
+// the palm, +- half_w along the closing direction, +- half_h along the hand's axis -- holds more than max_points (default 0) points
+// of the cloud: 0,0.12,0.05,0.04 is a gripper body of 10 x 8 cm over 12 cm (Localization::setHandClearance).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,10 +47,13 @@ int main(int argc, char** argv)
   int vf_radius = 0, vf_neighbors = 0;
   agh_hand_filter_params hand_filter;
   agh_default_hand_filter_params(&hand_filter);
+  bool clearance = false;
+  agh_hand_clearance_params hand_clearance;
+  agh_default_hand_clearance_params(&hand_clearance);
   double plane[4] = { 0.0, 0.0, 1.0, 0.0 }, cluster_tolerance = 0.01;
   while (argc > 2 && (std::strcmp(argv[1], "--table") == 0 || std::strcmp(argv[1], "--cluster-tolerance") == 0 ||
                       std::strcmp(argv[1], "--voxel-filter") == 0 || std::strcmp(argv[1], "--approach") == 0 ||
-                      std::strcmp(argv[1], "--aperture") == 0))
+                      std::strcmp(argv[1], "--aperture") == 0 || std::strcmp(argv[1], "--clearance") == 0))
   {
     if (std::strcmp(argv[1], "--table") == 0)
       table = std::sscanf(argv[2], "%lf,%lf,%lf,%lf", &plane[0], &plane[1], &plane[2], &plane[3]) == 4;
@@ -57,6 +64,9 @@ int main(int argc, char** argv)
                    &hand_filter.approach_dir[2], &hand_filter.min_approach_cos) == 4;
     else if (std::strcmp(argv[1], "--aperture") == 0)
       aperture = std::sscanf(argv[2], "%lf,%lf", &hand_filter.min_width, &hand_filter.max_width) == 2;
+    else if (std::strcmp(argv[1], "--clearance") == 0)
+      clearance = std::sscanf(argv[2], "%lf,%lf,%lf,%lf,%d", &hand_clearance.near_offset, &hand_clearance.far_offset,
+                    &hand_clearance.half_width, &hand_clearance.half_height, &hand_clearance.max_points) >= 4;
     else
       cluster_tolerance = std::atof(argv[2]);
     argv[2] = argv[0];
@@ -66,7 +76,8 @@ int main(int argc, char** argv)
   if (argc < 3)
   {
     std::printf("usage: %s [--filters-boundaries] [--voxel-filter R,K] [--approach dx,dy,dz,cos] [--aperture lo,hi] "
-                "[--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]\n", argv[0]);
+                "[--clearance near,far,half_w,half_h[,max_points]] [--table a,b,c,d [--cluster-tolerance t]] "
+                "<svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]\n", argv[0]);
     return 2;
   }
   const std::string svm = argv[1], left = argv[2], right = argc > 3 ? argv[3] : "";
@@ -109,6 +120,8 @@ int main(int argc, char** argv)
     if (!loc.setHandFilter(hand_filter))  // (likewise)
       return 1;
   }
+  if (clearance && !loc.setHandClearance(hand_clearance))  // (likewise)
+    return 1;
 
   if (table)
   {

@@ -276,11 +276,11 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a begin).
  * Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_depth_stage,
  * agh_localize_end,
- * agh_get_cloud_cam_origins, agh_get_depth_filter, agh_get_voxel_filter, agh_get_hand_filter, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
+ * agh_get_cloud_cam_origins, agh_get_depth_filter, agh_get_voxel_filter, agh_get_hand_filter, agh_get_hand_clearance, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
  * agh_destroy, the host-side counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats, agh_get_grid_desc) and the
  * communicator's bookkeeping (agh_comm_rank, agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault,
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
- * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_set_depth_filter, agh_set_voxel_filter, agh_set_hand_filter, agh_preprocess*, agh_find_hands*, agh_classify*,
+ * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_set_depth_filter, agh_set_voxel_filter, agh_set_hand_filter, agh_set_hand_clearance, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
  * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled*, agh_localize_depth_labeled*,
  * agh_localize_clustered*, agh_localize_depth_clustered*, agh_localize_clustered_fit*, agh_localize_depth_clustered_fit*,
@@ -293,7 +293,7 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info,
  * agh_get_cluster_labels, agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts,
  * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels, agh_get_batch_plane_fit,
- * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts, agh_get_voxel_filter_counts, agh_get_hand_filter_counts and every getter of device results (frames, normals,
+ * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts, agh_get_voxel_filter_counts, agh_get_hand_filter_counts, agh_get_hand_clearance_counts and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -731,8 +731,9 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * agh_deproject_batch, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info, agh_get_cluster_labels,
  * agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info,
  * agh_get_batch_cluster_labels, agh_get_batch_plane_fit, agh_get_batch_plane_fit_candidates, agh_set_depth_filter,
- * agh_get_depth_filter_counts, agh_set_voxel_filter, agh_get_voxel_filter_counts, agh_set_hand_filter and
- * agh_get_hand_filter_counts are refused as well),
+ * agh_get_depth_filter_counts, agh_set_voxel_filter, agh_get_voxel_filter_counts, agh_set_hand_filter,
+ * agh_get_hand_filter_counts, agh_set_hand_clearance and agh_get_hand_clearance_counts are refused as well; agh_get_hand_clearance
+ * is host-side and allowed, as agh_get_hand_filter),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
@@ -978,6 +979,68 @@ void agh_default_hand_filter_params(agh_hand_filter_params* p);
 int agh_set_hand_filter(agh_ctx* ctx, const agh_hand_filter_params* fp);
 int agh_get_hand_filter(agh_ctx* ctx, agh_hand_filter_params* out);
 int agh_get_hand_filter_counts(agh_ctx* ctx, agh_hand_filter_counts* out, int32_t cap_lists);
+
+/* HAND CLEARANCE: the sweep proves a hand collision-free against the points of the 8 cm ball around its sample, cropped to
+ * +- hand_height, and against the two finger columns and the half-space behind the hand's back only (FingerHand::evaluateFingers).
+ * The gripper's body (flange, camera mount, wrist) and the volume it sweeps on its way in along `approach` are never tested: a hand
+ * lying almost flat on the table, or one reached under a shelf board, comes back collision-free.  agh_set_hand_clearance makes
+ * every agh_localize* chain drop, between the search and the classifier and behind the hand filter (k_hand_clearance, the same drop
+ * byte per hypothesis), the hands whose CORRIDOR -- an oriented box behind the palm, swept backwards along the approach -- holds
+ * more than max_points points of the capture's own voxelised cloud.  All arithmetic is float64, left to right, never contracted.
+ *  1. PALM POINT.  agh_hypothesis::bottom is NOT the palm: it is the deepest point of the object between the fingers.  The palm
+ *     is derived as the hand filter derives its probes: s = the float32 point of the voxelised cloud at samples[H.sample],
+ *     widened; h = ((b0 - s0) n0 + (b1 - s1) n1) + (b2 - s2) n2, b = bottom, n = binormal; y0 = depths[clamp(depth_index)] -
+ *     hand_depth, the sweep's own bite table (init_bite, then += 0.005 depth_index times);
+ *       o = (s + h x binormal) + y0 x approach                       (per coordinate)
+ *  2. POINT IN CORRIDOR.  For a point p of the cloud (float32 widened), e = p - o, yb = (e0 a0 + e1 a1) + e2 a2 with
+ *     a = approach, xb the same with the binormal, zb with the axis.  p is IN the corridor iff
+ *       -far_offset <= yb && yb <= -near_offset && fabs(xb) <= half_width && fabs(zb) <= half_height
+ *     All four comparisons are closed.  A NaN anywhere compares false: the point is not counted, so a record with a NaN field is
+ *     kept, as the other filters keep it.
+ *  3. POINTS TESTED: all voxels of the capture the hypothesis's list belongs to, both cameras.  A batch capture sees only its own
+ *     cloud; a labelled or clustered list sees the whole cloud of its capture.  The voxel filter (agh_set_voxel_filter), if set,
+ *     has already pruned: the clearance test sees what the sweep saw.
+ *  4. DECISION.  A hand is dropped iff its count exceeds max_points.  The decision equals a brute-force count over all points: the
+ *     count is an integer and depends on no traversal order, no atomic order and no early exit.
+ *  5. ORDER.  The hand filter's three criteria come first: a hand they drop is not tested and does not count here.
+ *     filters_boundaries stays independent: a hand goes if either says so.
+ *  6. agh_get_hand_filter_counts keeps its meaning exactly: it returns 0 when only a clearance is set, and with both set its
+ *     n_kept is still "before the classifier, the boundary filter and the clearance".
+ *  7. SCOPE.  As agh_set_hand_filter: sticky per context until cleared (cp == NULL) or replaced; setting it does no device work;
+ *     an invalid field returns AGH_ERR_INVALID_ARGUMENT, the text names it, and the setting held before stays.  It applies to
+ *     every agh_localize* chain form -- points and depth, single, batch and _begin / _stage / _end, masked, labelled, clustered
+ *     and fitted -- and to every in-call repeat that re-queues the search; it needs no depth images, so no form is refused.  The
+ *     stage-wise and sharded calls (agh_find_hands*, agh_classify*) are not touched.  Only surviving hands reach the classifier,
+ *     the 8192-hand limit, hands_out and the handle search; n_hypotheses stays the search's unfiltered count.  With nothing set
+ *     nothing new is launched or allocated.
+ *  8. MID-CHAIN (single or batch) agh_set_hand_clearance and agh_get_hand_clearance_counts return AGH_ERR_STATE;
+ *     agh_get_hand_clearance (1 and a copy, or 0 if none is set) is host-side and allowed mid-chain.  The counts arrive in pinned
+ *     memory with the chain's one synchronisation: one record per list of the last chain collected, in the order of its results,
+ *     if it ran with a clearance; returns the number of lists, 0 if it ran without (or none ran), AGH_ERR_CAPACITY if cap_lists is
+ *     smaller.
+ *  The bounds far_offset <= 0.5 and half_width, half_height <= 0.25 are stated limits, not measured ones: they bound the grid cells
+ *  one hand may walk (the corridor's bounding box is at most 1 m across).  tests/hand_clearance_cases.py is the numpy model the
+ *  kernel matches decision for decision. */
+typedef struct agh_hand_clearance_params
+{
+  double near_offset;   /* metres behind the palm where the corridor begins, finite, >= 0 */
+  double far_offset;    /* ... and ends: near_offset < far_offset <= 0.5 */
+  double half_width;    /* along the binormal, 0 < . <= 0.25 */
+  double half_height;   /* along the axis, 0 < . <= 0.25 */
+  int32_t max_points;   /* >= 0: a hand is dropped iff MORE points than this lie in its corridor */
+  int32_t reserved;     /* 0 */
+} agh_hand_clearance_params;
+typedef struct agh_hand_clearance_counts
+{
+  int64_t n_tested;     /* the list's hypotheses that the hand filter (if set) kept */
+  int64_t n_dropped;
+  int64_t n_kept;       /* n_tested - n_dropped */
+} agh_hand_clearance_counts;
+/* near_offset 0, far_offset 0.12, half_width 0.05, half_height 0.04, max_points 0 */
+void agh_default_hand_clearance_params(agh_hand_clearance_params* p);
+int agh_set_hand_clearance(agh_ctx* ctx, const agh_hand_clearance_params* cp);
+int agh_get_hand_clearance(agh_ctx* ctx, agh_hand_clearance_params* out);
+int agh_get_hand_clearance_counts(agh_ctx* ctx, agh_hand_clearance_counts* out, int32_t cap_lists);
 
 /* The batch chains with every capture's samples drawn UNDER ITS OWN MASK: a cell with several sensor pairs and one detector per
  * sensor hands over, per rig, a capture and an object mask, and wants handles on the masked object of every rig from one call.

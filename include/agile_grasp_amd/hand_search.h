@@ -1368,6 +1368,52 @@ public:
     out.resize(n > 0 ? (std::size_t) n : 0);
     return out;
   }
+  /** Additional: the hand clearance (agh_set_hand_clearance) -- every later localize chain of this search (points or depth
+   *  images, single or batch) drops, on the device, behind the hand filter and ahead of the classifier, the hands whose approach
+   *  corridor (an oriented box behind the palm, swept backwards along the approach) holds more than max_points points of the
+   *  capture's own voxelised cloud.  Sticky until clearHandClearance, also across a context this search re-creates.  Refused while
+   *  a chain is pending.
+   *  @return false (after printing) on error; the setting held before stays in force */
+  bool setHandClearance(const agh_hand_clearance_params& cp)
+  {
+    if (!ensureContext())
+      return false;
+    if (agh_set_hand_clearance(ctx_, &cp) != AGH_OK)
+    {
+      fail("agh_set_hand_clearance");
+      return false;
+    }
+    hand_clearance_ = cp;
+    hand_clearance_set_ = true;
+    return true;
+  }
+  bool clearHandClearance()
+  {
+    if (ctx_ && agh_set_hand_clearance(ctx_, nullptr) != AGH_OK)
+    {
+      fail("agh_set_hand_clearance");
+      return false;
+    }
+    hand_clearance_set_ = false;
+    return true;
+  }
+  /** the clearance held (agh_get_hand_clearance); false: none */
+  bool handClearance(agh_hand_clearance_params& out) const
+  {
+    if (hand_clearance_set_)
+      out = hand_clearance_;
+    return hand_clearance_set_;
+  }
+  /** agh_get_hand_clearance_counts: per list of the last chain collected (the call, a batch's captures, or the (capture, object)
+   *  pairs, in the order of its results) what the clearance did; empty if that chain ran without one, if there was none, or
+   *  while a chain is pending */
+  std::vector<agh_hand_clearance_counts> handClearanceCounts()
+  {
+    std::vector<agh_hand_clearance_counts> out(64);
+    const int n = ctx_ ? agh_get_hand_clearance_counts(ctx_, out.data(), (std::int32_t) out.size()) : 0;
+    out.resize(n > 0 ? (std::size_t) n : 0);
+    return out;
+  }
   /** agh_get_depth_filter_counts: per view of the last deprojection, in launch order, what the filter did; empty if that
    *  deprojection ran without a filter, if there was none, or while a chain is pending */
   std::vector<agh_depth_filter_counts> depthFilterCounts()
@@ -1722,6 +1768,11 @@ private:
       fail("agh_set_hand_filter");
       return false;
     }
+    if (hand_clearance_set_ && agh_set_hand_clearance(ctx_, &hand_clearance_) != AGH_OK)
+    {
+      fail("agh_set_hand_clearance");
+      return false;
+    }
     return true;
   }
 
@@ -1732,6 +1783,8 @@ private:
   bool voxel_filter_set_ = false;
   agh_hand_filter_params hand_filter_ = agh_hand_filter_params();  // setHandFilter
   bool hand_filter_set_ = false;
+  agh_hand_clearance_params hand_clearance_ = agh_hand_clearance_params();  // setHandClearance
+  bool hand_clearance_set_ = false;
   std::int64_t searched_n_ = 0;
   // What an End reads of the chain in flight.  The rule for every Begin: these (and last_samples_, sized by chainBegun for
   // localizeEnd) are written only after the library's begin has returned AGH_OK, so a Begin that fails for any reason -- a

@@ -711,6 +711,45 @@ public:
     return search_ ? search_->handFilterCounts() : std::vector<agh_hand_filter_counts>();
   }
 
+  /** Additional: the hand clearance of every localizeHandles* form (agh_set_hand_clearance; agh_default_hand_clearance_params
+   *  fills a record with a corridor of 12 cm x +- 5 cm x +- 4 cm that must be empty).  With one set the chain drops, on the device,
+   *  behind the hand filter and ahead of the classifier, the hands whose approach corridor -- the oriented box the gripper's body
+   *  sweeps behind the palm on its way in -- holds more than max_points points of the capture's own voxelised cloud: the hands
+   *  a real gripper would drive into the table or a neighbouring object.  The handles are those of the surviving hands.  Sticky
+   *  until clearHandClearance, also across the setters that re-create the search.  Refused while a chain is pending.
+   *  @return false (after printing) on error; the setting held before stays in force */
+  bool setHandClearance(const agh_hand_clearance_params& cp)
+  {
+    if (chainPending("setHandClearance"))
+      return false;
+    ensureSearch();
+    if (!search_->setHandClearance(cp))
+      return false;
+    hand_clearance_ = cp;
+    hand_clearance_set_ = true;
+    return true;
+  }
+  bool clearHandClearance()
+  {
+    if (chainPending("clearHandClearance") || (search_ && !search_->clearHandClearance()))
+      return false;
+    hand_clearance_set_ = false;
+    return true;
+  }
+  /** the clearance held; false: none */
+  bool handClearance(agh_hand_clearance_params& out) const
+  {
+    if (hand_clearance_set_)
+      out = hand_clearance_;
+    return hand_clearance_set_;
+  }
+  /** What the clearance did in the last localizeHandles* call (agh_get_hand_clearance_counts): one record per list of its
+   *  results; empty if that call ran without one, if there was none, or while a chain is pending. */
+  std::vector<agh_hand_clearance_counts> handClearanceCounts()
+  {
+    return search_ ? search_->handClearanceCounts() : std::vector<agh_hand_clearance_counts>();
+  }
+
   /** What the filter did in the last depth call (agh_get_depth_filter_counts): one record per image, in capture order; empty if
    *  that call ran without a filter, if there was none, or while a chain is pending. */
   std::vector<agh_depth_filter_counts> depthFilterCounts()
@@ -1519,6 +1558,8 @@ private:
       search_->setVoxelFilter(voxel_filter_);
     if (hand_filter_set_)
       search_->setHandFilter(hand_filter_);
+    if (hand_clearance_set_)
+      search_->setHandClearance(hand_clearance_);
   }
 
   int num_threads_, num_samples_;
@@ -1531,6 +1572,8 @@ private:
   bool voxel_filter_set_ = false;
   agh_hand_filter_params hand_filter_ = agh_hand_filter_params();  // setHandFilter
   bool hand_filter_set_ = false;
+  agh_hand_clearance_params hand_clearance_ = agh_hand_clearance_params();  // setHandClearance
+  bool hand_clearance_set_ = false;
   int plotting_mode_;
   Matrix4d cam_tf_left_, cam_tf_right_;
   VectorXd workspace_;
