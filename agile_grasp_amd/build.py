@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = ["voxelize.hip", "sample_mask.hip", "sample_labels.hip", "sample_cluster.hip", "plane_fit.hip", "grid.hip", "taubin.hip", "hand_sweep.hip", "hog_svm.hip", "handles.hip", "train.hip", "points.hip", "shard.hip", "localize.hip", "localize_batch.hip", "depth.hip", "plane.hip", "api.hip"]
+SRC = ["voxelize.hip", "sample_mask.hip", "sample_labels.hip", "sample_cluster.hip", "plane_fit.hip", "grid.hip", "taubin.hip", "hand_sweep.hip", "hog_svm.hip", "handles.hip", "train.hip", "points.hip", "shard.hip", "localize.hip", "localize_batch.hip", "hand_drop.hip", "hand_filter.hip", "hand_clearance.hip", "depth.hip", "plane.hip", "api.hip"]
 LIB = os.path.join(HERE, "lib", "libagile_grasp_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value",
          "-fno-gpu-rdc"]
@@ -20,7 +20,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(HERE, "csrc", f) for f in SRC + ["agh_internal.h", "taubin_eigen.h", "hand_filter.hip", "hand_clearance.hip"]] + [os.path.join(ROOT, "include", "agh.h")]
+    deps = [os.path.join(HERE, "csrc", f) for f in SRC + ["agh_internal.h", "taubin_eigen.h"]] + [os.path.join(ROOT, "include", "agh.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

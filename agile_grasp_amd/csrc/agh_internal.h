@@ -174,6 +174,16 @@ struct BatchCapture
   int32_t capture;  // the capture the list belongs to (a labelled batch has a list per object; otherwise list k is capture k) ...
   int32_t object;   // ... and its object there (0 without labels)
 };
+// the list of the chain a position of its sample list belongs to: the last list whose span starts at or before it and is not
+// empty (k_batch_samples' rule)
+__device__ __forceinline__ int list_of_sample(const BatchCapture* __restrict__ tab, int n_lists, int64_t sample)
+{
+  int l = 0;
+  for (int q = 1; q < n_lists; q++)
+    if (tab[q].soff <= sample && tab[q].S > 0)
+      l = q;
+  return l;
+}
 
 struct Comm;  // shard.hip
 
@@ -208,9 +218,11 @@ inline BoundaryBox boundary_box(const double* ws)  // ws == nullptr: off
   return b;
 }
 
-// agh_set_hand_filter (hand_filter.hip; DESIGN.md, "Hand filter"): the second drop decision between the search and the classifier,
-// one byte per hypothesis (1: dropped), which k_hog_svm, k_svm_decide and compact_kept_records honour beside BoundaryBox; a null
-// pointer is "no filter" (every chain without one, agh_classify*, the sharded calls).
+// ---- the hand drop stage (hand_drop.hip; DESIGN.md, "Hand filter" and "Hand clearance"): the second drop decision between the
+// search and the classifier, one byte per hypothesis (1: dropped), which k_hog_svm, k_svm_decide and compact_kept_records honour
+// beside BoundaryBox; a null pointer is "no test set" (every chain without one, agh_classify*, the sharded calls).  hand_drop_stage
+// provides the bytes and a list's counters and lets the two tests write them in turn, as peers: agh_set_hand_filter's k_hand_filter
+// (hand_filter.hip), then agh_set_hand_clearance's k_hand_clearance (hand_clearance.hip), which skips what the first dropped. ----
 // One depth image as the observed-space test reads it: the bytes where the chain's deprojection read them, the float64
 // intrinsics and pose of the caller's record (DepthView holds their float32 roundings, which the contract does not use here).
 struct HandView
@@ -223,6 +235,8 @@ struct HandView
   double R[9], t[3];    // pose: row-major rotation, translation
 };
 constexpr int kMaxHandViews = 2 * kMaxClouds;
+// a batch's view table: kMaxHandViews records, the captures' first views (kMaxClouds + 1) behind them
+constexpr size_t kHandViewTableBytes = sizeof(HandView) * (size_t) kMaxHandViews + sizeof(int32_t) * (size_t) (kMaxClouds + 1);
 struct HandViewPair  // a single capture's views, by value
 {
   HandView v[2];
@@ -237,14 +251,48 @@ struct HandFilterArgs
   double depths[16];   // HandGeom::depths
   int32_t n_depths, pad;
 };
-constexpr int kHandFilterCounters = 4;  // per list: dropped by approach, by width, unobserved; by the clearance (hand_clearance.hip)
-// agh_set_hand_clearance (hand_clearance.hip; DESIGN.md, "Hand clearance"): what k_hand_clearance needs beside the record
-struct HandClearanceArgs
+struct HandClearanceArgs  // what k_hand_clearance needs beside the record
 {
   agh_hand_clearance_params p;
   double hand_depth;
   double depths[16];   // HandGeom::depths
   int32_t n_depths, pad;
+};
+// a list's counters, the device's and the pinned copy the compaction writes: the hands each test dropped (k_hand_filter's reason
+// for a drop is 1 + its slot)
+enum HandDropSlot : int { kDropApproach = 0, kDropWidth, kDropUnobserved, kDropClearance, kHandDropCounters };
+struct HandDropState
+{
+  // the two sticky settings, host-side (they travel as kernel arguments)
+  bool filter_set = false, clearance_set = false;
+  agh_hand_filter_params filter = {};
+  agh_hand_clearance_params clearance = {};
+  // the buffers, made by the first chain with a test set: the drop bytes, one per record of d_out_own, regrown with s_cap; the
+  // counters, kMaxClouds lists, zeroed on the chain's stream in front of the tests, and their pinned copy; a batch's view table
+  uint8_t* d_drop = nullptr;
+  int64_t drop_cap = 0;
+  unsigned* d_counts = nullptr;
+  int* h_counts = nullptr;
+  uint8_t *d_views = nullptr, *h_views = nullptr;  // kHandViewTableBytes
+  // what the chain in flight (then the last one collected) left: its depth images' views (capture k's are view_first[k] ..
+  // view_first[k + 1] - 1), kept for its repeats; the tests it queued; the lists it counted and their hypotheses
+  std::vector<HandView> views;
+  std::vector<int32_t> view_first;
+  bool filter_ran = false, clearance_ran = false;
+  int lists = 0;
+  int64_t hyp[kMaxClouds] = {};
+};
+struct HandDropView  // what the stage hands the classifier and the compaction, host-side: all null without a test
+{
+  int rc = AGH_OK;
+  const uint8_t* drop = nullptr;
+  const unsigned* d_counts = nullptr;
+  int* h_counts = nullptr;
+};
+struct HandDropCounts  // a list's counters as the two counts getters report them
+{
+  int64_t hypotheses, approach, width, unobserved, clearance;
+  int64_t past_filter() const { return hypotheses - (approach + width + unobserved); }  // kept by the filter = the clearance tested
 };
 
 // ---- what a localize chain draws its samples under (include/agh.h: agh_localize_masked*, _labeled*, _clustered*, _clustered_fit*
@@ -554,33 +602,7 @@ struct Ctx
   int64_t* d_filter_counts = nullptr;
   int filter_views = 0;
   hipStream_t filter_stream = nullptr;
-  // agh_set_hand_filter (hand_filter.hip): the sticky filter every localize chain of this context applies, host-side (it travels
-  // as a kernel argument).  d_hand_drop: the drop bytes, one per record of d_out_own, made by the first filtered chain and regrown
-  // with s_cap; d_hand_counts / h_hand_counts: kMaxClouds x kHandFilterCounters counters, the device's (zeroed on the chain's
-  // stream in front of k_hand_filter) and the pinned copy the compaction writes; hand_views: the views of the depth chain in
-  // flight (capture k's are hand_view_first[k] .. hand_view_first[k + 1] - 1), kept for its repeats; d_hand_views / h_hand_views:
-  // a batch's table and the captures' first views behind it; hand_filter_ran: the chain in flight (then the last one collected)
-  // queued the filter, and hand_filter_lists the lists whose counts it left.
-  bool hand_filter_set = false;
-  agh_hand_filter_params hand_filter = {};
-  uint8_t* d_hand_drop = nullptr;
-  int64_t hand_drop_cap = 0;
-  unsigned* d_hand_counts = nullptr;
-  int* h_hand_counts = nullptr;
-  std::vector<HandView> hand_views;
-  std::vector<int32_t> hand_view_first;
-  uint8_t* d_hand_views = nullptr;
-  uint8_t* h_hand_views = nullptr;
-  bool hand_filter_ran = false;
-  // agh_set_hand_clearance (hand_clearance.hip): the sticky corridor test, host-side.  It shares the hand filter's drop bytes and
-  // counters (the fourth of a list's kHandFilterCounters is its own), so either setting makes hand_filter_stage provide them;
-  // hand_clearance_ran: the chain in flight (then the last one collected) queued k_hand_clearance -- hand_filter_ran alone no longer
-  // stands for "a drop buffer exists".  hand_filter_lists and hand_filter_hyp serve both getters.
-  bool hand_clearance_set = false;
-  agh_hand_clearance_params hand_clearance = {};
-  bool hand_clearance_ran = false;
-  int hand_filter_lists = 0;
-  int64_t hand_filter_hyp[kMaxClouds] = {};
+  HandDropState hand_drop;         // the hand drop stage (hand_drop.hip): agh_set_hand_filter, agh_set_hand_clearance
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
   LocalizeBatchState* lbatch = nullptr;  // agh_localize_batch's buffers (localize_batch.hip), made by its first call
   bool batch_active = false;       // inside agh_localize_batch (agh_localize_begin refuses)
@@ -1123,14 +1145,18 @@ int ball_counts(Ctx* c, int64_t S, hipStream_t st);  // d_nh of the last call's 
 int compact_hypotheses(Ctx* c, int64_t S, agh_hypothesis* d_out, int64_t cap, int64_t* d_nout, hipStream_t st,
   int64_t* d_hdr_flags = nullptr);  // d_hdr_flags: sharded search, slices of at most 65536 samples (see shard.hip)
 // ws: the workspace of a chain with filters_boundaries (the hypotheses near its faces are labelled 0 and not classified), or null
-// drop: the hand filter's bytes (agh_set_hand_filter), or null: a dropped hypothesis is labelled 0 and not classified either
+// drop: the hand drop stage's bytes, or null: a dropped hypothesis is labelled 0 and not classified either
 int hog_svm(Ctx* c, int64_t n_hyp_cap, uint8_t* d_keep, hipStream_t st, const double* ws = nullptr, const uint8_t* drop = nullptr);
-// hand_filter.hip: k_hand_filter queued on st behind the search (the records of d_out_own, *d_nout of them, at most `bound`), if
-// a filter or a clearance (agh_set_hand_clearance) is set: *drop = the drop bytes, else *drop = nullptr and nothing is launched.  tab / n_lists: the batch chain's list
-// table (null: the one list of the single chain).
-int hand_filter_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st, const uint8_t** drop);
-// hand_clearance.hip: k_hand_clearance queued on st behind k_hand_filter by hand_filter_stage, if a clearance is set.  has_drop: the
-// hand filter wrote the bytes already (the kernel skips the hands it dropped); else the kernel writes every byte itself.
+// hand_drop.hip: the set tests queued on st behind the search (the records of d_out_own, *d_nout of them, at most `bound`); without
+// one nothing is allocated or launched.  tab / n_lists: the batch chain's list table (null: the one list of the single chain).
+HandDropView hand_drop_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st);
+// a chain's end: its lists and their hypotheses, for the two counts getters (0 lists: nothing collected)
+void hand_drop_collect(Ctx* c, int lists, const int64_t* hyp);
+HandDropCounts hand_drop_counts(const Ctx* c, int k);
+void hand_drop_release(Ctx* c);
+// the two tests, each launched only if its own setting is set.  has_drop: the bytes are written already (the kernel skips the
+// dropped hands); else it writes every byte itself
+int hand_filter_launch(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st);
 int hand_clearance_launch(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st, bool has_drop);
 // the views of a depth chain's images, as the chain's deprojection read them (depth.hip), kept while a filter with view_on is set
 void hand_filter_keep_views(Ctx* c, const agh_depth_image* images, const int32_t* n_images, int C, const uint8_t* const* data,
@@ -1138,7 +1164,6 @@ void hand_filter_keep_views(Ctx* c, const agh_depth_image* images, const int32_t
 // the rules a set filter adds to a chain's arguments: view_on needs depth images with orthonormal poses (C captures, capture k's
 // images the next n_images[k] of the flat array; the text names the image, and for C > 1 its capture)
 int hand_filter_check(Ctx* c, const char* who, const agh_depth_image* images, const int32_t* n_images, int C, bool has_depth);
-void hand_filter_release(Ctx* c);
 int hog_images(Ctx* c, const uint32_t* d_images, const int32_t* d_order, int64_t n, float* d_desc, hipStream_t st);
 int svm_predict_general(Ctx* c, const float* d_desc, int64_t cap, uint8_t* d_keep, hipStream_t st,
   const BoundaryBox& box = BoundaryBox{}, const uint8_t* drop = nullptr);

@@ -1,10 +1,9 @@
 // hand_clearance.hip -- agh_set_hand_clearance (include/agh.h; DESIGN.md, "Hand clearance"): the hands whose approach corridor -- an
 // oriented box behind the palm, swept backwards along the approach -- holds more than max_points points of the capture's own
 // voxelised cloud are dropped inside the localize chains, behind the hand filter and ahead of the classifier.  k_hand_clearance
-// shares k_hand_filter's drop bytes and counters (the fourth of a list's kHandFilterCounters), so the classifier kernels and the
-// compactions need nothing new.  The arithmetic is the contract's, float64, left to right, not contracted (-ffp-contract=off is the
-// build's); tests/hand_clearance_cases.py is its numpy model.
-// No translation unit of its own: localize.hip includes this file behind hand_filter.hip, so the build's list of units stays.
+// writes the hand drop stage's bytes and its own counter of a list (hand_drop.hip, whose stage calls hand_clearance_launch behind
+// hand_filter_launch), so the classifier kernels and the compactions need nothing of its own.  The arithmetic is the contract's,
+// float64, left to right, not contracted (-ffp-contract=off is the build's); tests/hand_clearance_cases.py is its numpy model.
 #include "agh_internal.h"
 
 #include <cmath>
@@ -33,7 +32,7 @@ __device__ __forceinline__ void span_along(const double* v, const double* o, con
   *mx = b;
 }
 
-// One drop byte per hypothesis in[0, min(*n_in, cap_in)) and the lists' fourth counter.  The launch is sized for the bound of the
+// One drop byte per hypothesis in[0, min(*n_in, cap_in)) and the lists' kDropClearance counter.  The launch is sized for the bound of the
 // list and exits on the count.  A wave per hypothesis: the record, its list, its capture and the capture's grid descriptor are
 // wave-uniform.  The corridor's bounding box becomes cell ranges (cell_coord clamps them as the build clamped the points, so the
 // border cells of a kept descriptor, which hold the points outside its box, are always inside the range); every (y, z) row of the
@@ -41,7 +40,7 @@ __device__ __forceinline__ void span_along(const double* v, const double* o, con
 // cell cannot meet the corridor is left out by interval arithmetic, border rows never -- then the wave walks the runs that hold
 // points, a lane per point, the contract's test, a ballot and a popcount into a wave-uniform count.  The wave leaves once the
 // count exceeds max_points: the decision is fixed then.  No LDS, no atomics on the count.
-// has_drop: k_hand_filter wrote the bytes (a hand it dropped is skipped and stays dropped); else this kernel writes every byte.
+// has_drop: the bytes are written already (a dropped hand is skipped and stays dropped); else this kernel writes every byte.
 // tab == null: the single chain's one list, capture 0; else list l = list_of_sample, capture tab[l].capture.
 __global__ __launch_bounds__(kHcBlock) void k_hand_clearance(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
   int64_t cap_in, HandClearanceArgs a, const BatchCapture* __restrict__ tab, int n_lists, GridView gv,
@@ -153,7 +152,7 @@ __global__ __launch_bounds__(kHcBlock) void k_hand_clearance(const agh_hypothesi
     const bool dropped = count > a.p.max_points;
     drop[i] = dropped ? 1 : 0;
     if (dropped)
-      atomicAdd(&counts[l * kHandFilterCounters + 3], 1u);
+      atomicAdd(&counts[l * kHandDropCounters + kDropClearance], 1u);
   }
 }
 
@@ -182,11 +181,12 @@ namespace agh
 {
 int hand_clearance_launch(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st, bool has_drop)
 {
-  if (bound <= 0)
+  const HandDropState& S = c->hand_drop;
+  if (!S.clearance_set)
     return AGH_OK;
   HandClearanceArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.p = c->hand_clearance;
+  a.p = S.clearance;
   a.hand_depth = c->geom.hand_depth;
   a.n_depths = c->geom.n_depths;
   for (int k = 0; k < 16; k++)
@@ -194,7 +194,7 @@ int hand_clearance_launch(Ctx* c, int64_t bound, const BatchCapture* tab, int n_
   const GridView gv{ c->d_desc, c->d_cell_start, c->d_sorted, c->d_cloud_off, c->n_clouds };
   hipLaunchKernelGGL(k_hand_clearance, dim3((unsigned) ((bound + kHcBlock / 64 - 1) / (kHcBlock / 64))), dim3(kHcBlock), 0, st,
     (const agh_hypothesis*) c->d_out_own, (const int64_t*) c->d_nout, c->s_cap * 8, a, tab, n_lists, gv, (const int32_t*) c->d_idx_own,
-    c->last_s, (const float*) c->d_xyz, c->stride_floats, has_drop ? 1 : 0, c->d_hand_drop, c->d_hand_counts);
+    c->last_s, (const float*) c->d_xyz, c->stride_floats, has_drop ? 1 : 0, S.d_drop, S.d_counts);
   if (hipGetLastError() != hipSuccess)
   {
     c->err = "k_hand_clearance launch failed";
@@ -232,7 +232,7 @@ int agh_set_hand_clearance(agh_ctx* ctx, const agh_hand_clearance_params* cp)
   }
   if (!cp)
   {
-    c->hand_clearance_set = false;
+    c->hand_drop.clearance_set = false;
     return AGH_OK;
   }
   const std::string fault = clearance_fault(*cp);
@@ -241,9 +241,9 @@ int agh_set_hand_clearance(agh_ctx* ctx, const agh_hand_clearance_params* cp)
     c->err = "agh_set_hand_clearance: " + fault;
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  c->hand_clearance = *cp;
-  c->hand_clearance.reserved = 0;
-  c->hand_clearance_set = true;
+  c->hand_drop.clearance = *cp;
+  c->hand_drop.clearance.reserved = 0;
+  c->hand_drop.clearance_set = true;
   return AGH_OK;
 }
 
@@ -252,14 +252,14 @@ int agh_get_hand_clearance(agh_ctx* ctx, agh_hand_clearance_params* out)
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
-  if (!c->hand_clearance_set)
+  if (!c->hand_drop.clearance_set)
     return 0;
   if (!out)
   {
     c->err = "agh_get_hand_clearance: out is NULL";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  *out = c->hand_clearance;
+  *out = c->hand_drop.clearance;
   return 1;
 }
 
@@ -270,22 +270,22 @@ int agh_get_hand_clearance_counts(agh_ctx* ctx, agh_hand_clearance_counts* out, 
   Ctx* c = &ctx->c;
   if (refuse_mid_chain(c, "agh_get_hand_clearance_counts"))
     return AGH_ERR_STATE;
-  if (!c->hand_clearance_ran || c->hand_filter_lists == 0)
+  const int lists = c->hand_drop.lists;
+  if (!c->hand_drop.clearance_ran || lists == 0)
     return 0;
-  if (cap_lists < c->hand_filter_lists || !out)
+  if (cap_lists < lists || !out)
   {
-    c->err = "agh_get_hand_clearance_counts: room for " + std::to_string(c->hand_filter_lists) + " lists is needed";
+    c->err = "agh_get_hand_clearance_counts: room for " + std::to_string(lists) + " lists is needed";
     return AGH_ERR_CAPACITY;
   }
-  for (int k = 0; k < c->hand_filter_lists; k++)
+  for (int k = 0; k < lists; k++)
   {
-    // (without a hand filter its three counters are the zeros hand_filter_stage wrote)
-    const int* h = c->h_hand_counts + k * kHandFilterCounters;
-    out[k].n_tested = c->hand_filter_hyp[k] - ((int64_t) h[0] + h[1] + h[2]);
-    out[k].n_dropped = h[3];
+    const HandDropCounts n = hand_drop_counts(c, k);
+    out[k].n_tested = n.past_filter();
+    out[k].n_dropped = n.clearance;
     out[k].n_kept = out[k].n_tested - out[k].n_dropped;
   }
-  return c->hand_filter_lists;
+  return lists;
 }
 
 }  // extern "C"

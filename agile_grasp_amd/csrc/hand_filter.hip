@@ -3,9 +3,8 @@
 // search's list and counts, per list of the chain, the hands each criterion dropped; k_hog_svm / k_svm_decide label a dropped
 // hand 0 without classifying it and compact_kept_records leaves it out, so the handle search (and its 8192-hand limit) sees the
 // survivors only.  The arithmetic is the contract's, float64, left to right, not contracted (-ffp-contract=off is the build's);
-// tests/hand_filter_cases.py is its numpy model.
-// No translation unit of its own: localize.hip, whose localize_queue runs the stage, includes this file at its end, so the
-// build's list of units (agile_grasp_amd/build.py) stays as it is.
+// tests/hand_filter_cases.py is its numpy model.  The bytes, the counters and what a chain leaves are hand_drop.hip's, whose stage
+// calls hand_filter_launch.
 #include "agh_internal.h"
 
 #include <algorithm>
@@ -18,28 +17,18 @@ namespace
 {
 constexpr int kHfBlock = 256;  // four waves
 
-// the list of the chain a position of its sample list belongs to: the last list whose span starts at or before it and is not
-// empty (k_batch_samples' rule)
-__device__ __forceinline__ int list_of_sample(const BatchCapture* __restrict__ tab, int n_lists, int64_t sample)
-{
-  int l = 0;
-  for (int q = 1; q < n_lists; q++)
-    if (tab[q].soff <= sample && tab[q].S > 0)
-      l = q;
-  return l;
-}
-
-// criteria 1 and 2 on a record's own doubles: 0 kept, 1 outside the approach cone, 2 outside the aperture
+// criteria 1 and 2 on a record's own doubles: 0 kept, else 1 + the counter of the criterion the hand fails (the approach cone,
+// then the aperture)
 __device__ __forceinline__ int cone_and_aperture(const agh_hypothesis& H, const agh_hand_filter_params& p)
 {
   if (p.approach_on)
   {
     const double dot = (H.approach[0] * p.approach_dir[0] + H.approach[1] * p.approach_dir[1]) + H.approach[2] * p.approach_dir[2];
     if (dot < p.min_approach_cos)
-      return 1;
+      return 1 + kDropApproach;
   }
   if (p.width_on && (H.width < p.min_width || H.width > p.max_width))
-    return 2;
+    return 1 + kDropWidth;
   return 0;
 }
 
@@ -75,8 +64,8 @@ __device__ __forceinline__ bool probe_seen(const HandView& V, double w0, double 
   return ok && qz <= (double) z + margin;
 }
 
-// One drop byte per hypothesis in[0, min(*n_in, cap_in)) and the lists' counters (kHandFilterCounters per list: approach, width,
-// unobserved).  The launch is sized for the bound of the list and exits on the count.
+// One drop byte per hypothesis in[0, min(*n_in, cap_in)) and the lists' counters (kHandDropCounters per list; this kernel's
+// are approach, width and unobserved).  The launch is sized for the bound of the list and exits on the count.
 // VIEW = false: a lane per hypothesis.  VIEW = true: a wave per hypothesis, so that the list, the capture and its views are
 // wave-uniform and the view records are read with scalar loads; the lanes take the hand's 2 x n x 3 <= 96 probes, two rounds
 // with a ballot each, every lane testing its probe against the capture's one or two views in turn; lane 0 writes the byte and
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(kHfBlock) void k_hand_filter(const agh_hypothesis* 
     const int reason = cone_and_aperture(in[i], a.p);
     drop[i] = reason ? 1 : 0;
     if (reason)
-      atomicAdd(&counts[(tab ? list_of_sample(tab, n_lists, in[i].sample) : 0) * kHandFilterCounters + reason - 1], 1u);
+      atomicAdd(&counts[(tab ? list_of_sample(tab, n_lists, in[i].sample) : 0) * kHandDropCounters + reason - 1], 1u);
     return;
   }
   const int lane = threadIdx.x & 63;
@@ -148,13 +137,13 @@ __global__ __launch_bounds__(kHfBlock) void k_hand_filter(const agh_hypothesis* 
       unobserved += __popcll(__ballot(unobs));
     }
     if (unobserved > a.p.max_unobserved)
-      reason = 3;
+      reason = 1 + kDropUnobserved;
   }
   if (lane == 0)
   {
     drop[i] = reason ? 1 : 0;
     if (reason)
-      atomicAdd(&counts[l * kHandFilterCounters + reason - 1], 1u);
+      atomicAdd(&counts[l * kHandDropCounters + reason - 1], 1u);
   }
 }
 
@@ -187,25 +176,9 @@ std::string params_fault(const agh_hand_filter_params& p)
 
 namespace agh
 {
-void hand_filter_release(Ctx* c)
-{
-  for (void* p : { (void*) c->d_hand_drop, (void*) c->d_hand_counts, (void*) c->d_hand_views })
-    if (p)
-      (void) hipFree(p);
-  for (void* p : { (void*) c->h_hand_counts, (void*) c->h_hand_views })
-    if (p)
-      (void) hipHostFree(p);
-  c->d_hand_drop = nullptr;
-  c->d_hand_counts = nullptr;
-  c->d_hand_views = nullptr;
-  c->h_hand_counts = nullptr;
-  c->h_hand_views = nullptr;
-  c->hand_drop_cap = 0;
-}
-
 int hand_filter_check(Ctx* c, const char* who, const agh_depth_image* images, const int32_t* n_images, int C, bool has_depth)
 {
-  if (!c->hand_filter_set || !c->hand_filter.view_on)
+  if (!c->hand_drop.filter_set || !c->hand_drop.filter.view_on)
     return AGH_OK;
   if (!has_depth)
   {
@@ -239,9 +212,10 @@ int hand_filter_check(Ctx* c, const char* who, const agh_depth_image* images, co
 void hand_filter_keep_views(Ctx* c, const agh_depth_image* images, const int32_t* n_images, int C, const uint8_t* const* data,
   const int64_t* stride)
 {
-  c->hand_views.clear();
-  c->hand_view_first.assign(1, 0);
-  if (!c->hand_filter_set || !c->hand_filter.view_on)
+  HandDropState& S = c->hand_drop;
+  S.views.clear();
+  S.view_first.assign(1, 0);
+  if (!S.filter_set || !S.filter.view_on)
     return;
   int j = 0;
   for (int k = 0; k < C; k++)
@@ -267,54 +241,21 @@ void hand_filter_keep_views(Ctx* c, const agh_depth_image* images, const int32_t
           v.R[3 * r + s] = im.pose[4 * r + s];
         v.t[r] = im.pose[4 * r + 3];
       }
-      c->hand_views.push_back(v);
+      S.views.push_back(v);
     }
-    c->hand_view_first.push_back(j);
+    S.view_first.push_back(j);
   }
 }
 
-int hand_filter_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st, const uint8_t** drop)
+// k_hand_filter queued on st, a batch's view table uploaded in front of it: every drop byte and the filter's counters
+int hand_filter_launch(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st)
 {
-  *drop = nullptr;
-  c->hand_filter_ran = false;
-  c->hand_clearance_ran = false;
-  if (!c->hand_filter_set && !c->hand_clearance_set)
+  HandDropState& S = c->hand_drop;
+  if (!S.filter_set)
     return AGH_OK;
   static_assert(sizeof(HandView) % 8 == 0, "the table's records are read with scalar loads");
-  const agh_hand_filter_params& p = c->hand_filter;
-  int rc;
+  const agh_hand_filter_params& p = S.filter;
   const int64_t cap = c->s_cap * 8;
-  if (cap > c->hand_drop_cap || !c->d_hand_drop)
-  {
-    c->hand_drop_cap = 0;
-    if ((rc = dev_alloc(c, &c->d_hand_drop, (size_t) std::max<int64_t>(cap, 1))))
-      return rc;
-    c->hand_drop_cap = std::max<int64_t>(cap, 1);
-  }
-  const size_t table_bytes = sizeof(HandView) * (size_t) kMaxHandViews + sizeof(int32_t) * (size_t) (kMaxClouds + 1);
-  if (!c->d_hand_counts)
-  {
-    void* pin = nullptr;
-    if ((rc = dev_alloc(c, &c->d_hand_counts, (size_t) kMaxClouds * kHandFilterCounters)) ||
-        (rc = dev_alloc(c, &c->d_hand_views, table_bytes)))
-      return rc;
-    AGH_HIPCHK(c, hipHostMalloc(&pin, sizeof(int) * (size_t) kMaxClouds * kHandFilterCounters, hipHostMallocDefault));
-    c->h_hand_counts = static_cast<int*>(pin);
-    AGH_HIPCHK(c, hipHostMalloc(&pin, table_bytes, hipHostMallocDefault));
-    c->h_hand_views = static_cast<uint8_t*>(pin);
-  }
-  const int lists = tab ? n_lists : 1;
-  for (int k = 0; k < lists * kHandFilterCounters; k++)
-    c->h_hand_counts[k] = 0;
-  AGH_HIPCHK(c, hipMemsetAsync(c->d_hand_counts, 0, sizeof(unsigned) * (size_t) kMaxClouds * kHandFilterCounters, st));
-  c->hand_filter_ran = c->hand_filter_set;
-  c->hand_clearance_ran = c->hand_clearance_set;
-  *drop = c->d_hand_drop;
-  if (bound <= 0)
-    return AGH_OK;
-  // (agh_set_hand_clearance alone: k_hand_clearance writes every drop byte itself)
-  if (!c->hand_filter_set)
-    return hand_clearance_launch(c, bound, tab, n_lists, st, false);
   HandFilterArgs a;
   std::memset(&a, 0, sizeof(a));
   a.p = p;
@@ -331,8 +272,8 @@ int hand_filter_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_list
   const int32_t* d_vfirst = nullptr;
   if (p.view_on)
   {
-    const int views = (int) c->hand_views.size();
-    const int captures = (int) c->hand_view_first.size() - 1;
+    const int views = (int) S.views.size();
+    const int captures = (int) S.view_first.size() - 1;
     if (views < 1 || views > kMaxHandViews || captures < 1 || captures > kMaxClouds)
     {
       c->err = "the hand filter's observed-space criterion has no views for this chain";
@@ -340,35 +281,35 @@ int hand_filter_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int n_list
     }
     if (tab)
     {
-      std::memcpy(c->h_hand_views, c->hand_views.data(), sizeof(HandView) * (size_t) views);
-      std::memcpy(c->h_hand_views + sizeof(HandView) * (size_t) kMaxHandViews, c->hand_view_first.data(),
+      std::memcpy(S.h_views, S.views.data(), sizeof(HandView) * (size_t) views);
+      std::memcpy(S.h_views + sizeof(HandView) * (size_t) kMaxHandViews, S.view_first.data(),
         sizeof(int32_t) * (size_t) (captures + 1));
-      AGH_HIPCHK(c, hipMemcpyAsync(c->d_hand_views, c->h_hand_views, table_bytes, hipMemcpyHostToDevice, st));
-      d_table = reinterpret_cast<const HandView*>(c->d_hand_views);
-      d_vfirst = reinterpret_cast<const int32_t*>(c->d_hand_views + sizeof(HandView) * (size_t) kMaxHandViews);
+      AGH_HIPCHK(c, hipMemcpyAsync(S.d_views, S.h_views, kHandViewTableBytes, hipMemcpyHostToDevice, st));
+      d_table = reinterpret_cast<const HandView*>(S.d_views);
+      d_vfirst = reinterpret_cast<const int32_t*>(S.d_views + sizeof(HandView) * (size_t) kMaxHandViews);
     }
     else
     {
       pair.n = std::min(views, 2);
       for (int k = 0; k < pair.n; k++)
-        pair.v[k] = c->hand_views[(size_t) k];
+        pair.v[k] = S.views[(size_t) k];
     }
     hipLaunchKernelGGL(k_hand_filter<true>, dim3((unsigned) ((bound + kHfBlock / 64 - 1) / (kHfBlock / 64))), dim3(kHfBlock), 0, st,
       (const agh_hypothesis*) c->d_out_own, (const int64_t*) c->d_nout, cap, a, tab, n_lists, pair, d_table, d_vfirst,
-      (const int32_t*) c->d_idx_own, c->last_s, c->d_xyz, c->stride_floats, (const int*) c->d_cloud_off, c->n_clouds, c->d_hand_drop,
-      c->d_hand_counts);
+      (const int32_t*) c->d_idx_own, c->last_s, c->d_xyz, c->stride_floats, (const int*) c->d_cloud_off, c->n_clouds, S.d_drop,
+      S.d_counts);
   }
   else
     hipLaunchKernelGGL(k_hand_filter<false>, dim3((unsigned) ((bound + kHfBlock - 1) / kHfBlock)), dim3(kHfBlock), 0, st,
       (const agh_hypothesis*) c->d_out_own, (const int64_t*) c->d_nout, cap, a, tab, n_lists, pair, d_table, d_vfirst,
-      (const int32_t*) c->d_idx_own, c->last_s, c->d_xyz, c->stride_floats, (const int*) c->d_cloud_off, c->n_clouds, c->d_hand_drop,
-      c->d_hand_counts);
+      (const int32_t*) c->d_idx_own, c->last_s, c->d_xyz, c->stride_floats, (const int*) c->d_cloud_off, c->n_clouds, S.d_drop,
+      S.d_counts);
   if (hipGetLastError() != hipSuccess)
   {
     c->err = "k_hand_filter launch failed";
     return AGH_ERR_HIP;
   }
-  return c->hand_clearance_set ? hand_clearance_launch(c, bound, tab, n_lists, st, true) : AGH_OK;
+  return AGH_OK;
 }
 }  // namespace agh
 
@@ -402,7 +343,7 @@ int agh_set_hand_filter(agh_ctx* ctx, const agh_hand_filter_params* fp)
   }
   if (!fp)
   {
-    c->hand_filter_set = false;
+    c->hand_drop.filter_set = false;
     return AGH_OK;
   }
   const std::string fault = params_fault(*fp);
@@ -411,9 +352,9 @@ int agh_set_hand_filter(agh_ctx* ctx, const agh_hand_filter_params* fp)
     c->err = "agh_set_hand_filter: " + fault;
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  c->hand_filter = *fp;
-  c->hand_filter.reserved = 0;
-  c->hand_filter_set = true;
+  c->hand_drop.filter = *fp;
+  c->hand_drop.filter.reserved = 0;
+  c->hand_drop.filter_set = true;
   return AGH_OK;
 }
 
@@ -422,14 +363,14 @@ int agh_get_hand_filter(agh_ctx* ctx, agh_hand_filter_params* out)
   if (!ctx)
     return AGH_ERR_INVALID_ARGUMENT;
   Ctx* c = &ctx->c;
-  if (!c->hand_filter_set)
+  if (!c->hand_drop.filter_set)
     return 0;
   if (!out)
   {
     c->err = "agh_get_hand_filter: out is NULL";
     return AGH_ERR_INVALID_ARGUMENT;
   }
-  *out = c->hand_filter;
+  *out = c->hand_drop.filter;
   return 1;
 }
 
@@ -440,23 +381,24 @@ int agh_get_hand_filter_counts(agh_ctx* ctx, agh_hand_filter_counts* out, int32_
   Ctx* c = &ctx->c;
   if (refuse_mid_chain(c, "agh_get_hand_filter_counts"))
     return AGH_ERR_STATE;
-  if (!c->hand_filter_ran || c->hand_filter_lists == 0)
+  const int lists = c->hand_drop.lists;
+  if (!c->hand_drop.filter_ran || lists == 0)
     return 0;
-  if (cap_lists < c->hand_filter_lists || !out)
+  if (cap_lists < lists || !out)
   {
-    c->err = "agh_get_hand_filter_counts: room for " + std::to_string(c->hand_filter_lists) + " lists is needed";
+    c->err = "agh_get_hand_filter_counts: room for " + std::to_string(lists) + " lists is needed";
     return AGH_ERR_CAPACITY;
   }
-  for (int k = 0; k < c->hand_filter_lists; k++)
+  for (int k = 0; k < lists; k++)
   {
-    const int* h = c->h_hand_counts + k * kHandFilterCounters;
-    out[k].n_hypotheses = c->hand_filter_hyp[k];
-    out[k].n_dropped_approach = h[0];
-    out[k].n_dropped_width = h[1];
-    out[k].n_dropped_unobserved = h[2];
-    out[k].n_kept = c->hand_filter_hyp[k] - ((int64_t) h[0] + h[1] + h[2]);
+    const HandDropCounts n = hand_drop_counts(c, k);
+    out[k].n_hypotheses = n.hypotheses;
+    out[k].n_dropped_approach = n.approach;
+    out[k].n_dropped_width = n.width;
+    out[k].n_dropped_unobserved = n.unobserved;
+    out[k].n_kept = n.past_filter();
   }
-  return c->hand_filter_lists;
+  return lists;
 }
 
 }  // extern "C"

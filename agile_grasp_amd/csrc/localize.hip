@@ -36,8 +36,8 @@ extern "C" __global__ void k_draw_samples(const int* __restrict__ cloud_off, int
 // box.on (a chain with filters_boundaries and no classifier): the hands Localization::filterHands drops are left out too (with
 // the classifier their svm_keep is 0 already).
 // host_counts: [4] hypotheses, [5] kept, [6] the search's error word.
-// drop (agh_set_hand_filter; null: none): the hand filter's bytes -- a dropped hand is left out -- and its counters, which go to
-// the pinned hf_host with the counts.
+// drop (null: none): the hand drop stage's bytes -- a dropped hand is left out -- and its counters, which go to the pinned hf_host
+// with the counts.
 extern "C" __global__ __launch_bounds__(1024) void k_compact_kept(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
   int64_t cap_in, int use_keep, BoundaryBox box, agh_hypothesis* __restrict__ out, int out_cap, int* __restrict__ n_out,
   agh_hypothesis* __restrict__ host_out, int host_cap, int* __restrict__ host_counts, const int32_t* __restrict__ flags,
@@ -48,7 +48,7 @@ extern "C" __global__ __launch_bounds__(1024) void k_compact_kept(const agh_hypo
   __shared__ int carry;
   const int64_t n = min(*n_in, cap_in);
   const int K = compact_kept_records(in, 0, n, use_keep, box.on, box.ws, src, wsum, &carry, out, out_cap, host_out, host_cap, 0, drop);
-  if (drop && threadIdx.x < kHandFilterCounters)
+  if (drop && threadIdx.x < kHandDropCounters)
     hf_host[threadIdx.x] = (int) hf_counts[threadIdx.x];
   if (threadIdx.x == 0)
   {
@@ -218,16 +218,17 @@ static int localize_queue(agh_ctx* ctx, bool handles_only)
     // (filters_boundaries: the classifier labels the hands near the workspace's faces 0 without classifying them; without it,
     // the compaction drops them)
     const double* ws = L.filters ? L.lp.workspace : nullptr;
-    // (agh_set_hand_filter: k_hand_filter's drop bytes, which the classifier and the compaction honour beside the box; null and
-    // nothing launched without a filter)
-    const uint8_t* drop = nullptr;
-    if ((rc = hand_filter_stage(c, std::min<int64_t>(c->last_s * 8, c->last_cap), nullptr, 1, st, &drop)) != AGH_OK)
-      return rc;
-    if (L.classify && (rc = hog_svm(c, std::min<int64_t>(c->last_s * 8, c->last_cap), c->d_keep, st, ws, drop)) != AGH_OK)
+    // (the hand drop stage's bytes, which the classifier and the compaction honour beside the box; null and nothing launched
+    // without a test set)
+    const int64_t hyp_bound = std::min<int64_t>(c->last_s * 8, c->last_cap);
+    const HandDropView hd = hand_drop_stage(c, hyp_bound, nullptr, 1, st);
+    if (hd.rc != AGH_OK)
+      return hd.rc;
+    if (L.classify && (rc = hog_svm(c, hyp_bound, c->d_keep, st, ws, hd.drop)) != AGH_OK)
       return rc;
     hipLaunchKernelGGL(k_compact_kept, dim3(1), dim3(1024), 0, st, (const agh_hypothesis*) c->d_out_own, (const int64_t*) c->d_nout,
       c->s_cap * 8, L.classify ? 1 : 0, boundary_box(L.classify ? nullptr : ws), c->d_h_hands, (int) hand_bound, d_hcount, pin.hands,
-      (int) c->h_pin_handles_cap, pin.counts, (const int32_t*) c->d_flags, drop, (const unsigned*) c->d_hand_counts, c->h_hand_counts);
+      (int) c->h_pin_handles_cap, pin.counts, (const int32_t*) c->d_flags, hd.drop, hd.d_counts, hd.h_counts);
     if (hipGetLastError() != hipSuccess)
     {
       c->err = "k_compact_kept launch failed";
@@ -623,7 +624,7 @@ static int localize_end_impl(agh_ctx* ctx, const ChainOutputs& out, agh_localize
   LocalizeState& L = c->loc;
   L.active = false;
   c->results = ChainResults{};
-  c->hand_filter_lists = 0;
+  hand_drop_collect(c, 0, nullptr);
   const int64_t S = L.S;
   const HandlePins pin = handle_pins(c);
   const int* h_counts = pin.counts;
@@ -712,8 +713,7 @@ static int localize_end_impl(agh_ctx* ctx, const ChainOutputs& out, agh_localize
   if ((rc = chain_collect(ctx, "agh_localize", nullptr, 1, h_counts, 0, S, nullptr, localize_queue)) != AGH_OK)
     return rc;
   const int64_t n_hyp = h_counts[4], n_kept = h_counts[5];
-  c->hand_filter_lists = 1;  // (agh_get_hand_filter_counts: the counters are in pinned memory if the chain ran the filter)
-  c->hand_filter_hyp[0] = n_hyp;
+  hand_drop_collect(c, 1, &n_hyp);  // (the counters are in pinned memory if the chain ran a test)
   c->last_nout = std::min<int64_t>(n_hyp, c->s_cap * 8);
   if (result)
     *result = agh_localize_result{ L.nv, n_hyp, n_kept, h_counts[0], h_counts[1] };
@@ -1213,8 +1213,3 @@ int agh_localize_stage(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, int
 }
 
 }  // extern "C"
-
-// ---- the hand filter's stage, kernel and entry points (agh_set_hand_filter): a file of its own, compiled here ----
-#include "hand_filter.hip"
-// ---- the corridor test behind it (agh_set_hand_clearance), likewise ----
-#include "hand_clearance.hip"

@@ -201,8 +201,8 @@ __global__ __launch_bounds__(1024) void k_compact_kept_batch(const agh_hypothesi
   const int room = min(slot, host_slot);
   const int K = compact_kept_records(in, r0, r1, use_keep, filters, ws, src, wsum, &carry, out + (int64_t) cap * slot, room,
     host_out + (int64_t) cap * host_slot, room, (int) s0, drop);
-  if (drop && tid < kHandFilterCounters)  // (agh_set_hand_filter: the list's counters to pinned memory with its counts)
-    hf_host[cap * kHandFilterCounters + tid] = (int) hf_counts[cap * kHandFilterCounters + tid];
+  if (drop && tid < kHandDropCounters)  // (the hand drop stage: the list's counters to pinned memory with its counts)
+    hf_host[cap * kHandDropCounters + tid] = (int) hf_counts[cap * kHandDropCounters + tid];
   if (tid == 0)
   {
     n_out[cap] = K;
@@ -436,16 +436,17 @@ int batch_queue(agh_ctx* ctx, bool handles_only)
     c->mirror = HostMirror{ nullptr, 0, nullptr };
     if ((rc = agh_find_hands_device(ctx, c->d_idx_own, B.S_tot, 0, c->d_out_own, c->s_cap * 8, c->d_nout, st)) != AGH_OK)
       return rc;
-    // (agh_set_hand_filter: as in localize_queue, with the list table to find a hand's list, capture and views)
-    const uint8_t* drop = nullptr;
-    if ((rc = hand_filter_stage(c, std::min<int64_t>(c->last_s * 8, c->last_cap), b->d_tab, C, st, &drop)) != AGH_OK)
-      return rc;
-    if (B.classify && (rc = hog_svm(c, std::min<int64_t>(c->last_s * 8, c->last_cap), c->d_keep, st, nullptr, drop)) != AGH_OK)
+    // (the hand drop stage as in localize_queue, with the list table to find a hand's list, capture and views)
+    const int64_t hyp_bound = std::min<int64_t>(c->last_s * 8, c->last_cap);
+    const HandDropView hd = hand_drop_stage(c, hyp_bound, b->d_tab, C, st);
+    if (hd.rc != AGH_OK)
+      return hd.rc;
+    if (B.classify && (rc = hog_svm(c, hyp_bound, c->d_keep, st, nullptr, hd.drop)) != AGH_OK)
       return rc;
     hipLaunchKernelGGL(k_compact_kept_batch, dim3(C), dim3(1024), 0, st, (const agh_hypothesis*) c->d_out_own,
       (const int64_t*) c->d_nout, c->s_cap * 8, B.classify ? 1 : 0, B.filters ? 1 : 0, (const BatchCapture*) b->d_tab, b->d.hands,
-      (int) b->slot, b->d_count, b->h_hands, (int) b->h_slot, b->h_counts, (const int32_t*) c->d_flags, drop,
-      (const unsigned*) c->d_hand_counts, c->h_hand_counts);
+      (int) b->slot, b->d_count, b->h_hands, (int) b->h_slot, b->h_counts, (const int32_t*) c->d_flags, hd.drop,
+      hd.d_counts, hd.h_counts);
     if (hipGetLastError() != hipSuccess)
     {
       c->err = "k_compact_kept_batch launch failed";
@@ -936,7 +937,7 @@ int batch_end_impl(agh_ctx* ctx, const ChainOutputs& out, agh_localize_batch_res
   c->loc.active = false;
   c->loc.batch = false;
   c->results = ChainResults{};
-  c->hand_filter_lists = 0;
+  hand_drop_collect(c, 0, nullptr);
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)
@@ -1088,11 +1089,11 @@ int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t
   if ((rc = chain_collect(ctx, who, unit, C, hc, kBatchCountsStride, S_tot, b->h_bad, batch_queue, B.per_object() ? &names : nullptr)) != AGH_OK)
     return rc;
   int64_t n_hyp_tot = 0, tot_handles = 0, tot_idx = 0, tot_hands = 0;
-  c->hand_filter_lists = C;  // (agh_get_hand_filter_counts)
+  int64_t n_hyp[kMaxClouds];
   for (int k = 0; k < C; k++)
   {
     const int* h = hc + k * kBatchCountsStride;
-    c->hand_filter_hyp[k] = h[4];
+    n_hyp[k] = h[4];
     if (results)
       results[k] = agh_localize_batch_result{ { nv[k], h[4], h[5], h[0], h[1] }, tot_handles, tot_idx, tot_hands, B.soff[k] };
     n_hyp_tot += h[4];
@@ -1100,6 +1101,7 @@ int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t
     tot_idx += h[1];
     tot_hands += h[5];
   }
+  hand_drop_collect(c, C, n_hyp);
   c->last_nout = std::min<int64_t>(n_hyp_tot, c->s_cap * 8);
   if (out.samples && S_tot > 0)
     std::memcpy(out.samples, b->h_samples, sizeof(int32_t) * (size_t) S_tot);

@@ -513,3 +513,40 @@ def test_set_then_clear_is_never_set(ctxs, svm_model):
         _same(got_b[k], want_b[k], f"cleared, capture {k}")
     assert one.hand_clearance_counts().shape == (0, 3)
     fresh.close()
+
+
+# ---- 11. the settings take turns on one context ----
+
+def test_settings_alternate_on_one_context(ctxs, svm_model):
+    """what a chain leaves for the two counts getters is that chain's alone: filter only, clearance only, neither, both, a
+    two-capture depth batch with both, then a single chain with the clearance only, all on one context, each step held against a
+    fresh context that ran nothing but that step with the same settings"""
+    one, _ = ctxs
+    sc, sc2 = HF.box_scene(2), HF.box_scene(2, w=144, h=100, f=180.0)
+    fp, cp = HF.scene_filters(sc)["all"], HC.params()
+    single = lambda c: [c.localize_depth(sc["images"], sc["ws"], samples=sc["samples"], **KW)]
+    batch = lambda c: c.localize_depth_batch([sc["images"], sc2["images"]], [sc["ws"], sc2["ws"]], samples=[sc["samples"], sc2["samples"]], **KW)
+    steps = [("filter only", fp, None, single, 1), ("clearance only", None, cp, single, 1), ("neither", None, None, single, 1),
+             ("both", fp, cp, single, 1), ("batch with both", fp, cp, batch, 2), ("clearance only, after the batch", None, cp, single, 1)]
+    for what, f, cl, run, lists in steps:
+        (fresh,) = _contexts(sc["origins"], svm_model, n=1)
+        for c in (one, fresh):
+            c.clear_hand_filter()
+            c.clear_hand_clearance()
+            if f is not None:
+                c.set_hand_filter(**f)
+            if cl is not None:
+                c.set_hand_clearance(**cl)
+        got, want = run(one), run(fresh)
+        fc, cc = one.hand_filter_counts(), one.hand_clearance_counts()
+        print(what, "filter", fc.tolist(), "clearance", cc.tolist(), "hands", [len(g["hands"]) for g in got])
+        assert len(got) == len(want) == lists, what
+        for k in range(lists):
+            _same(got[k], want[k], f"{what}, list {k}")
+        assert fc.tolist() == fresh.hand_filter_counts().tolist() and cc.tolist() == fresh.hand_clearance_counts().tolist(), what
+        # (no records exactly where the test is not set, one per list of THIS chain where it is)
+        assert fc.shape == ((lists, 5) if f is not None else (0, 5)) and cc.shape == ((lists, 3) if cl is not None else (0, 3)), what
+        if f is not None and cl is not None:  # both tests bite and both keep: every list drops and keeps under each
+            assert (fc[:, 1:4].sum(1) >= 1).all() and (fc[:, 4] >= 1).all() and (cc[:, 1] >= 1).all() and (cc[:, 2] >= 1).all(), what
+            assert (cc[:, 0] == fc[:, 4]).all() and all(len(g["hands"]) >= 1 for g in got), what
+        fresh.close()
