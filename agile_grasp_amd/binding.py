@@ -117,6 +117,7 @@ EXPORTS = [
     "agh_localize_depth_batch_clustered_fit_device", "agh_localize_depth_batch_clustered_fit_begin",
     "agh_localize_depth_batch_clustered_fit_begin_device", "agh_get_batch_plane_fit", "agh_get_batch_plane_fit_candidates",
     "agh_default_depth_filter_params", "agh_set_depth_filter", "agh_get_depth_filter", "agh_get_depth_filter_counts",
+    "agh_default_depth_fusion_params", "agh_fuse_depth", "agh_fuse_depth_device", "agh_get_depth_fusion_counts", "agh_get_fused_depth",
     "agh_default_voxel_filter_params", "agh_set_voxel_filter", "agh_get_voxel_filter", "agh_get_voxel_filter_counts",
     "agh_default_hand_filter_params", "agh_set_hand_filter", "agh_get_hand_filter", "agh_get_hand_filter_counts",
     "agh_default_hand_clearance_params", "agh_set_hand_clearance", "agh_get_hand_clearance", "agh_get_hand_clearance_counts",
@@ -259,6 +260,15 @@ class AghDepthFilterCounts(C.Structure):
     _fields_ = [("n_valid", C.c_int64), ("n_out_of_range", C.c_int64), ("n_unsupported", C.c_int64), ("n_kept", C.c_int64)]
 
 
+class AghDepthFusionParams(C.Structure):
+    _fields_ = [("min_valid", C.c_int32), ("reserved", C.c_int32), ("max_spread_abs", C.c_double), ("max_spread_rel", C.c_double)]
+
+
+class AghDepthFusionCounts(C.Structure):
+    _fields_ = [("n_pixels", C.c_int64), ("n_empty", C.c_int64), ("n_unsupported", C.c_int64), ("n_inconsistent", C.c_int64),
+                ("n_fused", C.c_int64), ("n_filled", C.c_int64)]
+
+
 class AghVoxelFilterParams(C.Structure):
     _fields_ = [("radius", C.c_int32), ("min_neighbors", C.c_int32)]
 
@@ -329,6 +339,41 @@ def depth_filter_params(**fields) -> AghDepthFilterParams:
             raise TypeError(f"agh_depth_filter_params has no field {k}")
         setattr(fp, k, v)
     return fp
+
+
+def depth_fusion_params(**fields) -> AghDepthFusionParams:
+    """agh_default_depth_fusion_params, then the given fields."""
+    fp = AghDepthFusionParams()
+    load_library().agh_default_depth_fusion_params(C.byref(fp))
+    for k, v in fields.items():
+        if not hasattr(fp, k):
+            raise TypeError(f"agh_depth_fusion_params has no field {k}")
+        setattr(fp, k, v)
+    return fp
+
+
+class DeviceImage:
+    """A fused depth image in a slot buffer of its context (Context.fuse_depth): the few tensor methods depth_image_records asks
+    of a torch CUDA tensor, so that the handle goes wherever such a tensor goes.  Valid until its slot is fused again or the
+    context is closed."""
+    is_cuda = True
+
+    def __init__(self, rec: "AghDepthImage"):
+        self._ptr, self.shape = int(rec.data), (int(rec.height), int(rec.width))
+        self._es = 2 if rec.format == DEPTH_U16 else 4
+        self._row = int(rec.row_stride_bytes) // self._es
+
+    def dim(self):
+        return 2
+
+    def stride(self, k: int):
+        return (self._row, 1)[k]
+
+    def element_size(self):
+        return self._es
+
+    def data_ptr(self):
+        return self._ptr
 
 
 def depth_image_records(images):
@@ -516,6 +561,7 @@ def load_library():
         lib.agh_default_cluster_params.restype = None
         lib.agh_default_plane_fit_params.restype = None
         lib.agh_default_depth_filter_params.restype = None
+        lib.agh_default_depth_fusion_params.restype = None
         lib.agh_default_voxel_filter_params.restype = None
         lib.agh_default_hand_filter_params.restype = None
         lib.agh_default_hand_clearance_params.restype = None
@@ -550,6 +596,7 @@ class Context:
         if rc != 0:
             raise AghError(rc, self.lib.agh_last_error(None).decode())
         self._keep = []  # device tensors that must outlive the context's use of them
+        self._fuse_keep = {}  # slot -> the device frames of its last fuse_depth
 
     def close(self):
         if self._h:
@@ -635,6 +682,42 @@ class Context:
         recs = (AghDepthFilterCounts * 128)()
         k = self._check(self.lib.agh_get_depth_filter_counts(self._h, recs, C.c_int32(128)))
         return np.array([[r.n_valid, r.n_out_of_range, r.n_unsupported, r.n_kept] for r in recs[:k]], np.int64).reshape(k, 4)
+
+    def fuse_depth(self, frames, slot: int = 0, **params):
+        """agh_fuse_depth (torch CUDA tensors: agh_fuse_depth_device): the burst `frames` of ONE camera -- 1 to 16 image dicts
+        as depth_image_records takes them, equal in everything but the pixels and the row stride -- fused into slot `slot`
+        (0 .. 127) of this context; `params`: min_valid, max_spread_abs, max_spread_rel on top of the defaults.  Returns frame
+        0's dict with `data` a DeviceImage: it goes into every localize_depth* form as a CUDA tensor does, with no
+        synchronisation in between."""
+        recs, keep, on_device = depth_image_records(frames)
+        fp = depth_fusion_params(**params)
+        out = AghDepthImage()
+        fn = self.lib.agh_fuse_depth_device if on_device else self.lib.agh_fuse_depth
+        self._check(fn(self._h, recs, C.c_int32(len(recs)), C.byref(fp), C.c_int32(slot), C.byref(out)))
+        if on_device:  # (read until the next synchronisation: kept until the slot is fused again)
+            self._fuse_keep[slot] = keep
+        fused = dict(frames[0])
+        fused["data"] = DeviceImage(out)
+        if out.format == DEPTH_U16:
+            fused["depth_scale"] = float(out.depth_scale)
+        return fused
+
+    def depth_fusion_counts(self, slot: int = 0):
+        """agh_get_depth_fusion_counts: the slot's AghDepthFusionCounts record, or None if the slot was never fused."""
+        rec = AghDepthFusionCounts()
+        return rec if self._check(self.lib.agh_get_depth_fusion_counts(self._h, C.c_int32(slot), C.byref(rec))) == 1 else None
+
+    def fused_depth(self, slot: int = 0):
+        """agh_get_fused_depth: the slot's fused image, an (H, W) uint16 or float32 array, or None if the slot was never fused."""
+        rec = AghDepthImage()
+        rc = self.lib.agh_get_fused_depth(self._h, C.c_int32(slot), None, C.c_int64(0), C.byref(rec))  # (the record: the image's size)
+        if rc != AGH_ERR_CAPACITY:
+            self._check(rc)
+            return None
+        out = np.empty((rec.height, rec.width), np.uint16 if rec.format == DEPTH_U16 else np.float32)
+        got = self._check(self.lib.agh_get_fused_depth(self._h, C.c_int32(slot), out.ctypes.data_as(C.c_void_p), C.c_int64(out.nbytes), None))
+        assert got == out.nbytes
+        return out
 
     def set_voxel_filter(self, fp=None, **fields):
         """agh_set_voxel_filter: every later voxelisation of this context (preprocess*, every localize* form) prunes the voxels

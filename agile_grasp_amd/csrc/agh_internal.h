@@ -282,6 +282,32 @@ struct HandDropState
   int lists = 0;
   int64_t hyp[kMaxClouds] = {};
 };
+// agh_fuse_depth (depth_fuse.hip): a slot holds one fused image in a device buffer of its own, regrown when an image is larger, the
+// record handed out for it, and the event behind its last kernel and the copy of its counters
+constexpr int kFuseSlots = 128, kFuseMaxFrames = 16;
+enum FuseCounter : int { kFuseEmpty = 0, kFuseUnsupported, kFuseInconsistent, kFuseFused, kFuseFilled, kFuseCounters };
+// a slot's counters: kFuseRows rows of kFuseCounters, a row every 256 bytes (the kernel's waves spread their atomics over the rows,
+// the getter adds the rows up)
+constexpr int kFuseRows = 64, kFuseRowWords = 32, kFuseSlotWords = kFuseRows * kFuseRowWords;
+struct DepthFuseSlot
+{
+  uint8_t* d = nullptr;
+  int64_t cap = 0;
+  bool fused = false;
+  agh_depth_image rec = {};
+  hipEvent_t done = nullptr;
+};
+struct DepthFuseState
+{
+  DepthFuseSlot slot[kFuseSlots];
+  // host frames, rows packed, each at a 256-byte boundary; the kernel reads them from here
+  uint8_t* d_stage = nullptr;
+  int64_t stage_cap = 0;
+  hipEvent_t staged = nullptr;  // behind the copies of page-locked frames
+  // kFuseSlots x kFuseSlotWords: the device's, a slot's zeroed in front of its kernel, and the pinned copy queued behind it
+  unsigned long long* d_counts = nullptr;
+  int64_t* h_counts = nullptr;
+};
 struct HandDropView  // what the stage hands the classifier and the compaction, host-side: all null without a test
 {
   int rc = AGH_OK;
@@ -603,6 +629,7 @@ struct Ctx
   int filter_views = 0;
   hipStream_t filter_stream = nullptr;
   HandDropState hand_drop;         // the hand drop stage (hand_drop.hip): agh_set_hand_filter, agh_set_hand_clearance
+  DepthFuseState* fuse = nullptr;  // agh_fuse_depth's slots, staging buffer and counters (depth_fuse.hip), made by its first call
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
   LocalizeBatchState* lbatch = nullptr;  // agh_localize_batch's buffers (localize_batch.hip), made by its first call
   bool batch_active = false;       // inside agh_localize_batch (agh_localize_begin refuses)
@@ -896,6 +923,21 @@ inline bool refuse_mid_chain(Ctx* c, const char* fn)
   return true;
 }
 
+// Page-locked host memory (hipHostMalloc / hipHostRegister)?  A copy from it is truly asynchronous: it returns before the
+// source has been read, where a pageable copy returns after.
+inline bool is_pinned_host(const void* p)
+{
+  if (!p)
+    return false;
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess)
+  {
+    (void) hipGetLastError();  // (an unregistered pointer is an error on older runtimes, hipMemoryTypeUnregistered on newer ones)
+    return false;
+  }
+  return a.type == hipMemoryTypeHost;
+}
+
 // The stage stream and its events, made by the first agh_localize_stage / agh_localize_batch_stage of a context.
 inline int ensure_stage_stream(Ctx* c, const char* fn)
 {
@@ -1154,6 +1196,7 @@ HandDropView hand_drop_stage(Ctx* c, int64_t bound, const BatchCapture* tab, int
 void hand_drop_collect(Ctx* c, int lists, const int64_t* hyp);
 HandDropCounts hand_drop_counts(const Ctx* c, int k);
 void hand_drop_release(Ctx* c);
+void depth_fuse_release(Ctx* c);
 // the two tests, each launched only if its own setting is set.  has_drop: the bytes are written already (the kernel skips the
 // dropped hands); else it writes every byte itself
 int hand_filter_launch(Ctx* c, int64_t bound, const BatchCapture* tab, int n_lists, hipStream_t st);

@@ -509,6 +509,7 @@ void agh_destroy(agh_ctx* ctx)
   plane_release(c);
   localize_batch_release(c);
   hand_drop_release(c);
+  depth_fuse_release(c);
   void* ptrs[] = { c->own_xyz, c->own_cam, c->d_desc, c->d_bbox_part, c->d_cell_start, c->d_cell_count, c->d_block_sums, c->d_cell_of,
     c->d_rank_of, c->d_sorted, c->d_samples, c->d_sums, c->d_nt, c->d_nh, c->d_status, c->d_nbr, c->d_eig, c->d_frames, c->d_slots,
     c->d_images, c->d_slot_index, c->d_scan_tmp, c->d_out_own, c->d_nout, c->d_out_images, c->d_draw_ofs, c->d_draws,
@@ -681,21 +682,6 @@ int agh_set_cloud(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, const in
 {
   const int64_t offsets[2] = { 0, n };
   return agh_set_cloud_batch(ctx, xyz, stride_bytes, cam_source, offsets, 1);
-}
-
-// Page-locked host memory (hipHostMalloc / hipHostRegister)?  A copy from it is truly asynchronous: it returns before the
-// source has been read, where a pageable copy returns after.
-static bool is_pinned_host(const void* p)
-{
-  if (!p)
-    return false;
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess)
-  {
-    (void) hipGetLastError();  // (an unregistered pointer is an error on older runtimes, hipMemoryTypeUnregistered on newer ones)
-    return false;
-  }
-  return a.type == hipMemoryTypeHost;
 }
 
 int agh_set_cloud_batch(agh_ctx* ctx, const float* xyz, int64_t stride_bytes, const int32_t* cam_source, const int64_t* offsets,

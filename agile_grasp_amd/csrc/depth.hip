@@ -3,7 +3,8 @@
 // k_deproject and its launch, the argument rules, the context's two depth buffers (this capture's images and the staged next
 // ones), agh_deproject and agh_localize_depth_stage; the chain itself is localize.hip's.  The depth filter (agh_set_depth_filter):
 // its setting, k_deproject_filtered / k_deproject_filtered_batch, which take the plain kernels' place while a filter is set, and
-// their per-view counters.
+// their per-view counters.  depth_fuse.hip (agh_fuse_depth: a burst of frames fused into one device image ahead of all this) is included
+// at the end.
 #include "agh_internal.h"
 
 #include <algorithm>
@@ -568,6 +569,40 @@ int ensure_depth_buffer(Ctx* c, uint8_t** buf, int64_t* cap, int64_t need)
   return AGH_OK;
 }
 
+// depth_check's rules for ONE image: the text of the first rule broken, without a prefix, or an empty string (agh_fuse_depth's
+// frames are checked with it too, under their own names)
+std::string depth_image_fault(const agh_depth_image& im, bool on_device)
+{
+  if (!im.data)
+    return "data is NULL";
+  if (im.width < 1 || im.width > 8192)
+    return "width must be 1..8192";
+  if (im.height < 1 || im.height > 8192)
+    return "height must be 1..8192";
+  if (im.format != AGH_DEPTH_U16 && im.format != AGH_DEPTH_F32)
+    return "format must be AGH_DEPTH_U16 or AGH_DEPTH_F32";
+  const int64_t es = elem_size(im.format);
+  // (a host image is repacked by its copy; a device image is read in place, an element at a time at the least)
+  if (on_device && reinterpret_cast<uintptr_t>(im.data) % (uintptr_t) es != 0)
+    return "data (a device pointer) must be aligned to the element size";
+  if (im.row_stride_bytes < im.width * es || im.row_stride_bytes % es != 0)
+    return "row_stride_bytes must be at least width x element size and a multiple of the element size";
+  if (!std::isfinite(im.fx) || im.fx == 0.0)
+    return "fx must be finite and not zero";
+  if (!std::isfinite(im.fy) || im.fy == 0.0)
+    return "fy must be finite and not zero";
+  if (!std::isfinite(im.cx))
+    return "cx must be finite";
+  if (!std::isfinite(im.cy))
+    return "cy must be finite";
+  for (int q = 0; q < 12; q++)
+    if (!std::isfinite(im.pose[q]))
+      return "pose[" + std::to_string(q) + "] must be finite";
+  if (im.format == AGH_DEPTH_U16 && !(std::isfinite(im.depth_scale) && im.depth_scale > 0.0f))
+    return "depth_scale must be finite and positive";
+  return std::string();
+}
+
 void swap_depth_buffers(Ctx* c)
 {
   std::swap(c->d_depth, c->d_depth_stage);
@@ -591,33 +626,9 @@ int depth_check(Ctx* c, const char* who, const agh_depth_image* images, int32_t 
   {
     const agh_depth_image& im = images[k];
     const std::string at = (capture >= 0 ? cap + ", " : cap) + "image " + std::to_string(k) + ": ";
-    if (!im.data)
-      return bad(at + "data is NULL");
-    if (im.width < 1 || im.width > 8192)
-      return bad(at + "width must be 1..8192");
-    if (im.height < 1 || im.height > 8192)
-      return bad(at + "height must be 1..8192");
-    if (im.format != AGH_DEPTH_U16 && im.format != AGH_DEPTH_F32)
-      return bad(at + "format must be AGH_DEPTH_U16 or AGH_DEPTH_F32");
-    const int64_t es = elem_size(im.format);
-    // (a host image is repacked by its copy; a device image is read in place, an element at a time at the least)
-    if (on_device && reinterpret_cast<uintptr_t>(im.data) % (uintptr_t) es != 0)
-      return bad(at + "data (a device pointer) must be aligned to the element size");
-    if (im.row_stride_bytes < im.width * es || im.row_stride_bytes % es != 0)
-      return bad(at + "row_stride_bytes must be at least width x element size and a multiple of the element size");
-    if (!std::isfinite(im.fx) || im.fx == 0.0)
-      return bad(at + "fx must be finite and not zero");
-    if (!std::isfinite(im.fy) || im.fy == 0.0)
-      return bad(at + "fy must be finite and not zero");
-    if (!std::isfinite(im.cx))
-      return bad(at + "cx must be finite");
-    if (!std::isfinite(im.cy))
-      return bad(at + "cy must be finite");
-    for (int q = 0; q < 12; q++)
-      if (!std::isfinite(im.pose[q]))
-        return bad(at + "pose[" + std::to_string(q) + "] must be finite");
-    if (im.format == AGH_DEPTH_U16 && !(std::isfinite(im.depth_scale) && im.depth_scale > 0.0f))
-      return bad(at + "depth_scale must be finite and positive");
+    const std::string fault = depth_image_fault(im, on_device);
+    if (!fault.empty())
+      return bad(at + fault);
     total += (int64_t) im.width * im.height;
   }
   if (n_points)
@@ -1026,3 +1037,6 @@ int agh_localize_depth_stage(agh_ctx* ctx, const agh_depth_image* images, int32_
 }
 
 }  // extern "C"
+
+// agh_fuse_depth and k_depth_fuse: part of this translation unit (the per-image rules and the packing of host images are shared)
+#include "depth_fuse.hip"

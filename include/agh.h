@@ -293,7 +293,8 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_remove_plane, agh_get_cloud, agh_get_sample_mask_count, agh_get_label_counts, agh_get_cluster_info,
  * agh_get_cluster_labels, agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts,
  * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels, agh_get_batch_plane_fit,
- * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts, agh_get_voxel_filter_counts, agh_get_hand_filter_counts, agh_get_hand_clearance_counts and every getter of device results (frames, normals,
+ * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts, agh_get_voxel_filter_counts, agh_get_hand_filter_counts, agh_get_hand_clearance_counts,
+ * agh_fuse_depth, agh_fuse_depth_device, agh_get_depth_fusion_counts, agh_get_fused_depth and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
  * sharded calls are collective and do not return early: on such a context they take part without searching, and every rank of
@@ -732,7 +733,8 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts, agh_get_batch_label_counts, agh_get_batch_cluster_info,
  * agh_get_batch_cluster_labels, agh_get_batch_plane_fit, agh_get_batch_plane_fit_candidates, agh_set_depth_filter,
  * agh_get_depth_filter_counts, agh_set_voxel_filter, agh_get_voxel_filter_counts, agh_set_hand_filter,
- * agh_get_hand_filter_counts, agh_set_hand_clearance and agh_get_hand_clearance_counts are refused as well; agh_get_hand_clearance
+ * agh_get_hand_filter_counts, agh_set_hand_clearance and agh_get_hand_clearance_counts are refused as well, and so are
+ * agh_fuse_depth, agh_fuse_depth_device, agh_get_depth_fusion_counts and agh_get_fused_depth; agh_get_hand_clearance
  * is host-side and allowed, as agh_get_hand_filter),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
@@ -836,8 +838,8 @@ int agh_deproject_batch(agh_ctx* ctx, const agh_depth_image* images, const int32
  * follow capture k - 1's): n_valid = n_out_of_range + n_unsupported + n_kept.  Returns the number of views, or 0 if the last
  * deprojection ran unfiltered (or none ran); AGH_ERR_CAPACITY if cap_views is smaller; AGH_ERR_STATE mid-chain.  One small copy
  * and one synchronisation.
- * Not built: temporal filtering over frames, hole filling, lens distortion, per-image parameters (the points forms have a
- * filter of their own: agh_set_voxel_filter below). */
+ * Not built: temporal filtering and hole filling inside the filter (a burst is fused ahead of it: agh_fuse_depth below),
+ * lens distortion, per-image parameters (the points forms have a filter of their own: agh_set_voxel_filter below). */
 typedef struct agh_depth_filter_params
 {
   int32_t radius;        /* 1 or 2: window (2 radius + 1)^2 */
@@ -857,6 +859,87 @@ void agh_default_depth_filter_params(agh_depth_filter_params* p);  /* radius 1; 
 int agh_set_depth_filter(agh_ctx* ctx, const agh_depth_filter_params* fp);
 int agh_get_depth_filter(agh_ctx* ctx, agh_depth_filter_params* out);
 int agh_get_depth_filter_counts(agh_ctx* ctx, agh_depth_filter_counts* out, int32_t cap_views);
+
+/* DEPTH FUSION: a burst of depth frames of ONE fixed camera, fused on the device into one depth image ahead of everything above.
+ * Between two picks the scene is static and the driver delivers 5 to 15 frames; a single frame of a structured-light or stereo
+ * sensor has 10 to 40 % invalid pixels, different ones in every frame, and millimetres of noise on the valid ones.  The sweep
+ * treats every hole as free space and the noise roughens the surfaces the normals are fitted on.  agh_fuse_depth turns the burst
+ * into one image in a buffer of the context and hands back an agh_depth_image whose `data` is that DEVICE pointer: the record
+ * goes into every agh_*depth*_device call of the same context (single, batch, masked, labelled, clustered, fitted), so the depth
+ * filter and the hand filter's observed-space test see the fused image.  No new chain variant, and no kernel of the chain changes.
+ * One kernel, k_depth_fuse, reads the n_frames x W x H readings once and writes W x H.
+ * agh_fuse_depth takes n_frames (1 .. 16) records of one camera: all of the same width, height and format; the row strides may
+ * differ per frame; depth_scale, fx, fy, cx, cy and the twelve pose entries must be BIT-EQUAL in all frames (a difference is an
+ * error: mixing cameras must not pass silently).  The host rounds once to float32: sa = (float) max_spread_abs,
+ * sr = (float) max_spread_rel.  Every pixel is treated independently of every other pixel; frames are taken in ascending
+ * frame index.
+ *  1. READING AND VALIDITY are k_deproject's.  U16: valid iff raw != 0, and z = (float) raw * depth_scale.  F32: valid iff
+ *     0 < z < +inf; NaN, negative values, both zeros and +inf are invalid.  m is the number of frames in which the pixel is valid.
+ *  2. MEDIAN.  The valid readings sorted ascending (U16: the raw integers; F32: the floats); med is the LOWER median, element
+ *     (m - 1) / 2 in integer division.  With two equally large clusters the nearer surface wins.
+ *  3. CONSENSUS.  zm is the depth of med; tol = sa + (sr * zm), float32, left to right, never contracted.  A valid reading is in
+ *     the consensus iff fabsf(z - zm) <= tol; the comparison is closed.  k is the number of consensus members.  The median is
+ *     always a member: with sa = sr = 0 the consensus is the set of readings equal to the median, and the result is the median.
+ *  4. DECISION, in this order.  m == 0: EMPTY.  m < min_valid: UNSUPPORTED.  k < min_valid: INCONSISTENT -- a pixel that keeps
+ *     changing sides, where writing either side would be a guess.  Otherwise FUSED.  Every pixel that is not FUSED writes the
+ *     format's invalid value: U16 writes 0, F32 writes a quiet NaN.
+ *  5. VALUE of a FUSED pixel.  U16: (sum + k / 2) / k in unsigned integer arithmetic, sum the sum of the members' raw values (at
+ *     most 16 x 65535).  F32: s is the first member, then s = s + z for every further member in frame order; the value is
+ *     s / (float) k with a correctly rounded float32 division.  An overflowing sum writes +inf: an invalid pixel by rule 1 that
+ *     still counts as FUSED.
+ *  6. OUTPUT.  The slot's device buffer receives a W x H image of the frames' format with tight rows.  fused_out receives that
+ *     pointer and row_stride_bytes = width x element size, and width, height, format, depth_scale, intrinsics and pose of frame
+ *     0.  The record is a legal image for every agh_*depth*_device call of the same context, and stays valid until that slot is
+ *     fused again or the context is destroyed.
+ *  7. COUNTS per slot: n_pixels = n_empty + n_unsupported + n_inconsistent + n_fused; n_filled counts the FUSED pixels whose
+ *     reading in the LAST frame was invalid -- the holes of the newest frame that the burst closed.
+ * SLOTS run 0 .. 127: two images per capture for a full 64-capture depth batch.  A slot's buffer is made on first use and
+ * regrown when an image is larger.
+ * ORDERING.  The fuse is queued on the context's stream and returns without waiting for the kernel.  A chain called next on the
+ * same context is behind it on that stream: agh_fuse_depth followed by agh_localize_depth_device needs no synchronisation in
+ * between, and the chain's one synchronisation stays one.  agh_fuse_depth (host frames, packed into a staging buffer of the
+ * context that the kernel reads) returns when the caller's frames have been READ, pageable or page-locked, as agh_set_cloud
+ * does.  agh_fuse_depth_device: the frames' data are device pointers, aligned to the element size, read in place with their
+ * strides; they must stay valid until the next synchronisation of the context.  The counts go to pinned memory;
+ * agh_get_depth_fusion_counts (1, or 0 if the slot was never fused) and agh_get_fused_depth wait on an event recorded behind
+ * that slot's kernel, a wait that is free once any later synchronisation has passed.  agh_get_fused_depth copies the slot's
+ * image, rows tight, into pixels_out and its record (data: the device pointer) into record_out, which may be NULL; it returns
+ * the bytes written, 0 if the slot was never fused, AGH_ERR_CAPACITY if cap_bytes is smaller than the image (record_out is filled
+ * then too: width x height x element size says what is needed).
+ * ERRORS, each AGH_ERR_INVALID_ARGUMENT, the text naming the frame and the field, nothing launched and the slot's previous image
+ * untouched: NULL frames, params or fused_out; n_frames outside 1 .. 16; slot outside 0 .. 127; min_valid outside
+ * 1 .. n_frames (the default of 2 with ONE frame is therefore refused: a single frame is passed with min_valid = 1); a spread
+ * that is non-finite or negative; a non-zero reserved; per frame every rule agh_localize_depth applies to an image ("frame 3:
+ * fx must be finite and not zero"); a frame that differs from frame 0 in a field that must be equal ("frame 2: cx differs from
+ * frame 0").
+ * MID-CHAIN (single or batch) agh_fuse_depth, agh_fuse_depth_device, agh_get_depth_fusion_counts and agh_get_fused_depth return
+ * AGH_ERR_STATE without touching anything.
+ * Not built: fusing the next burst under a chain in flight; a ring of frames kept by the context between calls (the device form
+ * lets the caller own the ring); motion compensation; spatial hole filling; confidence outputs.
+ * The contract is a numpy model the kernel matches bit for bit: tests/depth_fusion_cases.py. */
+typedef struct agh_depth_fusion_params
+{
+  int32_t min_valid;       /* 1 .. n_frames */
+  int32_t reserved;        /* 0 */
+  double max_spread_abs;   /* metres, finite, >= 0 */
+  double max_spread_rel;   /* per metre of depth, finite, >= 0 */
+} agh_depth_fusion_params;
+typedef struct agh_depth_fusion_counts
+{
+  int64_t n_pixels;        /* W x H */
+  int64_t n_empty;         /* no frame valid */
+  int64_t n_unsupported;   /* fewer than min_valid frames valid */
+  int64_t n_inconsistent;  /* fewer than min_valid readings in the consensus */
+  int64_t n_fused;
+  int64_t n_filled;        /* fused, and invalid in the last frame */
+} agh_depth_fusion_counts;
+void agh_default_depth_fusion_params(agh_depth_fusion_params* p);  /* min_valid 2; 0.005 m; 0.005 per metre */
+int agh_fuse_depth(agh_ctx* ctx, const agh_depth_image* frames, int32_t n_frames, const agh_depth_fusion_params* fp, int32_t slot,
+  agh_depth_image* fused_out);
+int agh_fuse_depth_device(agh_ctx* ctx, const agh_depth_image* frames, int32_t n_frames, const agh_depth_fusion_params* fp,
+  int32_t slot, agh_depth_image* fused_out);
+int agh_get_depth_fusion_counts(agh_ctx* ctx, int32_t slot, agh_depth_fusion_counts* out);
+int agh_get_fused_depth(agh_ctx* ctx, int32_t slot, void* pixels_out, int64_t cap_bytes, agh_depth_image* record_out);
 
 /* A VOXEL FILTER for every call that voxelises: the depth filter above only helps callers who hand over depth images.  A cloud
  * from a stereo matcher, a lidar, a fused map or a driver that already deprojected carries stray returns in free space; each

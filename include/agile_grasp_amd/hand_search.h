@@ -1424,6 +1424,78 @@ public:
     return out;
   }
 
+  /** Additional: a burst of depth frames of ONE fixed camera fused on the device (agh_fuse_depth, include/agh.h "DEPTH FUSION"):
+   *  1 to 16 frames, equal in everything but the pixels and the row stride, into slot `slot` (0 .. 127) of this search's
+   *  context.  A frame without a pose takes the transform of camera `camera` (0: left, 1: right).  The call is queued, not
+   *  waited for; *fused_out receives the fused image's record, whose data is a DEVICE pointer (the C ABI's _device calls take
+   *  it).  This adapter's depth chains take host images: fusedDepth brings the image back for them.  Refused while a chain is
+   *  pending; the slots do not survive a context this search re-creates (a changed hand geometry or device).
+   *  @return false (after printing) on error; the slot's previous image is untouched */
+  bool fuseDepth(const std::vector<DepthImage>& frames, const agh_depth_fusion_params& fp, int slot = 0, int camera = 0,
+    agh_depth_image* fused_out = nullptr)
+  {
+    if (!ensureContext())
+      return false;
+    std::vector<DepthImage> burst(frames);
+    for (std::size_t t = 0; t < burst.size(); t++)
+      if (!burst[t].has_pose)
+      {
+        burst[t].pose = camera == 0 ? cam_tf_left_ : cam_tf_right_;
+        burst[t].has_pose = true;
+      }
+    const std::vector<agh_depth_image> recs = depthRecords(burst);
+    agh_depth_image fused;
+    if (agh_fuse_depth(ctx_, recs.empty() ? nullptr : recs.data(), (std::int32_t) recs.size(), &fp, (std::int32_t) slot, &fused) != AGH_OK)
+    {
+      fail("agh_fuse_depth");
+      return false;
+    }
+    if (fused_out)
+      *fused_out = fused;
+    return true;
+  }
+  /** agh_get_depth_fusion_counts: what the slot's last fuse did; false if the slot was never fused, or while a chain is pending */
+  bool depthFusionCounts(int slot, agh_depth_fusion_counts& out)
+  {
+    return ctx_ && agh_get_depth_fusion_counts(ctx_, (std::int32_t) slot, &out) == 1;
+  }
+  /** agh_get_fused_depth: the slot's fused image into `pixels` (rows tight), and `image` describing it over those bytes with its
+   *  own pose -- what localizeDepth* and Localization::localizeHandlesDepth take.  Keep `pixels` alive and unchanged as long as
+   *  `image` is used.  false if the slot was never fused, or while a chain is pending */
+  bool fusedDepth(int slot, std::vector<std::uint8_t>& pixels, DepthImage& image)
+  {
+    agh_depth_fusion_counts counts;
+    if (!depthFusionCounts(slot, counts))
+      return false;
+    pixels.resize((std::size_t) counts.n_pixels * 4);  // (enough for either format)
+    agh_depth_image rec;
+    const int got = agh_get_fused_depth(ctx_, (std::int32_t) slot, pixels.data(), (std::int64_t) pixels.size(), &rec);
+    if (got <= 0)
+    {
+      if (got < 0)
+        fail("agh_get_fused_depth");
+      return false;
+    }
+    pixels.resize((std::size_t) got);
+    image = DepthImage();
+    image.data = pixels.data();
+    image.width = rec.width;
+    image.height = rec.height;
+    image.row_stride_bytes = rec.row_stride_bytes;
+    image.is_float = rec.format == AGH_DEPTH_F32;
+    image.depth_scale = rec.depth_scale;
+    image.fx = rec.fx;
+    image.fy = rec.fy;
+    image.cx = rec.cx;
+    image.cy = rec.cy;
+    image.has_pose = true;
+    image.pose = cam_tf_left_;  // (the last row of a transform; the three above it are the record's)
+    for (int row = 0; row < 3; row++)
+      for (int col = 0; col < 4; col++)
+        image.pose(row, col) = rec.pose[4 * row + col];
+    return true;
+  }
+
   /** agh_localize_stage: the NEXT capture up, beside the chain in flight (keep `next` alive and unchanged until the
    *  localizeEnd of the chain that searches it has returned). */
   bool localizeStage(const PointCloud::Ptr& next)

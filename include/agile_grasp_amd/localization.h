@@ -757,6 +757,31 @@ public:
     return search_ ? search_->depthFilterCounts() : std::vector<agh_depth_filter_counts>();
   }
 
+  /** Additional: a burst of depth frames of ONE fixed camera fused on the device ahead of the depth calls (agh_fuse_depth;
+   *  agh_default_depth_fusion_params fills a record: 2 valid frames, 5 mm + 0.5 % of the depth): the lower median of a pixel's
+   *  valid readings, the mean of the readings within the spread of it, and an invalid pixel where too few frames agree.  1 to 16
+   *  frames into slot `slot` (0 .. 127); a frame without a pose takes camera `camera`'s transform of setCameraTransforms.
+   *  fusedDepth then hands the image back for localizeHandlesDepth.  Refused while a chain is pending.
+   *  @return false (after printing) on error; the slot's previous image is untouched */
+  bool fuseDepth(const std::vector<DepthImage>& frames, const agh_depth_fusion_params& fp, int slot = 0, int camera = 0,
+    agh_depth_image* fused_out = nullptr)
+  {
+    if (chainPending("fuseDepth"))
+      return false;
+    ensureSearch();
+    return search_->fuseDepth(frames, fp, slot, camera, fused_out);
+  }
+  /** What the slot's last fuse did (agh_get_depth_fusion_counts); false if the slot was never fused or while a chain is pending */
+  bool depthFusionCounts(int slot, agh_depth_fusion_counts& out)
+  {
+    return search_ && search_->depthFusionCounts(slot, out);
+  }
+  /** The slot's fused image in `pixels`, described by `image` (agh_get_fused_depth); keep `pixels` alive while `image` is used */
+  bool fusedDepth(int slot, std::vector<std::uint8_t>& pixels, DepthImage& image)
+  {
+    return search_ && search_->fusedDepth(slot, pixels, image);
+  }
+
   /** The plane the last fitted call used (agh_get_plane_fit): (a, b, c, d), the normal towards camera 0; zeros, and *found false,
    *  if it found none, if the last chain collected was not a fitted one, or while a chain is pending. */
   VectorXd fittedPlane(bool* found = nullptr)
