@@ -121,6 +121,8 @@ EXPORTS = [
     "agh_default_voxel_filter_params", "agh_set_voxel_filter", "agh_get_voxel_filter", "agh_get_voxel_filter_counts",
     "agh_default_hand_filter_params", "agh_set_hand_filter", "agh_get_hand_filter", "agh_get_hand_filter_counts",
     "agh_default_hand_clearance_params", "agh_set_hand_clearance", "agh_get_hand_clearance", "agh_get_hand_clearance_counts",
+    "agh_default_handle_ranking_params", "agh_set_handle_ranking", "agh_get_handle_ranking", "agh_get_handle_scores",
+    "agh_get_handle_ranking_counts", "agh_get_hand_margins", "agh_rank_handles",
 ]
 
 
@@ -295,6 +297,38 @@ class AghHandClearanceParams(C.Structure):
 
 class AghHandClearanceCounts(C.Structure):
     _fields_ = [("n_tested", C.c_int64), ("n_dropped", C.c_int64), ("n_kept", C.c_int64)]
+
+
+class AghHandleRankingParams(C.Structure):
+    _fields_ = [("w_support", C.c_double), ("w_margin", C.c_double), ("w_approach", C.c_double), ("w_position", C.c_double),
+                ("w_distance", C.c_double), ("w_width", C.c_double), ("w_length", C.c_double), ("approach_dir", C.c_double * 3),
+                ("position_dir", C.c_double * 3), ("ref_point", C.c_double * 3), ("preferred_width", C.c_double),
+                ("min_score", C.c_double), ("support_cap", C.c_int32), ("max_handles", C.c_int32)]
+
+
+class AghHandleScore(C.Structure):
+    _fields_ = [("score", C.c_double), ("terms", C.c_double * 7), ("index", C.c_int32), ("best_inlier", C.c_int32)]
+
+
+class AghHandleRankingCounts(C.Structure):
+    _fields_ = [("n_found", C.c_int64), ("n_below", C.c_int64), ("n_returned", C.c_int64)]
+
+
+SCORE_DTYPE = np.dtype([("score", "<f8"), ("terms", "<f8", 7), ("index", "<i4"), ("best_inlier", "<i4")])
+assert SCORE_DTYPE.itemsize == 72 == C.sizeof(AghHandleScore)
+
+
+def handle_ranking_params(**fields) -> AghHandleRankingParams:
+    """agh_default_handle_ranking_params, then the given fields (the three vectors: any sequence of three floats)."""
+    rp = AghHandleRankingParams()
+    load_library().agh_default_handle_ranking_params(C.byref(rp))
+    for k, v in fields.items():
+        if not hasattr(rp, k):
+            raise TypeError(f"agh_handle_ranking_params has no field {k}")
+        if k in ("approach_dir", "position_dir", "ref_point"):
+            v = (C.c_double * 3)(*[float(x) for x in v])
+        setattr(rp, k, v)
+    return rp
 
 
 def hand_clearance_params(**fields) -> AghHandClearanceParams:
@@ -565,6 +599,7 @@ def load_library():
         lib.agh_default_voxel_filter_params.restype = None
         lib.agh_default_hand_filter_params.restype = None
         lib.agh_default_hand_clearance_params.restype = None
+        lib.agh_default_handle_ranking_params.restype = None
         _LIB = lib
     return _LIB
 
@@ -805,6 +840,69 @@ class Context:
         recs = (AghHandClearanceCounts * 64)()
         k = self._check(self.lib.agh_get_hand_clearance_counts(self._h, recs, C.c_int32(64)))
         return np.array([[r.n_tested, r.n_dropped, r.n_kept] for r in recs[:k]], np.int64).reshape(k, 3)
+
+    def set_handle_ranking(self, rp=None, **fields):
+        """agh_set_handle_ranking: every later localize* chain of this context returns each list's handles in rank order -- score
+        descending, NaN last, ties by the position in the unranked list, the handles below min_score left out, at most max_handles
+        of them.  `rp`: a handle_ranking_params() record, or None for the defaults (support and margin, weight 1 each); the keyword
+        fields are set on top.  Sticky until clear_handle_ranking()."""
+        rec = handle_ranking_params(**fields)
+        if rp is not None:
+            given = rec
+            rec = AghHandleRankingParams()
+            C.memmove(C.byref(rec), C.byref(rp), C.sizeof(AghHandleRankingParams))
+            for k in fields:
+                setattr(rec, k, getattr(given, k))
+        self._check(self.lib.agh_set_handle_ranking(self._h, C.byref(rec)))
+
+    def clear_handle_ranking(self):
+        self._check(self.lib.agh_set_handle_ranking(self._h, None))
+
+    def get_handle_ranking(self):
+        """The agh_handle_ranking_params record held, or None."""
+        rec = AghHandleRankingParams()
+        return rec if self._check(self.lib.agh_get_handle_ranking(self._h, C.byref(rec))) == 1 else None
+
+    def handle_scores(self, cap: int = 8192 * 64) -> np.ndarray:
+        """agh_get_handle_scores: the score records of the last chain's handles (SCORE_DTYPE), laid out as its handles_out."""
+        out = np.zeros(max(cap, 1), SCORE_DTYPE)
+        n = self._check(self.lib.agh_get_handle_scores(self._h, out.ctypes.data_as(C.c_void_p), C.c_int64(cap)))
+        return out[:n].copy()
+
+    def handle_ranking_counts(self) -> np.ndarray:
+        """agh_get_handle_ranking_counts: an (n_lists, 3) int64 array, a row per list of the last chain -- n_found, n_below,
+        n_returned."""
+        recs = (AghHandleRankingCounts * 64)()
+        k = self._check(self.lib.agh_get_handle_ranking_counts(self._h, recs, C.c_int32(64)))
+        return np.array([[r.n_found, r.n_below, r.n_returned] for r in recs[:k]], np.int64).reshape(k, 3)
+
+    def hand_margins(self, cap: int = 8192 * 64) -> np.ndarray:
+        """agh_get_hand_margins: minus the classifier's decision sum of every hand of the last chain, laid out as its hands_out."""
+        out = np.zeros(max(cap, 1), np.float64)
+        n = self._check(self.lib.agh_get_hand_margins(self._h, _p(out, C.c_double), C.c_int64(cap)))
+        return out[:n].copy()
+
+    def rank_handles(self, rp, hands, margins, handles, inlier_idx, cap=None):
+        """agh_rank_handles: the ranking `rp` (a handle_ranking_params() record) on one list in host buffers, by the chains' kernel.
+        Returns (handles in rank order, their SCORE_DTYPE records, [n_found, n_below, n_returned])."""
+        hands = np.ascontiguousarray(hands, HYP_DTYPE)
+        handles = np.ascontiguousarray(handles, HANDLE_DTYPE)
+        idx = np.ascontiguousarray(inlier_idx, np.int32)
+        if margins is not None:
+            margins = np.ascontiguousarray(margins, np.float64)
+            assert margins.shape[0] == hands.shape[0]
+        cap = handles.shape[0] if cap is None else cap
+        out, sc = np.zeros(max(cap, 1), HANDLE_DTYPE), np.zeros(max(cap, 1), SCORE_DTYPE)
+        counts = AghHandleRankingCounts()
+        rc = self.lib.agh_rank_handles(self._h, C.byref(rp) if rp is not None else None, hands.ctypes.data_as(C.c_void_p),
+                                       C.c_int64(hands.shape[0]), _p(margins, C.c_double) if margins is not None else None,
+                                       handles.ctypes.data_as(C.c_void_p), C.c_int64(handles.shape[0]), _p(idx, C.c_int32),
+                                       C.c_int64(idx.shape[0]), out.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
+                                       C.c_int64(cap), C.byref(counts))
+        self.last_rank_counts = [counts.n_found, counts.n_below, counts.n_returned]
+        self._check(rc)
+        n = counts.n_returned
+        return out[:n].copy(), sc[:n].copy(), list(self.last_rank_counts)
 
     def set_cloud_batch_torch(self, xyz_t, cam_t, offsets, stream=None):
         assert xyz_t.is_cuda and xyz_t.is_contiguous()

@@ -282,6 +282,29 @@ struct HandDropState
   int lists = 0;
   int64_t hyp[kMaxClouds] = {};
 };
+// agh_set_handle_ranking (handle_rank.hip): the sticky setting, host-side; the buffers of k_handle_rank, made by the first chain
+// with a ranking set -- the kept hands' margins (device and pinned), the score records in list order (device) and in rank order
+// (pinned), a list's three counts (pinned) -- and what the last chain collected left for the getters
+struct HandleRankState
+{
+  bool set = false;
+  agh_handle_ranking_params p = {};
+  double* d_margin = nullptr;
+  double* h_margin = nullptr;          // pinned
+  agh_handle_score* d_scores = nullptr;
+  agh_handle_score* h_scores = nullptr;  // pinned
+  int* h_counts = nullptr;             // pinned: kMaxClouds x 4 (found, below, returned)
+  int64_t dev_cap = 0, host_cap = 0;   // elements
+  // the chain in flight: queued with a ranking, its lists' strides in the buffers above, and whether it has margins
+  bool queued = false, with_margins = false;
+  int64_t slot = 0, host_slot = 0;
+  // the last chain collected
+  bool ran = false;
+  int lists = 0;
+  std::vector<agh_handle_score> scores;
+  std::vector<double> margins;
+  agh_handle_ranking_counts counts[kMaxClouds] = {};
+};
 // agh_fuse_depth (depth_fuse.hip): a slot holds one fused image in a device buffer of its own, regrown when an image is larger, the
 // record handed out for it, and the event behind its last kernel and the copy of its counters
 constexpr int kFuseSlots = 128, kFuseMaxFrames = 16;
@@ -629,6 +652,7 @@ struct Ctx
   int filter_views = 0;
   hipStream_t filter_stream = nullptr;
   HandDropState hand_drop;         // the hand drop stage (hand_drop.hip): agh_set_hand_filter, agh_set_hand_clearance
+  HandleRankState handle_rank;     // agh_set_handle_ranking (handle_rank.hip)
   DepthFuseState* fuse = nullptr;  // agh_fuse_depth's slots, staging buffer and counters (depth_fuse.hip), made by its first call
   PlaneState* plane = nullptr;     // agh_remove_plane's buffers and last result (plane.hip), made by its first call
   LocalizeBatchState* lbatch = nullptr;  // agh_localize_batch's buffers (localize_batch.hip), made by its first call
@@ -1175,6 +1199,48 @@ struct HandleBufs
 // k x hm.handle_cap (hm.idx_cap must equal it), its counts at k x host_counts_stride ints.
 int handle_search_batch(const HandleBufs& b, int n_lists, int64_t slot, int64_t H, double x1, double x2, int min_inliers,
   double min_length, hipStream_t st, const HandleMirror& hm, int host_counts_stride, bool with_sequential, const int* d_H);
+// agh_localize_batch: the hand lists of several captures side by side, one per blockIdx.y, each in a slice of every buffer at these
+// element strides (all 0 and a grid of one row: the single list of agh_find_handles / agh_localize).  counts and d_H are arrays
+// with one entry per capture.  (handles.hip's kernels and handle_rank.hip's)
+struct HandleSlots
+{
+  int64_t hands;     // hands, rowcnt, h_first, h_n, inlier_idx, tmp, the device-side handles
+  int64_t bits;      // the pair matrix
+  int64_t host;      // host_idx and the host-side handles
+  int host_counts;   // host_counts
+};
+#define AGH_HANDLE_SLICE(p, stride)      \
+  do                                     \
+  {                                      \
+    if (p)                               \
+      p += (int64_t) blockIdx.y * (stride); \
+  } while (0)
+struct HandleCounts
+{
+  int n_handles, n_idx, error;
+  int sequential;  // set by k_handle_batch when it declines (a row longer than kMaxRow, two waves' worth): k_handle_greedy runs
+};
+// ---- agh_set_handle_ranking (handle_rank.hip; DESIGN.md, "Handle ranking") ----
+// What a chain's compaction writes beside the kept hands when a ranking is set: for output position k the margin -sums[src[k]]
+// (0.0 without a classifier: sums null), to a device array and to its pinned mirror.  out null: nothing (every chain without one).
+struct MarginOut
+{
+  const double* sums;
+  double* out;
+  double* host;
+  int64_t stride, host_stride;  // a batch's lists: list l at l x stride (the handle search's slots)
+};
+// the chain's lists for k_handle_rank, queued behind k_handle_build on st: no-op unless handle_rank_prepare saw a ranking set
+int handle_rank_stage(Ctx* c, const HandleBufs& b, int n_lists, int64_t slot, const HandleMirror& hm, int host_counts_stride,
+  hipStream_t st);
+// the buffers for n_lists lists of at most `slot` hands (host mirror: host_slot), made or regrown if a ranking is set; *m = what the
+// compaction writes (out null if none is set).  Called where a chain queues its compaction.
+int handle_rank_prepare(Ctx* c, int n_lists, int64_t slot, int64_t host_slot, bool classify, MarginOut* m);
+// a chain's end: lists = 0 forgets the last chain's; else list l's n_kept[l] hands, for the three getters
+void handle_rank_collect(Ctx* c, int lists, const int64_t* n_kept);
+// the rule a set ranking adds to a chain's arguments: w_margin != 0 needs the classifier
+int handle_rank_check(Ctx* c, const char* who, bool classify);
+void handle_rank_release(Ctx* c);
 int grid_build(Ctx* c, hipStream_t st);
 int taubin_frames(Ctx* c, const int32_t* d_samples, int64_t S, double radius, agh_frame* d_frames, int32_t* d_nt,
   bool write_normals, hipStream_t st);
@@ -1279,11 +1345,13 @@ __device__ __forceinline__ bool near_workspace_boundary(const double* surface, c
 // compaction is a scan: a ballot, sixteen wave sums, a carry), each as one 160-byte run, ten threads of sixteen bytes, to out and,
 // below host_cap, to host_out (pinned; null: none), `sample` less sample_base.  dev_cap bounds what is written, not what is
 // counted; the count is returned.  LDS of the caller: src[kCompactList] (position in the output -> position in the input),
-// wsum[16], carry.
+// wsum[16], carry.  marg (agh_set_handle_ranking; null: none): for output position k the value -sums[src[k]], to marg and, below
+// host_cap, to marg_host.
 constexpr int kCompactList = 8192;  // (the handle search takes no more)
 __device__ __forceinline__ int compact_kept_records(const agh_hypothesis* __restrict__ in, int64_t r0, int64_t r1, int use_keep,
   int filters, const double* ws, int* src, int* wsum, int* carry, agh_hypothesis* __restrict__ out, int dev_cap,
-  agh_hypothesis* __restrict__ host_out, int host_cap, int sample_base, const uint8_t* __restrict__ drop)
+  agh_hypothesis* __restrict__ host_out, int host_cap, int sample_base, const uint8_t* __restrict__ drop,
+  const double* __restrict__ sums = nullptr, double* __restrict__ marg = nullptr, double* __restrict__ marg_host = nullptr)
 {
   static_assert(sizeof(agh_hypothesis) == 160 && offsetof(agh_hypothesis, sample) == 8 * 16,
     "ten 16-byte parts; sample is the first word of the ninth");
@@ -1324,6 +1392,15 @@ __device__ __forceinline__ int compact_kept_records(const agh_hypothesis* __rest
     if (host_out && k < host_cap)
       reinterpret_cast<uint4*>(host_out + k)[part] = v;
   }
+  // agh_set_handle_ranking: the kept hands' margins, minus the classifier's decision sums (0.0 without a classifier)
+  if (marg)
+    for (int k = tid; k < kw; k += 1024)
+    {
+      const double g = sums ? -sums[src[k]] : 0.0;
+      marg[k] = g;
+      if (marg_host && k < host_cap)
+        marg_host[k] = g;
+    }
   return K;
 }
 

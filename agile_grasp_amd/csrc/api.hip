@@ -509,6 +509,7 @@ void agh_destroy(agh_ctx* ctx)
   plane_release(c);
   localize_batch_release(c);
   hand_drop_release(c);
+  handle_rank_release(c);
   depth_fuse_release(c);
   void* ptrs[] = { c->own_xyz, c->own_cam, c->d_desc, c->d_bbox_part, c->d_cell_start, c->d_cell_count, c->d_block_sums, c->d_cell_of,
     c->d_rank_of, c->d_sorted, c->d_samples, c->d_sums, c->d_nt, c->d_nh, c->d_status, c->d_nbr, c->d_eig, c->d_frames, c->d_slots,

@@ -27,23 +27,6 @@ constexpr int kHandleMaxHands = 8192;
 
 __device__ __forceinline__ double dot3d(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
-// agh_localize_batch: the hand lists of several captures side by side, one per blockIdx.y, each in a slice of every buffer at these
-// element strides (all 0 and a grid of one row: the single list of agh_find_handles / agh_localize).  counts and d_H are arrays
-// with one entry per capture.
-struct HandleSlots
-{
-  int64_t hands;     // hands, rowcnt, h_first, h_n, inlier_idx, tmp, the device-side handles
-  int64_t bits;      // the pair matrix
-  int64_t host;      // host_idx and the host-side handles
-  int host_counts;   // host_counts
-};
-#define AGH_HANDLE_SLICE(p, stride)      \
-  do                                     \
-  {                                      \
-    if (p)                               \
-      p += (int64_t) blockIdx.y * (stride); \
-  } while (0)
-
 // d_H (all kernels of this file): the number of hands in device memory, when the host does not know it (agh_localize: the
 // hands are what the SVM kept of a search still in flight); the launch is then sized for a bound and H, W are read here.
 __global__ __launch_bounds__(256) void k_handle_pairs(const agh_hypothesis* __restrict__ hands, int H, double x1, double x2,
@@ -99,12 +82,6 @@ __global__ __launch_bounds__(256) void k_handle_pairs(const agh_hypothesis* __re
   if (tid == 0)
     rowcnt[i] = sc[0] + sc[1] + sc[2] + sc[3];
 }
-
-struct HandleCounts
-{
-  int n_handles, n_idx, error;
-  int sequential;  // set by k_handle_batch when it declines (a row longer than kMaxRow, two waves' worth): k_handle_greedy runs
-};
 
 constexpr int kHandleLdsHands = 640;  // hands whose axis, bottom and pair-matrix rows fit the LDS of the small variant
 constexpr int kHandleLdsWords = kHandleLdsHands / 64;
@@ -1076,3 +1053,7 @@ int handle_search_batch(const HandleBufs& b, int n_lists, int64_t slot, int64_t 
 }
 
 }  // namespace agh
+
+// ---- the ranking of a list's handles behind k_handle_build (agh_set_handle_ranking, agh_rank_handles): a file of its own, compiled
+// here ----
+#include "handle_rank.hip"

@@ -41,13 +41,14 @@ extern "C" __global__ void k_draw_samples(const int* __restrict__ cloud_off, int
 extern "C" __global__ __launch_bounds__(1024) void k_compact_kept(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
   int64_t cap_in, int use_keep, BoundaryBox box, agh_hypothesis* __restrict__ out, int out_cap, int* __restrict__ n_out,
   agh_hypothesis* __restrict__ host_out, int host_cap, int* __restrict__ host_counts, const int32_t* __restrict__ flags,
-  const uint8_t* __restrict__ drop, const unsigned* __restrict__ hf_counts, int* __restrict__ hf_host)
+  const uint8_t* __restrict__ drop, const unsigned* __restrict__ hf_counts, int* __restrict__ hf_host, MarginOut mg)
 {
   __shared__ int src[kCompactList];
   __shared__ int wsum[16];
   __shared__ int carry;
   const int64_t n = min(*n_in, cap_in);
-  const int K = compact_kept_records(in, 0, n, use_keep, box.on, box.ws, src, wsum, &carry, out, out_cap, host_out, host_cap, 0, drop);
+  const int K = compact_kept_records(in, 0, n, use_keep, box.on, box.ws, src, wsum, &carry, out, out_cap, host_out, host_cap, 0, drop,
+    mg.sums, mg.out, mg.host);
   if (drop && threadIdx.x < kHandDropCounters)
     hf_host[threadIdx.x] = (int) hf_counts[threadIdx.x];
   if (threadIdx.x == 0)
@@ -226,9 +227,13 @@ static int localize_queue(agh_ctx* ctx, bool handles_only)
       return hd.rc;
     if (L.classify && (rc = hog_svm(c, hyp_bound, c->d_keep, st, ws, hd.drop)) != AGH_OK)
       return rc;
+    // (agh_set_handle_ranking: the kept hands' margins leave with them; nothing without one)
+    MarginOut mg;
+    if ((rc = handle_rank_prepare(c, 1, hand_bound, hand_bound, L.classify, &mg)) != AGH_OK)
+      return rc;
     hipLaunchKernelGGL(k_compact_kept, dim3(1), dim3(1024), 0, st, (const agh_hypothesis*) c->d_out_own, (const int64_t*) c->d_nout,
       c->s_cap * 8, L.classify ? 1 : 0, boundary_box(L.classify ? nullptr : ws), c->d_h_hands, (int) hand_bound, d_hcount, pin.hands,
-      (int) c->h_pin_handles_cap, pin.counts, (const int32_t*) c->d_flags, hd.drop, hd.d_counts, hd.h_counts);
+      (int) c->h_pin_handles_cap, pin.counts, (const int32_t*) c->d_flags, hd.drop, hd.d_counts, hd.h_counts, mg);
     if (hipGetLastError() != hipSuccess)
     {
       c->err = "k_compact_kept launch failed";
@@ -239,8 +244,13 @@ static int localize_queue(agh_ctx* ctx, bool handles_only)
   rc = handle_search(c, hand_bound, L.x1, L.x2, L.min_inliers, L.min_length, st, hm, L.with_sequential, d_hcount);
   timing_mark(c, "handle_search", st);
   if (rc != AGH_OK)
+  {
     c->err = "handle search launch failed";
-  return rc;
+    return rc;
+  }
+  const HandleBufs hb{ c->d_h_hands, c->d_h_bits, c->d_h_rowcnt, c->d_h_first, c->d_h_n, c->d_h_idx, c->d_h_counts, c->d_h_tmp,
+    c->d_h_handles };
+  return handle_rank_stage(c, hb, 1, 0, hm, 0, st);
 }
 
 std::string agh::cluster_params_fault(const agh_cluster_params& cp)
@@ -476,6 +486,8 @@ static int localize_begin_impl(agh_ctx* ctx, const float* xyz, bool xyz_on_devic
   if (!L.repeated)
     if (int rc = hand_filter_check(c, who, depth ? depth->images : nullptr, depth ? depth->n_images : nullptr, depth ? 1 : 0, depth != nullptr))
       return rc;
+  if (int rc = handle_rank_check(c, who, lp->classify != 0))
+    return rc;
   AGH_HIPCHK(c, hipSetDevice(c->device));
   const int64_t S = lp->n_samples;
   const int K = src && src->per_object() ? src->objects(0) : 0;  // (a chain with a list per object: K lists of S samples)
@@ -625,6 +637,7 @@ static int localize_end_impl(agh_ctx* ctx, const ChainOutputs& out, agh_localize
   L.active = false;
   c->results = ChainResults{};
   hand_drop_collect(c, 0, nullptr);
+  handle_rank_collect(c, 0, nullptr);
   const int64_t S = L.S;
   const HandlePins pin = handle_pins(c);
   const int* h_counts = pin.counts;
@@ -714,6 +727,7 @@ static int localize_end_impl(agh_ctx* ctx, const ChainOutputs& out, agh_localize
     return rc;
   const int64_t n_hyp = h_counts[4], n_kept = h_counts[5];
   hand_drop_collect(c, 1, &n_hyp);  // (the counters are in pinned memory if the chain ran a test)
+  handle_rank_collect(c, 1, &n_kept);
   c->last_nout = std::min<int64_t>(n_hyp, c->s_cap * 8);
   if (result)
     *result = agh_localize_result{ L.nv, n_hyp, n_kept, h_counts[0], h_counts[1] };

@@ -168,7 +168,8 @@ __global__ void k_batch_samples(const BatchCapture* __restrict__ tab, int C, int
 __global__ __launch_bounds__(1024) void k_compact_kept_batch(const agh_hypothesis* __restrict__ in, const int64_t* __restrict__ n_in,
   int64_t cap_in, int use_keep, int filters, const BatchCapture* __restrict__ tab, agh_hypothesis* __restrict__ out, int slot,
   int* __restrict__ n_out, agh_hypothesis* __restrict__ host_out, int host_slot, int* __restrict__ host_counts,
-  const int32_t* __restrict__ flags, const uint8_t* __restrict__ drop, const unsigned* __restrict__ hf_counts, int* __restrict__ hf_host)
+  const int32_t* __restrict__ flags, const uint8_t* __restrict__ drop, const unsigned* __restrict__ hf_counts, int* __restrict__ hf_host,
+  MarginOut mg)
 {
   __shared__ int src[kCompactList];
   __shared__ int wsum[16];
@@ -200,7 +201,8 @@ __global__ __launch_bounds__(1024) void k_compact_kept_batch(const agh_hypothesi
     ws[q] = tab[cap].ws[q];
   const int room = min(slot, host_slot);
   const int K = compact_kept_records(in, r0, r1, use_keep, filters, ws, src, wsum, &carry, out + (int64_t) cap * slot, room,
-    host_out + (int64_t) cap * host_slot, room, (int) s0, drop);
+    host_out + (int64_t) cap * host_slot, room, (int) s0, drop, mg.sums, mg.out ? mg.out + (int64_t) cap * mg.stride : nullptr,
+    mg.host ? mg.host + (int64_t) cap * mg.host_stride : nullptr);
   if (drop && tid < kHandDropCounters)  // (the hand drop stage: the list's counters to pinned memory with its counts)
     hf_host[cap * kHandDropCounters + tid] = (int) hf_counts[cap * kHandDropCounters + tid];
   if (tid == 0)
@@ -443,10 +445,14 @@ int batch_queue(agh_ctx* ctx, bool handles_only)
       return hd.rc;
     if (B.classify && (rc = hog_svm(c, hyp_bound, c->d_keep, st, nullptr, hd.drop)) != AGH_OK)
       return rc;
+    // (agh_set_handle_ranking: the kept hands' margins leave with them, list by list; nothing without one)
+    MarginOut mg;
+    if ((rc = handle_rank_prepare(c, C, b->slot, b->h_slot, B.classify, &mg)) != AGH_OK)
+      return rc;
     hipLaunchKernelGGL(k_compact_kept_batch, dim3(C), dim3(1024), 0, st, (const agh_hypothesis*) c->d_out_own,
       (const int64_t*) c->d_nout, c->s_cap * 8, B.classify ? 1 : 0, B.filters ? 1 : 0, (const BatchCapture*) b->d_tab, b->d.hands,
       (int) b->slot, b->d_count, b->h_hands, (int) b->h_slot, b->h_counts, (const int32_t*) c->d_flags, hd.drop,
-      hd.d_counts, hd.h_counts);
+      hd.d_counts, hd.h_counts, mg);
     if (hipGetLastError() != hipSuccess)
     {
       c->err = "k_compact_kept_batch launch failed";
@@ -459,8 +465,11 @@ int batch_queue(agh_ctx* ctx, bool handles_only)
     kBatchCountsStride, c->loc.with_sequential, b->d_count);
   timing_mark(c, "handle_search", st);
   if (rc != AGH_OK)
+  {
     c->err = "handle search launch failed";
-  return rc;
+    return rc;
+  }
+  return handle_rank_stage(c, b->d, C, b->slot, hm, kBatchCountsStride, st);
 }
 
 namespace
@@ -799,6 +808,8 @@ int batch_begin_impl(agh_ctx* ctx, const float* const* xyz, bool on_device, cons
   if (int rc = hand_filter_check(c, who.c_str(), depth ? depth->images : nullptr, depth ? depth->n_images : nullptr, depth ? C : 0,
         depth != nullptr))
     return rc;
+  if (int rc = handle_rank_check(c, who.c_str(), lp[0].classify != 0))
+    return rc;
   if (cam_table_mismatch(c, who.c_str(), C))  // (capture k = cloud k: row k of agh_set_cloud_cam_origins' table is its rig;
     return AGH_ERR_INVALID_ARGUMENT;                    // the table stays the context's until agh_localize_batch_end: the setter
                                                         // refuses mid-chain, so the repeats search with it too)
@@ -938,6 +949,7 @@ int batch_end_impl(agh_ctx* ctx, const ChainOutputs& out, agh_localize_batch_res
   c->loc.batch = false;
   c->results = ChainResults{};
   hand_drop_collect(c, 0, nullptr);
+  handle_rank_collect(c, 0, nullptr);
   ActiveGuard guard(c);
   int rc;
   for (int pass = 0;; pass++)
@@ -1102,6 +1114,12 @@ int batch_collect(agh_ctx* ctx, const char* who, const char* unit, const int64_t
     tot_hands += h[5];
   }
   hand_drop_collect(c, C, n_hyp);
+  {
+    int64_t n_kept[kMaxClouds];
+    for (int k = 0; k < C; k++)
+      n_kept[k] = hc[k * kBatchCountsStride + 5];
+    handle_rank_collect(c, C, n_kept);
+  }
   c->last_nout = std::min<int64_t>(n_hyp_tot, c->s_cap * 8);
   if (out.samples && S_tot > 0)
     std::memcpy(out.samples, b->h_samples, sizeof(int32_t) * (size_t) S_tot);

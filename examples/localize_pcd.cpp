@@ -4,7 +4,7 @@
 //   g++ -std=c++11 -O2 -Iinclude examples/localize_pcd.cpp -o localize_pcd -Lagile_grasp_amd/lib -lagile_grasp_hip
 //       -Wl,-rpath,$PWD/agile_grasp_amd/lib -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
 //   ./localize_pcd [--filters-boundaries] [--voxel-filter R,K] [--approach dx,dy,dz,cos] [--aperture lo,hi]
-//                  [--clearance near,far,half_w,half_h[,max_points]]
+//                  [--clearance near,far,half_w,half_h[,max_points]] [--rank w_support,w_margin[,max_handles]]
 //                  [--table a,b,c,d [--cluster-tolerance t]] <svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]
 //
 // Parameters are the node's defaults (find_grasps.cpp:10-21): finger width 0.01, outer diameter 0.09, hand depth 0.06,
@@ -24,6 +24,10 @@
 // --clearance near,far,half_w,half_h[,max_points] drops the hands whose approach corridor -- the box from near to far metres behind
 // the palm, +- half_w along the closing direction, +- half_h along the hand's axis -- holds more than max_points (default 0) points
 // of the cloud: 0,0.12,0.05,0.04 is a gripper body of 10 x 8 cm over 12 cm (Localization::setHandClearance).
+// --rank w_support,w_margin[,max_handles] returns the handles best first: scored on the device by their number of hands (up to
+// ten) and the classifier's mean margin under the two weights, at most max_handles of them (default 0: all), the score printed
+// beside each (Localization::setHandleRanking).  The ranking is a stage of the one-call chain, so with --rank and no --table the
+// cloud goes through localizeHandles, samples drawn on the device, where it otherwise takes the node's three calls.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -50,10 +54,14 @@ int main(int argc, char** argv)
   bool clearance = false;
   agh_hand_clearance_params hand_clearance;
   agh_default_hand_clearance_params(&hand_clearance);
+  bool rank = false;
+  agh_handle_ranking_params ranking;
+  agh_default_handle_ranking_params(&ranking);
   double plane[4] = { 0.0, 0.0, 1.0, 0.0 }, cluster_tolerance = 0.01;
   while (argc > 2 && (std::strcmp(argv[1], "--table") == 0 || std::strcmp(argv[1], "--cluster-tolerance") == 0 ||
                       std::strcmp(argv[1], "--voxel-filter") == 0 || std::strcmp(argv[1], "--approach") == 0 ||
-                      std::strcmp(argv[1], "--aperture") == 0 || std::strcmp(argv[1], "--clearance") == 0))
+                      std::strcmp(argv[1], "--aperture") == 0 || std::strcmp(argv[1], "--clearance") == 0 ||
+                      std::strcmp(argv[1], "--rank") == 0))
   {
     if (std::strcmp(argv[1], "--table") == 0)
       table = std::sscanf(argv[2], "%lf,%lf,%lf,%lf", &plane[0], &plane[1], &plane[2], &plane[3]) == 4;
@@ -67,6 +75,8 @@ int main(int argc, char** argv)
     else if (std::strcmp(argv[1], "--clearance") == 0)
       clearance = std::sscanf(argv[2], "%lf,%lf,%lf,%lf,%d", &hand_clearance.near_offset, &hand_clearance.far_offset,
                     &hand_clearance.half_width, &hand_clearance.half_height, &hand_clearance.max_points) >= 4;
+    else if (std::strcmp(argv[1], "--rank") == 0)
+      rank = std::sscanf(argv[2], "%lf,%lf,%d", &ranking.w_support, &ranking.w_margin, &ranking.max_handles) >= 2;
     else
       cluster_tolerance = std::atof(argv[2]);
     argv[2] = argv[0];
@@ -76,7 +86,8 @@ int main(int argc, char** argv)
   if (argc < 3)
   {
     std::printf("usage: %s [--filters-boundaries] [--voxel-filter R,K] [--approach dx,dy,dz,cos] [--aperture lo,hi] "
-                "[--clearance near,far,half_w,half_h[,max_points]] [--table a,b,c,d [--cluster-tolerance t]] "
+                "[--clearance near,far,half_w,half_h[,max_points]] [--rank w_support,w_margin[,max_handles]] "
+                "[--table a,b,c,d [--cluster-tolerance t]] "
                 "<svm file> <left.pcd> [right.pcd] [num_samples] [min_inliers]\n", argv[0]);
     return 2;
   }
@@ -122,6 +133,8 @@ int main(int argc, char** argv)
   }
   if (clearance && !loc.setHandClearance(hand_clearance))  // (likewise)
     return 1;
+  if (rank && !loc.setHandleRanking(ranking))  // (likewise)
+    return 1;
 
   if (table)
   {
@@ -141,14 +154,52 @@ int main(int argc, char** argv)
     loc.setClusterParams(0.01, 0.5, cluster_tolerance, 50, 16);
     const std::vector<std::vector<Handle> > per_object = loc.localizeHandlesClustered(cloud, size_left, pl, svm, min_inliers, 0.005);
     const std::vector<std::int64_t> sizes = loc.getClusterSizes();
-    for (std::size_t j = 0; j < per_object.size() && j < sizes.size() && sizes[j] > 0; j++)
+    const std::vector<agh_handle_score> scores = loc.handleScores();  // (all objects' handles, object after object; empty unranked)
+    std::size_t first = 0;
+    for (std::size_t j = 0; j < per_object.size(); first += per_object[j].size(), j++)
     {
+      if (j >= sizes.size() || sizes[j] <= 0)
+        continue;
       const Grasps msg = createGraspsMsg(per_object[j]);
       std::printf("object %zu: %lld voxels, %zu handles\n", j, (long long) sizes[j], per_object[j].size());
       for (std::size_t i = 0; i < msg.grasps.size(); i++)
-        std::printf("  grasp %zu: center %.4f %.4f %.4f  axis %.4f %.4f %.4f  width %.4f\n", i, msg.grasps[i].center(0),
+      {
+        std::printf("  grasp %zu: center %.4f %.4f %.4f  axis %.4f %.4f %.4f  width %.4f", i, msg.grasps[i].center(0),
           msg.grasps[i].center(1), msg.grasps[i].center(2), msg.grasps[i].axis(0), msg.grasps[i].axis(1), msg.grasps[i].axis(2),
           (double) msg.grasps[i].width);
+        if (first + i < scores.size())
+          std::printf("  score %.6f (found as handle %d)", scores[first + i].score, (int) scores[first + i].index);
+        std::printf("\n");
+      }
+    }
+    return 0;
+  }
+  if (rank)
+  {
+    // the one-call chain, which ranks: the clouds read as localizeHands(left, right) reads them, the samples drawn on the device
+    PointCloud::Ptr cloud(new PointCloud), cloud_right(new PointCloud);
+    if (loadPCDFile(left, *cloud) == -1 || (right.length() > 0 && loadPCDFile(right, *cloud_right) == -1))
+    {
+      std::printf("could not read the PCD files\n");
+      return 1;
+    }
+    const int size_left = (int) cloud->size();
+    cloud->points.insert(cloud->points.end(), cloud_right->points.begin(), cloud_right->points.end());
+    cloud->is_dense = cloud->is_dense && cloud_right->is_dense;
+    std::vector<GraspHypothesis> antipodal;
+    const std::vector<Handle> handles = loc.localizeHandles(cloud, size_left, std::vector<int>(), svm, min_inliers, 0.005, &antipodal);
+    const std::vector<agh_handle_score> scores = loc.handleScores();
+    const Grasps msg = createGraspsMsg(handles);
+    std::printf("%zu antipodal, %zu handles\n", antipodal.size(), handles.size());
+    for (std::size_t i = 0; i < msg.grasps.size(); i++)
+    {
+      const Grasp& g = msg.grasps[i];
+      std::printf("grasp %zu: center %.4f %.4f %.4f  axis %.4f %.4f %.4f  approach %.4f %.4f %.4f  width %.4f", i,
+        g.center(0), g.center(1), g.center(2), g.axis(0), g.axis(1), g.axis(2), g.approach(0), g.approach(1), g.approach(2),
+        (double) g.width);
+      if (i < scores.size())
+        std::printf("  score %.6f (found as handle %d)", scores[i].score, (int) scores[i].index);
+      std::printf("\n");
     }
     return 0;
   }

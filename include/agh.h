@@ -276,11 +276,13 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_localize(...) is begin + end.  One chain may be in flight (AGH_ERR_STATE for a second begin, or an end without a begin).
  * Between begin and end the chain owns the context's buffers and its cloud: only agh_localize_stage, agh_localize_depth_stage,
  * agh_localize_end,
- * agh_get_cloud_cam_origins, agh_get_depth_filter, agh_get_voxel_filter, agh_get_hand_filter, agh_get_hand_clearance, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
+ * agh_get_cloud_cam_origins, agh_get_depth_filter, agh_get_voxel_filter, agh_get_hand_filter, agh_get_hand_clearance,
+ * agh_get_handle_ranking, agh_synchronize (it waits, and leaves the chain's results to agh_localize_end), agh_last_error,
  * agh_destroy, the host-side counters (agh_get_timing, agh_get_timing_counts, agh_get_grid_stats, agh_get_grid_desc) and the
  * communicator's bookkeeping (agh_comm_rank, agh_comm_init*, agh_comm_destroy, agh_comm_inject_fault,
  * agh_comm_set_segment_records, agh_comm_last_*) may be called on the context.  Every other call on it returns AGH_ERR_STATE
- * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_set_depth_filter, agh_set_voxel_filter, agh_set_hand_filter, agh_set_hand_clearance, agh_preprocess*, agh_find_hands*, agh_classify*,
+ * without touching anything: agh_set_cloud*, agh_set_cloud_cam_origins, agh_set_depth_filter, agh_set_voxel_filter, agh_set_hand_filter, agh_set_hand_clearance,
+ * agh_set_handle_ranking, agh_rank_handles, agh_preprocess*, agh_find_hands*, agh_classify*,
  * agh_find_handles, agh_localize* (agh_localize_depth_batch*, agh_localize_masked*, agh_localize_masked_begin,
  * agh_localize_depth_masked*, agh_localize_depth_masked_begin, agh_localize_labeled*, agh_localize_depth_labeled*,
  * agh_localize_clustered*, agh_localize_depth_clustered*, agh_localize_clustered_fit*, agh_localize_depth_clustered_fit*,
@@ -294,6 +296,7 @@ int agh_localize_device(agh_ctx* ctx, const float* d_xyz, int64_t stride_bytes, 
  * agh_get_cluster_labels, agh_get_plane_fit, agh_get_plane_fit_candidates, agh_get_batch_mask_counts,
  * agh_get_batch_label_counts, agh_get_batch_cluster_info, agh_get_batch_cluster_labels, agh_get_batch_plane_fit,
  * agh_get_batch_plane_fit_candidates, agh_get_depth_filter_counts, agh_get_voxel_filter_counts, agh_get_hand_filter_counts, agh_get_hand_clearance_counts,
+ * agh_get_handle_scores, agh_get_handle_ranking_counts, agh_get_hand_margins,
  * agh_fuse_depth, agh_fuse_depth_device, agh_get_depth_fusion_counts, agh_get_fused_depth and every getter of device results (frames, normals,
  * neighbour counts, images, HOG, learning points, plane results, agh_get_epoch), agh_load_svm*, the training calls
  * (agh_set_training_images, agh_get_training_images, agh_hog_images, agh_train_svm), agh_set_profile and agh_selftest_math.  The
@@ -734,8 +737,9 @@ int agh_localize_batch_device(agh_ctx* ctx, const float* const* xyz, const int64
  * agh_get_batch_cluster_labels, agh_get_batch_plane_fit, agh_get_batch_plane_fit_candidates, agh_set_depth_filter,
  * agh_get_depth_filter_counts, agh_set_voxel_filter, agh_get_voxel_filter_counts, agh_set_hand_filter,
  * agh_get_hand_filter_counts, agh_set_hand_clearance and agh_get_hand_clearance_counts are refused as well, and so are
+ * agh_set_handle_ranking, agh_rank_handles, agh_get_handle_scores, agh_get_handle_ranking_counts, agh_get_hand_margins,
  * agh_fuse_depth, agh_fuse_depth_device, agh_get_depth_fusion_counts and agh_get_fused_depth; agh_get_hand_clearance
- * is host-side and allowed, as agh_get_hand_filter),
+ * and agh_get_handle_ranking are host-side and allowed, as agh_get_hand_filter),
  * agh_localize_batch_end without an agh_localize_batch_begin in flight (agh_localize_end for a batch chain likewise):
  * AGH_ERR_STATE, the chain untouched.  Between agh_localize_batch_begin and _end the calls allowed on the context are those
  * listed at agh_localize_begin, with agh_localize_batch_stage / agh_localize_batch_end (and agh_localize_stage) in place of
@@ -1124,6 +1128,92 @@ void agh_default_hand_clearance_params(agh_hand_clearance_params* p);
 int agh_set_hand_clearance(agh_ctx* ctx, const agh_hand_clearance_params* cp);
 int agh_get_hand_clearance(agh_ctx* ctx, agh_hand_clearance_params* out);
 int agh_get_hand_clearance_counts(agh_ctx* ctx, agh_hand_clearance_counts* out, int32_t cap_lists);
+
+/* HANDLE RANKING: the chains end with the handle list in discovery order, the handle search's seed order (handle_search.cpp:79),
+ * and the classifier's decision value never leaves the device.  A cell executes one grasp per pick, so every caller sorted the
+ * handles itself, without the best criterion to sort by.  agh_set_handle_ranking makes every agh_localize* chain return each
+ * list's handles_out span in RANK ORDER (k_handle_rank, queued behind k_handle_build; the chain's one synchronisation stays one).
+ * The reference publishes its handles unranked: this is a capability on top of it, and with nothing set every result, launch and
+ * allocation is what it was.  All arithmetic is float64, evaluated left to right, never contracted (-ffp-contract=off).
+ *  1. INPUTS.  A handle of a list has inliers in[0..n) into the list's hands (hands_out).  g_k is the MARGIN of hand in[k]: minus
+ *     the decision sum the classifier kernels store (k_hog_svm stores sum = -rho + res and keeps a hand iff sum <= 0; the
+ *     general-model path uses the same convention), so kept hands have g >= 0.  With classify == 0, g = 0.0.
+ *  2. THE WAVE SUM W(v, n), the only sum whose order matters: p[l] = ((v[l] + v[l+64]) + v[l+128]) + ... for l < 64, starting
+ *     from +0.0, absent entries add nothing; then p[l] = p[l] + p[l ^ o] for o = 32, 16, 8, 4, 2, 1 (as k_handle_build sums its
+ *     axis moments); the result is p[0].
+ *  3. THE SEVEN TERMS, in terms[] order, with c = handle.center, a = handle.approach:
+ *       t_support = (double) min(n, support_cap) / (double) support_cap
+ *       t_margin = W(g, n) / (double) n
+ *       t_approach = (a0 d0 + a1 d1) + a2 d2, d = approach_dir
+ *       t_position = (c0 p0 + c1 p1) + c2 p2, p = position_dir
+ *       t_distance = sqrt((e0 e0 + e1 e1) + e2 e2), e = c - ref_point
+ *       t_width = fabs(handle.width - preferred_width)
+ *       t_length = max_k(x_k) - min_k(x_k), x_k = (axis0 b0 + axis1 b1) + axis2 b2 over the inliers' bottom b, by fmax / fmin
+ *         from -inf / +inf (order cannot matter)
+ *  4. THE SCORE.  score = (((((w_support t1 + w_margin t2) + w_approach t3) + w_position t4) + w_distance t5) + w_width t6) +
+ *     w_length t7.  Every term is always computed: a NaN term makes the score NaN even under weight 0.
+ *  5. best_inlier: the first k in inlier order with the largest g_k; a NaN g never wins; 0 if none wins.
+ *  6. ORDER.  With min_score = -inf no handle is left out.  Else a handle is left out iff !(score >= min_score) -- a NaN score is
+ *     therefore left out whenever min_score is finite -- and counted in n_below.  The rest are ordered by score descending, NaN scores after every number, ties (decided by ==, so
+ *     +0 and -0 tie) by ascending index, the handle's position in the unranked list.  The first max_handles are returned
+ *     (0: all).  The order is total: it depends on no sort algorithm and on the order of no atomic.
+ *  7. OUTPUTS.  results[l].r.n_handles is the number returned, and AGH_ERR_CAPACITY for handle_cap is judged on it.
+ *     inlier_idx_out, n_inlier_idx, hands_out and every first_inlier are exactly the unranked call's: only the handle records
+ *     move, so no index needs rewriting.  n_hypotheses and n_hands keep their meaning.
+ *  8. SCOPE.  Sticky per context until cleared (rp == NULL) or replaced; the setter does no device work; an invalid field -- a
+ *     non-finite one other than min_score = -inf, approach_dir off unit length by more than 1e-6, support_cap < 1, max_handles
+ *     < 0 -- returns AGH_ERR_INVALID_ARGUMENT, the text names it, and the setting held before stays.  It applies to every
+ *     agh_localize* chain form -- points and depth, single, batch and _begin / _stage / _end, masked, labelled, clustered and
+ *     fitted -- and to every in-call repeat.  A chain call with w_margin != 0 and classify == 0 returns AGH_ERR_INVALID_ARGUMENT
+ *     and launches nothing.  Set-then-clear is the same as never set.
+ *  9. MID-CHAIN (single or batch) agh_set_handle_ranking and agh_rank_handles return AGH_ERR_STATE; agh_get_handle_ranking (1 and
+ *     a copy, or 0 if none is set) is host-side and allowed mid-chain.  agh_get_handle_scores, agh_get_handle_ranking_counts and
+ *     agh_get_hand_margins return AGH_ERR_STATE while a chain is in flight and when the last chain collected ran without a
+ *     ranking; else the number of records written (scores: laid out as handles_out, all lists; margins: per hand, laid out as
+ *     hands_out; counts: one per list), AGH_ERR_CAPACITY if the room is smaller.  They arrive in pinned memory with the chain's
+ *     one synchronisation.
+ * 10. STAGE-WISE.  agh_rank_handles takes host buffers and runs the same kernel on one list: the same order on agh_find_handles'
+ *     output (margins NULL: zeros).  Refused on the host: rp NULL or an invalid record (AGH_ERR_INVALID_ARGUMENT); n_hands or
+ *     n_handles above 8192 (AGH_ERR_CAPACITY); an n_inliers < 1, a span outside n_idx, an index outside n_hands
+ *     (AGH_ERR_INVALID_ARGUMENT).  counts is filled before AGH_ERR_CAPACITY for cap.
+ *  Not built: ranking in the sharded calls; a per-capture ranking record in a batch; terms that need the cloud, such as clearance
+ *  counts or unobserved probes; reordering of inlier_idx_out.  tests/handle_ranking_cases.py is the numpy model the kernel
+ *  matches bit for bit. */
+typedef struct agh_handle_ranking_params
+{
+  double w_support, w_margin, w_approach, w_position, w_distance, w_width, w_length;
+  double approach_dir[3];   /* unit within 1e-6 */
+  double position_dir[3];   /* any finite vector; (0,0,1) = highest first */
+  double ref_point[3];
+  double preferred_width;
+  double min_score;         /* -inf: none */
+  int32_t support_cap;      /* >= 1 */
+  int32_t max_handles;      /* 0: all; else top-k per list */
+} agh_handle_ranking_params;
+typedef struct agh_handle_score
+{
+  double score;
+  double terms[7];
+  int32_t index;            /* position in the unranked list */
+  int32_t best_inlier;
+} agh_handle_score;         /* 72 bytes, frozen */
+typedef struct agh_handle_ranking_counts
+{
+  int64_t n_found;          /* the handles of the unranked list */
+  int64_t n_below;          /* left out by min_score */
+  int64_t n_returned;
+} agh_handle_ranking_counts;
+/* w_support 1, w_margin 1, other weights 0; approach_dir (0,0,-1); position_dir (0,0,1); ref_point 0; preferred_width 0;
+ * min_score -inf; support_cap 10; max_handles 0 */
+void agh_default_handle_ranking_params(agh_handle_ranking_params* p);
+int agh_set_handle_ranking(agh_ctx* ctx, const agh_handle_ranking_params* rp);
+int agh_get_handle_ranking(agh_ctx* ctx, agh_handle_ranking_params* out);
+int agh_get_handle_scores(agh_ctx* ctx, agh_handle_score* out, int64_t cap);
+int agh_get_handle_ranking_counts(agh_ctx* ctx, agh_handle_ranking_counts* out, int32_t cap_lists);
+int agh_get_hand_margins(agh_ctx* ctx, double* out, int64_t cap);
+int agh_rank_handles(agh_ctx* ctx, const agh_handle_ranking_params* rp, const agh_hypothesis* hands, int64_t n_hands,
+  const double* margins, const agh_handle* handles, int64_t n_handles, const int32_t* inlier_idx, int64_t n_idx,
+  agh_handle* handles_out, agh_handle_score* scores_out, int64_t cap, agh_handle_ranking_counts* counts);
 
 /* The batch chains with every capture's samples drawn UNDER ITS OWN MASK: a cell with several sensor pairs and one detector per
  * sensor hands over, per rig, a capture and an object mask, and wants handles on the masked object of every rig from one call.

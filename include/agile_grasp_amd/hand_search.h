@@ -1414,6 +1414,79 @@ public:
     out.resize(n > 0 ? (std::size_t) n : 0);
     return out;
   }
+  /** Additional: the handle ranking (agh_set_handle_ranking) -- every later localize chain of this search (points or depth
+   *  images, single or batch) returns each list's handles in rank order: score descending (support, classifier margin, approach,
+   *  position, distance, width and length under the record's weights), ties by the order of discovery, the handles below
+   *  min_score left out, at most max_handles per list.  Sticky until clearHandleRanking, also across a context this search
+   *  re-creates.  Refused while a chain is pending.
+   *  @return false (after printing) on error; the setting held before stays in force */
+  bool setHandleRanking(const agh_handle_ranking_params& rp)
+  {
+    if (!ensureContext())
+      return false;
+    if (agh_set_handle_ranking(ctx_, &rp) != AGH_OK)
+    {
+      fail("agh_set_handle_ranking");
+      return false;
+    }
+    handle_ranking_ = rp;
+    handle_ranking_set_ = true;
+    return true;
+  }
+  bool clearHandleRanking()
+  {
+    if (ctx_ && agh_set_handle_ranking(ctx_, nullptr) != AGH_OK)
+    {
+      fail("agh_set_handle_ranking");
+      return false;
+    }
+    handle_ranking_set_ = false;
+    return true;
+  }
+  /** the ranking held (agh_get_handle_ranking); false: none */
+  bool handleRanking(agh_handle_ranking_params& out) const
+  {
+    if (handle_ranking_set_)
+      out = handle_ranking_;
+    return handle_ranking_set_;
+  }
+  /** agh_get_handle_scores: the score record of every handle the last chain collected returned, laid out as its handles (all
+   *  lists, list after list); empty if that chain ran without a ranking, if there was none, or while a chain is pending */
+  std::vector<agh_handle_score> handleScores()
+  {
+    std::vector<agh_handle_score> out(8192);
+    int n = ctx_ ? agh_get_handle_scores(ctx_, out.data(), (std::int64_t) out.size()) : 0;
+    if (n == AGH_ERR_CAPACITY)  // (several full lists)
+    {
+      out.resize((std::size_t) 8192 * 64);
+      n = agh_get_handle_scores(ctx_, out.data(), (std::int64_t) out.size());
+    }
+    out.resize(n > 0 ? (std::size_t) n : 0);
+    return out;
+  }
+  /** agh_get_handle_ranking_counts: per list of the last chain collected how many handles were found, left out by min_score and
+   *  returned; empty as handleScores */
+  std::vector<agh_handle_ranking_counts> handleRankingCounts()
+  {
+    std::vector<agh_handle_ranking_counts> out(64);
+    const int n = ctx_ ? agh_get_handle_ranking_counts(ctx_, out.data(), (std::int32_t) out.size()) : 0;
+    out.resize(n > 0 ? (std::size_t) n : 0);
+    return out;
+  }
+  /** agh_get_hand_margins: the classifier margin (minus its decision sum; 0 without a classifier) of every hand the last chain's
+   *  handle search ran on, laid out as the hands; empty as handleScores */
+  std::vector<double> handMargins()
+  {
+    std::vector<double> out(8192);
+    int n = ctx_ ? agh_get_hand_margins(ctx_, out.data(), (std::int64_t) out.size()) : 0;
+    if (n == AGH_ERR_CAPACITY)
+    {
+      out.resize((std::size_t) 8192 * 64);
+      n = agh_get_hand_margins(ctx_, out.data(), (std::int64_t) out.size());
+    }
+    out.resize(n > 0 ? (std::size_t) n : 0);
+    return out;
+  }
   /** agh_get_depth_filter_counts: per view of the last deprojection, in launch order, what the filter did; empty if that
    *  deprojection ran without a filter, if there was none, or while a chain is pending */
   std::vector<agh_depth_filter_counts> depthFilterCounts()
@@ -1845,6 +1918,11 @@ private:
       fail("agh_set_hand_clearance");
       return false;
     }
+    if (handle_ranking_set_ && agh_set_handle_ranking(ctx_, &handle_ranking_) != AGH_OK)
+    {
+      fail("agh_set_handle_ranking");
+      return false;
+    }
     return true;
   }
 
@@ -1857,6 +1935,8 @@ private:
   bool hand_filter_set_ = false;
   agh_hand_clearance_params hand_clearance_ = agh_hand_clearance_params();  // setHandClearance
   bool hand_clearance_set_ = false;
+  agh_handle_ranking_params handle_ranking_ = agh_handle_ranking_params();  // setHandleRanking
+  bool handle_ranking_set_ = false;
   std::int64_t searched_n_ = 0;
   // What an End reads of the chain in flight.  The rule for every Begin: these (and last_samples_, sized by chainBegun for
   // localizeEnd) are written only after the library's begin has returned AGH_OK, so a Begin that fails for any reason -- a

@@ -750,6 +750,56 @@ public:
     return search_ ? search_->handClearanceCounts() : std::vector<agh_hand_clearance_counts>();
   }
 
+  /** Additional: the handle ranking of every localizeHandles* form (agh_set_handle_ranking; agh_default_handle_ranking_params
+   *  fills a record that scores a handle by its support and its classifier margin).  With one set the chain returns each list's
+   *  handles in rank order -- best first, ties in the order of discovery, the handles below min_score left out, at most
+   *  max_handles per list -- sorted on the device behind the handle search; the inlier lists and the hands are untouched.  A call
+   *  without a classifier (svm_filename empty) is refused while w_margin is not 0.  Sticky until clearHandleRanking, also across
+   *  the setters that re-create the search.  Refused while a chain is pending.
+   *  @return false (after printing) on error; the setting held before stays in force */
+  bool setHandleRanking(const agh_handle_ranking_params& rp)
+  {
+    if (chainPending("setHandleRanking"))
+      return false;
+    ensureSearch();
+    if (!search_->setHandleRanking(rp))
+      return false;
+    handle_ranking_ = rp;
+    handle_ranking_set_ = true;
+    return true;
+  }
+  bool clearHandleRanking()
+  {
+    if (chainPending("clearHandleRanking") || (search_ && !search_->clearHandleRanking()))
+      return false;
+    handle_ranking_set_ = false;
+    return true;
+  }
+  /** the ranking held; false: none */
+  bool handleRanking(agh_handle_ranking_params& out) const
+  {
+    if (handle_ranking_set_)
+      out = handle_ranking_;
+    return handle_ranking_set_;
+  }
+  /** The score records of the handles the last localizeHandles* call returned, in their order (agh_get_handle_scores): score, the
+   *  seven terms, the handle's position in the unranked list and its best inlier; empty if that call ran without a ranking, if
+   *  there was none, or while a chain is pending. */
+  std::vector<agh_handle_score> handleScores()
+  {
+    return search_ ? search_->handleScores() : std::vector<agh_handle_score>();
+  }
+  /** per list of that call: handles found, left out by min_score, returned (agh_get_handle_ranking_counts) */
+  std::vector<agh_handle_ranking_counts> handleRankingCounts()
+  {
+    return search_ ? search_->handleRankingCounts() : std::vector<agh_handle_ranking_counts>();
+  }
+  /** the classifier margins of the hands that call's handle search ran on (agh_get_hand_margins) */
+  std::vector<double> handMargins()
+  {
+    return search_ ? search_->handMargins() : std::vector<double>();
+  }
+
   /** What the filter did in the last depth call (agh_get_depth_filter_counts): one record per image, in capture order; empty if
    *  that call ran without a filter, if there was none, or while a chain is pending. */
   std::vector<agh_depth_filter_counts> depthFilterCounts()
@@ -1585,6 +1635,8 @@ private:
       search_->setHandFilter(hand_filter_);
     if (hand_clearance_set_)
       search_->setHandClearance(hand_clearance_);
+    if (handle_ranking_set_)
+      search_->setHandleRanking(handle_ranking_);
   }
 
   int num_threads_, num_samples_;
@@ -1599,6 +1651,8 @@ private:
   bool hand_filter_set_ = false;
   agh_hand_clearance_params hand_clearance_ = agh_hand_clearance_params();  // setHandClearance
   bool hand_clearance_set_ = false;
+  agh_handle_ranking_params handle_ranking_ = agh_handle_ranking_params();  // setHandleRanking
+  bool handle_ranking_set_ = false;
   int plotting_mode_;
   Matrix4d cam_tf_left_, cam_tf_right_;
   VectorXd workspace_;
